@@ -15,8 +15,12 @@ through ``GpuVecSampler`` followed by one ``PPO._train_once`` (value baselines,
 GAE scan, advantage centring, E epochs x 32 minibatches of policy updates, then
 the same for the value function, diagnostics, old-policy sync) -- all of it in
 the timed region.  Weak scaling: every rank owns ``n_envs`` environments.
-Prints ONE JSON line (rank 0) with ``roofline`` (dominant kernel, HIP-event
-timed), ``roofline_gae_scan`` and ``cpu_baseline``.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps
+and prints the headline; ``--full`` adds what takes runs of its own after the
+timed region: ``roofline`` (dominant kernel, HIP-event timed),
+``roofline_gae_scan``, the split-operand variant and ``cpu_baseline``.
+``--dump-outputs DIR`` writes what the last timed step computed to
+``DIR/<name>.npy`` (seeded inputs: identical from run to run).
 """
 import argparse
 import ctypes as C
@@ -235,7 +239,61 @@ def build_engine(cfg, comm, seed=1, algo_name='ppo'):
 
 def one_iteration(algo, sampler, pol, S, itr):
     eps = sampler.obtain_samples(itr, S, None)
-    algo._train_once(itr, eps)
+    return eps, algo._train_once(itr, eps)
+
+
+DUMP_ROWS = 16384         # sampled steps of the per-step arrays (C5: 27 MB in all)
+DUMP_BYTES = 64 * 2**20
+
+
+def sample_rows(n):
+    """A fixed, seeded choice of at most ``DUMP_ROWS`` of ``n`` rows, in order."""
+    if n <= DUMP_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(0).choice(n, DUMP_ROWS, replace=False))
+
+
+def step_outputs(algo, pol, eps, avg_return, cfg):
+    """What a caller of one iteration receives: the episode batch, the returned
+    average return, the diagnostics, advantages / returns / baselines and the
+    trained parameters (per-step arrays on a seeded sample of the steps)."""
+    idx = torch.from_numpy(sample_rows(eps.n_samples)).to(eps.obs_dev.device)
+    A = cfg['act_dim']
+    tab = algo.last_tabular
+    out = {
+        'lengths': eps.lengths,
+        'observations': eps.obs_dev[idx, :cfg['obs_dim']],
+        'actions': eps.actions_dev[idx, :1 if cfg.get('discrete') else A],
+        'rewards': eps.rewards_dev[idx],
+        'step_types': eps.step_types_dev[idx],
+        'average_return': np.float64(avg_return),
+        'diagnostics': np.array([tab[k] for k in sorted(tab)], np.float64),
+        'policy_params': torch.cat(
+            [t.reshape(-1) for t in pol.state_dict().values()]),
+        'vf_params': torch.cat([t.reshape(-1) for t in
+                                algo._value_function.state_dict().values()]),
+    }
+    if eps.head_dev is not None:
+        out['agent_head'] = eps.head_dev[idx, :A]
+    for key in ('advantages', 'returns', 'values'):
+        out[key] = algo.last_tensors[key][idx]
+    return out
+
+
+def dump_outputs(path, arrays):
+    """``arrays`` (name -> tensor / array) as ``path/<name>.npy``: float64 stays
+    float64, everything else is written as float32."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write {} bytes (limit '
+                         '{})'.format(total, DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def roofline_pass(algo, sampler, pol, S, itr):
@@ -356,7 +414,8 @@ def scan_launches(n, T, steps, sets, warmup=2):
     with ``sets`` x that well above the 256 MiB Infinity Cache every launch's
     inputs come from HBM and its outputs evict to HBM (``sets == 1``: the same
     buffers back to back, i.e. last-level-cache resident below 256 MiB).
-    Returns (GB/s of algorithmic bytes, mean launch us, bytes per launch)."""
+    Returns (GB/s of algorithmic bytes, mean launch us, bytes per launch, the
+    last launch's (A, G))."""
     from garage_amd import _lib
     from garage_amd.engine import gae_scan
     lib = _lib.load()
@@ -385,9 +444,10 @@ def scan_launches(n, T, steps, sets, warmup=2):
     out = (C.c_double * (3 * len(KIND_NAMES)))()
     lib.ga_prof_collect(out, len(KIND_NAMES))
     ms, work, cnt = out[18], out[19], out[20]
+    last = bufs[(steps - 1) % sets][2:]
     del bufs
     return (work / (ms * 1e-3) / 1e9, ms * 1e3 / max(1.0, cnt),
-            work / max(1.0, cnt))
+            work / max(1.0, cnt), last)
 
 
 MALL_BYTES = 256 * 2**20  # Infinity Cache (MI355X_MICROARCH.md)
@@ -405,17 +465,22 @@ def scan_bench(args):
     with the launches rotating through enough distinct buffer sets that inputs
     and outputs really travel to / from HBM; the same launch on buffers that stay
     in the 256 MiB Infinity Cache (what a scan inside a PPO iteration sees for
-    its just-written baselines) is reported beside it as ``llc_resident`` --
-    cache bandwidth, no fraction of the HBM peak attached."""
+    its just-written baselines) is reported beside it as ``llc_resident`` with
+    ``--full`` -- cache bandwidth, no fraction of the HBM peak attached."""
     cfg = SCAN_CONFIGS[args.config]
     n, T = cfg['n_rows'], cfg['T']
     torch.cuda.set_device(0)
     sets = scan_sets_for_hbm(n, T)
     t0 = time.perf_counter()
-    gbs, us, nbytes = scan_launches(n, T, args.steps, sets, args.warmup)
+    gbs, us, nbytes, (adv, ret) = scan_launches(n, T, args.steps, sets,
+                                                args.warmup)
     elapsed = time.perf_counter() - t0
-    gbs_llc, us_llc, _ = scan_launches(n, T, args.steps, 1, args.warmup)
-    print(json.dumps({
+    if args.dump_outputs:
+        idx = torch.from_numpy(sample_rows(n)).to(adv.device)
+        dump_outputs(args.dump_outputs, {'advantages': adv[idx],
+                                         'returns': ret[idx]})
+    del adv, ret
+    line = {
         'metric': 'GAE-scan HBM GB/s', 'value': gbs, 'unit': 'GB/s',
         'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': us * 1e-3, 'higher_is_better': True,
@@ -437,12 +502,15 @@ def scan_bench(args):
                                  'launches (ms_per_step is their mean); the '
                                  'whole leg incl. allocation took {:.2f} s of '
                                  'host time'.format(args.steps, elapsed)},
-        'llc_resident': {'achieved': gbs_llc, 'unit': 'GB/s',
-                         'avg_launch_us': us_llc,
-                         'note': 'same launch, same buffers back to back: '
-                                 'Infinity-Cache bandwidth below 256 MiB, not '
-                                 'HBM'},
-    }))
+    }
+    if args.full:
+        gbs_llc, us_llc, _, _ = scan_launches(n, T, args.steps, 1, args.warmup)
+        line['llc_resident'] = {'achieved': gbs_llc, 'unit': 'GB/s',
+                                'avg_launch_us': us_llc,
+                                'note': 'same launch, same buffers back to back: '
+                                        'Infinity-Cache bandwidth below 256 MiB, '
+                                        'not HBM'}
+    print(json.dumps(line))
 
 
 def main():
@@ -452,12 +520,23 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', default='c3',
                     choices=sorted(CONFIGS) + sorted(SCAN_CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the instrumented '
+                    'roofline iterations, the split-operand variant, the '
+                    'C4-footprint scan and the CPU baseline (scan configs: the '
+                    'cache-resident leg); a plain run prints the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as '
+                    'DIR/<name>.npy (float32 / float64; per-step arrays on a '
+                    'seeded sample of the steps)')
     ap.add_argument('--cpu-envs', type=int, default=1024,
-                    help='envs of the bounded CPU-baseline sample (0: skip)')
-    ap.add_argument('--no-roofline', action='store_true')
+                    help='with --full: envs of the bounded CPU-baseline sample '
+                    '(0: skip)')
+    ap.add_argument('--no-roofline', action='store_true',
+                    help='with --full: skip the instrumented iterations')
     ap.add_argument('--no-scan-c4', action='store_true',
-                    help='skip the C4-footprint scan launches after the timed '
-                    'region (roofline_gae_scan_c4)')
+                    help='with --full: skip the C4-footprint scan launches after '
+                    'the timed region (roofline_gae_scan_c4)')
     ap.add_argument('--fuse-head', action='store_true',
                     help='compute the head layer inside the loss kernel '
                     '(opt-in; measured neutral at C3)')
@@ -487,8 +566,8 @@ def main():
                     help='run the policy and value-function passes one after '
                     'the other on one stream (isolated per-kernel timings)')
     ap.add_argument('--no-split-variant', action='store_true',
-                    help='skip the extra timed steps with the opt-in split-operand '
-                    '(3 x bf16) k-loops that fill value_split_bf16')
+                    help='with --full: skip the extra timed steps with the opt-in '
+                    'split-operand (3 x bf16) k-loops that fill value_split_bf16')
     args = ap.parse_args()
 
     if args.config in SCAN_CONFIGS:
@@ -549,7 +628,8 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_iteration(algo, sampler, pol, S, itr)
+        last = None  # (no step's batch outlives the next step)
+        last = one_iteration(algo, sampler, pol, S, itr)
         itr += 1
     sync()
     elapsed = torch.tensor([time.perf_counter() - t0], dtype=torch.float64,
@@ -557,15 +637,18 @@ def main():
     if comm is not None:
         comm.all_reduce(elapsed, 'max')
     elapsed = float(elapsed.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(algo, pol, *last, cfg))
+    last = None
 
-    # Instrumented iterations after the timed region (every GEMM / scan /
+    # With --full: instrumented iterations after the timed region (every GEMM / scan /
     # streaming launch bracketed by HIP events on its stream).  `rows`: policy and
     # value passes on ONE stream, so a launch's duration is the kernel's own;
     # `rows_ovl`: the timed region's mode when that is the overlapped one (there
     # a duration includes the time the kernel shares the chip with the other
     # chain's kernels).
     rows = rows_ovl = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         algo.overlap_updates = False
         rows = roofline_pass(algo, sampler, pol, S, itr)
         itr += 1
@@ -578,8 +661,9 @@ def main():
     # fp32 accumulation).  The headline `value` above is exact fp32 and stays so.
     split = None
     # (one GPU only: the N > 1 runs are the driver's scaling measurement of the exact path)
-    if (args.config in ('c3', 'c5') and args.algo == 'ppo' and not args.no_split_variant
-            and world == 1 and not os.environ.get('GARAGE_AMD_SPLIT_BF16')):
+    if (args.full and args.config in ('c3', 'c5') and args.algo == 'ppo'
+            and not args.no_split_variant and world == 1
+            and not os.environ.get('GARAGE_AMD_SPLIT_BF16')):
         from garage_amd import _lib
         lib = _lib.load()
         lib.ga_set_split_bf16(1)
@@ -725,7 +809,7 @@ def main():
             # through buffer sets so that every launch streams from / to HBM
             n4, T4 = SCAN_CONFIGS['c4scan']['n_rows'], SCAN_CONFIGS['c4scan']['T']
             sets = scan_sets_for_hbm(n4, T4)
-            gbs4, us4, nb4 = scan_launches(n4, T4, 20, sets)
+            gbs4, us4, nb4, _ = scan_launches(n4, T4, 20, sets)
             line['roofline_gae_scan_c4'] = {
                 'kernel': 'gae_scan_rows_kernel<1>', 'bound': 'hbm',
                 'achieved': gbs4, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
@@ -758,7 +842,7 @@ def main():
                      avg_us=round(r['total_ms'] * 1e3 / max(1, r['launches']), 2))
                 for r in split['rows'] if r['launches'] > 0
             ]
-    if args.cpu_envs > 0 and world == 1 and args.algo == 'ppo':
+    if args.full and args.cpu_envs > 0 and world == 1 and args.algo == 'ppo':
         line['cpu_baseline'] = cpu_baseline(cfg, min(args.cpu_envs,
                                                      cfg['n_envs']))
     print(json.dumps(line))

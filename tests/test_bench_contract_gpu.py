@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_has_the_contract_fields():
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1',
-         '--warmup', '1', '--cpu-envs', '8'],
+         '--warmup', '1', '--cpu-envs', '8', '--full'],
         cwd=ROOT, capture_output=True, text=True, timeout=550)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -47,6 +48,37 @@ def test_bench_line_has_the_contract_fields():
     assert g['bound'] == 'hbm' and g['unit'] == 'GB/s'
     assert line['grad_allreduce'].startswith('none') and \
         line['rccl_ranks'] is None
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without ``--full`` the line carries the headline only; ``--dump-outputs``
+    writes what the last timed step computed, float32 / float64, 64 MB at most."""
+    out_dir = tmp_path / 'out'
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2',
+         '--warmup', '1', '--dump-outputs', str(out_dir)],
+        cwd=ROOT, capture_output=True, text=True, timeout=550)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['steps'] == 2 and line['warmup'] == 1
+    assert line['ms_per_step'] > 0 and line['value'] > 0
+    assert abs(line['value'] - 4096 * 256 / (line['ms_per_step'] * 1e-3)) < \
+        1e-6 * line['value']
+    for key in ('roofline', 'roofline_gae_scan', 'roofline_gae_scan_c4',
+                'value_split_bf16', 'cpu_baseline', 'kernels'):
+        assert key not in line, key
+    arrays = {f[:-4]: np.load(str(out_dir / f)) for f in os.listdir(str(out_dir))}
+    assert {'observations', 'actions', 'rewards', 'step_types', 'lengths',
+            'agent_head', 'advantages', 'returns', 'values', 'average_return',
+            'diagnostics', 'policy_params', 'vf_params'} == set(arrays)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    assert arrays['observations'].shape == (16384, 17)
+    assert arrays['lengths'].sum() == 4096 * 256
+    assert all(np.isfinite(a).all() for a in arrays.values())
 
 
 @pytest.mark.timeout(900)
