@@ -7,9 +7,7 @@
 #include <stdint.h>
 #include <string.h>
 
-void ga_set_error(const char* fmt, ...);
-typedef int (*ga_allreduce_fn)(void* comm, float* buf, int64_t n, void* stream);
-extern "C" void ga_set_allreduce_hook(ga_allreduce_fn fn);
+#include "internal.h"
 
 namespace {
 struct Api {
@@ -83,12 +81,12 @@ extern "C" void* ga_comm_init_rank(const void* id128_host, int rank, int world) 
 }
 
 extern "C" int ga_comm_allreduce_sum_f32(void* comm, float* buf, int64_t n,
-                                         hipStream_t stream) {
+                                         ga_stream_t stream) {
   if (!comm || !buf || n <= 0 || !load_api()) {
     ga_set_error("ga_comm_allreduce_sum_f32: bad arguments");
     return -1;
   }
-  return allreduce_hook(comm, buf, n, (void*)stream);
+  return allreduce_hook(comm, buf, n, stream);
 }
 
 extern "C" int ga_comm_count(void* comm) {

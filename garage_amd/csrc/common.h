@@ -5,11 +5,11 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "internal.h"
+
 #define GA_WAVE 64
 
-// ---- error plumbing (thread-local message, negative return codes) ----------
-extern "C" const char* ga_last_error(void);
-void ga_set_error(const char* fmt, ...);
+// ---- error plumbing (ga_set_error: thread-local message, negative return codes) --
 
 #define GA_OK 0
 #define GA_ERR_ARG (-1)

@@ -2,6 +2,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "internal.h"
+
 static thread_local char g_err[512] = "";
 
 void ga_set_error(const char* fmt, ...) {

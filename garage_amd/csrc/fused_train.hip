@@ -1753,7 +1753,8 @@ __global__ __launch_bounds__(512, 4) void mfma_burn_kernel(int mode, int iters, 
 }
 }  // namespace
 extern "C" int ga_debug_mfma_burn(int mode, int iters, int blocks, float* sink,
-                                  hipStream_t stream) {
+                                  ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   hipLaunchKernelGGL(mfma_burn_kernel, dim3(blocks), dim3(512), 0, stream, mode, iters, sink);
   return 0;
 }

@@ -413,7 +413,8 @@ extern "C" int ga_gae_scan_f32(const float* rewards, const float* values,
                                int64_t ld, int64_t max_len, int mode,
                                int max_episode_length, double discount,
                                double gae_lambda, float v0, float bonus_const,
-                               float* adv, float* ret, hipStream_t stream) {
+                               float* adv, float* ret, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(rewards && values && adv && ret, "ga_gae_scan_f32: null pointer");
   GA_REQUIRE(n_rows >= 0 && T >= 0, "ga_gae_scan_f32: negative size");
   GA_REQUIRE(mode == 0 || mode == 1, "ga_gae_scan_f32: mode must be 0 or 1");

@@ -742,44 +742,9 @@ int launch_gemm_with_head(const GemmParams& p_in, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // C ABI (see include/garage_amd.h)
 // ---------------------------------------------------------------------------
-struct ga_mlp_desc {
-  int32_t n_layers;    // linear layers (hidden + output), 1..8
-  int32_t dims[9];     // dims[0] = input width, dims[l + 1] = output width of layer l
-  int64_t w_off[8];    // offset (floats) of W_l [dims[l+1]][round4(dims[l])] in params
-  int64_t b_off[8];    // offset (floats) of b_l [dims[l+1]]
-  int64_t act_off[8];  // offset (floats) of layer l's output in the activation
-                       // workspace, row stride round4(dims[l + 1]) (hidden layers)
-  int32_t hidden_act;  // 0 tanh, 1 relu, 2 none
-  int32_t output_act;  // 0 none, 1 tanh, 2 relu (forward codes)
-  int32_t layer_norm;  // 1: LayerNorm in front of every hidden linear layer
-  int32_t pad_;
-  int64_t ln_off[8];   // gamma_l [round4(dims[l])] in params, beta_l right behind it
-  int64_t lnx_off[8];  // normalised input of hidden layer l in the activation
-                       // workspace, row stride round4(dims[l])
-  int64_t lns_off[8];  // (mean, rstd) per row of hidden layer l's input, there too
-};
-
-// lnorm.hip
-int ga_ln_forward(const float* X, int64_t ldx, const int32_t* idx, int64_t M, int D,
-                  const float* gamma, const float* beta, float* Y, int64_t ldy,
-                  float* stats, hipStream_t stream);
-int ga_ln_backward(float* dY, int64_t ldd, const float* X, int64_t ldx, const int32_t* idx,
-                   const float* stats, int64_t M, int D, const float* gamma, int want_dx,
-                   int hact, int rows_per_split, int n_splits, float* dgamma, float* dbeta,
-                   int64_t split_stride, hipStream_t stream);
-int ga_ln_jvp(const float* tX, int64_t ldt, const float* X, int64_t ldx, const int32_t* idx,
-              const float* stats, int64_t M, int D, const float* gamma,
-              const float* tgamma, const float* tbeta, float* tY, int64_t ldy,
-              hipStream_t stream);
-
-// The whole-network forward in one launch (policy_fused.hip) for nets whose
-// layers fit its LDS tiles; ga_set_fused_forward(0) forces the per-layer GEMMs.
-extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d);
-extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* params,
-                                        const float* X, int64_t ldx,
-                                        const int32_t* row_idx, int64_t M,
-                                        float* acts, float* out, int64_t ldo,
-                                        hipStream_t stream);
+// The whole-network forward in one launch (ga_mlp_forward_fused_f32,
+// policy_fused.hip) for nets whose layers fit its LDS tiles;
+// ga_set_fused_forward(0) forces the per-layer GEMMs.
 // Off by default: at the C3 minibatch (32768 x 256 x 256) the fused forward
 // measures 86-107 us against 82-87 us for the three per-layer GEMMs -- it keeps
 // one workgroup per CU (140 KB of LDS) and its per-layer epilogues are exposed,
@@ -809,18 +774,6 @@ extern "C" int ga_set_fused_forward(int on) {
   return 0;
 }
 
-// Streaming kernels for the layer products with one dimension <= 32 (skinny.hip).
-// Return 1 when they do not take the shape: the MFMA tile kernel handles it.
-int ga_skinny_forward(const float* X, int64_t ldx, const int32_t* idx, const float* W,
-                      int64_t ldw, bool w_kc, const float* bias, int act,
-                      const float* H, int64_t ldh, float* Y, int64_t ldy, int M, int N,
-                      int K, hipStream_t stream);
-int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const float* Nr,
-                    int64_t ldn, const int32_t* n_idx, int rows, int wide, int NS,
-                    int rows_per_split, int n_splits, float* C, int64_t c_wide_stride,
-                    int64_t c_narrow_stride, int64_t split_stride, float* colsum_wide,
-                    float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
-                    int64_t lddz, hipStream_t stream);
 // 0 off, 1 hidden layers up to 128 wide, 2 also 256-wide ones.  At 256 units the
 // fused launch (64 x 256 tiles, 75 KB of LDS) saves 7.7 us per minibatch with the
 // chip to itself (C3, one stream: 167.0 -> 160.6 ms per iteration) but loses 1 %
@@ -872,7 +825,8 @@ static int check_desc(const ga_mlp_desc* d, const char* who) {
 extern "C" int ga_mlp_forward_f32(const ga_mlp_desc* d, const float* params,
                                   const float* X, int64_t ldx,
                                   const int32_t* row_idx, int64_t M, float* acts,
-                                  float* out, int64_t ldo, hipStream_t stream) {
+                                  float* out, int64_t ldo, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   int rc = check_desc(d, "ga_mlp_forward_f32");
   if (rc) return rc;
   GA_REQUIRE(params && X, "ga_mlp_forward_f32: null pointer");
@@ -1002,15 +956,6 @@ extern "C" int64_t ga_mlp_backward_splits(const ga_mlp_desc* d, int64_t M) {
   return s;
 }
 
-extern "C" int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params,
-                                         const float* X, int64_t ldx,
-                                         const int32_t* row_idx, int64_t M,
-                                         const float* acts, const float* dout,
-                                         int64_t ldo, float* dacts, float* grad_slabs,
-                                         int64_t slab_stride, int64_t n_splits,
-                                         int l_start, int fused_first,
-                                         hipStream_t stream);
-
 // dW = dz^T in (+ db = column sums of dz) of the MIDDLE layer of two 3-layer networks,
 // both out_w x in_w with 33 .. wide sides (the 128 x 128-tile kernel), split-K over the
 // M rows into n_splits slabs each: the launch ga_mlp_backward_range_f32 makes for
@@ -1071,7 +1016,8 @@ extern "C" int ga_mlp_backward_f32(const ga_mlp_desc* d, const float* params,
                                    const float* acts, const float* dout,
                                    int64_t ldo, float* dacts, float* grad_slabs,
                                    int64_t slab_stride, int64_t n_splits,
-                                   hipStream_t stream) {
+                                   ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(d != nullptr, "ga_mlp_backward_f32: null descriptor");
   return ga_mlp_backward_range_f32(d, params, X, ldx, row_idx, M, acts, dout, ldo, dacts,
                                    grad_slabs, slab_stride, n_splits, d->n_layers - 1, 0,
@@ -1234,7 +1180,8 @@ extern "C" int ga_mlp_jvp_f32(const ga_mlp_desc* d, const float* params,
                               const float* tangent, const float* X, int64_t ldx,
                               const int32_t* row_idx, int64_t M, const float* acts,
                               float* tacts, float* tout, int64_t ldo,
-                              hipStream_t stream) {
+                              ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   int rc = check_desc(d, "ga_mlp_jvp_f32");
   if (rc) return rc;
   GA_REQUIRE(params && tangent && X && tout, "ga_mlp_jvp_f32: null pointer");
@@ -1319,7 +1266,8 @@ __global__ __launch_bounds__(256) void act_slope_mul_kernel(float* dout, int64_t
 
 extern "C" int ga_act_slope_mul_f32(float* dout, int64_t ldd, const float* out,
                                     int64_t ldo, int64_t M, int N, int act,
-                                    hipStream_t stream) {
+                                    ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(dout && out && M >= 0 && N >= 1 && ldd >= N && ldo >= N && act >= 0 &&
                  act <= 6,
              "ga_act_slope_mul_f32: bad arguments");
@@ -1333,7 +1281,8 @@ extern "C" int ga_act_slope_mul_f32(float* dout, int64_t ldd, const float* out,
 // Plain GEMM entry used by tests: C[M,N] = A[M,K] * B[N,K]^T (both k-contiguous).
 extern "C" int ga_gemm_nt_f32(const float* A, int64_t lda, const float* B,
                               int64_t ldb, float* C, int64_t ldc, int64_t M,
-                              int64_t N, int64_t K, hipStream_t stream) {
+                              int64_t N, int64_t K, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(A && B && C, "ga_gemm_nt_f32: null pointer");
   GA_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && ga_aligned16(A) && ga_aligned16(B),
              "ga_gemm_nt_f32: operands must be 16-B aligned with ld %% 4 == 0");

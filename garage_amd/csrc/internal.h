@@ -1,0 +1,55 @@
+// Entry points that one source file of the library defines and another calls, and
+// the public header every source file compiles against.  Not part of the C ABI:
+// the library is built with -fvisibility=hidden and exports include/garage_amd.h
+// only.  Host C++ (no device code), so that the CPU harness under tests/host can
+// build update.cpp and rollout_loop.cpp against it too.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/garage_amd.h"
+
+// errors.cpp: sets the thread-local message ga_last_error() returns
+void ga_set_error(const char* fmt, ...);
+
+// lnorm.hip: LayerNorm of the hidden-layer inputs (forward, backward, tangent)
+int ga_ln_forward(const float* X, int64_t ldx, const int32_t* idx, int64_t M, int D,
+                  const float* gamma, const float* beta, float* Y, int64_t ldy,
+                  float* stats, hipStream_t stream);
+int ga_ln_backward(float* dY, int64_t ldd, const float* X, int64_t ldx, const int32_t* idx,
+                   const float* stats, int64_t M, int D, const float* gamma, int want_dx,
+                   int hact, int rows_per_split, int n_splits, float* dgamma, float* dbeta,
+                   int64_t split_stride, hipStream_t stream);
+int ga_ln_jvp(const float* tX, int64_t ldt, const float* X, int64_t ldx, const int32_t* idx,
+              const float* stats, int64_t M, int D, const float* gamma,
+              const float* tgamma, const float* tbeta, float* tY, int64_t ldy,
+              hipStream_t stream);
+
+// skinny.hip: streaming kernels for the layer products with one dimension <= 32.
+// Return 1 when they do not take the shape: the MFMA tile kernel handles it.
+int ga_skinny_forward(const float* X, int64_t ldx, const int32_t* idx, const float* W,
+                      int64_t ldw, bool w_kc, const float* bias, int act,
+                      const float* H, int64_t ldh, float* Y, int64_t ldy, int M, int N,
+                      int K, hipStream_t stream);
+int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const float* Nr,
+                    int64_t ldn, const int32_t* n_idx, int rows, int wide, int NS,
+                    int rows_per_split, int n_splits, float* C, int64_t c_wide_stride,
+                    int64_t c_narrow_stride, int64_t split_stride, float* colsum_wide,
+                    float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
+                    int64_t lddz, hipStream_t stream);
+
+extern "C" {
+// gemm.hip: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
+// of layer l_start in dacts (l_start = n_layers - 1 with `dout`: the whole pass, what
+// ga_mlp_backward_f32 does); fused_first: the data gradient into layer 0's output and
+// layer 0's weight gradient are computed elsewhere (ga_fused_dgrad_wgrad0)
+int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params, const float* X,
+                              int64_t ldx, const int32_t* row_idx, int64_t M,
+                              const float* acts, const float* dout, int64_t ldo,
+                              float* dacts, float* grad_slabs, int64_t slab_stride,
+                              int64_t n_splits, int l_start, int fused_first,
+                              hipStream_t stream);
+// losses.hip: doubles of per-block partial sums at the front of the reduction
+// workspace (ga_reduction_workspace_doubles)
+int64_t ga_reduction_partials_doubles(void);
+}

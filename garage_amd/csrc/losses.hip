@@ -867,7 +867,8 @@ extern "C" int ga_ppo_gaussian_loss_f32(
     int has_min, float min_log_std, int has_max, float max_log_std, int64_t M, int A,
     int algo, float clip, float ent_coeff, int ent_flags, float* dmean,
     float* ll_out, float* loss_out, float* grad_slab0, int64_t slab_stride,
-    int64_t n_splits, double* workspace, hipStream_t stream) {
+    int64_t n_splits, double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(mean && actions && adv && log_std && loss_out && workspace,
              "ga_ppo_gaussian_loss_f32: null pointer");
   GA_REQUIRE(algo == 1 || old_ll, "ga_ppo_gaussian_loss_f32: PPO needs old_ll");
@@ -907,7 +908,8 @@ extern "C" int ga_ppo_categorical_loss_f32(
     int double_softmax, int algo, float clip, float ent_coeff, int ent_flags,
     float* dscores, float* ll_out, float* ent_out, float* loss_out,
     double* ent_sum_out, float* grad_slab0, int64_t slab_stride, int64_t n_splits,
-    double* workspace, hipStream_t stream) {
+    double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(scores && actions && adv && loss_out && workspace,
              "ga_ppo_categorical_loss_f32: null pointer");
   GA_REQUIRE(algo == 1 || old_ll, "ga_ppo_categorical_loss_f32: PPO needs old_ll");
@@ -940,7 +942,8 @@ extern "C" int ga_ppo_categorical_loss_f32(
 extern "C" int ga_categorical_kl_f32(const float* scores_old, const float* scores_new,
                                      int64_t ld, int64_t M, int A, int double_softmax,
                                      double* kl_sum_out, double* workspace,
-                                     hipStream_t stream) {
+                                     ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(scores_old && scores_new && kl_sum_out && workspace,
              "ga_categorical_kl_f32: null pointer");
   GA_REQUIRE(M > 0 && A > 0 && ld >= A, "ga_categorical_kl_f32: bad sizes");
@@ -959,7 +962,8 @@ extern "C" int ga_gaussian_nll_loss_f32(const float* v, int64_t ldv,
                                         const float* log_std, int64_t M, float* dv,
                                         float* loss_out, float* grad_slab0,
                                         int64_t slab_stride, int64_t n_splits,
-                                        double* workspace, hipStream_t stream) {
+                                        double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(v && returns && log_std && loss_out && workspace,
              "ga_gaussian_nll_loss_f32: null pointer");
   GA_REQUIRE(M > 0 && ldv >= 1, "ga_gaussian_nll_loss_f32: bad sizes");
@@ -984,7 +988,8 @@ extern "C" int ga_gaussian_nll_loss_f32(const float* v, int64_t ldv,
 extern "C" int ga_gaussian_kl_f32(const float* mean_old, const float* mean_new,
                                   int64_t ld, int64_t M, int A, float log_std_old,
                                   float log_std_new, double* kl_sum_out,
-                                  double* workspace, hipStream_t stream) {
+                                  double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(mean_old && mean_new && kl_sum_out && workspace,
              "ga_gaussian_kl_f32: null pointer");
   GA_REQUIRE(M > 0 && A > 0 && ld >= A, "ga_gaussian_kl_f32: bad sizes");
@@ -1000,7 +1005,8 @@ extern "C" int ga_gaussian_kl_f32(const float* mean_old, const float* mean_new,
 
 extern "C" int ga_reduce_slabs_f32(const float* slabs, int64_t n_splits,
                                    int64_t slab_stride, int64_t n, float scale,
-                                   float* out, hipStream_t stream) {
+                                   float* out, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(slabs && out, "ga_reduce_slabs_f32: null pointer");
   GA_REQUIRE(n > 0 && n % 4 == 0 && slab_stride % 4 == 0 && n_splits >= 1,
              "ga_reduce_slabs_f32: n and stride must be multiples of 4");
@@ -1017,7 +1023,8 @@ extern "C" int ga_reduce_adam_f32(const float* slabs, int64_t n_splits,
                                   int64_t slab_stride, float* params, float* grads,
                                   float* exp_avg, float* exp_avg_sq, int64_t n,
                                   int64_t step, double lr, double beta1, double beta2,
-                                  double eps, int zero_slot0, hipStream_t stream) {
+                                  double eps, int zero_slot0, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(slabs && params && grads && exp_avg && exp_avg_sq,
              "ga_reduce_adam_f32: null pointer");
   GA_REQUIRE(n > 0 && n % 4 == 0 && slab_stride % 4 == 0 && n_splits >= 1 && step >= 1,
@@ -1045,7 +1052,8 @@ extern "C" int ga_reduce_adam_f32(const float* slabs, int64_t n_splits,
 extern "C" int ga_adam_step_f32(float* params, const float* grads, float* exp_avg,
                                 float* exp_avg_sq, int64_t n, int64_t step, double lr,
                                 double beta1, double beta2, double eps,
-                                hipStream_t stream) {
+                                ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(params && grads && exp_avg && exp_avg_sq, "ga_adam_step_f32: null pointer");
   GA_REQUIRE(n > 0 && step >= 1, "ga_adam_step_f32: bad n / step");
   AdamParams a;
@@ -1067,7 +1075,8 @@ extern "C" int ga_adam_step_f32(float* params, const float* grads, float* exp_av
 extern "C" int ga_optimizer_step_f32(int kind, float* params, const float* grads,
                                      float* s1, float* s2, float* s3, int64_t n,
                                      int64_t step, const double* h, int flags,
-                                     hipStream_t stream) {
+                                     ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(params && grads && h, "ga_optimizer_step_f32: null pointer");
   GA_REQUIRE(n > 0 && step >= 1 && kind >= 1 && kind <= 3,
              "ga_optimizer_step_f32: bad n / step / kind");
@@ -1097,7 +1106,8 @@ extern "C" int ga_optimizer_step_f32(int kind, float* params, const float* grads
 }
 
 extern "C" int ga_stats_f32(const float* x, int64_t n, int what, double* stats,
-                            double* workspace, hipStream_t stream) {
+                            double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(x && stats && workspace, "ga_stats_f32: null pointer");
   GA_REQUIRE(n > 0 && what >= 0 && what <= 2, "ga_stats_f32: bad arguments");
   const int nb = red_blocks(n);
@@ -1122,7 +1132,8 @@ extern "C" int ga_stats_f32(const float* x, int64_t n, int what, double* stats,
 }
 
 extern "C" int ga_adv_center_f32(float* x, int64_t n, const double* stats, float eps,
-                                 hipStream_t stream) {
+                                 ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(x && stats && n > 0, "ga_adv_center_f32: bad arguments");
   hipLaunchKernelGGL(adv_center_kernel, dim3(red_blocks(n)), dim3(256), 0, stream, x,
                      n, stats, eps);
@@ -1131,7 +1142,8 @@ extern "C" int ga_adv_center_f32(float* x, int64_t n, const double* stats, float
 }
 
 extern "C" int ga_sub_scalar_f32(float* x, int64_t n, const double* scalar,
-                                 hipStream_t stream) {
+                                 ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(x && scalar && n > 0, "ga_sub_scalar_f32: bad arguments");
   hipLaunchKernelGGL(sub_scalar_kernel, dim3(red_blocks(n)), dim3(256), 0, stream, x,
                      n, scalar);
@@ -1239,7 +1251,8 @@ __global__ __launch_bounds__(256) void fisher_seed_categorical_kernel(
 }  // namespace
 
 extern "C" int ga_dot_f32(const float* a, const float* b, int64_t n, double* out,
-                          hipStream_t stream) {
+                          ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && b && out && n > 0, "ga_dot_f32: bad arguments");
   hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(1024), 0, stream, a, b, n, out);
   GA_CHECK_LAUNCH("dot");
@@ -1247,7 +1260,8 @@ extern "C" int ga_dot_f32(const float* a, const float* b, int64_t n, double* out
 }
 
 extern "C" int ga_axpby_f32(double alpha, const float* x, double beta, float* y,
-                            int64_t n, hipStream_t stream) {
+                            int64_t n, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(x && y && n > 0, "ga_axpby_f32: bad arguments");
   hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0,
                      stream, (float)alpha, x, (float)beta, y, n);
@@ -1259,7 +1273,8 @@ extern "C" int ga_fisher_seed_gaussian_f32(const float* tmean, int64_t ldt, int6
                                            int A, const float* log_std, int has_min,
                                            float min_log_std, int has_max,
                                            float max_log_std, float* dout, int64_t ldd,
-                                           hipStream_t stream) {
+                                           ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(tmean && log_std && dout && M > 0 && A > 0 && ldt >= A && ldd >= A,
              "ga_fisher_seed_gaussian_f32: bad arguments");
   hipLaunchKernelGGL(fisher_seed_kernel, dim3((unsigned)ga_ceil_div(M, 256)), dim3(256),
@@ -1273,7 +1288,8 @@ extern "C" int ga_fisher_seed_categorical_f32(const float* scores, int64_t lds,
                                               const float* tscores, int64_t ldt,
                                               int64_t M, int A, int double_softmax,
                                               float* dout, int64_t ldd,
-                                              hipStream_t stream) {
+                                              ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(scores && tscores && dout && M > 0 && A > 0 && A <= FS_MAX_A && lds >= A &&
                  ldt >= A && ldd >= A,
              "ga_fisher_seed_categorical_f32: bad arguments");
@@ -1547,7 +1563,8 @@ extern "C" int ga_head_ppo_gaussian_loss_f32(
     int has_min, float min_log_std, int has_max, float max_log_std, int64_t M, int A,
     int algo, float clip, float ent_coeff, int ent_flags, float* dmean, int64_t ldd,
     float* ll_out, float* loss_out, float* grad_slab0, int64_t slab_stride,
-    int64_t n_splits, double* workspace, hipStream_t stream) {
+    int64_t n_splits, double* workspace, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(H && W && bias && actions && adv && log_std && loss_out && workspace,
              "ga_head_ppo_gaussian_loss_f32: null pointer");
   GA_REQUIRE(ga_head_loss_supported(hidden_width, A),
@@ -1597,7 +1614,8 @@ extern "C" int ga_head_gaussian_nll_loss_f32(
     float* v_out, int64_t ldv_out, const float* returns, const int32_t* idx,
     const float* log_std, int64_t M, float* dv, int64_t ldd, float* loss_out,
     float* grad_slab0, int64_t slab_stride, int64_t n_splits, double* workspace,
-    hipStream_t stream) {
+    ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(H && W && bias && returns && log_std && loss_out && workspace,
              "ga_head_gaussian_nll_loss_f32: null pointer");
   GA_REQUIRE(ga_head_loss_supported(hidden_width, 1),

@@ -717,34 +717,8 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
 
 }  // namespace
 
-struct ga_mlp_desc_c {
-  int32_t n_layers;
-  int32_t dims[9];
-  int64_t w_off[8];
-  int64_t b_off[8];
-  int64_t act_off[8];
-  int32_t hidden_act;  // 0 tanh, 1 relu, 2 none: these kernels implement tanh
-  int32_t output_act;  // 0 none, 1 tanh, 2 relu: ... and a linear output layer
-  int32_t layer_norm;  // ... and no layer normalisation
-  int32_t pad_;
-  int64_t ln_off[8], lnx_off[8], lns_off[8];
-};
-
-struct ga_head_args_c {
-  int64_t n, env_id0;
-  int32_t A, kind;
-  const float* head; int64_t ldh;
-  const float* log_std; int32_t has_min, has_max; float min_log_std, max_log_std;
-  const float* noise; int64_t ldn;
-  uint64_t seed; uint32_t step; int32_t double_softmax;
-  const float* obs; int64_t ldo; int32_t obs_dim;
-  int64_t col, Tcap;
-  float* action; int64_t lda;
-  float* obs_buf; float* act_buf; float* head_buf;
-};
-
 // 1 when ga_policy_step_fused_f32 supports this network shape.
-extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc_c* d) {
+extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
   if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
   // tanh hidden layers, a linear output layer, no layer normalisation
   if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return 0;
@@ -756,8 +730,8 @@ extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc_c* d) {
 
 // `head` of args is ignored (the means / scores stay on chip); everything else
 // as in ga_policy_head_sample.
-static int policy_step_launch(const ga_mlp_desc_c* d, const float* params,
-                              const ga_head_args_c* a, const ga_rollout::EnvStepArgs* es,
+static int policy_step_launch(const ga_mlp_desc* d, const float* params,
+                              const ga_head_args* a, const ga_rollout::EnvStepArgs* es,
                               int64_t n_steps, hipStream_t stream);
 
 static bool g_ps_no_resident = getenv("GARAGE_AMD_ROLLOUT_RESIDENT") &&
@@ -778,8 +752,9 @@ extern "C" int ga_policy_step_debug(long long* host_out32) {
                  hipSuccess ? 0 : -1;
 }
 
-extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc_c* d, const float* params,
-                                        const ga_head_args_c* a, hipStream_t stream) {
+extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* params,
+                                        const ga_head_args* a, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   return policy_step_launch(d, params, a, nullptr, 1, stream);
 }
 
@@ -789,12 +764,13 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc_c* d, const float* par
 // envs through all of them (nothing couples envs within a rollout), alternating
 // between `a->obs` and `rec->next_obs` (and the raw pair of `norm`).  `a->action` is
 // what the env is stepped with.
-extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc_c* d, const float* params,
-                                            const ga_head_args_c* a,
+extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
+                                            const ga_head_args* a,
                                             const ga_synth_env* env,
                                             const ga_record_args* rec,
                                             const ga_norm_args* norm, int64_t n_steps,
-                                            hipStream_t stream) {
+                                            ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && rec, "ga_policy_env_step_fused_f32: null pointer");
   GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
              "ga_policy_env_step_fused_f32: steps exceed the rollout buffer");
@@ -810,8 +786,8 @@ extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc_c* d, const float*
   return policy_step_launch(d, params, a, &es, n_steps, stream);
 }
 
-static int policy_step_launch(const ga_mlp_desc_c* d, const float* params,
-                              const ga_head_args_c* a, const ga_rollout::EnvStepArgs* es,
+static int policy_step_launch(const ga_mlp_desc* d, const float* params,
+                              const ga_head_args* a, const ga_rollout::EnvStepArgs* es,
                               int64_t n_steps, hipStream_t stream) {
   GA_REQUIRE(d && params && a, "ga_policy_step_fused_f32: null pointer");
   GA_REQUIRE(ga_policy_step_fused_supported(d),
@@ -855,11 +831,12 @@ static int policy_step_launch(const ga_mlp_desc_c* d, const float* params,
 
 // Training / evaluation forward of the whole MLP in one launch (same contract
 // as ga_mlp_forward_f32, which dispatches here when the shape is supported).
-extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc_c* d, const float* params,
+extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* params,
                                         const float* X, int64_t ldx,
                                         const int32_t* row_idx, int64_t M,
                                         float* acts, float* out, int64_t ldo,
-                                        hipStream_t stream) {
+                                        ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(d && params && X && out, "ga_mlp_forward_fused_f32: null pointer");
   GA_REQUIRE(ga_policy_step_fused_supported(d),
              "ga_mlp_forward_fused_f32: unsupported network shape");

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <vector>
 
+#include "internal.h"
 #include "prof.h"
 
 namespace {

@@ -311,16 +311,6 @@ __global__ __launch_bounds__(256) void feistel_perm_kernel(int64_t n, int half_b
 // ---------------------------------------------------------------------------
 // C ABI (see include/garage_amd.h)
 // ---------------------------------------------------------------------------
-struct ga_synth_env {
-  int64_t n;
-  int64_t env_id0;
-  int32_t obs_dim, act_dim, discrete, min_len, max_len;
-  uint64_t seed;
-  int32_t* episode;
-  int32_t* t;
-  int32_t* len;
-};
-
 static SynthEnv to_dev(const ga_synth_env* e) {
   SynthEnv d;
   d.n = e->n; d.env_id0 = e->env_id0; d.obs_dim = e->obs_dim; d.act_dim = e->act_dim;
@@ -339,7 +329,8 @@ static int check_env(const ga_synth_env* e, const char* who) {
 }
 
 extern "C" int ga_synth_env_reset(const ga_synth_env* env, const uint8_t* mask,
-                                  float* obs, int64_t ldo, hipStream_t stream) {
+                                  float* obs, int64_t ldo, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   int rc = check_env(env, "ga_synth_env_reset");
   if (rc) return rc;
   GA_REQUIRE(obs && ldo >= env->obs_dim, "ga_synth_env_reset: bad obs buffer");
@@ -352,7 +343,8 @@ extern "C" int ga_synth_env_reset(const ga_synth_env* env, const uint8_t* mask,
 extern "C" int ga_synth_env_step(const ga_synth_env* env, const float* actions,
                                  int64_t lda, const float* obs, float* next_obs,
                                  int64_t ldo, float* reward, uint8_t* step_type,
-                                 hipStream_t stream) {
+                                 ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   int rc = check_env(env, "ga_synth_env_step");
   if (rc) return rc;
   GA_REQUIRE(actions && obs && next_obs && reward && step_type,
@@ -366,20 +358,8 @@ extern "C" int ga_synth_env_step(const ga_synth_env* env, const float* actions,
   return GA_OK;
 }
 
-struct ga_head_args {
-  int64_t n, env_id0;
-  int32_t A, kind;  // kind 0 gaussian, 1 categorical
-  const float* head; int64_t ldh;
-  const float* log_std; int32_t has_min, has_max; float min_log_std, max_log_std;
-  const float* noise; int64_t ldn;
-  uint64_t seed; uint32_t step; int32_t double_softmax;
-  const float* obs; int64_t ldo; int32_t obs_dim;
-  int64_t col, Tcap;
-  float* action; int64_t lda;
-  float* obs_buf; float* act_buf; float* head_buf;
-};
-
-extern "C" int ga_policy_head_sample(const ga_head_args* a, hipStream_t stream) {
+extern "C" int ga_policy_head_sample(const ga_head_args* a, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && a->head && a->obs && a->action && a->obs_buf && a->act_buf,
              "ga_policy_head_sample: null pointer");
   GA_REQUIRE(a->n > 0 && a->A > 0 && a->ldh >= a->A && a->ldo >= a->obs_dim,
@@ -407,17 +387,8 @@ extern "C" int ga_policy_head_sample(const ga_head_args* a, hipStream_t stream) 
   return GA_OK;
 }
 
-struct ga_record_args {
-  int64_t n, col, Tcap;
-  int32_t max_episode_length;
-  const float* reward; const uint8_t* step_type; const float* next_obs;
-  int64_t ldo; int32_t obs_dim;
-  int32_t* ep_t; float* rew_buf; uint8_t* st_buf; uint16_t* tail_buf;
-  float* lastobs_buf; uint8_t* done; int32_t* step_eps; int32_t* step_samples;
-  int32_t terminal_only;
-};
-
-extern "C" int ga_record_step(const ga_record_args* a, hipStream_t stream) {
+extern "C" int ga_record_step(const ga_record_args* a, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
                  a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
                  a->step_eps && a->step_samples,
@@ -440,14 +411,6 @@ extern "C" int ga_record_step(const ga_record_args* a, hipStream_t stream) {
   GA_CHECK_LAUNCH("record_step");
   return GA_OK;
 }
-
-struct ga_norm_args {
-  int32_t normalize_obs, normalize_reward;
-  double* obs_mean; double* obs_var; double obs_alpha;
-  double* reward_mean; double* reward_var; double reward_alpha, reward_scale;
-  const float* raw_obs;  // the wrapped env's own current observations
-  float* raw_next_obs;   // ... and where its next observations go
-};
 
 // Validation + conversion of the C-ABI arguments of one env step (also used by the
 // fused policy + env step of policy_fused.hip)
@@ -509,7 +472,8 @@ extern "C" int ga_synth_env_step_record_norm(const ga_synth_env* env,
                                              const ga_record_args* a,
                                              const ga_norm_args* norm,
                                              const float* actions, int64_t lda,
-                                             const float* obs, hipStream_t stream) {
+                                             const float* obs, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   EnvStepArgs args;
   int rc = ga_build_env_step(env, a, norm, actions, lda, obs, "ga_synth_env_step_record",
                              &args);
@@ -523,14 +487,15 @@ extern "C" int ga_synth_env_step_record_norm(const ga_synth_env* env,
 extern "C" int ga_synth_env_step_record(const ga_synth_env* env,
                                         const ga_record_args* a, const float* actions,
                                         int64_t lda, const float* obs,
-                                        hipStream_t stream) {
+                                        ga_stream_t stream) {
   return ga_synth_env_step_record_norm(env, a, nullptr, actions, lda, obs, stream);
 }
 
 extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,
                                 int64_t n_steps, const int32_t* ep_base,
                                 int32_t* ep_env, int32_t* ep_end, int32_t* ep_len,
-                                hipStream_t stream) {
+                                ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(tail_buf && ep_base && ep_env && ep_end && ep_len,
              "ga_pack_episodes: null pointer");
   GA_REQUIRE(n > 0 && n_steps > 0 && n_steps <= Tcap, "ga_pack_episodes: bad sizes");
@@ -543,7 +508,8 @@ extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tca
 extern "C" int ga_pack_src_index(const int32_t* ep_env, const int32_t* ep_end,
                                  const int32_t* ep_len, const int64_t* ep_off,
                                  int64_t n_eps, int64_t Tcap, int32_t* src,
-                                 hipStream_t stream) {
+                                 ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(ep_env && ep_end && ep_len && ep_off && src,
              "ga_pack_src_index: null pointer");
   GA_REQUIRE(n_eps > 0 && n_eps < (1ll << 31), "ga_pack_src_index: bad n_eps");
@@ -555,7 +521,8 @@ extern "C" int ga_pack_src_index(const int32_t* ep_env, const int32_t* ep_end,
 
 extern "C" int ga_gather_rows_f32(const float* src, int64_t ld_src,
                                   const int32_t* idx, int64_t rows, int64_t width,
-                                  float* dst, int64_t ld_dst, hipStream_t stream) {
+                                  float* dst, int64_t ld_dst, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(src && idx && dst, "ga_gather_rows_f32: null pointer");
   GA_REQUIRE(rows > 0 && width > 0 && width % 4 == 0 && ld_src % 4 == 0 &&
                  ld_dst % 4 == 0 && ld_src >= width && ld_dst >= width,
@@ -571,7 +538,8 @@ extern "C" int ga_gather_rows_f32(const float* src, int64_t ld_src,
 }
 
 extern "C" int ga_gather_f32(const float* src, const int32_t* idx, int64_t n,
-                             float* dst, hipStream_t stream) {
+                             float* dst, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(src && idx && dst && n > 0, "ga_gather_f32: bad arguments");
   hipLaunchKernelGGL(gather_scalar_kernel<float>,
                      dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0, stream, src,
@@ -581,7 +549,8 @@ extern "C" int ga_gather_f32(const float* src, const int32_t* idx, int64_t n,
 }
 
 extern "C" int ga_gather_u8(const uint8_t* src, const int32_t* idx, int64_t n,
-                            uint8_t* dst, hipStream_t stream) {
+                            uint8_t* dst, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(src && idx && dst && n > 0, "ga_gather_u8: bad arguments");
   hipLaunchKernelGGL(gather_scalar_kernel<uint8_t>,
                      dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0, stream, src,
@@ -591,7 +560,8 @@ extern "C" int ga_gather_u8(const uint8_t* src, const int32_t* idx, int64_t n,
 }
 
 extern "C" int ga_episode_sums_f32(const float* rewards, const int64_t* ep_off,
-                                   int64_t n_eps, double* sums, hipStream_t stream) {
+                                   int64_t n_eps, double* sums, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(rewards && ep_off && sums && n_eps > 0, "ga_episode_sums_f32: bad args");
   hipLaunchKernelGGL(episode_sums_kernel, dim3((unsigned)ga_ceil_div(n_eps, 256)),
                      dim3(256), 0, stream, rewards, ep_off, n_eps, sums);
@@ -600,7 +570,8 @@ extern "C" int ga_episode_sums_f32(const float* rewards, const int64_t* ep_off,
 }
 
 extern "C" int ga_permutation_i32(int64_t n, uint64_t key, int32_t* out,
-                                  hipStream_t stream) {
+                                  ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(out && n > 0 && n < (1ll << 30), "ga_permutation_i32: bad arguments");
   int half_bits = 1;
   while ((1ll << (2 * half_bits)) < n) ++half_bits;
@@ -614,7 +585,8 @@ extern "C" int ga_permutation_i32(int64_t n, uint64_t key, int32_t* out,
 extern "C" int ga_obs_normalize_from_f64(int64_t n, int obs_dim, const float* src,
                                          float* dst, int64_t ldo, double* mean,
                                          double* var, double alpha,
-                                         const uint8_t* mask, hipStream_t stream) {
+                                         const uint8_t* mask, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(src && dst && mean && var, "ga_obs_normalize_from_f64: null pointer");
   GA_REQUIRE(n > 0 && obs_dim > 0 && ldo >= obs_dim,
              "ga_obs_normalize_from_f64: bad sizes");
@@ -627,11 +599,12 @@ extern "C" int ga_obs_normalize_from_f64(int64_t n, int obs_dim, const float* sr
 
 extern "C" int ga_obs_normalize_f64(int64_t n, int obs_dim, float* obs, int64_t ldo,
                                     double* mean, double* var, double alpha,
-                                    const uint8_t* mask, hipStream_t stream) {
+                                    const uint8_t* mask, ga_stream_t stream) {
   return ga_obs_normalize_from_f64(n, obs_dim, obs, obs, ldo, mean, var, alpha, mask,
                                    stream);
 }
 
+namespace {
 // NormalizedEnv.step's action rescale (envs/normalized_env.py:90-100): fp32, one
 // rounding per numpy operation (no fused multiply-add), np.clip's comparisons (a
 // NaN stays a NaN)
@@ -651,11 +624,13 @@ __global__ __launch_bounds__(256) void action_rescale_kernel(
   v = v < lo ? lo : (v > hi ? hi : v);
   out[r * ldo + j] = v;
 }
+}  // namespace
 
 extern "C" int ga_action_rescale_f32(int64_t n, int A, const float* actions, int64_t lda,
                                      const float* low, const float* high,
                                      float expected_action_scale, float* out,
-                                     int64_t ldo, hipStream_t stream) {
+                                     int64_t ldo, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(actions && low && high && out, "ga_action_rescale_f32: null pointer");
   GA_REQUIRE(n > 0 && A > 0 && lda >= A && ldo >= A, "ga_action_rescale_f32: bad sizes");
   hipLaunchKernelGGL(action_rescale_kernel, dim3((unsigned)ga_ceil_div(n * A, 256)),
@@ -667,7 +642,8 @@ extern "C" int ga_action_rescale_f32(int64_t n, int A, const float* actions, int
 
 extern "C" int ga_reward_normalize_f64(int64_t n, float* reward, double* mean,
                                        double* var, double alpha, double scale,
-                                       int normalize, hipStream_t stream) {
+                                       int normalize, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(reward && (!normalize || (mean && var)),
              "ga_reward_normalize_f64: null pointer");
   GA_REQUIRE(n > 0, "ga_reward_normalize_f64: bad size");

@@ -343,11 +343,8 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgs& a, int64_t
 
 }  // namespace ga_rollout
 
-// C-ABI argument structs of the rollout step (include/garage_amd.h) and their
-// validated conversion (rollout.hip)
-struct ga_synth_env;
-struct ga_record_args;
-struct ga_norm_args;
+// Validated conversion of the C-ABI arguments of the rollout step
+// (include/garage_amd.h) into EnvStepArgs (rollout.hip)
 int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
                       const ga_norm_args* norm, const float* actions, int64_t lda,
                       const float* obs, const char* who, ga_rollout::EnvStepArgs* out);

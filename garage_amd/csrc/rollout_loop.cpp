@@ -8,9 +8,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/garage_amd.h"
-
-void ga_set_error(const char* fmt, ...);
+#include "internal.h"
 
 // 1 (default): policy step and env step of a rollout step in ONE launch
 // (ga_policy_env_step_fused_f32) unless the actions are rescaled in between;

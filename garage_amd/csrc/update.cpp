@@ -17,13 +17,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/garage_amd.h"
+#include "internal.h"
 #include "small_step.h"
 #include "fused_train.h"
 
-void ga_set_error(const char* fmt, ...);
-
-typedef int (*ga_allreduce_fn)(void* comm, float* buf, int64_t n, void* stream);
 static ga_allreduce_fn g_allreduce = nullptr;
 
 extern "C" void ga_set_allreduce_hook(ga_allreduce_fn fn) { g_allreduce = fn; }
@@ -37,21 +34,6 @@ extern "C" int ga_set_fused_head_loss(int on) {
   g_fuse_head = on != 0;
   return 0;
 }
-
-// small_step.hip: one launch per optimizer step for minibatches of <= 64 rows
-extern "C" int64_t ga_reduction_partials_doubles(void);
-
-// gemm.hip: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
-// of layer l_start in dacts; fused_first: the data gradient into layer 0's output
-// and layer 0's weight gradient are computed elsewhere (ga_fused_dgrad_wgrad0)
-extern "C" int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params,
-                                         const float* X, int64_t ldx,
-                                         const int32_t* row_idx, int64_t M,
-                                         const float* acts, const float* dout,
-                                         int64_t ldo, float* dacts, float* grad_slabs,
-                                         int64_t slab_stride, int64_t n_splits,
-                                         int l_start, int fused_first,
-                                         ga_stream_t stream);
 
 // The optimizer step with the streaming passes folded into the GEMM epilogues
 // (fused_train.hip) for networks whose last hidden layer is 64 / 128 / 256 wide

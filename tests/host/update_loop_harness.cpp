@@ -18,6 +18,7 @@
 
 #include "../../include/garage_amd.h"
 #include "../../garage_amd/csrc/fused_train.h"
+#include "../../garage_amd/csrc/internal.h"
 #include "../../garage_amd/csrc/small_step.h"
 
 static std::vector<std::string> g_log;
@@ -123,7 +124,7 @@ int ga_mlp_backward_f32(const ga_mlp_desc*, const float*, const float*, int64_t,
 int ga_mlp_backward_range_f32(const ga_mlp_desc*, const float*, const float*, int64_t,
                               const int32_t*, int64_t M, const float*, const float*,
                               int64_t, float*, float*, int64_t, int64_t, int l_start,
-                              int fused_first, ga_stream_t) {
+                              int fused_first, hipStream_t) {
   logf("bwd_range M=%lld l_start=%d fused_first=%d", (long long)M, l_start, fused_first);
   return 0;
 }
@@ -406,10 +407,6 @@ struct Net {
   }
 };
 
-extern "C" int ga_set_small_step(int on);
-extern "C" int ga_set_fused_train(int on);
-extern "C" int64_t ga_update_partials_floats(const ga_mlp_desc* d, int64_t M);
-extern "C" void ga_set_allreduce_hook(ga_allreduce_fn fn);
 static int fake_allreduce(void*, float*, int64_t n, void*) {
   logf("allreduce n=%lld", (long long)n);
   return 0;

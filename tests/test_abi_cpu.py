@@ -1,7 +1,12 @@
-"""CPU checks of the boundary: the library loads and exports every symbol the
-header declares; the product never imports the oracle."""
+"""CPU checks of the boundary: the library loads and exports exactly the symbols
+the header declares; the ctypes structs match the header's layout; the product
+never imports the oracle."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
+import tempfile
 
 import pytest
 
@@ -14,7 +19,18 @@ def _header_symbols():
     return sorted(set(re.findall(r'\b(ga_[a-z0-9_]+)\s*\(', text)))
 
 
+def _dynamic_symbols(path):
+    """(type, name) of every defined dynamic symbol of the shared library."""
+    nm = shutil.which('nm') or '/opt/rocm/llvm/bin/llvm-nm'
+    out = subprocess.run([nm, '-D', '--defined-only', path], capture_output=True,
+                         text=True, check=True).stdout
+    return [tuple(line.split()[-2:]) for line in out.splitlines() if line.strip()]
+
+
 def test_library_exports_every_declared_symbol():
+    """... and nothing else: every other function is hidden (-fvisibility=hidden,
+    GA_API on the header's declarations), so a definition that drifts from its
+    declaration fails to compile instead of exporting a second symbol."""
     from garage_amd import _lib
     lib = _lib.load()
     names = _header_symbols()
@@ -24,6 +40,43 @@ def test_library_exports_every_declared_symbol():
     # the ctypes table and the header must describe the same set
     assert sorted(_lib.SIGNATURES) == names
     assert lib.ga_abi_version() == 4
+    syms = _dynamic_symbols(_lib.LIB_PATH)
+    functions = sorted(n for t, n in syms if t in ('T', 'W'))
+    assert functions == names
+    assert not [n for _, n in syms if n.startswith('_Z')]
+    data = [n for t, n in syms if t not in ('T', 'W')]
+    assert data and all(n.startswith('__hip_cuid_') for n in data), data
+
+
+def test_ctypes_structs_match_the_header():
+    """sizeof / offsetof / field sizes of the header's structs, from a C program
+    compiled by the host compiler, against the ctypes mirrors in _lib.py."""
+    from garage_amd import _lib
+    structs = {'ga_mlp_desc': _lib.MlpDesc, 'ga_synth_env': _lib.SynthEnv,
+               'ga_head_args': _lib.HeadArgs, 'ga_record_args': _lib.RecordArgs,
+               'ga_norm_args': _lib.NormArgs, 'ga_update_args': _lib.UpdateArgs}
+    lines = ['#include <stddef.h>', '#include <stdio.h>',
+             '#include "garage_amd.h"', 'int main(void) {']
+    want = []
+    for cname, py in structs.items():
+        lines.append('printf("{0} %zu\\n", sizeof({0}));'.format(cname))
+        want.append('{} {}'.format(cname, ctypes.sizeof(py)))
+        for field, ftype in py._fields_:
+            lines.append('printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), '
+                         'sizeof((({0}*)0)->{1}));'.format(cname, field))
+            want.append('{}.{} {} {}'.format(cname, field,
+                                             getattr(py, field).offset,
+                                             ctypes.sizeof(ftype)))
+    lines += ['return 0;', '}']
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, 'layout.c'), os.path.join(tmp, 'layout')
+        with open(src, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        subprocess.run(['cc', '-std=c99', '-Wall', '-Werror', '-I',
+                        os.path.join(ROOT, 'include'), src, '-o', exe], check=True)
+        got = subprocess.run([exe], capture_output=True, text=True,
+                             check=True).stdout.split('\n')[:-1]
+    assert got == want
 
 
 def test_argument_errors_are_reported_without_a_gpu():
