@@ -38,6 +38,47 @@ static inline bool ga_aligned16(const void* p) {
 
 static inline int64_t ga_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- torch.optim.Adam (OptimizerWrapper.step, torch/optimizers/optimizer_wrapper.py:53-63)
+// The per-step constants, derived on the host in double and rounded once.
+struct GaAdam {
+  float lerp_w;         // 1 - beta1
+  float beta2, one_minus_beta2;
+  float neg_step_size;  // -lr / (1 - beta1^t)
+  float bc2_sqrt;       // sqrt(1 - beta2^t)
+  float eps;
+};
+
+static inline GaAdam ga_adam_coeffs(double lr, double beta1, double beta2, double eps,
+                                    int64_t step) {
+  GaAdam a;
+  a.lerp_w = (float)(1.0 - beta1);
+  a.beta2 = (float)beta2;
+  a.one_minus_beta2 = (float)(1.0 - beta2);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  a.neg_step_size = (float)(-(lr / bc1));
+  a.bc2_sqrt = (float)sqrt(bc2);
+  a.eps = (float)eps;
+  return a;
+}
+
+// One element of torch.optim.Adam's single-tensor step, the ONE Adam of every kernel,
+// with fused multiply-add contraction switched off (HIP's __fmul_rn / __fadd_rn are
+// plain operators, so the compiler would otherwise be free to contract differently in
+// each kernel): one rounding per torch operation.
+__device__ __forceinline__ void ga_adam_update(const GaAdam& a, float g, float& p,
+                                               float& m, float& v) {
+#pragma clang fp contract(off)
+  const float diff = g - m;
+  m = fmaf(a.lerp_w, diff, m);             // exp_avg.lerp_(grad, 1 - beta1): torch's
+                                           // lerp is one fused multiply-add
+  const float gg = (a.one_minus_beta2 * g) * g;
+  v = v * a.beta2 + gg;                    // mul_(beta2).addcmul_(g, g, 1 - beta2)
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+  const float num = a.neg_step_size * m;
+  p = p + num / denom;                     // addcdiv_(exp_avg, denom, -step_size)
+}
+
 // ---- device helpers --------------------------------------------------------
 // XCD-aware workgroup order.  Workgroups are dealt to the 8 XCDs round-robin by
 // their linear id, and each XCD has its own L2, so workgroups that read the same

@@ -1502,21 +1502,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
 }
 
 // ---------------------------------------------------------------------------
-struct FtAdam {  // losses.hip: AdamParams / adam_update
+struct FtAdam {
   float* p; float* m; float* v;
-  float lerp_w, beta2, one_minus_beta2, neg_step_size, bc2_sqrt, eps;
+  GaAdam c;
 };
-__device__ __forceinline__ void ft_adam_update(const FtAdam& a, float g, float& p,
-                                               float& m, float& v) {
-#pragma clang fp contract(off)
-  const float diff = g - m;
-  m = fmaf(a.lerp_w, diff, m);
-  const float gg = (a.one_minus_beta2 * g) * g;
-  v = v * a.beta2 + gg;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  const float num = a.neg_step_size * m;
-  p = p + num / denom;
-}
 
 constexpr int FT_MAX_REGIONS = 16;
 struct FtRegion {
@@ -1583,7 +1572,7 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
     N.grads[0] = g;
     if (N.do_adam) {
       float pp = N.a.p[0], mm = N.a.m[0], vv = N.a.v[0];
-      ft_adam_update(N.a, g, pp, mm, vv);
+      ga_adam_update(N.a.c, g, pp, mm, vv);
       N.a.p[0] = pp; N.a.m[0] = mm; N.a.v[0] = vv;
     }
     return;
@@ -1658,7 +1647,7 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
     float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
           vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ft_adam_update(N.a, g[j], pp[j], mm[j], vv[j]);
+    for (int j = 0; j < 4; ++j) ga_adam_update(N.a.c, g[j], pp[j], mm[j], vv[j]);
     *reinterpret_cast<float4*>(N.a.p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
     *reinterpret_cast<float4*>(N.a.m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
     *reinterpret_cast<float4*>(N.a.v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
@@ -1698,20 +1687,6 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
       }
     }
   }
-}
-
-LossRowArgs loss_args(const ga_fused_loss_args* l, int64_t M) {
-  LossRowArgs L;
-  memset(&L, 0, sizeof(L));
-  L.kind = l->kind; L.actions = l->actions; L.lda = l->lda; L.old_ll = l->old_ll;
-  L.adv = l->adv; L.returns = l->returns; L.idx = l->idx; L.log_std = l->log_std;
-  L.has_min = l->has_min; L.has_max = l->has_max; L.min_log_std = l->min_log_std;
-  L.max_log_std = l->max_log_std; L.A = l->A; L.algo = l->algo; L.clip = l->clip;
-  L.ent_coeff = l->ent_coeff; L.ent_regularized = l->ent_flags & 1;
-  L.ent_softplus = (l->ent_flags >> 1) & 1; L.ent_stop_grad = (l->ent_flags >> 2) & 1;
-  L.double_softmax = l->double_softmax;
-  L.invM = 1.f / (float)M;
-  return L;
 }
 
 }  // namespace
@@ -2142,14 +2117,7 @@ static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_fused_region
   p.n_virtual = v;
   FtNet& N = p.net[net];
   N.a.p = params; N.a.m = exp_avg; N.a.v = exp_avg_sq;
-  N.a.lerp_w = (float)(1.0 - beta1);
-  N.a.beta2 = (float)beta2;
-  N.a.one_minus_beta2 = (float)(1.0 - beta2);
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  N.a.neg_step_size = (float)(-(lr / bc1));
-  N.a.bc2_sqrt = (float)sqrt(bc2);
-  N.a.eps = (float)eps;
+  N.a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
   N.grads = grads; N.scale = scale; N.do_adam = do_adam; N.zero_slot0 = zero_slot0;
   N.lpart = lpart; N.n_lpart = n_lpart; N.M = M;
   N.loss = loss_args(loss, M);

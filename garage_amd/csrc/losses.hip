@@ -17,17 +17,11 @@
 // are <= a few tens of floats), fp32 math, fp64 block partials reduced in a
 // fixed order (bitwise reproducible run to run; no float atomics).
 #include "common.h"
+#include "loss_rows.h"
 
 namespace {
 
 constexpr int RED_BLOCKS = 512;  // upper bound on partial-producing blocks
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-
-__device__ __forceinline__ float softplusf(float x) {
-  // F.softplus with beta=1, threshold=20 (torch default)
-  return x > 20.f ? x : log1pf(expf(x));
-}
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
 // Multi-block reductions finish in the same launch: every block publishes its
 // partial sums, then takes a ticket; the block that draws the last one sees all of
@@ -78,8 +72,7 @@ struct PpoLossParams {
   int algo;               // 0 PPO clipped surrogate, 1 VPG (ll * adv),
                           // 2 TRPO unclipped surrogate (ratio * adv)
   float clip;
-  float ent_coeff;        // added to the objective when ent_regularized
-  int ent_regularized, ent_softplus, ent_stop_grad;
+  LossEnt ent;
   float* dmean;           // optional [M, ldm]: dLoss/dmean (already / M)
   float* ll_out;          // optional [M]: new log-likelihoods
   double* partials;       // [gridDim.x][2]: sum objective, sum dLoss/dlog_std * M
@@ -95,29 +88,14 @@ struct PpoLossParams {
 __device__ void ppo_gaussian_finish(double obj, double ds, const float* log_std,
                                     int has_min, float min_log_std, int has_max,
                                     float max_log_std, int64_t M, int A,
-                                    float ent_coeff, int ent_regularized,
-                                    int ent_softplus, int ent_stop_grad,
-                                    float* loss_out, float* grad_slab0,
-                                    int64_t slab_stride, int64_t n_splits) {
-  float chain;
+                                    const LossEnt& ent, float* loss_out,
+                                    float* grad_slab0, int64_t slab_stride,
+                                    int64_t n_splits) {
+  float chain, dlogstd;
   const float s = ga_log_std(*log_std, has_min, min_log_std, has_max, max_log_std, &chain);
-  double mean_obj = obj / (double)M;
-  double dlogstd = ds / (double)M;  // d(-mean obj)/ds through the likelihood
-  if (ent_regularized) {
-    // Independent Normal entropy: A * (0.5 + 0.5 log 2pi + s), state independent
-    float ent = (float)A * (0.5f + (float)HALF_LOG_2PI + s);
-    float dent = (float)A;
-    if (ent_softplus) {
-      dent *= sigmoidf(ent);
-      ent = softplusf(ent);
-    }
-    mean_obj += (double)(ent_coeff * ent);
-    if (!ent_stop_grad) dlogstd += -(double)(ent_coeff * dent);
-  }
-  *loss_out = (float)(-mean_obj);
+  lr_gaussian_finish(ent, A, s, chain, obj, ds, M, loss_out, &dlogstd);
   if (grad_slab0) {
-    // (through the clamp and the std parameterisation: 0 when the clamp is active)
-    grad_slab0[0] = chain != 0.f ? (float)dlogstd * chain : 0.f;
+    grad_slab0[0] = dlogstd;
     for (int64_t k = 1; k < n_splits; ++k) grad_slab0[k * slab_stride] = 0.f;
   }
 }
@@ -137,34 +115,11 @@ __global__ __launch_bounds__(256) void ppo_gaussian_loss_kernel(PpoLossParams p)
     const float* mu = p.mean + i * p.ldm;
     const float* a = p.actions + src * p.lda;
     float ll = 0.f, q = 0.f;  // q = sum (a-mu)^2 / var
-    for (int j = 0; j < p.A; ++j) {
-      const float d = a[j] - mu[j];
-      const float z = d * d * inv_var;
-      q += z;
-      ll += -0.5f * z - lognorm;
-    }
+    for (int j = 0; j < p.A; ++j) lr_gauss_dim(a[j], mu[j], inv_var, lognorm, q, ll);
     if (p.ll_out) p.ll_out[i] = ll;
-    const float adv = p.adv[src];
-    float obj, g;  // g = d obj / d ll
-    if (p.algo == 1) {
-      obj = ll * adv;
-      g = adv;
-    } else if (p.algo == 2) {
-      // torch/algos/trpo.py:113-117: likelihood ratio times advantage
-      const float ratio = expf(ll - p.old_ll[src]);
-      obj = ratio * adv;
-      g = obj;
-    } else {
-      const float ratio = expf(ll - p.old_ll[src]);
-      const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-      const float rc = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = ratio * adv, s2 = rc * adv;
-      obj = fminf(s1, s2);
-      const float g1 = adv * ratio;                                  // via surr
-      const float g2 = (ratio >= lo && ratio <= hi) ? adv * ratio : 0.f;  // via clip
-      // torch.min backward: the smaller input gets the gradient, ties split it
-      g = (s1 < s2) ? g1 : ((s1 > s2) ? g2 : 0.5f * (g1 + g2));
-    }
+    float g;  // d obj / d ll
+    const float obj = lr_surrogate(p.algo, p.clip, ll, p.algo == 1 ? 0.f : p.old_ll[src],
+                                   p.adv[src], &g);
     obj_sum += (double)obj;
     if (p.dmean) {
       float* dm = p.dmean + i * p.ldm;
@@ -189,8 +144,7 @@ __global__ __launch_bounds__(256) void ppo_gaussian_loss_kernel(PpoLossParams p)
   }
   if (threadIdx.x == 0 && p.loss_out)
     ppo_gaussian_finish(bo, bd, p.log_std, p.has_min, p.min_log_std, p.has_max,
-                        p.max_log_std, p.M, p.A, p.ent_coeff, p.ent_regularized,
-                        p.ent_softplus, p.ent_stop_grad, p.loss_out, p.grad_slab0,
+                        p.max_log_std, p.M, p.A, p.ent, p.loss_out, p.grad_slab0,
                         p.slab_stride, p.n_splits);
 }
 
@@ -202,8 +156,7 @@ struct PpoFinalizeParams {
   int has_min, has_max;
   int64_t M;
   int A;
-  float ent_coeff;
-  int ent_regularized, ent_softplus, ent_stop_grad;
+  LossEnt ent;
   float* loss_out;      // scalar
   float* grad_slab0;    // optional: slot that receives dLoss/dlog_std
   int64_t slab_stride;  // the same slot of slabs 1..n_splits-1 is zeroed
@@ -221,8 +174,7 @@ __global__ void ppo_gaussian_finalize_kernel(PpoFinalizeParams p) {
   ds = ga_wave_sum(ds);
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   ppo_gaussian_finish(obj, ds, p.log_std, p.has_min, p.min_log_std, p.has_max,
-                      p.max_log_std, p.M, p.A, p.ent_coeff, p.ent_regularized,
-                      p.ent_softplus, p.ent_stop_grad, p.loss_out, p.grad_slab0,
+                      p.max_log_std, p.M, p.A, p.ent, p.loss_out, p.grad_slab0,
                       p.slab_stride, p.n_splits);
 }
 
@@ -244,8 +196,7 @@ struct CatLossParams {
   int double_softmax;
   int algo;
   float clip;
-  float ent_coeff;
-  int ent_regularized, ent_softplus, ent_stop_grad;
+  LossEnt ent;
   float* dscores;        // optional [M, lds]: dLoss/dscores (already / M)
   float* ll_out;         // optional [M]
   float* ent_out;        // optional [M]: per-row entropy (after softplus if set)
@@ -299,62 +250,31 @@ __global__ __launch_bounds__(256) void ppo_categorical_loss_kernel(CatLossParams
       if (j == a) ll = lp;
     }
     float Hs = H, dHs = 1.f;  // softplus(H) and its derivative
-    if (p.ent_softplus) {
-      dHs = sigmoidf(H);
-      Hs = softplusf(H);
-    }
+    if (p.ent.softplus) Hs = lr_softplus(H, &dHs);
     if (p.ll_out) p.ll_out[i] = ll;
     if (p.ent_out) p.ent_out[i] = Hs;
-    const float adv = p.adv[src];
-    float obj, g;
-    if (p.algo == 1) {
-      obj = ll * adv;
-      g = adv;
-    } else if (p.algo == 2) {
-      // torch/algos/trpo.py:113-117: likelihood ratio times advantage
-      const float ratio = expf(ll - p.old_ll[src]);
-      obj = ratio * adv;
-      g = obj;
-    } else {
-      const float ratio = expf(ll - p.old_ll[src]);
-      const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-      const float rc = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = ratio * adv, s2 = rc * adv;
-      obj = fminf(s1, s2);
-      const float g1 = adv * ratio;
-      const float g2 = (ratio >= lo && ratio <= hi) ? adv * ratio : 0.f;
-      g = (s1 < s2) ? g1 : ((s1 > s2) ? g2 : 0.5f * (g1 + g2));
-    }
-    if (p.ent_regularized) obj += p.ent_coeff * Hs;
+    float g;
+    float obj = lr_surrogate(p.algo, p.clip, ll, p.algo == 1 ? 0.f : p.old_ll[src],
+                             p.adv[src], &g);
+    if (p.ent.regularized) obj += p.ent.coeff * Hs;
     obj_sum += (double)obj;
     ent_sum += (double)Hs;
     if (p.dscores) {
-      // dObj/dlogit'_j = g (1[j=a] - q_j) + c_H * (-q_j (lp_j + H))
-      const float cH = (p.ent_regularized && !p.ent_stop_grad)
-                           ? p.ent_coeff * dHs : 0.f;
+      const float cH = (p.ent.regularized && !p.ent.stop_grad) ? p.ent.coeff * dHs : 0.f;
       float* ds = p.dscores + i * p.lds;
       if (!p.double_softmax) {
-        for (int j = 0; j < p.A; ++j) {
-          const float lp = sc[j] - lse;
-          const float q = expf(lp);
-          const float d = g * ((j == a ? 1.f : 0.f) - q) - cH * q * (lp + H);
-          ds[j] = -d * invM;
-        }
+        for (int j = 0; j < p.A; ++j)
+          ds[j] = -lr_cat_grad(g, cH, sc[j] - lse, H, j == a) * invM;
       } else {
         // chain through p = softmax(scores): dz_k = p_k (dp_k - sum_j dp_j p_j)
         float dot = 0.f;
         for (int j = 0; j < p.A; ++j) {
           const float pj = expf(sc[j] - mx) / den;
-          const float lp = pj - lse;
-          const float q = expf(lp);
-          const float dp = g * ((j == a ? 1.f : 0.f) - q) - cH * q * (lp + H);
-          dot += dp * pj;
+          dot += lr_cat_grad(g, cH, pj - lse, H, j == a) * pj;
         }
         for (int k = 0; k < p.A; ++k) {
           const float pk = expf(sc[k] - mx) / den;
-          const float lp = pk - lse;
-          const float q = expf(lp);
-          const float dp = g * ((k == a ? 1.f : 0.f) - q) - cH * q * (lp + H);
+          const float dp = lr_cat_grad(g, cH, pk - lse, H, k == a);
           ds[k] = -(pk * (dp - dot)) * invM;
         }
       }
@@ -448,11 +368,10 @@ __global__ __launch_bounds__(256) void gaussian_nll_kernel(NllParams p) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.M;
        i += (int64_t)gridDim.x * 256) {
     const int64_t src = p.idx ? (int64_t)p.idx[i] : i;
-    const float d = p.returns[src] - p.v[i * p.ldv];
-    const float z = d * d * inv_var;
-    nll += (double)(0.5f * z + s + (float)HALF_LOG_2PI);
-    ds += (double)(1.f - z);
-    if (p.dv) p.dv[i * p.ldv] = -d * inv_var * invM;
+    float dsi, dvi;
+    nll += (double)lr_nll_row(p.returns[src], p.v[i * p.ldv], s, inv_var, invM, &dsi, &dvi);
+    ds += (double)dsi;
+    if (p.dv) p.dv[i * p.ldv] = dvi;
   }
   const double a = ga_block_sum_256(nll, red);
   const double b = ga_block_sum_256(ds, red);
@@ -578,30 +497,8 @@ struct AdamParams {
   float* m;
   float* v;
   int64_t n;
-  float lerp_w;        // 1 - beta1
-  float beta2, one_minus_beta2;
-  float neg_step_size; // -lr / (1 - beta1^t)
-  float bc2_sqrt;      // sqrt(1 - beta2^t)
-  float eps;
+  GaAdam c;
 };
-
-// One element of torch.optim.Adam's single-tensor step with fused multiply-add
-// contraction switched off (HIP's __fmul_rn / __fadd_rn are plain operators, so
-// the compiler would otherwise be free to contract differently in each kernel):
-// the stand-alone kernel and the slab-reduction + Adam kernel produce the same
-// bits, which are those of one rounding per torch operation.
-__device__ __forceinline__ void adam_update(const AdamParams& a, float g, float& p,
-                                            float& m, float& v) {
-#pragma clang fp contract(off)
-  const float diff = g - m;
-  m = fmaf(a.lerp_w, diff, m);             // exp_avg.lerp_(grad, 1 - beta1): torch's
-                                           // lerp is one fused multiply-add
-  const float gg = (a.one_minus_beta2 * g) * g;
-  v = v * a.beta2 + gg;                    // mul_(beta2).addcmul_(g, g, 1 - beta2)
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  const float num = a.neg_step_size * m;
-  p = p + num / denom;                     // addcdiv_(exp_avg, denom, -step_size)
-}
 
 __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
   // (a short launch on its chain's critical path: its waves go first beside the other
@@ -610,7 +507,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
   float p = a.p[i], m = a.m[i], v = a.v[i];
-  adam_update(a, a.g[i], p, m, v);
+  ga_adam_update(a.c, a.g[i], p, m, v);
   a.p[i] = p;
   a.m[i] = m;
   a.v[i] = v;
@@ -755,7 +652,7 @@ __global__ __launch_bounds__(256) void reduce_adam_kernel(const float* slabs,
   float pp[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
         vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-  for (int j = 0; j < 4; ++j) adam_update(a, g[j], pp[j], mm[j], vv[j]);
+  for (int j = 0; j < 4; ++j) ga_adam_update(a.c, g[j], pp[j], mm[j], vv[j]);
   *reinterpret_cast<float4*>(a.p + i4) = make_float4(pp[0], pp[1], pp[2], pp[3]);
   *reinterpret_cast<float4*>(a.m + i4) = make_float4(mm[0], mm[1], mm[2], mm[3]);
   *reinterpret_cast<float4*>(a.v + i4) = make_float4(vv[0], vv[1], vv[2], vv[3]);
@@ -878,9 +775,7 @@ extern "C" int ga_ppo_gaussian_loss_f32(
   p.mean = mean; p.ldm = ldm; p.actions = actions; p.lda = lda; p.old_ll = old_ll;
   p.adv = adv; p.idx = idx; p.log_std = log_std; p.min_log_std = min_log_std;
   p.has_min = has_min; p.max_log_std = max_log_std; p.has_max = has_max; p.M = M;
-  p.A = A; p.algo = algo; p.clip = clip; p.ent_coeff = ent_coeff;
-  p.ent_regularized = ent_flags & 1; p.ent_softplus = (ent_flags >> 1) & 1;
-  p.ent_stop_grad = (ent_flags >> 2) & 1;
+  p.A = A; p.algo = algo; p.clip = clip; p.ent = lr_ent(ent_coeff, ent_flags);
   p.dmean = dmean; p.ll_out = ll_out; p.partials = workspace;
   const int nb = red_blocks(M);
   const bool one_launch = nb == 1 || g_one_launch_losses != 0;
@@ -893,9 +788,7 @@ extern "C" int ga_ppo_gaussian_loss_f32(
   PpoFinalizeParams f;
   f.partials = workspace; f.nblocks = nb; f.log_std = log_std;
   f.min_log_std = min_log_std; f.max_log_std = max_log_std; f.has_min = has_min;
-  f.has_max = has_max; f.M = M; f.A = A; f.ent_coeff = ent_coeff;
-  f.ent_regularized = p.ent_regularized; f.ent_softplus = p.ent_softplus;
-  f.ent_stop_grad = p.ent_stop_grad; f.loss_out = loss_out;
+  f.has_max = has_max; f.M = M; f.A = A; f.ent = p.ent; f.loss_out = loss_out;
   f.grad_slab0 = grad_slab0; f.slab_stride = slab_stride; f.n_splits = n_splits;
   hipLaunchKernelGGL(ppo_gaussian_finalize_kernel, dim3(1), dim3(64), 0, stream, f);
   GA_CHECK_LAUNCH("ppo_gaussian_finalize");
@@ -919,8 +812,7 @@ extern "C" int ga_ppo_categorical_loss_f32(
   p.scores = scores; p.lds = lds; p.actions = actions; p.lda = lda;
   p.old_ll = old_ll; p.adv = adv; p.idx = idx; p.M = M; p.A = A;
   p.double_softmax = double_softmax; p.algo = algo; p.clip = clip;
-  p.ent_coeff = ent_coeff; p.ent_regularized = ent_flags & 1;
-  p.ent_softplus = (ent_flags >> 1) & 1; p.ent_stop_grad = (ent_flags >> 2) & 1;
+  p.ent = lr_ent(ent_coeff, ent_flags);
   p.dscores = dscores; p.ll_out = ll_out; p.ent_out = ent_out;
   p.partials = workspace;
   const int nb = red_blocks(M);
@@ -1034,14 +926,7 @@ extern "C" int ga_reduce_adam_f32(const float* slabs, int64_t n_splits,
              "ga_reduce_adam_f32: 16-B alignment required");
   AdamParams a;
   a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
-  a.lerp_w = (float)(1.0 - beta1);
-  a.beta2 = (float)beta2;
-  a.one_minus_beta2 = (float)(1.0 - beta2);
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  a.neg_step_size = (float)(-(lr / bc1));
-  a.bc2_sqrt = (float)sqrt(bc2);
-  a.eps = (float)eps;
+  a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
   const int64_t nb = ga_ceil_div(n / 4, 64);
   hipLaunchKernelGGL(reduce_adam_kernel, dim3((unsigned)nb), dim3(256), 0, stream,
                      slabs, n_splits, slab_stride, zero_slot0, a, grads);
@@ -1058,14 +943,7 @@ extern "C" int ga_adam_step_f32(float* params, const float* grads, float* exp_av
   GA_REQUIRE(n > 0 && step >= 1, "ga_adam_step_f32: bad n / step");
   AdamParams a;
   a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
-  a.lerp_w = (float)(1.0 - beta1);
-  a.beta2 = (float)beta2;
-  a.one_minus_beta2 = (float)(1.0 - beta2);
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  a.neg_step_size = (float)(-(lr / bc1));
-  a.bc2_sqrt = (float)sqrt(bc2);
-  a.eps = (float)eps;
+  a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0,
                      stream, a);
   GA_CHECK_LAUNCH("adam");
@@ -1094,10 +972,9 @@ extern "C" int ga_optimizer_step_f32(int kind, float* params, const float* grads
   } else {
     GA_REQUIRE(s1 && s2 && (!(flags & 1) || s3),
                "ga_optimizer_step_f32: Adam state buffers");
-    const double bc1 = 1.0 - pow(h[1], (double)step);
-    const double bc2 = 1.0 - pow(h[2], (double)step);
-    a.neg_step_size = (float)(-(h[0] / bc1));
-    a.bc2_sqrt = (float)sqrt(bc2);
+    const GaAdam c = ga_adam_coeffs(h[0], h[1], h[2], h[3], step);
+    a.neg_step_size = c.neg_step_size;
+    a.bc2_sqrt = c.bc2_sqrt;
   }
   hipLaunchKernelGGL(optimizer_step_kernel, dim3((unsigned)ga_ceil_div(n, 256)),
                      dim3(256), 0, stream, a);
@@ -1306,7 +1183,8 @@ extern "C" int ga_fisher_seed_categorical_f32(const float* scores, int64_t lds,
 // loss kernel: 16 lanes own one row of the last hidden activations (16-B loads, a
 // whole row coalesced), the head weights sit in LDS, the A dot products are
 // reduced over the 16 lanes with xor shuffles, and the per-row loss / gradient
-// seed is the same arithmetic as ppo_gaussian_loss_kernel / gaussian_nll_kernel.
+// seed comes from the helpers of loss_rows.h, like ppo_gaussian_loss_kernel's and
+// gaussian_nll_kernel's.
 // One pass over the [rows x hidden] matrix replaces the narrow GEMM launch, the
 // round trip of its output and the loss launch.
 namespace {
@@ -1433,35 +1311,13 @@ __global__ __launch_bounds__(HL_THREADS) void head_ppo_gaussian_kernel(HeadLayer
       for (int t = 0; t < 4; ++t) {
         const int j = gl + 16 * t;
         dj[t] = 0.f;
-        if (j < p.A) {
-          const float d = actr[r][t] - rowbuf[j];
-          const float z = d * d * inv_var;
-          dj[t] = d;
-          q_part += z;
-          ll_part += -0.5f * z - lognorm;
-        }
+        if (j < p.A)
+          dj[t] = lr_gauss_dim(actr[r][t], rowbuf[j], inv_var, lognorm, q_part, ll_part);
       }
       const float q = group16_sum(q_part);
       const float ll = group16_sum(ll_part);
-      const float adv = advr[r];
-      float obj, g;
-      if (p.algo == 1) {
-        obj = ll * adv;
-        g = adv;
-      } else if (p.algo == 2) {
-        const float ratio = expf(ll - oldr[r]);
-        obj = ratio * adv;
-        g = obj;
-      } else {
-        const float ratio = expf(ll - oldr[r]);
-        const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-        const float rc = fminf(fmaxf(ratio, lo), hi);
-        const float s1 = ratio * adv, s2 = rc * adv;
-        obj = fminf(s1, s2);
-        const float g1 = adv * ratio;
-        const float g2 = (ratio >= lo && ratio <= hi) ? adv * ratio : 0.f;
-        g = (s1 < s2) ? g1 : ((s1 > s2) ? g2 : 0.5f * (g1 + g2));
-      }
+      float g;
+      const float obj = lr_surrogate(p.algo, p.clip, ll, oldr[r], advr[r], &g);
       if (live[r]) {
         if (p.ll_out && gl == 0) p.ll_out[irow[r]] = ll;
         if (p.dmean) {
@@ -1525,11 +1381,10 @@ __global__ __launch_bounds__(HL_THREADS) void head_gaussian_nll_kernel(HeadLayer
       const int64_t row = live[r] ? irow[r] : p.M - 1;
       head_row<KV>(L, 1, wlds, h[r], row, live[r], gl, rowbuf);
       if (live[r] && gl == 0) {
-        const float d = retr[r] - rowbuf[0];
-        const float z = d * d * inv_var;
-        nll += (double)(0.5f * z + s + (float)HALF_LOG_2PI);
-        ds += (double)(1.f - z);
-        if (p.dv) p.dv[irow[r] * p.ldv] = -d * inv_var * invM;
+        float dsi, dvi;
+        nll += (double)lr_nll_row(retr[r], rowbuf[0], s, inv_var, invM, &dsi, &dvi);
+        ds += (double)dsi;
+        if (p.dv) p.dv[irow[r] * p.ldv] = dvi;
       }
     }
   }
@@ -1581,9 +1436,7 @@ extern "C" int ga_head_ppo_gaussian_loss_f32(
   p.mean = nullptr; p.ldm = ldd; p.actions = actions; p.lda = lda; p.old_ll = old_ll;
   p.adv = adv; p.idx = idx; p.log_std = log_std; p.min_log_std = min_log_std;
   p.has_min = has_min; p.max_log_std = max_log_std; p.has_max = has_max; p.M = M;
-  p.A = A; p.algo = algo; p.clip = clip; p.ent_coeff = ent_coeff;
-  p.ent_regularized = ent_flags & 1; p.ent_softplus = (ent_flags >> 1) & 1;
-  p.ent_stop_grad = (ent_flags >> 2) & 1;
+  p.A = A; p.algo = algo; p.clip = clip; p.ent = lr_ent(ent_coeff, ent_flags);
   p.dmean = dmean; p.ll_out = ll_out; p.partials = workspace;
   p.loss_out = nullptr; p.grad_slab0 = nullptr; p.slab_stride = 0; p.n_splits = 0;
   p.ticket = nullptr;
@@ -1600,9 +1453,7 @@ extern "C" int ga_head_ppo_gaussian_loss_f32(
   PpoFinalizeParams f;
   f.partials = workspace; f.nblocks = nb; f.log_std = log_std;
   f.min_log_std = min_log_std; f.max_log_std = max_log_std; f.has_min = has_min;
-  f.has_max = has_max; f.M = M; f.A = A; f.ent_coeff = ent_coeff;
-  f.ent_regularized = p.ent_regularized; f.ent_softplus = p.ent_softplus;
-  f.ent_stop_grad = p.ent_stop_grad; f.loss_out = loss_out;
+  f.has_max = has_max; f.M = M; f.A = A; f.ent = p.ent; f.loss_out = loss_out;
   f.grad_slab0 = grad_slab0; f.slab_stride = slab_stride; f.n_splits = n_splits;
   hipLaunchKernelGGL(ppo_gaussian_finalize_kernel, dim3(1), dim3(64), 0, stream, f);
   GA_CHECK_LAUNCH("ppo_gaussian_finalize");

@@ -432,22 +432,6 @@ extern "C" int ga_narrow_step_debug(long long* host_out16) {
                  hipSuccess ? 0 : -1;
 }
 
-// LossRowArgs from the epoch loop's arguments (fused_train.hip holds the same
-// conversion for its kernels)
-static LossRowArgs narrow_loss_args(const ga_fused_loss_args* l, int64_t M) {
-  LossRowArgs L;
-  memset(&L, 0, sizeof(L));
-  L.kind = l->kind; L.actions = l->actions; L.lda = l->lda; L.old_ll = l->old_ll;
-  L.adv = l->adv; L.returns = l->returns; L.idx = l->idx; L.log_std = l->log_std;
-  L.has_min = l->has_min; L.has_max = l->has_max; L.min_log_std = l->min_log_std;
-  L.max_log_std = l->max_log_std; L.A = l->A; L.algo = l->algo; L.clip = l->clip;
-  L.ent_coeff = l->ent_coeff; L.ent_regularized = l->ent_flags & 1;
-  L.ent_softplus = (l->ent_flags >> 1) & 1; L.ent_stop_grad = (l->ent_flags >> 2) & 1;
-  L.double_softmax = l->double_softmax;
-  L.invM = 1.f / (float)M;
-  return L;
-}
-
 extern "C" int ga_narrow_step_supported(int n_layers, const int* dims) {
   return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&
          dims[0] >= 1 && dims[0] <= 32 && dims[3] >= 1 && dims[3] <= 8;
@@ -486,7 +470,7 @@ extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
   p.params = params;
   for (int l = 0; l < 3; ++l) { p.w_off[l] = w_off[l]; p.b_off[l] = b_off[l]; }
   p.in_w = in_w; p.out_w = out_w; p.M = (int)M; p.X = X; p.ldx = ldx;
-  p.loss = narrow_loss_args(loss, M);
+  p.loss = loss_args(loss, M);
   p.part = part; p.stride = ga_narrow_step_stride(in_w, H); p.lpart = lpart;
   p.dbg = g_ns_dbg;
   const dim3 grid((unsigned)ga_fused_tiles(M));

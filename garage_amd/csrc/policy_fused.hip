@@ -44,35 +44,6 @@ constexpr int KC = 32;            // k chunk
 constexpr int LDW = KC + 4;       // weight stage row stride
 constexpr int MAX_OUT = 32;       // widest output head
 
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
-                                            uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ float unit_interval(uint32_t u) {
-  return ((float)(u >> 8) + 0.5f) * 5.9604644775390625e-08f;
-}
-__device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
-                                           float* z1) {
-  const float a = unit_interval(u0), b = unit_interval(u1);
-  const float rad = sqrtf(-2.f * logf(a));
-  float s, c;
-  sincosf(6.28318530717958647692f * b, &s, &c);
-  *z0 = rad * c;
-  *z1 = rad * s;
-}
 __device__ __forceinline__ float tanh_fast(float x) {
   return ga_tanh(x);  // common.h
 }
@@ -474,6 +445,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams p) {
       const int64_t cell = env * p.Tcap + col;
       const float* h = head[tid];
       float* act_row = head[tid];  // the sampled action replaces the mean / scores
+      const ga_rollout::ActionNoise rng = {p.noise, p.ldn, p.env_id0, step, p.k0, p.k1};
       if (p.head_buf) {
         // agent_info: Gaussian mean (probabilities are written below)
         if (p.kind == 0)
@@ -482,51 +454,14 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams p) {
       if (p.kind == 0) {
         const float s = ga_log_std(p.params[0], p.has_min, p.min_log_std, p.has_max,
                                    p.max_log_std, nullptr);
-        const float sd = expf(s);
-        for (int b = 0; b * 4 < N; ++b) {
-          float z[4];
-          if (p.noise) {
-            for (int j = 0; j < 4 && b * 4 + j < N; ++j)
-              z[j] = p.noise[env * p.ldn + b * 4 + j];
-          } else {
-            const U4 rr = philox4x32_10((uint32_t)(p.env_id0 + env), step,
-                                        (uint32_t)b, 3u << 16, p.k0, p.k1);
-            box_muller(rr.x, rr.y, &z[0], &z[1]);
-            box_muller(rr.z, rr.w, &z[2], &z[3]);
-          }
-          for (int j = 0; j < 4 && b * 4 + j < N; ++j) {
-            const float a = h[b * 4 + j] + sd * z[j];
-            p.action[env * p.lda + b * 4 + j] = a;
-            p.act_buf[cell * p.lda + b * 4 + j] = a;
-            act_row[b * 4 + j] = a;
-          }
-        }
+        ga_rollout::sample_gaussian(h, expf(s), N, rng, env, [&](int j, float a) {
+              p.action[env * p.lda + j] = a;
+              p.act_buf[cell * p.lda + j] = a;
+              act_row[j] = a;
+            });
       } else {
-        float mx = h[0];
-        for (int j = 1; j < N; ++j) mx = fmaxf(mx, h[j]);
-        float den = 0.f;
-        for (int j = 0; j < N; ++j) den += expf(h[j] - mx);
-        float den2 = 0.f;
-        if (p.double_softmax)
-          for (int j = 0; j < N; ++j) den2 += expf(expf(h[j] - mx) / den);
-        float u;
-        if (p.noise) {
-          u = p.noise[env * p.ldn];
-        } else {
-          const U4 rr = philox4x32_10((uint32_t)(p.env_id0 + env), step, 0u,
-                                      3u << 16, p.k0, p.k1);
-          u = unit_interval(rr.x);
-        }
-        float cdf = 0.f;
-        int pick = N - 1;
-        bool found = false;
-        for (int j = 0; j < N; ++j) {
-          float pr = expf(h[j] - mx) / den;
-          if (p.double_softmax) pr = expf(pr) / den2;
-          if (p.head_buf) p.head_buf[cell * p.ldh + j] = pr;
-          cdf += pr;
-          if (!found && u < cdf) { pick = j; found = true; }
-        }
+        const int pick = ga_rollout::sample_categorical(
+            h, N, p.double_softmax, rng, env, p.head_buf ? p.head_buf + cell * p.ldh : nullptr);
         p.action[env * p.lda] = (float)pick;
         p.act_buf[cell * p.lda] = (float)pick;
         act_row[0] = (float)pick;

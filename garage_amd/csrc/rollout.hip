@@ -79,16 +79,6 @@ struct HeadParams {
   float* head_buf;        // optional [n, Tcap, ldh]: agent_info 'mean' / probs
 };
 
-__device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
-                                           float* z1) {
-  const float a = u32_unit_interval(u0), b = u32_unit_interval(u1);
-  const float rad = sqrtf(-2.f * logf(a));
-  float s, c;
-  sincosf(6.28318530717958647692f * b, &s, &c);
-  *z0 = rad * c;
-  *z1 = rad * s;
-}
-
 // The step's observations into the rollout buffer (the list append of
 // vec_worker.py:188), by the whole workgroup: consecutive threads copy consecutive
 // columns of a row.  (One thread per env copying its own row -- obs_dim strided
@@ -110,29 +100,15 @@ __global__ __launch_bounds__(256) void gaussian_head_kernel(HeadParams p) {
   if (i >= p.n) return;
   const float s = ga_log_std(*p.log_std, p.has_min, p.min_log_std, p.has_max,
                              p.max_log_std, nullptr);
-  const float std = expf(s);
-  const uint32_t env = (uint32_t)(p.env_id0 + i);
   const float* mu = p.head + i * p.ldh;
   float* act = p.action + i * p.lda;
   const int64_t cell = i * p.Tcap + p.col;
   float* act_row = p.act_buf + cell * p.lda;
-  for (int b = 0; b * 4 < p.A; ++b) {
-    float z[4];
-    if (p.noise) {
-      for (int j = 0; j < 4 && b * 4 + j < p.A; ++j)
-        z[j] = p.noise[i * p.ldn + b * 4 + j];
-    } else {
-      const U4 r = philox4x32_10(env, p.step, (uint32_t)b, STREAM_ACTION << 16, p.k0,
-                                 p.k1);
-      box_muller(r.x, r.y, &z[0], &z[1]);
-      box_muller(r.z, r.w, &z[2], &z[3]);
-    }
-    for (int j = 0; j < 4 && b * 4 + j < p.A; ++j) {
-      const float a = mu[b * 4 + j] + std * z[j];
-      act[b * 4 + j] = a;
-      act_row[b * 4 + j] = a;
-    }
-  }
+  const ActionNoise r = {p.noise, p.ldn, p.env_id0, p.step, p.k0, p.k1};
+  sample_gaussian(mu, expf(s), p.A, r, i, [&](int j, float a) {
+    act[j] = a;
+    act_row[j] = a;
+  });
   if (p.head_buf) {
     float* h = p.head_buf + cell * p.ldh;
     for (int j = 0; j < p.A; ++j) h[j] = mu[j];
@@ -145,33 +121,9 @@ __global__ __launch_bounds__(256) void categorical_head_kernel(HeadParams p) {
   if (i >= p.n) return;
   const float* sc = p.head + i * p.ldh;
   const int64_t cell = i * p.Tcap + p.col;
-  // probabilities: softmax(scores), or softmax(softmax(scores))
-  float mx = sc[0];
-  for (int j = 1; j < p.A; ++j) mx = fmaxf(mx, sc[j]);
-  float den = 0.f;
-  for (int j = 0; j < p.A; ++j) den += expf(sc[j] - mx);
-  float den2 = 0.f;
-  if (p.double_softmax)
-    for (int j = 0; j < p.A; ++j) den2 += expf(expf(sc[j] - mx) / den);
-  float u;
-  if (p.noise) {
-    u = p.noise[i * p.ldn];
-  } else {
-    const U4 r = philox4x32_10((uint32_t)(p.env_id0 + i), p.step, 0u,
-                               STREAM_ACTION << 16, p.k0, p.k1);
-    u = u32_unit_interval(r.x);
-  }
-  float cdf = 0.f;
-  int pick = p.A - 1;
-  float* h = p.head_buf ? p.head_buf + cell * p.ldh : nullptr;
-  bool found = false;
-  for (int j = 0; j < p.A; ++j) {
-    float pr = expf(sc[j] - mx) / den;
-    if (p.double_softmax) pr = expf(pr) / den2;
-    if (h) h[j] = pr;
-    cdf += pr;
-    if (!found && u < cdf) { pick = j; found = true; }
-  }
+  const ActionNoise r = {p.noise, p.ldn, p.env_id0, p.step, p.k0, p.k1};
+  const int pick = sample_categorical(sc, p.A, p.double_softmax, r, i,
+                                      p.head_buf ? p.head_buf + cell * p.ldh : nullptr);
   p.action[i * p.lda] = (float)pick;
   p.act_buf[cell * p.lda] = (float)pick;
 }

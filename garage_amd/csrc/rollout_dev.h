@@ -1,7 +1,7 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
-// policy + env step of policy_fused.hip: Philox, the synthetic environment, the
-// NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
-// (sampler/vec_worker.py:176-204).  One thread owns one env.
+// policy + env step of policy_fused.hip: Philox, action sampling, the synthetic
+// environment, the NormalizedEnv statistics, the per-step bookkeeping of
+// VecWorker.step_episode (sampler/vec_worker.py:176-204).  One thread owns one env.
 #pragma once
 #include "common.h"
 
@@ -45,6 +45,83 @@ static __device__ __forceinline__ float u32_unit_interval(uint32_t u) {
 
 static constexpr uint32_t STREAM_OBS = 0, STREAM_REWARD = 1, STREAM_LENGTH = 2;
 static constexpr uint32_t STREAM_ACTION = 3;
+
+// ---- action sampling (the rollout head kernels and the fused policy + env step) ----
+static __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
+                                                  float* z1) {
+  const float a = u32_unit_interval(u0), b = u32_unit_interval(u1);
+  const float rad = sqrtf(-2.f * logf(a));
+  float s, c;
+  sincosf(6.28318530717958647692f * b, &s, &c);
+  *z0 = rad * c;
+  *z1 = rad * s;
+}
+
+// The action noise of env `row` (global id env_id0 + row): row `row` of `noise`
+// [*, ldn] when given, else the env's action stream of Philox at `step`.
+struct ActionNoise {
+  const float* noise;
+  int64_t ldn;
+  int64_t env_id0;
+  uint32_t step, k0, k1;
+};
+
+// Gaussian action of one env: a_j = mu_j + sd z_j, j < A, with z from the noise row,
+// or Box-Muller on the action stream (4 draws per Philox block b); emit(j, a_j)
+// stores each.
+template <class Emit>
+static __device__ __forceinline__ void sample_gaussian(const float* mu, float sd, int A,
+                                                       const ActionNoise& r, int64_t row,
+                                                       Emit emit) {
+  for (int b = 0; b * 4 < A; ++b) {
+    float z[4];
+    if (r.noise) {
+      for (int j = 0; j < 4 && b * 4 + j < A; ++j) z[j] = r.noise[row * r.ldn + b * 4 + j];
+    } else {
+      const U4 u = philox4x32_10((uint32_t)(r.env_id0 + row), r.step, (uint32_t)b,
+                                 STREAM_ACTION << 16, r.k0, r.k1);
+      box_muller(u.x, u.y, &z[0], &z[1]);
+      box_muller(u.z, u.w, &z[2], &z[3]);
+    }
+    for (int j = 0; j < 4 && b * 4 + j < A; ++j) emit(b * 4 + j, mu[b * 4 + j] + sd * z[j]);
+  }
+}
+
+// Categorical action of one env by inverse CDF over softmax(sc), or
+// softmax(softmax(sc)) with double_softmax, with u from the noise
+// row or the first uniform of the action stream.  probs (optional) <- the
+// probabilities.
+static __device__ __forceinline__ int sample_categorical(const float* sc, int A,
+                                                         int double_softmax,
+                                                         const ActionNoise& r, int64_t row,
+                                                         float* probs) {
+  float mx = sc[0];
+  for (int j = 1; j < A; ++j) mx = fmaxf(mx, sc[j]);
+  float den = 0.f;
+  for (int j = 0; j < A; ++j) den += expf(sc[j] - mx);
+  float den2 = 0.f;
+  if (double_softmax)
+    for (int j = 0; j < A; ++j) den2 += expf(expf(sc[j] - mx) / den);
+  float u;
+  if (r.noise) {
+    u = r.noise[row * r.ldn];
+  } else {
+    const U4 v = philox4x32_10((uint32_t)(r.env_id0 + row), r.step, 0u, STREAM_ACTION << 16,
+                               r.k0, r.k1);
+    u = u32_unit_interval(v.x);
+  }
+  float cdf = 0.f;
+  int pick = A - 1;
+  bool found = false;
+  for (int j = 0; j < A; ++j) {
+    float pr = expf(sc[j] - mx) / den;
+    if (double_softmax) pr = expf(pr) / den2;
+    if (probs) probs[j] = pr;
+    cdf += pr;
+    if (!found && u < cdf) { pick = j; found = true; }
+  }
+  return pick;
+}
 
 // ---- synthetic environment ---------------------------------------------------
 struct SynthEnv {

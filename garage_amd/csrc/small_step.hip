@@ -24,9 +24,11 @@
 // Shapes: two tanh hidden layers of equal width H (multiple of 32, <= 256), input
 // width <= 32, <= 8 outputs, <= 64 rows; Gaussian or categorical PPO / VPG objective
 // (with the entropy options), or the value function's Gaussian NLL.  Everything else takes the
-// per-layer path.  Same formulas as losses.hip / gemm.hip; sums are taken in a
-// different order, so results agree to rounding, not bit for bit.
+// per-layer path.  The loss rows and Adam are those of loss_rows.h and common.h, the
+// layers the formulas of gemm.hip; sums are taken in a different order, so results
+// agree to rounding, not bit for bit.
 #include "common.h"
+#include "loss_rows.h"
 #include "small_step.h"
 
 // ---- Audit (round 3) of global loads whose lane / wave index can lie outside the
@@ -59,7 +61,6 @@ constexpr int SS_HMAX = 256;
 constexpr int SS_LDH = SS_HMAX + 4;
 constexpr int SS_LDX = 36;
 constexpr int SS_LDO = 20;      // own-slice tiles [64][16 + 4]
-constexpr double SS_HALF_LOG_2PI = 0.91893853320467274178;
 
 typedef const __attribute__((address_space(4))) float* uptr;  // wave-uniform reads
 
@@ -76,9 +77,9 @@ struct SmallStepParams {
   const float* returns;
   int algo; float clip;
   int has_min, has_max; float min_log_std, max_log_std;
-  float ent_coeff; int ent_regularized, ent_softplus, ent_stop_grad;
+  LossEnt ent;
   // Adam (one step for every parameter)
-  float lerp_w, beta2, one_minus_beta2, neg_step_size, bc2_sqrt, eps;
+  GaAdam adam;
   int learn_std;
   // exchange buffers [64][H] each (H2, dZ2) and the barrier words {count, flag}
   // (zero between launches)
@@ -93,21 +94,9 @@ __device__ __forceinline__ float ss_tanh(float x) {
   return ga_tanh(x);  // common.h
 }
 
-// torch.optim.Adam, one element (losses.hip: adam_update)
-__device__ __forceinline__ void ss_adam_math(const SmallStepParams& a, float g, float& p,
-                                             float& m, float& v) {
-#pragma clang fp contract(off)
-  const float diff = g - m;
-  m = fmaf(a.lerp_w, diff, m);
-  const float gg = (a.one_minus_beta2 * g) * g;
-  v = v * a.beta2 + gg;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  const float num = a.neg_step_size * m;
-  p = p + num / denom;
-}
 __device__ __forceinline__ void ss_adam(const SmallStepParams& a, float g, int64_t i) {
   float p = a.params[i], m = a.m[i], v = a.v[i];
-  ss_adam_math(a, g, p, m, v);
+  ga_adam_update(a.adam, g, p, m, v);
   a.params[i] = p; a.m[i] = m; a.v[i] = v;
 }
 // N elements `stride` apart: every load first (one memory round trip, not N)
@@ -122,7 +111,7 @@ __device__ __forceinline__ void ss_adam_n(const SmallStepParams& a, const float 
     v[n] = a.v[i0 + n * stride];
   }
 #pragma unroll
-  for (int n = 0; n < N; ++n) ss_adam_math(a, g[n], p[n], m[n], v[n]);
+  for (int n = 0; n < N; ++n) ga_adam_update(a.adam, g[n], p[n], m[n], v[n]);
 #pragma unroll
   for (int n = 0; n < N; ++n) {
     a.params[i0 + n * stride] = p[n];
@@ -481,39 +470,28 @@ __global__ __launch_bounds__(SS_THREADS) void small_step_kernel(SmallStepParams 
     float s = p.params[0], s_chain = 1.f;
     bool s_grad = true;
     double obj = 0.0, ds = 0.0;
+    const int algo = p.algo == 1 ? 1 : 0;  // (the epoch loop admits PPO and VPG only)
     float dm[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) dm[j] = 0.f;
+    float row_out[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) row_out[j] = outl[r * 8 + j];
     if (p.kind == 0) {
       s = ga_log_std(s, p.has_min, p.min_log_std, p.has_max, p.max_log_std, &s_chain);
       s_grad = s_chain != 0.f;
       const float inv_var = expf(-2.f * s);
-      const float lognorm = s + (float)SS_HALF_LOG_2PI;
+      const float lognorm = s + (float)HALF_LOG_2PI;
       if (live) {
+        // (a loop over A, not lr_gauss_row's unrolled one: the two contract the sums
+        // into fused multiply-adds differently)
         const float* a = p.actions + src * p.lda;
         float ll = 0.f, q = 0.f;
-        for (int j = 0; j < A; ++j) {
-          const float d = a[j] - outl[r * 8 + j];
-          const float z = d * d * inv_var;
-          q += z;
-          ll += -0.5f * z - lognorm;
-        }
-        const float adv = p.adv[src];
-        float o, g;
-        if (p.algo == 1) {
-          o = ll * adv;
-          g = adv;
-        } else {
-          const float ratio = expf(ll - p.old_ll[src]);
-          const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-          const float rc = fminf(fmaxf(ratio, lo), hi);
-          const float s1 = ratio * adv, s2 = rc * adv;
-          o = fminf(s1, s2);
-          const float g1 = adv * ratio;
-          const float g2 = (ratio >= lo && ratio <= hi) ? adv * ratio : 0.f;
-          g = (s1 < s2) ? g1 : ((s1 > s2) ? g2 : 0.5f * (g1 + g2));
-        }
-        obj = (double)o;
+        for (int j = 0; j < A; ++j)
+          lr_gauss_dim(a[j], outl[r * 8 + j], inv_var, lognorm, q, ll);
+        float g;
+        obj = (double)lr_surrogate(algo, p.clip, ll, algo == 1 ? 0.f : p.old_ll[src],
+                                   p.adv[src], &g);
         const float scale = -g * invM * inv_var;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -521,90 +499,21 @@ __global__ __launch_bounds__(SS_THREADS) void small_step_kernel(SmallStepParams 
         ds = (double)(-g * (q - (float)A));
       }
     } else if (p.kind == 2) {
-      // categorical head (losses.hip: ppo_categorical_loss_kernel): the scores are
-      // logits, or -- double_softmax -- their softmax is
+      // categorical head: the scores are logits, or -- double_softmax -- their
+      // softmax is
       s_grad = false;  // no log-std parameter: its slot keeps a zero gradient
       if (live) {
-        float sc[8], pr[8], lp[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sc[j] = outl[r * 8 + j];
-        float mx = sc[0];
-#pragma unroll
-        for (int j = 1; j < 8; ++j)
-          if (j < A) mx = fmaxf(mx, sc[j]);
-        float den = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (j < A) den += expf(sc[j] - mx);
-        float lse;
-        if (!p.double_softmax) {
-          lse = mx + logf(den);
-        } else {
-          float s2 = 0.f;
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (j < A) s2 += expf(expf(sc[j] - mx) / den);
-          lse = logf(s2);
-        }
-        const int a = (int)p.actions[src * p.lda];
-        float ll = 0.f, Hent = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          pr[j] = 0.f; lp[j] = 0.f;
-          if (j < A) {
-            pr[j] = expf(sc[j] - mx) / den;
-            lp[j] = (p.double_softmax ? pr[j] : sc[j]) - lse;
-            Hent -= expf(lp[j]) * lp[j];
-            if (j == a) ll = lp[j];
-          }
-        }
-        float Hs = Hent, dHs = 1.f;
-        if (p.ent_softplus) {
-          dHs = 1.f / (1.f + expf(-Hent));
-          Hs = Hent > 20.f ? Hent : log1pf(expf(Hent));
-        }
-        const float adv = p.adv[src];
-        float o, g;
-        if (p.algo == 1) {
-          o = ll * adv;
-          g = adv;
-        } else {
-          const float ratio = expf(ll - p.old_ll[src]);
-          const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-          const float rc = fminf(fmaxf(ratio, lo), hi);
-          const float s1 = ratio * adv, s2 = rc * adv;
-          o = fminf(s1, s2);
-          const float g1 = adv * ratio;
-          const float g2 = (ratio >= lo && ratio <= hi) ? adv * ratio : 0.f;
-          g = (s1 < s2) ? g1 : ((s1 > s2) ? g2 : 0.5f * (g1 + g2));
-        }
-        if (p.ent_regularized) o += p.ent_coeff * Hs;
-        obj = (double)o;
-        const float cH = (p.ent_regularized && !p.ent_stop_grad) ? p.ent_coeff * dHs : 0.f;
-        float dp[8];
-        float dot = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          dp[j] = 0.f;
-          if (j < A) {
-            const float q = expf(lp[j]);
-            dp[j] = g * ((j == a ? 1.f : 0.f) - q) - cH * q * (lp[j] + Hent);
-            dot += dp[j] * pr[j];
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (j < A)
-            dm[j] = p.double_softmax ? -(pr[j] * (dp[j] - dot)) * invM : -dp[j] * invM;
+        float Hs;
+        obj = (double)lr_cat_row(algo, p.clip, p.ent, p.double_softmax, A, invM, row_out,
+                                 (int)p.actions[src * p.lda], p.adv[src],
+                                 algo == 1 ? 0.f : p.old_ll[src], dm, &Hs);
       }
     } else {
       const float inv_var = expf(-2.f * s);
       if (live) {
-        const float d = p.returns[src] - outl[r * 8];
-        const float z = d * d * inv_var;
-        obj = (double)(0.5f * z + s + (float)SS_HALF_LOG_2PI);
-        ds = (double)(1.f - z);
-        dm[0] = -d * inv_var * invM;
+        float dsr;
+        obj = (double)lr_nll_row(p.returns[src], row_out[0], s, inv_var, invM, &dsr, &dm[0]);
+        ds = (double)dsr;
       }
     }
 #pragma unroll
@@ -612,22 +521,13 @@ __global__ __launch_bounds__(SS_THREADS) void small_step_kernel(SmallStepParams 
     obj = ga_wave_sum(obj);
     ds = ga_wave_sum(ds);
     if (tid == 0) {
-      double mean = obj / (double)M;
-      double dls = ds / (double)M;
-      if (p.kind == 0 && p.ent_regularized) {
-        // entropy of the Independent Normal, A (0.5 + 0.5 log 2 pi + s): the same for
-        // every state (losses.hip: ppo_gaussian_finish)
-        float ent = (float)A * (0.5f + (float)SS_HALF_LOG_2PI + s);
-        float dent = (float)A;
-        if (p.ent_softplus) {
-          dent *= 1.f / (1.f + expf(-ent));
-          ent = ent > 20.f ? ent : log1pf(expf(ent));
-        }
-        mean += (double)(p.ent_coeff * ent);
-        if (!p.ent_stop_grad) dls += -(double)(p.ent_coeff * dent);
-      }
-      if (blockIdx.x == 0) *p.loss_out = (float)(p.kind == 1 ? mean : -mean);
-      dlogstd_s = s_grad ? (float)dls * s_chain : 0.f;
+      float loss = (float)(obj / (double)M), dls = (float)(ds / (double)M);
+      if (p.kind == 0)
+        lr_gaussian_finish(p.ent, A, s, s_chain, obj, ds, M, &loss, &dls);
+      else if (p.kind == 2)
+        loss = (float)(-(obj / (double)M));
+      if (blockIdx.x == 0) *p.loss_out = loss;
+      dlogstd_s = s_grad ? dls : 0.f;
     }
   }
   __syncthreads();
@@ -775,7 +675,7 @@ __global__ __launch_bounds__(SS_THREADS) void small_step_kernel(SmallStepParams 
         for (int i = 0; i < 8; ++i) {
           const int row = (i & 3) + 8 * (i >> 2) + 4 * kh;
           const int64_t e = p.w_off[1] + (int64_t)(c0 + row) * H + 32 * cj + l31;
-          ss_adam_math(p, g_w1[t][i], ap[t][i], am[t][i], av[t][i]);
+          ga_adam_update(p.adam, g_w1[t][i], ap[t][i], am[t][i], av[t][i]);
           p.params[e] = ap[t][i]; p.m[e] = am[t][i]; p.v[e] = av[t][i];
         }
       }
@@ -900,16 +800,8 @@ extern "C" int ga_small_step(const ga_small_step_args* a, void* stream_) {
   p.returns = a->returns; p.algo = a->algo; p.clip = a->clip;
   p.has_min = a->has_min; p.has_max = a->has_max; p.min_log_std = a->min_log_std;
   p.max_log_std = a->max_log_std;
-  p.ent_coeff = a->ent_coeff; p.ent_regularized = a->ent_flags & 1;
-  p.ent_softplus = (a->ent_flags >> 1) & 1; p.ent_stop_grad = (a->ent_flags >> 2) & 1;
-  p.lerp_w = (float)(1.0 - a->beta1);
-  p.beta2 = (float)a->beta2;
-  p.one_minus_beta2 = (float)(1.0 - a->beta2);
-  const double bc1 = 1.0 - pow(a->beta1, (double)a->step);
-  const double bc2 = 1.0 - pow(a->beta2, (double)a->step);
-  p.neg_step_size = (float)(-(a->lr / bc1));
-  p.bc2_sqrt = (float)sqrt(bc2);
-  p.eps = (float)a->eps;
+  p.ent = lr_ent(a->ent_coeff, a->ent_flags);
+  p.adam = ga_adam_coeffs(a->lr, a->beta1, a->beta2, a->eps, a->step);
   p.learn_std = a->learn_std;
   p.dbg = g_dbg;
   p.max_polls = g_max_polls;
