@@ -30,6 +30,28 @@ class SynthEnv(C.Structure):
                 ('t', ptr), ('len', ptr)]
 
 
+class PointEnv(C.Structure):
+    """``ga_point_env``."""
+    _fields_ = [('n', c_i64), ('arena_size', c_f32), ('done_bonus', c_f32),
+                ('never_done', c_i32), ('max_episode_length', c_i32),
+                ('point', ptr), ('goal', ptr), ('t', ptr), ('success', ptr)]
+
+
+class GridEnv(C.Structure):
+    """``ga_grid_env``."""
+    _fields_ = [('n', c_i64), ('rows', c_i32), ('cols', c_i32),
+                ('max_episode_length', c_i32), ('pad_', c_i32), ('map', ptr),
+                ('start', ptr), ('state', ptr), ('t', ptr)]
+
+
+class EnvRef(C.Structure):
+    """``ga_env_ref``: kind ``ENV_SYNTH`` / ``ENV_POINT`` / ``ENV_GRID``."""
+    _fields_ = [('kind', c_i32), ('pad_', c_i32), ('env', ptr)]
+
+
+ENV_SYNTH, ENV_POINT, ENV_GRID = 0, 1, 2
+
+
 class HeadArgs(C.Structure):
     """``ga_head_args``."""
     _fields_ = [('n', c_i64), ('env_id0', c_i64), ('A', c_i32), ('kind', c_i32),
@@ -211,6 +233,25 @@ SIGNATURES = {
                                        C.POINTER(RecordArgs), ptr, ptr,
                                        C.POINTER(NormArgs), ptr, ptr, c_i64,
                                        ptr]),
+    'ga_point_env_reset': (c_int, [C.POINTER(PointEnv), ptr, ptr, c_i64, ptr]),
+    'ga_point_env_step': (c_int, [C.POINTER(PointEnv), ptr, c_i64, ptr, ptr,
+                                  c_i64, ptr, ptr, ptr]),
+    'ga_point_env_step_record_norm': (c_int, [C.POINTER(PointEnv),
+                                              C.POINTER(RecordArgs),
+                                              C.POINTER(NormArgs), ptr, c_i64,
+                                              ptr, ptr]),
+    'ga_grid_env_reset': (c_int, [C.POINTER(GridEnv), ptr, ptr, c_i64, ptr]),
+    'ga_grid_env_step': (c_int, [C.POINTER(GridEnv), ptr, c_i64, ptr, ptr,
+                                 c_i64, ptr, ptr, ptr]),
+    'ga_grid_env_step_record_norm': (c_int, [C.POINTER(GridEnv),
+                                             C.POINTER(RecordArgs),
+                                             C.POINTER(NormArgs), ptr, c_i64,
+                                             ptr, ptr]),
+    'ga_rollout_env_steps': (c_int, [C.POINTER(MlpDesc), ptr,
+                                     C.POINTER(HeadArgs), C.POINTER(EnvRef),
+                                     C.POINTER(RecordArgs), ptr, ptr,
+                                     C.POINTER(NormArgs), ptr, ptr, c_i64,
+                                     ptr]),
     'ga_pack_episodes': (c_int, [ptr, c_i64, c_i64, c_i64, ptr, ptr, ptr, ptr,
                                  ptr]),
     'ga_pack_src_index': (c_int, [ptr, ptr, ptr, ptr, c_i64, c_i64, ptr, ptr]),

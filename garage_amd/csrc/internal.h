@@ -38,6 +38,19 @@ int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const fl
                     float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
                     int64_t lddz, hipStream_t stream);
 
+// rollout.hip / policy_fused.hip: ga_*_env_step_record_norm and
+// ga_policy_env_step_fused_f32 for any device env (rollout_env_loop.cpp)
+int ga_env_step_record_ref(const ga_env_ref* env, const ga_record_args* rec,
+                           const ga_norm_args* norm, const float* actions, int64_t lda,
+                           const float* obs, ga_stream_t stream);
+int ga_policy_env_step_fused_ref(const ga_mlp_desc* d, const float* params,
+                                 const ga_head_args* head, const ga_env_ref* env,
+                                 const ga_record_args* rec, const ga_norm_args* norm,
+                                 int64_t n_steps, ga_stream_t stream);
+// rollout_loop.cpp: 1 when a rollout step takes the one fused policy + env launch
+// (ga_set_fused_env_step, GARAGE_AMD_FUSED_ENV_STEP)
+int ga_fused_env_step_enabled(void);
+
 extern "C" {
 // gemm.hip: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
 // of layer l_start in dacts (l_start = n_layers - 1 with `dout`: the whole pass, what

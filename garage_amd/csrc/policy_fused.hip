@@ -16,9 +16,9 @@
 // the narrow output layer is a 16-lane VALU dot product, and the head (Gaussian:
 // mean + std * noise; categorical: inverse CDF) writes the action and the rollout
 // buffers.  Hidden widths up to 256 (C2, C3); wider nets use the per-layer path.
-// With the synthetic env the thread that sampled an env's action also steps it, and
-// a whole rollout is ONE launch with the weights resident on the CU (see the
-// kernel).
+// With a device env (synthetic, PointEnv, GridWorldEnv: a template parameter of the
+// kernel) the thread that sampled an env's action also steps it, and a whole
+// rollout is ONE launch with the weights resident on the CU (see the kernel).
 #include "common.h"
 #include "prof.h"
 
@@ -48,6 +48,7 @@ __device__ __forceinline__ float tanh_fast(float x) {
   return ga_tanh(x);  // common.h
 }
 
+template <class Env>
 struct FusedParams {
   int n_layers;
   int dims[9];
@@ -70,12 +71,11 @@ struct FusedParams {
   float* act_buf;
   float* head_buf;
   int64_t ldh;
-  // env_step: the synthetic env's step, the NormalizedEnv statistics, the
-  // bookkeeping and the reset of finished envs follow in the same launch, each env by
-  // the thread that sampled its action (rollout_dev.h: the code of
-  // synth_step_record_kernel)
+  // env_step: the env's step, the NormalizedEnv statistics, the bookkeeping and the
+  // reset of finished envs follow in the same launch, each env by the thread that
+  // sampled its action (rollout_dev.h: the code of env_step_record_kernel)
   int env_step;
-  ga_rollout::EnvStepArgs es;
+  ga_rollout::EnvStepArgsT<Env> es;
   // n_steps > 1 (needs env_step): the workgroup takes its envs through n_steps
   // consecutive rollout steps in this one launch -- nothing couples the envs of
   // different workgroups within a rollout -- alternating between the two
@@ -206,8 +206,8 @@ __device__ __forceinline__ void resident_layer_k(const float* __restrict__ A, in
 // MFMAs consume: 256 of the 512 registers a wave has at one wave per SIMD), so that
 // layer runs without a barrier or a weight fetch.  Same k order per accumulator as
 // the streamed loop: bit-identical.
-template <bool RES>
-__global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams p) {
+template <bool RES, class Env>
+__global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env> p) {
   __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDACT];
   __shared__ __attribute__((aligned(16))) float wst[2][HMAX * LDW];
   __shared__ float head[ROWS][MAX_OUT];
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams p) {
   const uint32_t step = p.step + (uint32_t)sidx;
   const bool odd = sidx & 1;
   const float* obs = odd ? p.es.seen_next : p.obs;
-  ga_rollout::EnvStepArgs es = p.es;
+  ga_rollout::EnvStepArgsT<Env> es = p.es;
   if (p.env_step) {
     es.p.col = col;
     es.seen_next = odd ? const_cast<float*>(p.obs) : p.es.seen_next;
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams p) {
     act[0][r * LDACT + c] = v;
   }
   // the env threads fetch what their env's step will read now, behind the network
-  ga_rollout::EnvPre pre;
+  decltype(ga_rollout::env_prefetch(es, 0)) pre;
   if (p.env_step && tid < ROWS && row0 + tid < p.n)
     pre = ga_rollout::env_prefetch(es, row0 + tid);
   __syncthreads();
@@ -665,9 +665,11 @@ extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
 
 // `head` of args is ignored (the means / scores stay on chip); everything else
 // as in ga_policy_head_sample.
+template <class Env>
 static int policy_step_launch(const ga_mlp_desc* d, const float* params,
-                              const ga_head_args* a, const ga_rollout::EnvStepArgs* es,
-                              int64_t n_steps, hipStream_t stream);
+                              const ga_head_args* a,
+                              const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
+                              hipStream_t stream);
 
 static bool g_ps_no_resident = getenv("GARAGE_AMD_ROLLOUT_RESIDENT") &&
                                atoi(getenv("GARAGE_AMD_ROLLOUT_RESIDENT")) == 0;
@@ -690,7 +692,7 @@ extern "C" int ga_policy_step_debug(long long* host_out32) {
 extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* params,
                                         const ga_head_args* a, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  return policy_step_launch(d, params, a, nullptr, 1, stream);
+  return policy_step_launch<ga_rollout::SynthEnv>(d, params, a, nullptr, 1, stream);
 }
 
 // The same launch followed, per env, by the synthetic env's step + NormalizedEnv
@@ -699,19 +701,22 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* param
 // envs through all of them (nothing couples envs within a rollout), alternating
 // between `a->obs` and `rec->next_obs` (and the raw pair of `norm`).  `a->action` is
 // what the env is stepped with.
-extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                            const ga_head_args* a,
-                                            const ga_synth_env* env,
-                                            const ga_record_args* rec,
-                                            const ga_norm_args* norm, int64_t n_steps,
-                                            ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// the kernel-side arguments of each C-ABI env (unevaluated: types only)
+ga_rollout::EnvStepArgs env_args_of(const ga_synth_env*);
+ga_rollout::EnvStepArgsT<ga_rollout::PointEnv> env_args_of(const ga_point_env*);
+ga_rollout::EnvStepArgsT<ga_rollout::GridEnv> env_args_of(const ga_grid_env*);
+
+template <class GaEnv>
+static int policy_env_step_fused(const ga_mlp_desc* d, const float* params,
+                                 const ga_head_args* a, const GaEnv* env,
+                                 const ga_record_args* rec, const ga_norm_args* norm,
+                                 int64_t n_steps, hipStream_t stream) {
   GA_REQUIRE(a && rec, "ga_policy_env_step_fused_f32: null pointer");
   GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
              "ga_policy_env_step_fused_f32: steps exceed the rollout buffer");
   GA_REQUIRE(!a->noise || n_steps == 1,
              "ga_policy_env_step_fused_f32: teacher-forced noise is per step");
-  ga_rollout::EnvStepArgs es;
+  decltype(env_args_of(env)) es;
   int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs,
                              "ga_policy_env_step_fused_f32", &es);
   if (rc) return rc;
@@ -721,9 +726,43 @@ extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* p
   return policy_step_launch(d, params, a, &es, n_steps, stream);
 }
 
+extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
+                                            const ga_head_args* a,
+                                            const ga_synth_env* env,
+                                            const ga_record_args* rec,
+                                            const ga_norm_args* norm, int64_t n_steps,
+                                            ga_stream_t stream_) {
+  return policy_env_step_fused(d, params, a, env, rec, norm, n_steps,
+                               (hipStream_t)stream_);
+}
+
+// The same for any device env (rollout_env_loop.cpp)
+int ga_policy_env_step_fused_ref(const ga_mlp_desc* d, const float* params,
+                                 const ga_head_args* a, const ga_env_ref* env,
+                                 const ga_record_args* rec, const ga_norm_args* norm,
+                                 int64_t n_steps, ga_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  GA_REQUIRE(env && env->env, "ga_rollout_env_steps: null env");
+  switch (env->kind) {
+    case GA_ENV_SYNTH:
+      return policy_env_step_fused(d, params, a, (const ga_synth_env*)env->env, rec, norm,
+                                   n_steps, stream);
+    case GA_ENV_POINT:
+      return policy_env_step_fused(d, params, a, (const ga_point_env*)env->env, rec, norm,
+                                   n_steps, stream);
+    case GA_ENV_GRID:
+      return policy_env_step_fused(d, params, a, (const ga_grid_env*)env->env, rec, norm,
+                                   n_steps, stream);
+  }
+  ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
+  return -1;
+}
+
+template <class Env>
 static int policy_step_launch(const ga_mlp_desc* d, const float* params,
-                              const ga_head_args* a, const ga_rollout::EnvStepArgs* es,
-                              int64_t n_steps, hipStream_t stream) {
+                              const ga_head_args* a,
+                              const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
+                              hipStream_t stream) {
   GA_REQUIRE(d && params && a, "ga_policy_step_fused_f32: null pointer");
   GA_REQUIRE(ga_policy_step_fused_supported(d),
              "ga_policy_step_fused_f32: unsupported network shape");
@@ -734,7 +773,7 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   GA_REQUIRE(a->col >= 0 && a->col < a->Tcap,
              "ga_policy_step_fused_f32: col out of range");
   GA_REQUIRE(ga_aligned16(params), "ga_policy_step_fused_f32: params alignment");
-  FusedParams p;
+  FusedParams<Env> p;
   p.n_layers = d->n_layers;
   for (int i = 0; i < 9; ++i) p.dims[i] = d->dims[i];
   for (int i = 0; i < 8; ++i) { p.w_off[i] = d->w_off[i]; p.b_off[i] = d->b_off[i]; }
@@ -757,9 +796,11 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                         (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
   if (resident) ga_prof_count(GA_PROF_ROLLOUT);
   if (resident)
-    hipLaunchKernelGGL(policy_step_fused_kernel<true>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env>), grid, dim3(256), 0, stream,
+                       p);
   else
-    hipLaunchKernelGGL(policy_step_fused_kernel<false>, grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env>), grid, dim3(256), 0, stream,
+                       p);
   GA_CHECK_LAUNCH("policy_step_fused");
   return GA_OK;
 }

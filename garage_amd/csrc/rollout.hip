@@ -1,5 +1,6 @@
-// Rollout-side kernels: action sampling heads, the synthetic batched
-// environment, per-step episode bookkeeping and the ragged -> packed compaction.
+// Rollout-side kernels: action sampling heads, the device environments
+// (synthetic, PointEnv, GridWorldEnv), per-step episode bookkeeping and the
+// ragged -> packed compaction.
 //
 // Together they replace the Python per-env loop of VecWorker.step_episode /
 // _gather_episode / collect_episode (sampler/vec_worker.py:139-219) and
@@ -28,6 +29,31 @@ __global__ __launch_bounds__(256) void synth_step_kernel(
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= e.n) return;
   synth_step_one(e, i, actions, lda, obs, next_obs, ldo, reward, step_type);
+}
+
+// reset / step of a PointEnv or GridWorldEnv batch (rollout_dev.h)
+template <class Env>
+__global__ __launch_bounds__(256) void env_reset_kernel(Env e, const uint8_t* mask,
+                                                        float* obs, int64_t ldo) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= e.n) return;
+  if (mask && !mask[i]) return;
+  env_reset_one(e, i, obs, ldo);
+}
+
+template <class Env>
+__global__ __launch_bounds__(256) void env_step_kernel(Env e, const float* actions,
+                                                       int64_t lda, float* next_obs,
+                                                       int64_t ldo, float* reward,
+                                                       uint8_t* step_type) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= e.n) return;
+  float rew;
+  uint8_t st;
+  env_core(e, i, env_pre(e, i), actions + i * lda, nullptr, next_obs + i * ldo, 0, &rew,
+           &st);
+  reward[i] = rew;
+  step_type[i] = st;
 }
 
 // src == dst normalises in place; otherwise the raw rows stay untouched (the
@@ -138,7 +164,9 @@ __global__ __launch_bounds__(256) void record_step_kernel(RecordParams p) {
 // touches env i's own state).  `raw_obs` / `raw_next` are the env's own
 // observations; p.next_obs is what the policy sees next and what is recorded as
 // the terminal observation -- the same buffer as raw_next without normalisation.
-__global__ __launch_bounds__(256) void synth_step_record_kernel(EnvStepArgs a) {
+// One instantiation per env kind (the type of a.e).
+template <class Env>
+__global__ __launch_bounds__(256) void env_step_record_kernel(EnvStepArgsT<Env> a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   record_counts(a.p, i < a.e.n ? env_step_one(a, i) : 0);
 }
@@ -365,23 +393,23 @@ extern "C" int ga_record_step(const ga_record_args* a, ga_stream_t stream_) {
 }
 
 // Validation + conversion of the C-ABI arguments of one env step (also used by the
-// fused policy + env step of policy_fused.hip)
-int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who, ga_rollout::EnvStepArgs* out) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
+// fused policy + env step of policy_fused.hip): the record / NormalizedEnv part, for
+// an env of obs_dim observations and act_w action columns
+template <class Env>
+static int build_env_step(const Env& e, int obs_dim, int act_w, const ga_record_args* a,
+                          const ga_norm_args* norm, const float* actions, int64_t lda,
+                          const float* obs, const char* who,
+                          ga_rollout::EnvStepArgsT<Env>* out) {
   GA_REQUIRE(a && a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
                  a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
                  a->step_eps && a->step_samples && actions && obs,
              "%s: null pointer", who);
-  GA_REQUIRE(a->n == env->n && a->col >= 0 && a->col < a->Tcap,
+  GA_REQUIRE(a->n == e.n && a->col >= 0 && a->col < a->Tcap,
              "%s: col %lld out of range (Tcap %lld)", who, (long long)a->col,
              (long long)a->Tcap);
   GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
              "%s: max_episode_length must be in 1..65535", who);
-  GA_REQUIRE(a->ldo >= env->obs_dim && a->obs_dim == env->obs_dim &&
-                 lda >= (env->discrete ? 1 : env->act_dim),
+  GA_REQUIRE(a->ldo >= obs_dim && a->obs_dim == obs_dim && lda >= act_w,
              "%s: leading dimensions too small", who);
   RecordParams p;
   p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
@@ -413,11 +441,20 @@ int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
       raw_next = norm->raw_next_obs;
     }
   }
-  out->e = to_dev(env); out->p = p; out->nm = nm;
+  out->e = e; out->p = p; out->nm = nm;
   out->actions = actions; out->lda = lda; out->raw_obs = raw_obs; out->raw_next = raw_next;
   out->seen_next = (float*)a->next_obs; out->reward = (float*)a->reward;
   out->step_type = (uint8_t*)a->step_type;
   return GA_OK;
+}
+
+int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who, ga_rollout::EnvStepArgs* out) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  return build_env_step(to_dev(env), env->obs_dim, env->discrete ? 1 : env->act_dim, a,
+                        norm, actions, lda, obs, who, out);
 }
 
 extern "C" int ga_synth_env_step_record_norm(const ga_synth_env* env,
@@ -430,8 +467,8 @@ extern "C" int ga_synth_env_step_record_norm(const ga_synth_env* env,
   int rc = ga_build_env_step(env, a, norm, actions, lda, obs, "ga_synth_env_step_record",
                              &args);
   if (rc) return rc;
-  hipLaunchKernelGGL(synth_step_record_kernel, dim3((unsigned)ga_ceil_div(a->n, 256)),
-                     dim3(256), 0, stream, args);
+  hipLaunchKernelGGL(env_step_record_kernel<SynthEnv>,
+                     dim3((unsigned)ga_ceil_div(a->n, 256)), dim3(256), 0, stream, args);
   GA_CHECK_LAUNCH("synth_step_record");
   return GA_OK;
 }
@@ -441,6 +478,178 @@ extern "C" int ga_synth_env_step_record(const ga_synth_env* env,
                                         int64_t lda, const float* obs,
                                         ga_stream_t stream) {
   return ga_synth_env_step_record_norm(env, a, nullptr, actions, lda, obs, stream);
+}
+
+// ---- PointEnv / GridWorldEnv batches ---------------------------------------------
+// succ_ld: row stride of the success buffer (1: [n], Tcap: the [n, Tcap] record buffer)
+static PointEnv to_dev(const ga_point_env* e, int64_t succ_ld) {
+  PointEnv d;
+  d.n = e->n; d.arena = e->arena_size; d.bonus = e->done_bonus;
+  d.never_done = e->never_done; d.max_len = e->max_episode_length;
+  d.point = e->point; d.goal = e->goal; d.t = e->t; d.success = e->success;
+  d.succ_ld = succ_ld;
+  return d;
+}
+
+static GridEnv to_dev(const ga_grid_env* e) {
+  GridEnv d;
+  d.n = e->n; d.rows = e->rows; d.cols = e->cols; d.max_len = e->max_episode_length;
+  d.map = e->map; d.start = e->start; d.state = e->state; d.t = e->t;
+  return d;
+}
+
+static int check_env(const ga_point_env* e, const char* who) {
+  GA_REQUIRE(e && e->point && e->goal && e->t, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->arena_size >= 0.f, "%s: arena_size must be >= 0", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_grid_env* e, const char* who) {
+  GA_REQUIRE(e && e->map && e->start && e->state && e->t, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0 && e->rows > 0 && e->cols > 0 && e->rows <= 4096 &&
+                 e->cols <= 4096 && (int64_t)e->rows * e->cols <= (1 << 20),
+             "%s: bad env sizes", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int env_obs_dim(const ga_point_env*) { return 3; }
+static int env_obs_dim(const ga_grid_env* e) { return e->rows * e->cols; }
+static int env_act_width(const ga_point_env*) { return 2; }
+static int env_act_width(const ga_grid_env*) { return 1; }
+
+int ga_build_env_step(const ga_point_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who,
+                      ga_rollout::EnvStepArgsT<ga_rollout::PointEnv>* out) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  GA_REQUIRE(a, "%s: null pointer", who);
+  return build_env_step(to_dev(env, a->Tcap), 3, 2, a, norm, actions, lda, obs, who, out);
+}
+
+int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who,
+                      ga_rollout::EnvStepArgsT<ga_rollout::GridEnv>* out) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  return build_env_step(to_dev(env), env->rows * env->cols, 1, a, norm, actions, lda, obs,
+                        who, out);
+}
+
+static PointEnv to_dev_step(const ga_point_env* e) { return to_dev(e, 1); }
+static GridEnv to_dev_step(const ga_grid_env* e) { return to_dev(e); }
+
+template <class GaEnv>
+static int env_reset(const GaEnv* env, const uint8_t* mask, float* obs, int64_t ldo,
+                     hipStream_t stream, const char* who) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  GA_REQUIRE(obs && ldo >= env_obs_dim(env), "%s: bad obs buffer", who);
+  const auto e = to_dev_step(env);
+  hipLaunchKernelGGL(env_reset_kernel<decltype(e)>,
+                     dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0, stream, e,
+                     mask, obs, ldo);
+  GA_CHECK_LAUNCH("env_reset");
+  return GA_OK;
+}
+
+template <class GaEnv>
+static int env_step(const GaEnv* env, const float* actions, int64_t lda, float* next_obs,
+                    int64_t ldo, float* reward, uint8_t* step_type, hipStream_t stream,
+                    const char* who) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  GA_REQUIRE(actions && next_obs && reward && step_type, "%s: null pointer", who);
+  GA_REQUIRE(ldo >= env_obs_dim(env) && lda >= env_act_width(env),
+             "%s: leading dimensions too small", who);
+  const auto e = to_dev_step(env);
+  hipLaunchKernelGGL(env_step_kernel<decltype(e)>,
+                     dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0, stream, e,
+                     actions, lda, next_obs, ldo, reward, step_type);
+  GA_CHECK_LAUNCH("env_step");
+  return GA_OK;
+}
+
+template <class GaEnv>
+static int env_step_record(const GaEnv* env, const ga_record_args* a,
+                           const ga_norm_args* norm, const float* actions, int64_t lda,
+                           const float* obs, hipStream_t stream, const char* who) {
+  using Env = decltype(to_dev_step(env));
+  EnvStepArgsT<Env> args;
+  int rc = ga_build_env_step(env, a, norm, actions, lda, obs, who, &args);
+  if (rc) return rc;
+  hipLaunchKernelGGL(env_step_record_kernel<Env>,
+                     dim3((unsigned)ga_ceil_div(a->n, 256)), dim3(256), 0, stream, args);
+  GA_CHECK_LAUNCH("env_step_record");
+  return GA_OK;
+}
+
+// envs/point_env.py:79-98 (reset), :100-170 (step)
+extern "C" int ga_point_env_reset(const ga_point_env* env, const uint8_t* mask, float* obs,
+                                  int64_t ldo, ga_stream_t stream) {
+  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_point_env_reset");
+}
+extern "C" int ga_point_env_step(const ga_point_env* env, const float* actions,
+                                 int64_t lda, const float*, float* next_obs, int64_t ldo,
+                                 float* reward, uint8_t* step_type, ga_stream_t stream) {
+  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
+                  (hipStream_t)stream, "ga_point_env_step");
+}
+// envs/point_env.py:100-170 + normalized_env.py:134-164 + vec_worker.py:176-204
+extern "C" int ga_point_env_step_record_norm(const ga_point_env* env,
+                                             const ga_record_args* rec,
+                                             const ga_norm_args* norm,
+                                             const float* actions, int64_t lda,
+                                             const float* obs, ga_stream_t stream) {
+  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
+                         "ga_point_env_step_record_norm");
+}
+
+// envs/grid_world_env.py:91-109 (reset), :111-215 (step)
+extern "C" int ga_grid_env_reset(const ga_grid_env* env, const uint8_t* mask, float* obs,
+                                 int64_t ldo, ga_stream_t stream) {
+  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_grid_env_reset");
+}
+extern "C" int ga_grid_env_step(const ga_grid_env* env, const float* actions, int64_t lda,
+                                const float*, float* next_obs, int64_t ldo, float* reward,
+                                uint8_t* step_type, ga_stream_t stream) {
+  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
+                  (hipStream_t)stream, "ga_grid_env_step");
+}
+// envs/grid_world_env.py:111-215 + normalized_env.py:134-164 + vec_worker.py:176-204
+extern "C" int ga_grid_env_step_record_norm(const ga_grid_env* env,
+                                            const ga_record_args* rec,
+                                            const ga_norm_args* norm, const float* actions,
+                                            int64_t lda, const float* obs,
+                                            ga_stream_t stream) {
+  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
+                         "ga_grid_env_step_record_norm");
+}
+
+// ga_*_env_step_record_norm of any device env (rollout_env_loop.cpp)
+int ga_env_step_record_ref(const ga_env_ref* env, const ga_record_args* rec,
+                           const ga_norm_args* norm, const float* actions, int64_t lda,
+                           const float* obs, ga_stream_t stream) {
+  GA_REQUIRE(env && env->env, "ga_rollout_env_steps: null env");
+  switch (env->kind) {
+    case GA_ENV_SYNTH:
+      return ga_synth_env_step_record_norm((const ga_synth_env*)env->env, rec, norm,
+                                           actions, lda, obs, stream);
+    case GA_ENV_POINT:
+      return ga_point_env_step_record_norm((const ga_point_env*)env->env, rec, norm,
+                                           actions, lda, obs, stream);
+    case GA_ENV_GRID:
+      return ga_grid_env_step_record_norm((const ga_grid_env*)env->env, rec, norm,
+                                          actions, lda, obs, stream);
+  }
+  ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
+  return -1;
 }
 
 extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,

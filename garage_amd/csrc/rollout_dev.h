@@ -1,7 +1,8 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
-// policy + env step of policy_fused.hip: Philox, action sampling, the synthetic
-// environment, the NormalizedEnv statistics, the per-step bookkeeping of
-// VecWorker.step_episode (sampler/vec_worker.py:176-204).  One thread owns one env.
+// policy + env step of policy_fused.hip: Philox, action sampling, the device
+// environments (synthetic, PointEnv, GridWorldEnv), the NormalizedEnv statistics,
+// the per-step bookkeeping of VecWorker.step_episode (sampler/vec_worker.py:176-204).
+// One thread owns one env.
 #pragma once
 #include "common.h"
 
@@ -162,6 +163,145 @@ static __device__ __forceinline__ void synth_reset_one(const SynthEnv& e, int64_
   e.t[i] = 0;
   e.len[i] = synth_len(e, env, (uint32_t)ep);
   synth_obs(e, env, (uint32_t)ep, 0u, obs + i * ldo);
+}
+
+// ---- PointEnv (envs/point_env.py:79-170) ----------------------------------------
+// numpy's fp32 arithmetic: np.clip keeps a NaN, np.linalg.norm of a 2-vector is the
+// correctly rounded sqrt of the unfused sum of the two squares, and the Python
+// scalars arena_size / done_bonus enter as fp32 (numpy's weak-scalar rule).
+struct PointEnv {
+  int64_t n;
+  float arena, bonus;   // arena_size, done_bonus
+  int never_done, max_len;
+  float* point;         // [n, 2]
+  const float* goal;    // [n, 2]
+  int32_t* t;           // [n] steps taken in the current episode
+  uint8_t* success;     // optional env_info 'success' at success[i * succ_ld + col]
+  int64_t succ_ld;
+};
+struct PointPre {
+  float px, py, gx, gy;
+  int t, ep_t;
+};
+
+static __device__ __forceinline__ float np_clip(float v, float lo, float hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+// numpy's float32 sqrt is correctly rounded; what sqrtf and __fsqrt_rn compile to
+// here (v_sqrt_f32 with exponent scaling) is within 1 ulp of it.  Step to the
+// neighbour whose product with the estimate brackets v (the correction LLVM emits
+// for a correctly rounded f32 sqrt); tiny v is scaled by 2^32 first.
+static __device__ __forceinline__ float sqrt_rn(float v) {
+  const bool tiny = v < 0x1.0p-96f;
+  const float x = tiny ? v * 0x1.0p+32f : v;
+  const float s = __builtin_sqrtf(x);
+  const float down = __int_as_float(__float_as_int(s) - 1);
+  const float up = __int_as_float(__float_as_int(s) + 1);
+  float r = s;
+  if (__builtin_fmaf(-down, s, x) <= 0.f) r = down;
+  if (__builtin_fmaf(-up, s, x) > 0.f) r = up;
+  r = tiny ? r * 0x1.0p-16f : r;
+  return (x == 0.f || __builtin_isinf(x)) ? x : r;
+}
+static __device__ __forceinline__ float norm2(float x, float y) {
+#pragma clang fp contract(off)
+  const float xx = x * x;
+  const float yy = y * y;
+  return sqrt_rn(xx + yy);
+}
+
+// reset(): point = 0, observation (0, 0, |0 - goal|)
+static __device__ __forceinline__ void env_reset_one(const PointEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const float gx = e.goal[2 * i], gy = e.goal[2 * i + 1];
+  e.point[2 * i] = 0.f;
+  e.point[2 * i + 1] = 0.f;
+  e.t[i] = 0;
+  float* o = obs + i * ldo;
+  o[0] = 0.f;
+  o[1] = 0.f;
+  o[2] = norm2(0.f - gx, 0.f - gy);
+}
+
+static __device__ __forceinline__ void env_core(const PointEnv& e, int64_t i,
+                                                const PointPre& s, const float* a,
+                                                const float*, float* next_row,
+                                                int64_t col, float* reward,
+                                                uint8_t* step_type) {
+#pragma clang fp contract(off)
+  const float ax = np_clip(a[0], -0.1f, 0.1f), ay = np_clip(a[1], -0.1f, 0.1f);
+  const float sx = s.px + ax, sy = s.py + ay;
+  const float px = np_clip(sx, -e.arena, e.arena), py = np_clip(sy, -e.arena, e.arena);
+  e.point[2 * i] = px;
+  e.point[2 * i + 1] = py;
+  const float dist = norm2(px - s.gx, py - s.gy);
+  const bool succ = dist < norm2(-0.1f, -0.1f);
+  float r = -dist;
+  if (succ) r = r + e.bonus;
+  *reward = r;
+  const bool done = succ && !e.never_done;
+  const int tn = s.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  next_row[0] = px;
+  next_row[1] = py;
+  next_row[2] = dist;
+  if (e.success) e.success[i * e.succ_ld + col] = succ ? 1 : 0;
+}
+
+// ---- GridWorldEnv (envs/grid_world_env.py:111-215) ------------------------------
+// The map is read from memory (cell codes below), never from a per-thread array.
+constexpr uint8_t GRID_FREE = 0, GRID_WALL = 1, GRID_HOLE = 2, GRID_GOAL = 3;
+struct GridEnv {
+  int64_t n;
+  int rows, cols, max_len;
+  const uint8_t* map;    // [n, rows * cols] cell codes (F and S are GRID_FREE)
+  const int32_t* start;  // [n] the S cell
+  int32_t* state;        // [n] current cell
+  int32_t* t;            // [n] steps taken in the current episode
+};
+struct GridPre {
+  int s, t, ep_t;
+};
+
+// the observation row: the one-hot of the cell (HostVecEnv._put_obs of a Discrete
+// observation space)
+static __device__ __forceinline__ void grid_one_hot(const GridEnv& e, int cell,
+                                                    float* row) {
+  const int cells = e.rows * e.cols;
+  for (int j = 0; j < cells; ++j) row[j] = j == cell ? 1.f : 0.f;
+}
+
+static __device__ __forceinline__ void env_reset_one(const GridEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const int s = e.start[i];
+  e.state[i] = s;
+  e.t[i] = 0;
+  grid_one_hot(e, s, obs + i * ldo);
+}
+
+static __device__ __forceinline__ void env_core(const GridEnv& e, int64_t i,
+                                                const GridPre& s, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  const uint8_t* m = e.map + i * (int64_t)(e.rows * e.cols);
+  const int x = s.s / e.cols, y = s.s % e.cols;
+  // increments [[0, -1], [1, 0], [0, 1], [-1, 0]] for actions 0..3, clipped to the grid
+  const int act = (int)a[0];
+  const int nx = min(max(x + (act == 1) - (act == 3), 0), e.rows - 1);
+  const int ny = min(max(y + (act == 2) - (act == 0), 0), e.cols - 1);
+  const int here = m[s.s], there = m[nx * e.cols + ny];
+  const bool stay = there == GRID_WALL || here == GRID_HOLE || here == GRID_GOAL;
+  const int next = stay ? s.s : nx * e.cols + ny;
+  const int type = stay ? here : there;
+  const bool done = type == GRID_HOLE || type == GRID_GOAL;
+  *reward = type == GRID_GOAL ? 1.f : 0.f;
+  e.state[i] = next;
+  const int tn = s.t + 1;
+  e.t[i] = tn;
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  grid_one_hot(e, next, next_row);
 }
 
 // What a step of env i reads of the env's and the worker's state: loaded up front,
@@ -360,14 +500,16 @@ struct NormParams {
 // `raw_obs` / `raw_next` are the env's own observations; seen_next is what the
 // policy sees next and what is recorded as the terminal observation -- the same
 // buffer as raw_next without normalisation.
-struct EnvStepArgs {
-  SynthEnv e;
+template <class Env>
+struct EnvStepArgsT {
+  Env e;
   RecordParams p;
   NormParams nm;
   const float* actions; int64_t lda;
   const float* raw_obs; float* raw_next; float* seen_next;
   float* reward; uint8_t* step_type;
 };
+using EnvStepArgs = EnvStepArgsT<SynthEnv>;
 
 static __device__ __forceinline__ EnvPre env_prefetch(const EnvStepArgs& a, int64_t i) {
   EnvPre s;
@@ -383,18 +525,56 @@ static __device__ __forceinline__ EnvPre env_prefetch(const EnvStepArgs& a, int6
   return s;
 }
 
+// the state a step of env i reads (env_prefetch adds the worker's ep_t)
+static __device__ __forceinline__ PointPre env_pre(const PointEnv& e, int64_t i) {
+  PointPre s;
+  s.px = e.point[2 * i];
+  s.py = e.point[2 * i + 1];
+  s.gx = e.goal[2 * i];
+  s.gy = e.goal[2 * i + 1];
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
+static __device__ __forceinline__ GridPre env_pre(const GridEnv& e, int64_t i) {
+  GridPre s;
+  s.s = e.state[i];
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
+template <class Env>
+static __device__ __forceinline__ auto env_prefetch(const EnvStepArgsT<Env>& a, int64_t i) {
+  auto s = env_pre(a.e, i);
+  s.ep_t = a.p.ep_t[i];
+  return s;
+}
+
+// the synthetic env under the names env_step_one dispatches on
+static __device__ __forceinline__ void env_core(const SynthEnv& e, int64_t i,
+                                                const EnvPre& s, const float* a,
+                                                const float* o, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  synth_step_core(e, i, s, a, o, next_row, reward, step_type);
+}
+static __device__ __forceinline__ void env_reset_one(const SynthEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  synth_reset_one(e, i, obs, ldo);
+}
+
 // `s`: env_prefetch(a, i), taken before anything of this step was stored;
-// `act_row`: the env's action (a.actions + i * a.lda, or a copy on chip).
-static __device__ __forceinline__ int env_step_one(const EnvStepArgs& a, int64_t i,
-                                                   const EnvPre& s,
-                                                   const float* act_row) {
-  const SynthEnv& e = a.e;
+// `act_row`: the env's action (a.actions + i * a.lda, or a copy on chip).  The env
+// kind is the type of `a.e`: every kernel that steps envs is instantiated per kind.
+template <class Env, class Pre>
+static __device__ __forceinline__ int env_step_one(const EnvStepArgsT<Env>& a, int64_t i,
+                                                   const Pre& s, const float* act_row) {
+  const Env& e = a.e;
   const RecordParams& p = a.p;
   const NormParams& nm = a.nm;
   float rew;
   uint8_t st;
-  synth_step_core(e, i, s, act_row, a.raw_obs + i * p.ldo, a.raw_next + i * p.ldo, &rew,
-                  &st);
+  env_core(e, i, s, act_row, a.raw_obs + i * p.ldo, a.raw_next + i * p.ldo, p.col, &rew,
+           &st);
   a.step_type[i] = st;
   if (nm.norm_obs)  // normalized_env.py:134-151: statistics first, then the value
     obs_normalize_one(a.raw_next + i * p.ldo, a.seen_next + i * p.ldo,
@@ -406,7 +586,7 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgs& a, int64_t
   a.reward[i] = rew;
   const int ended_len = record_core(p, i, s.ep_t, rew, st);
   if (ended_len > 0) {
-    synth_reset_one(e, i, a.raw_next, p.ldo);
+    env_reset_one(e, i, a.raw_next, p.ldo);
     if (nm.norm_obs)
       obs_normalize_one(a.raw_next + i * p.ldo, a.seen_next + i * p.ldo,
                         nm.obs_mean + i * p.obs_dim, nm.obs_var + i * p.obs_dim,
@@ -414,14 +594,23 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgs& a, int64_t
   }
   return ended_len;
 }
-static __device__ __forceinline__ int env_step_one(const EnvStepArgs& a, int64_t i) {
+template <class Env>
+static __device__ __forceinline__ int env_step_one(const EnvStepArgsT<Env>& a, int64_t i) {
   return env_step_one(a, i, env_prefetch(a, i), a.actions + i * a.lda);
 }
 
 }  // namespace ga_rollout
 
 // Validated conversion of the C-ABI arguments of the rollout step
-// (include/garage_amd.h) into EnvStepArgs (rollout.hip)
+// (include/garage_amd.h) into EnvStepArgsT (rollout.hip), one per env kind
 int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
                       const ga_norm_args* norm, const float* actions, int64_t lda,
                       const float* obs, const char* who, ga_rollout::EnvStepArgs* out);
+int ga_build_env_step(const ga_point_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who,
+                      ga_rollout::EnvStepArgsT<ga_rollout::PointEnv>* out);
+int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who,
+                      ga_rollout::EnvStepArgsT<ga_rollout::GridEnv>* out);

@@ -25,6 +25,7 @@ static int fused_env_step_on() {
   }
   return g_fused_env_step;
 }
+int ga_fused_env_step_enabled(void) { return fused_env_step_on(); }
 
 extern "C" int ga_rollout_synth_steps(const ga_mlp_desc* desc, const float* params,
                                       const ga_head_args* head,

@@ -13,7 +13,10 @@ a single call and keeps its state in HBM:
                               their first observation overwrites ``next_obs``
 
 ``SyntheticVecEnv`` is the benchmark workload of BASELINE.json (HIP kernels,
-Philox-keyed).  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
+Philox-keyed).  ``PointVecEnv`` and ``GridWorldVecEnv`` are the reference's own
+``PointEnv`` and ``GridWorldEnv`` as device batches (HIP kernels, numpy's fp32
+arithmetic), stepped inside the sampler's one-launch rollout like the synthetic
+env.  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
 """
@@ -73,6 +76,29 @@ class VecEnv:
 
     def close(self):
         pass
+
+    # -- device env_infos / episode_infos ------------------------------------
+    # A device batch declares the per-step ``env_info`` keys it writes on the GPU
+    # (key -> numpy dtype; bool is the one kind the kernels write, as uint8) and
+    # reports per-episode ``episode_info`` values as (n, ...) device tensors.  The
+    # worker records the former per rollout column and gathers both into the
+    # packed batch with the same indices as the observations.
+    env_info_specs = {}
+
+    def step_env_infos(self):
+        """``{key: (n,) device tensor}`` of the last :meth:`step_all`."""
+        return {}
+
+    def device_episode_infos(self):
+        """``{key: (n, ...) device tensor}``: what ``reset()`` reported for each
+        member's episode."""
+        return {}
+
+    def native_env_ref(self, info_bufs):
+        """``(ga_env_ref, keepalive)`` for ``ga_rollout_env_steps`` with the
+        per-step env_infos written into ``info_bufs`` (``{key: (n, Tcap)}``), or
+        None when the batch has no device step."""
+        return None
 
 
 class SyntheticVecEnv(VecEnv):
@@ -159,6 +185,265 @@ class SyntheticVecEnv(VecEnv):
             getattr(self, k).copy_(torch.from_numpy(v))
 
 
+def _check_finite_length(max_episode_length):
+    if max_episode_length is None or not np.isfinite(max_episode_length):
+        raise ValueError('a device env batch needs a finite max_episode_length')
+    max_episode_length = int(max_episode_length)
+    if not 1 <= max_episode_length <= 65535:
+        raise ValueError('max_episode_length must be in 1..65535')
+    return max_episode_length
+
+
+class _DeviceStateEnv(VecEnv):
+    """Pickling of a device batch: plain attributes as they are, the listed
+    state tensors through the host."""
+
+    _STATE = ()
+
+    def __getstate__(self):
+        state = {
+            k: v for k, v in self.__dict__.items()
+            if not torch.is_tensor(v) and k not in ('_c', 'device')
+        }
+        state['_saved'] = {k: getattr(self, k).cpu().numpy()
+                           for k in self._STATE + ('obs', )}
+        return state
+
+    def __setstate__(self, state):
+        saved = state.pop('_saved')
+        self.__dict__.update(state)
+        self._init_device(None)
+        for k, v in saved.items():
+            getattr(self, k).copy_(torch.from_numpy(v))
+
+
+class PointVecEnv(_DeviceStateEnv):
+    """``n_envs`` copies of ``garage.envs.PointEnv`` (``envs/point_env.py``)
+    stepped by one HIP kernel, one thread per env, in numpy's fp32 arithmetic:
+    observations, rewards, step types and ``env_info['success']`` equal the
+    reference's bit for bit.
+
+    Each member has its own goal (``goals``, an ``(n, 2)`` float32 device
+    tensor); ``set_task`` sets every member's, ``set_tasks`` one per member.
+    The per-step ``env_info['success']`` is recorded on the device and each
+    episode reports ``episode_infos['goal']``.
+
+    Deviations from the reference:
+
+    - the per-step ``env_info['task']`` dict is not reported (the goal is in
+      ``episode_infos``);
+    - ``episode_infos['goal']`` is the goal in force when the batch is packed,
+      which differs only if ``set_task`` is called mid-rollout (the sampler
+      never does);
+    - goals are held in float32, as the reference's constructor holds them
+      (its ``set_task`` keeps a float64 goal as float64);
+    - the goal check of the constructor raises ``ValueError`` instead of an
+      assertion, and ``max_episode_length`` must be finite.
+    """
+
+    env_info_specs = {'success': np.bool_}
+    _STATE = ('_point', 'goals', '_t')
+
+    def __init__(self, n_envs, goal=(1., 1.), arena_size=5., done_bonus=0.,
+                 never_done=False, max_episode_length=None, device=None):
+        self.n_envs = int(n_envs)
+        self._arena_size = float(arena_size)
+        self._done_bonus = float(done_bonus)
+        self._never_done = bool(never_done)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self._goal0 = self._check_goal(goal)
+        self.spec = EnvSpec(Box(-np.inf, np.inf, (3, )), Box(-0.1, 0.1, (2, )),
+                            max_episode_length=self.max_episode_length)
+        self._init_device(device)
+        self.goals.copy_(torch.from_numpy(np.tile(self._goal0, (self.n_envs, 1))))
+
+    def _check_goal(self, goal):
+        goal = np.array(goal, dtype=np.float32).reshape(2)
+        if not ((goal >= -self._arena_size) &
+                (goal <= self._arena_size)).all():
+            raise ValueError('goal {} lies outside the arena [-{}, {}]'.format(
+                goal, self._arena_size, self._arena_size))
+        return goal
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._point = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self.goals = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._success = torch.zeros(n, dtype=torch.uint8, device=device)
+        self._c = self._struct(self._success)
+
+    def _struct(self, success):
+        e = _lib.PointEnv()
+        e.n = self.n_envs
+        e.arena_size, e.done_bonus = self._arena_size, self._done_bonus
+        e.never_done = int(self._never_done)
+        e.max_episode_length = self.max_episode_length
+        e.point, e.goal = self._point.data_ptr(), self.goals.data_ptr()
+        e.t = self._t.data_ptr()
+        e.success = success.data_ptr()
+        return e
+
+    # -- tasks (point_env.py:172-212) -------------------------------------------
+    @staticmethod
+    def sample_tasks(num_tasks):
+        """``PointEnv.sample_tasks``: the same draw from numpy's global RNG."""
+        goals = np.random.uniform(-2, 2, size=(num_tasks, 2))
+        return [{'goal': goal} for goal in goals]
+
+    def set_task(self, task):
+        """Every member's goal <- ``task['goal']``."""
+        self.set_tasks([task] * self.n_envs)
+
+    def set_tasks(self, tasks):
+        """Member ``i``'s goal <- ``tasks[i]['goal']``."""
+        if len(tasks) != self.n_envs:
+            raise ValueError('set_tasks needs one task per env ({}), got '
+                             '{}'.format(self.n_envs, len(tasks)))
+        goals = np.stack([np.asarray(t['goal'], dtype=np.float32).reshape(2)
+                          for t in tasks])
+        self.goals.copy_(torch.from_numpy(goals))
+
+    # -- batch protocol ------------------------------------------------------------
+    def reset_all(self):
+        call('ga_point_env_reset', C.byref(self._c), None, dptr(self.obs),
+             self.obs.stride(0), stream_ptr())
+
+    def step_all(self, actions):
+        call('ga_point_env_step', C.byref(self._c), dptr(actions),
+             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
+             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
+             stream_ptr())
+
+    def reset_where(self, done):
+        call('ga_point_env_reset', C.byref(self._c), dptr(done),
+             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
+
+    def step_env_infos(self):
+        return {'success': self._success}
+
+    def device_episode_infos(self):
+        return {'goal': self.goals}
+
+    def native_env_ref(self, info_bufs):
+        e = self._struct(info_bufs['success'])
+        ref = _lib.EnvRef(kind=_lib.ENV_POINT,
+                          env=C.cast(C.pointer(e), C.c_void_p))
+        return ref, e
+
+
+# garage.envs.grid_world_env.MAPS by name ('F' / '.' free, 'S' start, 'W' / 'x'
+# wall, 'H' / 'o' hole, 'G' goal)
+GRID_MAPS = {
+    'chain': ('G' + 'F' * 13 + 'S' + 'F' * 13 + 'G', ),
+    '4x4_safe': ('SFFF', 'FWFW', 'FFFW', 'WFFG'),
+    '4x4': ('SFFF', 'FHFH', 'FFFH', 'HFFG'),
+    '8x8': ('SFFFFFFF', 'FFFFFFFF', 'FFFHFFFF', 'FFFFFHFF', 'FFFHFFFF',
+            'FHHFFFHF', 'FHFFHFHF', 'FFFHFFFG'),
+}
+_GRID_CODES = {'F': 0, '.': 0, 'S': 0, 'W': 1, 'x': 1, 'H': 2, 'o': 2, 'G': 3}
+
+
+def _grid_rows(desc):
+    """A map name or a list of row strings -> the list of rows."""
+    if isinstance(desc, str):
+        if desc not in GRID_MAPS:
+            raise ValueError('unknown grid map {!r} (known: {})'.format(
+                desc, sorted(GRID_MAPS)))
+        return list(GRID_MAPS[desc])
+    rows = [str(r) for r in desc]
+    if not rows or any(len(r) != len(rows[0]) for r in rows) or not rows[0]:
+        raise ValueError('a grid map is a non-empty list of rows of one length')
+    return rows
+
+
+class GridWorldVecEnv(_DeviceStateEnv):
+    """``n_envs`` copies of ``garage.envs.GridWorldEnv``
+    (``envs/grid_world_env.py``) stepped by one HIP kernel, one thread per env.
+
+    ``desc`` is a map name of the reference's ``MAPS``, a list of row strings,
+    or a list of one such map per env (all of one shape).  The observation row
+    is the one-hot of the cell, as a discrete observation is seen by the
+    policies.  Deviations from the reference: the device batch does not draw
+    the one ``np.random.choice(..., p=[1.])`` per step the reference draws (the
+    global numpy RNG is not consumed), and ``max_episode_length`` must be
+    finite.
+    """
+
+    _STATE = ('_state', '_t')
+
+    def __init__(self, n_envs, desc='4x4', max_episode_length=None,
+                 device=None):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        per_env = (isinstance(desc, (list, tuple)) and len(desc) > 0 and all(
+            isinstance(d, (list, tuple)) or (isinstance(d, str) and d in
+                                              GRID_MAPS) for d in desc))
+        if per_env:
+            if len(desc) != self.n_envs:
+                raise ValueError('one map per env: {} maps for {} envs'.format(
+                    len(desc), self.n_envs))
+            maps = [_grid_rows(d) for d in desc]
+        else:
+            maps = [_grid_rows(desc)] * self.n_envs
+        shape = (len(maps[0]), len(maps[0][0]))
+        codes, start = [], []
+        for rows in maps:
+            if (len(rows), len(rows[0])) != shape:
+                raise ValueError('every env map must have the shape {}'.format(
+                    shape))
+            flat = ''.join(rows)
+            bad = set(flat) - set(_GRID_CODES)
+            if bad:
+                raise ValueError('unknown grid cells {}'.format(sorted(bad)))
+            if flat.count('S') != 1:
+                raise ValueError('a grid map needs exactly one S cell')
+            codes.append([_GRID_CODES[c] for c in flat])
+            start.append(flat.index('S'))
+        self.rows, self.cols = shape
+        self._map_np = np.asarray(codes, dtype=np.uint8)
+        self._start_np = np.asarray(start, dtype=np.int32)
+        self.spec = EnvSpec(Discrete(self.rows * self.cols), Discrete(4),
+                            max_episode_length=self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._map = torch.from_numpy(self._map_np).to(device)
+        self._start = torch.from_numpy(self._start_np).to(device)
+        self._state = torch.zeros(n, dtype=torch.int32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.GridEnv()
+        e.n, e.rows, e.cols = n, self.rows, self.cols
+        e.max_episode_length = self.max_episode_length
+        e.map, e.start = self._map.data_ptr(), self._start.data_ptr()
+        e.state, e.t = self._state.data_ptr(), self._t.data_ptr()
+        self._c = e
+
+    def reset_all(self):
+        call('ga_grid_env_reset', C.byref(self._c), None, dptr(self.obs),
+             self.obs.stride(0), stream_ptr())
+
+    def step_all(self, actions):
+        call('ga_grid_env_step', C.byref(self._c), dptr(actions),
+             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
+             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
+             stream_ptr())
+
+    def reset_where(self, done):
+        call('ga_grid_env_reset', C.byref(self._c), dptr(done),
+             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
+
+    def native_env_ref(self, info_bufs):
+        ref = _lib.EnvRef(kind=_lib.ENV_GRID,
+                          env=C.cast(C.pointer(self._c), C.c_void_p))
+        return ref, self._c
+
+
 class NormalizedVecEnv(VecEnv):
     """``garage.envs.normalize`` for a device batch (``envs/normalized_env.py``).
 
@@ -233,6 +518,14 @@ class NormalizedVecEnv(VecEnv):
     def pop_finished_episode_infos(self):
         pop = getattr(self._env, 'pop_finished_episode_infos', None)
         return pop() if pop is not None else []
+
+    env_info_specs = property(lambda self: self._env.env_info_specs)
+
+    def step_env_infos(self):
+        return self._env.step_env_infos()
+
+    def device_episode_infos(self):
+        return self._env.device_episode_infos()
 
     def advance(self):
         self._env.advance()
@@ -419,4 +712,5 @@ class HostVecEnv(VecEnv):
             env.close()
 
 
-__all__ = ['VecEnv', 'SyntheticVecEnv', 'HostVecEnv', 'StepType']
+__all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
+           'GRID_MAPS', 'NormalizedVecEnv', 'HostVecEnv', 'StepType']

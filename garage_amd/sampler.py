@@ -280,6 +280,9 @@ class GpuVecWorker:
             # column -> {env index: episode_info} for the episodes that ended
             # there (CPU env batches whose resets report any)
             'ep_infos': {},
+            # per-step env_infos a device env batch writes on the GPU
+            'dev_infos': {k: torch.zeros(n, tcap, dtype=torch.uint8, device=dev)
+                          for k in env.env_info_specs},
         }
         if ldo != env.obs_dim:
             b['obs'].zero_()      # padding columns feed the GEMMs: keep them 0
@@ -323,6 +326,8 @@ class GpuVecWorker:
             call('ga_policy_head_sample', C.byref(a), s)
         env.step_all(b['action'])
         b['infos'][col] = getattr(env, 'last_env_infos', None)
+        for key, val in env.step_env_infos().items():
+            b['dev_infos'][key][:, col] = val
         r = self._record_args(b, col)
         call('ga_record_step', C.byref(r), s)
         env.reset_where(b['done'])
@@ -390,24 +395,34 @@ class GpuVecWorker:
 
     def _native_steps(self, b, col, n_steps):
         """``n_steps`` steps enqueued by ``ga_rollout_synth_steps`` (synthetic
-        env, fused policy step, device RNG); False when not applicable."""
+        env) or ``ga_rollout_env_steps`` (the other device env batches): fused
+        policy step, device RNG; False when not applicable."""
         from garage_amd.envs import NormalizedVecEnv, SyntheticVecEnv
         env = self.env
         inner, norm = env, None
         if type(env) is NormalizedVecEnv:  # statistics fused into the env step
             inner, norm = env._env, env.norm_args()
-        if (n_steps <= 0 or type(inner) is not SyntheticVecEnv
+        synth = type(inner) is SyntheticVecEnv
+        ref = None if synth else inner.native_env_ref(b['dev_infos'])
+        if (n_steps <= 0 or not (synth or ref is not None)
                 or self._noise_fn is not None or not self._fused_ok()):
             return False
         a = self._head_args(b, col, True)
         r = self._record_args(b, col)
         raw = norm is not None and norm.normalize_obs
-        call('ga_rollout_synth_steps', C.byref(self.agent.net._desc),
-             dptr(self.agent.net.params), C.byref(a), C.byref(inner._c),
-             C.byref(r), dptr(env.obs), dptr(env.next_obs),
-             None if norm is None else C.byref(norm),
-             dptr(inner.obs) if raw else None,
-             dptr(inner.next_obs) if raw else None, n_steps, stream_ptr())
+        tail = (C.byref(r), dptr(env.obs), dptr(env.next_obs),
+                None if norm is None else C.byref(norm),
+                dptr(inner.obs) if raw else None,
+                dptr(inner.next_obs) if raw else None, n_steps, stream_ptr())
+        if synth:
+            call('ga_rollout_synth_steps', C.byref(self.agent.net._desc),
+                 dptr(self.agent.net.params), C.byref(a), C.byref(inner._c),
+                 *tail)
+        else:
+            env_ref, _keepalive = ref
+            call('ga_rollout_env_steps', C.byref(self.agent.net._desc),
+                 dptr(self.agent.net.params), C.byref(a), C.byref(env_ref),
+                 *tail)
         if n_steps % 2:
             env.advance()
         self._global_step += n_steps
@@ -490,6 +505,9 @@ class GpuVecWorker:
         call('ga_gather_u8', dptr(b['st']), dptr(src), S, dptr(st), s)
         pol = self.agent
         gaussian = pol.kind == 'gaussian'
+        env_infos, episode_infos = self._device_infos(
+            b, src, ep_env, self._packed_env_infos(b, src, tcap),
+            self._packed_episode_infos(b, ep_env, ep_end))
         return DeviceEpisodeBatch(
             self.env.spec, lengths=lengths, obs_dev=obs, last_obs_dev=last,
             actions_dev=act, rewards_dev=rew, step_types_dev=st,
@@ -497,8 +515,21 @@ class GpuVecWorker:
             head_name='mean' if gaussian else 'prob',
             log_std=pol.clamped_log_std() if gaussian else None,
             discrete=is_discrete(self.env.spec.action_space),
-            env_infos=self._packed_env_infos(b, src, tcap),
-            episode_infos=self._packed_episode_infos(b, ep_env, ep_end))
+            env_infos=env_infos, episode_infos=episode_infos)
+
+    def _device_infos(self, b, src, ep_env, env_infos, episode_infos):
+        """Adds the env_infos a device env batch recorded (gathered by the
+        samples' cells ``src``) and its episode_infos (rows ``ep_env``)."""
+        S, s = int(src.numel()), stream_ptr()
+        for key, buf in b['dev_infos'].items():
+            out = torch.empty(S, dtype=torch.uint8, device=self.device)
+            if S:
+                call('ga_gather_u8', dptr(buf), dptr(src), S, dptr(out), s)
+            env_infos[key] = out.cpu().numpy().astype(
+                self.env.env_info_specs[key])
+        for key, val in self.env.device_episode_infos().items():
+            episode_infos[key] = val[ep_env.long()].cpu().numpy()
+        return env_infos, episode_infos
 
     @staticmethod
     def _packed_episode_infos(b, ep_env, ep_end):
@@ -609,6 +640,8 @@ class GpuVecWorker:
             if old[k] is not None:
                 new[k][:, :keep] = old[k][:, col - keep:col]
         new['infos'][:keep] = old['infos'][col - keep:col]
+        for k, v in old['dev_infos'].items():
+            new['dev_infos'][k][:, :keep] = v[:, col - keep:col]
         new['ep_infos'] = {c - (col - keep): v
                            for c, v in old['ep_infos'].items()
                            if c >= col - keep}
@@ -624,6 +657,8 @@ class GpuVecWorker:
         for k in ('step_eps', 'step_samples'):
             new[k][:col] = old[k][:col]
         new['infos'][:col] = old['infos'][:col]
+        for k, v in old['dev_infos'].items():
+            new['dev_infos'][k][:, :col] = v[:, :col]
         new['ep_infos'] = dict(old['ep_infos'])
         return new
 
@@ -777,6 +812,9 @@ class GpuFragmentWorker(GpuVecWorker):
         call('ga_gather_u8', dptr(b['st']), dptr(src), S, dptr(st), s)
         pol = self.agent
         gaussian = pol.kind == 'gaussian'
+        env_infos, episode_infos = self._device_infos(
+            b, src, ep_env, self._packed_env_infos(b, src, tcap),
+            self._packed_episode_infos(b, ep_env, ep_end))
         return DeviceEpisodeBatch(
             self.env.spec, lengths=length.astype(np.int64), obs_dev=obs,
             last_obs_dev=last, actions_dev=act, rewards_dev=rew,
@@ -784,8 +822,7 @@ class GpuFragmentWorker(GpuVecWorker):
             head_name='mean' if gaussian else 'prob',
             log_std=pol.clamped_log_std() if gaussian else None,
             discrete=is_discrete(self.env.spec.action_space),
-            env_infos=self._packed_env_infos(b, src, tcap),
-            episode_infos=self._packed_episode_infos(b, ep_env, ep_end))
+            env_infos=env_infos, episode_infos=episode_infos)
 
 
 class GpuVecSampler:

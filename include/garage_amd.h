@@ -521,6 +521,81 @@ GA_API int ga_rollout_synth_steps(const ga_mlp_desc* desc, const float* params,
                                   const ga_norm_args* norm, float* raw_a, float* raw_b,
                                   int64_t n_steps, ga_stream_t stream);
 
+/* ---- device copies of the reference's own environments ---------------------
+ * One thread per env, numpy's fp32 arithmetic, the same entry points as the
+ * synthetic env: reset (mask == NULL: all), step (obs is not read: the state is the
+ * env's own), and the fused step + NormalizedEnv statistics + bookkeeping + reset of
+ * the finished envs (what ga_synth_env_step_record_norm does for the synthetic
+ * env).  max_episode_length must be finite (1..65535).
+ *
+ * PointEnv (envs/point_env.py:79-170): a = clip(action, -0.1, 0.1), point =
+ * clip(point + a, -arena_size, arena_size), dist = |point - goal|, success = dist <
+ * |(-0.1, -0.1)|, reward = -dist (+ done_bonus on success), done = success and not
+ * never_done; observation (x, y, dist), obs_dim 3, act_dim 2.  `success` (optional)
+ * receives env_info['success'] as uint8: success[i] from ga_point_env_step,
+ * success[i * rec->Tcap + rec->col] from the record entries (env-major [n, Tcap],
+ * like the other rollout buffers). */
+typedef struct {
+  int64_t n;
+  float arena_size, done_bonus;
+  int32_t never_done, max_episode_length;
+  float* point;      /* [n, 2] */
+  const float* goal; /* [n, 2] */
+  int32_t* t;        /* [n] steps taken in the current episode */
+  uint8_t* success;  /* optional, see above */
+} ga_point_env;
+
+GA_API int ga_point_env_reset(const ga_point_env* env, const uint8_t* mask, float* obs,
+                              int64_t ldo, ga_stream_t stream);
+GA_API int ga_point_env_step(const ga_point_env* env, const float* actions, int64_t lda,
+                             const float* obs, float* next_obs, int64_t ldo, float* reward,
+                             uint8_t* step_type, ga_stream_t stream);
+GA_API int ga_point_env_step_record_norm(const ga_point_env* env, const ga_record_args* rec,
+                                         const ga_norm_args* norm, const float* actions,
+                                         int64_t lda, const float* obs, ga_stream_t stream);
+
+/* GridWorldEnv (envs/grid_world_env.py:111-215): `map` holds every env's grid as
+ * rows * cols cell codes (0 = F or S, 1 = W, 2 = H, 3 = G); action 0..3 = left, down,
+ * right, up, clipped to the grid; the env stays put on a wall or when already on H
+ * or G; reward 1 on G, else 0; done on H or G.  The observation is the one-hot of
+ * the cell (obs_dim = rows * cols); reset puts env i on start[i]. */
+typedef struct {
+  int64_t n;
+  int32_t rows, cols, max_episode_length, pad_;
+  const uint8_t* map;   /* [n, rows * cols] */
+  const int32_t* start; /* [n] */
+  int32_t* state;       /* [n] current cell */
+  int32_t* t;           /* [n] steps taken in the current episode */
+} ga_grid_env;
+
+GA_API int ga_grid_env_reset(const ga_grid_env* env, const uint8_t* mask, float* obs,
+                             int64_t ldo, ga_stream_t stream);
+GA_API int ga_grid_env_step(const ga_grid_env* env, const float* actions, int64_t lda,
+                            const float* obs, float* next_obs, int64_t ldo, float* reward,
+                            uint8_t* step_type, ga_stream_t stream);
+GA_API int ga_grid_env_step_record_norm(const ga_grid_env* env, const ga_record_args* rec,
+                                        const ga_norm_args* norm, const float* actions,
+                                        int64_t lda, const float* obs, ga_stream_t stream);
+
+/* Any device env: `env` points to a ga_synth_env, ga_point_env or ga_grid_env. */
+#define GA_ENV_SYNTH 0
+#define GA_ENV_POINT 1
+#define GA_ENV_GRID 2
+typedef struct {
+  int32_t kind, pad_;
+  const void* env;
+} ga_env_ref;
+
+/* ga_rollout_synth_steps for any device env (the while-loop body of VecWorker.rollout,
+ * sampler/default_worker.py:176-186 + vec_worker.py:176-204): same arguments, same
+ * buffers, same one-launch rollout where it applies (otherwise a fused policy step
+ * and an env step per rollout step). */
+GA_API int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params,
+                                const ga_head_args* head, const ga_env_ref* env,
+                                const ga_record_args* rec, float* obs_a, float* obs_b,
+                                const ga_norm_args* norm, float* raw_a, float* raw_b,
+                                int64_t n_steps, ga_stream_t stream);
+
 /* EpisodeBatch.concatenate in completion order (sampler/vec_worker.py:206-219,
  * local_sampler.py:134-166; order = (completion step, env index)). */
 GA_API int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,

@@ -1,0 +1,63 @@
+"""Env-steps per second of the one-launch rollout (ga_rollout_env_steps /
+ga_rollout_synth_steps) with PointVecEnv against SyntheticVecEnv of the same
+observation / action sizes: 4096 envs x T 256, a (256, 256) Gaussian MLP policy.
+
+    python tools/device_env_rate.py [--envs 4096] [--T 256] [--reps 5]
+
+Prints one JSON line per env: the median over `reps` rollouts of
+(env steps taken) / (wall time of rollout_samples incl. packing).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def measure(kind, n, T, reps):
+    from garage_amd.envs import PointVecEnv, SyntheticVecEnv
+    from garage_amd.policies import GaussianMLPPolicy
+    from garage_amd.sampler import GpuVecSampler, GpuVecWorker
+    torch.manual_seed(0)
+    if kind == 'point':
+        env = PointVecEnv(n, goal=(1., 1.), max_episode_length=T)
+    else:
+        env = SyntheticVecEnv(n, 3, 2, T, seed=1)
+    pol = GaussianMLPPolicy(env.spec, hidden_sizes=(256, 256), init_std=0.1)
+    s = GpuVecSampler(pol, env, max_episode_length=T, n_workers=1,
+                      worker_class=GpuVecWorker, seed=1,
+                      worker_args=dict(n_envs=n))
+    w = s._workers[0]
+    rates = []
+    for r in range(reps + 1):
+        s._update_workers(None, None)
+        torch.cuda.synchronize()
+        step0 = w._global_step
+        t0 = time.perf_counter()
+        w.rollout_samples(n * T)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if r:  # the first rollout warms up
+            rates.append(n * (w._global_step - step0) / dt)
+    return dict(env=kind, n_envs=n, T=T, hidden=[256, 256],
+                env_steps_per_s=float(np.median(rates)),
+                min=float(np.min(rates)), max=float(np.max(rates)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--envs', type=int, default=4096)
+    ap.add_argument('--T', type=int, default=256)
+    ap.add_argument('--reps', type=int, default=5)
+    a = ap.parse_args()
+    for kind in ('point', 'synthetic'):
+        print(json.dumps(measure(kind, a.envs, a.T, a.reps)))
+
+
+if __name__ == '__main__':
+    main()
