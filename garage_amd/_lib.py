@@ -44,12 +44,23 @@ class GridEnv(C.Structure):
                 ('start', ptr), ('state', ptr), ('t', ptr)]
 
 
+class MultiPointEnv(C.Structure):
+    """``ga_multi_point_env``: ``ga_point_env`` plus the task layer."""
+    _fields_ = PointEnv._fields_ + [
+        ('num_tasks', c_i32), ('strategy', c_i32), ('mode', c_i32),
+        ('pad_', c_i32), ('seed', c_u64), ('task_goals', ptr),
+        ('last_task', ptr), ('resets', ptr), ('task_id', ptr)]
+
+
 class EnvRef(C.Structure):
-    """``ga_env_ref``: kind ``ENV_SYNTH`` / ``ENV_POINT`` / ``ENV_GRID``."""
+    """``ga_env_ref``: kind ``ENV_SYNTH`` / ``ENV_POINT`` / ``ENV_GRID`` /
+    ``ENV_MULTI_POINT``."""
     _fields_ = [('kind', c_i32), ('pad_', c_i32), ('env', ptr)]
 
 
-ENV_SYNTH, ENV_POINT, ENV_GRID = 0, 1, 2
+ENV_SYNTH, ENV_POINT, ENV_GRID, ENV_MULTI_POINT = 0, 1, 2, 3
+TASK_ROUND_ROBIN, TASK_UNIFORM_RANDOM = 0, 1
+TASK_VANILLA, TASK_ADD_ONEHOT = 0, 1
 
 
 class HeadArgs(C.Structure):
@@ -247,6 +258,14 @@ SIGNATURES = {
                                              C.POINTER(RecordArgs),
                                              C.POINTER(NormArgs), ptr, c_i64,
                                              ptr, ptr]),
+    'ga_multi_point_env_reset': (c_int, [C.POINTER(MultiPointEnv), ptr, ptr,
+                                         c_i64, ptr]),
+    'ga_multi_point_env_step': (c_int, [C.POINTER(MultiPointEnv), ptr, c_i64,
+                                        ptr, ptr, c_i64, ptr, ptr, ptr]),
+    'ga_multi_point_env_step_record_norm': (c_int, [
+        C.POINTER(MultiPointEnv), C.POINTER(RecordArgs), C.POINTER(NormArgs),
+        ptr, c_i64, ptr, ptr]),
+    'ga_multi_env_task_draw': (c_int, [c_u64, c_i64, c_u32, c_int]),
     'ga_rollout_env_steps': (c_int, [C.POINTER(MlpDesc), ptr,
                                      C.POINTER(HeadArgs), C.POINTER(EnvRef),
                                      C.POINTER(RecordArgs), ptr, ptr,

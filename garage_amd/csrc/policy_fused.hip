@@ -16,8 +16,8 @@
 // the narrow output layer is a 16-lane VALU dot product, and the head (Gaussian:
 // mean + std * noise; categorical: inverse CDF) writes the action and the rollout
 // buffers.  Hidden widths up to 256 (C2, C3); wider nets use the per-layer path.
-// With a device env (synthetic, PointEnv, GridWorldEnv: a template parameter of the
-// kernel) the thread that sampled an env's action also steps it, and a whole
+// With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv:
+// a template parameter of the kernel) the thread that sampled an env's action also steps it, and a whole
 // rollout is ONE launch with the weights resident on the CU (see the kernel).
 #include "common.h"
 #include "prof.h"
@@ -705,6 +705,8 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* param
 ga_rollout::EnvStepArgs env_args_of(const ga_synth_env*);
 ga_rollout::EnvStepArgsT<ga_rollout::PointEnv> env_args_of(const ga_point_env*);
 ga_rollout::EnvStepArgsT<ga_rollout::GridEnv> env_args_of(const ga_grid_env*);
+ga_rollout::EnvStepArgsT<ga_rollout::MultiTaskEnv<ga_rollout::PointEnv>> env_args_of(
+    const ga_multi_point_env*);
 
 template <class GaEnv>
 static int policy_env_step_fused(const ga_mlp_desc* d, const float* params,
@@ -753,6 +755,9 @@ int ga_policy_env_step_fused_ref(const ga_mlp_desc* d, const float* params,
     case GA_ENV_GRID:
       return policy_env_step_fused(d, params, a, (const ga_grid_env*)env->env, rec, norm,
                                    n_steps, stream);
+    case GA_ENV_MULTI_POINT:
+      return policy_env_step_fused(d, params, a, (const ga_multi_point_env*)env->env, rec,
+                                   norm, n_steps, stream);
   }
   ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
   return -1;

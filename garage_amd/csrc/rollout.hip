@@ -1,5 +1,6 @@
 // Rollout-side kernels: action sampling heads, the device environments
-// (synthetic, PointEnv, GridWorldEnv), per-step episode bookkeeping and the
+// (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv), per-step
+// episode bookkeeping and the
 // ragged -> packed compaction.
 //
 // Together they replace the Python per-env loop of VecWorker.step_episode /
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void synth_step_kernel(
   synth_step_one(e, i, actions, lda, obs, next_obs, ldo, reward, step_type);
 }
 
-// reset / step of a PointEnv or GridWorldEnv batch (rollout_dev.h)
+// reset / step of a PointEnv, GridWorldEnv or multi-task PointEnv batch (rollout_dev.h)
 template <class Env>
 __global__ __launch_bounds__(256) void env_reset_kernel(Env e, const uint8_t* mask,
                                                         float* obs, int64_t ldo) {
@@ -517,10 +518,50 @@ static int check_env(const ga_grid_env* e, const char* who) {
   return GA_OK;
 }
 
+// the PointEnv part of a multi-task batch; info_ld as succ_ld above
+static ga_point_env point_part(const ga_multi_point_env* e) {
+  ga_point_env p;
+  p.n = e->n; p.arena_size = e->arena_size; p.done_bonus = e->done_bonus;
+  p.never_done = e->never_done; p.max_episode_length = e->max_episode_length;
+  p.point = e->point; p.goal = e->goal; p.t = e->t; p.success = e->success;
+  return p;
+}
+
+static MultiTaskEnv<PointEnv> to_dev(const ga_multi_point_env* e, int64_t info_ld) {
+  MultiTaskEnv<PointEnv> d;
+  const ga_point_env p = point_part(e);
+  d.n = e->n; d.in = to_dev(&p, info_ld);
+  d.num_tasks = e->num_tasks; d.strategy = e->strategy;
+  d.one_hot = e->mode == GA_TASK_ADD_ONEHOT;
+  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  d.payload = e->task_goals; d.last_task = e->last_task; d.resets = e->resets;
+  d.task_id = e->task_id; d.info_ld = info_ld;
+  return d;
+}
+
+static int check_env(const ga_multi_point_env* e, const char* who) {
+  GA_REQUIRE(e && e->point && e->goal && e->t && e->task_goals && e->last_task &&
+                 e->resets, "%s: null env state", who);
+  const ga_point_env p = point_part(e);
+  int rc = check_env(&p, who);
+  if (rc) return rc;
+  GA_REQUIRE(e->num_tasks >= 1 && e->num_tasks <= 256,
+             "%s: num_tasks must be in 1..256 (got %d)", who, e->num_tasks);
+  GA_REQUIRE(e->strategy == GA_TASK_ROUND_ROBIN || e->strategy == GA_TASK_UNIFORM_RANDOM,
+             "%s: unknown sample strategy %d", who, e->strategy);
+  GA_REQUIRE(e->mode == GA_TASK_VANILLA || e->mode == GA_TASK_ADD_ONEHOT,
+             "%s: unknown mode %d", who, e->mode);
+  return GA_OK;
+}
+
 static int env_obs_dim(const ga_point_env*) { return 3; }
 static int env_obs_dim(const ga_grid_env* e) { return e->rows * e->cols; }
+static int env_obs_dim(const ga_multi_point_env* e) {
+  return 3 + (e->mode == GA_TASK_ADD_ONEHOT ? e->num_tasks : 0);
+}
 static int env_act_width(const ga_point_env*) { return 2; }
 static int env_act_width(const ga_grid_env*) { return 1; }
+static int env_act_width(const ga_multi_point_env*) { return 2; }
 
 int ga_build_env_step(const ga_point_env* env, const ga_record_args* a,
                       const ga_norm_args* norm, const float* actions, int64_t lda,
@@ -542,7 +583,24 @@ int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
                         who, out);
 }
 
+int ga_build_env_step(const ga_multi_point_env* env, const ga_record_args* a,
+                      const ga_norm_args* norm, const float* actions, int64_t lda,
+                      const float* obs, const char* who,
+                      ga_rollout::EnvStepArgsT<MultiTaskEnv<PointEnv>>* out) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  GA_REQUIRE(a, "%s: null pointer", who);
+  GA_REQUIRE(a->ldo >= env_obs_dim(env),
+             "%s: observation rows of %lld columns are narrower than 3 + num_tasks = %d",
+             who, (long long)a->ldo, env_obs_dim(env));
+  return build_env_step(to_dev(env, a->Tcap), env_obs_dim(env), 2, a, norm, actions, lda,
+                        obs, who, out);
+}
+
 static PointEnv to_dev_step(const ga_point_env* e) { return to_dev(e, 1); }
+static MultiTaskEnv<PointEnv> to_dev_step(const ga_multi_point_env* e) {
+  return to_dev(e, 1);
+}
 static GridEnv to_dev_step(const ga_grid_env* e) { return to_dev(e); }
 
 template <class GaEnv>
@@ -611,6 +669,35 @@ extern "C" int ga_point_env_step_record_norm(const ga_point_env* env,
                          "ga_point_env_step_record_norm");
 }
 
+// envs/multi_env_wrapper.py:169-194 (reset), :196-226 (step) over PointEnv
+extern "C" int ga_multi_point_env_reset(const ga_multi_point_env* env, const uint8_t* mask,
+                                        float* obs, int64_t ldo, ga_stream_t stream) {
+  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_multi_point_env_reset");
+}
+extern "C" int ga_multi_point_env_step(const ga_multi_point_env* env, const float* actions,
+                                       int64_t lda, const float*, float* next_obs,
+                                       int64_t ldo, float* reward, uint8_t* step_type,
+                                       ga_stream_t stream) {
+  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
+                  (hipStream_t)stream, "ga_multi_point_env_step");
+}
+extern "C" int ga_multi_point_env_step_record_norm(const ga_multi_point_env* env,
+                                                   const ga_record_args* rec,
+                                                   const ga_norm_args* norm,
+                                                   const float* actions, int64_t lda,
+                                                   const float* obs, ga_stream_t stream) {
+  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
+                         "ga_multi_point_env_step_record_norm");
+}
+// the device's task_draw on the host (tests compare it with a numpy restatement)
+extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                      int num_tasks) {
+  GA_REQUIRE(num_tasks >= 1 && num_tasks <= 256,
+             "ga_multi_env_task_draw: num_tasks must be in 1..256 (got %d)", num_tasks);
+  return task_draw((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
+                   (uint32_t)env_id, counter, num_tasks);
+}
+
 // envs/grid_world_env.py:91-109 (reset), :111-215 (step)
 extern "C" int ga_grid_env_reset(const ga_grid_env* env, const uint8_t* mask, float* obs,
                                  int64_t ldo, ga_stream_t stream) {
@@ -647,6 +734,9 @@ int ga_env_step_record_ref(const ga_env_ref* env, const ga_record_args* rec,
     case GA_ENV_GRID:
       return ga_grid_env_step_record_norm((const ga_grid_env*)env->env, rec, norm,
                                           actions, lda, obs, stream);
+    case GA_ENV_MULTI_POINT:
+      return ga_multi_point_env_step_record_norm((const ga_multi_point_env*)env->env, rec,
+                                                 norm, actions, lda, obs, stream);
   }
   ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
   return -1;

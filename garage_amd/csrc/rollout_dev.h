@@ -1,7 +1,7 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
 // policy + env step of policy_fused.hip: Philox, action sampling, the device
-// environments (synthetic, PointEnv, GridWorldEnv), the NormalizedEnv statistics,
-// the per-step bookkeeping of VecWorker.step_episode (sampler/vec_worker.py:176-204).
+// environments (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv),
+// the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode (sampler/vec_worker.py:176-204).
 // One thread owns one env.
 #pragma once
 #include "common.h"
@@ -11,7 +11,7 @@ namespace ga_rollout {
 // ---- Philox4x32-10 (Random123; Salmon et al. SC'11) --------------------------
 struct U4 { uint32_t x, y, z, w; };
 
-static __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
+static __host__ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
                                             uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -46,6 +46,7 @@ static __device__ __forceinline__ float u32_unit_interval(uint32_t u) {
 
 static constexpr uint32_t STREAM_OBS = 0, STREAM_REWARD = 1, STREAM_LENGTH = 2;
 static constexpr uint32_t STREAM_ACTION = 3;
+static constexpr uint32_t STREAM_TASK = 4;
 
 // ---- action sampling (the rollout head kernels and the fused policy + env step) ----
 static __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
@@ -248,6 +249,89 @@ static __device__ __forceinline__ void env_core(const PointEnv& e, int64_t i,
   next_row[1] = py;
   next_row[2] = dist;
   if (e.success) e.success[i * e.succ_ld + col] = succ ? 1 : 0;
+}
+
+// ---- MultiEnvWrapper (envs/multi_env_wrapper.py:169-226) over an inner env ------
+// Every member is its own wrapper over the K task envs, which differ by a task
+// payload only (PointEnv: the goal): reset() picks the next task from the member's
+// own last one, copies the task's payload into the member's state and resets the
+// inner env; with one_hot the K columns after the inner observation hold the
+// one-hot of the active task, on reset and on every step.  An inner env joins by
+// defining env_inner_obs_dim and env_apply_task.
+constexpr int TASK_ROUND_ROBIN = 0, TASK_UNIFORM_RANDOM = 1;
+template <class Inner>
+struct MultiTaskEnv {
+  int64_t n;
+  Inner in;
+  int num_tasks, strategy, one_hot;
+  uint32_t k0, k1;        // seed of the uniform_random_strategy stream
+  const float* payload;   // [num_tasks, ...] what env_apply_task copies from
+  int32_t* last_task;     // [n] the active task (-1: no reset yet)
+  uint32_t* resets;       // [n] resets so far (the random stream's counter)
+  uint8_t* task_id;       // optional env_info 'task_id' at task_id[i * info_ld + col]
+  int64_t info_ld;
+};
+template <class InnerPre>
+struct MultiTaskPre {
+  InnerPre in;
+  int task, ep_t;
+};
+
+static __device__ __forceinline__ int env_inner_obs_dim(const PointEnv&) { return 3; }
+// the member becomes PointEnv(goal=task_goals[task]); goal is the member's own row
+static __device__ __forceinline__ void env_apply_task(const PointEnv& e, int64_t i,
+                                                      const float* task_goals, int task) {
+  float* g = const_cast<float*>(e.goal) + 2 * i;
+  g[0] = task_goals[2 * task];
+  g[1] = task_goals[2 * task + 1];
+}
+
+// uniform_random_strategy: the reference draws random.randint(0, K - 1) from Python's
+// global generator; here reset number `counter` of env `env` takes the first word of
+// its own Philox block and scales it to [0, K) by the high half of u * K (a task's
+// probability is off from 1 / K by less than K / 2^32).
+static __host__ __device__ __forceinline__ int task_draw(uint32_t k0, uint32_t k1,
+                                                         uint32_t env, uint32_t counter,
+                                                         int num_tasks) {
+  const U4 r = philox4x32_10(env, counter, 0u, STREAM_TASK << 16, k0, k1);
+  return (int)(((uint64_t)r.x * (uint64_t)(uint32_t)num_tasks) >> 32);
+}
+
+template <class Inner>
+static __device__ __forceinline__ void task_one_hot(const MultiTaskEnv<Inner>& e, int task,
+                                                    float* row) {
+  if (!e.one_hot) return;
+  float* h = row + env_inner_obs_dim(e.in);
+  for (int j = 0; j < e.num_tasks; ++j) h[j] = j == task ? 1.f : 0.f;
+}
+
+template <class Inner>
+static __device__ __forceinline__ void env_reset_one(const MultiTaskEnv<Inner>& e,
+                                                     int64_t i, float* obs, int64_t ldo) {
+  const int last = e.last_task[i];
+  const uint32_t cnt = e.resets[i];
+  // round_robin_strategy: 0 after None, else (last + 1) % K
+  const int task = e.strategy == TASK_UNIFORM_RANDOM
+                       ? task_draw(e.k0, e.k1, (uint32_t)i, cnt, e.num_tasks)
+                       : (last < 0 ? 0 : (last + 1) % e.num_tasks);
+  e.last_task[i] = task;
+  e.resets[i] = cnt + 1u;
+  env_apply_task(e.in, i, e.payload, task);
+  env_reset_one(e.in, i, obs, ldo);
+  task_one_hot(e, task, obs + i * ldo);
+}
+
+// the step's observation and env_info carry the task of the episode the step
+// belongs to: env_step_one records the last observation before it resets the env
+template <class Inner, class InnerPre>
+static __device__ __forceinline__ void env_core(const MultiTaskEnv<Inner>& e, int64_t i,
+                                                const MultiTaskPre<InnerPre>& s,
+                                                const float* a, const float* o,
+                                                float* next_row, int64_t col,
+                                                float* reward, uint8_t* step_type) {
+  env_core(e.in, i, s.in, a, o, next_row, col, reward, step_type);
+  task_one_hot(e, s.task, next_row);
+  if (e.task_id) e.task_id[i * e.info_ld + col] = (uint8_t)s.task;
 }
 
 // ---- GridWorldEnv (envs/grid_world_env.py:111-215) ------------------------------
@@ -543,6 +627,14 @@ static __device__ __forceinline__ GridPre env_pre(const GridEnv& e, int64_t i) {
   s.ep_t = 0;
   return s;
 }
+template <class Inner>
+static __device__ __forceinline__ auto env_pre(const MultiTaskEnv<Inner>& e, int64_t i) {
+  MultiTaskPre<decltype(env_pre(e.in, i))> s;
+  s.in = env_pre(e.in, i);
+  s.task = e.last_task[i];
+  s.ep_t = 0;
+  return s;
+}
 template <class Env>
 static __device__ __forceinline__ auto env_prefetch(const EnvStepArgsT<Env>& a, int64_t i) {
   auto s = env_pre(a.e, i);
@@ -614,3 +706,7 @@ int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
                       const ga_norm_args* norm, const float* actions, int64_t lda,
                       const float* obs, const char* who,
                       ga_rollout::EnvStepArgsT<ga_rollout::GridEnv>* out);
+int ga_build_env_step(
+    const ga_multi_point_env* env, const ga_record_args* a, const ga_norm_args* norm,
+    const float* actions, int64_t lda, const float* obs, const char* who,
+    ga_rollout::EnvStepArgsT<ga_rollout::MultiTaskEnv<ga_rollout::PointEnv>>* out);

@@ -32,6 +32,9 @@ int env_shape(const ga_env_ref* env, EnvShape* out) {
     case GA_ENV_GRID:
       *out = EnvShape{((const ga_grid_env*)env->env)->n, 1, 1};
       return 0;
+    case GA_ENV_MULTI_POINT:
+      *out = EnvShape{((const ga_multi_point_env*)env->env)->n, 2, 0};
+      return 0;
   }
   ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
   return -1;

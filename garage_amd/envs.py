@@ -16,7 +16,8 @@ a single call and keeps its state in HBM:
 Philox-keyed).  ``PointVecEnv`` and ``GridWorldVecEnv`` are the reference's own
 ``PointEnv`` and ``GridWorldEnv`` as device batches (HIP kernels, numpy's fp32
 arithmetic), stepped inside the sampler's one-launch rollout like the synthetic
-env.  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
+env; ``MultiTaskPointVecEnv`` is ``MultiEnvWrapper`` over ``PointEnv`` tasks, the
+task switch at every reset included.  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
 """
@@ -93,6 +94,20 @@ class VecEnv:
         """``{key: (n, ...) device tensor}``: what ``reset()`` reported for each
         member's episode."""
         return {}
+
+    def finish_env_infos(self, env_infos):
+        """Adds, in place, the ``env_info`` keys that are made on the host from
+        the gathered ``(S,)`` arrays of the recorded ones (a batch that reports
+        such a key says so here; nothing by default)."""
+
+    def episode_infos_of(self, ep_env, info_at_end):
+        """``{key: (N, ...) array}``: the ``episode_info`` of each packed
+        episode, given its member index (``ep_env``, an ``(N,)`` device tensor);
+        ``info_at_end(key)`` gathers the recorded env_info ``key`` of each
+        episode's last step as an ``(N,)`` array.  By default the member's row
+        of :meth:`device_episode_infos`."""
+        return {k: v[ep_env.long()].cpu().numpy()
+                for k, v in self.device_episode_infos().items()}
 
     def native_env_ref(self, info_bufs):
         """``(ga_env_ref, keepalive)`` for ``ga_rollout_env_steps`` with the
@@ -234,7 +249,8 @@ class PointVecEnv(_DeviceStateEnv):
       ``episode_infos``);
     - ``episode_infos['goal']`` is the goal in force when the batch is packed,
       which differs only if ``set_task`` is called mid-rollout (the sampler
-      never does);
+      never does; :class:`MultiTaskPointVecEnv`, whose goals change at every
+      reset, reports each episode's own);
     - goals are held in float32, as the reference's constructor holds them
       (its ``set_task`` keeps a float64 goal as float64);
     - the goal check of the constructor raises ``ValueError`` instead of an
@@ -330,6 +346,216 @@ class PointVecEnv(_DeviceStateEnv):
     def native_env_ref(self, info_bufs):
         e = self._struct(info_bufs['success'])
         ref = _lib.EnvRef(kind=_lib.ENV_POINT,
+                          env=C.cast(C.pointer(e), C.c_void_p))
+        return ref, e
+
+
+def round_robin_strategy(num_tasks, last_task=None):
+    """``garage.envs.multi_env_wrapper.round_robin_strategy``: task 0 first,
+    then ``(last_task + 1) % num_tasks``.  :class:`MultiTaskPointVecEnv`
+    recognises the function and runs the rule on the device."""
+    if last_task is None:
+        return 0
+    return (last_task + 1) % num_tasks
+
+
+def uniform_random_strategy(num_tasks, _):
+    """``garage.envs.multi_env_wrapper.uniform_random_strategy``.  Called on
+    the host it draws from Python's ``random`` like the reference;
+    :class:`MultiTaskPointVecEnv` recognises the function and draws on the
+    device from its own Philox stream instead (see there)."""
+    import random
+    return random.randint(0, num_tasks - 1)
+
+
+_STRATEGIES = {round_robin_strategy: _lib.TASK_ROUND_ROBIN,
+               uniform_random_strategy: _lib.TASK_UNIFORM_RANDOM}
+MAX_TASKS = 256  # env_info['task_id'] is recorded as uint8 on the device
+
+
+def task_draw(seed, env_id, counter, num_tasks):
+    """The task :class:`MultiTaskPointVecEnv`'s uniform random strategy gives
+    member ``env_id`` at its reset number ``counter`` (host only, no GPU)."""
+    task = _lib.load().ga_multi_env_task_draw(int(seed), int(env_id),
+                                              int(counter), int(num_tasks))
+    if task < 0:
+        raise ValueError('num_tasks must be in 1..{}'.format(MAX_TASKS))
+    return task
+
+
+class MultiTaskPointVecEnv(_DeviceStateEnv):
+    """``n_envs`` copies of ``MultiEnvWrapper([PointEnv(goal=g, ...) for g in
+    goals], sample_strategy, mode, env_names)`` (``envs/multi_env_wrapper.py``)
+    stepped by one HIP kernel inside the one-launch rollout.
+
+    Every member keeps its own active task, as the reference ``VecWorker``'s
+    deep-copied wrappers do: each reset -- ``reset_all``, ``reset_where`` and
+    the reset of a finished member inside the rollout kernels -- picks the
+    member's next task, and the member's PointEnv gets that task's goal.  With
+    ``mode='add-onehot'`` the observation is the PointEnv's ``(x, y, dist)``
+    followed by the one-hot of the active task (``spec.observation_space`` is
+    the ``(3 + K,)`` Box); ``mode='vanilla'`` leaves it as it is.  Every step
+    reports ``env_info['task_id']`` (int64) and, with ``env_names``,
+    ``env_info['task_name']`` next to ``success``; each episode reports
+    ``episode_infos['goal']``, the goal of the task *that episode* ran.
+    Round robin equals the reference bit for bit.
+
+    ``start='same'`` is one wrapper deep-copied ``n_envs`` times (every member
+    begins with task 0); ``start='spread'`` lets member ``i`` begin with task
+    ``i % K`` (the reference given ``n_envs`` wrappers whose
+    ``_active_task_index`` is preset), so that a batch covers all tasks from
+    its first step.  It has no effect on ``uniform_random_strategy``.
+
+    Limits and deviations from the reference:
+
+    - ``uniform_random_strategy`` does not consume Python's global ``random``:
+      reset number ``c`` of member ``i`` takes the first word ``u`` of
+      Philox4x32-10 keyed ``(seed; i, c)`` on its own stream and runs task
+      ``(u * K) >> 32`` (:func:`task_draw` gives the same number on the host);
+    - the tasks share ``arena_size``, ``done_bonus``, ``never_done`` and
+      ``max_episode_length``; only the goal differs;
+    - ``task_id`` is held as uint8 on the device: at most 256 tasks.  The
+      one-launch rollout with resident weights needs ``3 + K <= 32``; the
+      fused policy step takes rows up to 256 wide, wider ones the per-layer
+      path, like any other observation;
+    - a sample strategy other than the two above raises
+      ``NotImplementedError`` (an arbitrary Python callable cannot run in the
+      kernel); ``mode='del-onehot'`` raises ``ValueError``: a PointEnv
+      observation has no one-hot to delete;
+    - no per-step ``env_info['task']`` dict, as for :class:`PointVecEnv`;
+      ``active_task_index`` is an ``(n_envs,)`` array (-1 before the first
+      reset, where the reference has ``None``).
+    """
+
+    _STATE = ('_point', '_goal', '_t', '_last_task', '_resets')
+
+    def __init__(self, n_envs, goals, sample_strategy=uniform_random_strategy,
+                 mode='add-onehot', env_names=None, start='same', seed=0,
+                 arena_size=5., done_bonus=0., never_done=False,
+                 max_episode_length=None, device=None):
+        self.n_envs = int(n_envs)
+        self._arena_size = float(arena_size)
+        self._done_bonus = float(done_bonus)
+        self._never_done = bool(never_done)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        goals = np.asarray(goals, dtype=np.float32)
+        if goals.ndim != 2 or goals.shape[1] != 2 or not len(goals):
+            raise ValueError('goals must be a non-empty (K, 2) array, one '
+                             'goal per task')
+        if len(goals) > MAX_TASKS:
+            raise ValueError('at most {} tasks (task_id is a uint8 on the '
+                             'device), got {}'.format(MAX_TASKS, len(goals)))
+        self._goals_np = np.stack(
+            [PointVecEnv._check_goal(self, g) for g in goals])
+        known = [v for f, v in _STRATEGIES.items() if f is sample_strategy]
+        if not known:
+            raise NotImplementedError(
+                'sample_strategy {!r} cannot run on the device: use '
+                'garage_amd.envs.round_robin_strategy or '
+                'uniform_random_strategy'.format(sample_strategy))
+        self._strategy = known[0]
+        if mode == 'del-onehot':
+            raise ValueError("mode 'del-onehot' has nothing to delete from a "
+                             'PointEnv observation')
+        if mode not in ('vanilla', 'add-onehot'):
+            raise ValueError("mode must be 'vanilla' or 'add-onehot', got "
+                             '{!r}'.format(mode))
+        self._mode = mode
+        if env_names is not None:
+            if not isinstance(env_names, list):
+                raise ValueError('env_names must be a list')
+            if len(set(env_names)) != len(goals):
+                raise ValueError('env_names are not unique or there is not an '
+                                 'env_name corresponding to each task')
+        self._env_names = env_names
+        if start not in ('same', 'spread'):
+            raise ValueError("start must be 'same' or 'spread', got "
+                             '{!r}'.format(start))
+        self._start = start
+        self.seed = int(seed)
+        K = self.num_tasks
+        low = np.concatenate([np.full(3, -np.inf), np.zeros(K)])
+        high = np.concatenate([np.full(3, np.inf), np.ones(K)])
+        obs_space = (Box(low, high) if mode == 'add-onehot' else
+                     Box(-np.inf, np.inf, (3, )))
+        self.spec = EnvSpec(obs_space, Box(-0.1, 0.1, (2, )),
+                            max_episode_length=self.max_episode_length)
+        self.env_info_specs = {'success': np.bool_, 'task_id': np.int64}
+        self._init_device(device)
+        if start == 'spread':  # the task before member i's first one
+            self._last_task.copy_(torch.arange(self.n_envs) % K - 1)
+
+    num_tasks = property(lambda self: len(self._goals_np))
+
+    @property
+    def task_space(self):
+        return Box(np.zeros(self.num_tasks), np.ones(self.num_tasks))
+
+    @property
+    def active_task_index(self):
+        return self._last_task.cpu().numpy().astype(np.int64)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._point = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self._goal = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._task_goals = torch.from_numpy(self._goals_np).to(device)
+        self._last_task = torch.full((n, ), -1, dtype=torch.int32,
+                                     device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        self._success = torch.zeros(n, dtype=torch.uint8, device=device)
+        self._task_id = torch.zeros(n, dtype=torch.uint8, device=device)
+        self._c = self._struct(self._success, self._task_id)
+
+    def _struct(self, success, task_id):
+        e = _lib.MultiPointEnv()
+        e.n = self.n_envs
+        e.arena_size, e.done_bonus = self._arena_size, self._done_bonus
+        e.never_done = int(self._never_done)
+        e.max_episode_length = self.max_episode_length
+        e.point, e.goal = self._point.data_ptr(), self._goal.data_ptr()
+        e.t = self._t.data_ptr()
+        e.success, e.task_id = success.data_ptr(), task_id.data_ptr()
+        e.num_tasks, e.strategy = self.num_tasks, self._strategy
+        e.mode = (_lib.TASK_ADD_ONEHOT if self._mode == 'add-onehot' else
+                  _lib.TASK_VANILLA)
+        e.seed = self.seed
+        e.task_goals = self._task_goals.data_ptr()
+        e.last_task = self._last_task.data_ptr()
+        e.resets = self._resets.data_ptr()
+        return e
+
+    def reset_all(self):
+        call('ga_multi_point_env_reset', C.byref(self._c), None,
+             dptr(self.obs), self.obs.stride(0), stream_ptr())
+
+    def step_all(self, actions):
+        call('ga_multi_point_env_step', C.byref(self._c), dptr(actions),
+             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
+             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
+             stream_ptr())
+
+    def reset_where(self, done):
+        call('ga_multi_point_env_reset', C.byref(self._c), dptr(done),
+             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
+
+    def step_env_infos(self):
+        return {'success': self._success, 'task_id': self._task_id}
+
+    def finish_env_infos(self, env_infos):
+        if self._env_names is not None:
+            env_infos['task_name'] = np.asarray(
+                self._env_names)[env_infos['task_id']]
+
+    def episode_infos_of(self, ep_env, info_at_end):
+        return {'goal': self._goals_np[info_at_end('task_id')]}
+
+    def native_env_ref(self, info_bufs):
+        e = self._struct(info_bufs['success'], info_bufs['task_id'])
+        ref = _lib.EnvRef(kind=_lib.ENV_MULTI_POINT,
                           env=C.cast(C.pointer(e), C.c_void_p))
         return ref, e
 
@@ -527,6 +753,12 @@ class NormalizedVecEnv(VecEnv):
     def device_episode_infos(self):
         return self._env.device_episode_infos()
 
+    def finish_env_infos(self, env_infos):
+        self._env.finish_env_infos(env_infos)
+
+    def episode_infos_of(self, ep_env, info_at_end):
+        return self._env.episode_infos_of(ep_env, info_at_end)
+
     def advance(self):
         self._env.advance()
         if self._normalize_obs:
@@ -713,4 +945,6 @@ class HostVecEnv(VecEnv):
 
 
 __all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
-           'GRID_MAPS', 'NormalizedVecEnv', 'HostVecEnv', 'StepType']
+           'MultiTaskPointVecEnv', 'round_robin_strategy',
+           'uniform_random_strategy', 'task_draw', 'GRID_MAPS',
+           'NormalizedVecEnv', 'HostVecEnv', 'StepType']

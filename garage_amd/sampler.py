@@ -506,7 +506,7 @@ class GpuVecWorker:
         pol = self.agent
         gaussian = pol.kind == 'gaussian'
         env_infos, episode_infos = self._device_infos(
-            b, src, ep_env, self._packed_env_infos(b, src, tcap),
+            b, src, ep_env, ep_end, self._packed_env_infos(b, src, tcap),
             self._packed_episode_infos(b, ep_env, ep_end))
         return DeviceEpisodeBatch(
             self.env.spec, lengths=lengths, obs_dev=obs, last_obs_dev=last,
@@ -517,18 +517,31 @@ class GpuVecWorker:
             discrete=is_discrete(self.env.spec.action_space),
             env_infos=env_infos, episode_infos=episode_infos)
 
-    def _device_infos(self, b, src, ep_env, env_infos, episode_infos):
+    def _device_infos(self, b, src, ep_env, ep_end, env_infos, episode_infos):
         """Adds the env_infos a device env batch recorded (gathered by the
-        samples' cells ``src``) and its episode_infos (rows ``ep_env``)."""
-        S, s = int(src.numel()), stream_ptr()
-        for key, buf in b['dev_infos'].items():
-            out = torch.empty(S, dtype=torch.uint8, device=self.device)
-            if S:
-                call('ga_gather_u8', dptr(buf), dptr(src), S, dptr(out), s)
-            env_infos[key] = out.cpu().numpy().astype(
-                self.env.env_info_specs[key])
-        for key, val in self.env.device_episode_infos().items():
-            episode_infos[key] = val[ep_env.long()].cpu().numpy()
+        samples' cells ``src``), the keys the batch derives from them on the
+        host, and its episode_infos (by member ``ep_env``; a batch may ask for
+        a recorded env_info at each episode's or fragment's last cell
+        ``(ep_env, ep_end)``, gathered only then)."""
+        specs, s = self.env.env_info_specs, stream_ptr()
+
+        def gather(key, idx):
+            count = int(idx.numel())
+            out = torch.empty(count, dtype=torch.uint8, device=self.device)
+            if count:
+                call('ga_gather_u8', dptr(b['dev_infos'][key]), dptr(idx),
+                     count, dptr(out), s)
+            return out.cpu().numpy().astype(specs[key])
+
+        def info_at_end(key):
+            cell = (ep_env.long() * b['Tcap'] + ep_end.long()).to(torch.int32)
+            return gather(key, cell)
+
+        for key in b['dev_infos']:
+            env_infos[key] = gather(key, src)
+        if b['dev_infos']:
+            self.env.finish_env_infos(env_infos)
+        episode_infos.update(self.env.episode_infos_of(ep_env, info_at_end))
         return env_infos, episode_infos
 
     @staticmethod
@@ -813,7 +826,7 @@ class GpuFragmentWorker(GpuVecWorker):
         pol = self.agent
         gaussian = pol.kind == 'gaussian'
         env_infos, episode_infos = self._device_infos(
-            b, src, ep_env, self._packed_env_infos(b, src, tcap),
+            b, src, ep_env, ep_end, self._packed_env_infos(b, src, tcap),
             self._packed_episode_infos(b, ep_env, ep_end))
         return DeviceEpisodeBatch(
             self.env.spec, lengths=length.astype(np.int64), obs_dev=obs,

@@ -577,10 +577,62 @@ GA_API int ga_grid_env_step_record_norm(const ga_grid_env* env, const ga_record_
                                         const ga_norm_args* norm, const float* actions,
                                         int64_t lda, const float* obs, ga_stream_t stream);
 
-/* Any device env: `env` points to a ga_synth_env, ga_point_env or ga_grid_env. */
+/* MultiEnvWrapper([PointEnv(goal=task_goals[k], ...) for k < num_tasks], strategy, mode)
+ * (envs/multi_env_wrapper.py:169-226), one wrapper per member.  The fields of
+ * ga_point_env (the other PointEnv parameters are shared by the tasks) plus the task
+ * layer: every reset -- ga_multi_point_env_reset, and the reset of a finished env
+ * inside the record entries -- picks the member's next task from its own last_task
+ * (round robin: 0 after -1, else (last + 1) % num_tasks; uniform random: the first
+ * word of Philox4x32-10 keyed (seed; env index, the member's reset counter), scaled
+ * to [0, num_tasks) by the high half of u * num_tasks -- the reference draws from
+ * Python's global `random` there), copies task_goals[task] into goal[i] and resets
+ * the PointEnv.  mode GA_TASK_ADD_ONEHOT: obs_dim = 3 + num_tasks, the one-hot of the
+ * active task follows the PointEnv observation on reset and on every step (the
+ * observation of an episode's last step carries that episode's task);
+ * GA_TASK_VANILLA: obs_dim = 3.  `task_id` (optional) receives env_info['task_id']
+ * as uint8, addressed like `success`; num_tasks is 1..256. */
+#define GA_TASK_ROUND_ROBIN 0
+#define GA_TASK_UNIFORM_RANDOM 1
+#define GA_TASK_VANILLA 0
+#define GA_TASK_ADD_ONEHOT 1
+typedef struct {
+  int64_t n;
+  float arena_size, done_bonus;
+  int32_t never_done, max_episode_length;
+  float* point;      /* [n, 2] */
+  float* goal;       /* [n, 2] the active task's goal, written at reset */
+  int32_t* t;        /* [n] steps taken in the current episode */
+  uint8_t* success;  /* optional, as in ga_point_env */
+  int32_t num_tasks, strategy, mode, pad_;
+  uint64_t seed;
+  const float* task_goals; /* [num_tasks, 2] */
+  int32_t* last_task;      /* [n] active task, -1 before the first reset */
+  uint32_t* resets;        /* [n] resets so far */
+  uint8_t* task_id;        /* optional, see above */
+} ga_multi_point_env;
+
+GA_API int ga_multi_point_env_reset(const ga_multi_point_env* env, const uint8_t* mask,
+                                    float* obs, int64_t ldo, ga_stream_t stream);
+GA_API int ga_multi_point_env_step(const ga_multi_point_env* env, const float* actions,
+                                   int64_t lda, const float* obs, float* next_obs,
+                                   int64_t ldo, float* reward, uint8_t* step_type,
+                                   ga_stream_t stream);
+GA_API int ga_multi_point_env_step_record_norm(const ga_multi_point_env* env,
+                                               const ga_record_args* rec,
+                                               const ga_norm_args* norm,
+                                               const float* actions, int64_t lda,
+                                               const float* obs, ga_stream_t stream);
+/* Host-only (no GPU needed): the task the uniform random strategy gives env `env_id`
+ * at its reset number `counter` (< 0: num_tasks outside 1..256). */
+GA_API int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                  int num_tasks);
+
+/* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env or
+ * ga_multi_point_env. */
 #define GA_ENV_SYNTH 0
 #define GA_ENV_POINT 1
 #define GA_ENV_GRID 2
+#define GA_ENV_MULTI_POINT 3
 typedef struct {
   int32_t kind, pad_;
   const void* env;

@@ -1,6 +1,10 @@
 """Env-steps per second of the one-launch rollout (ga_rollout_env_steps /
 ga_rollout_synth_steps) with PointVecEnv against SyntheticVecEnv of the same
-observation / action sizes: 4096 envs x T 256, a (256, 256) Gaussian MLP policy.
+observation / action sizes, and with MultiTaskPointVecEnv (K = 4 and K = 16 goals
+on the unit circle, round robin, add-onehot: observations 3 + K wide;
+never_done, so that every episode runs its T steps as the other rows' do and the
+rows differ by the work per step alone): 4096 envs x T 256, a (256, 256)
+Gaussian MLP policy.
 
     python tools/device_env_rate.py [--envs 4096] [--T 256] [--reps 5]
 
@@ -20,12 +24,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def measure(kind, n, T, reps):
-    from garage_amd.envs import PointVecEnv, SyntheticVecEnv
+    from garage_amd.envs import (MultiTaskPointVecEnv, PointVecEnv,
+                                 SyntheticVecEnv, round_robin_strategy)
     from garage_amd.policies import GaussianMLPPolicy
     from garage_amd.sampler import GpuVecSampler, GpuVecWorker
     torch.manual_seed(0)
     if kind == 'point':
         env = PointVecEnv(n, goal=(1., 1.), max_episode_length=T)
+    elif kind.startswith('multitask'):
+        K = int(kind.split('_k')[1])
+        angle = 2 * np.pi * np.arange(K) / K
+        env = MultiTaskPointVecEnv(
+            n, np.stack([np.cos(angle), np.sin(angle)], axis=1),
+            round_robin_strategy, 'add-onehot', start='spread',
+            never_done=True, max_episode_length=T)
     else:
         env = SyntheticVecEnv(n, 3, 2, T, seed=1)
     pol = GaussianMLPPolicy(env.spec, hidden_sizes=(256, 256), init_std=0.1)
@@ -55,7 +67,7 @@ def main():
     ap.add_argument('--T', type=int, default=256)
     ap.add_argument('--reps', type=int, default=5)
     a = ap.parse_args()
-    for kind in ('point', 'synthetic'):
+    for kind in ('point', 'synthetic', 'multitask_k4', 'multitask_k16'):
         print(json.dumps(measure(kind, a.envs, a.T, a.reps)))
 
 
