@@ -452,8 +452,12 @@ extern "C" int ga_gae_scan_f32(const float* rewards, const float* values,
   const int64_t waves = ga_ceil_div(n_rows, rows_per_wave);
   const int64_t blocks = ga_ceil_div(waves, 4);
   GA_REQUIRE(blocks < (1ll << 31), "ga_gae_scan_f32: grid too large");
-  // whole-episode rows of at most 256 steps: the constant-decay kernel
-  if (g_fixed_fast_path && mode == 1 && !bonus && max_len <= 256) {
+  const bool aligned = ga_aligned16(rewards) && ga_aligned16(values) &&
+                       ga_aligned16(adv) && ga_aligned16(ret) &&
+                       (!bonus || ga_aligned16(bonus));
+  // whole-episode rows of at most 256 steps: the constant-decay kernel (its lanes
+  // decide on 16-B accesses from the step index alone, so the bases must be aligned)
+  if (g_fixed_fast_path && mode == 1 && !bonus && max_len <= 256 && aligned) {
     const int nq = (g_rows_steps_per_lane == 8 && max_len > 4) ? 2 : 1;
     int flpr = 1;
     while (flpr < 64 && (int64_t)flpr * 4 * nq < max_len) flpr <<= 1;
@@ -489,9 +493,7 @@ extern "C" int ga_gae_scan_f32(const float* rewards, const float* values,
     GA_CHECK_LAUNCH("ga_gae_scan_f32");
     return GA_OK;
   }
-  const bool vec = (offsets || ld % 4 == 0) && ga_aligned16(rewards) &&
-                   ga_aligned16(values) && ga_aligned16(adv) && ga_aligned16(ret) &&
-                   (!bonus || ga_aligned16(bonus)) &&
+  const bool vec = (offsets || ld % 4 == 0) && aligned &&
                    (!tail || (reinterpret_cast<uintptr_t>(tail) & 7u) == 0);
   // algorithmic bytes: 16 per step (r, V in; A, G out)
   const double steps = offsets ? 0.0 : (double)n_rows * (double)T;

@@ -341,6 +341,15 @@ def pad_rows(x, width=None):
     return out
 
 
+def _empty_rows_like(t, shape, strides):
+    """Uninitialised fp32 tensor of ``shape`` whose rows lie ``strides[0]``
+    floats apart (a view of an ``(n_rows, ld)`` buffer when ``ld > T``)."""
+    if len(shape) == 1 or strides[0] == shape[1]:
+        return torch.empty(shape, dtype=t.dtype, device=t.device)
+    buf = torch.empty(shape[0], strides[0], dtype=t.dtype, device=t.device)
+    return buf[:, :shape[1]]
+
+
 def gae_scan(rewards, values, *, discount, gae_lambda, max_episode_length,
              tail=None, offsets=None, max_len=None, v0=0.0, bonus=None,
              bonus_const=0.0, adv=None, ret=None):
@@ -348,21 +357,47 @@ def gae_scan(rewards, values, *, discount, gae_lambda, max_episode_length,
 
     ``rewards``/``values`` are ``(n_rows, T)`` device tensors (mode 0 with
     ``tail``; mode 1 without), or packed 1-D tensors with ``offsets``.
+
+    The library takes ONE row stride for every array, so 2-D inputs may be
+    strided views (``buf[:, :T]``) as long as ``values``, ``bonus``, ``tail``,
+    ``adv`` and ``ret`` share ``rewards.stride(0)`` and have unit-stride rows;
+    anything else raises ``ValueError`` before a launch.  Outputs that are not
+    passed are allocated with that row stride.
     """
     if offsets is not None:
         n_rows = offsets.numel() - 1
         T, ld = rewards.numel(), 0  # packed: T carries the total step count
         if max_len is None:
             raise ValueError('max_len is required with offsets')
+        shape, strides = (T, ), (1, )
     else:
         n_rows, T = rewards.shape
-        ld = rewards.stride(0)
-        assert values.stride(0) == ld
+        # (a single row has no stride to speak of)
+        ld = rewards.stride(0) if n_rows > 1 else T
+        if ld < T:
+            raise ValueError('gae_scan: rows of rewards overlap (row stride '
+                             '{} < {} columns)'.format(ld, T))
         max_len = T
+        shape, strides = (n_rows, T), (ld, 1)
     if adv is None:
-        adv = torch.empty_like(rewards)
+        adv = _empty_rows_like(rewards, shape, strides)
     if ret is None:
-        ret = torch.empty_like(rewards)
+        ret = _empty_rows_like(rewards, shape, strides)
+    for name, t in (('rewards', rewards), ('values', values), ('bonus', bonus),
+                    ('tail', tail), ('adv', adv), ('ret', ret)):
+        if t is None:
+            continue
+        if tuple(t.shape) != shape:
+            raise ValueError('gae_scan: {} has shape {}, rewards {}'.format(
+                name, tuple(t.shape), shape))
+        # (the stride of a dimension of size 1 addresses nothing)
+        bad = [d for d in range(len(shape))
+               if shape[d] > 1 and t.stride(d) != strides[d]]
+        if bad:
+            raise ValueError(
+                'gae_scan: {} has strides {}, but every array must have unit-'
+                'stride rows {} floats apart (the row stride of rewards)'.format(
+                    name, tuple(t.stride()), strides[0]))
     mode = 0 if tail is not None else 1
     call('ga_gae_scan_f32', dptr(rewards), dptr(values), dptr(bonus),
          dptr(tail), dptr(offsets), n_rows, T, ld, int(max_len), mode,

@@ -67,8 +67,8 @@ GA_API int ga_gae_scan_f32(const float* rewards, const float* values, const floa
                            ga_stream_t stream);
 /* Whole-episode rows (mode 1) of at most 256 steps without a per-step bonus take
  * constant-decay fast paths (fixed horizon: aligned rows of exactly
- * max_episode_length steps; otherwise the ragged variant); 0 forces the general
- * kernel (A/B runs, tests). */
+ * max_episode_length steps; otherwise the ragged variant) when all four arrays
+ * start on 16-byte boundaries; 0 forces the general kernel (A/B runs, tests). */
 GA_API int ga_set_gae_fixed_fast_path(int on);
 /* Steps per lane of those fast paths: 4 (one 16-B access per array and lane) or 8
  * (two; half the lanes, waves and shuffle steps per row).  Same recurrences in
