@@ -7,7 +7,7 @@ ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
 HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step lnorm
-CPPS  := errors prof update comm rollout_loop rollout_env_loop
+CPPS  := errors prof update comm rollout_loop
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -63,30 +63,30 @@ clean:
 
 .PHONY: all clean mfma-peak mfma-tools slp-variant
 
-# Host-side epoch / rollout loops under AddressSanitizer + UBSan on the CPU, with
-# every kernel entry point replaced by a recording fake (tests/host/).
+# Host-side epoch loops under AddressSanitizer + UBSan on the CPU, with every kernel
+# entry point replaced by a recording fake (tests/host/).
 asan-host: $(OUT)/host_asan_test
 	$(OUT)/host_asan_test
 
-$(OUT)/host_asan_test: tests/host/update_loop_harness.cpp $(CSRC)/update.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+$(OUT)/host_asan_test: tests/host/update_loop_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/update_loop_harness.cpp $(CSRC)/update.cpp $(CSRC)/rollout_loop.cpp \
+	  tests/host/update_loop_harness.cpp $(CSRC)/update.cpp \
 	  -o $@
 
 .PHONY: asan-host
 
-# ga_rollout_env_steps' host loop (rollout_env_loop.cpp) under AddressSanitizer +
+# ga_rollout_env_steps' host loop (rollout_loop.cpp) under AddressSanitizer +
 # UBSan with recording fakes for the kernels it launches (tests/host/).
 asan-env-loop: $(OUT)/env_loop_asan_test
 	$(OUT)/env_loop_asan_test
 
-$(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_env_loop.cpp $(CSRC)/internal.h include/garage_amd.h
+$(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_env_loop.cpp \
+	  tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_loop.cpp \
 	  -o $@
 
 .PHONY: asan-env-loop

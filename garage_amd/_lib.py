@@ -59,6 +59,16 @@ class EnvRef(C.Structure):
 
 
 ENV_SYNTH, ENV_POINT, ENV_GRID, ENV_MULTI_POINT = 0, 1, 2, 3
+
+
+def env_ref(kind, env):
+    """``ga_env_ref`` of kind ``kind`` to the ctypes env struct ``env`` (kept
+    alive by the reference)."""
+    ref = EnvRef(kind=kind, env=C.addressof(env))
+    ref.keepalive = env
+    return ref
+
+
 TASK_ROUND_ROBIN, TASK_UNIFORM_RANDOM = 0, 1
 TASK_VANILLA, TASK_ADD_ONEHOT = 0, 1
 
@@ -119,7 +129,7 @@ class UpdateArgs(C.Structure):
                 ('partials_floats', c_i64), ('phase', c_i32)]
 
 
-ABI_VERSION = 4  # ga_abi_version() of the library these structs mirror
+ABI_VERSION = 5  # ga_abi_version() of the library these structs mirror
 
 # name -> (restype, argtypes); mirrors include/garage_amd.h one to one.
 SIGNATURES = {
@@ -209,9 +219,6 @@ SIGNATURES = {
     'ga_stats_f32': (c_int, [ptr, c_i64, c_int, ptr, ptr, ptr]),
     'ga_adv_center_f32': (c_int, [ptr, c_i64, ptr, c_f32, ptr]),
     'ga_sub_scalar_f32': (c_int, [ptr, c_i64, ptr, ptr]),
-    'ga_synth_env_reset': (c_int, [C.POINTER(SynthEnv), ptr, ptr, c_i64, ptr]),
-    'ga_synth_env_step': (c_int, [C.POINTER(SynthEnv), ptr, c_i64, ptr, ptr,
-                                  c_i64, ptr, ptr, ptr]),
     'ga_obs_normalize_f64': (c_int, [c_i64, c_int, ptr, c_i64, ptr, ptr, c_f64,
                                      ptr, ptr]),
     'ga_obs_normalize_from_f64': (c_int, [c_i64, c_int, ptr, ptr, c_i64, ptr,
@@ -225,47 +232,18 @@ SIGNATURES = {
     'ga_policy_step_fused_f32': (c_int, [C.POINTER(MlpDesc), ptr,
                                          C.POINTER(HeadArgs), ptr]),
     'ga_record_step': (c_int, [C.POINTER(RecordArgs), ptr]),
-    'ga_synth_env_step_record': (c_int, [C.POINTER(SynthEnv),
-                                         C.POINTER(RecordArgs), ptr, c_i64, ptr,
-                                         ptr]),
-    'ga_synth_env_step_record_norm': (c_int, [C.POINTER(SynthEnv),
-                                              C.POINTER(RecordArgs),
-                                              C.POINTER(NormArgs), ptr, c_i64,
-                                              ptr, ptr]),
+    'ga_multi_env_task_draw': (c_int, [c_u64, c_i64, c_u32, c_int]),
+    'ga_env_reset': (c_int, [C.POINTER(EnvRef), ptr, ptr, c_i64, ptr]),
+    'ga_env_step': (c_int, [C.POINTER(EnvRef), ptr, c_i64, ptr, ptr, c_i64, ptr,
+                            ptr, ptr]),
+    'ga_env_step_record': (c_int, [C.POINTER(EnvRef), C.POINTER(RecordArgs),
+                                   C.POINTER(NormArgs), ptr, c_i64, ptr, ptr]),
     'ga_policy_env_step_fused_f32': (c_int, [C.POINTER(MlpDesc), ptr,
                                              C.POINTER(HeadArgs),
-                                             C.POINTER(SynthEnv),
+                                             C.POINTER(EnvRef),
                                              C.POINTER(RecordArgs),
                                              C.POINTER(NormArgs), c_i64, ptr]),
     'ga_set_fused_env_step': (c_int, [c_int]),
-    'ga_rollout_synth_steps': (c_int, [C.POINTER(MlpDesc), ptr,
-                                       C.POINTER(HeadArgs),
-                                       C.POINTER(SynthEnv),
-                                       C.POINTER(RecordArgs), ptr, ptr,
-                                       C.POINTER(NormArgs), ptr, ptr, c_i64,
-                                       ptr]),
-    'ga_point_env_reset': (c_int, [C.POINTER(PointEnv), ptr, ptr, c_i64, ptr]),
-    'ga_point_env_step': (c_int, [C.POINTER(PointEnv), ptr, c_i64, ptr, ptr,
-                                  c_i64, ptr, ptr, ptr]),
-    'ga_point_env_step_record_norm': (c_int, [C.POINTER(PointEnv),
-                                              C.POINTER(RecordArgs),
-                                              C.POINTER(NormArgs), ptr, c_i64,
-                                              ptr, ptr]),
-    'ga_grid_env_reset': (c_int, [C.POINTER(GridEnv), ptr, ptr, c_i64, ptr]),
-    'ga_grid_env_step': (c_int, [C.POINTER(GridEnv), ptr, c_i64, ptr, ptr,
-                                 c_i64, ptr, ptr, ptr]),
-    'ga_grid_env_step_record_norm': (c_int, [C.POINTER(GridEnv),
-                                             C.POINTER(RecordArgs),
-                                             C.POINTER(NormArgs), ptr, c_i64,
-                                             ptr, ptr]),
-    'ga_multi_point_env_reset': (c_int, [C.POINTER(MultiPointEnv), ptr, ptr,
-                                         c_i64, ptr]),
-    'ga_multi_point_env_step': (c_int, [C.POINTER(MultiPointEnv), ptr, c_i64,
-                                        ptr, ptr, c_i64, ptr, ptr, ptr]),
-    'ga_multi_point_env_step_record_norm': (c_int, [
-        C.POINTER(MultiPointEnv), C.POINTER(RecordArgs), C.POINTER(NormArgs),
-        ptr, c_i64, ptr, ptr]),
-    'ga_multi_env_task_draw': (c_int, [c_u64, c_i64, c_u32, c_int]),
     'ga_rollout_env_steps': (c_int, [C.POINTER(MlpDesc), ptr,
                                      C.POINTER(HeadArgs), C.POINTER(EnvRef),
                                      C.POINTER(RecordArgs), ptr, ptr,

@@ -15,4 +15,4 @@ void ga_set_error(const char* fmt, ...) {
 
 extern "C" const char* ga_last_error(void) { return g_err; }
 
-extern "C" int ga_abi_version(void) { return 4; }
+extern "C" int ga_abi_version(void) { return 5; }

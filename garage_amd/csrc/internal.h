@@ -38,18 +38,42 @@ int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const fl
                     float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
                     int64_t lddz, hipStream_t stream);
 
-// rollout.hip / policy_fused.hip: ga_*_env_step_record_norm and
-// ga_policy_env_step_fused_f32 for any device env (rollout_env_loop.cpp)
-int ga_env_step_record_ref(const ga_env_ref* env, const ga_record_args* rec,
-                           const ga_norm_args* norm, const float* actions, int64_t lda,
-                           const float* obs, ga_stream_t stream);
-int ga_policy_env_step_fused_ref(const ga_mlp_desc* d, const float* params,
-                                 const ga_head_args* head, const ga_env_ref* env,
-                                 const ga_record_args* rec, const ga_norm_args* norm,
-                                 int64_t n_steps, ga_stream_t stream);
-// rollout_loop.cpp: 1 when a rollout step takes the one fused policy + env launch
-// (ga_set_fused_env_step, GARAGE_AMD_FUSED_ENV_STEP)
-int ga_fused_env_step_enabled(void);
+// ---- device envs: what every kind states about itself, and the ONE dispatch from a
+// ga_env_ref to its typed struct (rollout.hip, policy_fused.hip, rollout_loop.cpp).
+// Every struct has `n`; the observation width, the columns of an action row and
+// whether the action is a class index are the overloads below.
+inline int ga_env_obs_dim(const ga_synth_env* e) { return e->obs_dim; }
+inline int ga_env_obs_dim(const ga_point_env*) { return 3; }
+inline int ga_env_obs_dim(const ga_grid_env* e) { return e->rows * e->cols; }
+inline int ga_env_obs_dim(const ga_multi_point_env* e) {
+  return 3 + (e->mode == GA_TASK_ADD_ONEHOT ? e->num_tasks : 0);
+}
+inline int ga_env_discrete(const ga_synth_env* e) { return e->discrete != 0; }
+inline int ga_env_discrete(const ga_point_env*) { return 0; }
+inline int ga_env_discrete(const ga_grid_env*) { return 1; }
+inline int ga_env_discrete(const ga_multi_point_env*) { return 0; }
+inline int ga_env_act_width(const ga_synth_env* e) { return e->discrete ? 1 : e->act_dim; }
+inline int ga_env_act_width(const ga_point_env*) { return 2; }
+inline int ga_env_act_width(const ga_grid_env*) { return 1; }
+inline int ga_env_act_width(const ga_multi_point_env*) { return 2; }
+
+// f(const ga_<kind>_env*) of the env `ref` points to; `who` names the entry point in
+// the two errors this owns
+template <class F>
+int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
+  if (!ref || !ref->env) {
+    ga_set_error("%s: null env", who);
+    return -1;
+  }
+  switch (ref->kind) {
+    case GA_ENV_SYNTH: return f((const ga_synth_env*)ref->env);
+    case GA_ENV_POINT: return f((const ga_point_env*)ref->env);
+    case GA_ENV_GRID: return f((const ga_grid_env*)ref->env);
+    case GA_ENV_MULTI_POINT: return f((const ga_multi_point_env*)ref->env);
+  }
+  ga_set_error("%s: unknown env kind %d", who, ref->kind);
+  return -1;
+}
 
 extern "C" {
 // gemm.hip: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)

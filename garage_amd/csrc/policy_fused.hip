@@ -19,6 +19,8 @@
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv:
 // a template parameter of the kernel) the thread that sampled an env's action also steps it, and a whole
 // rollout is ONE launch with the weights resident on the CU (see the kernel).
+#include <type_traits>
+
 #include "common.h"
 #include "prof.h"
 
@@ -695,72 +697,32 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* param
   return policy_step_launch<ga_rollout::SynthEnv>(d, params, a, nullptr, 1, stream);
 }
 
-// The same launch followed, per env, by the synthetic env's step + NormalizedEnv
-// statistics + bookkeeping + reset (what ga_synth_env_step_record_norm does as its
-// own launch), for n_steps consecutive rollout steps: every workgroup takes its 32
-// envs through all of them (nothing couples envs within a rollout), alternating
-// between `a->obs` and `rec->next_obs` (and the raw pair of `norm`).  `a->action` is
-// what the env is stepped with.
-// the kernel-side arguments of each C-ABI env (unevaluated: types only)
-ga_rollout::EnvStepArgs env_args_of(const ga_synth_env*);
-ga_rollout::EnvStepArgsT<ga_rollout::PointEnv> env_args_of(const ga_point_env*);
-ga_rollout::EnvStepArgsT<ga_rollout::GridEnv> env_args_of(const ga_grid_env*);
-ga_rollout::EnvStepArgsT<ga_rollout::MultiTaskEnv<ga_rollout::PointEnv>> env_args_of(
-    const ga_multi_point_env*);
-
-template <class GaEnv>
-static int policy_env_step_fused(const ga_mlp_desc* d, const float* params,
-                                 const ga_head_args* a, const GaEnv* env,
-                                 const ga_record_args* rec, const ga_norm_args* norm,
-                                 int64_t n_steps, hipStream_t stream) {
-  GA_REQUIRE(a && rec, "ga_policy_env_step_fused_f32: null pointer");
-  GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
-             "ga_policy_env_step_fused_f32: steps exceed the rollout buffer");
-  GA_REQUIRE(!a->noise || n_steps == 1,
-             "ga_policy_env_step_fused_f32: teacher-forced noise is per step");
-  decltype(env_args_of(env)) es;
-  int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs,
-                             "ga_policy_env_step_fused_f32", &es);
-  if (rc) return rc;
-  GA_REQUIRE(es.e.n == a->n, "ga_policy_env_step_fused_f32: env count mismatch");
-  GA_REQUIRE(es.p.col == a->col && es.p.col + n_steps <= es.p.Tcap,
-             "ga_policy_env_step_fused_f32: record columns do not match the policy's");
-  return policy_step_launch(d, params, a, &es, n_steps, stream);
-}
-
+// The same launch followed, per env, by the env's step + NormalizedEnv statistics +
+// bookkeeping + reset (what ga_env_step_record does as its own launch), for n_steps
+// consecutive rollout steps: every workgroup takes its 32 envs through all of them
+// (nothing couples envs within a rollout), alternating between `a->obs` and
+// `rec->next_obs` (and the raw pair of `norm`).  `a->action` is what the env is
+// stepped with.
 extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                            const ga_head_args* a,
-                                            const ga_synth_env* env,
+                                            const ga_head_args* a, const ga_env_ref* ref,
                                             const ga_record_args* rec,
                                             const ga_norm_args* norm, int64_t n_steps,
-                                            ga_stream_t stream_) {
-  return policy_env_step_fused(d, params, a, env, rec, norm, n_steps,
-                               (hipStream_t)stream_);
-}
-
-// The same for any device env (rollout_env_loop.cpp)
-int ga_policy_env_step_fused_ref(const ga_mlp_desc* d, const float* params,
-                                 const ga_head_args* a, const ga_env_ref* env,
-                                 const ga_record_args* rec, const ga_norm_args* norm,
-                                 int64_t n_steps, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(env && env->env, "ga_rollout_env_steps: null env");
-  switch (env->kind) {
-    case GA_ENV_SYNTH:
-      return policy_env_step_fused(d, params, a, (const ga_synth_env*)env->env, rec, norm,
-                                   n_steps, stream);
-    case GA_ENV_POINT:
-      return policy_env_step_fused(d, params, a, (const ga_point_env*)env->env, rec, norm,
-                                   n_steps, stream);
-    case GA_ENV_GRID:
-      return policy_env_step_fused(d, params, a, (const ga_grid_env*)env->env, rec, norm,
-                                   n_steps, stream);
-    case GA_ENV_MULTI_POINT:
-      return policy_env_step_fused(d, params, a, (const ga_multi_point_env*)env->env, rec,
-                                   norm, n_steps, stream);
-  }
-  ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
-  return -1;
+                                            ga_stream_t stream) {
+  const char* who = "ga_policy_env_step_fused_f32";
+  return ga_visit_env(ref, who, [&](auto* env) {
+    GA_REQUIRE(a && rec, "%s: null pointer", who);
+    GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
+               "%s: steps exceed the rollout buffer", who);
+    GA_REQUIRE(!a->noise || n_steps == 1, "%s: teacher-forced noise is per step", who);
+    using GaEnv = std::remove_cv_t<std::remove_pointer_t<decltype(env)>>;
+    ga_env_step_args_t<GaEnv> es;
+    int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs, who, &es);
+    if (rc) return rc;
+    GA_REQUIRE(es.e.n == a->n, "%s: env count mismatch", who);
+    GA_REQUIRE(es.p.col == a->col && es.p.col + n_steps <= es.p.Tcap,
+               "%s: record columns do not match the policy's", who);
+    return policy_step_launch(d, params, a, &es, n_steps, (hipStream_t)stream);
+  });
 }
 
 template <class Env>

@@ -8,6 +8,8 @@
 // StochasticPolicy.get_actions' dist.sample() (torch/policies/stochastic_policy.py:
 // 46-89).  Rollout buffers are env-major (n_envs, Tcap[, width]) in HBM; one
 // thread owns one env (its row tails are 16-B friendly: widths are padded to 4).
+#include <type_traits>
+
 #include "common.h"
 
 #include "rollout_dev.h"
@@ -15,24 +17,7 @@
 namespace {
 using namespace ga_rollout;
 
-__global__ __launch_bounds__(256) void synth_reset_kernel(SynthEnv e,
-                                                          const uint8_t* mask,
-                                                          float* obs, int64_t ldo) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= e.n) return;
-  if (mask && !mask[i]) return;
-  synth_reset_one(e, i, obs, ldo);
-}
-
-__global__ __launch_bounds__(256) void synth_step_kernel(
-    SynthEnv e, const float* actions, int64_t lda, const float* obs, float* next_obs,
-    int64_t ldo, float* reward, uint8_t* step_type) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= e.n) return;
-  synth_step_one(e, i, actions, lda, obs, next_obs, ldo, reward, step_type);
-}
-
-// reset / step of a PointEnv, GridWorldEnv or multi-task PointEnv batch (rollout_dev.h)
+// reset / step of a batch of any env kind (rollout_dev.h)
 template <class Env>
 __global__ __launch_bounds__(256) void env_reset_kernel(Env e, const uint8_t* mask,
                                                         float* obs, int64_t ldo) {
@@ -42,17 +27,19 @@ __global__ __launch_bounds__(256) void env_reset_kernel(Env e, const uint8_t* ma
   env_reset_one(e, i, obs, ldo);
 }
 
+// `obs`: the current observations, read by the synthetic env only (the others keep
+// their state themselves)
 template <class Env>
 __global__ __launch_bounds__(256) void env_step_kernel(Env e, const float* actions,
-                                                       int64_t lda, float* next_obs,
-                                                       int64_t ldo, float* reward,
-                                                       uint8_t* step_type) {
+                                                       int64_t lda, const float* obs,
+                                                       float* next_obs, int64_t ldo,
+                                                       float* reward, uint8_t* step_type) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= e.n) return;
   float rew;
   uint8_t st;
-  env_core(e, i, env_pre(e, i), actions + i * lda, nullptr, next_obs + i * ldo, 0, &rew,
-           &st);
+  env_core(e, i, env_pre(e, i), actions + i * lda, obs + i * ldo, next_obs + i * ldo, 0,
+           &rew, &st);
   reward[i] = rew;
   step_type[i] = st;
 }
@@ -292,53 +279,6 @@ __global__ __launch_bounds__(256) void feistel_perm_kernel(int64_t n, int half_b
 // ---------------------------------------------------------------------------
 // C ABI (see include/garage_amd.h)
 // ---------------------------------------------------------------------------
-static SynthEnv to_dev(const ga_synth_env* e) {
-  SynthEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.obs_dim = e->obs_dim; d.act_dim = e->act_dim;
-  d.discrete = e->discrete; d.min_len = e->min_len; d.max_len = e->max_len;
-  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
-  d.episode = e->episode; d.t = e->t; d.len = e->len;
-  return d;
-}
-
-static int check_env(const ga_synth_env* e, const char* who) {
-  GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
-  GA_REQUIRE(e->min_len >= 1 && e->min_len <= e->max_len && e->max_len <= 65535,
-             "%s: episode lengths must satisfy 1 <= min <= max <= 65535", who);
-  return GA_OK;
-}
-
-extern "C" int ga_synth_env_reset(const ga_synth_env* env, const uint8_t* mask,
-                                  float* obs, int64_t ldo, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_env(env, "ga_synth_env_reset");
-  if (rc) return rc;
-  GA_REQUIRE(obs && ldo >= env->obs_dim, "ga_synth_env_reset: bad obs buffer");
-  hipLaunchKernelGGL(synth_reset_kernel, dim3((unsigned)ga_ceil_div(env->n, 256)),
-                     dim3(256), 0, stream, to_dev(env), mask, obs, ldo);
-  GA_CHECK_LAUNCH("synth_reset");
-  return GA_OK;
-}
-
-extern "C" int ga_synth_env_step(const ga_synth_env* env, const float* actions,
-                                 int64_t lda, const float* obs, float* next_obs,
-                                 int64_t ldo, float* reward, uint8_t* step_type,
-                                 ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_env(env, "ga_synth_env_step");
-  if (rc) return rc;
-  GA_REQUIRE(actions && obs && next_obs && reward && step_type,
-             "ga_synth_env_step: null pointer");
-  GA_REQUIRE(ldo >= env->obs_dim && lda >= (env->discrete ? 1 : env->act_dim),
-             "ga_synth_env_step: leading dimensions too small");
-  hipLaunchKernelGGL(synth_step_kernel, dim3((unsigned)ga_ceil_div(env->n, 256)),
-                     dim3(256), 0, stream, to_dev(env), actions, lda, obs, next_obs,
-                     ldo, reward, step_type);
-  GA_CHECK_LAUNCH("synth_step");
-  return GA_OK;
-}
-
 extern "C" int ga_policy_head_sample(const ga_head_args* a, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && a->head && a->obs && a->action && a->obs_buf && a->act_buf,
@@ -393,24 +333,121 @@ extern "C" int ga_record_step(const ga_record_args* a, ga_stream_t stream_) {
   return GA_OK;
 }
 
+// ---- the device envs ---------------------------------------------------------------
+// the kernel-side struct of each C-ABI env (rollout_dev.h)
+SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t) {
+  SynthEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.obs_dim = e->obs_dim; d.act_dim = e->act_dim;
+  d.discrete = e->discrete; d.min_len = e->min_len; d.max_len = e->max_len;
+  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  d.episode = e->episode; d.t = e->t; d.len = e->len;
+  return d;
+}
+
+PointEnv ga_env_to_dev(const ga_point_env* e, int64_t succ_ld) {
+  PointEnv d;
+  d.n = e->n; d.arena = e->arena_size; d.bonus = e->done_bonus;
+  d.never_done = e->never_done; d.max_len = e->max_episode_length;
+  d.point = e->point; d.goal = e->goal; d.t = e->t; d.success = e->success;
+  d.succ_ld = succ_ld;
+  return d;
+}
+
+GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t) {
+  GridEnv d;
+  d.n = e->n; d.rows = e->rows; d.cols = e->cols; d.max_len = e->max_episode_length;
+  d.map = e->map; d.start = e->start; d.state = e->state; d.t = e->t;
+  return d;
+}
+
+// the PointEnv part of a multi-task batch
+static ga_point_env point_part(const ga_multi_point_env* e) {
+  ga_point_env p;
+  p.n = e->n; p.arena_size = e->arena_size; p.done_bonus = e->done_bonus;
+  p.never_done = e->never_done; p.max_episode_length = e->max_episode_length;
+  p.point = e->point; p.goal = e->goal; p.t = e->t; p.success = e->success;
+  return p;
+}
+
+MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_ld) {
+  MultiTaskEnv<PointEnv> d;
+  const ga_point_env p = point_part(e);
+  d.n = e->n; d.in = ga_env_to_dev(&p, info_ld);
+  d.num_tasks = e->num_tasks; d.strategy = e->strategy;
+  d.one_hot = e->mode == GA_TASK_ADD_ONEHOT;
+  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  d.payload = e->task_goals; d.last_task = e->last_task; d.resets = e->resets;
+  d.task_id = e->task_id; d.info_ld = info_ld;
+  return d;
+}
+
+static int check_env(const ga_synth_env* e, const char* who) {
+  GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
+  GA_REQUIRE(e->min_len >= 1 && e->min_len <= e->max_len && e->max_len <= 65535,
+             "%s: episode lengths must satisfy 1 <= min <= max <= 65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_point_env* e, const char* who) {
+  GA_REQUIRE(e && e->point && e->goal && e->t, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->arena_size >= 0.f, "%s: arena_size must be >= 0", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_grid_env* e, const char* who) {
+  GA_REQUIRE(e && e->map && e->start && e->state && e->t, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0 && e->rows > 0 && e->cols > 0 && e->rows <= 4096 &&
+                 e->cols <= 4096 && (int64_t)e->rows * e->cols <= (1 << 20),
+             "%s: bad env sizes", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_multi_point_env* e, const char* who) {
+  GA_REQUIRE(e && e->point && e->goal && e->t && e->task_goals && e->last_task &&
+                 e->resets, "%s: null env state", who);
+  const ga_point_env p = point_part(e);
+  int rc = check_env(&p, who);
+  if (rc) return rc;
+  GA_REQUIRE(e->num_tasks >= 1 && e->num_tasks <= 256,
+             "%s: num_tasks must be in 1..256 (got %d)", who, e->num_tasks);
+  GA_REQUIRE(e->strategy == GA_TASK_ROUND_ROBIN || e->strategy == GA_TASK_UNIFORM_RANDOM,
+             "%s: unknown sample strategy %d", who, e->strategy);
+  GA_REQUIRE(e->mode == GA_TASK_VANILLA || e->mode == GA_TASK_ADD_ONEHOT,
+             "%s: unknown mode %d", who, e->mode);
+  return GA_OK;
+}
+
 // Validation + conversion of the C-ABI arguments of one env step (also used by the
-// fused policy + env step of policy_fused.hip): the record / NormalizedEnv part, for
-// an env of obs_dim observations and act_w action columns
-template <class Env>
-static int build_env_step(const Env& e, int obs_dim, int act_w, const ga_record_args* a,
-                          const ga_norm_args* norm, const float* actions, int64_t lda,
-                          const float* obs, const char* who,
-                          ga_rollout::EnvStepArgsT<Env>* out) {
-  GA_REQUIRE(a && a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
+// fused policy + env step of policy_fused.hip): the env, the record and the
+// NormalizedEnv part
+template <class GaEnv>
+int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
+                      const float* actions, int64_t lda, const float* obs, const char* who,
+                      ga_env_step_args_t<GaEnv>* out) {
+  int rc = check_env(env, who);
+  if (rc) return rc;
+  const int obs_dim = ga_env_obs_dim(env);
+  GA_REQUIRE(a, "%s: null pointer", who);
+  if (std::is_same<GaEnv, ga_multi_point_env>::value)
+    GA_REQUIRE(a->ldo >= obs_dim,
+               "%s: observation rows of %lld columns are narrower than 3 + num_tasks = %d",
+               who, (long long)a->ldo, obs_dim);
+  GA_REQUIRE(a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
                  a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
                  a->step_eps && a->step_samples && actions && obs,
              "%s: null pointer", who);
-  GA_REQUIRE(a->n == e.n && a->col >= 0 && a->col < a->Tcap,
+  GA_REQUIRE(a->n == env->n && a->col >= 0 && a->col < a->Tcap,
              "%s: col %lld out of range (Tcap %lld)", who, (long long)a->col,
              (long long)a->Tcap);
   GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
              "%s: max_episode_length must be in 1..65535", who);
-  GA_REQUIRE(a->ldo >= obs_dim && a->obs_dim == obs_dim && lda >= act_w,
+  GA_REQUIRE(a->ldo >= obs_dim && a->obs_dim == obs_dim && lda >= ga_env_act_width(env),
              "%s: leading dimensions too small", who);
   RecordParams p;
   p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
@@ -442,253 +479,83 @@ static int build_env_step(const Env& e, int obs_dim, int act_w, const ga_record_
       raw_next = norm->raw_next_obs;
     }
   }
-  out->e = e; out->p = p; out->nm = nm;
+  out->e = ga_env_to_dev(env, a->Tcap);  // env_infos go into the [n, Tcap] buffers
+  out->p = p; out->nm = nm;
   out->actions = actions; out->lda = lda; out->raw_obs = raw_obs; out->raw_next = raw_next;
   out->seen_next = (float*)a->next_obs; out->reward = (float*)a->reward;
   out->step_type = (uint8_t*)a->step_type;
   return GA_OK;
 }
+#define GA_BUILD_ENV_STEP_OF(E)                                                        \
+  template int ga_build_env_step<E>(const E*, const ga_record_args*, const ga_norm_args*, \
+                                    const float*, int64_t, const float*, const char*,  \
+                                    ga_env_step_args_t<E>*);
+GA_BUILD_ENV_STEP_OF(ga_synth_env)
+GA_BUILD_ENV_STEP_OF(ga_point_env)
+GA_BUILD_ENV_STEP_OF(ga_grid_env)
+GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
+#undef GA_BUILD_ENV_STEP_OF
 
-int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who, ga_rollout::EnvStepArgs* out) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  return build_env_step(to_dev(env), env->obs_dim, env->discrete ? 1 : env->act_dim, a,
-                        norm, actions, lda, obs, who, out);
-}
-
-extern "C" int ga_synth_env_step_record_norm(const ga_synth_env* env,
-                                             const ga_record_args* a,
-                                             const ga_norm_args* norm,
-                                             const float* actions, int64_t lda,
-                                             const float* obs, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  EnvStepArgs args;
-  int rc = ga_build_env_step(env, a, norm, actions, lda, obs, "ga_synth_env_step_record",
-                             &args);
-  if (rc) return rc;
-  hipLaunchKernelGGL(env_step_record_kernel<SynthEnv>,
-                     dim3((unsigned)ga_ceil_div(a->n, 256)), dim3(256), 0, stream, args);
-  GA_CHECK_LAUNCH("synth_step_record");
-  return GA_OK;
-}
-
-extern "C" int ga_synth_env_step_record(const ga_synth_env* env,
-                                        const ga_record_args* a, const float* actions,
-                                        int64_t lda, const float* obs,
-                                        ga_stream_t stream) {
-  return ga_synth_env_step_record_norm(env, a, nullptr, actions, lda, obs, stream);
+// Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
+// grid_world_env.py:91-109, multi_env_wrapper.py:169-194)
+extern "C" int ga_env_reset(const ga_env_ref* ref, const uint8_t* mask, float* obs,
+                            int64_t ldo, ga_stream_t stream) {
+  const char* who = "ga_env_reset";
+  return ga_visit_env(ref, who, [&](auto* env) {
+    int rc = check_env(env, who);
+    if (rc) return rc;
+    GA_REQUIRE(obs && ldo >= ga_env_obs_dim(env), "%s: bad obs buffer", who);
+    const auto e = ga_env_to_dev(env, 1);
+    hipLaunchKernelGGL(env_reset_kernel<decltype(e)>,
+                       dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0,
+                       (hipStream_t)stream, e, mask, obs, ldo);
+    GA_CHECK_LAUNCH("env_reset");
+    return GA_OK;
+  });
 }
 
-// ---- PointEnv / GridWorldEnv batches ---------------------------------------------
-// succ_ld: row stride of the success buffer (1: [n], Tcap: the [n, Tcap] record buffer)
-static PointEnv to_dev(const ga_point_env* e, int64_t succ_ld) {
-  PointEnv d;
-  d.n = e->n; d.arena = e->arena_size; d.bonus = e->done_bonus;
-  d.never_done = e->never_done; d.max_len = e->max_episode_length;
-  d.point = e->point; d.goal = e->goal; d.t = e->t; d.success = e->success;
-  d.succ_ld = succ_ld;
-  return d;
+// Environment.step (envs/point_env.py:100-170, grid_world_env.py:111-215,
+// multi_env_wrapper.py:196-226)
+extern "C" int ga_env_step(const ga_env_ref* ref, const float* actions, int64_t lda,
+                           const float* obs, float* next_obs, int64_t ldo, float* reward,
+                           uint8_t* step_type, ga_stream_t stream) {
+  const char* who = "ga_env_step";
+  return ga_visit_env(ref, who, [&](auto* env) {
+    int rc = check_env(env, who);
+    if (rc) return rc;
+    const bool reads_obs = std::is_same<decltype(env), const ga_synth_env*>::value;
+    GA_REQUIRE(actions && next_obs && reward && step_type && (obs || !reads_obs),
+               "%s: null pointer", who);
+    GA_REQUIRE(ldo >= ga_env_obs_dim(env) && lda >= ga_env_act_width(env),
+               "%s: leading dimensions too small", who);
+    const auto e = ga_env_to_dev(env, 1);
+    hipLaunchKernelGGL(env_step_kernel<decltype(e)>,
+                       dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0,
+                       (hipStream_t)stream, e, actions, lda, obs, next_obs, ldo, reward,
+                       step_type);
+    GA_CHECK_LAUNCH("env_step");
+    return GA_OK;
+  });
 }
 
-static GridEnv to_dev(const ga_grid_env* e) {
-  GridEnv d;
-  d.n = e->n; d.rows = e->rows; d.cols = e->cols; d.max_len = e->max_episode_length;
-  d.map = e->map; d.start = e->start; d.state = e->state; d.t = e->t;
-  return d;
+// the step + normalized_env.py:134-164 + vec_worker.py:176-204
+extern "C" int ga_env_step_record(const ga_env_ref* ref, const ga_record_args* rec,
+                                  const ga_norm_args* norm, const float* actions,
+                                  int64_t lda, const float* obs, ga_stream_t stream) {
+  const char* who = "ga_env_step_record";
+  return ga_visit_env(ref, who, [&](auto* env) {
+    using GaEnv = std::remove_cv_t<std::remove_pointer_t<decltype(env)>>;
+    ga_env_step_args_t<GaEnv> args;
+    int rc = ga_build_env_step(env, rec, norm, actions, lda, obs, who, &args);
+    if (rc) return rc;
+    hipLaunchKernelGGL(env_step_record_kernel<decltype(args.e)>,
+                       dim3((unsigned)ga_ceil_div(rec->n, 256)), dim3(256), 0,
+                       (hipStream_t)stream, args);
+    GA_CHECK_LAUNCH("env_step_record");
+    return GA_OK;
+  });
 }
 
-static int check_env(const ga_point_env* e, const char* who) {
-  GA_REQUIRE(e && e->point && e->goal && e->t, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->arena_size >= 0.f, "%s: arena_size must be >= 0", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_grid_env* e, const char* who) {
-  GA_REQUIRE(e && e->map && e->start && e->state && e->t, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0 && e->rows > 0 && e->cols > 0 && e->rows <= 4096 &&
-                 e->cols <= 4096 && (int64_t)e->rows * e->cols <= (1 << 20),
-             "%s: bad env sizes", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-// the PointEnv part of a multi-task batch; info_ld as succ_ld above
-static ga_point_env point_part(const ga_multi_point_env* e) {
-  ga_point_env p;
-  p.n = e->n; p.arena_size = e->arena_size; p.done_bonus = e->done_bonus;
-  p.never_done = e->never_done; p.max_episode_length = e->max_episode_length;
-  p.point = e->point; p.goal = e->goal; p.t = e->t; p.success = e->success;
-  return p;
-}
-
-static MultiTaskEnv<PointEnv> to_dev(const ga_multi_point_env* e, int64_t info_ld) {
-  MultiTaskEnv<PointEnv> d;
-  const ga_point_env p = point_part(e);
-  d.n = e->n; d.in = to_dev(&p, info_ld);
-  d.num_tasks = e->num_tasks; d.strategy = e->strategy;
-  d.one_hot = e->mode == GA_TASK_ADD_ONEHOT;
-  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
-  d.payload = e->task_goals; d.last_task = e->last_task; d.resets = e->resets;
-  d.task_id = e->task_id; d.info_ld = info_ld;
-  return d;
-}
-
-static int check_env(const ga_multi_point_env* e, const char* who) {
-  GA_REQUIRE(e && e->point && e->goal && e->t && e->task_goals && e->last_task &&
-                 e->resets, "%s: null env state", who);
-  const ga_point_env p = point_part(e);
-  int rc = check_env(&p, who);
-  if (rc) return rc;
-  GA_REQUIRE(e->num_tasks >= 1 && e->num_tasks <= 256,
-             "%s: num_tasks must be in 1..256 (got %d)", who, e->num_tasks);
-  GA_REQUIRE(e->strategy == GA_TASK_ROUND_ROBIN || e->strategy == GA_TASK_UNIFORM_RANDOM,
-             "%s: unknown sample strategy %d", who, e->strategy);
-  GA_REQUIRE(e->mode == GA_TASK_VANILLA || e->mode == GA_TASK_ADD_ONEHOT,
-             "%s: unknown mode %d", who, e->mode);
-  return GA_OK;
-}
-
-static int env_obs_dim(const ga_point_env*) { return 3; }
-static int env_obs_dim(const ga_grid_env* e) { return e->rows * e->cols; }
-static int env_obs_dim(const ga_multi_point_env* e) {
-  return 3 + (e->mode == GA_TASK_ADD_ONEHOT ? e->num_tasks : 0);
-}
-static int env_act_width(const ga_point_env*) { return 2; }
-static int env_act_width(const ga_grid_env*) { return 1; }
-static int env_act_width(const ga_multi_point_env*) { return 2; }
-
-int ga_build_env_step(const ga_point_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who,
-                      ga_rollout::EnvStepArgsT<ga_rollout::PointEnv>* out) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  GA_REQUIRE(a, "%s: null pointer", who);
-  return build_env_step(to_dev(env, a->Tcap), 3, 2, a, norm, actions, lda, obs, who, out);
-}
-
-int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who,
-                      ga_rollout::EnvStepArgsT<ga_rollout::GridEnv>* out) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  return build_env_step(to_dev(env), env->rows * env->cols, 1, a, norm, actions, lda, obs,
-                        who, out);
-}
-
-int ga_build_env_step(const ga_multi_point_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who,
-                      ga_rollout::EnvStepArgsT<MultiTaskEnv<PointEnv>>* out) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  GA_REQUIRE(a, "%s: null pointer", who);
-  GA_REQUIRE(a->ldo >= env_obs_dim(env),
-             "%s: observation rows of %lld columns are narrower than 3 + num_tasks = %d",
-             who, (long long)a->ldo, env_obs_dim(env));
-  return build_env_step(to_dev(env, a->Tcap), env_obs_dim(env), 2, a, norm, actions, lda,
-                        obs, who, out);
-}
-
-static PointEnv to_dev_step(const ga_point_env* e) { return to_dev(e, 1); }
-static MultiTaskEnv<PointEnv> to_dev_step(const ga_multi_point_env* e) {
-  return to_dev(e, 1);
-}
-static GridEnv to_dev_step(const ga_grid_env* e) { return to_dev(e); }
-
-template <class GaEnv>
-static int env_reset(const GaEnv* env, const uint8_t* mask, float* obs, int64_t ldo,
-                     hipStream_t stream, const char* who) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  GA_REQUIRE(obs && ldo >= env_obs_dim(env), "%s: bad obs buffer", who);
-  const auto e = to_dev_step(env);
-  hipLaunchKernelGGL(env_reset_kernel<decltype(e)>,
-                     dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0, stream, e,
-                     mask, obs, ldo);
-  GA_CHECK_LAUNCH("env_reset");
-  return GA_OK;
-}
-
-template <class GaEnv>
-static int env_step(const GaEnv* env, const float* actions, int64_t lda, float* next_obs,
-                    int64_t ldo, float* reward, uint8_t* step_type, hipStream_t stream,
-                    const char* who) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  GA_REQUIRE(actions && next_obs && reward && step_type, "%s: null pointer", who);
-  GA_REQUIRE(ldo >= env_obs_dim(env) && lda >= env_act_width(env),
-             "%s: leading dimensions too small", who);
-  const auto e = to_dev_step(env);
-  hipLaunchKernelGGL(env_step_kernel<decltype(e)>,
-                     dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0, stream, e,
-                     actions, lda, next_obs, ldo, reward, step_type);
-  GA_CHECK_LAUNCH("env_step");
-  return GA_OK;
-}
-
-template <class GaEnv>
-static int env_step_record(const GaEnv* env, const ga_record_args* a,
-                           const ga_norm_args* norm, const float* actions, int64_t lda,
-                           const float* obs, hipStream_t stream, const char* who) {
-  using Env = decltype(to_dev_step(env));
-  EnvStepArgsT<Env> args;
-  int rc = ga_build_env_step(env, a, norm, actions, lda, obs, who, &args);
-  if (rc) return rc;
-  hipLaunchKernelGGL(env_step_record_kernel<Env>,
-                     dim3((unsigned)ga_ceil_div(a->n, 256)), dim3(256), 0, stream, args);
-  GA_CHECK_LAUNCH("env_step_record");
-  return GA_OK;
-}
-
-// envs/point_env.py:79-98 (reset), :100-170 (step)
-extern "C" int ga_point_env_reset(const ga_point_env* env, const uint8_t* mask, float* obs,
-                                  int64_t ldo, ga_stream_t stream) {
-  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_point_env_reset");
-}
-extern "C" int ga_point_env_step(const ga_point_env* env, const float* actions,
-                                 int64_t lda, const float*, float* next_obs, int64_t ldo,
-                                 float* reward, uint8_t* step_type, ga_stream_t stream) {
-  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
-                  (hipStream_t)stream, "ga_point_env_step");
-}
-// envs/point_env.py:100-170 + normalized_env.py:134-164 + vec_worker.py:176-204
-extern "C" int ga_point_env_step_record_norm(const ga_point_env* env,
-                                             const ga_record_args* rec,
-                                             const ga_norm_args* norm,
-                                             const float* actions, int64_t lda,
-                                             const float* obs, ga_stream_t stream) {
-  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
-                         "ga_point_env_step_record_norm");
-}
-
-// envs/multi_env_wrapper.py:169-194 (reset), :196-226 (step) over PointEnv
-extern "C" int ga_multi_point_env_reset(const ga_multi_point_env* env, const uint8_t* mask,
-                                        float* obs, int64_t ldo, ga_stream_t stream) {
-  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_multi_point_env_reset");
-}
-extern "C" int ga_multi_point_env_step(const ga_multi_point_env* env, const float* actions,
-                                       int64_t lda, const float*, float* next_obs,
-                                       int64_t ldo, float* reward, uint8_t* step_type,
-                                       ga_stream_t stream) {
-  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
-                  (hipStream_t)stream, "ga_multi_point_env_step");
-}
-extern "C" int ga_multi_point_env_step_record_norm(const ga_multi_point_env* env,
-                                                   const ga_record_args* rec,
-                                                   const ga_norm_args* norm,
-                                                   const float* actions, int64_t lda,
-                                                   const float* obs, ga_stream_t stream) {
-  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
-                         "ga_multi_point_env_step_record_norm");
-}
 // the device's task_draw on the host (tests compare it with a numpy restatement)
 extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                       int num_tasks) {
@@ -696,50 +563,6 @@ extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t co
              "ga_multi_env_task_draw: num_tasks must be in 1..256 (got %d)", num_tasks);
   return task_draw((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
                    (uint32_t)env_id, counter, num_tasks);
-}
-
-// envs/grid_world_env.py:91-109 (reset), :111-215 (step)
-extern "C" int ga_grid_env_reset(const ga_grid_env* env, const uint8_t* mask, float* obs,
-                                 int64_t ldo, ga_stream_t stream) {
-  return env_reset(env, mask, obs, ldo, (hipStream_t)stream, "ga_grid_env_reset");
-}
-extern "C" int ga_grid_env_step(const ga_grid_env* env, const float* actions, int64_t lda,
-                                const float*, float* next_obs, int64_t ldo, float* reward,
-                                uint8_t* step_type, ga_stream_t stream) {
-  return env_step(env, actions, lda, next_obs, ldo, reward, step_type,
-                  (hipStream_t)stream, "ga_grid_env_step");
-}
-// envs/grid_world_env.py:111-215 + normalized_env.py:134-164 + vec_worker.py:176-204
-extern "C" int ga_grid_env_step_record_norm(const ga_grid_env* env,
-                                            const ga_record_args* rec,
-                                            const ga_norm_args* norm, const float* actions,
-                                            int64_t lda, const float* obs,
-                                            ga_stream_t stream) {
-  return env_step_record(env, rec, norm, actions, lda, obs, (hipStream_t)stream,
-                         "ga_grid_env_step_record_norm");
-}
-
-// ga_*_env_step_record_norm of any device env (rollout_env_loop.cpp)
-int ga_env_step_record_ref(const ga_env_ref* env, const ga_record_args* rec,
-                           const ga_norm_args* norm, const float* actions, int64_t lda,
-                           const float* obs, ga_stream_t stream) {
-  GA_REQUIRE(env && env->env, "ga_rollout_env_steps: null env");
-  switch (env->kind) {
-    case GA_ENV_SYNTH:
-      return ga_synth_env_step_record_norm((const ga_synth_env*)env->env, rec, norm,
-                                           actions, lda, obs, stream);
-    case GA_ENV_POINT:
-      return ga_point_env_step_record_norm((const ga_point_env*)env->env, rec, norm,
-                                           actions, lda, obs, stream);
-    case GA_ENV_GRID:
-      return ga_grid_env_step_record_norm((const ga_grid_env*)env->env, rec, norm,
-                                          actions, lda, obs, stream);
-    case GA_ENV_MULTI_POINT:
-      return ga_multi_point_env_step_record_norm((const ga_multi_point_env*)env->env, rec,
-                                                 norm, actions, lda, obs, stream);
-  }
-  ga_set_error("ga_rollout_env_steps: unknown env kind %d", env->kind);
-  return -1;
 }
 
 extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,

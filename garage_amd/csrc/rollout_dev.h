@@ -453,23 +453,6 @@ static __device__ __forceinline__ void synth_step_core(
   *step_type = st;
 }
 
-static __device__ __forceinline__ void synth_step_one(
-    const SynthEnv& e, int64_t i, const float* actions, int64_t lda, const float* obs,
-    float* next_obs, int64_t ldo, float* reward, uint8_t* step_type) {
-  EnvPre s;
-  s.ep = e.episode[i];
-  s.t = e.t[i];
-  s.len = e.len[i];
-  s.ep_t = 0;
-  s.has_o = false;
-  float rew;
-  uint8_t st;
-  synth_step_core(e, i, s, actions + i * lda, obs + i * ldo, next_obs + i * ldo, &rew,
-                  &st);
-  reward[i] = rew;
-  step_type[i] = st;
-}
-
 // ---- NormalizedEnv observation / reward path -----------------------------------
 // envs/normalized_env.py:118-132,134-164: per-env exponential moving mean and
 // variance (float64 state, alpha = 0.001 by default); the mean is updated first,
@@ -610,6 +593,15 @@ static __device__ __forceinline__ EnvPre env_prefetch(const EnvStepArgs& a, int6
 }
 
 // the state a step of env i reads (env_prefetch adds the worker's ep_t)
+static __device__ __forceinline__ EnvPre env_pre(const SynthEnv& e, int64_t i) {
+  EnvPre s;
+  s.ep = e.episode[i];
+  s.t = e.t[i];
+  s.len = e.len[i];
+  s.ep_t = 0;
+  s.has_o = false;  // the reward reads its observation entries from memory
+  return s;
+}
 static __device__ __forceinline__ PointPre env_pre(const PointEnv& e, int64_t i) {
   PointPre s;
   s.px = e.point[2 * i];
@@ -693,20 +685,20 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgsT<Env>& a, i
 
 }  // namespace ga_rollout
 
+// The kernel-side env of each C-ABI env struct (rollout.hip).  info_ld: row stride of
+// the env_info buffers (1: [n], Tcap: the [n, Tcap] record buffers).
+ga_rollout::SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t info_ld);
+ga_rollout::PointEnv ga_env_to_dev(const ga_point_env* e, int64_t info_ld);
+ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
+ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_point_env* e,
+                                                             int64_t info_ld);
+template <class GaEnv>
+using ga_env_step_args_t =
+    ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;
+
 // Validated conversion of the C-ABI arguments of the rollout step
-// (include/garage_amd.h) into EnvStepArgsT (rollout.hip), one per env kind
-int ga_build_env_step(const ga_synth_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who, ga_rollout::EnvStepArgs* out);
-int ga_build_env_step(const ga_point_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who,
-                      ga_rollout::EnvStepArgsT<ga_rollout::PointEnv>* out);
-int ga_build_env_step(const ga_grid_env* env, const ga_record_args* a,
-                      const ga_norm_args* norm, const float* actions, int64_t lda,
-                      const float* obs, const char* who,
-                      ga_rollout::EnvStepArgsT<ga_rollout::GridEnv>* out);
-int ga_build_env_step(
-    const ga_multi_point_env* env, const ga_record_args* a, const ga_norm_args* norm,
-    const float* actions, int64_t lda, const float* obs, const char* who,
-    ga_rollout::EnvStepArgsT<ga_rollout::MultiTaskEnv<ga_rollout::PointEnv>>* out);
+// (include/garage_amd.h) into EnvStepArgsT; rollout.hip instantiates it per env kind
+template <class GaEnv>
+int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
+                      const float* actions, int64_t lda, const float* obs, const char* who,
+                      ga_env_step_args_t<GaEnv>* out);

@@ -1,9 +1,11 @@
-// `n_steps` vectorised rollout steps of the synthetic environment enqueued from
-// C++: fused policy step, then env step -> bookkeeping -> reset of finished envs
-// in one launch, ping-ponging the two observation buffers.  Same per-env
-// operations and order as GpuVecWorker._step drives from Python
-// (VecWorker.step_episode, sampler/vec_worker.py:176-204); it exists because the
-// Python/ctypes overhead per launch (~12 us) exceeds the device time of a step.
+// `n_steps` vectorised rollout steps of any device env enqueued from C++: fused
+// policy step, then env step -> bookkeeping -> reset of finished envs in one launch,
+// ping-ponging the two observation buffers -- or the whole rollout in one fused
+// launch where it applies.  Same per-env operations and order as GpuVecWorker._step
+// drives from Python (VecWorker.step_episode, sampler/vec_worker.py:176-204); it
+// exists because the Python/ctypes overhead per launch (~12 us) exceeds the device
+// time of a step.  The env is a tagged pointer (ga_env_ref); the kernels are
+// instantiated per env kind.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -25,36 +27,42 @@ static int fused_env_step_on() {
   }
   return g_fused_env_step;
 }
-int ga_fused_env_step_enabled(void) { return fused_env_step_on(); }
 
-extern "C" int ga_rollout_synth_steps(const ga_mlp_desc* desc, const float* params,
-                                      const ga_head_args* head,
-                                      const ga_synth_env* env,
-                                      const ga_record_args* rec, float* obs_a,
-                                      float* obs_b, const ga_norm_args* norm,
-                                      float* raw_a, float* raw_b, int64_t n_steps,
-                                      ga_stream_t stream) {
+extern "C" int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params,
+                                    const ga_head_args* head, const ga_env_ref* env,
+                                    const ga_record_args* rec, float* obs_a, float* obs_b,
+                                    const ga_norm_args* norm, float* raw_a, float* raw_b,
+                                    int64_t n_steps, ga_stream_t stream) {
   if (!desc || !params || !head || !env || !rec || !obs_a || !obs_b) {
-    ga_set_error("ga_rollout_synth_steps: null pointer");
+    ga_set_error("ga_rollout_env_steps: null pointer");
     return -1;
   }
-  if (norm && norm->act_low && (!norm->act_high || !norm->scaled_action || env->discrete)) {
-    ga_set_error("ga_rollout_synth_steps: action rescale needs bounds, scratch and a "
+  // what the loop needs to know of the env: its size and action columns
+  int64_t n = 0;
+  int act_width = 0, discrete = 0;
+  if (ga_visit_env(env, "ga_rollout_env_steps", [&](auto* e) {
+        n = e->n;
+        act_width = ga_env_act_width(e);
+        discrete = ga_env_discrete(e);
+        return 0;
+      }))
+    return -1;
+  if (norm && norm->act_low && (!norm->act_high || !norm->scaled_action || discrete)) {
+    ga_set_error("ga_rollout_env_steps: action rescale needs bounds, scratch and a "
                  "continuous action space");
     return -1;
   }
-  const bool norm_obs = norm && norm->normalize_obs;
-  if (norm_obs && (!raw_a || !raw_b)) {
-    ga_set_error("ga_rollout_synth_steps: observation normalisation needs the raw "
+  if (norm && norm->normalize_obs && (!raw_a || !raw_b)) {
+    ga_set_error("ga_rollout_env_steps: observation normalisation needs the raw "
                  "observation buffers");
     return -1;
   }
   if (n_steps < 0 || head->col + n_steps > head->Tcap) {
-    ga_set_error("ga_rollout_synth_steps: steps exceed the rollout buffer");
+    ga_set_error("ga_rollout_env_steps: steps exceed the rollout buffer");
     return -1;
   }
   if (!ga_policy_step_fused_supported(desc)) {
-    ga_set_error("ga_rollout_synth_steps: network not supported by the fused step");
+    ga_set_error("ga_rollout_env_steps: network not supported by the fused step");
     return -1;
   }
   float* cur = obs_a;
@@ -88,22 +96,20 @@ extern "C" int ga_rollout_synth_steps(const ga_mlp_desc* desc, const float* para
       nm.raw_obs = raw_cur;
       nm.raw_next_obs = raw_nxt;
     }
-    int rc;
-    rc = ga_policy_step_fused_f32(desc, params, &h, stream);
+    int rc = ga_policy_step_fused_f32(desc, params, &h, stream);
     if (rc) return rc;
     // env step -> bookkeeping -> reset of the finished envs: one launch
     const float* env_action = h.action;
     if (norm && nm.act_low) {
       // NormalizedEnv.step: the wrapped env sees the rescaled, clipped action; the
       // batch keeps the policy's own (normalized_env.py:90-114)
-      rc = ga_action_rescale_f32(env->n, env->act_dim, h.action, h.lda, nm.act_low,
-                                 nm.act_high, nm.expected_action_scale,
-                                 nm.scaled_action, h.lda, stream);
+      rc = ga_action_rescale_f32(n, act_width, h.action, h.lda, nm.act_low, nm.act_high,
+                                 nm.expected_action_scale, nm.scaled_action, h.lda,
+                                 stream);
       if (rc) return rc;
       env_action = nm.scaled_action;
     }
-    rc = ga_synth_env_step_record_norm(env, &r, norm ? &nm : nullptr, env_action, h.lda,
-                                       cur, stream);
+    rc = ga_env_step_record(env, &r, norm ? &nm : nullptr, env_action, h.lda, cur, stream);
     if (rc) return rc;
     float* t = cur;
     cur = nxt;

@@ -116,7 +116,54 @@ class VecEnv:
         return None
 
 
-class SyntheticVecEnv(VecEnv):
+class _DeviceVecEnv(VecEnv):
+    """A batch stepped by the HIP kernels: the batch protocol over ``ga_env_*``
+    and the ``ga_env_ref`` of the subclass's C struct (``_set_struct``), and
+    pickling -- plain attributes as they are, the listed state tensors through
+    the host (trainer.py:263-293 pickles algo + env)."""
+
+    _KIND = None
+    _STATE = ()
+
+    def _set_struct(self, c):
+        self._c = c
+        self._ref = _lib.env_ref(self._KIND, c)
+
+    def reset_all(self):
+        call('ga_env_reset', C.byref(self._ref), None, dptr(self.obs),
+             self.obs.stride(0), stream_ptr())
+
+    def step_all(self, actions):
+        call('ga_env_step', C.byref(self._ref), dptr(actions),
+             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
+             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
+             stream_ptr())
+
+    def reset_where(self, done):
+        call('ga_env_reset', C.byref(self._ref), dptr(done),
+             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
+
+    def native_env_ref(self, info_bufs):
+        return self._ref, self._c
+
+    def __getstate__(self):
+        state = {
+            k: v for k, v in self.__dict__.items()
+            if not torch.is_tensor(v) and k not in ('_c', '_ref', 'device')
+        }
+        state['_saved'] = {k: getattr(self, k).cpu().numpy()
+                           for k in self._STATE + ('obs', )}
+        return state
+
+    def __setstate__(self, state):
+        saved = state.pop('_saved')
+        self.__dict__.update(state)
+        self._init_device(None)
+        for k, v in saved.items():
+            getattr(self, k).copy_(torch.from_numpy(v))
+
+
+class SyntheticVecEnv(_DeviceVecEnv):
     """``n_envs`` synthetic environments stepped by one HIP kernel.
 
     Observation ``t`` of episode ``e`` of env ``i``: ``obs_dim`` unit-variance
@@ -126,6 +173,9 @@ class SyntheticVecEnv(VecEnv):
     TIMEOUT when ``L == max_episode_length`` else TERMINAL.  ``oracle/envs.py``
     holds the bit-identical per-env CPU twin used by the parity tests.
     """
+
+    _KIND = _lib.ENV_SYNTH
+    _STATE = ('_episode', '_t', '_len')
 
     def __init__(self, n_envs, obs_dim, act_dim, max_episode_length, *,
                  min_len=None, seed=0, discrete=False, env_id0=0, device=None,
@@ -164,40 +214,7 @@ class SyntheticVecEnv(VecEnv):
         e.episode = self._episode.data_ptr()
         e.t = self._t.data_ptr()
         e.len = self._len.data_ptr()
-        self._c = e
-
-    def reset_all(self):
-        call('ga_synth_env_reset', C.byref(self._c), None, dptr(self.obs),
-             self.obs.stride(0), stream_ptr())
-
-    def step_all(self, actions):
-        call('ga_synth_env_step', C.byref(self._c), dptr(actions),
-             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
-             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
-             stream_ptr())
-
-    def reset_where(self, done):
-        call('ga_synth_env_reset', C.byref(self._c), dptr(done),
-             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
-
-    # -- snapshot support (trainer.py:263-293 pickles algo + env) -----------
-    def __getstate__(self):
-        state = {
-            k: v for k, v in self.__dict__.items()
-            if not torch.is_tensor(v) and k not in ('_c', 'device')
-        }
-        state['_saved'] = {
-            k: getattr(self, k).cpu().numpy()
-            for k in ('_episode', '_t', '_len', 'obs')
-        }
-        return state
-
-    def __setstate__(self, state):
-        saved = state.pop('_saved')
-        self.__dict__.update(state)
-        self._init_device(None)
-        for k, v in saved.items():
-            getattr(self, k).copy_(torch.from_numpy(v))
+        self._set_struct(e)
 
 
 def _check_finite_length(max_episode_length):
@@ -209,30 +226,7 @@ def _check_finite_length(max_episode_length):
     return max_episode_length
 
 
-class _DeviceStateEnv(VecEnv):
-    """Pickling of a device batch: plain attributes as they are, the listed
-    state tensors through the host."""
-
-    _STATE = ()
-
-    def __getstate__(self):
-        state = {
-            k: v for k, v in self.__dict__.items()
-            if not torch.is_tensor(v) and k not in ('_c', 'device')
-        }
-        state['_saved'] = {k: getattr(self, k).cpu().numpy()
-                           for k in self._STATE + ('obs', )}
-        return state
-
-    def __setstate__(self, state):
-        saved = state.pop('_saved')
-        self.__dict__.update(state)
-        self._init_device(None)
-        for k, v in saved.items():
-            getattr(self, k).copy_(torch.from_numpy(v))
-
-
-class PointVecEnv(_DeviceStateEnv):
+class PointVecEnv(_DeviceVecEnv):
     """``n_envs`` copies of ``garage.envs.PointEnv`` (``envs/point_env.py``)
     stepped by one HIP kernel, one thread per env, in numpy's fp32 arithmetic:
     observations, rewards, step types and ``env_info['success']`` equal the
@@ -258,6 +252,7 @@ class PointVecEnv(_DeviceStateEnv):
     """
 
     env_info_specs = {'success': np.bool_}
+    _KIND = _lib.ENV_POINT
     _STATE = ('_point', 'goals', '_t')
 
     def __init__(self, n_envs, goal=(1., 1.), arena_size=5., done_bonus=0.,
@@ -289,7 +284,7 @@ class PointVecEnv(_DeviceStateEnv):
         self.goals = torch.zeros(n, 2, dtype=torch.float32, device=device)
         self._t = torch.zeros(n, dtype=torch.int32, device=device)
         self._success = torch.zeros(n, dtype=torch.uint8, device=device)
-        self._c = self._struct(self._success)
+        self._set_struct(self._struct(self._success))
 
     def _struct(self, success):
         e = _lib.PointEnv()
@@ -322,21 +317,6 @@ class PointVecEnv(_DeviceStateEnv):
                           for t in tasks])
         self.goals.copy_(torch.from_numpy(goals))
 
-    # -- batch protocol ------------------------------------------------------------
-    def reset_all(self):
-        call('ga_point_env_reset', C.byref(self._c), None, dptr(self.obs),
-             self.obs.stride(0), stream_ptr())
-
-    def step_all(self, actions):
-        call('ga_point_env_step', C.byref(self._c), dptr(actions),
-             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
-             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
-             stream_ptr())
-
-    def reset_where(self, done):
-        call('ga_point_env_reset', C.byref(self._c), dptr(done),
-             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
-
     def step_env_infos(self):
         return {'success': self._success}
 
@@ -345,9 +325,7 @@ class PointVecEnv(_DeviceStateEnv):
 
     def native_env_ref(self, info_bufs):
         e = self._struct(info_bufs['success'])
-        ref = _lib.EnvRef(kind=_lib.ENV_POINT,
-                          env=C.cast(C.pointer(e), C.c_void_p))
-        return ref, e
+        return _lib.env_ref(self._KIND, e), e
 
 
 def round_robin_strategy(num_tasks, last_task=None):
@@ -383,7 +361,7 @@ def task_draw(seed, env_id, counter, num_tasks):
     return task
 
 
-class MultiTaskPointVecEnv(_DeviceStateEnv):
+class MultiTaskPointVecEnv(_DeviceVecEnv):
     """``n_envs`` copies of ``MultiEnvWrapper([PointEnv(goal=g, ...) for g in
     goals], sample_strategy, mode, env_names)`` (``envs/multi_env_wrapper.py``)
     stepped by one HIP kernel inside the one-launch rollout.
@@ -427,6 +405,7 @@ class MultiTaskPointVecEnv(_DeviceStateEnv):
       reset, where the reference has ``None``).
     """
 
+    _KIND = _lib.ENV_MULTI_POINT
     _STATE = ('_point', '_goal', '_t', '_last_task', '_resets')
 
     def __init__(self, n_envs, goals, sample_strategy=uniform_random_strategy,
@@ -508,7 +487,7 @@ class MultiTaskPointVecEnv(_DeviceStateEnv):
         self._resets = torch.zeros(n, dtype=torch.int32, device=device)
         self._success = torch.zeros(n, dtype=torch.uint8, device=device)
         self._task_id = torch.zeros(n, dtype=torch.uint8, device=device)
-        self._c = self._struct(self._success, self._task_id)
+        self._set_struct(self._struct(self._success, self._task_id))
 
     def _struct(self, success, task_id):
         e = _lib.MultiPointEnv()
@@ -528,20 +507,6 @@ class MultiTaskPointVecEnv(_DeviceStateEnv):
         e.resets = self._resets.data_ptr()
         return e
 
-    def reset_all(self):
-        call('ga_multi_point_env_reset', C.byref(self._c), None,
-             dptr(self.obs), self.obs.stride(0), stream_ptr())
-
-    def step_all(self, actions):
-        call('ga_multi_point_env_step', C.byref(self._c), dptr(actions),
-             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
-             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
-             stream_ptr())
-
-    def reset_where(self, done):
-        call('ga_multi_point_env_reset', C.byref(self._c), dptr(done),
-             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
-
     def step_env_infos(self):
         return {'success': self._success, 'task_id': self._task_id}
 
@@ -555,9 +520,7 @@ class MultiTaskPointVecEnv(_DeviceStateEnv):
 
     def native_env_ref(self, info_bufs):
         e = self._struct(info_bufs['success'], info_bufs['task_id'])
-        ref = _lib.EnvRef(kind=_lib.ENV_MULTI_POINT,
-                          env=C.cast(C.pointer(e), C.c_void_p))
-        return ref, e
+        return _lib.env_ref(self._KIND, e), e
 
 
 # garage.envs.grid_world_env.MAPS by name ('F' / '.' free, 'S' start, 'W' / 'x'
@@ -585,7 +548,7 @@ def _grid_rows(desc):
     return rows
 
 
-class GridWorldVecEnv(_DeviceStateEnv):
+class GridWorldVecEnv(_DeviceVecEnv):
     """``n_envs`` copies of ``garage.envs.GridWorldEnv``
     (``envs/grid_world_env.py``) stepped by one HIP kernel, one thread per env.
 
@@ -598,6 +561,7 @@ class GridWorldVecEnv(_DeviceStateEnv):
     finite.
     """
 
+    _KIND = _lib.ENV_GRID
     _STATE = ('_state', '_t')
 
     def __init__(self, n_envs, desc='4x4', max_episode_length=None,
@@ -648,26 +612,7 @@ class GridWorldVecEnv(_DeviceStateEnv):
         e.max_episode_length = self.max_episode_length
         e.map, e.start = self._map.data_ptr(), self._start.data_ptr()
         e.state, e.t = self._state.data_ptr(), self._t.data_ptr()
-        self._c = e
-
-    def reset_all(self):
-        call('ga_grid_env_reset', C.byref(self._c), None, dptr(self.obs),
-             self.obs.stride(0), stream_ptr())
-
-    def step_all(self, actions):
-        call('ga_grid_env_step', C.byref(self._c), dptr(actions),
-             actions.stride(0), dptr(self.obs), dptr(self.next_obs),
-             self.obs.stride(0), dptr(self.reward), dptr(self.step_type),
-             stream_ptr())
-
-    def reset_where(self, done):
-        call('ga_grid_env_reset', C.byref(self._c), dptr(done),
-             dptr(self.next_obs), self.next_obs.stride(0), stream_ptr())
-
-    def native_env_ref(self, info_bufs):
-        ref = _lib.EnvRef(kind=_lib.ENV_GRID,
-                          env=C.cast(C.pointer(self._c), C.c_void_p))
-        return ref, self._c
+        self._set_struct(e)
 
 
 class NormalizedVecEnv(VecEnv):

@@ -394,35 +394,27 @@ class GpuVecWorker:
         return r
 
     def _native_steps(self, b, col, n_steps):
-        """``n_steps`` steps enqueued by ``ga_rollout_synth_steps`` (synthetic
-        env) or ``ga_rollout_env_steps`` (the other device env batches): fused
-        policy step, device RNG; False when not applicable."""
-        from garage_amd.envs import NormalizedVecEnv, SyntheticVecEnv
+        """``n_steps`` steps enqueued by ``ga_rollout_env_steps`` (device env
+        batches): fused policy step, device RNG; False when not applicable."""
+        from garage_amd.envs import NormalizedVecEnv
         env = self.env
         inner, norm = env, None
         if type(env) is NormalizedVecEnv:  # statistics fused into the env step
             inner, norm = env._env, env.norm_args()
-        synth = type(inner) is SyntheticVecEnv
-        ref = None if synth else inner.native_env_ref(b['dev_infos'])
-        if (n_steps <= 0 or not (synth or ref is not None)
-                or self._noise_fn is not None or not self._fused_ok()):
+        ref = inner.native_env_ref(b['dev_infos'])
+        if (n_steps <= 0 or ref is None or self._noise_fn is not None
+                or not self._fused_ok()):
             return False
+        env_ref, _keepalive = ref
         a = self._head_args(b, col, True)
         r = self._record_args(b, col)
         raw = norm is not None and norm.normalize_obs
-        tail = (C.byref(r), dptr(env.obs), dptr(env.next_obs),
-                None if norm is None else C.byref(norm),
-                dptr(inner.obs) if raw else None,
-                dptr(inner.next_obs) if raw else None, n_steps, stream_ptr())
-        if synth:
-            call('ga_rollout_synth_steps', C.byref(self.agent.net._desc),
-                 dptr(self.agent.net.params), C.byref(a), C.byref(inner._c),
-                 *tail)
-        else:
-            env_ref, _keepalive = ref
-            call('ga_rollout_env_steps', C.byref(self.agent.net._desc),
-                 dptr(self.agent.net.params), C.byref(a), C.byref(env_ref),
-                 *tail)
+        call('ga_rollout_env_steps', C.byref(self.agent.net._desc),
+             dptr(self.agent.net.params), C.byref(a), C.byref(env_ref),
+             C.byref(r), dptr(env.obs), dptr(env.next_obs),
+             None if norm is None else C.byref(norm),
+             dptr(inner.obs) if raw else None,
+             dptr(inner.next_obs) if raw else None, n_steps, stream_ptr())
         if n_steps % 2:
             env.advance()
         self._global_step += n_steps

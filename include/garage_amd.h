@@ -33,7 +33,7 @@ extern "C" {
 
 typedef void* ga_stream_t; /* hipStream_t */
 
-GA_API int ga_abi_version(void); /* 4 */
+GA_API int ga_abi_version(void); /* 5 */
 /* Wherever a policy's scalar std parameter crosses this interface it comes as
  * (log_std pointer, has_min, min_log_std, has_max, max_log_std) and goes through
  * GaussianMLPBaseModule.forward's transformation
@@ -378,7 +378,8 @@ GA_API int ga_sub_scalar_f32(float* x, int64_t n, const double* scalar, ga_strea
 
 /* ---- rollout ----------------------------------------------------------------
  * Synthetic batched environment (the benchmark workload of BASELINE.json;
- * Environment.reset/step contract of _environment.py:237-276). */
+ * Environment.reset/step contract of _environment.py:237-276), stepped through
+ * ga_env_reset / ga_env_step / ga_env_step_record below like every device env. */
 typedef struct {
   int64_t n;
   int64_t env_id0;
@@ -388,12 +389,6 @@ typedef struct {
   int32_t* t;       /* [n] */
   int32_t* len;     /* [n] */
 } ga_synth_env;
-
-GA_API int ga_synth_env_reset(const ga_synth_env* env, const uint8_t* mask, float* obs,
-                              int64_t ldo, ga_stream_t stream);
-GA_API int ga_synth_env_step(const ga_synth_env* env, const float* actions, int64_t lda,
-                             const float* obs, float* next_obs, int64_t ldo, float* reward,
-                             uint8_t* step_type, ga_stream_t stream);
 
 /* NormalizedEnv's observation / reward normalisation
  * (envs/normalized_env.py:118-132,134-164): per-env float64 moving mean and
@@ -458,19 +453,13 @@ typedef struct {
                             (sampler/fragment_worker.py:114-115) */
 } ga_record_args;
 GA_API int ga_record_step(const ga_record_args* args, ga_stream_t stream);
-/* ga_synth_env_step -> ga_record_step -> ga_synth_env_reset(done) of the synthetic
- * environment in one launch (same per-env results; rec->next_obs receives the next
- * observation, or the first observation of the new episode where one ended). */
-GA_API int ga_synth_env_step_record(const ga_synth_env* env, const ga_record_args* rec,
-                                    const float* actions, int64_t lda, const float* obs,
-                                    ga_stream_t stream);
-/* ... with NormalizedEnv's observation / reward normalisation fused in (the
- * north star's "fused obs-normalise"): the env steps on its raw observations
+/* NormalizedEnv's observation / reward normalisation fused into ga_env_step_record
+ * (the north star's "fused obs-normalise"): the env steps on its raw observations
  * (raw_obs -> raw_next_obs), the moving statistics are updated and
  * rec->next_obs receives the normalised observation the policy sees next -- for
  * the step's observation (recorded as the terminal one where an episode ends)
  * and again for the first observation of a new episode, in that order, as
- * envs/normalized_env.py:134-151 does.  norm == NULL: no normalisation. */
+ * envs/normalized_env.py:134-151 does. */
 typedef struct ga_norm_args {
   int32_t normalize_obs, normalize_reward;
   double* obs_mean;      /* [n, obs_dim] float64 moving mean */
@@ -488,52 +477,18 @@ typedef struct ga_norm_args {
   float expected_action_scale;
   float* scaled_action;
 } ga_norm_args;
-GA_API int ga_synth_env_step_record_norm(const ga_synth_env* env, const ga_record_args* rec,
-                                         const ga_norm_args* norm, const float* actions,
-                                         int64_t lda, const float* obs, ga_stream_t stream);
-
-/* ga_policy_step_fused_f32 followed, per env and in the same launch, by what
- * ga_synth_env_step_record_norm does (env step with `head->action`, NormalizedEnv
- * statistics, bookkeeping, reset of the finished envs), for n_steps consecutive
- * rollout steps of the synthetic env in ONE launch: a workgroup takes its 32 envs
- * through all of them (envs do not interact within a rollout), alternating between
- * the buffers head->obs / rec->next_obs (norm: raw_obs / raw_next_obs); columns
- * head->col .. head->col + n_steps - 1, Philox counters head->step + s.  Device
- * noise only (head->noise must be null for n_steps > 1). */
-GA_API int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                        const ga_head_args* head, const ga_synth_env* env,
-                                        const ga_record_args* rec, const ga_norm_args* norm,
-                                        int64_t n_steps, ga_stream_t stream);
-/* 1 (default): ga_rollout_synth_steps takes that launch (unless actions are
- * rescaled between policy and env); 0: policy step and env step as two launches. */
-GA_API int ga_set_fused_env_step(int on);
-/* n_steps consecutive vectorised steps (fused policy step, synthetic env step,
- * bookkeeping, reset of finished envs) starting at head->col / head->step,
- * alternating the observation buffers obs_a (current) / obs_b; after an odd
- * number of steps the current observations are in obs_b.  The while-loop body of
- * VecWorker.rollout (sampler/default_worker.py:176-186 + vec_worker.py:176-204)
- * enqueued natively.  With norm != NULL (NormalizedEnv around the synthetic env)
- * obs_a / obs_b hold the normalised observations and raw_a / raw_b, alternating
- * the same way, the env's own. */
-GA_API int ga_rollout_synth_steps(const ga_mlp_desc* desc, const float* params,
-                                  const ga_head_args* head, const ga_synth_env* env,
-                                  const ga_record_args* rec, float* obs_a, float* obs_b,
-                                  const ga_norm_args* norm, float* raw_a, float* raw_b,
-                                  int64_t n_steps, ga_stream_t stream);
 
 /* ---- device copies of the reference's own environments ---------------------
  * One thread per env, numpy's fp32 arithmetic, the same entry points as the
- * synthetic env: reset (mask == NULL: all), step (obs is not read: the state is the
- * env's own), and the fused step + NormalizedEnv statistics + bookkeeping + reset of
- * the finished envs (what ga_synth_env_step_record_norm does for the synthetic
- * env).  max_episode_length must be finite (1..65535).
+ * synthetic env (ga_env_reset / ga_env_step / ga_env_step_record below).
+ * max_episode_length must be finite (1..65535).
  *
  * PointEnv (envs/point_env.py:79-170): a = clip(action, -0.1, 0.1), point =
  * clip(point + a, -arena_size, arena_size), dist = |point - goal|, success = dist <
  * |(-0.1, -0.1)|, reward = -dist (+ done_bonus on success), done = success and not
  * never_done; observation (x, y, dist), obs_dim 3, act_dim 2.  `success` (optional)
- * receives env_info['success'] as uint8: success[i] from ga_point_env_step,
- * success[i * rec->Tcap + rec->col] from the record entries (env-major [n, Tcap],
+ * receives env_info['success'] as uint8: success[i] from ga_env_step,
+ * success[i * rec->Tcap + rec->col] from ga_env_step_record (env-major [n, Tcap],
  * like the other rollout buffers). */
 typedef struct {
   int64_t n;
@@ -544,15 +499,6 @@ typedef struct {
   int32_t* t;        /* [n] steps taken in the current episode */
   uint8_t* success;  /* optional, see above */
 } ga_point_env;
-
-GA_API int ga_point_env_reset(const ga_point_env* env, const uint8_t* mask, float* obs,
-                              int64_t ldo, ga_stream_t stream);
-GA_API int ga_point_env_step(const ga_point_env* env, const float* actions, int64_t lda,
-                             const float* obs, float* next_obs, int64_t ldo, float* reward,
-                             uint8_t* step_type, ga_stream_t stream);
-GA_API int ga_point_env_step_record_norm(const ga_point_env* env, const ga_record_args* rec,
-                                         const ga_norm_args* norm, const float* actions,
-                                         int64_t lda, const float* obs, ga_stream_t stream);
 
 /* GridWorldEnv (envs/grid_world_env.py:111-215): `map` holds every env's grid as
  * rows * cols cell codes (0 = F or S, 1 = W, 2 = H, 3 = G); action 0..3 = left, down,
@@ -568,20 +514,11 @@ typedef struct {
   int32_t* t;           /* [n] steps taken in the current episode */
 } ga_grid_env;
 
-GA_API int ga_grid_env_reset(const ga_grid_env* env, const uint8_t* mask, float* obs,
-                             int64_t ldo, ga_stream_t stream);
-GA_API int ga_grid_env_step(const ga_grid_env* env, const float* actions, int64_t lda,
-                            const float* obs, float* next_obs, int64_t ldo, float* reward,
-                            uint8_t* step_type, ga_stream_t stream);
-GA_API int ga_grid_env_step_record_norm(const ga_grid_env* env, const ga_record_args* rec,
-                                        const ga_norm_args* norm, const float* actions,
-                                        int64_t lda, const float* obs, ga_stream_t stream);
-
 /* MultiEnvWrapper([PointEnv(goal=task_goals[k], ...) for k < num_tasks], strategy, mode)
  * (envs/multi_env_wrapper.py:169-226), one wrapper per member.  The fields of
  * ga_point_env (the other PointEnv parameters are shared by the tasks) plus the task
- * layer: every reset -- ga_multi_point_env_reset, and the reset of a finished env
- * inside the record entries -- picks the member's next task from its own last_task
+ * layer: every reset -- ga_env_reset, and the reset of a finished env
+ * inside ga_env_step_record -- picks the member's next task from its own last_task
  * (round robin: 0 after -1, else (last + 1) % num_tasks; uniform random: the first
  * word of Philox4x32-10 keyed (seed; env index, the member's reset counter), scaled
  * to [0, num_tasks) by the high half of u * num_tasks -- the reference draws from
@@ -611,17 +548,6 @@ typedef struct {
   uint8_t* task_id;        /* optional, see above */
 } ga_multi_point_env;
 
-GA_API int ga_multi_point_env_reset(const ga_multi_point_env* env, const uint8_t* mask,
-                                    float* obs, int64_t ldo, ga_stream_t stream);
-GA_API int ga_multi_point_env_step(const ga_multi_point_env* env, const float* actions,
-                                   int64_t lda, const float* obs, float* next_obs,
-                                   int64_t ldo, float* reward, uint8_t* step_type,
-                                   ga_stream_t stream);
-GA_API int ga_multi_point_env_step_record_norm(const ga_multi_point_env* env,
-                                               const ga_record_args* rec,
-                                               const ga_norm_args* norm,
-                                               const float* actions, int64_t lda,
-                                               const float* obs, ga_stream_t stream);
 /* Host-only (no GPU needed): the task the uniform random strategy gives env `env_id`
  * at its reset number `counter` (< 0: num_tasks outside 1..256). */
 GA_API int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
@@ -638,10 +564,51 @@ typedef struct {
   const void* env;
 } ga_env_ref;
 
-/* ga_rollout_synth_steps for any device env (the while-loop body of VecWorker.rollout,
- * sampler/default_worker.py:176-186 + vec_worker.py:176-204): same arguments, same
- * buffers, same one-launch rollout where it applies (otherwise a fused policy step
- * and an env step per rollout step). */
+/* One thread per env, one launch per call, for every env kind.
+ * ga_env_reset: Environment.reset of the envs with mask != 0 (mask == NULL: all); obs
+ * [n, ldo] receives their first observations (envs/point_env.py:79-98,
+ * grid_world_env.py:91-109, multi_env_wrapper.py:169-194).
+ * ga_env_step: Environment.step with actions [n, lda] into next_obs, reward [n] and
+ * step_type [n] (envs/point_env.py:100-170, grid_world_env.py:111-215,
+ * multi_env_wrapper.py:196-226); `obs`, the current observations, is read by the
+ * synthetic env only (the state of the others is their own).
+ * ga_env_step_record: ga_env_step -> NormalizedEnv statistics of `norm` (may be
+ * NULL; normalized_env.py:134-164) -> ga_record_step -> ga_env_reset of the finished
+ * envs in one launch, same per-env results (vec_worker.py:176-204): rec->next_obs
+ * receives the next observation, or the first one of the new episode where one
+ * ended. */
+GA_API int ga_env_reset(const ga_env_ref* env, const uint8_t* mask, float* obs, int64_t ldo,
+                        ga_stream_t stream);
+GA_API int ga_env_step(const ga_env_ref* env, const float* actions, int64_t lda,
+                       const float* obs, float* next_obs, int64_t ldo, float* reward,
+                       uint8_t* step_type, ga_stream_t stream);
+GA_API int ga_env_step_record(const ga_env_ref* env, const ga_record_args* rec,
+                              const ga_norm_args* norm, const float* actions, int64_t lda,
+                              const float* obs, ga_stream_t stream);
+
+/* ga_policy_step_fused_f32 followed, per env and in the same launch, by what
+ * ga_env_step_record does (env step with `head->action`, NormalizedEnv
+ * statistics, bookkeeping, reset of the finished envs), for n_steps consecutive
+ * rollout steps in ONE launch: a workgroup takes its 32 envs
+ * through all of them (envs do not interact within a rollout), alternating between
+ * the buffers head->obs / rec->next_obs (norm: raw_obs / raw_next_obs); columns
+ * head->col .. head->col + n_steps - 1, Philox counters head->step + s.  Device
+ * noise only (head->noise must be null for n_steps > 1). */
+GA_API int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
+                                        const ga_head_args* head, const ga_env_ref* env,
+                                        const ga_record_args* rec, const ga_norm_args* norm,
+                                        int64_t n_steps, ga_stream_t stream);
+/* 1 (default): ga_rollout_env_steps takes that launch (unless actions are
+ * rescaled between policy and env); 0: policy step and env step as two launches. */
+GA_API int ga_set_fused_env_step(int on);
+/* n_steps consecutive vectorised steps (fused policy step, env step,
+ * bookkeeping, reset of finished envs) starting at head->col / head->step,
+ * alternating the observation buffers obs_a (current) / obs_b; after an odd
+ * number of steps the current observations are in obs_b.  The while-loop body of
+ * VecWorker.rollout (sampler/default_worker.py:176-186 + vec_worker.py:176-204)
+ * enqueued natively.  With norm != NULL (NormalizedEnv around the env)
+ * obs_a / obs_b hold the normalised observations and raw_a / raw_b, alternating
+ * the same way, the env's own. */
 GA_API int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params,
                                 const ga_head_args* head, const ga_env_ref* env,
                                 const ga_record_args* rec, float* obs_a, float* obs_b,

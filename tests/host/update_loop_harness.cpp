@@ -1,5 +1,4 @@
-// Host-logic harness for the C++ epoch loops (garage_amd/csrc/update.cpp,
-// rollout_loop.cpp), built with -fsanitize=address,undefined on the CPU
+// Host-logic harness for the C++ epoch loops (garage_amd/csrc/update.cpp), built with -fsanitize=address,undefined on the CPU
 // (`make asan-host`; SURVEY.md section 5 "sanitizers": GPU sanitizers are not
 // available, the host loops are plain C++).  Every kernel entry point the loops
 // call -- and the handful of HIP runtime calls they make -- is replaced by a fake
@@ -316,32 +315,6 @@ int ga_narrow_train_step(const float*, const int64_t*, const int64_t*, int in_w,
   }
   return 0;
 }
-int ga_policy_step_fused_supported(const ga_mlp_desc*) { return 1; }
-int ga_policy_step_fused_f32(const ga_mlp_desc*, const float*, const ga_head_args* h,
-                             ga_stream_t) {
-  logf("policy_step col=%lld step=%u obs=%p", (long long)h->col, h->step, (void*)h->obs);
-  return 0;
-}
-int ga_policy_env_step_fused_f32(const ga_mlp_desc*, const float*, const ga_head_args* h,
-                                 const ga_synth_env*, const ga_record_args* r,
-                                 const ga_norm_args* nm, int64_t n_steps, ga_stream_t) {
-  logf("policy_env_step col=%lld step=%u obs=%p next=%p norm=%d steps=%lld",
-       (long long)h->col, h->step, (void*)h->obs, (void*)r->next_obs, nm != nullptr,
-       (long long)n_steps);
-  return 0;
-}
-int ga_synth_env_step_record_norm(const ga_synth_env*, const ga_record_args* r,
-                                  const ga_norm_args* nm, const float* act, int64_t,
-                                  const float* obs, ga_stream_t) {
-  logf("env_step col=%lld obs=%p next=%p act=%p norm=%d", (long long)r->col, (void*)obs,
-       (void*)r->next_obs, (void*)act, nm != nullptr);
-  return 0;
-}
-int ga_action_rescale_f32(int64_t n, int A, const float*, int64_t, const float*,
-                          const float*, float s, float*, int64_t, ga_stream_t) {
-  logf("rescale n=%lld A=%d s=%.2f", (long long)n, A, s);
-  return 0;
-}
 }  // extern "C"
 
 // ---- checks ------------------------------------------------------------------
@@ -549,39 +522,6 @@ int main() {
     CHECK(count("narrow M=100 in=4 H=64 out=2") == 2 && count("fwd") == 0);
     CHECK(count("reduce_regions n=6 step=1") == 1 && count("reduce_regions n=6 step=2") == 1);
     CHECK(count("  region beg=4 n=256 parts=2") == 2);  // W1, both steps
-  }
-  // 8. the native rollout loop ping-pongs the observation buffers
-  {
-    g_log.clear();
-    ga_head_args h;
-    memset(&h, 0, sizeof(h));
-    h.col = 3; h.Tcap = 16; h.step = 100;
-    ga_synth_env env;
-    memset(&env, 0, sizeof(env));
-    env.n = 4; env.act_dim = 2;
-    ga_record_args rec;
-    memset(&rec, 0, sizeof(rec));
-    float A[4], B[4];
-    Net pol(17, 64, 64, 6);
-    CHECK(ga_rollout_synth_steps(&pol.d, pol.params.data(), &h, &env, &rec, A, B, nullptr,
-                                 nullptr, nullptr, 3, nullptr) == 0);
-    // (ONE launch for all the steps by default)
-    CHECK(count("policy_env_step") == 1 && count("policy_step ") == 0);
-    char want[160];
-    snprintf(want, sizeof(want),
-             "policy_env_step col=3 step=100 obs=%p next=%p norm=0 steps=3", (void*)A,
-             (void*)B);
-    CHECK(count(want) == 1);
-    ga_set_fused_env_step(0);
-    g_log.clear();
-    CHECK(ga_rollout_synth_steps(&pol.d, pol.params.data(), &h, &env, &rec, A, B, nullptr,
-                                 nullptr, nullptr, 3, nullptr) == 0);
-    CHECK(count("policy_step") == 3 && count("env_step col") == 3);
-    snprintf(want, sizeof(want), "env_step col=4 obs=%p next=%p", (void*)B, (void*)A);
-    CHECK(count(want) == 1);
-    ga_set_fused_env_step(1);
-    CHECK(ga_rollout_synth_steps(&pol.d, pol.params.data(), &h, &env, &rec, A, B, nullptr,
-                                 nullptr, nullptr, 14, nullptr) != 0);  // past Tcap
   }
   // 8b. Two 256-wide passes with equal shapes: ga_update_epoch_pair runs step k of
   //     both as four pair launches on stream_a, ordered against stream_b on both

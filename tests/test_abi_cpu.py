@@ -39,7 +39,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     # the ctypes table and the header must describe the same set
     assert sorted(_lib.SIGNATURES) == names
-    assert lib.ga_abi_version() == 4
+    assert lib.ga_abi_version() == 5
     syms = _dynamic_symbols(_lib.LIB_PATH)
     functions = sorted(n for t, n in syms if t in ('T', 'W'))
     assert functions == names
@@ -99,13 +99,12 @@ def test_product_never_imports_the_oracle():
 
 
 def test_host_loops_under_address_sanitizer():
-    """``make asan-host``: the C++ epoch and rollout loops (update.cpp,
-    rollout_loop.cpp) compiled with ``-fsanitize=address,undefined`` for the CPU
+    """``make asan-host``: the C++ epoch loops (update.cpp) compiled with ``-fsanitize=address,undefined`` for the CPU
     and run against recording fakes of every kernel entry point
     (tests/host/update_loop_harness.cpp): minibatch ranges, the data-parallel even
     split and per-step scales, phase 1, the interleaving of two passes, argument
-    errors, the fused step's scratch layout and regions, the rollout loop's buffer
-    ping-pong.  GPU sanitizers are not available on this pool."""
+    errors, the fused step's scratch layout and regions (the rollout loop has its own
+    harness, ``make asan-env-loop``).  GPU sanitizers are not available on this pool."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run(['make', '-C', root, 'asan-host'], capture_output=True,

@@ -227,25 +227,68 @@ def test_new_ctypes_structs_match_the_header():
 def test_new_entry_points_report_argument_errors_without_a_gpu():
     from garage_amd import _lib
     C = ctypes
+
+    def ref(kind, env):
+        return C.byref(_lib.env_ref(kind, env))
+
     p = _lib.PointEnv(n=4, max_episode_length=5)
-    for name in ('ga_point_env_reset', ):
-        with pytest.raises(_lib.GarageAmdError, match='null env state'):
-            _lib.call(name, C.byref(p), None, None, 4, None)
     with pytest.raises(_lib.GarageAmdError, match='null env state'):
-        _lib.call('ga_point_env_step', C.byref(p), None, 2, None, None, 4,
-                  None, None, None)
+        _lib.call('ga_env_reset', ref(_lib.ENV_POINT, p), None, None, 4, None)
+    with pytest.raises(_lib.GarageAmdError, match='null env state'):
+        _lib.call('ga_env_step', ref(_lib.ENV_POINT, p), None, 2, None, None,
+                  4, None, None, None)
     gr = _lib.GridEnv(n=4, rows=4, cols=4, max_episode_length=5)
     with pytest.raises(_lib.GarageAmdError, match='null env state'):
-        _lib.call('ga_grid_env_reset', C.byref(gr), None, None, 16, None)
+        _lib.call('ga_env_reset', ref(_lib.ENV_GRID, gr), None, None, 16,
+                  None)
     with pytest.raises(_lib.GarageAmdError, match='null env state'):
-        _lib.call('ga_grid_env_step_record_norm', C.byref(gr),
+        _lib.call('ga_env_step_record', ref(_lib.ENV_GRID, gr),
                   C.byref(_lib.RecordArgs()), None, None, 1, None, None)
     buf = C.create_string_buffer(64)
     addr = C.addressof(buf)
     p2 = _lib.PointEnv(n=4, max_episode_length=0, point=addr, goal=addr, t=addr)
     with pytest.raises(_lib.GarageAmdError, match='max_episode_length'):
-        _lib.call('ga_point_env_step_record_norm', C.byref(p2),
+        _lib.call('ga_env_step_record', ref(_lib.ENV_POINT, p2),
                   C.byref(_lib.RecordArgs()), None, None, 2, None, None)
+    # the synthetic env through the same three entries
+    def synth(**kw):
+        e = _lib.SynthEnv(n=4, obs_dim=6, act_dim=3, min_len=2, max_len=5,
+                          episode=addr, t=addr, len=addr)
+        for k, v in kw.items():
+            setattr(e, k, v)
+        return ref(_lib.ENV_SYNTH, e)
+
+    def reset(e, ldo=8):
+        _lib.call('ga_env_reset', e, None, addr, ldo, None)
+
+    def step(e, ldo=8):
+        _lib.call('ga_env_step', e, addr, 4, addr, addr, ldo, addr, addr, None)
+
+    def record(e, ldo=8):
+        rec = _lib.RecordArgs(
+            n=4, col=0, Tcap=8, max_episode_length=5, reward=addr,
+            step_type=addr, next_obs=addr, ldo=ldo, obs_dim=6, ep_t=addr,
+            rew_buf=addr, st_buf=addr, tail_buf=addr, lastobs_buf=addr,
+            done=addr, step_eps=addr, step_samples=addr)
+        _lib.call('ga_env_step_record', e, C.byref(rec), None, addr, 4, addr,
+                  None)
+
+    for fn in (reset, step, record):
+        for field in ('episode', 't', 'len'):
+            with pytest.raises(_lib.GarageAmdError, match='null env state'):
+                fn(synth(**{field: None}))
+        with pytest.raises(_lib.GarageAmdError,
+                           match='1 <= min <= max <= 65535'):
+            fn(synth(min_len=6))
+    with pytest.raises(_lib.GarageAmdError, match='bad obs buffer'):
+        reset(synth(), ldo=5)
+    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
+        step(synth(), ldo=5)
+    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
+        record(synth(), ldo=5)
+    with pytest.raises(_lib.GarageAmdError, match='null pointer'):
+        _lib.call('ga_env_step', synth(), addr, 4, None, addr, 8, addr, addr,
+                  None)  # the synthetic env reads the current observations
     desc, head, rec = _lib.MlpDesc(), _lib.HeadArgs(), _lib.RecordArgs()
     with pytest.raises(_lib.GarageAmdError, match='null pointer'):
         _lib.call('ga_rollout_env_steps', C.byref(desc), None, C.byref(head),
@@ -255,6 +298,20 @@ def test_new_entry_points_report_argument_errors_without_a_gpu():
         _lib.call('ga_rollout_env_steps', C.byref(desc), addr, C.byref(head),
                   C.byref(bad), C.byref(rec), addr, addr, None, None, None, 1,
                   None)
+    with pytest.raises(_lib.GarageAmdError, match='unknown env kind'):
+        _lib.call('ga_env_reset', C.byref(bad), None, addr, 8, None)
+    with pytest.raises(_lib.GarageAmdError, match='unknown env kind'):
+        _lib.call('ga_env_step', C.byref(bad), addr, 4, addr, addr, 8, addr,
+                  addr, None)
+    with pytest.raises(_lib.GarageAmdError, match='unknown env kind'):
+        _lib.call('ga_env_step_record', C.byref(bad), C.byref(rec), None,
+                  addr, 4, addr, None)
+    with pytest.raises(_lib.GarageAmdError, match='unknown env kind'):
+        _lib.call('ga_policy_env_step_fused_f32', C.byref(desc), addr,
+                  C.byref(head), C.byref(bad), C.byref(rec), None, 1, None)
+    with pytest.raises(_lib.GarageAmdError, match='null env'):
+        _lib.call('ga_env_reset', C.byref(_lib.EnvRef(kind=_lib.ENV_POINT)),
+                  None, addr, 8, None)
 
 
 @pytest.mark.ref
@@ -276,7 +333,8 @@ def test_env_rollout_loop_under_address_sanitizer():
     """``make asan-env-loop``: ga_rollout_env_steps' host loop compiled with
     ``-fsanitize=address,undefined`` against recording fakes of the kernels
     (tests/host/rollout_env_loop_harness.cpp): argument errors, the one-launch
-    rollout per env kind, the per-step buffer ping-pong and the action rescale."""
+    rollout per env kind (the synthetic env included), the per-step buffer
+    ping-pong and the action rescale."""
     out = subprocess.run(['make', '-C', ROOT, 'asan-env-loop'],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]

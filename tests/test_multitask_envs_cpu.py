@@ -315,7 +315,7 @@ def test_new_ctypes_struct_matches_the_header():
     for field, _ in _lib.PointEnv._fields_:
         assert (getattr(py, field).offset ==
                 getattr(_lib.PointEnv, field).offset), field
-    assert _lib.load().ga_abi_version() == 4
+    assert _lib.load().ga_abi_version() == 5
 
 
 def test_new_entry_points_report_argument_errors_without_a_gpu():
@@ -332,19 +332,17 @@ def test_new_entry_points_report_argument_errors_without_a_gpu():
                                mode=_lib.TASK_ADD_ONEHOT)
         for k, v in kw.items():
             setattr(e, k, v)
-        return e
+        return C.byref(_lib.env_ref(_lib.ENV_MULTI_POINT, e))
 
     def reset(e, ldo=8):
-        _lib.call('ga_multi_point_env_reset', C.byref(e), None, addr, ldo,
-                  None)
+        _lib.call('ga_env_reset', e, None, addr, ldo, None)
 
     def step(e, ldo=8):
-        _lib.call('ga_multi_point_env_step', C.byref(e), addr, 4, None, addr,
-                  ldo, addr, addr, None)
+        _lib.call('ga_env_step', e, addr, 4, None, addr, ldo, addr, addr, None)
 
     def record(e, rec):
-        _lib.call('ga_multi_point_env_step_record_norm', C.byref(e),
-                  C.byref(rec), None, addr, 4, addr, None)
+        _lib.call('ga_env_step_record', e, C.byref(rec), None, addr, 4, addr,
+                  None)
 
     rec = _lib.RecordArgs(n=4, col=0, Tcap=8, max_episode_length=5,
                           reward=addr, step_type=addr, next_obs=addr, ldo=4,
@@ -375,8 +373,8 @@ def test_new_entry_points_report_argument_errors_without_a_gpu():
     with pytest.raises(_lib.GarageAmdError, match=r'narrower than 3 \+ num'):
         record(env(), rec)
     with pytest.raises(_lib.GarageAmdError, match='null pointer'):
-        _lib.call('ga_multi_point_env_step', C.byref(env()), None, 4, None,
-                  None, 8, None, None, None)
+        _lib.call('ga_env_step', env(), None, 4, None, None, 8, None, None,
+                  None)
     with pytest.raises(_lib.GarageAmdError, match='null pointer'):
         record(env(), _lib.RecordArgs(n=4, Tcap=8, ldo=8, obs_dim=6))
     assert _lib.load().ga_multi_env_task_draw(0, 0, 0, 0) < 0

@@ -130,7 +130,7 @@ def test_action_rescale_and_reward_normalisation_match_real_normalized_env(
 
 
 def test_native_rollout_rescales_actions_like_the_stepwise_path():
-    """``ga_rollout_synth_steps`` with a bounded action space (rescale launch
+    """``ga_rollout_env_steps`` with a bounded action space (rescale launch
     between the policy step and the env step) against the same rollout driven
     step by step from Python: same bits; and the batch keeps the policy's own
     actions, not the rescaled ones (``normalized_env.py:109``)."""

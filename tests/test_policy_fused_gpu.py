@@ -64,14 +64,9 @@ def test_fused_step_matches_per_layer_path(discrete, O, A, hidden, n):
         assert np.allclose(a.rewards, b.rewards, atol=2e-6)
 
 
-@pytest.mark.parametrize('normalize', [False, True])
-@pytest.mark.parametrize('ragged', [False, True])
-def test_native_rollout_loop_equals_python_driven_steps(ragged, normalize):
-    """ga_rollout_synth_steps enqueues the same launches as GpuVecWorker._step:
-    with the device RNG both give bit-identical batches, twice in a row (the
-    second call exercises the partial reset and the odd/even buffer parity)."""
+def _native_against_python_steps(ragged, normalize, discrete, O, A):
     from garage_amd.envs import NormalizedVecEnv, SyntheticVecEnv
-    from garage_amd.policies import GaussianMLPPolicy
+    from garage_amd.policies import CategoricalMLPPolicy, GaussianMLPPolicy
     from garage_amd.sampler import GpuVecSampler, GpuVecWorker
 
     class PythonSteps(GpuVecWorker):
@@ -79,16 +74,18 @@ def test_native_rollout_loop_equals_python_driven_steps(ragged, normalize):
         def _native_steps(self, b, col, n_steps):
             return False
 
-    n, O, A, P = 70, 6, 3, 11
+    n, P = 70, 11
     out = []
     for cls in (GpuVecWorker, PythonSteps):
         torch.manual_seed(4)
-        env = SyntheticVecEnv(n, O, A, P, min_len=3 if ragged else None, seed=8)
+        env = SyntheticVecEnv(n, O, A, P, min_len=3 if ragged else None, seed=8,
+                              discrete=discrete)
         if normalize:  # statistics + normalisation fused into the env step
             env = NormalizedVecEnv(env, normalize_obs=True,
                                    normalize_reward=True, scale_reward=0.5,
                                    obs_alpha=0.05, reward_alpha=0.05)
-        pol = GaussianMLPPolicy(env.spec, hidden_sizes=(32, 32))
+        policy = CategoricalMLPPolicy if discrete else GaussianMLPPolicy
+        pol = policy(env.spec, hidden_sizes=(32, 32))
         sampler = GpuVecSampler(pol, env, max_episode_length=P, n_workers=1,
                                 seed=3, worker_class=cls,
                                 worker_args=dict(n_envs=n))
@@ -103,6 +100,31 @@ def test_native_rollout_loop_equals_python_driven_steps(ragged, normalize):
         assert np.isfinite(a.observations).all() and a.lengths.sum() > 0
         assert np.array_equal([int(s) for s in a.step_types],
                               [int(s) for s in b.step_types])
+
+
+@pytest.mark.parametrize('normalize', [False, True])
+@pytest.mark.parametrize('ragged', [False, True])
+def test_native_rollout_loop_equals_python_driven_steps(ragged, normalize):
+    """ga_rollout_env_steps enqueues the same launches as GpuVecWorker._step
+    (env_step_kernel + record_step + env_reset_kernel of the synthetic env):
+    with the device RNG both give bit-identical batches, twice in a row (the
+    second call exercises the partial reset and the odd/even buffer parity).
+    O = 6, A = 3 continuous: the fused side prefetches the observation entries
+    the reward reads (width <= 8), the plain side reads them from memory."""
+    _native_against_python_steps(ragged, normalize, False, 6, 3)
+
+
+@pytest.mark.parametrize('normalize', [False, True])
+@pytest.mark.parametrize('ragged', [False, True])
+@pytest.mark.parametrize('discrete,O,A', [(False, 12, 10), (True, 4, 2),
+                                          (True, 9, 5)])
+def test_native_rollout_loop_equals_python_driven_steps_on_every_reward_branch(
+        discrete, O, A, ragged, normalize):
+    """The same on the other three branches of the synthetic reward: continuous
+    with a reward width of 10 > 8 (not prefetched), discrete prefetched
+    (O = 4) and discrete with O = 9 > 8; the discrete actions, sampled by the
+    same fused policy step from the device RNG, are compared exactly too."""
+    _native_against_python_steps(ragged, normalize, discrete, O, A)
 
 
 @pytest.mark.parametrize('O,A,hidden,M', [(17, 6, (256, 256), 1000),

@@ -1,5 +1,5 @@
-"""Env-steps per second of the one-launch rollout (ga_rollout_env_steps /
-ga_rollout_synth_steps) with PointVecEnv against SyntheticVecEnv of the same
+"""Env-steps per second of the one-launch rollout (ga_rollout_env_steps)
+with PointVecEnv against SyntheticVecEnv of the same
 observation / action sizes, and with MultiTaskPointVecEnv (K = 4 and K = 16 goals
 on the unit circle, round robin, add-onehot: observations 3 + K wide;
 never_done, so that every episode runs its T steps as the other rows' do and the
