@@ -40,15 +40,6 @@ typedef struct ga_fused_first_layer {
   int64_t ldh;
 } ga_fused_first_layer;
 int ga_fused_first_layer_ok(int in_w, int K);
-// last hidden layer + head + loss + gradient seed + head weight-gradient shares;
-// hpart: [tiles][8 * width + 8] floats, lpart: [tiles][2] doubles.  first != null:
-// A / lda / a_idx are ignored, the operand comes from `first`
-int ga_fused_fwd_head_loss(const float* A, int64_t lda, const int32_t* a_idx,
-                           const float* W, int64_t ldw, const float* bias, int64_t M,
-                           int width, int K, const float* head_W, int64_t head_ldw,
-                           const float* head_bias, const ga_fused_loss_args* loss,
-                           float* dZ, int64_t lddz, float* hpart, double* lpart,
-                           const ga_fused_first_layer* first, hipStream_t stream);
 // The whole MLP (two hidden tanh layers of the shapes above, <= 8 linear outputs) for
 // its OUTPUTS only: out[m] = MLP(X[idx ? idx[m] : m]); no activation reaches memory.
 int ga_fused_eval_supported(int n_layers, const int* dims);
@@ -56,12 +47,6 @@ int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t* idx, int64
                           const int* dims, const float* W1, const float* b1,
                           const float* W2, const float* b2, const float* Wh,
                           const float* bh, float* out, int64_t ldo, hipStream_t stream);
-// data gradient into the first hidden layer + first-layer weight / bias gradient
-// shares; wpart: [tiles][width * round4(in_w) + width] floats
-int ga_fused_dgrad_wgrad0(const float* dZ2, int64_t lddz, const float* W2, int64_t ldw,
-                          int64_t M, int width, int K, const float* H1, int64_t ldh,
-                          const float* X, int64_t ldx, const int32_t* idx, int in_w,
-                          float* wpart, hipStream_t stream);
 // narrow_step.hip: forward + loss + backward of a 2 x H network (H = 32 or 64) in one
 // launch; part: [tiles][ga_narrow_step_stride] floats, lpart: [tiles][2] doubles
 int ga_narrow_step_supported(int n_layers, const int* dims);
@@ -70,48 +55,58 @@ int ga_narrow_train_step(const float* params, const int64_t* w_off, const int64_
                          int in_w, int H, int out_w, const float* X, int64_t ldx,
                          int64_t M, const ga_fused_loss_args* loss, float* part,
                          double* lpart, hipStream_t stream);
-// ---- two networks in one launch each (the policy's and the value function's step k):
-// same shapes for both (width 256, first layer in the kernel), same row count
+// ---- The four launches of a fused optimizer step.  Each takes one descriptor per
+// network: n_nets = 1, or 2 for the policy's and the value function's step k in ONE
+// grid (same shapes and row count for both; ga_fused_pair_supported: width 256, first
+// layer in the kernel).  update.cpp (fused_step) fills the descriptors.
+//
+// 1. last hidden layer + head + loss + gradient seed + head weight-gradient shares;
+// hpart: [tiles][8 * width + 8] floats, lpart: [tiles][2] doubles.  first != null:
+// A / lda / a_idx are ignored, the operand comes from `first`
+typedef struct ga_fused_fwd_net {
+  const float* A; int64_t lda; const int32_t* a_idx;
+  const float* W; int64_t ldw; const float* bias;
+  const float* head_W; int64_t head_ldw; const float* head_bias;
+  const ga_fused_loss_args* loss;
+  float* dZ; int64_t lddz; float* hpart; double* lpart;
+  const ga_fused_first_layer* first;
+} ga_fused_fwd_net;
 int ga_fused_pair_supported(int width, int K, int in_w);
-int ga_fused_fwd_head_loss_pair(
-    int64_t M, int width, int K,
-    const float* Wa, int64_t ldwa, const float* biasa, const float* head_Wa,
-    int64_t head_ldwa, const float* head_biasa, const ga_fused_loss_args* lossa,
-    float* dZa, int64_t lddza, float* hparta, double* lparta,
-    const ga_fused_first_layer* firsta,
-    const float* Wb, int64_t ldwb, const float* biasb, const float* head_Wb,
-    int64_t head_ldwb, const float* head_biasb, const ga_fused_loss_args* lossb,
-    float* dZb, int64_t lddzb, float* hpartb, double* lpartb,
-    const ga_fused_first_layer* firstb, hipStream_t stream);
-int ga_fused_dgrad_wgrad0_pair(
-    int64_t M, int width, int K, int in_w,
-    const float* dZ2a, int64_t lddza, const float* W2a, int64_t ldwa, const float* H1a,
-    int64_t ldha, const float* Xa, int64_t ldxa, const int32_t* idxa, float* wparta,
-    const float* dZ2b, int64_t lddzb, const float* W2b, int64_t ldwb, const float* H1b,
-    int64_t ldhb, const float* Xb, int64_t ldxb, const int32_t* idxb, float* wpartb,
-    hipStream_t stream);
-// gemm.hip: the weight-gradient GEMM of the middle layer (dW2 = dZ2^T H1, split-K
-// slabs + bias column sums) of two 3-layer networks in one grid
-int ga_wgrad_mid_pair(int64_t M, int64_t n_splits, int out_w, int in_w,
-                      const float* dza, const float* ina, float* slabs_wa, float* slabs_ba,
-                      int64_t slab_stride_a,
-                      const float* dzb, const float* inb, float* slabs_wb, float* slabs_bb,
-                      int64_t slab_stride_b, hipStream_t stream);
+int ga_fused_fwd_head_loss(const ga_fused_fwd_net* nets, int n_nets, int64_t M, int width,
+                           int K, hipStream_t stream);
+// 2. gemm.hip: the weight-gradient GEMM of the middle layer (dW2 = dZ2^T H1, split-K
+// slabs + bias column sums) of a 3-layer network: the launch ga_mlp_backward_range_f32
+// makes for layer 1 with fused_first = 1.  n_nets = 2 only: one network's middle layers,
+// of any depth, go through ga_mlp_backward_range_f32
+typedef struct ga_wgrad_mid_net {
+  const float* dz; const float* in; float* slabs_w; float* slabs_b; int64_t slab_stride;
+} ga_wgrad_mid_net;
+int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M, int64_t n_splits,
+                 int out_w, int in_w, hipStream_t stream);
+// 3. data gradient into the first hidden layer + first-layer weight / bias gradient
+// shares; wpart: [tiles][width * round4(in_w) + width] floats
+typedef struct ga_fused_dgrad_net {
+  const float* dZ2; int64_t lddz; const float* W2; int64_t ldw;
+  const float* H1; int64_t ldh; const float* X; int64_t ldx; const int32_t* idx;
+  float* wpart;
+} ga_fused_dgrad_net;
+int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M, int width,
+                          int K, int in_w, hipStream_t stream);
+// 4. partial sums -> gradient -> Adam, and the loss.  pl_rows > 0 (one network only):
+// the launch also rewrites the split-operand planes of the [pl_rows][pl_cols] weight
+// matrix at flat index pl_beg, when the step's forward launch used them;
+// ga_planes_epoch_begin: planes written that way are trusted only until the epoch
+// call that wrote them returns.
 typedef struct ga_reduce_net {
   const ga_fused_region* regions; int n_regions;
   float* params; float* grads; float* exp_avg; float* exp_avg_sq;
   int64_t step; double lr, beta1, beta2, eps; float scale; int do_adam, zero_slot0;
   const double* lpart; int n_lpart; int64_t M; const ga_fused_loss_args* loss;
   float* loss_out;
+  int64_t pl_beg; int pl_rows, pl_cols;
 } ga_reduce_net;
-int ga_reduce_regions_adam_pair(const ga_reduce_net* a, const ga_reduce_net* b,
-                                hipStream_t stream);
-int ga_reduce_regions_adam(const ga_fused_region* regions, int n_regions, float* params,
-                           float* grads, float* exp_avg, float* exp_avg_sq, int64_t step,
-                           double lr, double beta1, double beta2, double eps, float scale,
-                           int do_adam, int zero_slot0, const double* lpart, int n_lpart,
-                           int64_t M, const ga_fused_loss_args* loss, float* loss_out,
-                           hipStream_t stream);
+int ga_reduce_regions_adam(const ga_reduce_net* nets, int n_nets, hipStream_t stream);
+void ga_planes_epoch_begin(void);
 /* 1 while the opt-in split-operand (3 x bf16) k-loops are selected
  * (ga_set_split_bf16 / GARAGE_AMD_SPLIT_BF16=1). */
 int ga_split_bf16_enabled(void); /* ... for the weight-gradient GEMM */
@@ -124,10 +119,4 @@ int ga_split_bf16_gemm(void);    /* ... for the per-layer forward / data-gradien
  * round32(cols). */
 const uint16_t* ga_weight_planes(const float* W, int64_t ld, int rows, int cols, int bwd,
                                  hipStream_t stream);
-/* The next ga_reduce_regions_adam of this thread also rewrites the planes of the
- * [rows][cols] weight matrix at flat index flat_beg (the step's forward launch used
- * them); ga_planes_epoch_begin: planes written that way are trusted only until the
- * epoch call that wrote them returns. */
-void ga_reduce_planes_hint(int64_t flat_beg, int rows, int cols);
-void ga_planes_epoch_begin(void);
 }

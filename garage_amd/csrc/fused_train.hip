@@ -1805,15 +1805,16 @@ extern "C" int ga_fused_first_layer_ok(int in_w, int K) {
 }
 
 // validation + kernel parameters of one network's launch
-static int fwd_build(const float* A, int64_t lda, const int32_t* a_idx, const float* W,
-                     int64_t ldw, const float* bias, int64_t M, int width, int K,
-                     const float* head_W, int64_t head_ldw, const float* head_bias,
-                     const ga_fused_loss_args* loss, float* dZ, int64_t lddz,
-                     float* hpart, double* lpart, const ga_fused_first_layer* first,
+static int fwd_build(const ga_fused_fwd_net& n, int64_t M, int width, int K,
                      FwdLossParams* out, double* flops_out) {
-  GA_REQUIRE((A || first) && W && bias && head_W && head_bias && loss && dZ && hpart &&
-                 lpart,
+  const ga_fused_first_layer* first = n.first;
+  const ga_fused_loss_args* loss = n.loss;
+  GA_REQUIRE((n.A || first) && n.W && n.bias && n.head_W && n.head_bias && loss && n.dZ &&
+                 n.hpart && n.lpart,
              "ga_fused_fwd_head_loss: null pointer");
+  const float* A = n.A;
+  int64_t lda = n.lda;
+  const int32_t* a_idx = n.a_idx;
   if (first) {
     GA_REQUIRE(first->X && first->W && first->b && first->H &&
                    ga_fused_first_layer_ok(first->in_w, K) && K <= 256 &&
@@ -1827,9 +1828,9 @@ static int fwd_build(const float* A, int64_t lda, const int32_t* a_idx, const fl
   GA_REQUIRE(ga_fused_width_ok(width) && M >= 1 && M < (1ll << 31) && K >= 1 &&
                  loss->A >= 1 && loss->A <= 8,
              "ga_fused_fwd_head_loss: unsupported shape");
-  GA_REQUIRE(lda % 4 == 0 && ldw % 4 == 0 && head_ldw % 4 == 0 && lddz % 4 == 0 &&
-                 ga_aligned16(A) && ga_aligned16(W) && ga_aligned16(bias) &&
-                 ga_aligned16(head_W) && ga_aligned16(dZ),
+  GA_REQUIRE(lda % 4 == 0 && n.ldw % 4 == 0 && n.head_ldw % 4 == 0 && n.lddz % 4 == 0 &&
+                 ga_aligned16(A) && ga_aligned16(n.W) && ga_aligned16(n.bias) &&
+                 ga_aligned16(n.head_W) && ga_aligned16(n.dZ),
              "ga_fused_fwd_head_loss: operands must be 16-B aligned quads");
   GA_REQUIRE(loss->kind == 1 ? loss->returns != nullptr
                              : (loss->actions && loss->adv &&
@@ -1842,11 +1843,11 @@ static int fwd_build(const float* A, int64_t lda, const int32_t* a_idx, const fl
   GA_REQUIRE(loss->algo == 0 || loss->algo == 1, "ga_fused_fwd_head_loss: algo");
   FwdLossParams& p = *out;
   memset(&p, 0, sizeof(p));
-  p.g.A = A; p.g.lda = lda; p.g.a_idx = a_idx; p.g.B = W; p.g.ldb = ldw;
-  p.g.M = (int)M; p.g.N = width; p.g.K = K; p.g.bias = bias;
-  p.head_W = head_W; p.head_ldw = head_ldw; p.head_bias = head_bias;
+  p.g.A = A; p.g.lda = lda; p.g.a_idx = a_idx; p.g.B = n.W; p.g.ldb = n.ldw;
+  p.g.M = (int)M; p.g.N = width; p.g.K = K; p.g.bias = n.bias;
+  p.head_W = n.head_W; p.head_ldw = n.head_ldw; p.head_bias = n.head_bias;
   p.loss = loss_args(loss, M);
-  p.dZ = dZ; p.lddz = lddz; p.hpart = hpart; p.lpart = lpart;
+  p.dZ = n.dZ; p.lddz = n.lddz; p.hpart = n.hpart; p.lpart = n.lpart;
   // algorithmic flops of the layers computed
   double flops = 2.0 * (double)M * width * ((double)K + loss->A);
   if (first) {
@@ -1858,88 +1859,69 @@ static int fwd_build(const float* A, int64_t lda, const int32_t* a_idx, const fl
   return GA_OK;
 }
 
-extern "C" int ga_fused_fwd_head_loss(const float* A, int64_t lda, const int32_t* a_idx,
-                                      const float* W, int64_t ldw, const float* bias,
-                                      int64_t M, int width, int K, const float* head_W,
-                                      int64_t head_ldw, const float* head_bias,
-                                      const ga_fused_loss_args* loss, float* dZ,
-                                      int64_t lddz, float* hpart, double* lpart,
-                                      const ga_fused_first_layer* first,
-                                      hipStream_t stream) {
-  FwdLossParams p;
-  double flops = 0.0;
-  const int rc = fwd_build(A, lda, a_idx, W, ldw, bias, M, width, K, head_W, head_ldw,
-                           head_bias, loss, dZ, lddz, hpart, lpart, first, &p, &flops);
-  if (rc) return rc;
-  p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_ft_dbg : nullptr;
-  const dim3 grid((unsigned)ga_fused_tiles(M));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_FWD, flops, &e0, &e1);
-  if (first && width == 64)
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2, true>), grid, dim3(256), 0,
-                          stream, e0, e1, 0, p);
-  else if (first && width == 128)
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4, true>), grid, dim3(256), 0,
-                          stream, e0, e1, 0, p);
-  else if (first && split_bf16_on(1) && K % 32 == 0 && first->in_w <= 20) {
-    p.bplanes = planes_for(W, ldw, width, K, PLANES_TRAIN_FWD, stream);
-    GA_REQUIRE(p.bplanes, "ga_fused_fwd_head_loss: no memory for the weight planes");
-    p.bplane_stride = (int64_t)width * K;
-    hipExtLaunchKernelGGL((fwd_head_loss_split_kernel<256, 1, 8>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
-  } else if (first && (first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true, 5>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
-  else if (first)
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
-  else if (width == 64)
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2>), grid, dim3(256), 0, stream,
-                          e0, e1, 0, p);
-  else if (width == 128)
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
-                          e0, e1, 0, p);
-  else
-    hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                          e0, e1, 0, p);
-  GA_CHECK_LAUNCH("fwd_head_loss");
-  return GA_OK;
-}
-
 // Pair launches are compiled for 256-wide last hidden layers with the first layer in
 // the kernel (the C3-class networks the two-chain schedule was built for).
 extern "C" int ga_fused_pair_supported(int width, int K, int in_w) {
   return width == 256 && K <= 256 && ga_fused_first_layer_ok(in_w, K);
 }
 
-// The two networks' launches of ga_fused_fwd_head_loss (first layer in the kernel) in
-// ONE grid; both must have the same width, K, input width and row count.
-extern "C" int ga_fused_fwd_head_loss_pair(
-    int64_t M, int width, int K,
-    const float* Wa, int64_t ldwa, const float* biasa, const float* head_Wa,
-    int64_t head_ldwa, const float* head_biasa, const ga_fused_loss_args* lossa,
-    float* dZa, int64_t lddza, float* hparta, double* lparta,
-    const ga_fused_first_layer* firsta,
-    const float* Wb, int64_t ldwb, const float* biasb, const float* head_Wb,
-    int64_t head_ldwb, const float* head_biasb, const ga_fused_loss_args* lossb,
-    float* dZb, int64_t lddzb, float* hpartb, double* lpartb,
-    const ga_fused_first_layer* firstb, hipStream_t stream) {
-  GA_REQUIRE(firsta && firstb && firsta->in_w == firstb->in_w &&
-                 ga_fused_pair_supported(width, K, firsta->in_w),
-             "ga_fused_fwd_head_loss_pair: unsupported shapes");
+// n_nets = 2: the two networks' launches (first layer in the kernel) in ONE grid; both
+// have the same width, K, input width and row count.
+extern "C" int ga_fused_fwd_head_loss(const ga_fused_fwd_net* nets, int n_nets, int64_t M,
+                                      int width, int K, hipStream_t stream) {
+  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
+             "ga_fused_fwd_head_loss: one or two networks");
+  const ga_fused_first_layer* first = nets[0].first;
+  if (n_nets == 2)
+    GA_REQUIRE(first && nets[1].first && first->in_w == nets[1].first->in_w &&
+                   ga_fused_pair_supported(width, K, first->in_w),
+               "ga_fused_fwd_head_loss_pair: unsupported shapes");
   FwdLossPair pp;
-  double fa = 0.0, fb = 0.0;
-  int rc = fwd_build(nullptr, 0, nullptr, Wa, ldwa, biasa, M, width, K, head_Wa, head_ldwa,
-                     head_biasa, lossa, dZa, lddza, hparta, lparta, firsta, &pp.a, &fa);
-  if (rc) return rc;
-  rc = fwd_build(nullptr, 0, nullptr, Wb, ldwb, biasb, M, width, K, head_Wb, head_ldwb,
-                 head_biasb, lossb, dZb, lddzb, hpartb, lpartb, firstb, &pp.b, &fb);
-  if (rc) return rc;
-  const dim3 grid((unsigned)(2 * ga_fused_tiles(M)));
+  FwdLossParams& p = pp.a;
+  double flops = 0.0;
+  for (int i = 0; i < n_nets; ++i) {
+    double f = 0.0;
+    const int rc = fwd_build(nets[i], M, width, K, i ? &pp.b : &pp.a, &f);
+    if (rc) return rc;
+    flops += f;
+  }
+  const dim3 grid((unsigned)(n_nets * ga_fused_tiles(M)));
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_FWD, fa + fb, &e0, &e1);
+  ga_prof_events(GA_PROF_FUSED_FWD, flops, &e0, &e1);
+  if (n_nets == 1) {
+    p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_ft_dbg : nullptr;
+    if (first && width == 64)
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2, true>), grid, dim3(256), 0,
+                            stream, e0, e1, 0, p);
+    else if (first && width == 128)
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4, true>), grid, dim3(256), 0,
+                            stream, e0, e1, 0, p);
+    else if (first && split_bf16_on(1) && K % 32 == 0 && first->in_w <= 20) {
+      p.bplanes = planes_for(nets[0].W, nets[0].ldw, width, K, PLANES_TRAIN_FWD, stream);
+      GA_REQUIRE(p.bplanes, "ga_fused_fwd_head_loss: no memory for the weight planes");
+      p.bplane_stride = (int64_t)width * K;
+      hipExtLaunchKernelGGL((fwd_head_loss_split_kernel<256, 1, 8>), grid, dim3(512), 0,
+                            stream, e0, e1, 0, p);
+    } else if (first && (first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true, 5>), grid, dim3(512), 0,
+                            stream, e0, e1, 0, p);
+    else if (first)
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true>), grid, dim3(512), 0,
+                            stream, e0, e1, 0, p);
+    else if (width == 64)
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2>), grid, dim3(256), 0, stream,
+                            e0, e1, 0, p);
+    else if (width == 128)
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
+                            e0, e1, 0, p);
+    else
+      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
+                            e0, e1, 0, p);
+    GA_CHECK_LAUNCH("fwd_head_loss");
+    return GA_OK;
+  }
   ga_prof_count(GA_PROF_FUSED_FWD);  // (one launch, two networks' steps)
-  if ((firsta->in_w + 3) / 4 == 5 && pipelined_kloop_on())
+  if ((first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
     hipExtLaunchKernelGGL((fwd_head_loss_pair_kernel<256, 1, 8, 5>), grid, dim3(512), 0,
                           stream, e0, e1, 0, pp);
   else
@@ -2001,102 +1983,83 @@ extern "C" int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t*
   return GA_OK;
 }
 
-static int dgrad_build(const float* dZ2, int64_t lddz, const float* W2, int64_t ldw,
-                       int64_t M, int width, int K, const float* H1, int64_t ldh,
-                       const float* X, int64_t ldx, const int32_t* idx, int in_w,
-                       float* wpart, DgradWgrad0Params* out, double* flops_out) {
-  GA_REQUIRE(dZ2 && W2 && H1 && X && wpart, "ga_fused_dgrad_wgrad0: null pointer");
+static int dgrad_build(const ga_fused_dgrad_net& n, int64_t M, int width, int K, int in_w,
+                       DgradWgrad0Params* out, double* flops_out) {
+  GA_REQUIRE(n.dZ2 && n.W2 && n.H1 && n.X && n.wpart, "ga_fused_dgrad_wgrad0: null pointer");
   GA_REQUIRE(ga_fused_width_ok(width) && M >= 1 && M < (1ll << 31) && K >= 1 &&
                  in_w >= 1 && in_w <= 32,
              "ga_fused_dgrad_wgrad0: unsupported shape");
-  GA_REQUIRE(lddz % 4 == 0 && ldw % 4 == 0 && ldh % 4 == 0 && ldx % 4 == 0 &&
-                 ldx >= ((in_w + 3) & ~3) && ga_aligned16(dZ2) && ga_aligned16(W2) &&
-                 ga_aligned16(H1) && ga_aligned16(X) && ga_aligned16(wpart),
+  GA_REQUIRE(n.lddz % 4 == 0 && n.ldw % 4 == 0 && n.ldh % 4 == 0 && n.ldx % 4 == 0 &&
+                 n.ldx >= ((in_w + 3) & ~3) && ga_aligned16(n.dZ2) && ga_aligned16(n.W2) &&
+                 ga_aligned16(n.H1) && ga_aligned16(n.X) && ga_aligned16(n.wpart),
              "ga_fused_dgrad_wgrad0: operands must be 16-B aligned quads");
   DgradWgrad0Params& p = *out;
   memset(&p, 0, sizeof(p));
-  p.g.A = dZ2; p.g.lda = lddz; p.g.B = W2; p.g.ldb = ldw;
+  p.g.A = n.dZ2; p.g.lda = n.lddz; p.g.B = n.W2; p.g.ldb = n.ldw;
   p.g.M = (int)M; p.g.N = width; p.g.K = K;
-  p.H = H1; p.ldh = ldh; p.X = X; p.ldx = ldx; p.idx = idx; p.in_w = in_w;
-  p.wpart = wpart;
+  p.H = n.H1; p.ldh = n.ldh; p.X = n.X; p.ldx = n.ldx; p.idx = n.idx; p.in_w = in_w;
+  p.wpart = n.wpart;
   *flops_out = 2.0 * (double)M * width * ((double)K + in_w);
   return GA_OK;
 }
 
-extern "C" int ga_fused_dgrad_wgrad0(const float* dZ2, int64_t lddz, const float* W2,
-                                     int64_t ldw, int64_t M, int width, int K,
-                                     const float* H1, int64_t ldh, const float* X,
-                                     int64_t ldx, const int32_t* idx, int in_w,
-                                     float* wpart, hipStream_t stream) {
-  DgradWgrad0Params p;
+// n_nets = 2: two networks' launches in one grid (width 256)
+extern "C" int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M,
+                                     int width, int K, int in_w, hipStream_t stream) {
+  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
+             "ga_fused_dgrad_wgrad0: one or two networks");
+  if (n_nets == 2)
+    GA_REQUIRE(width == 256, "ga_fused_dgrad_wgrad0_pair: unsupported width");
+  DgradWgrad0Pair pp;
+  DgradWgrad0Params& p = pp.a;
   double flops = 0.0;
-  const int rc = dgrad_build(dZ2, lddz, W2, ldw, M, width, K, H1, ldh, X, ldx, idx, in_w,
-                             wpart, &p, &flops);
-  if (rc) return rc;
-  p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_dg_dbg : nullptr;
-  const dim3 grid((unsigned)ga_fused_tiles(M));
+  for (int i = 0; i < n_nets; ++i) {
+    double f = 0.0;
+    const int rc = dgrad_build(nets[i], M, width, K, in_w, i ? &pp.b : &pp.a, &f);
+    if (rc) return rc;
+    flops += f;
+  }
+  const dim3 grid((unsigned)(n_nets * ga_fused_tiles(M)));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ga_prof_events(GA_PROF_FUSED_DGRAD, flops, &e0, &e1);
-  if (width == 64)
-    hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<64, 2, 2>), grid, dim3(256), 0, stream, e0,
-                          e1, 0, p);
-  else if (width == 128)
-    hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
-                          e0, e1, 0, p);
-  else if (split_bf16_on(2) && K % 32 == 0) {
-    p.bplanes = planes_for(W2, ldw, K, width, PLANES_BWD, stream);
-    GA_REQUIRE(p.bplanes, "ga_fused_dgrad_wgrad0: no memory for the weight planes");
-    p.bplane_stride = (int64_t)width * K;
-    hipExtLaunchKernelGGL((dgrad_wgrad0_split_kernel<256, 1, 8>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
-  } else
-    hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                          e0, e1, 0, p);
-  GA_CHECK_LAUNCH("dgrad_wgrad0");
-  return GA_OK;
-}
-
-// two networks' launches of ga_fused_dgrad_wgrad0 in one grid (width 256)
-extern "C" int ga_fused_dgrad_wgrad0_pair(
-    int64_t M, int width, int K, int in_w,
-    const float* dZ2a, int64_t lddza, const float* W2a, int64_t ldwa, const float* H1a,
-    int64_t ldha, const float* Xa, int64_t ldxa, const int32_t* idxa, float* wparta,
-    const float* dZ2b, int64_t lddzb, const float* W2b, int64_t ldwb, const float* H1b,
-    int64_t ldhb, const float* Xb, int64_t ldxb, const int32_t* idxb, float* wpartb,
-    hipStream_t stream) {
-  GA_REQUIRE(width == 256, "ga_fused_dgrad_wgrad0_pair: unsupported width");
-  DgradWgrad0Pair pp;
-  double fa = 0.0, fb = 0.0;
-  int rc = dgrad_build(dZ2a, lddza, W2a, ldwa, M, width, K, H1a, ldha, Xa, ldxa, idxa,
-                       in_w, wparta, &pp.a, &fa);
-  if (rc) return rc;
-  rc = dgrad_build(dZ2b, lddzb, W2b, ldwb, M, width, K, H1b, ldhb, Xb, ldxb, idxb, in_w,
-                   wpartb, &pp.b, &fb);
-  if (rc) return rc;
-  const dim3 grid((unsigned)(2 * ga_fused_tiles(M)));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_DGRAD, fa + fb, &e0, &e1);
+  if (n_nets == 1) {
+    p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_dg_dbg : nullptr;
+    if (width == 64)
+      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<64, 2, 2>), grid, dim3(256), 0, stream, e0,
+                            e1, 0, p);
+    else if (width == 128)
+      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
+                            e0, e1, 0, p);
+    else if (split_bf16_on(2) && K % 32 == 0) {
+      p.bplanes = planes_for(nets[0].W2, nets[0].ldw, K, width, PLANES_BWD, stream);
+      GA_REQUIRE(p.bplanes, "ga_fused_dgrad_wgrad0: no memory for the weight planes");
+      p.bplane_stride = (int64_t)width * K;
+      hipExtLaunchKernelGGL((dgrad_wgrad0_split_kernel<256, 1, 8>), grid, dim3(512), 0,
+                            stream, e0, e1, 0, p);
+    } else
+      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
+                            e0, e1, 0, p);
+    GA_CHECK_LAUNCH("dgrad_wgrad0");
+    return GA_OK;
+  }
   ga_prof_count(GA_PROF_FUSED_DGRAD);
-  hipExtLaunchKernelGGL((dgrad_wgrad0_pair_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                        e0, e1, 0, pp);
+  hipExtLaunchKernelGGL((dgrad_wgrad0_pair_kernel<256, 1, 8>), grid, dim3(512), 0,
+                        stream, e0, e1, 0, pp);
   GA_CHECK_LAUNCH("dgrad_wgrad0_pair");
   return GA_OK;
 }
 
 // regions + optimizer constants of one network into slot `net` of the launch
-static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_fused_region* regions,
-                          int n_regions, float* params, float* grads, float* exp_avg,
-                          float* exp_avg_sq, int64_t step, double lr, double beta1,
-                          double beta2, double eps, float scale, int do_adam,
-                          int zero_slot0, const double* lpart, int n_lpart, int64_t M,
-                          const ga_fused_loss_args* loss, float* loss_out) {
-  GA_REQUIRE(regions && params && grads && exp_avg && exp_avg_sq && lpart && loss,
+static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_reduce_net& n) {
+  const ga_fused_region* regions = n.regions;
+  GA_REQUIRE(regions && n.params && n.grads && n.exp_avg && n.exp_avg_sq && n.lpart &&
+                 n.loss,
              "ga_reduce_regions_adam: null pointer");
-  GA_REQUIRE(n_regions >= 1 && p.n_regions + n_regions <= FT_MAX_REGIONS && step >= 1 &&
-                 n_lpart >= 1,
+  GA_REQUIRE(n.n_regions >= 1 && p.n_regions + n.n_regions <= FT_MAX_REGIONS &&
+                 n.step >= 1 && n.n_lpart >= 1,
              "ga_reduce_regions_adam: bad arguments");
   int64_t v = p.n_virtual;
-  for (int k = 0; k < n_regions; ++k) {
+  for (int k = 0; k < n.n_regions; ++k) {
     // regions are walked 4 elements at a time: the flat layout pads every weight
     // row and bias vector to a multiple of 4 floats, and the padding of every
     // partial is zero, so a region is rounded up to whole quads
@@ -2113,22 +2076,19 @@ static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_fused_region
     r.net = net;
     v += ga_ceil_div(r.n / 4, r.quads);  // workgroups of this region
   }
-  p.n_regions += n_regions;
+  p.n_regions += n.n_regions;
   p.n_virtual = v;
   FtNet& N = p.net[net];
-  N.a.p = params; N.a.m = exp_avg; N.a.v = exp_avg_sq;
-  N.a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
-  N.grads = grads; N.scale = scale; N.do_adam = do_adam; N.zero_slot0 = zero_slot0;
-  N.lpart = lpart; N.n_lpart = n_lpart; N.M = M;
-  N.loss = loss_args(loss, M);
-  N.loss_out = loss_out;
+  N.a.p = n.params; N.a.m = n.exp_avg; N.a.v = n.exp_avg_sq;
+  N.a.c = ga_adam_coeffs(n.lr, n.beta1, n.beta2, n.eps, n.step);
+  N.grads = n.grads; N.scale = n.scale; N.do_adam = n.do_adam;
+  N.zero_slot0 = n.zero_slot0;
+  N.lpart = n.lpart; N.n_lpart = n.n_lpart; N.M = n.M;
+  N.loss = loss_args(n.loss, n.M);
+  N.loss_out = n.loss_out;
   return GA_OK;
 }
 
-// The next ga_reduce_regions_adam call of this thread (with do_adam) also rewrites the
-// planes of W = params + flat_beg ([rows][cols], ld = cols); update.cpp asks for it when
-// the step's forward launch ran the split-operand kernel.
-static thread_local struct { int64_t beg; int rows, cols; bool set; } t_planes_hint = {0, 0, 0, false};
 // developer / test switch: 0 = every forward launch computes its planes itself again
 static int g_adam_planes = -1;
 static bool adam_planes_on() {
@@ -2142,11 +2102,6 @@ extern "C" int ga_set_split_adam_planes(int on) {
   g_adam_planes = on != 0;
   return 0;
 }
-extern "C" void ga_reduce_planes_hint(int64_t flat_beg, int rows, int cols) {
-  if (!adam_planes_on()) return;
-  t_planes_hint.beg = flat_beg; t_planes_hint.rows = rows; t_planes_hint.cols = cols;
-  t_planes_hint.set = true;
-}
 // trust in optimizer-written planes never outlives an epoch call (anything may write
 // the parameters between two calls)
 extern "C" void ga_planes_epoch_begin(void) {
@@ -2154,67 +2109,46 @@ extern "C" void ga_planes_epoch_begin(void) {
   for (PlaneBuf& b : g_plane_bufs) b.adam_fresh = false;
 }
 
-extern "C" int ga_reduce_regions_adam(const ga_fused_region* regions, int n_regions,
-                                      float* params, float* grads, float* exp_avg,
-                                      float* exp_avg_sq, int64_t step, double lr,
-                                      double beta1, double beta2, double eps, float scale,
-                                      int do_adam, int zero_slot0, const double* lpart,
-                                      int n_lpart, int64_t M,
-                                      const ga_fused_loss_args* loss, float* loss_out,
+// n_nets = 2: both networks' optimizer steps in one launch (regions of two flat buffers,
+// two loss blocks); the same per-element arithmetic and summation trees as two single
+// launches
+extern "C" int ga_reduce_regions_adam(const ga_reduce_net* nets, int n_nets,
                                       hipStream_t stream) {
+  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
+             "ga_reduce_regions_adam: one or two networks");
   ReduceRegionsParams p;
   memset(&p, 0, sizeof(p));
-  const int rc = reduce_add_net(p, 0, regions, n_regions, params, grads, exp_avg,
-                                exp_avg_sq, step, lr, beta1, beta2, eps, scale, do_adam,
-                                zero_slot0, lpart, n_lpart, M, loss, loss_out);
-  if (rc) return rc;
-  p.n_nets = 1;
-  PlaneBuf* written = nullptr;
-  if (t_planes_hint.set) {
-    t_planes_hint.set = false;
-    const int rows = t_planes_hint.rows, cols = t_planes_hint.cols;
-    if (do_adam && split_bf16_on(1) && rows % 32 == 0 && cols % 32 == 0) {
-      const float* W = params + t_planes_hint.beg;
-      std::lock_guard<std::mutex> lock(g_plane_mu);
-      for (PlaneBuf& b : g_plane_bufs)
-        if (b.W == W && b.rows == rows && b.cols == cols) written = &b;
-      if (written) {  // (the forward launch of this step created it)
-        p.net[0].pl_fwd = reinterpret_cast<uint32_t*>(written->fwd);
-        p.net[0].pl_bwd = reinterpret_cast<uint32_t*>(written->bwd);
-        p.net[0].pl_beg = t_planes_hint.beg;
-        p.net[0].pl_rows = rows;
-        p.net[0].pl_cols = cols;
-        written->adam_fresh = true;
-        written->adam_stream = stream;
-        written->bwd_fresh = false;
-      }
-    }
-  }
-  const unsigned blocks = (unsigned)p.n_virtual + 1;  // + the loss block
-  hipLaunchKernelGGL(reduce_regions_adam_kernel, dim3(blocks), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("reduce_regions_adam");
-  return GA_OK;
-}
-
-// both networks' optimizer steps in one launch (regions of two flat buffers, two loss
-// blocks); the same per-element arithmetic and summation trees as two single launches
-extern "C" int ga_reduce_regions_adam_pair(const ga_reduce_net* a, const ga_reduce_net* b,
-                                           hipStream_t stream) {
-  GA_REQUIRE(a && b, "ga_reduce_regions_adam_pair: null pointer");
-  ReduceRegionsParams p;
-  memset(&p, 0, sizeof(p));
-  const ga_reduce_net* nets[2] = {a, b};
-  for (int i = 0; i < 2; ++i) {
-    const ga_reduce_net* n = nets[i];
-    const int rc = reduce_add_net(p, i, n->regions, n->n_regions, n->params, n->grads,
-                                  n->exp_avg, n->exp_avg_sq, n->step, n->lr, n->beta1,
-                                  n->beta2, n->eps, n->scale, n->do_adam, n->zero_slot0,
-                                  n->lpart, n->n_lpart, n->M, n->loss, n->loss_out);
+  for (int i = 0; i < n_nets; ++i) {
+    const int rc = reduce_add_net(p, i, nets[i]);
     if (rc) return rc;
   }
-  p.n_nets = 2;
-  const unsigned blocks = (unsigned)p.n_virtual + 2;  // + the two loss blocks
+  p.n_nets = n_nets;
+  // (with do_adam) the launch also rewrites the planes of W = params + pl_beg
+  // ([rows][cols], ld = cols); update.cpp asks for it when the step's forward launch
+  // ran the split-operand kernel
+  GA_REQUIRE(n_nets == 1 || (!nets[0].pl_rows && !nets[1].pl_rows),
+             "ga_reduce_regions_adam: no plane rewriting for two networks");
+  const int rows = nets[0].pl_rows, cols = nets[0].pl_cols;
+  if (rows > 0 && adam_planes_on() && nets[0].do_adam && split_bf16_on(1) &&
+      rows % 32 == 0 && cols % 32 == 0) {
+    const float* W = nets[0].params + nets[0].pl_beg;
+    PlaneBuf* written = nullptr;
+    std::lock_guard<std::mutex> lock(g_plane_mu);
+    for (PlaneBuf& b : g_plane_bufs)
+      if (b.W == W && b.rows == rows && b.cols == cols) written = &b;
+    if (written) {  // (the forward launch of this step created it)
+      p.net[0].pl_fwd = reinterpret_cast<uint32_t*>(written->fwd);
+      p.net[0].pl_bwd = reinterpret_cast<uint32_t*>(written->bwd);
+      p.net[0].pl_beg = nets[0].pl_beg;
+      p.net[0].pl_rows = rows;
+      p.net[0].pl_cols = cols;
+      written->adam_fresh = true;
+      written->adam_stream = stream;
+      written->bwd_fresh = false;
+    }
+  }
+  const unsigned blocks = (unsigned)p.n_virtual + n_nets;  // + one loss block per network
   hipLaunchKernelGGL(reduce_regions_adam_kernel, dim3(blocks), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("reduce_regions_adam_pair");
+  GA_CHECK_LAUNCH(n_nets == 2 ? "reduce_regions_adam_pair" : "reduce_regions_adam");
   return GA_OK;
 }

@@ -956,45 +956,37 @@ extern "C" int64_t ga_mlp_backward_splits(const ga_mlp_desc* d, int64_t M) {
   return s;
 }
 
-// dW = dz^T in (+ db = column sums of dz) of the MIDDLE layer of two 3-layer networks,
-// both out_w x in_w with 33 .. wide sides (the 128 x 128-tile kernel), split-K over the
-// M rows into n_splits slabs each: the launch ga_mlp_backward_range_f32 makes for
-// layer 1 with fused_first = 1, for two networks in one grid.  Same tiles, same k
-// ranges, same summation order per element.
-extern "C" int ga_wgrad_mid_pair(int64_t M, int64_t n_splits, int out_w, int in_w,
-                                 const float* dza, const float* ina, float* slabs_wa,
-                                 float* slabs_ba, int64_t slab_stride_a,
-                                 const float* dzb, const float* inb, float* slabs_wb,
-                                 float* slabs_bb, int64_t slab_stride_b,
-                                 hipStream_t stream) {
-  GA_REQUIRE(dza && ina && slabs_wa && slabs_ba && dzb && inb && slabs_wb && slabs_bb,
-             "ga_wgrad_mid_pair: null pointer");
+// dW = dz^T in (+ db = column sums of dz) of the MIDDLE layer of a 3-layer network,
+// out_w x in_w with 33 .. wide sides (the 128 x 128-tile kernel), split-K over the M
+// rows into n_splits slabs: the launch ga_mlp_backward_range_f32 makes for layer 1 with
+// fused_first = 1, for two networks in one grid.  Same tiles, same k ranges, same
+// summation order per element.  (One network: ga_mlp_backward_range_f32, any depth.)
+extern "C" int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M,
+                            int64_t n_splits, int out_w, int in_w, hipStream_t stream) {
+  GA_REQUIRE(nets && n_nets == 2,
+             "ga_wgrad_mid: two networks (one: ga_mlp_backward_range_f32)");
   GA_REQUIRE(M > 0 && M < (1ll << 31) && n_splits >= 1 && n_splits <= 1024 &&
-                 out_w > 64 && in_w > 64 && slab_stride_a % 4 == 0 &&
-                 slab_stride_b % 4 == 0,
+                 out_w > 64 && in_w > 64,
              "ga_wgrad_mid_pair: unsupported shape");
-  GA_REQUIRE(ga_aligned16(dza) && ga_aligned16(ina) && ga_aligned16(slabs_wa) &&
-                 ga_aligned16(dzb) && ga_aligned16(inb) && ga_aligned16(slabs_wb),
-             "ga_wgrad_mid_pair: pointers must be 16-B aligned");
   const int kps = (int)(ga_ceil_div(ga_ceil_div(M, n_splits), BK) * BK);
   GemmPair pp;
-  const float* dz[2] = {dza, dzb};
-  const float* in[2] = {ina, inb};
-  float* sw[2] = {slabs_wa, slabs_wb};
-  float* sb[2] = {slabs_ba, slabs_bb};
-  const int64_t ss[2] = {slab_stride_a, slab_stride_b};
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < n_nets; ++i) {
+    const ga_wgrad_mid_net& n = nets[i];
+    GA_REQUIRE(n.dz && n.in && n.slabs_w && n.slabs_b, "ga_wgrad_mid_pair: null pointer");
+    GA_REQUIRE(n.slab_stride % 4 == 0, "ga_wgrad_mid_pair: unsupported shape");
+    GA_REQUIRE(ga_aligned16(n.dz) && ga_aligned16(n.in) && ga_aligned16(n.slabs_w),
+               "ga_wgrad_mid_pair: pointers must be 16-B aligned");
     GemmParams& p = i ? pp.b : pp.a;
     memset(&p, 0, sizeof(p));
     p.K = (int)M;
     p.k_per_split = kps;
     p.epi = EPI_PLAIN;
-    p.c_split_stride = ss[i];
-    p.colsum = sb[i];
-    p.colsum_split_stride = ss[i];
-    p.A = dz[i]; p.lda = round4(out_w); p.B = in[i]; p.ldb = round4(in_w);
+    p.c_split_stride = n.slab_stride;
+    p.colsum = n.slabs_b;
+    p.colsum_split_stride = n.slab_stride;
+    p.A = n.dz; p.lda = round4(out_w); p.B = n.in; p.ldb = round4(in_w);
     p.M = out_w; p.N = in_w;
-    p.C = sw[i]; p.c_rs = round4(in_w); p.c_cs = 1;
+    p.C = n.slabs_w; p.c_rs = round4(in_w); p.c_cs = 1;
     p.colsum_of_b = 0;
     p.gx = (int)ga_ceil_div(p.M, 128); p.gy = (int)ga_ceil_div(p.N, 128);
     p.gz = (int)n_splits;

@@ -244,143 +244,158 @@ float step_scale(const ga_update_args* a, int64_t k) {
                                                           : a->grad_scale;
 }
 
-// One optimizer step on the fused kernels: hidden layers 0 .. L-3 per layer, then
-// last hidden layer + head + loss + gradient seed in one launch, the middle
-// layers' backward GEMMs, the data gradient into the first hidden layer with the
-// first layer's weight gradient in one launch, and one reduction + Adam launch.
-int run_minibatch_fused(const ga_update_args* a, const FusedPlan& f, int64_t k,
-                        int64_t M, const int32_t* idx, float* loss_slot,
-                        ga_stream_t stream_, const ArOrder* order) {
-  hipStream_t stream = (hipStream_t)stream_;
+// Everything ONE network contributes to fused optimizer step k on the M rows `idx`: the
+// loss arguments, where its partial sums go, and one descriptor per launch
+// (fused_train.h).  The narrow step, the wide step and the merged schedule all launch
+// from this description.  Filled in place: the descriptors point into it.
+struct FusedStep {
+  int64_t splits;
+  ga_fused_loss_args la;
+  double* lpart;
+  float* hpart;
+  float* wpart;
+  ga_fused_first_layer fl;  // (fwd.first points here when the kernel computes layer 0)
+  ga_fused_region reg[16];
+  ga_fused_fwd_net fwd;     // wide steps
+  ga_wgrad_mid_net mid;     // 3-layer wide steps
+  ga_fused_dgrad_net dgrad; // wide steps with f.first
+  ga_reduce_net red;
+};
+
+void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t M,
+                const int32_t* idx, FusedStep* s) {
   const ga_mlp_desc* d = a->desc;
   const int L = d->n_layers;
-  const int out_w = d->dims[L];
-  const int64_t splits = ga_mlp_backward_splits(d, M);
-  if (splits > a->max_splits) {
-    ga_set_error("ga_update_epoch: slab workspace too small");
-    return -1;
-  }
+  const int wl = d->dims[L - 1];  // last hidden width
   auto r4 = [](int v) { return (int64_t)((v + 3) & ~3); };
-  int rc;
-  if (f.narrow) {
-    ga_fused_loss_args la;
-    memset(&la, 0, sizeof(la));
-    la.kind = a->kind; la.actions = a->actions; la.lda = a->lda; la.old_ll = a->old_ll;
-    la.adv = a->adv; la.returns = a->returns; la.idx = idx; la.log_std = a->params;
-    la.has_min = a->has_min; la.has_max = a->has_max; la.min_log_std = a->min_log_std;
-    la.max_log_std = a->max_log_std; la.A = out_w; la.algo = a->algo; la.clip = a->clip;
-    la.ent_coeff = a->ent_coeff; la.ent_flags = a->ent_flags;
-    la.double_softmax = a->double_softmax;
-    double* lpart = reinterpret_cast<double*>(a->partials + f.lpart_off);
-    float* part = a->partials + f.hpart_off;
-    const int H = d->dims[1];
-    rc = ga_narrow_train_step(a->params, d->w_off, d->b_off, d->dims[0], H, out_w, a->X,
-                              a->ldx, M, &la, part, lpart, stream);
-    if (rc) return rc;
-    const int64_t ld0 = r4(d->dims[0]);
-    const int64_t off[6] = {0, (int64_t)H * ld0, (int64_t)H * ld0 + H,
-                            (int64_t)H * ld0 + H + (int64_t)H * H,
-                            (int64_t)H * ld0 + 2 * H + (int64_t)H * H,
-                            (int64_t)H * ld0 + 2 * H + (int64_t)H * H + 8 * (int64_t)H};
-    ga_fused_region reg[6];
-    for (int l = 0; l < 3; ++l) {
-      reg[2 * l].beg = d->w_off[l];
-      reg[2 * l].n = (int64_t)d->dims[l + 1] * r4(d->dims[l]);
-      reg[2 * l + 1].beg = d->b_off[l];
-      reg[2 * l + 1].n = d->dims[l + 1];
-    }
-    for (int k = 0; k < 6; ++k) {
-      reg[k].src = part + off[k];
-      reg[k].stride = f.hstride;
-      reg[k].n_part = (int)f.tiles;
-    }
-    const bool exchange = a->comm && a->phase != 1;
-    const bool do_adam = !exchange && a->phase != 1;
-    rc = ga_reduce_regions_adam(reg, 6, a->params, a->grads, a->exp_avg, a->exp_avg_sq,
-                                a->step0 + k + 1, a->lr, a->beta1, a->beta2, a->eps,
-                                step_scale(a, k), do_adam ? 1 : 0, !a->learn_std, lpart,
-                                (int)f.tiles, M, &la, loss_slot, stream);
-    if (rc || !exchange) return rc;
-    return allreduce_and_adam(a, k, stream_, order);
-  }
-  const bool first_in_kernel =
-      fused_first_layer_on() && L == 3 && ga_fused_first_layer_ok(d->dims[0], d->dims[1]);
-  if (L >= 3 && !first_in_kernel) {
-    ga_mlp_desc below = *d;  // layers 0 .. L-3: the hidden layers under the last one
-    below.n_layers = L - 1;
-    rc = ga_mlp_forward_f32(&below, a->params, a->X, a->ldx, idx, M, a->acts, nullptr,
-                            a->ldo, stream_);
-    if (rc) return rc;
-  }
-  ga_fused_loss_args la;
+  s->splits = ga_mlp_backward_splits(d, M);
+  ga_fused_loss_args& la = s->la;
   memset(&la, 0, sizeof(la));
   la.kind = a->kind; la.actions = a->actions; la.lda = a->lda; la.old_ll = a->old_ll;
   la.adv = a->adv; la.returns = a->returns; la.idx = idx; la.log_std = a->params;
   la.has_min = a->has_min; la.has_max = a->has_max; la.min_log_std = a->min_log_std;
-  la.max_log_std = a->max_log_std; la.A = out_w; la.algo = a->algo; la.clip = a->clip;
+  la.max_log_std = a->max_log_std; la.A = d->dims[L]; la.algo = a->algo; la.clip = a->clip;
   la.ent_coeff = a->ent_coeff; la.ent_flags = a->ent_flags;
   la.double_softmax = a->double_softmax;
-  double* lpart = reinterpret_cast<double*>(a->partials + f.lpart_off);
-  float* hpart = a->partials + f.hpart_off;
-  float* wpart = a->partials + f.wpart_off;
-  const int wl = d->dims[L - 1];  // last hidden width
-  const float* Ain = L >= 3 ? a->acts + d->act_off[L - 3] : a->X;
-  ga_fused_first_layer fl;
+  s->lpart = reinterpret_cast<double*>(a->partials + f.lpart_off);
+  s->hpart = a->partials + f.hpart_off;
+  s->wpart = a->partials + f.wpart_off;
+  // the parameter regions: weights and bias of every layer, and the partials that sum
+  // to their gradient
+  const float* nsrc = s->hpart;
+  for (int l = 0; l < L; ++l) {
+    const int64_t wn = (int64_t)d->dims[l + 1] * r4(d->dims[l]);
+    ga_fused_region& w = s->reg[2 * l];
+    ga_fused_region& b = s->reg[2 * l + 1];
+    w.beg = d->w_off[l]; w.n = wn;
+    b.beg = d->b_off[l]; b.n = d->dims[l + 1];
+    if (f.narrow) {  // a tile's shares: W0 | b0 | W1 | b1 | 8 head rows | 8 (narrow_step.hip)
+      w.src = nsrc; b.src = nsrc + (l == L - 1 ? 8 * (int64_t)wl : wn);
+      nsrc = b.src + d->dims[l + 1];
+      w.stride = b.stride = f.hstride; w.n_part = b.n_part = (int)f.tiles;
+    } else if (l == L - 1) {
+      w.src = s->hpart; b.src = s->hpart + 8 * (int64_t)wl;
+      w.stride = b.stride = f.hstride; w.n_part = b.n_part = (int)f.tiles;
+    } else if (l == 0 && f.first) {
+      w.src = s->wpart; b.src = s->wpart + wn;
+      w.stride = b.stride = f.wstride; w.n_part = b.n_part = (int)f.tiles;
+    } else {
+      w.src = a->slabs + d->w_off[l]; b.src = a->slabs + d->b_off[l];
+      w.stride = b.stride = a->n_flat; w.n_part = b.n_part = (int)s->splits;
+    }
+  }
+  const bool exchange = a->comm && a->phase != 1;
+  ga_reduce_net& r = s->red;
+  r.regions = s->reg; r.n_regions = 2 * L;
+  r.params = a->params; r.grads = a->grads; r.exp_avg = a->exp_avg;
+  r.exp_avg_sq = a->exp_avg_sq; r.step = a->step0 + k + 1; r.lr = a->lr;
+  r.beta1 = a->beta1; r.beta2 = a->beta2; r.eps = a->eps; r.scale = step_scale(a, k);
+  r.do_adam = !exchange && a->phase != 1; r.zero_slot0 = !a->learn_std;
+  r.lpart = s->lpart; r.n_lpart = (int)f.tiles; r.M = M; r.loss = &la;
+  r.loss_out = a->losses ? a->losses + k : a->loss_scratch;
+  // (split-operand experiment: the optimizer launch rewrites the planes of the last
+  // hidden layer's weights, the next step's forward launch then needs no plane launch)
+  r.pl_beg = 0; r.pl_rows = r.pl_cols = 0;
+  if (f.first && L == 3 && r.do_adam && ga_split_bf16_any() && d->dims[2] == 256 &&
+      d->dims[1] % 32 == 0) {
+    r.pl_beg = d->w_off[1]; r.pl_rows = d->dims[2]; r.pl_cols = d->dims[1];
+  }
+  if (f.narrow) return;
+  const bool first_in_kernel =
+      fused_first_layer_on() && L == 3 && ga_fused_first_layer_ok(d->dims[0], d->dims[1]);
   if (first_in_kernel) {
+    ga_fused_first_layer& fl = s->fl;
     fl.X = a->X; fl.ldx = a->ldx; fl.W = a->params + d->w_off[0];
     fl.b = a->params + d->b_off[0]; fl.in_w = d->dims[0];
     fl.H = a->acts + d->act_off[0]; fl.ldh = r4(d->dims[1]);
   }
-  rc = ga_fused_fwd_head_loss(Ain, L >= 3 ? r4(d->dims[L - 2]) : a->ldx,
-                              L >= 3 ? nullptr : idx, a->params + d->w_off[L - 2],
-                              r4(d->dims[L - 2]), a->params + d->b_off[L - 2], M, wl,
-                              d->dims[L - 2], a->params + d->w_off[L - 1], r4(wl),
-                              a->params + d->b_off[L - 1], &la,
-                              a->dacts + d->act_off[L - 2], r4(wl), hpart, lpart,
-                              first_in_kernel ? &fl : nullptr, stream);
-  if (rc) return rc;
-  rc = ga_mlp_backward_range_f32(d, a->params, a->X, a->ldx, idx, M, a->acts, nullptr,
-                                 a->ldo, a->dacts, a->slabs, a->n_flat, splits, L - 2,
-                                 f.first ? 1 : 0, stream);
-  if (rc) return rc;
+  ga_fused_fwd_net& fw = s->fwd;
+  fw.A = L >= 3 ? a->acts + d->act_off[L - 3] : a->X;
+  fw.lda = L >= 3 ? r4(d->dims[L - 2]) : a->ldx;
+  fw.a_idx = L >= 3 ? nullptr : idx;
+  fw.W = a->params + d->w_off[L - 2]; fw.ldw = r4(d->dims[L - 2]);
+  fw.bias = a->params + d->b_off[L - 2];
+  fw.head_W = a->params + d->w_off[L - 1]; fw.head_ldw = r4(wl);
+  fw.head_bias = a->params + d->b_off[L - 1];
+  fw.loss = &la; fw.dZ = a->dacts + d->act_off[L - 2]; fw.lddz = r4(wl);
+  fw.hpart = s->hpart; fw.lpart = s->lpart;
+  fw.first = first_in_kernel ? &s->fl : nullptr;
   if (f.first) {
-    rc = ga_fused_dgrad_wgrad0(a->dacts + d->act_off[1], r4(d->dims[2]),
-                               a->params + d->w_off[1], r4(d->dims[1]), M, d->dims[1],
-                               d->dims[2], a->acts + d->act_off[0], r4(d->dims[1]), a->X,
-                               a->ldx, idx, d->dims[0], wpart, stream);
-    if (rc) return rc;
+    ga_fused_dgrad_net& g = s->dgrad;
+    g.dZ2 = a->dacts + d->act_off[1]; g.lddz = r4(d->dims[2]);
+    g.W2 = a->params + d->w_off[1]; g.ldw = r4(d->dims[1]);
+    g.H1 = a->acts + d->act_off[0]; g.ldh = r4(d->dims[1]);
+    g.X = a->X; g.ldx = a->ldx; g.idx = idx; g.wpart = s->wpart;
   }
-  ga_fused_region reg[16];
-  int nr = 0;
-  for (int l = 0; l < L; ++l) {
-    const int64_t wn = (int64_t)d->dims[l + 1] * r4(d->dims[l]);
-    ga_fused_region& w = reg[nr++];
-    ga_fused_region& b = reg[nr++];
-    w.beg = d->w_off[l]; w.n = wn;
-    b.beg = d->b_off[l]; b.n = d->dims[l + 1];
-    if (l == L - 1) {
-      w.src = hpart; b.src = hpart + 8 * (int64_t)wl;
-      w.stride = b.stride = f.hstride; w.n_part = b.n_part = (int)f.tiles;
-    } else if (l == 0 && f.first) {
-      w.src = wpart; b.src = wpart + wn;
-      w.stride = b.stride = f.wstride; w.n_part = b.n_part = (int)f.tiles;
-    } else {
-      w.src = a->slabs + d->w_off[l]; b.src = a->slabs + d->b_off[l];
-      w.stride = b.stride = a->n_flat; w.n_part = b.n_part = (int)splits;
+  if (L == 3) {  // (layer 1 is THE middle layer)
+    ga_wgrad_mid_net& m = s->mid;
+    m.dz = a->dacts + d->act_off[1]; m.in = a->acts + d->act_off[0];
+    m.slabs_w = a->slabs + d->w_off[1]; m.slabs_b = a->slabs + d->b_off[1];
+    m.slab_stride = a->n_flat;
+  }
+}
+
+// One optimizer step on the fused kernels: hidden layers 0 .. L-3 per layer, then
+// last hidden layer + head + loss + gradient seed in one launch, the middle
+// layers' backward GEMMs, the data gradient into the first hidden layer with the
+// first layer's weight gradient in one launch, and one reduction + Adam launch.
+// (Narrow networks: everything up to the reduction in one launch.)
+int run_minibatch_fused(const ga_update_args* a, const FusedPlan& f, int64_t k,
+                        int64_t M, const int32_t* idx, ga_stream_t stream_,
+                        const ArOrder* order) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const ga_mlp_desc* d = a->desc;
+  const int L = d->n_layers;
+  FusedStep s;
+  fused_step(a, f, k, M, idx, &s);
+  int rc;
+  if (f.narrow) {
+    rc = ga_narrow_train_step(a->params, d->w_off, d->b_off, d->dims[0], d->dims[1],
+                              d->dims[L], a->X, a->ldx, M, &s.la, s.hpart, s.lpart,
+                              stream);
+    if (rc) return rc;
+  } else {
+    if (L >= 3 && !s.fwd.first) {
+      ga_mlp_desc below = *d;  // layers 0 .. L-3: the hidden layers under the last one
+      below.n_layers = L - 1;
+      rc = ga_mlp_forward_f32(&below, a->params, a->X, a->ldx, idx, M, a->acts, nullptr,
+                              a->ldo, stream_);
+      if (rc) return rc;
+    }
+    rc = ga_fused_fwd_head_loss(&s.fwd, 1, M, d->dims[L - 1], d->dims[L - 2], stream);
+    if (rc) return rc;
+    rc = ga_mlp_backward_range_f32(d, a->params, a->X, a->ldx, idx, M, a->acts, nullptr,
+                                   a->ldo, a->dacts, a->slabs, a->n_flat, s.splits, L - 2,
+                                   f.first ? 1 : 0, stream);
+    if (rc) return rc;
+    if (f.first) {
+      rc = ga_fused_dgrad_wgrad0(&s.dgrad, 1, M, d->dims[1], d->dims[2], d->dims[0],
+                                 stream);
+      if (rc) return rc;
     }
   }
-  const bool exchange = a->comm && a->phase != 1;
-  const bool do_adam = !exchange && a->phase != 1;
-  // (split-operand experiment: the optimizer launch rewrites the planes of the last
-  // hidden layer's weights, the next step's forward launch then needs no plane launch)
-  if (f.first && L == 3 && do_adam && ga_split_bf16_any() && d->dims[2] == 256 &&
-      d->dims[1] % 32 == 0)
-    ga_reduce_planes_hint(d->w_off[1], d->dims[2], d->dims[1]);
-  rc = ga_reduce_regions_adam(reg, nr, a->params, a->grads, a->exp_avg, a->exp_avg_sq,
-                              a->step0 + k + 1, a->lr, a->beta1, a->beta2, a->eps,
-                              step_scale(a, k), do_adam ? 1 : 0, !a->learn_std, lpart,
-                              (int)f.tiles, M, &la, loss_slot, stream);
-  if (rc || !exchange) return rc;
+  rc = ga_reduce_regions_adam(&s.red, 1, stream);
+  if (rc || !(a->comm && a->phase != 1)) return rc;
   return allreduce_and_adam(a, k, stream_, order);
 }
 
@@ -436,7 +451,7 @@ int run_minibatch(const ga_update_args* a, int64_t k, ga_stream_t stream,
       (a->algo == 0 || a->algo == 1) && a->acts && a->dacts) {
     const FusedPlan f = fused_plan(a->desc, M);
     if (f.ok && f.floats <= a->partials_floats)
-      return run_minibatch_fused(a, f, k, M, idx, loss_slot, stream, order);
+      return run_minibatch_fused(a, f, k, M, idx, stream, order);
   }
   // the head layer (hidden -> means / value) is computed inside the loss kernel
   // when its shape allows: no narrow GEMM launch, no round trip of its output
@@ -583,16 +598,6 @@ static int merged_pair_on() {
 
 namespace {
 
-struct MergedNet {
-  ga_fused_loss_args la;
-  ga_fused_first_layer fl;
-  double* lpart;
-  float* hpart;
-  float* wpart;
-  ga_fused_region reg[8];
-  int nr;
-};
-
 // can step k of the two passes run as pair launches?
 bool merged_ok(const ga_update_args* a, const ga_update_args* b, int64_t k) {
   const ga_update_args* two[2] = {a, b};
@@ -623,107 +628,32 @@ bool merged_ok(const ga_update_args* a, const ga_update_args* b, int64_t k) {
   return ga_mlp_backward_splits(a->desc, M0) == ga_mlp_backward_splits(b->desc, M0);
 }
 
-void merged_fill(const ga_update_args* a, const FusedPlan& f, const int32_t* idx,
-                 int64_t splits, MergedNet* n) {
-  const ga_mlp_desc* d = a->desc;
-  auto r4 = [](int v) { return (int64_t)((v + 3) & ~3); };
-  const int out_w = d->dims[3];
-  ga_fused_loss_args& la = n->la;
-  memset(&la, 0, sizeof(la));
-  la.kind = a->kind; la.actions = a->actions; la.lda = a->lda; la.old_ll = a->old_ll;
-  la.adv = a->adv; la.returns = a->returns; la.idx = idx; la.log_std = a->params;
-  la.has_min = a->has_min; la.has_max = a->has_max; la.min_log_std = a->min_log_std;
-  la.max_log_std = a->max_log_std; la.A = out_w; la.algo = a->algo; la.clip = a->clip;
-  la.ent_coeff = a->ent_coeff; la.ent_flags = a->ent_flags;
-  la.double_softmax = a->double_softmax;
-  n->lpart = reinterpret_cast<double*>(a->partials + f.lpart_off);
-  n->hpart = a->partials + f.hpart_off;
-  n->wpart = a->partials + f.wpart_off;
-  ga_fused_first_layer& fl = n->fl;
-  fl.X = a->X; fl.ldx = a->ldx; fl.W = a->params + d->w_off[0];
-  fl.b = a->params + d->b_off[0]; fl.in_w = d->dims[0];
-  fl.H = a->acts + d->act_off[0]; fl.ldh = r4(d->dims[1]);
-  // the parameter regions, exactly as run_minibatch_fused lists them
-  const int wl = d->dims[2];
-  n->nr = 0;
-  for (int l = 0; l < 3; ++l) {
-    const int64_t wn = (int64_t)d->dims[l + 1] * r4(d->dims[l]);
-    ga_fused_region& w = n->reg[n->nr++];
-    ga_fused_region& bb = n->reg[n->nr++];
-    w.beg = d->w_off[l]; w.n = wn;
-    bb.beg = d->b_off[l]; bb.n = d->dims[l + 1];
-    if (l == 2) {
-      w.src = n->hpart; bb.src = n->hpart + 8 * (int64_t)wl;
-      w.stride = bb.stride = f.hstride; w.n_part = bb.n_part = (int)f.tiles;
-    } else if (l == 0) {
-      w.src = n->wpart; bb.src = n->wpart + wn;
-      w.stride = bb.stride = f.wstride; w.n_part = bb.n_part = (int)f.tiles;
-    } else {
-      w.src = a->slabs + d->w_off[l]; bb.src = a->slabs + d->b_off[l];
-      w.stride = bb.stride = a->n_flat; w.n_part = bb.n_part = (int)splits;
-    }
-  }
-}
-
-// step k of both passes: four pair launches on `stream_`
+// step k of both passes: the four launches on `stream_`, two networks each
 int run_minibatch_merged(const ga_update_args* a, const ga_update_args* b, int64_t k,
                          ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  auto r4 = [](int v) { return (int64_t)((v + 3) & ~3); };
-  int64_t sa, sb, M, Mb;
-  minibatch_range(a, k, &sa, &M);
-  minibatch_range(b, k, &sb, &Mb);
-  const ga_mlp_desc* da = a->desc;
-  const ga_mlp_desc* db = b->desc;
-  const int64_t splits = ga_mlp_backward_splits(da, M);
-  const FusedPlan fa = fused_plan(da, M), fb = fused_plan(db, M);
-  const int32_t* ia = a->perm ? a->perm + sa : nullptr;
-  const int32_t* ib = b->perm ? b->perm + sb : nullptr;
-  MergedNet na, nb;
-  merged_fill(a, fa, ia, splits, &na);
-  merged_fill(b, fb, ib, splits, &nb);
-  const int in_w = da->dims[0], K = da->dims[1], wl = da->dims[2];
-  GA_TRACE(stream_, "merged step k=%lld M=%lld", (long long)k, (long long)M);
-  int rc = ga_fused_fwd_head_loss_pair(
-      M, wl, K,
-      a->params + da->w_off[1], r4(K), a->params + da->b_off[1],
-      a->params + da->w_off[2], r4(wl), a->params + da->b_off[2], &na.la,
-      a->dacts + da->act_off[1], r4(wl), na.hpart, na.lpart, &na.fl,
-      b->params + db->w_off[1], r4(K), b->params + db->b_off[1],
-      b->params + db->w_off[2], r4(wl), b->params + db->b_off[2], &nb.la,
-      b->dacts + db->act_off[1], r4(wl), nb.hpart, nb.lpart, &nb.fl, stream);
-  if (rc) return rc;
-  rc = ga_wgrad_mid_pair(M, splits, wl, K,
-                         a->dacts + da->act_off[1], a->acts + da->act_off[0],
-                         a->slabs + da->w_off[1], a->slabs + da->b_off[1], a->n_flat,
-                         b->dacts + db->act_off[1], b->acts + db->act_off[0],
-                         b->slabs + db->w_off[1], b->slabs + db->b_off[1], b->n_flat,
-                         stream);
-  if (rc) return rc;
-  rc = ga_fused_dgrad_wgrad0_pair(
-      M, K, wl, in_w,
-      a->dacts + da->act_off[1], r4(wl), a->params + da->w_off[1], r4(K),
-      a->acts + da->act_off[0], r4(K), a->X, a->ldx, ia, na.wpart,
-      b->dacts + db->act_off[1], r4(wl), b->params + db->w_off[1], r4(K),
-      b->acts + db->act_off[0], r4(K), b->X, b->ldx, ib, nb.wpart, stream);
-  if (rc) return rc;
-  ga_reduce_net ra, rb;
   const ga_update_args* two[2] = {a, b};
-  MergedNet* nets[2] = {&na, &nb};
-  const FusedPlan* plans[2] = {&fa, &fb};
-  ga_reduce_net* rr[2] = {&ra, &rb};
+  FusedStep s[2];
+  int64_t M = 0;
   for (int i = 0; i < 2; ++i) {
-    const ga_update_args* x = two[i];
-    ga_reduce_net& r = *rr[i];
-    r.regions = nets[i]->reg; r.n_regions = nets[i]->nr;
-    r.params = x->params; r.grads = x->grads; r.exp_avg = x->exp_avg;
-    r.exp_avg_sq = x->exp_avg_sq; r.step = x->step0 + k + 1; r.lr = x->lr;
-    r.beta1 = x->beta1; r.beta2 = x->beta2; r.eps = x->eps; r.scale = step_scale(x, k);
-    r.do_adam = 1; r.zero_slot0 = !x->learn_std; r.lpart = nets[i]->lpart;
-    r.n_lpart = (int)plans[i]->tiles; r.M = M; r.loss = &nets[i]->la;
-    r.loss_out = x->losses ? x->losses + k : x->loss_scratch;
+    int64_t start;
+    minibatch_range(two[i], k, &start, &M);
+    fused_step(two[i], fused_plan(two[i]->desc, M), k, M,
+               two[i]->perm ? two[i]->perm + start : nullptr, &s[i]);
   }
-  return ga_reduce_regions_adam_pair(&ra, &rb, stream);
+  const ga_fused_fwd_net fwd[2] = {s[0].fwd, s[1].fwd};
+  const ga_wgrad_mid_net mid[2] = {s[0].mid, s[1].mid};
+  const ga_fused_dgrad_net dgrad[2] = {s[0].dgrad, s[1].dgrad};
+  const ga_reduce_net red[2] = {s[0].red, s[1].red};
+  const int in_w = a->desc->dims[0], K = a->desc->dims[1], wl = a->desc->dims[2];
+  GA_TRACE(stream_, "merged step k=%lld M=%lld", (long long)k, (long long)M);
+  int rc = ga_fused_fwd_head_loss(fwd, 2, M, wl, K, stream);
+  if (rc) return rc;
+  rc = ga_wgrad_mid(mid, 2, M, s[0].splits, wl, K, stream);
+  if (rc) return rc;
+  rc = ga_fused_dgrad_wgrad0(dgrad, 2, M, K, wl, in_w, stream);
+  if (rc) return rc;
+  return ga_reduce_regions_adam(red, 2, stream);
 }
 
 hipEvent_t g_merge_events[2] = {nullptr, nullptr};

@@ -193,107 +193,73 @@ int ga_fused_first_layer_ok(int in_w, int K) {
   return in_w >= 1 && in_w <= 32 && K % 32 == 0 && K * ((in_w + 3) & ~3) <= 5120;
 }
 int64_t ga_fused_tiles(int64_t M) { return (M + 63) / 64; }
-int ga_fused_fwd_head_loss(const float*, int64_t, const int32_t* a_idx, const float*,
-                           int64_t, const float*, int64_t M, int width, int K,
-                           const float*, int64_t, const float*,
-                           const ga_fused_loss_args* loss, float*, int64_t, float* hpart,
-                           double* lpart, const ga_fused_first_layer* first,
-                           hipStream_t) {
-  logf("fused_fwd M=%lld width=%d K=%d a_idx=%d A=%d first=%d", (long long)M, width, K,
-       a_idx != nullptr, loss->A, first != nullptr);
+// ---- the four launches of a fused step.  One network: the single launch's line; two
+// networks (one grid): the pair_* line.  Either way the fakes write the same extents
+// for every network.
+int ga_fused_fwd_head_loss(const ga_fused_fwd_net* n, int n_nets, int64_t M, int width,
+                           int K, hipStream_t s) {
+  if (n_nets == 1)
+    logf("fused_fwd M=%lld width=%d K=%d a_idx=%d A=%d first=%d", (long long)M, width, K,
+         n->a_idx != nullptr, n->loss->A, n->first != nullptr);
+  else
+    logf("pair_fwd stream=%p M=%lld width=%d K=%d A=%d/%d in=%d/%d", (void*)s,
+         (long long)M, width, K, n[0].loss->A, n[1].loss->A, n[0].first->in_w,
+         n[1].first->in_w);
   // the partial-sum scratch must hold what the plan says
   const int64_t tiles = ga_fused_tiles(M);
-  for (int64_t t = 0; t < tiles; ++t) {
-    lpart[2 * t] = 0.0;
-    lpart[2 * t + 1] = 0.0;
-    memset(hpart + t * (8 * (int64_t)width + 8), 0, sizeof(float) * (8 * width + 8));
+  for (int i = 0; i < n_nets; ++i)
+    for (int64_t t = 0; t < tiles; ++t) {
+      n[i].lpart[2 * t] = n[i].lpart[2 * t + 1] = 0.0;
+      memset(n[i].hpart + t * (8 * (int64_t)width + 8), 0, sizeof(float) * (8 * width + 8));
+    }
+  return 0;
+}
+int ga_wgrad_mid(const ga_wgrad_mid_net* n, int n_nets, int64_t M, int64_t n_splits,
+                 int out_w, int in_w, hipStream_t s) {
+  logf("pair_wgrad stream=%p M=%lld splits=%lld out=%d in=%d", (void*)s, (long long)M,
+       (long long)n_splits, out_w, in_w);
+  for (int i = 0; i < n_nets; ++i)
+    for (int64_t k = 0; k < n_splits; ++k) {
+      memset(n[i].slabs_w + k * n[i].slab_stride, 0, sizeof(float) * (size_t)out_w * in_w);
+      memset(n[i].slabs_b + k * n[i].slab_stride, 0, sizeof(float) * (size_t)out_w);
+    }
+  return 0;
+}
+int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* n, int n_nets, int64_t M, int width,
+                          int K, int in_w, hipStream_t s) {
+  if (n_nets == 1)
+    logf("fused_dgrad M=%lld width=%d K=%d in=%d", (long long)M, width, K, in_w);
+  else
+    logf("pair_dgrad stream=%p M=%lld width=%d K=%d in=%d", (void*)s, (long long)M, width,
+         K, in_w);
+  const int64_t ld0 = (in_w + 3) & ~3, tiles = ga_fused_tiles(M);
+  for (int i = 0; i < n_nets; ++i)
+    for (int64_t t = 0; t < tiles; ++t)
+      memset(n[i].wpart + t * (width * ld0 + width), 0,
+             sizeof(float) * (width * ld0 + width));
+  return 0;
+}
+int ga_reduce_regions_adam(const ga_reduce_net* n, int n_nets, hipStream_t s) {
+  if (n_nets == 1) {
+    logf("reduce_regions n=%d step=%lld scale=%.4f adam=%d zero0=%d lparts=%d M=%lld",
+         n->n_regions, (long long)n->step, n->scale, n->do_adam, n->zero_slot0, n->n_lpart,
+         (long long)n->M);
+    for (int k = 0; k < n->n_regions; ++k)
+      logf("  region beg=%lld n=%lld parts=%d stride=%lld", (long long)n->regions[k].beg,
+           (long long)n->regions[k].n, n->regions[k].n_part, (long long)n->regions[k].stride);
+  } else {
+    logf("pair_reduce stream=%p steps=%lld/%lld regions=%d/%d adam=%d/%d M=%lld", (void*)s,
+         (long long)n[0].step, (long long)n[1].step, n[0].n_regions, n[1].n_regions,
+         n[0].do_adam, n[1].do_adam, (long long)n[0].M);
   }
+  for (int i = 0; i < n_nets; ++i)
+    if (n[i].loss_out) *n[i].loss_out = 1.f;
   return 0;
 }
-int ga_fused_dgrad_wgrad0(const float*, int64_t, const float*, int64_t, int64_t M,
-                          int width, int K, const float*, int64_t, const float*, int64_t,
-                          const int32_t*, int in_w, float* wpart, hipStream_t) {
-  logf("fused_dgrad M=%lld width=%d K=%d in=%d", (long long)M, width, K, in_w);
-  const int64_t ld0 = (in_w + 3) & ~3;
-  const int64_t tiles = ga_fused_tiles(M);
-  for (int64_t t = 0; t < tiles; ++t)
-    memset(wpart + t * (width * ld0 + width), 0, sizeof(float) * (width * ld0 + width));
-  return 0;
-}
-int ga_reduce_regions_adam(const ga_fused_region* r, int n, float*, float*, float*, float*,
-                           int64_t step, double, double, double, double, float scale,
-                           int do_adam, int zero0, const double*, int n_lpart, int64_t M,
-                           const ga_fused_loss_args*, float* loss_out, hipStream_t) {
-  logf("reduce_regions n=%d step=%lld scale=%.4f adam=%d zero0=%d lparts=%d M=%lld", n,
-       (long long)step, scale, do_adam, zero0, n_lpart, (long long)M);
-  for (int k = 0; k < n; ++k)
-    logf("  region beg=%lld n=%lld parts=%d stride=%lld", (long long)r[k].beg,
-         (long long)r[k].n, r[k].n_part, (long long)r[k].stride);
-  if (loss_out) *loss_out = 1.f;
-  return 0;
-}
-// ---- pair launches (two networks per grid): the fakes write the same extents
 int ga_split_bf16_any(void) { return 0; }
-void ga_reduce_planes_hint(int64_t, int, int) {}
 void ga_planes_epoch_begin(void) {}
 int ga_fused_pair_supported(int width, int K, int in_w) {
   return width == 256 && K <= 256 && ga_fused_first_layer_ok(in_w, K);
-}
-int ga_fused_fwd_head_loss_pair(
-    int64_t M, int width, int K, const float*, int64_t, const float*, const float*, int64_t,
-    const float*, const ga_fused_loss_args* la, float*, int64_t, float* hpa, double* lpa,
-    const ga_fused_first_layer* fa, const float*, int64_t, const float*, const float*,
-    int64_t, const float*, const ga_fused_loss_args* lb, float*, int64_t, float* hpb,
-    double* lpb, const ga_fused_first_layer* fb, hipStream_t s) {
-  logf("pair_fwd stream=%p M=%lld width=%d K=%d A=%d/%d in=%d/%d", (void*)s, (long long)M,
-       width, K, la->A, lb->A, fa->in_w, fb->in_w);
-  const int64_t tiles = ga_fused_tiles(M);
-  float* hp[2] = {hpa, hpb};
-  double* lp[2] = {lpa, lpb};
-  for (int i = 0; i < 2; ++i)
-    for (int64_t t = 0; t < tiles; ++t) {
-      lp[i][2 * t] = lp[i][2 * t + 1] = 0.0;
-      memset(hp[i] + t * (8 * (int64_t)width + 8), 0, sizeof(float) * (8 * width + 8));
-    }
-  return 0;
-}
-int ga_wgrad_mid_pair(int64_t M, int64_t n_splits, int out_w, int in_w, const float*,
-                      const float*, float* swa, float* sba, int64_t ssa, const float*,
-                      const float*, float* swb, float* sbb, int64_t ssb, hipStream_t s) {
-  logf("pair_wgrad stream=%p M=%lld splits=%lld out=%d in=%d", (void*)s, (long long)M,
-       (long long)n_splits, out_w, in_w);
-  float* sw[2] = {swa, swb};
-  float* sb[2] = {sba, sbb};
-  const int64_t ss[2] = {ssa, ssb};
-  for (int i = 0; i < 2; ++i)
-    for (int64_t k = 0; k < n_splits; ++k) {
-      memset(sw[i] + k * ss[i], 0, sizeof(float) * (size_t)out_w * in_w);
-      memset(sb[i] + k * ss[i], 0, sizeof(float) * (size_t)out_w);
-    }
-  return 0;
-}
-int ga_fused_dgrad_wgrad0_pair(int64_t M, int width, int K, int in_w, const float*, int64_t,
-                               const float*, int64_t, const float*, int64_t, const float*,
-                               int64_t, const int32_t*, float* wpa, const float*, int64_t,
-                               const float*, int64_t, const float*, int64_t, const float*,
-                               int64_t, const int32_t*, float* wpb, hipStream_t s) {
-  logf("pair_dgrad stream=%p M=%lld width=%d K=%d in=%d", (void*)s, (long long)M, width, K,
-       in_w);
-  const int64_t ld0 = (in_w + 3) & ~3, tiles = ga_fused_tiles(M);
-  float* wp[2] = {wpa, wpb};
-  for (int i = 0; i < 2; ++i)
-    for (int64_t t = 0; t < tiles; ++t)
-      memset(wp[i] + t * (width * ld0 + width), 0, sizeof(float) * (width * ld0 + width));
-  return 0;
-}
-int ga_reduce_regions_adam_pair(const ga_reduce_net* a, const ga_reduce_net* b,
-                                hipStream_t s) {
-  logf("pair_reduce stream=%p steps=%lld/%lld regions=%d/%d adam=%d/%d M=%lld", (void*)s,
-       (long long)a->step, (long long)b->step, a->n_regions, b->n_regions, a->do_adam,
-       b->do_adam, (long long)a->M);
-  if (a->loss_out) *a->loss_out = 1.f;
-  if (b->loss_out) *b->loss_out = 1.f;
-  return 0;
 }
 int ga_narrow_step_supported(int n_layers, const int* dims) {
   return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&

@@ -51,17 +51,22 @@ CASES = {
                           {'entropy_method': 'regularized',
                            'policy_ent_coeff': 0.03}),
 }
+# (not a CASES entry: only the three-schedule test at the end of the file runs it, on
+# 330 samples of its own)
+SHAPES = dict(CASES, merged_ragged=(17, 6, (256, 256), 130, False, {}))
 
 
-def _problem(case):
+def _problem(case, lens=None):
     from garage_amd._dtypes import Box, Discrete, EnvSpec, EpisodeBatch, StepType
-    O, A, hidden, mb, discrete, kw = CASES[case]
+    O, A, hidden, mb, discrete, kw = SHAPES[case]
     P = 40
     act_space = Discrete(A) if discrete else Box(-np.inf, np.inf, (A, ))
     spec = EnvSpec(Box(-np.inf, np.inf, (O, )), act_space, max_episode_length=P)
     rng = np.random.RandomState(len(case))
-    lens = rng.randint(5, P + 1, size=230)
-    lens[0] = P
+    if lens is None:
+        lens = rng.randint(5, P + 1, size=230)
+        lens[0] = P
+    lens = np.asarray(lens)
     S = int(lens.sum())
     st = []
     for n in lens:
@@ -87,7 +92,7 @@ def _algo(case, spec, opt, epochs=1):
     from garage_amd.optimizers import OptimizerWrapper
     from garage_amd.policies import (CategoricalMLPPolicy, GaussianMLPPolicy,
                                      GaussianMLPValueFunction)
-    O, A, hidden, mb, discrete, kw = CASES[case]
+    O, A, hidden, mb, discrete, kw = SHAPES[case]
     kw = dict(kw)
     cls = VPG if kw.pop('vpg', False) else PPO
     torch.manual_seed(3)
@@ -332,3 +337,47 @@ def test_pipelined_kloop_is_bit_identical_to_the_plain_loop(case):
         lib.ga_set_pipelined_kloop(1)
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert torch.equal(res[0][2], res[1][2]) and res[0][3] == res[1][3]
+
+
+def test_merged_pair_two_streams_and_one_stream_are_the_same_bits_on_ragged_tiles():
+    """The three schedules of ``ga_update_epoch_pair`` -- ``ga_set_merged_pair(1)``
+    (step k of both networks as four launches over the tiles of both), two streams,
+    one stream -- on 330 samples in minibatches of 130, 130 and 70 rows, two epochs:
+    every minibatch is above ``merged_ok``'s 64-row floor, ends in a ragged last
+    64-row tile (2 and 6 valid rows), and the tile counts differ (3, 3, 2).  The
+    same bits in the parameters, the second moments and the logged values, and the
+    same launch totals (a pair launch counts for both networks).  The counters cannot
+    tell a pair launch from two single ones: that the pair launches are selected for
+    such a pass is pinned on the CPU (tests/host/update_loop_harness.cpp, check 8b);
+    here the selection is only as good as the switch."""
+    from garage_amd import _lib
+    lib = _lib.load()
+    spec, batch = _problem('merged_ragged',
+                           lens=[40, 35, 30, 25, 40, 40, 40, 40, 40])
+    assert int(batch.lengths.sum()) == 330
+    opt = (torch.optim.Adam, dict(lr=1e-3))
+    out, launches = [], []
+    try:
+        for merged, overlap in ((1, True), (0, True), (0, False)):
+            lib.ga_set_merged_pair(merged)
+            algo, pol, vf = _algo('merged_ragged', spec, opt, epochs=2)
+            algo.overlap_updates = overlap
+            np.random.seed(11)
+            n0 = [int(lib.ga_launch_count(k)) for k in (9, 2)]
+            algo._train_once(0, batch)
+            torch.cuda.synchronize()
+            # fused forward launches, weight-gradient GEMM launches
+            launches.append(tuple(int(lib.ga_launch_count(k)) - n
+                                  for k, n in zip((9, 2), n0)))
+            out.append((pol.net.params.clone(), vf.net.params.clone(),
+                        pol.net.exp_avg_sq.clone(), vf.net.exp_avg_sq.clone(),
+                        dict(algo.last_tabular)))
+    finally:
+        lib.ga_set_merged_pair(0)
+    for got in out[1:]:
+        for i in range(4):
+            assert torch.equal(got[i], out[0][i]), i
+        assert got[4] == out[0][4]
+    assert launches[0] == launches[1] == launches[2], launches
+    # 2 networks x 2 epochs x 3 minibatches
+    assert launches[0][0] == 12, launches

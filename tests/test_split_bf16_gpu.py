@@ -281,7 +281,7 @@ def test_backward_pass_keeps_its_bits_next_to_bf16_mfmas():
 def test_planes_written_by_the_optimizer_launch_are_the_plane_launchs(split_mode):
     """Inside an epoch call the reduction + Adam launch rewrites the bf16 planes of the
     weights it just updated, so that the next step's forward launch needs no plane
-    launch (``ga_reduce_planes_hint``); with that off every forward launch computes
+    launch (``ga_reduce_net.pl_rows``); with that off every forward launch computes
     them again.  Same planes, same bits."""
     import test_fused_train_gpu as T
     lib = split_mode
