@@ -16,6 +16,11 @@
 // the narrow output layer is a 16-lane VALU dot product, and the head (Gaussian:
 // mean + std * noise; categorical: inverse CDF) writes the action and the rollout
 // buffers.  Hidden widths up to 256 (C2, C3); wider nets use the per-layer path.
+// Every network option of ga_mlp_desc runs here: the tanh / linear-output network in
+// the kernels it always had (GEN = false), any other hidden_act / output_act (0 .. 6)
+// and layer_norm in a second set of instantiations (GEN = true) whose epilogues
+// apply gemm_core.h's activations to the same sums and which normalise each hidden
+// layer's input rows in LDS (ln_rows, lnorm.hip's formula).
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv:
 // a template parameter of the kernel) the thread that sampled an env's action also steps it, and a whole
 // rollout is ONE launch with the weights resident on the CU (see the kernel).
@@ -24,6 +29,7 @@
 #include "common.h"
 #include "prof.h"
 
+#include "gemm_core.h"  // act_apply / act_forward_code: the per-layer epilogue's own
 #include "rollout_dev.h"
 
 // ---- Audit (round 3) of out-of-range lanes / idle waves.  Clamped loads (value
@@ -32,11 +38,14 @@
 // the row).  Guarded loads: the register-resident second layer (ncol < N && k < K,
 // a 16-B read at k <= ld - 4), biases (ncol < dims[l + 1], tid < dims[L]), the output
 // layer's [N][ld] block (e < N * ld / 4), observations (env < n && c < in_w), noise
-// rows (per env < n).  Nothing is fetched from an index derived from a wave number
-// alone.
+// rows (per env < n); LayerNorm gamma / beta: the resident copy element by element
+// (tid < dims[l], zero beyond), the streamed 16-B reads only where the vector's first
+// column k < dims[l] -- it ends at k + 3 < round4(dims[l]), the length the layout
+// gives gamma and beta each -- and never for a row index: all 16 rows of the tile
+// exist in LDS (rows of envs >= n hold zeros and normalise to beta; they are never
+// stored).  Nothing is fetched from an index derived from a wave number alone.
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ROWS = 16;          // envs per workgroup (one 16 x 16 MFMA tile of rows)
@@ -46,8 +55,34 @@ constexpr int KC = 32;            // k chunk
 constexpr int LDW = KC + 4;       // weight stage row stride
 constexpr int MAX_OUT = 32;       // widest output head
 
-__device__ __forceinline__ float tanh_fast(float x) {
-  return ga_tanh(x);  // common.h
+// (tanh_fast: gemm_core.h)
+
+// gemm_core.h's act_apply / act_apply_more (forward codes 0 .. 6), the same
+// expressions, one activation per instantiation and force-inlined: a call to the
+// noinline act_apply_more from the rollout kernel, whose lanes hold 256 weight
+// registers, costs 96 - 144 B of scratch per lane for the saves around it.
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float v) {
+  if constexpr (ACT == 1) return tanh_fast(v);
+  else if constexpr (ACT == 2) return fmaxf(v, 0.f);
+  else if constexpr (ACT == 3) return 1.f / (1.f + expf(-v));
+  else if constexpr (ACT == 4) return v > 0.f ? v : expm1f(v);
+  else if constexpr (ACT == 5) return v > 0.f ? v : 0.01f * v;
+  else if constexpr (ACT == 6) return v > 20.f ? v : log1pf(expf(v));
+  else return v;
+}
+// f(integral_constant<forward code>) behind a wave-uniform switch
+template <class F>
+__device__ __forceinline__ void act_dispatch(int act, F&& f) {
+  switch (act) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+  }
 }
 
 template <class Env>
@@ -85,6 +120,10 @@ struct FusedParams {
   // es.raw_obs / es.raw_next)
   int n_steps;
   long long* dbg;  // developer hook: phase timestamps of workgroup 0
+  // GEN kernels only (behind everything the tanh kernels read): the descriptor's
+  // network options -- hidden_act in network code, output_act in forward code
+  int hidden_act, output_act, layer_norm;
+  int64_t ln_off[8];
 };
 
 #define PS_STAMP(i) \
@@ -138,6 +177,68 @@ __device__ __forceinline__ float sum16(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
            __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
   return v;
+}
+
+// layer_normalization: LayerNorm of the 16 x D input tile of a hidden layer, in
+// place in LDS, by lnorm.hip:ln_fwd_kernel's formula (two-pass mean and biased
+// variance, eps 1e-5, y = (x - mean) * rstd * gamma + beta).  16 lanes per row, each
+// lane the 16-B vectors at k = 4 part + 64 i; the columns D <= k < round4(D) stay 0
+// (they are the layer's k padding).  gamma / beta: [round4(D)] floats each, in LDS
+// (RES) or in the parameter buffer; a vector is read only where its first column
+// k < D, and it ends inside the round4(D) floats the layout gives either row.
+constexpr float LN_EPS = 1e-5f;
+__device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
+                                        const float* __restrict__ gamma,
+                                        const float* __restrict__ beta) {
+  const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
+  float* a = tile + r * LDACT;
+  // (branch free, as the output layer reads its rows: out-of-range vectors read
+  // vector 0 and are selected away; the row stays in registers for the three passes)
+  float4 x[HMAX / 64];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < HMAX / 64; ++i) {
+    const int k = part * 4 + 64 * i;
+    float4 v = *reinterpret_cast<const float4*>(a + (k < D ? k : 0));
+    v.x = k < D ? v.x : 0.f;
+    v.y = k + 1 < D ? v.y : 0.f;
+    v.z = k + 2 < D ? v.z : 0.f;
+    v.w = k + 3 < D ? v.w : 0.f;
+    x[i] = v;
+    s += (v.x + v.y) + (v.z + v.w);
+  }
+  const float mean = sum16(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < HMAX / 64; ++i) {
+    const int k = part * 4 + 64 * i;
+    const float d0 = k < D ? x[i].x - mean : 0.f;
+    const float d1 = k + 1 < D ? x[i].y - mean : 0.f;
+    const float d2 = k + 2 < D ? x[i].z - mean : 0.f;
+    const float d3 = k + 3 < D ? x[i].w - mean : 0.f;
+    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  }
+  const float rstd = 1.f / sqrtf(sum16(q) / (float)D + LN_EPS);
+#pragma unroll
+  for (int i = 0; i < HMAX / 64; ++i) {
+    const int k = part * 4 + 64 * i;
+    if (k < D) {
+      const float4 g = *reinterpret_cast<const float4*>(gamma + k);
+      const float4 b = *reinterpret_cast<const float4*>(beta + k);
+      float4 y;
+      y.x = (x[i].x - mean) * rstd * g.x + b.x;
+      y.y = k + 1 < D ? (x[i].y - mean) * rstd * g.y + b.y : 0.f;
+      y.z = k + 2 < D ? (x[i].z - mean) * rstd * g.z + b.z : 0.f;
+      y.w = k + 3 < D ? (x[i].w - mean) * rstd * g.w + b.w : 0.f;
+      *reinterpret_cast<float4*>(a + k) = y;
+    }
+  }
+}
+// (RES && GEN kernels only: a function-scope array, so that the LDS layout of every
+// other instantiation is what it was)
+__device__ __forceinline__ float* ln_resident_store() {
+  __shared__ __attribute__((aligned(16))) float g[2][2][HMAX];
+  return &g[0][0][0];
 }
 
 // The hidden layers run on v_mfma_f32_16x16x4_f32 (lane l: A[row l % 16][slot l / 16],
@@ -208,7 +309,13 @@ __device__ __forceinline__ void resident_layer_k(const float* __restrict__ A, in
 // MFMAs consume: 256 of the 512 registers a wave has at one wave per SIMD), so that
 // layer runs without a barrier or a weight fetch.  Same k order per accumulator as
 // the streamed loop: bit-identical.
-template <bool RES, class Env>
+// GEN = false is the tanh / linear-output / no-LayerNorm network (instruction for
+// instruction what it was before GEN existed).  GEN = true takes hidden_act,
+// output_act and layer_norm from the descriptor, every branch on them wave-uniform:
+// the epilogues call gemm_core.h's act_apply on the same sums, and a LayerNorm
+// (ln_rows) normalises each hidden layer's input tile in LDS first -- gamma / beta
+// resident on the CU next to obias in the RES variant.
+template <bool RES, class Env, bool GEN>
 __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env> p) {
   __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDACT];
   __shared__ __attribute__((aligned(16))) float wst[2][HMAX * LDW];
@@ -270,6 +377,26 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
       for (int e = tid; e < N * (ldw / 4); e += 256)
         reinterpret_cast<float4*>(wst[1])[e] = reinterpret_cast<const float4*>(W)[e];
     }
+    if constexpr (GEN) {
+      // gamma / beta of the (at most two) normalised layer inputs: [l][2][HMAX]
+      // (constant indices: a dynamically indexed ln_off[l] is fetched as a whole
+      // 16-register tuple)
+      if (p.layer_norm) {
+        float* lnp = ln_resident_store();
+        if (L >= 2) {
+          const int D = p.dims[0], ldn = (D + 3) & ~3;
+          const float* g = p.params + p.ln_off[0];
+          lnp[0 * HMAX + tid] = tid < D ? g[tid] : 0.f;
+          lnp[1 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
+        }
+        if (L == 3) {
+          const int D = p.dims[1], ldn = (D + 3) & ~3;
+          const float* g = p.params + p.ln_off[1];
+          lnp[2 * HMAX + tid] = tid < D ? g[tid] : 0.f;
+          lnp[3 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
+        }
+      }
+    }
     __syncthreads();
   }
   for (int sidx = 0; sidx < p.n_steps; ++sidx) {
@@ -327,6 +454,19 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     // this wave's tiles: columns 16 (wave + 4 t); a narrow layer is one tile per wave
     const bool wave_on = 16 * wave < n_pad;
     const bool one_tile = n_pad <= 64;
+    if constexpr (GEN) {
+      // LayerNorm of this layer's input rows, in place (obs_buf already holds the
+      // raw observations)
+      if (p.layer_norm) {
+        const int ldn = (K + 3) & ~3;
+        if constexpr (RES)
+          ln_rows(act[cur], K, ln_resident_store() + (2 * l) * HMAX,
+                  ln_resident_store() + (2 * l + 1) * HMAX);
+        else
+          ln_rows(act[cur], K, p.params + p.ln_off[l], p.params + p.ln_off[l] + ldn);
+        __syncthreads();
+      }
+    }
     f32x4 acc[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
@@ -364,6 +504,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     (void)nk;
     // bias + tanh -> the other activation tile (zero padded to the k chunk)
     float* out = act[cur ^ 1];
+    if constexpr (!GEN) {
     if (wave_on) {
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
@@ -385,6 +526,33 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
         }
       }
     }
+    } else {
+    // GEN: the same epilogue, one copy per activation behind a wave-uniform switch.
+    // The columns N <= ncol < n_pad are 0, not f(0): they are the next layer's k
+    // padding.
+    auto epilogue = [&](auto code) {
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) {
+        if (t == 0 || !one_tile) {
+          const int ncol = 16 * (wave + 4 * t) + r16;
+          const float bv = RES ? (l == 0 ? bias_r[0][t] : bias_r[1][t])
+                               : (ncol < N ? bias[ncol] : 0.f);
+          // (straight-line: f of every element, then one guarded run of stores)
+          float v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float th = act_fwd<decltype(code)::value>(acc[t][r] + bv);
+            v[r] = ncol < N ? th : 0.f;
+          }
+          if (ncol < n_pad) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDACT + ncol] = v[r];
+          }
+        }
+      }
+    };
+    if (wave_on) act_dispatch(act_forward_code(p.hidden_act), epilogue);
+    }  // GEN
     __syncthreads();
     cur ^= 1;
     PS_STAMP(2 + l);
@@ -432,7 +600,16 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
         sum = part * 4 + 64 * i < ldw ? t : sum;
       }
       sum = sum16(sum);
-      if (part == 0) head[r][o] = sum + (RES ? obias[o] : bias[o]);
+      if constexpr (GEN) {
+        if (part == 0) {
+          const float z = sum + (RES ? obias[o] : bias[o]);
+          act_dispatch(p.output_act, [&](auto code) {
+            head[r][o] = act_fwd<decltype(code)::value>(z);
+          });
+        }
+      } else {
+        if (part == 0) head[r][o] = sum + (RES ? obias[o] : bias[o]);
+      }
     }
   }
   __syncthreads();
@@ -657,8 +834,9 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
 // 1 when ga_policy_step_fused_f32 supports this network shape.
 extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
   if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
-  // tanh hidden layers, a linear output layer, no layer normalisation
-  if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return 0;
+  // every nonlinearity the descriptor can name, with or without layer normalisation
+  if (d->hidden_act < 0 || d->hidden_act > 6 || d->output_act < 0 || d->output_act > 6)
+    return 0;
   for (int l = 0; l < d->n_layers; ++l)
     if (d->dims[l] > HMAX) return 0;  // every layer INPUT lives in an LDS tile
   if (d->dims[d->n_layers] > MAX_OUT) return 0;
@@ -740,6 +918,10 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   GA_REQUIRE(a->col >= 0 && a->col < a->Tcap,
              "ga_policy_step_fused_f32: col out of range");
   GA_REQUIRE(ga_aligned16(params), "ga_policy_step_fused_f32: params alignment");
+  if (d->layer_norm)
+    for (int l = 0; l + 1 < d->n_layers; ++l)
+      GA_REQUIRE(d->ln_off[l] > 0 && d->ln_off[l] % 4 == 0,
+                 "ga_policy_step_fused_f32: ln_off[%d] is not a multiple of 4", l);
   FusedParams<Env> p;
   p.n_layers = d->n_layers;
   for (int i = 0; i < 9; ++i) p.dims[i] = d->dims[i];
@@ -753,6 +935,9 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   p.lda = a->lda; p.obs_buf = a->obs_buf; p.act_buf = a->act_buf;
   p.head_buf = a->head_buf; p.ldh = a->ldh;
   p.dbg = g_ps_dbg;
+  p.hidden_act = d->hidden_act; p.output_act = d->output_act;
+  p.layer_norm = d->layer_norm != 0;
+  for (int i = 0; i < 8; ++i) p.ln_off[i] = d->ln_off[i];
   p.env_step = es != nullptr;
   p.n_steps = (int)n_steps;
   if (es) p.es = *es;
@@ -761,13 +946,21 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   // a whole rollout in one launch keeps the weights on the CU (see the kernel)
   const bool resident = n_steps > 1 && d->dims[0] <= KC &&
                         (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
+  // the tanh / linear-output / no-LayerNorm network keeps the kernel it always had
+  const bool general = d->hidden_act != 0 || d->output_act != 0 || d->layer_norm;
   if (resident) ga_prof_count(GA_PROF_ROLLOUT);
-  if (resident)
-    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env>), grid, dim3(256), 0, stream,
-                       p);
+  if (resident && general)
+    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env, true>), grid, dim3(256), 0,
+                       stream, p);
+  else if (resident)
+    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env, false>), grid, dim3(256), 0,
+                       stream, p);
+  else if (general)
+    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env, true>), grid, dim3(256), 0,
+                       stream, p);
   else
-    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env>), grid, dim3(256), 0, stream,
-                       p);
+    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env, false>), grid, dim3(256), 0,
+                       stream, p);
   GA_CHECK_LAUNCH("policy_step_fused");
   return GA_OK;
 }
@@ -781,8 +974,10 @@ extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* param
                                         ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(d && params && X && out, "ga_mlp_forward_fused_f32: null pointer");
-  GA_REQUIRE(ga_policy_step_fused_supported(d),
-             "ga_mlp_forward_fused_f32: unsupported network shape");
+  // (this kernel is the tanh network only; the rollout step's predicate is wider)
+  GA_REQUIRE(ga_policy_step_fused_supported(d) && d->hidden_act == 0 &&
+                 d->output_act == 0 && !d->layer_norm,
+             "ga_mlp_forward_fused_f32: unsupported network shape or options");
   GA_REQUIRE(d->n_layers == 1 || acts, "ga_mlp_forward_fused_f32: acts needed");
   GA_REQUIRE(M > 0 && M < (1ll << 31), "ga_mlp_forward_fused_f32: bad M");
   GA_REQUIRE(ga_aligned16(params), "ga_mlp_forward_fused_f32: params alignment");

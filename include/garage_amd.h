@@ -91,17 +91,22 @@ typedef struct {
   int32_t hidden_act; /* hidden_nonlinearity of MLPModule
                          (torch/modules/mlp_module.py:43-44): 0 = tanh (the
                          GaussianMLP* default; what a zeroed descriptor means),
-                         1 = relu, 2 = none.  The fused / one-launch kernels
-                         implement tanh; other networks take the per-layer GEMMs. */
+                         1 = relu, 2 = none, 3 = sigmoid, 4 = elu, 5 = leaky_relu,
+                         6 = softplus (torch's defaults).  The fused rollout step
+                         (ga_policy_step_fused_f32, the one-launch rollout) takes
+                         all of them; the fused TRAINING kernels implement tanh,
+                         other networks train through the per-layer GEMMs. */
   int32_t output_act; /* output_nonlinearity of the same module applied to the last
                          layer (the Gaussian mean / the value): 0 = none (default),
-                         1 = tanh, 2 = relu.  Per-layer kernels only; the caller
-                         scales the loss's d(output) by the slope before the backward
-                         pass (ga_act_slope_mul_f32). */
+                         1 = tanh, 2 = relu, 3 .. 6 as hidden_act.  Per-layer
+                         kernels and the fused rollout step; the caller scales the
+                         loss's d(output) by the slope before the backward pass
+                         (ga_act_slope_mul_f32). */
   int32_t layer_norm; /* layer_normalization of the same module
                          (multi_headed_mlp_module.py:77-81): LayerNorm(eps 1e-5,
                          affine) over the input of every hidden linear layer.
-                         Per-layer kernels only. */
+                         Per-layer kernels and the fused rollout step (which
+                         normalises the rows in LDS; ln_off[l] % 4 == 0). */
   int32_t pad_;
   int64_t ln_off[8];  /* gamma_l [round4(dims[l])] offset in params; beta_l follows */
   int64_t lnx_off[8]; /* normalised input of hidden layer l in the activation
@@ -122,8 +127,9 @@ GA_API int ga_mlp_forward_f32(const ga_mlp_desc* d, const float* params, const f
                               float* out, int64_t ldo, ga_stream_t stream);
 /* The same forward with every layer in ONE launch (activations of 32 rows stay in
  * LDS between layers, weights stream from L2); ga_mlp_forward_f32 dispatches to
- * it when ga_policy_step_fused_supported(d).  ga_set_fused_forward(0) forces
- * the per-layer GEMM path (A/B measurements). */
+ * it when ga_policy_step_fused_supported(d) and the network is the tanh one
+ * (hidden_act 0, output_act 0, no layer_norm; anything else is refused here).
+ * ga_set_fused_forward(0) forces the per-layer GEMM path (A/B measurements). */
 GA_API int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* params,
                                     const float* X, int64_t ldx, const int32_t* row_idx,
                                     int64_t M, float* acts, float* out, int64_t ldo,
@@ -433,9 +439,11 @@ GA_API int ga_policy_head_sample(const ga_head_args* args, ga_stream_t stream);
 /* The same step with the MLP fused in: policy forward (all layers, activations
  * resident in LDS, weights streamed through LDS, hidden layers on MFMA) + the
  * action head + the rollout-buffer writes in ONE launch; `args->head` is
- * ignored.  Supported when every layer input is <= 256 wide and the head <= 32
+ * ignored.  Supported when every layer input is <= 256 wide and the head <= 32,
+ * for every hidden_act / output_act in 0..6 with or without layer_norm
  * (ga_policy_step_fused_supported); otherwise use ga_mlp_forward_f32 +
- * ga_policy_head_sample. */
+ * ga_policy_head_sample.  head_buf receives the Gaussian mean AFTER the
+ * output_nonlinearity, as the per-layer path's does. */
 GA_API int ga_policy_step_fused_supported(const ga_mlp_desc* d);
 GA_API int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* params,
                                     const ga_head_args* args, ga_stream_t stream);

@@ -4,9 +4,14 @@ observation / action sizes, and with MultiTaskPointVecEnv (K = 4 and K = 16 goal
 on the unit circle, round robin, add-onehot: observations 3 + K wide;
 never_done, so that every episode runs its T steps as the other rows' do and the
 rows differ by the work per step alone): 4096 envs x T 256, a (256, 256)
-Gaussian MLP policy.
+Gaussian MLP policy.  ``--options`` adds PointVecEnv behind a relu, an elu and a
+LayerNorm + tanh policy of the same sizes (rows ``point_relu``, ``point_elu``,
+``point_ln_tanh``): the one-launch rollout with the network options.
 
-    python tools/device_env_rate.py [--envs 4096] [--T 256] [--reps 5]
+    python tools/device_env_rate.py [--envs 4096] [--T 256] [--reps 5] [--options]
+                                    [--lib path/to/libgarage_amd.so]
+
+``--lib`` loads another build of the library (A/B runs against an earlier commit's).
 
 Prints one JSON line per env: the median over `reps` rollouts of
 (env steps taken) / (wall time of rollout_samples incl. packing).
@@ -29,7 +34,10 @@ def measure(kind, n, T, reps):
     from garage_amd.policies import GaussianMLPPolicy
     from garage_amd.sampler import GpuVecSampler, GpuVecWorker
     torch.manual_seed(0)
-    if kind == 'point':
+    options = {}
+    if kind in POLICY_OPTIONS:
+        options = POLICY_OPTIONS[kind]()
+    if kind == 'point' or options:
         env = PointVecEnv(n, goal=(1., 1.), max_episode_length=T)
     elif kind.startswith('multitask'):
         K = int(kind.split('_k')[1])
@@ -40,7 +48,8 @@ def measure(kind, n, T, reps):
             never_done=True, max_episode_length=T)
     else:
         env = SyntheticVecEnv(n, 3, 2, T, seed=1)
-    pol = GaussianMLPPolicy(env.spec, hidden_sizes=(256, 256), init_std=0.1)
+    pol = GaussianMLPPolicy(env.spec, hidden_sizes=(256, 256), init_std=0.1,
+                            **options)
     s = GpuVecSampler(pol, env, max_episode_length=T, n_workers=1,
                       worker_class=GpuVecWorker, seed=1,
                       worker_args=dict(n_envs=n))
@@ -61,13 +70,38 @@ def measure(kind, n, T, reps):
                 min=float(np.min(rates)), max=float(np.max(rates)))
 
 
+def _relu():
+    return dict(hidden_nonlinearity=torch.relu)
+
+
+def _elu():
+    return dict(hidden_nonlinearity=torch.nn.functional.elu)
+
+
+def _ln_tanh():
+    return dict(layer_normalization=True)
+
+
+POLICY_OPTIONS = {'point_relu': _relu, 'point_elu': _elu,
+                  'point_ln_tanh': _ln_tanh}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--envs', type=int, default=4096)
     ap.add_argument('--T', type=int, default=256)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--options', action='store_true',
+                    help='also the point_relu / point_elu / point_ln_tanh rows')
+    ap.add_argument('--lib', help='load this build of libgarage_amd.so')
     a = ap.parse_args()
-    for kind in ('point', 'synthetic', 'multitask_k4', 'multitask_k16'):
+    if a.lib:
+        from garage_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+    kinds = ('point', 'synthetic', 'multitask_k4', 'multitask_k16')
+    if a.options:
+        kinds += tuple(POLICY_OPTIONS)
+    for kind in kinds:
         print(json.dumps(measure(kind, a.envs, a.T, a.reps)))
 
 
