@@ -21,9 +21,9 @@
 // and layer_norm in a second set of instantiations (GEN = true) whose epilogues
 // apply gemm_core.h's activations to the same sums and which normalise each hidden
 // layer's input rows in LDS (ln_rows, lnorm.hip's formula).
-// With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv:
-// a template parameter of the kernel) the thread that sampled an env's action also steps it, and a whole
-// rollout is ONE launch with the weights resident on the CU (see the kernel).
+// With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
+// CartPole: a template parameter of the kernel) the thread that sampled an env's action
+// also steps it, and a whole rollout is ONE launch with the weights resident on the CU (see the kernel).
 #include <type_traits>
 
 #include "common.h"

@@ -1,5 +1,5 @@
 // Rollout-side kernels: action sampling heads, the device environments
-// (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv), per-step
+// (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole), per-step
 // episode bookkeeping and the
 // ragged -> packed compaction.
 //
@@ -381,6 +381,14 @@ MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_l
   return d;
 }
 
+CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t) {
+  CartPoleEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
+  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  d.state = e->state; d.t = e->t; d.resets = e->resets;
+  return d;
+}
+
 static int check_env(const ga_synth_env* e, const char* who) {
   GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
   GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
@@ -420,6 +428,14 @@ static int check_env(const ga_multi_point_env* e, const char* who) {
              "%s: unknown sample strategy %d", who, e->strategy);
   GA_REQUIRE(e->mode == GA_TASK_VANILLA || e->mode == GA_TASK_ADD_ONEHOT,
              "%s: unknown mode %d", who, e->mode);
+  return GA_OK;
+}
+
+static int check_env(const ga_cartpole_env* e, const char* who) {
+  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
   return GA_OK;
 }
 
@@ -494,6 +510,7 @@ GA_BUILD_ENV_STEP_OF(ga_synth_env)
 GA_BUILD_ENV_STEP_OF(ga_point_env)
 GA_BUILD_ENV_STEP_OF(ga_grid_env)
 GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
+GA_BUILD_ENV_STEP_OF(ga_cartpole_env)
 #undef GA_BUILD_ENV_STEP_OF
 
 // Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
@@ -563,6 +580,17 @@ extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t co
              "ga_multi_env_task_draw: num_tasks must be in 1..256 (got %d)", num_tasks);
   return task_draw((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
                    (uint32_t)env_id, counter, num_tasks);
+}
+
+// the device's cartpole_reset_draw on the host (tests compare it with a pure-Python
+// Philox; garage_amd.envs.CartPoleEnv starts its episodes from it)
+extern "C" int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                      float out4[4]) {
+  GA_REQUIRE(out4, "ga_cartpole_reset_draw: null pointer");
+  const CartPoleState s = cartpole_reset_draw(
+      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)env_id, counter);
+  out4[0] = s.x; out4[1] = s.xd; out4[2] = s.th; out4[3] = s.thd;
+  return GA_OK;
 }
 
 extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,

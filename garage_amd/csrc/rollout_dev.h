@@ -1,6 +1,7 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
 // policy + env step of policy_fused.hip: Philox, action sampling, the device
-// environments (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv),
+// environments (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
+// CartPole),
 // the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode (sampler/vec_worker.py:176-204).
 // One thread owns one env.
 #pragma once
@@ -40,13 +41,14 @@ static __device__ __forceinline__ float u32_unit_variance(uint32_t u) {
   const float c = f - 1.0f;
   return c * 1.7320508f;
 }
-static __device__ __forceinline__ float u32_unit_interval(uint32_t u) {
+static __host__ __device__ __forceinline__ float u32_unit_interval(uint32_t u) {
   return ((float)(u >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0,1)
 }
 
 static constexpr uint32_t STREAM_OBS = 0, STREAM_REWARD = 1, STREAM_LENGTH = 2;
 static constexpr uint32_t STREAM_ACTION = 3;
 static constexpr uint32_t STREAM_TASK = 4;
+static constexpr uint32_t STREAM_CARTPOLE = 5;
 
 // ---- action sampling (the rollout head kernels and the fused policy + env step) ----
 static __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
@@ -388,6 +390,124 @@ static __device__ __forceinline__ void env_core(const GridEnv& e, int64_t i,
   grid_one_hot(e, next, next_row);
 }
 
+// ---- CartPole (include/garage_amd.h states the arithmetic, operation by operation) ----
+// One fp32 operation per statement, no contraction; `/` is the correctly rounded
+// division.  The step and the reset draw are written once, here.
+struct CartPoleEnv {
+  int64_t n;
+  int64_t env_id0;   // global id of env 0 of this shard
+  int max_len;
+  uint32_t k0, k1;   // seed
+  float* state;      // [n, 4] x, x_dot, theta, theta_dot
+  int32_t* t;        // [n] steps taken in the current episode
+  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
+};
+struct CartPolePre {
+  float x, xd, th, thd;
+  int t, ep_t;
+};
+struct CartPoleState { float x, xd, th, thd; };
+
+// the state reset number `counter` gives env `env` (global id)
+static __host__ __device__ __forceinline__ CartPoleState cartpole_reset_draw(
+    uint32_t k0, uint32_t k1, uint32_t env, uint32_t counter) {
+#pragma clang fp contract(off)
+  const U4 r = philox4x32_10(env, counter, 0u, STREAM_CARTPOLE << 16, k0, k1);
+  const float w0 = 0.1f * u32_unit_interval(r.x);
+  const float w1 = 0.1f * u32_unit_interval(r.y);
+  const float w2 = 0.1f * u32_unit_interval(r.z);
+  const float w3 = 0.1f * u32_unit_interval(r.w);
+  return CartPoleState{-0.05f + w0, -0.05f + w1, -0.05f + w2, -0.05f + w3};
+}
+
+// one Euler step; returns done (evaluated on the new state)
+static __host__ __device__ __forceinline__ bool cartpole_advance(CartPoleState* s,
+                                                                 bool push_right) {
+#pragma clang fp contract(off)
+  constexpr float S3 = (float)(-1.0 / 6.0), S5 = (float)(1.0 / 120.0),
+                  S7 = (float)(-1.0 / 5040.0);
+  constexpr float C2 = -0.5f, C4 = (float)(1.0 / 24.0), C6 = (float)(-1.0 / 720.0),
+                  C8 = (float)(1.0 / 40320.0);
+  constexpr float FOUR_THIRDS = (float)(4.0 / 3.0);
+  constexpr float TH_LIMIT = (float)(12.0 * 2.0 * 3.141592653589793 / 360.0);
+  const float x = s->x, xd = s->xd, th = s->th, thd = s->thd;
+  const float force = push_right ? 10.0f : -10.0f;
+  const float t2 = th * th;
+  float ps = t2 * S7;
+  ps = S5 + ps;
+  ps = t2 * ps;
+  ps = S3 + ps;
+  ps = t2 * ps;
+  ps = 1.0f + ps;
+  const float sn = th * ps;
+  float pc = t2 * C8;
+  pc = C6 + pc;
+  pc = t2 * pc;
+  pc = C4 + pc;
+  pc = t2 * pc;
+  pc = C2 + pc;
+  pc = t2 * pc;
+  const float cs = 1.0f + pc;
+  const float thd2 = thd * thd;
+  const float pl = 0.05f * thd2;
+  const float pls = pl * sn;
+  const float fsum = force + pls;
+  const float temp = fsum / 1.1f;
+  const float gs = 9.8f * sn;
+  const float ct = cs * temp;
+  const float num = gs - ct;
+  const float cs2 = cs * cs;
+  const float mc = 0.1f * cs2;
+  const float mct = mc / 1.1f;
+  const float br = FOUR_THIRDS - mct;
+  const float den = 0.5f * br;
+  const float th_acc = num / den;
+  const float pa = 0.05f * th_acc;
+  const float pac = pa * cs;
+  const float pact = pac / 1.1f;
+  const float x_acc = temp - pact;
+  const float dx = 0.02f * xd;
+  const float dxd = 0.02f * x_acc;
+  const float dth = 0.02f * thd;
+  const float dthd = 0.02f * th_acc;
+  const float nx = x + dx;
+  const float nth = th + dth;
+  s->x = nx;
+  s->xd = xd + dxd;
+  s->th = nth;
+  s->thd = thd + dthd;
+  return __builtin_fabsf(nx) > 2.4f || __builtin_fabsf(nth) > TH_LIMIT;
+}
+
+static __device__ __forceinline__ void env_reset_one(const CartPoleEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const CartPoleState s =
+      cartpole_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float* st = e.state + 4 * i;
+  float* o = obs + i * ldo;
+  st[0] = s.x; st[1] = s.xd; st[2] = s.th; st[3] = s.thd;
+  o[0] = s.x; o[1] = s.xd; o[2] = s.th; o[3] = s.thd;
+}
+
+static __device__ __forceinline__ void env_core(const CartPoleEnv& e, int64_t i,
+                                                const CartPolePre& p, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  CartPoleState s{p.x, p.xd, p.th, p.thd};
+  const bool done = cartpole_advance(&s, (int)a[0] == 1);
+  float* st = e.state + 4 * i;
+  st[0] = s.x; st[1] = s.xd; st[2] = s.th; st[3] = s.thd;
+  *reward = 1.0f;
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  next_row[0] = s.x; next_row[1] = s.xd; next_row[2] = s.th; next_row[3] = s.thd;
+}
+
 // What a step of env i reads of the env's and the worker's state: loaded up front,
 // so that no load waits behind the step's own stores (the memory counter retires in
 // order).  `o` holds the observation entries the reward looks at when they are few.
@@ -619,6 +739,17 @@ static __device__ __forceinline__ GridPre env_pre(const GridEnv& e, int64_t i) {
   s.ep_t = 0;
   return s;
 }
+static __device__ __forceinline__ CartPolePre env_pre(const CartPoleEnv& e, int64_t i) {
+  CartPolePre s;
+  const float* st = e.state + 4 * i;
+  s.x = st[0];
+  s.xd = st[1];
+  s.th = st[2];
+  s.thd = st[3];
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
 template <class Inner>
 static __device__ __forceinline__ auto env_pre(const MultiTaskEnv<Inner>& e, int64_t i) {
   MultiTaskPre<decltype(env_pre(e.in, i))> s;
@@ -692,6 +823,7 @@ ga_rollout::PointEnv ga_env_to_dev(const ga_point_env* e, int64_t info_ld);
 ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
 ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_point_env* e,
                                                              int64_t info_ld);
+ga_rollout::CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t info_ld);
 template <class GaEnv>
 using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;

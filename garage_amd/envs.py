@@ -17,10 +17,12 @@ Philox-keyed).  ``PointVecEnv`` and ``GridWorldVecEnv`` are the reference's own
 ``PointEnv`` and ``GridWorldEnv`` as device batches (HIP kernels, numpy's fp32
 arithmetic), stepped inside the sampler's one-launch rollout like the synthetic
 env; ``MultiTaskPointVecEnv`` is ``MultiEnvWrapper`` over ``PointEnv`` tasks, the
-task switch at every reset included.  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
+task switch at every reset included.  ``CartPoleVecEnv`` is gym's CartPole-v1 in a
+fixed fp32 arithmetic (``CartPoleEnv`` is its per-env numpy twin).  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -615,6 +617,182 @@ class GridWorldVecEnv(_DeviceVecEnv):
         self._set_struct(e)
 
 
+class CartPoleVecEnv(_DeviceVecEnv):
+    """``n_envs`` cart-poles (gym's ``CartPole-v1``: the same constants, Euler
+    step, termination limits and reward 1 per step) stepped by one HIP kernel,
+    one thread per env, inside the sampler's one-launch rollout.
+
+    Observation ``(x, x_dot, theta, theta_dot)``, ``Discrete(2)`` actions
+    (1 pushes right).  ``include/garage_amd.h`` states the arithmetic operation
+    by operation; :class:`CartPoleEnv` is the per-env numpy twin that gives the
+    same bits.  ``set_state`` / ``get_state`` move the ``(n, 4)`` float32 states
+    (scripted starts; the step counters are left alone).
+
+    Deviations from gym:
+
+    - fp32 throughout, ``sin`` / ``cos`` as fixed polynomials (valid because an
+      episode ends once ``|theta|`` passes 0.2094): one step differs from the
+      float64 equations by a few 1e-7;
+    - resets draw from Philox4x32-10 keyed ``(seed; env_id0 + i, the member's
+      reset counter)`` instead of gym's ``np_random``
+      (:func:`cartpole_reset_draw` gives the same state on the host);
+    - ``max_episode_length`` must be finite (default 500, CartPole-v1's limit):
+      the step that reaches it is TIMEOUT.
+    """
+
+    _KIND = _lib.ENV_CARTPOLE
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+
+    def __init__(self, n_envs, max_episode_length=500, seed=0, env_id0=0,
+                 device=None):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = EnvSpec(Box(-np.inf, np.inf, (4, )), Discrete(2),
+                            max_episode_length=self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, 4, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.CartPoleEnv()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def set_state(self, states):
+        """Every member's state <- row of ``states`` (``(n, 4)`` float32); the
+        current observations follow."""
+        states = torch.as_tensor(np.asarray(states, dtype=np.float32))
+        if tuple(states.shape) != (self.n_envs, 4):
+            raise ValueError('set_state needs an ({}, 4) array, got {}'.format(
+                self.n_envs, tuple(states.shape)))
+        self._state.copy_(states)
+        self.obs[:, :4].copy_(self._state)
+
+    def get_state(self):
+        """The ``(n, 4)`` float32 states."""
+        return self._state.cpu().numpy()
+
+
+def cartpole_reset_draw(seed, env_id, counter):
+    """The ``(4,)`` float32 state reset number ``counter`` gives member
+    ``env_id`` (= ``env_id0 + i``) of a :class:`CartPoleVecEnv` with this seed
+    (host only, no GPU)."""
+    out = (C.c_float * 4)()
+    call('ga_cartpole_reset_draw', int(seed), int(env_id), int(counter), out)
+    return np.array(out, dtype=np.float32)
+
+
+CartPoleStep = collections.namedtuple(
+    'CartPoleStep', ['action', 'reward', 'observation', 'env_info',
+                     'step_type'])
+_F = np.float32
+
+
+class CartPoleEnv:
+    """One member of :class:`CartPoleVecEnv` on the host, in numpy fp32: the
+    same operations in the same order (``include/garage_amd.h``) and the same
+    Philox reset draws, so observations, rewards and step types equal the
+    device batch's bit for bit.  garage's ``Environment`` shape --
+    ``reset() -> (obs, {})``, ``step(a)`` with ``reward / observation /
+    step_type`` -- so a list of them goes behind :class:`HostVecEnv`."""
+
+    S3, S5, S7 = _F(-1.0 / 6.0), _F(1.0 / 120.0), _F(-1.0 / 5040.0)
+    C2, C4, C6, C8 = (_F(-0.5), _F(1.0 / 24.0), _F(-1.0 / 720.0),
+                      _F(1.0 / 40320.0))
+    X_LIMIT = _F(2.4)
+    THETA_LIMIT = _F(12.0 * 2.0 * 3.141592653589793 / 360.0)
+
+    def __init__(self, seed=0, env_id=0, max_episode_length=500):
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = EnvSpec(Box(-np.inf, np.inf, (4, )), Discrete(2),
+                            max_episode_length=self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(4, dtype=np.float32)
+        self._t = 0
+
+    def reset(self):
+        self.state = cartpole_reset_draw(self.seed, self.env_id, self.resets)
+        self.resets += 1
+        self._t = 0
+        return self.state.copy(), {}
+
+    @classmethod
+    def advance(cls, state, push_right):
+        """One Euler step of ``state`` (``(..., 4)`` float32): the new states
+        and ``done``.  Every line is one fp32 operation."""
+        state = np.asarray(state, dtype=np.float32)
+        x, xd, th, thd = (state[..., j] for j in range(4))
+        one, total = _F(1.0), _F(1.1)
+        force = np.where(push_right, _F(10.0), _F(-10.0)).astype(np.float32)
+        t2 = th * th
+        ps = t2 * cls.S7
+        ps = cls.S5 + ps
+        ps = t2 * ps
+        ps = cls.S3 + ps
+        ps = t2 * ps
+        ps = one + ps
+        sn = th * ps
+        pc = t2 * cls.C8
+        pc = cls.C6 + pc
+        pc = t2 * pc
+        pc = cls.C4 + pc
+        pc = t2 * pc
+        pc = cls.C2 + pc
+        pc = t2 * pc
+        cs = one + pc
+        thd2 = thd * thd
+        pl = _F(0.05) * thd2
+        pls = pl * sn
+        fsum = force + pls
+        temp = fsum / total
+        gs = _F(9.8) * sn
+        ct = cs * temp
+        num = gs - ct
+        cs2 = cs * cs
+        mc = _F(0.1) * cs2
+        mct = mc / total
+        br = _F(4.0 / 3.0) - mct
+        den = _F(0.5) * br
+        th_acc = num / den
+        pa = _F(0.05) * th_acc
+        pac = pa * cs
+        pact = pac / total
+        x_acc = temp - pact
+        tau = _F(0.02)
+        dx = tau * xd
+        dxd = tau * x_acc
+        dth = tau * thd
+        dthd = tau * th_acc
+        new = np.stack([x + dx, xd + dxd, th + dth, thd + dthd],
+                       axis=-1).astype(np.float32)
+        done = ((np.abs(new[..., 0]) > cls.X_LIMIT) |
+                (np.abs(new[..., 2]) > cls.THETA_LIMIT))
+        return new, done
+
+    def step(self, action):
+        self.state, done = self.advance(self.state, int(action) == 1)
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length,
+                                    bool(done))
+        return CartPoleStep(action, 1.0, self.state.copy(), {}, st)
+
+    def close(self):
+        pass
+
+
 class NormalizedVecEnv(VecEnv):
     """``garage.envs.normalize`` for a device batch (``envs/normalized_env.py``).
 
@@ -892,4 +1070,5 @@ class HostVecEnv(VecEnv):
 __all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
            'MultiTaskPointVecEnv', 'round_robin_strategy',
            'uniform_random_strategy', 'task_draw', 'GRID_MAPS',
+           'CartPoleVecEnv', 'CartPoleEnv', 'cartpole_reset_draw',
            'NormalizedVecEnv', 'HostVecEnv', 'StepType']

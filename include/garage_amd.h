@@ -561,12 +561,63 @@ typedef struct {
 GA_API int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                   int num_tasks);
 
-/* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env or
- * ga_multi_point_env. */
+/* CartPole (gym's CartPole-v1: Barto, Sutton and Anderson's cart-pole, Euler step),
+ * observation = state (x, x_dot, theta, theta_dot), obs_dim 4, one action column
+ * holding a class index: 1 pushes right, anything else left.  Reward 1 on every step,
+ * the terminating one included.
+ *
+ * The arithmetic is fixed here, so that a numpy twin (garage_amd.envs.CartPoleEnv)
+ * and the kernels give the same bits: every operation below is ONE fp32 operation,
+ * rounded to nearest on its own (no fused multiply-add, correctly rounded division),
+ * evaluated in the order the parentheses give; a constant written (float)(expr) is
+ * the double value of expr rounded to fp32.  sin and cos are fixed polynomials, not
+ * library calls: an episode ends once |theta| passes 0.2094, so |theta| < 0.3 at every
+ * step, where their truncation error is below 1e-10.
+ *
+ *   force = action == 1 ? 10.0f : -10.0f
+ *   t2 = th * th
+ *   sn = th * (1.0f + t2 * (S3 + t2 * (S5 + t2 * S7)))
+ *   cs = 1.0f + t2 * (C2 + t2 * (C4 + t2 * (C6 + t2 * C8)))
+ *     S3 = (float)(-1.0 / 6.0), S5 = (float)(1.0 / 120.0), S7 = (float)(-1.0 / 5040.0),
+ *     C2 = -0.5f, C4 = (float)(1.0 / 24.0), C6 = (float)(-1.0 / 720.0),
+ *     C8 = (float)(1.0 / 40320.0)
+ *   temp   = (force + ((0.05f * (thd * thd)) * sn)) / 1.1f
+ *   th_acc = ((9.8f * sn) - (cs * temp)) /
+ *            (0.5f * ((float)(4.0 / 3.0) - ((0.1f * (cs * cs)) / 1.1f)))
+ *   x_acc  = temp - (((0.05f * th_acc) * cs) / 1.1f)
+ *   x'   = x + (0.02f * xd)        xd'  = xd + (0.02f * x_acc)
+ *   th'  = th + (0.02f * thd)      thd' = thd + (0.02f * th_acc)
+ *   done = |x'| > 2.4f || |th'| > (float)(12.0 * 2.0 * 3.141592653589793 / 360.0)
+ *   step type: TIMEOUT when the episode reaches max_episode_length (1..65535), else
+ *   TERMINAL when done, as for the other envs.
+ *
+ * Reset number c (= resets[i], which then advances) of env i takes the four words
+ * w_0..w_3 of Philox4x32-10 with counter (env_id0 + i, c, 0, 5 << 16) -- stream 5 --
+ * and key (seed & 0xffffffff, seed >> 32):
+ *   u_j = ((float)(w_j >> 8) + 0.5f) * 0x1p-24f,   state[j] = -0.05f + (0.1f * u_j)
+ * (gym draws U(-0.05, 0.05) from its np_random).  ga_cartpole_reset_draw below gives
+ * the same four values on the host. */
+typedef struct {
+  int64_t n, env_id0;
+  int32_t max_episode_length, pad_;
+  uint64_t seed;
+  float* state;     /* [n, 4] x, x_dot, theta, theta_dot */
+  int32_t* t;       /* [n] steps taken in the current episode */
+  uint32_t* resets; /* [n] resets so far */
+} ga_cartpole_env;
+
+/* Host-only (no GPU needed): the state reset number `counter` gives env `env_id`
+ * (= env_id0 + i) of a ga_cartpole_env with this seed. */
+GA_API int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                  float out4[4]);
+
+/* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env,
+ * ga_multi_point_env or ga_cartpole_env. */
 #define GA_ENV_SYNTH 0
 #define GA_ENV_POINT 1
 #define GA_ENV_GRID 2
 #define GA_ENV_MULTI_POINT 3
+#define GA_ENV_CARTPOLE 4
 typedef struct {
   int32_t kind, pad_;
   const void* env;
