@@ -21,6 +21,8 @@
 // and layer_norm in a second set of instantiations (GEN = true) whose epilogues
 // apply gemm_core.h's activations to the same sums and which normalise each hidden
 // layer's input rows in LDS (ln_rows, lnorm.hip's formula).
+// The parameters describe the network as NetDev (net_to_dev, below) and the head as
+// rollout_dev.h's HeadDev (ga_head_to_dev), the struct the per-layer head kernel takes.
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
 // CartPole: a template parameter of the kernel) the thread that sampled an env's action
 // also steps it, and a whole rollout is ONE launch with the weights resident on the CU (see the kernel).
@@ -85,29 +87,18 @@ __device__ __forceinline__ void act_dispatch(int act, F&& f) {
   }
 }
 
-template <class Env>
-struct FusedParams {
+// the layers of a ga_mlp_desc (net_to_dev)
+struct NetDev {
   int n_layers;
   int dims[9];
   int64_t w_off[8], b_off[8];
+};
+
+template <class Env>
+struct FusedParams {
+  NetDev net;
   const float* params;
-  int64_t n, env_id0;
-  int kind;  // 0 gaussian, 1 categorical
-  int has_min, has_max;
-  float min_log_std, max_log_std;
-  const float* noise;
-  int64_t ldn;
-  uint32_t k0, k1, step;
-  int double_softmax;
-  const float* obs;
-  int64_t ldo;
-  int64_t col, Tcap;
-  float* action;
-  int64_t lda;
-  float* obs_buf;
-  float* act_buf;
-  float* head_buf;
-  int64_t ldh;
+  ga_rollout::HeadDev hd;  // the step's head and rollout-buffer writes (rollout_dev.h)
   // env_step: the env's step, the NormalizedEnv statistics, the bookkeeping and the
   // reset of finished envs follow in the same launch, each env by the thread that
   // sampled its action (rollout_dev.h: the code of env_step_record_kernel)
@@ -324,7 +315,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * ROWS;
-  const int L = p.n_layers;
+  const int L = p.net.n_layers;
   float wreg[TPW][HMAX / 4];
   float bias_r[2][TPW];  // RES: hidden biases of this lane's columns
 #pragma unroll
@@ -335,23 +326,23 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const int ncol = 16 * (wave + 4 * t) + r16;
-        const float b = ncol < p.dims[l + 1] ? p.params[p.b_off[l] + ncol] : 0.f;
+        const float b = ncol < p.net.dims[l + 1] ? p.params[p.net.b_off[l] + ncol] : 0.f;
         if (l == 0) bias_r[0][t] = b;
         else bias_r[1][t] = b;
       }
-    if (tid < p.dims[L]) obias[tid] = p.params[p.b_off[L - 1] + tid];
+    if (tid < p.net.dims[L]) obias[tid] = p.params[p.net.b_off[L - 1] + tid];
     // (the register-resident layer multiplies whole tiles: no stale columns)
     for (int e = tid; e < ROWS * LDACT; e += 256) act[0][e] = act[1][e] = 0.f;
     {
-      const int K = p.dims[0], N = p.dims[1];
+      const int K = p.net.dims[0], N = p.net.dims[1];
       WeightStage ws;
-      ws.load(p.params + p.w_off[0], (K + 3) & ~3, N, K, 0);
+      ws.load(p.params + p.net.w_off[0], (K + 3) & ~3, N, K, 0);
       ws.store(wst[0], N, K, 0);
     }
     if (L == 3) {
-      const int K = p.dims[1], N = p.dims[2];
+      const int K = p.net.dims[1], N = p.net.dims[2];
       const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.w_off[1];
+      const float* W = p.params + p.net.w_off[1];
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const int ncol = 16 * (wave + 4 * t) + r16;
@@ -371,9 +362,9 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
       }
     }
     {
-      const int K = p.dims[L - 1], N = p.dims[L];
+      const int K = p.net.dims[L - 1], N = p.net.dims[L];
       const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.w_off[L - 1];
+      const float* W = p.params + p.net.w_off[L - 1];
       for (int e = tid; e < N * (ldw / 4); e += 256)
         reinterpret_cast<float4*>(wst[1])[e] = reinterpret_cast<const float4*>(W)[e];
     }
@@ -384,13 +375,13 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
       if (p.layer_norm) {
         float* lnp = ln_resident_store();
         if (L >= 2) {
-          const int D = p.dims[0], ldn = (D + 3) & ~3;
+          const int D = p.net.dims[0], ldn = (D + 3) & ~3;
           const float* g = p.params + p.ln_off[0];
           lnp[0 * HMAX + tid] = tid < D ? g[tid] : 0.f;
           lnp[1 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
         }
         if (L == 3) {
-          const int D = p.dims[1], ldn = (D + 3) & ~3;
+          const int D = p.net.dims[1], ldn = (D + 3) & ~3;
           const float* g = p.params + p.ln_off[1];
           lnp[2 * HMAX + tid] = tid < D ? g[tid] : 0.f;
           lnp[3 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
@@ -402,14 +393,14 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   for (int sidx = 0; sidx < p.n_steps; ++sidx) {
   // this step's column, Philox counter and observation buffers (they swap roles
   // every step)
-  const int64_t col = p.col + sidx;
-  const uint32_t step = p.step + (uint32_t)sidx;
+  const int64_t col = p.hd.col + sidx;
+  const uint32_t step = p.hd.step + (uint32_t)sidx;
   const bool odd = sidx & 1;
-  const float* obs = odd ? p.es.seen_next : p.obs;
+  const float* obs = odd ? p.es.seen_next : p.hd.obs;
   ga_rollout::EnvStepArgsT<Env> es = p.es;
   if (p.env_step) {
     es.p.col = col;
-    es.seen_next = odd ? const_cast<float*>(p.obs) : p.es.seen_next;
+    es.seen_next = odd ? const_cast<float*>(p.hd.obs) : p.es.seen_next;
     es.p.next_obs = es.seen_next;
     if (p.es.raw_next != p.es.seen_next) {  // NormalizedEnv: the env's own rows
       es.raw_obs = odd ? p.es.raw_next : p.es.raw_obs;
@@ -423,21 +414,21 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   // ---- observations -> act[0] (zero padded to a multiple of the k chunk) and
   //      into the rollout buffer (the list append of vec_worker.py:188)
   PS_STAMP(0);
-  const int in_w = p.dims[0];
+  const int in_w = p.net.dims[0];
   const int in_pad = (in_w + KC - 1) / KC * KC;
   for (int e = tid; e < ROWS * in_pad; e += 256) {
     const int r = e / in_pad, c = e % in_pad;
     const int64_t env = row0 + r;
     float v = 0.f;
-    if (env < p.n && c < in_w) {
-      v = obs[env * p.ldo + c];
-      p.obs_buf[(env * p.Tcap + col) * p.ldo + c] = v;
+    if (env < p.hd.n && c < in_w) {
+      v = obs[env * p.hd.ldo + c];
+      p.hd.obs_buf[(env * p.hd.Tcap + col) * p.hd.ldo + c] = v;
     }
     act[0][r * LDACT + c] = v;
   }
   // the env threads fetch what their env's step will read now, behind the network
   decltype(ga_rollout::env_prefetch(es, 0)) pre;
-  if (p.env_step && tid < ROWS && row0 + tid < p.n)
+  if (p.env_step && tid < ROWS && row0 + tid < p.hd.n)
     pre = ga_rollout::env_prefetch(es, row0 + tid);
   __syncthreads();
   PS_STAMP(1);
@@ -445,10 +436,10 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   // ---- hidden layers on the matrix cores
   int cur = 0;
   for (int l = 0; l < L - 1; ++l) {
-    const int K = p.dims[l], N = p.dims[l + 1];
+    const int K = p.net.dims[l], N = p.net.dims[l + 1];
     const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.w_off[l];
-    const float* bias = p.params + p.b_off[l];
+    const float* W = p.params + p.net.w_off[l];
+    const float* bias = p.params + p.net.b_off[l];
     const int nk = (K + KC - 1) / KC;
     const int n_pad = (N + KC - 1) / KC * KC;
     // this wave's tiles: columns 16 (wave + 4 t); a narrow layer is one tile per wave
@@ -561,10 +552,10 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   // ---- narrow output layer: its weights go to LDS once; 16 lanes per row hold
   //      their k slice of the row in registers and dot it with every output
   {
-    const int K = p.dims[L - 1], N = p.dims[L];
+    const int K = p.net.dims[L - 1], N = p.net.dims[L];
     const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.w_off[L - 1];
-    const float* bias = p.params + p.b_off[L - 1];
+    const float* W = p.params + p.net.w_off[L - 1];
+    const float* bias = p.params + p.net.b_off[L - 1];
     float* wo = wst[RES ? 1 : 0];  // [N][ldw]: N <= 32, ldw <= 256 -> fits one stage
     if constexpr (!RES)
       for (int e = tid; e < N * (ldw / 4); e += 256)
@@ -615,34 +606,37 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   __syncthreads();
   PS_STAMP(10);
 
-  // ---- action head: one thread per env
+  // ---- action head: one thread per env (rollout_dev.h's head_one at this sub-step's
+  //      col / step plus act_row, restated: calling it changes the kernel's code)
   int ended_len = 0;
   if (tid < ROWS) {
     const int64_t env = row0 + tid;
-    if (env < p.n) {
-      const int N = p.dims[L];
-      const int64_t cell = env * p.Tcap + col;
+    if (env < p.hd.n) {
+      const int N = p.net.dims[L];
+      const int64_t cell = env * p.hd.Tcap + col;
       const float* h = head[tid];
       float* act_row = head[tid];  // the sampled action replaces the mean / scores
-      const ga_rollout::ActionNoise rng = {p.noise, p.ldn, p.env_id0, step, p.k0, p.k1};
-      if (p.head_buf) {
+      const ga_rollout::ActionNoise rng = {p.hd.noise, p.hd.ldn, p.hd.env_id0,
+                                           step, p.hd.k0, p.hd.k1};
+      if (p.hd.head_buf) {
         // agent_info: Gaussian mean (probabilities are written below)
-        if (p.kind == 0)
-          for (int j = 0; j < N; ++j) p.head_buf[cell * p.ldh + j] = h[j];
+        if (p.hd.kind == 0)
+          for (int j = 0; j < N; ++j) p.hd.head_buf[cell * p.hd.ldh + j] = h[j];
       }
-      if (p.kind == 0) {
-        const float s = ga_log_std(p.params[0], p.has_min, p.min_log_std, p.has_max,
-                                   p.max_log_std, nullptr);
+      if (p.hd.kind == 0) {
+        const float s = ga_log_std(p.params[0], p.hd.has_min, p.hd.min_log_std,
+                                   p.hd.has_max, p.hd.max_log_std, nullptr);
         ga_rollout::sample_gaussian(h, expf(s), N, rng, env, [&](int j, float a) {
-              p.action[env * p.lda + j] = a;
-              p.act_buf[cell * p.lda + j] = a;
+              p.hd.action[env * p.hd.lda + j] = a;
+              p.hd.act_buf[cell * p.hd.lda + j] = a;
               act_row[j] = a;
             });
       } else {
         const int pick = ga_rollout::sample_categorical(
-            h, N, p.double_softmax, rng, env, p.head_buf ? p.head_buf + cell * p.ldh : nullptr);
-        p.action[env * p.lda] = (float)pick;
-        p.act_buf[cell * p.lda] = (float)pick;
+            h, N, p.hd.double_softmax, rng, env,
+            p.hd.head_buf ? p.hd.head_buf + cell * p.hd.ldh : nullptr);
+        p.hd.action[env * p.hd.lda] = (float)pick;
+        p.hd.act_buf[cell * p.hd.lda] = (float)pick;
         act_row[0] = (float)pick;
       }
       if (p.env_step) ended_len = ga_rollout::env_step_one(es, env, pre, act_row);
@@ -665,9 +659,8 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
 // three per-layer GEMM launches of ga_mlp_forward_f32 (the activations' HBM
 // read between layers disappears, the weights come from L2).
 struct TrainFwdParams {
-  int n_layers;
-  int dims[9];
-  int64_t w_off[8], b_off[8], act_off[8];
+  NetDev net;
+  int64_t act_off[8];
   const float* params;
   const float* X;
   int64_t ldx;
@@ -695,9 +688,9 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
   const int half = lane >> 5, l31 = lane & 31;
   const int ri = wave >> 2, cj = wave & 3;
   const int64_t row0 = (int64_t)blockIdx.x * TROWS;
-  const int L = p.n_layers;
+  const int L = p.net.n_layers;
 
-  const int in_w = p.dims[0];
+  const int in_w = p.net.dims[0];
   const int in_pad = (in_w + KC - 1) / KC * KC;
   for (int e = tid; e < TROWS * in_pad; e += NT) {
     const int r = e / in_pad, c = e % in_pad;
@@ -712,11 +705,11 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
   __syncthreads();
 
   for (int l = 0; l < L - 1; ++l) {
-    const int K = p.dims[l], N = p.dims[l + 1];
+    const int K = p.net.dims[l], N = p.net.dims[l + 1];
     const int ldw = (K + 3) & ~3;
     const int ldh = (N + 3) & ~3;
-    const float* W = p.params + p.w_off[l];
-    const float* bias = p.params + p.b_off[l];
+    const float* W = p.params + p.net.w_off[l];
+    const float* bias = p.params + p.net.b_off[l];
     float* gact = p.acts + p.act_off[l];
     const int nk = (K + KC - 1) / KC;
     const int n0 = cj * 64;
@@ -800,10 +793,10 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
 
   // narrow output layer: its weights go to LDS once, then 8 lanes per row
   {
-    const int K = p.dims[L - 1], N = p.dims[L];
+    const int K = p.net.dims[L - 1], N = p.net.dims[L];
     const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.w_off[L - 1];
-    const float* bias = p.params + p.b_off[L - 1];
+    const float* W = p.params + p.net.w_off[L - 1];
+    const float* bias = p.params + p.net.b_off[L - 1];
     float* wo = wst[0];  // [N][ldw] fits: N <= 32, ldw <= 256
     for (int e = tid; e < N * (ldw / 4); e += NT)
       reinterpret_cast<float4*>(wo)[e] = reinterpret_cast<const float4*>(W)[e];
@@ -830,6 +823,14 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
 }
 
 }  // namespace
+
+static NetDev net_to_dev(const ga_mlp_desc* d) {
+  NetDev n;
+  n.n_layers = d->n_layers;
+  for (int i = 0; i < 9; ++i) n.dims[i] = d->dims[i];
+  for (int i = 0; i < 8; ++i) { n.w_off[i] = d->w_off[i]; n.b_off[i] = d->b_off[i]; }
+  return n;
+}
 
 // 1 when ga_policy_step_fused_f32 supports this network shape.
 extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
@@ -923,17 +924,9 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
       GA_REQUIRE(d->ln_off[l] > 0 && d->ln_off[l] % 4 == 0,
                  "ga_policy_step_fused_f32: ln_off[%d] is not a multiple of 4", l);
   FusedParams<Env> p;
-  p.n_layers = d->n_layers;
-  for (int i = 0; i < 9; ++i) p.dims[i] = d->dims[i];
-  for (int i = 0; i < 8; ++i) { p.w_off[i] = d->w_off[i]; p.b_off[i] = d->b_off[i]; }
-  p.params = params; p.n = a->n; p.env_id0 = a->env_id0; p.kind = a->kind;
-  p.has_min = a->has_min; p.has_max = a->has_max; p.min_log_std = a->min_log_std;
-  p.max_log_std = a->max_log_std; p.noise = a->noise; p.ldn = a->ldn;
-  p.k0 = (uint32_t)(a->seed & 0xffffffffu); p.k1 = (uint32_t)(a->seed >> 32);
-  p.step = a->step; p.double_softmax = a->double_softmax; p.obs = a->obs;
-  p.ldo = a->ldo; p.col = a->col; p.Tcap = a->Tcap; p.action = a->action;
-  p.lda = a->lda; p.obs_buf = a->obs_buf; p.act_buf = a->act_buf;
-  p.head_buf = a->head_buf; p.ldh = a->ldh;
+  p.net = net_to_dev(d);
+  p.params = params;
+  p.hd = ga_head_to_dev(a);
   p.dbg = g_ps_dbg;
   p.hidden_act = d->hidden_act; p.output_act = d->output_act;
   p.layer_norm = d->layer_norm != 0;
@@ -982,11 +975,8 @@ extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* param
   GA_REQUIRE(M > 0 && M < (1ll << 31), "ga_mlp_forward_fused_f32: bad M");
   GA_REQUIRE(ga_aligned16(params), "ga_mlp_forward_fused_f32: params alignment");
   TrainFwdParams p;
-  p.n_layers = d->n_layers;
-  for (int i = 0; i < 9; ++i) p.dims[i] = d->dims[i];
-  for (int i = 0; i < 8; ++i) {
-    p.w_off[i] = d->w_off[i]; p.b_off[i] = d->b_off[i]; p.act_off[i] = d->act_off[i];
-  }
+  p.net = net_to_dev(d);
+  for (int i = 0; i < 8; ++i) p.act_off[i] = d->act_off[i];
   p.params = params; p.X = X; p.ldx = ldx; p.idx = row_idx; p.M = M; p.acts = acts;
   p.out = out; p.ldo = ldo;
   hipLaunchKernelGGL(mlp_train_fwd_fused_kernel, dim3((unsigned)ga_ceil_div(M, TROWS)),

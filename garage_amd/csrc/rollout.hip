@@ -1,7 +1,8 @@
-// Rollout-side kernels: action sampling heads, the device environments
+// Rollout-side kernels: the per-layer path's action head, the device environments
 // (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole), per-step
-// episode bookkeeping and the
-// ragged -> packed compaction.
+// episode bookkeeping and the ragged -> packed compaction.  A step's device code is
+// rollout_dev.h's; here are its kernels and the one converter and check of each C-ABI
+// struct: ga_head_to_dev, ga_record_to_dev / check_record, ga_env_to_dev / check_env.
 //
 // Together they replace the Python per-env loop of VecWorker.step_episode /
 // _gather_episode / collect_episode (sampler/vec_worker.py:139-219) and
@@ -66,31 +67,14 @@ __global__ __launch_bounds__(256) void reward_normalize_kernel(
                                    normalize);
 }
 
-// ---- action heads --------------------------------------------------------------
+// ---- action head ---------------------------------------------------------------
+// the shared description of a step's head plus what only the per-layer path reads
 struct HeadParams {
-  int64_t n;
-  int64_t env_id0;
-  int A;                  // action dim (gaussian) or number of classes (categorical)
-  const float* head;      // [n, ldh] means or class scores
-  int64_t ldh;
-  const float* log_std;   // gaussian: device scalar
-  int has_min, has_max;
-  float min_log_std, max_log_std;
-  const float* noise;     // optional [n, ldn]: N(0,1) (gaussian) / U(0,1) (categorical)
-  int64_t ldn;
-  uint32_t k0, k1;
-  uint32_t step;          // global step counter (Philox counter)
-  int double_softmax;
-  const float* obs;       // [n, ldo] current observations (copied into the buffer)
-  int64_t ldo;
+  HeadDev hd;
+  int A;                 // action dim (gaussian) or number of classes (categorical)
+  const float* head;     // [n, ldh] means or class scores
+  const float* log_std;  // gaussian: device scalar
   int obs_dim;
-  // rollout buffers, column `col`
-  int64_t col, Tcap;
-  float* action;          // [n, lda] actions handed to the env
-  int64_t lda;
-  float* obs_buf;         // [n, Tcap, ldo]
-  float* act_buf;         // [n, Tcap, lda]
-  float* head_buf;        // optional [n, Tcap, ldh]: agent_info 'mean' / probs
 };
 
 // The step's observations into the rollout buffer (the list append of
@@ -99,47 +83,21 @@ struct HeadParams {
 // scalar loads and stores per thread -- cost 156 us per step at C5's 8192 x 376.)
 __device__ __forceinline__ void copy_obs_rows(const HeadParams& p) {
   const int64_t env0 = (int64_t)blockIdx.x * 256;
-  const int64_t rows = min((int64_t)256, p.n - env0);
+  const int64_t rows = min((int64_t)256, p.hd.n - env0);
   const int64_t total = rows * p.obs_dim;
   for (int64_t e = threadIdx.x; e < total; e += 256) {
     const int64_t env = env0 + e / p.obs_dim;
     const int j = (int)(e % p.obs_dim);
-    p.obs_buf[(env * p.Tcap + p.col) * p.ldo + j] = p.obs[env * p.ldo + j];
+    p.hd.obs_buf[(env * p.hd.Tcap + p.hd.col) * p.hd.ldo + j] = p.hd.obs[env * p.hd.ldo + j];
   }
 }
 
-__global__ __launch_bounds__(256) void gaussian_head_kernel(HeadParams p) {
+// one thread per env; hd.kind is wave-uniform
+__global__ __launch_bounds__(256) void head_sample_kernel(HeadParams p) {
   copy_obs_rows(p);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.n) return;
-  const float s = ga_log_std(*p.log_std, p.has_min, p.min_log_std, p.has_max,
-                             p.max_log_std, nullptr);
-  const float* mu = p.head + i * p.ldh;
-  float* act = p.action + i * p.lda;
-  const int64_t cell = i * p.Tcap + p.col;
-  float* act_row = p.act_buf + cell * p.lda;
-  const ActionNoise r = {p.noise, p.ldn, p.env_id0, p.step, p.k0, p.k1};
-  sample_gaussian(mu, expf(s), p.A, r, i, [&](int j, float a) {
-    act[j] = a;
-    act_row[j] = a;
-  });
-  if (p.head_buf) {
-    float* h = p.head_buf + cell * p.ldh;
-    for (int j = 0; j < p.A; ++j) h[j] = mu[j];
-  }
-}
-
-__global__ __launch_bounds__(256) void categorical_head_kernel(HeadParams p) {
-  copy_obs_rows(p);
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.n) return;
-  const float* sc = p.head + i * p.ldh;
-  const int64_t cell = i * p.Tcap + p.col;
-  const ActionNoise r = {p.noise, p.ldn, p.env_id0, p.step, p.k0, p.k1};
-  const int pick = sample_categorical(sc, p.A, p.double_softmax, r, i,
-                                      p.head_buf ? p.head_buf + cell * p.ldh : nullptr);
-  p.action[i * p.lda] = (float)pick;
-  p.act_buf[cell * p.lda] = (float)pick;
+  if (i >= p.hd.n) return;
+  head_one(p.hd, p.head + i * p.hd.ldh, p.A, p.log_std, i);
 }
 
 __global__ __launch_bounds__(256) void record_step_kernel(RecordParams p) {
@@ -279,6 +237,44 @@ __global__ __launch_bounds__(256) void feistel_perm_kernel(int64_t n, int half_b
 // ---------------------------------------------------------------------------
 // C ABI (see include/garage_amd.h)
 // ---------------------------------------------------------------------------
+// the kernel-side head of a step (rollout_dev.h)
+HeadDev ga_head_to_dev(const ga_head_args* a) {
+  HeadDev d;
+  d.n = a->n; d.env_id0 = a->env_id0; d.kind = a->kind; d.has_min = a->has_min;
+  d.has_max = a->has_max; d.min_log_std = a->min_log_std; d.max_log_std = a->max_log_std;
+  d.noise = a->noise; d.ldn = a->ldn; ga_key(a->seed, &d.k0, &d.k1); d.step = a->step;
+  d.double_softmax = a->double_softmax; d.obs = a->obs; d.ldo = a->ldo; d.col = a->col;
+  d.Tcap = a->Tcap; d.action = a->action; d.lda = a->lda; d.obs_buf = a->obs_buf;
+  d.act_buf = a->act_buf; d.head_buf = a->head_buf; d.ldh = a->ldh;
+  return d;
+}
+
+// the kernel-side record of a step, and its checks (`n`: the batch it must cover)
+static RecordParams ga_record_to_dev(const ga_record_args* a) {
+  RecordParams p;
+  p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
+  p.max_episode_length = a->max_episode_length; p.reward = a->reward;
+  p.step_type = a->step_type; p.next_obs = a->next_obs; p.ldo = a->ldo;
+  p.obs_dim = a->obs_dim; p.ep_t = a->ep_t; p.rew_buf = a->rew_buf;
+  p.st_buf = a->st_buf; p.tail_buf = a->tail_buf; p.lastobs_buf = a->lastobs_buf;
+  p.done = a->done; p.step_eps = a->step_eps; p.step_samples = a->step_samples;
+  p.terminal_only = a->terminal_only;
+  return p;
+}
+
+static int check_record(const ga_record_args* a, int64_t n, const char* who) {
+  GA_REQUIRE(a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
+                 a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
+                 a->step_eps && a->step_samples,
+             "%s: null pointer", who);
+  GA_REQUIRE(a->n == n && n > 0 && a->col >= 0 && a->col < a->Tcap,
+             "%s: col %lld out of range (Tcap %lld)", who, (long long)a->col,
+             (long long)a->Tcap);
+  GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
 extern "C" int ga_policy_head_sample(const ga_head_args* a, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a && a->head && a->obs && a->action && a->obs_buf && a->act_buf,
@@ -289,44 +285,20 @@ extern "C" int ga_policy_head_sample(const ga_head_args* a, ga_stream_t stream_)
              "range (Tcap %lld)", (long long)a->col, (long long)a->Tcap);
   GA_REQUIRE(a->kind == 1 || (a->log_std && a->lda >= a->A),
              "ga_policy_head_sample: gaussian head needs log_std and lda >= A");
-  HeadParams p;
-  p.n = a->n; p.env_id0 = a->env_id0; p.A = a->A; p.head = a->head; p.ldh = a->ldh;
-  p.log_std = a->log_std; p.has_min = a->has_min; p.has_max = a->has_max;
-  p.min_log_std = a->min_log_std; p.max_log_std = a->max_log_std; p.noise = a->noise;
-  p.ldn = a->ldn; p.k0 = (uint32_t)(a->seed & 0xffffffffu);
-  p.k1 = (uint32_t)(a->seed >> 32); p.step = a->step;
-  p.double_softmax = a->double_softmax; p.obs = a->obs; p.ldo = a->ldo;
-  p.obs_dim = a->obs_dim; p.col = a->col; p.Tcap = a->Tcap; p.action = a->action;
-  p.lda = a->lda; p.obs_buf = a->obs_buf; p.act_buf = a->act_buf;
-  p.head_buf = a->head_buf;
-  const dim3 grid((unsigned)ga_ceil_div(a->n, 256));
-  if (a->kind == 0)
-    hipLaunchKernelGGL(gaussian_head_kernel, grid, dim3(256), 0, stream, p);
-  else
-    hipLaunchKernelGGL(categorical_head_kernel, grid, dim3(256), 0, stream, p);
+  const HeadParams p = {ga_head_to_dev(a), a->A, a->head, a->log_std, a->obs_dim};
+  hipLaunchKernelGGL(head_sample_kernel, dim3((unsigned)ga_ceil_div(a->n, 256)),
+                     dim3(256), 0, stream, p);
   GA_CHECK_LAUNCH("policy_head_sample");
   return GA_OK;
 }
 
 extern "C" int ga_record_step(const ga_record_args* a, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(a && a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
-                 a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
-                 a->step_eps && a->step_samples,
-             "ga_record_step: null pointer");
-  GA_REQUIRE(a->n > 0 && a->col >= 0 && a->col < a->Tcap,
-             "ga_record_step: col %lld out of range (Tcap %lld)", (long long)a->col,
-             (long long)a->Tcap);
-  GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
-             "ga_record_step: max_episode_length must be in 1..65535");
-  RecordParams p;
-  p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
-  p.max_episode_length = a->max_episode_length; p.reward = a->reward;
-  p.step_type = a->step_type; p.next_obs = a->next_obs; p.ldo = a->ldo;
-  p.obs_dim = a->obs_dim; p.ep_t = a->ep_t; p.rew_buf = a->rew_buf;
-  p.st_buf = a->st_buf; p.tail_buf = a->tail_buf; p.lastobs_buf = a->lastobs_buf;
-  p.done = a->done; p.step_eps = a->step_eps; p.step_samples = a->step_samples;
-  p.terminal_only = a->terminal_only;
+  const char* who = "ga_record_step";
+  GA_REQUIRE(a, "%s: null pointer", who);
+  int rc = check_record(a, a->n, who);
+  if (rc) return rc;
+  const RecordParams p = ga_record_to_dev(a);
   hipLaunchKernelGGL(record_step_kernel, dim3((unsigned)ga_ceil_div(a->n, 256)),
                      dim3(256), 0, stream, p);
   GA_CHECK_LAUNCH("record_step");
@@ -339,7 +311,7 @@ SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t) {
   SynthEnv d;
   d.n = e->n; d.env_id0 = e->env_id0; d.obs_dim = e->obs_dim; d.act_dim = e->act_dim;
   d.discrete = e->discrete; d.min_len = e->min_len; d.max_len = e->max_len;
-  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  ga_key(e->seed, &d.k0, &d.k1);
   d.episode = e->episode; d.t = e->t; d.len = e->len;
   return d;
 }
@@ -375,7 +347,7 @@ MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_l
   d.n = e->n; d.in = ga_env_to_dev(&p, info_ld);
   d.num_tasks = e->num_tasks; d.strategy = e->strategy;
   d.one_hot = e->mode == GA_TASK_ADD_ONEHOT;
-  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  ga_key(e->seed, &d.k0, &d.k1);
   d.payload = e->task_goals; d.last_task = e->last_task; d.resets = e->resets;
   d.task_id = e->task_id; d.info_ld = info_ld;
   return d;
@@ -384,7 +356,7 @@ MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_l
 CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t) {
   CartPoleEnv d;
   d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  d.k0 = (uint32_t)(e->seed & 0xffffffffu); d.k1 = (uint32_t)(e->seed >> 32);
+  ga_key(e->seed, &d.k0, &d.k1);
   d.state = e->state; d.t = e->t; d.resets = e->resets;
   return d;
 }
@@ -454,25 +426,11 @@ int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_a
     GA_REQUIRE(a->ldo >= obs_dim,
                "%s: observation rows of %lld columns are narrower than 3 + num_tasks = %d",
                who, (long long)a->ldo, obs_dim);
-  GA_REQUIRE(a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
-                 a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
-                 a->step_eps && a->step_samples && actions && obs,
-             "%s: null pointer", who);
-  GA_REQUIRE(a->n == env->n && a->col >= 0 && a->col < a->Tcap,
-             "%s: col %lld out of range (Tcap %lld)", who, (long long)a->col,
-             (long long)a->Tcap);
-  GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
+  GA_REQUIRE(actions && obs, "%s: null pointer", who);
+  rc = check_record(a, env->n, who);
+  if (rc) return rc;
   GA_REQUIRE(a->ldo >= obs_dim && a->obs_dim == obs_dim && lda >= ga_env_act_width(env),
              "%s: leading dimensions too small", who);
-  RecordParams p;
-  p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
-  p.max_episode_length = a->max_episode_length; p.reward = a->reward;
-  p.step_type = a->step_type; p.next_obs = a->next_obs; p.ldo = a->ldo;
-  p.obs_dim = a->obs_dim; p.ep_t = a->ep_t; p.rew_buf = a->rew_buf;
-  p.st_buf = a->st_buf; p.tail_buf = a->tail_buf; p.lastobs_buf = a->lastobs_buf;
-  p.done = a->done; p.step_eps = a->step_eps; p.step_samples = a->step_samples;
-  p.terminal_only = a->terminal_only;
   NormParams nm;
   memset(&nm, 0, sizeof(nm));
   const float* raw_obs = obs;
@@ -496,7 +454,7 @@ int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_a
     }
   }
   out->e = ga_env_to_dev(env, a->Tcap);  // env_infos go into the [n, Tcap] buffers
-  out->p = p; out->nm = nm;
+  out->p = ga_record_to_dev(a); out->nm = nm;
   out->actions = actions; out->lda = lda; out->raw_obs = raw_obs; out->raw_next = raw_next;
   out->seen_next = (float*)a->next_obs; out->reward = (float*)a->reward;
   out->step_type = (uint8_t*)a->step_type;
@@ -578,8 +536,9 @@ extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t co
                                       int num_tasks) {
   GA_REQUIRE(num_tasks >= 1 && num_tasks <= 256,
              "ga_multi_env_task_draw: num_tasks must be in 1..256 (got %d)", num_tasks);
-  return task_draw((uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
-                   (uint32_t)env_id, counter, num_tasks);
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  return task_draw(k0, k1, (uint32_t)env_id, counter, num_tasks);
 }
 
 // the device's cartpole_reset_draw on the host (tests compare it with a pure-Python
@@ -587,8 +546,9 @@ extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t co
 extern "C" int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                       float out4[4]) {
   GA_REQUIRE(out4, "ga_cartpole_reset_draw: null pointer");
-  const CartPoleState s = cartpole_reset_draw(
-      (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)env_id, counter);
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  const CartPoleState s = cartpole_reset_draw(k0, k1, (uint32_t)env_id, counter);
   out4[0] = s.x; out4[1] = s.xd; out4[2] = s.th; out4[3] = s.thd;
   return GA_OK;
 }
@@ -677,9 +637,10 @@ extern "C" int ga_permutation_i32(int64_t n, uint64_t key, int32_t* out,
   GA_REQUIRE(out && n > 0 && n < (1ll << 30), "ga_permutation_i32: bad arguments");
   int half_bits = 1;
   while ((1ll << (2 * half_bits)) < n) ++half_bits;
+  uint32_t k0, k1;
+  ga_key(key, &k0, &k1);
   hipLaunchKernelGGL(feistel_perm_kernel, dim3((unsigned)ga_ceil_div(n, 256)),
-                     dim3(256), 0, stream, n, half_bits,
-                     (uint32_t)(key & 0xffffffffu), (uint32_t)(key >> 32), out);
+                     dim3(256), 0, stream, n, half_bits, k0, k1, out);
   GA_CHECK_LAUNCH("feistel_perm");
   return GA_OK;
 }

@@ -1,9 +1,9 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
-// policy + env step of policy_fused.hip: Philox, action sampling, the device
-// environments (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
-// CartPole),
-// the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode (sampler/vec_worker.py:176-204).
-// One thread owns one env.
+// policy + env step of policy_fused.hip, each written once: Philox, the head of a step
+// (HeadDev, head_one), the device environments (synthetic, PointEnv, GridWorldEnv,
+// MultiEnvWrapper over PointEnv, CartPole; env_pre / env_core / env_reset_one of each),
+// the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
+// (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
 #pragma once
 #include "common.h"
 
@@ -50,7 +50,14 @@ static constexpr uint32_t STREAM_ACTION = 3;
 static constexpr uint32_t STREAM_TASK = 4;
 static constexpr uint32_t STREAM_CARTPOLE = 5;
 
-// ---- action sampling (the rollout head kernels and the fused policy + env step) ----
+// the two Philox key words of a 64-bit seed
+static __host__ __device__ __forceinline__ void ga_key(uint64_t seed, uint32_t* k0,
+                                                       uint32_t* k1) {
+  *k0 = (uint32_t)(seed & 0xffffffffu);
+  *k1 = (uint32_t)(seed >> 32);
+}
+
+// ---- action sampling ------------------------------------------------------------
 static __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
                                                   float* z1) {
   const float a = u32_unit_interval(u0), b = u32_unit_interval(u1);
@@ -127,6 +134,50 @@ static __device__ __forceinline__ int sample_categorical(const float* sc, int A,
   return pick;
 }
 
+// ---- the head of a rollout step ------------------------------------------------
+// What the head reads and where it writes: ga_head_args (ga_head_to_dev) without the
+// per-layer path's own `head`, `A`, `log_std`, `obs_dim`.  The fused kernel's
+// parameters and the per-layer head kernel's both hold one.
+struct HeadDev {
+  int64_t n, env_id0;
+  int kind;  // 0 gaussian, 1 categorical
+  int has_min, has_max;
+  float min_log_std, max_log_std;
+  const float* noise; int64_t ldn;  // optional [n, ldn]: N(0,1) / U(0,1) by kind
+  uint32_t k0, k1, step;            // seed, global step counter (Philox counter)
+  int double_softmax;
+  const float* obs; int64_t ldo;    // [n, ldo] current observations
+  int64_t col, Tcap;                // the rollout buffers' column of this step
+  float* action; int64_t lda;       // [n, lda] actions handed to the env
+  float* obs_buf; float* act_buf;   // [n, Tcap, ldo], [n, Tcap, lda]
+  float* head_buf; int64_t ldh;     // optional [n, Tcap, ldh]: agent_info mean / probs
+};
+
+// The head of env `env`: h = its A means (kind 0; log_std: the device scalar) or class
+// scores (kind 1).  Mean / probabilities -> head_buf when given, the sample -> action
+// and act_buf.  The per-layer head kernel calls it; the fused kernel's `action head`
+// section restates it at its sub-step's column and Philox step (see there).
+static __device__ __forceinline__ void head_one(const HeadDev& p, const float* h, int A,
+                                                const float* log_std, int64_t env) {
+  const int64_t cell = env * p.Tcap + p.col;
+  const ActionNoise rng = {p.noise, p.ldn, p.env_id0, p.step, p.k0, p.k1};
+  if (p.head_buf && p.kind == 0)  // agent_info 'mean' (sample_categorical: the probs)
+    for (int j = 0; j < A; ++j) p.head_buf[cell * p.ldh + j] = h[j];
+  if (p.kind == 0) {
+    const float s = ga_log_std(*log_std, p.has_min, p.min_log_std, p.has_max,
+                               p.max_log_std, nullptr);
+    sample_gaussian(h, expf(s), A, rng, env, [&](int j, float a) {
+      p.action[env * p.lda + j] = a;
+      p.act_buf[cell * p.lda + j] = a;
+    });
+  } else {
+    const int pick = sample_categorical(h, A, p.double_softmax, rng, env,
+                                        p.head_buf ? p.head_buf + cell * p.ldh : nullptr);
+    p.action[env * p.lda] = (float)pick;
+    p.act_buf[cell * p.lda] = (float)pick;
+  }
+}
+
 // ---- synthetic environment ---------------------------------------------------
 struct SynthEnv {
   int64_t n;
@@ -158,8 +209,8 @@ static __device__ __forceinline__ int synth_len(const SynthEnv& e, uint32_t env,
 }
 
 // reset envs where mask != 0 (mask == null: all); writes the first observation.
-static __device__ __forceinline__ void synth_reset_one(const SynthEnv& e, int64_t i,
-                                                float* obs, int64_t ldo) {
+static __device__ __forceinline__ void env_reset_one(const SynthEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
   const uint32_t env = (uint32_t)(e.env_id0 + i);
   const int ep = e.episode[i] + 1;
   e.episode[i] = ep;
@@ -523,9 +574,10 @@ static __device__ __forceinline__ int synth_reward_width(const SynthEnv& e) {
 
 // one env step: reward, step type and the (true) next observation.  `a` is the
 // env's action row (any address space), `o` its observation row.
-static __device__ __forceinline__ void synth_step_core(
-    const SynthEnv& e, int64_t i, const EnvPre& s, const float* a, const float* o,
-    float* next_row, float* reward, uint8_t* step_type) {
+static __device__ __forceinline__ void env_core(const SynthEnv& e, int64_t i,
+                                                const EnvPre& s, const float* a,
+                                                const float* o, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
 #pragma clang fp contract(off)
   const uint32_t env = (uint32_t)(e.env_id0 + i);
   const uint32_t ep = (uint32_t)s.ep;
@@ -765,18 +817,6 @@ static __device__ __forceinline__ auto env_prefetch(const EnvStepArgsT<Env>& a, 
   return s;
 }
 
-// the synthetic env under the names env_step_one dispatches on
-static __device__ __forceinline__ void env_core(const SynthEnv& e, int64_t i,
-                                                const EnvPre& s, const float* a,
-                                                const float* o, float* next_row, int64_t,
-                                                float* reward, uint8_t* step_type) {
-  synth_step_core(e, i, s, a, o, next_row, reward, step_type);
-}
-static __device__ __forceinline__ void env_reset_one(const SynthEnv& e, int64_t i,
-                                                     float* obs, int64_t ldo) {
-  synth_reset_one(e, i, obs, ldo);
-}
-
 // `s`: env_prefetch(a, i), taken before anything of this step was stored;
 // `act_row`: the env's action (a.actions + i * a.lda, or a copy on chip).  The env
 // kind is the type of `a.e`: every kernel that steps envs is instantiated per kind.
@@ -816,8 +856,10 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgsT<Env>& a, i
 
 }  // namespace ga_rollout
 
-// The kernel-side env of each C-ABI env struct (rollout.hip).  info_ld: row stride of
-// the env_info buffers (1: [n], Tcap: the [n, Tcap] record buffers).
+// The kernel-side head of ga_head_args and the kernel-side env of each C-ABI env
+// struct (rollout.hip).  info_ld: row stride of the env_info buffers (1: [n],
+// Tcap: the [n, Tcap] record buffers).
+ga_rollout::HeadDev ga_head_to_dev(const ga_head_args* a);
 ga_rollout::SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t info_ld);
 ga_rollout::PointEnv ga_env_to_dev(const ga_point_env* e, int64_t info_ld);
 ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
