@@ -7,7 +7,7 @@ ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
 HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step lnorm
-CPPS  := errors prof update comm rollout_loop
+CPPS  := errors prof update comm rollout_loop mlp_layers
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -25,11 +25,11 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function 
 
 all: $(OUT)/libgarage_amd.so
 
-$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/gemm_core.h $(CSRC)/loss_rows.h $(CSRC)/fused_train.h $(CSRC)/rollout_dev.h include/garage_amd.h
+$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/gemm_core.h $(CSRC)/gemm_params.h $(CSRC)/loss_rows.h $(CSRC)/fused_train.h $(CSRC)/rollout_dev.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
-$(OUT)/%.o: $(CSRC)/%.cpp $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+$(OUT)/%.o: $(CSRC)/%.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(FLAGS) -x hip -c $< -o $@
 
@@ -90,3 +90,18 @@ $(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollo
 	  -o $@
 
 .PHONY: asan-env-loop
+
+# The per-layer MLP dispatch (mlp_layers.cpp) under AddressSanitizer + UBSan with
+# recording fakes for the launches it makes; every fake checks the extent its kernel
+# would reach against the exactly-sized buffer the pointer came from (tests/host/).
+asan-mlp: $(OUT)/mlp_layers_asan_test
+	$(OUT)/mlp_layers_asan_test
+
+$(OUT)/mlp_layers_asan_test: tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layers.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/fused_train.h include/garage_amd.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layers.cpp \
+	  -o $@
+
+.PHONY: asan-mlp

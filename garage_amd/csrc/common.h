@@ -38,6 +38,10 @@ static inline bool ga_aligned16(const void* p) {
 
 static inline int64_t ga_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Everything below is for the device compiler; the host C++ that the CPU harnesses
+// under tests/host build (mlp_layers.cpp) takes the plumbing above.
+#ifdef __HIP__
+
 // ---- torch.optim.Adam (OptimizerWrapper.step, torch/optimizers/optimizer_wrapper.py:53-63)
 // The per-step constants, derived on the host in double and rounded once.
 struct GaAdam {
@@ -169,3 +173,4 @@ __device__ __forceinline__ double ga_block_sum_256(double v, double* smem4) {
   __syncthreads();
   return r;
 }
+#endif  // __HIP__

@@ -1,5 +1,5 @@
 // Entry points of the fused optimizer-step kernels (fused_train.hip) and of the MLP
-// layer ranges they combine with (gemm.hip), used by the epoch loop (update.cpp).
+// layer ranges they combine with (mlp_layers.cpp), used by the epoch loop (update.cpp).
 // Not part of the C ABI: ga_update_epoch* is what callers see.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -74,7 +74,7 @@ typedef struct ga_fused_fwd_net {
 int ga_fused_pair_supported(int width, int K, int in_w);
 int ga_fused_fwd_head_loss(const ga_fused_fwd_net* nets, int n_nets, int64_t M, int width,
                            int K, hipStream_t stream);
-// 2. gemm.hip: the weight-gradient GEMM of the middle layer (dW2 = dZ2^T H1, split-K
+// 2. mlp_layers.cpp: the weight-gradient GEMM of the middle layer (dW2 = dZ2^T H1, split-K
 // slabs + bias column sums) of a 3-layer network: the launch ga_mlp_backward_range_f32
 // makes for layer 1 with fused_first = 1.  n_nets = 2 only: one network's middle layers,
 // of any depth, go through ga_mlp_backward_range_f32

@@ -441,12 +441,7 @@ __global__ __launch_bounds__(512, 4) void gemm_kc_split_kernel(GemmParams p) {
   gemm_f32_body<128, 128, 2, 4, true, true, BK, false, true>(p, (int)blockIdx.x);
 }
 
-// Two problems of the same shape in one grid (the policy's and the value function's
-// weight-gradient GEMM of one optimizer step): workgroup b takes workgroup b / 2 of
-// problem b % 2 (see fwd_head_loss_pair_kernel, fused_train.hip).
-struct GemmPair {
-  GemmParams a, b;
-};
+// Two problems of the same shape in one grid (GemmPair, gemm_params.h)
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KC, bool B_KC>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_f32_pair_kernel(
     GemmPair pp) {
@@ -703,8 +698,6 @@ int launch_gemm(const GemmParams& p_in, int splits, hipStream_t stream) {
   return GA_OK;
 }
 
-inline int round4(int v) { return (v + 3) & ~3; }
-
 // The last hidden layer and the head layer in one launch (tiles that span the
 // layer's whole width: 64, 128 or 256 units).  Returns 1 when the shape is not
 // taken -- every workgroup must be on the staged-epilogue path, which the kernel
@@ -740,258 +733,35 @@ int launch_gemm_with_head(const GemmParams& p_in, hipStream_t stream) {
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// C ABI (see include/garage_amd.h)
+// The launches (gemm_params.h), for the per-layer dispatch in mlp_layers.cpp
 // ---------------------------------------------------------------------------
-// The whole-network forward in one launch (ga_mlp_forward_fused_f32,
-// policy_fused.hip) for nets whose layers fit its LDS tiles;
-// ga_set_fused_forward(0) forces the per-layer GEMMs.
-// Off by default: at the C3 minibatch (32768 x 256 x 256) the fused forward
-// measures 86-107 us against 82-87 us for the three per-layer GEMMs -- it keeps
-// one workgroup per CU (140 KB of LDS) and its per-layer epilogues are exposed,
-// which costs what the saved activation round trip gains.  The rollout step
-// (policy_step_fused_kernel, n_envs rows) is where the fusion pays.
-// Outputs-only forward of a whole two-hidden-layer tanh network in one launch
-// (fused_train.hip: mlp_eval_forward_kernel); ga_set_eval_forward(0) makes callers
-// that ask fall back to the per-layer kernels.
-static int g_eval_forward = -1;
-extern "C" int ga_set_eval_forward(int on) {
-  g_eval_forward = on != 0;
-  return GA_OK;
-}
-extern "C" int ga_mlp_forward_eval_supported(const ga_mlp_desc* d) {
-  if (g_eval_forward < 0) {
-    const char* e = getenv("GARAGE_AMD_EVAL_FORWARD");
-    g_eval_forward = e ? atoi(e) != 0 : 1;
-  }
-  // (64-wide layers: the per-layer kernels' 64 x 64 tiles are 2 % faster at C2)
-  return g_eval_forward && d && d->n_layers == 3 && d->hidden_act == 0 &&
-         d->output_act == 0 && !d->layer_norm && d->dims[1] >= 128 && d->dims[2] >= 128 &&
-         ga_fused_eval_supported(3, d->dims);
-}
-static int g_fused_forward = 0;
-extern "C" int ga_set_fused_forward(int on) {
-  g_fused_forward = on != 0;
-  return 0;
-}
-
-// 0 off, 1 hidden layers up to 128 wide, 2 also 256-wide ones.  At 256 units the
-// fused launch (64 x 256 tiles, 75 KB of LDS) saves 7.7 us per minibatch with the
-// chip to itself (C3, one stream: 167.0 -> 160.6 ms per iteration) but loses 1 %
-// when the policy and value chains share the chip on two streams, where the narrow
-// head GEMM it replaces was hidden under the other chain's kernels anyway
-// (3 x A/B: 147.1 / 148.5 / 149.4 vs 146.6 / 146.7 / 147.5 ms) -- so the default
-// stops at 128 and both schedules keep the same arithmetic.
-static int g_fuse_head_forward = 1;
-extern "C" int ga_set_fused_head_forward(int mode) {
-  g_fuse_head_forward = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
-  return 0;
-}
 extern "C" int ga_set_small_m_gemm(int on) {
   g_small_m = on != 0;
   return 0;
 }
-static int g_fuse_head_dgrad = 1;
-extern "C" int ga_set_fused_head_dgrad(int on) {
-  g_fuse_head_dgrad = on != 0;
-  return 0;
-}
-static int g_skinny = 1;
-extern "C" int ga_set_skinny_kernels(int on) {
-  g_skinny = on != 0;
-  return 0;
+
+int ga_gemm_launch(const GemmParams* p, int a_kc, int b_kc, int splits, hipStream_t stream) {
+  if (a_kc && b_kc) return launch_gemm<true, true>(*p, splits, stream);
+  if (a_kc && !b_kc) return launch_gemm<true, false>(*p, splits, stream);
+  GA_REQUIRE(!a_kc && !b_kc, "ga_gemm_launch: orientation not instantiated");
+  return launch_gemm<false, false>(*p, splits, stream);
 }
 
-static int check_desc(const ga_mlp_desc* d, const char* who) {
-  GA_REQUIRE(d != nullptr, "%s: null descriptor", who);
-  GA_REQUIRE(d->n_layers >= 1 && d->n_layers <= 8, "%s: n_layers %d not in 1..8",
-             who, d->n_layers);
-  for (int l = 0; l <= d->n_layers; ++l)
-    GA_REQUIRE(d->dims[l] >= 1, "%s: dims[%d] < 1", who, l);
-  for (int l = 0; l < d->n_layers; ++l)
-    GA_REQUIRE(d->w_off[l] % 4 == 0 && d->act_off[l] % 4 == 0,
-               "%s: offsets of layer %d not 16-B aligned", who, l);
-  GA_REQUIRE(d->hidden_act >= 0 && d->hidden_act <= 6, "%s: hidden_act %d not in 0..6",
-             who, d->hidden_act);
-  GA_REQUIRE(d->output_act >= 0 && d->output_act <= 6, "%s: output_act %d not in 0..6",
-             who, d->output_act);
-  if (d->layer_norm)
-    for (int l = 0; l + 1 < d->n_layers; ++l)
-      GA_REQUIRE(d->ln_off[l] % 4 == 0 && d->lnx_off[l] % 4 == 0 && d->dims[l] <= 1024,
-                 "%s: layer normalisation of layer %d: unaligned offsets or more than "
-                 "1024 inputs", who, l);
-  return GA_OK;
+int ga_gemm_launch_with_head(const GemmParams* p, hipStream_t stream) {
+  return launch_gemm_with_head(*p, stream);
 }
 
-extern "C" int ga_mlp_forward_f32(const ga_mlp_desc* d, const float* params,
-                                  const float* X, int64_t ldx,
-                                  const int32_t* row_idx, int64_t M, float* acts,
-                                  float* out, int64_t ldo, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_desc(d, "ga_mlp_forward_f32");
-  if (rc) return rc;
-  GA_REQUIRE(params && X, "ga_mlp_forward_f32: null pointer");
-  // out == NULL: hidden layers only (the head is fused into the loss kernel)
-  GA_REQUIRE(out || d->n_layers >= 2, "ga_mlp_forward_f32: nothing to compute");
-  // acts == NULL: outputs only (ga_mlp_forward_eval_supported: the whole network in
-  // one launch, no activation reaches memory)
-  if (!acts && d->n_layers > 1) {
-    GA_REQUIRE(out && ga_mlp_forward_eval_supported(d),
-               "ga_mlp_forward_f32: acts workspace needed");
-    GA_REQUIRE(M >= 0 && M < (1ll << 31), "ga_mlp_forward_f32: bad M");
-    if (M == 0) return GA_OK;
-    return ga_fused_eval_forward(X, ldx, row_idx, M, d->dims, params + d->w_off[0],
-                                 params + d->b_off[0], params + d->w_off[1],
-                                 params + d->b_off[1], params + d->w_off[2],
-                                 params + d->b_off[2], out, ldo, stream);
-  }
-  GA_REQUIRE(M >= 0 && M < (1ll << 31), "ga_mlp_forward_f32: bad M");
-  GA_REQUIRE(ldx % 4 == 0 && ldx >= d->dims[0], "ga_mlp_forward_f32: ldx %lld",
-             (long long)ldx);
-  GA_REQUIRE(!out || ldo >= d->dims[d->n_layers], "ga_mlp_forward_f32: ldo too small");
-  GA_REQUIRE(ga_aligned16(params) && ga_aligned16(X) && (!acts || ga_aligned16(acts)),
-             "ga_mlp_forward_f32: pointers must be 16-B aligned");
-  if (M == 0) return GA_OK;
-  if (out && g_fused_forward && d->hidden_act == 0 && d->output_act == 0 &&
-      !d->layer_norm && ga_policy_step_fused_supported(d))
-    return ga_mlp_forward_fused_f32(d, params, X, ldx, row_idx, M, acts, out, ldo,
-                                    stream);
-  const int L = d->n_layers;
-  for (int l = 0; l < L; ++l) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    if (l == 0) {
-      p.A = X; p.lda = ldx; p.a_idx = row_idx;
-    } else {
-      p.A = acts + d->act_off[l - 1]; p.lda = round4(d->dims[l]);
-    }
-    p.B = params + d->w_off[l];
-    p.ldb = round4(d->dims[l]);
-    const bool last = (l == L - 1);
-    if (last && !out) break;
-    if (d->layer_norm && !last) {
-      // LayerNorm(prev) -> Linear -> nonlinearity
-      // (multi_headed_mlp_module.py:77-92): the GEMM reads the normalised rows
-      const int64_t ldn = round4(d->dims[l]);
-      float* xn = acts + d->lnx_off[l];
-      rc = ga_ln_forward(p.A, p.lda, p.a_idx, M, d->dims[l], params + d->ln_off[l],
-                         params + d->ln_off[l] + ldn, xn, ldn, acts + d->lns_off[l],
-                         stream);
-      if (rc) return rc;
-      p.A = xn; p.lda = ldn; p.a_idx = nullptr;
-    }
-    p.C = last ? out : acts + d->act_off[l];
-    p.c_rs = last ? ldo : round4(d->dims[l + 1]);
-    p.c_cs = 1;
-    p.M = (int)M; p.N = d->dims[l + 1]; p.K = d->dims[l];
-    p.epi = EPI_BIAS_ACT;
-    p.bias = params + d->b_off[l];
-    p.act = last ? d->output_act : act_forward_code(d->hidden_act);
-    p.k_per_split = (int)ga_ceil_div(p.K, BK) * BK;
-    // (the streaming kernels know tanh and the identity)
-    if (g_skinny && p.act <= 1 && p.K <= 32 && p.N > 32) {
-      rc = ga_skinny_forward(p.A, p.lda, p.a_idx, p.B, p.ldb, true, p.bias, p.act,
-                             nullptr, 0, p.C, p.c_rs, p.M, p.N, p.K, stream);
-      if (rc < 0) return rc;
-      if (rc == 0) continue;
-    }
-    if (out && l == L - 2 && d->output_act == 0 && !d->layer_norm &&
-        (g_fuse_head_forward == 2 || (g_fuse_head_forward == 1 && p.N <= 128))) {
-      p.head_W = params + d->w_off[L - 1];
-      p.head_ldw = round4(d->dims[L - 1]);
-      p.head_bias = params + d->b_off[L - 1];
-      p.head_n = d->dims[L];
-      p.head_out = out;
-      p.head_ld = ldo;
-      rc = launch_gemm_with_head(p, stream);
-      if (rc < 0) return rc;
-      if (rc == 0) break;  // both layers done
-      p.head_n = 0;
-    }
-    rc = launch_gemm<true, true>(p, 1, stream);
-    if (rc) return rc;
-  }
-  return GA_OK;
-}
-
-extern "C" int64_t ga_mlp_backward_splits(const ga_mlp_desc* d, int64_t M) {
-  // Rows of the batch each weight-gradient workgroup reduces before writing a
-  // slab: large enough to amortise the slab write, small enough to fill 256 CUs.
-  // 256 rows per slab: the widest layer (256x256 -> 2x2 tiles) then launches
-  // 4 * M/256 workgroups, i.e. 512 at the C3 minibatch of 32768 rows.
-  int64_t s = ga_ceil_div(M, 256);
-  // nets whose layers are all <= 64 wide have one weight-gradient tile per split:
-  // 128-row slabs double the workgroups (their slabs are a few KB each)
-  bool small = true;
-  for (int l = 0; l <= d->n_layers; ++l) small = small && d->dims[l] <= 64;
-  if (small) s = ga_ceil_div(M, 128);
-  // wide layers have many output tiles per split: fewer, longer splits then fill the
-  // chip just as well, and every split less is a slab of the whole parameter vector
-  // not written and not read back (C5, 512-wide layers: 16 tiles per split; 128 splits
-  // of 512 rows moved 744 MB of slabs per optimizer step, 64 splits of 1024 rows --
-  // 1024 workgroups for the widest layer -- move half).  256 x 256 layers (4 tiles)
-  // keep 128 splits.
-  int64_t tiles = 1;
-  for (int l = 0; l < d->n_layers; ++l) {
-    const int64_t t = ga_ceil_div(d->dims[l + 1], 128) * ga_ceil_div(d->dims[l], 128);
-    tiles = t > tiles ? t : tiles;
-  }
-  static int64_t target_env = -1;  // workgroups of the widest layer's weight gradient
-  if (target_env < 0) {
-    const char* e = getenv("GARAGE_AMD_WGRAD_WORKGROUPS");  // developer sweep
-    target_env = e ? atoll(e) : 0;
-    if (target_env < 1) target_env = 0;
-  }
-  // (the split-operand weight-gradient kernel is three times faster per row: half the
-  // workgroups and half the slabs -- 64 splits at C3 -- are the better trade there,
-  // measured 82.3 -> 79.8 ms per iteration; an engine keeps the split count it was
-  // built with)
-  const int64_t target = target_env ? target_env : (ga_split_bf16_enabled() ? 256 : 1024);
-  int64_t by_tiles = ga_ceil_div(target, tiles);
-  // (never below 64 splits on that account: the streaming weight-gradient kernels of the
-  // narrow layers take one workgroup per split and column block)
-  if (!target_env && ga_split_bf16_enabled() && by_tiles < 64) by_tiles = 64;
-  if (!small && s > by_tiles) s = by_tiles;
-  if (s < 1) s = 1;
-  if (s > 128) s = 128;
-  return s;
-}
-
-// dW = dz^T in (+ db = column sums of dz) of the MIDDLE layer of a 3-layer network,
-// out_w x in_w with 33 .. wide sides (the 128 x 128-tile kernel), split-K over the M
-// rows into n_splits slabs: the launch ga_mlp_backward_range_f32 makes for layer 1 with
-// fused_first = 1, for two networks in one grid.  Same tiles, same k ranges, same
-// summation order per element.  (One network: ga_mlp_backward_range_f32, any depth.)
-extern "C" int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M,
-                            int64_t n_splits, int out_w, int in_w, hipStream_t stream) {
-  GA_REQUIRE(nets && n_nets == 2,
-             "ga_wgrad_mid: two networks (one: ga_mlp_backward_range_f32)");
-  GA_REQUIRE(M > 0 && M < (1ll << 31) && n_splits >= 1 && n_splits <= 1024 &&
-                 out_w > 64 && in_w > 64,
-             "ga_wgrad_mid_pair: unsupported shape");
-  const int kps = (int)(ga_ceil_div(ga_ceil_div(M, n_splits), BK) * BK);
+int ga_gemm_launch_pair(const GemmParams* a, const GemmParams* b, hipStream_t stream) {
+  GA_REQUIRE(a->M == b->M && a->N == b->N && a->K == b->K && a->gz == b->gz && a->gz >= 1,
+             "ga_gemm_launch_pair: two products of one shape");
   GemmPair pp;
-  for (int i = 0; i < n_nets; ++i) {
-    const ga_wgrad_mid_net& n = nets[i];
-    GA_REQUIRE(n.dz && n.in && n.slabs_w && n.slabs_b, "ga_wgrad_mid_pair: null pointer");
-    GA_REQUIRE(n.slab_stride % 4 == 0, "ga_wgrad_mid_pair: unsupported shape");
-    GA_REQUIRE(ga_aligned16(n.dz) && ga_aligned16(n.in) && ga_aligned16(n.slabs_w),
-               "ga_wgrad_mid_pair: pointers must be 16-B aligned");
-    GemmParams& p = i ? pp.b : pp.a;
-    memset(&p, 0, sizeof(p));
-    p.K = (int)M;
-    p.k_per_split = kps;
-    p.epi = EPI_PLAIN;
-    p.c_split_stride = n.slab_stride;
-    p.colsum = n.slabs_b;
-    p.colsum_split_stride = n.slab_stride;
-    p.A = n.dz; p.lda = round4(out_w); p.B = n.in; p.ldb = round4(in_w);
-    p.M = out_w; p.N = in_w;
-    p.C = n.slabs_w; p.c_rs = round4(in_w); p.c_cs = 1;
-    p.colsum_of_b = 0;
-    p.gx = (int)ga_ceil_div(p.M, 128); p.gy = (int)ga_ceil_div(p.N, 128);
-    p.gz = (int)n_splits;
+  pp.a = *a;
+  pp.b = *b;
+  // (gz: the caller's split count)
+  for (GemmParams* p : {&pp.a, &pp.b}) {
+    p->gx = (int)ga_ceil_div(p->M, 128); p->gy = (int)ga_ceil_div(p->N, 128);
   }
-  const double flops = 2.0 * 2.0 * (double)out_w * (double)in_w * (double)M;
+  const double flops = 2.0 * 2.0 * (double)pp.a.M * (double)pp.a.N * (double)pp.a.K;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ga_prof_events(GA_PROF_GEMM_TN_128, flops, &e0, &e1);
   ga_prof_count(GA_PROF_GEMM_TN_128);
@@ -999,247 +769,6 @@ extern "C" int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M,
   hipExtLaunchKernelGGL((gemm_f32_pair_kernel<128, 128, 2, 4, false, false>), grid,
                         dim3(512), 0, stream, e0, e1, 0, pp);
   GA_CHECK_LAUNCH("gemm_f32_pair");
-  return GA_OK;
-}
-
-extern "C" int ga_mlp_backward_f32(const ga_mlp_desc* d, const float* params,
-                                   const float* X, int64_t ldx,
-                                   const int32_t* row_idx, int64_t M,
-                                   const float* acts, const float* dout,
-                                   int64_t ldo, float* dacts, float* grad_slabs,
-                                   int64_t slab_stride, int64_t n_splits,
-                                   ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(d != nullptr, "ga_mlp_backward_f32: null descriptor");
-  return ga_mlp_backward_range_f32(d, params, X, ldx, row_idx, M, acts, dout, ldo, dacts,
-                                   grad_slabs, slab_stride, n_splits, d->n_layers - 1, 0,
-                                   stream);
-}
-
-// Layers l_start .. 0 (fused_train.h).  l_start = n_layers - 1 with `dout` is the
-// whole backward pass; the fused optimizer step enters below the head with the
-// data gradient of the last hidden layer already in `dacts`.
-extern "C" int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params,
-                                         const float* X, int64_t ldx,
-                                         const int32_t* row_idx, int64_t M,
-                                         const float* acts, const float* dout,
-                                         int64_t ldo, float* dacts, float* grad_slabs,
-                                         int64_t slab_stride, int64_t n_splits,
-                                         int l_start, int fused_first,
-                                         hipStream_t stream) {
-  int rc = check_desc(d, "ga_mlp_backward_f32");
-  if (rc) return rc;
-  GA_REQUIRE(params && X && grad_slabs, "ga_mlp_backward_f32: null pointer");
-  GA_REQUIRE(l_start >= 0 && l_start < d->n_layers &&
-                 (l_start < d->n_layers - 1 || dout) && (!fused_first || l_start >= 1),
-             "ga_mlp_backward_f32: bad layer range");
-  GA_REQUIRE(d->n_layers == 1 || (acts && dacts),
-             "ga_mlp_backward_f32: workspaces needed");
-  GA_REQUIRE(M > 0 && M < (1ll << 31), "ga_mlp_backward_f32: bad M");
-  GA_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && slab_stride % 4 == 0,
-             "ga_mlp_backward_f32: strides must be multiples of 4");
-  GA_REQUIRE(n_splits >= 1 && n_splits <= 1024, "ga_mlp_backward_f32: n_splits");
-  GA_REQUIRE(ga_aligned16(params) && ga_aligned16(X) && (!dout || ga_aligned16(dout)) &&
-                 ga_aligned16(grad_slabs) && (!acts || ga_aligned16(acts)) &&
-                 (!dacts || ga_aligned16(dacts)),
-             "ga_mlp_backward_f32: pointers must be 16-B aligned");
-  const int L = d->n_layers;
-  int kps = (int)(ga_ceil_div(ga_ceil_div(M, n_splits), BK) * BK);
-  for (int l = l_start; l >= (fused_first ? 1 : 0); --l) {
-    bool dgrad_done = fused_first && l == 1;
-    const float* dz = (l == L - 1) ? dout : dacts + d->act_off[l];
-    const int64_t lddz = (l == L - 1) ? ldo : round4(d->dims[l + 1]);
-    const int out_w = d->dims[l + 1], in_w = d->dims[l];
-    // ---- weight + bias gradient slabs: dW[o][i] = sum_b dz[b][o] * in[b][i]
-    {
-      GemmParams p;
-      memset(&p, 0, sizeof(p));
-      const bool ln = d->layer_norm && l < L - 1;  // this layer reads normalised rows
-      const float* in = ln ? acts + d->lnx_off[l]
-                           : ((l == 0) ? X : acts + d->act_off[l - 1]);
-      const int64_t ldin = (ln || l > 0) ? round4(in_w) : ldx;
-      const int32_t* in_idx = (l == 0 && !ln) ? row_idx : nullptr;
-      p.K = (int)M;
-      p.k_per_split = kps;
-      p.epi = EPI_PLAIN;
-      p.c_split_stride = slab_stride;
-      p.colsum = grad_slabs + d->b_off[l];
-      p.colsum_split_stride = slab_stride;
-      if (in_w <= 32 && out_w > 32) {
-        // (out x in), narrow in: natural orientation, 256x32 tiles
-        p.A = dz; p.lda = lddz; p.B = in; p.ldb = ldin; p.b_idx = in_idx;
-        p.M = out_w; p.N = in_w;
-        p.C = grad_slabs + d->w_off[l]; p.c_rs = round4(in_w); p.c_cs = 1;
-        p.colsum_of_b = 0;
-      } else if (out_w <= 32) {
-        // narrow out: compute dW^T = in^T dz so the narrow side is N
-        p.A = in; p.lda = ldin; p.a_idx = in_idx; p.B = dz; p.ldb = lddz;
-        p.M = in_w; p.N = out_w;
-        p.C = grad_slabs + d->w_off[l]; p.c_rs = 1; p.c_cs = round4(in_w);
-        p.colsum_of_b = 1;
-      } else {
-        p.A = dz; p.lda = lddz; p.B = in; p.ldb = ldin; p.b_idx = in_idx;
-        p.M = out_w; p.N = in_w;
-        p.C = grad_slabs + d->w_off[l]; p.c_rs = round4(in_w); p.c_cs = 1;
-        p.colsum_of_b = 0;
-      }
-      rc = 1;
-      if (g_skinny && in_w <= 32 && out_w > 32) {
-        // wide = dz (bias gradient = its column sums), narrow = layer input
-        rc = ga_skinny_wgrad(dz, lddz, nullptr, in, ldin, in_idx, (int)M, out_w, in_w, kps,
-                             (int)n_splits, grad_slabs + d->w_off[l], round4(in_w), 1,
-                             slab_stride, grad_slabs + d->b_off[l], nullptr, nullptr, 0,
-                             nullptr, 0, stream);
-      } else if (g_skinny && out_w <= 32 && in_w > 32) {
-        // head layer: the same pass over the hidden activations also yields the
-        // data gradient of the layer below (it needs dz and tanh' of `in` only)
-        const bool with_dz = g_fuse_head_dgrad && l > 0 && in_idx == nullptr &&
-                             d->hidden_act == 0 && !d->layer_norm;
-        rc = ga_skinny_wgrad(in, ldin, in_idx, dz, lddz, nullptr, (int)M, in_w, out_w, kps,
-                             (int)n_splits, grad_slabs + d->w_off[l], 1, round4(in_w),
-                             slab_stride, nullptr, grad_slabs + d->b_off[l],
-                             with_dz ? params + d->w_off[l] : nullptr, round4(in_w),
-                             with_dz ? dacts + d->act_off[l - 1] : nullptr, round4(in_w),
-                             stream);
-        if (rc == 1 && with_dz)  // shape not taken with the data gradient: without
-          rc = ga_skinny_wgrad(in, ldin, in_idx, dz, lddz, nullptr, (int)M, in_w, out_w,
-                               kps, (int)n_splits, grad_slabs + d->w_off[l], 1,
-                               round4(in_w), slab_stride, nullptr,
-                               grad_slabs + d->b_off[l], nullptr, 0, nullptr, 0, stream);
-        else if (rc == 0 && with_dz)
-          dgrad_done = true;
-      }
-      if (rc < 0) return rc;
-      if (rc == 1) {
-        rc = launch_gemm<false, false>(p, (int)n_splits, stream);
-        if (rc) return rc;
-      }
-    }
-    // ---- data gradient for the layer below
-    // A normalised layer input (hidden layers with layer_norm) takes the plain
-    // product dz W -- also for the first layer, whose gamma / beta need it -- and
-    // the LayerNorm's backward pass then turns it, in place, into the data
-    // gradient of the layer below.
-    const bool ln_in = d->layer_norm && l < L - 1;
-    if ((l > 0 || ln_in) && !dgrad_done) {
-      GemmParams p;
-      memset(&p, 0, sizeof(p));
-      float* dst = l > 0 ? dacts + d->act_off[l - 1] : dacts + d->lnx_off[0];
-      p.A = dz; p.lda = lddz;
-      p.B = params + d->w_off[l]; p.ldb = round4(in_w);
-      p.C = dst; p.c_rs = round4(in_w); p.c_cs = 1;
-      p.M = (int)M; p.N = in_w; p.K = out_w;
-      if (ln_in) {
-        p.epi = EPI_PLAIN;
-      } else {
-        p.epi = EPI_MUL_DTANH;
-        p.H = acts + d->act_off[l - 1]; p.ldh = round4(in_w);
-        p.hact = d->hidden_act;
-      }
-      p.k_per_split = (int)ga_ceil_div(p.K, BK) * BK;
-      rc = 1;
-      if (g_skinny && !ln_in && d->hidden_act == 0 && p.K <= 32 && p.N > 32)
-        rc = ga_skinny_forward(p.A, p.lda, nullptr, p.B, p.ldb, false, nullptr, 0, p.H,
-                               p.ldh, p.C, p.c_rs, p.M, p.N, p.K, stream);
-      if (rc < 0) return rc;
-      if (rc == 1) {
-        rc = launch_gemm<true, false>(p, 1, stream);
-        if (rc) return rc;
-      }
-      if (ln_in) {
-        const int64_t ldn = round4(in_w);
-        rc = ga_ln_backward(dst, ldn, l == 0 ? X : acts + d->act_off[l - 1],
-                            l == 0 ? ldx : ldn, l == 0 ? row_idx : nullptr,
-                            acts + d->lns_off[l], M, in_w, params + d->ln_off[l],
-                            l > 0 ? 1 : 0, d->hidden_act, kps, (int)n_splits,
-                            grad_slabs + d->ln_off[l], grad_slabs + d->ln_off[l] + ldn,
-                            slab_stride, stream);
-        if (rc) return rc;
-      }
-    }
-  }
-  return GA_OK;
-}
-
-// Tangent (forward-mode) pass: with dtheta = `tangent` (flat parameter layout) and
-// the activations of a forward at the same rows in `acts`,
-//   tz_l = in_l dW_l^T + db_l + tin_l W_l^T,   th_l = tz_l * (1 - h_l^2)
-// (in_0 = X, tin_0 = 0); `tout` receives d(output).  This is the J v half of the
-// Fisher-vector product the TRPO policy step solves with
-// (torch/optimizers/conjugate_gradient_optimizer.py:18-66 takes the same product
-// by double backward through the KL constraint).
-extern "C" int ga_mlp_jvp_f32(const ga_mlp_desc* d, const float* params,
-                              const float* tangent, const float* X, int64_t ldx,
-                              const int32_t* row_idx, int64_t M, const float* acts,
-                              float* tacts, float* tout, int64_t ldo,
-                              ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_desc(d, "ga_mlp_jvp_f32");
-  if (rc) return rc;
-  GA_REQUIRE(params && tangent && X && tout, "ga_mlp_jvp_f32: null pointer");
-  GA_REQUIRE(d->n_layers == 1 || (acts && tacts), "ga_mlp_jvp_f32: workspaces needed");
-  GA_REQUIRE(M > 0 && M < (1ll << 31), "ga_mlp_jvp_f32: bad M");
-  GA_REQUIRE(ldx % 4 == 0 && ldx >= d->dims[0] && ldo >= d->dims[d->n_layers],
-             "ga_mlp_jvp_f32: leading dimensions");
-  GA_REQUIRE(ga_aligned16(params) && ga_aligned16(tangent) && ga_aligned16(X) &&
-                 (!acts || ga_aligned16(acts)) && (!tacts || ga_aligned16(tacts)),
-             "ga_mlp_jvp_f32: pointers must be 16-B aligned");
-  const int L = d->n_layers;
-  for (int l = 0; l < L; ++l) {
-    const bool last = (l == L - 1);
-    const int in_w = d->dims[l], out_w = d->dims[l + 1];
-    float* C = last ? tout : tacts + d->act_off[l];
-    const int64_t ldc = last ? ldo : round4(out_w);
-    const float* H = last ? nullptr : acts + d->act_off[l];
-    // a normalised layer input: its tangent (through the LayerNorm, from the
-    // tangent of the layer below and of gamma / beta) is a second product even
-    // for the first layer
-    const bool ln = d->layer_norm && !last;
-    const int64_t ldn = round4(in_w);
-    if (ln) {
-      rc = ga_ln_jvp(l > 0 ? tacts + d->act_off[l - 1] : nullptr, ldn,
-                     l > 0 ? acts + d->act_off[l - 1] : X, l > 0 ? ldn : ldx,
-                     l > 0 ? nullptr : row_idx, acts + d->lns_off[l], M, in_w,
-                     params + d->ln_off[l], tangent + d->ln_off[l],
-                     tangent + d->ln_off[l] + ldn, tacts + d->lnx_off[l], ldn, stream);
-      if (rc) return rc;
-    }
-    const bool two = l > 0 || ln;
-    // in_l dW_l^T + db_l  (and the tanh' factor when it is the only product)
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    if (ln) {
-      p.A = acts + d->lnx_off[l]; p.lda = ldn;
-    } else if (l == 0) {
-      p.A = X; p.lda = ldx; p.a_idx = row_idx;
-    } else {
-      p.A = acts + d->act_off[l - 1]; p.lda = round4(in_w);
-    }
-    p.B = tangent + d->w_off[l]; p.ldb = round4(in_w);
-    p.C = C; p.c_rs = ldc; p.c_cs = 1;
-    p.M = (int)M; p.N = out_w; p.K = in_w;
-    p.epi = EPI_BIAS_ACT; p.bias = tangent + d->b_off[l]; p.act = 0;
-    if (!two) { p.H = H; p.ldh = ldc; p.hact = d->hidden_act; }
-    p.k_per_split = (int)ga_ceil_div(p.K, BK) * BK;
-    rc = launch_gemm<true, true>(p, 1, stream);
-    if (rc) return rc;
-    if (two) {
-      // += tin_l W_l^T, then the tanh' factor
-      GemmParams q;
-      memset(&q, 0, sizeof(q));
-      q.A = ln ? tacts + d->lnx_off[l] : tacts + d->act_off[l - 1];
-      q.lda = round4(in_w);
-      q.B = params + d->w_off[l]; q.ldb = round4(in_w);
-      q.C = C; q.c_rs = ldc; q.c_cs = 1;
-      q.M = (int)M; q.N = out_w; q.K = in_w;
-      q.accum = 1;
-      if (H) { q.epi = EPI_MUL_DTANH; q.H = H; q.ldh = ldc; q.hact = d->hidden_act; }
-      else q.epi = EPI_PLAIN;
-      q.k_per_split = (int)ga_ceil_div(q.K, BK) * BK;
-      rc = launch_gemm<true, true>(q, 1, stream);
-      if (rc) return rc;
-    }
-  }
   return GA_OK;
 }
 
@@ -1268,20 +797,4 @@ extern "C" int ga_act_slope_mul_f32(float* dout, int64_t ldd, const float* out,
                      dim3(256), 0, stream, dout, ldd, out, ldo, M, N, act);
   GA_CHECK_LAUNCH("act_slope_mul");
   return GA_OK;
-}
-
-// Plain GEMM entry used by tests: C[M,N] = A[M,K] * B[N,K]^T (both k-contiguous).
-extern "C" int ga_gemm_nt_f32(const float* A, int64_t lda, const float* B,
-                              int64_t ldb, float* C, int64_t ldc, int64_t M,
-                              int64_t N, int64_t K, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(A && B && C, "ga_gemm_nt_f32: null pointer");
-  GA_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && ga_aligned16(A) && ga_aligned16(B),
-             "ga_gemm_nt_f32: operands must be 16-B aligned with ld %% 4 == 0");
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.c_rs = ldc; p.c_cs = 1;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.epi = EPI_PLAIN;
-  p.k_per_split = (int)ga_ceil_div(K, BK) * BK;
-  return launch_gemm<true, true>(p, 1, stream);
 }

@@ -4,19 +4,17 @@
 // layout notes.
 #pragma once
 #include "common.h"
+#include "gemm_params.h"  // GemmParams, BK, the EPI_* codes, act_forward_code
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 32;
 constexpr int PAD = 4;
 // One LDS stage per operand tile (37 KB per 128x128 workgroup): a second stage
 // (one barrier per k-step instead of two) measured no faster at the K = 256 shapes
 // of this workload, and the small footprint lets the workgroups of the policy and
 // the value-function update chains co-reside on a CU when they run on two streams.
-
-enum Epilogue { EPI_BIAS_ACT = 0, EPI_MUL_DTANH = 1, EPI_PLAIN = 2 };
 
 // tanh on the hardware exp / rcp units (common.h: the one definition every kernel
 // shares; 64 of these per lane per output tile).
@@ -61,9 +59,6 @@ __device__ __forceinline__ float act_slope(float h, int hact) {
   if (__builtin_expect(hact <= 2, 1))
     return hact == 0 ? 1.f - h * h : (hact == 1 ? (h > 0.f ? 1.f : 0.f) : 1.f);
   return act_slope_more(h, hact);
-}
-__host__ __device__ inline int act_forward_code(int hidden_act) {
-  return hidden_act == 0 ? 1 : (hidden_act == 1 ? 2 : (hidden_act == 2 ? 0 : hidden_act));
 }
 // slope of an OUTPUT activation given in forward code
 __device__ __forceinline__ float act_slope_fwd(float o, int act) {
@@ -118,47 +113,6 @@ __device__ __forceinline__ void ft_mfma6(const ft_bf16x8 (&a)[3], const ft_bf16x
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
-
-
-struct GemmParams {
-  const float* A;
-  int64_t lda;           // floats between consecutive memory lines of A
-  const int32_t* a_idx;  // optional gather applied to A's memory-line index
-  const float* B;
-  int64_t ldb;
-  const int32_t* b_idx;
-  float* C;
-  int64_t c_rs, c_cs;    // C(m,n) at C[m * c_rs + n * c_cs]
-  int M, N, K;
-  int epi;
-  const float* bias;     // EPI_BIAS_ACT: per-n bias (may be null)
-  int act;               // 0 identity, 1 tanh
-  const float* H;        // EPI_MUL_DTANH (or EPI_BIAS_ACT with H set): activation
-  int64_t ldh;           // outputs H[m * ldh + n]; the result is scaled by the
-  int hact;              // activation's slope there (network code, 0 = tanh)
-  int accum;             // 1: add the product to what C already holds
-  int k_per_split;       // multiple of BK
-  int64_t c_split_stride;
-  float* colsum;         // optional: sum_k of operand A (or B) -> colsum[line]
-  int colsum_of_b;       // 0: columns of A tile (index m), 1: of B tile (index n)
-  int64_t colsum_split_stride;
-  int gx, gy, gz;        // logical grid (m blocks, n blocks, splits); 1-D launch
-  // HEAD kernels (the tile spans all N columns): the next, narrow layer is applied to
-  // the staged output rows in the epilogue: head_out[m, j] = head_bias[j] +
-  // sum_n C(m, n) * head_W[j * head_ldw + n],  j < head_n <= 8
-  const float* head_W;
-  int64_t head_ldw;
-  const float* head_bias;
-  int head_n;
-  float* head_out;
-  int64_t head_ld;
-  // split-operand instantiation (opt-in): the B operand as three bf16 planes in
-  // fragment order (fused_train.h: ga_weight_planes), plane pl at + pl * stride,
-  // bplane_nblk = round32(N) / 32 column blocks per 16-deep k group
-  const uint16_t* bplanes;
-  int64_t bplane_stride;
-  int bplane_nblk;
-};
 
 // One [BR x BK] operand tile: global -> registers -> LDS.
 //   KC = true : memory line = r (tile row), contiguous along k

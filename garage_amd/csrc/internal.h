@@ -1,8 +1,8 @@
 // Entry points that one source file of the library defines and another calls, and
 // the public header every source file compiles against.  Not part of the C ABI:
 // the library is built with -fvisibility=hidden and exports include/garage_amd.h
-// only.  Host C++ (no device code), so that the CPU harness under tests/host can
-// build update.cpp and rollout_loop.cpp against it too.
+// only.  Host C++ (no device code), so that the CPU harnesses under tests/host can
+// build update.cpp, rollout_loop.cpp and mlp_layers.cpp against it too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,7 +80,7 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
 }
 
 extern "C" {
-// gemm.hip: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
+// mlp_layers.cpp: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
 // of layer l_start in dacts (l_start = n_layers - 1 with `dout`: the whole pass, what
 // ga_mlp_backward_f32 does); fused_first: the data gradient into layer 0's output and
 // layer 0's weight gradient are computed elsewhere (ga_fused_dgrad_wgrad0)

@@ -391,7 +391,7 @@ void launch_fwd(const SkinnyFwdParams& p, bool w_kc, int epi, dim3 grid,
 
 }  // namespace
 
-// Internal entry points (called from gemm.hip's layer dispatch; not in the C ABI).
+// Internal entry points (called from the layer dispatch, mlp_layers.cpp; not in the C ABI).
 // Return 1 when the shape is not one these kernels take (caller falls back to the
 // MFMA tile kernel), 0 on launch, negative on error.
 

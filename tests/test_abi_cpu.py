@@ -113,6 +113,20 @@ def test_host_loops_under_address_sanitizer():
     assert 'host loops ok' in out.stdout
 
 
+def test_mlp_layer_dispatch_under_address_sanitizer():
+    """``make asan-mlp``: the per-layer MLP dispatch (mlp_layers.cpp) compiled with
+    ``-fsanitize=address,undefined`` for the CPU and run against recording fakes of
+    every launch it makes (tests/host/mlp_layers_harness.cpp).  Each fake checks the
+    extent its kernel would reach against the exactly-sized buffer the pointer came
+    from: ragged widths, LayerNorm offsets, slabs x splits, the head layer's
+    transposed weight gradient; which launcher a layer takes under every switch; and
+    that the pair launch's weight-gradient descriptors are the single launch's."""
+    out = subprocess.run(['make', '-C', ROOT, 'asan-mlp'], capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert 'mlp layers ok' in out.stdout
+
+
 def test_driver_build_entry_point():
     """``__graft_entry__.build()`` -- what the driver runs on a CPU-only machine --
     compiles (a no-op when the library is current), imports the package and agrees
