@@ -80,7 +80,8 @@ GA_API int ga_set_gae_rows_steps_per_lane(int steps);
  * (torch/modules/multi_headed_mlp_module.py:136-151) and its autograd backward
  * as used by VPG._train_policy / _train_value_function (vpg.py:250-293).
  * Hidden activations: tanh (the GaussianMLP* defaults,
- * torch/policies/gaussian_mlp_policy.py:44-60), relu or none. */
+ * torch/policies/gaussian_mlp_policy.py:44-60), relu, none, sigmoid, elu, leaky_relu
+ * or softplus (hidden_act below); the output layer takes the same set (output_act). */
 typedef struct {
   int32_t n_layers;   /* linear layers incl. the output layer, 1..8 */
   int32_t dims[9];    /* dims[0] = input width, dims[l+1] = width of layer l */
@@ -114,7 +115,9 @@ typedef struct {
   int64_t lns_off[8]; /* ... and its per-row (mean, rstd) pairs */
 } ga_mlp_desc;
 
-/* dout[i, j] *= slope of the activation `act` (1 tanh, 2 relu) at its OUTPUT
+/* dout[i, j] *= slope of the activation `act` (the codes of ga_mlp_desc.output_act:
+ * 0 none -- nothing is launched --, 1 tanh, 2 relu, 3 sigmoid, 4 elu, 5 leaky_relu,
+ * 6 softplus) at its OUTPUT
  * out[i, j], j < N: turns the loss's gradient with respect to an output layer
  * with an output_nonlinearity into the gradient with respect to its pre-activation
  * (what ga_mlp_backward_f32 takes). */
