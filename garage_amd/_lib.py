@@ -236,6 +236,7 @@ SIGNATURES = {
                                       ptr, c_i64, ptr]),
     'ga_policy_head_sample': (c_int, [C.POINTER(HeadArgs), ptr]),
     'ga_policy_step_fused_supported': (c_int, [C.POINTER(MlpDesc)]),
+    'ga_policy_step_wide_supported': (c_int, [C.POINTER(MlpDesc)]),
     'ga_policy_step_fused_f32': (c_int, [C.POINTER(MlpDesc), ptr,
                                          C.POINTER(HeadArgs), ptr]),
     'ga_record_step': (c_int, [C.POINTER(RecordArgs), ptr]),

@@ -79,6 +79,19 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
   return -1;
 }
 
+// The networks policy_fused.hip's wide rollout step takes (layer inputs up to 512, a
+// head up to 32, up to 8 layers, activation codes 0 .. 6): a superset of what
+// ga_policy_step_fused_supported accepts.  ga_policy_step_wide_supported and
+// ga_rollout_env_steps both ask here.
+static inline int ga_step_wide_rule(const ga_mlp_desc* d) {
+  if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
+  if (d->hidden_act < 0 || d->hidden_act > 6 || d->output_act < 0 || d->output_act > 6)
+    return 0;
+  for (int l = 0; l < d->n_layers; ++l)
+    if (d->dims[l] > 512) return 0;
+  return d->dims[d->n_layers] <= 32;
+}
+
 extern "C" {
 // mlp_layers.cpp: the backward pass of layers l_start .. 0 given d(loss)/d(pre-activation)
 // of layer l_start in dacts (l_start = n_layers - 1 with `dout`: the whole pass, what

@@ -15,7 +15,8 @@
 // 16-column tiles w, w + 4, ...; means agree with the per-layer path to rounding),
 // the narrow output layer is a 16-lane VALU dot product, and the head (Gaussian:
 // mean + std * noise; categorical: inverse CDF) writes the action and the rollout
-// buffers.  Hidden widths up to 256 (C2, C3); wider nets use the per-layer path.
+// buffers.  Layer inputs up to 256 (C2, C3) run in policy_step_fused_kernel; up to 512
+// (C5) in policy_step_wide_kernel, below it; wider nets use the per-layer path.
 // Every network option of ga_mlp_desc runs here: the tanh / linear-output network in
 // the kernels it always had (GEN = false), any other hidden_act / output_act (0 .. 6)
 // and layer_norm in a second set of instantiations (GEN = true) whose epilogues
@@ -46,6 +47,13 @@
 // gives gamma and beta each -- and never for a row index: all 16 rows of the tile
 // exist in LDS (rows of envs >= n hold zeros and normalise to beta; they are never
 // stored).  Nothing is fetched from an index derived from a wave number alone.
+// policy_step_wide_kernel: the same loads with the same guards.  WeightStage::load is
+// given the panel's base W + n0 * ldw and rows = min(N - n0, 256) >= 1, so nrow is
+// clamped against the rows left in the panel (and k against the row's last vector);
+// biases ncol < rows at bias[n0 + ncol]; epilogue stores n0 + ncol < n_pad <= 512 < the
+// row stride; the output layer's block e < N * ld / 4 <= 32 * 128 vectors, inside the two
+// contiguous stages (4608 vectors); row vectors (output layer, ln_rows_w<512>) at
+// k < K <= 512 or vector 0; gamma / beta where the vector's first column k < dims[l].
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -56,6 +64,8 @@ constexpr int LDACT = HMAX + 4;   // activation tile row stride (floats)
 constexpr int KC = 32;            // k chunk
 constexpr int LDW = KC + 4;       // weight stage row stride
 constexpr int MAX_OUT = 32;       // widest output head
+constexpr int WMAX = 512;         // widest layer input of policy_step_wide_kernel
+constexpr int LDACT_W = WMAX + 4; // its activation tile row stride
 
 // (tanh_fast: gemm_core.h)
 
@@ -178,17 +188,20 @@ __device__ __forceinline__ float sum16(float v) {
 // (RES) or in the parameter buffer; a vector is read only where its first column
 // k < D, and it ends inside the round4(D) floats the layout gives either row.
 constexpr float LN_EPS = 1e-5f;
-__device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
-                                        const float* __restrict__ gamma,
-                                        const float* __restrict__ beta) {
+// (WIDTH: the widest row the tile holds, its row stride WIDTH + 4 -- HMAX in the
+// kernels for widths up to 256, WMAX in the wide one: 4 or 8 vectors per lane)
+template <int WIDTH>
+__device__ __forceinline__ void ln_rows_w(float* __restrict__ tile, int D,
+                                          const float* __restrict__ gamma,
+                                          const float* __restrict__ beta) {
   const int r = threadIdx.x >> 4, part = threadIdx.x & 15;
-  float* a = tile + r * LDACT;
+  float* a = tile + r * (WIDTH + 4);
   // (branch free, as the output layer reads its rows: out-of-range vectors read
   // vector 0 and are selected away; the row stays in registers for the three passes)
-  float4 x[HMAX / 64];
+  float4 x[WIDTH / 64];
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < HMAX / 64; ++i) {
+  for (int i = 0; i < WIDTH / 64; ++i) {
     const int k = part * 4 + 64 * i;
     float4 v = *reinterpret_cast<const float4*>(a + (k < D ? k : 0));
     v.x = k < D ? v.x : 0.f;
@@ -201,7 +214,7 @@ __device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
   const float mean = sum16(s) / (float)D;
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < HMAX / 64; ++i) {
+  for (int i = 0; i < WIDTH / 64; ++i) {
     const int k = part * 4 + 64 * i;
     const float d0 = k < D ? x[i].x - mean : 0.f;
     const float d1 = k + 1 < D ? x[i].y - mean : 0.f;
@@ -211,7 +224,7 @@ __device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
   }
   const float rstd = 1.f / sqrtf(sum16(q) / (float)D + LN_EPS);
 #pragma unroll
-  for (int i = 0; i < HMAX / 64; ++i) {
+  for (int i = 0; i < WIDTH / 64; ++i) {
     const int k = part * 4 + 64 * i;
     if (k < D) {
       const float4 g = *reinterpret_cast<const float4*>(gamma + k);
@@ -224,6 +237,11 @@ __device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
       *reinterpret_cast<float4*>(a + k) = y;
     }
   }
+}
+__device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
+                                        const float* __restrict__ gamma,
+                                        const float* __restrict__ beta) {
+  ln_rows_w<HMAX>(tile, D, gamma, beta);
 }
 // (RES && GEN kernels only: a function-scope array, so that the LDS layout of every
 // other instantiation is what it was)
@@ -652,6 +670,221 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   }  // steps
 }
 
+// ---- the same step for layer inputs up to WMAX = 512 (C5: MLP(512, 512, 512)) -----
+// The contract of policy_step_fused_kernel<false, Env, GEN>: one workgroup of 256
+// threads owns 16 envs through every layer, the head, the rollout-buffer writes and
+// (env_step) the env's step for n_steps consecutive steps.  A 512 x 512 fp32 layer is
+// 1 MB, so there is no resident variant: the weights stream from L2 every step.  LDS:
+// two [16][512 + 4] activation tiles (66 048 B) + the [256][32 + 4] x 2 weight stage
+// (73 728 B) + head[16][32] (2048 B) = 141 824 B, one workgroup per CU.  A layer's
+// output columns come in panels of HMAX = 256, so the stage keeps its size: per panel
+// the k loop of the streamed kernel (32-wide chunks, ascending, one order per
+// accumulator; wave w owns the panel's tiles w, w + 4, ...) and an epilogue that
+// writes bias + activation into the other tile at the panel's column offset.  The
+// output layer's [N][ldw] block (up to 32 x 512 floats = 64 KB) spans both stages,
+// which are contiguous; every wave is past a barrier behind its last stage read by then.
+// The head is rollout_dev.h's head_one at this sub-step's column and Philox step; the
+// env steps from the action row head_one wrote (same thread).
+template <class Env, bool GEN>
+__global__ __launch_bounds__(256) void policy_step_wide_kernel(FusedParams<Env> p) {
+  constexpr bool RES = false;  // (PS_STAMP: the streamed kernel's slots)
+  constexpr int STAGE = HMAX * LDW;
+  __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDACT_W];
+  __shared__ __attribute__((aligned(16))) float wst[2 * STAGE];
+  __shared__ float head[ROWS][MAX_OUT];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const int64_t row0 = (int64_t)blockIdx.x * ROWS;
+  const int L = p.net.n_layers;
+  for (int sidx = 0; sidx < p.n_steps; ++sidx) {
+    // this step's column, Philox counter and observation buffers (they swap roles
+    // every step)
+    ga_rollout::HeadDev hd = p.hd;
+    hd.col = p.hd.col + sidx;
+    hd.step = p.hd.step + (uint32_t)sidx;
+    const bool odd = sidx & 1;
+    const float* obs = odd ? p.es.seen_next : p.hd.obs;
+    ga_rollout::EnvStepArgsT<Env> es = p.es;
+    if (p.env_step) {
+      es.p.col = hd.col;
+      es.seen_next = odd ? const_cast<float*>(p.hd.obs) : p.es.seen_next;
+      es.p.next_obs = es.seen_next;
+      if (p.es.raw_next != p.es.seen_next) {  // NormalizedEnv: the env's own rows
+        es.raw_obs = odd ? p.es.raw_next : p.es.raw_obs;
+        es.raw_next = odd ? const_cast<float*>(p.es.raw_obs) : p.es.raw_next;
+      } else {
+        es.raw_obs = obs;
+        es.raw_next = es.seen_next;
+      }
+    }
+
+    // ---- observations -> act[0] (zero padded to a multiple of the k chunk) and
+    //      into the rollout buffer
+    PS_STAMP(0);
+    const int in_w = p.net.dims[0];
+    const int in_pad = (in_w + KC - 1) / KC * KC;
+    for (int e = tid; e < ROWS * in_pad; e += 256) {
+      const int r = e / in_pad, c = e % in_pad;
+      const int64_t env = row0 + r;
+      float v = 0.f;
+      if (env < hd.n && c < in_w) {
+        v = obs[env * hd.ldo + c];
+        hd.obs_buf[(env * hd.Tcap + hd.col) * hd.ldo + c] = v;
+      }
+      act[0][r * LDACT_W + c] = v;
+    }
+    decltype(ga_rollout::env_prefetch(es, 0)) pre;
+    if (p.env_step && tid < ROWS && row0 + tid < hd.n)
+      pre = ga_rollout::env_prefetch(es, row0 + tid);
+    __syncthreads();
+    PS_STAMP(1);
+
+    // ---- hidden layers on the matrix cores, one panel of 256 output columns at a time
+    int cur = 0;
+    for (int l = 0; l < L - 1; ++l) {
+      const int K = p.net.dims[l], N = p.net.dims[l + 1];
+      const int ldw = (K + 3) & ~3;
+      const float* W = p.params + p.net.w_off[l];
+      const float* bias = p.params + p.net.b_off[l];
+      const int nk = (K + KC - 1) / KC;
+      const int n_pad = (N + KC - 1) / KC * KC;
+      if constexpr (GEN) {
+        if (p.layer_norm) {
+          ln_rows_w<WMAX>(act[cur], K, p.params + p.ln_off[l], p.params + p.ln_off[l] + ldw);
+          __syncthreads();
+        }
+      }
+      const float* Arow = act[cur] + r16 * LDACT_W + 4 * kq;
+      float* out = act[cur ^ 1];
+      for (int n0 = 0; n0 < n_pad; n0 += HMAX) {
+        // the rows of W and the (padded) columns left in this panel: 1 <= rows, since
+        // n_pad - N < KC and n0 is a multiple of HMAX
+        const int rows = min(N - n0, HMAX), cols = min(n_pad - n0, HMAX);
+        const float* Wp = W + (int64_t)n0 * ldw;
+        const bool wave_on = 16 * wave < cols;
+        const bool one_tile = cols <= 64;
+        f32x4 acc[TPW];
+#pragma unroll
+        for (int t = 0; t < TPW; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[t][r] = 0.f;
+        // (every wave is past the barrier behind the previous panel's last chunk)
+        WeightStage ws;
+        ws.load(Wp, ldw, rows, K, 0);
+        ws.store(wst, rows, K, 0);
+        __syncthreads();
+        for (int s = 0; s < nk; ++s) {
+          const bool more = s + 1 < nk;
+          if (more) ws.load(Wp, ldw, rows, K, (s + 1) * KC);
+          if (wave_on) {
+            const float* B = wst + (s & 1) * STAGE + (16 * wave + r16) * LDW + 4 * kq;
+            if (one_tile) staged_chunk<1>(Arow + s * KC, B, acc);
+            else staged_chunk<TPW>(Arow + s * KC, B, acc);
+          }
+          if (more) ws.store(wst + ((s + 1) & 1) * STAGE, rows, K, (s + 1) * KC);
+          __syncthreads();
+        }
+        // bias + activation -> the other tile at the panel's offset.  The columns
+        // N <= n0 + ncol < n_pad are 0, not f(0): they are the next layer's k padding.
+        auto epilogue = [&](auto code) {
+#pragma unroll
+          for (int t = 0; t < TPW; ++t) {
+            if (t == 0 || !one_tile) {
+              const int ncol = 16 * (wave + 4 * t) + r16;
+              const float bv = ncol < rows ? bias[n0 + ncol] : 0.f;
+              float v[4];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float th = act_fwd<decltype(code)::value>(acc[t][r] + bv);
+                v[r] = ncol < rows ? th : 0.f;
+              }
+              if (ncol < cols) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDACT_W + n0 + ncol] = v[r];
+              }
+            }
+          }
+        };
+        if (wave_on) {
+          if constexpr (GEN) act_dispatch(act_forward_code(p.hidden_act), epilogue);
+          else epilogue(std::integral_constant<int, 1>{});  // tanh
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+      PS_STAMP(2 + l);
+    }
+
+    // ---- narrow output layer: its [N][ldw] block goes to LDS across both stages;
+    //      16 lanes per row hold their k slice of the row in registers
+    {
+      const int K = p.net.dims[L - 1], N = p.net.dims[L];
+      const int ldw = (K + 3) & ~3;
+      const float* W = p.params + p.net.w_off[L - 1];
+      const float* bias = p.params + p.net.b_off[L - 1];
+      for (int e = tid; e < N * (ldw / 4); e += 256)  // <= 32 * 128 vectors < 2 * STAGE / 4
+        reinterpret_cast<float4*>(wst)[e] = reinterpret_cast<const float4*>(W)[e];
+      const int r = tid >> 4, part = tid & 15;
+      const float* a = act[cur] + r * LDACT_W;
+      float4 xr[WMAX / 64];
+#pragma unroll
+      for (int i = 0; i < WMAX / 64; ++i) {
+        const int k = part * 4 + 64 * i;
+        float4 v = *reinterpret_cast<const float4*>(a + (k < K ? k : 0));
+        v.x = k < K ? v.x : 0.f;
+        v.y = k + 1 < K ? v.y : 0.f;
+        v.z = k + 2 < K ? v.z : 0.f;
+        v.w = k + 3 < K ? v.w : 0.f;
+        xr[i] = v;
+      }
+      __syncthreads();
+      for (int o = 0; o < N; ++o) {
+        const float* w = wst + o * ldw + part * 4;
+        float4 wv[WMAX / 64];
+#pragma unroll
+        for (int i = 0; i < WMAX / 64; ++i)
+          wv[i] = *reinterpret_cast<const float4*>(
+              w + (part * 4 + 64 * i < ldw ? 64 * i : 0));
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < WMAX / 64; ++i) {
+          const float t = sum + (xr[i].x * wv[i].x + xr[i].y * wv[i].y +
+                                 xr[i].z * wv[i].z + xr[i].w * wv[i].w);
+          sum = part * 4 + 64 * i < ldw ? t : sum;
+        }
+        sum = sum16(sum);
+        if (part == 0) {
+          const float z = sum + bias[o];
+          if constexpr (GEN)
+            act_dispatch(p.output_act, [&](auto code) {
+              head[r][o] = act_fwd<decltype(code)::value>(z);
+            });
+          else
+            head[r][o] = z;
+        }
+      }
+    }
+    __syncthreads();
+    PS_STAMP(10);
+
+    // ---- action head and env step: one thread per env
+    int ended_len = 0;
+    if (tid < ROWS) {
+      const int64_t env = row0 + tid;
+      if (env < hd.n) {
+        ga_rollout::head_one(hd, head[tid], p.net.dims[L], p.params, env);
+        if (p.env_step)
+          ended_len = ga_rollout::env_step_one(es, env, pre, hd.action + env * hd.lda);
+      }
+    }
+    if (p.env_step && wave == 0) ga_rollout::record_counts(es.p, ended_len);
+    PS_STAMP(11);
+    // the next step reads what the env threads just wrote and reuses the LDS tiles
+    if (sidx + 1 < p.n_steps) __syncthreads();
+  }  // steps
+}
+
 // ---- the same network, training forward ---------------------------------------
 // All layers of one minibatch forward in one launch: 8 waves own 32 (gathered)
 // rows; hidden activations go to LDS for the next layer AND to HBM for the
@@ -844,6 +1077,19 @@ extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
   return 1;
 }
 
+// GARAGE_AMD_ROLLOUT_WIDE=0: networks only the wide kernel takes go back to the
+// per-layer path (A/B runs)
+static bool g_ps_no_wide = getenv("GARAGE_AMD_ROLLOUT_WIDE") &&
+                           atoi(getenv("GARAGE_AMD_ROLLOUT_WIDE")) == 0;
+
+// 1 when ga_policy_step_fused_f32 / ga_policy_env_step_fused_f32 / ga_rollout_env_steps
+// take this network: what the predicate above accepts (the kernels it always had), or
+// layer inputs up to 512 (internal.h: ga_step_wide_rule; policy_step_wide_kernel).
+extern "C" int ga_policy_step_wide_supported(const ga_mlp_desc* d) {
+  if (ga_policy_step_fused_supported(d)) return 1;
+  return !g_ps_no_wide && ga_step_wide_rule(d);
+}
+
 // `head` of args is ignored (the means / scores stay on chip); everything else
 // as in ga_policy_head_sample.
 template <class Env>
@@ -858,7 +1104,8 @@ static long long* g_ps_dbg = nullptr;
 // developer hook: phase timestamps (100 MHz wall clock) of workgroup 0 of the most
 // recent fused rollout step -- first call arms it, second call reads 32 values back
 // (0 start, 1 observations staged, 2 + l hidden layer l done, 10 output layer,
-// 11 sampled + env stepped; + 16: the same of the resident-weights kernel; the middle step of the launch)
+// 11 sampled + env stepped; + 16: the same of the resident-weights kernel; the middle step of the launch;
+// policy_step_wide_kernel writes the streamed kernel's slots)
 extern "C" int ga_policy_step_debug(long long* host_out32) {
   if (!g_ps_dbg) {
     if (hipMalloc(&g_ps_dbg, 32 * sizeof(long long)) != hipSuccess) return -1;
@@ -910,7 +1157,9 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                               const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
                               hipStream_t stream) {
   GA_REQUIRE(d && params && a, "ga_policy_step_fused_f32: null pointer");
-  GA_REQUIRE(ga_policy_step_fused_supported(d),
+  // every descriptor the old predicate accepts keeps the kernel it had
+  const bool wide = !ga_policy_step_fused_supported(d);
+  GA_REQUIRE(!wide || ga_policy_step_wide_supported(d),
              "ga_policy_step_fused_f32: unsupported network shape");
   GA_REQUIRE(a->obs && a->action && a->obs_buf && a->act_buf,
              "ga_policy_step_fused_f32: null buffer");
@@ -941,6 +1190,17 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                         (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
   // the tanh / linear-output / no-LayerNorm network keeps the kernel it always had
   const bool general = d->hidden_act != 0 || d->output_act != 0 || d->layer_norm;
+  if (wide) {
+    if (n_steps > 1) ga_prof_count(GA_PROF_ROLLOUT_WIDE);
+    if (general)
+      hipLaunchKernelGGL((policy_step_wide_kernel<Env, true>), grid, dim3(256), 0, stream,
+                         p);
+    else
+      hipLaunchKernelGGL((policy_step_wide_kernel<Env, false>), grid, dim3(256), 0, stream,
+                         p);
+    GA_CHECK_LAUNCH("policy_step_wide");
+    return GA_OK;
+  }
   if (resident) ga_prof_count(GA_PROF_ROLLOUT);
   if (resident && general)
     hipLaunchKernelGGL((policy_step_fused_kernel<true, Env, true>), grid, dim3(256), 0,

@@ -19,7 +19,9 @@ enum GaProfKind {
   GA_PROF_ROLLOUT = 13,     // policy_step_fused_kernel<true>: a whole rollout (policy +
                             // env + bookkeeping for n_steps > 1) in one launch; counted
                             // only (ga_launch_count), never timed
-  GA_PROF_KINDS = 14
+  GA_PROF_ROLLOUT_WIDE = 14,  // policy_step_wide_kernel with n_steps > 1 (weights
+                              // streamed: layer inputs up to 512); counted only
+  GA_PROF_KINDS = 15
 };
 
 // When profiling is on, hands out a (start, stop) event pair to attach to ONE

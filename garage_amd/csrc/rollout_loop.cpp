@@ -61,7 +61,7 @@ extern "C" int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params
     ga_set_error("ga_rollout_env_steps: steps exceed the rollout buffer");
     return -1;
   }
-  if (!ga_policy_step_fused_supported(desc)) {
+  if (!ga_policy_step_fused_supported(desc) && !ga_step_wide_rule(desc)) {
     ga_set_error("ga_rollout_env_steps: network not supported by the fused step");
     return -1;
   }

@@ -395,9 +395,9 @@ class MultiTaskPointVecEnv(_DeviceVecEnv):
     - the tasks share ``arena_size``, ``done_bonus``, ``never_done`` and
       ``max_episode_length``; only the goal differs;
     - ``task_id`` is held as uint8 on the device: at most 256 tasks.  The
-      one-launch rollout with resident weights needs ``3 + K <= 32``; the
-      fused policy step takes rows up to 256 wide, wider ones the per-layer
-      path, like any other observation;
+      one-launch rollout with resident weights needs ``3 + K <= 32``; rows
+      up to 512 wide (every ``K`` a uint8 can name) stay in the one-launch
+      rollout with the weights streamed, like any other observation;
     - a sample strategy other than the two above raises
       ``NotImplementedError`` (an arbitrary Python callable cannot run in the
       kernel); ``mode='del-onehot'`` raises ``ValueError``: a PointEnv

@@ -340,9 +340,12 @@ class GpuVecWorker:
         self._global_step += 1
 
     def _fused_ok(self):
+        # (layer inputs up to 256: the resident-weights kernels; up to 512: the
+        # wide one)
+        lib, desc = _lib.load(), C.byref(self.agent.net._desc)
         return self._use_fused and bool(
-            _lib.load().ga_policy_step_fused_supported(
-                C.byref(self.agent.net._desc)))
+            lib.ga_policy_step_fused_supported(desc)
+            or lib.ga_policy_step_wide_supported(desc))
 
     def _head_args(self, b, col, fused):
         env, pol, n = self.env, self.agent, self._n_envs

@@ -6,10 +6,15 @@ never_done, so that every episode runs its T steps as the other rows' do and the
 rows differ by the work per step alone): 4096 envs x T 256, a (256, 256)
 Gaussian MLP policy.  ``--options`` adds PointVecEnv behind a relu, an elu and a
 LayerNorm + tanh policy of the same sizes (rows ``point_relu``, ``point_elu``,
-``point_ln_tanh``): the one-launch rollout with the network options.
+``point_ln_tanh``): the one-launch rollout with the network options.  ``--wide`` adds
+SyntheticVecEnv behind networks wider than 256 (the wide rollout kernel; with
+``GARAGE_AMD_ROLLOUT_WIDE=0`` in the environment the same rows take the per-layer path):
+``synthetic_c5`` -- obs 376, act 17, (512, 512, 512), ragged episodes of 32..T steps,
+8192 envs unless ``--envs`` says otherwise -- and ``synthetic_320`` -- obs 17, act 6,
+(320, 320).
 
     python tools/device_env_rate.py [--envs 4096] [--T 256] [--reps 5] [--options]
-                                    [--lib path/to/libgarage_amd.so]
+                                    [--wide] [--lib path/to/libgarage_amd.so]
 
 ``--lib`` loads another build of the library (A/B runs against an earlier commit's).
 
@@ -35,6 +40,7 @@ def measure(kind, n, T, reps):
     from garage_amd.sampler import GpuVecSampler, GpuVecWorker
     torch.manual_seed(0)
     options = {}
+    hidden = (256, 256)
     if kind in POLICY_OPTIONS:
         options = POLICY_OPTIONS[kind]()
     if kind == 'point' or options:
@@ -46,9 +52,12 @@ def measure(kind, n, T, reps):
             n, np.stack([np.cos(angle), np.sin(angle)], axis=1),
             round_robin_strategy, 'add-onehot', start='spread',
             never_done=True, max_episode_length=T)
+    elif kind in WIDE_ROWS:
+        O, A, hidden, min_len = WIDE_ROWS[kind]
+        env = SyntheticVecEnv(n, O, A, T, min_len=min_len, seed=1)
     else:
         env = SyntheticVecEnv(n, 3, 2, T, seed=1)
-    pol = GaussianMLPPolicy(env.spec, hidden_sizes=(256, 256), init_std=0.1,
+    pol = GaussianMLPPolicy(env.spec, hidden_sizes=hidden, init_std=0.1,
                             **options)
     s = GpuVecSampler(pol, env, max_episode_length=T, n_workers=1,
                       worker_class=GpuVecWorker, seed=1,
@@ -65,7 +74,7 @@ def measure(kind, n, T, reps):
         dt = time.perf_counter() - t0
         if r:  # the first rollout warms up
             rates.append(n * (w._global_step - step0) / dt)
-    return dict(env=kind, n_envs=n, T=T, hidden=[256, 256],
+    return dict(env=kind, n_envs=n, T=T, hidden=list(hidden),
                 env_steps_per_s=float(np.median(rates)),
                 min=float(np.min(rates)), max=float(np.max(rates)))
 
@@ -86,13 +95,21 @@ POLICY_OPTIONS = {'point_relu': _relu, 'point_elu': _elu,
                   'point_ln_tanh': _ln_tanh}
 
 
+# obs, act, hidden, min_len
+WIDE_ROWS = {'synthetic_c5': (376, 17, (512, 512, 512), 32),
+             'synthetic_320': (17, 6, (320, 320), None)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--envs', type=int, default=4096)
+    ap.add_argument('--envs', type=int, default=None,
+                    help='default 4096 (synthetic_c5: 8192)')
     ap.add_argument('--T', type=int, default=256)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--options', action='store_true',
                     help='also the point_relu / point_elu / point_ln_tanh rows')
+    ap.add_argument('--wide', action='store_true',
+                    help='also the synthetic_c5 / synthetic_320 rows')
     ap.add_argument('--lib', help='load this build of libgarage_amd.so')
     a = ap.parse_args()
     if a.lib:
@@ -101,8 +118,11 @@ def main():
     kinds = ('point', 'synthetic', 'multitask_k4', 'multitask_k16')
     if a.options:
         kinds += tuple(POLICY_OPTIONS)
+    if a.wide:
+        kinds += tuple(WIDE_ROWS)
     for kind in kinds:
-        print(json.dumps(measure(kind, a.envs, a.T, a.reps)))
+        n = a.envs or (8192 if kind == 'synthetic_c5' else 4096)
+        print(json.dumps(measure(kind, n, a.T, a.reps)), flush=True)
 
 
 if __name__ == '__main__':
