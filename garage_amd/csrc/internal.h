@@ -79,7 +79,7 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
   return -1;
 }
 
-// The networks policy_fused.hip's wide rollout step takes (layer inputs up to 512, a
+// The networks policy_fused.hip's step kernel takes at WIDTH = 512 (layer inputs up to 512, a
 // head up to 32, up to 8 layers, activation codes 0 .. 6): a superset of what
 // ga_policy_step_fused_supported accepts.  ga_policy_step_wide_supported and
 // ga_rollout_env_steps both ask here.

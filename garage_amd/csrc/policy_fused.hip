@@ -15,13 +15,13 @@
 // 16-column tiles w, w + 4, ...; means agree with the per-layer path to rounding),
 // the narrow output layer is a 16-lane VALU dot product, and the head (Gaussian:
 // mean + std * noise; categorical: inverse CDF) writes the action and the rollout
-// buffers.  Layer inputs up to 256 (C2, C3) run in policy_step_fused_kernel; up to 512
-// (C5) in policy_step_wide_kernel, below it; wider nets use the per-layer path.
+// buffers.  Layer inputs up to 256 (C2, C3) run in policy_step_fused_kernel<WIDTH = 256>,
+// up to 512 (C5) in its WIDTH = 512 instantiations; wider nets use the per-layer path.
 // Every network option of ga_mlp_desc runs here: the tanh / linear-output network in
 // the kernels it always had (GEN = false), any other hidden_act / output_act (0 .. 6)
 // and layer_norm in a second set of instantiations (GEN = true) whose epilogues
 // apply gemm_core.h's activations to the same sums and which normalise each hidden
-// layer's input rows in LDS (ln_rows, lnorm.hip's formula).
+// layer's input rows in LDS (ln_rows_w, lnorm.hip's formula).
 // The parameters describe the network as NetDev (net_to_dev, below) and the head as
 // rollout_dev.h's HeadDev (ga_head_to_dev), the struct the per-layer head kernel takes.
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
@@ -35,37 +35,39 @@
 #include "gemm_core.h"  // act_apply / act_forward_code: the per-layer epilogue's own
 #include "rollout_dev.h"
 
-// ---- Audit (round 3) of out-of-range lanes / idle waves.  Clamped loads (value
-// discarded by the matching store's mask): WeightStage::load and the training
-// forward's wload -- nrow = min(f >> 3, N - 1), k = min(k0 + 4 (f & 7), last vector of
-// the row).  Guarded loads: the register-resident second layer (ncol < N && k < K,
-// a 16-B read at k <= ld - 4), biases (ncol < dims[l + 1], tid < dims[L]), the output
-// layer's [N][ld] block (e < N * ld / 4), observations (env < n && c < in_w), noise
-// rows (per env < n); LayerNorm gamma / beta: the resident copy element by element
-// (tid < dims[l], zero beyond), the streamed 16-B reads only where the vector's first
-// column k < dims[l] -- it ends at k + 3 < round4(dims[l]), the length the layout
-// gives gamma and beta each -- and never for a row index: all 16 rows of the tile
-// exist in LDS (rows of envs >= n hold zeros and normalise to beta; they are never
-// stored).  Nothing is fetched from an index derived from a wave number alone.
-// policy_step_wide_kernel: the same loads with the same guards.  WeightStage::load is
-// given the panel's base W + n0 * ldw and rows = min(N - n0, 256) >= 1, so nrow is
-// clamped against the rows left in the panel (and k against the row's last vector);
-// biases ncol < rows at bias[n0 + ncol]; epilogue stores n0 + ncol < n_pad <= 512 < the
-// row stride; the output layer's block e < N * ld / 4 <= 32 * 128 vectors, inside the two
-// contiguous stages (4608 vectors); row vectors (output layer, ln_rows_w<512>) at
-// k < K <= 512 or vector 0; gamma / beta where the vector's first column k < dims[l].
+// ---- Audit of out-of-range lanes / idle waves in the step kernel (one body for every
+// WIDTH) and the training forward.  A hidden layer's weights are fetched per panel of
+// up to 256 output columns: panel base W + n0 * ldw, rows = min(N - n0, 256) >= 1 rows
+// of W left in it (n0 = 0 and rows = N at WIDTH = 256 and in the training forward).
+// Clamped loads (value discarded by the matching store's mask): WeightStage::load --
+// nrow = min(f >> 3, rows - 1), k = min(k0 + 4 (f & 7), last vector of the row); its
+// store zeroes nrow >= rows and k >= K.
+// Guarded loads: the register-resident second layer (ncol < N && k < K, a 16-B read
+// at k <= ld - 4); biases (ncol < rows at bias[n0 + ncol]; resident: ncol <
+// dims[l + 1], tid < dims[L]); the output layer's [N][ld] block (e < N * ld / 4 <=
+// 32 * WIDTH / 4 vectors, inside the two contiguous stages of 4608 vectors; resident:
+// <= 2048 vectors at stage 1, which holds 2304);
+// observations (env < n && c < in_w); noise rows (per env < n); row vectors (output
+// layer, ln_rows_w) at k < K <= WIDTH or vector 0; LayerNorm gamma / beta: the resident
+// copy element by element (tid < dims[l], zero beyond), the streamed 16-B reads only
+// where the vector's first column k < dims[l] -- it ends at k + 3 < round4(dims[l]),
+// the length the layout gives gamma and beta each -- and never for a row index: all
+// 16 rows of the tile exist in LDS (rows of envs >= n hold zeros and normalise to
+// beta; they are never stored).
+// Guarded stores: the epilogue's at n0 + ncol < n_pad <= WIDTH < the row stride.
+// Nothing is fetched from an index derived from a wave number alone.
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ROWS = 16;          // envs per workgroup (one 16 x 16 MFMA tile of rows)
-constexpr int HMAX = 256;         // widest supported layer
-constexpr int LDACT = HMAX + 4;   // activation tile row stride (floats)
+constexpr int HMAX = 256;         // output columns per panel; widest layer of the
+                                  // WIDTH = 256 kernels and the training forward
+constexpr int LDACT = HMAX + 4;   // the training forward's activation row stride (floats)
 constexpr int KC = 32;            // k chunk
 constexpr int LDW = KC + 4;       // weight stage row stride
 constexpr int MAX_OUT = 32;       // widest output head
-constexpr int WMAX = 512;         // widest layer input of policy_step_wide_kernel
-constexpr int LDACT_W = WMAX + 4; // its activation tile row stride
+constexpr int WMAX = 512;         // widest layer input of the WIDTH = 512 step kernels
 
 // (tanh_fast: gemm_core.h)
 
@@ -131,16 +133,19 @@ struct FusedParams {
   if (p.dbg && blockIdx.x == 0 && threadIdx.x == 0 && sidx == p.n_steps / 2) \
     p.dbg[(i) + (RES ? 16 : 0)] = wall_clock64()
 
-// Stage W[:, k0 : k0 + 32] of a [N][ldw] weight matrix: registers -> LDS.
+// Stage W[:, k0 : k0 + 32] of a [N][ldw] weight matrix (N <= HMAX rows: a panel):
+// registers -> LDS, by a workgroup of NTHREADS.
+template <int NTHREADS>
 struct WeightStage {
-  float4 regs[HMAX * KC / 4 / 256];  // 8 vectors per thread at N = 256
+  static constexpr int NV = HMAX * KC / 4 / NTHREADS;  // vectors per thread: 8 or 4
+  float4 regs[NV];
 
   __device__ __forceinline__ void load(const float* __restrict__ W, int ldw, int N,
                                        int K, int k0) {
     const int last = max(((K + 3) & ~3) - 4, 0);
 #pragma unroll
-    for (int i = 0; i < HMAX * KC / 4 / 256; ++i) {
-      const int f = threadIdx.x + 256 * i;
+    for (int i = 0; i < NV; ++i) {
+      const int f = threadIdx.x + NTHREADS * i;
       const int nrow = min(f >> 3, N - 1);
       const int k = min(k0 + 4 * (f & 7), last);
       regs[i] = *reinterpret_cast<const float4*>(W + (int64_t)nrow * ldw + k);
@@ -149,8 +154,8 @@ struct WeightStage {
   __device__ __forceinline__ void store(float* __restrict__ stage, int N, int K,
                                         int k0) const {
 #pragma unroll
-    for (int i = 0; i < HMAX * KC / 4 / 256; ++i) {
-      const int f = threadIdx.x + 256 * i;
+    for (int i = 0; i < NV; ++i) {
+      const int f = threadIdx.x + NTHREADS * i;
       const int nrow = f >> 3;
       const int k = 4 * (f & 7);
       float4 v = regs[i];
@@ -188,8 +193,8 @@ __device__ __forceinline__ float sum16(float v) {
 // (RES) or in the parameter buffer; a vector is read only where its first column
 // k < D, and it ends inside the round4(D) floats the layout gives either row.
 constexpr float LN_EPS = 1e-5f;
-// (WIDTH: the widest row the tile holds, its row stride WIDTH + 4 -- HMAX in the
-// kernels for widths up to 256, WMAX in the wide one: 4 or 8 vectors per lane)
+// (WIDTH: the step kernel's -- the widest row the tile holds, its row stride
+// WIDTH + 4: 4 or 8 vectors per lane)
 template <int WIDTH>
 __device__ __forceinline__ void ln_rows_w(float* __restrict__ tile, int D,
                                           const float* __restrict__ gamma,
@@ -238,11 +243,6 @@ __device__ __forceinline__ void ln_rows_w(float* __restrict__ tile, int D,
     }
   }
 }
-__device__ __forceinline__ void ln_rows(float* __restrict__ tile, int D,
-                                        const float* __restrict__ gamma,
-                                        const float* __restrict__ beta) {
-  ln_rows_w<HMAX>(tile, D, gamma, beta);
-}
 // (RES && GEN kernels only: a function-scope array, so that the LDS layout of every
 // other instantiation is what it was)
 __device__ __forceinline__ float* ln_resident_store() {
@@ -258,7 +258,7 @@ __device__ __forceinline__ float* ln_resident_store() {
 constexpr int TPW = HMAX / 64;  // tiles per wave
 
 // One 32-deep chunk with the B fragments in a staged [N][LDW] chunk.
-//   A: act + (l % 16) * LDACT + 32 * chunk + 4 * (l / 16)
+//   A: act + (l % 16) * (WIDTH + 4) + 32 * chunk + 4 * (l / 16)
 //   B: stage + (16 * wave + l % 16) * LDW + 4 * (l / 16)
 template <int NT>
 __device__ __forceinline__ void staged_chunk(const float* __restrict__ A,
@@ -311,23 +311,40 @@ __device__ __forceinline__ void resident_layer_k(const float* __restrict__ A, in
   else resident_layer<16, NT>(A, wreg, acc);
 }
 
-// RES (a whole rollout in one launch, observations no wider than one k chunk, one
-// or two hidden layers): the weights stay on the CU for all the steps -- the first
-// layer's chunk in wst[0], the output layer's rows in wst[1], and the second hidden
-// layer's [N][K] matrix in REGISTERS (each lane holds the 4 x 64 B operands its
-// MFMAs consume: 256 of the 512 registers a wave has at one wave per SIMD), so that
-// layer runs without a barrier or a weight fetch.  Same k order per accumulator as
-// the streamed loop: bit-identical.
-// GEN = false is the tanh / linear-output / no-LayerNorm network (instruction for
-// instruction what it was before GEN existed).  GEN = true takes hidden_act,
-// output_act and layer_norm from the descriptor, every branch on them wave-uniform:
-// the epilogues call gemm_core.h's act_apply on the same sums, and a LayerNorm
-// (ln_rows) normalises each hidden layer's input tile in LDS first -- gamma / beta
-// resident on the CU next to obias in the RES variant.
-template <bool RES, class Env, bool GEN>
+// The step kernel.  WIDTH is the widest layer input it takes and sizes the two
+// activation tiles ([16][WIDTH + 4]) and the row registers of the output layer and
+// the LayerNorm (WIDTH / 64 vectors per lane): HMAX = 256 (109 056 B of LDS) or
+// WMAX = 512 (C5: MLP(512, 512, 512); 141 824 B, one workgroup per CU).  The weight
+// stage is 2 x [HMAX][32 + 4] at either width: a layer's output columns come in
+// panels of HMAX, per panel the k loop (32-wide chunks, ascending, one order per
+// accumulator; wave w owns the panel's tiles w, w + 4, ...) and an epilogue that
+// writes bias + activation into the other tile at the panel's column offset.  At
+// WIDTH = HMAX a layer is one panel at offset 0 and the panel loop compiles away.
+// The output layer's [N][ldw] block (up to 32 x 512 floats = 64 KB) goes to LDS across
+// the two stages, which are contiguous; every wave is past a barrier behind its last
+// stage read by then.
+// RES (WIDTH = HMAX only: a 512 x 512 fp32 layer is 1 MB; a whole rollout in one
+// launch, observations no wider than one k chunk, one or two hidden layers): the
+// weights stay on the CU for all the steps -- the first layer's chunk in stage 0, the
+// output layer's rows in stage 1, and the second hidden layer's [N][K] matrix in
+// REGISTERS (each lane holds the 4 x 64 B operands its MFMAs consume: 256 of the 512
+// registers a wave has at one wave per SIMD), so that layer runs without a barrier
+// or a weight fetch.  Same k order per accumulator as the streamed loop:
+// bit-identical.
+// GEN = false is the tanh / linear-output / no-LayerNorm network.  GEN = true takes
+// hidden_act, output_act and layer_norm from the descriptor, every branch on them
+// wave-uniform: the epilogues apply gemm_core.h's activations to the same sums, and a
+// LayerNorm (ln_rows_w) normalises each hidden layer's input tile in LDS first --
+// gamma / beta resident on the CU next to obias in the RES variant.
+template <int WIDTH, bool RES, class Env, bool GEN>
 __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env> p) {
-  __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDACT];
-  __shared__ __attribute__((aligned(16))) float wst[2][HMAX * LDW];
+  static_assert(WIDTH == HMAX || WIDTH == WMAX, "activation tile width");
+  static_assert(!RES || WIDTH == HMAX, "resident weights: layer inputs up to HMAX");
+  constexpr bool PANELS = WIDTH > HMAX;  // a layer's outputs can need a second panel
+  constexpr int LDA = WIDTH + 4;       // activation tile row stride (floats)
+  constexpr int STAGE = HMAX * LDW;
+  __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDA];
+  __shared__ __attribute__((aligned(16))) float wst[2 * STAGE];
   __shared__ float head[ROWS][MAX_OUT];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -350,12 +367,12 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
       }
     if (tid < p.net.dims[L]) obias[tid] = p.params[p.net.b_off[L - 1] + tid];
     // (the register-resident layer multiplies whole tiles: no stale columns)
-    for (int e = tid; e < ROWS * LDACT; e += 256) act[0][e] = act[1][e] = 0.f;
+    for (int e = tid; e < ROWS * LDA; e += 256) act[0][e] = act[1][e] = 0.f;
     {
       const int K = p.net.dims[0], N = p.net.dims[1];
-      WeightStage ws;
+      WeightStage<256> ws;
       ws.load(p.params + p.net.w_off[0], (K + 3) & ~3, N, K, 0);
-      ws.store(wst[0], N, K, 0);
+      ws.store(wst, N, K, 0);
     }
     if (L == 3) {
       const int K = p.net.dims[1], N = p.net.dims[2];
@@ -384,7 +401,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
       const int ldw = (K + 3) & ~3;
       const float* W = p.params + p.net.w_off[L - 1];
       for (int e = tid; e < N * (ldw / 4); e += 256)
-        reinterpret_cast<float4*>(wst[1])[e] = reinterpret_cast<const float4*>(W)[e];
+        reinterpret_cast<float4*>(wst + STAGE)[e] = reinterpret_cast<const float4*>(W)[e];
     }
     if constexpr (GEN) {
       // gamma / beta of the (at most two) normalised layer inputs: [l][2][HMAX]
@@ -411,13 +428,14 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   for (int sidx = 0; sidx < p.n_steps; ++sidx) {
   // this step's column, Philox counter and observation buffers (they swap roles
   // every step)
-  const int64_t col = p.hd.col + sidx;
-  const uint32_t step = p.hd.step + (uint32_t)sidx;
+  ga_rollout::HeadDev hd = p.hd;
+  hd.col = p.hd.col + sidx;
+  hd.step = p.hd.step + (uint32_t)sidx;
   const bool odd = sidx & 1;
   const float* obs = odd ? p.es.seen_next : p.hd.obs;
   ga_rollout::EnvStepArgsT<Env> es = p.es;
   if (p.env_step) {
-    es.p.col = col;
+    es.p.col = hd.col;
     es.seen_next = odd ? const_cast<float*>(p.hd.obs) : p.es.seen_next;
     es.p.next_obs = es.seen_next;
     if (p.es.raw_next != p.es.seen_next) {  // NormalizedEnv: the env's own rows
@@ -438,15 +456,15 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     const int r = e / in_pad, c = e % in_pad;
     const int64_t env = row0 + r;
     float v = 0.f;
-    if (env < p.hd.n && c < in_w) {
-      v = obs[env * p.hd.ldo + c];
-      p.hd.obs_buf[(env * p.hd.Tcap + col) * p.hd.ldo + c] = v;
+    if (env < hd.n && c < in_w) {
+      v = obs[env * hd.ldo + c];
+      hd.obs_buf[(env * hd.Tcap + hd.col) * hd.ldo + c] = v;
     }
-    act[0][r * LDACT + c] = v;
+    act[0][r * LDA + c] = v;
   }
   // the env threads fetch what their env's step will read now, behind the network
   decltype(ga_rollout::env_prefetch(es, 0)) pre;
-  if (p.env_step && tid < ROWS && row0 + tid < p.hd.n)
+  if (p.env_step && tid < ROWS && row0 + tid < hd.n)
     pre = ga_rollout::env_prefetch(es, row0 + tid);
   __syncthreads();
   PS_STAMP(1);
@@ -460,317 +478,53 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     const float* bias = p.params + p.net.b_off[l];
     const int nk = (K + KC - 1) / KC;
     const int n_pad = (N + KC - 1) / KC * KC;
-    // this wave's tiles: columns 16 (wave + 4 t); a narrow layer is one tile per wave
-    const bool wave_on = 16 * wave < n_pad;
-    const bool one_tile = n_pad <= 64;
     if constexpr (GEN) {
       // LayerNorm of this layer's input rows, in place (obs_buf already holds the
-      // raw observations)
+      // raw observations); gamma / beta are [ldw] floats each
       if (p.layer_norm) {
-        const int ldn = (K + 3) & ~3;
         if constexpr (RES)
-          ln_rows(act[cur], K, ln_resident_store() + (2 * l) * HMAX,
-                  ln_resident_store() + (2 * l + 1) * HMAX);
+          ln_rows_w<WIDTH>(act[cur], K, ln_resident_store() + (2 * l) * HMAX,
+                           ln_resident_store() + (2 * l + 1) * HMAX);
         else
-          ln_rows(act[cur], K, p.params + p.ln_off[l], p.params + p.ln_off[l] + ldn);
+          ln_rows_w<WIDTH>(act[cur], K, p.params + p.ln_off[l],
+                           p.params + p.ln_off[l] + ldw);
         __syncthreads();
       }
     }
-    f32x4 acc[TPW];
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t][r] = 0.f;
-    const float* Arow = act[cur] + r16 * LDACT + 4 * kq;
-    if constexpr (RES) {
-      if (wave_on) {
-        if (l == 0) {
-          const float* B = wst[0] + (16 * wave + r16) * LDW + 4 * kq;
-          if (one_tile) staged_chunk<1>(Arow, B, acc);
-          else staged_chunk<TPW>(Arow, B, acc);
-        } else {
-          if (one_tile) resident_layer_k<1>(Arow, K, wreg, acc);
-          else resident_layer_k<TPW>(Arow, K, wreg, acc);
-        }
-      }
-    } else {
-    WeightStage ws;
-    ws.load(W, ldw, N, K, 0);
-    ws.store(wst[0], N, K, 0);
-    __syncthreads();
-    for (int s = 0; s < nk; ++s) {
-      const bool more = s + 1 < nk;
-      if (more) ws.load(W, ldw, N, K, (s + 1) * KC);
-      if (wave_on) {
-        const float* B = wst[s & 1] + (16 * wave + r16) * LDW + 4 * kq;
-        if (one_tile) staged_chunk<1>(Arow + s * KC, B, acc);
-        else staged_chunk<TPW>(Arow + s * KC, B, acc);
-      }
-      if (more) ws.store(wst[(s + 1) & 1], N, K, (s + 1) * KC);
-      __syncthreads();
-    }
-    }  // streamed weights
-    (void)nk;
-    // bias + tanh -> the other activation tile (zero padded to the k chunk)
+    const float* Arow = act[cur] + r16 * LDA + 4 * kq;
     float* out = act[cur ^ 1];
-    if constexpr (!GEN) {
-    if (wave_on) {
+    // one panel of (up to) HMAX output columns at a time: a single pass at n0 = 0
+    // unless PANELS
+    for (int n0 = 0; n0 < (PANELS ? n_pad : 1); n0 += HMAX) {
+      // the rows of W and the (padded) columns left in this panel: 1 <= rows, since
+      // n_pad - N < KC and n0 is a multiple of HMAX
+      const int rows = PANELS ? min(N - n0, HMAX) : N;
+      const int cols = PANELS ? min(n_pad - n0, HMAX) : n_pad;
+      // this wave's tiles: the panel's columns 16 (wave + 4 t); a narrow panel is one
+      // tile per wave
+      const bool wave_on = 16 * wave < cols;
+      const bool one_tile = cols <= 64;
+      f32x4 acc[TPW];
 #pragma unroll
-      for (int t = 0; t < TPW; ++t) {
-        if (t == 0 || !one_tile) {
-          const int ncol = 16 * (wave + 4 * t) + r16;
-          const float bv = RES ? (l == 0 ? bias_r[0][t] : bias_r[1][t])
-                               : (ncol < N ? bias[ncol] : 0.f);
-          // (straight-line: tanh of every element, then one guarded run of stores)
-          float v[4];
+      for (int t = 0; t < TPW; ++t)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float th = tanh_fast(acc[t][r] + bv);
-            v[r] = ncol < N ? th : 0.f;
+        for (int r = 0; r < 4; ++r) acc[t][r] = 0.f;
+      if constexpr (RES) {
+        if (wave_on) {
+          if (l == 0) {
+            const float* B = wst + (16 * wave + r16) * LDW + 4 * kq;
+            if (one_tile) staged_chunk<1>(Arow, B, acc);
+            else staged_chunk<TPW>(Arow, B, acc);
+          } else {
+            if (one_tile) resident_layer_k<1>(Arow, K, wreg, acc);
+            else resident_layer_k<TPW>(Arow, K, wreg, acc);
           }
-          if (ncol < n_pad) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDACT + ncol] = v[r];
-          }
-        }
-      }
-    }
-    } else {
-    // GEN: the same epilogue, one copy per activation behind a wave-uniform switch.
-    // The columns N <= ncol < n_pad are 0, not f(0): they are the next layer's k
-    // padding.
-    auto epilogue = [&](auto code) {
-#pragma unroll
-      for (int t = 0; t < TPW; ++t) {
-        if (t == 0 || !one_tile) {
-          const int ncol = 16 * (wave + 4 * t) + r16;
-          const float bv = RES ? (l == 0 ? bias_r[0][t] : bias_r[1][t])
-                               : (ncol < N ? bias[ncol] : 0.f);
-          // (straight-line: f of every element, then one guarded run of stores)
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float th = act_fwd<decltype(code)::value>(acc[t][r] + bv);
-            v[r] = ncol < N ? th : 0.f;
-          }
-          if (ncol < n_pad) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDACT + ncol] = v[r];
-          }
-        }
-      }
-    };
-    if (wave_on) act_dispatch(act_forward_code(p.hidden_act), epilogue);
-    }  // GEN
-    __syncthreads();
-    cur ^= 1;
-    PS_STAMP(2 + l);
-  }
-
-  // ---- narrow output layer: its weights go to LDS once; 16 lanes per row hold
-  //      their k slice of the row in registers and dot it with every output
-  {
-    const int K = p.net.dims[L - 1], N = p.net.dims[L];
-    const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.net.w_off[L - 1];
-    const float* bias = p.params + p.net.b_off[L - 1];
-    float* wo = wst[RES ? 1 : 0];  // [N][ldw]: N <= 32, ldw <= 256 -> fits one stage
-    if constexpr (!RES)
-      for (int e = tid; e < N * (ldw / 4); e += 256)
-        reinterpret_cast<float4*>(wo)[e] = reinterpret_cast<const float4*>(W)[e];
-    const int r = tid >> 4, part = tid & 15;
-    const float* a = act[cur] + r * LDACT;
-    // (branch free: out-of-range slices read slice 0 and are selected away, so the
-    // LDS reads of a row go out together instead of one latency after another)
-    float4 xr[HMAX / 64];
-#pragma unroll
-    for (int i = 0; i < HMAX / 64; ++i) {
-      const int k = part * 4 + 64 * i;
-      float4 v = *reinterpret_cast<const float4*>(a + (k < K ? k : 0));
-      v.x = k < K ? v.x : 0.f;
-      v.y = k + 1 < K ? v.y : 0.f;
-      v.z = k + 2 < K ? v.z : 0.f;
-      v.w = k + 3 < K ? v.w : 0.f;
-      xr[i] = v;
-    }
-    __syncthreads();
-    for (int o = 0; o < N; ++o) {
-      const float* w = wo + o * ldw + part * 4;
-      float4 wv[HMAX / 64];
-#pragma unroll
-      for (int i = 0; i < HMAX / 64; ++i)
-        wv[i] = *reinterpret_cast<const float4*>(
-            w + (part * 4 + 64 * i < ldw ? 64 * i : 0));
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < HMAX / 64; ++i) {
-        const float t = sum + (xr[i].x * wv[i].x + xr[i].y * wv[i].y +
-                               xr[i].z * wv[i].z + xr[i].w * wv[i].w);
-        sum = part * 4 + 64 * i < ldw ? t : sum;
-      }
-      sum = sum16(sum);
-      if constexpr (GEN) {
-        if (part == 0) {
-          const float z = sum + (RES ? obias[o] : bias[o]);
-          act_dispatch(p.output_act, [&](auto code) {
-            head[r][o] = act_fwd<decltype(code)::value>(z);
-          });
         }
       } else {
-        if (part == 0) head[r][o] = sum + (RES ? obias[o] : bias[o]);
-      }
-    }
-  }
-  __syncthreads();
-  PS_STAMP(10);
-
-  // ---- action head: one thread per env (rollout_dev.h's head_one at this sub-step's
-  //      col / step plus act_row, restated: calling it changes the kernel's code)
-  int ended_len = 0;
-  if (tid < ROWS) {
-    const int64_t env = row0 + tid;
-    if (env < p.hd.n) {
-      const int N = p.net.dims[L];
-      const int64_t cell = env * p.hd.Tcap + col;
-      const float* h = head[tid];
-      float* act_row = head[tid];  // the sampled action replaces the mean / scores
-      const ga_rollout::ActionNoise rng = {p.hd.noise, p.hd.ldn, p.hd.env_id0,
-                                           step, p.hd.k0, p.hd.k1};
-      if (p.hd.head_buf) {
-        // agent_info: Gaussian mean (probabilities are written below)
-        if (p.hd.kind == 0)
-          for (int j = 0; j < N; ++j) p.hd.head_buf[cell * p.hd.ldh + j] = h[j];
-      }
-      if (p.hd.kind == 0) {
-        const float s = ga_log_std(p.params[0], p.hd.has_min, p.hd.min_log_std,
-                                   p.hd.has_max, p.hd.max_log_std, nullptr);
-        ga_rollout::sample_gaussian(h, expf(s), N, rng, env, [&](int j, float a) {
-              p.hd.action[env * p.hd.lda + j] = a;
-              p.hd.act_buf[cell * p.hd.lda + j] = a;
-              act_row[j] = a;
-            });
-      } else {
-        const int pick = ga_rollout::sample_categorical(
-            h, N, p.hd.double_softmax, rng, env,
-            p.hd.head_buf ? p.hd.head_buf + cell * p.hd.ldh : nullptr);
-        p.hd.action[env * p.hd.lda] = (float)pick;
-        p.hd.act_buf[cell * p.hd.lda] = (float)pick;
-        act_row[0] = (float)pick;
-      }
-      if (p.env_step) ended_len = ga_rollout::env_step_one(es, env, pre, act_row);
-    }
-  }
-  // (episode counts of the step: a wave-aggregated integer atomic; the envs of a
-  // workgroup all sit in wave 0)
-  if (p.env_step && wave == 0) ga_rollout::record_counts(es.p, ended_len);
-  PS_STAMP(11);
-  // the next step reads what the env threads just wrote (same workgroup: one CU,
-  // one L1) and reuses the LDS tiles
-  if (sidx + 1 < p.n_steps) __syncthreads();
-  }  // steps
-}
-
-// ---- the same step for layer inputs up to WMAX = 512 (C5: MLP(512, 512, 512)) -----
-// The contract of policy_step_fused_kernel<false, Env, GEN>: one workgroup of 256
-// threads owns 16 envs through every layer, the head, the rollout-buffer writes and
-// (env_step) the env's step for n_steps consecutive steps.  A 512 x 512 fp32 layer is
-// 1 MB, so there is no resident variant: the weights stream from L2 every step.  LDS:
-// two [16][512 + 4] activation tiles (66 048 B) + the [256][32 + 4] x 2 weight stage
-// (73 728 B) + head[16][32] (2048 B) = 141 824 B, one workgroup per CU.  A layer's
-// output columns come in panels of HMAX = 256, so the stage keeps its size: per panel
-// the k loop of the streamed kernel (32-wide chunks, ascending, one order per
-// accumulator; wave w owns the panel's tiles w, w + 4, ...) and an epilogue that
-// writes bias + activation into the other tile at the panel's column offset.  The
-// output layer's [N][ldw] block (up to 32 x 512 floats = 64 KB) spans both stages,
-// which are contiguous; every wave is past a barrier behind its last stage read by then.
-// The head is rollout_dev.h's head_one at this sub-step's column and Philox step; the
-// env steps from the action row head_one wrote (same thread).
-template <class Env, bool GEN>
-__global__ __launch_bounds__(256) void policy_step_wide_kernel(FusedParams<Env> p) {
-  constexpr bool RES = false;  // (PS_STAMP: the streamed kernel's slots)
-  constexpr int STAGE = HMAX * LDW;
-  __shared__ __attribute__((aligned(16))) float act[2][ROWS * LDACT_W];
-  __shared__ __attribute__((aligned(16))) float wst[2 * STAGE];
-  __shared__ float head[ROWS][MAX_OUT];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r16 = lane & 15, kq = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * ROWS;
-  const int L = p.net.n_layers;
-  for (int sidx = 0; sidx < p.n_steps; ++sidx) {
-    // this step's column, Philox counter and observation buffers (they swap roles
-    // every step)
-    ga_rollout::HeadDev hd = p.hd;
-    hd.col = p.hd.col + sidx;
-    hd.step = p.hd.step + (uint32_t)sidx;
-    const bool odd = sidx & 1;
-    const float* obs = odd ? p.es.seen_next : p.hd.obs;
-    ga_rollout::EnvStepArgsT<Env> es = p.es;
-    if (p.env_step) {
-      es.p.col = hd.col;
-      es.seen_next = odd ? const_cast<float*>(p.hd.obs) : p.es.seen_next;
-      es.p.next_obs = es.seen_next;
-      if (p.es.raw_next != p.es.seen_next) {  // NormalizedEnv: the env's own rows
-        es.raw_obs = odd ? p.es.raw_next : p.es.raw_obs;
-        es.raw_next = odd ? const_cast<float*>(p.es.raw_obs) : p.es.raw_next;
-      } else {
-        es.raw_obs = obs;
-        es.raw_next = es.seen_next;
-      }
-    }
-
-    // ---- observations -> act[0] (zero padded to a multiple of the k chunk) and
-    //      into the rollout buffer
-    PS_STAMP(0);
-    const int in_w = p.net.dims[0];
-    const int in_pad = (in_w + KC - 1) / KC * KC;
-    for (int e = tid; e < ROWS * in_pad; e += 256) {
-      const int r = e / in_pad, c = e % in_pad;
-      const int64_t env = row0 + r;
-      float v = 0.f;
-      if (env < hd.n && c < in_w) {
-        v = obs[env * hd.ldo + c];
-        hd.obs_buf[(env * hd.Tcap + hd.col) * hd.ldo + c] = v;
-      }
-      act[0][r * LDACT_W + c] = v;
-    }
-    decltype(ga_rollout::env_prefetch(es, 0)) pre;
-    if (p.env_step && tid < ROWS && row0 + tid < hd.n)
-      pre = ga_rollout::env_prefetch(es, row0 + tid);
-    __syncthreads();
-    PS_STAMP(1);
-
-    // ---- hidden layers on the matrix cores, one panel of 256 output columns at a time
-    int cur = 0;
-    for (int l = 0; l < L - 1; ++l) {
-      const int K = p.net.dims[l], N = p.net.dims[l + 1];
-      const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.net.w_off[l];
-      const float* bias = p.params + p.net.b_off[l];
-      const int nk = (K + KC - 1) / KC;
-      const int n_pad = (N + KC - 1) / KC * KC;
-      if constexpr (GEN) {
-        if (p.layer_norm) {
-          ln_rows_w<WMAX>(act[cur], K, p.params + p.ln_off[l], p.params + p.ln_off[l] + ldw);
-          __syncthreads();
-        }
-      }
-      const float* Arow = act[cur] + r16 * LDACT_W + 4 * kq;
-      float* out = act[cur ^ 1];
-      for (int n0 = 0; n0 < n_pad; n0 += HMAX) {
-        // the rows of W and the (padded) columns left in this panel: 1 <= rows, since
-        // n_pad - N < KC and n0 is a multiple of HMAX
-        const int rows = min(N - n0, HMAX), cols = min(n_pad - n0, HMAX);
+        // streamed weights, double buffered (every wave is past the barrier behind
+        // the previous panel's last chunk)
         const float* Wp = W + (int64_t)n0 * ldw;
-        const bool wave_on = 16 * wave < cols;
-        const bool one_tile = cols <= 64;
-        f32x4 acc[TPW];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[t][r] = 0.f;
-        // (every wave is past the barrier behind the previous panel's last chunk)
-        WeightStage ws;
+        WeightStage<256> ws;
         ws.load(Wp, ldw, rows, K, 0);
         ws.store(wst, rows, K, 0);
         __syncthreads();
@@ -785,103 +539,117 @@ __global__ __launch_bounds__(256) void policy_step_wide_kernel(FusedParams<Env> 
           if (more) ws.store(wst + ((s + 1) & 1) * STAGE, rows, K, (s + 1) * KC);
           __syncthreads();
         }
-        // bias + activation -> the other tile at the panel's offset.  The columns
-        // N <= n0 + ncol < n_pad are 0, not f(0): they are the next layer's k padding.
-        auto epilogue = [&](auto code) {
+      }
+      // bias + activation -> the other tile at the panel's offset (zero padded to the
+      // k chunk), one copy per activation behind a wave-uniform switch.  The columns
+      // N <= n0 + ncol < n_pad are 0, not f(0): they are the next layer's k padding.
+      auto epilogue = [&](auto code) {
 #pragma unroll
-          for (int t = 0; t < TPW; ++t) {
-            if (t == 0 || !one_tile) {
-              const int ncol = 16 * (wave + 4 * t) + r16;
-              const float bv = ncol < rows ? bias[n0 + ncol] : 0.f;
-              float v[4];
+        for (int t = 0; t < TPW; ++t) {
+          if (t == 0 || !one_tile) {
+            const int ncol = 16 * (wave + 4 * t) + r16;
+            const float bv = RES ? (l == 0 ? bias_r[0][t] : bias_r[1][t])
+                                 : (ncol < rows ? bias[n0 + ncol] : 0.f);
+            // (straight-line: f of every element, then one guarded run of stores)
+            float v[4];
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float th = act_fwd<decltype(code)::value>(acc[t][r] + bv);
-                v[r] = ncol < rows ? th : 0.f;
-              }
-              if (ncol < cols) {
+            for (int r = 0; r < 4; ++r) {
+              const float th = act_fwd<decltype(code)::value>(acc[t][r] + bv);
+              v[r] = ncol < rows ? th : 0.f;
+            }
+            if (n0 + ncol < n_pad) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDACT_W + n0 + ncol] = v[r];
-              }
+              for (int r = 0; r < 4; ++r) out[(4 * kq + r) * LDA + n0 + ncol] = v[r];
             }
           }
-        };
-        if (wave_on) {
-          if constexpr (GEN) act_dispatch(act_forward_code(p.hidden_act), epilogue);
-          else epilogue(std::integral_constant<int, 1>{});  // tanh
         }
+      };
+      if (wave_on) {
+        if constexpr (GEN) act_dispatch(act_forward_code(p.hidden_act), epilogue);
+        else epilogue(std::integral_constant<int, 1>{});  // tanh
       }
-      __syncthreads();
-      cur ^= 1;
-      PS_STAMP(2 + l);
-    }
+    }  // panels
+    (void)nk; (void)W;
+    __syncthreads();
+    cur ^= 1;
+    PS_STAMP(2 + l);
+  }
 
-    // ---- narrow output layer: its [N][ldw] block goes to LDS across both stages;
-    //      16 lanes per row hold their k slice of the row in registers
-    {
-      const int K = p.net.dims[L - 1], N = p.net.dims[L];
-      const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.net.w_off[L - 1];
-      const float* bias = p.params + p.net.b_off[L - 1];
-      for (int e = tid; e < N * (ldw / 4); e += 256)  // <= 32 * 128 vectors < 2 * STAGE / 4
-        reinterpret_cast<float4*>(wst)[e] = reinterpret_cast<const float4*>(W)[e];
-      const int r = tid >> 4, part = tid & 15;
-      const float* a = act[cur] + r * LDACT_W;
-      float4 xr[WMAX / 64];
+  // ---- narrow output layer: its [N][ldw] block goes to LDS once (N <= 32,
+  //      ldw <= WIDTH: inside the two stages); 16 lanes per row hold their k slice of
+  //      the row in registers and dot it with every output
+  {
+    const int K = p.net.dims[L - 1], N = p.net.dims[L];
+    const int ldw = (K + 3) & ~3;
+    const float* W = p.params + p.net.w_off[L - 1];
+    const float* bias = p.params + p.net.b_off[L - 1];
+    float* wo = wst + (RES ? STAGE : 0);
+    if constexpr (!RES)
+      for (int e = tid; e < N * (ldw / 4); e += 256)
+        reinterpret_cast<float4*>(wo)[e] = reinterpret_cast<const float4*>(W)[e];
+    const int r = tid >> 4, part = tid & 15;
+    const float* a = act[cur] + r * LDA;
+    // (branch free: out-of-range slices read slice 0 and are selected away, so the
+    // LDS reads of a row go out together instead of one latency after another)
+    float4 xr[WIDTH / 64];
 #pragma unroll
-      for (int i = 0; i < WMAX / 64; ++i) {
-        const int k = part * 4 + 64 * i;
-        float4 v = *reinterpret_cast<const float4*>(a + (k < K ? k : 0));
-        v.x = k < K ? v.x : 0.f;
-        v.y = k + 1 < K ? v.y : 0.f;
-        v.z = k + 2 < K ? v.z : 0.f;
-        v.w = k + 3 < K ? v.w : 0.f;
-        xr[i] = v;
-      }
-      __syncthreads();
-      for (int o = 0; o < N; ++o) {
-        const float* w = wst + o * ldw + part * 4;
-        float4 wv[WMAX / 64];
-#pragma unroll
-        for (int i = 0; i < WMAX / 64; ++i)
-          wv[i] = *reinterpret_cast<const float4*>(
-              w + (part * 4 + 64 * i < ldw ? 64 * i : 0));
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < WMAX / 64; ++i) {
-          const float t = sum + (xr[i].x * wv[i].x + xr[i].y * wv[i].y +
-                                 xr[i].z * wv[i].z + xr[i].w * wv[i].w);
-          sum = part * 4 + 64 * i < ldw ? t : sum;
-        }
-        sum = sum16(sum);
-        if (part == 0) {
-          const float z = sum + bias[o];
-          if constexpr (GEN)
-            act_dispatch(p.output_act, [&](auto code) {
-              head[r][o] = act_fwd<decltype(code)::value>(z);
-            });
-          else
-            head[r][o] = z;
-        }
-      }
+    for (int i = 0; i < WIDTH / 64; ++i) {
+      const int k = part * 4 + 64 * i;
+      float4 v = *reinterpret_cast<const float4*>(a + (k < K ? k : 0));
+      v.x = k < K ? v.x : 0.f;
+      v.y = k + 1 < K ? v.y : 0.f;
+      v.z = k + 2 < K ? v.z : 0.f;
+      v.w = k + 3 < K ? v.w : 0.f;
+      xr[i] = v;
     }
     __syncthreads();
-    PS_STAMP(10);
-
-    // ---- action head and env step: one thread per env
-    int ended_len = 0;
-    if (tid < ROWS) {
-      const int64_t env = row0 + tid;
-      if (env < hd.n) {
-        ga_rollout::head_one(hd, head[tid], p.net.dims[L], p.params, env);
-        if (p.env_step)
-          ended_len = ga_rollout::env_step_one(es, env, pre, hd.action + env * hd.lda);
+    for (int o = 0; o < N; ++o) {
+      const float* w = wo + o * ldw + part * 4;
+      float4 wv[WIDTH / 64];
+#pragma unroll
+      for (int i = 0; i < WIDTH / 64; ++i)
+        wv[i] = *reinterpret_cast<const float4*>(
+            w + (part * 4 + 64 * i < ldw ? 64 * i : 0));
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < WIDTH / 64; ++i) {
+        const float t = sum + (xr[i].x * wv[i].x + xr[i].y * wv[i].y +
+                               xr[i].z * wv[i].z + xr[i].w * wv[i].w);
+        sum = part * 4 + 64 * i < ldw ? t : sum;
+      }
+      sum = sum16(sum);
+      if (part == 0) {
+        const float z = sum + (RES ? obias[o] : bias[o]);
+        if constexpr (GEN)
+          act_dispatch(p.output_act, [&](auto code) {
+            head[r][o] = act_fwd<decltype(code)::value>(z);
+          });
+        else
+          head[r][o] = z;
       }
     }
-    if (p.env_step && wave == 0) ga_rollout::record_counts(es.p, ended_len);
-    PS_STAMP(11);
-    // the next step reads what the env threads just wrote and reuses the LDS tiles
-    if (sidx + 1 < p.n_steps) __syncthreads();
+  }
+  __syncthreads();
+  PS_STAMP(10);
+
+  // ---- action head and env step: one thread per env (rollout_dev.h's head_one at this
+  //      sub-step's column and Philox step; the env steps from the action row it wrote)
+  int ended_len = 0;
+  if (tid < ROWS) {
+    const int64_t env = row0 + tid;
+    if (env < hd.n) {
+      ga_rollout::head_one(hd, head[tid], p.net.dims[L], p.params, env);
+      if (p.env_step)
+        ended_len = ga_rollout::env_step_one(es, env, pre, hd.action + env * hd.lda);
+    }
+  }
+  // (episode counts of the step: a wave-aggregated integer atomic; the envs of a
+  // workgroup all sit in wave 0)
+  if (p.env_step && wave == 0) ga_rollout::record_counts(es.p, ended_len);
+  PS_STAMP(11);
+  // the next step reads what the env threads just wrote (same workgroup: one CU,
+  // one L1) and reuses the LDS tiles
+  if (sidx + 1 < p.n_steps) __syncthreads();
   }  // steps
 }
 
@@ -952,37 +720,13 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    float4 wr[4];  // weight stage: 256 x 32 floats = 2048 vectors, 4 per thread
-    const int last = max(((K + 3) & ~3) - 4, 0);
-    auto wload = [&](int k0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int f = tid + NT * i;
-        const int nrow = min(f >> 3, N - 1);
-        wr[i] = *reinterpret_cast<const float4*>(W + (int64_t)nrow * ldw +
-                                                 min(k0 + 4 * (f & 7), last));
-      }
-    };
-    auto wstore = [&](float* stage, int k0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int f = tid + NT * i;
-        const int nrow = f >> 3, k = 4 * (f & 7);
-        float4 v = wr[i];
-        const bool ok = nrow < N;
-        v.x = (ok && k0 + k + 0 < K) ? v.x : 0.f;
-        v.y = (ok && k0 + k + 1 < K) ? v.y : 0.f;
-        v.z = (ok && k0 + k + 2 < K) ? v.z : 0.f;
-        v.w = (ok && k0 + k + 3 < K) ? v.w : 0.f;
-        *reinterpret_cast<float4*>(stage + nrow * LDW + k) = v;
-      }
-    };
-    wload(0);
-    wstore(wst[0], 0);
+    WeightStage<NT> ws;  // 256 x 32 floats = 2048 vectors, 4 per thread
+    ws.load(W, ldw, N, K, 0);
+    ws.store(wst[0], N, K, 0);
     __syncthreads();
     for (int s = 0; s < nk; ++s) {
       const bool more = s + 1 < nk;
-      if (more) wload((s + 1) * KC);
+      if (more) ws.load(W, ldw, N, K, (s + 1) * KC);
       if (wave_on) {
         const float* A = act + (32 * ri + l31) * LDACT + s * KC;
         const float* B = wst[s & 1] + (n0 + l31) * LDW;
@@ -1002,7 +746,7 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
           acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, acc[1], 0, 0, 0);
         }
       }
-      if (more) wstore(wst[(s + 1) & 1], (s + 1) * KC);
+      if (more) ws.store(wst[(s + 1) & 1], N, K, (s + 1) * KC);
       __syncthreads();
     }
     // every wave is past its last read of `act`: overwrite it with this layer
@@ -1077,14 +821,14 @@ extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
   return 1;
 }
 
-// GARAGE_AMD_ROLLOUT_WIDE=0: networks only the wide kernel takes go back to the
+// GARAGE_AMD_ROLLOUT_WIDE=0: networks only the WIDTH = 512 kernels take go back to the
 // per-layer path (A/B runs)
 static bool g_ps_no_wide = getenv("GARAGE_AMD_ROLLOUT_WIDE") &&
                            atoi(getenv("GARAGE_AMD_ROLLOUT_WIDE")) == 0;
 
 // 1 when ga_policy_step_fused_f32 / ga_policy_env_step_fused_f32 / ga_rollout_env_steps
 // take this network: what the predicate above accepts (the kernels it always had), or
-// layer inputs up to 512 (internal.h: ga_step_wide_rule; policy_step_wide_kernel).
+// layer inputs up to 512 (internal.h: ga_step_wide_rule; the WIDTH = 512 kernels).
 extern "C" int ga_policy_step_wide_supported(const ga_mlp_desc* d) {
   if (ga_policy_step_fused_supported(d)) return 1;
   return !g_ps_no_wide && ga_step_wide_rule(d);
@@ -1105,7 +849,7 @@ static long long* g_ps_dbg = nullptr;
 // recent fused rollout step -- first call arms it, second call reads 32 values back
 // (0 start, 1 observations staged, 2 + l hidden layer l done, 10 output layer,
 // 11 sampled + env stepped; + 16: the same of the resident-weights kernel; the middle step of the launch;
-// policy_step_wide_kernel writes the streamed kernel's slots)
+// the WIDTH = 512 kernels write the streamed slots)
 extern "C" int ga_policy_step_debug(long long* host_out32) {
   if (!g_ps_dbg) {
     if (hipMalloc(&g_ps_dbg, 32 * sizeof(long long)) != hipSuccess) return -1;
@@ -1151,6 +895,17 @@ extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* p
   });
 }
 
+template <int WIDTH, bool RES, class Env>
+static void step_kernel_launch(bool general, dim3 grid, hipStream_t stream,
+                               const FusedParams<Env>& p) {
+  if (general)
+    hipLaunchKernelGGL((policy_step_fused_kernel<WIDTH, RES, Env, true>), grid, dim3(256),
+                       0, stream, p);
+  else
+    hipLaunchKernelGGL((policy_step_fused_kernel<WIDTH, RES, Env, false>), grid, dim3(256),
+                       0, stream, p);
+}
+
 template <class Env>
 static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                               const ga_head_args* a,
@@ -1190,30 +945,16 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                         (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
   // the tanh / linear-output / no-LayerNorm network keeps the kernel it always had
   const bool general = d->hidden_act != 0 || d->output_act != 0 || d->layer_norm;
+  // every descriptor the old predicate accepts runs at WIDTH = HMAX
   if (wide) {
     if (n_steps > 1) ga_prof_count(GA_PROF_ROLLOUT_WIDE);
-    if (general)
-      hipLaunchKernelGGL((policy_step_wide_kernel<Env, true>), grid, dim3(256), 0, stream,
-                         p);
-    else
-      hipLaunchKernelGGL((policy_step_wide_kernel<Env, false>), grid, dim3(256), 0, stream,
-                         p);
+    step_kernel_launch<WMAX, false>(general, grid, stream, p);
     GA_CHECK_LAUNCH("policy_step_wide");
     return GA_OK;
   }
   if (resident) ga_prof_count(GA_PROF_ROLLOUT);
-  if (resident && general)
-    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env, true>), grid, dim3(256), 0,
-                       stream, p);
-  else if (resident)
-    hipLaunchKernelGGL((policy_step_fused_kernel<true, Env, false>), grid, dim3(256), 0,
-                       stream, p);
-  else if (general)
-    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env, true>), grid, dim3(256), 0,
-                       stream, p);
-  else
-    hipLaunchKernelGGL((policy_step_fused_kernel<false, Env, false>), grid, dim3(256), 0,
-                       stream, p);
+  if (resident) step_kernel_launch<HMAX, true>(general, grid, stream, p);
+  else step_kernel_launch<HMAX, false>(general, grid, stream, p);
   GA_CHECK_LAUNCH("policy_step_fused");
   return GA_OK;
 }

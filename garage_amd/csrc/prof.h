@@ -16,10 +16,10 @@ enum GaProfKind {
   GA_PROF_FUSED_DGRAD = 10, // dgrad_wgrad0_kernel<*>   (data grad + first-layer wgrad)
   GA_PROF_NARROW_STEP = 11, // narrow_train_kernel<*>  (whole forward + backward, H <= 64)
   GA_PROF_EVAL_FWD = 12,    // mlp_eval_forward_kernel<*> (whole MLP, outputs only)
-  GA_PROF_ROLLOUT = 13,     // policy_step_fused_kernel<true>: a whole rollout (policy +
+  GA_PROF_ROLLOUT = 13,     // policy_step_fused_kernel<256, RES>: a whole rollout (policy +
                             // env + bookkeeping for n_steps > 1) in one launch; counted
                             // only (ga_launch_count), never timed
-  GA_PROF_ROLLOUT_WIDE = 14,  // policy_step_wide_kernel with n_steps > 1 (weights
+  GA_PROF_ROLLOUT_WIDE = 14,  // policy_step_fused_kernel<512> with n_steps > 1 (weights
                               // streamed: layer inputs up to 512); counted only
   GA_PROF_KINDS = 15
 };

@@ -155,8 +155,8 @@ struct HeadDev {
 
 // The head of env `env`: h = its A means (kind 0; log_std: the device scalar) or class
 // scores (kind 1).  Mean / probabilities -> head_buf when given, the sample -> action
-// and act_buf.  The per-layer head kernel calls it; the fused kernel's `action head`
-// section restates it at its sub-step's column and Philox step (see there).
+// and act_buf.  The per-layer head kernel calls it, and the fused step kernel with a
+// HeadDev at its sub-step's column and Philox step.
 static __device__ __forceinline__ void head_one(const HeadDev& p, const float* h, int A,
                                                 const float* log_std, int64_t env) {
   const int64_t cell = env * p.Tcap + p.col;

@@ -448,12 +448,13 @@ GA_API int ga_policy_head_sample(const ga_head_args* args, ga_stream_t stream);
  * ga_policy_head_sample.  head_buf receives the Gaussian mean AFTER the
  * output_nonlinearity, as the per-layer path's does.
  * ga_policy_step_fused_supported is the narrower rule -- every layer input <= 256 --
- * of the kernels that keep the weights resident over a rollout where they fit; the
- * descriptors it accepts run in those kernels, unchanged, and it is also what
- * ga_mlp_forward_fused_f32 (256-wide tiles) and ga_mlp_forward_f32's dispatch to it
- * ask.  The rest of what ga_policy_step_wide_supported accepts (a superset) runs in
- * one kernel that streams the weights; GARAGE_AMD_ROLLOUT_WIDE=0 in the environment
- * makes it refuse them, so that callers take the per-layer path (A/B runs).
+ * of the step kernel's WIDTH = 256 instantiations, which keep the weights resident
+ * over a rollout where they fit; the descriptors it accepts run in those, and it is
+ * also what ga_mlp_forward_fused_f32 (256-wide tiles) and ga_mlp_forward_f32's
+ * dispatch to it ask.  The rest of what ga_policy_step_wide_supported accepts (a
+ * superset) runs in the same kernel at WIDTH = 512, which streams the weights;
+ * GARAGE_AMD_ROLLOUT_WIDE=0 in the environment makes it refuse them, so that callers
+ * take the per-layer path (A/B runs).
  * ga_policy_step_fused_f32, ga_policy_env_step_fused_f32 and ga_rollout_env_steps
  * take every descriptor ga_policy_step_wide_supported accepts. */
 GA_API int ga_policy_step_fused_supported(const ga_mlp_desc* d);

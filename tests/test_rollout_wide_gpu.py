@@ -1,5 +1,5 @@
 """The one-launch rollout step for networks with layer inputs up to 512 wide
-(``policy_step_wide_kernel``: 256-column panels, weights streamed):
+(``policy_step_fused_kernel<WIDTH = 512>``: 256-column panels, weights streamed):
 
 A. the wide step against the per-layer path, both measured against an fp64
    evaluation of the policy's own parameters on the first step's observations;
@@ -8,7 +8,9 @@ B. a whole rollout in ONE launch bit for bit against the same kernel stepped
 C. the NormalizedEnv statistics inside that launch against Python-driven steps;
 D. C5's policy -- MLP(512, 512, 512), obs 376, act 17 -- against the oracle's
    ``VecWorker``;
-E. the training forward of a wide network stays on the per-layer GEMMs.
+E. the training forward of a wide network stays on the per-layer GEMMs;
+F. a (256, 256) policy against its zero-padded (272, 272) twin, bit for bit: the
+   kernel at WIDTH = 256 (weights resident and streamed) against WIDTH = 512.
 
 Measured on an MI355X: see DESIGN.md, "Networks up to 512 wide through the
 one-launch rollout".
@@ -196,7 +198,7 @@ C5_ATOL = {'mean': 1e-5, 'actions': 1e-5, 'rewards': 1e-5}
 def test_c5_whole_rollout_launch_matches_oracle_vecworker():
     """The rollout of C5's policy -- MLP(512, 512, 512), obs 376, act 17, ragged
     episodes L ~ U{8..64}, 24 envs, device Philox action noise -- with its
-    first ``ceil(num / n)`` steps in ONE ``policy_step_wide_kernel`` launch
+    first ``ceil(num / n)`` steps in ONE ``policy_step_fused_kernel<512>`` launch
     against the oracle's ``VecWorker`` (``sampler/vec_worker.py:176-204``)
     stepping the per-env CPU twins with the same noise stream: observations /
     last observations / lengths / step types bit for bit, means / actions /
@@ -336,3 +338,93 @@ def test_fused_training_forward_refuses_a_wide_network():
         call('ga_mlp_forward_fused_f32', C.byref(net._desc), dptr(net.params),
              dptr(X), X.stride(0), None, M, dptr(net._acts), dptr(out),
              out.stride(0), stream_ptr())
+
+
+def _zero_padded_pair(make_env, nonlinearity, n, P):
+    """[(worker, policy)] of a (256, 256) Gaussian policy and of a (272, 272) one
+    that holds the first's parameters in the leading blocks and exactly zero
+    elsewhere, each over its own env batch from ``make_env()``, same seeds,
+    device RNG."""
+    from garage_amd.policies import GaussianMLPPolicy
+    from garage_amd.sampler import GpuVecSampler, GpuVecWorker
+    out = []
+    for hidden in ((256, 256), (272, 272)):
+        torch.manual_seed(6)
+        env = make_env()
+        pol = GaussianMLPPolicy(env.spec, hidden_sizes=hidden, init_std=0.1,
+                                hidden_nonlinearity=nonlinearity)
+        with torch.no_grad():
+            if not out:  # biases away from zero
+                for l in range(3):
+                    pol.net.bias(l).add_(
+                        torch.randn_like(pol.net.bias(l)) * 0.05)
+            else:
+                src = out[0][1].net
+                pol.net.params.zero_()
+                pol.net.params[:4].copy_(src.params[:4])  # log_std
+                for l in range(3):
+                    rows, cols = src.dims[l + 1], src.dims[l]
+                    pol.net.weight(l)[:rows, :cols].copy_(src.weight(l))
+                    pol.net.bias(l)[:rows].copy_(src.bias(l))
+        s = GpuVecSampler(pol, env, max_episode_length=P, n_workers=1,
+                          worker_class=GpuVecWorker, seed=2,
+                          worker_args=dict(n_envs=n))
+        assert s._workers[0]._fused_ok()
+        out.append((s._workers[0], pol))
+    assert _predicates(out[0][1].net) == (1, 1)
+    assert _predicates(out[1][1].net) == (0, 1)
+    return out
+
+
+# launches of (GA_PROF_ROLLOUT, GA_PROF_ROLLOUT_WIDE) by the 256 side / the wide side
+@pytest.mark.parametrize('nonlinearity', [torch.tanh, torch.relu],
+                         ids=['tanh', 'relu'])
+@pytest.mark.parametrize('kind,whole,counts', [
+    ('point', True, ((1, 0), (0, 1))),
+    ('synthetic', True, ((0, 0), (0, 1))),
+    ('synthetic', False, ((0, 0), (0, 0))),
+], ids=['a-resident', 'b-streamed', 'c-streamed-per-step'])
+def test_zero_padding_across_the_256_boundary_keeps_the_bits(
+        kind, whole, counts, nonlinearity):
+    """A (256, 256) policy against its zero-padded (272, 272) twin: with tanh and
+    with relu f(0) = 0, so the twin's extra products are zeros added in ascending
+    k after the same terms, and the rollouts agree bit for bit -- (a) PointVecEnv,
+    P = 6 steps in one launch, the resident WIDTH = 256 kernel against WIDTH =
+    512; (b) SyntheticVecEnv with O = 40, A = 3, the streamed WIDTH = 256 kernel
+    against WIDTH = 512; (c) as (b), one step per launch.  20 envs: one full and
+    one partial workgroup.  No LayerNorm: it depends on the width."""
+    from garage_amd import _lib
+    from garage_amd.envs import PointVecEnv, SyntheticVecEnv
+    lib = _lib.load()
+    n, P = 20, 6
+
+    def make_env():
+        if kind == 'point':
+            return PointVecEnv(n, goal=(0.1, 0.1), done_bonus=0.5,
+                               max_episode_length=P)
+        return SyntheticVecEnv(n, 40, 3, P, min_len=2, seed=5)
+
+    got = []
+    for (worker, pol), want in zip(
+            _zero_padded_pair(make_env, nonlinearity, n, P), counts):
+        assert pol.net.in_dim <= 32 if kind == 'point' else pol.net.in_dim == 40
+        before = [int(lib.ga_launch_count(k))
+                  for k in (GA_PROF_ROLLOUT, GA_PROF_ROLLOUT_WIDE)]
+        if whole:
+            eps = worker.rollout_samples(n * P).to_host()
+        else:
+            eps = _stepwise(worker, n * P)
+        torch.cuda.synchronize()
+        after = [int(lib.ga_launch_count(k))
+                 for k in (GA_PROF_ROLLOUT, GA_PROF_ROLLOUT_WIDE)]
+        assert tuple(x - y for x, y in zip(after, before)) == want
+        got.append(eps)
+    a, b = got
+    mean = a.agent_infos['mean']
+    assert np.isfinite(mean).all() and np.abs(mean).max() > 0
+    assert np.array_equal(a.observations, b.observations)
+    assert np.array_equal(a.actions, b.actions)
+    assert np.array_equal(mean, b.agent_infos['mean'])
+    assert np.array_equal(a.lengths, b.lengths)
+    assert np.array_equal([int(s) for s in a.step_types],
+                          [int(s) for s in b.step_types])
