@@ -105,3 +105,18 @@ $(OUT)/mlp_layers_asan_test: tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layer
 	  -o $@
 
 .PHONY: asan-mlp
+
+# fused_step's slab ranges for the data-gradient launch and the optimizer launch's
+# pre-summed regions (update.cpp) under AddressSanitizer + UBSan, with fakes that walk
+# the ranges inside an exactly-sized slab workspace (tests/host/).
+asan-slab-sum: $(OUT)/slab_sum_asan_test
+	$(OUT)/slab_sum_asan_test
+
+$(OUT)/slab_sum_asan_test: tests/host/slab_sum_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  tests/host/slab_sum_harness.cpp $(CSRC)/update.cpp \
+	  -o $@
+
+.PHONY: asan-slab-sum

@@ -84,11 +84,21 @@ typedef struct ga_wgrad_mid_net {
 int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M, int64_t n_splits,
                  int out_w, int in_w, hipStream_t stream);
 // 3. data gradient into the first hidden layer + first-layer weight / bias gradient
-// shares; wpart: [tiles][width * round4(in_w) + width] floats
+// shares; wpart: [tiles][width * round4(in_w) + width] floats.
+// sum_w / sum_b (src != null): split-K slabs that the launch BEFORE this one on the same
+// stream wrote and that this launch sums on the side -- n elements (a multiple of 4),
+// partial k of element e at src[k * stride + e]; every element's sum, in the order
+// reduce_regions_adam_kernel gives a region of <= 128 partials, replaces its partial 0.
+// Two ranges of one launch share stride and n_part and lie within 2^30 floats of each
+// other, partials included.
+typedef struct ga_slab_range {
+  float* src; int64_t n; int64_t stride; int n_part;
+} ga_slab_range;
 typedef struct ga_fused_dgrad_net {
   const float* dZ2; int64_t lddz; const float* W2; int64_t ldw;
   const float* H1; int64_t ldh; const float* X; int64_t ldx; const int32_t* idx;
   float* wpart;
+  ga_slab_range sum_w, sum_b;
 } ga_fused_dgrad_net;
 int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M, int width,
                           int K, int in_w, hipStream_t stream);
@@ -97,6 +107,8 @@ int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M,
 // matrix at flat index pl_beg, when the step's forward launch used them;
 // ga_planes_epoch_begin: planes written that way are trusted only until the epoch
 // call that wrote them returns.
+// presummed, bit k: partial 0 of region k already holds the sum of all its partials
+// (ga_fused_dgrad_net::sum_w / sum_b); the launch reads nothing else of that region.
 typedef struct ga_reduce_net {
   const ga_fused_region* regions; int n_regions;
   float* params; float* grads; float* exp_avg; float* exp_avg_sq;
@@ -104,6 +116,7 @@ typedef struct ga_reduce_net {
   const double* lpart; int n_lpart; int64_t M; const ga_fused_loss_args* loss;
   float* loss_out;
   int64_t pl_beg; int pl_rows, pl_cols;
+  uint32_t presummed;
 } ga_reduce_net;
 int ga_reduce_regions_adam(const ga_reduce_net* nets, int n_nets, hipStream_t stream);
 void ga_planes_epoch_begin(void);

@@ -29,11 +29,18 @@
 //       db1 = 1^T dZ1  (X: <= 32 observation columns, gathered).
 //       dZ1 is never stored.  Replaces the first-layer weight-gradient streaming
 //       kernel and one [M x width] store + load.
+//       On the side (two hidden layers, more than one split; ga_set_slab_sum_in_dgrad):
+//       the launch sums the split-K slabs of the MIDDLE layer's weight gradient, which
+//       the GEMM one launch earlier on the same stream wrote, over their partial 0 --
+//       one group of four partials per k-step, in the optimizer kernel's own order
+//       (FtSlabSummer) -- so that the optimizer launch reads one partial of them.
 //
 //   reduce_regions_adam_kernel   the optimizer step over per-region partial sums
 //       (split-K slabs of the weight-gradient GEMMs, per-workgroup partials of
 //       the two kernels above), each element summed in a fixed tree by 16 shares
-//       of a workgroup; one extra block finishes the loss (batch sums -> loss
+//       of a workgroup (ft_share_run and its neighbours: one definition for this
+//       kernel and the slab sum of dgrad_wgrad0_kernel; a region that launch has
+//       summed already is read as one partial); one extra block finishes the loss (batch sums -> loss
 //       value, log-std gradient) and steps the log-std slot.
 //       torch.optim.Adam arithmetic as in losses.hip.
 //
@@ -1208,6 +1215,231 @@ const uint16_t* planes_for(const float* W, int64_t ld, int rows, int cols, int m
 }
 
 // ---------------------------------------------------------------------------
+// The sum of one parameter quad's partials, written once for the two kernels that run
+// it (reduce_regions_adam_kernel, and dgrad_wgrad0_body for the middle layer's split-K
+// slabs).  4 * (64 / Q) shares per quad: a share sums a contiguous run of
+// ceil(n_part / shares) partials, in groups of four, then singly; the lane-shares meet
+// in a butterfly, the wave-shares (four of them; or, where one wave holds all four
+// shares of a quad, lanes 16 and 32 apart in a two-step butterfly: the same tree) as
+// (a0 + a1) + (a2 + a3).  An accumulator starts at +0 and so never becomes -0: a
+// share with an empty run adds an exact zero.
+__device__ __forceinline__ void ft_sum_group4(float4& acc, const float4& v0,
+                                              const float4& v1, const float4& v2,
+                                              const float4& v3) {
+  acc.x += (v0.x + v1.x) + (v2.x + v3.x);
+  acc.y += (v0.y + v1.y) + (v2.y + v3.y);
+  acc.z += (v0.z + v1.z) + (v2.z + v3.z);
+  acc.w += (v0.w + v1.w) + (v2.w + v3.w);
+}
+__device__ __forceinline__ void ft_sum_single(float4& acc, const float4& v0) {
+  acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+}
+// partials [p0, p1) of the quad at s, four independent 16-B loads in flight
+__device__ __forceinline__ float4 ft_share_run(const float* s, int64_t stride, int p0,
+                                               int p1) {
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int k = p0;
+  for (; k + 4 <= p1; k += 4) {
+    const float4 v0 = *reinterpret_cast<const float4*>(s + (int64_t)k * stride);
+    const float4 v1 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 1) * stride);
+    const float4 v2 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 2) * stride);
+    const float4 v3 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 3) * stride);
+    ft_sum_group4(acc, v0, v1, v2, v3);
+  }
+  for (; k < p1; ++k)
+    ft_sum_single(acc, *reinterpret_cast<const float4*>(s + (int64_t)k * stride));
+  return acc;
+}
+// lanes Q, 2 Q, .. 32 apart: lane-share 0 ends with ((a0 + a1) + (a2 + a3)) + ...
+__device__ __forceinline__ void ft_lane_shares_meet(float (&g)[4], int Q) {
+  for (int off = Q; off < 64; off <<= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g[j] += __shfl_xor(g[j], off, 64);
+  }
+}
+__device__ __forceinline__ void ft_wave_shares_meet(float (&g)[4], const float4& a0,
+                                                    const float4& a1, const float4& a2,
+                                                    const float4& a3) {
+  g[0] = (a0.x + a1.x) + (a2.x + a3.x);
+  g[1] = (a0.y + a1.y) + (a2.y + a3.y);
+  g[2] = (a0.z + a1.z) + (a2.z + a3.z);
+  g[3] = (a0.w + a1.w) + (a2.w + a3.w);
+}
+
+// Slab ranges one data-gradient launch sums on the side (ga_fused_dgrad_net::sum_w /
+// sum_b): quad v of the launch is quad v of range 0 for v < nq[0], quad v - nq[0] of
+// range 1 after that; off: floats from `base` to partial 0 of a range's element 0.
+struct FtSlabSum {
+  float* base;
+  uint32_t off[2];
+  int nq[2];
+  int64_t stride;   // floats between partials
+  int n_part;       // 0: nothing to sum
+  int tiles;        // workgroups of this network's launch
+};
+
+// The other lane of a lane pair (l ^ 1), as a DPP operand: no LDS round trip
+__device__ __forceinline__ float ft_pair_swap(float x) {
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float4 ft_pair_swap(const float4& v) {
+  return make_float4(ft_pair_swap(v.x), ft_pair_swap(v.y), ft_pair_swap(v.z),
+                     ft_pair_swap(v.w));
+}
+
+// The quads of FtSlabSum are spread evenly over the launch's workgroups; a workgroup
+// takes its quads 8 * (NT / 64) at a time (a pass): wave w the 8 quads from 8 w on,
+// lane l quad (l % 16) / 2 and share l / 16 (four shares, no wave-shares).  A STEP is
+// one group of four partials per share (or the run's last one to three): issue() puts
+// its loads in flight, consume() adds them; the last step of a pass lets the shares
+// meet and the lane of share 0 -- the one that read partial 0 -- writes the sum over
+// it.  The two lanes of a pair hold the same share of the same quad and load HALF a
+// group each (lane bit 0 = 0: v0, v1; 1: v2, v3: eight registers in flight per lane
+// instead of sixteen); (v0 + v1) and (v2 + v3) cross the pair, and both lanes carry
+// the same accumulator.
+// No other workgroup reads or writes that quad's partials.  gemm_mainloop runs one
+// step per k-step (the loads land under the MFMAs); drain() runs what is left.
+// Every load is unconditional: quads are clamped to the workgroup's last one, partials
+// to the last one, and what a clamped lane loaded is not used.
+// IN_LOOP = false: everything in drain().
+template <int NT, bool IN_LOOP>
+struct FtSlabSummer {
+  static constexpr int QPW = 8;               // quads per wave and pass
+  static constexpr int QPP = QPW * (NT / 64);  // quads per pass
+  const FtSlabSum& S;
+  int wave, lane;
+  int chunk, steps, q_end, pass_base, j;
+  int in_loop;    // steps of the first pass that gemm_mainloop still runs
+  bool fast;      // every share's run is whole groups of four
+  bool busy;      // this workgroup has a pass under way
+  bool wave_on;   // ... and this wave has quads in it
+  uint32_t sb;    // bytes between partials
+  // bytes from S.base to this lane's quad; fast: to the first partial this lane
+  // loads (share 0, lane bit 0 = 0: partial 0 either way)
+  uint32_t voff;
+  float4 acc, v[2];
+
+  __device__ __forceinline__ FtSlabSummer(const FtSlabSum& S_, int tile) : S(S_) {
+    wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    lane = threadIdx.x & 63;
+    busy = wave_on = false;
+    in_loop = 0;
+    if (S.n_part <= 0) return;
+    const int nq = S.nq[0] + S.nq[1];
+    const int per = (nq + S.tiles - 1) / S.tiles;
+    chunk = (S.n_part + 3) / 4;
+    fast = S.n_part == 4 * chunk && chunk % 4 == 0;
+    steps = (chunk + 3) / 4;
+    sb = (uint32_t)S.stride * 4u;
+    // (tile * per < 2^31: tile < tiles and per <= nq / tiles + 1)
+    pass_base = min(nq, tile * per);
+    q_end = min(nq, pass_base + per);
+    start_pass();
+    in_loop = (IN_LOOP && fast && wave_on) ? steps : 0;
+  }
+  __device__ __forceinline__ int lane_quad() const {
+    return pass_base + QPW * wave + ((lane & 15) >> 1);
+  }
+  __device__ __forceinline__ void start_pass() {
+    busy = pass_base < q_end;
+    wave_on = pass_base + QPW * wave < q_end;
+    j = 0;
+    if (!wave_on) return;
+    const int qc = min(lane_quad(), q_end - 1);  // (its own quads only)
+    const uint32_t qoff = qc < S.nq[0] ? S.off[0] + 4u * (uint32_t)qc
+                                       : S.off[1] + 4u * (uint32_t)(qc - S.nq[0]);
+    voff = 4u * qoff +
+           (fast ? (uint32_t)((lane >> 4) * chunk + 2 * (lane & 1)) * sb : 0u);
+    acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // gemm_mainloop's side work: steps of whole groups of the workgroup's FIRST pass --
+  // two loads and twelve additions per step and nothing else in the loop (beside an
+  // fp32 MFMA every vector instruction costs its full issue time); ragged steps (three
+  // times the registers), the end of the pass and further passes wait for drain()
+  __device__ __forceinline__ void issue() {
+    if (IN_LOOP && in_loop > 0) issue_step<true>();
+  }
+  __device__ __forceinline__ void consume() {
+    if (IN_LOOP && in_loop > 0) {
+      add_step<true>();
+      --in_loop;
+    }
+  }
+  template <bool FAST>
+  __device__ __forceinline__ void issue_step() {
+    if (FAST) {
+      // a wave-uniform base per load (scalar registers) and one 32-bit lane offset: no
+      // vector address arithmetic
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t uo = __builtin_amdgcn_readfirstlane((uint32_t)(4 * j + i) * sb);
+        const char* bi = reinterpret_cast<const char*>(S.base) + uo;
+        v[i] = *reinterpret_cast<const float4*>(bi + voff);
+      }
+    } else {
+      const char* b = reinterpret_cast<const char*>(S.base);
+      const int k = (lane >> 4) * chunk + 4 * j + 2 * (lane & 1);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        v[i] = *reinterpret_cast<const float4*>(
+            b + (voff + (uint32_t)min(k + i, S.n_part - 1) * sb));
+    }
+  }
+  template <bool FAST>
+  __device__ __forceinline__ void add_step() {
+    if (FAST) {
+      // this lane's half (v0 + v1) or (v2 + v3), then the pair's other half: the two
+      // lanes add the same two values, (v0 + v1) + (v2 + v3)
+      const float4 h = make_float4(v[0].x + v[1].x, v[0].y + v[1].y, v[0].z + v[1].z,
+                                   v[0].w + v[1].w);
+      const float4 o = ft_pair_swap(h);
+      acc.x += h.x + o.x; acc.y += h.y + o.y; acc.z += h.z + o.z; acc.w += h.w + o.w;
+    } else {
+      const bool hi = lane & 1;
+      const float4 o0 = ft_pair_swap(v[0]), o1 = ft_pair_swap(v[1]);
+      const float4 v0 = hi ? o0 : v[0], v1 = hi ? o1 : v[1];
+      const float4 v2 = hi ? v[0] : o0, v3 = hi ? v[1] : o1;
+      const int p0 = (lane >> 4) * chunk, p1 = min(S.n_part, p0 + chunk);
+      const int k = p0 + 4 * j;
+      if (k + 4 <= p1) {
+        ft_sum_group4(acc, v0, v1, v2, v3);
+      } else {
+        if (k < p1) ft_sum_single(acc, v0);
+        if (k + 1 < p1) ft_sum_single(acc, v1);
+        if (k + 2 < p1) ft_sum_single(acc, v2);
+      }
+    }
+    ++j;
+  }
+  __device__ __forceinline__ void drain() {
+    in_loop = 0;
+    while (busy) {
+      if (wave_on) {
+        if (fast) {
+          while (j < steps) {
+            issue_step<true>();
+            add_step<true>();
+          }
+        } else {
+          while (j < steps) {
+            issue_step<false>();
+            add_step<false>();
+          }
+        }
+        float g[4] = {acc.x, acc.y, acc.z, acc.w};
+        ft_lane_shares_meet(g, 16);
+        if (lane < 16 && !(lane & 1) && lane_quad() < q_end)
+          *reinterpret_cast<float4*>(reinterpret_cast<char*>(S.base) + voff) =
+              make_float4(g[0], g[1], g[2], g[3]);
+      }
+      pass_base += QPP;
+      start_pass();
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
 struct DgradWgrad0Params {
   GemmParams g;        // A = dZ2 [M][lda], B = W2 [K][ldb] (n contiguous), M, N = BN, K
   const float* H;      // tanh outputs of the first hidden layer [M][ldh]
@@ -1222,6 +1454,7 @@ struct DgradWgrad0Params {
   const uint16_t* bplanes;
   int64_t bplane_stride;
   long long* dbg;      // developer hook: phase timestamps (FT_STAMP / FT_MARK)
+  FtSlabSum sum;       // the middle layer's split-K slabs, summed on the side
 };
 
 template <int BN, int WAVES_M, int WAVES_N, bool SPLIT = false>
@@ -1267,6 +1500,11 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
     const int64_t src = p.idx ? (int64_t)p.idx[m] : (int64_t)m;
     xq[i] = *reinterpret_cast<const float4*>(p.X + src * p.ldx + 4 * q);
   }
+
+  // the slab sum: one step per k-step of the plain loop, the rest (all of it beside the
+  // hand-scheduled split-operand loop, and at 64 units, where the steps' registers
+  // would cost the kernel a wave per SIMD) behind the loop
+  FtSlabSummer<NT, (!SPLIT && BN > 64)> slab(p.sum, ft_tile);
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -1373,11 +1611,12 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
     const bool full = m0 + FT_ROWS <= M;
     if (full)
       gemm_mainloop<FT_ROWS, BN, WAVES_M, WAVES_N, true, false, BK, true>(
-          p.g, lds, acc, csum, false, m0, 0, 0, p.g.K, wm0, wn0);
+          p.g, lds, acc, csum, false, m0, 0, 0, p.g.K, wm0, wn0, slab);
     else
       gemm_mainloop<FT_ROWS, BN, WAVES_M, WAVES_N, true, false, BK, false>(
-          p.g, lds, acc, csum, false, m0, 0, 0, p.g.K, wm0, wn0);
+          p.g, lds, acc, csum, false, m0, 0, 0, p.g.K, wm0, wn0, slab);
   }
+  slab.drain();
   FT_STAMP(1);
   FT_MARK(1);
 
@@ -1514,7 +1753,8 @@ struct FtRegion {
   const float* src;   // partial 0 of element 0
   int64_t stride;     // floats between consecutive partials
   int n_part;
-  int quads;          // quads per workgroup: 64 or 16
+  int quads;          // quads per workgroup: 64 or 16 (pre: 256)
+  int pre;            // partial 0 holds the sum already: nothing else is read
   int64_t vbeg;       // first workgroup of the region
   int net;            // which network's buffers (a pair launch steps two)
 };
@@ -1583,7 +1823,8 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
   // Q = 64 (whole 1-KB rows per load instruction, 4 shares) for regions of up to 128
   // partials -- the split-K slabs --, Q = 16 (256-B segments, 16 shares) for the
   // small regions with one partial per 64-row tile.  The lane-shares meet in a
-  // butterfly, the wave-shares in LDS, both fixed trees.
+  // butterfly, the wave-shares in LDS, both fixed trees (ft_share_run and its
+  // neighbours above).
   __shared__ float4 wsum[4][64];
   const int64_t b = blockIdx.x;
   int ri = 0;
@@ -1593,48 +1834,34 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
   const FtRegion& R = p.r[ri];
   const FtNet& N = p.net[R.net];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int Q = R.quads;  // 64 or 16
-  const int lwc = 64 / Q;
-  const int q = lane % Q, lw = lane / Q;
-  const int way = lwc * wv + lw;
-  const int64_t e4 = (b - R.vbeg) * Q + q;  // this lane's quad
-  const bool on = 4 * e4 < R.n;
-  const int shares = 4 * lwc;
-  const int chunk = (R.n_part + shares - 1) / shares;
-  const int p0 = way * chunk, p1 = min(R.n_part, p0 + chunk);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (on) {
-    const float* s = R.src + 4 * e4;
-    int k = p0;
-    for (; k + 4 <= p1; k += 4) {
-      const float4 v0 = *reinterpret_cast<const float4*>(s + (int64_t)k * R.stride);
-      const float4 v1 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 1) * R.stride);
-      const float4 v2 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 2) * R.stride);
-      const float4 v3 = *reinterpret_cast<const float4*>(s + (int64_t)(k + 3) * R.stride);
-      acc.x += (v0.x + v1.x) + (v2.x + v3.x);
-      acc.y += (v0.y + v1.y) + (v2.y + v3.y);
-      acc.z += (v0.z + v1.z) + (v2.z + v3.z);
-      acc.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; k < p1; ++k) {
-      const float4 v0 = *reinterpret_cast<const float4*>(s + (int64_t)k * R.stride);
-      acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-    }
-  }
-  float g[4] = {acc.x, acc.y, acc.z, acc.w};
-  for (int off = Q; off < 64; off <<= 1) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g[j] += __shfl_xor(g[j], off, 64);
-  }
-  if (lw == 0) wsum[wv][q] = make_float4(g[0], g[1], g[2], g[3]);
-  __syncthreads();
-  if ((int)threadIdx.x >= Q || !on) return;
-  {
-    const float4 a0 = wsum[0][q], a1 = wsum[1][q], a2 = wsum[2][q], a3 = wsum[3][q];
-    g[0] = (a0.x + a1.x) + (a2.x + a3.x);
-    g[1] = (a0.y + a1.y) + (a2.y + a3.y);
-    g[2] = (a0.z + a1.z) + (a2.z + a3.z);
-    g[3] = (a0.w + a1.w) + (a2.w + a3.w);
+  float g[4];
+  int64_t e4;  // this lane's quad
+  if (R.pre) {
+    // partial 0 already holds the sum of the region's partials (the data-gradient
+    // launch ran the tree above on them): the region as one of n_part = 1, in which
+    // shares 1 .. 3 contribute exact zeros -- a quad per thread, nothing to meet
+    e4 = (b - R.vbeg) * 256 + threadIdx.x;
+    if (4 * e4 >= R.n) return;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    ft_wave_shares_meet(g, ft_share_run(R.src + 4 * e4, R.stride, 0, 1), zero, zero, zero);
+  } else {
+    const int Q = R.quads;  // 64 or 16
+    const int lwc = 64 / Q;
+    const int q = lane % Q, lw = lane / Q;
+    const int way = lwc * wv + lw;
+    e4 = (b - R.vbeg) * Q + q;
+    const bool on = 4 * e4 < R.n;
+    const int shares = 4 * lwc;
+    const int chunk = (R.n_part + shares - 1) / shares;
+    const int p0 = way * chunk, p1 = min(R.n_part, p0 + chunk);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (on) acc = ft_share_run(R.src + 4 * e4, R.stride, p0, p1);
+    g[0] = acc.x; g[1] = acc.y; g[2] = acc.z; g[3] = acc.w;
+    ft_lane_shares_meet(g, Q);
+    if (lw == 0) wsum[wv][q] = make_float4(g[0], g[1], g[2], g[3]);
+    __syncthreads();
+    if ((int)threadIdx.x >= Q || !on) return;
+    ft_wave_shares_meet(g, wsum[0][q], wsum[1][q], wsum[2][q], wsum[3][q]);
   }
   const int64_t i = R.beg + 4 * e4;
 #pragma unroll
@@ -1999,6 +2226,36 @@ static int dgrad_build(const ga_fused_dgrad_net& n, int64_t M, int width, int K,
   p.g.M = (int)M; p.g.N = width; p.g.K = K;
   p.H = n.H1; p.ldh = n.ldh; p.X = n.X; p.ldx = n.ldx; p.idx = n.idx; p.in_w = in_w;
   p.wpart = n.wpart;
+  if (n.sum_w.src || n.sum_b.src) {
+    const ga_slab_range* r[2] = {&n.sum_w, &n.sum_b};
+    const ga_slab_range& any = n.sum_w.src ? n.sum_w : n.sum_b;
+    uintptr_t lo = UINTPTR_MAX, hi = 0;
+    for (int i = 0; i < 2; ++i) {
+      if (!r[i]->src) continue;
+      GA_REQUIRE(r[i]->n >= 4 && r[i]->n % 4 == 0 && r[i]->n_part >= 1 &&
+                     r[i]->stride >= r[i]->n && r[i]->stride % 4 == 0 &&
+                     ga_aligned16(r[i]->src) && r[i]->stride == any.stride &&
+                     r[i]->n_part == any.n_part,
+                 "ga_fused_dgrad_wgrad0: bad slab range %d", i);
+      const uintptr_t b = reinterpret_cast<uintptr_t>(r[i]->src);
+      lo = b < lo ? b : lo;
+      const uintptr_t e =
+          b + sizeof(float) * (uintptr_t)((r[i]->n_part - 1) * r[i]->stride + r[i]->n);
+      hi = e > hi ? e : hi;
+    }
+    // (the kernel addresses the ranges with 32-bit byte offsets from the lower one)
+    GA_REQUIRE(hi - lo <= ((uintptr_t)1 << 32),
+               "ga_fused_dgrad_wgrad0: slab ranges further apart than 2^30 floats");
+    p.sum.base = reinterpret_cast<float*>(lo);
+    for (int i = 0; i < 2; ++i) {
+      if (!r[i]->src) continue;
+      p.sum.off[i] = (uint32_t)(r[i]->src - p.sum.base);
+      p.sum.nq[i] = (int)(r[i]->n / 4);
+    }
+    p.sum.stride = any.stride;
+    p.sum.n_part = any.n_part;
+    p.sum.tiles = (int)ga_fused_tiles(M);
+  }
   *flops_out = 2.0 * (double)M * width * ((double)K + in_w);
   return GA_OK;
 }
@@ -2056,7 +2313,7 @@ static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_reduce_net& 
                  n.loss,
              "ga_reduce_regions_adam: null pointer");
   GA_REQUIRE(n.n_regions >= 1 && p.n_regions + n.n_regions <= FT_MAX_REGIONS &&
-                 n.step >= 1 && n.n_lpart >= 1,
+                 n.step >= 1 && n.n_lpart >= 1 && (n.presummed >> n.n_regions) == 0,
              "ga_reduce_regions_adam: bad arguments");
   int64_t v = p.n_virtual;
   for (int k = 0; k < n.n_regions; ++k) {
@@ -2072,6 +2329,9 @@ static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_reduce_net& 
     r.src = regions[k].src;
     r.stride = regions[k].stride; r.n_part = regions[k].n_part;
     r.quads = regions[k].n_part <= 128 ? 64 : 16;
+    r.pre = (n.presummed >> k) & 1u;
+    // (a pre-summed region has a quad per THREAD to move, not per four or sixteen)
+    if (r.pre) r.quads = 256;
     r.vbeg = v;
     r.net = net;
     v += ga_ceil_div(r.n / 4, r.quads);  // workgroups of this region

@@ -259,15 +259,24 @@ struct TileLoader {
   }
 };
 
+// Work of the caller's that rides along with gemm_mainloop's k-steps: issue() right
+// in front of a step's tile loads, consume() behind the barrier that has waited for them
+// (the caller's loads have landed by then too).  The default does nothing.
+struct GemmNoSideWork {
+  __device__ __forceinline__ void issue() {}
+  __device__ __forceinline__ void consume() {}
+};
+
 // The k-loop of one workgroup: global -> registers -> LDS -> MFMA.  FULL selects the
 // mask-free loader (the caller has checked that this workgroup's tile rows are
 // entirely inside the matrices; the last k-step is masked either way).
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool A_KC, bool B_KC, int BKT,
-          bool FULL, int TM, int TN>
+          bool FULL, int TM, int TN, class SideWork = GemmNoSideWork>
 __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, float* lds,
                                               f32x16 (&acc)[TM][TN], float& csum,
                                               bool do_colsum, int m0, int n0,
-                                              int kbeg, int kend, int wm0, int wn0) {
+                                              int kbeg, int kend, int wm0, int wn0,
+                                              SideWork&& side = SideWork()) {
   constexpr int NT = 64 * WAVES_M * WAVES_N;
   constexpr int LDA_S = BM + PAD, LDB_S = BN + PAD, LDK = BKT + PAD;
   constexpr int A_FLOATS = A_KC ? BM * LDK : BKT * LDA_S;
@@ -299,6 +308,10 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, float* lds,
     const bool more = (s + 1 < nk);
     const bool tail = (s + 2 == nk);  // the tile being fetched is the last one
     const int k_next = kbeg + (s + 1) * BKT;
+    // (in FRONT of the tile loads: nothing is in flight here, so whatever the compiler
+    // makes the side work's loads wait for costs nothing; behind them it waited for the
+    // tiles before the MFMAs could start)
+    side.issue();
     if (more) {
       la.rotate();
       lb.rotate();
@@ -372,7 +385,10 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, float* lds,
     if (more) {
       la.store(As, m0, p.M, k_next, kend, tail);
       lb.store(Bs, n0, p.N, k_next, kend, tail);
+      side.consume();
       __syncthreads();
+    } else {
+      side.consume();
     }
   }
 }

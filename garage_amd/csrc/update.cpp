@@ -89,6 +89,24 @@ static int fused_first_layer_on() {
   return g_fused_first_layer;
 }
 
+// The middle layer's split-K weight-gradient slabs are summed inside the data-gradient
+// launch that follows the weight-gradient GEMM (fused_train.hip: FtSlabSummer), and
+// the optimizer launch reads one partial of them instead of `splits`; same bits either
+// way.  0 (or GARAGE_AMD_SLAB_SUM_IN_DGRAD=0 in the environment): the optimizer launch
+// sums them (A/B runs, tests)
+static int g_slab_sum_in_dgrad = -1;
+extern "C" int ga_set_slab_sum_in_dgrad(int on) {
+  g_slab_sum_in_dgrad = on != 0;
+  return 0;
+}
+static int slab_sum_in_dgrad_on() {
+  if (g_slab_sum_in_dgrad < 0) {
+    const char* e = getenv("GARAGE_AMD_SLAB_SUM_IN_DGRAD");
+    g_slab_sum_in_dgrad = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_slab_sum_in_dgrad;
+}
+
 namespace {
 struct FusedPlan {
   bool ok = false;
@@ -316,6 +334,7 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
   // (split-operand experiment: the optimizer launch rewrites the planes of the last
   // hidden layer's weights, the next step's forward launch then needs no plane launch)
   r.pl_beg = 0; r.pl_rows = r.pl_cols = 0;
+  r.presummed = 0;
   if (f.first && L == 3 && r.do_adam && ga_split_bf16_any() && d->dims[2] == 256 &&
       d->dims[1] % 32 == 0) {
     r.pl_beg = d->w_off[1]; r.pl_rows = d->dims[2]; r.pl_cols = d->dims[1];
@@ -346,6 +365,20 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
     g.W2 = a->params + d->w_off[1]; g.ldw = r4(d->dims[1]);
     g.H1 = a->acts + d->act_off[0]; g.ldh = r4(d->dims[1]);
     g.X = a->X; g.ldx = a->ldx; g.idx = idx; g.wpart = s->wpart;
+    g.sum_w = g.sum_b = ga_slab_range{nullptr, 0, 0, 0};
+    if (L == 3 && s->splits > 1 && slab_sum_in_dgrad_on()) {
+      // The middle layer's slabs (regions 2 and 3).  The weight-gradient GEMM that
+      // writes them is the launch right before the data-gradient launch, on the same
+      // stream, in both schedules: ga_mlp_backward_range_f32 in run_minibatch_fused,
+      // ga_wgrad_mid in run_minibatch_merged.  Keep it so.
+      ga_slab_range* sum[2] = {&g.sum_w, &g.sum_b};
+      for (int i = 0; i < 2; ++i) {
+        const ga_fused_region& reg = s->reg[2 + i];
+        *sum[i] = ga_slab_range{a->slabs + reg.beg, (reg.n + 3) & ~(int64_t)3, reg.stride,
+                                reg.n_part};
+        r.presummed |= 1u << (2 + i);
+      }
+    }
   }
   if (L == 3) {  // (layer 1 is THE middle layer)
     ga_wgrad_mid_net& m = s->mid;

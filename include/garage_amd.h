@@ -800,6 +800,12 @@ GA_API int ga_set_fused_first_layer(int on);
  * first layers of 17 .. 20 inputs at 256 units): 1 default, 0 the plain loop (also
  * GARAGE_AMD_PIPELINED_KLOOP=0).  Bit-identical results either way. */
 GA_API int ga_set_pipelined_kloop(int on);
+/* The split-K weight-gradient slabs of the middle layer (two hidden layers, more than
+ * one split) are summed inside the data-gradient launch that follows the
+ * weight-gradient GEMM, in the optimizer launch's own order, and the optimizer launch
+ * reads one partial of them instead of all: 1 default, 0 the optimizer launch sums
+ * them (also GARAGE_AMD_SLAB_SUM_IN_DGRAD=0).  Bit-identical results either way. */
+GA_API int ga_set_slab_sum_in_dgrad(int on);
 /* EXPERIMENT, off by default (also GARAGE_AMD_SPLIT_BF16=1): the k-loops of the fused
  * update kernels that have such an instantiation (256-unit networks, first layer in
  * the kernel) run on v_mfma_f32_32x32x16_bf16 with every fp32 operand split exactly
