@@ -253,6 +253,12 @@ SIGNATURES = {
                                              C.POINTER(EnvRef),
                                              C.POINTER(RecordArgs),
                                              C.POINTER(NormArgs), c_i64, ptr]),
+    'ga_policy_env_step_members_f32': (c_int, [C.POINTER(MlpDesc), ptr,
+                                               C.POINTER(HeadArgs),
+                                               C.POINTER(EnvRef),
+                                               C.POINTER(RecordArgs),
+                                               C.POINTER(NormArgs), c_i64,
+                                               c_i64, c_i64, ptr]),
     'ga_set_fused_env_step': (c_int, [c_int]),
     'ga_rollout_env_steps': (c_int, [C.POINTER(MlpDesc), ptr,
                                      C.POINTER(HeadArgs), C.POINTER(EnvRef),

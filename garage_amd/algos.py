@@ -19,6 +19,7 @@ from garage_amd._dtypes import (DeviceEpisodeBatch, StepType, is_discrete,
 from garage_amd._lib import call, dptr, stream_ptr
 from garage_amd.engine import (HALF_LOG_2PI, center_advantages, gae_scan,
                                pad_rows, reduction_workspace, round4)
+from garage_amd.functions import log_performance, log_performance_host
 from garage_amd.optimizers import OptimizerWrapper, data_parallel_plan
 from garage_amd.policies import GaussianMLPPolicy
 
@@ -1230,4 +1231,157 @@ class TRPO(VPG):
         return loss0
 
 
-__all__ = ['VPG', 'PPO', 'TRPO']
+class CEM:
+    """Cross Entropy Method (``np/algos/cem.py:11-172``) over a population rollout.
+
+    Same constructor keywords, order and defaults, same private state and the
+    same ``np.random`` call order as the reference, whose ``n_samples`` candidate
+    policies are evaluated strictly one after another; here an epoch's candidates
+    are rolled out together by a
+    :class:`~garage_amd.sampler.GpuPopulationSampler` with
+    ``n_members == n_samples`` and the reference's ``_train_once`` is then
+    replayed for them in order.  The distribution arithmetic is host numpy in
+    float64, as the reference writes it; the parameter vector is the policy's
+    ``get_flat_param_values()`` (the reference's torch policies return a
+    ``state_dict``, so its CEM only runs on flat-vector policies).
+
+    Quirks kept because they fix the ``np.random`` call order and the numbers:
+    the first candidate ever is the policy's own parameters; the extra-std decay
+    is driven by ``itr`` (``_sample_params(itr)``), not by the epoch; after
+    ``train`` the policy holds the first candidate of the next epoch, not the
+    mean (``_cur_mean``).
+    """
+
+    def __init__(self,
+                 env_spec,
+                 policy,
+                 sampler,
+                 n_samples,
+                 discount=0.99,
+                 init_std=1,
+                 best_frac=0.05,
+                 extra_std=1.,
+                 extra_decay_time=100):
+        self.policy = policy
+        self.max_episode_length = env_spec.max_episode_length
+
+        self._sampler = sampler
+        if getattr(sampler, 'n_members', n_samples) != n_samples:
+            raise ValueError('CEM evaluates n_samples = {} candidates per epoch; '
+                             'the sampler rolls out {} members'.format(
+                                 n_samples, sampler.n_members))
+
+        self._best_frac = best_frac
+        self._init_std = init_std
+        self._extra_std = extra_std
+        self._extra_decay_time = extra_decay_time
+        self._episode_reward_mean = collections.deque(maxlen=100)
+        self._env_spec = env_spec
+        self._discount = discount
+        self._n_samples = n_samples
+
+        self._cur_std = None
+        self._cur_mean = None
+        self._cur_params = None
+        self._all_returns = None
+        self._all_params = None
+        self._n_best = None
+        self._n_params = None
+
+    def _sample_params(self, epoch):
+        """``cem.py:68-83`` (called with ``itr``)."""
+        extra_var_mult = max(1.0 - epoch / self._extra_decay_time, 0)
+        sample_std = np.sqrt(
+            np.square(self._cur_std) +
+            np.square(self._extra_std) * extra_var_mult)
+        return np.random.standard_normal(
+            self._n_params) * sample_std + self._cur_mean
+
+    def train(self, trainer):
+        """``cem.py:85-120``: per epoch, the candidates ``1 .. n - 1`` are drawn
+        first (the draws the reference makes at the end of the iterations
+        ``itr .. itr + n - 2``), all ``n`` are evaluated in one
+        ``obtain_samples`` of ``trainer._train_args.batch_size`` samples each,
+        and the iterations are replayed in order."""
+        # epoch-wise
+        self._cur_std = self._init_std
+        self._cur_mean = np.asarray(self.policy.get_flat_param_values(),
+                                    dtype=np.float64)
+        # epoch-cycle-wise
+        self._cur_params = self._cur_mean
+        self._all_returns = []
+        self._all_params = [self._cur_mean.copy()]
+        # constant
+        self._n_best = int(self._n_samples * self._best_frac)
+        assert self._n_best >= 1, (
+            'n_samples is too low. Make sure that n_samples * best_frac >= 1')
+        self._n_params = len(self._cur_mean)
+
+        last_return = None
+        for _ in trainer.step_epochs():
+            for i in range(1, self._n_samples):
+                self._all_params.append(
+                    self._sample_params(trainer.step_itr + i - 1).copy())
+            batches = self._sampler.obtain_samples(
+                trainer.step_itr, trainer._train_args.batch_size,
+                np.asarray(self._all_params))
+            if hasattr(trainer, 'total_env_steps'):
+                trainer.total_env_steps += int(sum(
+                    int(sum(b.lengths)) for b in batches))
+            for episodes in batches:
+                trainer.step_episode = episodes
+                last_return = self._train_once(trainer.step_itr, episodes)
+                trainer.step_itr += 1
+        return last_return
+
+    def _log_performance(self, itr, episodes):
+        if hasattr(episodes, 'rewards_dev'):
+            return log_performance(itr, episodes, discount=self._discount)
+        return log_performance_host(itr, episodes, discount=self._discount)
+
+    def _train_once(self, itr, episodes):
+        """``cem.py:122-172`` for the candidate evaluated as iteration ``itr``;
+        the next candidate was drawn before the rollout unless this one closes
+        the epoch."""
+        tab = logger.tabular
+        undiscounted_returns = self._log_performance(itr, episodes)
+        self._episode_reward_mean.extend(undiscounted_returns)
+        tab.record('Extras/EpisodeRewardMean',
+                   np.mean(self._episode_reward_mean))
+        average_return = np.mean(undiscounted_returns)
+
+        epoch = itr // self._n_samples
+        i_sample = itr - epoch * self._n_samples
+        tab.record('Epoch', epoch)
+        tab.record('# Sample', i_sample)
+        rtn = average_return
+        self._all_returns.append(average_return)
+
+        if (itr + 1) % self._n_samples == 0:
+            avg_rtns = np.array(self._all_returns)
+            best_inds = np.argsort(-avg_rtns)[:self._n_best]
+            best_params = np.array(self._all_params)[best_inds]
+
+            # MLE of normal distribution
+            self._cur_mean = best_params.mean(axis=0)
+            self._cur_std = best_params.std(axis=0)
+
+            # Clear for next epoch
+            rtn = max(self._all_returns)
+            self._all_returns.clear()
+            self._all_params.clear()
+
+            # the first candidate of the next epoch (the policy holds it, as
+            # in the reference: its set_param_values(_cur_mean) is overwritten
+            # by this one at once)
+            self._cur_params = self._sample_params(itr)
+            self._all_params.append(self._cur_params.copy())
+            self.policy.set_flat_param_values(self._cur_params)
+        else:
+            self._cur_params = self._all_params[i_sample + 1]
+
+        logger.log(tab)
+        return rtn
+
+
+__all__ = ['VPG', 'PPO', 'TRPO', 'CEM']

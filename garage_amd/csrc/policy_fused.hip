@@ -27,6 +27,7 @@
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
 // CartPole: a template parameter of the kernel) the thread that sampled an env's action
 // also steps it, and a whole rollout is ONE launch with the weights resident on the CU (see the kernel).
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -122,6 +123,11 @@ struct FusedParams {
   // observation buffers (obs / es.seen_next and, with observation normalisation,
   // es.raw_obs / es.raw_next)
   int n_steps;
+  // a population of parameter vectors behind one launch: workgroups
+  // [m * wg_per_member, (m + 1) * wg_per_member) read member m's vector at
+  // params + m * member_stride floats (one policy: stride 0, wg_per_member 1)
+  int wg_per_member;
+  int member_stride;
   long long* dbg;  // developer hook: phase timestamps of workgroup 0
   // GEN kernels only (behind everything the tanh kernels read): the descriptor's
   // network options -- hidden_act in network code, output_act in forward code
@@ -351,6 +357,21 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   const int r16 = lane & 15, kq = lane >> 4;
   const int64_t row0 = (int64_t)blockIdx.x * ROWS;
   const int L = p.net.n_layers;
+  // This workgroup's parameter vector: member blockIdx.x / wg_per_member of a
+  // population launch, p.params itself at member_stride 0.  The member's offset is
+  // computed once (wave-uniform, one SGPR); every read of a parameter goes through
+  // params(), which adds it to p.params behind an empty asm.  Without that the compiler
+  // hoists a 64-bit base, and addresses derived from it, out of the step loop into
+  // SGPRs the streamed kernels do not have (106 in use, hundreds of lane spills): that
+  // form measured 0.9 % below the parent at (512, 512, 512), this one 3 % above
+  // (DESIGN.md section 7).
+  const int member_off =
+      (int)(blockIdx.x / (unsigned)p.wg_per_member) * p.member_stride;
+  auto params = [&]() -> const float* {
+    int off = member_off;
+    asm volatile("" : "+s"(off));
+    return p.params + off;
+  };
   float wreg[TPW][HMAX / 4];
   float bias_r[2][TPW];  // RES: hidden biases of this lane's columns
 #pragma unroll
@@ -361,23 +382,23 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const int ncol = 16 * (wave + 4 * t) + r16;
-        const float b = ncol < p.net.dims[l + 1] ? p.params[p.net.b_off[l] + ncol] : 0.f;
+        const float b = ncol < p.net.dims[l + 1] ? params()[p.net.b_off[l] + ncol] : 0.f;
         if (l == 0) bias_r[0][t] = b;
         else bias_r[1][t] = b;
       }
-    if (tid < p.net.dims[L]) obias[tid] = p.params[p.net.b_off[L - 1] + tid];
+    if (tid < p.net.dims[L]) obias[tid] = params()[p.net.b_off[L - 1] + tid];
     // (the register-resident layer multiplies whole tiles: no stale columns)
     for (int e = tid; e < ROWS * LDA; e += 256) act[0][e] = act[1][e] = 0.f;
     {
       const int K = p.net.dims[0], N = p.net.dims[1];
       WeightStage<256> ws;
-      ws.load(p.params + p.net.w_off[0], (K + 3) & ~3, N, K, 0);
+      ws.load(params() + p.net.w_off[0], (K + 3) & ~3, N, K, 0);
       ws.store(wst, N, K, 0);
     }
     if (L == 3) {
       const int K = p.net.dims[1], N = p.net.dims[2];
       const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.net.w_off[1];
+      const float* W = params() + p.net.w_off[1];
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const int ncol = 16 * (wave + 4 * t) + r16;
@@ -399,7 +420,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     {
       const int K = p.net.dims[L - 1], N = p.net.dims[L];
       const int ldw = (K + 3) & ~3;
-      const float* W = p.params + p.net.w_off[L - 1];
+      const float* W = params() + p.net.w_off[L - 1];
       for (int e = tid; e < N * (ldw / 4); e += 256)
         reinterpret_cast<float4*>(wst + STAGE)[e] = reinterpret_cast<const float4*>(W)[e];
     }
@@ -411,13 +432,13 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
         float* lnp = ln_resident_store();
         if (L >= 2) {
           const int D = p.net.dims[0], ldn = (D + 3) & ~3;
-          const float* g = p.params + p.ln_off[0];
+          const float* g = params() + p.ln_off[0];
           lnp[0 * HMAX + tid] = tid < D ? g[tid] : 0.f;
           lnp[1 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
         }
         if (L == 3) {
           const int D = p.net.dims[1], ldn = (D + 3) & ~3;
-          const float* g = p.params + p.ln_off[1];
+          const float* g = params() + p.ln_off[1];
           lnp[2 * HMAX + tid] = tid < D ? g[tid] : 0.f;
           lnp[3 * HMAX + tid] = tid < D ? g[ldn + tid] : 0.f;
         }
@@ -474,8 +495,8 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   for (int l = 0; l < L - 1; ++l) {
     const int K = p.net.dims[l], N = p.net.dims[l + 1];
     const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.net.w_off[l];
-    const float* bias = p.params + p.net.b_off[l];
+    const float* W = params() + p.net.w_off[l];
+    const float* bias = params() + p.net.b_off[l];
     const int nk = (K + KC - 1) / KC;
     const int n_pad = (N + KC - 1) / KC * KC;
     if constexpr (GEN) {
@@ -486,8 +507,8 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
           ln_rows_w<WIDTH>(act[cur], K, ln_resident_store() + (2 * l) * HMAX,
                            ln_resident_store() + (2 * l + 1) * HMAX);
         else
-          ln_rows_w<WIDTH>(act[cur], K, p.params + p.ln_off[l],
-                           p.params + p.ln_off[l] + ldw);
+          ln_rows_w<WIDTH>(act[cur], K, params() + p.ln_off[l],
+                           params() + p.ln_off[l] + ldw);
         __syncthreads();
       }
     }
@@ -581,8 +602,8 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   {
     const int K = p.net.dims[L - 1], N = p.net.dims[L];
     const int ldw = (K + 3) & ~3;
-    const float* W = p.params + p.net.w_off[L - 1];
-    const float* bias = p.params + p.net.b_off[L - 1];
+    const float* W = params() + p.net.w_off[L - 1];
+    const float* bias = params() + p.net.b_off[L - 1];
     float* wo = wst + (RES ? STAGE : 0);
     if constexpr (!RES)
       for (int e = tid; e < N * (ldw / 4); e += 256)
@@ -638,7 +659,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
   if (tid < ROWS) {
     const int64_t env = row0 + tid;
     if (env < hd.n) {
-      ga_rollout::head_one(hd, head[tid], p.net.dims[L], p.params, env);
+      ga_rollout::head_one(hd, head[tid], p.net.dims[L], params(), env);
       if (p.env_step)
         ended_len = ga_rollout::env_step_one(es, env, pre, hd.action + env * hd.lda);
     }
@@ -840,7 +861,8 @@ template <class Env>
 static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                               const ga_head_args* a,
                               const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
-                              hipStream_t stream);
+                              hipStream_t stream, int64_t n_members = 0,
+                              int64_t member_stride = 0);
 
 static bool g_ps_no_resident = getenv("GARAGE_AMD_ROLLOUT_RESIDENT") &&
                                atoi(getenv("GARAGE_AMD_ROLLOUT_RESIDENT")) == 0;
@@ -873,12 +895,11 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* param
 // (nothing couples envs within a rollout), alternating between `a->obs` and
 // `rec->next_obs` (and the raw pair of `norm`).  `a->action` is what the env is
 // stepped with.
-extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                            const ga_head_args* a, const ga_env_ref* ref,
-                                            const ga_record_args* rec,
-                                            const ga_norm_args* norm, int64_t n_steps,
-                                            ga_stream_t stream) {
-  const char* who = "ga_policy_env_step_fused_f32";
+static int policy_env_step(const char* who, const ga_mlp_desc* d, const float* params,
+                           const ga_head_args* a, const ga_env_ref* ref,
+                           const ga_record_args* rec, const ga_norm_args* norm,
+                           int64_t n_steps, int64_t n_members, int64_t member_stride,
+                           ga_stream_t stream) {
   return ga_visit_env(ref, who, [&](auto* env) {
     GA_REQUIRE(a && rec, "%s: null pointer", who);
     GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
@@ -891,8 +912,66 @@ extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* p
     GA_REQUIRE(es.e.n == a->n, "%s: env count mismatch", who);
     GA_REQUIRE(es.p.col == a->col && es.p.col + n_steps <= es.p.Tcap,
                "%s: record columns do not match the policy's", who);
-    return policy_step_launch(d, params, a, &es, n_steps, (hipStream_t)stream);
+    return policy_step_launch(d, params, a, &es, n_steps, (hipStream_t)stream, n_members,
+                              member_stride);
   });
+}
+
+extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
+                                            const ga_head_args* a, const ga_env_ref* ref,
+                                            const ga_record_args* rec,
+                                            const ga_norm_args* norm, int64_t n_steps,
+                                            ga_stream_t stream) {
+  return policy_env_step("ga_policy_env_step_fused_f32", d, params, a, ref, rec, norm,
+                         n_steps, 0, 0, stream);
+}
+
+// floats of the parameter vector `d` describes: the end of its last block
+static int64_t desc_flat_size(const ga_mlp_desc* d) {
+  int64_t end = 4;
+  for (int l = 0; l < d->n_layers; ++l) {
+    end = std::max(end, d->w_off[l] + (int64_t)d->dims[l + 1] * ((d->dims[l] + 3) & ~3));
+    end = std::max(end, d->b_off[l] + ((d->dims[l + 1] + 3) & ~3));
+    if (d->layer_norm && l + 1 < d->n_layers)
+      end = std::max(end, d->ln_off[l] + 2 * ((d->dims[l] + 3) & ~3));
+  }
+  return end;
+}
+
+// The same launch over a population: member m's envs [m g, (m + 1) g), g = n /
+// n_members, are stepped by the parameter vector at params + m * member_stride.  Every
+// check precedes the first device call.
+extern "C" int ga_policy_env_step_members_f32(const ga_mlp_desc* d, const float* params,
+                                              const ga_head_args* a, const ga_env_ref* ref,
+                                              const ga_record_args* rec,
+                                              const ga_norm_args* norm, int64_t n_steps,
+                                              int64_t n_members, int64_t member_stride,
+                                              ga_stream_t stream) {
+  const char* who = "ga_policy_env_step_members_f32";
+  GA_REQUIRE(d && params && a && ref && rec, "%s: null pointer", who);
+  GA_REQUIRE(n_members >= 1, "%s: n_members must be at least 1", who);
+  GA_REQUIRE(a->n > 0 && a->n % n_members == 0,
+             "%s: %lld envs do not split into %lld members", who, (long long)a->n,
+             (long long)n_members);
+  // (one member is the single-policy launch, whose last workgroup may be ragged)
+  GA_REQUIRE(n_members == 1 || a->n / n_members % ROWS == 0,
+             "%s: %lld envs per member are not a multiple of the %d rows of a workgroup",
+             who, (long long)(a->n / n_members), ROWS);
+  GA_REQUIRE(ga_policy_step_wide_supported(d),
+             "%s: network not supported by the fused step", who);
+  GA_REQUIRE(member_stride % 4 == 0 && member_stride >= desc_flat_size(d),
+             "%s: member_stride %lld is not a multiple of 4 floats or is smaller than "
+             "the %lld floats of a parameter vector",
+             who, (long long)member_stride, (long long)desc_flat_size(d));
+  // (the kernel adds a member's offset as a 32-bit count of floats)
+  GA_REQUIRE((n_members - 1) * member_stride + desc_flat_size(d) < (1ll << 31),
+             "%s: %lld members x %lld floats exceed 2^31 floats", who,
+             (long long)n_members, (long long)member_stride);
+  GA_REQUIRE(!a->noise, "%s: teacher-forced noise is not supported", who);
+  GA_REQUIRE(!(norm && norm->act_low),
+             "%s: the action rescale is its own launch (not supported)", who);
+  return policy_env_step(who, d, params, a, ref, rec, norm, n_steps, n_members,
+                         member_stride, stream);
 }
 
 template <int WIDTH, bool RES, class Env>
@@ -910,7 +989,8 @@ template <class Env>
 static int policy_step_launch(const ga_mlp_desc* d, const float* params,
                               const ga_head_args* a,
                               const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
-                              hipStream_t stream) {
+                              hipStream_t stream, int64_t n_members,
+                              int64_t member_stride) {
   GA_REQUIRE(d && params && a, "ga_policy_step_fused_f32: null pointer");
   // every descriptor the old predicate accepts keeps the kernel it had
   const bool wide = !ga_policy_step_fused_supported(d);
@@ -937,15 +1017,21 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   for (int i = 0; i < 8; ++i) p.ln_off[i] = d->ln_off[i];
   p.env_step = es != nullptr;
   p.n_steps = (int)n_steps;
+  const dim3 grid((unsigned)ga_ceil_div(a->n, ROWS));
+  // n_members > 1 (ga_policy_env_step_members_f32, which checked the split): member m
+  // owns the grid.x / n_members workgroups of its envs
+  p.wg_per_member = n_members > 1 ? (int)(grid.x / n_members) : 1;
+  p.member_stride = n_members > 1 ? (int)member_stride : 0;
   if (es) p.es = *es;
   else memset(&p.es, 0, sizeof(p.es));
-  const dim3 grid((unsigned)ga_ceil_div(a->n, ROWS));
   // a whole rollout in one launch keeps the weights on the CU (see the kernel)
   const bool resident = n_steps > 1 && d->dims[0] <= KC &&
                         (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
   // the tanh / linear-output / no-LayerNorm network keeps the kernel it always had
   const bool general = d->hidden_act != 0 || d->output_act != 0 || d->layer_norm;
   // every descriptor the old predicate accepts runs at WIDTH = HMAX
+  // (the population entry point counts its rollouts as kind 13 whatever the kernel)
+  if (n_members >= 1 && n_steps > 1 && (wide || !resident)) ga_prof_count(GA_PROF_ROLLOUT);
   if (wide) {
     if (n_steps > 1) ga_prof_count(GA_PROF_ROLLOUT_WIDE);
     step_kernel_launch<WMAX, false>(general, grid, stream, p);

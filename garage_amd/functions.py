@@ -135,6 +135,32 @@ def log_performance(itr, batch, discount, prefix='Evaluation', returns=None):
     return list(und)
 
 
+def log_performance_host(itr, batch, discount, prefix='Evaluation'):
+    """:func:`log_performance` of a HOST batch with the reference's own host
+    arithmetic (``_functions.py:246-260``: per episode ``sum(rewards)``, the
+    first element of ``discount_cumsum`` and whether a step is ``TERMINAL``), for
+    callers whose episodes never were on the device."""
+    rewards = np.asarray(batch.rewards)
+    types = step_types_as_uint8(batch.step_types)
+    und, disc, term, success = [], [], [], []
+    start = 0
+    for length in np.asarray(batch.lengths, dtype=np.int64):
+        r = rewards[start:start + length]
+        und.append(sum(r))
+        ret = 0.0
+        for x in r[::-1]:
+            ret = float(x) + discount * ret
+        disc.append(ret)
+        term.append(float((types[start:start + length] ==
+                           int(StepType.TERMINAL)).any()))
+        if 'success' in batch.env_infos:
+            success.append(float(np.asarray(
+                batch.env_infos['success'][start:start + length]).any()))
+        start += length
+    _record_rows(itr, prefix, und, disc, term, success or None)
+    return und
+
+
 def log_multitask_performance(itr, batch, discount, name_map=None):
     """``_functions.py:177-230``: one block of rows per task plus ``Average/``.
 

@@ -201,6 +201,54 @@ class _GaussianMLP:
             out.append((self._prefix + key, view))
         return out
 
+    # -- flat parameter vectors (population rollouts, CEM) ---------------------
+    def _flat_index(self):
+        """Position in the padded ``FlatMLP`` buffer of every element of the
+        compact vector (``parameters()`` order, each tensor row-major): built
+        once, from ``FlatMLP.named_views`` over a buffer of positions."""
+        idx = getattr(self, '_flat_idx', None)
+        if idx is None:
+            pos = torch.arange(self.net.n_flat, dtype=torch.int64)
+            views = self.net.named_views(pos)
+            if not self._learn_std:
+                views = views[1:]
+            idx = torch.cat([v.reshape(-1) for _, v in views])
+            self._flat_idx = idx = idx.to(self.device)
+        return idx
+
+    def get_flat_param_values(self):
+        """The trainable parameters as one compact float32 vector, in
+        ``parameters()`` order (what the reference's flat-vector policies
+        return from ``get_param_values``; the padding of the device layout is
+        left out)."""
+        return self.net.params[self._flat_index()].cpu().numpy()
+
+    def set_flat_param_values(self, vec):
+        idx = self._flat_index()
+        vec = torch.as_tensor(np.asarray(vec, dtype=np.float32).reshape(-1))
+        if vec.numel() != idx.numel():
+            raise ValueError('flat parameter vector of {} values given to a '
+                             'policy with {}'.format(vec.numel(), idx.numel()))
+        self.net.params[idx] = vec.to(self.device)
+
+    def pack_members(self, vectors):
+        """``(M, P)`` compact vectors -> ``(M, n_flat)`` device tensor, every
+        row one policy in the ``FlatMLP`` layout (what
+        ``GpuPopulationSampler.obtain_samples`` rolls out).  Padding slots are
+        zero -- padded columns feed the GEMMs -- and where the std is not
+        learned every member carries this policy's own log-std in slot 0."""
+        idx = self._flat_index()
+        vectors = torch.as_tensor(np.asarray(vectors, dtype=np.float32))
+        if vectors.dim() != 2 or vectors.shape[1] != idx.numel():
+            raise ValueError('pack_members needs an (M, {}) array, got {}'.format(
+                idx.numel(), tuple(vectors.shape)))
+        out = torch.zeros(vectors.shape[0], self.net.n_flat,
+                          dtype=torch.float32, device=self.device)
+        out[:, idx] = vectors.to(self.device)
+        if not self._learn_std:
+            out[:, 0] = self.net.params[0]
+        return out
+
     def get_param_values(self):
         return self.state_dict()
 
@@ -320,7 +368,7 @@ class _GaussianMLP:
     # -- pickling (Trainer snapshots cloudpickle the algo, trainer.py:263-293)
     def __getstate__(self):
         state = {k: v for k, v in self.__dict__.items()
-                 if k not in ('net', 'device')}
+                 if k not in ('net', 'device', '_flat_idx')}
         state['_hidden_sizes'] = self.net.hidden_sizes
         state['_hidden_act'] = self.net.hidden_act
         state['_output_act'] = self.net.output_act

@@ -19,7 +19,8 @@ from garage_amd import _lib
 from garage_amd._dtypes import DeviceEpisodeBatch, EpisodeBatch, is_discrete
 from garage_amd._lib import call, dptr, stream_ptr
 from garage_amd.engine import require_gpu, round4
-from garage_amd.envs import HostVecEnv, VecEnv
+from garage_amd.envs import (HostVecEnv, NormalizedVecEnv, VecEnv,
+                             _DeviceVecEnv)
 
 
 def _identity(value):
@@ -248,11 +249,14 @@ class GpuVecWorker:
         self._needs_env_reset = True
 
     # -- rollout buffers ------------------------------------------------------
-    def _alloc_buffers(self, num_samples):
+    def _alloc_buffers(self, num_samples, n_share=None):
+        """Rollout buffers of all the envs; ``n_share``: how many of them work
+        towards one ``num_samples`` target (default: all; a population member's
+        envs)."""
         env, n = self.env, self._n_envs
         P = int(self._max_episode_length)
         # the last step t* satisfies t* <= ceil(num_samples / n) + P - 2
-        tcap = -(-int(num_samples) // n) + P - 1
+        tcap = -(-int(num_samples) // (n_share or n)) + P - 1
         tcap = round4(max(tcap, 1))
         if tcap > 65535 * 4:
             raise ValueError('rollout too long for one obtain_samples call')
@@ -455,9 +459,29 @@ class GpuVecWorker:
             col += 1
         return self._pack(b, col)
 
-    def _pack(self, b, n_steps, first_step=0):
-        """Episodes that ended in columns ``[first_step, n_steps)`` -> batch."""
-        dev, n, tcap = self.device, self._n_envs, b['Tcap']
+    @staticmethod
+    def _env_rows(b, lo, hi, step_eps):
+        """The rollout buffers of the envs ``[lo, hi)`` alone (views), with the
+        episodes THEY finished per column (``step_eps``, counted from their
+        ``tail`` rows by the caller)."""
+        out = dict(b)
+        for k in ('obs', 'act', 'head', 'lastobs', 'rew', 'st', 'tail'):
+            if b[k] is not None:
+                out[k] = b[k][lo:hi]
+        out['dev_infos'] = {k: v[lo:hi] for k, v in b['dev_infos'].items()}
+        out['step_eps'] = step_eps
+        return out
+
+    def _pack(self, b, n_steps, first_step=0, member=None):
+        """Episodes that ended in columns ``[first_step, n_steps)`` -> batch; with
+        ``member = (lo, hi, step_eps, log_std)`` those of the envs ``[lo, hi)``
+        only: a population member's, with its own episode counts per column (a
+        host tensor) and its own clamped log-std."""
+        lo, hi, log_std = 0, self._n_envs, None
+        if member is not None:
+            lo, hi, step_eps, log_std = member
+            b = self._env_rows(b, lo, hi, step_eps)
+        dev, n, tcap = self.device, hi - lo, b['Tcap']
         step_eps = b['step_eps'][:n_steps].cpu().numpy().astype(np.int64)
         step_eps[:first_step] = 0
         ep_base = np.concatenate([[0], np.cumsum(step_eps)[:-1]])
@@ -502,22 +526,26 @@ class GpuVecWorker:
         gaussian = pol.kind == 'gaussian'
         env_infos, episode_infos = self._device_infos(
             b, src, ep_env, ep_end, self._packed_env_infos(b, src, tcap),
-            self._packed_episode_infos(b, ep_env, ep_end))
+            self._packed_episode_infos(b, ep_env, ep_end), env0=lo)
+        if gaussian and log_std is None:
+            log_std = pol.clamped_log_std()
         return DeviceEpisodeBatch(
             self.env.spec, lengths=lengths, obs_dev=obs, last_obs_dev=last,
             actions_dev=act, rewards_dev=rew, step_types_dev=st,
             ep_off_dev=off_dev, head_dev=head,
             head_name='mean' if gaussian else 'prob',
-            log_std=pol.clamped_log_std() if gaussian else None,
+            log_std=log_std if gaussian else None,
             discrete=is_discrete(self.env.spec.action_space),
             env_infos=env_infos, episode_infos=episode_infos)
 
-    def _device_infos(self, b, src, ep_env, ep_end, env_infos, episode_infos):
+    def _device_infos(self, b, src, ep_env, ep_end, env_infos, episode_infos,
+                      env0=0):
         """Adds the env_infos a device env batch recorded (gathered by the
         samples' cells ``src``), the keys the batch derives from them on the
         host, and its episode_infos (by member ``ep_env``; a batch may ask for
         a recorded env_info at each episode's or fragment's last cell
-        ``(ep_env, ep_end)``, gathered only then)."""
+        ``(ep_env, ep_end)``, gathered only then).  ``env0``: the batch member
+        that row 0 of ``b`` belongs to."""
         specs, s = self.env.env_info_specs, stream_ptr()
 
         def gather(key, idx):
@@ -536,7 +564,8 @@ class GpuVecWorker:
             env_infos[key] = gather(key, src)
         if b['dev_infos']:
             self.env.finish_env_infos(env_infos)
-        episode_infos.update(self.env.episode_infos_of(ep_env, info_at_end))
+        episode_infos.update(self.env.episode_infos_of(
+            ep_env + env0 if env0 else ep_env, info_at_end))
         return env_infos, episode_infos
 
     @staticmethod
@@ -946,5 +975,192 @@ class GpuVecSampler:
                 w._needs_env_reset = False  # the env came back with its state
 
 
+class GpuPopulationSampler:
+    """Rolls out a POPULATION of policies in one launch per chunk of steps.
+
+    ``env`` is one device :class:`~garage_amd.envs.VecEnv` of ``n_members * g``
+    envs (optionally inside :class:`~garage_amd.envs.NormalizedVecEnv` for
+    observation / reward statistics); member ``m`` owns the envs
+    ``[m * g, (m + 1) * g)`` and steps them with its own parameter vector
+    (``ga_policy_env_step_members_f32``).  ``agent`` is the template policy:
+    network shape, head options and -- where the std is not learned -- the
+    log-std every member uses.  There is no reference counterpart: its samplers
+    give each worker its own ``agent_update`` and step them one after another.
+
+    A host env, ``noise_fn``, an action-rescaling ``NormalizedVecEnv`` or a
+    network the fused step does not take raise here; nothing falls back to the
+    stepwise path.
+    """
+
+    def __init__(self, agent, env, *, n_members, max_episode_length, seed=None,
+                 worker_args=None):
+        self._agent = agent
+        self._n_members = int(n_members)
+        if self._n_members < 1:
+            raise ValueError('n_members must be at least 1')
+        self._max_episode_length = max_episode_length
+        self._seed = seed
+        self._worker_args = dict(worker_args or {})
+        if self._worker_args.get('noise_fn') is not None:
+            raise ValueError('GpuPopulationSampler: noise_fn (teacher-forced '
+                             'noise) is per step and per policy; the '
+                             'population rollout draws its noise on the device')
+        if not self._worker_args.get('fused_policy_step', True):
+            raise ValueError('GpuPopulationSampler: the population rollout IS '
+                             'the fused policy step (fused_policy_step=False)')
+        self._worker_args.pop('n_envs', None)
+        self._check_env(env)
+        lib, desc = _lib.load(), C.byref(agent.net._desc)
+        if not lib.ga_policy_step_wide_supported(desc):
+            raise ValueError('GpuPopulationSampler: the fused rollout step does '
+                             'not take this network (layer inputs up to 512, '
+                             'outputs up to 32)')
+        self._env = env
+        self._build_worker()
+        self.total_env_steps = 0
+
+    def _check_env(self, env):
+        inner = env._env if type(env) is NormalizedVecEnv else env
+        if not isinstance(inner, _DeviceVecEnv):
+            raise TypeError('GpuPopulationSampler needs a device env batch '
+                            '(a host env steps on the CPU, one policy at a '
+                            'time); got {!r}'.format(type(inner).__name__))
+        if type(env) is NormalizedVecEnv and env._act_low is not None:
+            raise ValueError('GpuPopulationSampler: this NormalizedVecEnv '
+                             'rescales actions, which is a launch of its own '
+                             'between policy and env; declare the action space '
+                             'unbounded or wrap the statistics only')
+        if env.n_envs % self._n_members:
+            raise ValueError('{} envs do not split into {} members'.format(
+                env.n_envs, self._n_members))
+
+    def _build_worker(self):
+        self._worker = GpuVecWorker(
+            seed=self._seed, max_episode_length=self._max_episode_length,
+            worker_number=0, n_envs=self._env.n_envs, **self._worker_args)
+        self._worker.update_agent(self._agent)
+        self._worker.update_env(self._env)
+
+    n_members = property(lambda self: self._n_members)
+
+    def start_worker(self):
+        """No-op, as in ``sampler/sampler.py``."""
+
+    def _packed(self, member_params):
+        """``pack_members``' tensor as it is, anything else through it."""
+        net, M = self._agent.net, self._n_members
+        if torch.is_tensor(member_params) and member_params.is_cuda:
+            p = member_params
+            if (p.dtype != torch.float32 or p.dim() != 2 or p.stride(1) != 1
+                    or p.shape != (M, net.n_flat)):
+                raise ValueError(
+                    'member_params on the device must be pack_members\' '
+                    '({}, {}) float32 tensor, got {}'.format(
+                        M, net.n_flat, tuple(p.shape)))
+            return p
+        vectors = np.asarray(member_params)
+        if vectors.ndim != 2 or vectors.shape[0] != M:
+            raise ValueError('member_params needs one row per member ({}), got '
+                             'shape {}'.format(M, vectors.shape))
+        return self._agent.pack_members(vectors)
+
+    def _steps(self, b, col, k, params):
+        """``k`` rollout steps of every member into columns ``[col, col + k)``:
+        one launch."""
+        w = self._worker
+        env = w.env
+        inner, norm = env, None
+        if type(env) is NormalizedVecEnv:  # statistics fused into the env step
+            inner, norm = env._env, env.norm_args()
+            if norm.normalize_obs:
+                norm.raw_obs = inner.obs.data_ptr()
+                norm.raw_next_obs = inner.next_obs.data_ptr()
+        env_ref, _keepalive = inner.native_env_ref(b['dev_infos'])
+        a = w._head_args(b, col, True)
+        r = w._record_args(b, col)
+        call('ga_policy_env_step_members_f32', C.byref(self._agent.net._desc),
+             dptr(params), C.byref(a), C.byref(env_ref), C.byref(r),
+             None if norm is None else C.byref(norm), k, self._n_members,
+             params.stride(0), stream_ptr())
+        if k % 2:
+            env.advance()
+        w._global_step += k
+
+    def obtain_samples(self, itr, num_samples, member_params, env_update=None):
+        """One :class:`~garage_amd._dtypes.DeviceEpisodeBatch` per member: the
+        episodes a lone ``GpuVecWorker`` of the member's ``g`` envs with the
+        member's parameters returns from ``rollout_samples(num_samples)`` --
+        those completed before the first column ``c_m`` at which the member's
+        completed episodes hold ``>= num_samples`` steps.  ``member_params``:
+        what ``policy.pack_members`` returns, or an ``(M, P)`` array of compact
+        vectors."""
+        del itr
+        w = self._worker
+        if env_update is not None:
+            w.update_env(env_update)
+            self._check_env(w.env)
+            self._env = w.env
+        w._needs_agent_reset = True  # every call brings new parameters
+        params = self._packed(member_params)
+        w._start()
+        M, g = self._n_members, w._n_envs // self._n_members
+        num_samples = max(int(num_samples), 1)
+        b = w._alloc_buffers(num_samples, n_share=g)
+        tcap = b['Tcap']
+        # no member can be done before step ceil(num_samples / g): one launch
+        # without a host check; after it, as many steps at a time as the member
+        # that is furthest behind needs at the very least
+        col, k = 0, min(-(-num_samples // g), tcap)
+        while True:
+            self._steps(b, col, k, params)
+            col += k
+            # per member and column: samples and episodes completed there
+            ended = b['tail'][:, :col].to(torch.int32).reshape(M, g, col)
+            host = torch.stack([torch.cumsum(ended.sum(1), 1),
+                                (ended != 0).sum(1)]).cpu()
+            done, eps = host[0].numpy(), host[1].to(torch.int32)  # (M, col)
+            if (done[:, -1] >= num_samples).all():
+                break
+            if col >= tcap:
+                raise RuntimeError('rollout buffer exhausted: an environment '
+                                   'ran past max_episode_length')
+            short = int(num_samples - done[:, -1].min())
+            k = min(-(-short // g), tcap - col)
+        # c_m: the columns a member keeps stepping past it are dropped here
+        c = (done >= num_samples).argmax(1) + 1
+        pol = self._agent
+        log_std = [None] * M
+        if pol.kind == 'gaussian':
+            raw = params[:, 0].cpu().numpy()
+            log_std = [pol.log_std_of(float(v))[0] for v in raw]
+        batches = [w._pack(b, int(c[m]), member=(m * g, (m + 1) * g, eps[m],
+                                                 log_std[m]))
+                   for m in range(M)]
+        self.total_env_steps += int(sum(int(sum(x.lengths)) for x in batches))
+        return batches
+
+    def shutdown_worker(self):
+        self._worker.shutdown()
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        w = state.pop('_worker')
+        # (as GpuVecSampler: the Philox step counter and the episodes in flight)
+        state['_worker_state'] = dict(
+            global_step=w._global_step,
+            ep_t=None if w._ep_t is None else w._ep_t.cpu().numpy())
+        return state
+
+    def __setstate__(self, state):
+        saved = state.pop('_worker_state')
+        self.__dict__.update(state)
+        self._build_worker()
+        self._worker._global_step = saved['global_step']
+        if saved['ep_t'] is not None:
+            self._worker._ep_t = torch.from_numpy(saved['ep_t']).to(
+                self._worker.device)
+            self._worker._needs_env_reset = False
+
+
 __all__ = ['WorkerFactory', 'GpuVecWorker', 'GpuFragmentWorker',
-           'GpuVecSampler']
+           'GpuVecSampler', 'GpuPopulationSampler']

@@ -671,6 +671,25 @@ GA_API int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* param
                                         const ga_head_args* head, const ga_env_ref* env,
                                         const ga_record_args* rec, const ga_norm_args* norm,
                                         int64_t n_steps, ga_stream_t stream);
+/* The same launch behind a POPULATION of parameter vectors: member m (0 <= m <
+ * n_members) owns the envs [m g, (m + 1) g), g = head->n / n_members, and its
+ * workgroups read every weight, bias, LayerNorm gain and the Gaussian head's log-std
+ * from params + m * member_stride (floats; each vector in the layout `d` describes).
+ * Nothing else differs: one env batch, one set of rollout buffers, Philox counters by
+ * env id.  Refused before any launch (negative return, ga_last_error): n_members < 1;
+ * head->n not a multiple of n_members; with n_members > 1, g not a multiple of the 16
+ * envs a workgroup owns; member_stride not a multiple of 4 or smaller than the
+ * vector `d` describes; 2^31 floats or more up to the last member's end; head->noise;
+ * norm->act_low (the action rescale is its own launch); a network the fused step does
+ * not take.  n_members == 1 is
+ * ga_policy_env_step_fused_f32.  ga_launch_count(13) counts every call with
+ * n_steps > 1 once. */
+GA_API int ga_policy_env_step_members_f32(const ga_mlp_desc* d, const float* params,
+                                          const ga_head_args* head, const ga_env_ref* env,
+                                          const ga_record_args* rec,
+                                          const ga_norm_args* norm, int64_t n_steps,
+                                          int64_t n_members, int64_t member_stride,
+                                          ga_stream_t stream);
 /* 1 (default): ga_rollout_env_steps takes that launch (unless actions are
  * rescaled between policy and env); 0: policy step and env step as two launches. */
 GA_API int ga_set_fused_env_step(int on);

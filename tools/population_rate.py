@@ -1,0 +1,148 @@
+"""Env-steps per second of a POPULATION rollout: one
+``GpuPopulationSampler.obtain_samples`` over ``members`` policies x ``g``
+CartPole envs each (default 64 x 64, categorical MLP(64, 64), T = 128 steps:
+``num_samples = g * T``, ``max_episode_length = T``), against
+
+- ``sequential``: ``members`` consecutive single-policy ``rollout_samples`` calls
+  on ``g`` envs each, ``set_flat_param_values`` between them -- what scoring
+  the candidates one after another costs -- and
+- ``single``: one single-policy rollout over all ``members * g`` envs, the
+  ceiling (same launch, one parameter vector, one packing).
+
+    python tools/population_rate.py [--members 64] [--g 64] [--T 128] [--reps 7]
+
+The three take turns within each repetition; the first repetition warms up.
+Prints one JSON line per row -- the median over ``reps`` of (env steps taken) /
+(wall time, ended by a device synchronise) -- then the ratios, then where the
+population call's time goes: the launches (first chunk and the rest, to their
+completion), the host checks between them and the per-member packing.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--members', type=int, default=64)
+    ap.add_argument('--g', type=int, default=64)
+    ap.add_argument('--T', type=int, default=128)
+    ap.add_argument('--reps', type=int, default=7)
+    a = ap.parse_args()
+    M, g, T = a.members, a.g, a.T
+    n, num = M * g, g * T
+
+    from garage_amd.envs import CartPoleVecEnv
+    from garage_amd.policies import CategoricalMLPPolicy
+    from garage_amd.sampler import (GpuPopulationSampler, GpuVecSampler,
+                                    GpuVecWorker)
+    torch.manual_seed(0)
+    env = CartPoleVecEnv(n, max_episode_length=T, seed=1)
+    pol = CategoricalMLPPolicy(env.spec, hidden_sizes=(64, 64))
+    base = pol.get_flat_param_values()
+    rng = np.random.RandomState(0)
+    vectors = base + 0.1 * rng.randn(M, base.size).astype(np.float32)
+    pop = GpuPopulationSampler(pol, env, n_members=M, max_episode_length=T,
+                               seed=1)
+    packed = pol.pack_members(vectors)
+
+    def single_sampler(envs):
+        e = CartPoleVecEnv(envs, max_episode_length=T, seed=1)
+        p = CategoricalMLPPolicy(e.spec, hidden_sizes=(64, 64))
+        s = GpuVecSampler(p, e, max_episode_length=T, n_workers=1,
+                          worker_class=GpuVecWorker, seed=1,
+                          worker_args=dict(n_envs=envs))
+        return s, p
+
+    seq, seq_pol = single_sampler(g)
+    one, _ = single_sampler(n)
+
+    def run_population(r):
+        w = pop._worker
+        step0 = w._global_step
+        pop.obtain_samples(r, num, packed)
+        return n * (w._global_step - step0)
+
+    def run_sequential(r):
+        w = seq._workers[0]
+        step0 = w._global_step
+        for m in range(M):
+            seq_pol.set_flat_param_values(vectors[m])
+            w._needs_agent_reset = True
+            w.rollout_samples(num)
+        return g * (w._global_step - step0)
+
+    def run_single(r):
+        w = one._workers[0]
+        step0 = w._global_step
+        w._needs_agent_reset = True
+        w.rollout_samples(n * T)
+        return n * (w._global_step - step0)
+
+    rows = dict(population=run_population, sequential=run_sequential,
+                single=run_single)
+    rates = {k: [] for k in rows}
+    for r in range(a.reps + 1):
+        for k, fn in rows.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            steps = fn(r)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if r:
+                rates[k].append(steps / dt)
+    med = {k: float(np.median(v)) for k, v in rates.items()}
+    for k in rows:
+        print(json.dumps(dict(row=k, members=M, envs_per_member=g, T=T,
+                              hidden=[64, 64], env_steps_per_s=med[k],
+                              min=float(np.min(rates[k])),
+                              max=float(np.max(rates[k])))))
+    print(json.dumps(dict(
+        population_over_sequential=med['population'] / med['sequential'],
+        population_over_single=med['population'] / med['single'])))
+
+    # where one population call spends its time (a synchronise after every
+    # part, so the parts add up to more than the untimed call)
+    parts = dict(first_launch=0.0, later_launches=0.0, host_checks=0.0,
+                 packing=0.0)
+    w = pop._worker
+    real_steps, real_pack = pop._steps, w._pack
+    state = dict(calls=0, last=None)
+
+    def timed(key, fn, *args, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if state['last'] is not None:
+            parts['host_checks'] += t0 - state['last']
+        out = fn(*args, **kw)
+        torch.cuda.synchronize()
+        state['last'] = time.perf_counter()
+        parts[key] += state['last'] - t0
+        return out
+
+    def steps(*args):
+        state['calls'] += 1
+        return timed('first_launch' if state['calls'] == 1
+                     else 'later_launches', real_steps, *args)
+
+    pop._steps = steps
+    w._pack = lambda *args, **kw: timed('packing', real_pack, *args, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pop.obtain_samples(0, num, packed)
+    torch.cuda.synchronize()
+    total = time.perf_counter() - t0
+    pop._steps, w._pack = real_steps, real_pack
+    print(json.dumps(dict(breakdown_ms={k: 1e3 * v for k, v in parts.items()},
+                          total_ms=1e3 * total, launches=state['calls'])))
+
+
+if __name__ == '__main__':
+    main()
