@@ -630,3 +630,33 @@ class DeviceEpisodeBatch(EpisodeBatch):
                             env_infos=dict(self.env_infos),
                             agent_infos=self.agent_infos,
                             step_types=self.step_types, lengths=self.lengths)
+
+
+class EpisodeStatistics:
+    """What ``log_performance`` (``_functions.py:233-275``) reduces a batch of
+    ``N`` episodes to, for callers that score episodes and read nothing else
+    (``GpuPopulationSampler.obtain_statistics``): per episode its length, the
+    sum of its rewards, the first element of its discounted return under
+    ``discount``, whether a step is ``StepType.TERMINAL`` and -- ``None`` when
+    the env records no ``success`` -- whether a step reported success."""
+
+    def __init__(self, lengths, undiscounted_returns, discounted_returns,
+                 terminated, success=None, discount=None):
+        f64 = np.float64
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self.undiscounted_returns = np.asarray(undiscounted_returns, dtype=f64)
+        self.discounted_returns = np.asarray(discounted_returns, dtype=f64)
+        self.terminated = np.asarray(terminated, dtype=f64)
+        self.success = (None if success is None else
+                        np.asarray(success, dtype=f64))
+        self.discount = discount
+        n = self.lengths.shape
+        for name in ('undiscounted_returns', 'discounted_returns',
+                     'terminated', 'success'):
+            arr = getattr(self, name)
+            if arr is not None and arr.shape != n:
+                raise ValueError('EpisodeStatistics: {} has shape {}, lengths '
+                                 '{}'.format(name, arr.shape, n))
+
+    def __len__(self):
+        return int(self.lengths.shape[0])

@@ -274,6 +274,12 @@ SIGNATURES = {
     'ga_gather_u8': (c_int, [ptr, ptr, c_i64, ptr, ptr]),
     'ga_permutation_i32': (c_int, [c_i64, c_u64, ptr, ptr]),
     'ga_episode_sums_f32': (c_int, [ptr, ptr, c_i64, ptr, ptr]),
+    'ga_member_progress': (c_int, [ptr, c_i64, c_i64, c_i64, c_i64, c_i64, ptr,
+                                   ptr, ptr]),
+    'ga_member_episode_statistics': (c_int, [ptr, ptr, ptr, ptr, c_i64, c_i64,
+                                             c_i64, c_i64, c_i64, c_f64, ptr,
+                                             ptr, c_i64, ptr, ptr, ptr, ptr,
+                                             ptr, ptr]),
     'ga_minibatch_range': (c_i64, [c_i64, c_i64, c_i64, c_int, c_i64,
                                    C.POINTER(c_i64), C.POINTER(c_i64)]),
     'ga_update_epoch': (c_int, [C.POINTER(UpdateArgs), ptr]),

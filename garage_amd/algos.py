@@ -14,12 +14,13 @@ import numpy as np
 import torch
 
 from garage_amd import logger
-from garage_amd._dtypes import (DeviceEpisodeBatch, StepType, is_discrete,
-                                step_types_as_uint8)
+from garage_amd._dtypes import (DeviceEpisodeBatch, EpisodeStatistics,
+                                StepType, is_discrete, step_types_as_uint8)
 from garage_amd._lib import call, dptr, stream_ptr
 from garage_amd.engine import (HALF_LOG_2PI, center_advantages, gae_scan,
                                pad_rows, reduction_workspace, round4)
-from garage_amd.functions import log_performance, log_performance_host
+from garage_amd.functions import (log_performance, log_performance_host,
+                                  log_performance_statistics)
 from garage_amd.optimizers import OptimizerWrapper, data_parallel_plan
 from garage_amd.policies import GaussianMLPPolicy
 
@@ -1301,8 +1302,10 @@ class CEM:
         """``cem.py:85-120``: per epoch, the candidates ``1 .. n - 1`` are drawn
         first (the draws the reference makes at the end of the iterations
         ``itr .. itr + n - 2``), all ``n`` are evaluated in one
-        ``obtain_samples`` of ``trainer._train_args.batch_size`` samples each,
-        and the iterations are replayed in order."""
+        ``obtain_samples`` of ``trainer._train_args.batch_size`` samples each
+        -- in one ``obtain_statistics`` where the sampler has
+        ``statistics_only`` set: the per-episode numbers ``_train_once`` logs,
+        nothing packed -- and the iterations are replayed in order."""
         # epoch-wise
         self._cur_std = self._init_std
         self._cur_mean = np.asarray(self.policy.get_flat_param_values(),
@@ -1322,9 +1325,16 @@ class CEM:
             for i in range(1, self._n_samples):
                 self._all_params.append(
                     self._sample_params(trainer.step_itr + i - 1).copy())
-            batches = self._sampler.obtain_samples(
-                trainer.step_itr, trainer._train_args.batch_size,
-                np.asarray(self._all_params))
+            # a sampler that says so scores the candidates on the device and
+            # returns per-episode statistics instead of batches
+            if getattr(self._sampler, 'statistics_only', False):
+                batches = self._sampler.obtain_statistics(
+                    trainer.step_itr, trainer._train_args.batch_size,
+                    np.asarray(self._all_params), discount=self._discount)
+            else:
+                batches = self._sampler.obtain_samples(
+                    trainer.step_itr, trainer._train_args.batch_size,
+                    np.asarray(self._all_params))
             if hasattr(trainer, 'total_env_steps'):
                 trainer.total_env_steps += int(sum(
                     int(sum(b.lengths)) for b in batches))
@@ -1335,6 +1345,8 @@ class CEM:
         return last_return
 
     def _log_performance(self, itr, episodes):
+        if isinstance(episodes, EpisodeStatistics):
+            return log_performance_statistics(itr, episodes)
         if hasattr(episodes, 'rewards_dev'):
             return log_performance(itr, episodes, discount=self._discount)
         return log_performance_host(itr, episodes, discount=self._discount)

@@ -198,6 +198,157 @@ __global__ __launch_bounds__(256) void episode_sums_kernel(const float* rewards,
   sums[e] = acc;
 }
 
+// ---- a population's score straight from the rollout buffers ---------------------
+// Member m owns the rows [m g, (m + 1) g).  What log_performance
+// (_functions.py:233-275) reduces an episode to is computed where the episode lies:
+// nothing is packed or gathered.
+
+// Inclusive sums of (a, b) over the block's 256 threads; *ta / *tb: the block's totals.
+__device__ __forceinline__ void block_scan2_256(int& a, int& b, int (*smem)[2], int* ta,
+                                                int* tb) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int ua = __shfl_up(a, o, 64), ub = __shfl_up(b, o, 64);
+    if (lane >= o) { a += ua; b += ub; }
+  }
+  if (lane == 63) { smem[w][0] = a; smem[w][1] = b; }
+  __syncthreads();
+  int sa = 0, sb = 0;
+  for (int k = 0; k < w; ++k) { sa += smem[k][0]; sb += smem[k][1]; }
+  *ta = smem[0][0] + smem[1][0] + smem[2][0] + smem[3][0];
+  *tb = smem[0][1] + smem[1][1] + smem[2][1] + smem[3][1];
+  a += sa; b += sb;
+  __syncthreads();
+}
+
+// One block per member, one thread per column (consecutive threads read consecutive
+// cells of a row).  progress[3 m ..] = {c_m, episodes, samples}: c_m the first column
+// count at which the member's completed episodes hold >= num_samples steps (0: not
+// within n_cols), the episodes that ended in [0, c_m) (in [0, n_cols) while c_m == 0)
+// and the steps of all episodes completed in [0, n_cols).  col_base[m Tcap + t]: the
+// member's episodes that ended before column t.
+__global__ __launch_bounds__(256) void member_progress_kernel(
+    const uint16_t* tail, int64_t g, int64_t Tcap, int n_cols, int num_samples,
+    int32_t* progress, int32_t* col_base) {
+  __shared__ int part[4][2];
+  __shared__ int found[2];
+  const int m = blockIdx.x;
+  const uint16_t* rows = tail + (int64_t)m * g * Tcap;
+  if (threadIdx.x == 0) found[0] = 0;
+  __syncthreads();
+  int carry_s = 0, carry_e = 0;
+  for (int t0 = 0; t0 < n_cols; t0 += 256) {
+    const int t = t0 + (int)threadIdx.x;
+    int s = 0, e = 0;
+    if (t < n_cols)
+      for (int64_t i = 0; i < g; ++i) {
+        const int L = (int)rows[i * Tcap + t];
+        s += L;
+        e += L > 0;
+      }
+    int cs = s, ce = e, ts, te;
+    block_scan2_256(cs, ce, part, &ts, &te);
+    cs += carry_s;
+    ce += carry_e;
+    if (t < n_cols) {
+      col_base[(int64_t)m * Tcap + t] = ce - e;
+      // the crossing: samples never decrease, so exactly one column sees it
+      if (cs >= num_samples && cs - s < num_samples) {
+        found[0] = t + 1;
+        found[1] = ce;
+      }
+    }
+    carry_s += ts;
+    carry_e += te;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    progress[3 * m + 0] = found[0];
+    progress[3 * m + 1] = found[0] ? found[1] : carry_e;
+    progress[3 * m + 2] = carry_s;
+  }
+}
+
+// The first element of discount_cumsum in the host's own arithmetic
+// (functions.log_performance_host): ret = r_t + discount * ret from the last step
+// back, product and sum rounded once each.  Plain operators with contraction switched
+// off (as ga_adam_update): HIP's __dmul_rn / __dadd_rn are plain operators inside a
+// header compiled with contraction on, and came out as one v_fmac_f64 here.
+__device__ __forceinline__ double first_discounted_return(const float* r, int L,
+                                                          double discount) {
+#pragma clang fp contract(off)
+  double ret = 0.0;
+  for (int j = L - 1; j >= 0; --j) {
+    const double carried = discount * ret;
+    ret = (double)r[j] + carried;
+  }
+  return ret;
+}
+
+struct EpisodeStatsOut {
+  int32_t* length;
+  double* undiscounted;
+  double* discounted;
+  uint8_t* terminated;
+  uint8_t* success;  // written only with a success plane
+};
+
+// One block per (column t, member m): the envs whose episode ended at t, ranked by env
+// index 256 at a time as pack_episodes_kernel ranks them; the thread of such an env
+// walks its own episode.  Episode e of the output = (episodes of the members before m
+// that reached their target) + col_base[m, t] + rank.
+__global__ __launch_bounds__(256) void member_episode_stats_kernel(
+    const float* rew, const uint8_t* st, const uint16_t* tail, const uint8_t* success,
+    int64_t g, int64_t Tcap, const int32_t* progress, const int32_t* col_base,
+    double discount, int64_t max_eps, EpisodeStatsOut out) {
+  __shared__ int wave_cnt[4];
+  __shared__ int before_members[4];
+  const int t = blockIdx.x, m = blockIdx.y;
+  if (t >= progress[3 * m]) return;  // (block-uniform) at or after c_m: left out
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int mine = 0;
+  for (int k = threadIdx.x; k < m; k += 256)
+    if (progress[3 * k]) mine += progress[3 * k + 1];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+  if (lane == 0) before_members[w] = mine;
+  __syncthreads();
+  int64_t running = (int64_t)before_members[0] + before_members[1] + before_members[2] +
+                    before_members[3] + col_base[(int64_t)m * Tcap + t];
+  for (int64_t i0 = 0; i0 < g; i0 += 256) {
+    const int64_t i = i0 + threadIdx.x;
+    const int64_t row = (int64_t)m * g + i;
+    int L = (i < g) ? (int)tail[row * Tcap + t] : 0;
+    if (L > t + 1) L = t + 1;  // (an episode cannot be longer than the columns behind it)
+    const uint64_t ballot = __ballot(L > 0);
+    const int before = (int)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[w] = (int)__popcll(ballot);
+    __syncthreads();
+    int64_t e = running + before;
+    for (int k = 0; k < w; ++k) e += wave_cnt[k];
+    running += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+    if (L > 0 && e < max_eps) {
+      const int64_t first = row * Tcap + (t - L + 1);
+      const float* r = rew + first;
+      // episode_sums_kernel's sum: in time order, fp64
+      double acc = 0.0;
+      for (int j = 0; j < L; ++j) acc += (double)r[j];
+      const double ret = first_discounted_return(r, L, discount);
+      int term = 0, succ = 0;
+      for (int j = 0; j < L; ++j) term |= st[first + j] == 2;  // StepType.TERMINAL
+      if (success)
+        for (int j = 0; j < L; ++j) succ |= success[first + j] != 0;
+      out.length[e] = L;
+      out.undiscounted[e] = acc;
+      out.discounted[e] = ret;
+      out.terminated[e] = (uint8_t)term;
+      if (success) out.success[e] = (uint8_t)succ;
+    }
+  }
+}
+
 
 // ---- keyed pseudo-random permutation of [0, n) --------------------------------
 // BatchDataset (np/optimizers/minibatch_dataset.py:4-35) shuffles ids on the host
@@ -628,6 +779,68 @@ extern "C" int ga_episode_sums_f32(const float* rewards, const int64_t* ep_off,
   hipLaunchKernelGGL(episode_sums_kernel, dim3((unsigned)ga_ceil_div(n_eps, 256)),
                      dim3(256), 0, stream, rewards, ep_off, n_eps, sums);
   GA_CHECK_LAUNCH("episode_sums");
+  return GA_OK;
+}
+
+// what both population-score entries check before any launch
+static int check_member_args(const char* who, int64_t n, int64_t Tcap, int64_t n_cols,
+                             int64_t n_members, int64_t num_samples) {
+  GA_REQUIRE(n_members >= 1, "%s: n_members must be at least 1 (got %lld)", who,
+             (long long)n_members);
+  GA_REQUIRE(n > 0 && n % n_members == 0, "%s: %lld envs do not split into %lld members",
+             who, (long long)n, (long long)n_members);
+  GA_REQUIRE(n_cols >= 1 && n_cols <= Tcap,
+             "%s: n_cols must be in 1..Tcap (got %lld, Tcap %lld)", who, (long long)n_cols,
+             (long long)Tcap);
+  GA_REQUIRE(num_samples >= 1 && num_samples < (1ll << 31),
+             "%s: num_samples must be at least 1 (got %lld)", who, (long long)num_samples);
+  // (cells are counted in int32, as ga_pack_src_index addresses them)
+  GA_REQUIRE(n * Tcap < (1ll << 31) && n_members < (1ll << 16),
+             "%s: rollout buffers too large (%lld x %lld cells, %lld members)", who,
+             (long long)n, (long long)Tcap, (long long)n_members);
+  return GA_OK;
+}
+
+extern "C" int ga_member_progress(const uint16_t* tail_buf, int64_t n, int64_t Tcap,
+                                  int64_t n_cols, int64_t n_members, int64_t num_samples,
+                                  int32_t* progress, int32_t* col_base,
+                                  ga_stream_t stream) {
+  const char* who = "ga_member_progress";
+  GA_REQUIRE(tail_buf && progress && col_base, "%s: null pointer", who);
+  int rc = check_member_args(who, n, Tcap, n_cols, n_members, num_samples);
+  if (rc) return rc;
+  hipLaunchKernelGGL(member_progress_kernel, dim3((unsigned)n_members), dim3(256), 0,
+                     (hipStream_t)stream, tail_buf, n / n_members, Tcap, (int)n_cols,
+                     (int)num_samples, progress, col_base);
+  GA_CHECK_LAUNCH("member_progress");
+  return GA_OK;
+}
+
+extern "C" int ga_member_episode_statistics(
+    const float* rew_buf, const uint8_t* st_buf, const uint16_t* tail_buf,
+    const uint8_t* success_buf, int64_t n, int64_t Tcap, int64_t n_cols,
+    int64_t n_members, int64_t num_samples, double discount, int32_t* progress,
+    int32_t* col_base, int64_t max_eps, int32_t* length, double* undiscounted,
+    double* discounted, uint8_t* terminated, uint8_t* success, ga_stream_t stream) {
+  const char* who = "ga_member_episode_statistics";
+  GA_REQUIRE(rew_buf && st_buf && tail_buf && progress && col_base && length &&
+                 undiscounted && discounted && terminated && (success || !success_buf),
+             "%s: null pointer", who);
+  int rc = check_member_args(who, n, Tcap, n_cols, n_members, num_samples);
+  if (rc) return rc;
+  GA_REQUIRE(max_eps >= 1, "%s: max_eps must be at least 1 (got %lld)", who,
+             (long long)max_eps);
+  const int64_t g = n / n_members;
+  hipLaunchKernelGGL(member_progress_kernel, dim3((unsigned)n_members), dim3(256), 0,
+                     (hipStream_t)stream, tail_buf, g, Tcap, (int)n_cols,
+                     (int)num_samples, progress, col_base);
+  GA_CHECK_LAUNCH("member_progress");
+  EpisodeStatsOut out{length, undiscounted, discounted, terminated, success};
+  hipLaunchKernelGGL(member_episode_stats_kernel,
+                     dim3((unsigned)n_cols, (unsigned)n_members), dim3(256), 0,
+                     (hipStream_t)stream, rew_buf, st_buf, tail_buf, success_buf, g, Tcap,
+                     progress, col_base, discount, max_eps, out);
+  GA_CHECK_LAUNCH("member_episode_stats");
   return GA_OK;
 }
 

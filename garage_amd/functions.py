@@ -161,6 +161,15 @@ def log_performance_host(itr, batch, discount, prefix='Evaluation'):
     return und
 
 
+def log_performance_statistics(itr, stats, prefix='Evaluation'):
+    """:func:`log_performance` of episodes that are already reduced
+    (:class:`~garage_amd._dtypes.EpisodeStatistics`, computed under
+    ``stats.discount``): the same rows in the same order, no device work."""
+    _record_rows(itr, prefix, stats.undiscounted_returns,
+                 stats.discounted_returns, stats.terminated, stats.success)
+    return list(stats.undiscounted_returns)
+
+
 def log_multitask_performance(itr, batch, discount, name_map=None):
     """``_functions.py:177-230``: one block of rows per task plus ``Average/``.
 

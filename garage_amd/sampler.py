@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from garage_amd import _lib
-from garage_amd._dtypes import DeviceEpisodeBatch, EpisodeBatch, is_discrete
+from garage_amd._dtypes import (DeviceEpisodeBatch, EpisodeBatch,
+                               EpisodeStatistics, is_discrete)
 from garage_amd._lib import call, dptr, stream_ptr
 from garage_amd.engine import require_gpu, round4
 from garage_amd.envs import (HostVecEnv, NormalizedVecEnv, VecEnv,
@@ -990,11 +991,19 @@ class GpuPopulationSampler:
     A host env, ``noise_fn``, an action-rescaling ``NormalizedVecEnv`` or a
     network the fused step does not take raise here; nothing falls back to the
     stepwise path.
+
+    :meth:`obtain_samples` packs every member's episodes into a batch;
+    :meth:`obtain_statistics` returns per-episode statistics of the same
+    episodes without packing anything.  ``statistics_only=True`` tells an
+    algorithm that reads a score per member and nothing else to call the latter.
     """
 
     def __init__(self, agent, env, *, n_members, max_episode_length, seed=None,
-                 worker_args=None):
+                 worker_args=None, statistics_only=False):
         self._agent = agent
+        # what an algorithm that only scores its members (CEM) reads to call
+        # obtain_statistics instead of obtain_samples; nothing here depends on it
+        self.statistics_only = bool(statistics_only)
         self._n_members = int(n_members)
         if self._n_members < 1:
             raise ValueError('n_members must be at least 1')
@@ -1086,6 +1095,37 @@ class GpuPopulationSampler:
             env.advance()
         w._global_step += k
 
+    def _rollout(self, num_samples, member_params, env_update, progress):
+        """The stepping both ``obtain_*`` methods share: one first launch of
+        ``ceil(num_samples / g)`` columns -- no member can be done before --
+        then as many steps at a time as the member that is furthest behind
+        needs at the very least.  ``progress(b, col)``, after every launch:
+        ``(samples each member has completed, whatever the caller keeps of the
+        check)``.  Returns ``(b, params, what the last check kept)``."""
+        w = self._worker
+        if env_update is not None:
+            w.update_env(env_update)
+            self._check_env(w.env)
+            self._env = w.env
+        w._needs_agent_reset = True  # every call brings new parameters
+        params = self._packed(member_params)
+        w._start()
+        g = w._n_envs // self._n_members
+        b = w._alloc_buffers(num_samples, n_share=g)
+        tcap = b['Tcap']
+        col, k = 0, min(-(-num_samples // g), tcap)
+        while True:
+            self._steps(b, col, k, params)
+            col += k
+            done, kept = progress(b, col)
+            if (done >= num_samples).all():
+                return b, params, kept
+            if col >= tcap:
+                raise RuntimeError('rollout buffer exhausted: an environment '
+                                   'ran past max_episode_length')
+            short = int(num_samples - done.min())
+            k = min(-(-short // g), tcap - col)
+
     def obtain_samples(self, itr, num_samples, member_params, env_update=None):
         """One :class:`~garage_amd._dtypes.DeviceEpisodeBatch` per member: the
         episodes a lone ``GpuVecWorker`` of the member's ``g`` envs with the
@@ -1095,37 +1135,19 @@ class GpuPopulationSampler:
         what ``policy.pack_members`` returns, or an ``(M, P)`` array of compact
         vectors."""
         del itr
-        w = self._worker
-        if env_update is not None:
-            w.update_env(env_update)
-            self._check_env(w.env)
-            self._env = w.env
-        w._needs_agent_reset = True  # every call brings new parameters
-        params = self._packed(member_params)
-        w._start()
-        M, g = self._n_members, w._n_envs // self._n_members
+        w, M = self._worker, self._n_members
         num_samples = max(int(num_samples), 1)
-        b = w._alloc_buffers(num_samples, n_share=g)
-        tcap = b['Tcap']
-        # no member can be done before step ceil(num_samples / g): one launch
-        # without a host check; after it, as many steps at a time as the member
-        # that is furthest behind needs at the very least
-        col, k = 0, min(-(-num_samples // g), tcap)
-        while True:
-            self._steps(b, col, k, params)
-            col += k
+
+        def progress(b, col):
             # per member and column: samples and episodes completed there
-            ended = b['tail'][:, :col].to(torch.int32).reshape(M, g, col)
+            ended = b['tail'][:, :col].to(torch.int32).reshape(M, -1, col)
             host = torch.stack([torch.cumsum(ended.sum(1), 1),
                                 (ended != 0).sum(1)]).cpu()
             done, eps = host[0].numpy(), host[1].to(torch.int32)  # (M, col)
-            if (done[:, -1] >= num_samples).all():
-                break
-            if col >= tcap:
-                raise RuntimeError('rollout buffer exhausted: an environment '
-                                   'ran past max_episode_length')
-            short = int(num_samples - done[:, -1].min())
-            k = min(-(-short // g), tcap - col)
+            return done[:, -1], (done, eps)
+
+        b, params, (done, eps) = self._rollout(num_samples, member_params,
+                                               env_update, progress)
         # c_m: the columns a member keeps stepping past it are dropped here
         c = (done >= num_samples).argmax(1) + 1
         pol = self._agent
@@ -1133,11 +1155,70 @@ class GpuPopulationSampler:
         if pol.kind == 'gaussian':
             raw = params[:, 0].cpu().numpy()
             log_std = [pol.log_std_of(float(v))[0] for v in raw]
+        g = w._n_envs // M
         batches = [w._pack(b, int(c[m]), member=(m * g, (m + 1) * g, eps[m],
                                                  log_std[m]))
                    for m in range(M)]
         self.total_env_steps += int(sum(int(sum(x.lengths)) for x in batches))
         return batches
+
+    def obtain_statistics(self, itr, num_samples, member_params, discount,
+                          env_update=None):
+        """One :class:`~garage_amd._dtypes.EpisodeStatistics` per member, of
+        exactly the episodes :meth:`obtain_samples` returns -- same stepping,
+        same columns ``c_m``, same order -- reduced on the device from the raw
+        rollout buffers (``ga_member_progress``,
+        ``ga_member_episode_statistics``): nothing is packed or gathered, a
+        progress check copies three integers per member to the host and the
+        ending one array of all members' episodes.  ``discount``: of the
+        discounted returns, in fp64 as ``log_performance_host`` applies it."""
+        del itr
+        w, M = self._worker, self._n_members
+        num_samples = max(int(num_samples), 1)
+        discount = float(discount)
+        s = stream_ptr()
+        prog = torch.empty(M, 3, dtype=torch.int32, device=w.device)
+        work = {}  # col_base: sized by the rollout buffers
+
+        def progress(b, col):
+            if not work:
+                work['col_base'] = torch.empty(M, b['Tcap'], dtype=torch.int32,
+                                               device=w.device)
+            call('ga_member_progress', dptr(b['tail']), w._n_envs, b['Tcap'],
+                 col, M, num_samples, dptr(prog), dptr(work['col_base']), s)
+            host = prog.cpu().numpy()
+            return host[:, 2], (col, host)
+
+        b, _, (col, host) = self._rollout(num_samples, member_params,
+                                          env_update, progress)
+        counts = host[:, 1].astype(np.int64)  # every member reached its c_m
+        N = int(counts.sum())
+        # one buffer, one copy: f64[N] f64[N] i32[N] u8[N] u8[N]
+        out = torch.empty(22 * N, dtype=torch.uint8, device=w.device)
+        und = out[:8 * N].view(torch.float64)
+        disc = out[8 * N:16 * N].view(torch.float64)
+        length = out[16 * N:20 * N].view(torch.int32)
+        term, succ = out[20 * N:21 * N], out[21 * N:]
+        plane = b['dev_infos'].get('success')
+        call('ga_member_episode_statistics', dptr(b['rew']), dptr(b['st']),
+             dptr(b['tail']), dptr(plane), w._n_envs, b['Tcap'], col, M,
+             num_samples, discount, dptr(prog), dptr(work['col_base']), N,
+             dptr(length), dptr(und), dptr(disc), dptr(term), dptr(succ), s)
+        raw = out.cpu().numpy()
+        und = raw[:8 * N].view(np.float64)
+        disc = raw[8 * N:16 * N].view(np.float64)
+        length = raw[16 * N:20 * N].view(np.int32).astype(np.int64)
+        term = raw[20 * N:21 * N].astype(np.float64)
+        succ = None if plane is None else raw[21 * N:].astype(np.float64)
+        stats, lo = [], 0
+        for m in range(M):
+            hi = lo + int(counts[m])
+            stats.append(EpisodeStatistics(
+                length[lo:hi], und[lo:hi], disc[lo:hi], term[lo:hi],
+                None if succ is None else succ[lo:hi], discount))
+            lo = hi
+        self.total_env_steps += int(length.sum())
+        return stats
 
     def shutdown_worker(self):
         self._worker.shutdown()

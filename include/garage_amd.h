@@ -731,6 +731,49 @@ GA_API int ga_permutation_i32(int64_t n, uint64_t key, int32_t* out, ga_stream_t
 GA_API int ga_episode_sums_f32(const float* rewards, const int64_t* ep_off, int64_t n_eps,
                                double* sums, ga_stream_t stream);
 
+/* ---- a population's score from the raw rollout buffers -------------------------
+ * The buffers are the ones ga_policy_env_step_members_f32 fills: tail_buf [n, Tcap]
+ * (an episode's length at its last cell, else 0), columns [0, n_cols) stepped so far;
+ * member m owns the rows [m g, (m + 1) g), g = n / n_members (any g >= 1).
+ *
+ * progress[3 m ..] = {c_m, episodes, samples} per member: c_m is the first column
+ * count at which the episodes the member has completed hold >= num_samples steps --
+ * the columns GpuPopulationSampler.obtain_samples keeps -- or 0 when that is not
+ * reached within n_cols; `episodes` those that ended in [0, c_m) (in [0, n_cols)
+ * while c_m == 0); `samples` the steps of all episodes completed in [0, n_cols).
+ * col_base [n_members, Tcap] (workspace): per member and column t < n_cols, its
+ * episodes that ended before t.  One launch; the caller copies 3 n_members integers.
+ * Refused before any launch: NULL pointers; n_members < 1; n not a multiple of
+ * n_members; n_cols outside 1..Tcap; num_samples < 1; n * Tcap >= 2^31. */
+GA_API int ga_member_progress(const uint16_t* tail_buf, int64_t n, int64_t Tcap,
+                              int64_t n_cols, int64_t n_members, int64_t num_samples,
+                              int32_t* progress, int32_t* col_base, ga_stream_t stream);
+/* What log_performance (_functions.py:233-275) reduces an episode to, for every
+ * episode of member m that ended in a column < c_m, written compactly in the order
+ * (member, end column, env index) -- ga_pack_episodes' order within a member; a member
+ * with c_m == 0 contributes none, nor do episodes in flight.  Two launches:
+ * ga_member_progress' (progress and col_base are written as above) and the statistics.
+ *   length        the episode's steps
+ *   undiscounted  its rewards (rew_buf [n, Tcap] f32) added in time order into an fp64
+ *                 accumulator: ga_episode_sums_f32's sum (_functions.py:253)
+ *   discounted    ret = (double)r_t + discount * ret from the last step back to the
+ *                 first, product and sum rounded once each (no fused multiply-add):
+ *                 the first element of discount_cumsum (_functions.py:250-252) in the
+ *                 host's own fp64 arithmetic
+ *   terminated    1 when a step of st_buf [n, Tcap] is StepType.TERMINAL
+ *                 (_functions.py:254-256)
+ *   success       1 when a step's flag in success_buf [n, Tcap] is set
+ *                 (_functions.py:257-259); success_buf NULL: the env records none and
+ *                 `success` is not written (it may be NULL)
+ * max_eps: the episodes the output arrays hold; nothing is written past it.
+ * Refusals: as ga_member_progress, and max_eps < 1. */
+GA_API int ga_member_episode_statistics(
+    const float* rew_buf, const uint8_t* st_buf, const uint16_t* tail_buf,
+    const uint8_t* success_buf, int64_t n, int64_t Tcap, int64_t n_cols,
+    int64_t n_members, int64_t num_samples, double discount, int32_t* progress,
+    int32_t* col_base, int64_t max_eps, int32_t* length, double* undiscounted,
+    double* discounted, uint8_t* terminated, uint8_t* success, ga_stream_t stream);
+
 /* ---- one optimisation pass, enqueued natively --------------------------------
  * All minibatches of one epoch of VPG._train (torch/algos/vpg.py:230-293) for
  * one network: forward, fused loss + gradient seed, backward, slab reduction,

@@ -16,6 +16,15 @@ Prints one JSON line per row -- the median over ``reps`` of (env steps taken) /
 (wall time, ended by a device synchronise) -- then the ratios, then where the
 population call's time goes: the launches (first chunk and the rest, to their
 completion), the host checks between them and the per-member packing.
+
+    python tools/population_rate.py --statistics [--reps 7]
+
+times ``obtain_statistics`` (per-episode statistics from the raw rollout buffers,
+nothing packed) beside ``obtain_samples`` on the same sampler, taking turns, with
+the ``single`` ceiling: every run's milliseconds, both ranges, the env-steps/s
+and where an ``obtain_statistics`` call's time goes -- the launches, the progress
+checks after them (kernel, copy of three integers per member, host logic), the
+final statistics (two launches) and the copy and split of the result.
 """
 import argparse
 import json
@@ -35,6 +44,8 @@ def main():
     ap.add_argument('--g', type=int, default=64)
     ap.add_argument('--T', type=int, default=128)
     ap.add_argument('--reps', type=int, default=7)
+    ap.add_argument('--statistics', action='store_true',
+                    help='time obtain_statistics beside obtain_samples')
     a = ap.parse_args()
     M, g, T = a.members, a.g, a.T
     n, num = M * g, g * T
@@ -85,6 +96,9 @@ def main():
         w._needs_agent_reset = True
         w.rollout_samples(n * T)
         return n * (w._global_step - step0)
+
+    if a.statistics:
+        return statistics_mode(a, pop, packed, run_population, run_single)
 
     rows = dict(population=run_population, sequential=run_sequential,
                 single=run_single)
@@ -142,6 +156,96 @@ def main():
     pop._steps, w._pack = real_steps, real_pack
     print(json.dumps(dict(breakdown_ms={k: 1e3 * v for k, v in parts.items()},
                           total_ms=1e3 * total, launches=state['calls'])))
+
+
+def statistics_mode(a, pop, packed, run_population, run_single):
+    """``obtain_samples`` / ``obtain_statistics`` / the single-policy ceiling,
+    taking turns; then the parts of one ``obtain_statistics`` call."""
+    import garage_amd.sampler as sampler_module
+    M, g, T = a.members, a.g, a.T
+    n, num = M * g, g * T
+    w = pop._worker
+
+    def run_statistics(r):
+        step0 = w._global_step
+        pop.obtain_statistics(r, num, packed, 0.99)
+        return n * (w._global_step - step0)
+
+    rows = dict(obtain_samples=run_population,
+                obtain_statistics=run_statistics, single=run_single)
+    ms, rates = {k: [] for k in rows}, {k: [] for k in rows}
+    for r in range(a.reps + 1):
+        for k, fn in rows.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            steps = fn(r)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if r:
+                ms[k].append(1e3 * dt)
+                rates[k].append(steps / dt)
+    for k in rows:
+        print(json.dumps(dict(
+            row=k, members=M, envs_per_member=g, T=T, hidden=[64, 64],
+            runs_ms=[round(x, 3) for x in ms[k]], min_ms=min(ms[k]),
+            max_ms=max(ms[k]), env_steps_per_s=float(np.median(rates[k])))))
+    med = {k: float(np.median(v)) for k, v in rates.items()}
+    print(json.dumps(dict(
+        every_statistics_run_faster_than_every_samples_run=bool(
+            max(ms['obtain_statistics']) < min(ms['obtain_samples'])),
+        statistics_over_samples=med['obtain_statistics'] /
+        med['obtain_samples'],
+        statistics_over_single=med['obtain_statistics'] / med['single'])))
+
+    # where one obtain_statistics call spends its time (a synchronise after
+    # every part, so the parts add up to more than the untimed call)
+    parts = dict(launches=0.0, progress_checks=0.0, final_statistics=0.0,
+                 copy_and_split=0.0)
+    real_steps, real_call = pop._steps, sampler_module.call
+    state = dict(launches=0, checks=0, last=None)
+
+    def close_check(now):
+        if state['last'] is not None:
+            parts['progress_checks'] += now - state['last']
+            state['last'] = None
+
+    def steps(*args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        close_check(t0)
+        real_steps(*args)
+        torch.cuda.synchronize()
+        state['last'] = time.perf_counter()
+        state['launches'] += 1
+        parts['launches'] += state['last'] - t0
+
+    def call(name, *args):
+        if name == 'ga_member_progress':
+            state['checks'] += 1
+        if name != 'ga_member_episode_statistics':
+            return real_call(name, *args)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        close_check(t0)
+        real_call(name, *args)
+        torch.cuda.synchronize()
+        state['end'] = time.perf_counter()
+        parts['final_statistics'] += state['end'] - t0
+
+    pop._steps, sampler_module.call = steps, call
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pop.obtain_statistics(0, num, packed, 0.99)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+    finally:
+        pop._steps, sampler_module.call = real_steps, real_call
+    parts['copy_and_split'] = t1 - state['end']
+    print(json.dumps(dict(breakdown_ms={k: 1e3 * v for k, v in parts.items()},
+                          total_ms=1e3 * (t1 - t0),
+                          launches=state['launches'],
+                          progress_checks=state['checks'])))
 
 
 if __name__ == '__main__':
