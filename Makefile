@@ -68,11 +68,11 @@ clean:
 asan-host: $(OUT)/host_asan_test
 	$(OUT)/host_asan_test
 
-$(OUT)/host_asan_test: tests/host/update_loop_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+$(OUT)/host_asan_test: tests/host/update_loop_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/update_loop_harness.cpp $(CSRC)/update.cpp \
+	  tests/host/update_loop_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp \
 	  -o $@
 
 .PHONY: asan-host
@@ -112,11 +112,29 @@ $(OUT)/mlp_layers_asan_test: tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layer
 asan-slab-sum: $(OUT)/slab_sum_asan_test
 	$(OUT)/slab_sum_asan_test
 
-$(OUT)/slab_sum_asan_test: tests/host/slab_sum_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+$(OUT)/slab_sum_asan_test: tests/host/slab_sum_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/slab_sum_harness.cpp $(CSRC)/update.cpp \
+	  tests/host/slab_sum_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp \
 	  -o $@
 
 .PHONY: asan-slab-sum
+
+# fused_step's choice between the fused forward + data-gradient launch and the two
+# launches (update.cpp, ga_set_fused_fwd_dgrad) under AddressSanitizer + UBSan: the order
+# of the launches on a stream, no slab ranges and no pre-summed regions with the fused
+# launch, the old sequence wherever it does not apply (tests/host/).  The two harnesses
+# above link a kernel side WITHOUT the fused instantiation (no_fused_fwd_dgrad.cpp) and
+# pin the two-launch sequence.
+asan-fwd-dgrad: $(OUT)/fused_fwd_dgrad_asan_test
+	$(OUT)/fused_fwd_dgrad_asan_test
+
+$(OUT)/fused_fwd_dgrad_asan_test: tests/host/fused_fwd_dgrad_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  tests/host/fused_fwd_dgrad_harness.cpp $(CSRC)/update.cpp \
+	  -o $@
+
+.PHONY: asan-fwd-dgrad

@@ -289,6 +289,7 @@ SIGNATURES = {
     'ga_set_fused_first_layer': (c_int, [c_int]),
     'ga_set_pipelined_kloop': (c_int, [c_int]),
     'ga_set_slab_sum_in_dgrad': (c_int, [c_int]),
+    'ga_set_fused_fwd_dgrad': (c_int, [c_int]),
     'ga_set_split_bf16': (c_int, [c_int]),
     'ga_update_epoch_pair': (c_int, [C.POINTER(UpdateArgs), ptr,
                                      C.POINTER(UpdateArgs), ptr]),

@@ -102,6 +102,14 @@ typedef struct ga_fused_dgrad_net {
 } ga_fused_dgrad_net;
 int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M, int width,
                           int K, int in_w, hipStream_t stream);
+// 1 + 3 in ONE launch, one network: every workgroup runs launch 1's body and then launch
+// 3's on the same 64 rows, dZ2 staying in LDS between them (it is still written once,
+// for launch 2, which now runs AFTER this one: `dgrad` carries no slab ranges).
+// ga_fused_fwd_dgrad_supported: two hidden layers of the same width (width == K), first
+// layer in the kernel.  `dgrad` must describe the step `fwd` describes.
+int ga_fused_fwd_dgrad_supported(int width, int K, int in_w);
+int ga_fused_fwd_dgrad(const ga_fused_fwd_net* fwd, const ga_fused_dgrad_net* dgrad,
+                       int64_t M, int width, int K, hipStream_t stream);
 // 4. partial sums -> gradient -> Adam, and the loss.  pl_rows > 0 (one network only):
 // the launch also rewrites the split-operand planes of the [pl_rows][pl_cols] weight
 // matrix at flat index pl_beg, when the step's forward launch used them;

@@ -35,6 +35,13 @@
 //       one group of four partials per k-step, in the optimizer kernel's own order
 //       (FtSlabSummer) -- so that the optimizer launch reads one partial of them.
 //
+//   fwd_dgrad_kernel       the two kernels above as ONE launch (one network, two
+//       hidden layers of the same width, first layer in the kernel; the default for
+//       such steps, ga_set_fused_fwd_dgrad): a workgroup runs both bodies on its 64
+//       rows and dZ2 stays in LDS between them as the data gradient's A operand.  dZ2
+//       is still written once, for the middle layer's weight-gradient GEMM, which then
+//       runs AFTER this launch: its slabs are summed by the optimizer launch.
+//
 //   reduce_regions_adam_kernel   the optimizer step over per-region partial sums
 //       (split-K slabs of the weight-gradient GEMMs, per-workgroup partials of
 //       the two kernels above), each element summed in a fixed tree by 16 shares
@@ -156,6 +163,12 @@ __device__ __forceinline__ void ft_kstep(const float* As, const float* Bs,
   }
 }
 
+// What fwd_head_loss_body<FUSE> leaves behind for the data-gradient body
+struct FtFusedLds {
+  float* stage;  // [64][BN + 4]: dZ of the tile's rows, rows >= M exact zeros
+  float* aux;    // 2048 floats, free once E5 is done
+};
+
 // (two 512-thread workgroups per CU need <= 128 registers: the second bound is waves
 // per SIMD)
 // EVAL (with L1): the whole MLP for its outputs only -- no H1 spill, and after the
@@ -167,12 +180,19 @@ __device__ __forceinline__ void ft_kstep(const float* As, const float* Bs,
 // the plain loop.
 // ft_tile / ft_tiles: this workgroup's 64-row tile and the number of tiles of ITS
 // network's minibatch (a pair launch carries the tiles of two networks in one grid)
+// FUSE (with L1, training): the data-gradient body runs behind this one in the same
+// workgroup (fwd_dgrad_kernel).  The epilogue then always takes E6 before E5, and E5
+// also leaves every dZ quad in the stage, over the H quad it was computed from: the
+// stage is the data gradient's A operand.  `keep` receives the workgroup's LDS.
 template <int BN, int WAVES_M, int WAVES_N, bool L1, bool EVAL, int KSC = 0,
-          bool SPLIT = false>
+          bool SPLIT = false, bool FUSE = false>
 __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
                                                    const int ft_tile,
-                                                   const int ft_tiles) {
+                                                   const int ft_tiles,
+                                                   FtFusedLds* keep = nullptr) {
   static_assert(L1 || !EVAL, "the evaluation forward computes the first layer itself");
+  static_assert(!FUSE || (L1 && !EVAL && !SPLIT),
+                "the fused data gradient: exact fp32 training step, first layer in the kernel");
   static_assert(L1 || KSC == 0, "KSC belongs to the first-layer producer");
   static_assert(!SPLIT || (L1 && KSC == 0 && WAVES_M * WAVES_N == 8),
                 "the split-operand loop: first layer in the kernel, 8 waves");
@@ -961,6 +981,13 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
     z.z *= (1.f - h.z * h.z); z.w *= (1.f - h.w * h.w);
     if (m0 + rr < M)
       *reinterpret_cast<float4*>(p.dZ + (int64_t)(m0 + rr) * p.lddz + 4 * c4) = z;
+    if constexpr (FUSE) {
+      // same thread, same address as the H quad above.  Rows beyond M: dout is zero
+      // there, but 0 * w is not zero for every w -- the operand gets the zeros the
+      // tile loader of the two-launch path gives it
+      if (m0 + rr >= M) z = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(stage + rr * LDC + 4 * c4) = z;
+    }
   }
   };
   auto phase_head_grad = [&](auto jn_tag) {
@@ -994,7 +1021,13 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
   }
   };
   auto two_phases = [&](auto jn_tag) {
-    if (ft_tile >= (ft_tiles + 1) / 2) {
+    if constexpr (FUSE) {
+      // E6 reads the staged H that E5 overwrites
+      phase_head_grad(jn_tag);
+      FT_STAMP(7);
+      __syncthreads();
+      phase_dz(jn_tag);
+    } else if (ft_tile >= (ft_tiles + 1) / 2) {
       phase_head_grad(jn_tag);
       FT_STAMP(7);
       phase_dz(jn_tag);
@@ -1012,6 +1045,11 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
     two_phases(std::integral_constant<int, 8>{});
   FT_STAMP(8);
   FT_MARK(2);
+  if constexpr (FUSE) {
+    static_assert(AUX_FLOATS >= FT_ROWS * 32, "the observation rows fit in aux");
+    keep->stage = stage;
+    keep->aux = aux;
+  }
 }
 
 template <int BN, int WAVES_M, int WAVES_N, bool L1 = false, int KSC = 0>
@@ -1457,6 +1495,94 @@ struct DgradWgrad0Params {
   FtSlabSum sum;       // the middle layer's split-K slabs, summed on the side
 };
 
+constexpr int FT_LDXS = 32;  // staged observation rows: 32 floats (zero beyond in_w)
+
+// The workgroup's observation rows, two quads per thread: loads issued in front of the
+// k-loop, staged behind it (dgrad_wgrad0_tail)
+template <int NT>
+__device__ __forceinline__ void dgrad_load_x(const DgradWgrad0Params& p, const int ft_tile,
+                                             float4 (&xq)[2]) {
+  static_assert(FT_ROWS * (FT_LDXS / 4) <= 2 * NT, "at most two quads of X per thread");
+  const int tid = threadIdx.x;
+  const int m0 = ft_tile * FT_ROWS;
+  const int M = p.g.M;
+  const int ld0 = (p.in_w + 3) & ~3;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + NT * i;
+    const int rr = min(e / (FT_LDXS / 4), FT_ROWS - 1);
+    const int q = min(e % (FT_LDXS / 4), ld0 / 4 - 1);
+    const int m = min(m0 + rr, M - 1);
+    const int64_t src = p.idx ? (int64_t)p.idx[m] : (int64_t)m;
+    xq[i] = *reinterpret_cast<const float4*>(p.X + src * p.ldx + 4 * q);
+  }
+}
+
+// The data-gradient k-loop on an A operand that is ALREADY in LDS: `stage` holds the
+// tile's 64 rows of dZ2 [64][BN + 4], k-contiguous (fwd_head_loss_body<FUSE> left them
+// there; K = BN), so the loop loads no A, stores nothing to LDS and has no barrier.
+// A fragments: one 16-B read per row block and group of four MFMAs (BN + 4 has the
+// residue of BK + PAD mod 32: gemm_mainloop's conflict-free pattern).  B fragments
+// (W2 [K][ldb], n-contiguous): lane (l31, half) feeds B(k, n = wn0 + 32 j + l31),
+// k = 32 s + 8 g + 4 half + q -- four dword loads per group, straight from L2 (every
+// workgroup reads all of W2), one step ahead, refilled in place as soon as the group's
+// MFMAs are issued.  MFMAs per accumulator in gemm_mainloop's order (s, g, q): the
+// same bits as dgrad_wgrad0_body's loop.
+template <int BN, int TM, int TN>
+__device__ __forceinline__ void dgrad_kloop_staged(const DgradWgrad0Params& p,
+                                                   const float* stage,
+                                                   f32x16 (&acc)[TM][TN], const int wm0,
+                                                   const int wn0) {
+  constexpr int LDC = BN + 4;
+  const int lane = threadIdx.x & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int nk = BN / BK;
+  // wave-uniform base + one 32-bit lane offset (rows k < K = BN, columns < BN <= ldb)
+  const uint32_t ldb = (uint32_t)p.g.ldb;
+  const uint32_t woff = (uint32_t)(4 * half) * ldb + (uint32_t)(wn0 + l31);
+  float bn[TN][BK / 8][4];
+  auto fetch_group = [&](int s, int g) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        bn[j][g][q] = p.g.B[woff + (uint32_t)(32 * s + 8 * g + q) * ldb + (uint32_t)(32 * j)];
+  };
+#pragma unroll
+  for (int g = 0; g < BK / 8; ++g) fetch_group(0, g);
+  const float* arow = stage + (wm0 + l31) * LDC + 4 * half;
+  for (int s = 0; s < nk; ++s) {
+    const bool more = s + 1 < nk;
+#pragma unroll
+    for (int g = 0; g < BK / 8; ++g) {
+      float a[TM][4];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const float4 v =
+            *reinterpret_cast<const float4*>(arow + 32 * i * LDC + 32 * s + 8 * g);
+        a[i][0] = v.x; a[i][1] = v.y; a[i][2] = v.z; a[i][3] = v.w;
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][q], bn[j][g][q], acc[i][j],
+                                                             0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+      if (more) fetch_group(s + 1, g);
+    }
+  }
+}
+
+template <int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void dgrad_wgrad0_tail(
+    const DgradWgrad0Params& p, const int ft_tile,
+    f32x16 (&acc)[FT_ROWS / WAVES_M / 32][BN / WAVES_N / 32], const float4 (&xq)[2],
+    float* stage, float* xs);
+
 template <int BN, int WAVES_M, int WAVES_N, bool SPLIT = false>
 __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
                                                   const int ft_tile) {
@@ -1471,11 +1597,8 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
   constexpr int STAGE_FLOATS = FT_ROWS * LDC;
   constexpr int TILE_FLOATS =
       A_FLOATS + B_FLOATS > STAGE_FLOATS ? A_FLOATS + B_FLOATS : STAGE_FLOATS;
-  constexpr int LDXS = 32;  // staged observation rows: 32 floats (zero beyond in_w)
-  static_assert((FT_ROWS * (BN / 4)) % NT == 0, "whole quads per thread");
-  static_assert(FT_ROWS * (LDXS / 4) <= 2 * NT, "at most two quads of X per thread");
   __shared__ __attribute__((aligned(16))) float lds[TILE_FLOATS];
-  __shared__ __attribute__((aligned(16))) float xs[FT_ROWS * LDXS];
+  __shared__ __attribute__((aligned(16))) float xs[FT_ROWS * FT_LDXS];
   float* stage = lds;
 
   const int tid = threadIdx.x;
@@ -1485,21 +1608,12 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
   const int wn0 = (wave % WAVES_N) * WN;
   const int m0 = ft_tile * FT_ROWS;
   const int M = p.g.M;
-  const int ld0 = (p.in_w + 3) & ~3;
 
   FT_STAMP(0);
   FT_MARK(0);
   // the workgroup's observation rows: loads issued now, staged after the k-loop
   float4 xq[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int e = tid + NT * i;
-    const int rr = min(e / (LDXS / 4), FT_ROWS - 1);
-    const int q = min(e % (LDXS / 4), ld0 / 4 - 1);
-    const int m = min(m0 + rr, M - 1);
-    const int64_t src = p.idx ? (int64_t)p.idx[m] : (int64_t)m;
-    xq[i] = *reinterpret_cast<const float4*>(p.X + src * p.ldx + 4 * q);
-  }
+  dgrad_load_x<NT>(p, ft_tile, xq);
 
   // the slab sum: one step per k-step of the plain loop, the rest (all of it beside the
   // hand-scheduled split-operand loop, and at 64 units, where the steps' registers
@@ -1516,7 +1630,12 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
   // (measured and not kept for this k-loop, see DESIGN.md section 5: B fragments
   // straight from L2 with the dZ2 tile double buffered in LDS and one barrier per
   // step -- 52.8 us; no LDS and no barrier at all, every wave fetching its own A and
-  // B fragments -- 62.1 us; against 50.9 us for the two-barrier loop below)
+  // B fragments -- 62.1 us; against 50.9 us for the two-barrier loop below.  Both
+  // were measured in THIS kernel, where dZ2 comes from memory and has to be staged.
+  // Where it is in LDS already -- fwd_dgrad_kernel, behind the forward body of the same
+  // tile -- the B-from-L2 loop needs no A loads, no LDS stores and no barrier
+  // (dgrad_kloop_staged), and the one launch takes 98.2 us against 54.5 + 52.6 for
+  // the two: DESIGN.md section 9 item 3, profiles/r05_notes.md)
   if constexpr (SPLIT) {
     // ---- split-operand k-loop (see ft_split3): the dZ2 tile is fetched as one 16-B
     // quad per thread and 32-deep step, TWO steps ahead (it comes from HBM), split and
@@ -1619,6 +1738,31 @@ __device__ __forceinline__ void dgrad_wgrad0_body(const DgradWgrad0Params& p,
   slab.drain();
   FT_STAMP(1);
   FT_MARK(1);
+  dgrad_wgrad0_tail<BN, WAVES_M, WAVES_N>(p, ft_tile, acc, xq, stage, xs);
+}
+
+// Behind the data-gradient k-loop: the accumulators (dZ2 W2 of the tile) times the
+// slope of H1 -> dZ1 in `stage`, then this workgroup's shares of dW1 and db1.  Nobody
+// reads `stage` or `xs` ([64][32] floats) any more when this is called.
+template <int BN, int WAVES_M, int WAVES_N>
+__device__ __forceinline__ void dgrad_wgrad0_tail(
+    const DgradWgrad0Params& p, const int ft_tile,
+    f32x16 (&acc)[FT_ROWS / WAVES_M / 32][BN / WAVES_N / 32], const float4 (&xq)[2],
+    float* stage, float* xs) {
+  constexpr int NT = 64 * WAVES_M * WAVES_N;
+  constexpr int WM = FT_ROWS / WAVES_M, WN = BN / WAVES_N;
+  constexpr int TM = WM / 32, TN = WN / 32;
+  constexpr int LDC = BN + 4;
+  constexpr int LDXS = FT_LDXS;
+  static_assert((FT_ROWS * (BN / 4)) % NT == 0, "whole quads per thread");
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm0 = (wave / WAVES_N) * WM;
+  const int wn0 = (wave % WAVES_N) * WN;
+  const int m0 = ft_tile * FT_ROWS;
+  const int M = p.g.M;
+  const int ld0 = (p.in_w + 3) & ~3;
 
   // H1 of this thread's quads: in flight while the accumulators are staged
   float4 hq[FT_ROWS * (BN / 4) / NT];
@@ -1738,6 +1882,62 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
     dgrad_wgrad0_body<BN, WAVES_M, WAVES_N>(pp.b, tile);
   else
     dgrad_wgrad0_body<BN, WAVES_M, WAVES_N>(pp.a, tile);
+}
+
+// The forward + loss body and the data-gradient body of the SAME 64-row tile in one
+// workgroup (two hidden layers of equal width, first layer in the kernel, exact fp32).
+// Workgroup t of dgrad_wgrad0_kernel reads back exactly the dZ2 rows workgroup t of
+// fwd_head_loss_kernel stored, restages them 32 columns at a time behind two barriers a
+// step, gathers the observation rows again and pays a second launch ramp, prologue and
+// drain.  Here dZ2 stays in the stage as the k-contiguous A operand
+// (dgrad_kloop_staged) and the rest of the data-gradient body follows unchanged.  dZ2
+// still goes to memory once: the middle layer's weight-gradient GEMM reads it -- AFTER
+// this launch, so its split-K slabs cannot be summed here (DgradWgrad0Params::sum is
+// unused) and the optimizer launch sums them.  Same arithmetic in the same order per
+// element as the two launches: the same bits.
+// LDS: what the forward body has (the observation rows go to its aux block).
+struct FwdDgradParams {
+  FwdLossParams f;
+  DgradWgrad0Params d;
+};
+template <int BN, int WAVES_M, int WAVES_N, int KSC>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
+                             WAVES_M * WAVES_N == 8 ? 4 : 2) void fwd_dgrad_kernel(
+    FwdDgradParams pp) {
+  constexpr int NT = 64 * WAVES_M * WAVES_N;
+  constexpr int WM = FT_ROWS / WAVES_M, WN = BN / WAVES_N;
+  constexpr int TM = WM / 32, TN = WN / 32;
+  const int ft_tile = (int)blockIdx.x;
+  FtFusedLds l;
+  fwd_head_loss_body<BN, WAVES_M, WAVES_N, true, false, KSC, false, true>(
+      pp.f, ft_tile, (int)gridDim.x, &l);
+  const DgradWgrad0Params& p = pp.d;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm0 = (wave / WAVES_N) * WM;
+  const int wn0 = (wave % WAVES_N) * WN;
+  FT_STAMP(0);
+  float4 xq[2];
+  dgrad_load_x<NT>(p, ft_tile, xq);
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  __syncthreads();  // E5 has left dZ2 in the stage
+  dgrad_kloop_staged<BN>(p, l.stage, acc, wm0, wn0);
+  FT_STAMP(1);
+  // The tail overwrites the stage (every wave read all of it) and reads H1 from
+  // memory, where other threads of this workgroup stored it during the forward k-loop.
+  // A workgroup-scope release / acquire pair around the barrier is enough for that: the
+  // workgroup sits on one CU, so stores and loads go through the same vector L1, and
+  // the loads are the first this launch makes of those lines (an H1 row is a whole
+  // number of lines that belong to this tile alone) -- no stale copy can be there.
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  dgrad_wgrad0_tail<BN, WAVES_M, WAVES_N>(p, ft_tile, acc, xq, l.stage, l.aux);
 }
 
 // ---------------------------------------------------------------------------
@@ -2303,6 +2503,57 @@ extern "C" int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets,
   hipExtLaunchKernelGGL((dgrad_wgrad0_pair_kernel<256, 1, 8>), grid, dim3(512), 0,
                         stream, e0, e1, 0, pp);
   GA_CHECK_LAUNCH("dgrad_wgrad0_pair");
+  return GA_OK;
+}
+
+// fwd_dgrad_kernel is compiled for two hidden layers of the same width (K = the first
+// one's, width = the second one's) with the first layer in the kernel.
+extern "C" int ga_fused_fwd_dgrad_supported(int width, int K, int in_w) {
+  return ga_fused_width_ok(width) && K == width && ga_fused_first_layer_ok(in_w, K);
+}
+
+// Launches 1 and 3 of a step as ONE dispatch (fwd_dgrad_kernel), one network.  `dgrad`
+// describes the same step as `fwd`: its dZ2 / H1 / X / idx are what `fwd` writes and
+// gathers, and it carries no slab ranges (the weight-gradient GEMM runs after this).
+// Timed as one GA_PROF_FUSED_FWD dispatch with both bodies' work; the step counter of
+// GA_PROF_FUSED_DGRAD advances too: the counters count network steps.
+extern "C" int ga_fused_fwd_dgrad(const ga_fused_fwd_net* fwd, const ga_fused_dgrad_net* dgrad,
+                                  int64_t M, int width, int K, hipStream_t stream) {
+  GA_REQUIRE(fwd && dgrad && fwd->first && fwd->loss, "ga_fused_fwd_dgrad: null pointer");
+  const ga_fused_first_layer* first = fwd->first;
+  GA_REQUIRE(ga_fused_fwd_dgrad_supported(width, K, first->in_w) && !split_bf16_on(),
+             "ga_fused_fwd_dgrad: unsupported shape or mode");
+  GA_REQUIRE(dgrad->dZ2 == fwd->dZ && dgrad->lddz == fwd->lddz && dgrad->H1 == first->H &&
+                 dgrad->ldh == first->ldh && dgrad->X == first->X &&
+                 dgrad->ldx == first->ldx && dgrad->idx == fwd->loss->idx &&
+                 !dgrad->sum_w.src && !dgrad->sum_b.src,
+             "ga_fused_fwd_dgrad: the two descriptors are not one step's");
+  FwdDgradParams pp;
+  double f0 = 0.0, f1 = 0.0;
+  int rc = fwd_build(*fwd, M, width, K, &pp.f, &f0);
+  if (rc) return rc;
+  rc = dgrad_build(*dgrad, M, K, width, first->in_w, &pp.d, &f1);
+  if (rc) return rc;
+  const bool dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS;
+  pp.f.dbg = dbg ? g_ft_dbg : nullptr;
+  pp.d.dbg = dbg ? g_dg_dbg : nullptr;
+  const dim3 grid((unsigned)ga_fused_tiles(M));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ga_prof_events(GA_PROF_FUSED_FWD, f0 + f1, &e0, &e1);
+  ga_prof_count(GA_PROF_FUSED_DGRAD);
+  if (width == 64)
+    hipExtLaunchKernelGGL((fwd_dgrad_kernel<64, 2, 2, 0>), grid, dim3(256), 0, stream, e0,
+                          e1, 0, pp);
+  else if (width == 128)
+    hipExtLaunchKernelGGL((fwd_dgrad_kernel<128, 1, 4, 0>), grid, dim3(256), 0, stream, e0,
+                          e1, 0, pp);
+  else if ((first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
+    hipExtLaunchKernelGGL((fwd_dgrad_kernel<256, 1, 8, 5>), grid, dim3(512), 0, stream, e0,
+                          e1, 0, pp);
+  else
+    hipExtLaunchKernelGGL((fwd_dgrad_kernel<256, 1, 8, 0>), grid, dim3(512), 0, stream, e0,
+                          e1, 0, pp);
+  GA_CHECK_LAUNCH("fwd_dgrad");
   return GA_OK;
 }
 

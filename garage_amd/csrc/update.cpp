@@ -107,6 +107,24 @@ static int slab_sum_in_dgrad_on() {
   return g_slab_sum_in_dgrad;
 }
 
+// The forward + loss launch and the data-gradient launch of a step as ONE launch
+// (fused_train.hip: fwd_dgrad_kernel), where one network's step has both, in exact fp32
+// and at a shape the kernel is compiled for; the middle layer's weight-gradient GEMM
+// then follows it and the optimizer launch sums that layer's slabs itself.  Same bits
+// either way.  0 (or GARAGE_AMD_FUSED_FWD_DGRAD=0 in the environment): two launches
+static int g_fused_fwd_dgrad = -1;
+extern "C" int ga_set_fused_fwd_dgrad(int on) {
+  g_fused_fwd_dgrad = on != 0;
+  return 0;
+}
+static int fused_fwd_dgrad_on() {
+  if (g_fused_fwd_dgrad < 0) {
+    const char* e = getenv("GARAGE_AMD_FUSED_FWD_DGRAD");
+    g_fused_fwd_dgrad = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_fused_fwd_dgrad;
+}
+
 namespace {
 struct FusedPlan {
   bool ok = false;
@@ -268,6 +286,7 @@ float step_scale(const ga_update_args* a, int64_t k) {
 // from this description.  Filled in place: the descriptors point into it.
 struct FusedStep {
   int64_t splits;
+  bool fwd_dgrad;           // fwd + dgrad go out as one launch (ga_fused_fwd_dgrad)
   ga_fused_loss_args la;
   double* lpart;
   float* hpart;
@@ -280,8 +299,9 @@ struct FusedStep {
   ga_reduce_net red;
 };
 
+// one_net: the step is launched for this network alone (not the merged pair schedule)
 void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t M,
-                const int32_t* idx, FusedStep* s) {
+                const int32_t* idx, FusedStep* s, bool one_net) {
   const ga_mlp_desc* d = a->desc;
   const int L = d->n_layers;
   const int wl = d->dims[L - 1];  // last hidden width
@@ -335,6 +355,7 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
   // hidden layer's weights, the next step's forward launch then needs no plane launch)
   r.pl_beg = 0; r.pl_rows = r.pl_cols = 0;
   r.presummed = 0;
+  s->fwd_dgrad = false;
   if (f.first && L == 3 && r.do_adam && ga_split_bf16_any() && d->dims[2] == 256 &&
       d->dims[1] % 32 == 0) {
     r.pl_beg = d->w_off[1]; r.pl_rows = d->dims[2]; r.pl_cols = d->dims[1];
@@ -366,7 +387,11 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
     g.H1 = a->acts + d->act_off[0]; g.ldh = r4(d->dims[1]);
     g.X = a->X; g.ldx = a->ldx; g.idx = idx; g.wpart = s->wpart;
     g.sum_w = g.sum_b = ga_slab_range{nullptr, 0, 0, 0};
-    if (L == 3 && s->splits > 1 && slab_sum_in_dgrad_on()) {
+    // (the fused launch runs BEFORE the weight-gradient GEMM: no slabs to sum there)
+    s->fwd_dgrad = one_net && L == 3 && first_in_kernel && fused_fwd_dgrad_on() &&
+                   !ga_split_bf16_any() &&
+                   ga_fused_fwd_dgrad_supported(d->dims[2], d->dims[1], d->dims[0]);
+    if (L == 3 && s->splits > 1 && slab_sum_in_dgrad_on() && !s->fwd_dgrad) {
       // The middle layer's slabs (regions 2 and 3).  The weight-gradient GEMM that
       // writes them is the launch right before the data-gradient launch, on the same
       // stream, in both schedules: ga_mlp_backward_range_f32 in run_minibatch_fused,
@@ -393,6 +418,8 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
 // layers' backward GEMMs, the data gradient into the first hidden layer with the
 // first layer's weight gradient in one launch, and one reduction + Adam launch.
 // (Narrow networks: everything up to the reduction in one launch.)
+// s.fwd_dgrad: the forward + loss launch carries the data-gradient launch's work too,
+// the middle layer's weight-gradient GEMM follows it, then the reduction + Adam launch.
 int run_minibatch_fused(const ga_update_args* a, const FusedPlan& f, int64_t k,
                         int64_t M, const int32_t* idx, ga_stream_t stream_,
                         const ArOrder* order) {
@@ -400,7 +427,7 @@ int run_minibatch_fused(const ga_update_args* a, const FusedPlan& f, int64_t k,
   const ga_mlp_desc* d = a->desc;
   const int L = d->n_layers;
   FusedStep s;
-  fused_step(a, f, k, M, idx, &s);
+  fused_step(a, f, k, M, idx, &s, true);
   int rc;
   if (f.narrow) {
     rc = ga_narrow_train_step(a->params, d->w_off, d->b_off, d->dims[0], d->dims[1],
@@ -415,13 +442,16 @@ int run_minibatch_fused(const ga_update_args* a, const FusedPlan& f, int64_t k,
                               a->ldo, stream_);
       if (rc) return rc;
     }
-    rc = ga_fused_fwd_head_loss(&s.fwd, 1, M, d->dims[L - 1], d->dims[L - 2], stream);
+    if (s.fwd_dgrad)
+      rc = ga_fused_fwd_dgrad(&s.fwd, &s.dgrad, M, d->dims[L - 1], d->dims[L - 2], stream);
+    else
+      rc = ga_fused_fwd_head_loss(&s.fwd, 1, M, d->dims[L - 1], d->dims[L - 2], stream);
     if (rc) return rc;
     rc = ga_mlp_backward_range_f32(d, a->params, a->X, a->ldx, idx, M, a->acts, nullptr,
                                    a->ldo, a->dacts, a->slabs, a->n_flat, s.splits, L - 2,
                                    f.first ? 1 : 0, stream);
     if (rc) return rc;
-    if (f.first) {
+    if (f.first && !s.fwd_dgrad) {
       rc = ga_fused_dgrad_wgrad0(&s.dgrad, 1, M, d->dims[1], d->dims[2], d->dims[0],
                                  stream);
       if (rc) return rc;
@@ -672,7 +702,7 @@ int run_minibatch_merged(const ga_update_args* a, const ga_update_args* b, int64
     int64_t start;
     minibatch_range(two[i], k, &start, &M);
     fused_step(two[i], fused_plan(two[i]->desc, M), k, M,
-               two[i]->perm ? two[i]->perm + start : nullptr, &s[i]);
+               two[i]->perm ? two[i]->perm + start : nullptr, &s[i], false);
   }
   const ga_fused_fwd_net fwd[2] = {s[0].fwd, s[1].fwd};
   const ga_wgrad_mid_net mid[2] = {s[0].mid, s[1].mid};

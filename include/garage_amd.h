@@ -868,6 +868,14 @@ GA_API int ga_set_pipelined_kloop(int on);
  * reads one partial of them instead of all: 1 default, 0 the optimizer launch sums
  * them (also GARAGE_AMD_SLAB_SUM_IN_DGRAD=0).  Bit-identical results either way. */
 GA_API int ga_set_slab_sum_in_dgrad(int on);
+/* Fused optimizer steps of ONE network with two hidden layers of the same width (64, 128
+ * or 256 units, <= 32 inputs), exact fp32: the forward + loss launch and the
+ * data-gradient launch go out as one launch whose workgroups keep the last hidden
+ * layer's data gradient in LDS between the two; the middle layer's weight-gradient GEMM
+ * follows it and the optimizer launch sums that layer's slabs itself
+ * (ga_set_slab_sum_in_dgrad has nothing to act on in such a step).  0: two launches
+ * (also GARAGE_AMD_FUSED_FWD_DGRAD=0).  Bit-identical results either way. */
+GA_API int ga_set_fused_fwd_dgrad(int on);
 /* EXPERIMENT, off by default (also GARAGE_AMD_SPLIT_BF16=1): the k-loops of the fused
  * update kernels that have such an instantiation (256-unit networks, first layer in
  * the kernel) run on v_mfma_f32_32x32x16_bf16 with every fp32 operand split exactly
