@@ -1,5 +1,6 @@
 // Rollout-side kernels: the per-layer path's action head, the device environments
-// (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole), per-step
+// (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole,
+// Pendulum), per-step
 // episode bookkeeping and the ragged -> packed compaction.  A step's device code is
 // rollout_dev.h's; here are its kernels and the one converter and check of each C-ABI
 // struct: ga_head_to_dev, ga_record_to_dev / check_record, ga_env_to_dev / check_env.
@@ -512,6 +513,14 @@ CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t) {
   return d;
 }
 
+PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t) {
+  PendulumEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
+  ga_key(e->seed, &d.k0, &d.k1);
+  d.state = e->state; d.t = e->t; d.resets = e->resets;
+  return d;
+}
+
 static int check_env(const ga_synth_env* e, const char* who) {
   GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
   GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
@@ -555,6 +564,14 @@ static int check_env(const ga_multi_point_env* e, const char* who) {
 }
 
 static int check_env(const ga_cartpole_env* e, const char* who) {
+  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_pendulum_env* e, const char* who) {
   GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
   GA_REQUIRE(e->n > 0, "%s: bad env size", who);
   GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
@@ -620,6 +637,7 @@ GA_BUILD_ENV_STEP_OF(ga_point_env)
 GA_BUILD_ENV_STEP_OF(ga_grid_env)
 GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
 GA_BUILD_ENV_STEP_OF(ga_cartpole_env)
+GA_BUILD_ENV_STEP_OF(ga_pendulum_env)
 #undef GA_BUILD_ENV_STEP_OF
 
 // Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
@@ -701,6 +719,18 @@ extern "C" int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t co
   ga_key(seed, &k0, &k1);
   const CartPoleState s = cartpole_reset_draw(k0, k1, (uint32_t)env_id, counter);
   out4[0] = s.x; out4[1] = s.xd; out4[2] = s.th; out4[3] = s.thd;
+  return GA_OK;
+}
+
+// the device's pendulum_reset_draw on the host (garage_amd.envs.PendulumEnv starts its
+// episodes from it)
+extern "C" int ga_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                      float out2[2]) {
+  GA_REQUIRE(out2, "ga_pendulum_reset_draw: null pointer");
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  const PendulumState s = pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
+  out2[0] = s.th; out2[1] = s.thd;
   return GA_OK;
 }
 

@@ -1,7 +1,8 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
 // policy + env step of policy_fused.hip, each written once: Philox, the head of a step
 // (HeadDev, head_one), the device environments (synthetic, PointEnv, GridWorldEnv,
-// MultiEnvWrapper over PointEnv, CartPole; env_pre / env_core / env_reset_one of each),
+// MultiEnvWrapper over PointEnv, CartPole, Pendulum; env_pre / env_core / env_reset_one
+// of each),
 // the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
 // (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
 #pragma once
@@ -49,6 +50,7 @@ static constexpr uint32_t STREAM_OBS = 0, STREAM_REWARD = 1, STREAM_LENGTH = 2;
 static constexpr uint32_t STREAM_ACTION = 3;
 static constexpr uint32_t STREAM_TASK = 4;
 static constexpr uint32_t STREAM_CARTPOLE = 5;
+static constexpr uint32_t STREAM_PENDULUM = 6;
 
 // the two Philox key words of a 64-bit seed
 static __host__ __device__ __forceinline__ void ga_key(uint64_t seed, uint32_t* k0,
@@ -559,6 +561,153 @@ static __device__ __forceinline__ void env_core(const CartPoleEnv& e, int64_t i,
   next_row[0] = s.x; next_row[1] = s.xd; next_row[2] = s.th; next_row[3] = s.thd;
 }
 
+// ---- Pendulum (include/garage_amd.h states the arithmetic, operation by operation) ----
+// One fp32 operation per statement, no contraction.  sincos, the step and the reset
+// draw are written once, here.
+struct PendulumEnv {
+  int64_t n;
+  int64_t env_id0;   // global id of env 0 of this shard
+  int max_len;
+  uint32_t k0, k1;   // seed
+  float* state;      // [n, 2] theta in [-PI, PI], theta_dot in [-8, 8]
+  int32_t* t;        // [n] steps taken in the current episode
+  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
+};
+struct PendulumPre {
+  float th, thd;
+  int t, ep_t;
+};
+struct PendulumState { float th, thd; };
+
+constexpr float PENDULUM_PI = (float)3.141592653589793;
+constexpr float PENDULUM_TWO_PI = (float)6.283185307179586;
+constexpr float PENDULUM_HALF_PI = (float)1.5707963267948966;
+
+// sin and cos of |th| <= PI: folded to |r| <= HALF_PI, then two fixed polynomials
+static __host__ __device__ __forceinline__ void pendulum_sincos(float th, float* sn,
+                                                                float* cs) {
+#pragma clang fp contract(off)
+  constexpr float S3 = (float)(-1.0 / 6.0), S5 = (float)(1.0 / 120.0),
+                  S7 = (float)(-1.0 / 5040.0), S9 = (float)(1.0 / 362880.0),
+                  S11 = (float)(-1.0 / 39916800.0), S13 = (float)(1.0 / 6227020800.0);
+  constexpr float C2 = -0.5f, C4 = (float)(1.0 / 24.0), C6 = (float)(-1.0 / 720.0),
+                  C8 = (float)(1.0 / 40320.0), C10 = (float)(-1.0 / 3628800.0),
+                  C12 = (float)(1.0 / 479001600.0), C14 = (float)(-1.0 / 87178291200.0);
+  float r = th, sg = 1.0f;
+  if (th > PENDULUM_HALF_PI) {
+    r = PENDULUM_PI - th;
+    sg = -1.0f;
+  } else if (th < -PENDULUM_HALF_PI) {
+    r = -PENDULUM_PI - th;
+    sg = -1.0f;
+  }
+  const float t2 = r * r;
+  float ps = t2 * S13;
+  ps = S11 + ps;
+  ps = t2 * ps;
+  ps = S9 + ps;
+  ps = t2 * ps;
+  ps = S7 + ps;
+  ps = t2 * ps;
+  ps = S5 + ps;
+  ps = t2 * ps;
+  ps = S3 + ps;
+  ps = t2 * ps;
+  ps = 1.0f + ps;
+  const float sp = r * ps;
+  // (next to +-HALF_PI the product can round to 1 + 2^-23; the cosine is 1 + a sum
+  // that is never positive)
+  *sn = sp < -1.0f ? -1.0f : (sp > 1.0f ? 1.0f : sp);
+  float pc = t2 * C14;
+  pc = C12 + pc;
+  pc = t2 * pc;
+  pc = C10 + pc;
+  pc = t2 * pc;
+  pc = C8 + pc;
+  pc = t2 * pc;
+  pc = C6 + pc;
+  pc = t2 * pc;
+  pc = C4 + pc;
+  pc = t2 * pc;
+  pc = C2 + pc;
+  pc = t2 * pc;
+  pc = 1.0f + pc;
+  *cs = sg * pc;
+}
+
+// the state reset number `counter` gives env `env` (global id)
+static __host__ __device__ __forceinline__ PendulumState pendulum_reset_draw(
+    uint32_t k0, uint32_t k1, uint32_t env, uint32_t counter) {
+#pragma clang fp contract(off)
+  const U4 r = philox4x32_10(env, counter, 0u, STREAM_PENDULUM << 16, k0, k1);
+  const float w0 = PENDULUM_TWO_PI * u32_unit_interval(r.x);
+  const float w1 = 2.0f * u32_unit_interval(r.y);
+  return PendulumState{-PENDULUM_PI + w0, -1.0f + w1};
+}
+
+// one step with torque `a` (clipped here); returns the reward.  Only the sine of the
+// old angle is evaluated: the cost and the dynamics need no cosine.
+static __host__ __device__ __forceinline__ float pendulum_advance(PendulumState* s,
+                                                                  float a) {
+#pragma clang fp contract(off)
+  const float th = s->th, thd = s->thd;
+  const float u = a < -2.0f ? -2.0f : (a > 2.0f ? 2.0f : a);
+  float sn, cs_unused;
+  pendulum_sincos(th, &sn, &cs_unused);
+  const float c1 = th * th;
+  const float c2 = thd * thd;
+  const float c3 = 0.1f * c2;
+  const float c4 = c1 + c3;
+  const float c5 = u * u;
+  const float c6 = 0.001f * c5;
+  const float cost = c4 + c6;
+  const float g1 = 15.0f * sn;
+  const float g2 = 3.0f * u;
+  const float acc = g1 + g2;
+  const float dv = acc * 0.05f;
+  const float v = thd + dv;
+  const float dth = v * 0.05f;
+  float nth = th + dth;
+  const float nthd = v < -8.0f ? -8.0f : (v > 8.0f ? 8.0f : v);
+  if (nth >= PENDULUM_PI) nth = nth - PENDULUM_TWO_PI;
+  else if (nth < -PENDULUM_PI) nth = nth + PENDULUM_TWO_PI;
+  s->th = nth;
+  s->thd = nthd;
+  return -cost;
+}
+
+static __device__ __forceinline__ void env_reset_one(const PendulumEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const PendulumState s =
+      pendulum_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float sn, cs;
+  pendulum_sincos(s.th, &sn, &cs);
+  float* st = e.state + 2 * i;
+  float* o = obs + i * ldo;
+  st[0] = s.th; st[1] = s.thd;
+  o[0] = cs; o[1] = sn; o[2] = s.thd;
+}
+
+static __device__ __forceinline__ void env_core(const PendulumEnv& e, int64_t i,
+                                                const PendulumPre& p, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  PendulumState s{p.th, p.thd};
+  *reward = pendulum_advance(&s, a[0]);
+  float sn, cs;
+  pendulum_sincos(s.th, &sn, &cs);
+  float* st = e.state + 2 * i;
+  st[0] = s.th; st[1] = s.thd;
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // never done: the step that reaches max_len is TIMEOUT (_dtypes.py:42-68)
+  *step_type = tn >= e.max_len ? 3 : tn == 1 ? 0 : 1;
+  next_row[0] = cs; next_row[1] = sn; next_row[2] = s.thd;
+}
+
 // What a step of env i reads of the env's and the worker's state: loaded up front,
 // so that no load waits behind the step's own stores (the memory counter retires in
 // order).  `o` holds the observation entries the reward looks at when they are few.
@@ -802,6 +951,15 @@ static __device__ __forceinline__ CartPolePre env_pre(const CartPoleEnv& e, int6
   s.ep_t = 0;
   return s;
 }
+static __device__ __forceinline__ PendulumPre env_pre(const PendulumEnv& e, int64_t i) {
+  PendulumPre s;
+  const float* st = e.state + 2 * i;
+  s.th = st[0];
+  s.thd = st[1];
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
 template <class Inner>
 static __device__ __forceinline__ auto env_pre(const MultiTaskEnv<Inner>& e, int64_t i) {
   MultiTaskPre<decltype(env_pre(e.in, i))> s;
@@ -866,6 +1024,7 @@ ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
 ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_point_env* e,
                                                              int64_t info_ld);
 ga_rollout::CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t info_ld);
+ga_rollout::PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t info_ld);
 template <class GaEnv>
 using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;

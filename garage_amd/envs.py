@@ -18,7 +18,9 @@ Philox-keyed).  ``PointVecEnv`` and ``GridWorldVecEnv`` are the reference's own
 arithmetic), stepped inside the sampler's one-launch rollout like the synthetic
 env; ``MultiTaskPointVecEnv`` is ``MultiEnvWrapper`` over ``PointEnv`` tasks, the
 task switch at every reset included.  ``CartPoleVecEnv`` is gym's CartPole-v1 in a
-fixed fp32 arithmetic (``CartPoleEnv`` is its per-env numpy twin).  ``HostVecEnv`` adapts a list of ordinary per-env objects (any
+fixed fp32 arithmetic (``CartPoleEnv`` is its per-env numpy twin), and
+``PendulumVecEnv`` gym's Pendulum-v0 the same way (twin: ``PendulumEnv``).
+``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
 """
@@ -793,6 +795,224 @@ class CartPoleEnv:
         pass
 
 
+def _pendulum_spec(max_episode_length):
+    high = np.array([1.0, 1.0, 8.0], dtype=np.float32)
+    return EnvSpec(Box(-high, high), Box(-2.0, 2.0, (1, )),
+                   max_episode_length=max_episode_length)
+
+
+class PendulumVecEnv(_DeviceVecEnv):
+    """``n_envs`` pendulums (gym 0.17's ``Pendulum-v0``: the same constants,
+    update order, clips of torque and speed, cost and reset ranges) stepped by
+    one HIP kernel, one thread per env, inside the sampler's one-launch rollout.
+
+    Observation ``(cos th, sin th, thdot)`` in ``Box(-[1, 1, 8], [1, 1, 8])``,
+    one torque in ``Box(-2, 2, (1,))``: the env clips the torque itself, so any
+    float may be passed and the batch keeps the policy's own actions.  Reward
+    ``-(th^2 + 0.1 thdot^2 + 0.001 u^2)`` of the state before the step.  An
+    episode never terminates: every ending is TIMEOUT.
+    ``include/garage_amd.h`` states the arithmetic operation by operation;
+    :class:`PendulumEnv` is the per-env numpy twin that gives the same bits.
+    ``set_state`` / ``get_state`` move the ``(n, 2)`` float32 states
+    ``(th, thdot)`` (scripted starts; the step counters are left alone).
+
+    Deviations from gym:
+
+    - fp32 throughout (gym steps in float64 and casts the observation): one
+      step differs from the float64 equations by less than 1e-6 in the
+      observation and 3e-6 in the reward;
+    - ``sin`` / ``cos`` are fixed polynomials on the angle folded to
+      ``[-pi/2, pi/2]``, within 2e-7 of the functions;
+    - the angle is kept wrapped to ``[-PI, PI]`` (gym lets it grow and wraps it
+      in the cost): the observation is periodic and ``angle_normalize`` of a
+      wrapped angle is the angle itself, so the dynamics are gym's;
+    - resets draw from Philox4x32-10 keyed ``(seed; env_id0 + i, the member's
+      reset counter)`` instead of gym's ``np_random``
+      (:func:`pendulum_reset_draw` gives the same state on the host);
+    - ``max_episode_length`` must be finite (default 200, Pendulum-v0's
+      TimeLimit): the step that reaches it is TIMEOUT.
+    """
+
+    _KIND = _lib.ENV_PENDULUM
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+
+    def __init__(self, n_envs, max_episode_length=200, seed=0, env_id0=0,
+                 device=None):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = _pendulum_spec(self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.PendulumEnv()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def set_state(self, states):
+        """Every member's ``(th, thdot)`` <- row of ``states`` (``(n, 2)``
+        float32, ``|th| <= PI``); the current observations follow."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.shape != (self.n_envs, 2):
+            raise ValueError('set_state needs an ({}, 2) array, got {}'.format(
+                self.n_envs, states.shape))
+        if not (np.abs(states[:, 0]) <= PendulumEnv.PI).all():
+            raise ValueError('set_state needs angles in [-PI, PI]')
+        sn, cs = PendulumEnv.sincos(states[:, 0])
+        obs = np.stack([cs, sn, states[:, 1]], axis=-1).astype(np.float32)
+        self._state.copy_(torch.from_numpy(states))
+        self.obs[:, :3].copy_(torch.from_numpy(obs))
+
+    def get_state(self):
+        """The ``(n, 2)`` float32 states ``(th, thdot)``."""
+        return self._state.cpu().numpy()
+
+
+def pendulum_reset_draw(seed, env_id, counter):
+    """The ``(2,)`` float32 state ``(th, thdot)`` reset number ``counter`` gives
+    member ``env_id`` (= ``env_id0 + i``) of a :class:`PendulumVecEnv` with this
+    seed (host only, no GPU)."""
+    out = (C.c_float * 2)()
+    call('ga_pendulum_reset_draw', int(seed), int(env_id), int(counter), out)
+    return np.array(out, dtype=np.float32)
+
+
+PendulumStep = collections.namedtuple(
+    'PendulumStep', ['action', 'reward', 'observation', 'env_info',
+                     'step_type'])
+
+
+def _fact(k):
+    out = 1.0
+    for j in range(2, k + 1):
+        out *= j
+    return out
+
+
+class PendulumEnv:
+    """One member of :class:`PendulumVecEnv` on the host, in numpy fp32: the
+    same operations in the same order (``include/garage_amd.h``) and the same
+    Philox reset draws, so observations, rewards and step types equal the
+    device batch's bit for bit.  garage's ``Environment`` shape --
+    ``reset() -> (obs, {})``, ``step(a)`` with ``reward / observation /
+    step_type`` -- so a list of them goes behind :class:`HostVecEnv`."""
+
+    PI = _F(3.141592653589793)
+    TWO_PI = _F(6.283185307179586)
+    HALF_PI = _F(1.5707963267948966)
+    # S[j] = S(2j + 3), C[j] = C(2j + 2): the Taylor coefficients rounded once
+    S = tuple(_F((-1.0)**(j + 1) / _fact(2 * j + 3)) for j in range(6))
+    C = tuple(_F((-1.0)**(j + 1) / _fact(2 * j + 2)) for j in range(7))
+
+    def __init__(self, seed=0, env_id=0, max_episode_length=200):
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = _pendulum_spec(self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(2, dtype=np.float32)
+        self._t = 0
+
+    @classmethod
+    def sincos(cls, th):
+        """``(sin, cos)`` of ``th`` (float32, ``|th| <= PI``), every line one
+        fp32 operation."""
+        th = np.asarray(th, dtype=np.float32)
+        one = _F(1.0)
+        hi = th > cls.HALF_PI
+        lo = th < -cls.HALF_PI
+        r_hi = cls.PI - th
+        r_lo = (-cls.PI) - th
+        r = np.where(hi, r_hi, np.where(lo, r_lo, th)).astype(np.float32)
+        sg = np.where(hi | lo, _F(-1.0), one).astype(np.float32)
+        t2 = r * r
+        ps = t2 * cls.S[5]
+        for j in (4, 3, 2, 1, 0):
+            ps = cls.S[j] + ps
+            ps = t2 * ps
+        ps = one + ps
+        sp = r * ps
+        sn = np.where(sp < -one, -one, np.where(sp > one, one, sp))
+        sn = sn.astype(np.float32)
+        pc = t2 * cls.C[6]
+        for j in (5, 4, 3, 2, 1, 0):
+            pc = cls.C[j] + pc
+            pc = t2 * pc
+        pc = one + pc
+        cs = sg * pc
+        return sn, cs
+
+    @classmethod
+    def advance(cls, state, action):
+        """One step of ``state`` (``(..., 2)`` float32 ``(th, thdot)``) with
+        the torques ``action`` (``(...)``; clipped here): the new states, the
+        observations ``(..., 3)`` and the rewards.  Every line is one fp32
+        operation."""
+        state = np.asarray(state, dtype=np.float32)
+        a = np.asarray(action, dtype=np.float32)
+        th, thd = state[..., 0], state[..., 1]
+        two, eight = _F(2.0), _F(8.0)
+        u = np.where(a < -two, -two, np.where(a > two, two, a))
+        u = u.astype(np.float32)
+        sn, _ = cls.sincos(th)
+        c1 = th * th
+        c2 = thd * thd
+        c3 = _F(0.1) * c2
+        c4 = c1 + c3
+        c5 = u * u
+        c6 = _F(0.001) * c5
+        cost = c4 + c6
+        g1 = _F(15.0) * sn
+        g2 = _F(3.0) * u
+        acc = g1 + g2
+        dv = acc * _F(0.05)
+        v = thd + dv
+        dth = v * _F(0.05)
+        nth = th + dth
+        nthd = np.where(v < -eight, -eight, np.where(v > eight, eight, v))
+        nthd = nthd.astype(np.float32)
+        down = nth - cls.TWO_PI
+        up = nth + cls.TWO_PI
+        nth = np.where(nth >= cls.PI, down, np.where(nth < -cls.PI, up, nth))
+        nth = nth.astype(np.float32)
+        sn2, cs2 = cls.sincos(nth)
+        new = np.stack([nth, nthd], axis=-1).astype(np.float32)
+        obs = np.stack([cs2, sn2, nthd], axis=-1).astype(np.float32)
+        return new, obs, (-cost).astype(np.float32)
+
+    def _obs(self):
+        sn, cs = self.sincos(self.state[0])
+        return np.array([cs, sn, self.state[1]], dtype=np.float32)
+
+    def reset(self):
+        self.state = pendulum_reset_draw(self.seed, self.env_id, self.resets)
+        self.resets += 1
+        self._t = 0
+        return self._obs(), {}
+
+    def step(self, action):
+        a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
+        self.state, obs, reward = self.advance(self.state, a)
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length, False)
+        return PendulumStep(action, _F(reward), obs, {}, st)
+
+    def close(self):
+        pass
+
+
 class NormalizedVecEnv(VecEnv):
     """``garage.envs.normalize`` for a device batch (``envs/normalized_env.py``).
 
@@ -1071,4 +1291,5 @@ __all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
            'MultiTaskPointVecEnv', 'round_robin_strategy',
            'uniform_random_strategy', 'task_draw', 'GRID_MAPS',
            'CartPoleVecEnv', 'CartPoleEnv', 'cartpole_reset_draw',
+           'PendulumVecEnv', 'PendulumEnv', 'pendulum_reset_draw',
            'NormalizedVecEnv', 'HostVecEnv', 'StepType']

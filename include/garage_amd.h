@@ -625,13 +625,84 @@ typedef struct {
 GA_API int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                   float out4[4]);
 
+/* Pendulum (gym 0.17's Pendulum-v0: g = 10, m = l = 1, dt = 0.05, speed clipped to
+ * [-8, 8], torque to [-2, 2]), observation (cos th, sin th, thdot), obs_dim 3, one
+ * action column holding the torque (the env clips it; any float may be passed).  An
+ * episode never terminates: the step that reaches max_episode_length (1..65535) is
+ * TIMEOUT.
+ *
+ * The arithmetic is fixed here as CartPole's is above: every operation below is ONE
+ * fp32 operation, rounded to nearest on its own (no fused multiply-add), evaluated in
+ * the order the parentheses give; a constant written (float)(expr) is the double value
+ * of expr rounded to fp32.  The state is (th, thd) with th kept in [-PI, PI]:
+ *
+ *   PI = (float)3.141592653589793   TWO_PI = (float)6.283185307179586 ( = 2 PI exactly)
+ *   HALF_PI = (float)1.5707963267948966
+ *
+ * sincos(th), |th| <= PI: the angle is folded to |r| <= HALF_PI (+ half an ulp of PI),
+ * where the two fixed Horner polynomials -- not library calls -- stay within 2e-7 of
+ * sin and cos:
+ *   th >  HALF_PI: r = PI - th,    sg = -1
+ *   th < -HALF_PI: r = (-PI) - th, sg = -1
+ *   else           r = th,         sg =  1
+ *   t2 = r * r
+ *   sp = r * (1.0f + t2 * (S3 + t2 * (S5 + t2 * (S7 + t2 * (S9 + t2 * (S11 + t2 * S13))))))
+ *   sn = sp < -1.0f ? -1.0f : (sp > 1.0f ? 1.0f : sp)   (sp reaches 1 + 2^-23 next to
+ *                                                        +-HALF_PI; cs cannot pass 1)
+ *   cs = sg * (1.0f + t2 * (C2 + t2 * (C4 + t2 * (C6 + t2 * (C8 + t2 * (C10 +
+ *                                                     t2 * (C12 + t2 * C14)))))))
+ *     S(2k+1) = (float)((-1)^k / (2k+1)!):  S3 = (float)(-1.0 / 6.0), S5 = (float)(1.0 /
+ *     120.0), S7 = (float)(-1.0 / 5040.0), S9 = (float)(1.0 / 362880.0), S11 =
+ *     (float)(-1.0 / 39916800.0), S13 = (float)(1.0 / 6227020800.0)
+ *     C(2k) = (float)((-1)^k / (2k)!):  C2 = -0.5f, C4 = (float)(1.0 / 24.0), C6 =
+ *     (float)(-1.0 / 720.0), C8 = (float)(1.0 / 40320.0), C10 = (float)(-1.0 /
+ *     3628800.0), C12 = (float)(1.0 / 479001600.0), C14 = (float)(-1.0 / 87178291200.0)
+ *
+ * step with action a (th, thd: the state BEFORE the step):
+ *   u    = a < -2.0f ? -2.0f : (a > 2.0f ? 2.0f : a)
+ *   sn   = the sine of sincos(th)
+ *   cost = ((th * th) + (0.1f * (thd * thd))) + (0.001f * (u * u))
+ *   v    = thd + (((15.0f * sn) + (3.0f * u)) * 0.05f)
+ *   nth  = th + (v * 0.05f)                 (the UNCLIPPED new speed: Pendulum-v0's order)
+ *   nthd = v < -8.0f ? -8.0f : (v > 8.0f ? 8.0f : v)
+ *   nth >= PI: nth = nth - TWO_PI;   nth < -PI: nth = nth + TWO_PI
+ *   (cs', sn') = sincos(nth)
+ *   observation = (cs', sn', nthd), reward = -cost, state = (nth, nthd)
+ * |v * 0.05f| <= 0.4525, so one wrap is enough; gym's angle_normalize of a wrapped angle
+ * is the angle itself, and the observation is periodic: the wrap leaves the dynamics
+ * as they are.
+ *
+ * Reset number c (= resets[i], which then advances) of env i takes the words w_0, w_1
+ * of Philox4x32-10 with counter (env_id0 + i, c, 0, 6 << 16) -- stream 6 -- and key
+ * (seed & 0xffffffff, seed >> 32):
+ *   u_j = ((float)(w_j >> 8) + 0.5f) * 0x1p-24f
+ *   th  = (-PI) + (TWO_PI * u_0)            (may round to exactly PI)
+ *   thd = -1.0f + (2.0f * u_1)
+ * (gym draws th ~ U(-pi, pi), thdot ~ U(-1, 1) from its np_random); the first
+ * observation is (sincos(th), thd).  ga_pendulum_reset_draw below gives (th, thd) on
+ * the host. */
+typedef struct {
+  int64_t n, env_id0;
+  int32_t max_episode_length, pad_;
+  uint64_t seed;
+  float* state;     /* [n, 2] theta, theta_dot */
+  int32_t* t;       /* [n] steps taken in the current episode */
+  uint32_t* resets; /* [n] resets so far */
+} ga_pendulum_env;
+
+/* Host-only (no GPU needed): the state (th, thd) reset number `counter` gives env
+ * `env_id` (= env_id0 + i) of a ga_pendulum_env with this seed. */
+GA_API int ga_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                  float out2[2]);
+
 /* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env,
- * ga_multi_point_env or ga_cartpole_env. */
+ * ga_multi_point_env, ga_cartpole_env or ga_pendulum_env. */
 #define GA_ENV_SYNTH 0
 #define GA_ENV_POINT 1
 #define GA_ENV_GRID 2
 #define GA_ENV_MULTI_POINT 3
 #define GA_ENV_CARTPOLE 4
+#define GA_ENV_PENDULUM 5
 typedef struct {
   int32_t kind, pad_;
   const void* env;
