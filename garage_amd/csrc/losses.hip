@@ -516,7 +516,13 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
 // ---------------------------------------------------------------------------
 // Optimizers other than the default Adam (make_optimizer, _functions.py:25-65,
 // builds any torch.optim class): elementwise steps over the flat parameter buffer
-// with torch's single-tensor arithmetic, one rounding per torch operation.
+// with torch's single-tensor arithmetic, one rounding per torch operation.  Every
+// scalar torch forms in Python before it reaches a tensor -- 1 - beta1, 1 - beta2,
+// 1 - alpha, 1 - dampening, 1 - lr * weight_decay, -lr / bias_correction1,
+// sqrt(bias_correction2), -lr -- is formed on the host from the doubles in h and
+// rounded to fp32 once, as ga_adam_coeffs does (1.f - 0.999f is 1.3e-5 away from
+// float(1 - 0.999)); the kernel never subtracts two rounded constants.  addcdiv
+// is x + (value * t1) / t2, as in ga_adam_update and torch's elementwise kernels.
 //   kind 1  torch.optim.SGD      h = {lr, momentum, dampening, weight_decay};
 //                                flag bit 0 nesterov; s1 = momentum buffer
 //   kind 2  torch.optim.RMSprop  h = {lr, alpha, eps, weight_decay, momentum};
@@ -534,7 +540,11 @@ struct OptParams {
   float* s3;
   int64_t n;
   int kind, flags, first;  // first: step == 1 (SGD initialises its buffer with g)
-  float lr, h1, h2, h3, h4;
+  float neg_lr, h1, h2, h3, h4;
+  // derived in double, rounded once (ga_optimizer_step_f32)
+  float w1;     // 1 - dampening (kind 1), 1 - alpha (kind 2), 1 - beta1 (kind 3)
+  float w2;     // 1 - beta2 (kind 3)
+  float decay;  // 1 - lr * weight_decay (AdamW)
   float neg_step_size, bc2_sqrt;  // kind 3
 };
 
@@ -544,7 +554,7 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(OptParams a) {
   if (i >= a.n) return;
   float p = a.p[i], g = a.g[i];
   if (a.kind == 1) {
-    const float momentum = a.h1, dampening = a.h2, wd = a.h3;
+    const float momentum = a.h1, wd = a.h3;
     if (wd != 0.f) g = g + wd * p;                      // grad.add(param, alpha=wd)
     if (momentum != 0.f) {
       float buf;
@@ -552,22 +562,22 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(OptParams a) {
         buf = g;                                        // torch.clone(grad)
       } else {
         buf = a.s1[i] * momentum;                       // buf.mul_(momentum)
-        buf = buf + (1.f - dampening) * g;              //    .add_(grad, alpha=1-damp)
+        buf = buf + a.w1 * g;                           //    .add_(grad, alpha=1-damp)
       }
       a.s1[i] = buf;
       g = (a.flags & 1) ? g + momentum * buf : buf;     // nesterov
     }
-    p = p + (-a.lr) * g;                                // param.add_(grad, alpha=-lr)
+    p = p + a.neg_lr * g;                               // param.add_(grad, alpha=-lr)
   } else if (a.kind == 2) {
     const float alpha = a.h1, eps = a.h2, wd = a.h3, momentum = a.h4;
     if (wd != 0.f) g = g + wd * p;
     float sq = a.s1[i] * alpha;                         // square_avg.mul_(alpha)
-    sq = sq + ((1.f - alpha) * g) * g;                  //    .addcmul_(g, g, 1-alpha)
+    sq = sq + (a.w1 * g) * g;                           //    .addcmul_(g, g, 1-alpha)
     a.s1[i] = sq;
     float avg;
     if (a.flags & 1) {
       float ga = a.s3[i];
-      ga = fmaf(1.f - alpha, g - ga, ga);               // grad_avg.lerp_(g, 1-alpha)
+      ga = fmaf(a.w1, g - ga, ga);                      // grad_avg.lerp_(g, 1-alpha)
       a.s3[i] = ga;
       avg = sqrtf(sq + (-1.f * ga) * ga);               // addcmul(ga, ga, -1).sqrt_()
     } else {
@@ -578,20 +588,20 @@ __global__ __launch_bounds__(256) void optimizer_step_kernel(OptParams a) {
       float buf = a.s2[i] * momentum;                   // buf.mul_(momentum)
       buf = buf + g / avg;                              //    .addcdiv_(grad, avg)
       a.s2[i] = buf;
-      p = p + (-a.lr) * buf;
+      p = p + a.neg_lr * buf;                           // add_(buf, alpha=-lr)
     } else {
-      p = p + (-a.lr) * (g / avg);                      // addcdiv_(grad, avg, -lr)
+      p = p + (a.neg_lr * g) / avg;                     // addcdiv_(grad, avg, -lr)
     }
   } else {
-    const float beta1 = a.h1, beta2 = a.h2, eps = a.h3, wd = a.h4;
+    const float beta2 = a.h2, eps = a.h3, wd = a.h4;
     if (a.flags & 2) {
-      p = p * (1.f - a.lr * wd);                        // AdamW: param.mul_(1 - lr wd)
+      p = p * a.decay;                                  // AdamW: param.mul_(1 - lr wd)
     } else if (wd != 0.f) {
       g = g + wd * p;
     }
     float m = a.s1[i], v = a.s2[i];
-    m = fmaf(1.f - beta1, g - m, m);                    // exp_avg.lerp_(grad, 1-beta1)
-    v = v * beta2 + ((1.f - beta2) * g) * g;
+    m = fmaf(a.w1, g - m, m);                           // exp_avg.lerp_(grad, 1-beta1)
+    v = v * beta2 + (a.w2 * g) * g;
     a.s1[i] = m;
     a.s2[i] = v;
     float vv = v;
@@ -962,17 +972,23 @@ extern "C" int ga_optimizer_step_f32(int kind, float* params, const float* grads
   memset(&a, 0, sizeof(a));
   a.p = params; a.g = grads; a.s1 = s1; a.s2 = s2; a.s3 = s3; a.n = n;
   a.kind = kind; a.flags = flags; a.first = step == 1;
-  a.lr = (float)h[0]; a.h1 = (float)h[1]; a.h2 = (float)h[2]; a.h3 = (float)h[3];
-  a.h4 = (float)h[4];
+  a.neg_lr = (float)(-h[0]); a.h1 = (float)h[1]; a.h2 = (float)h[2];
+  a.h3 = (float)h[3]; a.h4 = (float)h[4];
+  // complements and products of the hyper-parameters: in double, rounded once
   if (kind == 1) {
     GA_REQUIRE(h[1] == 0.0 || s1, "ga_optimizer_step_f32: SGD momentum buffer");
+    a.w1 = (float)(1.0 - h[2]);
   } else if (kind == 2) {
     GA_REQUIRE(s1 && (h[4] <= 0.0 || s2) && (!(flags & 1) || s3),
                "ga_optimizer_step_f32: RMSprop state buffers");
+    a.w1 = (float)(1.0 - h[1]);
   } else {
     GA_REQUIRE(s1 && s2 && (!(flags & 1) || s3),
                "ga_optimizer_step_f32: Adam state buffers");
     const GaAdam c = ga_adam_coeffs(h[0], h[1], h[2], h[3], step);
+    a.w1 = c.lerp_w;
+    a.w2 = c.one_minus_beta2;
+    a.decay = (float)(1.0 - h[0] * h[4]);
     a.neg_step_size = c.neg_step_size;
     a.bc2_sqrt = c.bc2_sqrt;
   }

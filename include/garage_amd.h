@@ -348,7 +348,12 @@ GA_API int ga_adam_step_f32(float* params, const float* grads, float* exp_avg,
  *                               h = {lr, beta1, beta2, eps, weight_decay}; flags bit 0
  *                               amsgrad, bit 1 decoupled decay (AdamW); s1 exp_avg,
  *                               s2 exp_avg_sq, s3 max_exp_avg_sq
- * h: HOST pointer to 5 doubles; step counts from 1; unused state pointers may be NULL. */
+ * h: HOST pointer to 5 doubles; step counts from 1; unused state pointers may be NULL.
+ * Rounding: one fp32 rounding per torch tensor operation (lerp_ is one fused
+ * multiply-add; addcdiv is x + (value * t1) / t2).  Every scalar torch forms in Python
+ * -- 1 - beta1, 1 - beta2, 1 - alpha, 1 - dampening, 1 - lr * weight_decay,
+ * -lr / bias_correction1, sqrt(bias_correction2), -lr -- is formed here from the
+ * doubles in h and rounded to fp32 once, never from constants already rounded. */
 GA_API int ga_optimizer_step_f32(int kind, float* params, const float* grads, float* s1,
                                  float* s2, float* s3, int64_t n, int64_t step,
                                  const double* h, int flags, ga_stream_t stream);
