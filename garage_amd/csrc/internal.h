@@ -50,18 +50,21 @@ inline int ga_env_obs_dim(const ga_multi_point_env* e) {
 }
 inline int ga_env_obs_dim(const ga_cartpole_env*) { return 4; }
 inline int ga_env_obs_dim(const ga_pendulum_env*) { return 3; }
+inline int ga_env_obs_dim(const ga_double_pendulum_env*) { return 11; }
 inline int ga_env_discrete(const ga_synth_env* e) { return e->discrete != 0; }
 inline int ga_env_discrete(const ga_point_env*) { return 0; }
 inline int ga_env_discrete(const ga_grid_env*) { return 1; }
 inline int ga_env_discrete(const ga_multi_point_env*) { return 0; }
 inline int ga_env_discrete(const ga_cartpole_env*) { return 1; }
 inline int ga_env_discrete(const ga_pendulum_env*) { return 0; }
+inline int ga_env_discrete(const ga_double_pendulum_env*) { return 0; }
 inline int ga_env_act_width(const ga_synth_env* e) { return e->discrete ? 1 : e->act_dim; }
 inline int ga_env_act_width(const ga_point_env*) { return 2; }
 inline int ga_env_act_width(const ga_grid_env*) { return 1; }
 inline int ga_env_act_width(const ga_multi_point_env*) { return 2; }
 inline int ga_env_act_width(const ga_cartpole_env*) { return 1; }
 inline int ga_env_act_width(const ga_pendulum_env*) { return 1; }
+inline int ga_env_act_width(const ga_double_pendulum_env*) { return 1; }
 
 // f(const ga_<kind>_env*) of the env `ref` points to; `who` names the entry point in
 // the two errors this owns
@@ -78,6 +81,7 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
     case GA_ENV_MULTI_POINT: return f((const ga_multi_point_env*)ref->env);
     case GA_ENV_CARTPOLE: return f((const ga_cartpole_env*)ref->env);
     case GA_ENV_PENDULUM: return f((const ga_pendulum_env*)ref->env);
+    case GA_ENV_DOUBLE_PENDULUM: return f((const ga_double_pendulum_env*)ref->env);
   }
   ga_set_error("%s: unknown env kind %d", who, ref->kind);
   return -1;

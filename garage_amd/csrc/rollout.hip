@@ -1,6 +1,6 @@
 // Rollout-side kernels: the per-layer path's action head, the device environments
 // (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole,
-// Pendulum), per-step
+// Pendulum, the inverted double pendulum), per-step
 // episode bookkeeping and the ragged -> packed compaction.  A step's device code is
 // rollout_dev.h's; here are its kernels and the one converter and check of each C-ABI
 // struct: ga_head_to_dev, ga_record_to_dev / check_record, ga_env_to_dev / check_env.
@@ -521,6 +521,14 @@ PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t) {
   return d;
 }
 
+DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e, int64_t) {
+  DoublePendulumEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
+  ga_key(e->seed, &d.k0, &d.k1);
+  d.state = e->state; d.t = e->t; d.resets = e->resets;
+  return d;
+}
+
 static int check_env(const ga_synth_env* e, const char* who) {
   GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
   GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
@@ -572,6 +580,14 @@ static int check_env(const ga_cartpole_env* e, const char* who) {
 }
 
 static int check_env(const ga_pendulum_env* e, const char* who) {
+  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_double_pendulum_env* e, const char* who) {
   GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
   GA_REQUIRE(e->n > 0, "%s: bad env size", who);
   GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
@@ -638,6 +654,7 @@ GA_BUILD_ENV_STEP_OF(ga_grid_env)
 GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
 GA_BUILD_ENV_STEP_OF(ga_cartpole_env)
 GA_BUILD_ENV_STEP_OF(ga_pendulum_env)
+GA_BUILD_ENV_STEP_OF(ga_double_pendulum_env)
 #undef GA_BUILD_ENV_STEP_OF
 
 // Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
@@ -731,6 +748,20 @@ extern "C" int ga_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t co
   ga_key(seed, &k0, &k1);
   const PendulumState s = pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
   out2[0] = s.th; out2[1] = s.thd;
+  return GA_OK;
+}
+
+// the device's double_pendulum_reset_draw on the host
+// (garage_amd.envs.DoublePendulumEnv starts its episodes from it)
+extern "C" int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id,
+                                             uint32_t counter, float out6[6]) {
+  GA_REQUIRE(out6, "ga_double_pendulum_reset_draw: null pointer");
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  const DoublePendulumState s =
+      double_pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
+  out6[0] = s.x; out6[1] = s.th1; out6[2] = s.th2;
+  out6[3] = s.xd; out6[4] = s.th1d; out6[5] = s.th2d;
   return GA_OK;
 }
 

@@ -1,8 +1,8 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
 // policy + env step of policy_fused.hip, each written once: Philox, the head of a step
 // (HeadDev, head_one), the device environments (synthetic, PointEnv, GridWorldEnv,
-// MultiEnvWrapper over PointEnv, CartPole, Pendulum; env_pre / env_core / env_reset_one
-// of each),
+// MultiEnvWrapper over PointEnv, CartPole, Pendulum, the inverted double pendulum;
+// env_pre / env_core / env_reset_one of each),
 // the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
 // (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
 #pragma once
@@ -51,6 +51,7 @@ static constexpr uint32_t STREAM_ACTION = 3;
 static constexpr uint32_t STREAM_TASK = 4;
 static constexpr uint32_t STREAM_CARTPOLE = 5;
 static constexpr uint32_t STREAM_PENDULUM = 6;
+static constexpr uint32_t STREAM_DOUBLE_PENDULUM = 7;
 
 // the two Philox key words of a 64-bit seed
 static __host__ __device__ __forceinline__ void ga_key(uint64_t seed, uint32_t* k0,
@@ -708,6 +709,239 @@ static __device__ __forceinline__ void env_core(const PendulumEnv& e, int64_t i,
   next_row[0] = cs; next_row[1] = sn; next_row[2] = s.thd;
 }
 
+// ---- Inverted double pendulum on a cart (include/garage_amd.h states the arithmetic,
+// operation by operation) ----
+// One fp32 operation per statement, no contraction; `/` is the correctly rounded
+// division.  The step and the reset draw are written once, here; sin and cos are
+// Pendulum's.
+struct DoublePendulumEnv {
+  int64_t n;
+  int64_t env_id0;   // global id of env 0 of this shard
+  int max_len;
+  uint32_t k0, k1;   // seed
+  float* state;      // [n, 6] x, th1, th2, xd, th1d, th2d; th1, th2 in [-PI, PI]
+  int32_t* t;        // [n] steps taken in the current episode
+  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
+};
+struct DoublePendulumState { float x, th1, th2, xd, th1d, th2d; };
+struct DoublePendulumPre {
+  DoublePendulumState s;
+  int t, ep_t;
+};
+// what a step (or a reset) shows of the state it leaves: the sines and cosines of the
+// two angles and of their difference
+struct DoublePendulumTrig { float s1, c1, sd, cd, yt; };
+
+constexpr float DP_D1 = (float)(10.5 + 4.2 + 4.2);
+constexpr float DP_D2 = (float)((4.2 / 2.0 + 4.2) * 0.6);
+constexpr float DP_D3 = (float)(4.2 * 0.6 / 2.0);
+constexpr float DP_D4 = (float)((4.2 / 3.0 + 4.2) * 0.6 * 0.6);
+constexpr float DP_D5 = (float)(4.2 * 0.6 * 0.6 / 2.0);
+constexpr float DP_D6 = (float)(4.2 * 0.6 * 0.6 / 3.0);
+constexpr float DP_F1 = (float)((4.2 / 2.0 + 4.2) * 0.6 * 9.81);
+constexpr float DP_F2 = (float)(4.2 * 0.6 * 9.81 / 2.0);
+
+// the state reset number `counter` gives env `env` (global id)
+static __host__ __device__ __forceinline__ DoublePendulumState double_pendulum_reset_draw(
+    uint32_t k0, uint32_t k1, uint32_t env, uint32_t counter) {
+#pragma clang fp contract(off)
+  const U4 a = philox4x32_10(env, counter, 0u, STREAM_DOUBLE_PENDULUM << 16, k0, k1);
+  const U4 b = philox4x32_10(env, counter, 1u, STREAM_DOUBLE_PENDULUM << 16, k0, k1);
+  const float w0 = 0.2f * u32_unit_interval(a.x);
+  const float w1 = 0.2f * u32_unit_interval(a.y);
+  const float w2 = 0.2f * u32_unit_interval(a.z);
+  const float w3 = 0.2f * u32_unit_interval(a.w);
+  const float w4 = 0.2f * u32_unit_interval(b.x);
+  const float w5 = 0.2f * u32_unit_interval(b.y);
+  return DoublePendulumState{-0.1f + w0, -0.1f + w1, -0.1f + w2,
+                             -0.1f + w3, -0.1f + w4, -0.1f + w5};
+}
+
+static __host__ __device__ __forceinline__ float double_pendulum_clip(float v, float b) {
+  return v < -b ? -b : (v > b ? b : v);
+}
+
+static __host__ __device__ __forceinline__ float double_pendulum_wrap(float th) {
+#pragma clang fp contract(off)
+  if (th >= PENDULUM_PI) th = th - PENDULUM_TWO_PI;
+  else if (th < -PENDULUM_PI) th = th + PENDULUM_TWO_PI;
+  return th;
+}
+
+// sincos of the two angles of `s`, and what follows from them alone
+static __host__ __device__ __forceinline__ DoublePendulumTrig double_pendulum_trig(
+    const DoublePendulumState& s, float* s2_out) {
+#pragma clang fp contract(off)
+  float s1, c1, s2, c2;
+  pendulum_sincos(s.th1, &s1, &c1);
+  pendulum_sincos(s.th2, &s2, &c2);
+  const float cc = c1 * c2;
+  const float ss = s1 * s2;
+  const float sc = s1 * c2;
+  const float cs = c1 * s2;
+  const float y1 = 0.6f * c1;
+  const float y2 = 0.6f * c2;
+  *s2_out = s2;
+  return DoublePendulumTrig{s1, c1, sc - cs, cc + ss, y1 + y2};
+}
+
+// the observation of state `s` (11 entries)
+static __host__ __device__ __forceinline__ void double_pendulum_obs(
+    const DoublePendulumState& s, const DoublePendulumTrig& g, float* o) {
+#pragma clang fp contract(off)
+  const float w2 = s.th2d - s.th1d;
+  o[0] = s.x; o[1] = g.s1; o[2] = -g.sd; o[3] = g.c1; o[4] = g.cd;
+  o[5] = double_pendulum_clip(s.xd, 10.0f);
+  o[6] = double_pendulum_clip(s.th1d, 10.0f);
+  o[7] = double_pendulum_clip(w2, 10.0f);
+  o[8] = 0.0f; o[9] = 0.0f; o[10] = 0.0f;
+}
+
+// one env step (five substeps) with action `a` (clipped here): the reward, done, and
+// the trigonometry of the new state.  The solve lives in named scalars: nothing is
+// indexed dynamically.  (The substep loop is left to the compiler, which unrolls it:
+// kept rolled, the streamed tanh rollout kernel reserved 180 B of private segment.)
+static __host__ __device__ __forceinline__ float double_pendulum_advance(
+    DoublePendulumState* st, float a, DoublePendulumTrig* trig, bool* done) {
+#pragma clang fp contract(off)
+  constexpr float H = 0.01f, VMAX = 100.0f;
+  const float u = double_pendulum_clip(a, 1.0f);
+  const float F = 500.0f * u;
+  float x = st->x, th1 = st->th1, th2 = st->th2;
+  float xd = st->xd, th1d = st->th1d, th2d = st->th2d;
+  for (int k = 0; k < 5; ++k) {
+    float s1, c1, s2, c2;
+    pendulum_sincos(th1, &s1, &c1);
+    pendulum_sincos(th2, &s2, &c2);
+    const float cc = c1 * c2;
+    const float ss = s1 * s2;
+    const float cd = cc + ss;
+    const float sc = s1 * c2;
+    const float cs = c1 * s2;
+    const float sd = sc - cs;
+    const float q1 = th1d * th1d;
+    const float q2 = th2d * th2d;
+    const float a12 = DP_D2 * c1;
+    const float a13 = DP_D3 * c2;
+    const float a23 = DP_D5 * cd;
+    const float b1 = DP_D2 * s1;
+    const float b2 = b1 * q1;
+    const float b3 = DP_D3 * s2;
+    const float b4 = b3 * q2;
+    const float b5 = F + b2;
+    const float r1 = b5 + b4;
+    const float e1 = DP_D5 * sd;
+    const float g1 = DP_F1 * s1;
+    const float e2 = e1 * q2;
+    const float r2 = g1 - e2;
+    const float g2 = DP_F2 * s2;
+    const float e3 = e1 * q1;
+    const float r3 = g2 + e3;
+    // D = L diag(D1, p22, p33) L^T, L unit lower triangular (l21, l31, l32)
+    const float l21 = a12 / DP_D1;
+    const float l31 = a13 / DP_D1;
+    const float m1 = l21 * a12;
+    const float p22 = DP_D4 - m1;
+    const float m2 = l21 * a13;
+    const float t23 = a23 - m2;
+    const float m3 = l31 * a13;
+    const float t33 = DP_D6 - m3;
+    const float l32 = t23 / p22;
+    const float m4 = l32 * t23;
+    const float p33 = t33 - m4;
+    // L y = r
+    const float m5 = l21 * r1;
+    const float y2 = r2 - m5;
+    const float m6 = l31 * r1;
+    const float y3a = r3 - m6;
+    const float m7 = l32 * y2;
+    const float y3 = y3a - m7;
+    // diag z = y, L^T qdd = z
+    const float z1 = r1 / DP_D1;
+    const float z2 = y2 / p22;
+    const float acc3 = y3 / p33;
+    const float m8 = l32 * acc3;
+    const float acc2 = z2 - m8;
+    const float m9 = l21 * acc2;
+    const float z1a = z1 - m9;
+    const float m10 = l31 * acc3;
+    const float acc1 = z1a - m10;
+    const float dv1 = H * acc1;
+    const float dv2 = H * acc2;
+    const float dv3 = H * acc3;
+    const float v1 = xd + dv1;
+    const float v2 = th1d + dv2;
+    const float v3 = th2d + dv3;
+    xd = double_pendulum_clip(v1, VMAX);
+    th1d = double_pendulum_clip(v2, VMAX);
+    th2d = double_pendulum_clip(v3, VMAX);
+    const float dx = H * xd;
+    const float dt1 = H * th1d;
+    const float dt2 = H * th2d;
+    x = x + dx;
+    const float n1 = th1 + dt1;
+    const float n2 = th2 + dt2;
+    th1 = double_pendulum_wrap(n1);
+    th2 = double_pendulum_wrap(n2);
+  }
+  st->x = x; st->th1 = th1; st->th2 = th2;
+  st->xd = xd; st->th1d = th1d; st->th2d = th2d;
+  float s2;
+  const DoublePendulumTrig g = double_pendulum_trig(*st, &s2);
+  const float xa = 0.6f * g.s1;
+  const float xb = 0.6f * s2;
+  const float xc = x + xa;
+  const float xt = xc + xb;
+  const float xt2 = xt * xt;
+  const float dist_x = 0.01f * xt2;
+  const float dy = g.yt - 2.0f;
+  const float dy2 = dy * dy;
+  const float dist = dist_x + dy2;
+  const float w2 = th2d - th1d;
+  const float w1s = th1d * th1d;
+  const float w2s = w2 * w2;
+  const float vp1 = 0.001f * w1s;
+  const float vp2 = 0.005f * w2s;
+  const float vel = vp1 + vp2;
+  const float alive = 10.0f - dist;
+  *trig = g;
+  *done = g.yt <= 1.0f;
+  return alive - vel;
+}
+
+static __device__ __forceinline__ void env_reset_one(const DoublePendulumEnv& e,
+                                                     int64_t i, float* obs,
+                                                     int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const DoublePendulumState s =
+      double_pendulum_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float s2_unused;
+  const DoublePendulumTrig g = double_pendulum_trig(s, &s2_unused);
+  float* st = e.state + 6 * i;
+  st[0] = s.x; st[1] = s.th1; st[2] = s.th2; st[3] = s.xd; st[4] = s.th1d; st[5] = s.th2d;
+  double_pendulum_obs(s, g, obs + i * ldo);
+}
+
+static __device__ __forceinline__ void env_core(const DoublePendulumEnv& e, int64_t i,
+                                                const DoublePendulumPre& p,
+                                                const float* a, const float*,
+                                                float* next_row, int64_t, float* reward,
+                                                uint8_t* step_type) {
+  DoublePendulumState s = p.s;
+  DoublePendulumTrig g;
+  bool done;
+  *reward = double_pendulum_advance(&s, a[0], &g, &done);
+  float* st = e.state + 6 * i;
+  st[0] = s.x; st[1] = s.th1; st[2] = s.th2; st[3] = s.xd; st[4] = s.th1d; st[5] = s.th2d;
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  double_pendulum_obs(s, g, next_row);
+}
+
 // What a step of env i reads of the env's and the worker's state: loaded up front,
 // so that no load waits behind the step's own stores (the memory counter retires in
 // order).  `o` holds the observation entries the reward looks at when they are few.
@@ -960,6 +1194,15 @@ static __device__ __forceinline__ PendulumPre env_pre(const PendulumEnv& e, int6
   s.ep_t = 0;
   return s;
 }
+static __device__ __forceinline__ DoublePendulumPre env_pre(const DoublePendulumEnv& e,
+                                                            int64_t i) {
+  DoublePendulumPre s;
+  const float* st = e.state + 6 * i;
+  s.s = DoublePendulumState{st[0], st[1], st[2], st[3], st[4], st[5]};
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
 template <class Inner>
 static __device__ __forceinline__ auto env_pre(const MultiTaskEnv<Inner>& e, int64_t i) {
   MultiTaskPre<decltype(env_pre(e.in, i))> s;
@@ -1025,6 +1268,8 @@ ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_poin
                                                              int64_t info_ld);
 ga_rollout::CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t info_ld);
 ga_rollout::PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t info_ld);
+ga_rollout::DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e,
+                                            int64_t info_ld);
 template <class GaEnv>
 using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;

@@ -19,7 +19,9 @@ arithmetic), stepped inside the sampler's one-launch rollout like the synthetic
 env; ``MultiTaskPointVecEnv`` is ``MultiEnvWrapper`` over ``PointEnv`` tasks, the
 task switch at every reset included.  ``CartPoleVecEnv`` is gym's CartPole-v1 in a
 fixed fp32 arithmetic (``CartPoleEnv`` is its per-env numpy twin), and
-``PendulumVecEnv`` gym's Pendulum-v0 the same way (twin: ``PendulumEnv``).
+``PendulumVecEnv`` gym's Pendulum-v0 the same way (twin: ``PendulumEnv``), and
+``DoublePendulumVecEnv`` the inverted double pendulum on a cart, the task of
+InvertedDoublePendulum-v2 (twin: ``DoublePendulumEnv``).
 ``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
@@ -1013,6 +1015,301 @@ class PendulumEnv:
         pass
 
 
+def _double_pendulum_spec(max_episode_length):
+    return EnvSpec(Box(-np.inf, np.inf, (11, )), Box(-1.0, 1.0, (1, )),
+                   max_episode_length=max_episode_length)
+
+
+class DoublePendulumVecEnv(_DeviceVecEnv):
+    """``n_envs`` inverted double pendulums on a cart (the task of gym's
+    ``InvertedDoublePendulum-v2``: the same bodies, action scale, frame skip,
+    reward, termination and observation layout) stepped by one HIP kernel, one
+    thread per env, inside the sampler's one-launch rollout.
+
+    State ``(x, th1, th2, xd, th1d, th2d)`` with ``th1``, ``th2`` the rods'
+    absolute angles from the upright.  Observation ``(x, sin th1,
+    sin(th2 - th1), cos th1, cos(th2 - th1), xd, th1d, th2d - th1d`` clipped to
+    ``+-10``, ``0, 0, 0)``, one push in ``Box(-1, 1, (1,))``: the env clips it
+    itself, so any float may be passed and the batch keeps the policy's own
+    actions.  Reward ``10 - (0.01 x_tip^2 + (y_tip - 2)^2) - (0.001 w1^2 +
+    0.005 w2^2)`` of the new state; an episode terminates once ``y_tip <= 1``.
+    ``include/garage_amd.h`` states the arithmetic operation by operation;
+    :class:`DoublePendulumEnv` is the per-env numpy twin that gives the same
+    bits.  ``set_state`` / ``get_state`` move the ``(n, 6)`` float32 states
+    (scripted starts; the step counters are left alone).
+
+    Deviations from MuJoCo's model (which cannot be matched bit for bit):
+
+    - the capsule masses rounded (10.5, 4.2, 4.2), no joint damping (0.05 in
+      the XML), no rail stops;
+    - five semi-implicit Euler substeps of 0.01 instead of RK4, in fp32, with
+      ``sin`` / ``cos`` as :class:`PendulumEnv`'s fixed polynomials;
+    - the last three observation entries (MuJoCo's constraint forces) are 0;
+    - resets draw all six states from ``U(-0.1, 0.1)`` (MuJoCo: Gaussian
+      velocities) by Philox4x32-10 keyed ``(seed; env_id0 + i, the member's
+      reset counter)`` (:func:`double_pendulum_reset_draw` gives the same
+      state on the host);
+    - ``max_episode_length`` must be finite (default 1000, the task's
+      TimeLimit): the step that reaches it is TIMEOUT.
+    """
+
+    _KIND = _lib.ENV_DOUBLE_PENDULUM
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+
+    def __init__(self, n_envs, max_episode_length=1000, seed=0, env_id0=0,
+                 device=None):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = _double_pendulum_spec(self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, 6, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.DoublePendulumEnv()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def set_state(self, states):
+        """Every member's state <- row of ``states`` (``(n, 6)`` float32,
+        ``|th1|, |th2| <= PI``); the current observations follow."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.shape != (self.n_envs, 6):
+            raise ValueError('set_state needs an ({}, 6) array, got {}'.format(
+                self.n_envs, states.shape))
+        if not (np.abs(states[:, 1:3]) <= PendulumEnv.PI).all():
+            raise ValueError('set_state needs angles in [-PI, PI]')
+        self._state.copy_(torch.from_numpy(states))
+        self.obs[:, :11].copy_(
+            torch.from_numpy(DoublePendulumEnv.observe(states)))
+
+    def get_state(self):
+        """The ``(n, 6)`` float32 states."""
+        return self._state.cpu().numpy()
+
+
+def double_pendulum_reset_draw(seed, env_id, counter):
+    """The ``(6,)`` float32 state reset number ``counter`` gives member
+    ``env_id`` (= ``env_id0 + i``) of a :class:`DoublePendulumVecEnv` with this
+    seed (host only, no GPU)."""
+    out = (C.c_float * 6)()
+    call('ga_double_pendulum_reset_draw', int(seed), int(env_id), int(counter),
+         out)
+    return np.array(out, dtype=np.float32)
+
+
+DoublePendulumStep = collections.namedtuple(
+    'DoublePendulumStep', ['action', 'reward', 'observation', 'env_info',
+                           'step_type'])
+
+
+def _clip32(v, b):
+    return np.where(v < -b, -b, np.where(v > b, b, v)).astype(np.float32)
+
+
+class DoublePendulumEnv:
+    """One member of :class:`DoublePendulumVecEnv` on the host, in numpy fp32:
+    the same operations in the same order (``include/garage_amd.h``) and the
+    same Philox reset draws, so observations, rewards and step types equal the
+    device batch's bit for bit.  garage's ``Environment`` shape --
+    ``reset() -> (obs, {})``, ``step(a)`` with ``reward / observation /
+    step_type`` -- so a list of them goes behind :class:`HostVecEnv`."""
+
+    M0, M1, M2, L, G = 10.5, 4.2, 4.2, 0.6, 9.81
+    D1 = _F(M0 + M1 + M2)
+    D2 = _F((M1 / 2.0 + M2) * L)
+    D3 = _F(M2 * L / 2.0)
+    D4 = _F((M1 / 3.0 + M2) * L * L)
+    D5 = _F(M2 * L * L / 2.0)
+    D6 = _F(M2 * L * L / 3.0)
+    F1 = _F((M1 / 2.0 + M2) * L * G)
+    F2 = _F(M2 * L * G / 2.0)
+    H, VMAX, SUBSTEPS = _F(0.01), _F(100.0), 5
+
+    def __init__(self, seed=0, env_id=0, max_episode_length=1000):
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = _double_pendulum_spec(self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(6, dtype=np.float32)
+        self._t = 0
+
+    @staticmethod
+    def _wrap(th):
+        pi, two_pi = PendulumEnv.PI, PendulumEnv.TWO_PI
+        down = th - two_pi
+        up = th + two_pi
+        return np.where(th >= pi, down,
+                        np.where(th < -pi, up, th)).astype(np.float32)
+
+    @classmethod
+    def _trig(cls, th1, th2):
+        """``s1, c1, s2, sd, cd, y_tip`` of the two angles."""
+        s1, c1 = PendulumEnv.sincos(th1)
+        s2, c2 = PendulumEnv.sincos(th2)
+        cc = c1 * c2
+        ss = s1 * s2
+        sc = s1 * c2
+        cs = c1 * s2
+        y1 = _F(0.6) * c1
+        y2 = _F(0.6) * c2
+        return s1, c1, s2, sc - cs, cc + ss, y1 + y2
+
+    @classmethod
+    def _observe(cls, state, s1, c1, sd, cd):
+        ten = _F(10.0)
+        x, xd, th1d, th2d = (state[..., j] for j in (0, 3, 4, 5))
+        w2 = th2d - th1d
+        zero = np.zeros_like(x)
+        return np.stack([x, s1, -sd, c1, cd, _clip32(xd, ten),
+                         _clip32(th1d, ten), _clip32(w2, ten), zero, zero,
+                         zero], axis=-1).astype(np.float32)
+
+    @classmethod
+    def observe(cls, state):
+        """The ``(..., 11)`` observations of ``state`` (``(..., 6)``)."""
+        state = np.asarray(state, dtype=np.float32)
+        s1, c1, _, sd, cd, _ = cls._trig(state[..., 1], state[..., 2])
+        return cls._observe(state, s1, c1, sd, cd)
+
+    @classmethod
+    def advance(cls, state, action):
+        """One env step (five substeps) of ``state`` (``(..., 6)`` float32)
+        with the pushes ``action`` (``(...)``; clipped here): the new states,
+        the observations ``(..., 11)``, the rewards and ``done``.  Every line
+        is one fp32 operation."""
+        state = np.asarray(state, dtype=np.float32)
+        a = np.asarray(action, dtype=np.float32)
+        x, th1, th2, xd, th1d, th2d = (state[..., j] for j in range(6))
+        D1, D2, D3, D4, D5, D6 = (cls.D1, cls.D2, cls.D3, cls.D4, cls.D5,
+                                  cls.D6)
+        H = cls.H
+        u = _clip32(a, _F(1.0))
+        F = _F(500.0) * u
+        for _ in range(cls.SUBSTEPS):
+            s1, c1 = PendulumEnv.sincos(th1)
+            s2, c2 = PendulumEnv.sincos(th2)
+            cc = c1 * c2
+            ss = s1 * s2
+            cd = cc + ss
+            sc = s1 * c2
+            cs = c1 * s2
+            sd = sc - cs
+            q1 = th1d * th1d
+            q2 = th2d * th2d
+            a12 = D2 * c1
+            a13 = D3 * c2
+            a23 = D5 * cd
+            b1 = D2 * s1
+            b2 = b1 * q1
+            b3 = D3 * s2
+            b4 = b3 * q2
+            b5 = F + b2
+            r1 = b5 + b4
+            e1 = D5 * sd
+            g1 = cls.F1 * s1
+            e2 = e1 * q2
+            r2 = g1 - e2
+            g2 = cls.F2 * s2
+            e3 = e1 * q1
+            r3 = g2 + e3
+            l21 = a12 / D1
+            l31 = a13 / D1
+            m1 = l21 * a12
+            p22 = D4 - m1
+            m2 = l21 * a13
+            t23 = a23 - m2
+            m3 = l31 * a13
+            t33 = D6 - m3
+            l32 = t23 / p22
+            m4 = l32 * t23
+            p33 = t33 - m4
+            m5 = l21 * r1
+            y2 = r2 - m5
+            m6 = l31 * r1
+            y3a = r3 - m6
+            m7 = l32 * y2
+            y3 = y3a - m7
+            z1 = r1 / D1
+            z2 = y2 / p22
+            acc3 = y3 / p33
+            m8 = l32 * acc3
+            acc2 = z2 - m8
+            m9 = l21 * acc2
+            z1a = z1 - m9
+            m10 = l31 * acc3
+            acc1 = z1a - m10
+            dv1 = H * acc1
+            dv2 = H * acc2
+            dv3 = H * acc3
+            v1 = xd + dv1
+            v2 = th1d + dv2
+            v3 = th2d + dv3
+            xd = _clip32(v1, cls.VMAX)
+            th1d = _clip32(v2, cls.VMAX)
+            th2d = _clip32(v3, cls.VMAX)
+            dx = H * xd
+            dt1 = H * th1d
+            dt2 = H * th2d
+            x = x + dx
+            n1 = th1 + dt1
+            n2 = th2 + dt2
+            th1 = cls._wrap(n1)
+            th2 = cls._wrap(n2)
+        new = np.stack([x, th1, th2, xd, th1d, th2d],
+                       axis=-1).astype(np.float32)
+        s1, c1, s2, sd, cd, yt = cls._trig(th1, th2)
+        xa = _F(0.6) * s1
+        xb = _F(0.6) * s2
+        xc = x + xa
+        xt = xc + xb
+        xt2 = xt * xt
+        dist_x = _F(0.01) * xt2
+        dy = yt - _F(2.0)
+        dy2 = dy * dy
+        dist = dist_x + dy2
+        w2 = th2d - th1d
+        w1s = th1d * th1d
+        w2s = w2 * w2
+        vp1 = _F(0.001) * w1s
+        vp2 = _F(0.005) * w2s
+        vel = vp1 + vp2
+        alive = _F(10.0) - dist
+        reward = (alive - vel).astype(np.float32)
+        obs = cls._observe(new, s1, c1, sd, cd)
+        return new, obs, reward, yt <= _F(1.0)
+
+    def reset(self):
+        self.state = double_pendulum_reset_draw(self.seed, self.env_id,
+                                                self.resets)
+        self.resets += 1
+        self._t = 0
+        return self.observe(self.state), {}
+
+    def step(self, action):
+        a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
+        self.state, obs, reward, done = self.advance(self.state, a)
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length,
+                                    bool(done))
+        return DoublePendulumStep(action, _F(reward), obs, {}, st)
+
+    def close(self):
+        pass
+
+
 class NormalizedVecEnv(VecEnv):
     """``garage.envs.normalize`` for a device batch (``envs/normalized_env.py``).
 
@@ -1292,4 +1589,6 @@ __all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
            'uniform_random_strategy', 'task_draw', 'GRID_MAPS',
            'CartPoleVecEnv', 'CartPoleEnv', 'cartpole_reset_draw',
            'PendulumVecEnv', 'PendulumEnv', 'pendulum_reset_draw',
+           'DoublePendulumVecEnv', 'DoublePendulumEnv',
+           'double_pendulum_reset_draw',
            'NormalizedVecEnv', 'HostVecEnv', 'StepType']

@@ -931,7 +931,7 @@ class GpuVecSampler:
                     if done >= num_samples:
                         break
             samples = EpisodeBatch.concatenate(*batches)
-        self.total_env_steps += int(sum(samples.lengths))
+        self.total_env_steps += int(np.sum(samples.lengths))
         return samples
 
     def obtain_exact_episodes(self, n_eps_per_worker, agent_update,
@@ -943,7 +943,7 @@ class GpuVecSampler:
             for _ in range(n_eps_per_worker):
                 batches.append(worker.rollout().to_host())
         samples = EpisodeBatch.concatenate(*batches)
-        self.total_env_steps += int(sum(samples.lengths))
+        self.total_env_steps += int(np.sum(samples.lengths))
         return samples
 
     def shutdown_worker(self):
@@ -1159,7 +1159,8 @@ class GpuPopulationSampler:
         batches = [w._pack(b, int(c[m]), member=(m * g, (m + 1) * g, eps[m],
                                                  log_std[m]))
                    for m in range(M)]
-        self.total_env_steps += int(sum(int(sum(x.lengths)) for x in batches))
+        self.total_env_steps += int(
+            sum(int(np.sum(x.lengths)) for x in batches))
         return batches
 
     def obtain_statistics(self, itr, num_samples, member_params, discount,

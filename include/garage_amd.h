@@ -700,14 +700,102 @@ typedef struct {
 GA_API int ga_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                   float out2[2]);
 
+/* Inverted double pendulum on a cart (the task of gym's InvertedDoublePendulum-v2: a
+ * cart on a rail carrying two uniform rods, upright at rest), obs_dim 11, one action
+ * column holding the push in [-1, 1] (the env clips it; any float may be passed).
+ * MuJoCo cannot be matched bit for bit, so the env is this model of the same machine,
+ * with these deviations from MuJoCo's: the capsule masses rounded (10.5 for the cart,
+ * 4.2 for each rod of length 0.6, g = 9.81), no joint damping (the XML has 0.05), no
+ * rail stops, semi-implicit Euler instead of RK4, uniform instead of Gaussian start
+ * velocities, and zeros where MuJoCo reports its constraint forces.
+ *
+ * The arithmetic is fixed here as CartPole's and Pendulum's are above: every operation
+ * below is ONE fp32 operation, rounded to nearest on its own (no fused multiply-add,
+ * correctly rounded division), evaluated in the order the parentheses give; a constant
+ * written (float)(expr) is the double value of expr rounded to fp32; sincos, PI and
+ * TWO_PI are Pendulum's.  The state is (x, th1, th2, xd, th1d, th2d); th1 and th2 are
+ * the rods' ABSOLUTE angles from the upright, positive towards +x, kept in [-PI, PI].
+ *
+ *   D1 = (float)(10.5 + 4.2 + 4.2)                  D2 = (float)((4.2 / 2.0 + 4.2) * 0.6)
+ *   D3 = (float)(4.2 * 0.6 / 2.0)                   D4 = (float)((4.2 / 3.0 + 4.2) * 0.6 * 0.6)
+ *   D5 = (float)(4.2 * 0.6 * 0.6 / 2.0)             D6 = (float)(4.2 * 0.6 * 0.6 / 3.0)
+ *   F1 = (float)((4.2 / 2.0 + 4.2) * 0.6 * 9.81)    F2 = (float)(4.2 * 0.6 * 9.81 / 2.0)
+ *   (18.9, 3.78, 1.26, 2.016, 0.756, 0.504, 37.0818, 12.3606 rounded to fp32)
+ *   clip(v, b) = v < -b ? -b : (v > b ? b : v)
+ *   wrap(th):  th >= PI: th - TWO_PI;   th < -PI: th + TWO_PI;   else th
+ *
+ * step with action a:
+ *   F = 500.0f * clip(a, 1.0f)
+ * then FIVE times, on the running state (the equations of motion D(q) qdd = r of the
+ * three bodies, solved by one LDL^T elimination without pivoting: the condition number
+ * of D is 39..108 over all angles):
+ *   (s1, c1) = sincos(th1)      (s2, c2) = sincos(th2)
+ *   cd = (c1 * c2) + (s1 * s2)              sd = (s1 * c2) - (c1 * s2)
+ *   q1 = th1d * th1d                        q2 = th2d * th2d
+ *   a12 = D2 * c1      a13 = D3 * c2        a23 = D5 * cd
+ *   r1 = (F + ((D2 * s1) * q1)) + ((D3 * s2) * q2)
+ *   e1 = D5 * sd
+ *   r2 = (F1 * s1) - (e1 * q2)
+ *   r3 = (F2 * s2) + (e1 * q1)
+ *   l21 = a12 / D1                          l31 = a13 / D1
+ *   p22 = D4 - (l21 * a12)                  t23 = a23 - (l21 * a13)
+ *   t33 = D6 - (l31 * a13)                  l32 = t23 / p22
+ *   p33 = t33 - (l32 * t23)
+ *   y2 = r2 - (l21 * r1)                    y3 = (r3 - (l31 * r1)) - (l32 * y2)
+ *   z1 = r1 / D1       z2 = y2 / p22        acc3 = y3 / p33
+ *   acc2 = z2 - (l32 * acc3)                acc1 = (z1 - (l21 * acc2)) - (l31 * acc3)
+ *   xd   = clip(xd   + (0.01f * acc1), 100.0f)
+ *   th1d = clip(th1d + (0.01f * acc2), 100.0f)
+ *   th2d = clip(th2d + (0.01f * acc3), 100.0f)      (a guard: free runs stay below 14)
+ *   x   = x + (0.01f * xd)                          (the NEW speeds: semi-implicit Euler)
+ *   th1 = wrap(th1 + (0.01f * th1d))        th2 = wrap(th2 + (0.01f * th2d))
+ * (|0.01f * v| <= 1, so one wrap is enough), and on the state they leave:
+ *   (s1, c1) = sincos(th1)      (s2, c2) = sincos(th2)
+ *   cd = (c1 * c2) + (s1 * s2)              sd = (s1 * c2) - (c1 * s2)
+ *   yt = (0.6f * c1) + (0.6f * c2)          xt = (x + (0.6f * s1)) + (0.6f * s2)
+ *   dist = (0.01f * (xt * xt)) + ((yt - 2.0f) * (yt - 2.0f))
+ *   w2  = th2d - th1d                       (MuJoCo's second joint speed; its first is th1d)
+ *   vel = (0.001f * (th1d * th1d)) + (0.005f * (w2 * w2))
+ *   reward = (10.0f - dist) - vel           (the terminating step keeps its reward)
+ *   done = yt <= 1.0f
+ *   observation = (x, s1, -sd, c1, cd, clip(xd, 10.0f), clip(th1d, 10.0f),
+ *                  clip(w2, 10.0f), 0, 0, 0)
+ *   (-sd = sin(th2 - th1), cd = cos(th2 - th1): the reference task's layout
+ *   (x, sin q1, sin q2, cos q1, cos q2, clipped joint speeds, constraint forces) with
+ *   MuJoCo's relative second joint angle q2 = th2 - th1)
+ *   step type: TIMEOUT when the episode reaches max_episode_length (1..65535), else
+ *   TERMINAL when done, as for the other envs.
+ *
+ * Reset number c (= resets[i], which then advances) of env i takes the words w_0..w_3
+ * of Philox4x32-10 with counter (env_id0 + i, c, 0, 7 << 16) and w_4, w_5, the first two
+ * words with counter (env_id0 + i, c, 1, 7 << 16) -- stream 7 -- and key
+ * (seed & 0xffffffff, seed >> 32):
+ *   u_j = ((float)(w_j >> 8) + 0.5f) * 0x1p-24f,   state[j] = -0.1f + (0.2f * u_j)
+ * the first observation is the observation above of that state.
+ * ga_double_pendulum_reset_draw below gives the six values on the host. */
+typedef struct {
+  int64_t n, env_id0;
+  int32_t max_episode_length, pad_;
+  uint64_t seed;
+  float* state;     /* [n, 6] x, th1, th2, xd, th1d, th2d */
+  int32_t* t;       /* [n] steps taken in the current episode */
+  uint32_t* resets; /* [n] resets so far */
+} ga_double_pendulum_env;
+
+/* Host-only (no GPU needed): the state reset number `counter` gives env `env_id`
+ * (= env_id0 + i) of a ga_double_pendulum_env with this seed. */
+GA_API int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                         float out6[6]);
+
 /* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env,
- * ga_multi_point_env, ga_cartpole_env or ga_pendulum_env. */
+ * ga_multi_point_env, ga_cartpole_env, ga_pendulum_env or ga_double_pendulum_env. */
 #define GA_ENV_SYNTH 0
 #define GA_ENV_POINT 1
 #define GA_ENV_GRID 2
 #define GA_ENV_MULTI_POINT 3
 #define GA_ENV_CARTPOLE 4
 #define GA_ENV_PENDULUM 5
+#define GA_ENV_DOUBLE_PENDULUM 6
 typedef struct {
   int32_t kind, pad_;
   const void* env;
