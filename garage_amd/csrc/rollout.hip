@@ -424,6 +424,10 @@ static int check_record(const ga_record_args* a, int64_t n, const char* who) {
              (long long)a->Tcap);
   GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
              "%s: max_episode_length must be in 1..65535", who);
+  // (the terminal observation is copied row to row, as ga_policy_head_sample's)
+  GA_REQUIRE(a->obs_dim >= 0 && a->ldo >= a->obs_dim,
+             "%s: leading dimensions too small (observation rows of %lld columns, "
+             "obs_dim %d)", who, (long long)a->ldo, (int)a->obs_dim);
   return GA_OK;
 }
 
@@ -787,6 +791,11 @@ extern "C" int ga_pack_src_index(const int32_t* ep_env, const int32_t* ep_end,
   GA_REQUIRE(ep_env && ep_end && ep_len && ep_off && src,
              "ga_pack_src_index: null pointer");
   GA_REQUIRE(n_eps > 0 && n_eps < (1ll << 31), "ga_pack_src_index: bad n_eps");
+  // (src holds int32 cells: the caller guarantees n * Tcap < 2^31 for its n envs, of
+  // which only Tcap and the episodes -- one cell each at the least -- are seen here)
+  GA_REQUIRE(Tcap > 0 && Tcap < (1ll << 31),
+             "ga_pack_src_index: rollout buffers too large (Tcap %lld: cells are "
+             "addressed in int32)", (long long)Tcap);
   hipLaunchKernelGGL(pack_src_index_kernel, dim3((unsigned)n_eps), dim3(256), 0,
                      stream, ep_env, ep_end, ep_len, ep_off, n_eps, Tcap, src);
   GA_CHECK_LAUNCH("pack_src_index");

@@ -148,6 +148,19 @@ def _apply_env_update(old_env, env_update):
     raise TypeError('Unknown environment update type.')
 
 
+def check_cells_int32(n_envs, tcap):
+    """The packing path addresses the cell ``env * tcap + column`` of a rollout
+    buffer in int32 (``ga_pack_src_index``, the gathers, ``ep_cell``): refuse
+    buffers with ``2^31`` cells or more before anything is allocated."""
+    n_envs, tcap = int(n_envs), int(tcap)
+    if n_envs * tcap >= 2**31:
+        raise ValueError(
+            'rollout buffers too large: {} envs x {} columns = {} cells, and '
+            'cells are addressed in int32 (fewer than 2^31); use fewer envs or '
+            'ask for fewer samples per call'.format(n_envs, tcap,
+                                                    n_envs * tcap))
+
+
 def _copy_env(env):
     """``copy.deepcopy`` for per-env objects; device batches are shared."""
     return env if isinstance(env, VecEnv) else copy.deepcopy(env)
@@ -261,6 +274,7 @@ class GpuVecWorker:
         tcap = round4(max(tcap, 1))
         if tcap > 65535 * 4:
             raise ValueError('rollout too long for one obtain_samples call')
+        check_cells_int32(n, tcap)
         dev = self.device
         ldo = round4(env.obs_dim)
         lda = round4(env.act_width)

@@ -468,7 +468,8 @@ GA_API int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* params,
                                     const ga_head_args* args, ga_stream_t stream);
 
 /* Reward / step-type / episode-end bookkeeping of VecWorker.step_episode and
- * _gather_episode (sampler/vec_worker.py:139-204). */
+ * _gather_episode (sampler/vec_worker.py:139-204).  Refused: a null pointer, col
+ * outside [0, Tcap), max_episode_length outside 1..65535, ldo < obs_dim. */
 typedef struct {
   int64_t n, col, Tcap;
   int32_t max_episode_length;
@@ -872,7 +873,11 @@ GA_API int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params,
                                 int64_t n_steps, ga_stream_t stream);
 
 /* EpisodeBatch.concatenate in completion order (sampler/vec_worker.py:206-219,
- * local_sampler.py:134-166; order = (completion step, env index)). */
+ * local_sampler.py:134-166; order = (completion step, env index)).
+ * ga_pack_src_index writes the flat cell env * Tcap + column of every packed sample
+ * as int32, and the gathers read such cells: the caller must guarantee
+ * n * Tcap < 2^31 for the n envs of its buffers.  The entry sees Tcap and the episodes
+ * only and refuses Tcap outside 1..2^31 - 1 and n_eps outside 1..2^31 - 1. */
 GA_API int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,
                             int64_t n_steps, const int32_t* ep_base, int32_t* ep_env,
                             int32_t* ep_end, int32_t* ep_len, ga_stream_t stream);
