@@ -73,16 +73,33 @@ class DoublePendulumEnv(C.Structure):
                 ('resets', ptr)]
 
 
+class AcrobotEnv(C.Structure):
+    """``ga_acrobot_env``."""
+    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
+                ('pad_', c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
+                ('resets', ptr)]
+
+
+class MountainCarEnv(C.Structure):
+    """``ga_mountain_car_env``."""
+    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
+                ('continuous', c_i32), ('seed', c_u64), ('state', ptr),
+                ('t', ptr), ('resets', ptr)]
+
+
 class EnvRef(C.Structure):
     """``ga_env_ref``: kind ``ENV_SYNTH`` / ``ENV_POINT`` / ``ENV_GRID`` /
     ``ENV_MULTI_POINT`` / ``ENV_CARTPOLE`` / ``ENV_PENDULUM`` /
-    ``ENV_DOUBLE_PENDULUM``."""
+    ``ENV_DOUBLE_PENDULUM`` / ``ENV_ACROBOT`` / ``ENV_MOUNTAIN_CAR``."""
     _fields_ = [('kind', c_i32), ('pad_', c_i32), ('env', ptr)]
 
 
 ENV_SYNTH, ENV_POINT, ENV_GRID, ENV_MULTI_POINT, ENV_CARTPOLE = 0, 1, 2, 3, 4
 ENV_PENDULUM = 5
 ENV_DOUBLE_PENDULUM = 6
+# (7 and 9 are not kinds: they stay the two that are refused as unknown)
+ENV_ACROBOT = 8
+ENV_MOUNTAIN_CAR = 10
 
 
 def env_ref(kind, env):
@@ -264,6 +281,10 @@ SIGNATURES = {
                                        C.POINTER(c_f32)]),
     'ga_double_pendulum_reset_draw': (c_int, [c_u64, c_i64, c_u32,
                                               C.POINTER(c_f32)]),
+    'ga_acrobot_reset_draw': (c_int, [c_u64, c_i64, c_u32,
+                                      C.POINTER(c_f32)]),
+    'ga_mountain_car_reset_draw': (c_int, [c_u64, c_i64, c_u32,
+                                           C.POINTER(c_f32)]),
     'ga_env_reset': (c_int, [C.POINTER(EnvRef), ptr, ptr, c_i64, ptr]),
     'ga_env_step': (c_int, [C.POINTER(EnvRef), ptr, c_i64, ptr, ptr, c_i64, ptr,
                             ptr, ptr]),

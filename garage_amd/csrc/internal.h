@@ -51,6 +51,8 @@ inline int ga_env_obs_dim(const ga_multi_point_env* e) {
 inline int ga_env_obs_dim(const ga_cartpole_env*) { return 4; }
 inline int ga_env_obs_dim(const ga_pendulum_env*) { return 3; }
 inline int ga_env_obs_dim(const ga_double_pendulum_env*) { return 11; }
+inline int ga_env_obs_dim(const ga_acrobot_env*) { return 6; }
+inline int ga_env_obs_dim(const ga_mountain_car_env*) { return 2; }
 inline int ga_env_discrete(const ga_synth_env* e) { return e->discrete != 0; }
 inline int ga_env_discrete(const ga_point_env*) { return 0; }
 inline int ga_env_discrete(const ga_grid_env*) { return 1; }
@@ -58,6 +60,10 @@ inline int ga_env_discrete(const ga_multi_point_env*) { return 0; }
 inline int ga_env_discrete(const ga_cartpole_env*) { return 1; }
 inline int ga_env_discrete(const ga_pendulum_env*) { return 0; }
 inline int ga_env_discrete(const ga_double_pendulum_env*) { return 0; }
+inline int ga_env_discrete(const ga_acrobot_env*) { return 1; }
+// the one kind whose answer is the struct's: MountainCar-v0 takes a class index,
+// MountainCarContinuous-v0 a force
+inline int ga_env_discrete(const ga_mountain_car_env* e) { return e->continuous == 0; }
 inline int ga_env_act_width(const ga_synth_env* e) { return e->discrete ? 1 : e->act_dim; }
 inline int ga_env_act_width(const ga_point_env*) { return 2; }
 inline int ga_env_act_width(const ga_grid_env*) { return 1; }
@@ -65,6 +71,8 @@ inline int ga_env_act_width(const ga_multi_point_env*) { return 2; }
 inline int ga_env_act_width(const ga_cartpole_env*) { return 1; }
 inline int ga_env_act_width(const ga_pendulum_env*) { return 1; }
 inline int ga_env_act_width(const ga_double_pendulum_env*) { return 1; }
+inline int ga_env_act_width(const ga_acrobot_env*) { return 1; }
+inline int ga_env_act_width(const ga_mountain_car_env*) { return 1; }
 
 // f(const ga_<kind>_env*) of the env `ref` points to; `who` names the entry point in
 // the two errors this owns
@@ -82,6 +90,8 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
     case GA_ENV_CARTPOLE: return f((const ga_cartpole_env*)ref->env);
     case GA_ENV_PENDULUM: return f((const ga_pendulum_env*)ref->env);
     case GA_ENV_DOUBLE_PENDULUM: return f((const ga_double_pendulum_env*)ref->env);
+    case GA_ENV_ACROBOT: return f((const ga_acrobot_env*)ref->env);
+    case GA_ENV_MOUNTAIN_CAR: return f((const ga_mountain_car_env*)ref->env);
   }
   ga_set_error("%s: unknown env kind %d", who, ref->kind);
   return -1;

@@ -25,7 +25,8 @@
 // The parameters describe the network as NetDev (net_to_dev, below) and the head as
 // rollout_dev.h's HeadDev (ga_head_to_dev), the struct the per-layer head kernel takes.
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
-// CartPole, Pendulum, the inverted double pendulum: a template parameter of the kernel) the
+// CartPole, Pendulum, the inverted double pendulum, Acrobot, MountainCar: a template
+// parameter of the kernel) the
 // thread that sampled an env's action
 // also steps it, and a whole rollout is ONE launch with the weights resident on the CU (see the kernel).
 #include <algorithm>

@@ -1,6 +1,6 @@
 // Rollout-side kernels: the per-layer path's action head, the device environments
 // (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole,
-// Pendulum, the inverted double pendulum), per-step
+// Pendulum, the inverted double pendulum, Acrobot, MountainCar), per-step
 // episode bookkeeping and the ragged -> packed compaction.  A step's device code is
 // rollout_dev.h's; here are its kernels and the one converter and check of each C-ABI
 // struct: ga_head_to_dev, ga_record_to_dev / check_record, ga_env_to_dev / check_env.
@@ -533,6 +533,23 @@ DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e, int64_t) {
   return d;
 }
 
+AcrobotEnv ga_env_to_dev(const ga_acrobot_env* e, int64_t) {
+  AcrobotEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
+  ga_key(e->seed, &d.k0, &d.k1);
+  d.state = e->state; d.t = e->t; d.resets = e->resets;
+  return d;
+}
+
+MountainCarEnv ga_env_to_dev(const ga_mountain_car_env* e, int64_t) {
+  MountainCarEnv d;
+  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
+  d.continuous = e->continuous;
+  ga_key(e->seed, &d.k0, &d.k1);
+  d.state = e->state; d.t = e->t; d.resets = e->resets;
+  return d;
+}
+
 static int check_env(const ga_synth_env* e, const char* who) {
   GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
   GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
@@ -599,6 +616,24 @@ static int check_env(const ga_double_pendulum_env* e, const char* who) {
   return GA_OK;
 }
 
+static int check_env(const ga_acrobot_env* e, const char* who) {
+  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  return GA_OK;
+}
+
+static int check_env(const ga_mountain_car_env* e, const char* who) {
+  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
+  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
+  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
+             "%s: max_episode_length must be in 1..65535", who);
+  GA_REQUIRE(e->continuous == 0 || e->continuous == 1, "%s: continuous must be 0 or 1",
+             who);
+  return GA_OK;
+}
+
 // Validation + conversion of the C-ABI arguments of one env step (also used by the
 // fused policy + env step of policy_fused.hip): the env, the record and the
 // NormalizedEnv part
@@ -659,6 +694,8 @@ GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
 GA_BUILD_ENV_STEP_OF(ga_cartpole_env)
 GA_BUILD_ENV_STEP_OF(ga_pendulum_env)
 GA_BUILD_ENV_STEP_OF(ga_double_pendulum_env)
+GA_BUILD_ENV_STEP_OF(ga_acrobot_env)
+GA_BUILD_ENV_STEP_OF(ga_mountain_car_env)
 #undef GA_BUILD_ENV_STEP_OF
 
 // Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
@@ -766,6 +803,30 @@ extern "C" int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id,
       double_pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
   out6[0] = s.x; out6[1] = s.th1; out6[2] = s.th2;
   out6[3] = s.xd; out6[4] = s.th1d; out6[5] = s.th2d;
+  return GA_OK;
+}
+
+// the device's acrobot_reset_draw on the host (garage_amd.envs.AcrobotEnv starts its
+// episodes from it)
+extern "C" int ga_acrobot_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                     float out4[4]) {
+  GA_REQUIRE(out4, "ga_acrobot_reset_draw: null pointer");
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  const AcrobotState s = acrobot_reset_draw(k0, k1, (uint32_t)env_id, counter);
+  out4[0] = s.th1; out4[1] = s.th2; out4[2] = s.w1; out4[3] = s.w2;
+  return GA_OK;
+}
+
+// the device's mountain_car_reset_draw on the host (garage_amd.envs.MountainCarEnv
+// starts its episodes from it)
+extern "C" int ga_mountain_car_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                          float out2[2]) {
+  GA_REQUIRE(out2, "ga_mountain_car_reset_draw: null pointer");
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  const MountainCarState s = mountain_car_reset_draw(k0, k1, (uint32_t)env_id, counter);
+  out2[0] = s.x; out2[1] = s.v;
   return GA_OK;
 }
 

@@ -1,7 +1,8 @@
 // Device-side pieces of the rollout step shared by rollout.hip and the fused
 // policy + env step of policy_fused.hip, each written once: Philox, the head of a step
 // (HeadDev, head_one), the device environments (synthetic, PointEnv, GridWorldEnv,
-// MultiEnvWrapper over PointEnv, CartPole, Pendulum, the inverted double pendulum;
+// MultiEnvWrapper over PointEnv, CartPole, Pendulum, the inverted double pendulum,
+// Acrobot, MountainCar;
 // env_pre / env_core / env_reset_one of each),
 // the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
 // (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
@@ -52,6 +53,8 @@ static constexpr uint32_t STREAM_TASK = 4;
 static constexpr uint32_t STREAM_CARTPOLE = 5;
 static constexpr uint32_t STREAM_PENDULUM = 6;
 static constexpr uint32_t STREAM_DOUBLE_PENDULUM = 7;
+static constexpr uint32_t STREAM_ACROBOT = 8;
+static constexpr uint32_t STREAM_MOUNTAIN_CAR = 9;
 
 // the two Philox key words of a 64-bit seed
 static __host__ __device__ __forceinline__ void ga_key(uint64_t seed, uint32_t* k0,
@@ -942,6 +945,304 @@ static __device__ __forceinline__ void env_core(const DoublePendulumEnv& e, int6
   double_pendulum_obs(s, g, next_row);
 }
 
+// ---- Acrobot (include/garage_amd.h states the arithmetic, operation by operation) ----
+// One fp32 operation per statement, no contraction; `/` is the correctly rounded
+// division.  The reduction, the dynamics, the RK4 step and the reset draw are written
+// once, here; sin and cos are Pendulum's.
+struct AcrobotEnv {
+  int64_t n;
+  int64_t env_id0;   // global id of env 0 of this shard
+  int max_len;
+  uint32_t k0, k1;   // seed
+  float* state;      // [n, 4] th1, th2, thd1, thd2; th1, th2 in [-PI, PI]
+  int32_t* t;        // [n] steps taken in the current episode
+  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
+};
+struct AcrobotState { float th1, th2, w1, w2; };
+struct AcrobotPre {
+  AcrobotState s;
+  int t, ep_t;
+};
+struct AcrobotTrig { float s1, c1, s2, c2; };
+
+constexpr float ACROBOT_INV_TWO_PI = (float)(1.0 / 6.283185307179586);
+constexpr float ACROBOT_R_HI = 6.28125f;
+constexpr float ACROBOT_R_LO = (float)(6.283185307179586 - 6.28125);
+constexpr float ACROBOT_MAX_VEL_1 = (float)(4.0 * 3.141592653589793);
+constexpr float ACROBOT_MAX_VEL_2 = (float)(9.0 * 3.141592653589793);
+
+// the state reset number `counter` gives env `env` (global id)
+static __host__ __device__ __forceinline__ AcrobotState acrobot_reset_draw(
+    uint32_t k0, uint32_t k1, uint32_t env, uint32_t counter) {
+#pragma clang fp contract(off)
+  const U4 r = philox4x32_10(env, counter, 0u, STREAM_ACROBOT << 16, k0, k1);
+  const float w0 = 0.2f * u32_unit_interval(r.x);
+  const float w1 = 0.2f * u32_unit_interval(r.y);
+  const float w2 = 0.2f * u32_unit_interval(r.z);
+  const float w3 = 0.2f * u32_unit_interval(r.w);
+  return AcrobotState{-0.1f + w0, -0.1f + w1, -0.1f + w2, -0.1f + w3};
+}
+
+// any stage angle (|th| < 34, the header says why) brought into [-PI, PI]: k * R_HI is
+// exact, so the only roundings of size are the last subtraction's and the wrap's
+static __host__ __device__ __forceinline__ float acrobot_reduce(float th) {
+#pragma clang fp contract(off)
+  const float q = th * ACROBOT_INV_TWO_PI;
+  const float k = __builtin_rintf(q);
+  const float m1 = k * ACROBOT_R_HI;
+  const float r1 = th - m1;
+  const float m2 = k * ACROBOT_R_LO;
+  float r = r1 - m2;
+  if (r >= PENDULUM_PI) r = r - PENDULUM_TWO_PI;
+  else if (r < -PENDULUM_PI) r = r + PENDULUM_TWO_PI;
+  return r;
+}
+
+// the accelerations of the book dynamics at (unreduced) angles th1, th2 and speeds w1,
+// w2 under torque a
+static __host__ __device__ __forceinline__ void acrobot_dynamics(float th1, float th2,
+                                                                 float w1, float w2,
+                                                                 float a, float* acc1_out,
+                                                                 float* acc2_out) {
+#pragma clang fp contract(off)
+  float s1, c1, s2, c2;
+  pendulum_sincos(acrobot_reduce(th1), &s1, &c1);
+  pendulum_sincos(acrobot_reduce(th2), &s2, &c2);
+  const float d1 = 3.5f + c2;
+  const float hc = 0.5f * c2;
+  const float d2 = 1.25f + hc;
+  const float sc = s1 * c2;
+  const float cs = c1 * s2;
+  const float s12 = sc + cs;
+  const float phi2 = 4.9f * s12;
+  const float q2 = w2 * w2;
+  const float p1 = -0.5f * q2;
+  const float p2 = p1 * s2;
+  const float p3 = w2 * w1;
+  const float p4 = p3 * s2;
+  const float p5 = p2 - p4;
+  const float p6 = 14.7f * s1;
+  const float p7 = p6 + phi2;
+  const float phi1 = p5 + p7;
+  const float r = d2 / d1;
+  const float e1 = r * phi1;
+  const float e2 = a + e1;
+  const float q1 = w1 * w1;
+  const float e3 = 0.5f * q1;
+  const float e4 = e3 * s2;
+  const float e5 = e2 - e4;
+  const float e6 = e5 - phi2;
+  const float e7 = d2 * r;
+  const float den = 1.25f - e7;
+  const float acc2 = e6 / den;
+  const float g1 = d2 * acc2;
+  const float g2 = g1 + phi1;
+  const float g3 = g2 / d1;
+  *acc1_out = -g3;
+  *acc2_out = acc2;
+}
+
+// one env step (one classical RK4 step of 0.2) with torque `a`: the new state, its
+// sines and cosines, and done.  k1..k4 are summed as they come (the order the header
+// gives), so one stage is live at a time.
+static __host__ __device__ __forceinline__ bool acrobot_advance(AcrobotState* st, float a,
+                                                                AcrobotTrig* trig) {
+#pragma clang fp contract(off)
+  constexpr float H6 = (float)(0.2 / 6.0);
+  const float th1 = st->th1, th2 = st->th2, w1 = st->w1, w2 = st->w2;
+  float k1 = w1, k2 = w2, k3, k4;
+  acrobot_dynamics(th1, th2, w1, w2, a, &k3, &k4);
+  float s_t1 = k1, s_t2 = k2, s_w1 = k3, s_w2 = k4;
+#pragma unroll
+  for (int stage = 0; stage < 3; ++stage) {
+    const float h = stage == 2 ? 0.2f : 0.1f;
+    const float dt1 = h * k1;
+    const float dt2 = h * k2;
+    const float dw1 = h * k3;
+    const float dw2 = h * k4;
+    const float y1 = th1 + dt1;
+    const float y2 = th2 + dt2;
+    const float v1 = w1 + dw1;
+    const float v2 = w2 + dw2;
+    acrobot_dynamics(y1, y2, v1, v2, a, &k3, &k4);
+    k1 = v1;
+    k2 = v2;
+    if (stage == 2) {
+      s_t1 = s_t1 + k1;
+      s_t2 = s_t2 + k2;
+      s_w1 = s_w1 + k3;
+      s_w2 = s_w2 + k4;
+    } else {
+      const float b1 = 2.0f * k1;
+      const float b2 = 2.0f * k2;
+      const float b3 = 2.0f * k3;
+      const float b4 = 2.0f * k4;
+      s_t1 = s_t1 + b1;
+      s_t2 = s_t2 + b2;
+      s_w1 = s_w1 + b3;
+      s_w2 = s_w2 + b4;
+    }
+  }
+  const float i1 = H6 * s_t1;
+  const float i2 = H6 * s_t2;
+  const float i3 = H6 * s_w1;
+  const float i4 = H6 * s_w2;
+  const float n1 = th1 + i1;
+  const float n2 = th2 + i2;
+  const float u1 = w1 + i3;
+  const float u2 = w2 + i4;
+  st->th1 = acrobot_reduce(n1);
+  st->th2 = acrobot_reduce(n2);
+  st->w1 = double_pendulum_clip(u1, ACROBOT_MAX_VEL_1);
+  st->w2 = double_pendulum_clip(u2, ACROBOT_MAX_VEL_2);
+  AcrobotTrig g;
+  pendulum_sincos(st->th1, &g.s1, &g.c1);
+  pendulum_sincos(st->th2, &g.s2, &g.c2);
+  const float cc = g.c1 * g.c2;
+  const float ss = g.s1 * g.s2;
+  const float c12 = cc - ss;
+  const float hgt = (-g.c1) - c12;
+  *trig = g;
+  return hgt > 1.0f;
+}
+
+// class index -> torque: 0 is -1, 2 is +1, anything else none
+static __host__ __device__ __forceinline__ float three_way_push(int k) {
+  return k == 0 ? -1.0f : (k == 2 ? 1.0f : 0.0f);
+}
+
+static __device__ __forceinline__ void env_reset_one(const AcrobotEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const AcrobotState s = acrobot_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float s1, c1, s2, c2;
+  pendulum_sincos(s.th1, &s1, &c1);
+  pendulum_sincos(s.th2, &s2, &c2);
+  float* st = e.state + 4 * i;
+  float* o = obs + i * ldo;
+  st[0] = s.th1; st[1] = s.th2; st[2] = s.w1; st[3] = s.w2;
+  o[0] = c1; o[1] = s1; o[2] = c2; o[3] = s2; o[4] = s.w1; o[5] = s.w2;
+}
+
+static __device__ __forceinline__ void env_core(const AcrobotEnv& e, int64_t i,
+                                                const AcrobotPre& p, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  AcrobotState s = p.s;
+  AcrobotTrig g;
+  const bool done = acrobot_advance(&s, three_way_push((int)a[0]), &g);
+  float* st = e.state + 4 * i;
+  st[0] = s.th1; st[1] = s.th2; st[2] = s.w1; st[3] = s.w2;
+  *reward = done ? 0.0f : -1.0f;
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  next_row[0] = g.c1; next_row[1] = g.s1; next_row[2] = g.c2; next_row[3] = g.s2;
+  next_row[4] = s.w1; next_row[5] = s.w2;
+}
+
+// ---- MountainCar, discrete and continuous (include/garage_amd.h states the arithmetic,
+// operation by operation) ----
+// One fp32 operation per statement, no contraction.  The step and the reset draw are
+// written once, here; the cosine is Pendulum's.
+struct MountainCarEnv {
+  int64_t n;
+  int64_t env_id0;   // global id of env 0 of this shard
+  int max_len;
+  int continuous;    // 0: MountainCar-v0 (class index), 1: MountainCarContinuous-v0
+  uint32_t k0, k1;   // seed
+  float* state;      // [n, 2] x in [-1.2, 0.6], v in [-0.07, 0.07]
+  int32_t* t;        // [n] steps taken in the current episode
+  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
+};
+struct MountainCarState { float x, v; };
+struct MountainCarPre {
+  float x, v;
+  int t, ep_t;
+};
+
+// the state reset number `counter` gives env `env` (global id)
+static __host__ __device__ __forceinline__ MountainCarState mountain_car_reset_draw(
+    uint32_t k0, uint32_t k1, uint32_t env, uint32_t counter) {
+#pragma clang fp contract(off)
+  const U4 r = philox4x32_10(env, counter, 0u, STREAM_MOUNTAIN_CAR << 16, k0, k1);
+  const float w0 = 0.2f * u32_unit_interval(r.x);
+  return MountainCarState{-0.6f + w0, 0.0f};
+}
+
+// one step with the action column's value `a` (a class index, or the force when
+// `continuous`); returns done and the reward
+static __host__ __device__ __forceinline__ bool mountain_car_advance(MountainCarState* s,
+                                                                     float a,
+                                                                     bool continuous,
+                                                                     float* reward) {
+#pragma clang fp contract(off)
+  const float x = s->x, v = s->v;
+  float ang = 3.0f * x;
+  if (ang >= PENDULUM_PI) ang = ang - PENDULUM_TWO_PI;
+  else if (ang < -PENDULUM_PI) ang = ang + PENDULUM_TWO_PI;
+  float sn_unused, cs;
+  pendulum_sincos(ang, &sn_unused, &cs);
+  float dv;
+  if (continuous) {
+    const float u = double_pendulum_clip(a, 1.0f);
+    const float f1 = u * 0.0015f;
+    const float f2 = 0.0025f * cs;
+    dv = f1 - f2;
+  } else {
+    const float f1 = three_way_push((int)a) * 0.001f;
+    const float f2 = cs * -0.0025f;
+    dv = f1 + f2;
+  }
+  const float v1 = v + dv;
+  float nv = double_pendulum_clip(v1, 0.07f);
+  const float x1 = x + nv;
+  const float nx = x1 < -1.2f ? -1.2f : (x1 > 0.6f ? 0.6f : x1);
+  if (nx == -1.2f && nv < 0.0f) nv = 0.0f;
+  s->x = nx;
+  s->v = nv;
+  const bool done = nx >= (continuous ? 0.45f : 0.5f) && nv >= 0.0f;
+  if (continuous) {
+    const float a2 = a * a;
+    const float cost = 0.1f * a2;
+    *reward = (done ? 100.0f : 0.0f) - cost;
+  } else {
+    *reward = -1.0f;
+  }
+  return done;
+}
+
+static __device__ __forceinline__ void env_reset_one(const MountainCarEnv& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const MountainCarState s =
+      mountain_car_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float* st = e.state + 2 * i;
+  float* o = obs + i * ldo;
+  st[0] = s.x; st[1] = s.v;
+  o[0] = s.x; o[1] = s.v;
+}
+
+static __device__ __forceinline__ void env_core(const MountainCarEnv& e, int64_t i,
+                                                const MountainCarPre& p, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  MountainCarState s{p.x, p.v};
+  const bool done = mountain_car_advance(&s, a[0], e.continuous != 0, reward);
+  float* st = e.state + 2 * i;
+  st[0] = s.x; st[1] = s.v;
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+  next_row[0] = s.x; next_row[1] = s.v;
+}
+
 // What a step of env i reads of the env's and the worker's state: loaded up front,
 // so that no load waits behind the step's own stores (the memory counter retires in
 // order).  `o` holds the observation entries the reward looks at when they are few.
@@ -1203,6 +1504,24 @@ static __device__ __forceinline__ DoublePendulumPre env_pre(const DoublePendulum
   s.ep_t = 0;
   return s;
 }
+static __device__ __forceinline__ AcrobotPre env_pre(const AcrobotEnv& e, int64_t i) {
+  AcrobotPre s;
+  const float* st = e.state + 4 * i;
+  s.s = AcrobotState{st[0], st[1], st[2], st[3]};
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
+static __device__ __forceinline__ MountainCarPre env_pre(const MountainCarEnv& e,
+                                                         int64_t i) {
+  MountainCarPre s;
+  const float* st = e.state + 2 * i;
+  s.x = st[0];
+  s.v = st[1];
+  s.t = e.t[i];
+  s.ep_t = 0;
+  return s;
+}
 template <class Inner>
 static __device__ __forceinline__ auto env_pre(const MultiTaskEnv<Inner>& e, int64_t i) {
   MultiTaskPre<decltype(env_pre(e.in, i))> s;
@@ -1270,6 +1589,8 @@ ga_rollout::CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t info_ld)
 ga_rollout::PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t info_ld);
 ga_rollout::DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e,
                                             int64_t info_ld);
+ga_rollout::AcrobotEnv ga_env_to_dev(const ga_acrobot_env* e, int64_t info_ld);
+ga_rollout::MountainCarEnv ga_env_to_dev(const ga_mountain_car_env* e, int64_t info_ld);
 template <class GaEnv>
 using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;

@@ -21,7 +21,10 @@ task switch at every reset included.  ``CartPoleVecEnv`` is gym's CartPole-v1 in
 fixed fp32 arithmetic (``CartPoleEnv`` is its per-env numpy twin), and
 ``PendulumVecEnv`` gym's Pendulum-v0 the same way (twin: ``PendulumEnv``), and
 ``DoublePendulumVecEnv`` the inverted double pendulum on a cart, the task of
-InvertedDoublePendulum-v2 (twin: ``DoublePendulumEnv``).
+InvertedDoublePendulum-v2 (twin: ``DoublePendulumEnv``).  ``AcrobotVecEnv`` is
+gym's Acrobot-v1 (twin: ``AcrobotEnv``) and ``MountainCarVecEnv`` its
+MountainCar-v0 and MountainCarContinuous-v0 (twin: ``MountainCarEnv``), which
+completes gym's classic control on the device.
 ``HostVecEnv`` adapts a list of ordinary per-env objects (any
 ``garage.Environment``-like with ``reset``/``step``) so existing CPU simulators
 still feed the device-resident update path.
@@ -1310,6 +1313,480 @@ class DoublePendulumEnv:
         pass
 
 
+def _acrobot_spec(max_episode_length):
+    high = np.array([1.0, 1.0, 1.0, 1.0, AcrobotEnv.MAX_VEL_1,
+                     AcrobotEnv.MAX_VEL_2], dtype=np.float32)
+    return EnvSpec(Box(-high, high), Discrete(3),
+                   max_episode_length=max_episode_length)
+
+
+class AcrobotVecEnv(_DeviceVecEnv):
+    """``n_envs`` acrobots (gym 0.17's ``Acrobot-v1``: the "book" dynamics, no
+    torque noise, one classical RK4 step of 0.2 s, the same speed bounds,
+    reward and goal) stepped by one HIP kernel, one thread per env, inside the
+    sampler's one-launch rollout.
+
+    State ``(th1, th2, thd1, thd2)`` with both angles kept in ``[-PI, PI]``.
+    Observation ``(cos th1, sin th1, cos th2, sin th2, thd1, thd2)`` in gym's
+    ``Box``, ``Discrete(3)`` actions: class 0 is torque -1, class 2 torque +1,
+    anything else (1, and any index out of range) no torque.  Reward -1 per
+    step and 0 on the step that swings the tip above the line,
+    ``-cos th1 - cos(th1 + th2) > 1``, which is TERMINAL.
+    ``include/garage_amd.h`` states the arithmetic operation by operation;
+    :class:`AcrobotEnv` is the per-env numpy twin that gives the same bits.
+    ``set_state`` / ``get_state`` move the ``(n, 4)`` float32 states (scripted
+    starts; the step counters are left alone).
+
+    Deviations from gym:
+
+    - fp32 throughout, ``sin`` / ``cos`` as :class:`PendulumEnv`'s fixed
+      polynomials behind a two-constant reduction of the RK4 stage angles
+      (which leave ``[-PI, PI]`` by far), ``sin(th1 + th2)`` by the addition
+      theorem;
+    - the angles are wrapped by that reduction instead of ``mod``;
+    - resets draw from Philox4x32-10 keyed ``(seed; env_id0 + i, the member's
+      reset counter)`` instead of gym's ``np_random``
+      (:func:`acrobot_reset_draw` gives the same state on the host);
+    - ``max_episode_length`` must be finite (default 500, Acrobot-v1's
+      TimeLimit): the step that reaches it is TIMEOUT.
+    """
+
+    _KIND = _lib.ENV_ACROBOT
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+
+    def __init__(self, n_envs, max_episode_length=500, seed=0, env_id0=0,
+                 device=None):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = _acrobot_spec(self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, 4, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.AcrobotEnv()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def set_state(self, states):
+        """Every member's state <- row of ``states`` (``(n, 4)`` float32,
+        angles in ``[-PI, PI]``, speeds inside their clips); the current
+        observations follow."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.shape != (self.n_envs, 4):
+            raise ValueError('set_state needs an ({}, 4) array, got {}'.format(
+                self.n_envs, states.shape))
+        if not (np.abs(states[:, :2]) <= AcrobotEnv.PI).all():
+            raise ValueError('set_state needs angles in [-PI, PI]')
+        if not ((np.abs(states[:, 2]) <= AcrobotEnv.MAX_VEL_1).all() and
+                (np.abs(states[:, 3]) <= AcrobotEnv.MAX_VEL_2).all()):
+            raise ValueError('set_state needs speeds within 4 pi and 9 pi')
+        self._state.copy_(torch.from_numpy(states))
+        self.obs[:, :6].copy_(torch.from_numpy(AcrobotEnv.observe(states)))
+
+    def get_state(self):
+        """The ``(n, 4)`` float32 states."""
+        return self._state.cpu().numpy()
+
+
+def acrobot_reset_draw(seed, env_id, counter):
+    """The ``(4,)`` float32 state reset number ``counter`` gives member
+    ``env_id`` (= ``env_id0 + i``) of an :class:`AcrobotVecEnv` with this seed
+    (host only, no GPU)."""
+    out = (C.c_float * 4)()
+    call('ga_acrobot_reset_draw', int(seed), int(env_id), int(counter), out)
+    return np.array(out, dtype=np.float32)
+
+
+AcrobotStep = collections.namedtuple(
+    'AcrobotStep', ['action', 'reward', 'observation', 'env_info',
+                    'step_type'])
+
+
+class AcrobotEnv:
+    """One member of :class:`AcrobotVecEnv` on the host, in numpy fp32: the
+    same operations in the same order (``include/garage_amd.h``) and the same
+    Philox reset draws, so observations, rewards and step types equal the
+    device batch's bit for bit.  garage's ``Environment`` shape --
+    ``reset() -> (obs, {})``, ``step(a)`` with ``reward / observation /
+    step_type`` -- so a list of them goes behind :class:`HostVecEnv`."""
+
+    PI, TWO_PI = PendulumEnv.PI, PendulumEnv.TWO_PI
+    INV_TWO_PI = _F(1.0 / 6.283185307179586)
+    # TWO_PI in two parts: R_HI has 9 significant bits, so k * R_HI is exact
+    R_HI = _F(6.28125)
+    R_LO = _F(6.283185307179586 - 6.28125)
+    MAX_VEL_1 = _F(4.0 * 3.141592653589793)
+    MAX_VEL_2 = _F(9.0 * 3.141592653589793)
+    H, H2, H6 = _F(0.2), _F(0.1), _F(0.2 / 6.0)
+
+    def __init__(self, seed=0, env_id=0, max_episode_length=500):
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = _acrobot_spec(self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(4, dtype=np.float32)
+        self._t = 0
+
+    @classmethod
+    def reduce(cls, th):
+        """``th`` (float32, any stage angle) brought into ``[-PI, PI]``."""
+        th = np.asarray(th, dtype=np.float32)
+        q = th * cls.INV_TWO_PI
+        k = np.rint(q)
+        m1 = k * cls.R_HI
+        r1 = th - m1
+        m2 = k * cls.R_LO
+        r = r1 - m2
+        down = r - cls.TWO_PI
+        up = r + cls.TWO_PI
+        return np.where(r >= cls.PI, down,
+                        np.where(r < -cls.PI, up, r)).astype(np.float32)
+
+    @classmethod
+    def torque(cls, action):
+        """The torque of the class indices ``action``: 0 -> -1, 2 -> +1,
+        anything else 0."""
+        a = np.asarray(action)
+        return np.where(a == 0, _F(-1.0),
+                        np.where(a == 2, _F(1.0), _F(0.0))).astype(np.float32)
+
+    @classmethod
+    def dynamics(cls, th1, th2, w1, w2, a):
+        """``(acc1, acc2)`` of the book dynamics at the (unreduced) angles and
+        speeds under torque ``a``; every line one fp32 operation."""
+        s1, c1 = PendulumEnv.sincos(cls.reduce(th1))
+        s2, c2 = PendulumEnv.sincos(cls.reduce(th2))
+        d1 = _F(3.5) + c2
+        hc = _F(0.5) * c2
+        d2 = _F(1.25) + hc
+        sc = s1 * c2
+        cs = c1 * s2
+        s12 = sc + cs
+        phi2 = _F(4.9) * s12
+        q2 = w2 * w2
+        p1 = _F(-0.5) * q2
+        p2 = p1 * s2
+        p3 = w2 * w1
+        p4 = p3 * s2
+        p5 = p2 - p4
+        p6 = _F(14.7) * s1
+        p7 = p6 + phi2
+        phi1 = p5 + p7
+        r = d2 / d1
+        e1 = r * phi1
+        e2 = a + e1
+        q1 = w1 * w1
+        e3 = _F(0.5) * q1
+        e4 = e3 * s2
+        e5 = e2 - e4
+        e6 = e5 - phi2
+        e7 = d2 * r
+        den = _F(1.25) - e7
+        acc2 = e6 / den
+        g1 = d2 * acc2
+        g2 = g1 + phi1
+        g3 = g2 / d1
+        acc1 = -g3
+        return acc1, acc2
+
+    @classmethod
+    def observe(cls, state):
+        """The ``(..., 6)`` observations of ``state`` (``(..., 4)``, angles in
+        ``[-PI, PI]``)."""
+        state = np.asarray(state, dtype=np.float32)
+        s1, c1 = PendulumEnv.sincos(state[..., 0])
+        s2, c2 = PendulumEnv.sincos(state[..., 1])
+        return np.stack([c1, s1, c2, s2, state[..., 2], state[..., 3]],
+                        axis=-1).astype(np.float32)
+
+    @classmethod
+    def advance(cls, state, action):
+        """One env step (one RK4 step of 0.2) of ``state`` (``(..., 4)``
+        float32) with the class indices ``action`` (``(...)``): the new states,
+        the observations ``(..., 6)``, the rewards and ``done``.  Every line
+        is one fp32 operation."""
+        state = np.asarray(state, dtype=np.float32)
+        a = cls.torque(action)
+        th1, th2, w1, w2 = (state[..., j] for j in range(4))
+        H, H2, H6, two = cls.H, cls.H2, cls.H6, _F(2.0)
+        # k1 = (w1, w2, a1, a2)
+        a1, a2 = cls.dynamics(th1, th2, w1, w2, a)
+        s_t1, s_t2, s_w1, s_w2 = w1, w2, a1, a2
+        k = (w1, w2, a1, a2)
+        for h, wt in ((H2, two), (H2, two), (H, None)):
+            dt1 = h * k[0]
+            dt2 = h * k[1]
+            dw1 = h * k[2]
+            dw2 = h * k[3]
+            y1 = th1 + dt1
+            y2 = th2 + dt2
+            v1 = w1 + dw1
+            v2 = w2 + dw2
+            a1, a2 = cls.dynamics(y1, y2, v1, v2, a)
+            k = (v1, v2, a1, a2)
+            if wt is None:
+                s_t1 = s_t1 + k[0]
+                s_t2 = s_t2 + k[1]
+                s_w1 = s_w1 + k[2]
+                s_w2 = s_w2 + k[3]
+            else:
+                s_t1 = s_t1 + wt * k[0]
+                s_t2 = s_t2 + wt * k[1]
+                s_w1 = s_w1 + wt * k[2]
+                s_w2 = s_w2 + wt * k[3]
+        n1 = th1 + H6 * s_t1
+        n2 = th2 + H6 * s_t2
+        u1 = w1 + H6 * s_w1
+        u2 = w2 + H6 * s_w2
+        nth1 = cls.reduce(n1)
+        nth2 = cls.reduce(n2)
+        nw1 = _clip32(u1, cls.MAX_VEL_1)
+        nw2 = _clip32(u2, cls.MAX_VEL_2)
+        s1, c1 = PendulumEnv.sincos(nth1)
+        s2, c2 = PendulumEnv.sincos(nth2)
+        cc = c1 * c2
+        ss = s1 * s2
+        c12 = cc - ss
+        hgt = (-c1) - c12
+        done = hgt > _F(1.0)
+        reward = np.where(done, _F(0.0), _F(-1.0)).astype(np.float32)
+        new = np.stack([nth1, nth2, nw1, nw2], axis=-1).astype(np.float32)
+        obs = np.stack([c1, s1, c2, s2, nw1, nw2], axis=-1).astype(np.float32)
+        return new, obs, reward, done
+
+    def reset(self):
+        self.state = acrobot_reset_draw(self.seed, self.env_id, self.resets)
+        self.resets += 1
+        self._t = 0
+        return self.observe(self.state), {}
+
+    def step(self, action):
+        a = int(np.asarray(action).reshape(-1)[0])
+        self.state, obs, reward, done = self.advance(self.state, a)
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length,
+                                    bool(done))
+        return AcrobotStep(action, _F(reward), obs, {}, st)
+
+    def close(self):
+        pass
+
+
+def _mountain_car_spec(continuous, max_episode_length):
+    low = np.array([-1.2, -0.07], dtype=np.float32)
+    high = np.array([0.6, 0.07], dtype=np.float32)
+    act = Box(-1.0, 1.0, (1, )) if continuous else Discrete(3)
+    return EnvSpec(Box(low, high), act, max_episode_length=max_episode_length)
+
+
+def _mountain_car_length(continuous, max_episode_length):
+    if max_episode_length is None:
+        return 999 if continuous else 200
+    return _check_finite_length(max_episode_length)
+
+
+class MountainCarVecEnv(_DeviceVecEnv):
+    """``n_envs`` mountain cars (gym 0.17's ``MountainCar-v0``, or with
+    ``continuous=True`` its ``MountainCarContinuous-v0``: the same constants,
+    update order, clips, wall, goals and rewards) stepped by one HIP kernel,
+    one thread per env, inside the sampler's one-launch rollout.
+
+    State and observation ``(x, v)`` in ``Box([-1.2, -0.07], [0.6, 0.07])``.
+    Discrete variant: ``Discrete(3)``, class 0 pushes left, class 2 right,
+    anything else coasts; reward -1 every step; TERMINAL once ``x >= 0.5`` with
+    ``v >= 0``.  Continuous variant: one force in ``Box(-1, 1, (1,))`` which
+    the env clips itself (the batch keeps the policy's own actions); reward
+    ``100`` on reaching ``x >= 0.45`` minus ``0.1 a^2`` of the UNCLIPPED
+    action, as in gym.  ``include/garage_amd.h`` states the arithmetic
+    operation by operation; :class:`MountainCarEnv` is the per-env numpy twin
+    that gives the same bits.  ``set_state`` / ``get_state`` move the
+    ``(n, 2)`` float32 states (scripted starts; the step counters are left
+    alone).
+
+    Deviations from gym:
+
+    - fp32 throughout, ``cos(3 x)`` as :class:`PendulumEnv`'s fixed polynomial;
+    - resets draw ``x`` from Philox4x32-10 keyed ``(seed; env_id0 + i, the
+      member's reset counter)`` instead of gym's ``np_random``
+      (:func:`mountain_car_reset_draw` gives the same state on the host);
+    - ``max_episode_length`` must be finite: ``None`` selects the variant's
+      TimeLimit (200, continuous 999); the step that reaches it is TIMEOUT.
+    """
+
+    _KIND = _lib.ENV_MOUNTAIN_CAR
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+
+    def __init__(self, n_envs, continuous=False, max_episode_length=None,
+                 seed=0, env_id0=0, device=None):
+        self.n_envs = int(n_envs)
+        self.continuous = bool(continuous)
+        self.max_episode_length = _mountain_car_length(self.continuous,
+                                                       max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = _mountain_car_spec(self.continuous,
+                                       self.max_episode_length)
+        self._init_device(device)
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, 2, dtype=torch.float32, device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = _lib.MountainCarEnv()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.continuous = int(self.continuous)
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def set_state(self, states):
+        """Every member's ``(x, v)`` <- row of ``states`` (``(n, 2)`` float32
+        inside the observation ``Box``); the current observations follow."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.shape != (self.n_envs, 2):
+            raise ValueError('set_state needs an ({}, 2) array, got {}'.format(
+                self.n_envs, states.shape))
+        box = self.spec.observation_space
+        if not ((states >= box.low).all() and (states <= box.high).all()):
+            raise ValueError('set_state needs x in [-1.2, 0.6] and v in '
+                             '[-0.07, 0.07]')
+        self._state.copy_(torch.from_numpy(states))
+        self.obs[:, :2].copy_(self._state)
+
+    def get_state(self):
+        """The ``(n, 2)`` float32 states ``(x, v)``."""
+        return self._state.cpu().numpy()
+
+
+def mountain_car_reset_draw(seed, env_id, counter):
+    """The ``(2,)`` float32 state ``(x, 0)`` reset number ``counter`` gives
+    member ``env_id`` (= ``env_id0 + i``) of a :class:`MountainCarVecEnv` with
+    this seed, either variant (host only, no GPU)."""
+    out = (C.c_float * 2)()
+    call('ga_mountain_car_reset_draw', int(seed), int(env_id), int(counter),
+         out)
+    return np.array(out, dtype=np.float32)
+
+
+MountainCarStep = collections.namedtuple(
+    'MountainCarStep', ['action', 'reward', 'observation', 'env_info',
+                        'step_type'])
+
+
+class MountainCarEnv:
+    """One member of :class:`MountainCarVecEnv` on the host, in numpy fp32:
+    the same operations in the same order (``include/garage_amd.h``) and the
+    same Philox reset draws, so observations, rewards and step types equal the
+    device batch's bit for bit.  garage's ``Environment`` shape --
+    ``reset() -> (obs, {})``, ``step(a)`` with ``reward / observation /
+    step_type`` -- so a list of them goes behind :class:`HostVecEnv`."""
+
+    MIN_X, MAX_X, MAX_V = _F(-1.2), _F(0.6), _F(0.07)
+    GOAL, GOAL_CONTINUOUS = _F(0.5), _F(0.45)
+
+    def __init__(self, seed=0, env_id=0, continuous=False,
+                 max_episode_length=None):
+        self.continuous = bool(continuous)
+        self.max_episode_length = _mountain_car_length(self.continuous,
+                                                       max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = _mountain_car_spec(self.continuous,
+                                       self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(2, dtype=np.float32)
+        self._t = 0
+
+    @classmethod
+    def advance(cls, state, action, continuous=False):
+        """One step of ``state`` (``(..., 2)`` float32 ``(x, v)``) with the
+        class indices (or, ``continuous``, the forces) ``action`` (``(...)``):
+        the new states, the observations (the new states), the rewards and
+        ``done``.  Every line is one fp32 operation."""
+        state = np.asarray(state, dtype=np.float32)
+        x, v = state[..., 0], state[..., 1]
+        x3 = _F(3.0) * x
+        up = x3 + PendulumEnv.TWO_PI
+        down = x3 - PendulumEnv.TWO_PI
+        ang = np.where(x3 >= PendulumEnv.PI, down,
+                       np.where(x3 < -PendulumEnv.PI, up, x3))
+        _, cs = PendulumEnv.sincos(ang.astype(np.float32))
+        if continuous:
+            a = np.asarray(action, dtype=np.float32)
+            u = _clip32(a, _F(1.0))
+            f1 = u * _F(0.0015)
+            f2 = _F(0.0025) * cs
+            dv = f1 - f2
+        else:
+            k = np.asarray(action)
+            push = np.where(k == 0, _F(-1.0),
+                            np.where(k == 2, _F(1.0),
+                                     _F(0.0))).astype(np.float32)
+            f1 = push * _F(0.001)
+            f2 = cs * _F(-0.0025)
+            dv = f1 + f2
+        v1 = v + dv
+        nv = _clip32(v1, cls.MAX_V)
+        x1 = x + nv
+        nx = np.where(x1 < cls.MIN_X, cls.MIN_X,
+                      np.where(x1 > cls.MAX_X, cls.MAX_X,
+                               x1)).astype(np.float32)
+        wall = (nx == cls.MIN_X) & (nv < _F(0.0))
+        nv = np.where(wall, _F(0.0), nv).astype(np.float32)
+        goal = cls.GOAL_CONTINUOUS if continuous else cls.GOAL
+        done = (nx >= goal) & (nv >= _F(0.0))
+        if continuous:
+            a2 = a * a
+            cost = _F(0.1) * a2
+            bonus = np.where(done, _F(100.0), _F(0.0)).astype(np.float32)
+            reward = (bonus - cost).astype(np.float32)
+        else:
+            reward = np.full(np.shape(nx), -1.0, dtype=np.float32)
+        new = np.stack([nx, nv], axis=-1).astype(np.float32)
+        return new, new.copy(), reward, done
+
+    def reset(self):
+        self.state = mountain_car_reset_draw(self.seed, self.env_id,
+                                             self.resets)
+        self.resets += 1
+        self._t = 0
+        return self.state.copy(), {}
+
+    def step(self, action):
+        if self.continuous:
+            a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
+        else:
+            a = int(np.asarray(action).reshape(-1)[0])
+        self.state, obs, reward, done = self.advance(self.state, a,
+                                                     self.continuous)
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length,
+                                    bool(done))
+        return MountainCarStep(action, _F(reward), obs, {}, st)
+
+    def close(self):
+        pass
+
+
 class NormalizedVecEnv(VecEnv):
     """``garage.envs.normalize`` for a device batch (``envs/normalized_env.py``).
 
@@ -1591,4 +2068,6 @@ __all__ = ['VecEnv', 'SyntheticVecEnv', 'PointVecEnv', 'GridWorldVecEnv',
            'PendulumVecEnv', 'PendulumEnv', 'pendulum_reset_draw',
            'DoublePendulumVecEnv', 'DoublePendulumEnv',
            'double_pendulum_reset_draw',
+           'AcrobotVecEnv', 'AcrobotEnv', 'acrobot_reset_draw',
+           'MountainCarVecEnv', 'MountainCarEnv', 'mountain_car_reset_draw',
            'NormalizedVecEnv', 'HostVecEnv', 'StepType']

@@ -788,8 +788,140 @@ typedef struct {
 GA_API int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                          float out6[6]);
 
+/* Acrobot (gym 0.17's Acrobot-v1: two unit links, unit masses, centres of mass at 0.5,
+ * moments of inertia 1, g = 9.8, the "book" dynamics, no torque noise, dt = 0.2),
+ * observation (cos th1, sin th1, cos th2, sin th2, thd1, thd2), obs_dim 6, one action
+ * column holding a class index k: 0 is torque a = -1.0f, 2 is a = 1.0f, anything else
+ * (1, and any index out of range) a = 0.0f.  th1 is the first link's angle from hanging
+ * straight down, th2 the second link's angle relative to the first.
+ *
+ * The arithmetic is fixed here as CartPole's and Pendulum's are above: every operation
+ * below is ONE fp32 operation, rounded to nearest on its own (no fused multiply-add,
+ * correctly rounded division), evaluated in the order the parentheses give; a constant
+ * written (float)(expr) is the double value of expr rounded to fp32; sincos, PI and
+ * TWO_PI are Pendulum's.  The state is (th1, th2, w1, w2) with both angles kept in
+ * [-PI, PI], |w1| <= V1 and |w2| <= V2:
+ *
+ *   V1 = (float)(4.0 * 3.141592653589793)      V2 = (float)(9.0 * 3.141592653589793)
+ *   clip(v, b) = v < -b ? -b : (v > b ? b : v)
+ *
+ * reduce(th), any stage angle -> [-PI, PI]:
+ *   k = rintf(th * (float)(1.0 / 6.283185307179586))       (round half to even)
+ *   r = (th - (k * R_HI)) - (k * R_LO)
+ *     R_HI = 6.28125f   R_LO = (float)(6.283185307179586 - 6.28125)
+ *   r >= PI: r = r - TWO_PI;   r < -PI: r = r + TWO_PI
+ * The stage angles of the RK4 step below are NOT in [-PI, PI]: the accelerations reach
+ * thousands at the speed bounds, and over the whole state box and the three torques
+ * the largest |stage angle| (the angle after the step, before its reduce, included) is
+ * 33.32, at (th1, th2, w1, w2) = (-+1.598, +-1.980, +-V1, +-V2), found by a random search
+ * of 4e6 states plus local refinement over the float64 equations; reduce is trusted,
+ * and tested, on |th| <= 34 (|k| <= 5).  The two-constant form is a change to the
+ * proposal r = th - (k * TWO_PI): R_HI has 9 significant bits, so k * R_HI and the first
+ * subtraction are exact and the error of r is half an ulp of PI plus |k| * 1e-10, where
+ * the one-constant form adds the rounding of k * TWO_PI and |k| times TWO_PI's own
+ * 1.7e-7.  Measured over |th| <= 34 against float64 sin / cos of the same fp32 angle:
+ * reduce + sincos within 2.2e-7 / 2.5e-7, the one-constant form within 1.4e-6 / 1.6e-6,
+ * for two more operations per reduction.
+ *
+ * f(th1, th2, w1, w2) with torque a = (w1, w2, acc1, acc2):
+ *   (s1, c1) = sincos(reduce(th1))          (s2, c2) = sincos(reduce(th2))
+ *   d1 = 3.5f + c2                          d2 = 1.25f + (0.5f * c2)
+ *   s12 = (s1 * c2) + (c1 * s2)             (sin(th1 + th2): no sincos of a sum)
+ *   phi2 = 4.9f * s12
+ *   phi1 = (((-0.5f * (w2 * w2)) * s2) - ((w2 * w1) * s2)) + ((14.7f * s1) + phi2)
+ *   r    = d2 / d1
+ *   acc2 = (((a + (r * phi1)) - ((0.5f * (w1 * w1)) * s2)) - phi2) / (1.25f - (d2 * r))
+ *   acc1 = -(((d2 * acc2) + phi1) / d1)
+ *   (1.25f - (d2 * r) lies in [0.56, 1.03] for every c2 in [-1, 1])
+ *
+ * step with action class k, y = (th1, th2, w1, w2) the state before it, one classical
+ * RK4 step of 0.2 (each line for all four components j):
+ *   k1 = f(y)
+ *   k2 = f(y + (0.1f * k1))       k3 = f(y + (0.1f * k2))       k4 = f(y + (0.2f * k3))
+ *   sum_j = ((k1_j + (2.0f * k2_j)) + (2.0f * k3_j)) + k4_j
+ *   y'_j  = y_j + ((float)(0.2 / 6.0) * sum_j)
+ *   th1 = reduce(y'_0)    th2 = reduce(y'_1)    w1 = clip(y'_2, V1)    w2 = clip(y'_3, V2)
+ * and on the state that leaves:
+ *   (s1, c1) = sincos(th1)                  (s2, c2) = sincos(th2)
+ *   done = ((-c1) - ((c1 * c2) - (s1 * s2))) > 1.0f
+ *   reward = done ? 0.0f : -1.0f
+ *   observation = (c1, s1, c2, s2, w1, w2)
+ *   step type: TIMEOUT when the episode reaches max_episode_length (1..65535), else
+ *   TERMINAL when done, as for the other envs.
+ *
+ * Reset number c (= resets[i], which then advances) of env i takes the words w_0..w_3
+ * of Philox4x32-10 with counter (env_id0 + i, c, 0, 8 << 16) -- stream 8 -- and key
+ * (seed & 0xffffffff, seed >> 32):
+ *   u_j = ((float)(w_j >> 8) + 0.5f) * 0x1p-24f,   state[j] = -0.1f + (0.2f * u_j)
+ * (gym draws the four from U(-0.1, 0.1) of its np_random); the first observation is the
+ * observation above of that state.  ga_acrobot_reset_draw below gives the four values
+ * on the host. */
+typedef struct {
+  int64_t n, env_id0;
+  int32_t max_episode_length, pad_;
+  uint64_t seed;
+  float* state;     /* [n, 4] th1, th2, thd1, thd2 */
+  int32_t* t;       /* [n] steps taken in the current episode */
+  uint32_t* resets; /* [n] resets so far */
+} ga_acrobot_env;
+
+/* Host-only (no GPU needed): the state reset number `counter` gives env `env_id`
+ * (= env_id0 + i) of a ga_acrobot_env with this seed. */
+GA_API int ga_acrobot_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                 float out4[4]);
+
+/* MountainCar (gym 0.17's MountainCar-v0, and with continuous = 1 its
+ * MountainCarContinuous-v0), state and observation (x, v), obs_dim 2, one action column:
+ * a class index k (0 pushes left, p = -1.0f; 2 pushes right, p = 1.0f; anything else
+ * coasts, p = 0.0f), or with continuous = 1 the force a (the env clips it; any float may
+ * be passed).  Whether the env takes a class index or a force is this struct's field,
+ * not its kind's.
+ *
+ * The arithmetic is fixed as above (one fp32 operation at a time, no fused
+ * multiply-add, the order the parentheses give); sincos, PI and TWO_PI are Pendulum's,
+ * clip is Acrobot's.  x is kept in [-1.2f, 0.6f] and v in [-0.07f, 0.07f].
+ *
+ * step:
+ *   g = 3.0f * x;   g >= PI: g = g - TWO_PI;   g < -PI: g = g + TWO_PI
+ *   cs = the cosine of sincos(g)     (3 x lies in [-3.6, 1.8]: one wrap is enough)
+ *   continuous == 0:   v1 = v + ((p * 0.001f) + (cs * -0.0025f))
+ *   continuous == 1:   v1 = v + ((clip(a, 1.0f) * 0.0015f) - (0.0025f * cs))
+ *   v' = clip(v1, 0.07f)
+ *   x1 = x + v'
+ *   x' = x1 < -1.2f ? -1.2f : (x1 > 0.6f ? 0.6f : x1)
+ *   x' == -1.2f and v' < 0.0f:  v' = 0.0f          (the left wall)
+ *   continuous == 0:   done = x' >= 0.5f and v' >= 0.0f      reward = -1.0f (every step)
+ *   continuous == 1:   done = x' >= 0.45f and v' >= 0.0f
+ *                      reward = (done ? 100.0f : 0.0f) - (0.1f * (a * a))
+ *                      (the UNCLIPPED a, as in gym)
+ *   observation = state = (x', v')
+ *   step type: TIMEOUT when the episode reaches max_episode_length (1..65535; gym's
+ *   limits are 200 and, continuous, 999), else TERMINAL when done.
+ *
+ * Reset number c (= resets[i], which then advances) of env i takes the word w_0 of
+ * Philox4x32-10 with counter (env_id0 + i, c, 0, 9 << 16) -- stream 9 -- and key
+ * (seed & 0xffffffff, seed >> 32):
+ *   u_0 = ((float)(w_0 >> 8) + 0.5f) * 0x1p-24f,   x = -0.6f + (0.2f * u_0),   v = 0.0f
+ * (gym draws x ~ U(-0.6, -0.4) from its np_random); the first observation is (x, v).
+ * ga_mountain_car_reset_draw below gives (x, v) on the host. */
+typedef struct {
+  int64_t n, env_id0;
+  int32_t max_episode_length;
+  int32_t continuous; /* 0: MountainCar-v0, 1: MountainCarContinuous-v0 */
+  uint64_t seed;
+  float* state;     /* [n, 2] x, v */
+  int32_t* t;       /* [n] steps taken in the current episode */
+  uint32_t* resets; /* [n] resets so far */
+} ga_mountain_car_env;
+
+/* Host-only (no GPU needed): the state (x, v) reset number `counter` gives env `env_id`
+ * (= env_id0 + i) of a ga_mountain_car_env with this seed (either variant). */
+GA_API int ga_mountain_car_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
+                                      float out2[2]);
+
 /* Any device env: `env` points to a ga_synth_env, ga_point_env, ga_grid_env,
- * ga_multi_point_env, ga_cartpole_env, ga_pendulum_env or ga_double_pendulum_env. */
+ * ga_multi_point_env, ga_cartpole_env, ga_pendulum_env, ga_double_pendulum_env,
+ * ga_acrobot_env or ga_mountain_car_env. */
 #define GA_ENV_SYNTH 0
 #define GA_ENV_POINT 1
 #define GA_ENV_GRID 2
@@ -797,6 +929,10 @@ GA_API int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t
 #define GA_ENV_CARTPOLE 4
 #define GA_ENV_PENDULUM 5
 #define GA_ENV_DOUBLE_PENDULUM 6
+/* (7 and 9 are not kinds, and will not become kinds: callers and the tests of the
+ * earlier kinds rely on both being refused as "unknown env kind") */
+#define GA_ENV_ACROBOT 8
+#define GA_ENV_MOUNTAIN_CAR 10
 typedef struct {
   int32_t kind, pad_;
   const void* env;
