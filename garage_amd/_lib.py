@@ -52,39 +52,38 @@ class MultiPointEnv(C.Structure):
         ('last_task', ptr), ('resets', ptr), ('task_id', ptr)]
 
 
+def _state_env_fields(slot='pad_'):
+    """The one field list of the seeded state-vector env structs; ``slot``
+    names the int32 after ``max_episode_length`` (padding unless the kind has
+    a variant switch)."""
+    return [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
+            (slot, c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
+            ('resets', ptr)]
+
+
 class CartPoleEnv(C.Structure):
     """``ga_cartpole_env``."""
-    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
-                ('pad_', c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
-                ('resets', ptr)]
+    _fields_ = _state_env_fields()
 
 
 class PendulumEnv(C.Structure):
     """``ga_pendulum_env``."""
-    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
-                ('pad_', c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
-                ('resets', ptr)]
+    _fields_ = _state_env_fields()
 
 
 class DoublePendulumEnv(C.Structure):
     """``ga_double_pendulum_env``."""
-    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
-                ('pad_', c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
-                ('resets', ptr)]
+    _fields_ = _state_env_fields()
 
 
 class AcrobotEnv(C.Structure):
     """``ga_acrobot_env``."""
-    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
-                ('pad_', c_i32), ('seed', c_u64), ('state', ptr), ('t', ptr),
-                ('resets', ptr)]
+    _fields_ = _state_env_fields()
 
 
 class MountainCarEnv(C.Structure):
     """``ga_mountain_car_env``."""
-    _fields_ = [('n', c_i64), ('env_id0', c_i64), ('max_episode_length', c_i32),
-                ('continuous', c_i32), ('seed', c_u64), ('state', ptr),
-                ('t', ptr), ('resets', ptr)]
+    _fields_ = _state_env_fields('continuous')
 
 
 class EnvRef(C.Structure):

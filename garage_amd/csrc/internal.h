@@ -42,37 +42,39 @@ int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const fl
 // ga_env_ref to its typed struct (rollout.hip, policy_fused.hip, rollout_loop.cpp).
 // Every struct has `n`; the observation width, the columns of an action row and
 // whether the action is a class index are the overloads below.
+//
+// The seeded state-vector kinds (rollout_dev.h: StateEnv<K>) state their facts in ONE
+// row each: X(C-ABI struct, kind code, device kind description, observation width,
+// whether the action -- always one column -- is a class index, as an expression in
+// the struct `e`).  MountainCar is the one kind whose answer is the struct's:
+// MountainCar-v0 takes a class index, MountainCarContinuous-v0 a force.
+#define GA_STATE_ENV_KINDS(X)                                                      \
+  X(ga_cartpole_env, GA_ENV_CARTPOLE, CartPoleKind, 4, 1)                          \
+  X(ga_pendulum_env, GA_ENV_PENDULUM, PendulumKind, 3, 0)                          \
+  X(ga_double_pendulum_env, GA_ENV_DOUBLE_PENDULUM, DoublePendulumKind, 11, 0)     \
+  X(ga_acrobot_env, GA_ENV_ACROBOT, AcrobotKind, 6, 1)                             \
+  X(ga_mountain_car_env, GA_ENV_MOUNTAIN_CAR, MountainCarKind, 2, e->continuous == 0)
+
 inline int ga_env_obs_dim(const ga_synth_env* e) { return e->obs_dim; }
 inline int ga_env_obs_dim(const ga_point_env*) { return 3; }
 inline int ga_env_obs_dim(const ga_grid_env* e) { return e->rows * e->cols; }
 inline int ga_env_obs_dim(const ga_multi_point_env* e) {
   return 3 + (e->mode == GA_TASK_ADD_ONEHOT ? e->num_tasks : 0);
 }
-inline int ga_env_obs_dim(const ga_cartpole_env*) { return 4; }
-inline int ga_env_obs_dim(const ga_pendulum_env*) { return 3; }
-inline int ga_env_obs_dim(const ga_double_pendulum_env*) { return 11; }
-inline int ga_env_obs_dim(const ga_acrobot_env*) { return 6; }
-inline int ga_env_obs_dim(const ga_mountain_car_env*) { return 2; }
 inline int ga_env_discrete(const ga_synth_env* e) { return e->discrete != 0; }
 inline int ga_env_discrete(const ga_point_env*) { return 0; }
 inline int ga_env_discrete(const ga_grid_env*) { return 1; }
 inline int ga_env_discrete(const ga_multi_point_env*) { return 0; }
-inline int ga_env_discrete(const ga_cartpole_env*) { return 1; }
-inline int ga_env_discrete(const ga_pendulum_env*) { return 0; }
-inline int ga_env_discrete(const ga_double_pendulum_env*) { return 0; }
-inline int ga_env_discrete(const ga_acrobot_env*) { return 1; }
-// the one kind whose answer is the struct's: MountainCar-v0 takes a class index,
-// MountainCarContinuous-v0 a force
-inline int ga_env_discrete(const ga_mountain_car_env* e) { return e->continuous == 0; }
 inline int ga_env_act_width(const ga_synth_env* e) { return e->discrete ? 1 : e->act_dim; }
 inline int ga_env_act_width(const ga_point_env*) { return 2; }
 inline int ga_env_act_width(const ga_grid_env*) { return 1; }
 inline int ga_env_act_width(const ga_multi_point_env*) { return 2; }
-inline int ga_env_act_width(const ga_cartpole_env*) { return 1; }
-inline int ga_env_act_width(const ga_pendulum_env*) { return 1; }
-inline int ga_env_act_width(const ga_double_pendulum_env*) { return 1; }
-inline int ga_env_act_width(const ga_acrobot_env*) { return 1; }
-inline int ga_env_act_width(const ga_mountain_car_env*) { return 1; }
+#define GA_STATE_ENV_FACTS(GaEnv, KIND, DEV, OBS, DISCRETE)             \
+  inline int ga_env_obs_dim(const GaEnv*) { return OBS; }               \
+  inline int ga_env_discrete(const GaEnv* e) { return (void)e, (DISCRETE); } \
+  inline int ga_env_act_width(const GaEnv*) { return 1; }
+GA_STATE_ENV_KINDS(GA_STATE_ENV_FACTS)
+#undef GA_STATE_ENV_FACTS
 
 // f(const ga_<kind>_env*) of the env `ref` points to; `who` names the entry point in
 // the two errors this owns
@@ -87,11 +89,10 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
     case GA_ENV_POINT: return f((const ga_point_env*)ref->env);
     case GA_ENV_GRID: return f((const ga_grid_env*)ref->env);
     case GA_ENV_MULTI_POINT: return f((const ga_multi_point_env*)ref->env);
-    case GA_ENV_CARTPOLE: return f((const ga_cartpole_env*)ref->env);
-    case GA_ENV_PENDULUM: return f((const ga_pendulum_env*)ref->env);
-    case GA_ENV_DOUBLE_PENDULUM: return f((const ga_double_pendulum_env*)ref->env);
-    case GA_ENV_ACROBOT: return f((const ga_acrobot_env*)ref->env);
-    case GA_ENV_MOUNTAIN_CAR: return f((const ga_mountain_car_env*)ref->env);
+#define GA_STATE_ENV_CASE(GaEnv, KIND, DEV, OBS, DISCRETE) \
+  case KIND: return f((const GaEnv*)ref->env);
+    GA_STATE_ENV_KINDS(GA_STATE_ENV_CASE)
+#undef GA_STATE_ENV_CASE
   }
   ga_set_error("%s: unknown env kind %d", who, ref->kind);
   return -1;

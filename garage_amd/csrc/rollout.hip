@@ -509,42 +509,17 @@ MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_l
   return d;
 }
 
-CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t) {
-  CartPoleEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.state = e->state; d.t = e->t; d.resets = e->resets;
-  return d;
-}
+// the five seeded state-vector kinds share their field names; MountainCar's
+// `continuous` is the frame's `variant` (0 for the others, whose slot is padding)
+static int state_env_variant(const ga_mountain_car_env* e) { return e->continuous; }
+template <class GaEnv>
+static int state_env_variant(const GaEnv*) { return 0; }
 
-PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t) {
-  PendulumEnv d;
+template <class GaEnv, class K>
+StateEnv<K> ga_env_to_dev(const GaEnv* e, int64_t) {
+  StateEnv<K> d;
   d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.state = e->state; d.t = e->t; d.resets = e->resets;
-  return d;
-}
-
-DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e, int64_t) {
-  DoublePendulumEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.state = e->state; d.t = e->t; d.resets = e->resets;
-  return d;
-}
-
-AcrobotEnv ga_env_to_dev(const ga_acrobot_env* e, int64_t) {
-  AcrobotEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.state = e->state; d.t = e->t; d.resets = e->resets;
-  return d;
-}
-
-MountainCarEnv ga_env_to_dev(const ga_mountain_car_env* e, int64_t) {
-  MountainCarEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  d.continuous = e->continuous;
+  d.variant = state_env_variant(e);
   ga_key(e->seed, &d.k0, &d.k1);
   d.state = e->state; d.t = e->t; d.resets = e->resets;
   return d;
@@ -592,45 +567,14 @@ static int check_env(const ga_multi_point_env* e, const char* who) {
   return GA_OK;
 }
 
-static int check_env(const ga_cartpole_env* e, const char* who) {
+template <class GaEnv, class K = typename ga_state_kind_of<GaEnv>::type>
+static int check_env(const GaEnv* e, const char* who) {
   GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
   GA_REQUIRE(e->n > 0, "%s: bad env size", who);
   GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
              "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_pendulum_env* e, const char* who) {
-  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_double_pendulum_env* e, const char* who) {
-  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_acrobot_env* e, const char* who) {
-  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_mountain_car_env* e, const char* who) {
-  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  GA_REQUIRE(e->continuous == 0 || e->continuous == 1, "%s: continuous must be 0 or 1",
-             who);
+  const int variant = state_env_variant(e);
+  GA_REQUIRE(variant == 0 || variant == 1, "%s: continuous must be 0 or 1", who);
   return GA_OK;
 }
 
@@ -691,11 +635,9 @@ GA_BUILD_ENV_STEP_OF(ga_synth_env)
 GA_BUILD_ENV_STEP_OF(ga_point_env)
 GA_BUILD_ENV_STEP_OF(ga_grid_env)
 GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
-GA_BUILD_ENV_STEP_OF(ga_cartpole_env)
-GA_BUILD_ENV_STEP_OF(ga_pendulum_env)
-GA_BUILD_ENV_STEP_OF(ga_double_pendulum_env)
-GA_BUILD_ENV_STEP_OF(ga_acrobot_env)
-GA_BUILD_ENV_STEP_OF(ga_mountain_car_env)
+#define GA_BUILD_STATE_ENV_STEP_OF(E, KIND, DEV, OBS, DISCRETE) GA_BUILD_ENV_STEP_OF(E)
+GA_STATE_ENV_KINDS(GA_BUILD_STATE_ENV_STEP_OF)
+#undef GA_BUILD_STATE_ENV_STEP_OF
 #undef GA_BUILD_ENV_STEP_OF
 
 // Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
@@ -768,66 +710,47 @@ extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t co
   return task_draw(k0, k1, (uint32_t)env_id, counter, num_tasks);
 }
 
-// the device's cartpole_reset_draw on the host (tests compare it with a pure-Python
-// Philox; garage_amd.envs.CartPoleEnv starts its episodes from it)
+// The device's reset draws on the host: the state reset number `counter` gives env
+// `env_id` of kind K (tests compare them with a pure-Python Philox; the host twins of
+// garage_amd.envs start their episodes from them)
+template <class K>
+static int state_reset_draw(const char* who, uint64_t seed, int64_t env_id,
+                            uint32_t counter, float* out) {
+  GA_REQUIRE(out, "%s: null pointer", who);
+  uint32_t k0, k1;
+  ga_key(seed, &k0, &k1);
+  state_store<K>(K::reset_draw(k0, k1, (uint32_t)env_id, counter), out);
+  return GA_OK;
+}
+
 extern "C" int ga_cartpole_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                       float out4[4]) {
-  GA_REQUIRE(out4, "ga_cartpole_reset_draw: null pointer");
-  uint32_t k0, k1;
-  ga_key(seed, &k0, &k1);
-  const CartPoleState s = cartpole_reset_draw(k0, k1, (uint32_t)env_id, counter);
-  out4[0] = s.x; out4[1] = s.xd; out4[2] = s.th; out4[3] = s.thd;
-  return GA_OK;
+  return state_reset_draw<CartPoleKind>("ga_cartpole_reset_draw", seed, env_id, counter,
+                                        out4);
 }
 
-// the device's pendulum_reset_draw on the host (garage_amd.envs.PendulumEnv starts its
-// episodes from it)
 extern "C" int ga_pendulum_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                       float out2[2]) {
-  GA_REQUIRE(out2, "ga_pendulum_reset_draw: null pointer");
-  uint32_t k0, k1;
-  ga_key(seed, &k0, &k1);
-  const PendulumState s = pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
-  out2[0] = s.th; out2[1] = s.thd;
-  return GA_OK;
+  return state_reset_draw<PendulumKind>("ga_pendulum_reset_draw", seed, env_id, counter,
+                                        out2);
 }
 
-// the device's double_pendulum_reset_draw on the host
-// (garage_amd.envs.DoublePendulumEnv starts its episodes from it)
 extern "C" int ga_double_pendulum_reset_draw(uint64_t seed, int64_t env_id,
                                              uint32_t counter, float out6[6]) {
-  GA_REQUIRE(out6, "ga_double_pendulum_reset_draw: null pointer");
-  uint32_t k0, k1;
-  ga_key(seed, &k0, &k1);
-  const DoublePendulumState s =
-      double_pendulum_reset_draw(k0, k1, (uint32_t)env_id, counter);
-  out6[0] = s.x; out6[1] = s.th1; out6[2] = s.th2;
-  out6[3] = s.xd; out6[4] = s.th1d; out6[5] = s.th2d;
-  return GA_OK;
+  return state_reset_draw<DoublePendulumKind>("ga_double_pendulum_reset_draw", seed,
+                                              env_id, counter, out6);
 }
 
-// the device's acrobot_reset_draw on the host (garage_amd.envs.AcrobotEnv starts its
-// episodes from it)
 extern "C" int ga_acrobot_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                      float out4[4]) {
-  GA_REQUIRE(out4, "ga_acrobot_reset_draw: null pointer");
-  uint32_t k0, k1;
-  ga_key(seed, &k0, &k1);
-  const AcrobotState s = acrobot_reset_draw(k0, k1, (uint32_t)env_id, counter);
-  out4[0] = s.th1; out4[1] = s.th2; out4[2] = s.w1; out4[3] = s.w2;
-  return GA_OK;
+  return state_reset_draw<AcrobotKind>("ga_acrobot_reset_draw", seed, env_id, counter,
+                                       out4);
 }
 
-// the device's mountain_car_reset_draw on the host (garage_amd.envs.MountainCarEnv
-// starts its episodes from it)
 extern "C" int ga_mountain_car_reset_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                           float out2[2]) {
-  GA_REQUIRE(out2, "ga_mountain_car_reset_draw: null pointer");
-  uint32_t k0, k1;
-  ga_key(seed, &k0, &k1);
-  const MountainCarState s = mountain_car_reset_draw(k0, k1, (uint32_t)env_id, counter);
-  out2[0] = s.x; out2[1] = s.v;
-  return GA_OK;
+  return state_reset_draw<MountainCarKind>("ga_mountain_car_reset_draw", seed, env_id,
+                                           counter, out2);
 }
 
 extern "C" int ga_pack_episodes(const uint16_t* tail_buf, int64_t n, int64_t Tcap,

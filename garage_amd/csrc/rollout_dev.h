@@ -3,7 +3,8 @@
 // (HeadDev, head_one), the device environments (synthetic, PointEnv, GridWorldEnv,
 // MultiEnvWrapper over PointEnv, CartPole, Pendulum, the inverted double pendulum,
 // Acrobot, MountainCar;
-// env_pre / env_core / env_reset_one of each),
+// env_pre / env_core / env_reset_one of each -- of the last five, the seeded
+// state-vector kinds, written once over a kind description: StateEnv<K>),
 // the NormalizedEnv statistics, the per-step bookkeeping of VecWorker.step_episode
 // (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
 #pragma once
@@ -447,22 +448,93 @@ static __device__ __forceinline__ void env_core(const GridEnv& e, int64_t i,
   grid_one_hot(e, next, next_row);
 }
 
-// ---- CartPole (include/garage_amd.h states the arithmetic, operation by operation) ----
-// One fp32 operation per statement, no contraction; `/` is the correctly rounded
-// division.  The step and the reset draw are written once, here.
-struct CartPoleEnv {
+// ---- seeded state-vector envs: the frame ------------------------------------------
+// CartPole, Pendulum, the inverted double pendulum, Acrobot and MountainCar are one
+// kind of object: an [n, S] fp32 state, a step counter and a reset counter per member,
+// a Philox reset stream keyed (seed; env_id0 + i, resets[i]) and a finite max_len
+// whose last step is TIMEOUT.  What is not dynamics is written once, here, over a
+// kind description K (CartPoleKind ... MountainCarKind below), which states
+//   State, S    the state: a struct of S floats, in the order of its row of `state`
+//   OBS         the observation width
+//   reset_draw  (k0, k1, env, counter) -> State, on the kind's own Philox stream
+//   observe     (State, o): the observation of a state (what a reset shows)
+//   step        (State*, action row, variant, reward*, o) -> done: one step; o is the
+//               observation of the new state
+// A new kind costs that description, its C-ABI struct and its row of
+// GA_STATE_ENV_KINDS (internal.h).
+template <class K>
+struct StateEnv {
   int64_t n;
   int64_t env_id0;   // global id of env 0 of this shard
   int max_len;
+  int variant;       // the kind's own switch (MountainCar: continuous), else 0
   uint32_t k0, k1;   // seed
-  float* state;      // [n, 4] x, x_dot, theta, theta_dot
+  float* state;      // [n, K::S]
   int32_t* t;        // [n] steps taken in the current episode
   uint32_t* resets;  // [n] resets so far (the reset stream's counter)
 };
-struct CartPolePre {
-  float x, xd, th, thd;
+template <class K>
+struct StatePre {
+  typename K::State s;
   int t, ep_t;
 };
+
+// A State and its row: S floats either way.  The copies index with compile-time
+// constants, so a state lives in registers.
+template <class K>
+struct StateRow { float v[K::S]; };
+template <class K>
+static __host__ __device__ __forceinline__ typename K::State state_load(const float* row) {
+  static_assert(sizeof(typename K::State) == sizeof(StateRow<K>), "State is S floats");
+  StateRow<K> w;
+#pragma unroll
+  for (int j = 0; j < K::S; ++j) w.v[j] = row[j];
+  return __builtin_bit_cast(typename K::State, w);
+}
+template <class K>
+static __host__ __device__ __forceinline__ void state_store(const typename K::State& s,
+                                                            float* row) {
+  const StateRow<K> w = __builtin_bit_cast(StateRow<K>, s);
+#pragma unroll
+  for (int j = 0; j < K::S; ++j) row[j] = w.v[j];
+}
+
+// The stores of a reset and of a step keep one order: (counters,) state, t, observation.
+template <class K>
+static __device__ __forceinline__ void env_reset_one(const StateEnv<K>& e, int64_t i,
+                                                     float* obs, int64_t ldo) {
+  const uint32_t cnt = e.resets[i];
+  const typename K::State s = K::reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
+  e.resets[i] = cnt + 1u;
+  e.t[i] = 0;
+  float o[K::OBS];
+  K::observe(s, o);
+  state_store<K>(s, e.state + K::S * i);
+  float* row = obs + i * ldo;
+#pragma unroll
+  for (int j = 0; j < K::OBS; ++j) row[j] = o[j];
+}
+
+template <class K>
+static __device__ __forceinline__ void env_core(const StateEnv<K>& e, int64_t i,
+                                                const StatePre<K>& p, const float* a,
+                                                const float*, float* next_row, int64_t,
+                                                float* reward, uint8_t* step_type) {
+  typename K::State s = p.s;
+  float o[K::OBS];
+  const bool done = K::step(&s, a, e.variant, reward, o);
+  state_store<K>(s, e.state + K::S * i);
+  const int tn = p.t + 1;
+  e.t[i] = tn;
+  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
+  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
+#pragma unroll
+  for (int j = 0; j < K::OBS; ++j) next_row[j] = o[j];
+}
+
+// ---- CartPole (include/garage_amd.h states the arithmetic, operation by operation) ----
+// One fp32 operation per statement, no contraction; `/` is the correctly rounded
+// division.  The step and the reset draw are written once, here.
 struct CartPoleState { float x, xd, th, thd; };
 
 // the state reset number `counter` gives env `env` (global id)
@@ -536,51 +608,30 @@ static __host__ __device__ __forceinline__ bool cartpole_advance(CartPoleState* 
   return __builtin_fabsf(nx) > 2.4f || __builtin_fabsf(nth) > TH_LIMIT;
 }
 
-static __device__ __forceinline__ void env_reset_one(const CartPoleEnv& e, int64_t i,
-                                                     float* obs, int64_t ldo) {
-  const uint32_t cnt = e.resets[i];
-  const CartPoleState s =
-      cartpole_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
-  e.resets[i] = cnt + 1u;
-  e.t[i] = 0;
-  float* st = e.state + 4 * i;
-  float* o = obs + i * ldo;
-  st[0] = s.x; st[1] = s.xd; st[2] = s.th; st[3] = s.thd;
-  o[0] = s.x; o[1] = s.xd; o[2] = s.th; o[3] = s.thd;
-}
-
-static __device__ __forceinline__ void env_core(const CartPoleEnv& e, int64_t i,
-                                                const CartPolePre& p, const float* a,
-                                                const float*, float* next_row, int64_t,
-                                                float* reward, uint8_t* step_type) {
-  CartPoleState s{p.x, p.xd, p.th, p.thd};
-  const bool done = cartpole_advance(&s, (int)a[0] == 1);
-  float* st = e.state + 4 * i;
-  st[0] = s.x; st[1] = s.xd; st[2] = s.th; st[3] = s.thd;
-  *reward = 1.0f;
-  const int tn = p.t + 1;
-  e.t[i] = tn;
-  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
-  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
-  next_row[0] = s.x; next_row[1] = s.xd; next_row[2] = s.th; next_row[3] = s.thd;
-}
+// state [n, 4] x, x_dot, theta, theta_dot; the observation is the state
+struct CartPoleKind {
+  using State = CartPoleState;
+  static constexpr int S = 4, OBS = 4;
+  static __host__ __device__ __forceinline__ State reset_draw(uint32_t k0, uint32_t k1,
+                                                              uint32_t env,
+                                                              uint32_t counter) {
+    return cartpole_reset_draw(k0, k1, env, counter);
+  }
+  static __device__ __forceinline__ void observe(const State& s, float* o) {
+    o[0] = s.x; o[1] = s.xd; o[2] = s.th; o[3] = s.thd;
+  }
+  static __device__ __forceinline__ bool step(State* s, const float* a, int,
+                                              float* reward, float* o) {
+    const bool done = cartpole_advance(s, (int)a[0] == 1);
+    *reward = 1.0f;
+    observe(*s, o);
+    return done;
+  }
+};
 
 // ---- Pendulum (include/garage_amd.h states the arithmetic, operation by operation) ----
 // One fp32 operation per statement, no contraction.  sincos, the step and the reset
 // draw are written once, here.
-struct PendulumEnv {
-  int64_t n;
-  int64_t env_id0;   // global id of env 0 of this shard
-  int max_len;
-  uint32_t k0, k1;   // seed
-  float* state;      // [n, 2] theta in [-PI, PI], theta_dot in [-8, 8]
-  int32_t* t;        // [n] steps taken in the current episode
-  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
-};
-struct PendulumPre {
-  float th, thd;
-  int t, ep_t;
-};
 struct PendulumState { float th, thd; };
 
 constexpr float PENDULUM_PI = (float)3.141592653589793;
@@ -680,57 +731,35 @@ static __host__ __device__ __forceinline__ float pendulum_advance(PendulumState*
   return -cost;
 }
 
-static __device__ __forceinline__ void env_reset_one(const PendulumEnv& e, int64_t i,
-                                                     float* obs, int64_t ldo) {
-  const uint32_t cnt = e.resets[i];
-  const PendulumState s =
-      pendulum_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
-  e.resets[i] = cnt + 1u;
-  e.t[i] = 0;
-  float sn, cs;
-  pendulum_sincos(s.th, &sn, &cs);
-  float* st = e.state + 2 * i;
-  float* o = obs + i * ldo;
-  st[0] = s.th; st[1] = s.thd;
-  o[0] = cs; o[1] = sn; o[2] = s.thd;
-}
-
-static __device__ __forceinline__ void env_core(const PendulumEnv& e, int64_t i,
-                                                const PendulumPre& p, const float* a,
-                                                const float*, float* next_row, int64_t,
-                                                float* reward, uint8_t* step_type) {
-  PendulumState s{p.th, p.thd};
-  *reward = pendulum_advance(&s, a[0]);
-  float sn, cs;
-  pendulum_sincos(s.th, &sn, &cs);
-  float* st = e.state + 2 * i;
-  st[0] = s.th; st[1] = s.thd;
-  const int tn = p.t + 1;
-  e.t[i] = tn;
-  // never done: the step that reaches max_len is TIMEOUT (_dtypes.py:42-68)
-  *step_type = tn >= e.max_len ? 3 : tn == 1 ? 0 : 1;
-  next_row[0] = cs; next_row[1] = sn; next_row[2] = s.thd;
-}
+// state [n, 2] theta in [-PI, PI], theta_dot in [-8, 8]
+struct PendulumKind {
+  using State = PendulumState;
+  static constexpr int S = 2, OBS = 3;
+  static __host__ __device__ __forceinline__ State reset_draw(uint32_t k0, uint32_t k1,
+                                                              uint32_t env,
+                                                              uint32_t counter) {
+    return pendulum_reset_draw(k0, k1, env, counter);
+  }
+  static __device__ __forceinline__ void observe(const State& s, float* o) {
+    float sn, cs;
+    pendulum_sincos(s.th, &sn, &cs);
+    o[0] = cs; o[1] = sn; o[2] = s.thd;
+  }
+  // never done: the step that reaches max_len is TIMEOUT
+  static __device__ __forceinline__ bool step(State* s, const float* a, int,
+                                              float* reward, float* o) {
+    *reward = pendulum_advance(s, a[0]);
+    observe(*s, o);
+    return false;
+  }
+};
 
 // ---- Inverted double pendulum on a cart (include/garage_amd.h states the arithmetic,
 // operation by operation) ----
 // One fp32 operation per statement, no contraction; `/` is the correctly rounded
 // division.  The step and the reset draw are written once, here; sin and cos are
 // Pendulum's.
-struct DoublePendulumEnv {
-  int64_t n;
-  int64_t env_id0;   // global id of env 0 of this shard
-  int max_len;
-  uint32_t k0, k1;   // seed
-  float* state;      // [n, 6] x, th1, th2, xd, th1d, th2d; th1, th2 in [-PI, PI]
-  int32_t* t;        // [n] steps taken in the current episode
-  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
-};
 struct DoublePendulumState { float x, th1, th2, xd, th1d, th2d; };
-struct DoublePendulumPre {
-  DoublePendulumState s;
-  int t, ep_t;
-};
 // what a step (or a reset) shows of the state it leaves: the sines and cosines of the
 // two angles and of their difference
 struct DoublePendulumTrig { float s1, c1, sd, cd, yt; };
@@ -912,57 +941,35 @@ static __host__ __device__ __forceinline__ float double_pendulum_advance(
   return alive - vel;
 }
 
-static __device__ __forceinline__ void env_reset_one(const DoublePendulumEnv& e,
-                                                     int64_t i, float* obs,
-                                                     int64_t ldo) {
-  const uint32_t cnt = e.resets[i];
-  const DoublePendulumState s =
-      double_pendulum_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
-  e.resets[i] = cnt + 1u;
-  e.t[i] = 0;
-  float s2_unused;
-  const DoublePendulumTrig g = double_pendulum_trig(s, &s2_unused);
-  float* st = e.state + 6 * i;
-  st[0] = s.x; st[1] = s.th1; st[2] = s.th2; st[3] = s.xd; st[4] = s.th1d; st[5] = s.th2d;
-  double_pendulum_obs(s, g, obs + i * ldo);
-}
-
-static __device__ __forceinline__ void env_core(const DoublePendulumEnv& e, int64_t i,
-                                                const DoublePendulumPre& p,
-                                                const float* a, const float*,
-                                                float* next_row, int64_t, float* reward,
-                                                uint8_t* step_type) {
-  DoublePendulumState s = p.s;
-  DoublePendulumTrig g;
-  bool done;
-  *reward = double_pendulum_advance(&s, a[0], &g, &done);
-  float* st = e.state + 6 * i;
-  st[0] = s.x; st[1] = s.th1; st[2] = s.th2; st[3] = s.xd; st[4] = s.th1d; st[5] = s.th2d;
-  const int tn = p.t + 1;
-  e.t[i] = tn;
-  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
-  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
-  double_pendulum_obs(s, g, next_row);
-}
+// state [n, 6] x, th1, th2, xd, th1d, th2d; th1, th2 in [-PI, PI]
+struct DoublePendulumKind {
+  using State = DoublePendulumState;
+  static constexpr int S = 6, OBS = 11;
+  static __host__ __device__ __forceinline__ State reset_draw(uint32_t k0, uint32_t k1,
+                                                              uint32_t env,
+                                                              uint32_t counter) {
+    return double_pendulum_reset_draw(k0, k1, env, counter);
+  }
+  static __device__ __forceinline__ void observe(const State& s, float* o) {
+    float s2_unused;
+    double_pendulum_obs(s, double_pendulum_trig(s, &s2_unused), o);
+  }
+  // the observation comes from the trigonometry the step has already evaluated
+  static __device__ __forceinline__ bool step(State* s, const float* a, int,
+                                              float* reward, float* o) {
+    DoublePendulumTrig g;
+    bool done;
+    *reward = double_pendulum_advance(s, a[0], &g, &done);
+    double_pendulum_obs(*s, g, o);
+    return done;
+  }
+};
 
 // ---- Acrobot (include/garage_amd.h states the arithmetic, operation by operation) ----
 // One fp32 operation per statement, no contraction; `/` is the correctly rounded
 // division.  The reduction, the dynamics, the RK4 step and the reset draw are written
 // once, here; sin and cos are Pendulum's.
-struct AcrobotEnv {
-  int64_t n;
-  int64_t env_id0;   // global id of env 0 of this shard
-  int max_len;
-  uint32_t k0, k1;   // seed
-  float* state;      // [n, 4] th1, th2, thd1, thd2; th1, th2 in [-PI, PI]
-  int32_t* t;        // [n] steps taken in the current episode
-  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
-};
 struct AcrobotState { float th1, th2, w1, w2; };
-struct AcrobotPre {
-  AcrobotState s;
-  int t, ep_t;
-};
 struct AcrobotTrig { float s1, c1, s2, c2; };
 
 constexpr float ACROBOT_INV_TWO_PI = (float)(1.0 / 6.283185307179586);
@@ -1111,58 +1118,41 @@ static __host__ __device__ __forceinline__ float three_way_push(int k) {
   return k == 0 ? -1.0f : (k == 2 ? 1.0f : 0.0f);
 }
 
-static __device__ __forceinline__ void env_reset_one(const AcrobotEnv& e, int64_t i,
-                                                     float* obs, int64_t ldo) {
-  const uint32_t cnt = e.resets[i];
-  const AcrobotState s = acrobot_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
-  e.resets[i] = cnt + 1u;
-  e.t[i] = 0;
-  float s1, c1, s2, c2;
-  pendulum_sincos(s.th1, &s1, &c1);
-  pendulum_sincos(s.th2, &s2, &c2);
-  float* st = e.state + 4 * i;
-  float* o = obs + i * ldo;
-  st[0] = s.th1; st[1] = s.th2; st[2] = s.w1; st[3] = s.w2;
-  o[0] = c1; o[1] = s1; o[2] = c2; o[3] = s2; o[4] = s.w1; o[5] = s.w2;
-}
-
-static __device__ __forceinline__ void env_core(const AcrobotEnv& e, int64_t i,
-                                                const AcrobotPre& p, const float* a,
-                                                const float*, float* next_row, int64_t,
-                                                float* reward, uint8_t* step_type) {
-  AcrobotState s = p.s;
-  AcrobotTrig g;
-  const bool done = acrobot_advance(&s, three_way_push((int)a[0]), &g);
-  float* st = e.state + 4 * i;
-  st[0] = s.th1; st[1] = s.th2; st[2] = s.w1; st[3] = s.w2;
-  *reward = done ? 0.0f : -1.0f;
-  const int tn = p.t + 1;
-  e.t[i] = tn;
-  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
-  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
-  next_row[0] = g.c1; next_row[1] = g.s1; next_row[2] = g.c2; next_row[3] = g.s2;
-  next_row[4] = s.w1; next_row[5] = s.w2;
-}
+// state [n, 4] th1, th2, thd1, thd2; th1, th2 in [-PI, PI]
+struct AcrobotKind {
+  using State = AcrobotState;
+  static constexpr int S = 4, OBS = 6;
+  static __host__ __device__ __forceinline__ State reset_draw(uint32_t k0, uint32_t k1,
+                                                              uint32_t env,
+                                                              uint32_t counter) {
+    return acrobot_reset_draw(k0, k1, env, counter);
+  }
+  static __device__ __forceinline__ void show(const State& s, const AcrobotTrig& g,
+                                              float* o) {
+    o[0] = g.c1; o[1] = g.s1; o[2] = g.c2; o[3] = g.s2; o[4] = s.w1; o[5] = s.w2;
+  }
+  static __device__ __forceinline__ void observe(const State& s, float* o) {
+    AcrobotTrig g;
+    pendulum_sincos(s.th1, &g.s1, &g.c1);
+    pendulum_sincos(s.th2, &g.s2, &g.c2);
+    show(s, g, o);
+  }
+  // the observation comes from the sines and cosines the step has already evaluated
+  static __device__ __forceinline__ bool step(State* s, const float* a, int,
+                                              float* reward, float* o) {
+    AcrobotTrig g;
+    const bool done = acrobot_advance(s, three_way_push((int)a[0]), &g);
+    *reward = done ? 0.0f : -1.0f;
+    show(*s, g, o);
+    return done;
+  }
+};
 
 // ---- MountainCar, discrete and continuous (include/garage_amd.h states the arithmetic,
 // operation by operation) ----
 // One fp32 operation per statement, no contraction.  The step and the reset draw are
 // written once, here; the cosine is Pendulum's.
-struct MountainCarEnv {
-  int64_t n;
-  int64_t env_id0;   // global id of env 0 of this shard
-  int max_len;
-  int continuous;    // 0: MountainCar-v0 (class index), 1: MountainCarContinuous-v0
-  uint32_t k0, k1;   // seed
-  float* state;      // [n, 2] x in [-1.2, 0.6], v in [-0.07, 0.07]
-  int32_t* t;        // [n] steps taken in the current episode
-  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
-};
 struct MountainCarState { float x, v; };
-struct MountainCarPre {
-  float x, v;
-  int t, ep_t;
-};
 
 // the state reset number `counter` gives env `env` (global id)
 static __host__ __device__ __forceinline__ MountainCarState mountain_car_reset_draw(
@@ -1215,33 +1205,26 @@ static __host__ __device__ __forceinline__ bool mountain_car_advance(MountainCar
   return done;
 }
 
-static __device__ __forceinline__ void env_reset_one(const MountainCarEnv& e, int64_t i,
-                                                     float* obs, int64_t ldo) {
-  const uint32_t cnt = e.resets[i];
-  const MountainCarState s =
-      mountain_car_reset_draw(e.k0, e.k1, (uint32_t)(e.env_id0 + i), cnt);
-  e.resets[i] = cnt + 1u;
-  e.t[i] = 0;
-  float* st = e.state + 2 * i;
-  float* o = obs + i * ldo;
-  st[0] = s.x; st[1] = s.v;
-  o[0] = s.x; o[1] = s.v;
-}
-
-static __device__ __forceinline__ void env_core(const MountainCarEnv& e, int64_t i,
-                                                const MountainCarPre& p, const float* a,
-                                                const float*, float* next_row, int64_t,
-                                                float* reward, uint8_t* step_type) {
-  MountainCarState s{p.x, p.v};
-  const bool done = mountain_car_advance(&s, a[0], e.continuous != 0, reward);
-  float* st = e.state + 2 * i;
-  st[0] = s.x; st[1] = s.v;
-  const int tn = p.t + 1;
-  e.t[i] = tn;
-  // StepType.get_step_type (_dtypes.py:42-68): TIMEOUT wins over done
-  *step_type = tn >= e.max_len ? 3 : done ? 2 : tn == 1 ? 0 : 1;
-  next_row[0] = s.x; next_row[1] = s.v;
-}
+// state [n, 2] x in [-1.2, 0.6], v in [-0.07, 0.07]; the observation is the state.
+// variant 0: MountainCar-v0 (class index), 1: MountainCarContinuous-v0
+struct MountainCarKind {
+  using State = MountainCarState;
+  static constexpr int S = 2, OBS = 2;
+  static __host__ __device__ __forceinline__ State reset_draw(uint32_t k0, uint32_t k1,
+                                                              uint32_t env,
+                                                              uint32_t counter) {
+    return mountain_car_reset_draw(k0, k1, env, counter);
+  }
+  static __device__ __forceinline__ void observe(const State& s, float* o) {
+    o[0] = s.x; o[1] = s.v;
+  }
+  static __device__ __forceinline__ bool step(State* s, const float* a, int continuous,
+                                              float* reward, float* o) {
+    const bool done = mountain_car_advance(s, a[0], continuous != 0, reward);
+    observe(*s, o);
+    return done;
+  }
+};
 
 // What a step of env i reads of the env's and the worker's state: loaded up front,
 // so that no load waits behind the step's own stores (the memory counter retires in
@@ -1475,49 +1458,10 @@ static __device__ __forceinline__ GridPre env_pre(const GridEnv& e, int64_t i) {
   s.ep_t = 0;
   return s;
 }
-static __device__ __forceinline__ CartPolePre env_pre(const CartPoleEnv& e, int64_t i) {
-  CartPolePre s;
-  const float* st = e.state + 4 * i;
-  s.x = st[0];
-  s.xd = st[1];
-  s.th = st[2];
-  s.thd = st[3];
-  s.t = e.t[i];
-  s.ep_t = 0;
-  return s;
-}
-static __device__ __forceinline__ PendulumPre env_pre(const PendulumEnv& e, int64_t i) {
-  PendulumPre s;
-  const float* st = e.state + 2 * i;
-  s.th = st[0];
-  s.thd = st[1];
-  s.t = e.t[i];
-  s.ep_t = 0;
-  return s;
-}
-static __device__ __forceinline__ DoublePendulumPre env_pre(const DoublePendulumEnv& e,
-                                                            int64_t i) {
-  DoublePendulumPre s;
-  const float* st = e.state + 6 * i;
-  s.s = DoublePendulumState{st[0], st[1], st[2], st[3], st[4], st[5]};
-  s.t = e.t[i];
-  s.ep_t = 0;
-  return s;
-}
-static __device__ __forceinline__ AcrobotPre env_pre(const AcrobotEnv& e, int64_t i) {
-  AcrobotPre s;
-  const float* st = e.state + 4 * i;
-  s.s = AcrobotState{st[0], st[1], st[2], st[3]};
-  s.t = e.t[i];
-  s.ep_t = 0;
-  return s;
-}
-static __device__ __forceinline__ MountainCarPre env_pre(const MountainCarEnv& e,
-                                                         int64_t i) {
-  MountainCarPre s;
-  const float* st = e.state + 2 * i;
-  s.x = st[0];
-  s.v = st[1];
+template <class K>
+static __device__ __forceinline__ StatePre<K> env_pre(const StateEnv<K>& e, int64_t i) {
+  StatePre<K> s;
+  s.s = state_load<K>(e.state + K::S * i);
   s.t = e.t[i];
   s.ep_t = 0;
   return s;
@@ -1585,12 +1529,20 @@ ga_rollout::PointEnv ga_env_to_dev(const ga_point_env* e, int64_t info_ld);
 ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
 ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_point_env* e,
                                                              int64_t info_ld);
-ga_rollout::CartPoleEnv ga_env_to_dev(const ga_cartpole_env* e, int64_t info_ld);
-ga_rollout::PendulumEnv ga_env_to_dev(const ga_pendulum_env* e, int64_t info_ld);
-ga_rollout::DoublePendulumEnv ga_env_to_dev(const ga_double_pendulum_env* e,
-                                            int64_t info_ld);
-ga_rollout::AcrobotEnv ga_env_to_dev(const ga_acrobot_env* e, int64_t info_ld);
-ga_rollout::MountainCarEnv ga_env_to_dev(const ga_mountain_car_env* e, int64_t info_ld);
+// the kind description of each row of GA_STATE_ENV_KINDS (internal.h), whose
+// observation width must be the description's; their one converter
+template <class GaEnv>
+struct ga_state_kind_of {};
+#define GA_STATE_ENV_KIND_OF(GaEnv, KIND, DEV, WIDTH, DISCRETE)                  \
+  template <>                                                                    \
+  struct ga_state_kind_of<GaEnv> {                                               \
+    using type = ga_rollout::DEV;                                                \
+    static_assert(type::OBS == WIDTH, "observation width of " #GaEnv);           \
+  };
+GA_STATE_ENV_KINDS(GA_STATE_ENV_KIND_OF)
+#undef GA_STATE_ENV_KIND_OF
+template <class GaEnv, class K = typename ga_state_kind_of<GaEnv>::type>
+ga_rollout::StateEnv<K> ga_env_to_dev(const GaEnv* e, int64_t info_ld);
 template <class GaEnv>
 using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;

@@ -624,7 +624,145 @@ class GridWorldVecEnv(_DeviceVecEnv):
         self._set_struct(e)
 
 
-class CartPoleVecEnv(_DeviceVecEnv):
+class _StateVecEnv(_DeviceVecEnv):
+    """A seeded state-vector batch: an ``(n, S)`` float32 state, a step and a
+    reset counter per member, Philox reset draws keyed ``(seed; env_id0 + i,
+    the member's reset counter)`` and a finite ``max_episode_length`` whose
+    last step is TIMEOUT (``rollout_dev.h``: ``StateEnv<K>``).  A kind states
+    ``_KIND``, its ctypes struct ``_STRUCT``, the state width ``_S``, its spec
+    (``_make_spec``) and, where they are not trivial, what ``set_state``
+    accepts (``_check_states``) and the observations of states
+    (``_observe``); its constructor names its own default length."""
+
+    _STATE = ('_state', '_t', '_resets')
+    env_info_specs = {}
+    _STRUCT = None
+    _S = 0
+
+    def _init_batch(self, n_envs, max_episode_length, seed, env_id0, device):
+        self.n_envs = int(n_envs)
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed = int(seed)
+        self.env_id0 = int(env_id0)
+        self.spec = self._make_spec(self.max_episode_length)
+        self._init_device(device)
+
+    def _new_struct(self):
+        return self._STRUCT()
+
+    def _init_device(self, device):
+        device = device or require_gpu()
+        self._alloc(device)
+        n = self.n_envs
+        self._state = torch.zeros(n, self._S, dtype=torch.float32,
+                                  device=device)
+        self._t = torch.zeros(n, dtype=torch.int32, device=device)
+        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
+        e = self._new_struct()
+        e.n, e.env_id0 = n, self.env_id0
+        e.max_episode_length = self.max_episode_length
+        e.seed = self.seed
+        e.state = self._state.data_ptr()
+        e.t = self._t.data_ptr()
+        e.resets = self._resets.data_ptr()
+        self._set_struct(e)
+
+    def _check_states(self, states):
+        """Raises ``ValueError`` for ``(n, S)`` states the kind cannot hold."""
+
+    def _observe(self, states):
+        """The observations of ``(n, S)`` states (by default the states)."""
+        return states
+
+    def set_state(self, states):
+        """Every member's state <- row of ``states`` (``(n, S)`` float32, what
+        the kind's ``_check_states`` accepts); the current observations
+        follow."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.shape != (self.n_envs, self._S):
+            raise ValueError('set_state needs an ({}, {}) array, got {}'.format(
+                self.n_envs, self._S, states.shape))
+        self._check_states(states)
+        obs = self._observe(states)
+        self._state.copy_(torch.from_numpy(states))
+        self.obs[:, :obs.shape[1]].copy_(torch.from_numpy(obs))
+
+    def get_state(self):
+        """The ``(n, S)`` float32 states."""
+        return self._state.cpu().numpy()
+
+
+def _state_reset_draw(entry, width, seed, env_id, counter):
+    """``ga_*_reset_draw``: the ``(width,)`` float32 state of one reset."""
+    out = (C.c_float * width)()
+    call(entry, int(seed), int(env_id), int(counter), out)
+    return np.array(out, dtype=np.float32)
+
+
+# what a host twin's ``step`` returns (garage's ``EnvStep`` fields)
+StateEnvStep = collections.namedtuple(
+    'StateEnvStep', ['action', 'reward', 'observation', 'env_info',
+                     'step_type'])
+CartPoleStep = PendulumStep = DoublePendulumStep = StateEnvStep
+AcrobotStep = MountainCarStep = StateEnvStep
+_F = np.float32
+
+
+class _StateEnv:
+    """One member of a :class:`_StateVecEnv` on the host: the bookkeeping every
+    twin shares.  A kind states its spec (``_make_spec``), its reset draw
+    (``_reset_draw``), ``advance`` and, where they are not trivial, ``observe``
+    (the observation of a state), ``_action`` (what ``advance`` takes of a
+    policy's action) and ``_advance``."""
+
+    _S = 0
+
+    def _init_twin(self, seed, env_id, max_episode_length):
+        self.max_episode_length = _check_finite_length(max_episode_length)
+        self.seed, self.env_id = int(seed), int(env_id)
+        self.spec = self._make_spec(self.max_episode_length)
+        self.resets = 0
+        self.state = np.zeros(self._S, dtype=np.float32)
+        self._t = 0
+
+    @classmethod
+    def observe(cls, state):
+        """The observations of ``state`` (``(..., S)``): the states."""
+        return np.array(state, dtype=np.float32)
+
+    @staticmethod
+    def _action(action):
+        """The torque / force of a continuous kind."""
+        return np.asarray(action, dtype=np.float32).reshape(-1)[0]
+
+    def _advance(self, a):
+        """``(state, observation, reward, done)`` after one step with ``a``."""
+        new, obs, reward, done = self.advance(self.state, a)
+        return new, obs, _F(reward), done
+
+    def reset(self):
+        self.state = self._reset_draw(self.seed, self.env_id, self.resets)
+        self.resets += 1
+        self._t = 0
+        return self.observe(self.state), {}
+
+    def step(self, action):
+        self.state, obs, reward, done = self._advance(self._action(action))
+        self._t += 1
+        st = StepType.get_step_type(self._t, self.max_episode_length,
+                                    bool(done))
+        return StateEnvStep(action, reward, obs, {}, st)
+
+    def close(self):
+        pass
+
+
+def _cartpole_spec(max_episode_length):
+    return EnvSpec(Box(-np.inf, np.inf, (4, )), Discrete(2),
+                   max_episode_length=max_episode_length)
+
+
+class CartPoleVecEnv(_StateVecEnv):
     """``n_envs`` cart-poles (gym's ``CartPole-v1``: the same constants, Euler
     step, termination limits and reward 1 per step) stepped by one HIP kernel,
     one thread per env, inside the sampler's one-launch rollout.
@@ -648,66 +786,23 @@ class CartPoleVecEnv(_DeviceVecEnv):
     """
 
     _KIND = _lib.ENV_CARTPOLE
-    _STATE = ('_state', '_t', '_resets')
-    env_info_specs = {}
+    _STRUCT = _lib.CartPoleEnv
+    _S = 4
+    _make_spec = staticmethod(_cartpole_spec)
 
     def __init__(self, n_envs, max_episode_length=500, seed=0, env_id0=0,
                  device=None):
-        self.n_envs = int(n_envs)
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed = int(seed)
-        self.env_id0 = int(env_id0)
-        self.spec = EnvSpec(Box(-np.inf, np.inf, (4, )), Discrete(2),
-                            max_episode_length=self.max_episode_length)
-        self._init_device(device)
-
-    def _init_device(self, device):
-        device = device or require_gpu()
-        self._alloc(device)
-        n = self.n_envs
-        self._state = torch.zeros(n, 4, dtype=torch.float32, device=device)
-        self._t = torch.zeros(n, dtype=torch.int32, device=device)
-        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
-        e = _lib.CartPoleEnv()
-        e.n, e.env_id0 = n, self.env_id0
-        e.max_episode_length = self.max_episode_length
-        e.seed = self.seed
-        e.state = self._state.data_ptr()
-        e.t = self._t.data_ptr()
-        e.resets = self._resets.data_ptr()
-        self._set_struct(e)
-
-    def set_state(self, states):
-        """Every member's state <- row of ``states`` (``(n, 4)`` float32); the
-        current observations follow."""
-        states = torch.as_tensor(np.asarray(states, dtype=np.float32))
-        if tuple(states.shape) != (self.n_envs, 4):
-            raise ValueError('set_state needs an ({}, 4) array, got {}'.format(
-                self.n_envs, tuple(states.shape)))
-        self._state.copy_(states)
-        self.obs[:, :4].copy_(self._state)
-
-    def get_state(self):
-        """The ``(n, 4)`` float32 states."""
-        return self._state.cpu().numpy()
+        self._init_batch(n_envs, max_episode_length, seed, env_id0, device)
 
 
 def cartpole_reset_draw(seed, env_id, counter):
     """The ``(4,)`` float32 state reset number ``counter`` gives member
     ``env_id`` (= ``env_id0 + i``) of a :class:`CartPoleVecEnv` with this seed
     (host only, no GPU)."""
-    out = (C.c_float * 4)()
-    call('ga_cartpole_reset_draw', int(seed), int(env_id), int(counter), out)
-    return np.array(out, dtype=np.float32)
+    return _state_reset_draw('ga_cartpole_reset_draw', 4, seed, env_id, counter)
 
 
-CartPoleStep = collections.namedtuple(
-    'CartPoleStep', ['action', 'reward', 'observation', 'env_info',
-                     'step_type'])
-_F = np.float32
-
-
-class CartPoleEnv:
+class CartPoleEnv(_StateEnv):
     """One member of :class:`CartPoleVecEnv` on the host, in numpy fp32: the
     same operations in the same order (``include/garage_amd.h``) and the same
     Philox reset draws, so observations, rewards and step types equal the
@@ -721,20 +816,12 @@ class CartPoleEnv:
     X_LIMIT = _F(2.4)
     THETA_LIMIT = _F(12.0 * 2.0 * 3.141592653589793 / 360.0)
 
-    def __init__(self, seed=0, env_id=0, max_episode_length=500):
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed, self.env_id = int(seed), int(env_id)
-        self.spec = EnvSpec(Box(-np.inf, np.inf, (4, )), Discrete(2),
-                            max_episode_length=self.max_episode_length)
-        self.resets = 0
-        self.state = np.zeros(4, dtype=np.float32)
-        self._t = 0
+    _S = 4
+    _make_spec = staticmethod(_cartpole_spec)
+    _reset_draw = staticmethod(cartpole_reset_draw)
 
-    def reset(self):
-        self.state = cartpole_reset_draw(self.seed, self.env_id, self.resets)
-        self.resets += 1
-        self._t = 0
-        return self.state.copy(), {}
+    def __init__(self, seed=0, env_id=0, max_episode_length=500):
+        self._init_twin(seed, env_id, max_episode_length)
 
     @classmethod
     def advance(cls, state, push_right):
@@ -789,15 +876,13 @@ class CartPoleEnv:
                 (np.abs(new[..., 2]) > cls.THETA_LIMIT))
         return new, done
 
-    def step(self, action):
-        self.state, done = self.advance(self.state, int(action) == 1)
-        self._t += 1
-        st = StepType.get_step_type(self._t, self.max_episode_length,
-                                    bool(done))
-        return CartPoleStep(action, 1.0, self.state.copy(), {}, st)
+    @staticmethod
+    def _action(action):
+        return int(action) == 1
 
-    def close(self):
-        pass
+    def _advance(self, push_right):
+        new, done = self.advance(self.state, push_right)
+        return new, new.copy(), 1.0, done
 
 
 def _pendulum_spec(max_episode_length):
@@ -806,7 +891,7 @@ def _pendulum_spec(max_episode_length):
                    max_episode_length=max_episode_length)
 
 
-class PendulumVecEnv(_DeviceVecEnv):
+class PendulumVecEnv(_StateVecEnv):
     """``n_envs`` pendulums (gym 0.17's ``Pendulum-v0``: the same constants,
     update order, clips of torque and speed, cost and reset ranges) stepped by
     one HIP kernel, one thread per env, inside the sampler's one-launch rollout.
@@ -839,65 +924,28 @@ class PendulumVecEnv(_DeviceVecEnv):
     """
 
     _KIND = _lib.ENV_PENDULUM
-    _STATE = ('_state', '_t', '_resets')
-    env_info_specs = {}
+    _STRUCT = _lib.PendulumEnv
+    _S = 2
+    _make_spec = staticmethod(_pendulum_spec)
 
     def __init__(self, n_envs, max_episode_length=200, seed=0, env_id0=0,
                  device=None):
-        self.n_envs = int(n_envs)
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed = int(seed)
-        self.env_id0 = int(env_id0)
-        self.spec = _pendulum_spec(self.max_episode_length)
-        self._init_device(device)
+        self._init_batch(n_envs, max_episode_length, seed, env_id0, device)
 
-    def _init_device(self, device):
-        device = device or require_gpu()
-        self._alloc(device)
-        n = self.n_envs
-        self._state = torch.zeros(n, 2, dtype=torch.float32, device=device)
-        self._t = torch.zeros(n, dtype=torch.int32, device=device)
-        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
-        e = _lib.PendulumEnv()
-        e.n, e.env_id0 = n, self.env_id0
-        e.max_episode_length = self.max_episode_length
-        e.seed = self.seed
-        e.state = self._state.data_ptr()
-        e.t = self._t.data_ptr()
-        e.resets = self._resets.data_ptr()
-        self._set_struct(e)
-
-    def set_state(self, states):
-        """Every member's ``(th, thdot)`` <- row of ``states`` (``(n, 2)``
-        float32, ``|th| <= PI``); the current observations follow."""
-        states = np.asarray(states, dtype=np.float32)
-        if states.shape != (self.n_envs, 2):
-            raise ValueError('set_state needs an ({}, 2) array, got {}'.format(
-                self.n_envs, states.shape))
+    def _check_states(self, states):
+        """``(th, thdot)`` rows with ``|th| <= PI``."""
         if not (np.abs(states[:, 0]) <= PendulumEnv.PI).all():
             raise ValueError('set_state needs angles in [-PI, PI]')
-        sn, cs = PendulumEnv.sincos(states[:, 0])
-        obs = np.stack([cs, sn, states[:, 1]], axis=-1).astype(np.float32)
-        self._state.copy_(torch.from_numpy(states))
-        self.obs[:, :3].copy_(torch.from_numpy(obs))
 
-    def get_state(self):
-        """The ``(n, 2)`` float32 states ``(th, thdot)``."""
-        return self._state.cpu().numpy()
+    def _observe(self, states):
+        return PendulumEnv.observe(states)
 
 
 def pendulum_reset_draw(seed, env_id, counter):
     """The ``(2,)`` float32 state ``(th, thdot)`` reset number ``counter`` gives
     member ``env_id`` (= ``env_id0 + i``) of a :class:`PendulumVecEnv` with this
     seed (host only, no GPU)."""
-    out = (C.c_float * 2)()
-    call('ga_pendulum_reset_draw', int(seed), int(env_id), int(counter), out)
-    return np.array(out, dtype=np.float32)
-
-
-PendulumStep = collections.namedtuple(
-    'PendulumStep', ['action', 'reward', 'observation', 'env_info',
-                     'step_type'])
+    return _state_reset_draw('ga_pendulum_reset_draw', 2, seed, env_id, counter)
 
 
 def _fact(k):
@@ -907,7 +955,7 @@ def _fact(k):
     return out
 
 
-class PendulumEnv:
+class PendulumEnv(_StateEnv):
     """One member of :class:`PendulumVecEnv` on the host, in numpy fp32: the
     same operations in the same order (``include/garage_amd.h``) and the same
     Philox reset draws, so observations, rewards and step types equal the
@@ -922,13 +970,12 @@ class PendulumEnv:
     S = tuple(_F((-1.0)**(j + 1) / _fact(2 * j + 3)) for j in range(6))
     C = tuple(_F((-1.0)**(j + 1) / _fact(2 * j + 2)) for j in range(7))
 
+    _S = 2
+    _make_spec = staticmethod(_pendulum_spec)
+    _reset_draw = staticmethod(pendulum_reset_draw)
+
     def __init__(self, seed=0, env_id=0, max_episode_length=200):
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed, self.env_id = int(seed), int(env_id)
-        self.spec = _pendulum_spec(self.max_episode_length)
-        self.resets = 0
-        self.state = np.zeros(2, dtype=np.float32)
-        self._t = 0
+        self._init_twin(seed, env_id, max_episode_length)
 
     @classmethod
     def sincos(cls, th):
@@ -997,25 +1044,17 @@ class PendulumEnv:
         obs = np.stack([cs2, sn2, nthd], axis=-1).astype(np.float32)
         return new, obs, (-cost).astype(np.float32)
 
-    def _obs(self):
-        sn, cs = self.sincos(self.state[0])
-        return np.array([cs, sn, self.state[1]], dtype=np.float32)
+    @classmethod
+    def observe(cls, state):
+        """The ``(..., 3)`` observations of ``state`` (``(..., 2)``, angles in
+        ``[-PI, PI]``)."""
+        state = np.asarray(state, dtype=np.float32)
+        sn, cs = cls.sincos(state[..., 0])
+        return np.stack([cs, sn, state[..., 1]], axis=-1).astype(np.float32)
 
-    def reset(self):
-        self.state = pendulum_reset_draw(self.seed, self.env_id, self.resets)
-        self.resets += 1
-        self._t = 0
-        return self._obs(), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
-        self.state, obs, reward = self.advance(self.state, a)
-        self._t += 1
-        st = StepType.get_step_type(self._t, self.max_episode_length, False)
-        return PendulumStep(action, _F(reward), obs, {}, st)
-
-    def close(self):
-        pass
+    def _advance(self, a):
+        new, obs, reward = self.advance(self.state, a)
+        return new, obs, _F(reward), False  # an episode never terminates
 
 
 def _double_pendulum_spec(max_episode_length):
@@ -1023,7 +1062,7 @@ def _double_pendulum_spec(max_episode_length):
                    max_episode_length=max_episode_length)
 
 
-class DoublePendulumVecEnv(_DeviceVecEnv):
+class DoublePendulumVecEnv(_StateVecEnv):
     """``n_envs`` inverted double pendulums on a cart (the task of gym's
     ``InvertedDoublePendulum-v2``: the same bodies, action scale, frame skip,
     reward, termination and observation layout) stepped by one HIP kernel, one
@@ -1057,72 +1096,36 @@ class DoublePendulumVecEnv(_DeviceVecEnv):
     """
 
     _KIND = _lib.ENV_DOUBLE_PENDULUM
-    _STATE = ('_state', '_t', '_resets')
-    env_info_specs = {}
+    _STRUCT = _lib.DoublePendulumEnv
+    _S = 6
+    _make_spec = staticmethod(_double_pendulum_spec)
 
     def __init__(self, n_envs, max_episode_length=1000, seed=0, env_id0=0,
                  device=None):
-        self.n_envs = int(n_envs)
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed = int(seed)
-        self.env_id0 = int(env_id0)
-        self.spec = _double_pendulum_spec(self.max_episode_length)
-        self._init_device(device)
+        self._init_batch(n_envs, max_episode_length, seed, env_id0, device)
 
-    def _init_device(self, device):
-        device = device or require_gpu()
-        self._alloc(device)
-        n = self.n_envs
-        self._state = torch.zeros(n, 6, dtype=torch.float32, device=device)
-        self._t = torch.zeros(n, dtype=torch.int32, device=device)
-        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
-        e = _lib.DoublePendulumEnv()
-        e.n, e.env_id0 = n, self.env_id0
-        e.max_episode_length = self.max_episode_length
-        e.seed = self.seed
-        e.state = self._state.data_ptr()
-        e.t = self._t.data_ptr()
-        e.resets = self._resets.data_ptr()
-        self._set_struct(e)
-
-    def set_state(self, states):
-        """Every member's state <- row of ``states`` (``(n, 6)`` float32,
-        ``|th1|, |th2| <= PI``); the current observations follow."""
-        states = np.asarray(states, dtype=np.float32)
-        if states.shape != (self.n_envs, 6):
-            raise ValueError('set_state needs an ({}, 6) array, got {}'.format(
-                self.n_envs, states.shape))
+    def _check_states(self, states):
+        """Rows with ``|th1|, |th2| <= PI``."""
         if not (np.abs(states[:, 1:3]) <= PendulumEnv.PI).all():
             raise ValueError('set_state needs angles in [-PI, PI]')
-        self._state.copy_(torch.from_numpy(states))
-        self.obs[:, :11].copy_(
-            torch.from_numpy(DoublePendulumEnv.observe(states)))
 
-    def get_state(self):
-        """The ``(n, 6)`` float32 states."""
-        return self._state.cpu().numpy()
+    def _observe(self, states):
+        return DoublePendulumEnv.observe(states)
 
 
 def double_pendulum_reset_draw(seed, env_id, counter):
     """The ``(6,)`` float32 state reset number ``counter`` gives member
     ``env_id`` (= ``env_id0 + i``) of a :class:`DoublePendulumVecEnv` with this
     seed (host only, no GPU)."""
-    out = (C.c_float * 6)()
-    call('ga_double_pendulum_reset_draw', int(seed), int(env_id), int(counter),
-         out)
-    return np.array(out, dtype=np.float32)
-
-
-DoublePendulumStep = collections.namedtuple(
-    'DoublePendulumStep', ['action', 'reward', 'observation', 'env_info',
-                           'step_type'])
+    return _state_reset_draw('ga_double_pendulum_reset_draw', 6, seed, env_id,
+                             counter)
 
 
 def _clip32(v, b):
     return np.where(v < -b, -b, np.where(v > b, b, v)).astype(np.float32)
 
 
-class DoublePendulumEnv:
+class DoublePendulumEnv(_StateEnv):
     """One member of :class:`DoublePendulumVecEnv` on the host, in numpy fp32:
     the same operations in the same order (``include/garage_amd.h``) and the
     same Philox reset draws, so observations, rewards and step types equal the
@@ -1141,13 +1144,12 @@ class DoublePendulumEnv:
     F2 = _F(M2 * L * G / 2.0)
     H, VMAX, SUBSTEPS = _F(0.01), _F(100.0), 5
 
+    _S = 6
+    _make_spec = staticmethod(_double_pendulum_spec)
+    _reset_draw = staticmethod(double_pendulum_reset_draw)
+
     def __init__(self, seed=0, env_id=0, max_episode_length=1000):
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed, self.env_id = int(seed), int(env_id)
-        self.spec = _double_pendulum_spec(self.max_episode_length)
-        self.resets = 0
-        self.state = np.zeros(6, dtype=np.float32)
-        self._t = 0
+        self._init_twin(seed, env_id, max_episode_length)
 
     @staticmethod
     def _wrap(th):
@@ -1294,24 +1296,6 @@ class DoublePendulumEnv:
         obs = cls._observe(new, s1, c1, sd, cd)
         return new, obs, reward, yt <= _F(1.0)
 
-    def reset(self):
-        self.state = double_pendulum_reset_draw(self.seed, self.env_id,
-                                                self.resets)
-        self.resets += 1
-        self._t = 0
-        return self.observe(self.state), {}
-
-    def step(self, action):
-        a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
-        self.state, obs, reward, done = self.advance(self.state, a)
-        self._t += 1
-        st = StepType.get_step_type(self._t, self.max_episode_length,
-                                    bool(done))
-        return DoublePendulumStep(action, _F(reward), obs, {}, st)
-
-    def close(self):
-        pass
-
 
 def _acrobot_spec(max_episode_length):
     high = np.array([1.0, 1.0, 1.0, 1.0, AcrobotEnv.MAX_VEL_1,
@@ -1320,7 +1304,7 @@ def _acrobot_spec(max_episode_length):
                    max_episode_length=max_episode_length)
 
 
-class AcrobotVecEnv(_DeviceVecEnv):
+class AcrobotVecEnv(_StateVecEnv):
     """``n_envs`` acrobots (gym 0.17's ``Acrobot-v1``: the "book" dynamics, no
     torque noise, one classical RK4 step of 0.2 s, the same speed bounds,
     reward and goal) stepped by one HIP kernel, one thread per env, inside the
@@ -1352,70 +1336,36 @@ class AcrobotVecEnv(_DeviceVecEnv):
     """
 
     _KIND = _lib.ENV_ACROBOT
-    _STATE = ('_state', '_t', '_resets')
-    env_info_specs = {}
+    _STRUCT = _lib.AcrobotEnv
+    _S = 4
+
+    _make_spec = staticmethod(_acrobot_spec)
 
     def __init__(self, n_envs, max_episode_length=500, seed=0, env_id0=0,
                  device=None):
-        self.n_envs = int(n_envs)
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed = int(seed)
-        self.env_id0 = int(env_id0)
-        self.spec = _acrobot_spec(self.max_episode_length)
-        self._init_device(device)
+        self._init_batch(n_envs, max_episode_length, seed, env_id0, device)
 
-    def _init_device(self, device):
-        device = device or require_gpu()
-        self._alloc(device)
-        n = self.n_envs
-        self._state = torch.zeros(n, 4, dtype=torch.float32, device=device)
-        self._t = torch.zeros(n, dtype=torch.int32, device=device)
-        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
-        e = _lib.AcrobotEnv()
-        e.n, e.env_id0 = n, self.env_id0
-        e.max_episode_length = self.max_episode_length
-        e.seed = self.seed
-        e.state = self._state.data_ptr()
-        e.t = self._t.data_ptr()
-        e.resets = self._resets.data_ptr()
-        self._set_struct(e)
-
-    def set_state(self, states):
-        """Every member's state <- row of ``states`` (``(n, 4)`` float32,
-        angles in ``[-PI, PI]``, speeds inside their clips); the current
-        observations follow."""
-        states = np.asarray(states, dtype=np.float32)
-        if states.shape != (self.n_envs, 4):
-            raise ValueError('set_state needs an ({}, 4) array, got {}'.format(
-                self.n_envs, states.shape))
+    def _check_states(self, states):
+        """Rows with the angles in ``[-PI, PI]`` and the speeds inside their
+        clips."""
         if not (np.abs(states[:, :2]) <= AcrobotEnv.PI).all():
             raise ValueError('set_state needs angles in [-PI, PI]')
         if not ((np.abs(states[:, 2]) <= AcrobotEnv.MAX_VEL_1).all() and
                 (np.abs(states[:, 3]) <= AcrobotEnv.MAX_VEL_2).all()):
             raise ValueError('set_state needs speeds within 4 pi and 9 pi')
-        self._state.copy_(torch.from_numpy(states))
-        self.obs[:, :6].copy_(torch.from_numpy(AcrobotEnv.observe(states)))
 
-    def get_state(self):
-        """The ``(n, 4)`` float32 states."""
-        return self._state.cpu().numpy()
+    def _observe(self, states):
+        return AcrobotEnv.observe(states)
 
 
 def acrobot_reset_draw(seed, env_id, counter):
     """The ``(4,)`` float32 state reset number ``counter`` gives member
     ``env_id`` (= ``env_id0 + i``) of an :class:`AcrobotVecEnv` with this seed
     (host only, no GPU)."""
-    out = (C.c_float * 4)()
-    call('ga_acrobot_reset_draw', int(seed), int(env_id), int(counter), out)
-    return np.array(out, dtype=np.float32)
+    return _state_reset_draw('ga_acrobot_reset_draw', 4, seed, env_id, counter)
 
 
-AcrobotStep = collections.namedtuple(
-    'AcrobotStep', ['action', 'reward', 'observation', 'env_info',
-                    'step_type'])
-
-
-class AcrobotEnv:
+class AcrobotEnv(_StateEnv):
     """One member of :class:`AcrobotVecEnv` on the host, in numpy fp32: the
     same operations in the same order (``include/garage_amd.h``) and the same
     Philox reset draws, so observations, rewards and step types equal the
@@ -1432,13 +1382,12 @@ class AcrobotEnv:
     MAX_VEL_2 = _F(9.0 * 3.141592653589793)
     H, H2, H6 = _F(0.2), _F(0.1), _F(0.2 / 6.0)
 
+    _S = 4
+    _make_spec = staticmethod(_acrobot_spec)
+    _reset_draw = staticmethod(acrobot_reset_draw)
+
     def __init__(self, seed=0, env_id=0, max_episode_length=500):
-        self.max_episode_length = _check_finite_length(max_episode_length)
-        self.seed, self.env_id = int(seed), int(env_id)
-        self.spec = _acrobot_spec(self.max_episode_length)
-        self.resets = 0
-        self.state = np.zeros(4, dtype=np.float32)
-        self._t = 0
+        self._init_twin(seed, env_id, max_episode_length)
 
     @classmethod
     def reduce(cls, th):
@@ -1567,22 +1516,9 @@ class AcrobotEnv:
         obs = np.stack([c1, s1, c2, s2, nw1, nw2], axis=-1).astype(np.float32)
         return new, obs, reward, done
 
-    def reset(self):
-        self.state = acrobot_reset_draw(self.seed, self.env_id, self.resets)
-        self.resets += 1
-        self._t = 0
-        return self.observe(self.state), {}
-
-    def step(self, action):
-        a = int(np.asarray(action).reshape(-1)[0])
-        self.state, obs, reward, done = self.advance(self.state, a)
-        self._t += 1
-        st = StepType.get_step_type(self._t, self.max_episode_length,
-                                    bool(done))
-        return AcrobotStep(action, _F(reward), obs, {}, st)
-
-    def close(self):
-        pass
+    @staticmethod
+    def _action(action):
+        return int(np.asarray(action).reshape(-1)[0])
 
 
 def _mountain_car_spec(continuous, max_episode_length):
@@ -1598,7 +1534,7 @@ def _mountain_car_length(continuous, max_episode_length):
     return _check_finite_length(max_episode_length)
 
 
-class MountainCarVecEnv(_DeviceVecEnv):
+class MountainCarVecEnv(_StateVecEnv):
     """``n_envs`` mountain cars (gym 0.17's ``MountainCar-v0``, or with
     ``continuous=True`` its ``MountainCarContinuous-v0``: the same constants,
     update order, clips, wall, goals and rewards) stepped by one HIP kernel,
@@ -1627,73 +1563,38 @@ class MountainCarVecEnv(_DeviceVecEnv):
     """
 
     _KIND = _lib.ENV_MOUNTAIN_CAR
-    _STATE = ('_state', '_t', '_resets')
-    env_info_specs = {}
+    _S = 2
 
     def __init__(self, n_envs, continuous=False, max_episode_length=None,
                  seed=0, env_id0=0, device=None):
-        self.n_envs = int(n_envs)
         self.continuous = bool(continuous)
-        self.max_episode_length = _mountain_car_length(self.continuous,
-                                                       max_episode_length)
-        self.seed = int(seed)
-        self.env_id0 = int(env_id0)
-        self.spec = _mountain_car_spec(self.continuous,
-                                       self.max_episode_length)
-        self._init_device(device)
+        self._init_batch(
+            n_envs, _mountain_car_length(self.continuous, max_episode_length),
+            seed, env_id0, device)
 
-    def _init_device(self, device):
-        device = device or require_gpu()
-        self._alloc(device)
-        n = self.n_envs
-        self._state = torch.zeros(n, 2, dtype=torch.float32, device=device)
-        self._t = torch.zeros(n, dtype=torch.int32, device=device)
-        self._resets = torch.zeros(n, dtype=torch.int32, device=device)
-        e = _lib.MountainCarEnv()
-        e.n, e.env_id0 = n, self.env_id0
-        e.max_episode_length = self.max_episode_length
-        e.continuous = int(self.continuous)
-        e.seed = self.seed
-        e.state = self._state.data_ptr()
-        e.t = self._t.data_ptr()
-        e.resets = self._resets.data_ptr()
-        self._set_struct(e)
+    def _make_spec(self, max_episode_length):
+        return _mountain_car_spec(self.continuous, max_episode_length)
 
-    def set_state(self, states):
-        """Every member's ``(x, v)`` <- row of ``states`` (``(n, 2)`` float32
-        inside the observation ``Box``); the current observations follow."""
-        states = np.asarray(states, dtype=np.float32)
-        if states.shape != (self.n_envs, 2):
-            raise ValueError('set_state needs an ({}, 2) array, got {}'.format(
-                self.n_envs, states.shape))
+    def _new_struct(self):
+        return _lib.MountainCarEnv(continuous=int(self.continuous))
+
+    def _check_states(self, states):
+        """``(x, v)`` rows inside the observation ``Box``."""
         box = self.spec.observation_space
         if not ((states >= box.low).all() and (states <= box.high).all()):
             raise ValueError('set_state needs x in [-1.2, 0.6] and v in '
                              '[-0.07, 0.07]')
-        self._state.copy_(torch.from_numpy(states))
-        self.obs[:, :2].copy_(self._state)
-
-    def get_state(self):
-        """The ``(n, 2)`` float32 states ``(x, v)``."""
-        return self._state.cpu().numpy()
 
 
 def mountain_car_reset_draw(seed, env_id, counter):
     """The ``(2,)`` float32 state ``(x, 0)`` reset number ``counter`` gives
     member ``env_id`` (= ``env_id0 + i``) of a :class:`MountainCarVecEnv` with
     this seed, either variant (host only, no GPU)."""
-    out = (C.c_float * 2)()
-    call('ga_mountain_car_reset_draw', int(seed), int(env_id), int(counter),
-         out)
-    return np.array(out, dtype=np.float32)
+    return _state_reset_draw('ga_mountain_car_reset_draw', 2, seed, env_id,
+                             counter)
 
 
-MountainCarStep = collections.namedtuple(
-    'MountainCarStep', ['action', 'reward', 'observation', 'env_info',
-                        'step_type'])
-
-
-class MountainCarEnv:
+class MountainCarEnv(_StateEnv):
     """One member of :class:`MountainCarVecEnv` on the host, in numpy fp32:
     the same operations in the same order (``include/garage_amd.h``) and the
     same Philox reset draws, so observations, rewards and step types equal the
@@ -1703,18 +1604,18 @@ class MountainCarEnv:
 
     MIN_X, MAX_X, MAX_V = _F(-1.2), _F(0.6), _F(0.07)
     GOAL, GOAL_CONTINUOUS = _F(0.5), _F(0.45)
+    _S = 2
+    _reset_draw = staticmethod(mountain_car_reset_draw)
 
     def __init__(self, seed=0, env_id=0, continuous=False,
                  max_episode_length=None):
         self.continuous = bool(continuous)
-        self.max_episode_length = _mountain_car_length(self.continuous,
-                                                       max_episode_length)
-        self.seed, self.env_id = int(seed), int(env_id)
-        self.spec = _mountain_car_spec(self.continuous,
-                                       self.max_episode_length)
-        self.resets = 0
-        self.state = np.zeros(2, dtype=np.float32)
-        self._t = 0
+        self._init_twin(
+            seed, env_id,
+            _mountain_car_length(self.continuous, max_episode_length))
+
+    def _make_spec(self, max_episode_length):
+        return _mountain_car_spec(self.continuous, max_episode_length)
 
     @classmethod
     def advance(cls, state, action, continuous=False):
@@ -1764,27 +1665,14 @@ class MountainCarEnv:
         new = np.stack([nx, nv], axis=-1).astype(np.float32)
         return new, new.copy(), reward, done
 
-    def reset(self):
-        self.state = mountain_car_reset_draw(self.seed, self.env_id,
-                                             self.resets)
-        self.resets += 1
-        self._t = 0
-        return self.state.copy(), {}
-
-    def step(self, action):
+    def _action(self, action):
         if self.continuous:
-            a = np.asarray(action, dtype=np.float32).reshape(-1)[0]
-        else:
-            a = int(np.asarray(action).reshape(-1)[0])
-        self.state, obs, reward, done = self.advance(self.state, a,
-                                                     self.continuous)
-        self._t += 1
-        st = StepType.get_step_type(self._t, self.max_episode_length,
-                                    bool(done))
-        return MountainCarStep(action, _F(reward), obs, {}, st)
+            return _StateEnv._action(action)
+        return int(np.asarray(action).reshape(-1)[0])
 
-    def close(self):
-        pass
+    def _advance(self, a):
+        new, obs, reward, done = self.advance(self.state, a, self.continuous)
+        return new, obs, _F(reward), done
 
 
 class NormalizedVecEnv(VecEnv):
