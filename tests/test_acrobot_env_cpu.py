@@ -3,10 +3,11 @@
 against a float64 restatement of gym 0.17's equations (the "book" dynamics with
 ``np.sin`` / ``np.cos``, one true RK4 step of 0.2, ``((x + pi) mod 2 pi) - pi``
 and the speed bounds), the range of the RK4 stage angles and the reduction that
-is trusted on it, the exact invariants of the state, the Philox reset draws
-against a pure-Python Philox4x32-10, episode semantics, the ctypes mirror of
-``ga_acrobot_env`` against the header and the argument errors of the entry
-points.
+is trusted on it, the exact invariants of the state and episode semantics.
+
+What every kind states the same way (reset draws against a
+pure-Python Philox, the ctypes mirror of its struct, the argument errors of the
+entry points) is in ``test_state_envs_cpu.py``, row ``acrobot``.
 
 The bounds on |twin - float64| are 4x the worst error measured when the
 arithmetic was fixed (the restatement is the yardstick; the factor leaves room
@@ -20,15 +21,9 @@ worst case over the whole state box is far above the typical one.  Measured
                                     2.1e-7 / 4.0e-7
   reduce + sincos over |th| <= 34 (sin / cos)       2.2e-7 / 2.5e-7
   largest |stage angle| over the box and the torques, float64: 33.32"""
-import ctypes
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PI = np.pi
 BOX = np.array([PI, PI, 4 * PI, 9 * PI])
 
@@ -295,61 +290,6 @@ def test_restatement_swings_up_under_a_pumping_torque():
     assert ended[1] is not None and ended[1] < 200
 
 
-def philox4x32_10(c, k):
-    """Philox4x32-10 (Salmon et al., SC'11) on Python integers."""
-    c0, c1, c2, c3 = c
-    k0, k1 = k
-    m32 = 0xffffffff
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & m32,
-                          (p0 >> 32) ^ c3 ^ k1, p0 & m32)
-        k0, k1 = (k0 + 0x9E3779B9) & m32, (k1 + 0xBB67AE85) & m32
-    return c0, c1, c2, c3
-
-
-STREAM = 8
-
-
-def reset_draw_py(seed, env_id, counter):
-    f = np.float32
-    key = (seed & 0xffffffff, seed >> 32)
-    w = philox4x32_10((env_id & 0xffffffff, counter, 0, STREAM << 16), key)
-    out = []
-    for j in range(4):
-        u = (f(w[j] >> 8) + f(0.5)) * f(2.0**-24)
-        out.append(f(-0.1) + f(0.2) * u)
-    return np.asarray(out, dtype=np.float32)
-
-
-def test_reset_draws_equal_a_pure_python_philox():
-    from garage_amd.envs import AcrobotEnv, acrobot_reset_draw
-    draws = {}
-    for seed in (0, (7 << 32) | 11):
-        for env_id in (0, 1, 1 << 31):
-            for counter in (0, 1, (1 << 32) - 1):
-                got = acrobot_reset_draw(seed, env_id, counter)
-                want = reset_draw_py(seed, env_id, counter)
-                assert got.dtype == np.float32 and got.shape == (4, )
-                assert got.tobytes() == want.tobytes(), (seed, env_id, counter)
-                assert (np.abs(got) <= np.float32(0.1)).all()
-                draws[(seed, env_id, counter)] = got.tobytes()
-    assert len(set(draws.values())) == len(draws) == 18
-    assert len(set(reset_draw_py(0, 0, 0).tolist())) == 4
-    # the key's high word counts
-    assert acrobot_reset_draw(11, 1, 1).tobytes() != draws[
-        ((7 << 32) | 11, 1, 1)]
-    # the twin starts its episodes there, and the counter advances
-    for i in (0, 3, 69):
-        env = AcrobotEnv(seed=5, env_id=37 + i)
-        first, info = env.reset()
-        assert info == {} and first.dtype == np.float32
-        assert np.array_equal(env.state, acrobot_reset_draw(5, 37 + i, 0))
-        assert first.tobytes() == AcrobotEnv.observe(env.state).tobytes()
-        env.reset()
-        assert np.array_equal(env.state, acrobot_reset_draw(5, 37 + i, 1))
-
-
 def _goal_state():
     """A state whose next step under class 2 swings the tip over the line
     (found on the twin: an arm pointing almost straight up, moving up)."""
@@ -415,118 +355,3 @@ def test_twin_episode_semantics():
     env.state = goal.copy()
     assert env.step(2).step_type == StepType.TERMINAL
     assert env.resets == 2
-
-
-def _layout_lines(cname, py, kind_macro):
-    lines = ['#include <stddef.h>', '#include <stdio.h>',
-             '#include "garage_amd.h"', 'int main(void) {',
-             'printf("%d\\n", {});'.format(kind_macro),
-             'printf("{0} %zu\\n", sizeof({0}));'.format(cname)]
-    want = ['{} {}'.format(cname, ctypes.sizeof(py))]
-    for field, ftype in py._fields_:
-        lines.append('printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), '
-                     'sizeof((({0}*)0)->{1}));'.format(cname, field))
-        want.append('{}.{} {} {}'.format(cname, field,
-                                         getattr(py, field).offset,
-                                         ctypes.sizeof(ftype)))
-    lines += ['return 0;', '}']
-    return lines, want
-
-
-def test_acrobot_ctypes_struct_matches_the_header():
-    from garage_amd import _lib
-    lines, want = _layout_lines('ga_acrobot_env', _lib.AcrobotEnv,
-                                'GA_ENV_ACROBOT')
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'layout.c'), os.path.join(tmp, 'layout')
-        with open(src, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-        subprocess.run(['cc', '-std=c99', '-Wall', '-Werror', '-I',
-                        os.path.join(ROOT, 'include'), src, '-o', exe],
-                       check=True)
-        got = subprocess.run([exe], capture_output=True, text=True,
-                             check=True).stdout.split('\n')[:-1]
-    assert got == ['{}'.format(_lib.ENV_ACROBOT)] + want
-    # 7 and 9 stay kinds that are refused as unknown (the tests of the earlier
-    # kinds rely on it), so the two kinds after the double pendulum are 8, 10
-    assert _lib.ENV_ACROBOT == 8
-    assert _lib.load().ga_abi_version() == 5
-
-
-def test_acrobot_argument_errors_without_a_gpu():
-    from garage_amd import _lib
-    from garage_amd.envs import AcrobotEnv, AcrobotVecEnv
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-
-    def env(kind=_lib.ENV_ACROBOT, **kw):
-        e = _lib.AcrobotEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                            resets=addr)
-        for k, v in kw.items():
-            setattr(e, k, v)
-        return C.byref(_lib.env_ref(kind, e))
-
-    def reset(e, ldo=8):
-        _lib.call('ga_env_reset', e, None, addr, ldo, None)
-
-    def step(e, ldo=8):
-        _lib.call('ga_env_step', e, addr, 1, None, addr, ldo, addr, addr, None)
-
-    def record(e, ldo=8):
-        rec = _lib.RecordArgs(n=4, col=0, Tcap=8, max_episode_length=5,
-                              reward=addr, step_type=addr, next_obs=addr,
-                              ldo=ldo, obs_dim=6, ep_t=addr, rew_buf=addr,
-                              st_buf=addr, tail_buf=addr, lastobs_buf=addr,
-                              done=addr, step_eps=addr, step_samples=addr)
-        _lib.call('ga_env_step_record', e, C.byref(rec), None, addr, 1, addr,
-                  None)
-
-    for fn in (reset, step, record):
-        for field in ('state', 't', 'resets'):
-            with pytest.raises(_lib.GarageAmdError, match='null env state'):
-                fn(env(**{field: None}))
-        for bad in (0, 65536):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='max_episode_length'):
-                fn(env(max_episode_length=bad))
-        with pytest.raises(_lib.GarageAmdError, match='bad env size'):
-            fn(env(n=0))
-        for unknown in (7, 9, 11):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='unknown env kind {}'.format(unknown)):
-                fn(env(kind=unknown))
-    # observation rows narrower than 6
-    with pytest.raises(_lib.GarageAmdError, match='bad obs buffer'):
-        reset(env(), ldo=5)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        step(env(), ldo=5)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        record(env(), ldo=5)
-    with pytest.raises(_lib.GarageAmdError, match='null pointer'):
-        _lib.call('ga_acrobot_reset_draw', 0, 0, 0, None)
-    for bad in (None, float('inf'), 0, 65536):
-        with pytest.raises(ValueError):
-            AcrobotVecEnv(4, max_episode_length=bad)
-        with pytest.raises(ValueError):
-            AcrobotEnv(max_episode_length=bad)
-
-
-def test_rollout_env_steps_takes_the_acrobot_kind_as_discrete():
-    """With rescale arguments the kind fails the "continuous action space"
-    check, before any device call."""
-    from garage_amd import _lib
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-    desc = _lib.MlpDesc()
-    head = _lib.HeadArgs(col=0, Tcap=4)
-    rec = _lib.RecordArgs()
-    norm = _lib.NormArgs(act_low=addr, act_high=addr, scaled_action=addr,
-                         expected_action_scale=1.0, reward_scale=1.0)
-    acro = _lib.AcrobotEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                           resets=addr)
-    with pytest.raises(_lib.GarageAmdError, match='continuous action space'):
-        _lib.call('ga_rollout_env_steps', C.byref(desc), addr, C.byref(head),
-                  C.byref(_lib.env_ref(_lib.ENV_ACROBOT, acro)),
-                  C.byref(rec), addr, addr, C.byref(norm), None, None, 5, None)

@@ -2,10 +2,11 @@
 no GPU: the fp32 twin (``garage_amd.envs.DoublePendulumEnv``, the arithmetic
 ``include/garage_amd.h`` fixes) against a float64 restatement of the same scheme
 (same substeps, clips and wraps; ``np.sin``, ``np.cos``, ``np.linalg.solve``),
-the physics of that restatement, the Philox reset draws against a pure-Python
-Philox4x32-10, episode semantics, the ctypes mirror of
-``ga_double_pendulum_env`` against the header and the argument errors of the
-entry points.
+the physics of that restatement and episode semantics.
+
+What every kind states the same way (reset draws against a
+pure-Python Philox, the ctypes mirror of its struct, the argument errors of the
+entry points) is in ``test_state_envs_cpu.py``, row ``double_pendulum``.
 
 The bounds on |twin - float64| are 4x the worst error measured when the
 arithmetic was fixed (the restatement is the yardstick; the factor covers states
@@ -14,15 +15,8 @@ constant).  Measured, observation / reward:
   one step from 4096 reset states, zero action    3.7e-7 / 1.2e-6
   five steps from them                            2.1e-6 / 1.2e-6
   one step from the grid of 225 000 states        1.6e-5 / 9.8e-6"""
-import ctypes
-import os
-import subprocess
-import tempfile
-
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 M0, M1, M2, L1, L2, G = 10.5, 4.2, 4.2, 0.6, 0.6, 9.81
 D1 = M0 + M1 + M2
@@ -93,71 +87,6 @@ def energy(state):
     d = mass_matrix(state[..., 1], state[..., 2])
     return (0.5 * np.einsum('...i,...ij,...j', v, d, v) +
             F1 * np.cos(state[..., 1]) + F2 * np.cos(state[..., 2]))
-
-
-def philox4x32_10(c, k):
-    """Philox4x32-10 (Salmon et al., SC'11) on Python integers."""
-    c0, c1, c2, c3 = c
-    k0, k1 = k
-    m32 = 0xffffffff
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & m32,
-                          (p0 >> 32) ^ c3 ^ k1, p0 & m32)
-        k0, k1 = (k0 + 0x9E3779B9) & m32, (k1 + 0xBB67AE85) & m32
-    return c0, c1, c2, c3
-
-
-STREAM = 7
-
-
-def reset_draw_py(seed, env_id, counter):
-    f = np.float32
-    key = (seed & 0xffffffff, seed >> 32)
-    w = (philox4x32_10((env_id & 0xffffffff, counter, 0, STREAM << 16), key) +
-         philox4x32_10((env_id & 0xffffffff, counter, 1, STREAM << 16), key))
-    out = []
-    for j in range(6):
-        u = (f(w[j] >> 8) + f(0.5)) * f(2.0**-24)
-        out.append(f(-0.1) + f(0.2) * u)
-    return np.asarray(out, dtype=np.float32)
-
-
-def test_reset_draws_equal_a_pure_python_philox():
-    from garage_amd.envs import DoublePendulumEnv, double_pendulum_reset_draw
-    draws = {}
-    for seed in (0, (7 << 32) | 11):
-        for env_id in (0, 1, 1 << 31):
-            for counter in (0, 1, (1 << 32) - 1):
-                got = double_pendulum_reset_draw(seed, env_id, counter)
-                want = reset_draw_py(seed, env_id, counter)
-                assert got.dtype == np.float32 and got.shape == (6, )
-                assert got.tobytes() == want.tobytes(), (seed, env_id, counter)
-                assert (np.abs(got) <= np.float32(0.1)).all()
-                draws[(seed, env_id, counter)] = got.tobytes()
-    # another seed, env id or counter: another state; six distinct words
-    assert len(set(draws.values())) == len(draws) == 18
-    assert len(set(reset_draw_py(0, 0, 0).tolist())) == 6
-    # the key's high word counts
-    assert double_pendulum_reset_draw(11, 1, 1).tobytes() != draws[
-        ((7 << 32) | 11, 1, 1)]
-    # the constants are the issue's, each rounded once
-    for got, want in zip((DoublePendulumEnv.D1, DoublePendulumEnv.D2,
-                          DoublePendulumEnv.D3, DoublePendulumEnv.D4,
-                          DoublePendulumEnv.D5, DoublePendulumEnv.D6,
-                          DoublePendulumEnv.F1, DoublePendulumEnv.F2),
-                         (18.9, 3.78, 1.26, 2.016, 0.756, 0.504, 37.0818,
-                          12.3606)):
-        assert got == np.float32(want) and isinstance(got, np.float32)
-    # the twin starts its episodes there, and the counter advances
-    for i in (0, 3, 69):
-        env = DoublePendulumEnv(seed=5, env_id=37 + i)
-        first, info = env.reset()
-        assert info == {} and first.dtype == np.float32
-        assert np.array_equal(env.state, double_pendulum_reset_draw(5, 37 + i, 0))
-        assert first.tobytes() == DoublePendulumEnv.observe(env.state).tobytes()
-        env.reset()
-        assert np.array_equal(env.state, double_pendulum_reset_draw(5, 37 + i, 1))
 
 
 def _reset_states(m, seed=4):
@@ -348,112 +277,3 @@ def test_twin_episode_semantics():
     env.state = fallen.copy()
     assert env.step(zero).step_type == StepType.TERMINAL
     assert env.resets == 2
-
-
-def test_double_pendulum_ctypes_struct_matches_the_header():
-    from garage_amd import _lib
-    cname, py = 'ga_double_pendulum_env', _lib.DoublePendulumEnv
-    lines = ['#include <stddef.h>', '#include <stdio.h>',
-             '#include "garage_amd.h"', 'int main(void) {',
-             'printf("%d\\n", GA_ENV_DOUBLE_PENDULUM);',
-             'printf("{0} %zu\\n", sizeof({0}));'.format(cname)]
-    want = ['{}'.format(_lib.ENV_DOUBLE_PENDULUM),
-            '{} {}'.format(cname, ctypes.sizeof(py))]
-    for field, ftype in py._fields_:
-        lines.append('printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), '
-                     'sizeof((({0}*)0)->{1}));'.format(cname, field))
-        want.append('{}.{} {} {}'.format(cname, field,
-                                         getattr(py, field).offset,
-                                         ctypes.sizeof(ftype)))
-    lines += ['return 0;', '}']
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'layout.c'), os.path.join(tmp, 'layout')
-        with open(src, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-        subprocess.run(['cc', '-std=c99', '-Wall', '-Werror', '-I',
-                        os.path.join(ROOT, 'include'), src, '-o', exe],
-                       check=True)
-        got = subprocess.run([exe], capture_output=True, text=True,
-                             check=True).stdout.split('\n')[:-1]
-    assert got == want
-    assert _lib.ENV_DOUBLE_PENDULUM == 6
-    assert _lib.load().ga_abi_version() == 5
-
-
-def test_double_pendulum_argument_errors_without_a_gpu():
-    from garage_amd import _lib
-    from garage_amd.envs import DoublePendulumEnv, DoublePendulumVecEnv
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-
-    def env(kind=_lib.ENV_DOUBLE_PENDULUM, **kw):
-        e = _lib.DoublePendulumEnv(n=4, max_episode_length=5, state=addr,
-                                   t=addr, resets=addr)
-        for k, v in kw.items():
-            setattr(e, k, v)
-        return C.byref(_lib.env_ref(kind, e))
-
-    def reset(e, ldo=12):
-        _lib.call('ga_env_reset', e, None, addr, ldo, None)
-
-    def step(e, ldo=12):
-        _lib.call('ga_env_step', e, addr, 1, None, addr, ldo, addr, addr, None)
-
-    def record(e, ldo=12):
-        rec = _lib.RecordArgs(n=4, col=0, Tcap=8, max_episode_length=5,
-                              reward=addr, step_type=addr, next_obs=addr,
-                              ldo=ldo, obs_dim=11, ep_t=addr, rew_buf=addr,
-                              st_buf=addr, tail_buf=addr, lastobs_buf=addr,
-                              done=addr, step_eps=addr, step_samples=addr)
-        _lib.call('ga_env_step_record', e, C.byref(rec), None, addr, 1, addr,
-                  None)
-
-    for fn in (reset, step, record):
-        for field in ('state', 't', 'resets'):
-            with pytest.raises(_lib.GarageAmdError, match='null env state'):
-                fn(env(**{field: None}))
-        for bad in (0, 65536):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='max_episode_length'):
-                fn(env(max_episode_length=bad))
-        with pytest.raises(_lib.GarageAmdError, match='bad env size'):
-            fn(env(n=0))
-        with pytest.raises(_lib.GarageAmdError, match='unknown env kind 7'):
-            fn(env(kind=7))
-    # observation rows narrower than 11
-    with pytest.raises(_lib.GarageAmdError, match='bad obs buffer'):
-        reset(env(), ldo=10)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        step(env(), ldo=10)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        record(env(), ldo=10)
-    with pytest.raises(_lib.GarageAmdError, match='null pointer'):
-        _lib.call('ga_double_pendulum_reset_draw', 0, 0, 0, None)
-    for bad in (None, float('inf'), 0, 65536):
-        with pytest.raises(ValueError):
-            DoublePendulumVecEnv(4, max_episode_length=bad)
-        with pytest.raises(ValueError):
-            DoublePendulumEnv(max_episode_length=bad)
-
-
-def test_rollout_env_steps_takes_the_double_pendulum_kind_as_continuous():
-    """With rescale arguments the kind passes the "continuous action space"
-    check a discrete env fails, and fails the next one (a rollout of more steps
-    than the buffer holds), before any device call."""
-    from garage_amd import _lib
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-    desc = _lib.MlpDesc()
-    head = _lib.HeadArgs(col=0, Tcap=4)
-    rec = _lib.RecordArgs()
-    norm = _lib.NormArgs(act_low=addr, act_high=addr, scaled_action=addr,
-                         expected_action_scale=1.0, reward_scale=1.0)
-    dp = _lib.DoublePendulumEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                                resets=addr)
-    with pytest.raises(_lib.GarageAmdError,
-                       match='steps exceed the rollout buffer'):
-        _lib.call('ga_rollout_env_steps', C.byref(desc), addr, C.byref(head),
-                  C.byref(_lib.env_ref(_lib.ENV_DOUBLE_PENDULUM, dp)),
-                  C.byref(rec), addr, addr, C.byref(norm), None, None, 5, None)

@@ -3,10 +3,12 @@ no GPU: the fp32 twin (``garage_amd.envs.MountainCarEnv``, the arithmetic
 ``include/garage_amd.h`` fixes) against a float64 restatement of gym 0.17's
 ``MountainCar-v0`` and ``MountainCarContinuous-v0`` steps, the exact invariants
 (the box, the wall), the "push the way you move" script reaching the goal on
-both, the Philox reset draws against a pure-Python Philox4x32-10, episode
-semantics, the ctypes mirror of ``ga_mountain_car_env`` against the header, the
-argument errors of the entry points and which of the two variants
-``ga_rollout_env_steps`` takes as discrete.
+both and episode semantics.
+
+What every kind states the same way (reset draws against a
+pure-Python Philox, the ctypes mirror of its struct, the argument errors of the
+entry points) is in ``test_state_envs_cpu.py``, rows ``mountain_car`` and
+``mountain_car_continuous``.
 
 The bounds on |twin - float64| are 4x the worst error measured when the
 arithmetic was fixed (the restatement is the yardstick; the factor leaves room
@@ -16,15 +18,9 @@ touches it stops: the states whose float64 position before the clip is within
 1e-6 of -1.2 are compared in position only):
   discrete, classes 0, 1, 2 and out of range     6.4e-8 / 4.3e-9
   continuous, forces in [-1.5, 1.5]              6.4e-8 / 4.3e-9"""
-import ctypes
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # 4x the measured worst (module docstring)
 STEP_X, STEP_V = 4 * 6.4e-8, 4 * 4.3e-9
@@ -200,59 +196,6 @@ def test_pushing_the_way_you_move_reaches_the_goal(continuous):
         assert np.array_equal(total32, -len32)
 
 
-def philox4x32_10(c, k):
-    """Philox4x32-10 (Salmon et al., SC'11) on Python integers."""
-    c0, c1, c2, c3 = c
-    k0, k1 = k
-    m32 = 0xffffffff
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & m32,
-                          (p0 >> 32) ^ c3 ^ k1, p0 & m32)
-        k0, k1 = (k0 + 0x9E3779B9) & m32, (k1 + 0xBB67AE85) & m32
-    return c0, c1, c2, c3
-
-
-STREAM = 9
-
-
-def reset_draw_py(seed, env_id, counter):
-    f = np.float32
-    key = (seed & 0xffffffff, seed >> 32)
-    w = philox4x32_10((env_id & 0xffffffff, counter, 0, STREAM << 16), key)
-    u = (f(w[0] >> 8) + f(0.5)) * f(2.0**-24)
-    return np.asarray([f(-0.6) + f(0.2) * u, 0], dtype=np.float32)
-
-
-def test_reset_draws_equal_a_pure_python_philox():
-    from garage_amd.envs import MountainCarEnv, mountain_car_reset_draw
-    draws = {}
-    for seed in (0, (7 << 32) | 11):
-        for env_id in (0, 1, 1 << 31):
-            for counter in (0, 1, (1 << 32) - 1):
-                got = mountain_car_reset_draw(seed, env_id, counter)
-                want = reset_draw_py(seed, env_id, counter)
-                assert got.dtype == np.float32 and got.shape == (2, )
-                assert got.tobytes() == want.tobytes(), (seed, env_id, counter)
-                assert np.float32(-0.6) <= got[0] <= np.float32(-0.4)
-                assert got[1] == 0
-                draws[(seed, env_id, counter)] = got.tobytes()
-    assert len(set(draws.values())) == len(draws) == 18
-    assert mountain_car_reset_draw(11, 1, 1).tobytes() != draws[
-        ((7 << 32) | 11, 1, 1)]
-    # the twin of either variant starts its episodes there
-    for continuous in (False, True):
-        for i in (0, 3, 69):
-            env = MountainCarEnv(seed=5, env_id=37 + i, continuous=continuous)
-            first, info = env.reset()
-            assert info == {} and first.dtype == np.float32
-            assert first.tobytes() == mountain_car_reset_draw(
-                5, 37 + i, 0).tobytes()
-            env.reset()
-            assert np.array_equal(env.state,
-                                  mountain_car_reset_draw(5, 37 + i, 1))
-
-
 def test_twin_episode_semantics():
     from garage_amd._dtypes import Box, Discrete, StepType
     from garage_amd.envs import MountainCarEnv
@@ -320,139 +263,3 @@ def test_twin_episode_semantics():
     back = np.asarray([[0.55, -0.02]], dtype=f)
     assert not MountainCarEnv.advance(back, np.full(1, -1.0, f), True)[3][0]
     assert not MountainCarEnv.advance(back, np.full(1, 0), False)[3][0]
-
-
-def test_mountain_car_ctypes_struct_matches_the_header():
-    from garage_amd import _lib
-    cname, py = 'ga_mountain_car_env', _lib.MountainCarEnv
-    lines = ['#include <stddef.h>', '#include <stdio.h>',
-             '#include "garage_amd.h"', 'int main(void) {',
-             'printf("%d\\n", GA_ENV_MOUNTAIN_CAR);',
-             'printf("{0} %zu\\n", sizeof({0}));'.format(cname)]
-    want = ['{}'.format(_lib.ENV_MOUNTAIN_CAR),
-            '{} {}'.format(cname, ctypes.sizeof(py))]
-    for field, ftype in py._fields_:
-        lines.append('printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), '
-                     'sizeof((({0}*)0)->{1}));'.format(cname, field))
-        want.append('{}.{} {} {}'.format(cname, field,
-                                         getattr(py, field).offset,
-                                         ctypes.sizeof(ftype)))
-    lines += ['return 0;', '}']
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, 'layout.c'), os.path.join(tmp, 'layout')
-        with open(src, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-        subprocess.run(['cc', '-std=c99', '-Wall', '-Werror', '-I',
-                        os.path.join(ROOT, 'include'), src, '-o', exe],
-                       check=True)
-        got = subprocess.run([exe], capture_output=True, text=True,
-                             check=True).stdout.split('\n')[:-1]
-    assert got == want
-    assert _lib.ENV_MOUNTAIN_CAR == 10
-    # `continuous` sits where the neighbours have their padding
-    assert _lib.MountainCarEnv.continuous.offset == _lib.PendulumEnv.pad_.offset
-    assert ctypes.sizeof(py) == ctypes.sizeof(_lib.PendulumEnv)
-    assert _lib.load().ga_abi_version() == 5
-
-
-def test_mountain_car_argument_errors_without_a_gpu():
-    from garage_amd import _lib
-    from garage_amd.envs import MountainCarEnv, MountainCarVecEnv
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-
-    def env(kind=_lib.ENV_MOUNTAIN_CAR, **kw):
-        e = _lib.MountainCarEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                                resets=addr)
-        for k, v in kw.items():
-            setattr(e, k, v)
-        return C.byref(_lib.env_ref(kind, e))
-
-    def reset(e, ldo=4):
-        _lib.call('ga_env_reset', e, None, addr, ldo, None)
-
-    def step(e, ldo=4):
-        _lib.call('ga_env_step', e, addr, 1, None, addr, ldo, addr, addr, None)
-
-    def record(e, ldo=4):
-        rec = _lib.RecordArgs(n=4, col=0, Tcap=8, max_episode_length=5,
-                              reward=addr, step_type=addr, next_obs=addr,
-                              ldo=ldo, obs_dim=2, ep_t=addr, rew_buf=addr,
-                              st_buf=addr, tail_buf=addr, lastobs_buf=addr,
-                              done=addr, step_eps=addr, step_samples=addr)
-        _lib.call('ga_env_step_record', e, C.byref(rec), None, addr, 1, addr,
-                  None)
-
-    for fn in (reset, step, record):
-        for field in ('state', 't', 'resets'):
-            with pytest.raises(_lib.GarageAmdError, match='null env state'):
-                fn(env(**{field: None}))
-        for bad in (0, 65536):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='max_episode_length'):
-                fn(env(max_episode_length=bad))
-        with pytest.raises(_lib.GarageAmdError, match='bad env size'):
-            fn(env(n=0))
-        for bad in (-1, 2):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='continuous must be 0 or 1'):
-                fn(env(continuous=bad))
-        for unknown in (7, 9, 11):
-            with pytest.raises(_lib.GarageAmdError,
-                               match='unknown env kind {}'.format(unknown)):
-                fn(env(kind=unknown))
-    # observation rows narrower than 2
-    with pytest.raises(_lib.GarageAmdError, match='bad obs buffer'):
-        reset(env(), ldo=1)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        step(env(), ldo=1)
-    with pytest.raises(_lib.GarageAmdError, match='leading dimensions'):
-        record(env(), ldo=1)
-    with pytest.raises(_lib.GarageAmdError, match='null pointer'):
-        _lib.call('ga_mountain_car_reset_draw', 0, 0, 0, None)
-    for bad in (float('inf'), 0, 65536):
-        for continuous in (False, True):
-            with pytest.raises(ValueError):
-                MountainCarVecEnv(4, continuous, max_episode_length=bad)
-            with pytest.raises(ValueError):
-                MountainCarEnv(continuous=continuous, max_episode_length=bad)
-
-
-def test_rollout_env_steps_asks_the_struct_whether_the_kind_is_discrete():
-    """With rescale arguments ``continuous = 0`` fails the "continuous action
-    space" check, as CartPole and Acrobot do; ``continuous = 1`` passes it, as
-    Pendulum does, and fails the next one (a rollout of more steps than the
-    buffer holds) -- all before any device call."""
-    from garage_amd import _lib
-    C = ctypes
-    buf = C.create_string_buffer(256)
-    addr = C.addressof(buf)
-    desc = _lib.MlpDesc()
-    head = _lib.HeadArgs(col=0, Tcap=4)
-    rec = _lib.RecordArgs()
-    norm = _lib.NormArgs(act_low=addr, act_high=addr, scaled_action=addr,
-                         expected_action_scale=1.0, reward_scale=1.0)
-
-    def steps(ref):
-        _lib.call('ga_rollout_env_steps', C.byref(desc), addr, C.byref(head),
-                  ref, C.byref(rec), addr, addr, C.byref(norm), None, None, 5,
-                  None)
-
-    def car(continuous):
-        e = _lib.MountainCarEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                                resets=addr, continuous=continuous)
-        return C.byref(_lib.env_ref(_lib.ENV_MOUNTAIN_CAR, e))
-
-    acro = _lib.AcrobotEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                           resets=addr)
-    pend = _lib.PendulumEnv(n=4, max_episode_length=5, state=addr, t=addr,
-                            resets=addr)
-    for ref in (car(0), C.byref(_lib.env_ref(_lib.ENV_ACROBOT, acro))):
-        with pytest.raises(_lib.GarageAmdError,
-                           match='continuous action space'):
-            steps(ref)
-    for ref in (car(1), C.byref(_lib.env_ref(_lib.ENV_PENDULUM, pend))):
-        with pytest.raises(_lib.GarageAmdError,
-                           match='steps exceed the rollout buffer'):
-            steps(ref)

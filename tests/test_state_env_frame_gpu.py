@@ -1,6 +1,7 @@
 """The frame the five seeded state-vector env kinds share on the device
 (``rollout_dev.h``: ``StateEnv<K>`` -- counters, step type, store order) at the
-sizes around the env kernels' 256-thread block, one table row per kind.
+sizes around the env kernels' 256-thread block, one row of
+``_state_env_kinds.KINDS`` per kind.
 
 Each case allocates three members more than the kernels are told of and poisons
 those guard rows, runs ``ga_env_step`` with a masked ``ga_env_reset`` of the
@@ -14,57 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+import _state_env_kinds as kinds
+from _state_env_helpers import GUARD, _bits, _guards_intact, _np, _poison
+
 pytestmark = pytest.mark.gpu
 
-GUARD = 3
-POISON = 12345.0
 P, STEPS = 3, 6  # max_episode_length, steps per case
 SEED, ID0 = 11, 1000
-
-# batch class, twin class, constructor keywords, action draw (rng, shape):
-# class indices with the out-of-range 3 and -1 where the kind takes three
-# classes, forces beyond the clips where it takes a force
-ROWS = {
-    'cartpole': ('CartPoleVecEnv', 'CartPoleEnv', {},
-                 lambda rng, shape: rng.randint(0, 2, shape)),
-    'pendulum': ('PendulumVecEnv', 'PendulumEnv', {},
-                 lambda rng, shape: rng.uniform(-2.5, 2.5, shape)),
-    'double_pendulum': ('DoublePendulumVecEnv', 'DoublePendulumEnv', {},
-                        lambda rng, shape: rng.uniform(-1.3, 1.3, shape)),
-    'acrobot': ('AcrobotVecEnv', 'AcrobotEnv', {},
-                lambda rng, shape: rng.randint(-1, 4, shape)),
-    'mountain_car': ('MountainCarVecEnv', 'MountainCarEnv',
-                     {'continuous': False},
-                     lambda rng, shape: rng.randint(-1, 4, shape)),
-    'mountain_car_continuous': ('MountainCarVecEnv', 'MountainCarEnv',
-                                {'continuous': True},
-                                lambda rng, shape: rng.uniform(-1.6, 1.6,
-                                                               shape)),
-}
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def _poison(env, n):
-    for t in (env._state, env.obs, env.next_obs, env.reward):
-        t[n:] = POISON
-    env.step_type[n:] = 77
-    env._t[n:] = 1234567
-    env._resets[n:] = 7654321
-
-
-def _guards_intact(env, n):
-    for t in (env._state, env.obs, env.next_obs, env.reward):
-        assert (_np(t[n:]) == np.float32(POISON)).all()
-    assert (_np(env.step_type[n:]) == 77).all()
-    assert (_np(env._t[n:]) == 1234567).all()
-    assert (_np(env._resets[n:]) == 7654321).all()
 
 
 def _frame_equals_twins(env, twins, n, obs, where):
@@ -82,14 +39,13 @@ def _frame_equals_twins(env, twins, n, obs, where):
 
 
 @pytest.mark.parametrize('n', [1, 255, 256, 257])
-@pytest.mark.parametrize('kind', sorted(ROWS))
+@pytest.mark.parametrize('kind', sorted(kinds.KINDS))
 def test_frame_equals_one_twin_per_member_bit_for_bit(kind, n):
-    from garage_amd import envs
-    batch, twin, kw, draw = ROWS[kind]
-    env = getattr(envs, batch)(n + GUARD, max_episode_length=P, seed=SEED,
-                               env_id0=ID0, **kw)
-    twins = [getattr(envs, twin)(seed=SEED, env_id=ID0 + i,
-                                 max_episode_length=P, **kw) for i in range(n)]
+    row = kinds.KINDS[kind]
+    env = row.new_batch(n + GUARD, max_episode_length=P, seed=SEED,
+                        env_id0=ID0)
+    twins = [row.new_twin(seed=SEED, env_id=ID0 + i, max_episode_length=P)
+             for i in range(n)]
     O = env.obs_dim
     env._c.n = n  # the kernels' batch; rows n .. n + 2 are guards
     _poison(env, n)
@@ -101,7 +57,8 @@ def test_frame_equals_one_twin_per_member_bit_for_bit(kind, n):
         tw._t = i % P
     _frame_equals_twins(env, twins, n, obs, 'reset_all')
 
-    actions = draw(np.random.RandomState(5 + n), (STEPS, n)).astype(np.float32)
+    actions = row.frame_actions(np.random.RandomState(5 + n),
+                                (STEPS, n)).astype(np.float32)
     act = torch.zeros(n + GUARD, 4, device=env.device)
     ends = 0
     for t in range(STEPS):
