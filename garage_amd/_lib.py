@@ -169,6 +169,28 @@ class UpdateArgs(C.Structure):
                 ('partials_floats', c_i64), ('phase', c_i32)]
 
 
+class MemberUpdate(C.Structure):
+    """``ga_member_update``."""
+    _fields_ = [('params', ptr), ('grads', ptr), ('exp_avg', ptr),
+                ('exp_avg_sq', ptr), ('X', ptr), ('ldx', c_i64), ('S', c_i64),
+                ('perm', ptr), ('actions', ptr), ('lda', c_i64),
+                ('old_ll', ptr), ('adv', ptr), ('returns', ptr),
+                ('step0', c_i64), ('lr', c_f64), ('clip', c_f32),
+                ('ent_coeff', c_f32), ('losses', ptr)]
+
+
+class UpdateMembersArgs(C.Structure):
+    """``ga_update_members_args``."""
+    _fields_ = [('desc', C.POINTER(MlpDesc)), ('kind', c_i32), ('algo', c_i32),
+                ('ent_flags', c_i32), ('has_min', c_i32),
+                ('min_log_std', c_f32), ('has_max', c_i32),
+                ('max_log_std', c_f32), ('double_softmax', c_i32),
+                ('learn_std', c_i32), ('beta1', c_f64), ('beta2', c_f64),
+                ('eps', c_f64), ('mb', c_i64), ('n_members', c_i64),
+                ('members_host', C.POINTER(MemberUpdate)), ('partials', ptr),
+                ('partials_floats', c_i64), ('workspace', ptr)]
+
+
 ABI_VERSION = 5  # ga_abi_version() of the library these structs mirror
 
 # name -> (restype, argtypes); mirrors include/garage_amd.h one to one.
@@ -334,6 +356,10 @@ SIGNATURES = {
     'ga_set_split_bf16': (c_int, [c_int]),
     'ga_update_epoch_pair': (c_int, [C.POINTER(UpdateArgs), ptr,
                                      C.POINTER(UpdateArgs), ptr]),
+    'ga_update_members_supported': (c_int, [C.POINTER(MlpDesc)]),
+    'ga_update_members_partials_floats': (c_i64, [C.POINTER(MlpDesc), c_i64,
+                                                  c_i64]),
+    'ga_update_epoch_members': (c_int, [C.POINTER(UpdateMembersArgs), ptr]),
     'ga_set_allreduce_hook': (None, [ptr]),
     'ga_comm_available': (c_int, []),
     'ga_comm_unique_id': (c_int, [ptr]),

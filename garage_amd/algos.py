@@ -9,6 +9,7 @@ leaves the GPU except for the episode lengths and the logged scalars.
 """
 import collections
 import math
+import types
 
 import numpy as np
 import torch
@@ -285,6 +286,14 @@ class VPG:
 
     # -- one iteration (vpg.py:136-206) -----------------------------------------
     def _train_once(self, itr, eps):
+        c = self._before_train(eps)
+        self._train(c.batch, c.adv, c.returns, c.old_ll)
+        return self._after_train(itr, c)
+
+    def _before_train(self, eps):
+        """Everything of an iteration up to the update: advantages, returns and
+        the diagnostics before it.  Returns what :meth:`_train` and
+        :meth:`_after_train` read."""
         batch = self._to_device_batch(eps)
         pol, vf = self.policy, self._value_function
         dev = pol.device
@@ -361,9 +370,24 @@ class VPG:
 
         steps_before = (pol.net.adam_steps,
                         self._value_function.net.adam_steps)
-        self._train(batch, adv, returns, old_ll)
+        return types.SimpleNamespace(
+            batch=batch, adv=adv, returns=returns, old_ll=old_ll, S=S,
+            zero_obs=zero_obs, n_pad=n_pad, n_cells=n_cells, share=share,
+            values=values, v0=v0, gaussian=gaussian, s_old=s_old,
+            mean_old=mean_old, mean_old_pad=mean_old_pad,
+            loss_before=loss_before, kl_before=kl_before,
+            vf_before=vf_before, steps_before=steps_before)
 
-        # ---- diagnostics after the update (vpg.py:178-184) -------------------
+    def _after_train(self, itr, c):
+        """The diagnostics after the update (``vpg.py:178-184``), the logged
+        scalars and the old policy's sync; returns the mean return."""
+        pol, dev = self.policy, self.policy.device
+        batch, adv, returns, old_ll, S = c.batch, c.adv, c.returns, c.old_ll, c.S
+        zero_obs, n_pad, n_cells, share = c.zero_obs, c.n_pad, c.n_cells, c.share
+        values, v0, gaussian, s_old = c.values, c.v0, c.gaussian, c.s_old
+        mean_old, mean_old_pad = c.mean_old, c.mean_old_pad
+        loss_before, kl_before = c.loss_before, c.kl_before
+        vf_before, steps_before = c.vf_before, c.steps_before
         loss_after, mean_new, _ = self._policy_loss_pass(
             batch, adv, old_ll, S, None)
         kl_after = self._mean_kl(mean_old, mean_old_pad, s_old, mean_new,
@@ -1396,4 +1420,299 @@ class CEM:
         return rtn
 
 
-__all__ = ['VPG', 'PPO', 'TRPO', 'CEM']
+class PopulationPPO:
+    """A population of narrow PPO (or VPG) learners trained in shared launches.
+
+    ``members`` are ordinary :class:`PPO` objects (or :class:`VPG` objects), one
+    per member of a :class:`~garage_amd.sampler.GpuPopulationSampler`.  Step ``k``
+    of every member's optimisation pass goes out as two launches
+    (``ga_update_epoch_members``) instead of two per member, network and
+    minibatch, and every member gets, bit for bit, what its own ``_train_once``
+    on its own batch gives it on the narrow path (``ga_set_small_step(0)``): seeds
+    and learning-rate sweeps of PPO at the launch count of one run.  There is no
+    reference counterpart: garage trains one learner per process.
+
+    The members must share the algorithm, the networks' shapes (two equal tanh
+    hidden layers of 32 or 64 units, at most 32 inputs and 8 outputs), the head
+    kind and its options, ``minibatch_size``, ``max_optimization_epochs``, the
+    permutation mode, the entropy configuration and torch's default-shaped Adam
+    with the same ``betas`` and ``eps``.  They may differ in ``lr``,
+    ``lr_clip_range``, ``policy_ent_coeff`` and their optimizers' ``seed``.
+    Anything else raises a ``ValueError`` naming it; nothing falls back to
+    training the members one by one.
+
+    The members' parameters, gradients and Adam moments move into rows of four
+    ``(M, n_flat)`` tensors per network and every member's ``net`` points at its
+    row, so the tensor that trains is the tensor that rolls out
+    (:attr:`member_params`).
+    """
+
+    _BUFFERS = ('params', 'grads', 'exp_avg', 'exp_avg_sq')
+
+    def __init__(self, members, sampler=None):
+        self.members = list(members)
+        self._sampler = sampler
+        self._check_members()
+        if sampler is not None and getattr(
+                sampler, 'n_members', len(self.members)) != len(self.members):
+            raise ValueError('PopulationPPO trains {} members; the sampler rolls '
+                             'out {}'.format(len(self.members),
+                                             sampler.n_members))
+        self._adopt()
+
+    # -- what the members must share ----------------------------------------------
+    @staticmethod
+    def _shared_facts(algo):
+        """(name, value) of everything the joint launches take ONE value of."""
+        pol, vf = algo.policy, algo._value_function
+        facts = [('algorithm', type(algo).__name__),
+                 ('policy kind', pol.kind)]
+        for name, mod in (('policy', pol), ('value function', vf)):
+            net = mod.net
+            facts += [(name + ' network shape', tuple(net.dims)),
+                      (name + ' hidden nonlinearity', net.hidden_act),
+                      (name + ' output nonlinearity', net.output_act),
+                      (name + ' layer normalization', net.layer_norm),
+                      (name + ' learn_std', bool(getattr(mod, '_learn_std',
+                                                         True)))]
+        if pol.kind == 'gaussian':
+            facts.append(('policy std options', pol._std_args()))
+        else:
+            facts.append(('policy double_softmax', bool(pol.double_softmax)))
+        for name, opt in (('policy optimizer', algo._policy_optimizer),
+                          ('vf optimizer', algo._vf_optimizer)):
+            h = opt._hyper
+            facts += [(name + ' minibatch_size', opt._minibatch_size),
+                      (name + ' max_optimization_epochs',
+                       opt._max_optimization_epochs),
+                      (name + ' permutation', opt._permutation),
+                      (name + ' betas', tuple(h.get('betas', (0.9, 0.999)))),
+                      (name + ' eps', h.get('eps', 1e-8))]
+        facts += [('entropy_method', algo._entropy_method),
+                  ('use_softplus_entropy', bool(algo._use_softplus_entropy)),
+                  ('stop_entropy_gradient', bool(algo._stop_entropy_gradient))]
+        return facts
+
+    def _check_members(self):
+        from garage_amd import _lib
+        import ctypes as C
+        if not self.members:
+            raise ValueError('PopulationPPO needs at least one member')
+        if len(self.members) > 1024:
+            raise ValueError('PopulationPPO trains at most 1024 members')
+        for m, algo in enumerate(self.members):
+            who = 'member {}'.format(m)
+            if type(algo) not in (PPO, VPG):
+                raise ValueError('{} is a {}: PopulationPPO trains PPO or VPG '
+                                 'objects'.format(who, type(algo).__name__))
+            for opt in (algo._policy_optimizer, algo._vf_optimizer):
+                if not opt.default_adam:
+                    raise ValueError('{}: an optimizer other than torch\'s '
+                                     'default-shaped Adam is not supported'
+                                     .format(who))
+                if opt.grad_hook is not None or opt.native_comm is not None \
+                        or opt.dp_minibatches:
+                    raise ValueError('{}: data-parallel members are not '
+                                     'supported'.format(who))
+            if algo._comm is not None:
+                raise ValueError('{}: data-parallel members are not supported'
+                                 .format(who))
+            if getattr(algo, 'fuse_head', False):
+                raise ValueError('{}: fuse_head is not supported'.format(who))
+            for name, mod in (('policy', algo.policy),
+                              ('value function', algo._value_function)):
+                if not _lib.load().ga_update_members_supported(
+                        C.byref(mod.net._desc)):
+                    raise ValueError(
+                        '{}: the {} network {} is unsupported (two equal tanh '
+                        'hidden layers of 32 or 64 units, <= 32 inputs, <= 8 '
+                        'linear outputs, no layer normalization)'.format(
+                            who, name, tuple(mod.net.dims)))
+        first = self._shared_facts(self.members[0])
+        for m, algo in enumerate(self.members[1:], 1):
+            for (name, a), (_, b) in zip(first, self._shared_facts(algo)):
+                if a != b:
+                    raise ValueError('member {} differs from member 0 in {}: '
+                                     '{!r} against {!r}'.format(m, name, b, a))
+        mods = [id(x) for a in self.members
+                for x in (a.policy, a._value_function)]
+        if len(set(mods)) != len(mods):
+            raise ValueError('every member needs a policy and a value function '
+                             'of its own')
+
+    def _modules(self, which):
+        return [a.policy if which == 'policy' else a._value_function
+                for a in self.members]
+
+    def _adopt(self):
+        """The members' buffers into rows of ``(M, n_flat)`` tensors; every
+        member's ``net`` then points at its row view."""
+        self._rows, self._partials = {}, {}
+        M = len(self.members)
+        for which in ('policy', 'vf'):
+            mods = self._modules(which)
+            net0 = mods[0].net
+            rows = {}
+            for name in self._BUFFERS:
+                t = torch.empty(M, net0.n_flat, dtype=torch.float32,
+                                device=net0.device)
+                for m, mod in enumerate(mods):
+                    t[m].copy_(getattr(mod.net, name))
+                    setattr(mod.net, name, t[m])
+                rows[name] = t
+            self._rows[which] = rows
+
+    @property
+    def member_params(self):
+        """The ``(M, n_flat)`` tensor of the members' policy parameters, as
+        ``GpuPopulationSampler.obtain_samples`` takes it."""
+        return self._rows['policy']['params']
+
+    # -- the joint update -----------------------------------------------------------
+    def _pass_args(self, which, ctxs):
+        """``ga_update_members_args`` of one network of every member (with what
+        keeps its pointers alive)."""
+        from garage_amd import _lib
+        import ctypes as C
+        first = self.members[0]
+        mods = self._modules(which)
+        opts = [a._policy_optimizer if which == 'policy' else a._vf_optimizer
+                for a in self.members]
+        net0, M = mods[0].net, len(self.members)
+        a = _lib.UpdateMembersArgs()
+        a.desc = C.pointer(net0._desc)
+        a.learn_std = int(getattr(mods[0], '_learn_std', True))
+        if which == 'policy':
+            pol = mods[0]
+            a.kind = 0
+            if pol.kind == 'gaussian':
+                a.has_min, a.min_log_std, a.has_max, a.max_log_std = \
+                    pol._std_args()
+            else:
+                a.kind = 2
+                a.double_softmax = int(pol.double_softmax)
+            a.algo = first._algo_id
+            a.ent_flags = first._ent_flags()
+        else:
+            a.kind = 1
+        h = opts[0]._hyper
+        betas = h.get('betas', (0.9, 0.999))
+        a.beta1, a.beta2 = float(betas[0]), float(betas[1])
+        a.eps = float(h.get('eps', 1e-8))
+        mb = opts[0]._minibatch_size
+        a.mb = 0 if mb is None else int(mb)
+        a.n_members = M
+        arr = (_lib.MemberUpdate * M)()
+        rows = self._rows[which]
+        max_rows = 1
+        for m, (algo, c) in enumerate(zip(self.members, ctxs)):
+            u, batch = arr[m], c.batch
+            for name in self._BUFFERS:
+                setattr(u, name, rows[name][m].data_ptr())
+            u.X, u.ldx = batch.obs_dev.data_ptr(), batch.obs_dev.stride(0)
+            u.S = c.S
+            if which == 'policy':
+                u.actions = batch.actions_dev.data_ptr()
+                u.lda = batch.actions_dev.stride(0)
+                u.old_ll, u.adv = c.old_ll.data_ptr(), c.adv.data_ptr()
+                u.clip = float(algo._lr_clip_range)
+                u.ent_coeff = float(algo._policy_ent_coeff)
+            else:
+                u.returns = c.returns.data_ptr()
+            u.lr = float(opts[m]._hyper['lr'])
+            max_rows = max(max_rows, c.S if mb is None else min(c.S, int(mb)))
+        a.members_host = arr
+        need = int(_lib.load().ga_update_members_partials_floats(
+            a.desc, M, max_rows))
+        part = self._partials.get(which)
+        if part is None or part.numel() < need:
+            part = self._partials[which] = torch.empty(
+                need, dtype=torch.float32, device=net0.device)
+        a.partials, a.partials_floats = part.data_ptr(), part.numel()
+        return a, arr, mods, opts
+
+    def _train(self, ctxs):
+        """The joint passes: per epoch one ``ga_update_epoch_members`` call for
+        the policies, then one for the value functions (on two streams).  The
+        permutations are drawn as ``M`` lone ``_train_once`` calls one after
+        another draw them: member 0's policy shuffles, then its value-function
+        shuffles, then member 1's."""
+        import ctypes as C
+        perms = []
+        for algo, c in zip(self.members, ctxs):
+            perms.append(
+                (list(algo._policy_optimizer.epoch_permutations(c.S)),
+                 list(algo._vf_optimizer.epoch_permutations(c.S))))
+        passes = [self._pass_args('policy', ctxs), self._pass_args('vf', ctxs)]
+        # the policies' passes on the current stream, the value functions' on a side
+        # stream: the two share no written state (as VPG._train_native_pair)
+        main = torch.cuda.current_stream()
+        if getattr(self, '_side_stream', None) is None:
+            self._side_stream = torch.cuda.Stream()
+        side = self._side_stream
+        side.wait_stream(main)  # inputs (adv, returns, perms) are ready
+        streams = [C.c_void_p(main.cuda_stream), C.c_void_p(side.cuda_stream)]
+        epochs = max(len(p) for p in perms[0])
+        for e in range(epochs):
+            for i, (a, arr, mods, opts) in enumerate(passes):
+                if e >= len(perms[0][i]):
+                    continue
+                for m, mod in enumerate(mods):
+                    perm = perms[m][i][e]
+                    arr[m].perm = None if perm is None else perm.data_ptr()
+                    arr[m].step0 = mod.net.adam_steps
+                call('ga_update_epoch_members', C.byref(a), streams[i])
+                for m, mod in enumerate(mods):
+                    mod.net.adam_steps += len(
+                        opts[m].minibatch_bounds(ctxs[m].S)) - 1
+        main.wait_stream(side)
+        del passes, perms
+
+    def train_once(self, itr, batches):
+        """One iteration of every member on its own batch (one
+        ``DeviceEpisodeBatch`` per member): every member's work before the
+        update, the joint passes, every member's diagnostics after it (logged
+        under ``member<m>/``).  Returns the members' mean returns."""
+        if len(batches) != len(self.members):
+            raise ValueError('train_once needs one batch per member ({}), got '
+                             '{}'.format(len(self.members), len(batches)))
+        ctxs = [algo._before_train(b)
+                for algo, b in zip(self.members, batches)]
+        self._train(ctxs)
+        returns = []
+        for m, (algo, c) in enumerate(zip(self.members, ctxs)):
+            with logger.tabular.prefix('member{}/'.format(m)):
+                returns.append(algo._after_train(itr, c))
+        return returns
+
+    def train(self, trainer):
+        """Drives a ``GpuPopulationSampler`` the way ``CEM.train`` does: per
+        epoch one rollout of every member with its own parameters, then one
+        joint iteration."""
+        if self._sampler is None:
+            raise ValueError('PopulationPPO.train needs a GpuPopulationSampler')
+        last_returns = None
+        for _ in trainer.step_epochs():
+            batches = self._sampler.obtain_samples(
+                trainer.step_itr, trainer._train_args.batch_size,
+                self.member_params)
+            if hasattr(trainer, 'total_env_steps'):
+                trainer.total_env_steps += int(sum(
+                    int(sum(b.lengths)) for b in batches))
+            last_returns = self.train_once(trainer.step_itr, batches)
+            trainer.step_itr += 1
+        return last_returns
+
+    # -- snapshots: the members rebuild their networks; the rows are re-established
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        for k in ('_rows', '_partials', '_side_stream'):
+            state.pop(k, None)
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._adopt()
+
+
+__all__ = ['VPG', 'PPO', 'TRPO', 'CEM', 'PopulationPPO']

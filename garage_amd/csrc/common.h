@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <math.h>
 #include <string.h>
 
 #include "internal.h"
@@ -38,10 +39,6 @@ static inline bool ga_aligned16(const void* p) {
 
 static inline int64_t ga_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Everything below is for the device compiler; the host C++ that the CPU harnesses
-// under tests/host build (mlp_layers.cpp) takes the plumbing above.
-#ifdef __HIP__
-
 // ---- torch.optim.Adam (OptimizerWrapper.step, torch/optimizers/optimizer_wrapper.py:53-63)
 // The per-step constants, derived on the host in double and rounded once.
 struct GaAdam {
@@ -65,6 +62,10 @@ static inline GaAdam ga_adam_coeffs(double lr, double beta1, double beta2, doubl
   a.eps = (float)eps;
   return a;
 }
+
+// Everything below is for the device compiler; the host C++ that the CPU harnesses
+// under tests/host build (mlp_layers.cpp) takes the plumbing above.
+#ifdef __HIP__
 
 // One element of torch.optim.Adam's single-tensor step, the ONE Adam of every kernel,
 // with fused multiply-add contraction switched off (HIP's __fmul_rn / __fadd_rn are

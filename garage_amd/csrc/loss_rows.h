@@ -30,7 +30,7 @@ struct LossEnt {
 };
 
 // ent_flags of the C ABI: bit 0 regularized, bit 1 softplus, bit 2 stop gradient
-inline LossEnt lr_ent(float coeff, int ent_flags) {
+__host__ __device__ inline LossEnt lr_ent(float coeff, int ent_flags) {
   LossEnt e;
   e.coeff = coeff;
   e.regularized = ent_flags & 1;

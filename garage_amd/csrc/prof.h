@@ -21,7 +21,9 @@ enum GaProfKind {
                             // only (ga_launch_count), never timed
   GA_PROF_ROLLOUT_WIDE = 14,  // policy_step_fused_kernel<512> with n_steps > 1 (weights
                               // streamed: layer inputs up to 512); counted only
-  GA_PROF_KINDS = 15
+  GA_PROF_MEMBERS_STEP = 15,  // narrow_train_members_kernel<*>: step k of a whole
+                              // population in one launch; counted only
+  GA_PROF_KINDS = 16
 };
 
 // When profiling is on, hands out a (start, stop) event pair to attach to ONE

@@ -1196,6 +1196,73 @@ GA_API int ga_set_split_bf16(int on);
 GA_API int ga_update_epoch_pair(const ga_update_args* a, ga_stream_t stream_a,
                                 const ga_update_args* b, ga_stream_t stream_b);
 
+/* ---- one optimisation pass of a POPULATION of networks, in shared launches -------
+ * ga_update_epoch for n_members networks of one shape at once (new: the reference
+ * trains one learner per process).  Step k of every member's pass goes out as two
+ * launches -- forward + loss + backward of every member's minibatch k, then every
+ * member's reduction + Adam -- instead of two per member.  Each member gets, bit for
+ * bit, what ga_update_epoch (with ga_set_small_step(0), the narrow step on) gives a
+ * lone network on the member's data: the same kernel body, summation trees and Adam.
+ * Members may hold different sample counts; a member whose pass has fewer steps than
+ * another's is left alone in the remaining ones (nothing of it is written, its step
+ * count does not advance).
+ *
+ * One member: rows of (n_members, stride) tensors with stride % 4 == 0 -- the layout
+ * ga_policy_env_step_members_f32 rolls out from, so the tensor that trains is the
+ * tensor that rolls out -- and the member's own batch and hyperparameters. */
+typedef struct ga_member_update {
+  float* params; float* grads; float* exp_avg; float* exp_avg_sq;
+  const float* X; int64_t ldx; int64_t S;
+  const int32_t* perm;     /* S minibatch ids of this pass; NULL only with mb == 0 */
+  const float* actions; int64_t lda; const float* old_ll; const float* adv;
+  const float* returns;
+  int64_t step0;           /* Adam steps this member has already taken */
+  double lr;
+  float clip; float ent_coeff;
+  float* losses;           /* optional [steps of this member's pass] per-step losses */
+} ga_member_update;
+/* What the members share.  Minibatch k of member m = ids [k * mb, min(S_m, (k + 1) *
+ * mb)) of its permutation (ga_minibatch_range with n_mb = 0); mb == 0: rows [0, S_m)
+ * in one step.  kind / algo / ent_flags / has_min .. max_log_std / double_softmax /
+ * learn_std / beta1 .. eps as in ga_update_args.  partials: at least
+ * ga_update_members_partials_floats(desc, n_members, rows of the largest minibatch of
+ * any member) floats, 16-byte aligned.  workspace: reserved, may be NULL. */
+typedef struct ga_update_members_args {
+  const ga_mlp_desc* desc;
+  int32_t kind; int32_t algo; int32_t ent_flags;
+  int32_t has_min; float min_log_std; int32_t has_max; float max_log_std;
+  int32_t double_softmax; int32_t learn_std;
+  double beta1, beta2, eps;
+  int64_t mb;
+  int64_t n_members;
+  const ga_member_update* members_host; /* HOST array [n_members] */
+  float* partials; int64_t partials_floats;
+  double* workspace;
+} ga_update_members_args;
+/* 1: networks ga_update_epoch_members takes -- two equal tanh hidden layers of 32 or 64
+ * units, <= 32 inputs, <= 8 linear outputs, no layer normalisation (the narrow step's
+ * shapes); 0 otherwise, NULL included. */
+GA_API int ga_update_members_supported(const ga_mlp_desc* desc);
+/* Floats of `partials` for n_members members with minibatches of up to max_rows rows;
+ * 0: unsupported network or sizes out of range. */
+GA_API int64_t ga_update_members_partials_floats(const ga_mlp_desc* desc, int64_t n_members,
+                                                 int64_t max_rows);
+/* One pass: max over the members of ceil(S_m / mb) pairs of launches on `stream`, after
+ * one asynchronous copy of the member and Adam tables (built in pinned host memory
+ * the library keeps, eight passes' worth, grown on demand and kept).  The call MAY
+ * BLOCK its caller: from the ninth call on it first waits on the host for the pass that
+ * used its tables eight calls earlier; it never waits inside the pass.  The one entry
+ * point that is therefore not graph-capture safe.  Refused before any launch (negative
+ * return, ga_last_error): null pointers (args, desc, members_host, partials, a
+ * member's params / grads / moments / X, the arrays its kind reads, perm with mb > 0),
+ * n_members outside 1 .. 1024, a network ga_update_members_supported refuses, a member
+ * pointer, ldx or lda that is not a 16-byte aligned quad (actions of kinds 0; params,
+ * grads, moments, X, partials always), parameter offsets that are not quads from 4 up,
+ * S_m < 1 or >= 2^31, mb < 0 or >= 2^31, step0 < 0, partials_floats smaller than
+ * ga_update_members_partials_floats returns, a kind outside 0 .. 2, an algo outside
+ * 0 .. 1. */
+GA_API int ga_update_epoch_members(const ga_update_members_args* args, ga_stream_t stream);
+
 /* RCCL communicator for the data-parallel gradient all-reduce (new: the
  * reference has no collective on this path).
  * ga_comm_unique_id fills 128 bytes on rank 0 (HOST pointer) to be broadcast by
@@ -1239,7 +1306,8 @@ GA_API int ga_prof_enable(int on);
 GA_API int ga_prof_collect(double* out_host, int n_kinds);
 /* Launches of kernel kind `kind` (csrc/prof.h: 9 = fwd_head_loss_kernel, 10 =
  * dgrad_wgrad0_kernel, 11 = narrow_train_kernel, 12 = mlp_eval_forward_kernel, 13 =
- * a whole rollout in one policy_step_fused_kernel launch, ...)
+ * a whole rollout in one policy_step_fused_kernel launch, 15 = a step of a whole
+ * population in one narrow_train_members_kernel launch, ...)
  * since the library was loaded, counted whether timing is on or not; -1 for an
  * unknown kind.  Tests use it to assert WHICH kernels an update dispatched to. */
 GA_API int64_t ga_launch_count(int kind);
