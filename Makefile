@@ -6,8 +6,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
-HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers
+HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -25,11 +25,11 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function 
 
 all: $(OUT)/libgarage_amd.so
 
-$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/gemm_core.h $(CSRC)/gemm_params.h $(CSRC)/loss_rows.h $(CSRC)/fused_train.h $(CSRC)/rollout_dev.h $(CSRC)/narrow_body.h $(CSRC)/reduce_trees.h $(CSRC)/members_step.h include/garage_amd.h
+$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/gemm_core.h $(CSRC)/gemm_params.h $(CSRC)/loss_rows.h $(CSRC)/fused_train.h $(CSRC)/rollout_dev.h $(CSRC)/narrow_body.h $(CSRC)/reduce_trees.h $(CSRC)/members_step.h $(CSRC)/member_pack.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
-$(OUT)/%.o: $(CSRC)/%.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/fused_train.h $(CSRC)/members_step.h include/garage_amd.h
+$(OUT)/%.o: $(CSRC)/%.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/fused_train.h $(CSRC)/members_step.h $(CSRC)/member_pack.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(FLAGS) -x hip -c $< -o $@
 
@@ -155,3 +155,19 @@ $(OUT)/update_members_asan_test: tests/host/update_members_harness.cpp $(CSRC)/u
 	  -o $@
 
 .PHONY: asan-members
+
+# The joint pack's argument checks, plane table and grids (member_pack_host.cpp) under
+# AddressSanitizer + UBSan with recording fakes for its three launches: every refusal
+# precedes the first launch, the table's paths, units and rows, the grids' bounds
+# (tests/host/).
+asan-member-pack: $(OUT)/member_pack_asan_test
+	$(OUT)/member_pack_asan_test
+
+$(OUT)/member_pack_asan_test: tests/host/member_pack_harness.cpp $(CSRC)/member_pack_host.cpp $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/member_pack.h include/garage_amd.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  tests/host/member_pack_harness.cpp $(CSRC)/member_pack_host.cpp \
+	  -o $@
+
+.PHONY: asan-member-pack

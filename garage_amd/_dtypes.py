@@ -632,6 +632,89 @@ class DeviceEpisodeBatch(EpisodeBatch):
                             step_types=self.step_types, lengths=self.lengths)
 
 
+class DevicePopulationBatch:
+    """The batches of a population's ``M`` members as views of ONE set of packed
+    arrays (``GpuPopulationSampler.obtain_population``).
+
+    ``obs_dev`` / ``actions_dev`` / ``head_dev`` / ``rewards_dev`` /
+    ``step_types_dev`` hold every member's samples: member ``m`` owns the rows
+    ``[member_off[m], member_off[m] + member_samples[m])``, and ``member_off``
+    (``M + 1`` entries) is a multiple of 16 rows, so that every member's slice of
+    every array starts on a 16-byte boundary; the rows in between are zeros.
+    ``last_obs_dev`` holds every member's episodes: member ``m`` owns the rows
+    ``[episode_start[m], episode_start[m + 1])``.  ``env_info_planes``: per
+    recorded env_info key the ``uint8`` device plane in sample rows.
+    ``ep_off_dev`` holds every member's episode offsets, relative to the member's
+    first sample: member ``m`` owns the ``episodes + 1`` entries from
+    ``episode_start[m] + m``.  ``members[m]`` is the member's
+    :class:`DeviceEpisodeBatch`, its tensors views of these; the three index arrays
+    live on the host.  Pickles as the batches it holds -- plain attributes, tensors
+    by value -- with the packed arrays stored once: the members' views are taken
+    again on loading.
+    """
+
+    # a member's tensors that are views of the packed arrays, by sample rows
+    _ROWS = ('obs_dev', 'actions_dev', 'head_dev', 'rewards_dev',
+             'step_types_dev')
+
+    def __init__(self, members, *, obs_dev, actions_dev, head_dev, rewards_dev,
+                 step_types_dev, last_obs_dev, ep_off_dev, env_info_planes,
+                 member_off, member_samples, episode_start):
+        self.members = list(members)
+        self.ep_off_dev = ep_off_dev
+        self.obs_dev = obs_dev
+        self.actions_dev = actions_dev
+        self.head_dev = head_dev
+        self.rewards_dev = rewards_dev
+        self.step_types_dev = step_types_dev
+        self.last_obs_dev = last_obs_dev
+        self.env_info_planes = dict(env_info_planes)
+        self.member_off = np.asarray(member_off, dtype=np.int64)
+        self.member_samples = np.asarray(member_samples, dtype=np.int64)
+        self.episode_start = np.asarray(episode_start, dtype=np.int64)
+        if (self.member_off.shape != (len(self.members) + 1, )
+                or self.member_samples.shape != (len(self.members), )
+                or self.episode_start.shape != self.member_off.shape):
+            raise ValueError('DevicePopulationBatch: {} members need {} offsets '
+                             'and {} sample counts'.format(
+                                 len(self.members), len(self.members) + 1,
+                                 len(self.members)))
+
+    def __len__(self):
+        return len(self.members)
+
+    def member_views(self, m):
+        """``{attribute: tensor}``: member ``m``'s views of the packed arrays."""
+        lo = int(self.member_off[m])
+        hi = lo + int(self.member_samples[m])
+        e0, e1 = int(self.episode_start[m]), int(self.episode_start[m + 1])
+        views = {}
+        for name in self._ROWS:
+            packed = getattr(self, name)
+            views[name] = None if packed is None else packed[lo:hi]
+        views['last_obs_dev'] = self.last_obs_dev[e0:e1]
+        views['ep_off_dev'] = self.ep_off_dev[e0 + m:e1 + m + 1]
+        return views
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        views = set(self.member_views(0)) if self.members else set()
+        state['members'] = [
+            (type(b), {k: v for k, v in b.__dict__.items() if k not in views})
+            for b in self.members]
+        return state
+
+    def __setstate__(self, state):
+        stored = state.pop('members')
+        self.__dict__.update(state)
+        self.members = []
+        for m, (cls, attrs) in enumerate(stored):
+            b = cls.__new__(cls)
+            b.__dict__.update(attrs)
+            b.__dict__.update(self.member_views(m))
+            self.members.append(b)
+
+
 class EpisodeStatistics:
     """What ``log_performance`` (``_functions.py:233-275``) reduces a batch of
     ``N`` episodes to, for callers that score episodes and read nothing else

@@ -109,6 +109,15 @@ def env_ref(kind, env):
     return ref
 
 
+class PackPlane(C.Structure):
+    """``ga_pack_plane``."""
+    _fields_ = [('src', ptr), ('dst', ptr), ('ld_src', c_i64),
+                ('ld_dst', c_i64), ('elem_size', c_i32), ('width', c_i32),
+                ('per_episode', c_i32), ('pad_', c_i32)]
+
+
+PACK_MAX_PLANES = 16
+
 TASK_ROUND_ROBIN, TASK_UNIFORM_RANDOM = 0, 1
 TASK_VANILLA, TASK_ADD_ONEHOT = 0, 1
 
@@ -343,6 +352,11 @@ SIGNATURES = {
                                              c_i64, c_i64, c_i64, c_f64, ptr,
                                              ptr, c_i64, ptr, ptr, ptr, ptr,
                                              ptr, ptr]),
+    'ga_member_pack_index': (c_int, [ptr, c_i64, c_i64, c_i64, c_i64, ptr, ptr,
+                                     c_i64, c_i64, ptr, ptr, ptr, ptr, ptr, ptr,
+                                     ptr, ptr]),
+    'ga_member_pack_gather': (c_int, [ptr, c_i64, ptr, c_i64, ptr, ptr, c_i64,
+                                      c_i64, ptr]),
     'ga_minibatch_range': (c_i64, [c_i64, c_i64, c_i64, c_int, c_i64,
                                    C.POINTER(c_i64), C.POINTER(c_i64)]),
     'ga_update_epoch': (c_int, [C.POINTER(UpdateArgs), ptr]),

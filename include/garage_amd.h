@@ -1079,6 +1079,74 @@ GA_API int ga_member_episode_statistics(
     int32_t* col_base, int64_t max_eps, int32_t* length, double* undiscounted,
     double* discounted, uint8_t* terminated, uint8_t* success, ga_stream_t stream);
 
+/* ---- a population's episodes packed in one pass over the rollout buffers --------
+ * EpisodeBatch.concatenate (sampler/vec_worker.py:206-219, local_sampler.py:134-166)
+ * for every member at once: what ga_pack_episodes, ga_pack_src_index and the gathers do
+ * for one member's rows, for all of them, from `progress` and `col_base` as
+ * ga_member_progress wrote them for the same tail_buf, n_cols and num_samples.  Both
+ * entries are graph-capture safe: they allocate nothing, copy nothing to the host and
+ * do not synchronise.
+ *
+ * ga_member_pack_index (two launches) writes, for every episode of member m that ended
+ * in a column < c_m, in the order (member, end column, env index) --
+ * ga_pack_episodes' inside a member, ga_member_episode_statistics' overall; a member
+ * with c_m == 0 contributes no episode:
+ *   ep_env, ep_end, ep_len  int32 [max_eps]: the GLOBAL env index, the last column and
+ *                 the length of episode e = episode_start[m] + (its rank in the
+ *                 member), episode_start[m] the episodes of the members before m
+ *   ep_off        int64 [max_eps + n_members]: member m owns the episodes_m + 1 entries
+ *                 from episode_start[m] + m, relative to the member's first sample:
+ *                 they start at 0 and end at S_m (a lone batch's ep_off)
+ *   member_samples int64 [n_members]: S_m, the steps of the member's episodes
+ *   member_off    int64 [n_members + 1]: the member's first row in the packed arrays,
+ *                 member_off[0] = 0 and member_off[m + 1] = member_off[m] + S_m rounded
+ *                 up to a multiple of 16 rows, so that every member's slice of every
+ *                 packed array (1-byte rows included) starts on a 16-byte boundary
+ *   src           int32 [max_samples]: the cell env * Tcap + column of the sample in
+ *                 row member_off[m] + ep_off[..] + j, and -1 in every other row below
+ *                 max_samples (the padding behind a member's samples and whatever lies
+ *                 behind member_off[n_members])
+ * Nothing is written past max_eps episodes or max_samples rows; S_m <= g c_m, so
+ * max_samples = sum over m of (g c_m rounded up to 16) always suffices.
+ * Refused before any launch: NULL pointers; n_members outside 1..1024; n not a
+ * multiple of n_members; n_cols outside 1..Tcap; n * Tcap >= 2^31; max_eps < 1;
+ * max_samples outside 1..2^31 - 1. */
+GA_API int ga_member_pack_index(const uint16_t* tail_buf, int64_t n, int64_t Tcap,
+                                int64_t n_cols, int64_t n_members,
+                                const int32_t* progress, const int32_t* col_base,
+                                int64_t max_eps, int64_t max_samples, int32_t* ep_env,
+                                int32_t* ep_end, int32_t* ep_len, int64_t* ep_off,
+                                int64_t* member_samples, int64_t* member_off,
+                                int32_t* src, ga_stream_t stream);
+/* One plane of the packed batch: dst[r, 0:width] = src[cell(r), 0:width], rows of
+ * `width` elements of elem_size bytes, ld_src / ld_dst elements apart.  per_episode 0:
+ * one row per packed sample, cell(r) = src[r], and a row with src[r] < 0 (padding) is
+ * written as zeros; per_episode 1: one row per episode, cell(e) = ep_env[e] * Tcap +
+ * ep_end[e], the episode's last cell (lastobs, an env_info at the episode's end). */
+typedef struct {
+  const void* src; void* dst;
+  int64_t ld_src, ld_dst;
+  int32_t elem_size;    /* 1 or 4 */
+  int32_t width;
+  int32_t per_episode;
+  int32_t pad_;
+} ga_pack_plane;
+#define GA_PACK_MAX_PLANES 16
+/* ga_member_pack_gather: every plane of the batch in ONE launch.  n_rows: the rows of
+ * `src` (every one of them is written in every per-sample plane: no byte of the packed
+ * arrays stays uninitialised; padding is where src says so, member_off is not read);
+ * n_eps: the episodes (0: no per-episode plane may be given).  4-byte planes of width
+ * >= 4 are copied in 16-byte pieces.
+ * Refused before the launch: NULL planes / src, a NULL pointer in a plane, NULL ep_env /
+ * ep_end with a per-episode plane; n_planes outside 1..16; n_rows outside 1..2^31 - 1;
+ * n_eps < 0, or 0 with a per-episode plane; Tcap outside 1..2^31 - 1; an elem_size other
+ * than 1 or 4; width < 1 or a stride below it; a 4-byte plane of width >= 4 whose width
+ * or strides are no multiple of 4 or whose pointers are not 16-byte aligned. */
+GA_API int ga_member_pack_gather(const ga_pack_plane* planes, int64_t n_planes,
+                                 const int32_t* src, int64_t n_rows,
+                                 const int32_t* ep_env, const int32_t* ep_end,
+                                 int64_t n_eps, int64_t Tcap, ga_stream_t stream);
+
 /* ---- one optimisation pass, enqueued natively --------------------------------
  * All minibatches of one epoch of VPG._train (torch/algos/vpg.py:230-293) for
  * one network: forward, fused loss + gradient seed, backward, slab reduction,

@@ -15,7 +15,11 @@ The three take turns within each repetition; the first repetition warms up.
 Prints one JSON line per row -- the median over ``reps`` of (env steps taken) /
 (wall time, ended by a device synchronise) -- then the ratios, then where the
 population call's time goes: the launches (first chunk and the rest, to their
-completion), the host checks between them and the per-member packing.
+completion), the host checks between them and the packing -- the joint pack of all
+members (``ga_member_pack_index``, ``ga_member_pack_gather``, one copy to the
+host), or with ``--per-member-pack`` one ``GpuVecWorker._pack`` per member -- and,
+for the joint pack, the gather launch alone between two HIP events with the bytes it
+moves (each packed byte read and written once, plus the index).
 
     python tools/population_rate.py --statistics [--reps 7]
 
@@ -46,6 +50,8 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--statistics', action='store_true',
                     help='time obtain_statistics beside obtain_samples')
+    ap.add_argument('--per-member-pack', action='store_true',
+                    help='joint_pack=False: one _pack per member')
     a = ap.parse_args()
     M, g, T = a.members, a.g, a.T
     n, num = M * g, g * T
@@ -61,7 +67,7 @@ def main():
     rng = np.random.RandomState(0)
     vectors = base + 0.1 * rng.randn(M, base.size).astype(np.float32)
     pop = GpuPopulationSampler(pol, env, n_members=M, max_episode_length=T,
-                               seed=1)
+                               seed=1, joint_pack=not a.per_member_pack)
     packed = pol.pack_members(vectors)
 
     def single_sampler(envs):
@@ -126,9 +132,28 @@ def main():
     # part, so the parts add up to more than the untimed call)
     parts = dict(first_launch=0.0, later_launches=0.0, host_checks=0.0,
                  packing=0.0)
+    import garage_amd.sampler as sampler_module
     w = pop._worker
     real_steps, real_pack = pop._steps, w._pack
+    real_joint, real_call = pop._pack_population, sampler_module.call
     state = dict(calls=0, last=None)
+    gather = dict(events=[], bytes=0)
+
+    def call(name, *args):
+        if name != 'ga_member_pack_gather':
+            return real_call(name, *args)
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        real_call(name, *args)
+        stop.record()
+        gather['events'].append((start, stop))
+        planes, n_planes, n_rows, n_eps = args[0], args[1], args[3], args[6]
+        for p in list(planes)[:n_planes]:
+            rows = n_eps if p.per_episode else n_rows
+            # read and written once; one index entry a row (two per episode)
+            gather['bytes'] += rows * (2 * p.width * p.elem_size
+                                       + (8 if p.per_episode else 4))
 
     def timed(key, fn, *args, **kw):
         torch.cuda.synchronize()
@@ -148,14 +173,37 @@ def main():
 
     pop._steps = steps
     w._pack = lambda *args, **kw: timed('packing', real_pack, *args, **kw)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    pop.obtain_samples(0, num, packed)
-    torch.cuda.synchronize()
-    total = time.perf_counter() - t0
-    pop._steps, w._pack = real_steps, real_pack
+    pop._pack_population = lambda *args, **kw: timed('packing', real_joint,
+                                                     *args, **kw)
+    sampler_module.call = call
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pop.obtain_samples(0, num, packed)
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+    finally:
+        pop._steps, w._pack = real_steps, real_pack
+        pop._pack_population, sampler_module.call = real_joint, real_call
     print(json.dumps(dict(breakdown_ms={k: 1e3 * v for k, v in parts.items()},
-                          total_ms=1e3 * total, launches=state['calls'])))
+                          total_ms=1e3 * total, launches=state['calls'],
+                          joint_pack=not a.per_member_pack)))
+    if gather['events']:
+        # the launch alone, over further calls (the first one above included)
+        sampler_module.call = call
+        try:
+            for r in range(a.reps):
+                pop.obtain_samples(r, num, packed)
+            torch.cuda.synchronize()
+        finally:
+            sampler_module.call = real_call
+        ms = [s.elapsed_time(e) for s, e in gather['events']]
+        per_call = gather['bytes'] / len(ms)
+        print(json.dumps(dict(
+            gather_launches=len(ms), gather_ms_median=float(np.median(ms)),
+            gather_ms_min=min(ms), gather_ms_max=max(ms),
+            gather_bytes=per_call,
+            gather_GB_per_s=per_call / (1e6 * float(np.median(ms))))))
 
 
 def statistics_mode(a, pop, packed, run_population, run_single):
