@@ -82,14 +82,30 @@ $(OUT)/host_asan_test: tests/host/update_loop_harness.cpp tests/host/no_fused_fw
 asan-env-loop: $(OUT)/env_loop_asan_test
 	$(OUT)/env_loop_asan_test
 
-$(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
+$(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp tests/host/no_rescale_in_launch.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
 	@mkdir -p $(OUT)
 	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
 	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/rollout_env_loop_harness.cpp $(CSRC)/rollout_loop.cpp \
-	  -o $@
+	  tests/host/rollout_env_loop_harness.cpp tests/host/no_rescale_in_launch.cpp \
+	  $(CSRC)/rollout_loop.cpp -o $@
 
 .PHONY: asan-env-loop
+
+# The same loop against a kernel side that rescales the actions inside the fused launch,
+# as policy_fused.hip does: a rescaled rollout is ONE launch, and three per step only
+# under ga_set_fused_env_step(0) (tests/host/).  The harness above links a kernel side
+# that does not (no_rescale_in_launch.cpp) and pins the three launches.
+asan-rescale-loop: $(OUT)/rescale_loop_asan_test
+	$(OUT)/rescale_loop_asan_test
+
+$(OUT)/rescale_loop_asan_test: tests/host/rollout_rescale_loop_harness.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
+	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  tests/host/rollout_rescale_loop_harness.cpp $(CSRC)/rollout_loop.cpp \
+	  -o $@
+
+.PHONY: asan-rescale-loop
 
 # The per-layer MLP dispatch (mlp_layers.cpp) under AddressSanitizer + UBSan with
 # recording fakes for the launches it makes; every fake checks the extent its kernel

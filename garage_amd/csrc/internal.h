@@ -122,6 +122,11 @@ int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params, const f
                               float* dacts, float* grad_slabs, int64_t slab_stride,
                               int64_t n_splits, int l_start, int fused_first,
                               hipStream_t stream);
+// policy_fused.hip: 1 when ga_policy_env_step_fused_f32 rescales the action inside its
+// launch under norm->act_low.  ga_rollout_env_steps asks before it hands such a rollout
+// to the one launch; a kernel side that answers 0 (tests/host/no_rescale_in_launch.cpp)
+// keeps the three launches per step.
+int ga_policy_env_step_rescales(void);
 // losses.hip: doubles of per-block partial sums at the front of the reduction
 // workspace (ga_reduction_workspace_doubles)
 int64_t ga_reduction_partials_doubles(void);

@@ -109,6 +109,8 @@ struct NetDev {
   int64_t w_off[8], b_off[8];
 };
 
+constexpr int ENV_STEP_RESCALE = 2;  // bit of FusedParams::env_step
+
 template <class Env>
 struct FusedParams {
   NetDev net;
@@ -116,7 +118,8 @@ struct FusedParams {
   ga_rollout::HeadDev hd;  // the step's head and rollout-buffer writes (rollout_dev.h)
   // env_step: the env's step, the NormalizedEnv statistics, the bookkeeping and the
   // reset of finished envs follow in the same launch, each env by the thread that
-  // sampled its action (rollout_dev.h: the code of env_step_record_kernel)
+  // sampled its action (rollout_dev.h: the code of env_step_record_kernel);
+  // | ENV_STEP_RESCALE: es.nm.act_low is set, the env steps on the rescaled action
   int env_step;
   ga_rollout::EnvStepArgsT<Env> es;
   // n_steps > 1 (needs env_step): the workgroup takes its envs through n_steps
@@ -374,6 +377,13 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     asm volatile("" : "+s"(off));
     return p.params + off;
   };
+  // The action rescale's bounds, scale and scratch rows wait in LDS, and its branch
+  // reads a bit of env_step, which every step reads anyway: held in SGPRs across the
+  // step loop (as a test of p.es.nm.act_low holds them) they are lane spills whose
+  // reloads every rollout pays in every step, rescale or not.  Thread 0 writes them
+  // and the env threads read them behind a step's barriers.
+  __shared__ ga_rollout::NormParams rescale;
+  if (tid == 0 && (p.env_step & ENV_STEP_RESCALE)) rescale = p.es.nm;
   float wreg[TPW][HMAX / 4];
   float bias_r[2][TPW];  // RES: hidden biases of this lane's columns
 #pragma unroll
@@ -662,8 +672,21 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
     const int64_t env = row0 + tid;
     if (env < hd.n) {
       ga_rollout::head_one(hd, head[tid], p.net.dims[L], params(), env);
-      if (p.env_step)
-        ended_len = ga_rollout::env_step_one(es, env, pre, hd.action + env * hd.lda);
+      if (p.env_step) {
+        const float* act_row = hd.action + env * hd.lda;
+        // NormalizedEnv.step (normalized_env.py:90-114): the wrapped env steps on the
+        // rescaled, clipped row, written to the scratch as the rescale launch writes
+        // it; the action buffer and act_buf keep the policy's own.  (Through memory:
+        // a register row indexed by j would spill for A up to MAX_OUT.)
+        if (p.env_step & ENV_STEP_RESCALE) {
+          float* scaled = rescale.scaled_action + env * rescale.scaled_ld;
+          ga_rollout::action_rescale_row(act_row, rescale.act_low, rescale.act_high,
+                                         rescale.expected_action_scale, p.net.dims[L],
+                                         scaled);
+          act_row = scaled;
+        }
+        ended_len = ga_rollout::env_step_one(es, env, pre, act_row);
+      }
     }
   }
   // (episode counts of the step: a wave-aggregated integer atomic; the envs of a
@@ -896,7 +919,9 @@ extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* param
 // consecutive rollout steps: every workgroup takes its 32 envs through all of them
 // (nothing couples envs within a rollout), alternating between `a->obs` and
 // `rec->next_obs` (and the raw pair of `norm`).  `a->action` is what the env is
-// stepped with.
+// stepped with -- or, with norm->act_low set, its rescaled copy in
+// norm->scaled_action, which the env thread writes (ga_build_env_step refuses missing
+// bounds or scratch and a discrete kind; none of the checks touches the device).
 static int policy_env_step(const char* who, const ga_mlp_desc* d, const float* params,
                            const ga_head_args* a, const ga_env_ref* ref,
                            const ga_record_args* rec, const ga_norm_args* norm,
@@ -909,15 +934,23 @@ static int policy_env_step(const char* who, const ga_mlp_desc* d, const float* p
     GA_REQUIRE(!a->noise || n_steps == 1, "%s: teacher-forced noise is per step", who);
     using GaEnv = std::remove_cv_t<std::remove_pointer_t<decltype(env)>>;
     ga_env_step_args_t<GaEnv> es;
-    int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs, who, &es);
+    int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs, who, &es,
+                               /*rescale_inside=*/true);
     if (rc) return rc;
     GA_REQUIRE(es.e.n == a->n, "%s: env count mismatch", who);
+    // (the kernel rescales the head's A columns)
+    GA_REQUIRE(!es.nm.act_low || a->A == ga_env_act_width(env),
+               "%s: action rescale of %d columns for an env of %d", who, a->A,
+               ga_env_act_width(env));
     GA_REQUIRE(es.p.col == a->col && es.p.col + n_steps <= es.p.Tcap,
                "%s: record columns do not match the policy's", who);
     return policy_step_launch(d, params, a, &es, n_steps, (hipStream_t)stream, n_members,
                               member_stride);
   });
 }
+
+// (internal.h: what ga_rollout_env_steps asks before it sends a rescaled rollout here)
+extern "C" int ga_policy_env_step_rescales(void) { return 1; }
 
 extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
                                             const ga_head_args* a, const ga_env_ref* ref,
@@ -1017,7 +1050,7 @@ static int policy_step_launch(const ga_mlp_desc* d, const float* params,
   p.hidden_act = d->hidden_act; p.output_act = d->output_act;
   p.layer_norm = d->layer_norm != 0;
   for (int i = 0; i < 8; ++i) p.ln_off[i] = d->ln_off[i];
-  p.env_step = es != nullptr;
+  p.env_step = es ? (es->nm.act_low ? 1 | ENV_STEP_RESCALE : 1) : 0;
   p.n_steps = (int)n_steps;
   const dim3 grid((unsigned)ga_ceil_div(a->n, ROWS));
   // n_members > 1 (ga_policy_env_step_members_f32, which checked the split): member m

@@ -584,7 +584,7 @@ static int check_env(const GaEnv* e, const char* who) {
 template <class GaEnv>
 int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
                       const float* actions, int64_t lda, const float* obs, const char* who,
-                      ga_env_step_args_t<GaEnv>* out) {
+                      ga_env_step_args_t<GaEnv>* out, bool rescale_inside) {
   int rc = check_env(env, who);
   if (rc) return rc;
   const int obs_dim = ga_env_obs_dim(env);
@@ -619,6 +619,16 @@ int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_a
       raw_obs = norm->raw_obs;
       raw_next = norm->raw_next_obs;
     }
+    if (rescale_inside && norm->act_low) {
+      // normalized_env.py:90-100 in the env thread of the caller's kernel: the scratch
+      // rows have the action rows' stride
+      GA_REQUIRE(norm->act_high && norm->scaled_action && !ga_env_discrete(env),
+                 "%s: action rescale needs bounds, scratch and a continuous action space",
+                 who);
+      nm.act_low = norm->act_low; nm.act_high = norm->act_high;
+      nm.expected_action_scale = norm->expected_action_scale;
+      nm.scaled_action = norm->scaled_action; nm.scaled_ld = lda;
+    }
   }
   out->e = ga_env_to_dev(env, a->Tcap);  // env_infos go into the [n, Tcap] buffers
   out->p = ga_record_to_dev(a); out->nm = nm;
@@ -630,7 +640,7 @@ int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_a
 #define GA_BUILD_ENV_STEP_OF(E)                                                        \
   template int ga_build_env_step<E>(const E*, const ga_record_args*, const ga_norm_args*, \
                                     const float*, int64_t, const float*, const char*,  \
-                                    ga_env_step_args_t<E>*);
+                                    ga_env_step_args_t<E>*, bool);
 GA_BUILD_ENV_STEP_OF(ga_synth_env)
 GA_BUILD_ENV_STEP_OF(ga_point_env)
 GA_BUILD_ENV_STEP_OF(ga_grid_env)
@@ -935,24 +945,15 @@ extern "C" int ga_obs_normalize_f64(int64_t n, int obs_dim, float* obs, int64_t 
 }
 
 namespace {
-// NormalizedEnv.step's action rescale (envs/normalized_env.py:90-100): fp32, one
-// rounding per numpy operation (no fused multiply-add), np.clip's comparisons (a
-// NaN stays a NaN)
+// NormalizedEnv.step's action rescale (envs/normalized_env.py:90-100) as a launch of
+// its own: one thread per env runs rollout_dev.h's action_rescale_row
 __global__ __launch_bounds__(256) void action_rescale_kernel(
     int64_t n, int A, const float* __restrict__ act, int64_t lda,
     const float* __restrict__ lb, const float* __restrict__ ub, float scale,
     float* __restrict__ out, int64_t ldo) {
-#pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n * A) return;
-  const int64_t r = i / A;
-  const int j = (int)(i % A);
-  const float a = act[r * lda + j];
-  const float lo = lb[j], hi = ub[j];
-  const float slope = (0.5f * (hi - lo)) / scale;
-  float v = lo + (a + scale) * slope;
-  v = v < lo ? lo : (v > hi ? hi : v);
-  out[r * ldo + j] = v;
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  action_rescale_row(act + r * lda, lb, ub, scale, A, out + r * ldo);
 }
 }  // namespace
 
@@ -963,7 +964,7 @@ extern "C" int ga_action_rescale_f32(int64_t n, int A, const float* actions, int
   hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(actions && low && high && out, "ga_action_rescale_f32: null pointer");
   GA_REQUIRE(n > 0 && A > 0 && lda >= A && ldo >= A, "ga_action_rescale_f32: bad sizes");
-  hipLaunchKernelGGL(action_rescale_kernel, dim3((unsigned)ga_ceil_div(n * A, 256)),
+  hipLaunchKernelGGL(action_rescale_kernel, dim3((unsigned)ga_ceil_div(n, 256)),
                      dim3(256), 0, stream, n, A, actions, lda, low, high,
                      expected_action_scale, out, ldo);
   GA_CHECK_LAUNCH("action_rescale");

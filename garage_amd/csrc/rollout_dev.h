@@ -1391,6 +1391,24 @@ static __device__ __forceinline__ void record_counts(const RecordParams& p, int 
   }
 }
 
+// NormalizedEnv.step's action rescale of one env (envs/normalized_env.py:90-100): the
+// A columns of `act` from [-scale, scale] to [lb_j, ub_j], clipped, into `out`.  fp32,
+// one rounding per numpy operation (no fused multiply-add), np.clip's comparisons (a
+// NaN stays a NaN).  The rescale launch and the fused rollout step both call it.
+static __device__ __forceinline__ void action_rescale_row(const float* act, const float* lb,
+                                                          const float* ub, float scale,
+                                                          int A, float* out) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < A; ++j) {
+    const float a = act[j];
+    const float lo = lb[j], hi = ub[j];
+    const float slope = (0.5f * (hi - lo)) / scale;
+    float v = lo + (a + scale) * slope;
+    v = v < lo ? lo : (v > hi ? hi : v);
+    out[j] = v;
+  }
+}
+
 struct NormParams {
   int norm_obs, norm_reward, scale_reward;
   double* obs_mean;   // [n, obs_dim]
@@ -1399,6 +1417,13 @@ struct NormParams {
   double* rew_mean;   // [n]
   double* rew_var;
   double rew_alpha, rew_scale;
+  // the action rescale inside the fused rollout step (null act_low: none; always null
+  // for ga_env_step_record, which steps on the actions it is handed)
+  const float* act_low;   // [act_dim]
+  const float* act_high;
+  float expected_action_scale;
+  float* scaled_action;   // [n, scaled_ld] what the wrapped env steps on
+  int64_t scaled_ld;
 };
 
 // env step -> (NormalizedEnv statistics + normalisation) -> bookkeeping -> reset of
@@ -1548,8 +1573,11 @@ using ga_env_step_args_t =
     ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;
 
 // Validated conversion of the C-ABI arguments of the rollout step
-// (include/garage_amd.h) into EnvStepArgsT; rollout.hip instantiates it per env kind
+// (include/garage_amd.h) into EnvStepArgsT; rollout.hip instantiates it per env kind.
+// rescale_inside: the caller's kernel rescales the policy's action itself when
+// norm->act_low is set (the fused rollout step); otherwise the bounds are not read and
+// the env steps on `actions` as they are (ga_env_step_record).
 template <class GaEnv>
 int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
                       const float* actions, int64_t lda, const float* obs, const char* who,
-                      ga_env_step_args_t<GaEnv>* out);
+                      ga_env_step_args_t<GaEnv>* out, bool rescale_inside = false);

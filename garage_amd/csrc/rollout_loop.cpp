@@ -13,8 +13,9 @@
 #include "internal.h"
 
 // 1 (default): policy step and env step of a rollout step in ONE launch
-// (ga_policy_env_step_fused_f32) unless the actions are rescaled in between;
-// 0, or GARAGE_AMD_FUSED_ENV_STEP=0 in the environment: two launches
+// (ga_policy_env_step_fused_f32), NormalizedEnv's action rescale included;
+// 0, or GARAGE_AMD_FUSED_ENV_STEP=0 in the environment: two launches, three with the
+// rescale
 static int g_fused_env_step = -1;
 extern "C" int ga_set_fused_env_step(int on) {
   g_fused_env_step = on != 0;
@@ -73,9 +74,14 @@ extern "C" int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params
   ga_record_args r = *rec;
   ga_norm_args nm;
   if (norm) nm = *norm;
-  if (fused_env_step_on() && !(norm && nm.act_low) && !head->noise && n_steps >= 1) {
+  // (the one launch rescales the actions itself where the kernel side says it does:
+  // policy_fused.hip always, the recording fakes of the loop's first harness never)
+  const bool rescale_in_launch = !(norm && nm.act_low) || ga_policy_env_step_rescales();
+  if (fused_env_step_on() && rescale_in_launch && !head->noise && n_steps >= 1) {
     // every rollout step -- policy, env, bookkeeping, reset of the finished envs --
     // in ONE launch for all n_steps: a workgroup owns its envs for the whole rollout
+    // (with nm.act_low set the env thread rescales its action row into
+    // nm.scaled_action, as ga_action_rescale_f32 does below)
     r.col = h.col;
     r.next_obs = nxt;
     h.obs = cur;

@@ -499,7 +499,12 @@ typedef struct ga_norm_args {
   const float* raw_obs;  /* [n, ldo] the wrapped env's current observations */
   float* raw_next_obs;   /* [n, ldo] where its next observations go */
   /* action rescale (normalized_env.py:90-100) when act_low != NULL: the wrapped env
-   * steps on scaled_action (scratch [n, lda]) = ga_action_rescale_f32(policy action) */
+   * steps on scaled_action (scratch [n, lda], lda the action rows' stride) =
+   * ga_action_rescale_f32(policy action); the action buffer and the rollout buffers
+   * keep the policy's own.  Read by ga_policy_env_step_fused_f32 and
+   * ga_rollout_env_steps, which rescale (columns j < act_dim of the scratch rows are
+   * written, nothing else); ga_env_step_record does not read these four fields: it
+   * steps on the actions it is handed. */
   const float* act_low;  /* [act_dim] */
   const float* act_high;
   float expected_action_scale;
@@ -967,7 +972,13 @@ GA_API int ga_env_step_record(const ga_env_ref* env, const ga_record_args* rec,
  * through all of them (envs do not interact within a rollout), alternating between
  * the buffers head->obs / rec->next_obs (norm: raw_obs / raw_next_obs); columns
  * head->col .. head->col + n_steps - 1, Philox counters head->step + s.  Device
- * noise only (head->noise must be null for n_steps > 1). */
+ * noise only (head->noise must be null for n_steps > 1).
+ * With norm->act_low set the thread that sampled an env's action also rescales it
+ * (ga_action_rescale_f32's arithmetic, the same function) into its row of
+ * norm->scaled_action and steps the env on that row.  Refused before any device call:
+ * act_low without act_high or without scaled_action, or with an env kind whose action
+ * is a class index ("action rescale needs bounds, scratch and a continuous action
+ * space"); a head of another width than the env's action. */
 GA_API int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
                                         const ga_head_args* head, const ga_env_ref* env,
                                         const ga_record_args* rec, const ga_norm_args* norm,
@@ -981,7 +992,8 @@ GA_API int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* param
  * head->n not a multiple of n_members; with n_members > 1, g not a multiple of the 16
  * envs a workgroup owns; member_stride not a multiple of 4 or smaller than the
  * vector `d` describes; 2^31 floats or more up to the last member's end; head->noise;
- * norm->act_low (the action rescale is its own launch); a network the fused step does
+ * norm->act_low (a population is not rescaled: the refusal stands, with its wording,
+ * though the kernel could); a network the fused step does
  * not take.  n_members == 1 is
  * ga_policy_env_step_fused_f32.  ga_launch_count(13) counts every call with
  * n_steps > 1 once. */
@@ -991,8 +1003,9 @@ GA_API int ga_policy_env_step_members_f32(const ga_mlp_desc* d, const float* par
                                           const ga_norm_args* norm, int64_t n_steps,
                                           int64_t n_members, int64_t member_stride,
                                           ga_stream_t stream);
-/* 1 (default): ga_rollout_env_steps takes that launch (unless actions are
- * rescaled between policy and env); 0: policy step and env step as two launches. */
+/* 1 (default): ga_rollout_env_steps takes that launch, the action rescale of
+ * norm->act_low included; 0: policy step and env step as two launches, with
+ * ga_action_rescale_f32 as a third between them under norm->act_low. */
 GA_API int ga_set_fused_env_step(int on);
 /* n_steps consecutive vectorised steps (fused policy step, env step,
  * bookkeeping, reset of finished envs) starting at head->col / head->step,
@@ -1001,7 +1014,9 @@ GA_API int ga_set_fused_env_step(int on);
  * VecWorker.rollout (sampler/default_worker.py:176-186 + vec_worker.py:176-204)
  * enqueued natively.  With norm != NULL (NormalizedEnv around the env)
  * obs_a / obs_b hold the normalised observations and raw_a / raw_b, alternating
- * the same way, the env's own. */
+ * the same way, the env's own; with norm->act_low the env steps on the rescaled
+ * actions (norm->scaled_action) in either form of the loop, bit for bit the same.
+ * One launch for all n_steps unless ga_set_fused_env_step(0) or head->noise. */
 GA_API int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params,
                                 const ga_head_args* head, const ga_env_ref* env,
                                 const ga_record_args* rec, float* obs_a, float* obs_b,

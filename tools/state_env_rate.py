@@ -24,14 +24,16 @@ exactly T steps, so a call is one launch), ``synthetic`` (the same, 3
 observations and 1 unbounded action, with a Philox draw for an env step:
 ``pendulum / synthetic`` is what the dynamics cost inside the launch) and
 ``pendulum_normalized`` (``normalize`` rescales the policy's action to the
-torque bounds in a launch of its own, so the rollout takes three launches per
-step: ``pendulum_normalized / pendulum`` is what that path costs).
+torque bounds; the env thread of the one launch does it, so a call stays one
+launch: ``pendulum_normalized / pendulum`` is what the rescale costs there).
 
 ``double_pendulum``: ``double_pendulum`` (under the untrained policy an episode
 falls within 3 .. 16 steps, so the first T steps are one launch with the resets
 inside it and the few steps that the in-flight episodes still lack are driven
 from Python with a host check each), ``synthetic`` (11 observations, every
-episode exactly T steps: a call is one launch) and ``pendulum`` (the same).
+episode exactly T steps: a call is one launch), ``pendulum`` (the same) and
+``double_pendulum_normalized`` (``normalize`` around the batch: the force is
+rescaled inside the launch).
 
 ``acrobot`` / ``mountain_car`` (the discrete variant): the kind itself (under
 the untrained policy no episode reaches its goal within T steps, so every
@@ -109,18 +111,26 @@ KINDS = {
               'synthetic': _synthetic(3, 1),
               'pendulum_normalized': _batch('PendulumVecEnv',
                                             normalized=True)},
-        launch=(),
+        launch=('pendulum', 'synthetic', 'pendulum_normalized'),
         ratios={'pendulum_over_synthetic': ('pendulum', 'synthetic'),
                 'pendulum_normalized_over_pendulum':
-                    ('pendulum_normalized', 'pendulum')}),
+                    ('pendulum_normalized', 'pendulum'),
+                'launch_pendulum_over_synthetic':
+                    ('pendulum_launch', 'synthetic_launch'),
+                'launch_pendulum_normalized_over_pendulum':
+                    ('pendulum_normalized_launch', 'pendulum_launch')}),
     'double_pendulum': dict(
         T=200, reps=15, policy='GaussianMLPPolicy',
         rows={'double_pendulum': _batch('DoublePendulumVecEnv'),
               'synthetic': _synthetic(11, 1),
-              'pendulum': _batch('PendulumVecEnv')},
+              'pendulum': _batch('PendulumVecEnv'),
+              'double_pendulum_normalized': _batch('DoublePendulumVecEnv',
+                                                   normalized=True)},
         launch=('double_pendulum', 'synthetic'),
         ratios={'double_pendulum_over_synthetic':
                     ('double_pendulum', 'synthetic'),
+                'double_pendulum_normalized_over_double_pendulum':
+                    ('double_pendulum_normalized', 'double_pendulum'),
                 'double_pendulum_over_pendulum':
                     ('double_pendulum', 'pendulum'),
                 'launch_double_pendulum_over_synthetic':
