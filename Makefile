@@ -59,131 +59,75 @@ slp-variant:
 	rm -rf $(OUT)/variants/slp
 
 clean:
-	rm -rf $(OUT)/*.o $(OUT)/*.so $(OUT)/mfma_peak $(OUT)/mfma_valu_overlap $(OUT)/mfma_valu_hazard $(OUT)/mfma_rounding $(OUT)/variants
+	rm -rf $(OUT)/*.o $(OUT)/*.so $(OUT)/asan $(OUT)/*_asan_test $(OUT)/mfma_peak $(OUT)/mfma_valu_overlap $(OUT)/mfma_valu_hazard $(OUT)/mfma_rounding $(OUT)/variants
 
 .PHONY: all clean mfma-peak mfma-tools slp-variant
 
-# Host-side epoch loops under AddressSanitizer + UBSan on the CPU, with every kernel
-# entry point replaced by a recording fake (tests/host/).
+# Host-side C++ under AddressSanitizer + UBSan on the CPU (tests/host/): a harness program
+# is one translation unit of tests/host/ -- recording fakes of every kernel entry point
+# and HIP call the product source makes, and the checks -- linked with that product
+# source.  One line per program: binary, harness source, product source.
+ASAN_PROGRAMS := \
+  host_asan_test:update_loop_harness:update \
+  rollout_asan_test:rollout_loop_harness:rollout_loop \
+  mlp_layers_asan_test:mlp_layers_harness:mlp_layers \
+  update_members_asan_test:update_members_harness:update_members \
+  member_pack_asan_test:member_pack_harness:member_pack_host
+ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
+
+# (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
+# header dependencies come from the compiler)
+$(OUT)/asan/%.o: %.cpp
+	@mkdir -p $(@D)
+	$(ASAN_CXX) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
+	  -MMD -MP -c $< -o $@
+
+define asan_program
+$(OUT)/$(1): $(OUT)/asan/tests/host/$(2).o $(OUT)/asan/$(CSRC)/$(3).o
+	$$(ASAN_CXX) $$^ -o $$@
+-include $(OUT)/asan/tests/host/$(2).d $(OUT)/asan/$(CSRC)/$(3).d
+endef
+$(foreach p,$(ASAN_PROGRAMS),$(eval $(call asan_program,$(word 1,$(subst :, ,$(p))),$(word 2,$(subst :, ,$(p))),$(word 3,$(subst :, ,$(p))))))
+
+# The epoch loops (update.cpp), three suites of one program: the loops' own arithmetic;
+# fused_step's slab ranges for the data-gradient launch and the optimizer launch's
+# pre-summed regions; fused_step's choice between the fused forward + data-gradient
+# launch and the two launches (ga_set_fused_fwd_dgrad).
 asan-host: $(OUT)/host_asan_test
-	$(OUT)/host_asan_test
+	$(OUT)/host_asan_test loops
+asan-slab-sum: $(OUT)/host_asan_test
+	$(OUT)/host_asan_test slab-sum
+asan-fwd-dgrad: $(OUT)/host_asan_test
+	$(OUT)/host_asan_test fwd-dgrad
 
-$(OUT)/host_asan_test: tests/host/update_loop_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/update_loop_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp \
-	  -o $@
+# ga_rollout_env_steps' host loop (rollout_loop.cpp), two suites of one program: against a
+# kernel side whose fused launch does not rescale the actions (three launches per step of
+# a rescaled rollout), and against one that does, as policy_fused.hip (ONE launch, and
+# three per step only under ga_set_fused_env_step(0)).
+asan-env-loop: $(OUT)/rollout_asan_test
+	$(OUT)/rollout_asan_test env-loop
+asan-rescale-loop: $(OUT)/rollout_asan_test
+	$(OUT)/rollout_asan_test rescale-loop
 
-.PHONY: asan-host
-
-# ga_rollout_env_steps' host loop (rollout_loop.cpp) under AddressSanitizer +
-# UBSan with recording fakes for the kernels it launches (tests/host/).
-asan-env-loop: $(OUT)/env_loop_asan_test
-	$(OUT)/env_loop_asan_test
-
-$(OUT)/env_loop_asan_test: tests/host/rollout_env_loop_harness.cpp tests/host/no_rescale_in_launch.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/rollout_env_loop_harness.cpp tests/host/no_rescale_in_launch.cpp \
-	  $(CSRC)/rollout_loop.cpp -o $@
-
-.PHONY: asan-env-loop
-
-# The same loop against a kernel side that rescales the actions inside the fused launch,
-# as policy_fused.hip does: a rescaled rollout is ONE launch, and three per step only
-# under ga_set_fused_env_step(0) (tests/host/).  The harness above links a kernel side
-# that does not (no_rescale_in_launch.cpp) and pins the three launches.
-asan-rescale-loop: $(OUT)/rescale_loop_asan_test
-	$(OUT)/rescale_loop_asan_test
-
-$(OUT)/rescale_loop_asan_test: tests/host/rollout_rescale_loop_harness.cpp $(CSRC)/rollout_loop.cpp $(CSRC)/internal.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/rollout_rescale_loop_harness.cpp $(CSRC)/rollout_loop.cpp \
-	  -o $@
-
-.PHONY: asan-rescale-loop
-
-# The per-layer MLP dispatch (mlp_layers.cpp) under AddressSanitizer + UBSan with
-# recording fakes for the launches it makes; every fake checks the extent its kernel
-# would reach against the exactly-sized buffer the pointer came from (tests/host/).
+# The per-layer MLP dispatch (mlp_layers.cpp): every fake checks the extent its kernel
+# would reach against the exactly-sized buffer the pointer came from.
 asan-mlp: $(OUT)/mlp_layers_asan_test
 	$(OUT)/mlp_layers_asan_test
 
-$(OUT)/mlp_layers_asan_test: tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layers.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/fused_train.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/mlp_layers_harness.cpp $(CSRC)/mlp_layers.cpp \
-	  -o $@
-
-.PHONY: asan-mlp
-
-# fused_step's slab ranges for the data-gradient launch and the optimizer launch's
-# pre-summed regions (update.cpp) under AddressSanitizer + UBSan, with fakes that walk
-# the ranges inside an exactly-sized slab workspace (tests/host/).
-asan-slab-sum: $(OUT)/slab_sum_asan_test
-	$(OUT)/slab_sum_asan_test
-
-$(OUT)/slab_sum_asan_test: tests/host/slab_sum_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/slab_sum_harness.cpp tests/host/no_fused_fwd_dgrad.cpp $(CSRC)/update.cpp \
-	  -o $@
-
-.PHONY: asan-slab-sum
-
-# fused_step's choice between the fused forward + data-gradient launch and the two
-# launches (update.cpp, ga_set_fused_fwd_dgrad) under AddressSanitizer + UBSan: the order
-# of the launches on a stream, no slab ranges and no pre-summed regions with the fused
-# launch, the old sequence wherever it does not apply (tests/host/).  The two harnesses
-# above link a kernel side WITHOUT the fused instantiation (no_fused_fwd_dgrad.cpp) and
-# pin the two-launch sequence.
-asan-fwd-dgrad: $(OUT)/fused_fwd_dgrad_asan_test
-	$(OUT)/fused_fwd_dgrad_asan_test
-
-$(OUT)/fused_fwd_dgrad_asan_test: tests/host/fused_fwd_dgrad_harness.cpp $(CSRC)/update.cpp $(CSRC)/internal.h $(CSRC)/small_step.h $(CSRC)/fused_train.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/fused_fwd_dgrad_harness.cpp $(CSRC)/update.cpp \
-	  -o $@
-
-.PHONY: asan-fwd-dgrad
-
-# The population's epoch loop (update_members.cpp) under AddressSanitizer + UBSan with
-# recording fakes for its two launches and the HIP calls it makes: which ids form which
-# member's step, which members are active in which step, the Adam table, the launch
-# count of a pass, the tables' exact sizes, nothing launched after a refusal
-# (tests/host/).
+# The population's epoch loop (update_members.cpp): which ids form which member's step,
+# which members are active in which step, the Adam table, the launch count of a pass, the
+# tables' exact sizes, nothing launched after a refusal.
 asan-members: $(OUT)/update_members_asan_test
 	$(OUT)/update_members_asan_test
 
-$(OUT)/update_members_asan_test: tests/host/update_members_harness.cpp $(CSRC)/update_members.cpp $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/members_step.h $(CSRC)/fused_train.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/update_members_harness.cpp $(CSRC)/update_members.cpp \
-	  -o $@
-
-.PHONY: asan-members
-
-# The joint pack's argument checks, plane table and grids (member_pack_host.cpp) under
-# AddressSanitizer + UBSan with recording fakes for its three launches: every refusal
-# precedes the first launch, the table's paths, units and rows, the grids' bounds
-# (tests/host/).
+# The joint pack's argument checks, plane table and grids (member_pack_host.cpp): every
+# refusal precedes the first launch, the table's paths, units and rows, the grids' bounds.
 asan-member-pack: $(OUT)/member_pack_asan_test
 	$(OUT)/member_pack_asan_test
 
-$(OUT)/member_pack_asan_test: tests/host/member_pack_harness.cpp $(CSRC)/member_pack_host.cpp $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/member_pack.h include/garage_amd.h
-	@mkdir -p $(OUT)
-	g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer \
-	  -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function \
-	  tests/host/member_pack_harness.cpp $(CSRC)/member_pack_host.cpp \
-	  -o $@
+# everything above; the programs with suites run all of them in one process
+asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
+	set -e; for t in $^; do ./$$t; done
 
-.PHONY: asan-member-pack
+.PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
+  asan-members asan-member-pack asan-all

@@ -6,39 +6,9 @@
 // trips the sanitizer.  The checks are about the host's own work: every refusal precedes
 // the first launch, the plane table (path, units, rows), the grids' bounds, the
 // launches of a pack.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "../../include/garage_amd.h"
 #include "../../garage_amd/csrc/internal.h"
 #include "../../garage_amd/csrc/member_pack.h"
-
-static std::string g_error;
-static int g_fail = 0;
-
-#define CHECK(cond)                                                      \
-  do {                                                                   \
-    if (!(cond)) {                                                       \
-      printf("CHECK failed at line %d: %s\n", __LINE__, #cond);          \
-      ++g_fail;                                                          \
-    }                                                                    \
-  } while (0)
-
-void ga_set_error(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-}
+#include "harness.h"
 
 // ---- what the fakes record -----------------------------------------------------
 static std::vector<GaPackIndexArgs> g_episodes, g_src;
@@ -161,10 +131,10 @@ static void index_refused(const char* what, F&& spoil) {
   c.alloc();
   spoil(c);
   const int rc = c.run();
-  if (!(rc < 0 && !g_error.empty() && g_episodes.empty() && g_src.empty())) {
-    printf("index not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
-    ++g_fail;
-  }
+  const bool refused = rc < 0 && !g_error.empty() && g_episodes.empty() && g_src.empty();
+  if (!refused)
+    fprintf(stderr, "index not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
+  CHECK(refused);
 }
 
 // ---- the gather ----------------------------------------------------------------------
@@ -251,10 +221,10 @@ static void gather_refused(const char* what, F&& spoil) {
   g.index();
   spoil(g);
   const int rc = g.run();
-  if (!(rc < 0 && !g_error.empty() && g_tables.empty())) {
-    printf("gather not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
-    ++g_fail;
-  }
+  const bool refused = rc < 0 && !g_error.empty() && g_tables.empty();
+  if (!refused)
+    fprintf(stderr, "gather not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
+  CHECK(refused);
 }
 
 int main() {
@@ -337,10 +307,5 @@ int main() {
     g.planes[5].dst = static_cast<char*>(g.planes[5].dst) + 8;
   });
   reset();
-  if (g_fail) {
-    printf("%d check(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("member pack ok\n");
-  return 0;
+  return finish("member pack ok");
 }

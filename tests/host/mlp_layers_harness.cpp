@@ -11,39 +11,10 @@
 // garage_amd/engine.py builds them), which kernel a layer takes by default and with
 // each developer switch flipped, and that ga_wgrad_mid and
 // ga_mlp_backward_range_f32 describe the middle layer's weight gradient alike.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "../../include/garage_amd.h"
 #include "../../garage_amd/csrc/fused_train.h"
 #include "../../garage_amd/csrc/gemm_params.h"
 #include "../../garage_amd/csrc/internal.h"
-
-static std::string g_error;
-void ga_set_error(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-}
-
-static int g_failed = 0;
-#define CHECK(cond)                                                       \
-  do {                                                                    \
-    if (!(cond)) {                                                        \
-      fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-      ++g_failed;                                                         \
-    }                                                                     \
-  } while (0)
+#include "harness.h"
 
 // ---- "device" buffers: exactly-sized heap blocks, known to the fakes -------------
 struct Region {
@@ -131,7 +102,7 @@ static std::vector<std::string> kinds() {
   for (auto& c : g_calls) k.push_back(c.kind);
   return k;
 }
-static int count(const char* kind) {
+static int calls_of(const char* kind) {
   int n = 0;
   for (auto& c : g_calls) n += c.kind == kind;
   return n;
@@ -140,7 +111,8 @@ static int count(const char* kind) {
 // what the fakes answer (0 launched, 1 shape not taken)
 static int g_head_answer = 0, g_skinny_fwd_answer = 0, g_skinny_wgrad_answer = 0;
 static int g_skinny_wgrad_refuse_dz = 0;
-static int g_eval_ok = 1, g_step_fused_ok = 1;
+// (ga_policy_step_fused_supported answers g_policy_step_fused_ok: harness.h)
+static int g_eval_ok = 1;
 
 static void gemm_extents(const GemmParams& p, int a_kc, int b_kc, int splits) {
   if (p.k_per_split % BK != 0 || (int64_t)p.k_per_split * splits < p.K || p.M < 1 ||
@@ -295,7 +267,6 @@ int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t* idx, int64
   reach_f(out, (M - 1) * ldo + dims[3], "eval out");
   return 0;
 }
-int ga_policy_step_fused_supported(const ga_mlp_desc*) { return g_step_fused_ok; }
 int ga_mlp_forward_fused_f32(const ga_mlp_desc*, const float*, const float*, int64_t,
                              const int32_t*, int64_t, float*, float* out, int64_t,
                              ga_stream_t) {
@@ -423,7 +394,7 @@ static void reset_switches() {
   ga_set_skinny_kernels(1);
   g_head_answer = g_skinny_fwd_answer = g_skinny_wgrad_answer = 0;
   g_skinny_wgrad_refuse_dz = 0;
-  g_eval_ok = g_step_fused_ok = 1;
+  g_eval_ok = g_policy_step_fused_ok = 1;
 }
 
 int main() {
@@ -453,8 +424,8 @@ int main() {
             for (int l = 1; l < n->L; ++l) CHECK(c.backward_range(l, 1) == 0);
             CHECK(c.jvp() == 0);
             CHECK(!g_calls.empty());
-            CHECK(count("skinny_fwd") + count("skinny_wgrad") + count("skinny_wgrad+dz") +
-                      count("skinny_dgrad") + count("gemm_head") == 0 || !tiles_only);
+            CHECK(calls_of("skinny_fwd") + calls_of("skinny_wgrad") + calls_of("skinny_wgrad+dz") +
+                      calls_of("skinny_dgrad") + calls_of("gemm_head") == 0 || !tiles_only);
           }
   }
   CHECK(g_extent_errors == 0);
@@ -527,17 +498,17 @@ int main() {
     Case cl(nln, 70, false, 1);  // never with layer_norm
     g_calls.clear();
     CHECK(cl.forward() == 0);
-    CHECK(count("gemm_head") == 0);
+    CHECK(calls_of("gemm_head") == 0);
     reset_switches();
     // the whole forward in one launch, on request
     ga_set_fused_forward(1);
     g_calls.clear();
     CHECK(c.forward() == 0);
     CHECK((kinds() == Kinds{"fused_fwd"}));
-    g_step_fused_ok = 0;
+    g_policy_step_fused_ok = 0;
     g_calls.clear();
     CHECK(c.forward() == 0);
-    CHECK(count("fused_fwd") == 0 && g_calls.size() == 3);
+    CHECK(calls_of("fused_fwd") == 0 && g_calls.size() == 3);
     reset_switches();
     // acts == NULL: the outputs-only forward when supported, else an error
     g_calls.clear();
@@ -800,10 +771,7 @@ int main() {
     ++g_failed;
   }
 
-  if (g_failed || g_extent_errors) {
-    fprintf(stderr, "%d check(s) failed, %d extent error(s)\n", g_failed, g_extent_errors);
-    return 1;
-  }
-  printf("mlp layers ok\n");
-  return 0;
+  if (g_extent_errors) fprintf(stderr, "%d extent error(s)\n", g_extent_errors);
+  CHECK(g_extent_errors == 0);
+  return finish("mlp layers ok");
 }

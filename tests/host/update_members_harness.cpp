@@ -8,40 +8,11 @@
 // loop's own arithmetic: which ids form member m's step k, which members are active in
 // which step, the Adam table, the launch count of a pass, the tables' sizes, and that
 // nothing is launched after a refusal.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "../../include/garage_amd.h"
 #include "../../garage_amd/csrc/fused_train.h"
 #include "../../garage_amd/csrc/internal.h"
 #include "../../garage_amd/csrc/members_step.h"
-
-static std::string g_error;
-static int g_fail = 0;
-
-#define CHECK(cond)                                                      \
-  do {                                                                   \
-    if (!(cond)) {                                                       \
-      printf("CHECK failed at line %d: %s\n", __LINE__, #cond);          \
-      ++g_fail;                                                          \
-    }                                                                    \
-  } while (0)
-
-void ga_set_error(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-}
+#include "harness.h"
+#include "shape_rules.h"
 
 // ---- what the fakes record -----------------------------------------------------
 struct StepRecord {
@@ -51,55 +22,11 @@ struct StepRecord {
   std::vector<long long> id_sum;  // ... and the sum of their ids
 };
 static std::vector<StepRecord> g_train, g_reduce;
-static std::vector<size_t> g_host_allocs, g_dev_allocs, g_copies;
-static int g_events_recorded = 0;
 // the host's view of the pass under test (for the reduce fake's Adam check)
 static const ga_update_members_args* g_args = nullptr;
 
+// ---- kernel-side fakes (the shape rules: shape_rules.h) ----------------------------------
 extern "C" {
-// ---- HIP runtime fakes -----------------------------------------------------------
-hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
-  g_host_allocs.push_back(bytes);
-  *p = malloc(bytes);
-  return hipSuccess;
-}
-hipError_t hipMalloc(void** p, size_t bytes) {
-  g_dev_allocs.push_back(bytes);
-  *p = malloc(bytes);
-  return hipSuccess;
-}
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind,
-                          hipStream_t) {
-  g_copies.push_back(bytes);
-  memcpy(dst, src, bytes);
-  return hipSuccess;
-}
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
-  static char slots[64];
-  static int next = 0;
-  *e = (hipEvent_t)&slots[next++ % 64];
-  return hipSuccess;
-}
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { ++g_events_recorded; return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static int g_device = 0;
-hipError_t hipGetDevice(int* d) { *d = g_device; return hipSuccess; }
-
-// ---- kernel-side fakes -------------------------------------------------------------
-int64_t ga_fused_tiles(int64_t M) { return (M + 63) / 64; }
-int ga_narrow_step_supported(int n_layers, const int* dims) {
-  return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&
-         dims[0] >= 1 && dims[0] <= 32 && dims[3] >= 1 && dims[3] <= 8;
-}
-int64_t ga_narrow_step_stride(int in_w, int H) {
-  const int64_t ld0 = (in_w + 3) & ~3;
-  return (int64_t)H * ld0 + H + (int64_t)H * H + H + 8 * (int64_t)H + 8;
-}
-
 static int64_t rows_of(const GaMemberDev& m, int64_t mb, int64_t k) {
   if (k >= m.n_steps) return 0;
   return k == m.n_steps - 1 ? m.last_M : mb;
@@ -219,6 +146,7 @@ static void reset() {
   g_train.clear(); g_reduce.clear();
   g_host_allocs.clear(); g_dev_allocs.clear(); g_copies.clear();
   g_events_recorded = 0;
+  g_log.clear();
   g_error.clear();
 }
 
@@ -287,11 +215,10 @@ static void check_refused(const char* what, F&& spoil) {
   const ga_update_members_args* args = &p.a;
   spoil(p, &args);
   const int rc = ga_update_epoch_members(args, nullptr);
-  if (!(rc < 0 && !g_error.empty() && g_train.empty() && g_reduce.empty() &&
-        g_copies.empty())) {
-    printf("not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
-    ++g_fail;
-  }
+  const bool refused = rc < 0 && !g_error.empty() && g_train.empty() && g_reduce.empty() &&
+                       g_copies.empty();
+  if (!refused) fprintf(stderr, "not refused: %s (rc %d, '%s')\n", what, rc, g_error.c_str());
+  CHECK(refused);
 }
 
 // A slot is allocated to grow and when the device changes, never to shrink: eight
@@ -370,10 +297,5 @@ int main() {
   check_refused("algo 2", [](Pass& p, Args) { p.a.algo = 2; });
   check_refused("step0 < 0", [](Pass& p, Args) { p.mem[0].step0 = -1; });
   reset();
-  if (g_fail) {
-    printf("%d check(s) failed\n", g_fail);
-    return 1;
-  }
-  printf("members loop ok\n");
-  return 0;
+  return finish("members loop ok");
 }

@@ -101,7 +101,7 @@ def test_product_never_imports_the_oracle():
 def test_host_loops_under_address_sanitizer():
     """``make asan-host``: the C++ epoch loops (update.cpp) compiled with ``-fsanitize=address,undefined`` for the CPU
     and run against recording fakes of every kernel entry point
-    (tests/host/update_loop_harness.cpp): minibatch ranges, the data-parallel even
+    (tests/host/update_loop_harness.cpp, suite loops): minibatch ranges, the data-parallel even
     split and per-step scales, phase 1, the interleaving of two passes, argument
     errors, the fused step's scratch layout and regions (the rollout loop has its own
     harness, ``make asan-env-loop``).  GPU sanitizers are not available on this pool."""

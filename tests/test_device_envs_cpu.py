@@ -332,7 +332,7 @@ def test_fixtures_regenerate_identically_from_the_reference():
 def test_env_rollout_loop_under_address_sanitizer():
     """``make asan-env-loop``: ga_rollout_env_steps' host loop compiled with
     ``-fsanitize=address,undefined`` against recording fakes of the kernels
-    (tests/host/rollout_env_loop_harness.cpp): argument errors, the one-launch
+    (tests/host/rollout_loop_harness.cpp, suite env-loop): argument errors, the one-launch
     rollout per env kind (the synthetic env included), the per-step buffer
     ping-pong and the action rescale."""
     out = subprocess.run(['make', '-C', ROOT, 'asan-env-loop'],

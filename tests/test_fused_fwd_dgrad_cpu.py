@@ -10,7 +10,7 @@ def test_launch_sequence_of_the_fused_forward_and_data_gradient_under_address_sa
     """``make asan-fwd-dgrad``: ``fused_step`` / ``run_minibatch_fused`` (update.cpp)
     compiled with ``-fsanitize=address,undefined`` for the CPU and run against fakes of
     every launch, with a kernel side that has the fused instantiation
-    (tests/host/fused_fwd_dgrad_harness.cpp).  A step of one network with two hidden
+    (tests/host/update_loop_harness.cpp, suite fwd-dgrad).  A step of one network with two hidden
     layers of the same width and a first layer the kernel computes is exactly: fused
     launch, middle-layer weight-gradient GEMM, optimizer launch, on one stream; the
     fused launch's two descriptors are one step's and carry no slab ranges; the

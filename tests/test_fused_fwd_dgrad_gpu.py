@@ -21,7 +21,7 @@ M     splits  tiles  what it exercises
 
 Every case trains a policy and a value function (head width 1).  The fused forward has
 tanh hidden layers only, so there is no case with another activation.  Which steps take
-the fused launch is pinned on the CPU (tests/host/fused_fwd_dgrad_harness.cpp).
+the fused launch is pinned on the CPU (tests/host/update_loop_harness.cpp, suite fwd-dgrad).
 """
 import numpy as np
 import pytest

@@ -74,7 +74,7 @@ def test_rescaled_rollout_loop_under_address_sanitizer():
     """``make asan-rescale-loop``: ga_rollout_env_steps' host loop compiled with
     ``-fsanitize=address,undefined`` against recording fakes of a kernel side that
     rescales inside the fused launch, as the library's does
-    (tests/host/rollout_rescale_loop_harness.cpp): one launch for a rescaled
+    (tests/host/rollout_loop_harness.cpp, suite rescale-loop): one launch for a rescaled
     rollout, three per step with fusion off or teacher-forced noise, the
     refusals and their order."""
     out = subprocess.run(['make', '-C', ROOT, 'asan-rescale-loop'],

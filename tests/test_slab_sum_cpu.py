@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_slab_ranges_of_the_fused_step_under_address_sanitizer():
     """``make asan-slab-sum``: ``fused_step`` (update.cpp) compiled with
     ``-fsanitize=address,undefined`` for the CPU and run against fakes of every launch
-    (tests/host/slab_sum_harness.cpp).  The data-gradient launch gets slab ranges
+    (tests/host/update_loop_harness.cpp, suite slab-sum).  The data-gradient launch gets slab ranges
     exactly when the step has that launch, two hidden layers, more than one split and
     the switch is on -- one network per launch and the merged pair schedule alike --;
     the ranges lie inside ``[slabs, slabs + splits * n_flat)`` (the fake walks them in a

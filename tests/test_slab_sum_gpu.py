@@ -19,7 +19,7 @@ M     splits  tiles  what it exercises
 ====  ======  =====  ==========================================================
 
 That the ranges are handed over at all (and only then) is pinned on the CPU
-(tests/host/slab_sum_harness.cpp).
+(tests/host/update_loop_harness.cpp, suite slab-sum).
 """
 import numpy as np
 import pytest
