@@ -7,7 +7,7 @@ ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
 HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -25,13 +25,16 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function 
 
 all: $(OUT)/libgarage_amd.so
 
-$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/gemm_core.h $(CSRC)/gemm_params.h $(CSRC)/loss_rows.h $(CSRC)/fused_train.h $(CSRC)/rollout_dev.h $(CSRC)/narrow_body.h $(CSRC)/reduce_trees.h $(CSRC)/members_step.h $(CSRC)/member_pack.h include/garage_amd.h
+# (header dependencies come from the compiler: -MMD -MP writes $(OUT)/x.d beside x.o)
+$(OUT)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(OUT)
-	$(HIPCC) $(FLAGS) -c $< -o $@
+	$(HIPCC) $(FLAGS) -MMD -MP -c $< -o $@
 
-$(OUT)/%.o: $(CSRC)/%.cpp $(CSRC)/common.h $(CSRC)/gemm_params.h $(CSRC)/internal.h $(CSRC)/prof.h $(CSRC)/small_step.h $(CSRC)/fused_train.h $(CSRC)/members_step.h $(CSRC)/member_pack.h include/garage_amd.h
+$(OUT)/%.o: $(CSRC)/%.cpp
 	@mkdir -p $(OUT)
-	$(HIPCC) $(FLAGS) -x hip -c $< -o $@
+	$(HIPCC) $(FLAGS) -MMD -MP -x hip -c $< -o $@
+
+-include $(OBJS:.o=.d)
 
 $(OUT)/libgarage_amd.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -ldl -o $@
@@ -59,7 +62,7 @@ slp-variant:
 	rm -rf $(OUT)/variants/slp
 
 clean:
-	rm -rf $(OUT)/*.o $(OUT)/*.so $(OUT)/asan $(OUT)/*_asan_test $(OUT)/mfma_peak $(OUT)/mfma_valu_overlap $(OUT)/mfma_valu_hazard $(OUT)/mfma_rounding $(OUT)/variants
+	rm -rf $(OUT)/*.o $(OUT)/*.d $(OUT)/*.so $(OUT)/asan $(OUT)/*_asan_test $(OUT)/mfma_peak $(OUT)/mfma_valu_overlap $(OUT)/mfma_valu_hazard $(OUT)/mfma_rounding $(OUT)/variants
 
 .PHONY: all clean mfma-peak mfma-tools slp-variant
 
@@ -72,7 +75,8 @@ ASAN_PROGRAMS := \
   rollout_asan_test:rollout_loop_harness:rollout_loop \
   mlp_layers_asan_test:mlp_layers_harness:mlp_layers \
   update_members_asan_test:update_members_harness:update_members \
-  member_pack_asan_test:member_pack_harness:member_pack_host
+  member_pack_asan_test:member_pack_harness:member_pack_host \
+  fused_host_asan_test:fused_host_harness:fused_train_host
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -125,9 +129,15 @@ asan-members: $(OUT)/update_members_asan_test
 asan-member-pack: $(OUT)/member_pack_asan_test
 	$(OUT)/member_pack_asan_test
 
+# The fused optimizer step's host side (fused_train_host.cpp) against fakes of the launch
+# seam: the kernel choice against a literal table, grids, every refusal before any launch,
+# the optimizer launch's virtual grid, the slab sum's offsets, the weight-plane cache.
+asan-fused-host: $(OUT)/fused_host_asan_test
+	$(OUT)/fused_host_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
-  asan-members asan-member-pack asan-all
+  asan-members asan-member-pack asan-fused-host asan-all

@@ -1,9 +1,16 @@
-// Entry points of the fused optimizer-step kernels (fused_train.hip) and of the MLP
-// layer ranges they combine with (mlp_layers.cpp), used by the epoch loop (update.cpp).
+// Entry points of the fused optimizer-step kernels and of the MLP layer ranges they
+// combine with (mlp_layers.cpp), used by the epoch loop (update.cpp).  The entry points
+// are host C++ (fused_train_host.cpp: argument checks, kernel choice, grids, the weight-
+// plane cache); they fill the kernels' parameter structs (fused_params.h) and hand them
+// to the launch seam of fused_train.hip, which holds the device code.  The shape rules
+// (ga_fused_tiles, ga_fused_width_ok, ga_fused_first_layer_ok, ga_fused_pair_supported,
+// ga_narrow_step_supported, ga_narrow_step_stride) are shape_rules.h's.
 // Not part of the C ABI: ga_update_epoch* is what callers see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "shape_rules.h"
 
 struct ga_fused_loss_args {
   int kind;                  // 0 Gaussian policy, 1 value NLL, 2 categorical policy
@@ -24,8 +31,6 @@ struct ga_fused_region {
 };
 
 extern "C" {
-int ga_fused_width_ok(int width);       // 64, 128 or 256 units
-int64_t ga_fused_tiles(int64_t M);      // workgroups (= partial sets) for M rows
 // The layer under the last hidden one when that is the network's FIRST layer and
 // the kernel is to produce its outputs itself (H = tanh(X W^T + b), X gathered
 // through loss->idx) instead of reading them: in_w <= 32, K * round4(in_w) <=
@@ -39,7 +44,6 @@ typedef struct ga_fused_first_layer {
   float* H;        // [M][ldh]
   int64_t ldh;
 } ga_fused_first_layer;
-int ga_fused_first_layer_ok(int in_w, int K);
 // The whole MLP (two hidden tanh layers of the shapes above, <= 8 linear outputs) for
 // its OUTPUTS only: out[m] = MLP(X[idx ? idx[m] : m]); no activation reaches memory.
 int ga_fused_eval_supported(int n_layers, const int* dims);
@@ -49,8 +53,6 @@ int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t* idx, int64
                           const float* bh, float* out, int64_t ldo, hipStream_t stream);
 // narrow_step.hip: forward + loss + backward of a 2 x H network (H = 32 or 64) in one
 // launch; part: [tiles][ga_narrow_step_stride] floats, lpart: [tiles][2] doubles
-int ga_narrow_step_supported(int n_layers, const int* dims);
-int64_t ga_narrow_step_stride(int in_w, int H);
 int ga_narrow_train_step(const float* params, const int64_t* w_off, const int64_t* b_off,
                          int in_w, int H, int out_w, const float* X, int64_t ldx,
                          int64_t M, const ga_fused_loss_args* loss, float* part,
@@ -71,7 +73,6 @@ typedef struct ga_fused_fwd_net {
   float* dZ; int64_t lddz; float* hpart; double* lpart;
   const ga_fused_first_layer* first;
 } ga_fused_fwd_net;
-int ga_fused_pair_supported(int width, int K, int in_w);
 int ga_fused_fwd_head_loss(const ga_fused_fwd_net* nets, int n_nets, int64_t M, int width,
                            int K, hipStream_t stream);
 // 2. mlp_layers.cpp: the weight-gradient GEMM of the middle layer (dW2 = dZ2^T H1, split-K

@@ -54,18 +54,19 @@
 // Everything is exact fp32 on v_mfma_f32_32x32x2_f32 with fixed summation orders
 // (bitwise reproducible run to run); orders differ from the unfused kernels, so
 // the two paths agree to rounding, not bit for bit.
+//
+// Device code and, at the end, the launch seam only.  The entry points -- argument
+// checks, kernel choice, grids, the weight-plane cache -- are host C++,
+// fused_train_host.cpp; the parameter structs it fills are fused_params.h's.
 #include "common.h"
 #include <hip/hip_ext.h>
-#include <mutex>
 #include <type_traits>
-#include <vector>
-
-#include "prof.h"
 
 #include "gemm_core.h"
 #include "loss_rows.h"
 #include "reduce_trees.h"
 #include "fused_train.h"
+#include "fused_params.h"
 
 // ---- Audit (round 3) of out-of-range lanes / idle waves (the class of the round-2
 // small_step fault).  Clamped loads whose value is masked afterwards: gathered row
@@ -79,36 +80,8 @@
 // ga_update_partials_floats (tests/host/update_loop_harness.cpp, check 9).
 namespace {
 
-constexpr int FT_ROWS = 64;  // rows per workgroup tile
-
-struct FwdLossParams {
-  GemmParams g;          // A, lda, a_idx, B (= W [BN][ldb]), bias, M, N (= BN), K
-  const float* head_W;   // [A][head_ldw]
-  int64_t head_ldw;
-  const float* head_bias;
-  LossRowArgs loss;
-  float* dZ;             // [M][lddz]
-  int64_t lddz;
-  float* hpart;          // [gx][8 * BN + 8]: dW_head (j major), then db_head
-  double* lpart;         // [gx][2]
-  // L1 instantiation: the layer below is the FIRST layer (<= 32 inputs) and its
-  // output -- this GEMM's A operand -- is produced by the kernel itself:
-  // H1 = tanh(X W1^T + b1) chunk by chunk; g.A / g.lda are unused
-  const float* l1_X;     // observations [*][l1_ldx], gathered through loss.idx
-  int64_t l1_ldx;
-  const float* l1_W;     // [K][round4(l1_in)]
-  const float* l1_b;     // [K]
-  int l1_in;
-  float* l1_H;           // [M][l1_ldh]: H1 is written once, for the backward pass
-  int64_t l1_ldh;
-  float* eval_out;       // EVAL: the head outputs [M][eval_ldo], nothing else is kept
-  int64_t eval_ldo;
-  // SPLIT instantiation (opt-in, see "split-operand k-loop" below): W as three bf16
-  // planes in fragment order (split_planes_kernel), plane p at bplanes + p * bplane_stride
-  const uint16_t* bplanes;
-  int64_t bplane_stride;
-  long long* dbg;        // developer hook: phase timestamps of one workgroup
-};
+// (FT_ROWS = 64 rows per workgroup tile, FT_W1_FLOATS: shape_rules.h; the parameter
+// structs: fused_params.h)
 
 // FT_STAMP: timestamp i of workgroup 8; FT_MARK: slot (0 start, 1 end of the k-loop,
 // 2 end) of EVERY workgroup, behind the 16 values of workgroup 8: the skew of a launch
@@ -119,8 +92,6 @@ struct FwdLossParams {
 
 typedef const __attribute__((address_space(4))) float* ft_uniform_ptr;
 typedef float ft_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FT_W1_FLOATS = 5120;  // LDS floats for the first layer's weights
 
 #ifdef GA_SPLIT_NO_SETPRIO
 #define FT_SPLIT_PRIO(x)
@@ -1061,15 +1032,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
                                                            (int)gridDim.x);
 }
 
-// The same step of TWO networks (the policy's and the value function's minibatch k:
-// vpg.py:244-248 runs them one after the other, neither reads what the other
-// writes) in one grid: workgroup b takes tile b / 2 of network b % 2.  Twice the
-// workgroups per launch: the second generation starts as first-generation
-// workgroups retire, one launch ramp and drain instead of two, and -- unlike two
-// free-running streams -- the same schedule every time.
-struct FwdLossPair {
-  FwdLossParams a, b;
-};
+// (FwdLossPair, fused_params.h: the same step of TWO networks in one grid)
 template <int BN, int WAVES_M, int WAVES_N, int KSC>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
                              WAVES_M * WAVES_N == 8 ? 4 : 2) void fwd_head_loss_pair_kernel(
@@ -1148,125 +1111,10 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   out[2 * pairs + e] = lo;
 }
 
-// The pipelined k-loop is compiled for first layers of 17 .. 20 inputs (KSC = 5: the
-// HalfCheetah-shaped configuration the headline metric is quoted on) at 256 units;
-// every other shape takes the plain loop.  0 (or GARAGE_AMD_PIPELINED_KLOOP=0 in the
-// environment): the plain loop everywhere (A/B runs, tests).
-int g_pipelined_kloop = -1;
-bool pipelined_kloop_on() {
-  if (g_pipelined_kloop < 0) {
-    const char* e = getenv("GARAGE_AMD_PIPELINED_KLOOP");
-    g_pipelined_kloop = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_pipelined_kloop != 0;
-}
-
-// 1: the update kernels that have a split-operand instantiation use it (opt-in;
-// GARAGE_AMD_SPLIT_BF16=1 in the environment or ga_set_split_bf16(1)); default 0:
-// exact fp32 everywhere.
-int g_split_bf16 = -1;
-int g_split_parts = -1;  // developer knob: which kernels (1 forward, 2 data gradient,
-                         // 4 weight gradient, 8 evaluation forward, 16 the per-layer forward / data-gradient
-                         // GEMMs of wide layers); default all
-bool split_bf16_on(int part = 0) {
-  if (g_split_bf16 < 0) {
-    const char* e = getenv("GARAGE_AMD_SPLIT_BF16");
-    g_split_bf16 = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (g_split_parts < 0) {
-    const char* e = getenv("GARAGE_AMD_SPLIT_PARTS");
-    g_split_parts = e ? atoi(e) : 31;
-  }
-  return g_split_bf16 != 0 && (part == 0 || (g_split_parts & part) != 0);
-}
-
-// Device buffers for the planes of a weight matrix, one per (matrix, orientation),
-// kept for the life of the process (a few 100 KB each); the planes are recomputed by
-// every launch that uses them (the weights change every optimizer step).
-struct PlaneBuf {
-  const float* W;
-  int rows, cols;       // W [rows][ld], cols valid
-  uint16_t* fwd;        // B(k = col, n = row): the forward kernel's operand
-  uint16_t* bwd;        // B(k = row, n = col): the data-gradient kernel's operand
-  hipStream_t bwd_stream;  // stream on which `bwd` was last refreshed, not yet consumed
-  bool bwd_fresh;
-  // both operands were rewritten by the optimizer launch (reduce_regions_adam_kernel)
-  // that last changed W, on this stream, inside the epoch call that is still running
-  hipStream_t adam_stream;
-  bool adam_fresh;
-};
-std::mutex g_plane_mu;
-std::vector<PlaneBuf> g_plane_bufs;
-// Both operands' planes of W [rows][ld] are written by ONE launch when the forward
-// kernel asks (want_bwd = false); the data-gradient launch of the same step -- same
-// stream, weights unchanged in between -- then finds its planes fresh and launches
-// nothing.  Any other order (a data-gradient launch on its own) recomputes.
-// PLANES_BWD: the fused data-gradient launch of the step whose forward launch asked with
-// PLANES_TRAIN_FWD (may reuse); PLANES_BWD_ALWAYS: anybody else (always recomputes)
-enum { PLANES_TRAIN_FWD = 0, PLANES_BWD = 1, PLANES_EVAL_FWD = 2, PLANES_BWD_ALWAYS = 3 };
-const uint16_t* planes_for(const float* W, int64_t ld, int rows, int cols, int mode,
-                           hipStream_t stream) {
-  uint16_t *fwd = nullptr, *bwd = nullptr;
-  bool reuse = false;
-  {
-    std::lock_guard<std::mutex> lock(g_plane_mu);
-    PlaneBuf* pb = nullptr;
-    for (PlaneBuf& b : g_plane_bufs)
-      if (b.W == W && b.rows == rows && b.cols == cols) pb = &b;
-    if (!pb) {
-      uint16_t* buf = nullptr;
-      const size_t padded = (size_t)((rows + 31) & ~31) * ((cols + 31) & ~31);
-      if (hipMalloc(&buf, 6 * padded * sizeof(uint16_t)) != hipSuccess) return nullptr;
-      g_plane_bufs.push_back(PlaneBuf{W, rows, cols, buf, buf + 3 * padded, nullptr, false});
-      pb = &g_plane_bufs.back();
-    }
-    bool from_adam = false;
-    if (mode == PLANES_BWD || mode == PLANES_BWD_ALWAYS) {
-      reuse = mode == PLANES_BWD && pb->bwd_fresh && pb->bwd_stream == stream;
-      pb->bwd_fresh = false;
-    } else if (mode == PLANES_TRAIN_FWD) {
-      // (the previous step's optimizer launch wrote both operands already)
-      from_adam = pb->adam_fresh && pb->adam_stream == stream;
-      pb->bwd_fresh = true;
-      pb->bwd_stream = stream;
-    } else {
-      pb->bwd_fresh = false;
-    }
-    pb->adam_fresh = false;
-    fwd = pb->fwd;
-    bwd = pb->bwd;
-    if (from_adam) return fwd;
-  }
-  const unsigned blocks = (unsigned)(
-      ((int64_t)((rows + 31) & ~31) * ((cols + 31) & ~31) / 2 + 255) / 256);
-  uint32_t* fwd32 = reinterpret_cast<uint32_t*>(fwd);
-  uint32_t* bwd32 = reinterpret_cast<uint32_t*>(bwd);
-  if (mode == PLANES_BWD || mode == PLANES_BWD_ALWAYS) {
-    if (!reuse)
-      hipLaunchKernelGGL(split_planes_kernel<true>, dim3(blocks), dim3(256), 0, stream, W,
-                         ld, rows, cols, fwd32, bwd32);
-    return bwd;
-  }
-  hipLaunchKernelGGL(split_planes_kernel<false>,
-                     dim3(mode == PLANES_TRAIN_FWD ? 2 * blocks : blocks), dim3(256), 0,
-                     stream, W, ld, rows, cols, fwd32, bwd32);
-  return fwd;
-}
-
 // (the sum of one parameter quad's partials -- ft_share_run and its neighbours -- is
 // in reduce_trees.h: reduce_members_adam_kernel of members_step.hip runs it too)
 
-// Slab ranges one data-gradient launch sums on the side (ga_fused_dgrad_net::sum_w /
-// sum_b): quad v of the launch is quad v of range 0 for v < nq[0], quad v - nq[0] of
-// range 1 after that; off: floats from `base` to partial 0 of a range's element 0.
-struct FtSlabSum {
-  float* base;
-  uint32_t off[2];
-  int nq[2];
-  int64_t stride;   // floats between partials
-  int n_part;       // 0: nothing to sum
-  int tiles;        // workgroups of this network's launch
-};
+// (FtSlabSum: fused_params.h)
 
 // The other lane of a lane pair (l ^ 1), as a DPP operand: no LDS round trip
 __device__ __forceinline__ float ft_pair_swap(float x) {
@@ -1430,23 +1278,6 @@ struct FtSlabSummer {
 };
 
 // ---------------------------------------------------------------------------
-struct DgradWgrad0Params {
-  GemmParams g;        // A = dZ2 [M][lda], B = W2 [K][ldb] (n contiguous), M, N = BN, K
-  const float* H;      // tanh outputs of the first hidden layer [M][ldh]
-  int64_t ldh;
-  const float* X;      // observations [*][ldx], in_w valid columns, gathered
-  int64_t ldx;
-  const int32_t* idx;
-  int in_w;            // <= 32
-  float* wpart;        // [gx][BN * ld0 + BN]: dW1 [n][ld0], then db1 [n]
-  // SPLIT instantiation: W2 as the B operand B(k = unit of layer 2, n = unit of layer
-  // 1) in three bf16 planes, fragment order (split_planes_kernel<true>)
-  const uint16_t* bplanes;
-  int64_t bplane_stride;
-  long long* dbg;      // developer hook: phase timestamps (FT_STAMP / FT_MARK)
-  FtSlabSum sum;       // the middle layer's split-K slabs, summed on the side
-};
-
 constexpr int FT_LDXS = 32;  // staged observation rows: 32 floats (zero beyond in_w)
 
 // The workgroup's observation rows, two quads per thread: loads issued in front of the
@@ -1821,9 +1652,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 4) void dgrad_wgrad0_split_
   dgrad_wgrad0_body<BN, WAVES_M, WAVES_N, true>(p, (int)blockIdx.x);
 }
 
-struct DgradWgrad0Pair {
-  DgradWgrad0Params a, b;
-};
 // two networks in one grid (see fwd_head_loss_pair_kernel)
 template <int BN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
@@ -1848,10 +1676,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
 // unused) and the optimizer launch sums them.  Same arithmetic in the same order per
 // element as the two launches: the same bits.
 // LDS: what the forward body has (the observation rows go to its aux block).
-struct FwdDgradParams {
-  FwdLossParams f;
-  DgradWgrad0Params d;
-};
 template <int BN, int WAVES_M, int WAVES_N, int KSC>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
                              WAVES_M * WAVES_N == 8 ? 4 : 2) void fwd_dgrad_kernel(
@@ -1893,52 +1717,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
 }
 
 // ---------------------------------------------------------------------------
-struct FtAdam {
-  float* p; float* m; float* v;
-  GaAdam c;
-};
-
-constexpr int FT_MAX_REGIONS = 16;
-struct FtRegion {
-  int64_t beg;        // first flat parameter index
-  int64_t n;          // elements (a multiple of 4)
-  const float* src;   // partial 0 of element 0
-  int64_t stride;     // floats between consecutive partials
-  int n_part;
-  int quads;          // quads per workgroup: 64 or 16 (pre: 256)
-  int pre;            // partial 0 holds the sum already: nothing else is read
-  int64_t vbeg;       // first workgroup of the region
-  int net;            // which network's buffers (a pair launch steps two)
-};
-struct FtNet {
-  FtAdam a;
-  float* grads;       // the reduced (scaled) gradient is also written here
-  float scale;
-  int do_adam;        // 0: stop after writing grads (an all-reduce follows)
-  int zero_slot0;     // the log-std slot is not trained
-  // loss finish (one extra block per network): batch sums -> loss value, log-std
-  // gradient
-  const double* lpart;
-  int n_lpart;
-  int64_t M;
-  LossRowArgs loss;
-  float* loss_out;
-  // split-operand experiment: the planes of ONE weight matrix (rows x cols, ld = cols, at
-  // flat index pl_beg) are rewritten with the updated values, so that the next step's
-  // forward launch needs no plane launch (null: nothing)
-  uint32_t* pl_fwd;
-  uint32_t* pl_bwd;
-  int64_t pl_beg;
-  int pl_rows, pl_cols;
-};
-struct ReduceRegionsParams {
-  FtRegion r[FT_MAX_REGIONS];
-  int n_regions;
-  int n_nets;         // 1 or 2
-  int64_t n_virtual;  // workgroups over all regions
-  FtNet net[2];
-};
-
+// (FtRegion, FtNet, ReduceRegionsParams: fused_params.h)
 __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsParams p) {
   // A short launch on its chain's critical path that usually lands beside the other
   // chain's GEMM-class kernel (traced: 17-57 us there against 11 us alone): its waves
@@ -2068,22 +1847,9 @@ __global__ __launch_bounds__(256) void reduce_regions_adam_kernel(ReduceRegionsP
   }
 }
 
-}  // namespace
-
-extern "C" int ga_set_pipelined_kloop(int on) {
-  g_pipelined_kloop = on != 0;
-  return 0;
-}
-
-extern "C" int ga_set_split_bf16(int on) {
-  g_split_bf16 = on != 0;
-  return 0;
-}
-
 // developer hook (tools/): a register-only MFMA loop on `stream`, mode 1 =
 // v_mfma_f32_32x32x16_bf16, 2 = v_mfma_f32_32x32x2_f32 -- a co-resident load with no
 // memory traffic at all
-namespace {
 __global__ __launch_bounds__(512, 4) void mfma_burn_kernel(int mode, int iters, float* sink) {
   f32x16 acc[2];
 #pragma unroll
@@ -2105,513 +1871,103 @@ __global__ __launch_bounds__(512, 4) void mfma_burn_kernel(int mode, int iters, 
   }
   if (acc[0][0] + acc[1][0] == 12345.f) sink[0] = 1.f;
 }
+
 }  // namespace
-extern "C" int ga_debug_mfma_burn(int mode, int iters, int blocks, float* sink,
-                                  ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mfma_burn_kernel, dim3(blocks), dim3(512), 0, stream, mode, iters, sink);
-  return 0;
-}
 
-extern "C" int ga_split_bf16_enabled(void) { return split_bf16_on(4) ? 1 : 0; }
-extern "C" int ga_split_bf16_gemm(void) { return split_bf16_on(16) ? 1 : 0; }
-extern "C" const uint16_t* ga_weight_planes(const float* W, int64_t ld, int rows, int cols,
-                                            int bwd, hipStream_t stream) {
-  return planes_for(W, ld, rows, cols, bwd ? PLANES_BWD_ALWAYS : PLANES_EVAL_FWD, stream);
-}
-extern "C" int ga_split_bf16_any(void) { return split_bf16_on() ? 1 : 0; }
+// ---- the launch seam (fused_params.h).  The host side (fused_train_host.cpp) has checked
+// the arguments, filled the parameter structs, chosen the variant and sized the grid;
+// these functions do nothing but instantiate and launch.
+#define FT_LAUNCH(threads, arg, ...) \
+  hipExtLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(threads), 0, stream, e0, e1, 0, arg)
 
-extern "C" int ga_fused_width_ok(int width) {
-  return width == 64 || width == 128 || width == 256;
-}
-
-extern "C" int64_t ga_fused_tiles(int64_t M) { return ga_ceil_div(M, FT_ROWS); }
-
-static long long* g_ft_dbg = nullptr;
-constexpr int FT_DBG_BLOCKS = 4096, FT_DBG_WORDS = 16 + 7 * FT_DBG_BLOCKS;
-// developer hook: phase timestamps (100 MHz wall clock) of workgroup 8 of the most
-// recent fwd_head_loss launch -- first call arms it, second call reads 16 values back
-extern "C" int ga_fused_fwd_debug(long long* host_out16) {
-  if (!g_ft_dbg) {
-    if (hipMalloc(&g_ft_dbg, FT_DBG_WORDS * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(g_ft_dbg, 0, FT_DBG_WORDS * sizeof(long long));
-    return 1;
-  }
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host_out16, g_ft_dbg, 16 * sizeof(long long), hipMemcpyDeviceToHost) ==
-                 hipSuccess ? 0 : -1;
-}
-// -DGA_FT_LOOP_STAMPS builds only (make EXTRA=-DGA_FT_LOOP_STAMPS): per workgroup,
-// ticks in (fragment reads + MFMAs, first barrier, tile stores, second barrier)
-// summed over the k-loop
-extern "C" int ga_fused_fwd_debug_loop(long long* host_out, int n) {
-  if (!g_ft_dbg || n < 1 || n > FT_DBG_BLOCKS) return -1;
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host_out, g_ft_dbg + 16 + 3 * FT_DBG_BLOCKS,
-                   4 * (size_t)n * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess
-             ? 0 : -1;
-}
-// (start, end of k-loop, end) of the first n workgroups of that launch, n <= 4096
-extern "C" int ga_fused_fwd_debug_skew(long long* host_out, int n) {
-  if (!g_ft_dbg || n < 1 || n > FT_DBG_BLOCKS) return -1;
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host_out, g_ft_dbg + 16, 3 * (size_t)n * sizeof(long long),
-                   hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-
-static long long* g_dg_dbg = nullptr;
-// the same two hooks for dgrad_wgrad0_kernel: which = 0 -> 16 phase stamps of
-// workgroup 8 (first call arms), which = 1 -> (start, end of k-loop, end) of the
-// first n workgroups
-extern "C" int ga_fused_dgrad_debug(long long* host_out, int which, int n) {
-  if (!g_dg_dbg) {
-    if (hipMalloc(&g_dg_dbg, FT_DBG_WORDS * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(g_dg_dbg, 0, FT_DBG_WORDS * sizeof(long long));
-    return 1;
-  }
-  (void)hipDeviceSynchronize();
-  if (which == 0)
-    return hipMemcpy(host_out, g_dg_dbg, 16 * sizeof(long long), hipMemcpyDeviceToHost) ==
-                   hipSuccess ? 0 : -1;
-  if (n < 1 || n > FT_DBG_BLOCKS) return -1;
-  return hipMemcpy(host_out, g_dg_dbg + 16, 3 * (size_t)n * sizeof(long long),
-                   hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-
-extern "C" int ga_fused_first_layer_ok(int in_w, int K) {
-  return in_w >= 1 && in_w <= 32 && K >= 32 && K % 32 == 0 &&
-         (int64_t)K * ((in_w + 3) & ~3) <= FT_W1_FLOATS;
-}
-
-// validation + kernel parameters of one network's launch
-static int fwd_build(const ga_fused_fwd_net& n, int64_t M, int width, int K,
-                     FwdLossParams* out, double* flops_out) {
-  const ga_fused_first_layer* first = n.first;
-  const ga_fused_loss_args* loss = n.loss;
-  GA_REQUIRE((n.A || first) && n.W && n.bias && n.head_W && n.head_bias && loss && n.dZ &&
-                 n.hpart && n.lpart,
-             "ga_fused_fwd_head_loss: null pointer");
-  const float* A = n.A;
-  int64_t lda = n.lda;
-  const int32_t* a_idx = n.a_idx;
-  if (first) {
-    GA_REQUIRE(first->X && first->W && first->b && first->H &&
-                   ga_fused_first_layer_ok(first->in_w, K) && K <= 256 &&
-                   first->ldx >= first->in_w && first->ldh % 4 == 0 && first->ldh >= K &&
-                   ga_aligned16(first->W),
-               "ga_fused_fwd_head_loss: unsupported first layer");
-    A = first->H;  // (only for the checks below; never read)
-    lda = first->ldh;
-    a_idx = nullptr;
-  }
-  GA_REQUIRE(ga_fused_width_ok(width) && M >= 1 && M < (1ll << 31) && K >= 1 &&
-                 loss->A >= 1 && loss->A <= 8,
-             "ga_fused_fwd_head_loss: unsupported shape");
-  GA_REQUIRE(lda % 4 == 0 && n.ldw % 4 == 0 && n.head_ldw % 4 == 0 && n.lddz % 4 == 0 &&
-                 ga_aligned16(A) && ga_aligned16(n.W) && ga_aligned16(n.bias) &&
-                 ga_aligned16(n.head_W) && ga_aligned16(n.dZ),
-             "ga_fused_fwd_head_loss: operands must be 16-B aligned quads");
-  GA_REQUIRE(loss->kind == 1 ? loss->returns != nullptr
-                             : (loss->actions && loss->adv &&
-                                (loss->algo == 1 || loss->old_ll) &&
-                                (loss->kind == 2 ||
-                                 (loss->lda % 4 == 0 && ga_aligned16(loss->actions) &&
-                                  loss->lda >= ((loss->A + 3) & ~3)))),
-             "ga_fused_fwd_head_loss: missing / misaligned minibatch arrays");
-  GA_REQUIRE(loss->kind == 2 || loss->log_std, "ga_fused_fwd_head_loss: log_std");
-  GA_REQUIRE(loss->algo == 0 || loss->algo == 1, "ga_fused_fwd_head_loss: algo");
-  FwdLossParams& p = *out;
-  memset(&p, 0, sizeof(p));
-  p.g.A = A; p.g.lda = lda; p.g.a_idx = a_idx; p.g.B = n.W; p.g.ldb = n.ldw;
-  p.g.M = (int)M; p.g.N = width; p.g.K = K; p.g.bias = n.bias;
-  p.head_W = n.head_W; p.head_ldw = n.head_ldw; p.head_bias = n.head_bias;
-  p.loss = loss_args(loss, M);
-  p.dZ = n.dZ; p.lddz = n.lddz; p.hpart = n.hpart; p.lpart = n.lpart;
-  // algorithmic flops of the layers computed
-  double flops = 2.0 * (double)M * width * ((double)K + loss->A);
-  if (first) {
-    p.l1_X = first->X; p.l1_ldx = first->ldx; p.l1_W = first->W; p.l1_b = first->b;
-    p.l1_in = first->in_w; p.l1_H = first->H; p.l1_ldh = first->ldh;
-    flops += 2.0 * (double)M * K * first->in_w;
-  }
-  *flops_out = flops;
-  return GA_OK;
-}
-
-// Pair launches are compiled for 256-wide last hidden layers with the first layer in
-// the kernel (the C3-class networks the two-chain schedule was built for).
-extern "C" int ga_fused_pair_supported(int width, int K, int in_w) {
-  return width == 256 && K <= 256 && ga_fused_first_layer_ok(in_w, K);
-}
-
-// n_nets = 2: the two networks' launches (first layer in the kernel) in ONE grid; both
-// have the same width, K, input width and row count.
-extern "C" int ga_fused_fwd_head_loss(const ga_fused_fwd_net* nets, int n_nets, int64_t M,
-                                      int width, int K, hipStream_t stream) {
-  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
-             "ga_fused_fwd_head_loss: one or two networks");
-  const ga_fused_first_layer* first = nets[0].first;
-  if (n_nets == 2)
-    GA_REQUIRE(first && nets[1].first && first->in_w == nets[1].first->in_w &&
-                   ga_fused_pair_supported(width, K, first->in_w),
-               "ga_fused_fwd_head_loss_pair: unsupported shapes");
-  FwdLossPair pp;
-  FwdLossParams& p = pp.a;
-  double flops = 0.0;
-  for (int i = 0; i < n_nets; ++i) {
-    double f = 0.0;
-    const int rc = fwd_build(nets[i], M, width, K, i ? &pp.b : &pp.a, &f);
-    if (rc) return rc;
-    flops += f;
-  }
-  const dim3 grid((unsigned)(n_nets * ga_fused_tiles(M)));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_FWD, flops, &e0, &e1);
-  if (n_nets == 1) {
-    p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_ft_dbg : nullptr;
-    if (first && width == 64)
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2, true>), grid, dim3(256), 0,
-                            stream, e0, e1, 0, p);
-    else if (first && width == 128)
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4, true>), grid, dim3(256), 0,
-                            stream, e0, e1, 0, p);
-    else if (first && split_bf16_on(1) && K % 32 == 0 && first->in_w <= 20) {
-      p.bplanes = planes_for(nets[0].W, nets[0].ldw, width, K, PLANES_TRAIN_FWD, stream);
-      GA_REQUIRE(p.bplanes, "ga_fused_fwd_head_loss: no memory for the weight planes");
-      p.bplane_stride = (int64_t)width * K;
-      hipExtLaunchKernelGGL((fwd_head_loss_split_kernel<256, 1, 8>), grid, dim3(512), 0,
-                            stream, e0, e1, 0, p);
-    } else if (first && (first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true, 5>), grid, dim3(512), 0,
-                            stream, e0, e1, 0, p);
-    else if (first)
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8, true>), grid, dim3(512), 0,
-                            stream, e0, e1, 0, p);
-    else if (width == 64)
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<64, 2, 2>), grid, dim3(256), 0, stream,
-                            e0, e1, 0, p);
-    else if (width == 128)
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
-                            e0, e1, 0, p);
-    else
-      hipExtLaunchKernelGGL((fwd_head_loss_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                            e0, e1, 0, p);
-    GA_CHECK_LAUNCH("fwd_head_loss");
-    return GA_OK;
-  }
-  ga_prof_count(GA_PROF_FUSED_FWD);  // (one launch, two networks' steps)
-  if ((first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
-    hipExtLaunchKernelGGL((fwd_head_loss_pair_kernel<256, 1, 8, 5>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, pp);
+void ft_launch_fwd_loss(const FwdLossParams& p, FtVariant v, unsigned blocks, hipEvent_t e0,
+                        hipEvent_t e1, hipStream_t stream) {
+  if (v.l1 && v.width == 64)
+    FT_LAUNCH(256, p, fwd_head_loss_kernel<64, 2, 2, true>);
+  else if (v.l1 && v.width == 128)
+    FT_LAUNCH(256, p, fwd_head_loss_kernel<128, 1, 4, true>);
+  else if (v.l1 && v.split)
+    FT_LAUNCH(512, p, fwd_head_loss_split_kernel<256, 1, 8>);
+  else if (v.l1 && v.ksc == 5)
+    FT_LAUNCH(512, p, fwd_head_loss_kernel<256, 1, 8, true, 5>);
+  else if (v.l1)
+    FT_LAUNCH(512, p, fwd_head_loss_kernel<256, 1, 8, true>);
+  else if (v.width == 64)
+    FT_LAUNCH(256, p, fwd_head_loss_kernel<64, 2, 2>);
+  else if (v.width == 128)
+    FT_LAUNCH(256, p, fwd_head_loss_kernel<128, 1, 4>);
   else
-    hipExtLaunchKernelGGL((fwd_head_loss_pair_kernel<256, 1, 8, 0>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, pp);
-  GA_CHECK_LAUNCH("fwd_head_loss_pair");
-  return GA_OK;
+    FT_LAUNCH(512, p, fwd_head_loss_kernel<256, 1, 8>);
 }
 
-extern "C" int ga_fused_eval_supported(int n_layers, const int* dims) {
-  return n_layers == 3 && dims && ga_fused_first_layer_ok(dims[0], dims[1]) &&
-         dims[1] <= 256 && ga_fused_width_ok(dims[2]) && dims[3] >= 1 && dims[3] <= 8;
-}
-
-extern "C" int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t* idx,
-                                     int64_t M, const int* dims, const float* W1,
-                                     const float* b1, const float* W2, const float* b2,
-                                     const float* Wh, const float* bh, float* out,
-                                     int64_t ldo, hipStream_t stream) {
-  GA_REQUIRE(X && dims && W1 && b1 && W2 && b2 && Wh && bh && out,
-             "ga_fused_eval_forward: null pointer");
-  GA_REQUIRE(ga_fused_eval_supported(3, dims), "ga_fused_eval_forward: unsupported shape");
-  GA_REQUIRE(M >= 1 && M < (1ll << 31) && ldx >= dims[0] && ldo >= dims[3],
-             "ga_fused_eval_forward: bad sizes");
-  GA_REQUIRE(ga_aligned16(W1) && ga_aligned16(W2) && ga_aligned16(b2) && ga_aligned16(Wh),
-             "ga_fused_eval_forward: operands must be 16-B aligned");
-  const int in_w = dims[0], K = dims[1], width = dims[2], A = dims[3];
-  FwdLossParams p;
-  memset(&p, 0, sizeof(p));
-  p.g.B = W2; p.g.ldb = (K + 3) & ~3;
-  p.g.M = (int)M; p.g.N = width; p.g.K = K; p.g.bias = b2;
-  p.head_W = Wh; p.head_ldw = (width + 3) & ~3; p.head_bias = bh;
-  p.loss.idx = idx; p.loss.A = A; p.loss.kind = 2;
-  p.l1_X = X; p.l1_ldx = ldx; p.l1_W = W1; p.l1_b = b1; p.l1_in = in_w;
-  p.eval_out = out; p.eval_ldo = ldo;
-  const dim3 grid((unsigned)ga_fused_tiles(M));
-  const double flops = 2.0 * (double)M * ((double)K * in_w + (double)width * (K + A));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_EVAL_FWD, flops, &e0, &e1);
-  if (width == 64)
-    hipExtLaunchKernelGGL((mlp_eval_forward_kernel<64, 2, 2>), grid, dim3(256), 0, stream,
-                          e0, e1, 0, p);
-  else if (width == 128)
-    hipExtLaunchKernelGGL((mlp_eval_forward_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
-                          e0, e1, 0, p);
-  else if (split_bf16_on(8) && K % 32 == 0 && in_w <= 20) {
-    p.bplanes = planes_for(W2, p.g.ldb, width, K, PLANES_EVAL_FWD, stream);
-    GA_REQUIRE(p.bplanes, "ga_fused_eval_forward: no memory for the weight planes");
-    p.bplane_stride = (int64_t)width * K;
-    hipExtLaunchKernelGGL((mlp_eval_forward_split_kernel<256, 1, 8>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
-  } else if ((in_w + 3) / 4 == 5 && pipelined_kloop_on())
-    hipExtLaunchKernelGGL((mlp_eval_forward_kernel<256, 1, 8, 5>), grid, dim3(512), 0,
-                          stream, e0, e1, 0, p);
+void ft_launch_fwd_loss_pair(const FwdLossPair& pp, FtVariant v, unsigned blocks,
+                             hipEvent_t e0, hipEvent_t e1, hipStream_t stream) {
+  if (v.ksc == 5)
+    FT_LAUNCH(512, pp, fwd_head_loss_pair_kernel<256, 1, 8, 5>);
   else
-    hipExtLaunchKernelGGL((mlp_eval_forward_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                          e0, e1, 0, p);
-  GA_CHECK_LAUNCH("mlp_eval_forward");
-  return GA_OK;
+    FT_LAUNCH(512, pp, fwd_head_loss_pair_kernel<256, 1, 8, 0>);
 }
 
-static int dgrad_build(const ga_fused_dgrad_net& n, int64_t M, int width, int K, int in_w,
-                       DgradWgrad0Params* out, double* flops_out) {
-  GA_REQUIRE(n.dZ2 && n.W2 && n.H1 && n.X && n.wpart, "ga_fused_dgrad_wgrad0: null pointer");
-  GA_REQUIRE(ga_fused_width_ok(width) && M >= 1 && M < (1ll << 31) && K >= 1 &&
-                 in_w >= 1 && in_w <= 32,
-             "ga_fused_dgrad_wgrad0: unsupported shape");
-  GA_REQUIRE(n.lddz % 4 == 0 && n.ldw % 4 == 0 && n.ldh % 4 == 0 && n.ldx % 4 == 0 &&
-                 n.ldx >= ((in_w + 3) & ~3) && ga_aligned16(n.dZ2) && ga_aligned16(n.W2) &&
-                 ga_aligned16(n.H1) && ga_aligned16(n.X) && ga_aligned16(n.wpart),
-             "ga_fused_dgrad_wgrad0: operands must be 16-B aligned quads");
-  DgradWgrad0Params& p = *out;
-  memset(&p, 0, sizeof(p));
-  p.g.A = n.dZ2; p.g.lda = n.lddz; p.g.B = n.W2; p.g.ldb = n.ldw;
-  p.g.M = (int)M; p.g.N = width; p.g.K = K;
-  p.H = n.H1; p.ldh = n.ldh; p.X = n.X; p.ldx = n.ldx; p.idx = n.idx; p.in_w = in_w;
-  p.wpart = n.wpart;
-  if (n.sum_w.src || n.sum_b.src) {
-    const ga_slab_range* r[2] = {&n.sum_w, &n.sum_b};
-    const ga_slab_range& any = n.sum_w.src ? n.sum_w : n.sum_b;
-    uintptr_t lo = UINTPTR_MAX, hi = 0;
-    for (int i = 0; i < 2; ++i) {
-      if (!r[i]->src) continue;
-      GA_REQUIRE(r[i]->n >= 4 && r[i]->n % 4 == 0 && r[i]->n_part >= 1 &&
-                     r[i]->stride >= r[i]->n && r[i]->stride % 4 == 0 &&
-                     ga_aligned16(r[i]->src) && r[i]->stride == any.stride &&
-                     r[i]->n_part == any.n_part,
-                 "ga_fused_dgrad_wgrad0: bad slab range %d", i);
-      const uintptr_t b = reinterpret_cast<uintptr_t>(r[i]->src);
-      lo = b < lo ? b : lo;
-      const uintptr_t e =
-          b + sizeof(float) * (uintptr_t)((r[i]->n_part - 1) * r[i]->stride + r[i]->n);
-      hi = e > hi ? e : hi;
-    }
-    // (the kernel addresses the ranges with 32-bit byte offsets from the lower one)
-    GA_REQUIRE(hi - lo <= ((uintptr_t)1 << 32),
-               "ga_fused_dgrad_wgrad0: slab ranges further apart than 2^30 floats");
-    p.sum.base = reinterpret_cast<float*>(lo);
-    for (int i = 0; i < 2; ++i) {
-      if (!r[i]->src) continue;
-      p.sum.off[i] = (uint32_t)(r[i]->src - p.sum.base);
-      p.sum.nq[i] = (int)(r[i]->n / 4);
-    }
-    p.sum.stride = any.stride;
-    p.sum.n_part = any.n_part;
-    p.sum.tiles = (int)ga_fused_tiles(M);
-  }
-  *flops_out = 2.0 * (double)M * width * ((double)K + in_w);
-  return GA_OK;
-}
-
-// n_nets = 2: two networks' launches in one grid (width 256)
-extern "C" int ga_fused_dgrad_wgrad0(const ga_fused_dgrad_net* nets, int n_nets, int64_t M,
-                                     int width, int K, int in_w, hipStream_t stream) {
-  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
-             "ga_fused_dgrad_wgrad0: one or two networks");
-  if (n_nets == 2)
-    GA_REQUIRE(width == 256, "ga_fused_dgrad_wgrad0_pair: unsupported width");
-  DgradWgrad0Pair pp;
-  DgradWgrad0Params& p = pp.a;
-  double flops = 0.0;
-  for (int i = 0; i < n_nets; ++i) {
-    double f = 0.0;
-    const int rc = dgrad_build(nets[i], M, width, K, in_w, i ? &pp.b : &pp.a, &f);
-    if (rc) return rc;
-    flops += f;
-  }
-  const dim3 grid((unsigned)(n_nets * ga_fused_tiles(M)));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_DGRAD, flops, &e0, &e1);
-  if (n_nets == 1) {
-    p.dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS ? g_dg_dbg : nullptr;
-    if (width == 64)
-      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<64, 2, 2>), grid, dim3(256), 0, stream, e0,
-                            e1, 0, p);
-    else if (width == 128)
-      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<128, 1, 4>), grid, dim3(256), 0, stream,
-                            e0, e1, 0, p);
-    else if (split_bf16_on(2) && K % 32 == 0) {
-      p.bplanes = planes_for(nets[0].W2, nets[0].ldw, K, width, PLANES_BWD, stream);
-      GA_REQUIRE(p.bplanes, "ga_fused_dgrad_wgrad0: no memory for the weight planes");
-      p.bplane_stride = (int64_t)width * K;
-      hipExtLaunchKernelGGL((dgrad_wgrad0_split_kernel<256, 1, 8>), grid, dim3(512), 0,
-                            stream, e0, e1, 0, p);
-    } else
-      hipExtLaunchKernelGGL((dgrad_wgrad0_kernel<256, 1, 8>), grid, dim3(512), 0, stream,
-                            e0, e1, 0, p);
-    GA_CHECK_LAUNCH("dgrad_wgrad0");
-    return GA_OK;
-  }
-  ga_prof_count(GA_PROF_FUSED_DGRAD);
-  hipExtLaunchKernelGGL((dgrad_wgrad0_pair_kernel<256, 1, 8>), grid, dim3(512), 0,
-                        stream, e0, e1, 0, pp);
-  GA_CHECK_LAUNCH("dgrad_wgrad0_pair");
-  return GA_OK;
-}
-
-// fwd_dgrad_kernel is compiled for two hidden layers of the same width (K = the first
-// one's, width = the second one's) with the first layer in the kernel.
-extern "C" int ga_fused_fwd_dgrad_supported(int width, int K, int in_w) {
-  return ga_fused_width_ok(width) && K == width && ga_fused_first_layer_ok(in_w, K);
-}
-
-// Launches 1 and 3 of a step as ONE dispatch (fwd_dgrad_kernel), one network.  `dgrad`
-// describes the same step as `fwd`: its dZ2 / H1 / X / idx are what `fwd` writes and
-// gathers, and it carries no slab ranges (the weight-gradient GEMM runs after this).
-// Timed as one GA_PROF_FUSED_FWD dispatch with both bodies' work; the step counter of
-// GA_PROF_FUSED_DGRAD advances too: the counters count network steps.
-extern "C" int ga_fused_fwd_dgrad(const ga_fused_fwd_net* fwd, const ga_fused_dgrad_net* dgrad,
-                                  int64_t M, int width, int K, hipStream_t stream) {
-  GA_REQUIRE(fwd && dgrad && fwd->first && fwd->loss, "ga_fused_fwd_dgrad: null pointer");
-  const ga_fused_first_layer* first = fwd->first;
-  GA_REQUIRE(ga_fused_fwd_dgrad_supported(width, K, first->in_w) && !split_bf16_on(),
-             "ga_fused_fwd_dgrad: unsupported shape or mode");
-  GA_REQUIRE(dgrad->dZ2 == fwd->dZ && dgrad->lddz == fwd->lddz && dgrad->H1 == first->H &&
-                 dgrad->ldh == first->ldh && dgrad->X == first->X &&
-                 dgrad->ldx == first->ldx && dgrad->idx == fwd->loss->idx &&
-                 !dgrad->sum_w.src && !dgrad->sum_b.src,
-             "ga_fused_fwd_dgrad: the two descriptors are not one step's");
-  FwdDgradParams pp;
-  double f0 = 0.0, f1 = 0.0;
-  int rc = fwd_build(*fwd, M, width, K, &pp.f, &f0);
-  if (rc) return rc;
-  rc = dgrad_build(*dgrad, M, K, width, first->in_w, &pp.d, &f1);
-  if (rc) return rc;
-  const bool dbg = ga_fused_tiles(M) <= FT_DBG_BLOCKS;
-  pp.f.dbg = dbg ? g_ft_dbg : nullptr;
-  pp.d.dbg = dbg ? g_dg_dbg : nullptr;
-  const dim3 grid((unsigned)ga_fused_tiles(M));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_FUSED_FWD, f0 + f1, &e0, &e1);
-  ga_prof_count(GA_PROF_FUSED_DGRAD);
-  if (width == 64)
-    hipExtLaunchKernelGGL((fwd_dgrad_kernel<64, 2, 2, 0>), grid, dim3(256), 0, stream, e0,
-                          e1, 0, pp);
-  else if (width == 128)
-    hipExtLaunchKernelGGL((fwd_dgrad_kernel<128, 1, 4, 0>), grid, dim3(256), 0, stream, e0,
-                          e1, 0, pp);
-  else if ((first->in_w + 3) / 4 == 5 && pipelined_kloop_on())
-    hipExtLaunchKernelGGL((fwd_dgrad_kernel<256, 1, 8, 5>), grid, dim3(512), 0, stream, e0,
-                          e1, 0, pp);
+void ft_launch_eval_forward(const FwdLossParams& p, FtVariant v, unsigned blocks,
+                            hipEvent_t e0, hipEvent_t e1, hipStream_t stream) {
+  if (v.width == 64)
+    FT_LAUNCH(256, p, mlp_eval_forward_kernel<64, 2, 2>);
+  else if (v.width == 128)
+    FT_LAUNCH(256, p, mlp_eval_forward_kernel<128, 1, 4>);
+  else if (v.split)
+    FT_LAUNCH(512, p, mlp_eval_forward_split_kernel<256, 1, 8>);
+  else if (v.ksc == 5)
+    FT_LAUNCH(512, p, mlp_eval_forward_kernel<256, 1, 8, 5>);
   else
-    hipExtLaunchKernelGGL((fwd_dgrad_kernel<256, 1, 8, 0>), grid, dim3(512), 0, stream, e0,
-                          e1, 0, pp);
-  GA_CHECK_LAUNCH("fwd_dgrad");
-  return GA_OK;
+    FT_LAUNCH(512, p, mlp_eval_forward_kernel<256, 1, 8>);
 }
 
-// regions + optimizer constants of one network into slot `net` of the launch
-static int reduce_add_net(ReduceRegionsParams& p, int net, const ga_reduce_net& n) {
-  const ga_fused_region* regions = n.regions;
-  GA_REQUIRE(regions && n.params && n.grads && n.exp_avg && n.exp_avg_sq && n.lpart &&
-                 n.loss,
-             "ga_reduce_regions_adam: null pointer");
-  GA_REQUIRE(n.n_regions >= 1 && p.n_regions + n.n_regions <= FT_MAX_REGIONS &&
-                 n.step >= 1 && n.n_lpart >= 1 && (n.presummed >> n.n_regions) == 0,
-             "ga_reduce_regions_adam: bad arguments");
-  int64_t v = p.n_virtual;
-  for (int k = 0; k < n.n_regions; ++k) {
-    // regions are walked 4 elements at a time: the flat layout pads every weight
-    // row and bias vector to a multiple of 4 floats, and the padding of every
-    // partial is zero, so a region is rounded up to whole quads
-    GA_REQUIRE(regions[k].src && regions[k].n >= 1 && regions[k].n_part >= 1 &&
-                   regions[k].beg >= 4 && regions[k].beg % 4 == 0 &&
-                   regions[k].stride % 4 == 0 && ga_aligned16(regions[k].src),
-               "ga_reduce_regions_adam: bad region %d", k);
-    FtRegion& r = p.r[p.n_regions + k];
-    r.beg = regions[k].beg; r.n = (regions[k].n + 3) & ~(int64_t)3;
-    r.src = regions[k].src;
-    r.stride = regions[k].stride; r.n_part = regions[k].n_part;
-    r.quads = regions[k].n_part <= 128 ? 64 : 16;
-    r.pre = (n.presummed >> k) & 1u;
-    // (a pre-summed region has a quad per THREAD to move, not per four or sixteen)
-    if (r.pre) r.quads = 256;
-    r.vbeg = v;
-    r.net = net;
-    v += ga_ceil_div(r.n / 4, r.quads);  // workgroups of this region
-  }
-  p.n_regions += n.n_regions;
-  p.n_virtual = v;
-  FtNet& N = p.net[net];
-  N.a.p = n.params; N.a.m = n.exp_avg; N.a.v = n.exp_avg_sq;
-  N.a.c = ga_adam_coeffs(n.lr, n.beta1, n.beta2, n.eps, n.step);
-  N.grads = n.grads; N.scale = n.scale; N.do_adam = n.do_adam;
-  N.zero_slot0 = n.zero_slot0;
-  N.lpart = n.lpart; N.n_lpart = n.n_lpart; N.M = n.M;
-  N.loss = loss_args(n.loss, n.M);
-  N.loss_out = n.loss_out;
-  return GA_OK;
+void ft_launch_dgrad(const DgradWgrad0Params& p, FtVariant v, unsigned blocks, hipEvent_t e0,
+                     hipEvent_t e1, hipStream_t stream) {
+  if (v.width == 64)
+    FT_LAUNCH(256, p, dgrad_wgrad0_kernel<64, 2, 2>);
+  else if (v.width == 128)
+    FT_LAUNCH(256, p, dgrad_wgrad0_kernel<128, 1, 4>);
+  else if (v.split)
+    FT_LAUNCH(512, p, dgrad_wgrad0_split_kernel<256, 1, 8>);
+  else
+    FT_LAUNCH(512, p, dgrad_wgrad0_kernel<256, 1, 8>);
 }
 
-// developer / test switch: 0 = every forward launch computes its planes itself again
-static int g_adam_planes = -1;
-static bool adam_planes_on() {
-  if (g_adam_planes < 0) {
-    const char* e = getenv("GARAGE_AMD_SPLIT_ADAM_PLANES");
-    g_adam_planes = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_adam_planes != 0;
-}
-extern "C" int ga_set_split_adam_planes(int on) {
-  g_adam_planes = on != 0;
-  return 0;
-}
-// trust in optimizer-written planes never outlives an epoch call (anything may write
-// the parameters between two calls)
-extern "C" void ga_planes_epoch_begin(void) {
-  std::lock_guard<std::mutex> lock(g_plane_mu);
-  for (PlaneBuf& b : g_plane_bufs) b.adam_fresh = false;
+void ft_launch_dgrad_pair(const DgradWgrad0Pair& pp, FtVariant, unsigned blocks,
+                          hipEvent_t e0, hipEvent_t e1, hipStream_t stream) {
+  FT_LAUNCH(512, pp, dgrad_wgrad0_pair_kernel<256, 1, 8>);
 }
 
-// n_nets = 2: both networks' optimizer steps in one launch (regions of two flat buffers,
-// two loss blocks); the same per-element arithmetic and summation trees as two single
-// launches
-extern "C" int ga_reduce_regions_adam(const ga_reduce_net* nets, int n_nets,
-                                      hipStream_t stream) {
-  GA_REQUIRE(nets && (n_nets == 1 || n_nets == 2),
-             "ga_reduce_regions_adam: one or two networks");
-  ReduceRegionsParams p;
-  memset(&p, 0, sizeof(p));
-  for (int i = 0; i < n_nets; ++i) {
-    const int rc = reduce_add_net(p, i, nets[i]);
-    if (rc) return rc;
-  }
-  p.n_nets = n_nets;
-  // (with do_adam) the launch also rewrites the planes of W = params + pl_beg
-  // ([rows][cols], ld = cols); update.cpp asks for it when the step's forward launch
-  // ran the split-operand kernel
-  GA_REQUIRE(n_nets == 1 || (!nets[0].pl_rows && !nets[1].pl_rows),
-             "ga_reduce_regions_adam: no plane rewriting for two networks");
-  const int rows = nets[0].pl_rows, cols = nets[0].pl_cols;
-  if (rows > 0 && adam_planes_on() && nets[0].do_adam && split_bf16_on(1) &&
-      rows % 32 == 0 && cols % 32 == 0) {
-    const float* W = nets[0].params + nets[0].pl_beg;
-    PlaneBuf* written = nullptr;
-    std::lock_guard<std::mutex> lock(g_plane_mu);
-    for (PlaneBuf& b : g_plane_bufs)
-      if (b.W == W && b.rows == rows && b.cols == cols) written = &b;
-    if (written) {  // (the forward launch of this step created it)
-      p.net[0].pl_fwd = reinterpret_cast<uint32_t*>(written->fwd);
-      p.net[0].pl_bwd = reinterpret_cast<uint32_t*>(written->bwd);
-      p.net[0].pl_beg = nets[0].pl_beg;
-      p.net[0].pl_rows = rows;
-      p.net[0].pl_cols = cols;
-      written->adam_fresh = true;
-      written->adam_stream = stream;
-      written->bwd_fresh = false;
-    }
-  }
-  const unsigned blocks = (unsigned)p.n_virtual + n_nets;  // + one loss block per network
+void ft_launch_fwd_dgrad(const FwdDgradParams& pp, FtVariant v, unsigned blocks,
+                         hipEvent_t e0, hipEvent_t e1, hipStream_t stream) {
+  if (v.width == 64)
+    FT_LAUNCH(256, pp, fwd_dgrad_kernel<64, 2, 2, 0>);
+  else if (v.width == 128)
+    FT_LAUNCH(256, pp, fwd_dgrad_kernel<128, 1, 4, 0>);
+  else if (v.ksc == 5)
+    FT_LAUNCH(512, pp, fwd_dgrad_kernel<256, 1, 8, 5>);
+  else
+    FT_LAUNCH(512, pp, fwd_dgrad_kernel<256, 1, 8, 0>);
+}
+#undef FT_LAUNCH
+
+void ft_launch_reduce_regions(const ReduceRegionsParams& p, unsigned blocks,
+                              hipStream_t stream) {
   hipLaunchKernelGGL(reduce_regions_adam_kernel, dim3(blocks), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH(n_nets == 2 ? "reduce_regions_adam_pair" : "reduce_regions_adam");
-  return GA_OK;
+}
+
+void ft_launch_split_planes(bool bwd_only, unsigned blocks, const float* W, int64_t ld,
+                            int rows, int cols, uint32_t* fwd, uint32_t* bwd,
+                            hipStream_t stream) {
+  if (bwd_only)
+    hipLaunchKernelGGL(split_planes_kernel<true>, dim3(blocks), dim3(256), 0, stream, W, ld,
+                       rows, cols, fwd, bwd);
+  else
+    hipLaunchKernelGGL(split_planes_kernel<false>, dim3(blocks), dim3(256), 0, stream, W,
+                       ld, rows, cols, fwd, bwd);
+}
+
+void ft_launch_mfma_burn(int mode, int iters, int blocks, float* sink, hipStream_t stream) {
+  hipLaunchKernelGGL(mfma_burn_kernel, dim3(blocks), dim3(512), 0, stream, mode, iters, sink);
 }

@@ -124,7 +124,7 @@ int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params, const f
                               hipStream_t stream);
 // policy_fused.hip: 1 when ga_policy_env_step_fused_f32 rescales the action inside its
 // launch under norm->act_low.  ga_rollout_env_steps asks before it hands such a rollout
-// to the one launch; a kernel side that answers 0 (tests/host/no_rescale_in_launch.cpp)
+// to the one launch; a kernel side that answers 0 (tests/host/rollout_loop_harness.cpp)
 // keeps the three launches per step.
 int ga_policy_env_step_rescales(void);
 // losses.hip: doubles of per-block partial sums at the front of the reduction

@@ -19,9 +19,8 @@
 // against exactly-sized buffers by tests/host/update_loop_harness.cpp, check 9).
 namespace {
 
-constexpr int NS_ROWS = 64;
+// (NS_ROWS = 64 rows per tile, NS_HN = 8 head outputs: shape_rules.h)
 constexpr int NS_THREADS = 256;
-constexpr int NS_HN = 8;
 
 typedef float ns_f32x16 __attribute__((ext_vector_type(16)));
 

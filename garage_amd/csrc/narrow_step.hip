@@ -52,15 +52,7 @@ extern "C" int ga_narrow_step_debug(long long* host_out16) {
                  hipSuccess ? 0 : -1;
 }
 
-extern "C" int ga_narrow_step_supported(int n_layers, const int* dims) {
-  return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&
-         dims[0] >= 1 && dims[0] <= 32 && dims[3] >= 1 && dims[3] <= 8;
-}
-
-extern "C" int64_t ga_narrow_step_stride(int in_w, int H) {
-  const int64_t ld0 = (in_w + 3) & ~3;
-  return (int64_t)H * ld0 + H + (int64_t)H * H + H + 8 * (int64_t)H + 8;
-}
+// (ga_narrow_step_supported, ga_narrow_step_stride: shape_rules.h)
 
 extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
                                     const int64_t* b_off, int in_w, int H, int out_w,

@@ -1,0 +1,63 @@
+// The kernel side's shape rules, each stated ONCE: which shapes a kernel family takes and
+// the tile arithmetic the host code sizes buffers and grids with (fused_train.hip,
+// narrow_step.hip, small_step.hip).  The kernels take their constants from here, the
+// library's host code and the CPU harnesses under tests/host the rules.  No device code.
+// Not part of the C ABI.
+#pragma once
+#include <stdint.h>
+
+// ---- fused_train.hip, narrow_body.h: a workgroup takes a 64-row tile of the minibatch
+constexpr int FT_ROWS = 64;          // rows per workgroup tile
+constexpr int FT_W1_FLOATS = 5120;   // LDS floats for the first layer's weights
+// ---- narrow_body.h: two hidden layers of equal width 32 or 64
+constexpr int NS_ROWS = FT_ROWS;     // (its launches size their grids by ga_fused_tiles)
+constexpr int NS_HN = 8;             // head outputs, at most
+// ---- small_step.hip: one tile of up to 64 rows, hidden width up to 256
+constexpr int SS_ROWS = 64;
+constexpr int SS_HMAX = 256;
+
+extern "C" {
+// workgroups (= partial sets) for M rows
+inline int64_t ga_fused_tiles(int64_t M) { return (M + FT_ROWS - 1) / FT_ROWS; }
+// the last hidden layer's width: one instantiation each
+inline int ga_fused_width_ok(int width) { return width == 64 || width == 128 || width == 256; }
+// the FIRST layer produced inside the forward kernel: in_w inputs, K units
+inline int ga_fused_first_layer_ok(int in_w, int K) {
+  return in_w >= 1 && in_w <= 32 && K >= 32 && K % 32 == 0 &&
+         (int64_t)K * ((in_w + 3) & ~3) <= FT_W1_FLOATS;
+}
+// Pair launches are compiled for 256-wide last hidden layers with the first layer in
+// the kernel (the C3-class networks the two-chain schedule was built for).
+inline int ga_fused_pair_supported(int width, int K, int in_w) {
+  return width == 256 && K <= 256 && ga_fused_first_layer_ok(in_w, K);
+}
+inline int ga_narrow_step_supported(int n_layers, const int* dims) {
+  return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&
+         dims[0] >= 1 && dims[0] <= 32 && dims[3] >= 1 && dims[3] <= NS_HN;
+}
+// floats of one tile's gradient shares: dW1 [H][round4(in_w)], db1, dW2 [H][H], db2,
+// dW_head [8][H], db_head [8]
+inline int64_t ga_narrow_step_stride(int in_w, int H) {
+  const int64_t ld0 = (in_w + 3) & ~3;
+  return (int64_t)H * ld0 + H + (int64_t)H * H + H + NS_HN * (int64_t)H + NS_HN;
+}
+}  // extern "C"
+
+// The rules behind the entry points that stay link-time seams (a harness makes them
+// answer 0): ga_fused_fwd_dgrad_supported, ga_fused_eval_supported and the shape part of
+// ga_small_step_supported are one-line wrappers over these.
+// fwd_dgrad_kernel is compiled for two hidden layers of the same width (K = the first
+// one's, width = the second one's) with the first layer in the kernel.
+inline int ga_fused_fwd_dgrad_rule(int width, int K, int in_w) {
+  return ga_fused_width_ok(width) && K == width && ga_fused_first_layer_ok(in_w, K);
+}
+inline int ga_fused_eval_rule(int n_layers, const int* dims) {
+  return n_layers == 3 && dims && ga_fused_first_layer_ok(dims[0], dims[1]) &&
+         dims[1] <= 256 && ga_fused_width_ok(dims[2]) && dims[3] >= 1 && dims[3] <= 8;
+}
+inline int ga_small_step_rule(int n_layers, const int* dims, int64_t M) {
+  if (n_layers != 3) return 0;
+  const int in_w = dims[0], H = dims[1], out_w = dims[3];
+  return dims[2] == H && H % 32 == 0 && H >= 32 && H <= SS_HMAX && in_w >= 1 &&
+         in_w <= 32 && out_w >= 1 && out_w <= 8 && M >= 1 && M <= SS_ROWS;
+}

@@ -29,6 +29,7 @@
 // agree to rounding, not bit for bit.
 #include "common.h"
 #include "loss_rows.h"
+#include "shape_rules.h"
 #include "small_step.h"
 
 // ---- Audit (round 3) of global loads whose lane / wave index can lie outside the
@@ -54,10 +55,9 @@
 // exactly-sized buffers under AddressSanitizer.
 namespace {
 
-constexpr int SS_ROWS = 64;
+// (SS_ROWS = 64 rows, SS_HMAX = 256 units: shape_rules.h)
 constexpr int SS_THREADS = 256;
 constexpr int SS_COLS = 16;     // hidden columns per workgroup
-constexpr int SS_HMAX = 256;
 constexpr int SS_LDH = SS_HMAX + 4;
 constexpr int SS_LDX = 36;
 constexpr int SS_LDO = 20;      // own-slice tiles [64][16 + 4]
@@ -715,10 +715,7 @@ __global__ __launch_bounds__(SS_THREADS) void small_step_kernel(SmallStepParams 
 // host side (called by update.cpp; not part of the C ABI)
 // ---------------------------------------------------------------------------
 extern "C" int ga_small_step_supported(int n_layers, const int* dims, int64_t M) {
-  if (n_layers != 3) return 0;
-  const int in_w = dims[0], H = dims[1], out_w = dims[3];
-  return dims[2] == H && H % 32 == 0 && H >= 32 && H <= SS_HMAX && in_w >= 1 &&
-         in_w <= 32 && out_w >= 1 && out_w <= 8 && M >= 1 && M <= SS_ROWS;
+  return ga_small_step_rule(n_layers, dims, M);
 }
 
 // Residency: the grid barriers need all H / 16 workgroups of a launch (and of the

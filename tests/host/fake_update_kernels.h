@@ -7,9 +7,9 @@
 #pragma once
 #include "../../garage_amd/csrc/fused_train.h"
 #include "../../garage_amd/csrc/internal.h"
+#include "../../garage_amd/csrc/shape_rules.h"
 #include "../../garage_amd/csrc/small_step.h"
 #include "harness.h"
-#include "shape_rules.h"
 
 // ---- switches; a suite sets each one it depends on at entry -----------------------------
 // ga_small_step_supported answers by the kernel's rule (default) or 0
@@ -184,7 +184,7 @@ int ga_adam_step_f32(float*, const float*, float*, float*, int64_t, int64_t step
 }
 int64_t ga_reduction_partials_doubles(void) { return 1024; }
 int ga_small_step_supported(int n_layers, const int* dims, int64_t M) {
-  return g_small_step_answers && small_step_rule(n_layers, dims, M);
+  return g_small_step_answers && ga_small_step_rule(n_layers, dims, M);
 }
 int ga_small_step_resident(int, int) { return 1; }
 int ga_small_step(const ga_small_step_args* a, void* s) {
@@ -239,7 +239,7 @@ int ga_fused_fwd_head_loss(const ga_fused_fwd_net* n, int n_nets, int64_t M, int
   return 0;
 }
 int ga_fused_fwd_dgrad_supported(int width, int K, int in_w) {
-  return g_fwd_dgrad_answers && fused_fwd_dgrad_rule(width, K, in_w);
+  return g_fwd_dgrad_answers && ga_fused_fwd_dgrad_rule(width, K, in_w);
 }
 int ga_fused_fwd_dgrad(const ga_fused_fwd_net* f, const ga_fused_dgrad_net* g, int64_t M,
                        int width, int K, hipStream_t s) {
@@ -251,7 +251,7 @@ int ga_fused_fwd_dgrad(const ga_fused_fwd_net* f, const ga_fused_dgrad_net* g, i
   // what the launch requires of its two descriptors
   CHECK(f && g && f->first && f->loss);
   if (f && g && f->first && f->loss) {
-    CHECK(fused_fwd_dgrad_rule(width, K, f->first->in_w));
+    CHECK(ga_fused_fwd_dgrad_rule(width, K, f->first->in_w));
     CHECK(g->dZ2 == f->dZ && g->lddz == f->lddz);
     CHECK(g->H1 == f->first->H && g->ldh == f->first->ldh);
     CHECK(g->X == f->first->X && g->ldx == f->first->ldx && g->idx == f->loss->idx);

@@ -116,6 +116,7 @@ static std::vector<long long> ms_of(const char* prefix) {
 static std::vector<size_t> g_host_allocs, g_dev_allocs, g_copies;  // bytes of each call
 static int g_events_recorded = 0;
 static int g_device = 0;  // what hipGetDevice answers
+static bool g_hip_malloc_fails = false;  // hipMalloc answers hipErrorOutOfMemory
 
 extern "C" {
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
@@ -124,6 +125,7 @@ hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
   return hipSuccess;
 }
 hipError_t hipMalloc(void** p, size_t bytes) {
+  if (g_hip_malloc_fails) return hipErrorOutOfMemory;
   g_dev_allocs.push_back(bytes);
   *p = malloc(bytes);
   return hipSuccess;

@@ -138,7 +138,7 @@ static void suite_loops() {
     const int64_t M = 1000;
     Net wide(17, {256, 256}, 6, M, M);
     const int64_t need = ga_update_partials_floats(&wide.d, M);
-    const int64_t tiles = (M + 63) / 64;
+    const int64_t tiles = ga_fused_tiles(M);
     CHECK(need == 4 * tiles + tiles * (8 * 256 + 8) + tiles * (256 * 20 + 256));
     CHECK(ga_update_partials_floats(&net.d, M) == 0);  // 48-wide: per-layer path
     ga_update_args a = wide.args(M, M, 0);

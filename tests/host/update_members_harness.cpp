@@ -11,8 +11,8 @@
 #include "../../garage_amd/csrc/fused_train.h"
 #include "../../garage_amd/csrc/internal.h"
 #include "../../garage_amd/csrc/members_step.h"
+#include "../../garage_amd/csrc/shape_rules.h"
 #include "harness.h"
-#include "shape_rules.h"
 
 // ---- what the fakes record -----------------------------------------------------
 struct StepRecord {
@@ -25,7 +25,7 @@ static std::vector<StepRecord> g_train, g_reduce;
 // the host's view of the pass under test (for the reduce fake's Adam check)
 static const ga_update_members_args* g_args = nullptr;
 
-// ---- kernel-side fakes (the shape rules: shape_rules.h) ----------------------------------
+// ---- kernel-side fakes (the shape rules: csrc/shape_rules.h) ----------------------------------
 extern "C" {
 static int64_t rows_of(const GaMemberDev& m, int64_t mb, int64_t k) {
   if (k >= m.n_steps) return 0;
@@ -42,7 +42,7 @@ int ga_members_train_step(const GaMembersShared* sh, const GaMemberDev* table, i
     if (M <= 0) continue;
     long long sum = 0;
     for (int64_t i = 0; i < M; ++i) sum += t.perm ? t.perm[k * sh->mb + i] : i;
-    const int64_t tiles = (M + 63) / 64;
+    const int64_t tiles = ga_fused_tiles(M);
     CHECK(tiles <= max_tiles);
     for (int64_t tile = 0; tile < tiles; ++tile) {  // what a tile writes
       for (int64_t e = 0; e < sh->stride; ++e) t.part[tile * sh->stride + e] = 1.f;
@@ -160,7 +160,7 @@ static void check_pass(int n, int64_t mb) {
     if (rows > largest) largest = rows;
   }
   CHECK(p.a.partials_floats ==
-        n * ((largest + 63) / 64) * (4 + ga_narrow_step_stride(4, 64)));
+        n * ga_fused_tiles(largest) * (4 + ga_narrow_step_stride(4, 64)));
   const int rc = ga_update_epoch_members(&p.a, nullptr);
   CHECK(rc == 0);
   int64_t steps[5], n_steps = 0;
@@ -202,7 +202,7 @@ static void check_pass(int n, int64_t mb) {
       if (hi - lo > max_rows) max_rows = hi - lo;
     }
     CHECK(t.active == active && r.active == active);
-    CHECK(t.max_tiles == (max_rows + 63) / 64 && r.max_tiles == t.max_tiles);
+    CHECK(t.max_tiles == ga_fused_tiles(max_rows) && r.max_tiles == t.max_tiles);
   }
 }
 
