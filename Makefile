@@ -7,7 +7,7 @@ ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
 HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -76,7 +76,8 @@ ASAN_PROGRAMS := \
   mlp_layers_asan_test:mlp_layers_harness:mlp_layers \
   update_members_asan_test:update_members_harness:update_members \
   member_pack_asan_test:member_pack_harness:member_pack_host \
-  fused_host_asan_test:fused_host_harness:fused_train_host
+  fused_host_asan_test:fused_host_harness:fused_train_host \
+  rollout_host_asan_test:rollout_host_harness:rollout_host
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -135,9 +136,16 @@ asan-member-pack: $(OUT)/member_pack_asan_test
 asan-fused-host: $(OUT)/fused_host_asan_test
 	$(OUT)/fused_host_asan_test
 
+# The rollout step's host side (rollout_host.cpp) against fakes of the launch seam: the
+# kernel choice, grid, member split and profile counts against a literal table, every
+# refusal of every entry point before any launch for every env kind, the conversions of
+# the C-ABI structs field by field, the debug hook's buffer.
+asan-rollout-host: $(OUT)/rollout_host_asan_test
+	$(OUT)/rollout_host_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
-  asan-members asan-member-pack asan-fused-host asan-all
+  asan-members asan-member-pack asan-fused-host asan-rollout-host asan-all

@@ -39,7 +39,7 @@ int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const fl
                     int64_t lddz, hipStream_t stream);
 
 // ---- device envs: what every kind states about itself, and the ONE dispatch from a
-// ga_env_ref to its typed struct (rollout.hip, policy_fused.hip, rollout_loop.cpp).
+// ga_env_ref to its typed struct (rollout_host.cpp, rollout_loop.cpp).
 // Every struct has `n`; the observation width, the columns of an action row and
 // whether the action is a class index are the overloads below.
 //
@@ -76,6 +76,17 @@ inline int ga_env_act_width(const ga_multi_point_env*) { return 2; }
 GA_STATE_ENV_KINDS(GA_STATE_ENV_FACTS)
 #undef GA_STATE_ENV_FACTS
 
+// EVERY device env kind, once: X(C-ABI struct, kind code, ...) -- the four kinds written by
+// hand and the rows of GA_STATE_ENV_KINDS with their further columns.  ga_visit_env's
+// switch and the per-kind instantiations of the launch seam (rollout_params.h) are
+// generated from it.
+#define GA_ENV_KINDS(X)                       \
+  X(ga_synth_env, GA_ENV_SYNTH)               \
+  X(ga_point_env, GA_ENV_POINT)               \
+  X(ga_grid_env, GA_ENV_GRID)                 \
+  X(ga_multi_point_env, GA_ENV_MULTI_POINT)   \
+  GA_STATE_ENV_KINDS(X)
+
 // f(const ga_<kind>_env*) of the env `ref` points to; `who` names the entry point in
 // the two errors this owns
 template <class F>
@@ -85,30 +96,21 @@ int ga_visit_env(const ga_env_ref* ref, const char* who, F&& f) {
     return -1;
   }
   switch (ref->kind) {
-    case GA_ENV_SYNTH: return f((const ga_synth_env*)ref->env);
-    case GA_ENV_POINT: return f((const ga_point_env*)ref->env);
-    case GA_ENV_GRID: return f((const ga_grid_env*)ref->env);
-    case GA_ENV_MULTI_POINT: return f((const ga_multi_point_env*)ref->env);
-#define GA_STATE_ENV_CASE(GaEnv, KIND, DEV, OBS, DISCRETE) \
+#define GA_ENV_CASE(GaEnv, KIND, ...) \
   case KIND: return f((const GaEnv*)ref->env);
-    GA_STATE_ENV_KINDS(GA_STATE_ENV_CASE)
-#undef GA_STATE_ENV_CASE
+    GA_ENV_KINDS(GA_ENV_CASE)
+#undef GA_ENV_CASE
   }
   ga_set_error("%s: unknown env kind %d", who, ref->kind);
   return -1;
 }
 
-// The networks policy_fused.hip's step kernel takes at WIDTH = 512 (layer inputs up to 512, a
-// head up to 32, up to 8 layers, activation codes 0 .. 6): a superset of what
-// ga_policy_step_fused_supported accepts.  ga_policy_step_wide_supported and
-// ga_rollout_env_steps both ask here.
-static inline int ga_step_wide_rule(const ga_mlp_desc* d) {
-  if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
-  if (d->hidden_act < 0 || d->hidden_act > 6 || d->output_act < 0 || d->output_act > 6)
-    return 0;
-  for (int l = 0; l < d->n_layers; ++l)
-    if (d->dims[l] > 512) return 0;
-  return d->dims[d->n_layers] <= 32;
+// What NormalizedEnv's action rescale (norm->act_low set) needs, stated once:
+// ga_rollout_env_steps and ga_build_env_step (rollout_host.cpp) both refuse through here.
+inline int ga_rescale_refused(const ga_norm_args* norm, int discrete, const char* who) {
+  if (norm->act_high && norm->scaled_action && !discrete) return 0;
+  ga_set_error("%s: action rescale needs bounds, scratch and a continuous action space", who);
+  return -1;
 }
 
 extern "C" {

@@ -22,18 +22,16 @@
 // and layer_norm in a second set of instantiations (GEN = true) whose epilogues
 // apply gemm_core.h's activations to the same sums and which normalise each hidden
 // layer's input rows in LDS (ln_rows_w, lnorm.hip's formula).
-// The parameters describe the network as NetDev (net_to_dev, below) and the head as
-// rollout_dev.h's HeadDev (ga_head_to_dev), the struct the per-layer head kernel takes.
+// The parameters describe the network as NetDev and the head as HeadDev
+// (rollout_params.h; filled by rollout_host.cpp), the struct the per-layer head kernel takes.
 // With a device env (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv,
 // CartPole, Pendulum, the inverted double pendulum, Acrobot, MountainCar: a template
 // parameter of the kernel) the
 // thread that sampled an env's action
 // also steps it, and a whole rollout is ONE launch with the weights resident on the CU (see the kernel).
-#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
-#include "prof.h"
 
 #include "gemm_core.h"  // act_apply / act_forward_code: the per-layer epilogue's own
 #include "rollout_dev.h"
@@ -63,14 +61,15 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int ROWS = 16;          // envs per workgroup (one 16 x 16 MFMA tile of rows)
-constexpr int HMAX = 256;         // output columns per panel; widest layer of the
-                                  // WIDTH = 256 kernels and the training forward
-constexpr int LDACT = HMAX + 4;   // the training forward's activation row stride (floats)
-constexpr int KC = 32;            // k chunk
-constexpr int LDW = KC + 4;       // weight stage row stride
-constexpr int MAX_OUT = 32;       // widest output head
-constexpr int WMAX = 512;         // widest layer input of the WIDTH = 512 step kernels
+// (shape_rules.h states them once, for the host side too)
+constexpr int ROWS = PS_ROWS;       // envs per workgroup (one 16 x 16 MFMA tile of rows)
+constexpr int HMAX = PS_HMAX;       // output columns per panel; widest layer of the
+                                    // WIDTH = 256 kernels and the training forward
+constexpr int LDACT = HMAX + 4;     // the training forward's activation row stride (floats)
+constexpr int KC = PS_KC;           // k chunk
+constexpr int LDW = KC + 4;         // weight stage row stride
+constexpr int MAX_OUT = PS_MAX_OUT; // widest output head
+constexpr int WMAX = PS_WMAX;       // widest layer input of the WIDTH = 512 step kernels
 
 // (tanh_fast: gemm_core.h)
 
@@ -102,43 +101,7 @@ __device__ __forceinline__ void act_dispatch(int act, F&& f) {
   }
 }
 
-// the layers of a ga_mlp_desc (net_to_dev)
-struct NetDev {
-  int n_layers;
-  int dims[9];
-  int64_t w_off[8], b_off[8];
-};
-
-constexpr int ENV_STEP_RESCALE = 2;  // bit of FusedParams::env_step
-
-template <class Env>
-struct FusedParams {
-  NetDev net;
-  const float* params;
-  ga_rollout::HeadDev hd;  // the step's head and rollout-buffer writes (rollout_dev.h)
-  // env_step: the env's step, the NormalizedEnv statistics, the bookkeeping and the
-  // reset of finished envs follow in the same launch, each env by the thread that
-  // sampled its action (rollout_dev.h: the code of env_step_record_kernel);
-  // | ENV_STEP_RESCALE: es.nm.act_low is set, the env steps on the rescaled action
-  int env_step;
-  ga_rollout::EnvStepArgsT<Env> es;
-  // n_steps > 1 (needs env_step): the workgroup takes its envs through n_steps
-  // consecutive rollout steps in this one launch -- nothing couples the envs of
-  // different workgroups within a rollout -- alternating between the two
-  // observation buffers (obs / es.seen_next and, with observation normalisation,
-  // es.raw_obs / es.raw_next)
-  int n_steps;
-  // a population of parameter vectors behind one launch: workgroups
-  // [m * wg_per_member, (m + 1) * wg_per_member) read member m's vector at
-  // params + m * member_stride floats (one policy: stride 0, wg_per_member 1)
-  int wg_per_member;
-  int member_stride;
-  long long* dbg;  // developer hook: phase timestamps of workgroup 0
-  // GEN kernels only (behind everything the tanh kernels read): the descriptor's
-  // network options -- hidden_act in network code, output_act in forward code
-  int hidden_act, output_act, layer_norm;
-  int64_t ln_off[8];
-};
+// (NetDev, FusedParams<Env>, ENV_STEP_RESCALE, TrainFwdParams: rollout_params.h)
 
 #define PS_STAMP(i) \
   if (p.dbg && blockIdx.x == 0 && threadIdx.x == 0 && sidx == p.n_steps / 2) \
@@ -705,20 +668,7 @@ __global__ __launch_bounds__(256) void policy_step_fused_kernel(FusedParams<Env>
 // backward pass; the narrow output layer is a 16-lane VALU dot.  Replaces the
 // three per-layer GEMM launches of ga_mlp_forward_f32 (the activations' HBM
 // read between layers disappears, the weights come from L2).
-struct TrainFwdParams {
-  NetDev net;
-  int64_t act_off[8];
-  const float* params;
-  const float* X;
-  int64_t ldx;
-  const int32_t* idx;
-  int64_t M;
-  float* acts;
-  float* out;
-  int64_t ldo;
-};
-
-constexpr int TROWS = 64;  // rows per workgroup of the training forward
+constexpr int TROWS = PS_TRAIN_ROWS;  // rows per workgroup of the training forward
 
 __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams p) {
   // 64 rows x 8 waves: wave (ri, cj) owns rows [32 ri, 32 ri + 32) and columns
@@ -847,168 +797,10 @@ __global__ __launch_bounds__(512) void mlp_train_fwd_fused_kernel(TrainFwdParams
 
 }  // namespace
 
-static NetDev net_to_dev(const ga_mlp_desc* d) {
-  NetDev n;
-  n.n_layers = d->n_layers;
-  for (int i = 0; i < 9; ++i) n.dims[i] = d->dims[i];
-  for (int i = 0; i < 8; ++i) { n.w_off[i] = d->w_off[i]; n.b_off[i] = d->b_off[i]; }
-  return n;
-}
-
-// 1 when ga_policy_step_fused_f32 supports this network shape.
-extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
-  if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
-  // every nonlinearity the descriptor can name, with or without layer normalisation
-  if (d->hidden_act < 0 || d->hidden_act > 6 || d->output_act < 0 || d->output_act > 6)
-    return 0;
-  for (int l = 0; l < d->n_layers; ++l)
-    if (d->dims[l] > HMAX) return 0;  // every layer INPUT lives in an LDS tile
-  if (d->dims[d->n_layers] > MAX_OUT) return 0;
-  return 1;
-}
-
-// GARAGE_AMD_ROLLOUT_WIDE=0: networks only the WIDTH = 512 kernels take go back to the
-// per-layer path (A/B runs)
-static bool g_ps_no_wide = getenv("GARAGE_AMD_ROLLOUT_WIDE") &&
-                           atoi(getenv("GARAGE_AMD_ROLLOUT_WIDE")) == 0;
-
-// 1 when ga_policy_step_fused_f32 / ga_policy_env_step_fused_f32 / ga_rollout_env_steps
-// take this network: what the predicate above accepts (the kernels it always had), or
-// layer inputs up to 512 (internal.h: ga_step_wide_rule; the WIDTH = 512 kernels).
-extern "C" int ga_policy_step_wide_supported(const ga_mlp_desc* d) {
-  if (ga_policy_step_fused_supported(d)) return 1;
-  return !g_ps_no_wide && ga_step_wide_rule(d);
-}
-
-// `head` of args is ignored (the means / scores stay on chip); everything else
-// as in ga_policy_head_sample.
-template <class Env>
-static int policy_step_launch(const ga_mlp_desc* d, const float* params,
-                              const ga_head_args* a,
-                              const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
-                              hipStream_t stream, int64_t n_members = 0,
-                              int64_t member_stride = 0);
-
-static bool g_ps_no_resident = getenv("GARAGE_AMD_ROLLOUT_RESIDENT") &&
-                               atoi(getenv("GARAGE_AMD_ROLLOUT_RESIDENT")) == 0;
-static long long* g_ps_dbg = nullptr;
-// developer hook: phase timestamps (100 MHz wall clock) of workgroup 0 of the most
-// recent fused rollout step -- first call arms it, second call reads 32 values back
-// (0 start, 1 observations staged, 2 + l hidden layer l done, 10 output layer,
-// 11 sampled + env stepped; + 16: the same of the resident-weights kernel; the middle step of the launch;
-// the WIDTH = 512 kernels write the streamed slots)
-extern "C" int ga_policy_step_debug(long long* host_out32) {
-  if (!g_ps_dbg) {
-    if (hipMalloc(&g_ps_dbg, 32 * sizeof(long long)) != hipSuccess) return -1;
-    (void)hipMemset(g_ps_dbg, 0, 32 * sizeof(long long));
-    return 1;
-  }
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host_out32, g_ps_dbg, 32 * sizeof(long long), hipMemcpyDeviceToHost) ==
-                 hipSuccess ? 0 : -1;
-}
-
-extern "C" int ga_policy_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                        const ga_head_args* a, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  return policy_step_launch<ga_rollout::SynthEnv>(d, params, a, nullptr, 1, stream);
-}
-
-// The same launch followed, per env, by the env's step + NormalizedEnv statistics +
-// bookkeeping + reset (what ga_env_step_record does as its own launch), for n_steps
-// consecutive rollout steps: every workgroup takes its 32 envs through all of them
-// (nothing couples envs within a rollout), alternating between `a->obs` and
-// `rec->next_obs` (and the raw pair of `norm`).  `a->action` is what the env is
-// stepped with -- or, with norm->act_low set, its rescaled copy in
-// norm->scaled_action, which the env thread writes (ga_build_env_step refuses missing
-// bounds or scratch and a discrete kind; none of the checks touches the device).
-static int policy_env_step(const char* who, const ga_mlp_desc* d, const float* params,
-                           const ga_head_args* a, const ga_env_ref* ref,
-                           const ga_record_args* rec, const ga_norm_args* norm,
-                           int64_t n_steps, int64_t n_members, int64_t member_stride,
-                           ga_stream_t stream) {
-  return ga_visit_env(ref, who, [&](auto* env) {
-    GA_REQUIRE(a && rec, "%s: null pointer", who);
-    GA_REQUIRE(n_steps >= 1 && a->col + n_steps <= a->Tcap,
-               "%s: steps exceed the rollout buffer", who);
-    GA_REQUIRE(!a->noise || n_steps == 1, "%s: teacher-forced noise is per step", who);
-    using GaEnv = std::remove_cv_t<std::remove_pointer_t<decltype(env)>>;
-    ga_env_step_args_t<GaEnv> es;
-    int rc = ga_build_env_step(env, rec, norm, a->action, a->lda, a->obs, who, &es,
-                               /*rescale_inside=*/true);
-    if (rc) return rc;
-    GA_REQUIRE(es.e.n == a->n, "%s: env count mismatch", who);
-    // (the kernel rescales the head's A columns)
-    GA_REQUIRE(!es.nm.act_low || a->A == ga_env_act_width(env),
-               "%s: action rescale of %d columns for an env of %d", who, a->A,
-               ga_env_act_width(env));
-    GA_REQUIRE(es.p.col == a->col && es.p.col + n_steps <= es.p.Tcap,
-               "%s: record columns do not match the policy's", who);
-    return policy_step_launch(d, params, a, &es, n_steps, (hipStream_t)stream, n_members,
-                              member_stride);
-  });
-}
-
-// (internal.h: what ga_rollout_env_steps asks before it sends a rescaled rollout here)
-extern "C" int ga_policy_env_step_rescales(void) { return 1; }
-
-extern "C" int ga_policy_env_step_fused_f32(const ga_mlp_desc* d, const float* params,
-                                            const ga_head_args* a, const ga_env_ref* ref,
-                                            const ga_record_args* rec,
-                                            const ga_norm_args* norm, int64_t n_steps,
-                                            ga_stream_t stream) {
-  return policy_env_step("ga_policy_env_step_fused_f32", d, params, a, ref, rec, norm,
-                         n_steps, 0, 0, stream);
-}
-
-// floats of the parameter vector `d` describes: the end of its last block
-static int64_t desc_flat_size(const ga_mlp_desc* d) {
-  int64_t end = 4;
-  for (int l = 0; l < d->n_layers; ++l) {
-    end = std::max(end, d->w_off[l] + (int64_t)d->dims[l + 1] * ((d->dims[l] + 3) & ~3));
-    end = std::max(end, d->b_off[l] + ((d->dims[l + 1] + 3) & ~3));
-    if (d->layer_norm && l + 1 < d->n_layers)
-      end = std::max(end, d->ln_off[l] + 2 * ((d->dims[l] + 3) & ~3));
-  }
-  return end;
-}
-
-// The same launch over a population: member m's envs [m g, (m + 1) g), g = n /
-// n_members, are stepped by the parameter vector at params + m * member_stride.  Every
-// check precedes the first device call.
-extern "C" int ga_policy_env_step_members_f32(const ga_mlp_desc* d, const float* params,
-                                              const ga_head_args* a, const ga_env_ref* ref,
-                                              const ga_record_args* rec,
-                                              const ga_norm_args* norm, int64_t n_steps,
-                                              int64_t n_members, int64_t member_stride,
-                                              ga_stream_t stream) {
-  const char* who = "ga_policy_env_step_members_f32";
-  GA_REQUIRE(d && params && a && ref && rec, "%s: null pointer", who);
-  GA_REQUIRE(n_members >= 1, "%s: n_members must be at least 1", who);
-  GA_REQUIRE(a->n > 0 && a->n % n_members == 0,
-             "%s: %lld envs do not split into %lld members", who, (long long)a->n,
-             (long long)n_members);
-  // (one member is the single-policy launch, whose last workgroup may be ragged)
-  GA_REQUIRE(n_members == 1 || a->n / n_members % ROWS == 0,
-             "%s: %lld envs per member are not a multiple of the %d rows of a workgroup",
-             who, (long long)(a->n / n_members), ROWS);
-  GA_REQUIRE(ga_policy_step_wide_supported(d),
-             "%s: network not supported by the fused step", who);
-  GA_REQUIRE(member_stride % 4 == 0 && member_stride >= desc_flat_size(d),
-             "%s: member_stride %lld is not a multiple of 4 floats or is smaller than "
-             "the %lld floats of a parameter vector",
-             who, (long long)member_stride, (long long)desc_flat_size(d));
-  // (the kernel adds a member's offset as a 32-bit count of floats)
-  GA_REQUIRE((n_members - 1) * member_stride + desc_flat_size(d) < (1ll << 31),
-             "%s: %lld members x %lld floats exceed 2^31 floats", who,
-             (long long)n_members, (long long)member_stride);
-  GA_REQUIRE(!a->noise, "%s: teacher-forced noise is not supported", who);
-  GA_REQUIRE(!(norm && norm->act_low),
-             "%s: the action rescale is its own launch (not supported)", who);
-  return policy_env_step(who, d, params, a, ref, rec, norm, n_steps, n_members,
-                         member_stride, stream);
-}
-
+// ---------------------------------------------------------------------------
+// The launch seam (rollout_params.h): instantiate and launch, nothing else.  The
+// checks, the parameters, the choice of the variant and the grid are rollout_host.cpp's.
+// ---------------------------------------------------------------------------
 template <int WIDTH, bool RES, class Env>
 static void step_kernel_launch(bool general, dim3 grid, hipStream_t stream,
                                const FusedParams<Env>& p) {
@@ -1021,88 +813,23 @@ static void step_kernel_launch(bool general, dim3 grid, hipStream_t stream,
 }
 
 template <class Env>
-static int policy_step_launch(const ga_mlp_desc* d, const float* params,
-                              const ga_head_args* a,
-                              const ga_rollout::EnvStepArgsT<Env>* es, int64_t n_steps,
-                              hipStream_t stream, int64_t n_members,
-                              int64_t member_stride) {
-  GA_REQUIRE(d && params && a, "ga_policy_step_fused_f32: null pointer");
-  // every descriptor the old predicate accepts keeps the kernel it had
-  const bool wide = !ga_policy_step_fused_supported(d);
-  GA_REQUIRE(!wide || ga_policy_step_wide_supported(d),
-             "ga_policy_step_fused_f32: unsupported network shape");
-  GA_REQUIRE(a->obs && a->action && a->obs_buf && a->act_buf,
-             "ga_policy_step_fused_f32: null buffer");
-  GA_REQUIRE(a->n > 0 && a->A == d->dims[d->n_layers] && a->obs_dim == d->dims[0],
-             "ga_policy_step_fused_f32: head / network size mismatch");
-  GA_REQUIRE(a->col >= 0 && a->col < a->Tcap,
-             "ga_policy_step_fused_f32: col out of range");
-  GA_REQUIRE(ga_aligned16(params), "ga_policy_step_fused_f32: params alignment");
-  if (d->layer_norm)
-    for (int l = 0; l + 1 < d->n_layers; ++l)
-      GA_REQUIRE(d->ln_off[l] > 0 && d->ln_off[l] % 4 == 0,
-                 "ga_policy_step_fused_f32: ln_off[%d] is not a multiple of 4", l);
-  FusedParams<Env> p;
-  p.net = net_to_dev(d);
-  p.params = params;
-  p.hd = ga_head_to_dev(a);
-  p.dbg = g_ps_dbg;
-  p.hidden_act = d->hidden_act; p.output_act = d->output_act;
-  p.layer_norm = d->layer_norm != 0;
-  for (int i = 0; i < 8; ++i) p.ln_off[i] = d->ln_off[i];
-  p.env_step = es ? (es->nm.act_low ? 1 | ENV_STEP_RESCALE : 1) : 0;
-  p.n_steps = (int)n_steps;
-  const dim3 grid((unsigned)ga_ceil_div(a->n, ROWS));
-  // n_members > 1 (ga_policy_env_step_members_f32, which checked the split): member m
-  // owns the grid.x / n_members workgroups of its envs
-  p.wg_per_member = n_members > 1 ? (int)(grid.x / n_members) : 1;
-  p.member_stride = n_members > 1 ? (int)member_stride : 0;
-  if (es) p.es = *es;
-  else memset(&p.es, 0, sizeof(p.es));
-  // a whole rollout in one launch keeps the weights on the CU (see the kernel)
-  const bool resident = n_steps > 1 && d->dims[0] <= KC &&
-                        (d->n_layers == 2 || d->n_layers == 3) && !g_ps_no_resident;
-  // the tanh / linear-output / no-LayerNorm network keeps the kernel it always had
-  const bool general = d->hidden_act != 0 || d->output_act != 0 || d->layer_norm;
-  // every descriptor the old predicate accepts runs at WIDTH = HMAX
-  // (the population entry point counts its rollouts as kind 13 whatever the kernel)
-  if (n_members >= 1 && n_steps > 1 && (wide || !resident)) ga_prof_count(GA_PROF_ROLLOUT);
-  if (wide) {
-    if (n_steps > 1) ga_prof_count(GA_PROF_ROLLOUT_WIDE);
-    step_kernel_launch<WMAX, false>(general, grid, stream, p);
-    GA_CHECK_LAUNCH("policy_step_wide");
-    return GA_OK;
-  }
-  if (resident) ga_prof_count(GA_PROF_ROLLOUT);
-  if (resident) step_kernel_launch<HMAX, true>(general, grid, stream, p);
-  else step_kernel_launch<HMAX, false>(general, grid, stream, p);
-  GA_CHECK_LAUNCH("policy_step_fused");
-  return GA_OK;
+void ps_launch_policy_step(const FusedParams<Env>& p, PsVariant v, unsigned blocks,
+                           hipStream_t stream) {
+  const dim3 grid(blocks);
+  if (v.width == WMAX) step_kernel_launch<WMAX, false>(v.general, grid, stream, p);
+  else if (v.resident) step_kernel_launch<HMAX, true>(v.general, grid, stream, p);
+  else step_kernel_launch<HMAX, false>(v.general, grid, stream, p);
+}
+#define GA_POLICY_STEP_OF(GaEnv, ...)                                                    \
+  template void ps_launch_policy_step(const FusedParams<ga_env_dev_t<GaEnv>>&, PsVariant, \
+                                      unsigned, hipStream_t);
+GA_ENV_KINDS(GA_POLICY_STEP_OF)
+#undef GA_POLICY_STEP_OF
+
+void ps_launch_train_forward(const TrainFwdParams& p, unsigned blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(mlp_train_fwd_fused_kernel, dim3(blocks), dim3(512), 0, stream, p);
 }
 
-// Training / evaluation forward of the whole MLP in one launch (same contract
-// as ga_mlp_forward_f32, which dispatches here when the shape is supported).
-extern "C" int ga_mlp_forward_fused_f32(const ga_mlp_desc* d, const float* params,
-                                        const float* X, int64_t ldx,
-                                        const int32_t* row_idx, int64_t M,
-                                        float* acts, float* out, int64_t ldo,
-                                        ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(d && params && X && out, "ga_mlp_forward_fused_f32: null pointer");
-  // (this kernel is the tanh network only; the rollout step's predicate is wider)
-  GA_REQUIRE(ga_policy_step_fused_supported(d) && d->hidden_act == 0 &&
-                 d->output_act == 0 && !d->layer_norm,
-             "ga_mlp_forward_fused_f32: unsupported network shape or options");
-  GA_REQUIRE(d->n_layers == 1 || acts, "ga_mlp_forward_fused_f32: acts needed");
-  GA_REQUIRE(M > 0 && M < (1ll << 31), "ga_mlp_forward_fused_f32: bad M");
-  GA_REQUIRE(ga_aligned16(params), "ga_mlp_forward_fused_f32: params alignment");
-  TrainFwdParams p;
-  p.net = net_to_dev(d);
-  for (int i = 0; i < 8; ++i) p.act_off[i] = d->act_off[i];
-  p.params = params; p.X = X; p.ldx = ldx; p.idx = row_idx; p.M = M; p.acts = acts;
-  p.out = out; p.ldo = ldo;
-  hipLaunchKernelGGL(mlp_train_fwd_fused_kernel, dim3((unsigned)ga_ceil_div(M, TROWS)),
-                     dim3(512), 0, stream, p);
-  GA_CHECK_LAUNCH("mlp_train_fwd_fused");
-  return GA_OK;
-}
+// (internal.h: what ga_rollout_env_steps asks before it sends a rescaled rollout to
+// ga_policy_env_step_fused_f32.  A link-time answer: the loop's harness fakes it.)
+extern "C" int ga_policy_env_step_rescales(void) { return 1; }

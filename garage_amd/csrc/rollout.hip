@@ -2,16 +2,14 @@
 // (synthetic, PointEnv, GridWorldEnv, MultiEnvWrapper over PointEnv, CartPole,
 // Pendulum, the inverted double pendulum, Acrobot, MountainCar), per-step
 // episode bookkeeping and the ragged -> packed compaction.  A step's device code is
-// rollout_dev.h's; here are its kernels and the one converter and check of each C-ABI
-// struct: ga_head_to_dev, ga_record_to_dev / check_record, ga_env_to_dev / check_env.
+// rollout_dev.h's and its host side rollout_host.cpp's; here are its kernels behind the
+// launch seam of rollout_params.h.
 //
 // Together they replace the Python per-env loop of VecWorker.step_episode /
 // _gather_episode / collect_episode (sampler/vec_worker.py:139-219) and
 // StochasticPolicy.get_actions' dist.sample() (torch/policies/stochastic_policy.py:
 // 46-89).  Rollout buffers are env-major (n_envs, Tcap[, width]) in HBM; one
 // thread owns one env (its row tails are 16-B friendly: widths are padded to 4).
-#include <type_traits>
-
 #include "common.h"
 
 #include "rollout_dev.h"
@@ -69,15 +67,7 @@ __global__ __launch_bounds__(256) void reward_normalize_kernel(
 }
 
 // ---- action head ---------------------------------------------------------------
-// the shared description of a step's head plus what only the per-layer path reads
-struct HeadParams {
-  HeadDev hd;
-  int A;                 // action dim (gaussian) or number of classes (categorical)
-  const float* head;     // [n, ldh] means or class scores
-  const float* log_std;  // gaussian: device scalar
-  int obs_dim;
-};
-
+// (HeadParams: rollout_params.h)
 // The step's observations into the rollout buffer (the list append of
 // vec_worker.py:188), by the whole workgroup: consecutive threads copy consecutive
 // columns of a row.  (One thread per env copying its own row -- obs_dim strided
@@ -387,329 +377,54 @@ __global__ __launch_bounds__(256) void feistel_perm_kernel(int64_t n, int half_b
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// C ABI (see include/garage_amd.h)
+// The launch seam of a rollout step (rollout_params.h): instantiate and launch, nothing
+// else.  The checks, the conversions of the C-ABI structs and the grids are
+// rollout_host.cpp's.
 // ---------------------------------------------------------------------------
-// the kernel-side head of a step (rollout_dev.h)
-HeadDev ga_head_to_dev(const ga_head_args* a) {
-  HeadDev d;
-  d.n = a->n; d.env_id0 = a->env_id0; d.kind = a->kind; d.has_min = a->has_min;
-  d.has_max = a->has_max; d.min_log_std = a->min_log_std; d.max_log_std = a->max_log_std;
-  d.noise = a->noise; d.ldn = a->ldn; ga_key(a->seed, &d.k0, &d.k1); d.step = a->step;
-  d.double_softmax = a->double_softmax; d.obs = a->obs; d.ldo = a->ldo; d.col = a->col;
-  d.Tcap = a->Tcap; d.action = a->action; d.lda = a->lda; d.obs_buf = a->obs_buf;
-  d.act_buf = a->act_buf; d.head_buf = a->head_buf; d.ldh = a->ldh;
-  return d;
+void ro_launch_head_sample(const HeadParams& p, unsigned blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(head_sample_kernel, dim3(blocks), dim3(256), 0, stream, p);
 }
 
-// the kernel-side record of a step, and its checks (`n`: the batch it must cover)
-static RecordParams ga_record_to_dev(const ga_record_args* a) {
-  RecordParams p;
-  p.n = a->n; p.col = a->col; p.Tcap = a->Tcap;
-  p.max_episode_length = a->max_episode_length; p.reward = a->reward;
-  p.step_type = a->step_type; p.next_obs = a->next_obs; p.ldo = a->ldo;
-  p.obs_dim = a->obs_dim; p.ep_t = a->ep_t; p.rew_buf = a->rew_buf;
-  p.st_buf = a->st_buf; p.tail_buf = a->tail_buf; p.lastobs_buf = a->lastobs_buf;
-  p.done = a->done; p.step_eps = a->step_eps; p.step_samples = a->step_samples;
-  p.terminal_only = a->terminal_only;
-  return p;
+void ro_launch_record(const RecordParams& p, unsigned blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(record_step_kernel, dim3(blocks), dim3(256), 0, stream, p);
 }
 
-static int check_record(const ga_record_args* a, int64_t n, const char* who) {
-  GA_REQUIRE(a->reward && a->step_type && a->next_obs && a->ep_t && a->rew_buf &&
-                 a->st_buf && a->tail_buf && a->lastobs_buf && a->done &&
-                 a->step_eps && a->step_samples,
-             "%s: null pointer", who);
-  GA_REQUIRE(a->n == n && n > 0 && a->col >= 0 && a->col < a->Tcap,
-             "%s: col %lld out of range (Tcap %lld)", who, (long long)a->col,
-             (long long)a->Tcap);
-  GA_REQUIRE(a->max_episode_length >= 1 && a->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  // (the terminal observation is copied row to row, as ga_policy_head_sample's)
-  GA_REQUIRE(a->obs_dim >= 0 && a->ldo >= a->obs_dim,
-             "%s: leading dimensions too small (observation rows of %lld columns, "
-             "obs_dim %d)", who, (long long)a->ldo, (int)a->obs_dim);
-  return GA_OK;
+template <class Env>
+void ro_launch_env_reset(const Env& e, const uint8_t* mask, float* obs, int64_t ldo,
+                         unsigned blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(env_reset_kernel<Env>, dim3(blocks), dim3(256), 0, stream, e, mask,
+                     obs, ldo);
 }
 
-extern "C" int ga_policy_head_sample(const ga_head_args* a, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(a && a->head && a->obs && a->action && a->obs_buf && a->act_buf,
-             "ga_policy_head_sample: null pointer");
-  GA_REQUIRE(a->n > 0 && a->A > 0 && a->ldh >= a->A && a->ldo >= a->obs_dim,
-             "ga_policy_head_sample: bad sizes");
-  GA_REQUIRE(a->col >= 0 && a->col < a->Tcap, "ga_policy_head_sample: col %lld out of "
-             "range (Tcap %lld)", (long long)a->col, (long long)a->Tcap);
-  GA_REQUIRE(a->kind == 1 || (a->log_std && a->lda >= a->A),
-             "ga_policy_head_sample: gaussian head needs log_std and lda >= A");
-  const HeadParams p = {ga_head_to_dev(a), a->A, a->head, a->log_std, a->obs_dim};
-  hipLaunchKernelGGL(head_sample_kernel, dim3((unsigned)ga_ceil_div(a->n, 256)),
-                     dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("policy_head_sample");
-  return GA_OK;
+template <class Env>
+void ro_launch_env_step(const Env& e, const float* actions, int64_t lda, const float* obs,
+                        float* next_obs, int64_t ldo, float* reward, uint8_t* step_type,
+                        unsigned blocks, hipStream_t stream) {
+  hipLaunchKernelGGL(env_step_kernel<Env>, dim3(blocks), dim3(256), 0, stream, e, actions,
+                     lda, obs, next_obs, ldo, reward, step_type);
 }
 
-extern "C" int ga_record_step(const ga_record_args* a, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const char* who = "ga_record_step";
-  GA_REQUIRE(a, "%s: null pointer", who);
-  int rc = check_record(a, a->n, who);
-  if (rc) return rc;
-  const RecordParams p = ga_record_to_dev(a);
-  hipLaunchKernelGGL(record_step_kernel, dim3((unsigned)ga_ceil_div(a->n, 256)),
-                     dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("record_step");
-  return GA_OK;
+template <class Env>
+void ro_launch_env_step_record(const EnvStepArgsT<Env>& a, unsigned blocks,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(env_step_record_kernel<Env>, dim3(blocks), dim3(256), 0, stream, a);
 }
 
-// ---- the device envs ---------------------------------------------------------------
-// the kernel-side struct of each C-ABI env (rollout_dev.h)
-SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t) {
-  SynthEnv d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.obs_dim = e->obs_dim; d.act_dim = e->act_dim;
-  d.discrete = e->discrete; d.min_len = e->min_len; d.max_len = e->max_len;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.episode = e->episode; d.t = e->t; d.len = e->len;
-  return d;
-}
+#define GA_ENV_SEAM_OF(GaEnv, ...)                                                        \
+  template void ro_launch_env_reset(const ga_env_dev_t<GaEnv>&, const uint8_t*, float*,   \
+                                    int64_t, unsigned, hipStream_t);                      \
+  template void ro_launch_env_step(const ga_env_dev_t<GaEnv>&, const float*, int64_t,     \
+                                   const float*, float*, int64_t, float*, uint8_t*,       \
+                                   unsigned, hipStream_t);                                \
+  template void ro_launch_env_step_record(const ga_env_step_args_t<GaEnv>&, unsigned,     \
+                                          hipStream_t);
+GA_ENV_KINDS(GA_ENV_SEAM_OF)
+#undef GA_ENV_SEAM_OF
 
-PointEnv ga_env_to_dev(const ga_point_env* e, int64_t succ_ld) {
-  PointEnv d;
-  d.n = e->n; d.arena = e->arena_size; d.bonus = e->done_bonus;
-  d.never_done = e->never_done; d.max_len = e->max_episode_length;
-  d.point = e->point; d.goal = e->goal; d.t = e->t; d.success = e->success;
-  d.succ_ld = succ_ld;
-  return d;
-}
-
-GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t) {
-  GridEnv d;
-  d.n = e->n; d.rows = e->rows; d.cols = e->cols; d.max_len = e->max_episode_length;
-  d.map = e->map; d.start = e->start; d.state = e->state; d.t = e->t;
-  return d;
-}
-
-// the PointEnv part of a multi-task batch
-static ga_point_env point_part(const ga_multi_point_env* e) {
-  ga_point_env p;
-  p.n = e->n; p.arena_size = e->arena_size; p.done_bonus = e->done_bonus;
-  p.never_done = e->never_done; p.max_episode_length = e->max_episode_length;
-  p.point = e->point; p.goal = e->goal; p.t = e->t; p.success = e->success;
-  return p;
-}
-
-MultiTaskEnv<PointEnv> ga_env_to_dev(const ga_multi_point_env* e, int64_t info_ld) {
-  MultiTaskEnv<PointEnv> d;
-  const ga_point_env p = point_part(e);
-  d.n = e->n; d.in = ga_env_to_dev(&p, info_ld);
-  d.num_tasks = e->num_tasks; d.strategy = e->strategy;
-  d.one_hot = e->mode == GA_TASK_ADD_ONEHOT;
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.payload = e->task_goals; d.last_task = e->last_task; d.resets = e->resets;
-  d.task_id = e->task_id; d.info_ld = info_ld;
-  return d;
-}
-
-// the five seeded state-vector kinds share their field names; MountainCar's
-// `continuous` is the frame's `variant` (0 for the others, whose slot is padding)
-static int state_env_variant(const ga_mountain_car_env* e) { return e->continuous; }
-template <class GaEnv>
-static int state_env_variant(const GaEnv*) { return 0; }
-
-template <class GaEnv, class K>
-StateEnv<K> ga_env_to_dev(const GaEnv* e, int64_t) {
-  StateEnv<K> d;
-  d.n = e->n; d.env_id0 = e->env_id0; d.max_len = e->max_episode_length;
-  d.variant = state_env_variant(e);
-  ga_key(e->seed, &d.k0, &d.k1);
-  d.state = e->state; d.t = e->t; d.resets = e->resets;
-  return d;
-}
-
-static int check_env(const ga_synth_env* e, const char* who) {
-  GA_REQUIRE(e && e->episode && e->t && e->len, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0 && e->obs_dim > 0 && e->act_dim > 0, "%s: bad env sizes", who);
-  GA_REQUIRE(e->min_len >= 1 && e->min_len <= e->max_len && e->max_len <= 65535,
-             "%s: episode lengths must satisfy 1 <= min <= max <= 65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_point_env* e, const char* who) {
-  GA_REQUIRE(e && e->point && e->goal && e->t, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->arena_size >= 0.f, "%s: arena_size must be >= 0", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_grid_env* e, const char* who) {
-  GA_REQUIRE(e && e->map && e->start && e->state && e->t, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0 && e->rows > 0 && e->cols > 0 && e->rows <= 4096 &&
-                 e->cols <= 4096 && (int64_t)e->rows * e->cols <= (1 << 20),
-             "%s: bad env sizes", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  return GA_OK;
-}
-
-static int check_env(const ga_multi_point_env* e, const char* who) {
-  GA_REQUIRE(e && e->point && e->goal && e->t && e->task_goals && e->last_task &&
-                 e->resets, "%s: null env state", who);
-  const ga_point_env p = point_part(e);
-  int rc = check_env(&p, who);
-  if (rc) return rc;
-  GA_REQUIRE(e->num_tasks >= 1 && e->num_tasks <= 256,
-             "%s: num_tasks must be in 1..256 (got %d)", who, e->num_tasks);
-  GA_REQUIRE(e->strategy == GA_TASK_ROUND_ROBIN || e->strategy == GA_TASK_UNIFORM_RANDOM,
-             "%s: unknown sample strategy %d", who, e->strategy);
-  GA_REQUIRE(e->mode == GA_TASK_VANILLA || e->mode == GA_TASK_ADD_ONEHOT,
-             "%s: unknown mode %d", who, e->mode);
-  return GA_OK;
-}
-
-template <class GaEnv, class K = typename ga_state_kind_of<GaEnv>::type>
-static int check_env(const GaEnv* e, const char* who) {
-  GA_REQUIRE(e && e->state && e->t && e->resets, "%s: null env state", who);
-  GA_REQUIRE(e->n > 0, "%s: bad env size", who);
-  GA_REQUIRE(e->max_episode_length >= 1 && e->max_episode_length <= 65535,
-             "%s: max_episode_length must be in 1..65535", who);
-  const int variant = state_env_variant(e);
-  GA_REQUIRE(variant == 0 || variant == 1, "%s: continuous must be 0 or 1", who);
-  return GA_OK;
-}
-
-// Validation + conversion of the C-ABI arguments of one env step (also used by the
-// fused policy + env step of policy_fused.hip): the env, the record and the
-// NormalizedEnv part
-template <class GaEnv>
-int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
-                      const float* actions, int64_t lda, const float* obs, const char* who,
-                      ga_env_step_args_t<GaEnv>* out, bool rescale_inside) {
-  int rc = check_env(env, who);
-  if (rc) return rc;
-  const int obs_dim = ga_env_obs_dim(env);
-  GA_REQUIRE(a, "%s: null pointer", who);
-  if (std::is_same<GaEnv, ga_multi_point_env>::value)
-    GA_REQUIRE(a->ldo >= obs_dim,
-               "%s: observation rows of %lld columns are narrower than 3 + num_tasks = %d",
-               who, (long long)a->ldo, obs_dim);
-  GA_REQUIRE(actions && obs, "%s: null pointer", who);
-  rc = check_record(a, env->n, who);
-  if (rc) return rc;
-  GA_REQUIRE(a->ldo >= obs_dim && a->obs_dim == obs_dim && lda >= ga_env_act_width(env),
-             "%s: leading dimensions too small", who);
-  NormParams nm;
-  memset(&nm, 0, sizeof(nm));
-  const float* raw_obs = obs;
-  float* raw_next = (float*)a->next_obs;
-  if (norm) {
-    nm.norm_obs = norm->normalize_obs != 0;
-    nm.norm_reward = norm->normalize_reward != 0;
-    nm.scale_reward = norm->reward_scale != 1.0;
-    nm.obs_mean = norm->obs_mean; nm.obs_var = norm->obs_var;
-    nm.obs_alpha = norm->obs_alpha; nm.rew_mean = norm->reward_mean;
-    nm.rew_var = norm->reward_var; nm.rew_alpha = norm->reward_alpha;
-    nm.rew_scale = norm->reward_scale;
-    GA_REQUIRE(!nm.norm_obs || (nm.obs_mean && nm.obs_var && norm->raw_obs &&
-                                norm->raw_next_obs),
-               "%s: observation statistics / raw buffers", who);
-    GA_REQUIRE(!nm.norm_reward || (nm.rew_mean && nm.rew_var), "%s: reward statistics",
-               who);
-    if (nm.norm_obs) {
-      raw_obs = norm->raw_obs;
-      raw_next = norm->raw_next_obs;
-    }
-    if (rescale_inside && norm->act_low) {
-      // normalized_env.py:90-100 in the env thread of the caller's kernel: the scratch
-      // rows have the action rows' stride
-      GA_REQUIRE(norm->act_high && norm->scaled_action && !ga_env_discrete(env),
-                 "%s: action rescale needs bounds, scratch and a continuous action space",
-                 who);
-      nm.act_low = norm->act_low; nm.act_high = norm->act_high;
-      nm.expected_action_scale = norm->expected_action_scale;
-      nm.scaled_action = norm->scaled_action; nm.scaled_ld = lda;
-    }
-  }
-  out->e = ga_env_to_dev(env, a->Tcap);  // env_infos go into the [n, Tcap] buffers
-  out->p = ga_record_to_dev(a); out->nm = nm;
-  out->actions = actions; out->lda = lda; out->raw_obs = raw_obs; out->raw_next = raw_next;
-  out->seen_next = (float*)a->next_obs; out->reward = (float*)a->reward;
-  out->step_type = (uint8_t*)a->step_type;
-  return GA_OK;
-}
-#define GA_BUILD_ENV_STEP_OF(E)                                                        \
-  template int ga_build_env_step<E>(const E*, const ga_record_args*, const ga_norm_args*, \
-                                    const float*, int64_t, const float*, const char*,  \
-                                    ga_env_step_args_t<E>*, bool);
-GA_BUILD_ENV_STEP_OF(ga_synth_env)
-GA_BUILD_ENV_STEP_OF(ga_point_env)
-GA_BUILD_ENV_STEP_OF(ga_grid_env)
-GA_BUILD_ENV_STEP_OF(ga_multi_point_env)
-#define GA_BUILD_STATE_ENV_STEP_OF(E, KIND, DEV, OBS, DISCRETE) GA_BUILD_ENV_STEP_OF(E)
-GA_STATE_ENV_KINDS(GA_BUILD_STATE_ENV_STEP_OF)
-#undef GA_BUILD_STATE_ENV_STEP_OF
-#undef GA_BUILD_ENV_STEP_OF
-
-// Environment.reset (_environment.py:237-276; envs/point_env.py:79-98,
-// grid_world_env.py:91-109, multi_env_wrapper.py:169-194)
-extern "C" int ga_env_reset(const ga_env_ref* ref, const uint8_t* mask, float* obs,
-                            int64_t ldo, ga_stream_t stream) {
-  const char* who = "ga_env_reset";
-  return ga_visit_env(ref, who, [&](auto* env) {
-    int rc = check_env(env, who);
-    if (rc) return rc;
-    GA_REQUIRE(obs && ldo >= ga_env_obs_dim(env), "%s: bad obs buffer", who);
-    const auto e = ga_env_to_dev(env, 1);
-    hipLaunchKernelGGL(env_reset_kernel<decltype(e)>,
-                       dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0,
-                       (hipStream_t)stream, e, mask, obs, ldo);
-    GA_CHECK_LAUNCH("env_reset");
-    return GA_OK;
-  });
-}
-
-// Environment.step (envs/point_env.py:100-170, grid_world_env.py:111-215,
-// multi_env_wrapper.py:196-226)
-extern "C" int ga_env_step(const ga_env_ref* ref, const float* actions, int64_t lda,
-                           const float* obs, float* next_obs, int64_t ldo, float* reward,
-                           uint8_t* step_type, ga_stream_t stream) {
-  const char* who = "ga_env_step";
-  return ga_visit_env(ref, who, [&](auto* env) {
-    int rc = check_env(env, who);
-    if (rc) return rc;
-    const bool reads_obs = std::is_same<decltype(env), const ga_synth_env*>::value;
-    GA_REQUIRE(actions && next_obs && reward && step_type && (obs || !reads_obs),
-               "%s: null pointer", who);
-    GA_REQUIRE(ldo >= ga_env_obs_dim(env) && lda >= ga_env_act_width(env),
-               "%s: leading dimensions too small", who);
-    const auto e = ga_env_to_dev(env, 1);
-    hipLaunchKernelGGL(env_step_kernel<decltype(e)>,
-                       dim3((unsigned)ga_ceil_div(env->n, 256)), dim3(256), 0,
-                       (hipStream_t)stream, e, actions, lda, obs, next_obs, ldo, reward,
-                       step_type);
-    GA_CHECK_LAUNCH("env_step");
-    return GA_OK;
-  });
-}
-
-// the step + normalized_env.py:134-164 + vec_worker.py:176-204
-extern "C" int ga_env_step_record(const ga_env_ref* ref, const ga_record_args* rec,
-                                  const ga_norm_args* norm, const float* actions,
-                                  int64_t lda, const float* obs, ga_stream_t stream) {
-  const char* who = "ga_env_step_record";
-  return ga_visit_env(ref, who, [&](auto* env) {
-    using GaEnv = std::remove_cv_t<std::remove_pointer_t<decltype(env)>>;
-    ga_env_step_args_t<GaEnv> args;
-    int rc = ga_build_env_step(env, rec, norm, actions, lda, obs, who, &args);
-    if (rc) return rc;
-    hipLaunchKernelGGL(env_step_record_kernel<decltype(args.e)>,
-                       dim3((unsigned)ga_ceil_div(rec->n, 256)), dim3(256), 0,
-                       (hipStream_t)stream, args);
-    GA_CHECK_LAUNCH("env_step_record");
-    return GA_OK;
-  });
-}
-
+// ---------------------------------------------------------------------------
+// C ABI (see include/garage_amd.h): the entry points that are one kernel each, and the
+// host twins of the device's draws
+// ---------------------------------------------------------------------------
 // the device's task_draw on the host (tests compare it with a numpy restatement)
 extern "C" int ga_multi_env_task_draw(uint64_t seed, int64_t env_id, uint32_t counter,
                                       int num_tasks) {

@@ -9,6 +9,7 @@
 // (sampler/vec_worker.py:176-204; RecordParams).  One thread owns one env.
 #pragma once
 #include "common.h"
+#include "rollout_params.h"  // the structs these functions read: host C++
 
 namespace ga_rollout {
 
@@ -56,13 +57,6 @@ static constexpr uint32_t STREAM_PENDULUM = 6;
 static constexpr uint32_t STREAM_DOUBLE_PENDULUM = 7;
 static constexpr uint32_t STREAM_ACROBOT = 8;
 static constexpr uint32_t STREAM_MOUNTAIN_CAR = 9;
-
-// the two Philox key words of a 64-bit seed
-static __host__ __device__ __forceinline__ void ga_key(uint64_t seed, uint32_t* k0,
-                                                       uint32_t* k1) {
-  *k0 = (uint32_t)(seed & 0xffffffffu);
-  *k1 = (uint32_t)(seed >> 32);
-}
 
 // ---- action sampling ------------------------------------------------------------
 static __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float* z0,
@@ -142,24 +136,7 @@ static __device__ __forceinline__ int sample_categorical(const float* sc, int A,
 }
 
 // ---- the head of a rollout step ------------------------------------------------
-// What the head reads and where it writes: ga_head_args (ga_head_to_dev) without the
-// per-layer path's own `head`, `A`, `log_std`, `obs_dim`.  The fused kernel's
-// parameters and the per-layer head kernel's both hold one.
-struct HeadDev {
-  int64_t n, env_id0;
-  int kind;  // 0 gaussian, 1 categorical
-  int has_min, has_max;
-  float min_log_std, max_log_std;
-  const float* noise; int64_t ldn;  // optional [n, ldn]: N(0,1) / U(0,1) by kind
-  uint32_t k0, k1, step;            // seed, global step counter (Philox counter)
-  int double_softmax;
-  const float* obs; int64_t ldo;    // [n, ldo] current observations
-  int64_t col, Tcap;                // the rollout buffers' column of this step
-  float* action; int64_t lda;       // [n, lda] actions handed to the env
-  float* obs_buf; float* act_buf;   // [n, Tcap, ldo], [n, Tcap, lda]
-  float* head_buf; int64_t ldh;     // optional [n, Tcap, ldh]: agent_info mean / probs
-};
-
+// (HeadDev: rollout_params.h)
 // The head of env `env`: h = its A means (kind 0; log_std: the device scalar) or class
 // scores (kind 1).  Mean / probabilities -> head_buf when given, the sample -> action
 // and act_buf.  The per-layer head kernel calls it, and the fused step kernel with a
@@ -186,17 +163,7 @@ static __device__ __forceinline__ void head_one(const HeadDev& p, const float* h
 }
 
 // ---- synthetic environment ---------------------------------------------------
-struct SynthEnv {
-  int64_t n;
-  int64_t env_id0;       // global id of env 0 of this shard
-  int obs_dim, act_dim, discrete;
-  int min_len, max_len;
-  uint32_t k0, k1;       // seed
-  int32_t* episode;      // [n] episode counter (-1 before the first reset)
-  int32_t* t;            // [n] steps taken in the current episode
-  int32_t* len;          // [n] length of the current episode
-};
-
+// (SynthEnv: rollout_params.h)
 static __device__ __forceinline__ void synth_obs(const SynthEnv& e, uint32_t env,
                                           uint32_t episode, uint32_t t, float* out) {
   for (int b = 0; b * 4 < e.obs_dim; ++b) {
@@ -230,16 +197,7 @@ static __device__ __forceinline__ void env_reset_one(const SynthEnv& e, int64_t 
 // numpy's fp32 arithmetic: np.clip keeps a NaN, np.linalg.norm of a 2-vector is the
 // correctly rounded sqrt of the unfused sum of the two squares, and the Python
 // scalars arena_size / done_bonus enter as fp32 (numpy's weak-scalar rule).
-struct PointEnv {
-  int64_t n;
-  float arena, bonus;   // arena_size, done_bonus
-  int never_done, max_len;
-  float* point;         // [n, 2]
-  const float* goal;    // [n, 2]
-  int32_t* t;           // [n] steps taken in the current episode
-  uint8_t* success;     // optional env_info 'success' at success[i * succ_ld + col]
-  int64_t succ_ld;
-};
+// (PointEnv: rollout_params.h)
 struct PointPre {
   float px, py, gx, gy;
   int t, ep_t;
@@ -319,18 +277,7 @@ static __device__ __forceinline__ void env_core(const PointEnv& e, int64_t i,
 // one-hot of the active task, on reset and on every step.  An inner env joins by
 // defining env_inner_obs_dim and env_apply_task.
 constexpr int TASK_ROUND_ROBIN = 0, TASK_UNIFORM_RANDOM = 1;
-template <class Inner>
-struct MultiTaskEnv {
-  int64_t n;
-  Inner in;
-  int num_tasks, strategy, one_hot;
-  uint32_t k0, k1;        // seed of the uniform_random_strategy stream
-  const float* payload;   // [num_tasks, ...] what env_apply_task copies from
-  int32_t* last_task;     // [n] the active task (-1: no reset yet)
-  uint32_t* resets;       // [n] resets so far (the random stream's counter)
-  uint8_t* task_id;       // optional env_info 'task_id' at task_id[i * info_ld + col]
-  int64_t info_ld;
-};
+// (MultiTaskEnv<Inner>: rollout_params.h)
 template <class InnerPre>
 struct MultiTaskPre {
   InnerPre in;
@@ -397,14 +344,7 @@ static __device__ __forceinline__ void env_core(const MultiTaskEnv<Inner>& e, in
 // ---- GridWorldEnv (envs/grid_world_env.py:111-215) ------------------------------
 // The map is read from memory (cell codes below), never from a per-thread array.
 constexpr uint8_t GRID_FREE = 0, GRID_WALL = 1, GRID_HOLE = 2, GRID_GOAL = 3;
-struct GridEnv {
-  int64_t n;
-  int rows, cols, max_len;
-  const uint8_t* map;    // [n, rows * cols] cell codes (F and S are GRID_FREE)
-  const int32_t* start;  // [n] the S cell
-  int32_t* state;        // [n] current cell
-  int32_t* t;            // [n] steps taken in the current episode
-};
+// (GridEnv: rollout_params.h)
 struct GridPre {
   int s, t, ep_t;
 };
@@ -462,17 +402,7 @@ static __device__ __forceinline__ void env_core(const GridEnv& e, int64_t i,
 //               observation of the new state
 // A new kind costs that description, its C-ABI struct and its row of
 // GA_STATE_ENV_KINDS (internal.h).
-template <class K>
-struct StateEnv {
-  int64_t n;
-  int64_t env_id0;   // global id of env 0 of this shard
-  int max_len;
-  int variant;       // the kind's own switch (MountainCar: continuous), else 0
-  uint32_t k0, k1;   // seed
-  float* state;      // [n, K::S]
-  int32_t* t;        // [n] steps taken in the current episode
-  uint32_t* resets;  // [n] resets so far (the reset stream's counter)
-};
+// (StateEnv<K>: rollout_params.h)
 template <class K>
 struct StatePre {
   typename K::State s;
@@ -1329,24 +1259,7 @@ static __device__ __forceinline__ float reward_normalize_one(float reward, doubl
 }
 
 // ---- per-step bookkeeping (VecWorker.step_episode, vec_worker.py:176-204) ------
-struct RecordParams {
-  int64_t n, col, Tcap;
-  int max_episode_length;
-  const float* reward;       // [n]
-  const uint8_t* step_type;  // [n]
-  const float* next_obs;     // [n, ldo]
-  int64_t ldo;
-  int obs_dim;
-  int32_t* ep_t;             // [n] steps so far in the running episode
-  float* rew_buf;            // [n, Tcap]
-  uint8_t* st_buf;           // [n, Tcap]
-  uint16_t* tail_buf;        // [n, Tcap] episode length at its last step, else 0
-  float* lastobs_buf;        // [n, Tcap, ldo] written at episode ends only
-  uint8_t* done;             // [n] 1 where the env must be reset
-  int32_t* step_eps;         // [Tcap] episodes finished at this step
-  int32_t* step_samples;     // [Tcap] their total length
-  int terminal_only;         // 1: only TERMINAL (not TIMEOUT) ends an episode
-};
+// (RecordParams: rollout_params.h)
 
 // bookkeeping of env i; returns the length of the episode that ended (else 0)
 static __device__ __forceinline__ int record_core(const RecordParams& p, int64_t i,
@@ -1409,37 +1322,12 @@ static __device__ __forceinline__ void action_rescale_row(const float* act, cons
   }
 }
 
-struct NormParams {
-  int norm_obs, norm_reward, scale_reward;
-  double* obs_mean;   // [n, obs_dim]
-  double* obs_var;
-  double obs_alpha;
-  double* rew_mean;   // [n]
-  double* rew_var;
-  double rew_alpha, rew_scale;
-  // the action rescale inside the fused rollout step (null act_low: none; always null
-  // for ga_env_step_record, which steps on the actions it is handed)
-  const float* act_low;   // [act_dim]
-  const float* act_high;
-  float expected_action_scale;
-  float* scaled_action;   // [n, scaled_ld] what the wrapped env steps on
-  int64_t scaled_ld;
-};
-
 // env step -> (NormalizedEnv statistics + normalisation) -> bookkeeping -> reset of
 // env i when it finished; returns the length of the episode that ended (else 0).
 // `raw_obs` / `raw_next` are the env's own observations; seen_next is what the
 // policy sees next and what is recorded as the terminal observation -- the same
 // buffer as raw_next without normalisation.
-template <class Env>
-struct EnvStepArgsT {
-  Env e;
-  RecordParams p;
-  NormParams nm;
-  const float* actions; int64_t lda;
-  const float* raw_obs; float* raw_next; float* seen_next;
-  float* reward; uint8_t* step_type;
-};
+// (NormParams, EnvStepArgsT<Env>: rollout_params.h)
 using EnvStepArgs = EnvStepArgsT<SynthEnv>;
 
 static __device__ __forceinline__ EnvPre env_prefetch(const EnvStepArgs& a, int64_t i) {
@@ -1545,39 +1433,9 @@ static __device__ __forceinline__ int env_step_one(const EnvStepArgsT<Env>& a, i
 
 }  // namespace ga_rollout
 
-// The kernel-side head of ga_head_args and the kernel-side env of each C-ABI env
-// struct (rollout.hip).  info_ld: row stride of the env_info buffers (1: [n],
-// Tcap: the [n, Tcap] record buffers).
-ga_rollout::HeadDev ga_head_to_dev(const ga_head_args* a);
-ga_rollout::SynthEnv ga_env_to_dev(const ga_synth_env* e, int64_t info_ld);
-ga_rollout::PointEnv ga_env_to_dev(const ga_point_env* e, int64_t info_ld);
-ga_rollout::GridEnv ga_env_to_dev(const ga_grid_env* e, int64_t info_ld);
-ga_rollout::MultiTaskEnv<ga_rollout::PointEnv> ga_env_to_dev(const ga_multi_point_env* e,
-                                                             int64_t info_ld);
-// the kind description of each row of GA_STATE_ENV_KINDS (internal.h), whose
-// observation width must be the description's; their one converter
-template <class GaEnv>
-struct ga_state_kind_of {};
-#define GA_STATE_ENV_KIND_OF(GaEnv, KIND, DEV, WIDTH, DISCRETE)                  \
-  template <>                                                                    \
-  struct ga_state_kind_of<GaEnv> {                                               \
-    using type = ga_rollout::DEV;                                                \
-    static_assert(type::OBS == WIDTH, "observation width of " #GaEnv);           \
-  };
-GA_STATE_ENV_KINDS(GA_STATE_ENV_KIND_OF)
-#undef GA_STATE_ENV_KIND_OF
-template <class GaEnv, class K = typename ga_state_kind_of<GaEnv>::type>
-ga_rollout::StateEnv<K> ga_env_to_dev(const GaEnv* e, int64_t info_ld);
-template <class GaEnv>
-using ga_env_step_args_t =
-    ga_rollout::EnvStepArgsT<decltype(ga_env_to_dev((const GaEnv*)nullptr, 0))>;
-
-// Validated conversion of the C-ABI arguments of the rollout step
-// (include/garage_amd.h) into EnvStepArgsT; rollout.hip instantiates it per env kind.
-// rescale_inside: the caller's kernel rescales the policy's action itself when
-// norm->act_low is set (the fused rollout step); otherwise the bounds are not read and
-// the env steps on `actions` as they are (ga_env_step_record).
-template <class GaEnv>
-int ga_build_env_step(const GaEnv* env, const ga_record_args* a, const ga_norm_args* norm,
-                      const float* actions, int64_t lda, const float* obs, const char* who,
-                      ga_env_step_args_t<GaEnv>* out, bool rescale_inside = false);
+// a row of GA_STATE_ENV_KINDS (internal.h) states the observation width its kind
+// description has
+#define GA_STATE_ENV_WIDTH(GaEnv, KIND, DEV, WIDTH, DISCRETE) \
+  static_assert(ga_rollout::DEV::OBS == WIDTH, "observation width of " #GaEnv);
+GA_STATE_ENV_KINDS(GA_STATE_ENV_WIDTH)
+#undef GA_STATE_ENV_WIDTH

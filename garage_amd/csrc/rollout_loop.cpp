@@ -11,6 +11,7 @@
 #include <stdlib.h>
 
 #include "internal.h"
+#include "shape_rules.h"
 
 // 1 (default): policy step and env step of a rollout step in ONE launch
 // (ga_policy_env_step_fused_f32), NormalizedEnv's action rescale included;
@@ -48,11 +49,8 @@ extern "C" int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params
         return 0;
       }))
     return -1;
-  if (norm && norm->act_low && (!norm->act_high || !norm->scaled_action || discrete)) {
-    ga_set_error("ga_rollout_env_steps: action rescale needs bounds, scratch and a "
-                 "continuous action space");
+  if (norm && norm->act_low && ga_rescale_refused(norm, discrete, "ga_rollout_env_steps"))
     return -1;
-  }
   if (norm && norm->normalize_obs && (!raw_a || !raw_b)) {
     ga_set_error("ga_rollout_env_steps: observation normalisation needs the raw "
                  "observation buffers");
@@ -62,7 +60,7 @@ extern "C" int ga_rollout_env_steps(const ga_mlp_desc* desc, const float* params
     ga_set_error("ga_rollout_env_steps: steps exceed the rollout buffer");
     return -1;
   }
-  if (!ga_policy_step_fused_supported(desc) && !ga_step_wide_rule(desc)) {
+  if (!ga_policy_step_fused_supported(desc) && !ga_policy_step_rule(desc, PS_WMAX)) {
     ga_set_error("ga_rollout_env_steps: network not supported by the fused step");
     return -1;
   }

@@ -1,10 +1,13 @@
 // The kernel side's shape rules, each stated ONCE: which shapes a kernel family takes and
 // the tile arithmetic the host code sizes buffers and grids with (fused_train.hip,
-// narrow_step.hip, small_step.hip).  The kernels take their constants from here, the
-// library's host code and the CPU harnesses under tests/host the rules.  No device code.
+// narrow_step.hip, small_step.hip, policy_fused.hip).  The kernels take their constants
+// from here, the library's host code and the CPU harnesses under tests/host the rules.
+// No device code.
 // Not part of the C ABI.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/garage_amd.h"
 
 // ---- fused_train.hip, narrow_body.h: a workgroup takes a 64-row tile of the minibatch
 constexpr int FT_ROWS = 64;          // rows per workgroup tile
@@ -15,6 +18,28 @@ constexpr int NS_HN = 8;             // head outputs, at most
 // ---- small_step.hip: one tile of up to 64 rows, hidden width up to 256
 constexpr int SS_ROWS = 64;
 constexpr int SS_HMAX = 256;
+// ---- policy_fused.hip: the rollout step (and, at PS_HMAX, the training forward)
+constexpr int PS_ROWS = 16;          // envs per workgroup (one 16 x 16 MFMA tile of rows)
+constexpr int PS_HMAX = 256;         // output columns per panel; widest layer input of the
+                                     // WIDTH = 256 kernels and the training forward
+constexpr int PS_WMAX = 512;         // widest layer input of the WIDTH = 512 kernels
+constexpr int PS_MAX_OUT = 32;       // widest output head
+constexpr int PS_KC = 32;            // k chunk
+constexpr int PS_TRAIN_ROWS = 64;    // rows per workgroup of the training forward
+
+// The networks the step kernel takes with layer inputs up to `max_in`: up to 8 layers,
+// every activation code the descriptor can name (0 .. 6), with or without layer
+// normalisation, every layer INPUT in an LDS tile of max_in columns, a head up to
+// PS_MAX_OUT.  ga_policy_step_fused_supported is this rule at PS_HMAX, the wide rule
+// (ga_policy_step_wide_supported, ga_rollout_env_steps) this rule at PS_WMAX.
+inline int ga_policy_step_rule(const ga_mlp_desc* d, int max_in) {
+  if (!d || d->n_layers < 1 || d->n_layers > 8) return 0;
+  if (d->hidden_act < 0 || d->hidden_act > 6 || d->output_act < 0 || d->output_act > 6)
+    return 0;
+  for (int l = 0; l < d->n_layers; ++l)
+    if (d->dims[l] > max_in) return 0;
+  return d->dims[d->n_layers] <= PS_MAX_OUT;
+}
 
 extern "C" {
 // workgroups (= partial sets) for M rows

@@ -968,7 +968,7 @@ GA_API int ga_env_step_record(const ga_env_ref* env, const ga_record_args* rec,
 /* ga_policy_step_fused_f32 followed, per env and in the same launch, by what
  * ga_env_step_record does (env step with `head->action`, NormalizedEnv
  * statistics, bookkeeping, reset of the finished envs), for n_steps consecutive
- * rollout steps in ONE launch: a workgroup takes its 32 envs
+ * rollout steps in ONE launch: a workgroup takes its 16 envs
  * through all of them (envs do not interact within a rollout), alternating between
  * the buffers head->obs / rec->next_obs (norm: raw_obs / raw_next_obs); columns
  * head->col .. head->col + n_steps - 1, Philox counters head->step + s.  Device

@@ -164,8 +164,11 @@ hipError_t hipGetDevice(int* d) { *d = g_device; return hipSuccess; }
 }  // extern "C"
 
 // ---- the one kernel-side answer two fake sides share ------------------------------------
-// (rollout_loop.cpp and mlp_layers.cpp both ask it)
+// (rollout_loop.cpp and mlp_layers.cpp both ask it; a program that links the real one,
+// rollout_host.cpp's, defines GA_HARNESS_REAL_STEP_PREDICATE before it includes this)
+#ifndef GA_HARNESS_REAL_STEP_PREDICATE
 static int g_policy_step_fused_ok = 1;
 extern "C" int ga_policy_step_fused_supported(const ga_mlp_desc* d) {
   return g_policy_step_fused_ok && d->n_layers >= 1;
 }
+#endif
