@@ -2,7 +2,8 @@
 // the public header every source file compiles against.  Not part of the C ABI:
 // the library is built with -fvisibility=hidden and exports include/garage_amd.h
 // only.  Host C++ (no device code), so that the CPU harnesses under tests/host can
-// build update.cpp, rollout_loop.cpp and mlp_layers.cpp against it too.
+// build the library's host sources (update.cpp, rollout_loop.cpp, mlp_layers.cpp, the
+// *_host.cpp files) against it too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -129,7 +130,7 @@ int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* params, const f
 // to the one launch; a kernel side that answers 0 (tests/host/rollout_loop_harness.cpp)
 // keeps the three launches per step.
 int ga_policy_env_step_rescales(void);
-// losses.hip: doubles of per-block partial sums at the front of the reduction
+// losses_host.cpp: doubles of per-block partial sums at the front of the reduction
 // workspace (ga_reduction_workspace_doubles)
 int64_t ga_reduction_partials_doubles(void);
 }

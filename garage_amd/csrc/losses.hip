@@ -1,27 +1,17 @@
-// Fused loss / gradient-seed / optimiser kernels of the PPO update (gfx950).
-//
-//   ga_ppo_gaussian_loss_f32   PPO._compute_objective + VPG._compute_loss_with_adv
-//                              (torch/algos/ppo.py:96-132, vpg.py:324-347,408-454)
-//                              forward AND the gradient wrt the policy mean /
-//                              scalar log-std, in one pass over the minibatch
-//   ga_gaussian_nll_loss_f32   GaussianMLPValueFunction.compute_loss
-//                              (torch/value_functions/gaussian_mlp_value_function.py:81-98)
-//   ga_gaussian_kl_f32         VPG._compute_kl_constraint (vpg.py:381-406)
-//   ga_reduce_slabs_f32 / ga_adam_step_f32
-//                              OptimizerWrapper.step == torch.optim.Adam.step
-//                              (torch/optimizers/optimizer_wrapper.py:53-63)
-//   ga_stats_* / ga_adv_center_f32 / ga_sub_scalar_f32
-//                              VPG._compute_advantage centring (vpg.py:371-377)
+// Fused loss / gradient-seed / optimiser kernels of the PPO update (gfx950): the device
+// code, and at the end of the file the launch seam of loss_params.h, which only
+// instantiates and launches.  The entry points -- checks, parameter structs, grids, one
+// launch or two -- are losses_host.cpp's; the parameter structs loss_params.h's.
 //
 // All are HBM / latency bound elementwise passes: one thread per sample (rows
 // are <= a few tens of floats), fp32 math, fp64 block partials reduced in a
 // fixed order (bitwise reproducible run to run; no float atomics).
 #include "common.h"
+#include "loss_params.h"
 #include "loss_rows.h"
+#include "shape_rules.h"
 
 namespace {
-
-constexpr int RED_BLOCKS = 512;  // upper bound on partial-producing blocks
 
 // Multi-block reductions finish in the same launch: every block publishes its
 // partial sums, then takes a ticket; the block that draws the last one sees all of
@@ -53,35 +43,6 @@ __device__ __forceinline__ double ga_sum_partials(const double* partials, int nb
   for (int b = threadIdx.x; b < nblocks; b += 64) v += ga_peek(partials + 2 * b + which);
   return ga_wave_sum(v);
 }
-
-struct PpoLossParams {
-  const float* mean;      // [M, ldm] policy means of the minibatch rows
-  int64_t ldm;
-  const float* actions;   // [*, lda] gathered through idx (or row i when null)
-  int64_t lda;
-  const float* old_ll;    // gathered through idx
-  const float* adv;       // gathered through idx
-  const int32_t* idx;
-  const float* log_std;   // device scalar parameter (unclamped)
-  float min_log_std;      // lower clamp, applied when has_min
-  int has_min;
-  float max_log_std;
-  int has_max;
-  int64_t M;
-  int A;
-  int algo;               // 0 PPO clipped surrogate, 1 VPG (ll * adv),
-                          // 2 TRPO unclipped surrogate (ratio * adv)
-  float clip;
-  LossEnt ent;
-  float* dmean;           // optional [M, ldm]: dLoss/dmean (already / M)
-  float* ll_out;          // optional [M]: new log-likelihoods
-  double* partials;       // [gridDim.x][2]: sum objective, sum dLoss/dlog_std * M
-  // the scalars of the batch (written by the last block to finish)
-  float* loss_out;        // null: a finalize launch follows
-  float* grad_slab0;
-  int64_t slab_stride, n_splits;
-  unsigned* ticket;
-};
 
 // Loss value and the log-std gradient slot from the batch sums (thread 0 of the
 // finalize kernel, or of the loss kernel when it is the only block).
@@ -148,21 +109,6 @@ __global__ __launch_bounds__(256) void ppo_gaussian_loss_kernel(PpoLossParams p)
                         p.slab_stride, p.n_splits);
 }
 
-struct PpoFinalizeParams {
-  const double* partials;
-  int nblocks;
-  const float* log_std;
-  float min_log_std, max_log_std;
-  int has_min, has_max;
-  int64_t M;
-  int A;
-  LossEnt ent;
-  float* loss_out;      // scalar
-  float* grad_slab0;    // optional: slot that receives dLoss/dlog_std
-  int64_t slab_stride;  // the same slot of slabs 1..n_splits-1 is zeroed
-  int64_t n_splits;
-};
-
 __global__ void ppo_gaussian_finalize_kernel(PpoFinalizeParams p) {
   // one wave: lanes stride over the block partials, then a fixed-order wave sum
   double obj = 0.0, ds = 0.0;
@@ -178,37 +124,7 @@ __global__ void ppo_gaussian_finalize_kernel(PpoFinalizeParams p) {
                       p.slab_stride, p.n_splits);
 }
 
-// ---- categorical policy head ---------------------------------------------------
-// The reference has no torch CategoricalMLPPolicy; its torch categorical (CNN)
-// policies feed softmax(net(x)) to Categorical(logits=...)
-// (torch/policies/categorical_cnn_policy.py:138-139).
-// double_softmax = 1 keeps that convention, 0 treats the MLP output as logits.
-struct CatLossParams {
-  const float* scores;   // [M, lds] MLP outputs of the minibatch rows
-  int64_t lds;
-  const float* actions;  // [*, lda] column 0 holds the class id (as float)
-  int64_t lda;
-  const float* old_ll;
-  const float* adv;
-  const int32_t* idx;
-  int64_t M;
-  int A;
-  int double_softmax;
-  int algo;
-  float clip;
-  LossEnt ent;
-  float* dscores;        // optional [M, lds]: dLoss/dscores (already / M)
-  float* ll_out;         // optional [M]
-  float* ent_out;        // optional [M]: per-row entropy (after softplus if set)
-  double* partials;      // [gridDim.x][2]: sum objective, sum entropy
-  // the scalars of the batch (written by the last block to finish)
-  float* loss_out;       // null: a finalize launch follows
-  double* ent_sum_out;
-  float* grad_slab0;
-  int64_t slab_stride, n_splits;
-  unsigned* ticket;
-};
-
+// ---- categorical policy head (CatLossParams, loss_params.h) ------------------------
 // Final log-probabilities lp[j] of the row, its entropy, and (for the
 // gradient) the softmax p of the raw scores.  A is small (number of actions).
 __device__ __forceinline__ void cat_row(const float* sc, int A, int dbl, float* lse_out,
@@ -344,21 +260,6 @@ __global__ __launch_bounds__(256) void categorical_kl_kernel(
   if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-struct NllParams {
-  const float* v;        // [M, ldv], value in column 0
-  int64_t ldv;
-  const float* returns;  // gathered through idx
-  const int32_t* idx;
-  const float* log_std;  // device scalar, no clamp (min_std=None, max_std=None)
-  int64_t M;
-  float* dv;             // optional [M, ldv] column 0
-  double* partials;      // [gridDim.x][2]
-  float* loss_out;       // written by the last block; null: a finalize launch follows
-  float* grad_slab0;
-  int64_t slab_stride, n_splits;
-  unsigned* ticket;
-};
-
 __global__ __launch_bounds__(256) void gaussian_nll_kernel(NllParams p) {
   __shared__ double red[4];
   const float s = *p.log_std;
@@ -491,15 +392,6 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* slabs,
   }
 }
 
-struct AdamParams {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  int64_t n;
-  GaAdam c;
-};
-
 __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
   // (a short launch on its chain's critical path: its waves go first beside the other
   // chain's GEMMs, see reduce_regions_adam_kernel)
@@ -513,41 +405,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamParams a) {
   a.v[i] = v;
 }
 
-// ---------------------------------------------------------------------------
-// Optimizers other than the default Adam (make_optimizer, _functions.py:25-65,
-// builds any torch.optim class): elementwise steps over the flat parameter buffer
-// with torch's single-tensor arithmetic, one rounding per torch operation.  Every
-// scalar torch forms in Python before it reaches a tensor -- 1 - beta1, 1 - beta2,
-// 1 - alpha, 1 - dampening, 1 - lr * weight_decay, -lr / bias_correction1,
-// sqrt(bias_correction2), -lr -- is formed on the host from the doubles in h and
-// rounded to fp32 once, as ga_adam_coeffs does (1.f - 0.999f is 1.3e-5 away from
-// float(1 - 0.999)); the kernel never subtracts two rounded constants.  addcdiv
-// is x + (value * t1) / t2, as in ga_adam_update and torch's elementwise kernels.
-//   kind 1  torch.optim.SGD      h = {lr, momentum, dampening, weight_decay};
-//                                flag bit 0 nesterov; s1 = momentum buffer
-//   kind 2  torch.optim.RMSprop  h = {lr, alpha, eps, weight_decay, momentum};
-//                                flag bit 0 centered; s1 = square_avg, s2 = momentum
-//                                buffer, s3 = grad_avg
-//   kind 3  torch.optim.Adam / AdamW beyond the defaults
-//                                h = {lr, beta1, beta2, eps, weight_decay};
-//                                flag bit 0 amsgrad, bit 1 decoupled decay (AdamW);
-//                                s1 = exp_avg, s2 = exp_avg_sq, s3 = max_exp_avg_sq
-struct OptParams {
-  float* p;
-  const float* g;
-  float* s1;
-  float* s2;
-  float* s3;
-  int64_t n;
-  int kind, flags, first;  // first: step == 1 (SGD initialises its buffer with g)
-  float neg_lr, h1, h2, h3, h4;
-  // derived in double, rounded once (ga_optimizer_step_f32)
-  float w1;     // 1 - dampening (kind 1), 1 - alpha (kind 2), 1 - beta1 (kind 3)
-  float w2;     // 1 - beta2 (kind 3)
-  float decay;  // 1 - lr * weight_decay (AdamW)
-  float neg_step_size, bc2_sqrt;  // kind 3
-};
-
+// Optimizers other than the default Adam: the kinds, their hyper-parameters and state
+// buffers are OptParams' (loss_params.h); torch's single-tensor arithmetic, one rounding
+// per torch operation, and never a difference of two rounded constants.
 __global__ __launch_bounds__(256) void optimizer_step_kernel(OptParams a) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -742,319 +602,18 @@ __global__ __launch_bounds__(256) void sub_scalar_kernel(float* x, int64_t n,
     x[i] -= s;
 }
 
-inline int red_blocks(int64_t n) {
-  int64_t b = ga_ceil_div(n, 256);  // one row per thread up to RED_BLOCKS blocks
-  if (b < 1) b = 1;
-  if (b > RED_BLOCKS) b = RED_BLOCKS;
-  return (int)b;
-}
-
-}  // namespace
-
-// [RED_BLOCKS][2] partial sums + one slot for the ticket of the single-launch
-// reductions / the grid-barrier words of small_step.hip (both leave it zero) + one
-// slot whose first word small_step.hip raises when a barrier gave up
-extern "C" int64_t ga_reduction_workspace_doubles(void) { return 2 * RED_BLOCKS + 2; }
-extern "C" int64_t ga_reduction_partials_doubles(void) { return 2 * RED_BLOCKS; }
-
-// A single block always finishes its own launch.  With several blocks the last
-// ticket saves the finalize launch but pays two device-scope fences (L2 write-back
-// / invalidate across the XCDs) in every block: measured +1 % per C3 iteration
-// (146.5 vs 145.1 ms overlapped, 167.4 vs 166.1 ms on one stream) and +2 % at C2,
-// so it is off by default.
-static int g_one_launch_losses = 0;
-extern "C" int ga_set_one_launch_losses(int on) {
-  g_one_launch_losses = on != 0;
-  return 0;
-}
-
-extern "C" int ga_ppo_gaussian_loss_f32(
-    const float* mean, int64_t ldm, const float* actions, int64_t lda,
-    const float* old_ll, const float* adv, const int32_t* idx, const float* log_std,
-    int has_min, float min_log_std, int has_max, float max_log_std, int64_t M, int A,
-    int algo, float clip, float ent_coeff, int ent_flags, float* dmean,
-    float* ll_out, float* loss_out, float* grad_slab0, int64_t slab_stride,
-    int64_t n_splits, double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(mean && actions && adv && log_std && loss_out && workspace,
-             "ga_ppo_gaussian_loss_f32: null pointer");
-  GA_REQUIRE(algo == 1 || old_ll, "ga_ppo_gaussian_loss_f32: PPO needs old_ll");
-  GA_REQUIRE(M > 0 && A > 0 && ldm >= A && lda >= A,
-             "ga_ppo_gaussian_loss_f32: bad sizes");
-  PpoLossParams p;
-  p.mean = mean; p.ldm = ldm; p.actions = actions; p.lda = lda; p.old_ll = old_ll;
-  p.adv = adv; p.idx = idx; p.log_std = log_std; p.min_log_std = min_log_std;
-  p.has_min = has_min; p.max_log_std = max_log_std; p.has_max = has_max; p.M = M;
-  p.A = A; p.algo = algo; p.clip = clip; p.ent = lr_ent(ent_coeff, ent_flags);
-  p.dmean = dmean; p.ll_out = ll_out; p.partials = workspace;
-  const int nb = red_blocks(M);
-  const bool one_launch = nb == 1 || g_one_launch_losses != 0;
-  p.loss_out = one_launch ? loss_out : nullptr;
-  p.grad_slab0 = grad_slab0; p.slab_stride = slab_stride; p.n_splits = n_splits;
-  p.ticket = reinterpret_cast<unsigned*>(workspace + 2 * RED_BLOCKS);
-  hipLaunchKernelGGL(ppo_gaussian_loss_kernel, dim3(nb), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("ppo_gaussian_loss");
-  if (one_launch) return GA_OK;
-  PpoFinalizeParams f;
-  f.partials = workspace; f.nblocks = nb; f.log_std = log_std;
-  f.min_log_std = min_log_std; f.max_log_std = max_log_std; f.has_min = has_min;
-  f.has_max = has_max; f.M = M; f.A = A; f.ent = p.ent; f.loss_out = loss_out;
-  f.grad_slab0 = grad_slab0; f.slab_stride = slab_stride; f.n_splits = n_splits;
-  hipLaunchKernelGGL(ppo_gaussian_finalize_kernel, dim3(1), dim3(64), 0, stream, f);
-  GA_CHECK_LAUNCH("ppo_gaussian_finalize");
-  return GA_OK;
-}
-
-extern "C" int ga_ppo_categorical_loss_f32(
-    const float* scores, int64_t lds, const float* actions, int64_t lda,
-    const float* old_ll, const float* adv, const int32_t* idx, int64_t M, int A,
-    int double_softmax, int algo, float clip, float ent_coeff, int ent_flags,
-    float* dscores, float* ll_out, float* ent_out, float* loss_out,
-    double* ent_sum_out, float* grad_slab0, int64_t slab_stride, int64_t n_splits,
-    double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(scores && actions && adv && loss_out && workspace,
-             "ga_ppo_categorical_loss_f32: null pointer");
-  GA_REQUIRE(algo == 1 || old_ll, "ga_ppo_categorical_loss_f32: PPO needs old_ll");
-  GA_REQUIRE(M > 0 && A > 0 && lds >= A && lda >= 1,
-             "ga_ppo_categorical_loss_f32: bad sizes");
-  CatLossParams p;
-  p.scores = scores; p.lds = lds; p.actions = actions; p.lda = lda;
-  p.old_ll = old_ll; p.adv = adv; p.idx = idx; p.M = M; p.A = A;
-  p.double_softmax = double_softmax; p.algo = algo; p.clip = clip;
-  p.ent = lr_ent(ent_coeff, ent_flags);
-  p.dscores = dscores; p.ll_out = ll_out; p.ent_out = ent_out;
-  p.partials = workspace;
-  const int nb = red_blocks(M);
-  const bool one_launch = nb == 1 || g_one_launch_losses != 0;
-  p.loss_out = one_launch ? loss_out : nullptr;
-  p.ent_sum_out = ent_sum_out; p.grad_slab0 = grad_slab0;
-  p.slab_stride = slab_stride; p.n_splits = n_splits;
-  p.ticket = reinterpret_cast<unsigned*>(workspace + 2 * RED_BLOCKS);
-  hipLaunchKernelGGL(ppo_categorical_loss_kernel, dim3(nb), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("ppo_categorical_loss");
-  if (one_launch) return GA_OK;
-  hipLaunchKernelGGL(ppo_categorical_finalize_kernel, dim3(1), dim3(64), 0, stream,
-                     (const double*)workspace, nb, M, loss_out, ent_sum_out,
-                     grad_slab0, slab_stride, n_splits);
-  GA_CHECK_LAUNCH("ppo_categorical_finalize");
-  return GA_OK;
-}
-
-extern "C" int ga_categorical_kl_f32(const float* scores_old, const float* scores_new,
-                                     int64_t ld, int64_t M, int A, int double_softmax,
-                                     double* kl_sum_out, double* workspace,
-                                     ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(scores_old && scores_new && kl_sum_out && workspace,
-             "ga_categorical_kl_f32: null pointer");
-  GA_REQUIRE(M > 0 && A > 0 && ld >= A, "ga_categorical_kl_f32: bad sizes");
-  const int nb = red_blocks(M);
-  hipLaunchKernelGGL(categorical_kl_kernel, dim3(nb), dim3(256), 0, stream,
-                     scores_old, scores_new, ld, M, A, double_softmax, workspace);
-  GA_CHECK_LAUNCH("categorical_kl");
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, stream,
-                     (const double*)workspace, nb, kl_sum_out);
-  GA_CHECK_LAUNCH("sum_partials");
-  return GA_OK;
-}
-
-extern "C" int ga_gaussian_nll_loss_f32(const float* v, int64_t ldv,
-                                        const float* returns, const int32_t* idx,
-                                        const float* log_std, int64_t M, float* dv,
-                                        float* loss_out, float* grad_slab0,
-                                        int64_t slab_stride, int64_t n_splits,
-                                        double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(v && returns && log_std && loss_out && workspace,
-             "ga_gaussian_nll_loss_f32: null pointer");
-  GA_REQUIRE(M > 0 && ldv >= 1, "ga_gaussian_nll_loss_f32: bad sizes");
-  NllParams p;
-  p.v = v; p.ldv = ldv; p.returns = returns; p.idx = idx; p.log_std = log_std;
-  p.M = M; p.dv = dv; p.partials = workspace;
-  const int nb = red_blocks(M);
-  const bool one_launch = nb == 1 || g_one_launch_losses != 0;
-  p.loss_out = one_launch ? loss_out : nullptr;
-  p.grad_slab0 = grad_slab0; p.slab_stride = slab_stride; p.n_splits = n_splits;
-  p.ticket = reinterpret_cast<unsigned*>(workspace + 2 * RED_BLOCKS);
-  hipLaunchKernelGGL(gaussian_nll_kernel, dim3(nb), dim3(256), 0, stream, p);
-  GA_CHECK_LAUNCH("gaussian_nll");
-  if (one_launch) return GA_OK;
-  hipLaunchKernelGGL(gaussian_nll_finalize_kernel, dim3(1), dim3(64), 0, stream,
-                     (const double*)workspace, nb, M, loss_out, grad_slab0,
-                     slab_stride, n_splits);
-  GA_CHECK_LAUNCH("gaussian_nll_finalize");
-  return GA_OK;
-}
-
-extern "C" int ga_gaussian_kl_f32(const float* mean_old, const float* mean_new,
-                                  int64_t ld, int64_t M, int A, float log_std_old,
-                                  float log_std_new, double* kl_sum_out,
-                                  double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(mean_old && mean_new && kl_sum_out && workspace,
-             "ga_gaussian_kl_f32: null pointer");
-  GA_REQUIRE(M > 0 && A > 0 && ld >= A, "ga_gaussian_kl_f32: bad sizes");
-  const int nb = red_blocks(M);
-  hipLaunchKernelGGL(gaussian_kl_kernel, dim3(nb), dim3(256), 0, stream, mean_old,
-                     mean_new, ld, M, A, log_std_old, log_std_new, workspace);
-  GA_CHECK_LAUNCH("gaussian_kl");
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, stream,
-                     (const double*)workspace, nb, kl_sum_out);
-  GA_CHECK_LAUNCH("sum_partials");
-  return GA_OK;
-}
-
-extern "C" int ga_reduce_slabs_f32(const float* slabs, int64_t n_splits,
-                                   int64_t slab_stride, int64_t n, float scale,
-                                   float* out, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(slabs && out, "ga_reduce_slabs_f32: null pointer");
-  GA_REQUIRE(n > 0 && n % 4 == 0 && slab_stride % 4 == 0 && n_splits >= 1,
-             "ga_reduce_slabs_f32: n and stride must be multiples of 4");
-  GA_REQUIRE(ga_aligned16(slabs) && ga_aligned16(out),
-             "ga_reduce_slabs_f32: 16-B alignment required");
-  const int64_t nb = ga_ceil_div(n / 4, 64);
-  hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)nb), dim3(256), 0, stream,
-                     slabs, n_splits, slab_stride, n, out, scale);
-  GA_CHECK_LAUNCH("reduce_slabs");
-  return GA_OK;
-}
-
-extern "C" int ga_reduce_adam_f32(const float* slabs, int64_t n_splits,
-                                  int64_t slab_stride, float* params, float* grads,
-                                  float* exp_avg, float* exp_avg_sq, int64_t n,
-                                  int64_t step, double lr, double beta1, double beta2,
-                                  double eps, int zero_slot0, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(slabs && params && grads && exp_avg && exp_avg_sq,
-             "ga_reduce_adam_f32: null pointer");
-  GA_REQUIRE(n > 0 && n % 4 == 0 && slab_stride % 4 == 0 && n_splits >= 1 && step >= 1,
-             "ga_reduce_adam_f32: bad sizes");
-  GA_REQUIRE(ga_aligned16(slabs) && ga_aligned16(params) && ga_aligned16(grads) &&
-                 ga_aligned16(exp_avg) && ga_aligned16(exp_avg_sq),
-             "ga_reduce_adam_f32: 16-B alignment required");
-  AdamParams a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
-  a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
-  const int64_t nb = ga_ceil_div(n / 4, 64);
-  hipLaunchKernelGGL(reduce_adam_kernel, dim3((unsigned)nb), dim3(256), 0, stream,
-                     slabs, n_splits, slab_stride, zero_slot0, a, grads);
-  GA_CHECK_LAUNCH("reduce_adam");
-  return GA_OK;
-}
-
-extern "C" int ga_adam_step_f32(float* params, const float* grads, float* exp_avg,
-                                float* exp_avg_sq, int64_t n, int64_t step, double lr,
-                                double beta1, double beta2, double eps,
-                                ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(params && grads && exp_avg && exp_avg_sq, "ga_adam_step_f32: null pointer");
-  GA_REQUIRE(n > 0 && step >= 1, "ga_adam_step_f32: bad n / step");
-  AdamParams a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
-  a.c = ga_adam_coeffs(lr, beta1, beta2, eps, step);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0,
-                     stream, a);
-  GA_CHECK_LAUNCH("adam");
-  return GA_OK;
-}
-
-extern "C" int ga_optimizer_step_f32(int kind, float* params, const float* grads,
-                                     float* s1, float* s2, float* s3, int64_t n,
-                                     int64_t step, const double* h, int flags,
-                                     ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(params && grads && h, "ga_optimizer_step_f32: null pointer");
-  GA_REQUIRE(n > 0 && step >= 1 && kind >= 1 && kind <= 3,
-             "ga_optimizer_step_f32: bad n / step / kind");
-  OptParams a;
-  memset(&a, 0, sizeof(a));
-  a.p = params; a.g = grads; a.s1 = s1; a.s2 = s2; a.s3 = s3; a.n = n;
-  a.kind = kind; a.flags = flags; a.first = step == 1;
-  a.neg_lr = (float)(-h[0]); a.h1 = (float)h[1]; a.h2 = (float)h[2];
-  a.h3 = (float)h[3]; a.h4 = (float)h[4];
-  // complements and products of the hyper-parameters: in double, rounded once
-  if (kind == 1) {
-    GA_REQUIRE(h[1] == 0.0 || s1, "ga_optimizer_step_f32: SGD momentum buffer");
-    a.w1 = (float)(1.0 - h[2]);
-  } else if (kind == 2) {
-    GA_REQUIRE(s1 && (h[4] <= 0.0 || s2) && (!(flags & 1) || s3),
-               "ga_optimizer_step_f32: RMSprop state buffers");
-    a.w1 = (float)(1.0 - h[1]);
-  } else {
-    GA_REQUIRE(s1 && s2 && (!(flags & 1) || s3),
-               "ga_optimizer_step_f32: Adam state buffers");
-    const GaAdam c = ga_adam_coeffs(h[0], h[1], h[2], h[3], step);
-    a.w1 = c.lerp_w;
-    a.w2 = c.one_minus_beta2;
-    a.decay = (float)(1.0 - h[0] * h[4]);
-    a.neg_step_size = c.neg_step_size;
-    a.bc2_sqrt = c.bc2_sqrt;
-  }
-  hipLaunchKernelGGL(optimizer_step_kernel, dim3((unsigned)ga_ceil_div(n, 256)),
-                     dim3(256), 0, stream, a);
-  GA_CHECK_LAUNCH("optimizer_step");
-  return GA_OK;
-}
-
-extern "C" int ga_stats_f32(const float* x, int64_t n, int what, double* stats,
-                            double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(x && stats && workspace, "ga_stats_f32: null pointer");
-  GA_REQUIRE(n > 0 && what >= 0 && what <= 2, "ga_stats_f32: bad arguments");
-  const int nb = red_blocks(n);
-  if (what == 0) {
-    hipLaunchKernelGGL(stats_partial_kernel<0>, dim3(nb), dim3(256), 0, stream, x, n,
-                       (const double*)stats, workspace);
-    hipLaunchKernelGGL(stats_finalize_kernel<0>, dim3(1), dim3(64), 0, stream,
-                       (const double*)workspace, nb, n, stats);
-  } else if (what == 1) {
-    hipLaunchKernelGGL(stats_partial_kernel<1>, dim3(nb), dim3(256), 0, stream, x, n,
-                       (const double*)stats, workspace);
-    hipLaunchKernelGGL(stats_finalize_kernel<1>, dim3(1), dim3(64), 0, stream,
-                       (const double*)workspace, nb, n, stats);
-  } else {
-    hipLaunchKernelGGL(stats_partial_kernel<2>, dim3(nb), dim3(256), 0, stream, x, n,
-                       (const double*)stats, workspace);
-    hipLaunchKernelGGL(stats_finalize_kernel<2>, dim3(1), dim3(64), 0, stream,
-                       (const double*)workspace, nb, n, stats);
-  }
-  GA_CHECK_LAUNCH("stats");
-  return GA_OK;
-}
-
-extern "C" int ga_adv_center_f32(float* x, int64_t n, const double* stats, float eps,
-                                 ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(x && stats && n > 0, "ga_adv_center_f32: bad arguments");
-  hipLaunchKernelGGL(adv_center_kernel, dim3(red_blocks(n)), dim3(256), 0, stream, x,
-                     n, stats, eps);
-  GA_CHECK_LAUNCH("adv_center");
-  return GA_OK;
-}
-
-extern "C" int ga_sub_scalar_f32(float* x, int64_t n, const double* scalar,
-                                 ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(x && scalar && n > 0, "ga_sub_scalar_f32: bad arguments");
-  hipLaunchKernelGGL(sub_scalar_kernel, dim3(red_blocks(n)), dim3(256), 0, stream, x,
-                     n, scalar);
-  GA_CHECK_LAUNCH("sub_scalar");
-  return GA_OK;
-}
-
 // ---- vector ops of the constrained (TRPO) policy step ------------------------------
 // torch/optimizers/conjugate_gradient_optimizer.py:69-104,146-186 works on the flat
 // parameter vector (~72 k floats at C3): dot products and axpy-type updates.
-namespace {
 
 // one workgroup, fp64 accumulation in a fixed order: bitwise reproducible
-__global__ __launch_bounds__(1024) void dot_kernel(const float* a, const float* b,
-                                                   int64_t n, double* out) {
+static_assert(LS_DOT_THREADS == 1024, "dot_kernel adds up 16 waves");
+__global__ __launch_bounds__(LS_DOT_THREADS) void dot_kernel(const float* a, const float* b,
+                                                             int64_t n, double* out) {
   __shared__ double part[16];
   double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 1024) s += (double)a[i] * (double)b[i];
+  for (int64_t i = threadIdx.x; i < n; i += LS_DOT_THREADS)
+    s += (double)a[i] * (double)b[i];
   s = ga_wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -1097,8 +656,7 @@ __global__ __launch_bounds__(256) void fisher_seed_kernel(
 // double_softmax), whose Jacobian J1 = diag(z) - z z^T is symmetric, so with the
 // tangent t of the scores:
 //   u = J1 t,  w = (diag(q) - q q^T) u,  dout = J1 w / M      (J1 = I without it).
-// One thread per row, A <= 32 classes in registers.
-constexpr int FS_MAX_A = 32;
+// One thread per row, A <= FS_MAX_A classes in registers.
 __global__ __launch_bounds__(256) void fisher_seed_categorical_kernel(
     const float* scores, int64_t lds, const float* tscores, int64_t ldt, int64_t M, int A,
     int double_softmax, float* dout, int64_t ldd) {
@@ -1141,58 +699,6 @@ __global__ __launch_bounds__(256) void fisher_seed_categorical_kernel(
   for (int j = 0; j < (int)ldd; ++j) dout[i * ldd + j] = (j < A) ? u[j] * inv_m : 0.f;
 }
 
-}  // namespace
-
-extern "C" int ga_dot_f32(const float* a, const float* b, int64_t n, double* out,
-                          ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(a && b && out && n > 0, "ga_dot_f32: bad arguments");
-  hipLaunchKernelGGL(dot_kernel, dim3(1), dim3(1024), 0, stream, a, b, n, out);
-  GA_CHECK_LAUNCH("dot");
-  return GA_OK;
-}
-
-extern "C" int ga_axpby_f32(double alpha, const float* x, double beta, float* y,
-                            int64_t n, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(x && y && n > 0, "ga_axpby_f32: bad arguments");
-  hipLaunchKernelGGL(axpby_kernel, dim3((unsigned)ga_ceil_div(n, 256)), dim3(256), 0,
-                     stream, (float)alpha, x, (float)beta, y, n);
-  GA_CHECK_LAUNCH("axpby");
-  return GA_OK;
-}
-
-extern "C" int ga_fisher_seed_gaussian_f32(const float* tmean, int64_t ldt, int64_t M,
-                                           int A, const float* log_std, int has_min,
-                                           float min_log_std, int has_max,
-                                           float max_log_std, float* dout, int64_t ldd,
-                                           ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(tmean && log_std && dout && M > 0 && A > 0 && ldt >= A && ldd >= A,
-             "ga_fisher_seed_gaussian_f32: bad arguments");
-  hipLaunchKernelGGL(fisher_seed_kernel, dim3((unsigned)ga_ceil_div(M, 256)), dim3(256),
-                     0, stream, tmean, ldt, M, A, log_std, has_min, min_log_std,
-                     has_max, max_log_std, dout, ldd);
-  GA_CHECK_LAUNCH("fisher_seed");
-  return GA_OK;
-}
-
-extern "C" int ga_fisher_seed_categorical_f32(const float* scores, int64_t lds,
-                                              const float* tscores, int64_t ldt,
-                                              int64_t M, int A, int double_softmax,
-                                              float* dout, int64_t ldd,
-                                              ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(scores && tscores && dout && M > 0 && A > 0 && A <= FS_MAX_A && lds >= A &&
-                 ldt >= A && ldd >= A,
-             "ga_fisher_seed_categorical_f32: bad arguments");
-  hipLaunchKernelGGL(fisher_seed_categorical_kernel, dim3((unsigned)ga_ceil_div(M, 256)),
-                     dim3(256), 0, stream, scores, lds, tscores, ldt, M, A, double_softmax,
-                     dout, ldd);
-  GA_CHECK_LAUNCH("fisher_seed_categorical");
-  return GA_OK;
-}
-
 // ---- head layer fused into the loss ------------------------------------------------
 // In a minibatch step the network's last linear layer (hidden -> action means, or
 // hidden -> value) feeds nothing but the loss.  These kernels compute it in the
@@ -1202,21 +708,9 @@ extern "C" int ga_fisher_seed_categorical_f32(const float* scores, int64_t lds,
 // seed comes from the helpers of loss_rows.h, like ppo_gaussian_loss_kernel's and
 // gaussian_nll_kernel's.
 // One pass over the [rows x hidden] matrix replaces the narrow GEMM launch, the
-// round trip of its output and the loss launch.
-namespace {
-
-struct HeadLayer {
-  const float* H;       // [M, ldh] last hidden activations (minibatch rows)
-  int64_t ldh;
-  const float* W;       // [A][ldw], k contiguous
-  int64_t ldw;
-  const float* bias;    // [A]
-  int K;                // hidden width, a multiple of 64
-  float* out;           // optional [M, ldo] head outputs
-  int64_t ldo;
-};
-
-constexpr int HL_THREADS = 256;
+// round trip of its output and the loss launch.  (HeadLayer: loss_params.h; the thread
+// count, the rows per group and the LDS layout: shape_rules.h.)
+static_assert(HL_GROUPS == 16, "group16_sum, and gl / rg below, are written for 16 groups of 16");
 
 __device__ __forceinline__ float group16_sum(float v) {
   v += __shfl_xor(v, 1, 64);
@@ -1231,8 +725,23 @@ __device__ __forceinline__ float group16_sum(float v) {
 // row ids, then everything else).
 template <int KV>
 struct HeadRows {
-  static constexpr int R = KV <= 4 ? 4 : 2;
+  static constexpr int R = ga_head_rows(KV);
+  static_assert(R <= HL_ROWS_MAX, "ga_head_lds sizes the row buffers for HL_ROWS_MAX");
 };
+
+// Floats from smem to the row buffers: ga_head_lds's w + bias (shape_rules.h).  The kernels
+// keep their own expression -- with the sum taken from the struct, the compiler orders three
+// scalar instructions of head_ppo_gaussian_kernel differently -- and the static_assert ties
+// the two at every shape ga_head_loss_rule admits.  (No outer parentheses: the kernels add
+// the two terms to the pointer one after the other.)
+#define HL_ROWS_AT(A, K) (A) * (K) + (((A) + 3) & ~3)
+constexpr bool hl_rows_at_is_the_layout() {
+  for (int K = 64; K <= 512; K *= 2)
+    for (int A = 1; A <= 64; ++A)
+      if ((HL_ROWS_AT(A, K)) != ga_head_lds(A, K).w + ga_head_lds(A, K).bias) return false;
+  return true;
+}
+static_assert(hl_rows_at_is_the_layout(), "HL_ROWS_AT and ga_head_lds disagree");
 
 // head outputs of one row from its activations h[KV] -> rowbuf[0..A) (LDS)
 template <int KV>
@@ -1274,7 +783,7 @@ __global__ __launch_bounds__(HL_THREADS) void head_ppo_gaussian_kernel(HeadLayer
   constexpr int R = HeadRows<KV>::R;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* wlds = smem;                                  // [A][K] + bias[A]
-  float* rows = smem + p.A * L.K + ((p.A + 3) & ~3);   // [16 groups][R][A]
+  float* rows = smem + HL_ROWS_AT(p.A, L.K);           // [16 groups][R][A]
   __shared__ double red[4];
   stage_head(L, p.A, wlds);
   __syncthreads();
@@ -1365,7 +874,7 @@ __global__ __launch_bounds__(HL_THREADS) void head_gaussian_nll_kernel(HeadLayer
   constexpr int R = HeadRows<KV>::R;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* wlds = smem;                 // [1][K] + bias
-  float* rows = smem + L.K + 4;       // [16 groups][R]
+  float* rows = smem + HL_ROWS_AT(1, L.K);  // [16 groups][R]
   __shared__ double red[4];
   stage_head(L, 1, wlds);
   __syncthreads();
@@ -1412,104 +921,129 @@ __global__ __launch_bounds__(HL_THREADS) void head_gaussian_nll_kernel(HeadLayer
   }
 }
 
-inline int head_blocks(int64_t M) {
-  int64_t b = (M + 63) / 64;  // rows per workgroup
-  if (b < 1) b = 1;
-  if (b > RED_BLOCKS) b = RED_BLOCKS;
-  return (int)b;
-}
-
 }  // namespace
 
-extern "C" int ga_head_loss_supported(int hidden_width, int A) {
-  return (hidden_width == 64 || hidden_width == 128 || hidden_width == 256 ||
-          hidden_width == 512) && A >= 1 && A <= 64 &&
-         (int64_t)A * hidden_width * 4 <= 60 * 1024;
-}
+// ---- the launch seam (loss_params.h): instantiate and launch, nothing else ----------------
+#define LS_LAUNCH(kernel, blocks, threads, lds, ...) \
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, stream, __VA_ARGS__)
 
-extern "C" int ga_head_ppo_gaussian_loss_f32(
-    const float* H, int64_t ldh, const float* W, int64_t ldw, const float* bias,
-    int hidden_width, float* mean_out, int64_t ldm, const float* actions, int64_t lda,
-    const float* old_ll, const float* adv, const int32_t* idx, const float* log_std,
-    int has_min, float min_log_std, int has_max, float max_log_std, int64_t M, int A,
-    int algo, float clip, float ent_coeff, int ent_flags, float* dmean, int64_t ldd,
-    float* ll_out, float* loss_out, float* grad_slab0, int64_t slab_stride,
-    int64_t n_splits, double* workspace, ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(H && W && bias && actions && adv && log_std && loss_out && workspace,
-             "ga_head_ppo_gaussian_loss_f32: null pointer");
-  GA_REQUIRE(ga_head_loss_supported(hidden_width, A),
-             "ga_head_ppo_gaussian_loss_f32: unsupported head %d x %d", A, hidden_width);
-  GA_REQUIRE(algo == 1 || old_ll, "ga_head_ppo_gaussian_loss_f32: PPO needs old_ll");
-  GA_REQUIRE(M > 0 && ldh >= hidden_width && ldh % 4 == 0 && ldw >= hidden_width &&
-                 ldw % 4 == 0 && lda >= A && (!dmean || ldd >= A) &&
-                 (!mean_out || ldm >= A) && ga_aligned16(H) && ga_aligned16(W),
-             "ga_head_ppo_gaussian_loss_f32: bad sizes / alignment");
-  HeadLayer L;
-  L.H = H; L.ldh = ldh; L.W = W; L.ldw = ldw; L.bias = bias; L.K = hidden_width;
-  L.out = mean_out; L.ldo = ldm;
-  PpoLossParams p;
-  p.mean = nullptr; p.ldm = ldd; p.actions = actions; p.lda = lda; p.old_ll = old_ll;
-  p.adv = adv; p.idx = idx; p.log_std = log_std; p.min_log_std = min_log_std;
-  p.has_min = has_min; p.max_log_std = max_log_std; p.has_max = has_max; p.M = M;
-  p.A = A; p.algo = algo; p.clip = clip; p.ent = lr_ent(ent_coeff, ent_flags);
-  p.dmean = dmean; p.ll_out = ll_out; p.partials = workspace;
-  p.loss_out = nullptr; p.grad_slab0 = nullptr; p.slab_stride = 0; p.n_splits = 0;
-  p.ticket = nullptr;
-  const int nb = head_blocks(M);
-  const unsigned lds =
-      (unsigned)((A * hidden_width + ((A + 3) & ~3) + 16 * 4 * A) * sizeof(float));
-  switch (hidden_width / 64) {
-    case 1: hipLaunchKernelGGL(head_ppo_gaussian_kernel<1>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    case 2: hipLaunchKernelGGL(head_ppo_gaussian_kernel<2>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    case 4: hipLaunchKernelGGL(head_ppo_gaussian_kernel<4>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    default: hipLaunchKernelGGL(head_ppo_gaussian_kernel<8>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-  }
-  GA_CHECK_LAUNCH("head_ppo_gaussian");
-  PpoFinalizeParams f;
-  f.partials = workspace; f.nblocks = nb; f.log_std = log_std;
-  f.min_log_std = min_log_std; f.max_log_std = max_log_std; f.has_min = has_min;
-  f.has_max = has_max; f.M = M; f.A = A; f.ent = p.ent; f.loss_out = loss_out;
-  f.grad_slab0 = grad_slab0; f.slab_stride = slab_stride; f.n_splits = n_splits;
-  hipLaunchKernelGGL(ppo_gaussian_finalize_kernel, dim3(1), dim3(64), 0, stream, f);
-  GA_CHECK_LAUNCH("ppo_gaussian_finalize");
-  return GA_OK;
+void ls_launch_ppo_gaussian_loss(const PpoLossParams& p, unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(ppo_gaussian_loss_kernel, blocks, 256, 0, p);
 }
-
-extern "C" int ga_head_gaussian_nll_loss_f32(
-    const float* H, int64_t ldh, const float* W, const float* bias, int hidden_width,
-    float* v_out, int64_t ldv_out, const float* returns, const int32_t* idx,
-    const float* log_std, int64_t M, float* dv, int64_t ldd, float* loss_out,
-    float* grad_slab0, int64_t slab_stride, int64_t n_splits, double* workspace,
-    ga_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  GA_REQUIRE(H && W && bias && returns && log_std && loss_out && workspace,
-             "ga_head_gaussian_nll_loss_f32: null pointer");
-  GA_REQUIRE(ga_head_loss_supported(hidden_width, 1),
-             "ga_head_gaussian_nll_loss_f32: unsupported hidden width %d", hidden_width);
-  GA_REQUIRE(M > 0 && ldh >= hidden_width && ldh % 4 == 0 && (!dv || ldd >= 1) &&
-                 (!v_out || ldv_out >= 1) && ga_aligned16(H) && ga_aligned16(W),
-             "ga_head_gaussian_nll_loss_f32: bad sizes / alignment");
-  HeadLayer L;
-  L.H = H; L.ldh = ldh; L.W = W; L.ldw = hidden_width; L.bias = bias;
-  L.K = hidden_width; L.out = v_out; L.ldo = ldv_out;
-  NllParams p;
-  p.v = nullptr; p.ldv = ldd; p.returns = returns; p.idx = idx; p.log_std = log_std;
-  p.M = M; p.dv = dv; p.partials = workspace;
-  p.loss_out = nullptr; p.grad_slab0 = nullptr; p.slab_stride = 0; p.n_splits = 0;
-  p.ticket = nullptr;
-  const int nb = head_blocks(M);
-  const unsigned lds = (unsigned)((hidden_width + 4 + 16 * 4) * sizeof(float));
-  switch (hidden_width / 64) {
-    case 1: hipLaunchKernelGGL(head_gaussian_nll_kernel<1>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    case 2: hipLaunchKernelGGL(head_gaussian_nll_kernel<2>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    case 4: hipLaunchKernelGGL(head_gaussian_nll_kernel<4>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
-    default: hipLaunchKernelGGL(head_gaussian_nll_kernel<8>, dim3(nb), dim3(HL_THREADS), lds, stream, L, p); break;
+void ls_launch_ppo_gaussian_finalize(const PpoFinalizeParams& f, hipStream_t stream) {
+  LS_LAUNCH(ppo_gaussian_finalize_kernel, 1, 64, 0, f);
+}
+void ls_launch_ppo_categorical_loss(const CatLossParams& p, unsigned blocks,
+                                    hipStream_t stream) {
+  LS_LAUNCH(ppo_categorical_loss_kernel, blocks, 256, 0, p);
+}
+void ls_launch_ppo_categorical_finalize(const double* partials, int nblocks, int64_t M,
+                                        float* loss_out, double* ent_sum_out,
+                                        float* grad_slab0, int64_t slab_stride,
+                                        int64_t n_splits, hipStream_t stream) {
+  LS_LAUNCH(ppo_categorical_finalize_kernel, 1, 64, 0, partials, nblocks, M, loss_out,
+            ent_sum_out, grad_slab0, slab_stride, n_splits);
+}
+void ls_launch_gaussian_nll(const NllParams& p, unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(gaussian_nll_kernel, blocks, 256, 0, p);
+}
+void ls_launch_gaussian_nll_finalize(const double* partials, int nblocks, int64_t M,
+                                     float* loss_out, float* grad_slab0,
+                                     int64_t slab_stride, int64_t n_splits,
+                                     hipStream_t stream) {
+  LS_LAUNCH(gaussian_nll_finalize_kernel, 1, 64, 0, partials, nblocks, M, loss_out,
+            grad_slab0, slab_stride, n_splits);
+}
+void ls_launch_categorical_kl(const float* sc_old, const float* sc_new, int64_t ld, int64_t M,
+                              int A, int dbl, double* partials, unsigned blocks,
+                              hipStream_t stream) {
+  LS_LAUNCH(categorical_kl_kernel, blocks, 256, 0, sc_old, sc_new, ld, M, A, dbl, partials);
+}
+void ls_launch_gaussian_kl(const float* mean_old, const float* mean_new, int64_t ld,
+                           int64_t M, int A, float s_old, float s_new, double* partials,
+                           unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(gaussian_kl_kernel, blocks, 256, 0, mean_old, mean_new, ld, M, A, s_old, s_new,
+            partials);
+}
+void ls_launch_sum_partials(const double* partials, int nblocks, double* out,
+                            hipStream_t stream) {
+  LS_LAUNCH(sum_partials_kernel, 1, 64, 0, partials, nblocks, out);
+}
+void ls_launch_reduce_slabs(const float* slabs, int64_t n_splits, int64_t stride, int64_t n,
+                            float* out, float scale, unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(reduce_slabs_kernel, blocks, 256, 0, slabs, n_splits, stride, n, out, scale);
+}
+void ls_launch_reduce_adam(const float* slabs, int64_t n_splits, int64_t stride,
+                           int zero_slot0, const AdamParams& a, float* grads, unsigned blocks,
+                           hipStream_t stream) {
+  LS_LAUNCH(reduce_adam_kernel, blocks, 256, 0, slabs, n_splits, stride, zero_slot0, a,
+            grads);
+}
+void ls_launch_adam(const AdamParams& a, unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(adam_kernel, blocks, 256, 0, a);
+}
+void ls_launch_optimizer_step(const OptParams& a, unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(optimizer_step_kernel, blocks, 256, 0, a);
+}
+template <int WHAT>
+static void stats_pair(const float* x, int64_t n, double* stats, double* partials,
+                       unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(stats_partial_kernel<WHAT>, blocks, 256, 0, x, n, (const double*)stats,
+            partials);
+  LS_LAUNCH(stats_finalize_kernel<WHAT>, 1, 64, 0, (const double*)partials, (int)blocks, n,
+            stats);
+}
+void ls_launch_stats(int what, const float* x, int64_t n, double* stats, double* partials,
+                     unsigned blocks, hipStream_t stream) {
+  switch (what) {
+    case 0: stats_pair<0>(x, n, stats, partials, blocks, stream); break;
+    case 1: stats_pair<1>(x, n, stats, partials, blocks, stream); break;
+    default: stats_pair<2>(x, n, stats, partials, blocks, stream); break;
   }
-  GA_CHECK_LAUNCH("head_gaussian_nll");
-  hipLaunchKernelGGL(gaussian_nll_finalize_kernel, dim3(1), dim3(64), 0, stream,
-                     (const double*)workspace, nb, M, loss_out, grad_slab0,
-                     slab_stride, n_splits);
-  GA_CHECK_LAUNCH("gaussian_nll_finalize");
-  return GA_OK;
+}
+void ls_launch_adv_center(float* x, int64_t n, const double* stats, float eps,
+                          unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(adv_center_kernel, blocks, 256, 0, x, n, stats, eps);
+}
+void ls_launch_sub_scalar(float* x, int64_t n, const double* scalar, unsigned blocks,
+                          hipStream_t stream) {
+  LS_LAUNCH(sub_scalar_kernel, blocks, 256, 0, x, n, scalar);
+}
+void ls_launch_dot(const float* a, const float* b, int64_t n, double* out, unsigned blocks,
+                   hipStream_t stream) {
+  LS_LAUNCH(dot_kernel, blocks, LS_DOT_THREADS, 0, a, b, n, out);
+}
+void ls_launch_axpby(float alpha, const float* x, float beta, float* y, int64_t n,
+                     unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(axpby_kernel, blocks, 256, 0, alpha, x, beta, y, n);
+}
+void ls_launch_fisher_seed_gaussian(const float* tmean, int64_t ldt, int64_t M, int A,
+                                    const float* log_std, int has_min, float min_log_std,
+                                    int has_max, float max_log_std, float* dout, int64_t ldd,
+                                    unsigned blocks, hipStream_t stream) {
+  LS_LAUNCH(fisher_seed_kernel, blocks, 256, 0, tmean, ldt, M, A, log_std, has_min,
+            min_log_std, has_max, max_log_std, dout, ldd);
+}
+void ls_launch_fisher_seed_categorical(const float* scores, int64_t lds, const float* tscores,
+                                       int64_t ldt, int64_t M, int A, int double_softmax,
+                                       float* dout, int64_t ldd, unsigned blocks,
+                                       hipStream_t stream) {
+  LS_LAUNCH(fisher_seed_categorical_kernel, blocks, 256, 0, scores, lds, tscores, ldt, M, A,
+            double_softmax, dout, ldd);
+}
+// one instantiation per hidden width: KV = L.K / 64 of 1, 2, 4, 8 (ga_head_loss_rule)
+#define LS_HEAD_LAUNCH(kernel)                                                     \
+  switch (L.K / 64) {                                                              \
+    case 1: LS_LAUNCH(kernel<1>, blocks, HL_THREADS, lds_bytes, L, p); break;      \
+    case 2: LS_LAUNCH(kernel<2>, blocks, HL_THREADS, lds_bytes, L, p); break;      \
+    case 4: LS_LAUNCH(kernel<4>, blocks, HL_THREADS, lds_bytes, L, p); break;      \
+    default: LS_LAUNCH(kernel<8>, blocks, HL_THREADS, lds_bytes, L, p); break;     \
+  }
+void ls_launch_head_ppo_gaussian(const HeadLayer& L, const PpoLossParams& p, unsigned blocks,
+                                 unsigned lds_bytes, hipStream_t stream) {
+  LS_HEAD_LAUNCH(head_ppo_gaussian_kernel)
+}
+void ls_launch_head_gaussian_nll(const HeadLayer& L, const NllParams& p, unsigned blocks,
+                                 unsigned lds_bytes, hipStream_t stream) {
+  LS_HEAD_LAUNCH(head_gaussian_nll_kernel)
 }

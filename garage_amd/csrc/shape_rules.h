@@ -1,6 +1,6 @@
 // The kernel side's shape rules, each stated ONCE: which shapes a kernel family takes and
 // the tile arithmetic the host code sizes buffers and grids with (fused_train.hip,
-// narrow_step.hip, small_step.hip, policy_fused.hip).  The kernels take their constants
+// narrow_step.hip, small_step.hip, policy_fused.hip, losses.hip).  The kernels take their constants
 // from here, the library's host code and the CPU harnesses under tests/host the rules.
 // No device code.
 // Not part of the C ABI.
@@ -26,6 +26,27 @@ constexpr int PS_WMAX = 512;         // widest layer input of the WIDTH = 512 ke
 constexpr int PS_MAX_OUT = 32;       // widest output head
 constexpr int PS_KC = 32;            // k chunk
 constexpr int PS_TRAIN_ROWS = 64;    // rows per workgroup of the training forward
+// ---- losses.hip: the stand-alone loss, statistics and optimizer kernels
+constexpr int RED_BLOCKS = 512;      // upper bound on partial-producing blocks
+constexpr int LS_DOT_THREADS = 1024; // the one workgroup of the dot product
+constexpr int FS_MAX_A = 32;         // classes of the categorical Fisher seed (in registers)
+// the head layer inside the loss kernel: 16 lanes own one row of the hidden activations
+constexpr int HL_THREADS = 256;
+constexpr int HL_GROUPS = HL_THREADS / 16;
+// rows per 16-lane group and block iteration at KV = hidden width / 64
+constexpr int ga_head_rows(int KV) { return KV <= 4 ? 4 : 2; }
+constexpr int HL_ROWS_MAX = ga_head_rows(1);
+// The head kernels' dynamic LDS, in floats: W [A][K] and the bias [round4(A)] -- what lies
+// before the row buffers -- then the row buffers [HL_GROUPS][rows per group][A], sized for
+// HL_ROWS_MAX at every width.  The kernels find the row buffers at smem + w + bias, the
+// host asks for floats() of them.
+struct HeadLds {
+  int w, bias, rows;
+  constexpr int floats() const { return w + bias + rows; }
+};
+constexpr HeadLds ga_head_lds(int A, int K) {
+  return HeadLds{A * K, (A + 3) & ~3, HL_GROUPS * HL_ROWS_MAX * A};
+}
 
 // The networks the step kernel takes with layer inputs up to `max_in`: up to 8 layers,
 // every activation code the descriptor can name (0 .. 6), with or without layer
@@ -69,8 +90,8 @@ inline int64_t ga_narrow_step_stride(int in_w, int H) {
 }  // extern "C"
 
 // The rules behind the entry points that stay link-time seams (a harness makes them
-// answer 0): ga_fused_fwd_dgrad_supported, ga_fused_eval_supported and the shape part of
-// ga_small_step_supported are one-line wrappers over these.
+// answer 0): ga_fused_fwd_dgrad_supported, ga_fused_eval_supported, ga_head_loss_supported
+// and the shape part of ga_small_step_supported are one-line wrappers over these.
 // fwd_dgrad_kernel is compiled for two hidden layers of the same width (K = the first
 // one's, width = the second one's) with the first layer in the kernel.
 inline int ga_fused_fwd_dgrad_rule(int width, int K, int in_w) {
@@ -79,6 +100,13 @@ inline int ga_fused_fwd_dgrad_rule(int width, int K, int in_w) {
 inline int ga_fused_eval_rule(int n_layers, const int* dims) {
   return n_layers == 3 && dims && ga_fused_first_layer_ok(dims[0], dims[1]) &&
          dims[1] <= 256 && ga_fused_width_ok(dims[2]) && dims[3] >= 1 && dims[3] <= 8;
+}
+// the head layer inside the loss kernel: one instantiation per hidden width, the head's
+// weights ([A][hidden_width]) within 60 KiB of LDS
+inline int ga_head_loss_rule(int hidden_width, int A) {
+  return (hidden_width == 64 || hidden_width == 128 || hidden_width == 256 ||
+          hidden_width == 512) && A >= 1 && A <= 64 &&
+         (int64_t)A * hidden_width * 4 <= 60 * 1024;
 }
 inline int ga_small_step_rule(int n_layers, const int* dims, int64_t M) {
   if (n_layers != 3) return 0;

@@ -110,6 +110,12 @@ GATHER_M, GATHER_POOL = 1000, 1500
 # (512 blocks of 256), and the head-in-loss kernels more than one chunk per block
 BIG = 512 * 256 + 257
 HEAD_BIG = 512 * 64 + 65
+# the grid's boundaries of the two-phase entries (policy losses, value NLL): one block,
+# two blocks (the first finalize launch), the first row count past the cap of 512 blocks
+# (one thread, and only one, takes a second row)
+CAPPED = 512 * 256 + 1
+BOUNDARY_ROWS = (1, 257, CAPPED)
+BOUNDARY_A = (1, 3)
 ROWS = (1, 255, 256, 257, GATHER_M)
 ENT_FLAGS = (0, 1, 3, 5, 7)
 ENT_COEFF = 0.02
@@ -190,6 +196,21 @@ def _cases():
     for k, M in enumerate(ROWS + (BIG, )):
         out.append(Case('nll', 1, M, M == GATHER_M, LAYOUTS[(k + 1) % 3], 0, CLIP, 0,
                         'free', None, 0, 0))
+    # the grid's boundaries: each two-phase entry at every BOUNDARY_ROWS count with a width
+    # of BOUNDARY_A (the rows the walks above do not already hold; a categorical head of
+    # one class has nothing to compare, so it goes with 3; its single row takes the scores
+    # as logits: the KL of ONE row of doubly-softmaxed scores is ~1e-3, and the fp32
+    # formulas on the CPU are 1.4e-7 away from it, 1.7e-4 of the result)
+    out += [
+        Case('gauss', 1, CAPPED, False, 'tight', 0, CLIP, 1, 'lo_inactive', None, 0, 0),
+        Case('gauss', 3, 1, False, 'wide', 0, CLIP, 1, 'free', None, 0, 0),
+        Case('gauss', 3, 257, False, 'pad4', 2, CLIP, 5, 'at_lo', None, 0, 0),
+        Case('gauss', 3, CAPPED, False, 'wide', 1, CLIP, 3, 'sp_free', None, 0, 0),
+        Case('cat', 3, 1, False, 'tight', 0, CLIP, 1, None, 'randn', 0, 0),
+        Case('cat', 3, 257, False, 'wide', 2, CLIP, 3, None, 'randn', 1, 0),
+        Case('cat', 3, CAPPED, False, 'pad4', 0, CLIP, 5, None, 'randn', 1, 0),
+        Case('nll', 1, CAPPED, False, 'wide', 0, CLIP, 0, 'free', None, 0, 0),
+    ]
     # the head layer inside the loss kernel: every hidden width sees every row count
     # and every head width twice (the row counts shifted per width), A = 64 at 64
     # units, the grid-stride size at 64 units; options walk as above

@@ -57,14 +57,21 @@ def test_table_covers_what_it_claims():
     for A in lc.CAT_A:
         assert {(c.scores, c.dsm) for c in cat if c.A == A} == {
             (s, d) for s in lc.SCORES for d in (0, 1)}
-    assert {c.M for c in cat} == set(lc.ROWS) | {lc.BIG}
+    assert {c.M for c in cat} == set(lc.ROWS) | {lc.BIG, lc.CAPPED}
     assert {c.M for c in cat if c.scores == 'randn'} >= set(lc.ROWS)
     for sc in ('shift', 'x30'):
         assert {c.M for c in cat if c.scores == sc} >= set(lc.ROWS[1:])
     assert {c.ent_flags for c in cat} == set(lc.ENT_FLAGS)
     assert {c.algo for c in cat} == {0, 1, 2}
-    assert all(c.A <= 4 for c in lc.CASES if c.M == lc.BIG)
-    assert {c.M for c in lc.cases_of('nll')} == set(lc.ROWS) | {lc.BIG}
+    assert all(c.A <= 4 for c in lc.CASES if c.M in (lc.BIG, lc.CAPPED))
+    assert {c.M for c in lc.cases_of('nll')} == set(lc.ROWS) | {lc.BIG, lc.CAPPED}
+    # the grid's boundaries of every two-phase entry, at a width of 1 or 3
+    assert lc.BOUNDARY_ROWS == (1, 257, 256 * 512 + 1)
+    for kind in ('gauss', 'cat', 'nll'):
+        for M in lc.BOUNDARY_ROWS:
+            assert any(c.M == M and c.A in lc.BOUNDARY_A for c in lc.cases_of(kind)), (kind, M)
+    for M in lc.BOUNDARY_ROWS:
+        assert {c.A for c in g if c.M == M} >= set(lc.BOUNDARY_A)
     h = lc.cases_of('hgauss')
     for hidden in lc.HEAD_HIDDEN:
         assert {c.A for c in h if c.hidden == hidden} >= set(lc.HEAD_A)

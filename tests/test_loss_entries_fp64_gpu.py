@@ -9,8 +9,10 @@ of every tolerance: ``test_loss_cases_cpu.py``.
 What no kernel may read is NaN: the padding columns of every strided input, the pool
 rows a gathered case does not name, the partial-sum slots of the reduction workspace,
 the slabs, the old log-likelihoods of a VPG case.  Every output starts as NaN.  Launches
-of more than one block run at both positions of ``ga_set_one_launch_losses`` and each
-position is compared with the reference, never with the other.
+of more than one block, and the rows of ``_loss_cases.BOUNDARY_ROWS`` (one block
+included: it finishes in its own launch whatever the switch says), run at both
+positions of ``ga_set_one_launch_losses`` and each position is compared with the
+reference, never with the other.
 """
 import numpy as np
 import pytest
@@ -92,7 +94,7 @@ class _Checker:
 
 
 def _positions(M, per_block):
-    return lc.ONE_LAUNCH if M > per_block else (0, )
+    return lc.ONE_LAUNCH if M > per_block or M in lc.BOUNDARY_ROWS else (0, )
 
 
 def _sample(c, b, dev):
