@@ -68,9 +68,9 @@ clean:
 
 # Host-side C++ under AddressSanitizer + UBSan on the CPU (tests/host/): a harness program
 # is one translation unit of tests/host/ -- recording fakes of every kernel entry point
-# or launch-seam function (fused_params.h, rollout_params.h, loss_params.h) and HIP call
-# the product source makes, and the checks -- linked with that product source.  One line
-# per program: binary, harness source, product source.
+# or launch-seam function (fused_params.h, rollout_params.h, loss_params.h, layer_plans.h)
+# and HIP call the product source makes, and the checks -- linked with that product source.
+# One line per program: binary, harness source, product source.
 ASAN_PROGRAMS := \
   host_asan_test:update_loop_harness:update \
   rollout_asan_test:rollout_loop_harness:rollout_loop \
@@ -116,8 +116,11 @@ asan-env-loop: $(OUT)/rollout_asan_test
 asan-rescale-loop: $(OUT)/rollout_asan_test
 	$(OUT)/rollout_asan_test rescale-loop
 
-# The per-layer MLP dispatch (mlp_layers.cpp): every fake checks the extent its kernel
-# would reach against the exactly-sized buffer the pointer came from.
+# The per-layer MLP dispatch (mlp_layers.cpp) with the library's kernel-choice rules
+# (layer_plans.h) against fakes of the launch seam: every fake checks the extent its kernel
+# would reach against the exactly-sized buffer the pointer came from and that the plan's
+# grid covers the product; the plans themselves against literal tables (tile, grid,
+# k_per_split, LDS bytes, variant) with both sides of every boundary.
 asan-mlp: $(OUT)/mlp_layers_asan_test
 	$(OUT)/mlp_layers_asan_test
 

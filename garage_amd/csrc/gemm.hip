@@ -30,7 +30,7 @@
 #include "prof.h"
 
 #include "gemm_core.h"
-#include "fused_train.h"
+#include "layer_plans.h"
 
 namespace {
 
@@ -589,183 +589,104 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_split_kernel(GemmParams p) {
   }
 }
 
-static int g_small_m = 1;
-
+// ---------------------------------------------------------------------------
+// The launch seam (layer_plans.h): which tile, which grid and which k range is the
+// plan's word, and `p` arrives with them filled in; here the plan's enum becomes an
+// instantiation.
+// ---------------------------------------------------------------------------
 template <bool A_KC, bool B_KC>
-int launch_gemm(const GemmParams& p_in, int splits, hipStream_t stream) {
-  GemmParams p = p_in;
-  const int mode = (A_KC && B_KC) ? 0 : (A_KC ? 1 : 2);
-  // algorithmic flops: 2 M N K (the padding of ragged tiles is not counted)
-  const double flops = 2.0 * (double)p.M * (double)p.N * (double)p.K;
+int launch_gemm(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
+  const dim3 grid((unsigned)(p.gx * p.gy * p.gz)), block((unsigned)plan.threads);
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_small_m && splits == 1 && p.K > 64 &&
-      (p.N > 32 ? ga_ceil_div(p.M, 128) * ga_ceil_div(p.N, 128) <= 128 : p.M <= 4096)) {
-    // fewer 128x128 tiles than half the CUs: the k-loop of one workgroup is then a
-    // chain of dependent memory round trips (the weights were rewritten by the
-    // optimizer step just before, so they come from beyond this XCD's L2) with
-    // nothing else on the CU to hide them.  64x64 tiles spread rows and columns
-    // over 4x the workgroups and a 128-deep k-step cuts the chain to K / 128 round
-    // trips with 16 16-B loads in flight per thread.  Same k order per output
-    // element as every other tile shape, so the results are bit-identical.
-    // MLP(256,256) forward + backward at 64 rows: 43.6 + 54.3 -> 26.5 + 33.3 us,
-    // at 4096 rows 43.5 + 81.2 -> 31.3 + 66.8 us; MLP(512,512,512) at 64 rows
-    // 149.5 + 141.9 -> 61.7 + 69.5 us (tools/small_m_ab.py).  Narrow outputs (the
-    // head layer) take the same kernel up to 4096 rows: a half-empty tile costs
-    // nothing when the launch is one round-trip chain anyway.
-    p.gx = (int)ga_ceil_div(p.M, 64); p.gy = (int)ga_ceil_div(p.N, 64); p.gz = 1;
-    p.k_per_split = (int)ga_ceil_div(p.K, 128) * 128;
-    dim3 grid((unsigned)(p.gx * p.gy));
-    ga_prof_events(GA_PROF_GEMM_NT_128 + mode, flops, &e0, &e1);
-    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, A_KC, B_KC, 128>), grid,
-                          dim3(256), 0, stream, e0, e1, 0, p);
-  } else if (p.N <= 32) {
-    // narrow outputs are HBM bound on the wide operand: 128-row tiles give
-    // M/128 workgroups (256 at the C3 minibatch) to pull it through
-    p.gx = (int)ga_ceil_div(p.M, 128); p.gy = (int)ga_ceil_div(p.N, 32); p.gz = splits;
-    dim3 grid((unsigned)(p.gx * p.gy * p.gz));
-    ga_prof_events(GA_PROF_GEMM_NT_256 + mode, flops, &e0, &e1);
-    // (a 128-deep k tile -- 80 KB in flight per workgroup -- was tried for these
-    // latency-bound shapes and measured no better than 32: one workgroup per CU)
-    hipExtLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, A_KC, B_KC>), grid,
-                          dim3(256), 0, stream, e0, e1, 0, p);
-  } else if (p.N <= 64) {
-    // 33..64 wide outputs (the 64-unit layers of the CartPole-shaped config): a
-    // 128x128 tile would be half empty and give M/128 workgroups; 64x64 tiles
-    // (4 waves, one 32x32 accumulator each) give 4x as many
-    p.gx = (int)ga_ceil_div(p.M, 64); p.gy = 1; p.gz = splits;
-    dim3 grid((unsigned)(p.gx * p.gy * p.gz));
-    ga_prof_events(GA_PROF_GEMM_NT_128 + mode, flops, &e0, &e1);
-    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, A_KC, B_KC>), grid, dim3(256),
-                          0, stream, e0, e1, 0, p);
-  } else if (A_KC && ga_split_bf16_gemm() && splits == 1 && p.N >= 128 && p.K >= 128 &&
-             p.K % 4 == 0 && p.M >= 1024 && !p.b_idx && !p.accum && !p.colsum &&
-             !p.head_W && p.c_cs == 1) {
-    // wide layers: forward (B(k, n) = W[n][k]) and data gradient (B(k, n) = W[k][n]);
-    // B_KC tells which orientation the weight planes are needed in
-    p.bplanes = B_KC ? ga_weight_planes(p.B, p.ldb, p.N, p.K, 0, stream)
-                     : ga_weight_planes(p.B, p.ldb, p.K, p.N, 1, stream);
-    GA_REQUIRE(p.bplanes, "gemm: no memory for the weight planes");
-    const int np = (p.N + 31) & ~31, kp = (p.K + 31) & ~31;
-    p.bplane_stride = (int64_t)np * kp;
-    p.bplane_nblk = np / 32;
-    p.gx = (int)ga_ceil_div(p.M, 128); p.gy = (int)ga_ceil_div(p.N, 128); p.gz = 1;
-    p.k_per_split = (int)ga_ceil_div(p.K, BK) * BK;
-    dim3 grid((unsigned)(p.gx * p.gy));
-    ga_prof_events(GA_PROF_GEMM_NT_128 + mode, flops, &e0, &e1);
-    hipExtLaunchKernelGGL(gemm_kc_split_kernel, grid, dim3(512), 0, stream, e0, e1, 0, p);
-  } else if (!A_KC && !B_KC && ga_split_bf16_enabled() && p.M % 128 == 0 &&
-             p.N % 128 == 0 && !p.a_idx && !p.b_idx && p.epi == EPI_PLAIN && !p.accum &&
-             p.k_per_split % 16 == 0 && !p.colsum_of_b) {
-    p.gx = p.M / 128; p.gy = p.N / 128; p.gz = splits;
-    dim3 grid((unsigned)(p.gx * p.gy * p.gz));
-    ga_prof_events(GA_PROF_GEMM_NT_128 + mode, flops, &e0, &e1);
-    hipExtLaunchKernelGGL(gemm_nt_split_kernel, grid, dim3(512), 0, stream, e0, e1, 0, p);
-  } else {
-    p.gx = (int)ga_ceil_div(p.M, 128); p.gy = (int)ga_ceil_div(p.N, 128); p.gz = splits;
-    dim3 grid((unsigned)(p.gx * p.gy * p.gz));
-    ga_prof_events(GA_PROF_GEMM_NT_128 + mode, flops, &e0, &e1);
-    // 8 waves (64x32 each): two workgroups per CU put 4 waves on every SIMD, so
-    // the matrix pipe has work while other waves sit at the barrier / vmcnt
+  ga_prof_events(plan.prof_kind, plan.work, &e0, &e1);
+  switch (plan.tile) {
+    case GT_SMALL_M:
+      hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, A_KC, B_KC, 128>), grid, block, 0,
+                            stream, e0, e1, 0, p);
+      break;
+    case GT_128x32:
+      hipExtLaunchKernelGGL((gemm_f32_kernel<128, 32, 4, 1, A_KC, B_KC>), grid, block, 0,
+                            stream, e0, e1, 0, p);
+      break;
+    case GT_64x64:
+      hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, A_KC, B_KC>), grid, block, 0,
+                            stream, e0, e1, 0, p);
+      break;
+    case GT_KC_SPLIT:
+      hipExtLaunchKernelGGL(gemm_kc_split_kernel, grid, block, 0, stream, e0, e1, 0, p);
+      break;
+    case GT_NT_SPLIT:
+      hipExtLaunchKernelGGL(gemm_nt_split_kernel, grid, block, 0, stream, e0, e1, 0, p);
+      break;
+    case GT_128x128:
 #ifdef GA_GEMM_BIG_TILE  // A/B builds: 4-wave workgroups with 128-row wave tiles
-    // 1: 256 x 256 tiles, waves of 128 x 128 (one per SIMD); 2: 256 x 128, waves of 128 x 64
-    if (splits == 1 && p.M >= 4096 && p.N % 256 == 0) {
-      constexpr int TBN = GA_GEMM_BIG_TILE == 2 ? 128 : 256;
-      p.gx = (int)ga_ceil_div(p.M, 256); p.gy = p.N / TBN; p.gz = 1;
-      dim3 g2((unsigned)(p.gx * p.gy));
-      const bool pipe_ok = !p.colsum && p.c_cs == 1 && (p.c_rs & 3) == 0 && ga_aligned16(p.C) &&
-                           (!p.H || ((p.ldh & 3) == 0 && ga_aligned16(p.H))) &&
-                           (!p.bias || ga_aligned16(p.bias)) && !p.accum &&
-                           p.K % BK == 0 && !p.a_idx && !p.b_idx;
-      if (GA_GEMM_BIG_TILE == 3 && pipe_ok)
-        hipExtLaunchKernelGGL((gemm_f32_pipe_kernel<A_KC, B_KC>), g2, dim3(256), 0, stream,
-                              e0, e1, 0, p);
-      else
-        hipExtLaunchKernelGGL((gemm_f32_kernel<256, TBN, 2, 2, A_KC, B_KC>), g2, dim3(256),
-                              0, stream, e0, e1, 0, p);
-      GA_CHECK_LAUNCH("gemm_f32 (256-row tiles)");
-      return GA_OK;
-    }
+      // 1: 256 x 256 tiles, waves of 128 x 128 (one per SIMD); 2: 256 x 128, waves of 128 x 64
+      if (p.gz == 1 && p.M >= 4096 && p.N % 256 == 0) {
+        constexpr int TBN = GA_GEMM_BIG_TILE == 2 ? 128 : 256;
+        GemmParams q = p;
+        q.gx = (int)ga_ceil_div(p.M, 256); q.gy = p.N / TBN;
+        dim3 g2((unsigned)(q.gx * q.gy));
+        const bool pipe_ok = !p.colsum && p.c_cs == 1 && (p.c_rs & 3) == 0 && ga_aligned16(p.C) &&
+                             (!p.H || ((p.ldh & 3) == 0 && ga_aligned16(p.H))) &&
+                             (!p.bias || ga_aligned16(p.bias)) && !p.accum &&
+                             p.K % BK == 0 && !p.a_idx && !p.b_idx;
+        if (GA_GEMM_BIG_TILE == 3 && pipe_ok)
+          hipExtLaunchKernelGGL((gemm_f32_pipe_kernel<A_KC, B_KC>), g2, dim3(256), 0, stream,
+                                e0, e1, 0, q);
+        else
+          hipExtLaunchKernelGGL((gemm_f32_kernel<256, TBN, 2, 2, A_KC, B_KC>), g2, dim3(256),
+                                0, stream, e0, e1, 0, q);
+        GA_CHECK_LAUNCH("gemm_f32 (256-row tiles)");
+        return GA_OK;
+      }
 #endif
 #ifdef GA_GEMM_BIG_BKT  // A/B builds (tools/build_variants.sh): k-tile depth of this shape
-    hipExtLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 4, A_KC, B_KC, GA_GEMM_BIG_BKT>),
-                          grid, dim3(512), 0, stream, e0, e1, 0, p);
+      hipExtLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 4, A_KC, B_KC, GA_GEMM_BIG_BKT>),
+                            grid, block, 0, stream, e0, e1, 0, p);
 #else
-    hipExtLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 4, A_KC, B_KC>), grid,
-                          dim3(512), 0, stream, e0, e1, 0, p);
+      hipExtLaunchKernelGGL((gemm_f32_kernel<128, 128, 2, 4, A_KC, B_KC>), grid, block, 0,
+                            stream, e0, e1, 0, p);
 #endif
+      break;
   }
   GA_CHECK_LAUNCH("gemm_f32");
   return GA_OK;
 }
 
-// The last hidden layer and the head layer in one launch (tiles that span the
-// layer's whole width: 64, 128 or 256 units).  Returns 1 when the shape is not
-// taken -- every workgroup must be on the staged-epilogue path, which the kernel
-// decides from the same conditions.
-int launch_gemm_with_head(const GemmParams& p_in, hipStream_t stream) {
-  GemmParams p = p_in;
-  const int bm = 64;
-  if (!(p.N == 64 || p.N == 128 || p.N == 256) || p.M % bm != 0 || p.M < bm ||
-      p.head_n < 1 || p.head_n > 8 || p.head_ld < p.head_n || p.head_ldw % 4 != 0 ||
-      !ga_aligned16(p.head_W) || p.c_cs != 1 || (p.c_rs & 3) != 0 ||
-      !ga_aligned16(p.C) || (p.bias && !ga_aligned16(p.bias)) || p.H || p.accum ||
-      p.colsum || p.epi != EPI_BIAS_ACT || p.K < 1)
-    return 1;
-  p.gx = p.M / bm; p.gy = 1; p.gz = 1;
-  dim3 grid((unsigned)p.gx);
-  // algorithmic flops of both layers
-  const double flops = 2.0 * (double)p.M * (double)p.N * ((double)p.K + p.head_n);
+}  // namespace
+
+int ga_gemm_launch(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
+  if (plan.a_kc && plan.b_kc) return launch_gemm<true, true>(plan, p, stream);
+  if (plan.a_kc) return launch_gemm<true, false>(plan, p, stream);
+  return launch_gemm<false, false>(plan, p, stream);
+}
+
+int ga_gemm_head_launch(const GemmHeadPlan& plan, const GemmParams& p, hipStream_t stream) {
+  const dim3 grid((unsigned)p.gx), block((unsigned)plan.threads);
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_GEMM_NT_128, flops, &e0, &e1);
-  if (p.N == 64)
-    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, true, true, BK, true>), grid,
-                          dim3(256), 0, stream, e0, e1, 0, p);
-  else if (p.N == 128)
-    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 128, 1, 4, true, true, BK, true>), grid,
-                          dim3(256), 0, stream, e0, e1, 0, p);
+  ga_prof_events(GA_PROF_GEMM_NT_128, plan.work, &e0, &e1);
+  if (plan.width == 64)
+    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 64, 2, 2, true, true, BK, true>), grid, block,
+                          0, stream, e0, e1, 0, p);
+  else if (plan.width == 128)
+    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 128, 1, 4, true, true, BK, true>), grid, block,
+                          0, stream, e0, e1, 0, p);
   else
-    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 256, 1, 8, true, true, BK, true>), grid,
-                          dim3(512), 0, stream, e0, e1, 0, p);
+    hipExtLaunchKernelGGL((gemm_f32_kernel<64, 256, 1, 8, true, true, BK, true>), grid, block,
+                          0, stream, e0, e1, 0, p);
   GA_CHECK_LAUNCH("gemm_f32 (+head)");
   return GA_OK;
 }
 
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// The launches (gemm_params.h), for the per-layer dispatch in mlp_layers.cpp
-// ---------------------------------------------------------------------------
-extern "C" int ga_set_small_m_gemm(int on) {
-  g_small_m = on != 0;
-  return 0;
-}
-
-int ga_gemm_launch(const GemmParams* p, int a_kc, int b_kc, int splits, hipStream_t stream) {
-  if (a_kc && b_kc) return launch_gemm<true, true>(*p, splits, stream);
-  if (a_kc && !b_kc) return launch_gemm<true, false>(*p, splits, stream);
-  GA_REQUIRE(!a_kc && !b_kc, "ga_gemm_launch: orientation not instantiated");
-  return launch_gemm<false, false>(*p, splits, stream);
-}
-
-int ga_gemm_launch_with_head(const GemmParams* p, hipStream_t stream) {
-  return launch_gemm_with_head(*p, stream);
-}
-
-int ga_gemm_launch_pair(const GemmParams* a, const GemmParams* b, hipStream_t stream) {
-  GA_REQUIRE(a->M == b->M && a->N == b->N && a->K == b->K && a->gz == b->gz && a->gz >= 1,
-             "ga_gemm_launch_pair: two products of one shape");
+int ga_gemm_pair_launch(const GemmPairPlan& plan, const GemmParams& a, const GemmParams& b,
+                        hipStream_t stream) {
   GemmPair pp;
-  pp.a = *a;
-  pp.b = *b;
-  // (gz: the caller's split count)
-  for (GemmParams* p : {&pp.a, &pp.b}) {
-    p->gx = (int)ga_ceil_div(p->M, 128); p->gy = (int)ga_ceil_div(p->N, 128);
-  }
-  const double flops = 2.0 * 2.0 * (double)pp.a.M * (double)pp.a.N * (double)pp.a.K;
+  pp.a = a;
+  pp.b = b;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  ga_prof_events(GA_PROF_GEMM_TN_128, flops, &e0, &e1);
+  ga_prof_events(GA_PROF_GEMM_TN_128, plan.work, &e0, &e1);
   ga_prof_count(GA_PROF_GEMM_TN_128);
-  const dim3 grid((unsigned)(2 * pp.a.gx * pp.a.gy * pp.a.gz));
+  const dim3 grid((unsigned)(2 * plan.gx * plan.gy * plan.gz));
   hipExtLaunchKernelGGL((gemm_f32_pair_kernel<128, 128, 2, 4, false, false>), grid,
                         dim3(512), 0, stream, e0, e1, 0, pp);
   GA_CHECK_LAUNCH("gemm_f32_pair");

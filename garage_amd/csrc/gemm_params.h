@@ -1,7 +1,8 @@
 // What the host says to the fp32 MFMA GEMM kernels (gemm.hip, gemm_core.h) about one
-// product, and the launch entries that take it.  Host C++ only (no device code), so
-// that the per-layer dispatch (mlp_layers.cpp) builds for the CPU harness under
-// tests/host as well.  Not part of the C ABI.
+// product.  Which kernel takes it, with which grid, and the launch entries are in
+// layer_plans.h.  Host C++ only (no device code), so that the per-layer dispatch
+// (mlp_layers.cpp) builds for the CPU harness under tests/host as well.  Not part of the
+// C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,16 +65,3 @@ struct GemmParams {
 struct GemmPair {
   GemmParams a, b;
 };
-
-// ---- gemm.hip: the launches.  The grid (gx, gy, gz), the tile shape and the weight
-// planes are theirs to fill in; everything else of a GemmParams is the caller's.
-// C(m, n) = epi(sum_k A(m, k) B(k, n)); a_kc / b_kc: the operand is k-contiguous in
-// memory.  (1, 1) forward, (1, 0) data gradient, (0, 0) weight gradient -- the three
-// orientations that are instantiated.
-int ga_gemm_launch(const GemmParams* p, int a_kc, int b_kc, int splits, hipStream_t stream);
-// The last hidden layer and the head layer (p->head_*) in one launch.  Returns 1 when
-// the shape is not taken.
-int ga_gemm_launch_with_head(const GemmParams* p, hipStream_t stream);
-// Two weight-gradient products of the same shape (128 x 128 tiles, gz = k splits) in
-// one grid.
-int ga_gemm_launch_pair(const GemmParams* a, const GemmParams* b, hipStream_t stream);

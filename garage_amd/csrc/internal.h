@@ -26,19 +26,6 @@ int ga_ln_jvp(const float* tX, int64_t ldt, const float* X, int64_t ldx, const i
               const float* tgamma, const float* tbeta, float* tY, int64_t ldy,
               hipStream_t stream);
 
-// skinny.hip: streaming kernels for the layer products with one dimension <= 32.
-// Return 1 when they do not take the shape: the MFMA tile kernel handles it.
-int ga_skinny_forward(const float* X, int64_t ldx, const int32_t* idx, const float* W,
-                      int64_t ldw, bool w_kc, const float* bias, int act,
-                      const float* H, int64_t ldh, float* Y, int64_t ldy, int M, int N,
-                      int K, hipStream_t stream);
-int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const float* Nr,
-                    int64_t ldn, const int32_t* n_idx, int rows, int wide, int NS,
-                    int rows_per_split, int n_splits, float* C, int64_t c_wide_stride,
-                    int64_t c_narrow_stride, int64_t split_stride, float* colsum_wide,
-                    float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
-                    int64_t lddz, hipStream_t stream);
-
 // ---- device envs: what every kind states about itself, and the ONE dispatch from a
 // ga_env_ref to its typed struct (rollout_host.cpp, rollout_loop.cpp).
 // Every struct has `n`; the observation width, the columns of an action row and

@@ -6,10 +6,12 @@
 // Host C++ only.  A layer is described ONCE (Layer, describe_layer: where its input,
 // weights and LayerNorm pieces sit in the flat layouts); a product of a layer is built
 // ONCE per kind (forward_product, wgrad_product, dgrad_product and the two tangent
-// products); each pass then reads: for each layer, describe, pick the streaming
-// (skinny.hip) / head-fused / tile kernel (gemm.hip), launch.  The kernels' entry
-// points are all this file calls, so tests/host/mlp_layers_harness.cpp builds it for
-// the CPU against recording fakes (`make asan-mlp`).
+// products); each pass then reads: for each layer, describe, ask the plans
+// (layer_plans.h: streaming, head-fused, tile -- which kernel takes a product is written
+// there, once) in that order, launch the first that takes the product.  The launch seam
+// of layer_plans.h and lnorm.hip's entry points are all this file calls, so
+// tests/host/mlp_layers_harness.cpp builds it for the CPU against recording fakes
+// (`make asan-mlp`).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -17,7 +19,7 @@
 #include "common.h"
 #include "internal.h"
 #include "fused_train.h"
-#include "gemm_params.h"
+#include "layer_plans.h"
 
 // ---------------------------------------------------------------------------
 // Developer switches of this dispatch
@@ -75,6 +77,12 @@ extern "C" int ga_set_fused_head_dgrad(int on) {
 static int g_skinny = 1;
 extern "C" int ga_set_skinny_kernels(int on) {
   g_skinny = on != 0;
+  return 0;
+}
+// the 64 x 64 x 128 tiles for products with few 128 x 128 tiles (layer_plans.h: GT_SMALL_M)
+static int g_small_m = 1;
+extern "C" int ga_set_small_m_gemm(int on) {
+  g_small_m = on != 0;
   return 0;
 }
 
@@ -201,7 +209,7 @@ static int rows_per_split(int64_t M, int64_t n_splits) {
 }
 
 // C = act(in W^T + b), M rows; head: the next (narrow, linear) layer in the same
-// launch, out = C head.W^T + head.bias (ga_gemm_launch_with_head)
+// launch, out = C head.W^T + head.bias (ga_gemm_head_launch)
 static GemmParams forward_product(const Layer& y, int64_t M, float* C, int64_t ldc, int act,
                                   const Layer* head = nullptr, float* out = nullptr,
                                   int64_t ldo = 0) {
@@ -224,8 +232,8 @@ static GemmParams forward_product(const Layer& y, int64_t M, float* C, int64_t l
 }
 
 // dW[o][i] = sum_b dz[b][o] * in[b][i] and db = column sums of dz, split-K over the M
-// rows into n_splits slabs (slab_w, slab_b: split 0's).  (gz: ga_gemm_launch_pair's
-// split count; ga_gemm_launch takes it as an argument.)
+// rows into n_splits slabs (slab_w, slab_b: split 0's).  (gz: the pair plan's split
+// count; ga_gemm_plan takes it as an argument.)
 static GemmParams wgrad_product(const Layer& y, const float* dz, int64_t lddz, int64_t M,
                                 int64_t n_splits, float* slab_w, float* slab_b,
                                 int64_t slab_stride) {
@@ -250,6 +258,34 @@ static GemmParams wgrad_product(const Layer& y, const float* dz, int64_t lddz, i
     p.M = y.out_w; p.N = y.in_w;
     p.c_rs = y.ldw; p.c_cs = 1;
     p.colsum_of_b = 0;
+  }
+  return p;
+}
+
+// The same product as the streaming kernel states it: C(wide, narrow) with the side that
+// is <= 32 as the narrow one (wgrad_product's choice of orientation); the bias gradient
+// is the column sums of whichever side dz is.
+static SkinnyWgradParams skinny_wgrad_product(const Layer& y, const float* dz, int64_t lddz,
+                                              int64_t M, int64_t n_splits, float* slab_w,
+                                              float* slab_b, int64_t slab_stride) {
+  SkinnyWgradParams p = {};
+  p.rows = (int)M;
+  p.rows_per_split = rows_per_split(M, n_splits);
+  p.n_splits = (int)n_splits;
+  p.C = slab_w;
+  p.split_stride = slab_stride;
+  if (y.out_w <= 32) {
+    // head layer: wide = the layer input, narrow = dz
+    p.Wd = y.in; p.ldw = y.ld_in; p.w_idx = y.in_idx; p.Nr = dz; p.ldn = lddz;
+    p.wide = y.in_w; p.NS = y.out_w;
+    p.c_wide_stride = 1; p.c_narrow_stride = y.ldw;
+    p.colsum_narrow = slab_b;
+  } else {
+    // wide = dz, narrow = the layer input
+    p.Wd = dz; p.ldw = lddz; p.Nr = y.in; p.ldn = y.ld_in; p.n_idx = y.in_idx;
+    p.wide = y.out_w; p.NS = y.in_w;
+    p.c_wide_stride = y.ldw; p.c_narrow_stride = 1;
+    p.colsum_wide = slab_b;
   }
   return p;
 }
@@ -297,6 +333,41 @@ static GemmParams tangent_input_product(const Layer& w, int64_t M, float* C, int
   else q.epi = EPI_PLAIN;
   q.k_per_split = full_k(q.K);
   return q;
+}
+
+// ---------------------------------------------------------------------------
+// Plan, then launch (layer_plans.h)
+// ---------------------------------------------------------------------------
+// The tile kernel takes every product: plan it under the switches, fill in what the plan
+// decides -- the weight planes are this side's to fetch -- and launch.
+static int launch_product(GemmParams p, int a_kc, int b_kc, int splits, hipStream_t stream) {
+  GA_REQUIRE(a_kc || !b_kc, "ga_gemm_launch: orientation not instantiated");
+  const GemmSwitches sw = {g_small_m != 0, ga_split_bf16_gemm() != 0,
+                           ga_split_bf16_enabled() != 0};
+  const GemmPlan plan = ga_gemm_plan(p, a_kc, b_kc, splits, sw);
+  ga_gemm_apply(plan, &p);
+  if (plan.planes) {
+    p.bplanes = ga_weight_planes(p.B, p.ldb, b_kc ? p.N : p.K, b_kc ? p.K : p.N,
+                                 plan.planes_bwd, stream);
+    GA_REQUIRE(p.bplanes, "gemm: no memory for the weight planes");
+  }
+  return ga_gemm_launch(plan, p, stream);
+}
+
+// The streaming forward (w_kc) / data gradient of `p` where its plan takes the product:
+// *taken says whether it did.
+static int try_skinny_forward(const GemmParams& p, bool w_kc, bool* taken,
+                              hipStream_t stream) {
+  static int rows_wg = -1;  // rows per workgroup
+  if (rows_wg < 0) {
+    const char* e = getenv("GARAGE_AMD_SKINNY_ROWS");  // A/B runs
+    rows_wg = e ? atoi(e) : 0;
+    if (rows_wg < 1) rows_wg = 32;
+  }
+  const SkinnyFwdPlan plan = ga_skinny_fwd_plan(p, w_kc, g_skinny != 0, rows_wg);
+  *taken = plan.taken;
+  return plan.taken ? ga_skinny_fwd_launch(plan, ga_skinny_fwd_params(p, plan), stream)
+                    : GA_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -356,20 +427,20 @@ extern "C" int ga_mlp_forward_f32(const ga_mlp_desc* d, const float* params,
         y, M, y.is_last ? out : acts + d->act_off[l], y.is_last ? ldo : round4(y.out_w),
         y.is_last ? d->output_act : act_forward_code(d->hidden_act),
         with_head ? &head : nullptr, out, ldo);
-    // (the streaming kernels know tanh and the identity)
-    if (g_skinny && p.act <= 1 && p.K <= 32 && p.N > 32) {
-      rc = ga_skinny_forward(p.A, p.lda, p.a_idx, p.B, p.ldb, true, p.bias, p.act,
-                             nullptr, 0, p.C, p.c_rs, p.M, p.N, p.K, stream);
-      if (rc < 0) return rc;
-      if (rc == 0) continue;
-    }
+    // the streaming kernel, else this layer and the head in one launch, else the tiles
+    bool streamed;
+    rc = try_skinny_forward(p, true, &streamed, stream);
+    if (rc) return rc;
+    if (streamed) continue;
     if (with_head) {
-      rc = ga_gemm_launch_with_head(&p, stream);
-      if (rc < 0) return rc;
-      if (rc == 0) break;  // both layers done
+      const GemmHeadPlan hp = ga_gemm_head_plan(p);
+      if (hp.taken) {
+        ga_gemm_head_apply(hp, &p);
+        return ga_gemm_head_launch(hp, p, stream);  // both layers done
+      }
       p.head_n = 0;
     }
-    rc = ga_gemm_launch(&p, 1, 1, 1, stream);
+    rc = launch_product(p, 1, 1, 1, stream);
     if (rc) return rc;
   }
   return GA_OK;
@@ -403,7 +474,10 @@ extern "C" int ga_wgrad_mid(const ga_wgrad_mid_net* nets, int n_nets, int64_t M,
     p[i] = wgrad_product(y, n.dz, round4(out_w), M, n_splits, n.slabs_w, n.slabs_b,
                          n.slab_stride);
   }
-  return ga_gemm_launch_pair(&p[0], &p[1], stream);
+  const GemmPairPlan plan = ga_gemm_pair_plan(p[0], p[1]);
+  GA_REQUIRE(plan.taken, "ga_gemm_launch_pair: two products of one shape");
+  for (GemmParams& q : p) { q.gx = plan.gx; q.gy = plan.gy; }  // (gz: wgrad_product's)
+  return ga_gemm_pair_launch(plan, p[0], p[1], stream);
 }
 
 extern "C" int ga_mlp_backward_f32(const ga_mlp_desc* d, const float* params,
@@ -455,34 +529,32 @@ extern "C" int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* para
     const int64_t lddz = y.is_last ? ldo : round4(y.out_w);
     float* slab_w = grad_slabs + d->w_off[l];
     float* slab_b = grad_slabs + d->b_off[l];
-    // ---- weight + bias gradient slabs
-    rc = 1;
-    if (g_skinny && y.in_w <= 32 && y.out_w > 32) {
-      // wide = dz (bias gradient = its column sums), narrow = layer input
-      rc = ga_skinny_wgrad(dz, lddz, nullptr, y.in, y.ld_in, y.in_idx, (int)M, y.out_w,
-                           y.in_w, kps, (int)n_splits, slab_w, y.ldw, 1, slab_stride, slab_b,
-                           nullptr, nullptr, 0, nullptr, 0, stream);
-    } else if (g_skinny && y.out_w <= 32 && y.in_w > 32) {
-      // head layer: the same pass over the hidden activations also yields the
-      // data gradient of the layer below (it needs dz and tanh' of `in` only)
-      const bool with_dz = g_fuse_head_dgrad && l > 0 && y.in_idx == nullptr &&
-                           d->hidden_act == 0 && !d->layer_norm;
-      rc = ga_skinny_wgrad(y.in, y.ld_in, y.in_idx, dz, lddz, nullptr, (int)M, y.in_w,
-                           y.out_w, kps, (int)n_splits, slab_w, 1, y.ldw, slab_stride,
-                           nullptr, slab_b, with_dz ? y.W : nullptr, y.ldw,
-                           with_dz ? dacts + d->act_off[l - 1] : nullptr, y.ldw, stream);
-      if (rc == 1 && with_dz)  // shape not taken with the data gradient: without
-        rc = ga_skinny_wgrad(y.in, y.ld_in, y.in_idx, dz, lddz, nullptr, (int)M, y.in_w,
-                             y.out_w, kps, (int)n_splits, slab_w, 1, y.ldw, slab_stride,
-                             nullptr, slab_b, nullptr, 0, nullptr, 0, stream);
-      else if (rc == 0 && with_dz)
-        dgrad_done = true;
+    // ---- weight + bias gradient slabs: the streaming kernel -- for the head layer with
+    // the data gradient of the layer below from the same pass over the hidden activations
+    // (it needs dz and tanh' of `in` only) where the shape takes it, else without -- else
+    // the tiles
+    SkinnyWgradParams w =
+        skinny_wgrad_product(y, dz, lddz, M, n_splits, slab_w, slab_b, slab_stride);
+    const bool with_dz = y.out_w <= 32 && g_fuse_head_dgrad && l > 0 &&
+                         y.in_idx == nullptr && d->hidden_act == 0 && !d->layer_norm;
+    if (with_dz) {
+      w.Wn = y.W; w.ldwn = y.ldw;
+      w.dz_out = dacts + d->act_off[l - 1]; w.lddz = y.ldw;
     }
-    if (rc < 0) return rc;
-    if (rc == 1) {
-      const GemmParams p =
-          wgrad_product(y, dz, lddz, M, n_splits, slab_w, slab_b, slab_stride);
-      rc = ga_gemm_launch(&p, 0, 0, (int)n_splits, stream);
+    SkinnyWgradPlan sp = ga_skinny_wgrad_plan(w, g_skinny != 0);
+    if (!sp.taken && with_dz) {
+      w.Wn = nullptr; w.ldwn = 0;
+      w.dz_out = nullptr; w.lddz = 0;
+      sp = ga_skinny_wgrad_plan(w, g_skinny != 0);
+    }
+    if (sp.taken) {
+      w.qpr = sp.qpr; w.n_colblk = sp.n_colblk;
+      rc = ga_skinny_wgrad_launch(sp, w, stream);
+      if (rc) return rc;
+      if (sp.variant == SWV_DZ) dgrad_done = true;
+    } else {
+      rc = launch_product(wgrad_product(y, dz, lddz, M, n_splits, slab_w, slab_b, slab_stride),
+                          0, 0, (int)n_splits, stream);
       if (rc) return rc;
     }
     // ---- data gradient for the layer below
@@ -494,13 +566,11 @@ extern "C" int ga_mlp_backward_range_f32(const ga_mlp_desc* d, const float* para
       float* dst = l > 0 ? dacts + d->act_off[l - 1] : dacts + y.xn_off;
       const GemmParams p = dgrad_product(y, M, dz, lddz, dst, y.norm_in ? nullptr : y.raw,
                                          d->hidden_act);
-      rc = 1;
-      if (g_skinny && !y.norm_in && d->hidden_act == 0 && p.K <= 32 && p.N > 32)
-        rc = ga_skinny_forward(p.A, p.lda, nullptr, p.B, p.ldb, false, nullptr, 0, p.H,
-                               p.ldh, p.C, p.c_rs, p.M, p.N, p.K, stream);
-      if (rc < 0) return rc;
-      if (rc == 1) {
-        rc = ga_gemm_launch(&p, 1, 0, 1, stream);
+      bool streamed;
+      rc = try_skinny_forward(p, false, &streamed, stream);
+      if (rc) return rc;
+      if (!streamed) {
+        rc = launch_product(p, 1, 0, 1, stream);
         if (rc) return rc;
       }
       if (y.norm_in) {
@@ -560,12 +630,12 @@ extern "C" int ga_mlp_jvp_f32(const ga_mlp_desc* d, const float* params,
     const bool two = l > 0 || t.norm_in;
     // in_l dW_l^T + db_l  (and the tanh' factor when it is the only product)
     const GemmParams p = tangent_weight_product(t, M, C, ldc, !two, H, d->hidden_act);
-    rc = ga_gemm_launch(&p, 1, 1, 1, stream);
+    rc = launch_product(p, 1, 1, 1, stream);
     if (rc) return rc;
     if (two) {
       // += tin_l W_l^T, then the tanh' factor
       const GemmParams q = tangent_input_product(w, M, C, ldc, H, d->hidden_act);
-      rc = ga_gemm_launch(&q, 1, 1, 1, stream);
+      rc = launch_product(q, 1, 1, 1, stream);
       if (rc) return rc;
     }
   }
@@ -584,5 +654,5 @@ extern "C" int ga_gemm_nt_f32(const float* A, int64_t lda, const float* B,
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.c_rs = ldc; p.c_cs = 1;
   p.M = (int)M; p.N = (int)N; p.K = (int)K; p.epi = EPI_PLAIN;
   p.k_per_split = full_k(p.K);
-  return ga_gemm_launch(&p, 1, 1, 1, stream);
+  return launch_product(p, 1, 1, 1, stream);
 }

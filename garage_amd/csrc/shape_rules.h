@@ -1,7 +1,8 @@
 // The kernel side's shape rules, each stated ONCE: which shapes a kernel family takes and
 // the tile arithmetic the host code sizes buffers and grids with (fused_train.hip,
-// narrow_step.hip, small_step.hip, policy_fused.hip, losses.hip).  The kernels take their constants
-// from here, the library's host code and the CPU harnesses under tests/host the rules.
+// narrow_step.hip, small_step.hip, policy_fused.hip, losses.hip, skinny.hip).  The kernels
+// take their constants from here, the library's host code and the CPU harnesses under
+// tests/host the rules.
 // No device code.
 // Not part of the C ABI.
 #pragma once
@@ -46,6 +47,32 @@ struct HeadLds {
 };
 constexpr HeadLds ga_head_lds(int A, int K) {
   return HeadLds{A * K, (A + 3) & ~3, HL_GROUPS * HL_ROWS_MAX * A};
+}
+
+// ---- skinny.hip: the streaming layer products (one dimension <= 32)
+constexpr int SK_THREADS = 256;      // forward / data gradient: threads per workgroup
+constexpr int SK_UNROLL = 4;         // rows a thread has in flight; rows_per_thread % 4 == 0
+constexpr int SK_KMAX = 32;          // the narrow operand: KV = round4(K) / 4 <= 8 quads
+constexpr int SK_LDS_CAP = 48 * 1024;  // bytes of staged narrow rows per workgroup, at most
+constexpr int SW_THREADS = 256;      // weight gradient: threads per workgroup
+constexpr int SW_QPR = 16;           // column quads (64 floats) per workgroup
+// (16 NV accumulator registers per thread: beyond NS = 24 the kernel spills; the
+// data-gradient instantiations exist for NV <= 4)
+constexpr int SW_NS_MAX = 24;
+constexpr int SW_NS_MAX_DZ = 16;
+constexpr bool ga_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// forward: column quads per workgroup -- the whole row when it is a power of two <= 256
+// floats, else 256-float column blocks; 0: no streaming shape
+constexpr int ga_skinny_fwd_qpr(int wide) {
+  return wide % 4 != 0 ? 0
+         : wide <= 256 ? (ga_pow2(wide / 4) ? wide / 4 : 0)
+                       : (wide % 256 == 0 ? 64 : 0);
+}
+// weight gradient: whole rows of <= 64 floats (a power of two), else 64-float column blocks
+constexpr int ga_skinny_wgrad_qpr(int wide) {
+  return wide % 4 != 0 ? 0
+         : wide <= 4 * SW_QPR ? (ga_pow2(wide / 4) ? wide / 4 : 0)
+                              : SW_QPR;
 }
 
 // The networks the step kernel takes with layer inputs up to `max_in`: up to 8 layers,

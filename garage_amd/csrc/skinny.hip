@@ -16,10 +16,11 @@
 // narrow operand is staged in LDS and read back as same-address broadcasts, and
 // the arithmetic is a sequential fp32 FMA chain on the vector ALU.
 #include "common.h"
-#include <stdlib.h>
 #include <hip/hip_ext.h>
 
 #include "prof.h"
+
+#include "layer_plans.h"  // SkinnyFwdParams, SkinnyWgradParams; shape_rules.h: SK_*, SW_*
 
 namespace {
 
@@ -30,27 +31,7 @@ __device__ __forceinline__ float tanh_fast(float x) {
 // ---------------------------------------------------------------------------
 // Y[m, n] = epi(sum_k X[row(m), k] * W(n, k)),  K <= 32, N = 4 * QPR * n_colblk
 // ---------------------------------------------------------------------------
-struct SkinnyFwdParams {
-  const float* X;        // [rows][ldx], K valid floats per row (ldx % 4 == 0)
-  int64_t ldx;
-  const int32_t* idx;    // optional row gather
-  const float* W;        // w_kc: W[n][ldw] (k contiguous) else W[k][ldw]
-  int64_t ldw;
-  const float* bias;     // epi 0: per-n bias (may be null)
-  const float* H;        // epi 1: tanh outputs H[m][ldh]
-  int64_t ldh;
-  float* Y;
-  int64_t ldy;
-  int M, N, K;
-  int act;               // epi 0: 1 = tanh
-  int qpr;               // column quads per row handled by one workgroup (<= 64)
-  int rows_per_thread;   // multiple of SK_UNROLL
-};
-
 typedef float sk_v2f __attribute__((ext_vector_type(2)));
-
-constexpr int SK_THREADS = 256;
-constexpr int SK_UNROLL = 4;
 
 // KV = round4(K) / 4 float4 of the narrow operand per row.  The X rows of the
 // workgroup are staged once in LDS (one gathered 16-B load per vector) and read
@@ -158,32 +139,6 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_fwd_kernel(SkinnyFwdParams 
 // ---------------------------------------------------------------------------
 // C(wide c, narrow j) = sum_r Wd[row_w(r), c] * Nr[row_n(r), j] per split of rows
 // ---------------------------------------------------------------------------
-struct SkinnyWgradParams {
-  const float* Wd;       // wide operand  [rows][ldw]
-  int64_t ldw;
-  const int32_t* w_idx;
-  const float* Nr;       // narrow operand [rows][ldn], NS valid floats
-  int64_t ldn;
-  const int32_t* n_idx;
-  int rows, wide, NS;
-  int rows_per_split;
-  int qpr;               // wide column quads per workgroup (<= 64)
-  int n_colblk, n_splits;  // logical grid; launched 1-D in XCD-aware order
-  float* C;
-  int64_t c_wide_stride, c_narrow_stride;  // C(c, j) at c * cws + j * cns
-  int64_t split_stride;
-  float* colsum_wide;    // optional: sum_r Wd[., c]  -> [split][c]
-  float* colsum_narrow;  // optional: sum_r Nr[., j]  -> [split][j]
-  // DZ instantiation (head weight gradient + the data gradient of the layer below
-  // in one pass over H): dz_out[r, c] = (sum_j Nr[r, j] * Wn[j, c]) * (1 - Wd[r, c]^2)
-  const float* Wn;       // [NS][ldwn] head weights, wide-contiguous
-  int64_t ldwn;
-  float* dz_out;         // [rows][lddz]
-  int64_t lddz;
-};
-
-constexpr int SW_THREADS = 256;
-constexpr int SW_QPR = 16;             // column quads (64 floats) per workgroup
 constexpr int SW_CHUNK = 256;          // rows of the narrow operand staged at a time
 constexpr int SW_LDS_FLOATS = 8192;    // 32 KB: narrow stage, then reduction stage
 
@@ -366,144 +321,69 @@ __global__ __launch_bounds__(SW_THREADS, (DZ && NV >= 4) ? 1 : 2) void skinny_wg
   }
 }
 
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-// columns per workgroup: the whole row when it is a power of two <= 256 floats,
-// else 256-float column blocks
-inline int pick_qpr(int wide) {
-  if (wide % 4 != 0) return 0;
-  if (wide <= 256) return pow2(wide / 4) ? wide / 4 : 0;
-  return (wide % 256 == 0) ? 64 : 0;
+// ---- the launch seam (layer_plans.h): the plan's words become an instantiation
+template <int KV>
+void launch_fwd(const SkinnyFwdPlan& plan, const SkinnyFwdParams& p, hipStream_t stream,
+                hipEvent_t e0, hipEvent_t e1) {
+  const dim3 grid(plan.gx, plan.gy);
+  if (plan.w_kc && plan.epi == 0)
+    hipExtLaunchKernelGGL((skinny_fwd_kernel<KV, true, 0>), grid, dim3(SK_THREADS),
+                          plan.lds_bytes, stream, e0, e1, 0, p);
+  else if (!plan.w_kc && plan.epi == 1)
+    hipExtLaunchKernelGGL((skinny_fwd_kernel<KV, false, 1>), grid, dim3(SK_THREADS),
+                          plan.lds_bytes, stream, e0, e1, 0, p);
 }
 
-template <int KV>
-void launch_fwd(const SkinnyFwdParams& p, bool w_kc, int epi, dim3 grid,
-                hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-  const int n_rg = SK_THREADS / p.qpr;
-  const unsigned lds = (unsigned)(n_rg * p.rows_per_thread * KV * 16);
-  if (w_kc && epi == 0)
-    hipExtLaunchKernelGGL((skinny_fwd_kernel<KV, true, 0>), grid, dim3(SK_THREADS), lds,
-                          stream, e0, e1, 0, p);
-  else if (!w_kc && epi == 1)
-    hipExtLaunchKernelGGL((skinny_fwd_kernel<KV, false, 1>), grid, dim3(SK_THREADS), lds,
-                          stream, e0, e1, 0, p);
+template <int NV>
+void launch_wgrad(const SkinnyWgradPlan& plan, const SkinnyWgradParams& p, hipStream_t stream,
+                  hipEvent_t e0, hipEvent_t e1) {
+  const dim3 grid(plan.grid), block(SW_THREADS);
+  if constexpr (NV <= 4) {  // (SW_NS_MAX_DZ)
+    if (plan.variant == SWV_DZ) {
+      hipExtLaunchKernelGGL((skinny_wgrad_kernel<NV, true, true>), grid, block, 0, stream, e0,
+                            e1, 0, p);
+      return;
+    }
+  }
+  if (plan.variant == SWV_NSUM)
+    hipExtLaunchKernelGGL((skinny_wgrad_kernel<NV, true>), grid, block, 0, stream, e0, e1, 0, p);
+  else if (plan.variant == SWV_PLAIN)
+    hipExtLaunchKernelGGL((skinny_wgrad_kernel<NV, false>), grid, block, 0, stream, e0, e1, 0,
+                          p);
 }
 
 }  // namespace
 
-// Internal entry points (called from the layer dispatch, mlp_layers.cpp; not in the C ABI).
-// Return 1 when the shape is not one these kernels take (caller falls back to the
-// MFMA tile kernel), 0 on launch, negative on error.
-
-// Y = act(X W^T + b): W[n][ldw] k-contiguous.  epi 0.
-// Y = (X W) * (1 - H^2): W[k][ldw] n-contiguous.  epi 1.
-int ga_skinny_forward(const float* X, int64_t ldx, const int32_t* idx, const float* W,
-                      int64_t ldw, bool w_kc, const float* bias, int act,
-                      const float* H, int64_t ldh, float* Y, int64_t ldy, int M, int N,
-                      int K, hipStream_t stream) {
-  const int qpr = pick_qpr(N);
-  if (K < 1 || K > 32 || qpr == 0 || ldx % 4 != 0 || ldw % 4 != 0 || ldy % 4 != 0 ||
-      (H && ldh % 4 != 0) || !ga_aligned16(X) || !ga_aligned16(W) || !ga_aligned16(Y) ||
-      (bias && !ga_aligned16(bias)) || (H && !ga_aligned16(H)) || ldx < ((K + 3) & ~3))
-    return 1;
-  if (w_kc != (H == nullptr)) return 1;  // only the two layer products above
-  SkinnyFwdParams p;
-  p.X = X; p.ldx = ldx; p.idx = idx; p.W = W; p.ldw = ldw; p.bias = bias; p.H = H;
-  p.ldh = ldh; p.Y = Y; p.ldy = ldy; p.M = M; p.N = N; p.K = K; p.act = act;
-  p.qpr = qpr;
-  const int n_rg = SK_THREADS / qpr;
-  // 32 rows per workgroup (never fewer than one unroll per thread): two generations
-  // of workgroups per CU, so one's prologue (gathered X rows, 20 KB of W quads from
-  // L2) runs under the other's stores.  Round 1 preferred 128 rows while the other
-  // update chain's streaming kernels shared the chip (146.2 / 143.3 / 152.9 ms per
-  // C3 iteration at 32 / 128 / 256); with those kernels folded into the GEMMs it
-  // is 131.5 / 133.0 / 132.7 ms at 32 / 64 / 128 (18.5 / 18.9 / 20.2 us a launch).
-  // Packed FMAs changed nothing: the kernel is bound by its store stream.
-  // (... but at least one workgroup per CU)
-  static int rows_wg_env = -1;  // A/B runs: GARAGE_AMD_SKINNY_ROWS
-  if (rows_wg_env < 0) {
-    const char* e = getenv("GARAGE_AMD_SKINNY_ROWS");
-    rows_wg_env = e ? atoi(e) : 0;
-  }
-  int rows_wg = rows_wg_env > 0 ? rows_wg_env : 32;
-  while (rows_wg > 32 && (int64_t)M < 256 * (int64_t)rows_wg) rows_wg >>= 1;
-  p.rows_per_thread = ((rows_wg / n_rg + SK_UNROLL - 1) / SK_UNROLL) * SK_UNROLL;
-  if (p.rows_per_thread < SK_UNROLL) p.rows_per_thread = SK_UNROLL;
-  const int rows_per_block = n_rg * p.rows_per_thread;
-  if ((int64_t)rows_per_block * ((K + 3) / 4) * 16 > 48 * 1024) return 1;
-  dim3 grid((unsigned)ga_ceil_div(M, rows_per_block),
-            (unsigned)ga_ceil_div(N, 4 * qpr));
+int ga_skinny_fwd_launch(const SkinnyFwdPlan& plan, const SkinnyFwdParams& p,
+                         hipStream_t stream) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // algorithmic bytes: the [M x N] output (+ H for the data gradient) + X
-  const double bytes = 4.0 * M * ((double)N * (H ? 2 : 1) + K);
-  ga_prof_events(GA_PROF_SKINNY_FWD, bytes, &e0, &e1);
-  const int epi = H ? 1 : 0;
-  switch ((K + 3) / 4) {
-    case 1: launch_fwd<1>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 2: launch_fwd<2>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 3: launch_fwd<3>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 4: launch_fwd<4>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 5: launch_fwd<5>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 6: launch_fwd<6>(p, w_kc, epi, grid, stream, e0, e1); break;
-    case 7: launch_fwd<7>(p, w_kc, epi, grid, stream, e0, e1); break;
-    default: launch_fwd<8>(p, w_kc, epi, grid, stream, e0, e1); break;
+  ga_prof_events(GA_PROF_SKINNY_FWD, plan.work, &e0, &e1);
+  switch (plan.KV) {
+    case 1: launch_fwd<1>(plan, p, stream, e0, e1); break;
+    case 2: launch_fwd<2>(plan, p, stream, e0, e1); break;
+    case 3: launch_fwd<3>(plan, p, stream, e0, e1); break;
+    case 4: launch_fwd<4>(plan, p, stream, e0, e1); break;
+    case 5: launch_fwd<5>(plan, p, stream, e0, e1); break;
+    case 6: launch_fwd<6>(plan, p, stream, e0, e1); break;
+    case 7: launch_fwd<7>(plan, p, stream, e0, e1); break;
+    default: launch_fwd<8>(plan, p, stream, e0, e1); break;
   }
   GA_CHECK_LAUNCH("skinny_fwd");
   return GA_OK;
 }
 
-int ga_skinny_wgrad(const float* Wd, int64_t ldw, const int32_t* w_idx, const float* Nr,
-                    int64_t ldn, const int32_t* n_idx, int rows, int wide, int NS,
-                    int rows_per_split, int n_splits, float* C, int64_t c_wide_stride,
-                    int64_t c_narrow_stride, int64_t split_stride, float* colsum_wide,
-                    float* colsum_narrow, const float* Wn, int64_t ldwn, float* dz_out,
-                    int64_t lddz, hipStream_t stream) {
-  // whole rows of <= 64 floats (a power of two), else 64-float column blocks
-  const int qpr = (wide % 4 != 0) ? 0
-                  : (wide <= 4 * SW_QPR ? (pow2(wide / 4) ? wide / 4 : 0) : SW_QPR);
-  // (16 NV accumulator registers per thread: beyond NS = 24 the kernel spills)
-  if (NS < 1 || NS > 24 || qpr == 0 || ldw % 4 != 0 || ldn % 4 != 0 ||
-      ldn < ((NS + 3) & ~3) || !ga_aligned16(Wd) || !ga_aligned16(Nr) ||
-      split_stride % 4 != 0 || (c_wide_stride == 1 && (c_narrow_stride % 4 != 0 ||
-                                                       !ga_aligned16(C))) ||
-      (colsum_wide && !ga_aligned16(colsum_wide)))
-    return 1;
-  SkinnyWgradParams p;
-  p.Wd = Wd; p.ldw = ldw; p.w_idx = w_idx; p.Nr = Nr; p.ldn = ldn; p.n_idx = n_idx;
-  p.rows = rows; p.wide = wide; p.NS = NS; p.rows_per_split = rows_per_split;
-  p.qpr = qpr; p.C = C; p.c_wide_stride = c_wide_stride;
-  p.c_narrow_stride = c_narrow_stride; p.split_stride = split_stride;
-  p.colsum_wide = colsum_wide; p.colsum_narrow = colsum_narrow;
-  p.Wn = Wn; p.ldwn = ldwn; p.dz_out = dz_out; p.lddz = lddz;
-  const bool dzf = dz_out != nullptr;
-  if (dzf && (w_idx || !Wn || ldwn % 4 != 0 || lddz % 4 != 0 || !ga_aligned16(Wn) ||
-              !ga_aligned16(dz_out) || NS > 16 || colsum_narrow == nullptr))
-    return 1;
-  p.n_colblk = (int)ga_ceil_div(wide, 4 * qpr);
-  p.n_splits = n_splits;
-  dim3 grid((unsigned)(p.n_colblk * p.n_splits));
+int ga_skinny_wgrad_launch(const SkinnyWgradPlan& plan, const SkinnyWgradParams& p,
+                           hipStream_t stream) {
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // algorithmic bytes: both operands once (+ the data gradient written once)
-  const double bytes = 4.0 * rows * ((double)wide * (dzf ? 2 : 1) + NS);
-  ga_prof_events(GA_PROF_SKINNY_WGRAD, bytes, &e0, &e1);
-  const bool nsum = colsum_narrow != nullptr;
-#define GA_SW_CASE(NVV)                                                              \
-  case NVV:                                                                          \
-    if (dzf && NVV <= 4)                                                             \
-      hipExtLaunchKernelGGL((skinny_wgrad_kernel<(NVV <= 4 ? NVV : 1), true, true>), \
-                            grid, dim3(SW_THREADS), 0, stream, e0, e1, 0, p);        \
-    else if (nsum)                                                                   \
-      hipExtLaunchKernelGGL((skinny_wgrad_kernel<NVV, true>), grid, dim3(SW_THREADS), \
-                            0, stream, e0, e1, 0, p);                                \
-    else                                                                             \
-      hipExtLaunchKernelGGL((skinny_wgrad_kernel<NVV, false>), grid,                 \
-                            dim3(SW_THREADS), 0, stream, e0, e1, 0, p);              \
-    break;
-  switch ((NS + 3) / 4) {
-    GA_SW_CASE(1) GA_SW_CASE(2) GA_SW_CASE(3) GA_SW_CASE(4) GA_SW_CASE(5) GA_SW_CASE(6)
-    default: return 1;
+  ga_prof_events(GA_PROF_SKINNY_WGRAD, plan.work, &e0, &e1);
+  switch (plan.NV) {
+    case 1: launch_wgrad<1>(plan, p, stream, e0, e1); break;
+    case 2: launch_wgrad<2>(plan, p, stream, e0, e1); break;
+    case 3: launch_wgrad<3>(plan, p, stream, e0, e1); break;
+    case 4: launch_wgrad<4>(plan, p, stream, e0, e1); break;
+    case 5: launch_wgrad<5>(plan, p, stream, e0, e1); break;
+    default: launch_wgrad<6>(plan, p, stream, e0, e1); break;
   }
-#undef GA_SW_CASE
   GA_CHECK_LAUNCH("skinny_wgrad");
   return GA_OK;
 }

@@ -115,12 +115,15 @@ def test_host_loops_under_address_sanitizer():
 
 def test_mlp_layer_dispatch_under_address_sanitizer():
     """``make asan-mlp``: the per-layer MLP dispatch (mlp_layers.cpp) compiled with
-    ``-fsanitize=address,undefined`` for the CPU and run against recording fakes of
-    every launch it makes (tests/host/mlp_layers_harness.cpp).  Each fake checks the
-    extent its kernel would reach against the exactly-sized buffer the pointer came
-    from: ragged widths, LayerNorm offsets, slabs x splits, the head layer's
-    transposed weight gradient; which launcher a layer takes under every switch; and
-    that the pair launch's weight-gradient descriptors are the single launch's."""
+    ``-fsanitize=address,undefined`` for the CPU, with the library's own kernel-choice
+    rules (layer_plans.h), and run against recording fakes of the launch seam below
+    them (tests/host/mlp_layers_harness.cpp).  Each fake checks the extent its kernel
+    would reach against the exactly-sized buffer the pointer came from -- ragged
+    widths, LayerNorm offsets, slabs x splits, the head layer's transposed weight
+    gradient, the weight planes -- and that the plan's grid covers the product; which
+    launcher a layer takes under every switch and at shapes a kernel refuses; that the
+    pair launch's weight-gradient descriptors are the single launch's; and the plans
+    against literal tables with both sides of every boundary."""
     out = subprocess.run(['make', '-C', ROOT, 'asan-mlp'], capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
