@@ -6,8 +6,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
-HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host
+HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack linear_baseline
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -68,7 +68,8 @@ clean:
 
 # Host-side C++ under AddressSanitizer + UBSan on the CPU (tests/host/): a harness program
 # is one translation unit of tests/host/ -- recording fakes of every kernel entry point
-# or launch-seam function (fused_params.h, rollout_params.h, loss_params.h, layer_plans.h)
+# or launch-seam function (fused_params.h, rollout_params.h, loss_params.h, layer_plans.h,
+# linear_baseline_params.h)
 # and HIP call the product source makes, and the checks -- linked with that product source.
 # One line per program: binary, harness source, product source.
 ASAN_PROGRAMS := \
@@ -79,7 +80,8 @@ ASAN_PROGRAMS := \
   member_pack_asan_test:member_pack_harness:member_pack_host \
   fused_host_asan_test:fused_host_harness:fused_train_host \
   rollout_host_asan_test:rollout_host_harness:rollout_host \
-  losses_host_asan_test:losses_host_harness:losses_host
+  losses_host_asan_test:losses_host_harness:losses_host \
+  linear_baseline_asan_test:linear_baseline_harness:linear_baseline_host
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -155,9 +157,17 @@ asan-rollout-host: $(OUT)/rollout_host_asan_test
 asan-losses-host: $(OUT)/losses_host_asan_test
 	$(OUT)/losses_host_asan_test
 
+# The host side of the linear feature baseline (linear_baseline_host.cpp) against fakes of
+# the launch seam: every refusal before any launch, grids that cover S on both sides of a
+# slab boundary, workspace sizes, tiles per wave and LDS bytes against literals, the
+# parameter structs field by field, the extents the kernels would reach.
+asan-linear-baseline: $(OUT)/linear_baseline_asan_test
+	$(OUT)/linear_baseline_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
-  asan-members asan-member-pack asan-fused-host asan-rollout-host asan-losses-host asan-all
+  asan-members asan-member-pack asan-fused-host asan-rollout-host asan-losses-host \
+  asan-linear-baseline asan-all

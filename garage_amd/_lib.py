@@ -374,6 +374,13 @@ SIGNATURES = {
     'ga_update_members_partials_floats': (c_i64, [C.POINTER(MlpDesc), c_i64,
                                                   c_i64]),
     'ga_update_epoch_members': (c_int, [C.POINTER(UpdateMembersArgs), ptr]),
+    # LinearFeatureBaseline (np/baselines/linear_feature_baseline.py:43-93)
+    'ga_linear_features_supported': (c_int, [c_int]),
+    'ga_linear_gram_workspace_doubles': (c_i64, [c_int, c_i64]),
+    'ga_linear_features_gram_f64': (c_int, [ptr, c_i64, c_int, ptr, c_i64,
+                                            c_i64, ptr, ptr, ptr, ptr, ptr]),
+    'ga_linear_features_predict_f32': (c_int, [ptr, c_i64, c_int, ptr, c_i64,
+                                               c_i64, ptr, ptr, c_i64, ptr]),
     'ga_set_allreduce_hook': (None, [ptr]),
     'ga_comm_available': (c_int, []),
     'ga_comm_unique_id': (c_int, [ptr]),

@@ -26,6 +26,11 @@ from garage_amd.optimizers import OptimizerWrapper, data_parallel_plan
 from garage_amd.policies import GaussianMLPPolicy
 
 
+def _is_linear(value_function):
+    """Whether ``value_function`` is a ``garage_amd.baselines.LinearFeatureBaseline``."""
+    return getattr(value_function, 'kind', None) == 'linear'
+
+
 class _OldPolicy:
     """Parameter snapshot standing in for ``copy.deepcopy(policy)`` (vpg.py:107)."""
 
@@ -81,8 +86,18 @@ class VPG:
                 'CategoricalMLPPolicy')
         self._policy_optimizer = policy_optimizer or OptimizerWrapper(
             torch.optim.Adam, policy)
-        self._vf_optimizer = vf_optimizer or OptimizerWrapper(
-            torch.optim.Adam, value_function)
+        # A LinearFeatureBaseline (garage_amd.baselines) is fitted in closed form
+        # once per iteration: no optimizer, no second chain of optimizer steps.
+        self._linear_vf = _is_linear(value_function)
+        if self._linear_vf:
+            if vf_optimizer is not None:
+                raise ValueError(
+                    'a LinearFeatureBaseline is fitted in closed form: pass no '
+                    'vf_optimizer beside it')
+            self._vf_optimizer = None
+        else:
+            self._vf_optimizer = vf_optimizer or OptimizerWrapper(
+                torch.optim.Adam, value_function)
         self._old_policy = _OldPolicy(policy)
         self._algo_id = 1  # VPG objective in the loss kernel
         self._lr_clip_range = 0.0
@@ -293,7 +308,15 @@ class VPG:
     def _before_train(self, eps):
         """Everything of an iteration up to the update: advantages, returns and
         the diagnostics before it.  Returns what :meth:`_train` and
-        :meth:`_after_train` read."""
+        :meth:`_after_train` read.
+
+        The value beyond an episode's end differs by baseline.  With an MLP
+        value function it is the value of the all-zero observation, which is
+        what the torch reference feeds through its padding.  With a
+        ``LinearFeatureBaseline`` it is ``v0 = 0.0``: garage's path for a numpy
+        baseline pads every episode's predictions with zeros
+        (``tf/algos/npo.py:195-201``), and the baselines themselves are the
+        previous iteration's fit (zeros in the first)."""
         batch = self._to_device_batch(eps)
         pol, vf = self.policy, self._value_function
         dev = pol.device
@@ -302,15 +325,25 @@ class VPG:
         n_cells, P = self._padded_cells(lengths)
         n_pad = n_cells - S
         pol.net._workspace(S)
-        vf.net._workspace(S)
         zero_obs = torch.zeros(1, batch.obs_dev.shape[1], device=dev)
         share = self._dp_setup(S)
 
-        # baselines on every valid step and on the all-zero observation the
-        # reference feeds through the padding (vpg.py:147,155-156; Q2)
-        values = torch.empty(S, 1, dtype=torch.float32, device=dev)
-        vf.net.forward(batch.obs_dev, S, out=values, keep_acts=False)
-        v0 = float(vf.net.forward(zero_obs, 1)[0, 0].item())
+        if self._linear_vf:
+            # The coefficients of the previous iteration's fit (zeros in the
+            # first).  The value beyond an episode's end is 0.0: garage's path
+            # for a numpy baseline pads every episode's predictions with zeros
+            # (tf/algos/npo.py:195-201, pad_batch_array) -- NOT with the value
+            # of the all-zero observation, which is what the MLP path below
+            # feeds.
+            values = vf.predict_batch(batch)
+            v0 = 0.0
+        else:
+            vf.net._workspace(S)
+            # baselines on every valid step and on the all-zero observation the
+            # reference feeds through the padding (vpg.py:147,155-156; Q2)
+            values = torch.empty(S, 1, dtype=torch.float32, device=dev)
+            vf.net.forward(batch.obs_dev, S, out=values, keep_acts=False)
+            v0 = float(vf.net.forward(zero_obs, 1)[0, 0].item())
 
         bonus, bonus_steps = 0.0, None
         gaussian = pol.kind == 'gaussian'
@@ -365,11 +398,14 @@ class VPG:
             batch, adv, old_ll, S, None, head=mean_old if same else None)
         kl_before = self._mean_kl(mean_old, mean_old_pad, s_old, mean_new,
                                   zero_obs, S, n_pad, n_cells)
-        vf_before, _, _ = self._value_loss_pass(batch, returns, S, None,
-                                                v=values)
+        if self._linear_vf:
+            vf_before = self._linear_vf_loss(values, returns)
+        else:
+            vf_before, _, _ = self._value_loss_pass(batch, returns, S, None,
+                                                    v=values)
 
         steps_before = (pol.net.adam_steps,
-                        self._value_function.net.adam_steps)
+                        None if self._linear_vf else vf.net.adam_steps)
         return types.SimpleNamespace(
             batch=batch, adv=adv, returns=returns, old_ll=old_ll, S=S,
             zero_obs=zero_obs, n_pad=n_pad, n_cells=n_cells, share=share,
@@ -392,15 +428,19 @@ class VPG:
             batch, adv, old_ll, S, None)
         kl_after = self._mean_kl(mean_old, mean_old_pad, s_old, mean_new,
                                  zero_obs, S, n_pad, n_cells)
-        vf_after, _, _ = self._value_loss_pass(batch, returns, S, None)
+        if self._linear_vf:
+            vf_after = self._linear_vf_loss(
+                self._value_function.predict_batch(batch), returns)
+        else:
+            vf_after, _, _ = self._value_loss_pass(batch, returns, S, None)
         if gaussian:
             entropy = self._entropy_value()
         else:
             entropy, _ = self._categorical_entropy(batch, adv, S, zero_obs,
                                                    n_pad, n_cells)
 
-        scalars = torch.stack([loss_before[0], loss_after[0], vf_before[0],
-                               vf_after[0]]).to(torch.float64)
+        scalars = torch.stack([x[0].to(torch.float64) for x in (
+            loss_before, loss_after, vf_before, vf_after)])
         scalars = torch.cat([scalars, kl_before, kl_after])
         if self._comm is not None:
             # losses are per-sample means: weight by this rank's sample share;
@@ -424,8 +464,9 @@ class VPG:
             # skipped: put them back to the iteration's start, so that a caller
             # who catches this and carries on (ga_set_small_step(0)) does not
             # train with bias corrections of steps that never happened
-            pol.net.adam_steps, self._value_function.net.adam_steps = \
-                steps_before
+            pol.net.adam_steps = steps_before[0]
+            if not self._linear_vf:
+                self._value_function.net.adam_steps = steps_before[1]
             raise RuntimeError(
                 'ga_small_step: a grid barrier timed out (reduction workspace '
                 'tag(s) {}: 0 = the main stream\'s network, 1 = the side '
@@ -628,9 +669,34 @@ class VPG:
         kl = self._kl_sum(head_old, s_old, head_new, s_new, M)
         return (kl[0] / M).to(torch.float32)
 
+    @staticmethod
+    def _linear_vf_loss(values, returns):
+        """Mean squared error of a linear baseline's predictions against the
+        returns, fp64, as a one-element device tensor."""
+        diff = values.view(-1).to(torch.float64) - returns.to(torch.float64)
+        return (diff * diff).mean().reshape(1)
+
     # -- the update (vpg.py:230-293) -------------------------------------------
     def _train(self, batch, adv, returns, old_ll):
         S = batch.n_samples
+        if self._linear_vf:
+            # The Gram pass goes first; the policy's passes follow on the same
+            # stream exactly as without it; the host solves the F x F system
+            # while they execute.
+            vf = self._value_function
+            vf.begin_fit(batch, returns)
+            try:
+                if self._native_update_ok():
+                    self._native_pass(self._policy_optimizer, self.policy, 0,
+                                      batch, adv, returns, old_ll)
+                else:
+                    for idx in self._policy_optimizer.minibatch_indices(S):
+                        self._train_policy(batch, adv, old_ll, idx)
+            except BaseException:
+                vf.cancel_fit()  # (the next iteration may begin one)
+                raise
+            vf.finish_fit()
+            return
         if self._native_update_ok():
             if getattr(self, 'overlap_updates', True):
                 self._train_native_pair(batch, adv, returns, old_ll)
@@ -651,6 +717,8 @@ class VPG:
                 or cls._train_value_function is not VPG._train_value_function):
             return False
         for opt in (self._policy_optimizer, self._vf_optimizer):
+            if opt is None:  # a linear baseline has no optimizer
+                continue
             if opt.grad_hook is not None and getattr(opt, 'native_comm',
                                                      None) is None:
                 return False
@@ -742,19 +810,23 @@ class VPG:
     def _train_native_serial(self, batch, adv, returns, old_ll):
         """Policy pass then value pass on the current stream (the reference's
         order, ``vpg.py:244-248``); ``overlap_updates = False`` selects it."""
-        import ctypes as C
-        S = batch.n_samples
         for opt, module, kind in ((self._policy_optimizer, self.policy, 0),
                                   (self._vf_optimizer, self._value_function,
                                    1)):
-            a, keep, n_mb = self._update_args(opt, module, kind, batch, adv,
-                                              returns, old_ll, 0)
-            for perm in opt.epoch_permutations(S):
-                a.perm = None if perm is None else perm.data_ptr()
-                a.step0 = module.net.adam_steps
-                call('ga_update_epoch', C.byref(a), stream_ptr())
-                module.net.adam_steps += n_mb
-            del keep
+            self._native_pass(opt, module, kind, batch, adv, returns, old_ll)
+
+    def _native_pass(self, opt, module, kind, batch, adv, returns, old_ll):
+        """Every epoch of one network's optimizer on the current stream."""
+        import ctypes as C
+        S = batch.n_samples
+        a, keep, n_mb = self._update_args(opt, module, kind, batch, adv,
+                                          returns, old_ll, 0)
+        for perm in opt.epoch_permutations(S):
+            a.perm = None if perm is None else perm.data_ptr()
+            a.step0 = module.net.adam_steps
+            call('ga_update_epoch', C.byref(a), stream_ptr())
+            module.net.adam_steps += n_mb
+        del keep
 
     def _train_native_pair(self, batch, adv, returns, old_ll):
         """Policy and value-function passes, interleaved on two HIP streams.
@@ -920,6 +992,9 @@ class VPG:
     def __setstate__(self, state):
         old = state.pop('_old_policy')
         self.__dict__.update(state)
+        # (snapshots written before linear baselines existed)
+        self.__dict__.setdefault('_linear_vf',
+                                 _is_linear(self._value_function))
         self._old_policy = _OldPolicy(self.policy)
         self._old_policy.params.copy_(torch.from_numpy(old))
 
@@ -948,7 +1023,7 @@ class PPO(VPG):
             policy_optimizer = OptimizerWrapper(
                 (torch.optim.Adam, dict(lr=2.5e-4)), policy,
                 max_optimization_epochs=10, minibatch_size=64)
-        if vf_optimizer is None:
+        if vf_optimizer is None and not _is_linear(value_function):
             vf_optimizer = OptimizerWrapper(
                 (torch.optim.Adam, dict(lr=2.5e-4)), value_function,
                 max_optimization_epochs=10, minibatch_size=64)
@@ -1008,7 +1083,7 @@ class TRPO(VPG):
             policy_optimizer = OptimizerWrapper(
                 (ConjugateGradientOptimizer, dict(max_constraint_value=0.01)),
                 policy)
-        if vf_optimizer is None:
+        if vf_optimizer is None and not _is_linear(value_function):
             vf_optimizer = OptimizerWrapper(
                 (torch.optim.Adam, dict(lr=2.5e-4)), value_function,
                 max_optimization_epochs=10, minibatch_size=64)
@@ -1048,6 +1123,16 @@ class TRPO(VPG):
         import ctypes as C
         S = batch.n_samples
         opt, vf = self._vf_optimizer, self._value_function
+        if self._linear_vf:
+            # as VPG._train: the Gram pass, the policy step, then the solve
+            vf.begin_fit(batch, returns)
+            try:
+                self._train_policy(batch, adv, old_ll, None)
+            except BaseException:
+                vf.cancel_fit()
+                raise
+            vf.finish_fit()
+            return
         native = (type(self)._train_value_function
                   is VPG._train_value_function
                   and getattr(opt, 'default_adam', True)
@@ -1505,6 +1590,10 @@ class PopulationPPO:
             if type(algo) not in (PPO, VPG):
                 raise ValueError('{} is a {}: PopulationPPO trains PPO or VPG '
                                  'objects'.format(who, type(algo).__name__))
+            if _is_linear(algo._value_function):
+                raise ValueError('{}: a LinearFeatureBaseline is not supported '
+                                 '(a population fits no joint Gram matrix)'
+                                 .format(who))
             for opt in (algo._policy_optimizer, algo._vf_optimizer):
                 if not opt.default_adam:
                     raise ValueError('{}: an optimizer other than torch\'s '

@@ -156,6 +156,10 @@ def shard_algo(algo, comm):
     """
     if comm is None:
         return algo
+    if getattr(algo._value_function, 'kind', None) == 'linear':
+        raise ValueError(
+            'shard_algo: a LinearFeatureBaseline is not data parallel (the '
+            'ranks\' Gram matrices are not summed)')
     algo._comm = comm
     use_rccl = dist.get_backend(comm.group) == 'nccl'
     pairs = ((algo.policy, algo._policy_optimizer),

@@ -1378,6 +1378,41 @@ GA_API int ga_set_ordered_allreduce(int on);
  * slower. */
 GA_API int ga_set_merged_pair(int on);
 
+/* ---- linear feature baseline ---------------------------------------------------
+ * garage.np.baselines.LinearFeatureBaseline (np/baselines/linear_feature_baseline.py):
+ * a ridge regression of the returns on the F = 2 * obs_dim + 4 features
+ *   [clip(obs, -10, 10), clip(obs)^2, al, al^2, al^3, 1],  al = t / 100.0,
+ * t the sample's index inside its episode (_features, lines 43-58).  Both passes form
+ * the feature rows on the fly, in fp64 from the clip on, and never write them to HBM.
+ *   obs     [S, ldo] fp32 (a DeviceEpisodeBatch's obs_dev); columns obs_dim .. ldo are
+ *           never read
+ *   ep_off  [n_eps + 1] int64, strictly increasing from 0 to S (episodes of length >= 1);
+ *           its CONTENT is the caller's contract: whatever it holds, no pass reads or
+ *           writes outside the arrays' stated sizes
+ * 1 <= obs_dim <= 128, 1 <= S < 2^31, 1 <= n_eps <= S; refused otherwise, and on a null
+ * pointer, ldo < obs_dim, ldv < 1 or an fp64 array that is not 8-byte aligned. */
+GA_API int ga_linear_features_supported(int obs_dim); /* 1 <= obs_dim <= 128 */
+/* doubles of `workspace` the Gram pass writes for (obs_dim, S) -- all of them, and
+ * nothing beyond; -1 for an obs_dim or S the passes refuse */
+GA_API int64_t ga_linear_gram_workspace_doubles(int obs_dim, int64_t S);
+/* gram [F, F] = featmat.T.dot(featmat) (full, exactly symmetric), rhs [F] =
+ * featmat.T.dot(returns) of LinearFeatureBaseline.fit (lines 68-75), fp64, returns [S]
+ * fp32.  The 16x16 tiles of the upper triangle run on the fp64 matrix instruction, one
+ * workgroup per slab of 2048 rows (every 1024th slab beyond 1024 of them); the
+ * workgroups' partials are added in a fixed order by a second launch: no atomics, the
+ * same inputs give the same bits.  The F x F solve is the caller's (numpy's lstsq, as the
+ * reference).  Algorithmic flops S * F * (F + 1) in fp64, HBM bytes 4 * S * (obs_dim + 1). */
+GA_API int ga_linear_features_gram_f64(const float* obs, int64_t ldo, int obs_dim,
+                                       const int64_t* ep_off, int64_t n_eps, int64_t S,
+                                       const float* returns, double* gram, double* rhs,
+                                       double* workspace, ga_stream_t stream);
+/* values[i * ldv] = (float)(features(i) . coeffs), coeffs [F] fp64 on the device: predict
+ * (lines 91-93) for every sample of the batch; one fp64 sum per row, in feature order. */
+GA_API int ga_linear_features_predict_f32(const float* obs, int64_t ldo, int obs_dim,
+                                          const int64_t* ep_off, int64_t n_eps, int64_t S,
+                                          const double* coeffs, float* values, int64_t ldv,
+                                          ga_stream_t stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Optional HIP-event timing of every GEMM / scan launch on its own stream
  * (bench.py's roofline leg; no reference counterpart).  kinds: 0..2 =
