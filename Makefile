@@ -7,7 +7,7 @@ ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
 HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack linear_baseline
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -81,7 +81,8 @@ ASAN_PROGRAMS := \
   fused_host_asan_test:fused_host_harness:fused_train_host \
   rollout_host_asan_test:rollout_host_harness:rollout_host \
   losses_host_asan_test:losses_host_harness:losses_host \
-  linear_baseline_asan_test:linear_baseline_harness:linear_baseline_host
+  linear_baseline_asan_test:linear_baseline_harness:linear_baseline_host \
+  linear_baseline_members_asan_test:linear_baseline_members_harness:linear_baseline_members_host
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -164,10 +165,17 @@ asan-losses-host: $(OUT)/losses_host_asan_test
 asan-linear-baseline: $(OUT)/linear_baseline_asan_test
 	$(OUT)/linear_baseline_asan_test
 
+# The population's entries of the linear feature baseline (linear_baseline_members_host.cpp)
+# against fakes of the seam: every refusal before any copy or launch, the flat grids and
+# prefix tables of uneven members (one beyond the grid's cap of a lone launch included),
+# each member's stretch of the workspace and the workspace bound, one table copy a call.
+asan-linear-baseline-members: $(OUT)/linear_baseline_members_asan_test
+	$(OUT)/linear_baseline_members_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
   asan-members asan-member-pack asan-fused-host asan-rollout-host asan-losses-host \
-  asan-linear-baseline asan-all
+  asan-linear-baseline asan-linear-baseline-members asan-all

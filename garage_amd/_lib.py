@@ -200,6 +200,20 @@ class UpdateMembersArgs(C.Structure):
                 ('partials_floats', c_i64), ('workspace', ptr)]
 
 
+class LinearGramMember(C.Structure):
+    """``ga_linear_gram_member``."""
+    _fields_ = [('obs', ptr), ('ldo', c_i64), ('ep_off', ptr),
+                ('n_eps', c_i64), ('S', c_i64), ('returns', ptr),
+                ('gram', ptr), ('rhs', ptr)]
+
+
+class LinearPredictMember(C.Structure):
+    """``ga_linear_predict_member``."""
+    _fields_ = [('obs', ptr), ('ldo', c_i64), ('ep_off', ptr),
+                ('n_eps', c_i64), ('S', c_i64), ('coeffs', ptr),
+                ('values', ptr), ('ldv', c_i64)]
+
+
 ABI_VERSION = 5  # ga_abi_version() of the library these structs mirror
 
 # name -> (restype, argtypes); mirrors include/garage_amd.h one to one.
@@ -381,6 +395,13 @@ SIGNATURES = {
                                             c_i64, ptr, ptr, ptr, ptr, ptr]),
     'ga_linear_features_predict_f32': (c_int, [ptr, c_i64, c_int, ptr, c_i64,
                                                c_i64, ptr, ptr, c_i64, ptr]),
+    'ga_linear_gram_members_workspace_doubles': (c_i64, [c_int, c_i64,
+                                                         C.POINTER(c_i64)]),
+    'ga_linear_features_gram_members_f64': (c_int, [
+        C.POINTER(LinearGramMember), c_i64, c_int, ptr, c_i64, ptr]),
+    'ga_linear_features_predict_members_f32': (c_int, [
+        C.POINTER(LinearPredictMember), c_i64, c_int, ptr]),
+    'ga_linear_members_release': (None, []),
     'ga_set_allreduce_hook': (None, [ptr]),
     'ga_comm_available': (c_int, []),
     'ga_comm_unique_id': (c_int, [ptr]),

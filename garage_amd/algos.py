@@ -305,10 +305,13 @@ class VPG:
         self._train(c.batch, c.adv, c.returns, c.old_ll)
         return self._after_train(itr, c)
 
-    def _before_train(self, eps):
+    def _before_train(self, eps, baselines=None):
         """Everything of an iteration up to the update: advantages, returns and
         the diagnostics before it.  Returns what :meth:`_train` and
-        :meth:`_after_train` read.
+        :meth:`_after_train` read.  ``baselines``: the ``[S, 1]`` predictions of
+        a ``LinearFeatureBaseline`` on ``eps`` where the caller has them already
+        (``PopulationPPO`` predicts every member's in one launch); without it
+        they are computed here.
 
         The value beyond an episode's end differs by baseline.  With an MLP
         value function it is the value of the all-zero observation, which is
@@ -335,7 +338,8 @@ class VPG:
             # (tf/algos/npo.py:195-201, pad_batch_array) -- NOT with the value
             # of the all-zero observation, which is what the MLP path below
             # feeds.
-            values = vf.predict_batch(batch)
+            values = (vf.predict_batch(batch) if baselines is None
+                      else baselines)
             v0 = 0.0
         else:
             vf.net._workspace(S)
@@ -414,9 +418,11 @@ class VPG:
             loss_before=loss_before, kl_before=kl_before,
             vf_before=vf_before, steps_before=steps_before)
 
-    def _after_train(self, itr, c):
+    def _after_train(self, itr, c, fitted=None):
         """The diagnostics after the update (``vpg.py:178-184``), the logged
-        scalars and the old policy's sync; returns the mean return."""
+        scalars and the old policy's sync; returns the mean return.  ``fitted``:
+        the ``[S, 1]`` predictions of the just fitted ``LinearFeatureBaseline``
+        where the caller has them already, as in :meth:`_before_train`."""
         pol, dev = self.policy, self.policy.device
         batch, adv, returns, old_ll, S = c.batch, c.adv, c.returns, c.old_ll, c.S
         zero_obs, n_pad, n_cells, share = c.zero_obs, c.n_pad, c.n_cells, c.share
@@ -430,7 +436,8 @@ class VPG:
                                  zero_obs, S, n_pad, n_cells)
         if self._linear_vf:
             vf_after = self._linear_vf_loss(
-                self._value_function.predict_batch(batch), returns)
+                self._value_function.predict_batch(batch) if fitted is None
+                else fitted, returns)
         else:
             vf_after, _, _ = self._value_loss_pass(batch, returns, S, None)
         if gaussian:
@@ -1523,6 +1530,14 @@ class PopulationPPO:
     permutation mode, the entropy configuration and torch's default-shaped Adam
     with the same ``betas`` and ``eps``.  They may differ in ``lr``,
     ``lr_clip_range``, ``policy_ent_coeff`` and their optimizers' ``seed``.
+    The value functions are either all MLPs, under the same rules, or -- in
+    member order -- the members of ONE
+    :class:`~garage_amd.baselines.LinearFeatureBaselinePopulation` (which may
+    differ in ``reg_coeff``): then there is no value-function pass at all, the
+    members' Gram passes are one launch begun before the policies' joint passes
+    and solved on the host while those execute, and their predictions are one
+    launch before and one after the update.  A ``LinearFeatureBaseline`` built
+    on its own is refused, as is a mixture.
     Anything else raises a ``ValueError`` naming it; nothing falls back to
     training the members one by one.
 
@@ -1550,9 +1565,13 @@ class PopulationPPO:
     def _shared_facts(algo):
         """(name, value) of everything the joint launches take ONE value of."""
         pol, vf = algo.policy, algo._value_function
+        linear = _is_linear(vf)
         facts = [('algorithm', type(algo).__name__),
-                 ('policy kind', pol.kind)]
+                 ('policy kind', pol.kind),
+                 ('value function kind', 'linear' if linear else 'mlp')]
         for name, mod in (('policy', pol), ('value function', vf)):
+            if linear and mod is vf:  # (no network: nothing more to share)
+                continue
             net = mod.net
             facts += [(name + ' network shape', tuple(net.dims)),
                       (name + ' hidden nonlinearity', net.hidden_act),
@@ -1566,6 +1585,8 @@ class PopulationPPO:
             facts.append(('policy double_softmax', bool(pol.double_softmax)))
         for name, opt in (('policy optimizer', algo._policy_optimizer),
                           ('vf optimizer', algo._vf_optimizer)):
+            if opt is None:  # a linear baseline has no optimizer
+                continue
             h = opt._hyper
             facts += [(name + ' minibatch_size', opt._minibatch_size),
                       (name + ' max_optimization_epochs',
@@ -1590,11 +1611,17 @@ class PopulationPPO:
             if type(algo) not in (PPO, VPG):
                 raise ValueError('{} is a {}: PopulationPPO trains PPO or VPG '
                                  'objects'.format(who, type(algo).__name__))
-            if _is_linear(algo._value_function):
-                raise ValueError('{}: a LinearFeatureBaseline is not supported '
-                                 '(a population fits no joint Gram matrix)'
-                                 .format(who))
+            linear = _is_linear(algo._value_function)
+            if linear and getattr(algo._value_function, '_population',
+                                  None) is None:
+                raise ValueError(
+                    '{}: a LinearFeatureBaseline built on its own is not '
+                    'supported: take the members\' value functions, in member '
+                    'order, from one garage_amd.baselines.'
+                    'LinearFeatureBaselinePopulation'.format(who))
             for opt in (algo._policy_optimizer, algo._vf_optimizer):
+                if opt is None:  # a linear baseline has no optimizer
+                    continue
                 if not opt.default_adam:
                     raise ValueError('{}: an optimizer other than torch\'s '
                                      'default-shaped Adam is not supported'
@@ -1610,6 +1637,8 @@ class PopulationPPO:
                 raise ValueError('{}: fuse_head is not supported'.format(who))
             for name, mod in (('policy', algo.policy),
                               ('value function', algo._value_function)):
+                if linear and name != 'policy':
+                    continue
                 if not _lib.load().ga_update_members_supported(
                         C.byref(mod.net._desc)):
                     raise ValueError(
@@ -1628,6 +1657,32 @@ class PopulationPPO:
         if len(set(mods)) != len(mods):
             raise ValueError('every member needs a policy and a value function '
                              'of its own')
+        # linear members: member m's value function is member m of ONE population
+        self._baselines = None
+        if _is_linear(self.members[0]._value_function):
+            population = self.members[0]._value_function._population
+            for m, algo in enumerate(self.members):
+                vf = algo._value_function
+                if vf._population is not population:
+                    raise ValueError(
+                        'member {}: its LinearFeatureBaseline belongs to another '
+                        'LinearFeatureBaselinePopulation than member 0\'s'
+                        .format(m))
+                if vf._index != m:
+                    raise ValueError(
+                        'member {}: its LinearFeatureBaseline is member {} of '
+                        'the LinearFeatureBaselinePopulation: hand them out in '
+                        'member order'.format(m, vf._index))
+            if len(population) != len(self.members):
+                raise ValueError(
+                    'the LinearFeatureBaselinePopulation has {} members, '
+                    'PopulationPPO {}'.format(len(population),
+                                              len(self.members)))
+            self._baselines = population
+
+    def _networks(self):
+        """Which of the members' networks train in the joint passes."""
+        return ('policy', ) if self._baselines is not None else ('policy', 'vf')
 
     def _modules(self, which):
         return [a.policy if which == 'policy' else a._value_function
@@ -1638,7 +1693,7 @@ class PopulationPPO:
         member's ``net`` then points at its row view."""
         self._rows, self._partials = {}, {}
         M = len(self.members)
-        for which in ('policy', 'vf'):
+        for which in self._networks():
             mods = self._modules(which)
             net0 = mods[0].net
             rows = {}
@@ -1725,14 +1780,33 @@ class PopulationPPO:
         the policies, then one for the value functions (on two streams).  The
         permutations are drawn as ``M`` lone ``_train_once`` calls one after
         another draw them: member 0's policy shuffles, then its value-function
-        shuffles, then member 1's."""
+        shuffles, then member 1's.
+
+        With linear baselines the joint Gram pass is begun first, the policies'
+        passes follow on the same stream and the host solves the members'
+        systems while they execute (as ``VPG._train`` does for one)."""
+        if self._baselines is None:
+            self._joint_passes(ctxs)
+            return
+        self._baselines.begin_fit([c.batch for c in ctxs],
+                                  [c.returns for c in ctxs])
+        try:
+            self._joint_passes(ctxs)
+        except BaseException:
+            self._baselines.cancel_fit()  # (the next iteration may begin one)
+            raise
+        self._baselines.finish_fit()
+
+    def _joint_passes(self, ctxs):
         import ctypes as C
+        networks = self._networks()
         perms = []
         for algo, c in zip(self.members, ctxs):
-            perms.append(
-                (list(algo._policy_optimizer.epoch_permutations(c.S)),
-                 list(algo._vf_optimizer.epoch_permutations(c.S))))
-        passes = [self._pass_args('policy', ctxs), self._pass_args('vf', ctxs)]
+            perms.append(tuple(
+                list((algo._policy_optimizer if which == 'policy'
+                      else algo._vf_optimizer).epoch_permutations(c.S))
+                for which in networks))
+        passes = [self._pass_args(which, ctxs) for which in networks]
         # the policies' passes on the current stream, the value functions' on a side
         # stream: the two share no written state (as VPG._train_native_pair)
         main = torch.cuda.current_stream()
@@ -1742,6 +1816,7 @@ class PopulationPPO:
         side.wait_stream(main)  # inputs (adv, returns, perms) are ready
         streams = [C.c_void_p(main.cuda_stream), C.c_void_p(side.cuda_stream)]
         epochs = max(len(p) for p in perms[0])
+        # (every member's counts are member 0's: _shared_facts)
         for e in range(epochs):
             for i, (a, arr, mods, opts) in enumerate(passes):
                 if e >= len(perms[0][i]):
@@ -1765,13 +1840,32 @@ class PopulationPPO:
         if len(batches) != len(self.members):
             raise ValueError('train_once needs one batch per member ({}), got '
                              '{}'.format(len(self.members), len(batches)))
-        ctxs = [algo._before_train(b)
-                for algo, b in zip(self.members, batches)]
+        ctxs = self._before_trains(batches)
         self._train(ctxs)
+        return self._after_trains(itr, ctxs)
+
+    def _before_trains(self, batches):
+        """Every member's ``_before_train``; linear baselines are predicted for
+        all members in one launch first (the previous iteration's fit)."""
+        before = [None] * len(self.members)
+        if self._baselines is not None:
+            batches = [algo._to_device_batch(b)
+                       for algo, b in zip(self.members, batches)]
+            before = self._baselines.predict_batches(batches)
+        return [algo._before_train(b, v)
+                for algo, b, v in zip(self.members, batches, before)]
+
+    def _after_trains(self, itr, ctxs):
+        """Every member's ``_after_train``, logged under ``member<m>/``; the just
+        fitted linear baselines are predicted in one launch first (for
+        ``vf/LossAfter``).  Returns the members' mean returns."""
+        after = [None] * len(self.members)
+        if self._baselines is not None:
+            after = self._baselines.predict_batches([c.batch for c in ctxs])
         returns = []
         for m, (algo, c) in enumerate(zip(self.members, ctxs)):
             with logger.tabular.prefix('member{}/'.format(m)):
-                returns.append(algo._after_train(itr, c))
+                returns.append(algo._after_train(itr, c, after[m]))
         return returns
 
     def train(self, trainer):
@@ -1801,6 +1895,7 @@ class PopulationPPO:
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('_baselines', None)
         self._adopt()
 
 

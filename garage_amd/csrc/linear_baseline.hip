@@ -25,6 +25,12 @@
 // writes every element of the upper triangle to both of its places (the lower half of
 // a diagonal tile is dropped, so G is exactly symmetric).  No atomics anywhere: the
 // same inputs give the same bits.
+//
+// A population.  gram_members_kernel, gram_reduce_members_kernel and predict_members_kernel
+// run every member's batch in one launch each: flat grids in which member m owns the
+// workgroups its lone grid would have, found through a prefix table, around the SAME
+// device functions (gram_body, gram_reduce_body, predict_body) with the workgroup's index
+// and count relative to the member -- so every member gets the lone kernels' bits.
 #include "common.h"
 #include "linear_baseline_params.h"
 #include "linear_features.h"
@@ -44,10 +50,15 @@ __device__ __forceinline__ void lb_tile_of(int p, int T, int* ti, int* tj) {
   *tj = i + rem;
 }
 
+// The Gram pass of ONE batch by workgroup `block` of the `n_blocks` that share it: the body
+// of gram_kernel (a batch a launch) and of gram_members_kernel (a population a launch),
+// written once.  The workgroup takes slabs block, block + n_blocks, .. and leaves its
+// partial in stretch `block` of p.partials.
 // One instantiation per number of column tiles T (1 .. 17), so that the waves' tiles and a
 // thread's loads are register arrays of exactly the size the shape needs.
 template <int T>
-__global__ __launch_bounds__(LB_THREADS) void gram_kernel(const LinGramParams p) {
+__device__ __forceinline__ void gram_body(const LinGramParams& p, const unsigned block,
+                                          const unsigned n_blocks) {
   constexpr int TPW = lb_tiles_per_wave_of(T);
   constexpr int NT = T * (T + 1) / 2;
   constexpr int LD = 16 * T + LB_LDS_PAD;
@@ -78,7 +89,7 @@ __global__ __launch_bounds__(LB_THREADS) void gram_kernel(const LinGramParams p)
   }
   double bacc = 0.0;  // (Phi^T r)[tid], tid < 16 T
 
-  for (int64_t slab = blockIdx.x; slab < p.n_slabs; slab += gridDim.x) {
+  for (int64_t slab = block; slab < p.n_slabs; slab += n_blocks) {
     const int64_t row0 = slab * LB_SLAB_ROWS;
     const int n_rows = (int)(p.S - row0 < LB_SLAB_ROWS ? p.S - row0 : LB_SLAB_ROWS);
     // ---- every row's step index: LB_SLAB_ROWS / LB_THREADS consecutive rows a thread
@@ -176,7 +187,7 @@ __global__ __launch_bounds__(LB_THREADS) void gram_kernel(const LinGramParams p)
   }
 
   // ---- this workgroup's partial
-  double* const out = p.partials + (int64_t)blockIdx.x * p.block_doubles;
+  double* const out = p.partials + (int64_t)block * p.block_doubles;
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
     const int tile = wave * TPW + q;
@@ -189,8 +200,40 @@ __global__ __launch_bounds__(LB_THREADS) void gram_kernel(const LinGramParams p)
   if (tid < 16 * T) out[NT * 256 + tid] = bacc;
 }
 
-__global__ __launch_bounds__(LB_REDUCE_THREADS) void gram_reduce_kernel(const LinReduceParams p) {
-  const int64_t e = (int64_t)blockIdx.x * LB_REDUCE_THREADS + threadIdx.x;
+template <int T>
+__global__ __launch_bounds__(LB_THREADS) void gram_kernel(const LinGramParams p) {
+  gram_body<T>(p, blockIdx.x, gridDim.x);
+}
+
+// The member of workgroup `block` of a flat grid: the last m with block0[m] <= block, for
+// block0 increasing from 0 (every member owns at least one workgroup).
+template <class Member>
+__device__ __forceinline__ int lb_member_of(const Member* __restrict__ members, int n_members,
+                                            int64_t block) {
+  int lo = 0, hi = n_members;
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if ((int64_t)members[mid].block0 <= block) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Every member of a population in one launch: the workgroup finds its member, and is
+// workgroup blockIdx.x - block0 of the n_blocks of that member's lone grid.
+template <int T>
+__global__ __launch_bounds__(LB_THREADS) void gram_members_kernel(const LinGramMembersParams g) {
+  const int m = lb_member_of(g.members, g.n_members, (int64_t)blockIdx.x);
+  const LinGramMemberDev& mem = g.members[m];
+  LinGramParams p;
+  p.obs = mem.obs; p.ldo = mem.ldo; p.obs_dim = g.obs_dim; p.ep_off = mem.ep_off;
+  p.n_eps = mem.n_eps; p.S = mem.S; p.returns = mem.returns; p.partials = mem.partials;
+  p.block_doubles = g.block_doubles; p.n_slabs = mem.n_slabs;
+  p.F = g.F; p.T = g.T; p.NT = g.NT; p.tpw = g.tpw; p.chunk_rows = g.chunk_rows;
+  gram_body<T>(p, blockIdx.x - (unsigned)mem.block0, (unsigned)mem.n_blocks);
+}
+
+// element e of a batch's G and b: its workgroups' partials added in workgroup order
+__device__ __forceinline__ void gram_reduce_body(const LinReduceParams& p, const int64_t e) {
   if (e >= p.block_doubles) return;
   double sum = 0.0;
   for (int b = 0; b < p.n_blocks; ++b) sum += p.partials[(int64_t)b * p.block_doubles + e];
@@ -209,9 +252,22 @@ __global__ __launch_bounds__(LB_REDUCE_THREADS) void gram_reduce_kernel(const Li
   }
 }
 
+__global__ __launch_bounds__(LB_REDUCE_THREADS) void gram_reduce_kernel(const LinReduceParams p) {
+  gram_reduce_body(p, (int64_t)blockIdx.x * LB_REDUCE_THREADS + threadIdx.x);
+}
+
+// row blockIdx.y of the grid is member blockIdx.y's reduce launch
+__global__ __launch_bounds__(LB_REDUCE_THREADS) void gram_reduce_members_kernel(
+    const LinGramMembersParams g) {
+  const LinGramMemberDev& mem = g.members[blockIdx.y];
+  LinReduceParams p;
+  p.partials = mem.partials; p.n_blocks = mem.n_blocks; p.block_doubles = g.block_doubles;
+  p.F = g.F; p.T = g.T; p.NT = g.NT; p.gram = mem.gram; p.rhs = mem.rhs;
+  gram_reduce_body(p, (int64_t)blockIdx.x * LB_REDUCE_THREADS + threadIdx.x);
+}
+
 // one thread a row; the sum runs in feature order, in fp64
-__global__ __launch_bounds__(LB_PREDICT_THREADS) void predict_kernel(const LinPredictParams p) {
-  const int64_t row = (int64_t)blockIdx.x * LB_PREDICT_THREADS + threadIdx.x;
+__device__ __forceinline__ void predict_body(const LinPredictParams& p, const int64_t row) {
   if (row >= p.S) return;
   const int64_t e = lb_episode_of(p.ep_off, p.n_eps, row);
   const int64_t t = row - p.ep_off[e];
@@ -231,6 +287,29 @@ __global__ __launch_bounds__(LB_PREDICT_THREADS) void predict_kernel(const LinPr
   p.values[row * p.ldv] = (float)v;
 }
 
+__global__ __launch_bounds__(LB_PREDICT_THREADS) void predict_kernel(const LinPredictParams p) {
+  predict_body(p, (int64_t)blockIdx.x * LB_PREDICT_THREADS + threadIdx.x);
+}
+
+// Every member of a population in one launch; a member without coefficients (a baseline
+// before its first fit) gets zeros.
+__global__ __launch_bounds__(LB_PREDICT_THREADS) void predict_members_kernel(
+    const LinPredictMembersParams g) {
+  const int m = lb_member_of(g.members, g.n_members, (int64_t)blockIdx.x);
+  const LinPredictMemberDev& mem = g.members[m];
+  const int64_t row =
+      ((int64_t)blockIdx.x - mem.block0) * LB_PREDICT_THREADS + threadIdx.x;
+  if (!mem.coeffs) {
+    if (row < mem.S) mem.values[row * mem.ldv] = 0.f;
+    return;
+  }
+  LinPredictParams p;
+  p.obs = mem.obs; p.ldo = mem.ldo; p.obs_dim = g.obs_dim; p.ep_off = mem.ep_off;
+  p.n_eps = mem.n_eps; p.S = mem.S; p.coeffs = mem.coeffs; p.values = mem.values;
+  p.ldv = mem.ldv;
+  predict_body(p, row);
+}
+
 }  // namespace
 
 // ---- the launch seam (linear_baseline_params.h): instantiate and launch, nothing else -----
@@ -246,6 +325,30 @@ void lb_launch_gram(const LinGramParams& p, unsigned blocks, unsigned lds_bytes,
     LB_GRAM(13); LB_GRAM(14); LB_GRAM(15); LB_GRAM(16); LB_GRAM(17);
   }
 #undef LB_GRAM
+}
+void lb_launch_gram_members(const LinGramMembersParams& p, unsigned blocks, unsigned lds_bytes,
+                            hipStream_t stream) {
+#define LB_GRAM(T)                                                                          \
+  case T:                                                                                   \
+    hipLaunchKernelGGL(gram_members_kernel<T>, dim3(blocks), dim3(LB_THREADS), lds_bytes,   \
+                       stream, p);                                                          \
+    break
+  switch (p.T) {
+    LB_GRAM(1); LB_GRAM(2); LB_GRAM(3); LB_GRAM(4); LB_GRAM(5); LB_GRAM(6);
+    LB_GRAM(7); LB_GRAM(8); LB_GRAM(9); LB_GRAM(10); LB_GRAM(11); LB_GRAM(12);
+    LB_GRAM(13); LB_GRAM(14); LB_GRAM(15); LB_GRAM(16); LB_GRAM(17);
+  }
+#undef LB_GRAM
+}
+void lb_launch_gram_reduce_members(const LinGramMembersParams& p, unsigned blocks,
+                                   hipStream_t stream) {
+  hipLaunchKernelGGL(gram_reduce_members_kernel, dim3(blocks, (unsigned)p.n_members),
+                     dim3(LB_REDUCE_THREADS), 0, stream, p);
+}
+void lb_launch_predict_members(const LinPredictMembersParams& p, unsigned blocks,
+                               hipStream_t stream) {
+  hipLaunchKernelGGL(predict_members_kernel, dim3(blocks), dim3(LB_PREDICT_THREADS), 0, stream,
+                     p);
 }
 void lb_launch_gram_reduce(const LinReduceParams& p, unsigned blocks, hipStream_t stream) {
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(blocks), dim3(LB_REDUCE_THREADS), 0, stream, p);

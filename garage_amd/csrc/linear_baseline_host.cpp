@@ -9,26 +9,10 @@
 //                                   (np/baselines/linear_feature_baseline.py:43-58,68-75)
 //   ga_linear_features_predict_f32  _features(path).dot(self._coeffs) of predict
 //                                   (linear_feature_baseline.py:91-93), a whole batch
+// (a population's entries, every member in one launch: linear_baseline_members_host.cpp)
 #include "common.h"
+#include "linear_baseline_checks.h"
 #include "linear_baseline_params.h"
-
-namespace {
-
-// what both passes ask of the batch; `who` names the entry point
-int batch_refused(const char* who, const float* obs, int64_t ldo, int obs_dim,
-                  const int64_t* ep_off, int64_t n_eps, int64_t S) {
-  GA_REQUIRE(obs && ep_off, "%s: null pointer", who);
-  GA_REQUIRE(obs_dim >= 1 && obs_dim <= LB_MAX_OBS,
-             "%s: obs_dim %d outside 1 .. %d", who, obs_dim, LB_MAX_OBS);
-  GA_REQUIRE(ldo >= obs_dim, "%s: ldo %lld < obs_dim %d", who, (long long)ldo, obs_dim);
-  GA_REQUIRE(S >= 1 && S < (1ll << 31), "%s: S %lld outside 1 .. 2^31 - 1", who,
-             (long long)S);
-  GA_REQUIRE(n_eps >= 1 && n_eps <= S, "%s: n_eps %lld outside 1 .. S", who,
-             (long long)n_eps);
-  return GA_OK;
-}
-
-}  // namespace
 
 extern "C" int ga_linear_features_supported(int obs_dim) {
   return obs_dim >= 1 && obs_dim <= LB_MAX_OBS;
@@ -45,7 +29,7 @@ extern "C" int ga_linear_features_gram_f64(const float* obs, int64_t ldo, int ob
                                            double* workspace, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "ga_linear_features_gram_f64";
-  if (int rc = batch_refused(who, obs, ldo, obs_dim, ep_off, n_eps, S)) return rc;
+  if (int rc = lb_batch_refused(who, obs, ldo, obs_dim, ep_off, n_eps, S)) return rc;
   GA_REQUIRE(returns && gram && rhs && workspace, "%s: null pointer", who);
   GA_REQUIRE(((uintptr_t)gram & 7) == 0 && ((uintptr_t)rhs & 7) == 0 &&
                  ((uintptr_t)workspace & 7) == 0,
@@ -73,7 +57,7 @@ extern "C" int ga_linear_features_predict_f32(const float* obs, int64_t ldo, int
                                               int64_t ldv, ga_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const char* who = "ga_linear_features_predict_f32";
-  if (int rc = batch_refused(who, obs, ldo, obs_dim, ep_off, n_eps, S)) return rc;
+  if (int rc = lb_batch_refused(who, obs, ldo, obs_dim, ep_off, n_eps, S)) return rc;
   GA_REQUIRE(coeffs && values, "%s: null pointer", who);
   GA_REQUIRE(((uintptr_t)coeffs & 7) == 0, "%s: coeffs must be 8-byte aligned", who);
   GA_REQUIRE(ldv >= 1, "%s: ldv %lld < 1", who, (long long)ldv);

@@ -96,6 +96,55 @@ struct LinPredictParams {
   int64_t ldv;
 };
 
+// ---- a population: every member's batch in ONE launch of each pass -----------------------
+// (linear_baseline_members_host.cpp).  The grids are flat: member m owns `n_blocks`
+// consecutive workgroups from `block0` on -- the prefix table a workgroup searches for its
+// member -- and inside them it is the lone kernel's grid: the workgroup's index and the
+// slab stride are relative to the member.
+struct LinGramMemberDev {
+  const float* obs;
+  int64_t ldo;
+  const int64_t* ep_off;
+  int64_t n_eps;
+  int64_t S;
+  const float* returns;
+  double* partials;        // the member's stretch: [n_blocks][block_doubles]
+  double* gram;            // [F, F]
+  double* rhs;             // [F]
+  int64_t n_slabs;         // lb_slabs(S)
+  int32_t block0;          // sum of the n_blocks of the members before this one
+  int32_t n_blocks;        // lb_gram_blocks(S)
+};
+
+// what the Gram launch and its reduce launch share
+struct LinGramMembersParams {
+  const LinGramMemberDev* members;  // DEVICE [n_members]
+  int n_members;
+  int obs_dim;
+  int64_t block_doubles;
+  int F, T, NT;
+  int tpw;
+  int chunk_rows;
+};
+
+struct LinPredictMemberDev {
+  const float* obs;
+  int64_t ldo;
+  const int64_t* ep_off;
+  int64_t n_eps;
+  int64_t S;
+  const double* coeffs;    // [F], or null: the member's values are zeros
+  float* values;
+  int64_t ldv;
+  int64_t block0;          // sum over the members before of ceil(S / LB_PREDICT_THREADS)
+};
+
+struct LinPredictMembersParams {
+  const LinPredictMemberDev* members;  // DEVICE [n_members]
+  int n_members;
+  int obs_dim;
+};
+
 // ---- linear_baseline.hip: the launch seam.  Each does nothing but launch on `stream`:
 // the Gram pass `blocks` workgroups of LB_THREADS with `lds_bytes` of dynamic LDS, the
 // instantiation p.T's; the other two `blocks` workgroups of their own thread count.
@@ -103,3 +152,11 @@ void lb_launch_gram(const LinGramParams& p, unsigned blocks, unsigned lds_bytes,
                     hipStream_t stream);
 void lb_launch_gram_reduce(const LinReduceParams& p, unsigned blocks, hipStream_t stream);
 void lb_launch_predict(const LinPredictParams& p, unsigned blocks, hipStream_t stream);
+// The population's: `blocks` is the sum of the members' workgroups (Gram, predict); the
+// reduce launch is a grid of (`blocks`, n_members) workgroups, row m member m's.
+void lb_launch_gram_members(const LinGramMembersParams& p, unsigned blocks, unsigned lds_bytes,
+                            hipStream_t stream);
+void lb_launch_gram_reduce_members(const LinGramMembersParams& p, unsigned blocks,
+                                   hipStream_t stream);
+void lb_launch_predict_members(const LinPredictMembersParams& p, unsigned blocks,
+                               hipStream_t stream);

@@ -16,6 +16,7 @@
 #include "internal.h"
 #include "fused_train.h"
 #include "members_step.h"
+#include "table_slots.h"
 
 namespace {
 
@@ -31,68 +32,9 @@ int64_t member_floats(const ga_mlp_desc* d, int64_t max_rows) {
   return 4 * tiles + tiles * ga_narrow_step_stride(d->dims[0], d->dims[1]);
 }
 
-// The tables of one pass: pinned host memory and its device copy.  A pass's launches
-// read the device copy after this call has returned, and the copies read the pinned
-// memory, so a pass takes the next of RING slots and `done` (recorded behind the
-// pass's last launch) is waited for before the slot is rewritten -- RING passes later:
-// the one place where this entry point may block its caller.
-struct Slot {
-  void* host = nullptr;
-  void* dev = nullptr;
-  size_t capacity = 0;  // bytes of each; grows, never shrinks
-  int device = -1;      // the device `dev` lives on
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
-constexpr int RING = 8;
-Slot g_slots[RING];
-int g_next = 0;
-std::mutex g_mu;
-
-void slot_free(Slot& s) {
-  if (s.host) (void)hipHostFree(s.host);
-  if (s.dev) (void)hipFree(s.dev);
-  s.host = s.dev = nullptr;
-  s.capacity = 0;
-  s.device = -1;
-}
-
-// The next slot, idle and holding at least `bytes` on the current device.  A slot is
-// re-allocated only to grow (to exactly `bytes`) or when the current device is another:
-// passes whose step counts differ by one from iteration to iteration reuse it as it is.
-Slot* slot_take(size_t bytes) {
-  Slot& s = g_slots[g_next];
-  g_next = (g_next + 1) % RING;
-  if (s.pending) {
-    if (hipEventSynchronize(s.done) != hipSuccess) return nullptr;
-    s.pending = false;
-  }
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return nullptr;
-  if (s.device != device && s.done) {  // (an event belongs to its device too)
-    (void)hipEventDestroy(s.done);
-    s.done = nullptr;
-  }
-  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
-    s.done = nullptr;
-    return nullptr;
-  }
-  if (s.capacity < bytes || s.device != device) {
-    slot_free(s);
-    if (hipHostMalloc(&s.host, bytes, hipHostMallocDefault) != hipSuccess) {
-      s.host = nullptr;
-      return nullptr;
-    }
-    if (hipMalloc(&s.dev, bytes) != hipSuccess) {
-      s.dev = nullptr;
-      slot_free(s);
-      return nullptr;
-    }
-    s.capacity = bytes;
-    s.device = device;
-  }
-  return &s;
-}
+// The tables of one pass go through a ring of pinned / device slots (table_slots.h): the
+// one place where this entry point may block its caller.
+GaTableRing g_ring;
 
 int64_t member_steps(int64_t S, int64_t mb) { return mb == 0 ? 1 : (S + mb - 1) / mb; }
 
@@ -171,12 +113,7 @@ extern "C" int64_t ga_update_members_partials_floats(const ga_mlp_desc* d, int64
 
 // frees the table slots (tests; the library otherwise keeps them for its lifetime)
 extern "C" void ga_update_members_release(void) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  for (Slot& s : g_slots) {
-    if (s.pending) (void)hipEventSynchronize(s.done);
-    s.pending = false;
-    slot_free(s);
-  }
+  g_ring.release();
 }
 
 extern "C" int ga_update_epoch_members(const ga_update_members_args* a,
@@ -210,8 +147,8 @@ extern "C" int ga_update_epoch_members(const ga_update_members_args* a,
   // [n] members, then [n_steps][n] Adam constants
   const size_t table_bytes = (size_t)n * sizeof(GaMemberDev);
   const size_t adam_bytes = (size_t)(n_steps * n) * sizeof(GaAdam);
-  std::lock_guard<std::mutex> lock(g_mu);
-  Slot* slot = slot_take(table_bytes + adam_bytes);
+  std::lock_guard<std::mutex> lock(g_ring.mu);
+  GaTableSlot* slot = g_ring.take(table_bytes + adam_bytes);
   if (!slot) {
     ga_set_error("ga_update_epoch_members: cannot allocate the member tables");
     return GA_ERR_HIP;
@@ -243,10 +180,8 @@ extern "C" int ga_update_epoch_members(const ga_update_members_args* a,
   GaAdam* adam_dev = reinterpret_cast<GaAdam*>(static_cast<char*>(slot->dev) + table_bytes);
   // from the first copy on the stream may read the slot: whatever happens after it, the
   // event goes behind what was enqueued and the slot counts as in flight
-  slot->pending = true;
   // (the two tables lie back to back in both memories: one copy carries both)
-  if (hipMemcpyAsync(slot->dev, slot->host, table_bytes + adam_bytes, hipMemcpyHostToDevice,
-                     stream) != hipSuccess) {
+  if (!GaTableRing::upload(slot, table_bytes + adam_bytes, stream)) {
     ga_set_error("ga_update_epoch_members: table upload failed");
     rc = GA_ERR_HIP;
   }
@@ -263,10 +198,7 @@ extern "C" int ga_update_epoch_members(const ga_update_members_args* a,
     if (!rc)
       rc = ga_members_reduce_adam(&sh, table_dev, adam_dev + k * n, k, tiles_k, stream);
   }
-  if (hipEventRecord(slot->done, stream) != hipSuccess) {
-    // nothing marks the end of what reads the slot: wait for it here
-    (void)hipStreamSynchronize(stream);
-    slot->pending = false;
+  if (!GaTableRing::mark_done(slot, stream)) {
     if (!rc) {
       ga_set_error("ga_update_epoch_members: hipEventRecord failed");
       rc = GA_ERR_HIP;

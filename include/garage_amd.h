@@ -1413,6 +1413,56 @@ GA_API int ga_linear_features_predict_f32(const float* obs, int64_t ldo, int obs
                                           const double* coeffs, float* values, int64_t ldv,
                                           ga_stream_t stream);
 
+/* The same two passes for a POPULATION of baselines of one obs_dim, every member's batch in
+ * ONE launch of each kernel (new: the reference fits one baseline per process).  Member m
+ * gets, bit for bit, what the lone entry point gives on its batch alone: the kernels share
+ * the lone kernels' bodies, a member owns the workgroups its lone grid would have (a flat
+ * grid, found through a prefix table), and its partials are added in its own workgroups'
+ * order.  members_host is a HOST array; the table the kernels read is built in pinned
+ * memory the library keeps and uploaded by one asynchronous copy, as
+ * ga_update_epoch_members' tables are (eight calls' worth: a call MAY BLOCK its caller on
+ * the call that used its slot eight calls earlier, and is not graph-capture safe). */
+typedef struct ga_linear_gram_member {
+  const float* obs; int64_t ldo;             /* [S, ldo] */
+  const int64_t* ep_off; int64_t n_eps;      /* [n_eps + 1] */
+  int64_t S;
+  const float* returns;                      /* [S] */
+  double* gram;                              /* [F, F] */
+  double* rhs;                               /* [F] */
+} ga_linear_gram_member;
+typedef struct ga_linear_predict_member {
+  const float* obs; int64_t ldo;
+  const int64_t* ep_off; int64_t n_eps;
+  int64_t S;
+  const double* coeffs;                      /* [F] fp64, or NULL: this member's values
+                                                are zeros (predict before the first fit,
+                                                linear_feature_baseline.py:91-92) */
+  float* values; int64_t ldv;                /* values[i * ldv] */
+} ga_linear_predict_member;
+/* doubles of `workspace` for members of S[0 .. n_members) samples (a HOST array): the sum of
+ * ga_linear_gram_workspace_doubles over them; -1 for anything the pass refuses */
+GA_API int64_t ga_linear_gram_members_workspace_doubles(int obs_dim, int64_t n_members,
+                                                        const int64_t* S);
+/* featmat.T.dot(featmat) and featmat.T.dot(returns) of LinearFeatureBaseline.fit
+ * (linear_feature_baseline.py:68-75, with _features' rows, lines 43-58) for every member:
+ * one Gram launch of sum_m blocks(S_m) workgroups and one reduce launch.  Refused before
+ * any launch or copy: null pointers, n_members outside 1 .. 1024, for any member what
+ * ga_linear_features_gram_f64 refuses, gram / rhs / workspace not 8-byte aligned,
+ * workspace_doubles below ga_linear_gram_members_workspace_doubles. */
+GA_API int ga_linear_features_gram_members_f64(const ga_linear_gram_member* members_host,
+                                               int64_t n_members, int obs_dim,
+                                               double* workspace, int64_t workspace_doubles,
+                                               ga_stream_t stream);
+/* _features(path).dot(self._coeffs) of predict (linear_feature_baseline.py:91-93) for every
+ * sample of every member, one launch.  Refused before any launch or copy: null pointers
+ * (coeffs excepted), n_members outside 1 .. 1024, for any member what
+ * ga_linear_features_predict_f32 refuses, more than 2^31 - 1 workgroups of 256 rows. */
+GA_API int ga_linear_features_predict_members_f32(const ga_linear_predict_member* members_host,
+                                                  int64_t n_members, int obs_dim,
+                                                  ga_stream_t stream);
+/* frees the member tables' slots (tests; the library otherwise keeps them) */
+GA_API void ga_linear_members_release(void);
+
 /* ---- measurement ----------------------------------------------------------
  * Optional HIP-event timing of every GEMM / scan launch on its own stream
  * (bench.py's roofline leg; no reference counterpart).  kinds: 0..2 =

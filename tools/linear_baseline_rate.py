@@ -16,12 +16,23 @@ events, after warm-up, ``--repeats`` times each, taking turns inside one process
             without this baseline -- GaussianMLPValueFunction MLP(256, 256),
             10 epochs x 32 minibatches of Adam on the current stream
 
+``--members M``: instead of the above, a population of M baselines at the
+population tools' member batch (64 episodes x 128 steps = 8192 samples, obs_dim 4,
+F = 12), host clock around each, the device idle before and after, taking turns:
+
+  joint     ``LinearFeatureBaselinePopulation``: ``begin_fit`` / ``finish_fit`` /
+            ``predict_batches`` -- one Gram launch, one reduce launch, one copy,
+            one wait, one predict launch for all members
+  lone      M ``LinearFeatureBaseline`` objects one after another, each
+            ``begin_fit`` / ``finish_fit`` / ``predict_batch``
+  (and the fit and the predict halves of each on their own)
+
 Printed per row, one JSON line: the median, the run-to-run spread
 ((max - min) / median), and for the two kernels the share of the fp64 matrix
 peak (algorithmic flops S * F * (F + 1) over 78.6 TF) and of the HBM bandwidth
 (algorithmic bytes 4 * S * (obs_dim + 1) over 8.0 TB/s spec).
 
-    python tools/linear_baseline_rate.py [--repeats 10] [--warmup 3]
+    python tools/linear_baseline_rate.py [--repeats 10] [--warmup 3] [--members M]
 """
 import argparse
 import json
@@ -108,13 +119,68 @@ def vf_mlp_pass(spec, batch, returns):
                                      returns, None)
 
 
+def members_rows(M, repeats, warmup):
+    """The joint fit + predict of M members against M lone ones."""
+    from garage_amd.baselines import (LinearFeatureBaseline,
+                                      LinearFeatureBaselinePopulation)
+    n_eps, T, obs_dim = 64, 128, 4
+    made = [make_batch(n_eps, T, obs_dim, seed=m) for m in range(M)]
+    spec = made[0][0]
+    batches, returns = [b for _, b, _ in made], [r for _, _, r in made]
+    pop = LinearFeatureBaselinePopulation(spec, M)
+    lones = [LinearFeatureBaseline(spec) for _ in range(M)]
+
+    def joint_fit():
+        pop.begin_fit(batches, returns)
+        pop.finish_fit()
+
+    def lone_fit():
+        for b, batch, ret in zip(lones, batches, returns):
+            b.begin_fit(batch, ret)
+            b.finish_fit()
+
+    def lone_predict():
+        return [b.predict_batch(batch) for b, batch in zip(lones, batches)]
+
+    rows = [('joint fit', joint_fit), ('lone fit', lone_fit),
+            ('joint predict', lambda: pop.predict_batches(batches)),
+            ('lone predict', lone_predict),
+            ('joint fit+predict', lambda: (joint_fit(),
+                                           pop.predict_batches(batches))),
+            ('lone fit+predict', lambda: (lone_fit(), lone_predict()))]
+    times = {name: [] for name, _ in rows}
+    for rep in range(warmup + repeats):
+        for name, fn in rows:
+            ms = host_ms(fn)
+            if rep >= warmup:
+                times[name].append(ms)
+    for m in range(M):  # the two sides computed the same
+        assert np.array_equal(pop[m].get_param_values(),
+                              lones[m].get_param_values()), m
+    for name, _ in rows:
+        t = np.asarray(times[name])
+        med = float(np.median(t))
+        print(json.dumps(dict(
+            members=M, S=n_eps * T, obs_dim=obs_dim, F=2 * obs_dim + 4,
+            what=name, median_ms=round(med, 4), min_ms=round(float(t.min()), 4),
+            max_ms=round(float(t.max()), 4),
+            spread=round(float((t.max() - t.min()) / med), 3),
+            repeats=len(t))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--members', type=int, default=0,
+                    help='a population of this many baselines against as many '
+                         'lone ones, instead of the kernels\' rates')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('linear_baseline_rate: needs an MI355X')
+    if args.members:
+        members_rows(args.members, args.repeats, args.warmup)
+        return
     from garage_amd import _lib
     from garage_amd.baselines import LinearFeatureBaseline
     for tag, n_eps, T, obs_dim in SHAPES:

@@ -11,6 +11,11 @@ it, with a device synchronise before and after each of the five phases:
   update         ``PopulationPPO._train``: the joint passes of both networks
   after_train    every member's ``_after_train``, one after another
 
+``--linear-baseline``: the value functions are the members of one
+``LinearFeatureBaselinePopulation``: before_train and after_train then begin with
+the one predict launch for all members, and update is the joint fit around the
+policies' passes.
+
 After warm-up every repeat runs the five phases in order; printed is one JSON line
 per phase with the median over the repeats, the range and the spread
 ((max - min) / median), then the phases' total.
@@ -44,15 +49,18 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--per-member-pack', action='store_true',
                     help='joint_pack=False: one _pack per member')
+    ap.add_argument('--linear-baseline', action='store_true',
+                    help='one LinearFeatureBaselinePopulation as the value '
+                         'functions')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_iteration_phases needs an MI355X: there is '
                          'nothing to measure on a CPU')
-    from garage_amd import logger
     from garage_amd.algos import PopulationPPO
     from garage_amd.sampler import GpuPopulationSampler
     M = args.members
-    env, members = make_members(M, args.minibatch)
+    env, members = make_members(M, args.minibatch,
+                                'joint' if args.linear_baseline else None)
     pop = PopulationPPO(members)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5,
@@ -89,13 +97,11 @@ def main():
         tick()
         batches = sampler.obtain_samples(itr, ENVS * STEPS, pop.member_params)
         sampled = tick()
-        ctxs = [algo._before_train(b) for algo, b in zip(pop.members, batches)]
+        ctxs = pop._before_trains(batches)
         before = tick()
         pop._train(ctxs)
         update = tick()
-        for m, (algo, c) in enumerate(zip(pop.members, ctxs)):
-            with logger.tabular.prefix('member{}/'.format(m)):
-                algo._after_train(itr, c)
+        pop._after_trains(itr, ctxs)
         after = tick()
         if keep:
             for k, v in zip(PHASES, (sampled - clock['packing'], clock['packing'],
@@ -106,7 +112,8 @@ def main():
         v = np.asarray(v)
         print(json.dumps(dict(
             phase=k, members=M, minibatch=args.minibatch,
-            joint_pack=not args.per_member_pack, median_ms=float(np.median(v)),
+            joint_pack=not args.per_member_pack,
+            linear_baseline=args.linear_baseline, median_ms=float(np.median(v)),
             min_ms=float(v.min()), max_ms=float(v.max()),
             spread=float((v.max() - v.min()) / np.median(v)),
             share=float(np.median(v) / np.median(total)),

@@ -13,11 +13,17 @@ batches and from the same initial state, for
   (c) the same with ``ga_set_small_step(0)``: the lone NARROW path at every minibatch
       size, the path each member is the bit-for-bit twin of.
 
+``--linear-baseline``: the members' value functions are the members of one
+``LinearFeatureBaselinePopulation`` (lone ``LinearFeatureBaseline`` objects in (b)
+and (c)): the update is then the policies' passes around the closed-form fit, and
+no value-function pass at all.
+
 A, B and C take turns inside one process; after warm-up every repeat is timed with HIP
 events around the update and the medians, their ratio and the run-to-run spread
 ((max - min) / median over the repeats) are printed, one JSON line per row.
 
     python tools/population_update_rate.py [--members 1 8 64] [--repeats 10]
+                                           [--linear-baseline]
 """
 import argparse
 import json
@@ -34,25 +40,37 @@ if ROOT not in sys.path:
 ENVS, STEPS, EPOCHS = 64, 128, 10
 
 
-def make_members(M, minibatch):
+def make_members(M, minibatch, linear=None):
+    """``linear``: None -- MLP(64, 64) value functions; 'joint' -- the members of
+    one LinearFeatureBaselinePopulation; 'lone' -- lone LinearFeatureBaselines."""
     from garage_amd.algos import PPO
+    from garage_amd.baselines import (LinearFeatureBaseline,
+                                      LinearFeatureBaselinePopulation)
     from garage_amd.envs import CartPoleVecEnv
     from garage_amd.optimizers import OptimizerWrapper
     from garage_amd.policies import (CategoricalMLPPolicy,
                                      GaussianMLPValueFunction)
     env = CartPoleVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
+    joint = LinearFeatureBaselinePopulation(env.spec, M) if linear == 'joint' \
+        else None
     members = []
     for m in range(M):
         torch.manual_seed(100 + m)
         pol = CategoricalMLPPolicy(env.spec, hidden_sizes=(64, 64))
-        vf = GaussianMLPValueFunction(env.spec, hidden_sizes=(64, 64))
         opt = (torch.optim.Adam, dict(lr=2.5e-4 * (1 + m % 4)))
+        if linear is None:
+            vf = GaussianMLPValueFunction(env.spec, hidden_sizes=(64, 64))
+            vf_opt = OptimizerWrapper(opt, vf, EPOCHS, minibatch,
+                                      permutation='device', seed=1000 + m)
+        else:
+            vf = joint[m] if joint is not None else LinearFeatureBaseline(
+                env.spec)
+            vf_opt = None
         members.append(PPO(
             env_spec=env.spec, policy=pol, value_function=vf, sampler=None,
             policy_optimizer=OptimizerWrapper(opt, pol, EPOCHS, minibatch,
                                               permutation='device', seed=m),
-            vf_optimizer=OptimizerWrapper(opt, vf, EPOCHS, minibatch,
-                                          permutation='device', seed=1000 + m)))
+            vf_optimizer=vf_opt))
     return env, members
 
 
@@ -67,19 +85,19 @@ def timed(fn):
     return start.elapsed_time(stop)
 
 
-def measure(M, minibatch, repeats, warmup):
+def measure(M, minibatch, repeats, warmup, linear=False):
     from garage_amd import _lib
     from garage_amd.algos import PopulationPPO
     from garage_amd.sampler import GpuPopulationSampler
     lib = _lib.load()
-    env, members = make_members(M, minibatch)
-    _, lones = make_members(M, minibatch)
-    _, narrows = make_members(M, minibatch)
+    env, members = make_members(M, minibatch, 'joint' if linear else None)
+    _, lones = make_members(M, minibatch, 'lone' if linear else None)
+    _, narrows = make_members(M, minibatch, 'lone' if linear else None)
     pop = PopulationPPO(members)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5)
     batches = sampler.obtain_samples(0, ENVS * STEPS, pop.member_params)
-    joint = [a._before_train(b) for a, b in zip(pop.members, batches)]
+    joint = pop._before_trains(batches)
     lone = [a._before_train(b) for a, b in zip(lones, batches)]
     narrow = [a._before_train(b) for a, b in zip(narrows, batches)]
 
@@ -113,7 +131,7 @@ def measure(M, minibatch, repeats, warmup):
         return float((t.max() - t.min()) / np.median(t))
 
     return dict(
-        members=M, minibatch=minibatch,
+        members=M, minibatch=minibatch, linear_baseline=bool(linear),
         samples_per_member=[int(c.S) for c in joint][:4],
         population_ms=float(np.median(ta)), lone_ms=float(np.median(tb)),
         lone_narrow_ms=float(np.median(tc)),
@@ -132,6 +150,10 @@ def main():
                          'minibatches per pass of 8192 samples)')
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--linear-baseline', action='store_true',
+                    help='LinearFeatureBaseline value functions: one '
+                         'LinearFeatureBaselinePopulation in (a), lone ones in '
+                         '(b) and (c)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_update_rate needs an MI355X: there is nothing '
@@ -140,7 +162,8 @@ def main():
         raise SystemExit('medians of at least 10 repeats')
     for minibatch in args.minibatches:
         for M in args.members:
-            print(json.dumps(measure(M, minibatch, args.repeats, args.warmup)),
+            print(json.dumps(measure(M, minibatch, args.repeats, args.warmup,
+                                     args.linear_baseline)),
                   flush=True)
 
 
