@@ -23,7 +23,7 @@ OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # include/garage_amd.h declares (GA_API); tests/test_abi_cpu.py compares the two.
 FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -fno-slp-vectorize -fvisibility=hidden -fvisibility-inlines-hidden $(EXTRA)
 
-all: $(OUT)/libgarage_amd.so
+all: $(OUT)/libgarage_amd.so $(OUT)/libgarage_amd_fused_entries.so
 
 # (header dependencies come from the compiler: -MMD -MP writes $(OUT)/x.d beside x.o)
 $(OUT)/%.o: $(CSRC)/%.hip
@@ -38,6 +38,19 @@ $(OUT)/%.o: $(CSRC)/%.cpp
 
 $(OUT)/libgarage_amd.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -ldl -o $@
+
+# For tests/test_fused_entries_strides_gpu.py only: the same objects linked a second time
+# with tests/host/fused_entries_shim.cpp, which exports one wrapper around the fused
+# step's forward + loss and data-gradient entry points (they are not part of the C ABI
+# and stay hidden in the library itself).
+$(OUT)/fused_entries_shim.o: tests/host/fused_entries_shim.cpp
+	@mkdir -p $(OUT)
+	$(HIPCC) $(FLAGS) -MMD -MP -x hip -c $< -o $@
+
+-include $(OUT)/fused_entries_shim.d
+
+$(OUT)/libgarage_amd_fused_entries.so: $(OBJS) $(OUT)/fused_entries_shim.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) $(OUT)/fused_entries_shim.o -ldl -o $@
 
 # developer tool: the matrix pipe's own ceiling (register-only MFMA loops)
 mfma-peak: tools/mfma_peak.hip

@@ -145,6 +145,41 @@ __host__ __device__ inline float ga_log_std(float param, int has_min, float min_
   return p;
 }
 
+// ---- scalar-offset addressing.  A buffer instruction's address is
+//   base (descriptor, 4 SGPRs) + scalar offset (SGPR) + lane offset (ONE VGPR) + immediate
+// (< 4096): where a loop's accesses differ from each other by wave-uniform amounts only,
+// the lane offset is computed once in front of the loop and the loop itself needs no
+// vector arithmetic for its addresses -- a global_load takes a 64-bit vector address per
+// access instead (beside an fp32 MFMA every vector instruction costs its issue time).
+// `base` and `bytes` must be wave-uniform (kernel arguments, blockIdx, a readfirstlane'd
+// wave id), so must every `soff`; all offsets are bytes, and base + every offset stays
+// below 4 GB from `base`.  `bytes` is the exact extent behind `base` that the caller may
+// touch: the unit drops an access whose lane offset + immediate reaches beyond it (a load
+// returns zero, a store writes nothing).  The scalar offset is NOT part of that test, so
+// this is a second line behind the caller's own clamps and predicates, never their
+// replacement.  Vector memory instructions only.
+struct GaBuffer {
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ GaBuffer(const void* base, uint32_t bytes)
+      : r(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes,
+                                            0x00020000)) {}
+  __device__ __forceinline__ float load(uint32_t voff, uint32_t soff) const {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
+  }
+  __device__ __forceinline__ float4 load4(uint32_t voff, uint32_t soff) const {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
+    return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                       __uint_as_float(v[3]));
+  }
+  __device__ __forceinline__ void store4(const float4& x, uint32_t voff, uint32_t soff) const {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z),
+                     __float_as_uint(x.w)};
+    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, (int)soff, 0);
+  }
+};
+
 __device__ __forceinline__ float ga_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -78,6 +78,9 @@
 // layer's width, k < K since K % 32 == 0), head weights and bias (j < A), bias
 // columns (< BN).  Stores of rows >= M are predicated; per-tile partials are sized by
 // ga_update_partials_floats (tests/host/update_loop_harness.cpp, check 9).
+// The accesses that go through a buffer descriptor (GaBuffer, common.h: W2 and W
+// fragments, the H1 spill, the fused epilogue's dZ stores) reach the addresses they
+// reached as global accesses and keep the guards above; the descriptor's extent is exact.
 namespace {
 
 // (FT_ROWS = 64 rows per workgroup tile, FT_W1_FLOATS: shape_rules.h; the parameter
@@ -135,6 +138,74 @@ __device__ __forceinline__ void ft_kstep(const float* As, const float* Bs,
   }
 }
 
+// The B fragments of dgrad_kloop_staged (W2 [K = BN][ldb], n-contiguous): lane (l31, half)
+// feeds B(k, n = wn0 + 32 j + l31), k = 32 s + 8 g + 4 half + q -- four dword loads per
+// group, straight from L2 (every workgroup reads all of W2).  A struct of its own because
+// fwd_dgrad_kernel issues the first step's loads from inside the forward body's epilogue.
+template <int BN, int TN>
+struct FtW2Frags {
+  float bn[TN][BK / 8][4];
+  // wave-uniform base + one 32-bit lane offset (rows k < K = BN, columns < BN <= ldb)
+  uint32_t ldb, woff;
+#ifdef GA_FT_NO_BUFFER_ADDR
+  const float* B;
+#else
+  // W2 as a buffer (GaBuffer, common.h) of BN rows, the last one BN floats long: the lane's
+  // byte offset is one register for the whole loop, a load's row (32 s + 8 g + q) * ldb is
+  // scalar arithmetic and the column block an immediate -- no vector instruction per load
+  GaBuffer w2;
+#endif
+  __device__ __forceinline__ FtW2Frags(const DgradWgrad0Params& p, const int wn0)
+      : ldb((uint32_t)p.g.ldb),
+#ifdef GA_FT_NO_BUFFER_ADDR
+        B(p.g.B)
+#else
+        w2(p.g.B, 4u * ((uint32_t)(BN - 1) * (uint32_t)p.g.ldb + (uint32_t)BN))
+#endif
+  {
+    const int lane = threadIdx.x & 63;
+    woff = (uint32_t)(4 * (lane >> 5)) * ldb + (uint32_t)(wn0 + (lane & 31));
+  }
+  __device__ __forceinline__ void fetch_group(int s, int g) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#ifdef GA_FT_NO_BUFFER_ADDR
+        bn[j][g][q] = B[woff + (uint32_t)(32 * s + 8 * g + q) * ldb + (uint32_t)(32 * j)];
+#else
+        bn[j][g][q] = w2.load(4u * woff + (uint32_t)(128 * j),
+                              4u * (uint32_t)(32 * s + 8 * g + q) * ldb);
+#endif
+  }
+  __device__ __forceinline__ void fetch_step0() {
+#pragma unroll
+    for (int g = 0; g < BK / 8; ++g) fetch_group(0, g);
+  }
+};
+
+template <int NT>
+__device__ __forceinline__ void dgrad_load_x(const DgradWgrad0Params& p, const int ft_tile,
+                                             float4 (&xq)[2]);
+
+// The loads of the data-gradient body that fwd_dgrad_kernel has in flight when that body
+// begins: the observation quads (behind a load of their gathered row numbers, which they
+// wait for) and the first k-step's W2 fragments.
+template <int BN, int TN, int NT>
+struct FtDgradLoads {
+  const DgradWgrad0Params& p;
+  const int ft_tile;
+  FtW2Frags<BN, TN> w;
+  float4 xq[2];
+  __device__ __forceinline__ FtDgradLoads(const DgradWgrad0Params& p_, const int tile,
+                                          const int wn0)
+      : p(p_), ft_tile(tile), w(p_, wn0) {}
+  __device__ __forceinline__ void issue() {
+    dgrad_load_x<NT>(p, ft_tile, xq);
+    w.fetch_step0();
+  }
+};
+
 // What fwd_head_loss_body<FUSE> leaves behind for the data-gradient body
 struct FtFusedLds {
   float* stage;  // [64][BN + 4]: dZ of the tile's rows, rows >= M exact zeros
@@ -153,15 +224,25 @@ struct FtFusedLds {
 // ft_tile / ft_tiles: this workgroup's 64-row tile and the number of tiles of ITS
 // network's minibatch (a pair launch carries the tiles of two networks in one grid)
 // FUSE (with L1, training): the data-gradient body runs behind this one in the same
-// workgroup (fwd_dgrad_kernel).  The epilogue then always takes E6 before E5, and E5
-// also leaves every dZ quad in the stage, over the H quad it was computed from: the
-// stage is the data gradient's A operand.  `keep` receives the workgroup's LDS.
+// workgroup (fwd_dgrad_kernel).  The stage then ends up holding every dZ quad over the H
+// quad it was computed from: the stage is the data gradient's A operand.  E5 comes first
+// and keeps its quads in registers (the accumulators are dead), so that the tile's 64 KB
+// of dZ stores drain under E6, which still reads the staged H; behind a barrier the kept
+// quads go over the stage.  The data gradient's first loads (`dgl`: observation rows,
+// the first k-step's W2 fragments) are requested IN FRONT of the dZ stores: the memory
+// counter retires in order, and behind them the gathered rows' wait and the k-loop's first
+// MFMAs would wait for the stores as well.  (GA_FT_NO_EARLY_DZ: E6, a barrier, then E5
+// writing global memory and the stage; those loads behind that.)
+// `keep` receives the workgroup's LDS.
 template <int BN, int WAVES_M, int WAVES_N, bool L1, bool EVAL, int KSC = 0,
           bool SPLIT = false, bool FUSE = false>
 __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
                                                    const int ft_tile,
                                                    const int ft_tiles,
-                                                   FtFusedLds* keep = nullptr) {
+                                                   FtFusedLds* keep = nullptr,
+                                                   FtDgradLoads<BN, BN / WAVES_N / 32,
+                                                                64 * WAVES_M * WAVES_N>* dgl =
+                                                       nullptr) {
   static_assert(L1 || !EVAL, "the evaluation forward computes the first layer itself");
   static_assert(!FUSE || (L1 && !EVAL && !SPLIT),
                 "the fused data gradient: exact fp32 training step, first layer in the kernel");
@@ -532,6 +613,22 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
       // wave-uniform 64-bit bases + 32-bit lane offsets (one address register each)
       const uint32_t wb_off = (uint32_t)(wn0 + l31) * (uint32_t)p.g.ldb + 4u * half;
       float* h1_tile = p.l1_H + (int64_t)m0 * p.l1_ldh;
+#ifndef GA_FT_NO_BUFFER_ADDR
+      // the same as buffers (GaBuffer, common.h): W [BN][ldb] with K floats in its last
+      // row, and this tile's rows of H1 (K floats in the last one that exists).  A lane's
+      // byte offsets are computed here, once; the k-step enters as a scalar offset
+      const GaBuffer wbuf(p.g.B, 4u * ((uint32_t)(BN - 1) * (uint32_t)p.g.ldb + (uint32_t)K));
+      const GaBuffer h1buf(h1_tile, 4u * ((uint32_t)(min(FT_ROWS, M - m0) - 1) *
+                                              (uint32_t)p.l1_ldh + (uint32_t)K));
+      const uint32_t wb_off_b = 4u * wb_off;
+      uint32_t sp_off_b[SPQ];
+#pragma unroll
+      for (int q = 0; q < SPQ; ++q) {
+        const int e = tid + NT * q;
+        sp_off_b[q] = 4u * ((uint32_t)(e / (BK / 4)) * (uint32_t)p.l1_ldh +
+                            (uint32_t)(4 * (e % (BK / 4))));
+      }
+#endif
 #define FT_SB __builtin_amdgcn_sched_barrier(0)
       auto step = [&](int s, auto more_tag, auto full_tag) {
         constexpr bool MORE = decltype(more_tag)::value;
@@ -596,10 +693,15 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
               for (int q = 0; q < SPQ; ++q) {
                 const int e = tid + NT * q;
                 const int row = e / (BK / 4), c4 = e % (BK / 4);
+#ifdef GA_FT_NO_BUFFER_ADDR
                 if (FULL || m0 + row < M)
                   *reinterpret_cast<float4*>(
                       h1_tile + ((uint32_t)row * (uint32_t)p.l1_ldh +
                                  (uint32_t)(32 * s + 4 * c4))) = sp[q];
+#else
+                (void)c4;
+                if (FULL || m0 + row < M) h1buf.store4(sp[q], sp_off_b[q], 128u * (uint32_t)s);
+#endif
               }
             }
           } else if (t < NSUB + 1 + 4 * NSUB) {
@@ -651,9 +753,15 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
             if (slot % (4 * TN) == 4 * TN - 1) {
 #pragma unroll
               for (int jj = 0; jj < TN; ++jj)
+#ifdef GA_FT_NO_BUFFER_ADDR
                 bn[jj][g] = *reinterpret_cast<const float4*>(
                     p.g.B + (wb_off + (uint32_t)(32 * jj) * (uint32_t)p.g.ldb +
                              (uint32_t)(32 * (s + 1) + 8 * g)));
+#else
+                bn[jj][g] = wbuf.load4(wb_off_b + (uint32_t)(32 * g),
+                                       4u * ((uint32_t)(32 * jj) * (uint32_t)p.g.ldb +
+                                             (uint32_t)(32 * (s + 1))));
+#endif
             }
           }
 #endif
@@ -924,7 +1032,8 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
   // E5 / E6 take only the head rows that exist (j < A; JN = 1, 4 or 8 compiled): rows
   // of W_head and entries of dout beyond A are zero and add nothing -- the value
   // function's head has ONE row, 7 of 8 products were multiplications by zero
-  auto phase_dz = [&](auto jn_tag) {
+  constexpr int QN = FT_ROWS * (BN / 4) / NT;  // column quads per thread
+  auto phase_dz = [&](auto jn_tag, float4* zk) {
   // ---- E5: dZ = (dout W_head) (1 - H^2) -> global (the only [M x BN] store).  A
   //      thread's column quad is the same for all its rows: its W_head values are
   //      read once
@@ -935,7 +1044,7 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
   for (int j = 0; j < JN; ++j)
     w8[j] = *reinterpret_cast<const float4*>(aux + j * BN + 4 * (tid % (BN / 4)));
 #pragma unroll
-  for (int q = 0; q < FT_ROWS * (BN / 4) / NT; ++q) {
+  for (int q = 0; q < QN; ++q) {
     const int e = tid + NT * q;
     const int rr = e / (BN / 4), c4 = e % (BN / 4);
     const float4 h = *reinterpret_cast<const float4*>(stage + rr * LDC + 4 * c4);
@@ -951,6 +1060,20 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
     }
     z.x *= (1.f - h.x * h.x); z.y *= (1.f - h.y * h.y);
     z.z *= (1.f - h.z * h.z); z.w *= (1.f - h.w * h.w);
+#ifndef GA_FT_NO_BUFFER_ADDR
+    if constexpr (FUSE) {
+      // the tile's rows of dZ as a buffer (GaBuffer, common.h; BN floats in the last row
+      // that exists): a thread's rows lie NT / (BN / 4) apart, a scalar offset (the
+      // descriptor and the lane offset are the same for every q: computed once)
+      const GaBuffer dzbuf(p.dZ + (int64_t)m0 * p.lddz,
+                           4u * ((uint32_t)(min(FT_ROWS, M - m0) - 1) * (uint32_t)p.lddz +
+                                 (uint32_t)BN));
+      const uint32_t dz_off = 4u * ((uint32_t)(tid / (BN / 4)) * (uint32_t)p.lddz +
+                                    (uint32_t)(4 * (tid % (BN / 4))));
+      if (m0 + rr < M)
+        dzbuf.store4(z, dz_off, 4u * (uint32_t)((NT / (BN / 4)) * q) * (uint32_t)p.lddz);
+    } else
+#endif
     if (m0 + rr < M)
       *reinterpret_cast<float4*>(p.dZ + (int64_t)(m0 + rr) * p.lddz + 4 * c4) = z;
     if constexpr (FUSE) {
@@ -958,7 +1081,10 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
       // there, but 0 * w is not zero for every w -- the operand gets the zeros the
       // tile loader of the two-launch path gives it
       if (m0 + rr >= M) z = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(stage + rr * LDC + 4 * c4) = z;
+      if (zk)
+        zk[q] = z;
+      else
+        *reinterpret_cast<float4*>(stage + rr * LDC + 4 * c4) = z;
     }
   }
   };
@@ -994,17 +1120,33 @@ __device__ __forceinline__ void fwd_head_loss_body(const FwdLossParams& p,
   };
   auto two_phases = [&](auto jn_tag) {
     if constexpr (FUSE) {
+#ifdef GA_FT_NO_EARLY_DZ
       // E6 reads the staged H that E5 overwrites
       phase_head_grad(jn_tag);
       FT_STAMP(7);
       __syncthreads();
-      phase_dz(jn_tag);
+      phase_dz(jn_tag, nullptr);
+      dgl->issue();
+#else
+      // E5 with its quads kept, E6 on the H that is still staged, then the quads over it
+      float4 zk[QN];
+      dgl->issue();
+      phase_dz(jn_tag, zk);
+      FT_STAMP(7);
+      phase_head_grad(jn_tag);
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < QN; ++q) {
+        const int e = tid + NT * q;
+        *reinterpret_cast<float4*>(stage + (e / (BN / 4)) * LDC + 4 * (e % (BN / 4))) = zk[q];
+      }
+#endif
     } else if (ft_tile >= (ft_tiles + 1) / 2) {
       phase_head_grad(jn_tag);
       FT_STAMP(7);
-      phase_dz(jn_tag);
+      phase_dz(jn_tag, nullptr);
     } else {
-      phase_dz(jn_tag);
+      phase_dz(jn_tag, nullptr);
       FT_STAMP(7);
       phase_head_grad(jn_tag);
     }
@@ -1305,35 +1447,19 @@ __device__ __forceinline__ void dgrad_load_x(const DgradWgrad0Params& p, const i
 // tile's 64 rows of dZ2 [64][BN + 4], k-contiguous (fwd_head_loss_body<FUSE> left them
 // there; K = BN), so the loop loads no A, stores nothing to LDS and has no barrier.
 // A fragments: one 16-B read per row block and group of four MFMAs (BN + 4 has the
-// residue of BK + PAD mod 32: gemm_mainloop's conflict-free pattern).  B fragments
-// (W2 [K][ldb], n-contiguous): lane (l31, half) feeds B(k, n = wn0 + 32 j + l31),
-// k = 32 s + 8 g + 4 half + q -- four dword loads per group, straight from L2 (every
-// workgroup reads all of W2), one step ahead, refilled in place as soon as the group's
-// MFMAs are issued.  MFMAs per accumulator in gemm_mainloop's order (s, g, q): the
-// same bits as dgrad_wgrad0_body's loop.
+// residue of BK + PAD mod 32: gemm_mainloop's conflict-free pattern).  B fragments:
+// FtW2Frags, one step ahead (the caller has requested step 0's), refilled in place as
+// soon as the group's MFMAs are issued.  MFMAs per accumulator in gemm_mainloop's order
+// (s, g, q): the same bits as dgrad_wgrad0_body's loop.
 template <int BN, int TM, int TN>
-__device__ __forceinline__ void dgrad_kloop_staged(const DgradWgrad0Params& p,
-                                                   const float* stage,
-                                                   f32x16 (&acc)[TM][TN], const int wm0,
-                                                   const int wn0) {
+__device__ __forceinline__ void dgrad_kloop_staged(const float* stage, FtW2Frags<BN, TN>& w,
+                                                   f32x16 (&acc)[TM][TN], const int wm0) {
   constexpr int LDC = BN + 4;
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5, l31 = lane & 31;
-  const int nk = BN / BK;
-  // wave-uniform base + one 32-bit lane offset (rows k < K = BN, columns < BN <= ldb)
-  const uint32_t ldb = (uint32_t)p.g.ldb;
-  const uint32_t woff = (uint32_t)(4 * half) * ldb + (uint32_t)(wn0 + l31);
-  float bn[TN][BK / 8][4];
-  auto fetch_group = [&](int s, int g) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        bn[j][g][q] = p.g.B[woff + (uint32_t)(32 * s + 8 * g + q) * ldb + (uint32_t)(32 * j)];
-  };
-#pragma unroll
-  for (int g = 0; g < BK / 8; ++g) fetch_group(0, g);
   const float* arow = stage + (wm0 + l31) * LDC + 4 * half;
+  constexpr int nk = BN / BK;
+#pragma unroll
   for (int s = 0; s < nk; ++s) {
     const bool more = s + 1 < nk;
 #pragma unroll
@@ -1352,10 +1478,10 @@ __device__ __forceinline__ void dgrad_kloop_staged(const DgradWgrad0Params& p,
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][q], bn[j][g][q], acc[i][j],
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][q], w.bn[j][g][q], acc[i][j],
                                                              0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
-      if (more) fetch_group(s + 1, g);
+      if (more) w.fetch_group(s + 1, g);
     }
   }
 }
@@ -1556,6 +1682,7 @@ __device__ __forceinline__ void dgrad_wgrad0_tail(
     const int m = min(m0 + rr, M - 1);
     hq[q] = *reinterpret_cast<const float4*>(p.H + (int64_t)m * p.ldh + 4 * c4);
   }
+  FT_STAMP(6);
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1685,15 +1812,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
   constexpr int TM = WM / 32, TN = WN / 32;
   const int ft_tile = (int)blockIdx.x;
   FtFusedLds l;
-  fwd_head_loss_body<BN, WAVES_M, WAVES_N, true, false, KSC, false, true>(
-      pp.f, ft_tile, (int)gridDim.x, &l);
   const DgradWgrad0Params& p = pp.d;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm0 = (wave / WAVES_N) * WM;
   const int wn0 = (wave % WAVES_N) * WN;
+  FtDgradLoads<BN, TN, NT> dgl(p, ft_tile, wn0);
+  fwd_head_loss_body<BN, WAVES_M, WAVES_N, true, false, KSC, false, true>(
+      pp.f, ft_tile, (int)gridDim.x, &l, &dgl);
   FT_STAMP(0);
-  float4 xq[2];
-  dgrad_load_x<NT>(p, ft_tile, xq);
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -1701,8 +1827,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  __syncthreads();  // E5 has left dZ2 in the stage
-  dgrad_kloop_staged<BN>(p, l.stage, acc, wm0, wn0);
+  __syncthreads();  // dZ2 is in the stage
+  FT_STAMP(5);
+  dgrad_kloop_staged<BN>(l.stage, dgl.w, acc, wm0);
   FT_STAMP(1);
   // The tail overwrites the stage (every wave read all of it) and reads H1 from
   // memory, where other threads of this workgroup stored it during the forward k-loop.
@@ -1713,7 +1840,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N,
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  dgrad_wgrad0_tail<BN, WAVES_M, WAVES_N>(p, ft_tile, acc, xq, l.stage, l.aux);
+  dgrad_wgrad0_tail<BN, WAVES_M, WAVES_N>(p, ft_tile, acc, dgl.xq, l.stage, l.aux);
 }
 
 // ---------------------------------------------------------------------------

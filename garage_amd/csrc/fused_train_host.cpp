@@ -229,6 +229,14 @@ extern "C" int ga_fused_fwd_dgrad_supported(int width, int K, int in_w) {
   return ga_fused_fwd_dgrad_rule(width, K, in_w);
 }
 
+// The kernels that compute the first layer themselves address a tile's 64 rows and the
+// weight matrices' (up to 256) rows with 32-bit BYTE offsets (GaBuffer, common.h): 256
+// rows of fewer than 2^22 floats each stay below 4 GB.  Checked where such a kernel may
+// be launched: the forward + loss entry (H1 and the weights; dZ2 too, for the fused
+// launch's sake) and the fused entry (the data gradient's W2).  The separate
+// data-gradient entry keeps 64-bit addresses and takes what it always took.
+static bool ft_ld_ok(int64_t ld) { return ld >= 0 && ld < (1ll << 22); }
+
 // ---- 1. forward + loss ---------------------------------------------------------------------
 // validation + kernel parameters of one network's launch
 static int fwd_build(const ga_fused_fwd_net& n, int64_t M, int width, int K,
@@ -254,6 +262,8 @@ static int fwd_build(const ga_fused_fwd_net& n, int64_t M, int width, int K,
   GA_REQUIRE(ga_fused_width_ok(width) && M >= 1 && M < (1ll << 31) && K >= 1 &&
                  loss->A >= 1 && loss->A <= 8,
              "ga_fused_fwd_head_loss: unsupported shape");
+  GA_REQUIRE(ft_ld_ok(lda) && ft_ld_ok(n.ldw) && ft_ld_ok(n.lddz),
+             "ga_fused_fwd_head_loss: leading dimension of 2^22 floats or more");
   GA_REQUIRE(lda % 4 == 0 && n.ldw % 4 == 0 && n.head_ldw % 4 == 0 && n.lddz % 4 == 0 &&
                  ga_aligned16(A) && ga_aligned16(n.W) && ga_aligned16(n.bias) &&
                  ga_aligned16(n.head_W) && ga_aligned16(n.dZ),
@@ -469,6 +479,8 @@ extern "C" int ga_fused_fwd_dgrad(const ga_fused_fwd_net* fwd, const ga_fused_dg
                  dgrad->ldx == first->ldx && dgrad->idx == fwd->loss->idx &&
                  !dgrad->sum_w.src && !dgrad->sum_b.src,
              "ga_fused_fwd_dgrad: the two descriptors are not one step's");
+  GA_REQUIRE(ft_ld_ok(dgrad->ldw),
+             "ga_fused_fwd_dgrad: leading dimension of 2^22 floats or more");
   FwdDgradParams pp;
   double f0 = 0.0, f1 = 0.0;
   int rc = fwd_build(*fwd, M, width, K, &pp.f, &f0);
