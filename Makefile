@@ -140,6 +140,15 @@ asan-rescale-loop: $(OUT)/rollout_asan_test
 asan-mlp: $(OUT)/mlp_layers_asan_test
 	$(OUT)/mlp_layers_asan_test
 
+# Which weight-gradient products take the paired-column GEMM (layer_plans.h:
+# ga_gemm_paired_ok): a stand-alone program of the plan functions alone, one refused
+# product per condition of the rule.
+$(OUT)/gemm_paired_plan_check: tests/host/gemm_paired_plan_check.cpp $(CSRC)/layer_plans.h $(CSRC)/gemm_params.h
+	@mkdir -p $(OUT)
+	$(ASAN_CXX) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wno-unused-function $< -o $@
+paired-plan-check: $(OUT)/gemm_paired_plan_check
+	$(OUT)/gemm_paired_plan_check
+
 # The population's epoch loop (update_members.cpp): which ids form which member's step,
 # which members are active in which step, the Adam table, the launch count of a pass, the
 # tables' exact sizes, nothing launched after a refusal.

@@ -379,6 +379,8 @@ SIGNATURES = {
     'ga_set_narrow_step': (c_int, [c_int]),
     'ga_set_fused_first_layer': (c_int, [c_int]),
     'ga_set_pipelined_kloop': (c_int, [c_int]),
+    'ga_set_wgrad_paired_columns': (c_int, [c_int]),
+    'ga_wgrad_paired_launches': (c_i64, []),
     'ga_set_slab_sum_in_dgrad': (c_int, [c_int]),
     'ga_set_fused_fwd_dgrad': (c_int, [c_int]),
     'ga_set_split_bf16': (c_int, [c_int]),

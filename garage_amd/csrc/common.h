@@ -178,6 +178,11 @@ struct GaBuffer {
                      __float_as_uint(x.w)};
     __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, (int)soff, 0);
   }
+  __device__ __forceinline__ void store2(float x, float y, uint32_t voff, uint32_t soff) const {
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 v = {__float_as_uint(x), __float_as_uint(y)};
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)voff, (int)soff, 0);
+  }
 };
 
 __device__ __forceinline__ float ga_wave_sum(float v) {

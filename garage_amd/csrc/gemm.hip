@@ -589,11 +589,261 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_split_kernel(GemmParams p) {
   }
 }
 
+// ---- weight-gradient GEMM, interior row-major shapes (layer_plans.h: ga_gemm_paired_ok).
+// gemm_f32_kernel<128, 128, 2, 4, false, false> again -- the same tiles, slabs, k order
+// per output element and column sums, so the same bits -- with the vector instructions
+// this case does not need taken out of the wave's instruction stream (beside an fp32 MFMA
+// every one of them is matrix time).  Three items, each with an A/B
+// macro that restores the parent's form (tools/build_variants.sh):
+//   * paired columns (GA_GEMM_NO_PAIRED_COLS): waves are 4 (m) x 2 (n) and own 32 x 64
+//     outputs; lane l31 of accumulator block j holds column wn0 + 2 l31 + j, so the two B
+//     values of a lane for one k are neighbours in the [k][BN + PAD] image and come with
+//     ONE ds_read_b64 (8-B aligned: LDB_S and wn0 are even; 32 lanes cover 64 consecutive
+//     dwords).  8 LDS reads per 8 MFMAs instead of 12.
+//   * direct stores (GA_GEMM_NO_DIRECT_STORE; needs the paired columns): a lane holds
+//     C[m][n] and C[m][n + 1] -- one 8-B store per accumulator register, a 256-B run per
+//     half wave, no LDS staging and none of its four barriers.
+//   * buffer addressing (GA_GEMM_NO_BUFFER_ADDR): the tile loads and the slab stores go
+//     through GaBuffer (common.h) -- one lane offset per operand computed in front of the
+//     loop, the k-step and the store's row as scalar offsets.  The descriptors' extents are
+//     exact; every clamp and mask of the ragged last k-step stays.
+// The last k-step is masked only where it is partial (the parent masks it always).
+#ifdef GA_GEMM_NO_PAIRED_COLS
+constexpr bool RR_PAIRED = false;
+#else
+constexpr bool RR_PAIRED = true;
+#endif
+#ifdef GA_GEMM_NO_DIRECT_STORE
+constexpr bool RR_DIRECT = false;
+#else
+constexpr bool RR_DIRECT = RR_PAIRED;
+#endif
+#ifdef GA_GEMM_NO_BUFFER_ADDR
+constexpr bool RR_BUF = false;
+#else
+constexpr bool RR_BUF = true;
+#endif
+
+// One [BK][128] tile of a row-major operand, two 16-B vectors per thread: rows
+// tid / 32 and tid / 32 + 16 of the k-step, columns 4 (tid % 32) ..
+struct RrLoader {
+  float4 regs[2];
+  GaBuffer buf;
+  uint32_t voff;        // RR_BUF: the lane's byte offset in the slab's rows of the tile
+  const float* ptr[2];  // !RR_BUF: the lane's two vectors of the slab's first k-step
+  int64_t ld;
+  int rows;             // of the slab
+
+  // base: the operand at (kbeg, first column of the tile)
+  __device__ __forceinline__ RrLoader(const float* base, int64_t ld_, int rows_)
+      : buf(base, rows_ > 0 ? 4u * ((uint32_t)(rows_ - 1) * (uint32_t)ld_ + 128u) : 0u),
+        ld(ld_), rows(rows_) {
+    const int tid = threadIdx.x;
+    voff = 4u * ((uint32_t)(tid >> 5) * (uint32_t)ld_ + 4u * (tid & 31));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) ptr[i] = base + (int64_t)((tid >> 5) + 16 * i) * ld_ + 4 * (tid & 31);
+  }
+  // krel: the k-step's first row within the slab
+  __device__ __forceinline__ void load(int krel) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (RR_BUF)
+        regs[i] = buf.load4(voff, 4u * (uint32_t)(krel + 16 * i) * (uint32_t)ld);
+      else
+        regs[i] = *reinterpret_cast<const float4*>(ptr[i] + (int64_t)krel * ld);
+    }
+  }
+  // a partial k-step: rows beyond the slab are clamped into it here and zeroed by store()
+  __device__ __forceinline__ void load_partial(int krel) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = min(krel + (tid >> 5) + 16 * i, rows - 1);  // (rows >= 1 here)
+      if (RR_BUF)
+        regs[i] = buf.load4(4u * ((uint32_t)row * (uint32_t)ld + 4u * (tid & 31)), 0u);
+      else
+        regs[i] = *reinterpret_cast<const float4*>(ptr[0] + (int64_t)(row - (tid >> 5)) * ld);
+    }
+  }
+  __device__ __forceinline__ void store(float* tile, int krel, bool masked) const {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = (tid >> 5) + 16 * i;
+      float4 v = regs[i];
+      if (masked && krel + k >= rows) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(tile + k * (128 + PAD) + 4 * (tid & 31)) = v;
+    }
+  }
+};
+
+__global__ __launch_bounds__(512) void gemm_rr_paired_kernel(GemmParams p) {
+  constexpr int BM = 128, BN = 128, NT_ALL = 512;
+  constexpr int LDA_S = BM + PAD, LDB_S = BN + PAD, A_FLOATS = BK * LDA_S;
+  constexpr int WAVES_N = RR_PAIRED ? 2 : 4;
+  constexpr int WM = RR_PAIRED ? 32 : 64, WN = RR_PAIRED ? 64 : 32;
+  // the operand tiles; the staged epilogue's 64 rows of BN + 4 are the same size (the
+  // parent's footprint: the two update chains' workgroups co-reside on a CU)
+  __shared__ __attribute__((aligned(16))) float lds[BK * (LDA_S + LDB_S)];
+  static_assert(BK * (LDA_S + LDB_S) >= 64 * (BN + 4), "the epilogue's stage");
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm0 = (wave / WAVES_N) * WM, wn0 = (wave % WAVES_N) * WN;
+  int bx, by, bz;  // (the parent's order, gemm_f32_body)
+  if (p.gz == 1) {
+    ga_xcd_group((int)blockIdx.x, p.gx, p.gy, &bx, &by);
+    bz = 0;
+  } else {
+    int mem;
+    ga_xcd_group((int)blockIdx.x, p.gz, p.gx * p.gy, &bz, &mem);
+    bx = mem % p.gx;
+    by = mem / p.gx;
+  }
+  const int m0 = bx * BM, n0 = by * BN;
+  const int kbeg = bz * p.k_per_split, kend = min(p.K, kbeg + p.k_per_split);
+  const int rows = max(kend - kbeg, 0);
+  const int nk = (rows + BK - 1) / BK;
+  const bool partial = (rows % BK) != 0;  // the last k-step is masked
+
+  // acc[t]: RR_PAIRED columns wn0 + 2 l31 + t, else rows wm0 + 32 t ..
+  f32x16 acc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  float csum = 0.f;
+  const bool do_colsum = p.colsum != nullptr && (p.colsum_of_b ? (bx == 0) : (by == 0));
+
+  float* As = lds;
+  float* Bs = lds + A_FLOATS;
+  RrLoader la(p.A + (int64_t)kbeg * p.lda + m0, p.lda, rows);
+  RrLoader lb(p.B + (int64_t)kbeg * p.ldb + n0, p.ldb, rows);
+  if (nk > 0) {
+    const bool t0 = partial && nk == 1;
+    if (t0) {
+      la.load_partial(0);
+      lb.load_partial(0);
+    } else {
+      la.load(0);
+      lb.load(0);
+    }
+    la.store(As, 0, t0);
+    lb.store(Bs, 0, t0);
+  }
+  __syncthreads();
+
+  // lane half h feeds k = 8 g + 4 h + q to MFMA q of group g (gemm_core.h: gemm_mainloop)
+  const float* fa = As + 4 * half * LDA_S + wm0 + l31;
+  const float* fb = Bs + 4 * half * LDB_S + wn0 + (RR_PAIRED ? 2 : 1) * l31;
+  for (int s = 0; s < nk; ++s) {
+    const bool more = s + 1 < nk;
+    const bool tail = partial && s + 2 == nk;  // the tile being fetched is the partial one
+    if (more) {
+      if (tail) {
+        la.load_partial((s + 1) * BK);
+        lb.load_partial((s + 1) * BK);
+      } else {
+        la.load((s + 1) * BK);
+        lb.load((s + 1) * BK);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < BK / 8; ++g) {
+      float a[2][4], b[2][4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[0][q] = fa[(8 * g + q) * LDA_S];
+        if (RR_PAIRED) {
+          const float2 v = *reinterpret_cast<const float2*>(fb + (8 * g + q) * LDB_S);
+          b[0][q] = v.x;
+          b[1][q] = v.y;
+        } else {
+          a[1][q] = fa[(8 * g + q) * LDA_S + 32];
+          b[0][q] = fb[(8 * g + q) * LDB_S];
+        }
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[RR_PAIRED ? 0 : t][q],
+                                                        b[RR_PAIRED ? t : 0][q], acc[t], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
+    if (do_colsum) {
+      const float* T = p.colsum_of_b ? Bs : As;
+      if (tid < 128) {
+#pragma unroll 8
+        for (int k = 0; k < BK; ++k) csum += T[k * LDA_S + tid];
+      }
+    }
+    __syncthreads();
+    if (more) {
+      la.store(As, (s + 1) * BK, tail);
+      lb.store(Bs, (s + 1) * BK, tail);
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue: the slab of this split.  D(row, col): col = lane & 31,
+  // row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  float* Ctile = p.C + (int64_t)bz * p.c_split_stride + (int64_t)m0 * p.c_rs + n0;
+  const GaBuffer cbuf(Ctile, 4u * ((uint32_t)(BM - 1) * (uint32_t)p.c_rs + BN));
+  if constexpr (RR_DIRECT) {
+    const uint32_t voff = 4u * ((uint32_t)(wm0 + 4 * half) * (uint32_t)p.c_rs + wn0 + 2 * l31);
+    float* dst = Ctile + (int64_t)(wm0 + 4 * half) * p.c_rs + wn0 + 2 * l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2);
+      if (RR_BUF)
+        cbuf.store2(acc[0][r], acc[1][r], voff, 4u * (uint32_t)row * (uint32_t)p.c_rs);
+      else
+        *reinterpret_cast<float2*>(dst + (int64_t)row * p.c_rs) = make_float2(acc[0][r], acc[1][r]);
+    }
+  } else {
+    // the parent's: through LDS, 64 rows at a time, 16-B stores of whole row segments
+    constexpr int LDC = BN + 4;
+    for (int hrow = 0; hrow < BM; hrow += 64) {
+      if (wm0 < hrow + 64 && wm0 + WM > hrow) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int rr = wm0 - hrow + (RR_PAIRED ? 0 : 32 * t) + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int cc = wn0 + (RR_PAIRED ? 2 * l31 + t : l31);
+            if (rr >= 0 && rr < 64) lds[rr * LDC + cc] = acc[t][r];
+          }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 64 * (BN / 4) / NT_ALL; ++q) {
+        const int rr = (tid >> 5) + 16 * q, c4 = tid & 31;
+        const float4 v = *reinterpret_cast<const float4*>(lds + rr * LDC + 4 * c4);
+        if (RR_BUF)
+          cbuf.store4(v, 4u * ((uint32_t)(tid >> 5) * (uint32_t)p.c_rs + 4u * c4),
+                      4u * (uint32_t)(hrow + 16 * q) * (uint32_t)p.c_rs);
+        else
+          *reinterpret_cast<float4*>(Ctile + (int64_t)(hrow + rr) * p.c_rs + 4 * c4) = v;
+      }
+      __syncthreads();
+    }
+  }
+  if (do_colsum && tid < 128)
+    p.colsum[(int64_t)bz * p.colsum_split_stride + (p.colsum_of_b ? n0 : m0) + tid] = csum;
+}
+
 // ---------------------------------------------------------------------------
 // The launch seam (layer_plans.h): which tile, which grid and which k range is the
 // plan's word, and `p` arrives with them filled in; here the plan's enum becomes an
 // instantiation.
 // ---------------------------------------------------------------------------
+// launches of gemm_rr_paired_kernel since the library was loaded (kind 2 times and counts
+// the weight-gradient GEMM whichever kernel it takes; tests ask which one it was)
+int64_t g_paired_launches = 0;
+
 template <bool A_KC, bool B_KC>
 int launch_gemm(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
   const dim3 grid((unsigned)(p.gx * p.gy * p.gz)), block((unsigned)plan.threads);
@@ -619,6 +869,11 @@ int launch_gemm(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
       hipExtLaunchKernelGGL(gemm_nt_split_kernel, grid, block, 0, stream, e0, e1, 0, p);
       break;
     case GT_128x128:
+      if (plan.paired_cols) {  // (the plan has checked the orientation and the layout)
+        ++g_paired_launches;
+        hipExtLaunchKernelGGL(gemm_rr_paired_kernel, grid, block, 0, stream, e0, e1, 0, p);
+        break;
+      }
 #ifdef GA_GEMM_BIG_TILE  // A/B builds: 4-wave workgroups with 128-row wave tiles
       // 1: 256 x 256 tiles, waves of 128 x 128 (one per SIMD); 2: 256 x 128, waves of 128 x 64
       if (p.gz == 1 && p.M >= 4096 && p.N % 256 == 0) {
@@ -654,6 +909,8 @@ int launch_gemm(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+extern "C" int64_t ga_wgrad_paired_launches(void) { return g_paired_launches; }
 
 int ga_gemm_launch(const GemmPlan& plan, const GemmParams& p, hipStream_t stream) {
   if (plan.a_kc && plan.b_kc) return launch_gemm<true, true>(plan, p, stream);

@@ -19,6 +19,7 @@ struct GemmSwitches {
   bool small_m;      // ga_set_small_m_gemm
   bool split_gemm;   // ga_split_bf16_gemm(): split-operand forward / data-gradient GEMM
   bool split_wgrad;  // ga_split_bf16_enabled(): split-operand weight-gradient GEMM
+  bool wgrad_paired; // ga_set_wgrad_paired_columns: the paired-column weight-gradient GEMM
 };
 
 // One value per arm of the chain in ga_gemm_plan, in its precedence.
@@ -52,7 +53,28 @@ struct GemmPlan {
   int planes_bwd;      // in the data gradient's orientation (B(k, n) = W[k][n]) or the
   int64_t bplane_stride;  // forward's (B(k, n) = W[n][k]), with this GemmParams geometry
   int bplane_nblk;
+  bool paired_cols;    // GT_128x128: gemm_rr_paired_kernel (same tiles, grid, k ranges and
+                       // bits as gemm_f32_kernel<128, 128, 2, 4, false, false>)
 };
+
+// The product is one gemm_rr_paired_kernel (gemm.hip) takes: both operands row-major with k
+// as the row index, no gather, every tile interior, the plain epilogue into a row-major C
+// whose lane pairs (n, n + 1) are 8-B aligned, and every byte offset of a slab's operand
+// rows and of a C tile's rows in 32 bits (the kernel addresses them through buffer
+// descriptors, as the fused step does: fused_train_host.cpp, ft_ld_ok).  A product that
+// is refused here takes gemm_f32_kernel and raises no error.
+inline bool ga_gemm_paired_ok(const GemmParams& p, int a_kc, int b_kc) {
+  const auto ld_ok = [](int64_t ld, int64_t rows) {
+    return ld >= 128 && ld < (1ll << 22) && rows * ld * 4 < (1ll << 31);
+  };
+  return !a_kc && !b_kc && !p.a_idx && !p.b_idx && p.epi == EPI_PLAIN && !p.accum && !p.H &&
+         !p.bias && !p.head_W && p.M >= 128 && p.N >= 128 && p.M % 128 == 0 &&
+         p.N % 128 == 0 && p.K >= 1 && p.k_per_split >= BK && p.k_per_split % BK == 0 &&
+         p.c_cs == 1 && p.c_rs % 2 == 0 && p.c_split_stride % 2 == 0 &&
+         (reinterpret_cast<uintptr_t>(p.C) & 7u) == 0 && p.lda % 4 == 0 && p.ldb % 4 == 0 &&
+         ga_aligned16(p.A) && ga_aligned16(p.B) && ld_ok(p.lda, p.k_per_split) &&
+         ld_ok(p.ldb, p.k_per_split) && ld_ok(p.c_rs, 128);
+}
 
 // C(m, n) = epi(sum_k A(m, k) B(k, n)) over `splits` slabs of k.
 inline GemmPlan ga_gemm_plan(const GemmParams& p, int a_kc, int b_kc, int splits,
@@ -108,6 +130,7 @@ inline GemmPlan ga_gemm_plan(const GemmParams& p, int a_kc, int b_kc, int splits
     // 8 waves (64x32 each): two workgroups per CU put 4 waves on every SIMD, so
     // the matrix pipe has work while other waves sit at the barrier / vmcnt
     g.tile = GT_128x128;
+    g.paired_cols = sw.wgrad_paired && ga_gemm_paired_ok(p, a_kc, b_kc);
   }
   const GemmTileShape t = ga_gemm_tile_shape(g.tile);
   // (the two arms that take the whole of K ask for splits == 1)

@@ -85,6 +85,22 @@ extern "C" int ga_set_small_m_gemm(int on) {
   g_small_m = on != 0;
   return 0;
 }
+// the paired-column instantiation of the 128 x 128 weight-gradient GEMM (layer_plans.h:
+// ga_gemm_paired_ok; gemm.hip: gemm_rr_paired_kernel).  0 (or GARAGE_AMD_WGRAD_PAIRED=0
+// in the environment when the library is first used): gemm_f32_kernel for every shape.
+// Bit-identical results either way.
+static int g_wgrad_paired = -1;
+static bool wgrad_paired_on() {
+  if (g_wgrad_paired < 0) {
+    const char* e = getenv("GARAGE_AMD_WGRAD_PAIRED");
+    g_wgrad_paired = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_wgrad_paired != 0;
+}
+extern "C" int ga_set_wgrad_paired_columns(int on) {
+  g_wgrad_paired = on != 0;
+  return 0;
+}
 
 extern "C" int64_t ga_mlp_backward_splits(const ga_mlp_desc* d, int64_t M) {
   // Rows of the batch each weight-gradient workgroup reduces before writing a
@@ -343,7 +359,7 @@ static GemmParams tangent_input_product(const Layer& w, int64_t M, float* C, int
 static int launch_product(GemmParams p, int a_kc, int b_kc, int splits, hipStream_t stream) {
   GA_REQUIRE(a_kc || !b_kc, "ga_gemm_launch: orientation not instantiated");
   const GemmSwitches sw = {g_small_m != 0, ga_split_bf16_gemm() != 0,
-                           ga_split_bf16_enabled() != 0};
+                           ga_split_bf16_enabled() != 0, wgrad_paired_on()};
   const GemmPlan plan = ga_gemm_plan(p, a_kc, b_kc, splits, sw);
   ga_gemm_apply(plan, &p);
   if (plan.planes) {

@@ -1250,6 +1250,16 @@ GA_API int ga_set_fused_first_layer(int on);
  * first layers of 17 .. 20 inputs at 256 units): 1 default, 0 the plain loop (also
  * GARAGE_AMD_PIPELINED_KLOOP=0).  Bit-identical results either way. */
 GA_API int ga_set_pipelined_kloop(int on);
+/* The weight-gradient GEMM of layers whose two sides are multiples of 128 (row-major
+ * operands, no gather, slabs with an even leading dimension) runs in an instantiation
+ * whose waves own 32 x 64 outputs with lane pairs of columns: one 8-B LDS read per pair
+ * of B values, 8-B stores straight from the accumulators, buffer addressing.  1 default,
+ * 0 the one kernel for every shape (also GARAGE_AMD_WGRAD_PAIRED=0).  Same tiles, slabs
+ * and summation order: bit-identical results either way. */
+GA_API int ga_set_wgrad_paired_columns(int on);
+/* Launches of that instantiation since the library was loaded (ga_launch_count(2) counts
+ * the weight-gradient GEMM whichever kernel takes it). */
+GA_API int64_t ga_wgrad_paired_launches(void);
 /* The split-K weight-gradient slabs of the middle layer (two hidden layers, more than
  * one split) are summed inside the data-gradient launch that follows the
  * weight-gradient GEMM, in the optimizer launch's own order, and the optimizer launch

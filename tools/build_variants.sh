@@ -30,4 +30,23 @@ build_ft() {  # name, flags...
 build_ft ft_none -DGA_FT_NO_BUFFER_ADDR -DGA_FT_NO_EARLY_DZ &
 build_ft ft_addr -DGA_FT_NO_EARLY_DZ &
 build_ft ft_early_dz -DGA_FT_NO_BUFFER_ADDR &
+# gemm.hip with the Makefile's flags: the three items of gemm_rr_paired_kernel (the
+# paired-column weight-gradient GEMM, r07) switched back one at a time and all together
+# (GA_GEMM_NO_PAIRED_COLS: 64 x 32 wave tiles and ds_read_b32 fragments, which also puts
+# the slab back through LDS; GA_GEMM_NO_DIRECT_STORE: the staged epilogue;
+# GA_GEMM_NO_BUFFER_ADDR: 64-bit vector addresses).  The parent's kernel itself is
+# GARAGE_AMD_WGRAD_PAIRED=0 with any of these libraries.
+build_rr() {  # name, flags...
+  name=$1; shift
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -fno-slp-vectorize -fvisibility=hidden -fvisibility-inlines-hidden "$@" -c garage_amd/csrc/gemm.hip -o $OUT/gemm_$name.o
+  objs=$(ls garage_amd/_C/*.o | grep -v '/gemm.o' | grep -v fused_entries_shim)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs $OUT/gemm_$name.o -ldl -o $OUT/lib_$name.so
+  echo built $name
+}
+build_rr rr_none -DGA_GEMM_NO_PAIRED_COLS -DGA_GEMM_NO_DIRECT_STORE -DGA_GEMM_NO_BUFFER_ADDR &
+build_rr rr_no_paired -DGA_GEMM_NO_PAIRED_COLS &
+build_rr rr_no_direct -DGA_GEMM_NO_DIRECT_STORE &
+build_rr rr_no_buffer -DGA_GEMM_NO_BUFFER_ADDR &
+build_rr rr_paired_only -DGA_GEMM_NO_DIRECT_STORE -DGA_GEMM_NO_BUFFER_ADDR &
+build_rr rr_buffer_only -DGA_GEMM_NO_PAIRED_COLS -DGA_GEMM_NO_DIRECT_STORE &
 wait
