@@ -280,6 +280,7 @@ def test_outputs_only_forward_matches_the_per_layer_forward(shape):
     and the activation workspace of an earlier pass is left alone."""
     from garage_amd import _lib
     from garage_amd.engine import FlatMLP
+    from _mlp_option_cases import TOL_FORWARD
     in_dim, hidden, out_dim, M = shape
     lib = _lib.load()
     dev = torch.device('cuda:0')
@@ -299,8 +300,14 @@ def test_outputs_only_forward_matches_the_per_layer_forward(shape):
         assert torch.equal(net._acts, torch.full_like(net._acts, 7.0))
         net._acts.copy_(acts)
         assert torch.isfinite(got[:, :out_dim]).all()
-        assert torch.allclose(got[:, :out_dim], ref[:, :out_dim], atol=2e-5,
-                              rtol=1e-5)
+        # two kernels that are each within TOL_FORWARD of fp64
+        # (test_whole_forward_fp64_gpu.py, test_mlp_options_fp64_gpu.py) are within
+        # twice that of each other
+        atol = 2 * TOL_FORWARD * max(1.0, float(ref[:, :out_dim].abs().max()))
+        err = float((got[:, :out_dim] - ref[:, :out_dim]).abs().max())
+        print('outputs-only against per-layer %s rows %d gather %s: err %.3e  atol %.3e' % (
+            shape[:3], M, row_idx is not None, err, atol))
+        assert torch.allclose(got[:, :out_dim], ref[:, :out_dim], atol=atol, rtol=0)
     # networks outside the kernel's shapes keep the per-layer path
     other = FlatMLP(40, 2, (128, 128), dev)
     assert lib.ga_mlp_forward_eval_supported(C.byref(other._desc)) == 0
