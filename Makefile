@@ -6,8 +6,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
-HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack linear_baseline
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host
+HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack linear_baseline members_diag
+CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host members_diag_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -84,7 +84,7 @@ clean:
 # or launch-seam function (fused_params.h, rollout_params.h, loss_params.h, layer_plans.h,
 # linear_baseline_params.h)
 # and HIP call the product source makes, and the checks -- linked with that product source.
-# One line per program: binary, harness source, product source.
+# One line per program: binary, harness source, product source (several joined by +).
 ASAN_PROGRAMS := \
   host_asan_test:update_loop_harness:update \
   rollout_asan_test:rollout_loop_harness:rollout_loop \
@@ -95,7 +95,8 @@ ASAN_PROGRAMS := \
   rollout_host_asan_test:rollout_host_harness:rollout_host \
   losses_host_asan_test:losses_host_harness:losses_host \
   linear_baseline_asan_test:linear_baseline_harness:linear_baseline_host \
-  linear_baseline_members_asan_test:linear_baseline_members_harness:linear_baseline_members_host
+  linear_baseline_members_asan_test:linear_baseline_members_harness:linear_baseline_members_host \
+  members_diag_asan_test:members_diag_harness:members_diag_host+mlp_layers
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -106,9 +107,9 @@ $(OUT)/asan/%.o: %.cpp
 	  -MMD -MP -c $< -o $@
 
 define asan_program
-$(OUT)/$(1): $(OUT)/asan/tests/host/$(2).o $(OUT)/asan/$(CSRC)/$(3).o
+$(OUT)/$(1): $(OUT)/asan/tests/host/$(2).o $(patsubst %,$(OUT)/asan/$(CSRC)/%.o,$(subst +, ,$(3)))
 	$$(ASAN_CXX) $$^ -o $$@
--include $(OUT)/asan/tests/host/$(2).d $(OUT)/asan/$(CSRC)/$(3).d
+-include $(OUT)/asan/tests/host/$(2).d $(patsubst %,$(OUT)/asan/$(CSRC)/%.d,$(subst +, ,$(3)))
 endef
 $(foreach p,$(ASAN_PROGRAMS),$(eval $(call asan_program,$(word 1,$(subst :, ,$(p))),$(word 2,$(subst :, ,$(p))),$(word 3,$(subst :, ,$(p))))))
 
@@ -194,10 +195,19 @@ asan-linear-baseline: $(OUT)/linear_baseline_asan_test
 asan-linear-baseline-members: $(OUT)/linear_baseline_members_asan_test
 	$(OUT)/linear_baseline_members_asan_test
 
+# The population's joint diagnostics (members_diag_host.cpp) TOGETHER with the per-layer
+# dispatch it asks for the members' forward plans (mlp_layers.cpp), against a fake kernel
+# side of its own: every table entry against the struct the lone entry point launches for
+# the same arguments, the kernel kinds and the launch count of members of different row
+# counts, the members' stretches of the partials at the exact size, one table copy a call,
+# every refusal before any copy or launch.
+asan-members-diag: $(OUT)/members_diag_asan_test
+	$(OUT)/members_diag_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
   asan-members asan-member-pack asan-fused-host asan-rollout-host asan-losses-host \
-  asan-linear-baseline asan-linear-baseline-members asan-all
+  asan-linear-baseline asan-linear-baseline-members asan-members-diag asan-all

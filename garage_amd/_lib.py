@@ -200,6 +200,47 @@ class UpdateMembersArgs(C.Structure):
                 ('partials_floats', c_i64), ('workspace', ptr)]
 
 
+class MemberForward(C.Structure):
+    """``ga_member_forward``."""
+    _fields_ = [('params', ptr), ('X', ptr), ('ldx', c_i64), ('rows', c_i64),
+                ('acts', ptr), ('out', ptr), ('ldo', c_i64)]
+
+
+class MembersLossArgs(C.Structure):
+    """``ga_members_loss_args``."""
+    _fields_ = [('kind', c_i32), ('A', c_i32), ('algo', c_i32),
+                ('ent_flags', c_i32), ('has_min', c_i32),
+                ('min_log_std', c_f32), ('has_max', c_i32),
+                ('max_log_std', c_f32), ('double_softmax', c_i32)]
+
+
+class MemberLoss(C.Structure):
+    """``ga_member_loss``."""
+    _fields_ = [('head', ptr), ('ld', c_i64), ('actions', ptr), ('lda', c_i64),
+                ('old_ll', ptr), ('adv', ptr), ('log_std', ptr),
+                ('rows', c_i64), ('clip', c_f32), ('ent_coeff', c_f32),
+                ('loss_out', ptr), ('ent_sum_out', ptr)]
+
+
+class MemberNll(C.Structure):
+    """``ga_member_nll``."""
+    _fields_ = [('v', ptr), ('ldv', c_i64), ('returns', ptr), ('log_std', ptr),
+                ('rows', c_i64), ('loss_out', ptr)]
+
+
+class MemberKl(C.Structure):
+    """``ga_member_kl``."""
+    _fields_ = [('head_old', ptr), ('head_new', ptr), ('ld', c_i64),
+                ('rows', c_i64), ('log_std_old', c_f32),
+                ('log_std_new', c_f32), ('kl_sum_out', ptr)]
+
+
+class MemberEpisodes(C.Structure):
+    """``ga_member_episodes``."""
+    _fields_ = [('rewards', ptr), ('ep_off', ptr), ('n_eps', c_i64),
+                ('returns', ptr), ('step_types', ptr), ('out', ptr)]
+
+
 class LinearGramMember(C.Structure):
     """``ga_linear_gram_member``."""
     _fields_ = [('obs', ptr), ('ldo', c_i64), ('ep_off', ptr),
@@ -390,6 +431,22 @@ SIGNATURES = {
     'ga_update_members_partials_floats': (c_i64, [C.POINTER(MlpDesc), c_i64,
                                                   c_i64]),
     'ga_update_epoch_members': (c_int, [C.POINTER(UpdateMembersArgs), ptr]),
+    # the diagnostics of a population in joint launches
+    'ga_mlp_forward_members_f32': (c_int, [C.POINTER(MlpDesc),
+                                           C.POINTER(MemberForward), c_i64,
+                                           ptr]),
+    'ga_mlp_forward_members_supported': (c_int, [C.POINTER(MlpDesc)]),
+    'ga_members_diag_partials_doubles': (c_i64, [C.POINTER(c_i64), c_i64]),
+    'ga_ppo_loss_members_f32': (c_int, [C.POINTER(MembersLossArgs),
+                                        C.POINTER(MemberLoss), c_i64, ptr,
+                                        c_i64, ptr]),
+    'ga_gaussian_nll_members_f32': (c_int, [C.POINTER(MemberNll), c_i64, ptr,
+                                            c_i64, ptr]),
+    'ga_kl_members_f32': (c_int, [c_int, c_int, c_int, C.POINTER(MemberKl),
+                                  c_i64, ptr, c_i64, ptr]),
+    'ga_episode_stats_members_f32': (c_int, [C.POINTER(MemberEpisodes), c_i64,
+                                             c_int, ptr]),
+    'ga_members_diag_release': (None, []),
     # LinearFeatureBaseline (np/baselines/linear_feature_baseline.py:43-93)
     'ga_linear_features_supported': (c_int, [c_int]),
     'ga_linear_gram_workspace_doubles': (c_i64, [c_int, c_i64]),

@@ -31,6 +31,18 @@ def _is_linear(value_function):
     return getattr(value_function, 'kind', None) == 'linear'
 
 
+def _barrier_fault_error(faulted):
+    """What ``_after_train`` raises when a reduction workspace's fault word is set."""
+    return RuntimeError(
+        'ga_small_step: a grid barrier timed out (reduction workspace '
+        'tag(s) {}: 0 = the main stream\'s network, 1 = the side '
+        'stream\'s); the optimizer steps from that point on were '
+        'skipped (parameters and Adam moments are those of the last '
+        'complete step, the step counts those of the start of this '
+        'iteration). Disable the one-launch step with '
+        'ga_set_small_step(0).'.format(faulted))
+
+
 class _OldPolicy:
     """Parameter snapshot standing in for ``copy.deepcopy(policy)`` (vpg.py:107)."""
 
@@ -155,8 +167,12 @@ class VPG:
         ``Independent(Normal).entropy() = A * (0.5 + 0.5 log 2pi + log_std)``,
         optionally through softplus (``vpg.py:408-432``).
         """
+        return self._entropy_of(self.policy.clamped_log_std())
+
+    def _entropy_of(self, log_std):
+        """... for a host value of the (clamped) log std."""
         A = self.policy.net.out_dim
-        s = np.float32(self.policy.clamped_log_std())
+        s = np.float32(log_std)
         ent = np.float32(A) * (np.float32(0.5) + np.float32(HALF_LOG_2PI) + s)
         if self._use_softplus_entropy:
             ent = np.float32(ent if ent > 20 else math.log1p(math.exp(ent)))
@@ -471,17 +487,23 @@ class VPG:
             # skipped: put them back to the iteration's start, so that a caller
             # who catches this and carries on (ga_set_small_step(0)) does not
             # train with bias corrections of steps that never happened
-            pol.net.adam_steps = steps_before[0]
-            if not self._linear_vf:
-                self._value_function.net.adam_steps = steps_before[1]
-            raise RuntimeError(
-                'ga_small_step: a grid barrier timed out (reduction workspace '
-                'tag(s) {}: 0 = the main stream\'s network, 1 = the side '
-                'stream\'s); the optimizer steps from that point on were '
-                'skipped (parameters and Adam moments are those of the last '
-                'complete step, the step counts those of the start of this '
-                'iteration). Disable the one-launch step with '
-                'ga_set_small_step(0).'.format(faulted))
+            self._restore_adam_steps(steps_before)
+            raise _barrier_fault_error(faulted)
+        self._record_diagnostics(c, pl_b, pl_a, vl_b, vl_a, kl_b, kl_a, entropy)
+
+        self._old_policy.sync(self.policy)  # vpg.py:201
+        undiscounted = self._log_performance(itr, batch, returns)
+        return np.mean(undiscounted)
+
+    def _restore_adam_steps(self, steps_before):
+        self.policy.net.adam_steps = steps_before[0]
+        if not self._linear_vf:
+            self._value_function.net.adam_steps = steps_before[1]
+
+    def _record_diagnostics(self, c, pl_b, pl_a, vl_b, vl_a, kl_b, kl_a, entropy):
+        """The nine logged scalars of an iteration from their host values
+        (``vpg.py:186-199``), and ``last_tabular`` / ``last_tensors``."""
+        adv, returns, values, v0 = c.adv, c.returns, c.values, c.v0
         tab = logger.tabular
         with tab.prefix(self.policy.name):
             tab.record('/LossBefore', pl_b)
@@ -503,10 +525,6 @@ class VPG:
         }
         self.last_tensors = {'advantages': adv, 'returns': returns,
                              'values': values.view(-1), 'v0': v0}
-
-        self._old_policy.sync(self.policy)  # vpg.py:201
-        undiscounted = self._log_performance(itr, batch, returns)
-        return np.mean(undiscounted)
 
     def _clamped(self, params):
         """Log std of the policy for the parameters in ``params``."""
@@ -948,6 +966,12 @@ class VPG:
         host = torch.cat([sums, first,
                           (last_st == int(StepType.TERMINAL)).to(
                               torch.float64)]).cpu().numpy()
+        return self._record_performance(itr, batch, host)
+
+    def _record_performance(self, itr, batch, host):
+        """The ``Evaluation/`` records from the host copy of ``[sums, first
+        returns, terminal flags]`` of the batch's episodes."""
+        N = len(batch.lengths)
         undiscounted, discounted, term = host[:N], host[N:2 * N], host[2 * N:]
         tab = logger.tabular
         with tab.prefix('Evaluation/'):
@@ -1545,13 +1569,22 @@ class PopulationPPO:
     ``(M, n_flat)`` tensors per network and every member's ``net`` points at its
     row, so the tensor that trains is the tensor that rolls out
     (:attr:`member_params`).
+
+    ``joint_diagnostics=True`` (off by default) also runs every member's
+    diagnostics after the update -- ``VPG._after_train``'s forwards, losses, KLs
+    and entropies and ``log_performance``'s episode sums -- in joint launches
+    (``ga_*_members_f32``: a fixed number of launches whatever the member count)
+    and brings all members' scalars to the host in one copy, instead of about
+    fifteen launches and six host waits per member.  Every member is left bit
+    for bit as the default path leaves it.
     """
 
     _BUFFERS = ('params', 'grads', 'exp_avg', 'exp_avg_sq')
 
-    def __init__(self, members, sampler=None):
+    def __init__(self, members, sampler=None, joint_diagnostics=False):
         self.members = list(members)
         self._sampler = sampler
+        self._joint_diagnostics = bool(joint_diagnostics)
         self._check_members()
         if sampler is not None and getattr(
                 sampler, 'n_members', len(self.members)) != len(self.members):
@@ -1646,6 +1679,8 @@ class PopulationPPO:
                         'hidden layers of 32 or 64 units, <= 32 inputs, <= 8 '
                         'linear outputs, no layer normalization)'.format(
                             who, name, tuple(mod.net.dims)))
+        if self._joint_diagnostics:
+            self._check_joint_diagnostics(ValueError)
         first = self._shared_facts(self.members[0])
         for m, algo in enumerate(self.members[1:], 1):
             for (name, a), (_, b) in zip(first, self._shared_facts(algo)):
@@ -1680,6 +1715,26 @@ class PopulationPPO:
                                               len(self.members)))
             self._baselines = population
 
+    def _check_joint_diagnostics(self, error):
+        """The joint diagnostics run the per-layer forward kernels' twins: a
+        developer switch that sends the members' networks to another kernel
+        (``ga_set_fused_forward(1)``) is refused here -- at construction, and
+        again before an iteration begins, never between the update and the
+        diagnostics."""
+        from garage_amd import _lib
+        import ctypes as C
+        lib = _lib.load()
+        algo = self.members[0]
+        mods = [('policy', algo.policy)]
+        if not _is_linear(algo._value_function):
+            mods.append(('value function', algo._value_function))
+        for name, mod in mods:
+            if not lib.ga_mlp_forward_members_supported(C.byref(mod.net._desc)):
+                raise error(
+                    'joint_diagnostics: the {} network cannot take the joint '
+                    'forward as the library is set now: {}'.format(
+                        name, lib.ga_last_error().decode('utf-8', 'replace')))
+
     def _networks(self):
         """Which of the members' networks train in the joint passes."""
         return ('policy', ) if self._baselines is not None else ('policy', 'vf')
@@ -1705,6 +1760,13 @@ class PopulationPPO:
                     setattr(mod.net, name, t[m])
                 rows[name] = t
             self._rows[which] = rows
+        if self._joint_diagnostics:
+            # the old policies' snapshots as rows too: one copy syncs them all
+            t = torch.empty_like(self._rows['policy']['params'])
+            for m, algo in enumerate(self.members):
+                t[m].copy_(algo._old_policy.params)
+                algo._old_policy.params = t[m]
+            self._old_rows = t
 
     @property
     def member_params(self):
@@ -1840,6 +1902,8 @@ class PopulationPPO:
         if len(batches) != len(self.members):
             raise ValueError('train_once needs one batch per member ({}), got '
                              '{}'.format(len(self.members), len(batches)))
+        if self._joint_diagnostics:
+            self._check_joint_diagnostics(RuntimeError)
         ctxs = self._before_trains(batches)
         self._train(ctxs)
         return self._after_trains(itr, ctxs)
@@ -1862,10 +1926,220 @@ class PopulationPPO:
         after = [None] * len(self.members)
         if self._baselines is not None:
             after = self._baselines.predict_batches([c.batch for c in ctxs])
+        if self._joint_diagnostics:
+            return self._after_trains_joint(itr, ctxs, after)
         returns = []
         for m, (algo, c) in enumerate(zip(self.members, ctxs)):
             with logger.tabular.prefix('member{}/'.format(m)):
                 returns.append(algo._after_train(itr, c, after[m]))
+        return returns
+
+    def _after_trains_joint(self, itr, ctxs, after):
+        """``_after_trains`` in joint launches: the device part of every
+        member's ``VPG._after_train`` and ``_log_performance`` through the
+        ``ga_*_members_f32`` entry points (each member gets the bits of its lone
+        launches), ONE copy of all members' scalars to the host, then per member
+        the host arithmetic and the records of the default path, in its order.
+
+        One more, earlier copy for Gaussian heads: the members' log-std
+        parameters, because the lone KL launch takes the log stds as host values
+        (``policy.log_std_of``: numpy's fp32 ``exp`` / ``log`` under softplus, which
+        no device function is pinned to bit for bit).  Linear baselines: the
+        members' ``_linear_vf_loss`` stays torch's fp64 mean, member by member
+        (no host wait; a joint reduction of another shape would round otherwise).
+        """
+        from garage_amd import _lib
+        import ctypes as C
+        algos, M = self.members, len(self.members)
+        first = algos[0]
+        pol0 = first.policy
+        net0 = pol0.net
+        dev = pol0.device
+        gaussian = pol0.kind == 'gaussian'
+        linear = self._baselines is not None
+        A, ld_out = net0.out_dim, net0.ld_out
+        S = [c.S for c in ctxs]
+        N = [len(c.batch.lengths) for c in ctxs]
+        stream = stream_ptr()
+        f32, f64 = torch.float32, torch.float64
+
+        # the host values of the new log stds, as VPG._mean_kl / _entropy_value
+        # take them (policy.clamped_log_std per member, in one copy)
+        s_new = [0.0] * M
+        if gaussian:
+            raw = self._rows['policy']['params'][:, 0].cpu().numpy()
+            s_new = [a.policy.log_std_of(float(raw[m]))[0]
+                     for m, a in enumerate(algos)]
+
+        # ---- every member's scalars: SLOTS doubles each (fp32 results in the low
+        # half of their slot), then its episodes' [sums, first returns, flags]
+        SLOTS = 8  # loss, kl, kl pad, vf loss, ent, ent pad, pad loss (unused), -
+        scal = torch.zeros(SLOTS * M + 3 * sum(N), dtype=f64, device=dev)
+        base = scal.data_ptr()
+
+        def slot(m, k):
+            return base + 8 * (SLOTS * m + k)
+        ep_at = np.concatenate([[0], np.cumsum(N)])
+
+        rows = (C.c_int64 * (2 * M))(*(S + [1] * M))
+        need = int(_lib.load().ga_members_diag_partials_doubles(rows, 2 * M))
+        partials = torch.empty(max(1, need), dtype=f64, device=dev)
+
+        def forward(nets, params_of):
+            """Every member's network on its batch and on the all-zero
+            observation: ([sum S, ld] outputs, [M, ld] outputs)."""
+            net = nets[0]
+            ld, aw = net.ld_out, net.act_width
+            out = torch.empty(sum(S) + M, ld, dtype=f32, device=dev)
+            acts = torch.empty(max(1, (sum(S) + M) * aw), dtype=f32, device=dev)
+            arr = (_lib.MemberForward * (2 * M))()
+            at = 0
+            for e in range(2 * M):
+                m, pad = e % M, e >= M
+                c = ctxs[m]
+                X = c.zero_obs if pad else c.batch.obs_dev
+                u = arr[e]
+                u.params = params_of(m).data_ptr()
+                u.X, u.ldx = X.data_ptr(), X.stride(0)
+                u.rows = 1 if pad else S[m]
+                u.acts = acts.data_ptr() + 4 * at * aw
+                u.out, u.ldo = out.data_ptr() + 4 * at * ld, ld
+                at += u.rows
+            call('ga_mlp_forward_members_f32', C.byref(net._desc), arr, 2 * M,
+                 stream)
+            return out, acts
+        off = np.concatenate([[0], np.cumsum(S)])
+        pad0 = int(off[-1])
+
+        head, keep = forward([a.policy.net for a in algos],
+                             lambda m: algos[m].policy.net.params)
+
+        # ---- LossAfter (and, categorical, the entropy sums of the batch and of
+        # the padded cell: the loss rows' second partial)
+        la = _lib.MembersLossArgs()
+        la.kind = 0 if gaussian else 2
+        la.A, la.algo, la.ent_flags = A, first._algo_id, first._ent_flags()
+        if gaussian:
+            la.has_min, la.min_log_std, la.has_max, la.max_log_std = \
+                pol0._std_args()
+        else:
+            la.double_softmax = int(pol0.double_softmax)
+        n_loss = M if gaussian else 2 * M
+        arr = (_lib.MemberLoss * n_loss)()
+        for e in range(n_loss):
+            m, pad = e % M, e >= M
+            a, c, u = algos[m], ctxs[m], arr[e]
+            row = (pad0 + m) if pad else int(off[m])
+            u.head, u.ld = head.data_ptr() + 4 * row * ld_out, ld_out
+            u.actions = c.batch.actions_dev.data_ptr()
+            u.lda = c.batch.actions_dev.stride(0)
+            u.old_ll, u.adv = c.old_ll.data_ptr(), c.adv.data_ptr()
+            u.log_std = a.policy.net.params.data_ptr()
+            u.rows = 1 if pad else S[m]
+            u.clip = float(a._lr_clip_range)
+            u.ent_coeff = float(a._policy_ent_coeff)
+            u.loss_out = slot(m, 6 if pad else 0)
+            u.ent_sum_out = slot(m, 5 if pad else 4)
+        call('ga_ppo_loss_members_f32', C.byref(la), arr, n_loss,
+             dptr(partials), partials.numel(), stream)
+
+        # ---- KL against the old policy: the batch's rows and the padded cell
+        arr = (_lib.MemberKl * (2 * M))()
+        for e in range(2 * M):
+            m, pad = e % M, e >= M
+            c, u = ctxs[m], arr[e]
+            old = c.mean_old_pad if pad else c.mean_old
+            row = (pad0 + m) if pad else int(off[m])
+            u.head_old, u.ld = old.data_ptr(), old.stride(0)
+            u.head_new = head.data_ptr() + 4 * row * ld_out
+            u.rows = 1 if pad else S[m]
+            u.log_std_old, u.log_std_new = float(c.s_old), float(s_new[m])
+            u.kl_sum_out = slot(m, 2 if pad else 1)
+        assert all(c.mean_old.stride(0) == ld_out for c in ctxs)
+        call('ga_kl_members_f32', int(not gaussian), A,
+             0 if gaussian else int(pol0.double_softmax), arr, 2 * M,
+             dptr(partials), partials.numel(), stream)
+
+        # ---- vf LossAfter
+        if linear:
+            vf_after = torch.cat([a._linear_vf_loss(after[m], ctxs[m].returns)
+                                  for m, a in enumerate(algos)])
+            scal[:SLOTS * M].view(M, SLOTS)[:, 3] = vf_after
+        else:
+            vnet0 = first._value_function.net
+            v, keep_v = forward([a._value_function.net for a in algos],
+                                lambda m: algos[m]._value_function.net.params)
+            arr = (_lib.MemberNll * M)()
+            for m, (a, c) in enumerate(zip(algos, ctxs)):
+                u = arr[m]
+                u.v = v.data_ptr() + 4 * int(off[m]) * vnet0.ld_out
+                u.ldv = vnet0.ld_out
+                u.returns = c.returns.data_ptr()
+                u.log_std = a._value_function.net.params.data_ptr()
+                u.rows = S[m]
+                u.loss_out = slot(m, 3)
+            call('ga_gaussian_nll_members_f32', arr, M, dptr(partials),
+                 partials.numel(), stream)
+
+        # ---- log_performance's device part
+        arr = (_lib.MemberEpisodes * M)()
+        for m, c in enumerate(ctxs):
+            u, b = arr[m], c.batch
+            u.rewards, u.ep_off = b.rewards_dev.data_ptr(), b.ep_off_dev.data_ptr()
+            u.n_eps = N[m]
+            u.returns = c.returns.data_ptr()
+            u.step_types = b.step_types_dev.data_ptr()
+            u.out = base + 8 * (SLOTS * M + 3 * int(ep_at[m]))
+        call('ga_episode_stats_members_f32', arr, M, int(StepType.TERMINAL),
+             stream)
+
+        # ---- ONE copy: the scalars, what the contexts hold from before the
+        # update, and the two fault words of the reduction workspaces
+        before = [torch.cat([c.loss_before for c in ctxs]).to(f64),
+                  torch.cat([c.vf_before for c in ctxs]).to(f64),
+                  torch.cat([c.kl_before for c in ctxs])]
+        words = [reduction_workspace(dev, tag)[-1:] for tag in (0, 1)]
+        host = torch.cat([scal] + before + words).cpu().numpy()
+        del head, keep
+        n_scal = scal.numel()
+        sc64 = host[:SLOTS * M].reshape(M, SLOTS)
+        sc32 = sc64.view(np.float32).reshape(M, SLOTS, 2)[:, :, 0]
+        lb, vb, kb = (host[n_scal + i * M:n_scal + (i + 1) * M]
+                      for i in range(3))
+        faulted = [tag for tag in (0, 1)
+                   if float(host[n_scal + 3 * M + tag]) != 0.0]
+        if faulted:
+            for tag in faulted:  # re-arm the barrier words for the next call
+                reduction_workspace(dev, tag)[-2:].zero_()
+            for a, c in zip(algos, ctxs):
+                a._restore_adam_steps(c.steps_before)
+            raise _barrier_fault_error(faulted)
+
+        # vpg.py:201 for every member (their snapshots are rows of one tensor)
+        self._old_rows.copy_(self._rows['policy']['params'])
+        returns = []
+        for m, (a, c) in enumerate(zip(algos, ctxs)):
+            # the device arithmetic of VPG._mean_kl on the host: fp64 throughout;
+            # torch divides a tensor by a Python number as a product with its
+            # reciprocal
+            kl = float(sc64[m, 1])
+            if c.n_pad > 0:
+                kl = kl + float(c.n_pad) * float(sc64[m, 2])
+            kl_a = kl * (1.0 / float(c.n_cells))
+            if gaussian:
+                entropy = a._entropy_of(s_new[m])
+            else:
+                tot, pad = float(sc64[m, 4]), float(sc64[m, 5])
+                entropy = (tot + c.n_pad * pad) / c.n_cells
+            vl_a = float(sc64[m, 3]) if linear else float(sc32[m, 3])
+            with logger.tabular.prefix('member{}/'.format(m)):
+                a._record_diagnostics(c, float(lb[m]), float(sc32[m, 0]),
+                                      float(vb[m]), vl_a, float(kb[m]), kl_a,
+                                      entropy)
+                lo = SLOTS * M + 3 * int(ep_at[m])
+                undiscounted = a._record_performance(
+                    itr, c.batch, host[lo:lo + 3 * N[m]])
+            returns.append(np.mean(undiscounted))
         return returns
 
     def train(self, trainer):
@@ -1889,13 +2163,15 @@ class PopulationPPO:
     # -- snapshots: the members rebuild their networks; the rows are re-established
     def __getstate__(self):
         state = self.__dict__.copy()
-        for k in ('_rows', '_partials', '_side_stream'):
+        for k in ('_rows', '_partials', '_side_stream', '_old_rows'):
             state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('_baselines', None)
+        # (snapshots written before the joint diagnostics existed)
+        self.__dict__.setdefault('_joint_diagnostics', False)
         self._adopt()
 
 

@@ -31,6 +31,7 @@
 
 #include "gemm_core.h"
 #include "layer_plans.h"
+#include "members_diag.h"
 
 namespace {
 
@@ -429,6 +430,17 @@ __attribute__((amdgpu_waves_per_eu(GA_GEMM_WAVES_PER_EU, 8)))
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_f32_kernel(
     GemmParams p) {
   gemm_f32_body<BM, BN, WAVES_M, WAVES_N, A_KC, B_KC, BKT, HEAD>(p, (int)blockIdx.x);
+}
+
+// The forward product (both operands k-contiguous) of every entry of a device table in one
+// grid (members_diag.h): entry blockIdx.y, whose own 1-D grid the launch's x covers or
+// exceeds.  The same body as gemm_f32_kernel's, so the same bits per entry.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool HEAD>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_f32_members_kernel(
+    const GemmParams* table) {
+  const GemmParams p = table[blockIdx.y];
+  if ((int)blockIdx.x >= p.gx * p.gy * p.gz) return;
+  gemm_f32_body<BM, BN, WAVES_M, WAVES_N, true, true, BK, HEAD>(p, (int)blockIdx.x);
 }
 
 // 256 x 256 tiles, 4 waves of 128 x 128: one wave per SIMD, pipelined k-loop
@@ -932,6 +944,32 @@ int ga_gemm_head_launch(const GemmHeadPlan& plan, const GemmParams& p, hipStream
     hipExtLaunchKernelGGL((gemm_f32_kernel<64, 256, 1, 8, true, true, BK, true>), grid, block,
                           0, stream, e0, e1, 0, p);
   GA_CHECK_LAUNCH("gemm_f32 (+head)");
+  return GA_OK;
+}
+
+int md_launch_gemm_members(int kind, const GemmParams* table, unsigned n, unsigned blocks,
+                           hipStream_t stream) {
+  // (counted as one launch of the lone kernel's kind, never timed)
+  ga_prof_count(kind == MD_GEMM_128x32 ? GA_PROF_GEMM_NT_256 : GA_PROF_GEMM_NT_128);
+  const dim3 grid(blocks, n), block(256);
+  switch (kind) {
+    case MD_GEMM_128x32:
+      hipLaunchKernelGGL((gemm_f32_members_kernel<128, 32, 4, 1, false>), grid, block, 0,
+                         stream, table);
+      break;
+    case MD_GEMM_64x64:
+      hipLaunchKernelGGL((gemm_f32_members_kernel<64, 64, 2, 2, false>), grid, block, 0, stream,
+                         table);
+      break;
+    case MD_GEMM_HEAD_64:
+      hipLaunchKernelGGL((gemm_f32_members_kernel<64, 64, 2, 2, true>), grid, block, 0, stream,
+                         table);
+      break;
+    default:
+      ga_set_error("gemm_f32_members: kind %d not instantiated", kind);
+      return GA_ERR_ARG;
+  }
+  GA_CHECK_LAUNCH("gemm_f32_members");
   return GA_OK;
 }
 

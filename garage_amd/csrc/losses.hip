@@ -9,9 +9,13 @@
 #include "common.h"
 #include "loss_params.h"
 #include "loss_rows.h"
+#include "members_diag.h"
 #include "shape_rules.h"
 
 namespace {
+
+// (the row kernels' bodies, loss_row_bodies.inc: the lone kernels take their own grid)
+#define GA_GRID_X gridDim.x
 
 // Multi-block reductions finish in the same launch: every block publishes its
 // partial sums, then takes a ticket; the block that draws the last one sees all of
@@ -62,51 +66,9 @@ __device__ void ppo_gaussian_finish(double obj, double ds, const float* log_std,
 }
 
 __global__ __launch_bounds__(256) void ppo_gaussian_loss_kernel(PpoLossParams p) {
-  __shared__ double red[4];
-  const float s = ga_log_std(*p.log_std, p.has_min, p.min_log_std, p.has_max,
-                             p.max_log_std, nullptr);
-  const float inv_var = expf(-2.f * s);
-  const float lognorm = s + (float)HALF_LOG_2PI;
-  const float invM = 1.f / (float)p.M;
-
-  double obj_sum = 0.0, ds_sum = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.M;
-       i += (int64_t)gridDim.x * 256) {
-    const int64_t src = p.idx ? (int64_t)p.idx[i] : i;
-    const float* mu = p.mean + i * p.ldm;
-    const float* a = p.actions + src * p.lda;
-    float ll = 0.f, q = 0.f;  // q = sum (a-mu)^2 / var
-    for (int j = 0; j < p.A; ++j) lr_gauss_dim(a[j], mu[j], inv_var, lognorm, q, ll);
-    if (p.ll_out) p.ll_out[i] = ll;
-    float g;  // d obj / d ll
-    const float obj = lr_surrogate(p.algo, p.clip, ll, p.algo == 1 ? 0.f : p.old_ll[src],
-                                   p.adv[src], &g);
-    obj_sum += (double)obj;
-    if (p.dmean) {
-      float* dm = p.dmean + i * p.ldm;
-      const float scale = -g * invM * inv_var;
-      for (int j = 0; j < p.A; ++j) dm[j] = scale * (a[j] - mu[j]);
-    }
-    // d ll / d s = sum_j ((a-mu)^2/var - 1)
-    ds_sum += (double)(-g * (q - (float)p.A));
-  }
-  const double o = ga_block_sum_256(obj_sum, red);
-  const double d = ga_block_sum_256(ds_sum, red);
-  double bo = o, bd = d;  // batch sums (the only block: its own)
-  if (gridDim.x > 1 || !p.loss_out) {
-    if (threadIdx.x == 0) {
-      p.partials[2 * blockIdx.x + 0] = o;
-      p.partials[2 * blockIdx.x + 1] = d;
-    }
-    if (!p.loss_out || !ga_take_last_ticket(p.ticket)) return;
-    if (threadIdx.x >= 64) return;
-    bo = ga_sum_partials(p.partials, gridDim.x, 0);
-    bd = ga_sum_partials(p.partials, gridDim.x, 1);
-  }
-  if (threadIdx.x == 0 && p.loss_out)
-    ppo_gaussian_finish(bo, bd, p.log_std, p.has_min, p.min_log_std, p.has_max,
-                        p.max_log_std, p.M, p.A, p.ent, p.loss_out, p.grad_slab0,
-                        p.slab_stride, p.n_splits);
+#define GA_LOSS_BODY 1
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
 }
 
 __global__ void ppo_gaussian_finalize_kernel(PpoFinalizeParams p) {
@@ -146,75 +108,9 @@ __device__ __forceinline__ void cat_row(const float* sc, int A, int dbl, float* 
 }
 
 __global__ __launch_bounds__(256) void ppo_categorical_loss_kernel(CatLossParams p) {
-  __shared__ double red[4];
-  const float invM = 1.f / (float)p.M;
-  double obj_sum = 0.0, ent_sum = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.M;
-       i += (int64_t)gridDim.x * 256) {
-    const int64_t src = p.idx ? (int64_t)p.idx[i] : i;
-    const float* sc = p.scores + i * p.lds;
-    const int a = (int)p.actions[src * p.lda];
-    float lse, mx, den;
-    cat_row(sc, p.A, p.double_softmax, &lse, &mx, &den);
-    // log-prob of the taken action and the entropy H = -sum q lp
-    float ll = 0.f, H = 0.f;
-    for (int j = 0; j < p.A; ++j) {
-      const float pj = expf(sc[j] - mx) / den;
-      const float lp = (p.double_softmax ? pj : sc[j]) - lse;
-      const float q = expf(lp);
-      H -= q * lp;
-      if (j == a) ll = lp;
-    }
-    float Hs = H, dHs = 1.f;  // softplus(H) and its derivative
-    if (p.ent.softplus) Hs = lr_softplus(H, &dHs);
-    if (p.ll_out) p.ll_out[i] = ll;
-    if (p.ent_out) p.ent_out[i] = Hs;
-    float g;
-    float obj = lr_surrogate(p.algo, p.clip, ll, p.algo == 1 ? 0.f : p.old_ll[src],
-                             p.adv[src], &g);
-    if (p.ent.regularized) obj += p.ent.coeff * Hs;
-    obj_sum += (double)obj;
-    ent_sum += (double)Hs;
-    if (p.dscores) {
-      const float cH = (p.ent.regularized && !p.ent.stop_grad) ? p.ent.coeff * dHs : 0.f;
-      float* ds = p.dscores + i * p.lds;
-      if (!p.double_softmax) {
-        for (int j = 0; j < p.A; ++j)
-          ds[j] = -lr_cat_grad(g, cH, sc[j] - lse, H, j == a) * invM;
-      } else {
-        // chain through p = softmax(scores): dz_k = p_k (dp_k - sum_j dp_j p_j)
-        float dot = 0.f;
-        for (int j = 0; j < p.A; ++j) {
-          const float pj = expf(sc[j] - mx) / den;
-          dot += lr_cat_grad(g, cH, pj - lse, H, j == a) * pj;
-        }
-        for (int k = 0; k < p.A; ++k) {
-          const float pk = expf(sc[k] - mx) / den;
-          const float dp = lr_cat_grad(g, cH, pk - lse, H, k == a);
-          ds[k] = -(pk * (dp - dot)) * invM;
-        }
-      }
-    }
-  }
-  const double o = ga_block_sum_256(obj_sum, red);
-  const double e = ga_block_sum_256(ent_sum, red);
-  double bo = o, be = e;  // batch sums (the only block: its own)
-  if (gridDim.x > 1 || !p.loss_out) {
-    if (threadIdx.x == 0) {
-      p.partials[2 * blockIdx.x + 0] = o;
-      p.partials[2 * blockIdx.x + 1] = e;
-    }
-    if (!p.loss_out || !ga_take_last_ticket(p.ticket)) return;
-    if (threadIdx.x >= 64) return;
-    bo = ga_sum_partials(p.partials, gridDim.x, 0);
-    be = ga_sum_partials(p.partials, gridDim.x, 1);
-  }
-  if (threadIdx.x == 0) {
-    *p.loss_out = (float)(-(bo / (double)p.M));
-    if (p.ent_sum_out) *p.ent_sum_out = be;
-    if (p.grad_slab0)  // the (unused) log-std slot of the flat layout stays 0
-      for (int64_t k = 0; k < p.n_splits; ++k) p.grad_slab0[k * p.slab_stride] = 0.f;
-  }
+#define GA_LOSS_BODY 2
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
 }
 
 __global__ void ppo_categorical_finalize_kernel(const double* partials, int nblocks,
@@ -239,61 +135,15 @@ __global__ void ppo_categorical_finalize_kernel(const double* partials, int nblo
 __global__ __launch_bounds__(256) void categorical_kl_kernel(
     const float* sc_old, const float* sc_new, int64_t ld, int64_t M, int A, int dbl,
     double* partials) {
-  __shared__ double red[4];
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M;
-       i += (int64_t)gridDim.x * 256) {
-    const float* so = sc_old + i * ld;
-    const float* sn = sc_new + i * ld;
-    float lo, mo, den_o, ln, mn, dn;
-    cat_row(so, A, dbl, &lo, &mo, &den_o);
-    cat_row(sn, A, dbl, &ln, &mn, &dn);
-    float kl = 0.f;
-    for (int j = 0; j < A; ++j) {
-      const float lpo = (dbl ? expf(so[j] - mo) / den_o : so[j]) - lo;
-      const float lpn = (dbl ? expf(sn[j] - mn) / dn : sn[j]) - ln;
-      kl += expf(lpo) * (lpo - lpn);
-    }
-    acc += (double)kl;
-  }
-  const double r = ga_block_sum_256(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = r;
+#define GA_LOSS_BODY 3
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
 }
 
 __global__ __launch_bounds__(256) void gaussian_nll_kernel(NllParams p) {
-  __shared__ double red[4];
-  const float s = *p.log_std;
-  const float inv_var = expf(-2.f * s);
-  const float invM = 1.f / (float)p.M;
-  double nll = 0.0, ds = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < p.M;
-       i += (int64_t)gridDim.x * 256) {
-    const int64_t src = p.idx ? (int64_t)p.idx[i] : i;
-    float dsi, dvi;
-    nll += (double)lr_nll_row(p.returns[src], p.v[i * p.ldv], s, inv_var, invM, &dsi, &dvi);
-    ds += (double)dsi;
-    if (p.dv) p.dv[i * p.ldv] = dvi;
-  }
-  const double a = ga_block_sum_256(nll, red);
-  const double b = ga_block_sum_256(ds, red);
-  double ba = a, bb = b;  // batch sums (the only block: its own)
-  if (gridDim.x > 1 || !p.loss_out) {
-    if (threadIdx.x == 0) {
-      p.partials[2 * blockIdx.x + 0] = a;
-      p.partials[2 * blockIdx.x + 1] = b;
-    }
-    if (!p.loss_out || !ga_take_last_ticket(p.ticket)) return;
-    if (threadIdx.x >= 64) return;
-    ba = ga_sum_partials(p.partials, gridDim.x, 0);
-    bb = ga_sum_partials(p.partials, gridDim.x, 1);
-  }
-  if (threadIdx.x == 0 && p.loss_out) {
-    *p.loss_out = (float)(ba / (double)p.M);
-    if (p.grad_slab0) {
-      p.grad_slab0[0] = (float)(bb / (double)p.M);
-      for (int64_t k = 1; k < p.n_splits; ++k) p.grad_slab0[k * p.slab_stride] = 0.f;
-    }
-  }
+#define GA_LOSS_BODY 4
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
 }
 
 __global__ void gaussian_nll_finalize_kernel(const double* partials, int nblocks,
@@ -319,23 +169,9 @@ __global__ void gaussian_nll_finalize_kernel(const double* partials, int nblocks
 __global__ __launch_bounds__(256) void gaussian_kl_kernel(
     const float* mean_old, const float* mean_new, int64_t ld, int64_t M, int A,
     float s_old, float s_new, double* partials) {
-  __shared__ double red[4];
-  // torch kl_normal_normal: 0.5 * (var_ratio + t1 - 1 - log(var_ratio))
-  const float ratio = expf(s_old - s_new);
-  const float var_ratio = ratio * ratio;
-  const float inv_std_new = expf(-s_new);
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M;
-       i += (int64_t)gridDim.x * 256) {
-    float kl = 0.f;
-    for (int j = 0; j < A; ++j) {
-      const float t = (mean_old[i * ld + j] - mean_new[i * ld + j]) * inv_std_new;
-      kl += 0.5f * (var_ratio + t * t - 1.f - logf(var_ratio));
-    }
-    acc += (double)kl;
-  }
-  const double r = ga_block_sum_256(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = r;
+#define GA_LOSS_BODY 5
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
 }
 
 __global__ void sum_partials_kernel(const double* partials, int nblocks, double* out) {
@@ -921,7 +757,159 @@ __global__ __launch_bounds__(HL_THREADS) void head_gaussian_nll_kernel(HeadLayer
   }
 }
 
+// ---- the member-indexed twins (members_diag.h) ---------------------------------------------
+// Row kernels: entry blockIdx.y of a device table, the lone kernel's body
+// (loss_row_bodies.inc) with the entry's own block count.  A members launch never takes the
+// single-launch finish: its host side asks for partials whenever an entry has more than one
+// block, and a one-block entry finishes itself as the lone kernel does.  They stay in this
+// file because the helpers the bodies call do.
+#undef GA_GRID_X
+#define GA_GRID_X md_entry.nb
+__global__ __launch_bounds__(256) void ppo_gaussian_loss_members_kernel(
+    const MdPpoEntry* table) {
+  const MdPpoEntry md_entry = table[blockIdx.y];
+  if (blockIdx.x >= md_entry.nb) return;
+  const PpoLossParams& p = md_entry.p;
+#define GA_LOSS_BODY 1
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
+}
+__global__ __launch_bounds__(256) void ppo_categorical_loss_members_kernel(
+    const MdCatEntry* table) {
+  const MdCatEntry md_entry = table[blockIdx.y];
+  if (blockIdx.x >= md_entry.nb) return;
+  const CatLossParams& p = md_entry.p;
+#define GA_LOSS_BODY 2
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
+}
+__global__ __launch_bounds__(256) void gaussian_nll_members_kernel(const MdNllEntry* table) {
+  const MdNllEntry md_entry = table[blockIdx.y];
+  if (blockIdx.x >= md_entry.nb) return;
+  const NllParams& p = md_entry.p;
+#define GA_LOSS_BODY 4
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
+}
+__global__ __launch_bounds__(256) void categorical_kl_members_kernel(const MdKlEntry* table) {
+  const MdKlEntry md_entry = table[blockIdx.y];
+  if (blockIdx.x >= md_entry.nb) return;
+  const float* sc_old = md_entry.head_old;
+  const float* sc_new = md_entry.head_new;
+  const int64_t ld = md_entry.ld, M = md_entry.M;
+  const int A = md_entry.A, dbl = md_entry.dbl;
+  double* partials = md_entry.partials;
+#define GA_LOSS_BODY 3
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
+}
+__global__ __launch_bounds__(256) void gaussian_kl_members_kernel(const MdKlEntry* table) {
+  const MdKlEntry md_entry = table[blockIdx.y];
+  if (blockIdx.x >= md_entry.nb) return;
+  const float* mean_old = md_entry.head_old;
+  const float* mean_new = md_entry.head_new;
+  const int64_t ld = md_entry.ld, M = md_entry.M;
+  const int A = md_entry.A;
+  const float s_old = md_entry.s_old, s_new = md_entry.s_new;
+  double* partials = md_entry.partials;
+#define GA_LOSS_BODY 5
+#include "loss_row_bodies.inc"
+#undef GA_LOSS_BODY
+}
+#undef GA_GRID_X
+// The fixed-order sums, one wave per entry (blockIdx.x): the lone finalize kernels' loops
+// and the same finish.  fp64 additions in the same order: the same bits.
+__global__ void ppo_gaussian_finalize_members_kernel(const PpoFinalizeParams* table) {
+  const PpoFinalizeParams p = table[blockIdx.x];
+  double obj = 0.0, ds = 0.0;
+  for (int b = threadIdx.x; b < p.nblocks; b += 64) {
+    obj += p.partials[2 * b + 0];
+    ds += p.partials[2 * b + 1];
+  }
+  obj = ga_wave_sum(obj);
+  ds = ga_wave_sum(ds);
+  if (threadIdx.x != 0) return;
+  ppo_gaussian_finish(obj, ds, p.log_std, p.has_min, p.min_log_std, p.has_max,
+                      p.max_log_std, p.M, p.A, p.ent, p.loss_out, p.grad_slab0,
+                      p.slab_stride, p.n_splits);
+}
+__global__ void ppo_categorical_finalize_members_kernel(const MdCatFinalize* table) {
+  const MdCatFinalize p = table[blockIdx.x];
+  double o = 0.0, e = 0.0;
+  for (int b = threadIdx.x; b < p.nblocks; b += 64) {
+    o += p.partials[2 * b];
+    e += p.partials[2 * b + 1];
+  }
+  o = ga_wave_sum(o);
+  e = ga_wave_sum(e);
+  if (threadIdx.x != 0) return;
+  *p.loss_out = (float)(-(o / (double)p.M));
+  if (p.ent_sum_out) *p.ent_sum_out = e;
+}
+__global__ void gaussian_nll_finalize_members_kernel(const MdNllFinalize* table) {
+  const MdNllFinalize p = table[blockIdx.x];
+  double a = 0.0;
+  for (int k = threadIdx.x; k < p.nblocks; k += 64) a += p.partials[2 * k];
+  a = ga_wave_sum(a);
+  if (threadIdx.x != 0) return;
+  *p.loss_out = (float)(a / (double)p.M);
+}
+__global__ void sum_partials_members_kernel(const MdSum* table) {
+  const MdSum p = table[blockIdx.x];
+  double a = 0.0;
+  for (int k = threadIdx.x; k < p.nblocks; k += 64) a += p.partials[k];
+  a = ga_wave_sum(a);
+  if (threadIdx.x == 0) *p.out = a;
+}
+
 }  // namespace
+
+// ---- the members' launch seam (members_diag.h) ---------------------------------------------
+#define MD_LAUNCH(name, kernel, grid, threads, table)                        \
+  do {                                                                       \
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, stream, table);       \
+    GA_CHECK_LAUNCH(name);                                                   \
+    return GA_OK;                                                            \
+  } while (0)
+int md_launch_ppo_gaussian_members(const MdPpoEntry* table, unsigned n, unsigned blocks,
+                                   hipStream_t stream) {
+  MD_LAUNCH("ppo_gaussian_loss_members", ppo_gaussian_loss_members_kernel, dim3(blocks, n),
+            256, table);
+}
+int md_launch_ppo_gaussian_finalize_members(const PpoFinalizeParams* table, unsigned n,
+                                            hipStream_t stream) {
+  MD_LAUNCH("ppo_gaussian_finalize_members", ppo_gaussian_finalize_members_kernel, dim3(n), 64,
+            table);
+}
+int md_launch_ppo_categorical_members(const MdCatEntry* table, unsigned n, unsigned blocks,
+                                      hipStream_t stream) {
+  MD_LAUNCH("ppo_categorical_loss_members", ppo_categorical_loss_members_kernel,
+            dim3(blocks, n), 256, table);
+}
+int md_launch_ppo_categorical_finalize_members(const MdCatFinalize* table, unsigned n,
+                                               hipStream_t stream) {
+  MD_LAUNCH("ppo_categorical_finalize_members", ppo_categorical_finalize_members_kernel,
+            dim3(n), 64, table);
+}
+int md_launch_nll_members(const MdNllEntry* table, unsigned n, unsigned blocks,
+                          hipStream_t stream) {
+  MD_LAUNCH("gaussian_nll_members", gaussian_nll_members_kernel, dim3(blocks, n), 256, table);
+}
+int md_launch_nll_finalize_members(const MdNllFinalize* table, unsigned n,
+                                   hipStream_t stream) {
+  MD_LAUNCH("gaussian_nll_finalize_members", gaussian_nll_finalize_members_kernel, dim3(n), 64,
+            table);
+}
+int md_launch_kl_members(int categorical, const MdKlEntry* table, unsigned n, unsigned blocks,
+                         hipStream_t stream) {
+  if (categorical)
+    MD_LAUNCH("categorical_kl_members", categorical_kl_members_kernel, dim3(blocks, n), 256, table);
+  MD_LAUNCH("gaussian_kl_members", gaussian_kl_members_kernel, dim3(blocks, n), 256, table);
+}
+int md_launch_sum_members(const MdSum* table, unsigned n, hipStream_t stream) {
+  MD_LAUNCH("sum_partials_members", sum_partials_members_kernel, dim3(n), 64, table);
+}
+#undef MD_LAUNCH
 
 // ---- the launch seam (loss_params.h): instantiate and launch, nothing else ----------------
 #define LS_LAUNCH(kernel, blocks, threads, lds, ...) \

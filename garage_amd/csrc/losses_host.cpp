@@ -22,12 +22,7 @@
 
 namespace {
 
-inline int red_blocks(int64_t n) {
-  int64_t b = ga_ceil_div(n, 256);  // one row per thread up to RED_BLOCKS blocks
-  if (b < 1) b = 1;
-  if (b > RED_BLOCKS) b = RED_BLOCKS;
-  return (int)b;
-}
+inline int red_blocks(int64_t n) { return ga_red_blocks(n); }  // (shape_rules.h)
 
 // the head kernels: a workgroup's 16-lane groups take HL_ROWS_MAX rows each per pass
 inline int head_blocks(int64_t M) {

@@ -20,6 +20,7 @@
 #include "internal.h"
 #include "fused_train.h"
 #include "layer_plans.h"
+#include "members_diag.h"
 
 // ---------------------------------------------------------------------------
 // Developer switches of this dispatch
@@ -370,20 +371,68 @@ static int launch_product(GemmParams p, int a_kc, int b_kc, int splits, hipStrea
   return ga_gemm_launch(plan, p, stream);
 }
 
-// The streaming forward (w_kc) / data gradient of `p` where its plan takes the product:
-// *taken says whether it did.
-static int try_skinny_forward(const GemmParams& p, bool w_kc, bool* taken,
-                              hipStream_t stream) {
+// The plan of the streaming forward (w_kc) / data gradient of `p` under the switches
+static SkinnyFwdPlan skinny_forward_plan(const GemmParams& p, bool w_kc) {
   static int rows_wg = -1;  // rows per workgroup
   if (rows_wg < 0) {
     const char* e = getenv("GARAGE_AMD_SKINNY_ROWS");  // A/B runs
     rows_wg = e ? atoi(e) : 0;
     if (rows_wg < 1) rows_wg = 32;
   }
-  const SkinnyFwdPlan plan = ga_skinny_fwd_plan(p, w_kc, g_skinny != 0, rows_wg);
+  return ga_skinny_fwd_plan(p, w_kc, g_skinny != 0, rows_wg);
+}
+// ... launched where it takes the product: *taken says whether it did.
+static int try_skinny_forward(const GemmParams& p, bool w_kc, bool* taken,
+                              hipStream_t stream) {
+  const SkinnyFwdPlan plan = skinny_forward_plan(p, w_kc);
   *taken = plan.taken;
   return plan.taken ? ga_skinny_fwd_launch(plan, ga_skinny_fwd_params(p, plan), stream)
                     : GA_OK;
+}
+
+// The launch that computes layer l of a forward pass over M rows (y = describe_layer's),
+// decided and NOT made: the streaming kernel, else this layer and the head in one launch,
+// else the tiles.  ga_mlp_forward_f32 launches the step; ga_mlp_forward_steps hands it to
+// the population's joint forward (members_diag_host.cpp), which launches the same kernel
+// for every member at once.
+static GaForwardStep plan_forward_step(const ga_mlp_desc* d, int l, const Layer& y,
+                                       const float* params, const float* X, int64_t ldx,
+                                       const int32_t* row_idx, int64_t M, float* acts,
+                                       float* out, int64_t ldo) {
+  const int L = d->n_layers;
+  GaForwardStep st = {};
+  st.layer = l;
+  // the last hidden layer of a net with a linear head may take the head along
+  const bool with_head =
+      out && l == L - 2 && d->output_act == 0 && !d->layer_norm &&
+      (g_fuse_head_forward == 2 || (g_fuse_head_forward == 1 && y.out_w <= 128));
+  Layer head = {};
+  if (with_head) head = describe_layer(d, L - 1, params, X, ldx, row_idx, acts);
+  st.g = forward_product(
+      y, M, y.is_last ? out : acts + d->act_off[l], y.is_last ? ldo : round4(y.out_w),
+      y.is_last ? d->output_act : act_forward_code(d->hidden_act),
+      with_head ? &head : nullptr, out, ldo);
+  st.sp = skinny_forward_plan(st.g, true);
+  if (st.sp.taken) {
+    st.kind = MD_FWD_SKINNY;
+    st.s = ga_skinny_fwd_params(st.g, st.sp);
+    return st;
+  }
+  if (with_head) {
+    st.hp = ga_gemm_head_plan(st.g);
+    if (st.hp.taken) {
+      st.kind = MD_FWD_GEMM_HEAD;
+      ga_gemm_head_apply(st.hp, &st.g);
+      return st;
+    }
+    st.g.head_n = 0;
+  }
+  st.kind = MD_FWD_GEMM;
+  const GemmSwitches sw = {g_small_m != 0, ga_split_bf16_gemm() != 0,
+                           ga_split_bf16_enabled() != 0, wgrad_paired_on()};
+  st.gp = ga_gemm_plan(st.g, 1, 1, 1, sw);
+  ga_gemm_apply(st.gp, &st.g);
+  return st;
 }
 
 // ---------------------------------------------------------------------------
@@ -433,31 +482,50 @@ extern "C" int ga_mlp_forward_f32(const ga_mlp_desc* d, const float* params,
                          stream);
       if (rc) return rc;
     }
-    // the last hidden layer of a net with a linear head may take the head along
-    const bool with_head =
-        out && l == L - 2 && d->output_act == 0 && !d->layer_norm &&
-        (g_fuse_head_forward == 2 || (g_fuse_head_forward == 1 && y.out_w <= 128));
-    Layer head = {};
-    if (with_head) head = describe_layer(d, L - 1, params, X, ldx, row_idx, acts);
-    GemmParams p = forward_product(
-        y, M, y.is_last ? out : acts + d->act_off[l], y.is_last ? ldo : round4(y.out_w),
-        y.is_last ? d->output_act : act_forward_code(d->hidden_act),
-        with_head ? &head : nullptr, out, ldo);
-    // the streaming kernel, else this layer and the head in one launch, else the tiles
-    bool streamed;
-    rc = try_skinny_forward(p, true, &streamed, stream);
-    if (rc) return rc;
-    if (streamed) continue;
-    if (with_head) {
-      const GemmHeadPlan hp = ga_gemm_head_plan(p);
-      if (hp.taken) {
-        ga_gemm_head_apply(hp, &p);
-        return ga_gemm_head_launch(hp, p, stream);  // both layers done
+    GaForwardStep st = plan_forward_step(d, l, y, params, X, ldx, row_idx, M, acts, out, ldo);
+    if (st.kind == MD_FWD_SKINNY) {
+      rc = ga_skinny_fwd_launch(st.sp, st.s, stream);
+    } else if (st.kind == MD_FWD_GEMM_HEAD) {
+      return ga_gemm_head_launch(st.hp, st.g, stream);  // both layers done
+    } else {
+      if (st.gp.planes) {  // the weight planes are this side's to fetch
+        st.g.bplanes = ga_weight_planes(st.g.B, st.g.ldb, st.g.N, st.g.K, st.gp.planes_bwd,
+                                        stream);
+        GA_REQUIRE(st.g.bplanes, "gemm: no memory for the weight planes");
       }
-      p.head_n = 0;
+      rc = ga_gemm_launch(st.gp, st.g, stream);
     }
-    rc = launch_product(p, 1, 1, 1, stream);
     if (rc) return rc;
+  }
+  return GA_OK;
+}
+
+// (members_diag.h)
+int ga_mlp_forward_steps(const ga_mlp_desc* d, const float* params, const float* X,
+                         int64_t ldx, const int32_t* row_idx, int64_t M, float* acts,
+                         float* out, int64_t ldo, GaForwardStep* steps, int* n_steps) {
+  int rc = check_desc(d, "ga_mlp_forward_steps");
+  if (rc) return rc;
+  GA_REQUIRE(params && X && acts && out && steps && n_steps,
+             "ga_mlp_forward_steps: null pointer");
+  GA_REQUIRE(M >= 1 && M < (1ll << 31), "ga_mlp_forward_steps: bad M");
+  GA_REQUIRE(ldx % 4 == 0 && ldx >= d->dims[0], "ga_mlp_forward_steps: ldx %lld",
+             (long long)ldx);
+  GA_REQUIRE(ldo >= d->dims[d->n_layers], "ga_mlp_forward_steps: ldo too small");
+  GA_REQUIRE(ga_aligned16(params) && ga_aligned16(X) && ga_aligned16(acts),
+             "ga_mlp_forward_steps: pointers must be 16-B aligned");
+  GA_REQUIRE(!d->layer_norm, "ga_mlp_forward_steps: layer normalisation is no layer product");
+  GA_REQUIRE(!(g_fused_forward && d->hidden_act == 0 && d->output_act == 0 &&
+               ga_policy_step_fused_supported(d)),
+             "ga_mlp_forward_steps: ga_set_fused_forward(1) takes this network in one launch");
+  *n_steps = 0;
+  for (int l = 0; l < d->n_layers; ++l) {
+    const Layer y = describe_layer(d, l, params, X, ldx, row_idx, acts);
+    GaForwardStep st = plan_forward_step(d, l, y, params, X, ldx, row_idx, M, acts, out, ldo);
+    GA_REQUIRE(st.kind != MD_FWD_GEMM || !st.gp.planes,
+               "ga_mlp_forward_steps: layer %d takes the split-operand GEMM", l);
+    steps[(*n_steps)++] = st;
+    if (st.kind == MD_FWD_GEMM_HEAD) break;  // both layers done
   }
   return GA_OK;
 }

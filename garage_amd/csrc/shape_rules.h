@@ -29,6 +29,11 @@ constexpr int PS_KC = 32;            // k chunk
 constexpr int PS_TRAIN_ROWS = 64;    // rows per workgroup of the training forward
 // ---- losses.hip: the stand-alone loss, statistics and optimizer kernels
 constexpr int RED_BLOCKS = 512;      // upper bound on partial-producing blocks
+// blocks of a row kernel over n rows: one row per thread of 256 up to RED_BLOCKS blocks
+// (losses_host.cpp, and members_diag_host.cpp for every member of a joint launch)
+constexpr int ga_red_blocks(int64_t n) {
+  return n <= 256 ? 1 : ((n + 255) / 256 > RED_BLOCKS ? RED_BLOCKS : (int)((n + 255) / 256));
+}
 constexpr int LS_DOT_THREADS = 1024; // the one workgroup of the dot product
 constexpr int FS_MAX_A = 32;         // classes of the categorical Fisher seed (in registers)
 // the head layer inside the loss kernel: 16 lanes own one row of the hidden activations

@@ -1356,6 +1356,100 @@ GA_API int64_t ga_update_members_partials_floats(const ga_mlp_desc* desc, int64_
  * 0 .. 1. */
 GA_API int ga_update_epoch_members(const ga_update_members_args* args, ga_stream_t stream);
 
+/* ---- the diagnostics of a POPULATION in joint launches -----------------------------
+ * What VPG._after_train runs per member after the update (vpg.py:178-184 and
+ * log_performance, _functions.py:233-275) -- ga_mlp_forward_f32, ga_ppo_*_loss_f32,
+ * ga_*_kl_f32, ga_gaussian_nll_loss_f32, ga_episode_sums_f32 -- for every member of a
+ * population in a FIXED number of launches per entry point, whatever the member count
+ * (new: the reference trains one learner per process).  Member m gets, bit for bit, what
+ * the lone entry point gives on its arguments alone: each launch runs the lone kernel's
+ * body for the member a workgroup belongs to (its parameter struct comes from a device
+ * table, its block index and block count are those of the lone launch), every member has
+ * its own stretch of the partials, and sums finish in a second fixed-order launch.  The
+ * members arrays are HOST arrays; the tables are built in pinned memory the library keeps
+ * and uploaded by one asynchronous copy per call, as ga_update_epoch_members' tables are
+ * (eight calls' worth: a call MAY BLOCK its caller on the call that used its slot eight
+ * calls earlier, and is not graph-capture safe).  Every entry refuses before any copy or
+ * launch (negative return, ga_last_error): null pointers, a member count outside 1 .. 1024
+ * (1 .. 2048 where it says so: a member's batch and its one padded cell are two entries),
+ * a member with rows < 1 or >= 2^31, strides narrower than the width they hold, partials
+ * smaller than ga_members_diag_partials_doubles of the members' rows. */
+/* ga_mlp_forward_f32(desc, params, X, ldx, NULL, rows, acts, out, ldo) of every entry.
+ * acts: rows * (round4(dims[1]) + round4(dims[2])) floats, layer l's block at (the widths
+ * below it) * rows -- the layout of ga_mlp_forward_f32's workspace at a capacity of
+ * exactly `rows`; desc->act_off is not read.  At most three launches per kernel kind a
+ * layer takes (the plans are those of ga_mlp_forward_f32 under the same switches; entries
+ * whose row counts take different kernels go to different launches).  Refuses networks
+ * ga_update_members_supported refuses and pointers / strides that are not 16-byte aligned
+ * quads.  1 .. 2048 entries. */
+typedef struct ga_member_forward {
+  const float* params; const float* X; int64_t ldx; int64_t rows;
+  float* acts; float* out; int64_t ldo;
+} ga_member_forward;
+GA_API int ga_mlp_forward_members_f32(const ga_mlp_desc* desc, const ga_member_forward* members,
+                                      int64_t n_members, ga_stream_t stream);
+/* 1: ga_mlp_forward_members_f32 takes this network under the developer switches as they
+ * stand NOW (ga_update_members_supported's shapes, and every layer on a kernel that has a
+ * members instantiation: not with ga_set_fused_forward(1), which takes the network in one
+ * launch of another kernel); 0 otherwise, with the reason in ga_last_error.  Callers ask
+ * before they begin work that the refusal would interrupt. */
+GA_API int ga_mlp_forward_members_supported(const ga_mlp_desc* desc);
+/* doubles of `partials` for members of these row counts (2 per block of a member's own
+ * grid; the KL entry needs half); 0: a bad count or row count */
+GA_API int64_t ga_members_diag_partials_doubles(const int64_t* rows, int64_t n_members);
+/* ga_ppo_gaussian_loss_f32 (kind 0) / ga_ppo_categorical_loss_f32 (kind 2) of every entry,
+ * forward only: no gradient seed, no log-likelihoods, rows in order.  One launch, and one
+ * more where an entry has more than 256 rows.  ent_sum_out (categorical, optional): the
+ * sum of the rows' entropies.  1 .. 2048 entries. */
+typedef struct ga_members_loss_args {
+  int32_t kind; int32_t A; int32_t algo; int32_t ent_flags;
+  int32_t has_min; float min_log_std; int32_t has_max; float max_log_std;
+  int32_t double_softmax;
+} ga_members_loss_args;
+typedef struct ga_member_loss {
+  const float* head; int64_t ld;          /* [rows, ld] means / class scores */
+  const float* actions; int64_t lda;
+  const float* old_ll; const float* adv;  /* old_ll: NULL with algo 1 */
+  const float* log_std;                   /* kind 0: the device scalar parameter */
+  int64_t rows;
+  float clip; float ent_coeff;
+  float* loss_out; double* ent_sum_out;
+} ga_member_loss;
+GA_API int ga_ppo_loss_members_f32(const ga_members_loss_args* args,
+                                   const ga_member_loss* members, int64_t n_members,
+                                   double* partials, int64_t partials_doubles,
+                                   ga_stream_t stream);
+/* ga_gaussian_nll_loss_f32 of every member, forward only.  1 .. 1024 members. */
+typedef struct ga_member_nll {
+  const float* v; int64_t ldv; const float* returns; const float* log_std;
+  int64_t rows; float* loss_out;
+} ga_member_nll;
+GA_API int ga_gaussian_nll_members_f32(const ga_member_nll* members, int64_t n_members,
+                                       double* partials, int64_t partials_doubles,
+                                       ga_stream_t stream);
+/* ga_gaussian_kl_f32 (categorical 0) / ga_categorical_kl_f32 (1) of every entry: two
+ * launches.  1 .. 2048 entries. */
+typedef struct ga_member_kl {
+  const float* head_old; const float* head_new; int64_t ld; int64_t rows;
+  float log_std_old; float log_std_new;   /* Gaussian heads */
+  double* kl_sum_out;
+} ga_member_kl;
+GA_API int ga_kl_members_f32(int categorical, int A, int double_softmax,
+                             const ga_member_kl* members, int64_t n_members, double* partials,
+                             int64_t partials_doubles, ga_stream_t stream);
+/* log_performance's device part of every member in one launch: out[0 .. n_eps) =
+ * ga_episode_sums_f32(rewards, ep_off), out[n_eps .. 2 n_eps) = returns[ep_off[e]],
+ * out[2 n_eps .. 3 n_eps) = 1.0 where step_types[ep_off[e + 1] - 1] == terminal, else 0.0.
+ * 1 .. 1024 members. */
+typedef struct ga_member_episodes {
+  const float* rewards; const int64_t* ep_off; int64_t n_eps;
+  const float* returns; const uint8_t* step_types; double* out;
+} ga_member_episodes;
+GA_API int ga_episode_stats_members_f32(const ga_member_episodes* members, int64_t n_members,
+                                        int terminal, ga_stream_t stream);
+/* frees the pinned / device table slots of the entries above (tests) */
+GA_API void ga_members_diag_release(void);
+
 /* RCCL communicator for the data-parallel gradient all-reduce (new: the
  * reference has no collective on this path).
  * ga_comm_unique_id fills 128 bytes on rank 0 (HOST pointer) to be broadcast by

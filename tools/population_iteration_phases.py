@@ -10,6 +10,8 @@ it, with a device synchronise before and after each of the five phases:
   before_train   every member's ``_before_train``, one after another
   update         ``PopulationPPO._train``: the joint passes of both networks
   after_train    every member's ``_after_train``, one after another
+                 (``--joint-diagnostics``: the joint launches and one host copy
+                 of ``PopulationPPO(joint_diagnostics=True)``)
 
 ``--linear-baseline``: the value functions are the members of one
 ``LinearFeatureBaselinePopulation``: before_train and after_train then begin with
@@ -52,6 +54,9 @@ def main():
     ap.add_argument('--linear-baseline', action='store_true',
                     help='one LinearFeatureBaselinePopulation as the value '
                          'functions')
+    ap.add_argument('--joint-diagnostics', action='store_true',
+                    help='PopulationPPO(joint_diagnostics=True): the members\' '
+                         'diagnostics after the update in joint launches')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_iteration_phases needs an MI355X: there is '
@@ -61,7 +66,7 @@ def main():
     M = args.members
     env, members = make_members(M, args.minibatch,
                                 'joint' if args.linear_baseline else None)
-    pop = PopulationPPO(members)
+    pop = PopulationPPO(members, joint_diagnostics=args.joint_diagnostics)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5,
                                    joint_pack=not args.per_member_pack)
@@ -113,7 +118,8 @@ def main():
         print(json.dumps(dict(
             phase=k, members=M, minibatch=args.minibatch,
             joint_pack=not args.per_member_pack,
-            linear_baseline=args.linear_baseline, median_ms=float(np.median(v)),
+            linear_baseline=args.linear_baseline,
+            joint_diagnostics=args.joint_diagnostics, median_ms=float(np.median(v)),
             min_ms=float(v.min()), max_ms=float(v.max()),
             spread=float((v.max() - v.min()) / np.median(v)),
             share=float(np.median(v) / np.median(total)),
