@@ -6,8 +6,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
-HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step lnorm member_pack linear_baseline members_diag
-CPPS  := errors prof update update_members comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host members_diag_host
+HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step members_natural lnorm member_pack linear_baseline members_diag
+CPPS  := errors prof update update_members members_natural_host comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host members_diag_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets
@@ -96,7 +96,8 @@ ASAN_PROGRAMS := \
   losses_host_asan_test:losses_host_harness:losses_host \
   linear_baseline_asan_test:linear_baseline_harness:linear_baseline_host \
   linear_baseline_members_asan_test:linear_baseline_members_harness:linear_baseline_members_host \
-  members_diag_asan_test:members_diag_harness:members_diag_host+mlp_layers
+  members_diag_asan_test:members_diag_harness:members_diag_host+mlp_layers \
+  members_natural_asan_test:members_natural_harness:members_natural_host
 ASAN_CXX := g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer
 
 # (the stem is the source's path: $(OUT)/asan/tests/host/x.o, $(OUT)/asan/$(CSRC)/y.o;
@@ -204,10 +205,18 @@ asan-linear-baseline-members: $(OUT)/linear_baseline_members_asan_test
 asan-members-diag: $(OUT)/members_diag_asan_test
 	$(OUT)/members_diag_asan_test
 
+# The population's natural-gradient step (members_natural_host.cpp) against fakes of the
+# launch seam: the launch sequence of a solve, a product and a backtrack round, the table's
+# contents, each member's stretch of an exactly sized workspace, every refusal before any
+# copy or launch.
+asan-members-natural: $(OUT)/members_natural_asan_test
+	$(OUT)/members_natural_asan_test
+
 # everything above; the programs with suites run all of them in one process
 asan-all: $(foreach p,$(ASAN_PROGRAMS),$(OUT)/$(word 1,$(subst :, ,$(p))))
 	set -e; for t in $^; do ./$$t; done
 
 .PHONY: asan-host asan-slab-sum asan-fwd-dgrad asan-env-loop asan-rescale-loop asan-mlp \
   asan-members asan-member-pack asan-fused-host asan-rollout-host asan-losses-host \
-  asan-linear-baseline asan-linear-baseline-members asan-members-diag asan-all
+  asan-linear-baseline asan-linear-baseline-members asan-members-diag \
+  asan-members-natural asan-all

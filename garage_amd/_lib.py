@@ -200,6 +200,29 @@ class UpdateMembersArgs(C.Structure):
                 ('partials_floats', c_i64), ('workspace', ptr)]
 
 
+class MemberNatural(C.Structure):
+    """``ga_member_natural``."""
+    _fields_ = [('params', ptr), ('X', ptr), ('ldx', c_i64), ('S', c_i64),
+                ('actions', ptr), ('lda', c_i64), ('old_ll', ptr),
+                ('adv', ptr), ('max_constraint_value', c_f64),
+                ('hvp_reg_coeff', c_f64), ('backtrack_ratio', c_f64),
+                ('ent_coeff', c_f32), ('state', c_i32), ('vec', ptr),
+                ('out', ptr)]
+
+
+class MembersNaturalArgs(C.Structure):
+    """``ga_members_natural_args``."""
+    _fields_ = [('desc', C.POINTER(MlpDesc)), ('n_flat', c_i64),
+                ('kind', c_i32), ('ent_flags', c_i32), ('has_min', c_i32),
+                ('min_log_std', c_f32), ('has_max', c_i32),
+                ('max_log_std', c_f32), ('double_softmax', c_i32),
+                ('learn_std', c_i32), ('cg_iters', c_i32), ('pad_', c_i32),
+                ('n_members', c_i64),
+                ('members_host', C.POINTER(MemberNatural)),
+                ('workspace', ptr), ('workspace_floats', c_i64),
+                ('result', ptr)]
+
+
 class MemberForward(C.Structure):
     """``ga_member_forward``."""
     _fields_ = [('params', ptr), ('X', ptr), ('ldx', c_i64), ('rows', c_i64),
@@ -431,6 +454,15 @@ SIGNATURES = {
     'ga_update_members_partials_floats': (c_i64, [C.POINTER(MlpDesc), c_i64,
                                                   c_i64]),
     'ga_update_epoch_members': (c_int, [C.POINTER(UpdateMembersArgs), ptr]),
+    # the natural-gradient (TRPO) step of a population
+    'ga_members_natural_supported': (c_int, [C.POINTER(MlpDesc)]),
+    'ga_members_natural_floats': (c_i64, [C.POINTER(MlpDesc), c_i64, c_i64,
+                                          C.POINTER(c_i64),
+                                          C.POINTER(c_i64)]),
+    'ga_members_natural_solve': (c_int, [C.POINTER(MembersNaturalArgs), ptr]),
+    'ga_members_natural_fvp': (c_int, [C.POINTER(MembersNaturalArgs), ptr]),
+    'ga_members_natural_candidates': (c_int, [C.POINTER(MembersNaturalArgs),
+                                              c_i64, ptr]),
     # the diagnostics of a population in joint launches
     'ga_mlp_forward_members_f32': (c_int, [C.POINTER(MlpDesc),
                                            C.POINTER(MemberForward), c_i64,

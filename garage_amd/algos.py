@@ -1580,6 +1580,7 @@ class PopulationPPO:
     """
 
     _BUFFERS = ('params', 'grads', 'exp_avg', 'exp_avg_sq')
+    _MEMBER_TYPES = (PPO, VPG)  # what a member may be (PopulationTRPO: TRPO)
 
     def __init__(self, members, sampler=None, joint_diagnostics=False):
         self.members = list(members)
@@ -1641,9 +1642,10 @@ class PopulationPPO:
             raise ValueError('PopulationPPO trains at most 1024 members')
         for m, algo in enumerate(self.members):
             who = 'member {}'.format(m)
-            if type(algo) not in (PPO, VPG):
-                raise ValueError('{} is a {}: PopulationPPO trains PPO or VPG '
-                                 'objects'.format(who, type(algo).__name__))
+            if type(algo) not in self._MEMBER_TYPES:
+                raise ValueError('{} is a {}: {} trains {} objects'.format(
+                    who, type(algo).__name__, type(self).__name__,
+                    ' or '.join(t.__name__ for t in self._MEMBER_TYPES)))
             linear = _is_linear(algo._value_function)
             if linear and getattr(algo._value_function, '_population',
                                   None) is None:
@@ -1652,7 +1654,7 @@ class PopulationPPO:
                     'supported: take the members\' value functions, in member '
                     'order, from one garage_amd.baselines.'
                     'LinearFeatureBaselinePopulation'.format(who))
-            for opt in (algo._policy_optimizer, algo._vf_optimizer):
+            for opt in self._adam_optimizers(algo):
                 if opt is None:  # a linear baseline has no optimizer
                     continue
                 if not opt.default_adam:
@@ -1714,6 +1716,11 @@ class PopulationPPO:
                     'PopulationPPO {}'.format(len(population),
                                               len(self.members)))
             self._baselines = population
+
+    @staticmethod
+    def _adam_optimizers(algo):
+        """The optimizers of a member that must be torch's default-shaped Adam."""
+        return (algo._policy_optimizer, algo._vf_optimizer)
 
     def _check_joint_diagnostics(self, error):
         """The joint diagnostics run the per-layer forward kernels' twins: a
@@ -2175,4 +2182,186 @@ class PopulationPPO:
         self._adopt()
 
 
-__all__ = ['VPG', 'PPO', 'TRPO', 'CEM', 'PopulationPPO']
+class PopulationTRPO(PopulationPPO):
+    """A population of narrow TRPO learners whose natural-gradient steps share
+    their launches.
+
+    ``members`` are ordinary :class:`TRPO` objects under :class:`PopulationPPO`'s
+    rules for the networks and the value functions (MLPs trained by the joint
+    passes on a side stream, or the members of one
+    ``LinearFeatureBaselinePopulation``).  The policies' pass of an iteration is
+    ``ga_members_natural_solve`` -- the surrogate's gradient, ``cg_iters``
+    conjugate-gradient iterations and the step length of EVERY member in
+    ``2 (cg_iters + 1) + 2`` launches with no host wait, where a lone ``TRPO`` pays
+    about 150 launches and 35 host waits per member -- followed by backtrack
+    rounds of two launches and ONE host copy of all members' ``(loss, KL)`` each
+    (``ga_members_natural_candidates``); the acceptance rule of
+    ``TRPO._train_policy`` is applied per member on the host.  The members may
+    differ in ``max_constraint_value``, ``hvp_reg_coeff`` and ``backtrack_ratio``
+    and must share ``cg_iters``, ``max_backtracks`` and ``accept_violation``.
+    Each member's ``last_cg`` holds ``grad``, ``step_dir``, ``descent_step`` (views
+    of the population's rows) and ``accepted``.  The arithmetic is the lone
+    path's in another summation order, not its bits.  Anything unsupported raises
+    a ``ValueError`` naming it; nothing falls back to per-member steps."""
+
+    _MEMBER_TYPES = (TRPO, )
+
+    @staticmethod
+    def _adam_optimizers(algo):
+        return (algo._vf_optimizer, )
+
+    @staticmethod
+    def _shared_facts(algo):
+        h = algo._policy_optimizer._hyper
+        return PopulationPPO._shared_facts(algo) + [
+            ('cg_iters', int(h['cg_iters'])),
+            ('max_backtracks', int(h['max_backtracks'])),
+            ('accept_violation', bool(h['accept_violation']))]
+
+    def _check_members(self):
+        from garage_amd import _lib
+        import ctypes as C
+        super()._check_members()
+        for m, algo in enumerate(self.members):
+            if not _lib.load().ga_members_natural_supported(
+                    C.byref(algo.policy.net._desc)):
+                raise ValueError('member {}: the policy network {} is unsupported '
+                                 'by the joint natural-gradient step'.format(
+                                     m, tuple(algo.policy.net.dims)))
+        self._natural_ws = None
+
+    def _joint_passes(self, ctxs):
+        import ctypes as C
+        main = torch.cuda.current_stream()
+        side = None
+        if self._baselines is None:
+            # the value functions' pass on a side stream, as PopulationPPO's (the
+            # permutations are drawn before the side stream waits for the inputs)
+            perms = [list(algo._vf_optimizer.epoch_permutations(c.S))
+                     for algo, c in zip(self.members, ctxs)]
+            a, arr, mods, opts = self._pass_args('vf', ctxs)
+            if getattr(self, '_side_stream', None) is None:
+                self._side_stream = torch.cuda.Stream()
+            side = self._side_stream
+            side.wait_stream(main)
+            for e in range(len(perms[0])):
+                for m, mod in enumerate(mods):
+                    perm = perms[m][e]
+                    arr[m].perm = None if perm is None else perm.data_ptr()
+                    arr[m].step0 = mod.net.adam_steps
+                call('ga_update_epoch_members', C.byref(a),
+                     C.c_void_p(side.cuda_stream))
+                for m, mod in enumerate(mods):
+                    mod.net.adam_steps += len(
+                        opts[m].minibatch_bounds(ctxs[m].S)) - 1
+        self._natural_step(ctxs)
+        if side is not None:
+            main.wait_stream(side)
+            del a, arr, perms
+
+    def _natural_step(self, ctxs):
+        """The policies' pass: the joint solve, then the backtrack rounds."""
+        from garage_amd import _lib
+        import ctypes as C
+        lib = _lib.load()
+        first, M = self.members[0], len(self.members)
+        pol, net0 = first.policy, first.policy.net
+        hypers = [algo._policy_optimizer._hyper for algo in self.members]
+        a = _lib.MembersNaturalArgs()
+        a.desc, a.n_flat, a.n_members = C.pointer(net0._desc), net0.n_flat, M
+        a.kind = 0 if pol.kind == 'gaussian' else 2
+        if pol.kind == 'gaussian':
+            a.has_min, a.min_log_std, a.has_max, a.max_log_std = pol._std_args()
+        else:
+            a.double_softmax = int(pol.double_softmax)
+        a.learn_std = int(getattr(pol, '_learn_std', True))
+        a.ent_flags = first._ent_flags()
+        a.cg_iters = int(hypers[0]['cg_iters'])
+        arr = (_lib.MemberNatural * M)()
+        rows = self._rows['policy']['params']
+        for m, (algo, c, h) in enumerate(zip(self.members, ctxs, hypers)):
+            u, batch = arr[m], c.batch
+            u.params = rows[m].data_ptr()
+            u.X, u.ldx, u.S = batch.obs_dev.data_ptr(), batch.obs_dev.stride(0), c.S
+            u.actions = batch.actions_dev.data_ptr()
+            u.lda = batch.actions_dev.stride(0)
+            u.old_ll, u.adv = c.old_ll.data_ptr(), c.adv.data_ptr()
+            u.max_constraint_value = float(h['max_constraint_value'])
+            u.hvp_reg_coeff = float(h['hvp_reg_coeff'])
+            u.backtrack_ratio = float(h['backtrack_ratio'])
+            u.ent_coeff = float(algo._policy_ent_coeff)
+        a.members_host = arr
+        sizes = (C.c_int64 * M)(*[int(c.S) for c in ctxs])
+        layout = (C.c_int64 * 5)()
+        need = int(lib.ga_members_natural_floats(a.desc, a.n_flat, M, sizes, layout))
+        if need <= 0:
+            raise ValueError('PopulationTRPO: the joint natural-gradient step does '
+                             'not take these members')
+        ws = self._natural_ws
+        if ws is None or ws.numel() < need:
+            ws = self._natural_ws = torch.zeros(need, dtype=torch.float32,
+                                                device=net0.device)
+        a.workspace, a.workspace_floats = ws.data_ptr(), ws.numel()
+        result = torch.zeros(M, 2, dtype=torch.float64, device=net0.device)
+        a.result = result.data_ptr()
+        stream = stream_ptr()
+        call('ga_members_natural_solve', C.byref(a), stream)
+        nf4 = (net0.n_flat + 3) & ~3
+        vectors = ws[layout[0]:layout[0] + 7 * M * nf4].view(7, M, nf4)
+        scalars = ws[layout[1]:layout[1] + 16 * M].view(torch.float64).view(M, 8)
+        searching, accepted = [True] * M, [-1] * M
+        last = [(float('nan'), float('nan'))] * M
+        loss_before = None
+        for k in range(int(hypers[0]['max_backtracks'])):
+            if not any(searching):
+                break
+            for m in range(M):
+                arr[m].state = 0 if searching[m] else 1
+            call('ga_members_natural_candidates', C.byref(a), k, stream)
+            if loss_before is None:
+                loss_before = scalars[:, 3].cpu().numpy()
+            res = result.cpu().numpy()  # ONE copy: every member's (loss, KL)
+            for m in range(M):
+                if not searching[m]:
+                    continue
+                last[m] = (float(res[m, 0]), float(res[m, 1]))
+                if (last[m][0] < loss_before[m] and last[m][1]
+                        <= hypers[m]['max_constraint_value']):
+                    searching[m], accepted[m] = False, k
+        if loss_before is None:
+            loss_before = scalars[:, 3].cpu().numpy()
+        restore = False
+        for m, h in enumerate(hypers):
+            loss, constraint = last[m]
+            arr[m].state = 1
+            if ((math.isnan(loss) or math.isnan(constraint)
+                 or loss >= loss_before[m]
+                 or constraint >= h['max_constraint_value'])
+                    and not h['accept_violation']):
+                # (the lone path's lines, with the member named)
+                who = 'member{}: '.format(m)
+                logger.log(who + 'Line search condition violated. Rejecting the '
+                           'step!')
+                if math.isnan(loss):
+                    logger.log(who + 'Violated because loss is NaN')
+                if math.isnan(constraint):
+                    logger.log(who + 'Violated because constraint is NaN')
+                if loss >= loss_before[m]:
+                    logger.log(who + 'Violated because loss not improving')
+                if constraint >= h['max_constraint_value']:
+                    logger.log(who + 'Violated because constraint is violated')
+                arr[m].state, accepted[m], restore = 2, -1, True
+        if restore:
+            call('ga_members_natural_candidates', C.byref(a), 0, stream)
+        for m, algo in enumerate(self.members):
+            algo.last_cg = dict(grad=vectors[0, m, :net0.n_flat],
+                                step_dir=vectors[1, m, :net0.n_flat],
+                                descent_step=vectors[5, m, :net0.n_flat],
+                                prev=vectors[6, m, :net0.n_flat],
+                                accepted=accepted[m], loss=last[m][0],
+                                constraint=last[m][1],
+                                loss_before=float(loss_before[m]))
+        del arr
+
+
+__all__ = ['VPG', 'PPO', 'TRPO', 'CEM', 'PopulationPPO', 'PopulationTRPO']

@@ -252,4 +252,128 @@ __device__ __forceinline__ void lr_finish(const LossRowArgs& a, double first, do
   lr_gaussian_finish(a.ent, a.A, s, chain, first, second, M, loss, dlogstd);
 }
 
+// ---- rows of the constrained (TRPO) step for heads of <= 8 outputs in registers: the
+// metric seed of the Fisher-vector product and the KL of two heads, in the operation
+// order of fisher_seed_kernel / fisher_seed_categorical_kernel / the KL kernels of
+// losses.hip (members_natural.hip computes them inside its pass over the rows).
+
+// Gaussian seed: dout_j = tout_j * scale, scale = exp(-2 s) / M
+__device__ __forceinline__ void lr_fisher_seed_gauss_row(int A, float scale,
+                                                         const float (&tout)[8],
+                                                         float (&dout)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dout[j] = j < A ? tout[j] * scale : 0.f;
+}
+
+// Categorical seed from the row's scores and their tangent:
+// u = J1 t, w = (diag(q) - q q^T) u, dout = J1 w / M (J1 = I without double_softmax)
+__device__ __forceinline__ void lr_fisher_seed_cat_row(int A, int double_softmax,
+                                                       float inv_m, const float (&sc)[8],
+                                                       const float (&tsc)[8],
+                                                       float (&dout)[8]) {
+  float z[8], q[8], u[8];
+  float mx = sc[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j)
+    if (j < A) mx = fmaxf(mx, sc[j]);
+  float den = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    z[j] = j < A ? expf(sc[j] - mx) : 0.f;
+    den += z[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z[j] /= den;
+  if (double_softmax) {
+    float den2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      q[j] = j < A ? expf(z[j]) : 0.f;  // z in (0, 1]: no shift needed
+      den2 += q[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q[j] /= den2;
+    float zt = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < A) zt += z[j] * tsc[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) u[j] = j < A ? z[j] * (tsc[j] - zt) : 0.f;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      q[j] = z[j];
+      u[j] = j < A ? tsc[j] : 0.f;
+    }
+  }
+  float qu = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) qu += q[j] * u[j];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) u[j] = q[j] * (u[j] - qu);  // w
+  if (double_softmax) {
+    float zw = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) zw += z[j] * u[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) u[j] = z[j] * (u[j] - zw);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dout[j] = j < A ? u[j] * inv_m : 0.f;
+}
+
+// KL(old || new) of one row of Independent Normals with scalar log-stds
+// (kl_normal_normal): var_ratio = exp(s_old - s_new)^2, inv_std_new = exp(-s_new)
+__device__ __forceinline__ float lr_kl_gauss_row(int A, float var_ratio, float inv_std_new,
+                                                 const float (&mo)[8],
+                                                 const float (&mn)[8]) {
+  float kl = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (j < A) {
+      const float t = (mo[j] - mn[j]) * inv_std_new;
+      kl += 0.5f * (var_ratio + t * t - 1.f - logf(var_ratio));
+    }
+  return kl;
+}
+
+// log-probabilities of a categorical row (scores sc[0..A))
+__device__ __forceinline__ void lr_cat_logp(int A, int double_softmax, const float (&sc)[8],
+                                            float (&lp)[8]) {
+  float mx = sc[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j)
+    if (j < A) mx = fmaxf(mx, sc[j]);
+  float den = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (j < A) den += expf(sc[j] - mx);
+  float lse;
+  if (!double_softmax) {
+    lse = mx + logf(den);
+  } else {
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < A) s2 += expf(expf(sc[j] - mx) / den);
+    lse = logf(s2);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    lp[j] = j < A ? (double_softmax ? expf(sc[j] - mx) / den : sc[j]) - lse : 0.f;
+}
+
+// KL(old || new) of one categorical row
+__device__ __forceinline__ float lr_kl_cat_row(int A, int double_softmax,
+                                               const float (&so)[8], const float (&sn)[8]) {
+  float lpo[8], lpn[8];
+  lr_cat_logp(A, double_softmax, so, lpo);
+  lr_cat_logp(A, double_softmax, sn, lpn);
+  float kl = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (j < A) kl += expf(lpo[j]) * (lpo[j] - lpn[j]);
+  return kl;
+}
+
 }  // namespace

@@ -22,7 +22,10 @@ enum GaProfKind {
   GA_PROF_ROLLOUT_WIDE = 14,  // policy_step_fused_kernel<512> with n_steps > 1 (weights
                               // streamed: layer inputs up to 512); counted only
   GA_PROF_MEMBERS_STEP = 15,  // narrow_train_members_kernel<*>: step k of a whole
-                              // population in one launch; counted only
+                              // population in one launch; and every launch of the
+                              // population's natural-gradient step (members_natural.hip:
+                              // a pass over the rows, a conjugate-gradient update, a
+                              // candidate's finish, a restore); counted only
   GA_PROF_KINDS = 16
 };
 

@@ -16,6 +16,9 @@ constexpr int FT_W1_FLOATS = 5120;   // LDS floats for the first layer's weights
 // ---- narrow_body.h: two hidden layers of equal width 32 or 64
 constexpr int NS_ROWS = FT_ROWS;     // (its launches size their grids by ga_fused_tiles)
 constexpr int NS_HN = 8;             // head outputs, at most
+// ---- members_natural.hip: a member's rows are split among at most NG_SHARES persistent
+// workgroups (one gradient share each), a function of the member's row count alone
+constexpr int NG_SHARES = 16;
 // ---- small_step.hip: one tile of up to 64 rows, hidden width up to 256
 constexpr int SS_ROWS = 64;
 constexpr int SS_HMAX = 256;

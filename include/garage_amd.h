@@ -1356,6 +1356,75 @@ GA_API int64_t ga_update_members_partials_floats(const ga_mlp_desc* desc, int64_
  * 0 .. 1. */
 GA_API int ga_update_epoch_members(const ga_update_members_args* args, ga_stream_t stream);
 
+/* ---- the natural-gradient (TRPO) step of a POPULATION of narrow networks -----------
+ * trpo.py:121-144 and ConjugateGradientOptimizer.step
+ * (torch/optimizers/conjugate_gradient_optimizer.py:69-104,146-186,236-277) for every
+ * member at once.  Each pass over the members' whole batches -- the gradient of the
+ * unclipped surrogate, a Fisher-vector product A v = J^T M J v + reg v (M: the Hessian of
+ * mean KL(old || new) with respect to the head outputs at new == old), a line-search
+ * candidate's loss and KL -- is ONE launch whatever the member count, with the member's
+ * weights (and v) held in LDS and no activation, tangent or seed written to memory; the
+ * conjugate-gradient vectors and scalars stay on the device.
+ * One member: its flat parameters (the row that rolls out), its batch, its own
+ * constraint, regularisation and backtrack ratio.  vec / out: ga_members_natural_fvp
+ * only (n_flat floats each).  state: ga_members_natural_candidates only -- 0 still
+ * searching, 1 accepted (left alone), 2 rejected (its saved parameters are put back). */
+typedef struct ga_member_natural {
+  float* params;
+  const float* X; int64_t ldx; int64_t S;
+  const float* actions; int64_t lda;
+  const float* old_ll; const float* adv;
+  double max_constraint_value, hvp_reg_coeff, backtrack_ratio;
+  float ent_coeff; int32_t state;
+  const float* vec; float* out;
+} ga_member_natural;
+/* What the members share.  kind 0 Gaussian / 2 categorical; ent_flags, has_min ..
+ * max_log_std, double_softmax, learn_std as in ga_update_args.  workspace: at least
+ * ga_members_natural_floats floats, 16-byte aligned, the SAME memory for the solve and
+ * the candidates that follow it.  result: device doubles [n_members][2], (loss, KL) of
+ * each searching member's candidate (ga_members_natural_candidates). */
+typedef struct ga_members_natural_args {
+  const ga_mlp_desc* desc; int64_t n_flat;
+  int32_t kind; int32_t ent_flags;
+  int32_t has_min; float min_log_std; int32_t has_max; float max_log_std;
+  int32_t double_softmax; int32_t learn_std;
+  int32_t cg_iters; int32_t pad_;
+  int64_t n_members;
+  const ga_member_natural* members_host; /* HOST array [n_members] */
+  float* workspace; int64_t workspace_floats;
+  double* result;
+} ga_members_natural_args;
+/* 1: the networks these entries take -- those of ga_update_members_supported. */
+GA_API int ga_members_natural_supported(const ga_mlp_desc* desc);
+/* Floats of `workspace` for members of rows[m] samples (HOST array); 0: unsupported
+ * network or sizes out of range.  layout (optional, 5 entries), in floats from the start
+ * of the workspace: [0] the members' vectors, [7][n_members][round4(n_flat)] floats --
+ * 0 gradient, 1 step direction x, 2 r, 3 p, 4 z, 5 descent step, 6 saved parameters --
+ * [1] their scalars, [n_members][8] doubles -- 0 r.r, 1 x.Ax, 2 step size, 3 loss before,
+ * 4 conjugate gradient finished early, 5 iterations run -- [2] .. [4] internal. */
+GA_API int64_t ga_members_natural_floats(const ga_mlp_desc* desc, int64_t n_flat,
+                                         int64_t n_members, const int64_t* rows,
+                                         int64_t* layout);
+/* The whole solve, 2 (cg_iters + 1) + 2 launches after one asynchronous copy of the member
+ * table, no host wait: gradient pass; b, x = 0, r = p = b; cg_iters x (product of p; the
+ * recurrence's update, a member whose r.r falls under 1e-10 is left alone from then on);
+ * product of x; x.Ax, the step size sqrt(2 delta / (x.Ax + 1e-8)), the descent step and
+ * the saved parameters. */
+GA_API int ga_members_natural_solve(const ga_members_natural_args* args, ga_stream_t stream);
+/* out_m = A_m vec_m for every member: two launches. */
+GA_API int ga_members_natural_fvp(const ga_members_natural_args* args, ga_stream_t stream);
+/* Backtrack round k: every searching member's parameters become saved - ratio^k descent
+ * and result gets the candidate's loss and KL (two launches); the saved parameters go
+ * back into every rejected member (one more launch when there is one).  All three
+ * refuse before any launch (negative return, ga_last_error): null pointers, n_members
+ * outside 1 .. 1024, an unsupported network, a kind other than 0 and 2, offsets that are
+ * not quads from 4 up inside n_flat, operands that are not 16-byte aligned quads,
+ * S outside 1 .. 2^31 - 1, a workspace smaller than ga_members_natural_floats,
+ * cg_iters or k outside 0 .. 1000, a constraint that is not positive, a negative
+ * regularisation, a ratio outside (0, 1], a state outside 0 .. 2. */
+GA_API int ga_members_natural_candidates(const ga_members_natural_args* args, int64_t k,
+                                         ga_stream_t stream);
+
 /* ---- the diagnostics of a POPULATION in joint launches -----------------------------
  * What VPG._after_train runs per member after the update (vpg.py:178-184 and
  * log_performance, _functions.py:233-275) -- ga_mlp_forward_f32, ga_ppo_*_loss_f32,
