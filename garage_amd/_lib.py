@@ -264,6 +264,14 @@ class MemberEpisodes(C.Structure):
                 ('returns', ptr), ('step_types', ptr), ('out', ptr)]
 
 
+class MemberAdvantage(C.Structure):
+    """``ga_member_advantage``."""
+    _fields_ = [('rewards', ptr), ('values', ptr), ('offsets', ptr),
+                ('n_rows', c_i64), ('T', c_i64), ('ld', c_i64),
+                ('max_len', c_i64), ('v0', ptr), ('bonus_const', c_f32),
+                ('adv', ptr), ('ret', ptr), ('stats', ptr)]
+
+
 class LinearGramMember(C.Structure):
     """``ga_linear_gram_member``."""
     _fields_ = [('obs', ptr), ('ldo', c_i64), ('ep_off', ptr),
@@ -472,6 +480,10 @@ SIGNATURES = {
     'ga_ppo_loss_members_f32': (c_int, [C.POINTER(MembersLossArgs),
                                         C.POINTER(MemberLoss), c_i64, ptr,
                                         c_i64, ptr]),
+    'ga_ppo_loss_ll_members_f32': (c_int, [C.POINTER(MembersLossArgs),
+                                           C.POINTER(MemberLoss),
+                                           C.POINTER(ptr), c_i64, ptr, c_i64,
+                                           ptr]),
     'ga_gaussian_nll_members_f32': (c_int, [C.POINTER(MemberNll), c_i64, ptr,
                                             c_i64, ptr]),
     'ga_kl_members_f32': (c_int, [c_int, c_int, c_int, C.POINTER(MemberKl),
@@ -479,6 +491,10 @@ SIGNATURES = {
     'ga_episode_stats_members_f32': (c_int, [C.POINTER(MemberEpisodes), c_i64,
                                              c_int, ptr]),
     'ga_members_diag_release': (None, []),
+    # the advantages of a population in one launch
+    'ga_advantages_members_f32': (c_int, [C.POINTER(MemberAdvantage), c_i64,
+                                          c_int, c_f64, c_f64, c_int, c_int,
+                                          ptr]),
     # LinearFeatureBaseline (np/baselines/linear_feature_baseline.py:43-93)
     'ga_linear_features_supported': (c_int, [c_int]),
     'ga_linear_gram_workspace_doubles': (c_i64, [c_int, c_i64]),

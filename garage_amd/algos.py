@@ -1577,15 +1577,30 @@ class PopulationPPO:
     and brings all members' scalars to the host in one copy, instead of about
     fifteen launches and six host waits per member.  Every member is left bit
     for bit as the default path leaves it.
+
+    ``joint_before=True`` (off by default) does the same for every member's work
+    before the update (``VPG._before_train``): the value functions' and the old
+    policies' forwards, every member's returns, advantages and their
+    normalisation in ONE launch (``ga_advantages_members_f32``), the
+    log-likelihoods under the old policies and LossBefore / KLBefore / the value
+    LossBefore, in a fixed number of launches whatever the member count, with two
+    host copies for the population instead of three host waits per member.
+    ``entropy_method='max'`` is refused (its reward bonus is a host value per
+    member, or per-step entropies), as is a member whose batch exceeds 32768
+    steps.  Again every member is bit for bit the default path's.
     """
+
+    MAX_JOINT_STEPS = 32768  # MA_MAX_STEPS: a member's advantages live in LDS
 
     _BUFFERS = ('params', 'grads', 'exp_avg', 'exp_avg_sq')
     _MEMBER_TYPES = (PPO, VPG)  # what a member may be (PopulationTRPO: TRPO)
 
-    def __init__(self, members, sampler=None, joint_diagnostics=False):
+    def __init__(self, members, sampler=None, joint_diagnostics=False,
+                 joint_before=False):
         self.members = list(members)
         self._sampler = sampler
         self._joint_diagnostics = bool(joint_diagnostics)
+        self._joint_before = bool(joint_before)
         self._check_members()
         if sampler is not None and getattr(
                 sampler, 'n_members', len(self.members)) != len(self.members):
@@ -1683,6 +1698,13 @@ class PopulationPPO:
                             who, name, tuple(mod.net.dims)))
         if self._joint_diagnostics:
             self._check_joint_diagnostics(ValueError)
+        if self._joint_before:
+            if any(a._maximum_entropy for a in self.members):
+                raise ValueError(
+                    "joint_before: entropy_method='max' is not supported (its "
+                    'reward bonus needs a host value per member, or per-step '
+                    'entropies)')
+            self._check_joint_diagnostics(ValueError, 'joint_before')
         first = self._shared_facts(self.members[0])
         for m, algo in enumerate(self.members[1:], 1):
             for (name, a), (_, b) in zip(first, self._shared_facts(algo)):
@@ -1722,7 +1744,7 @@ class PopulationPPO:
         """The optimizers of a member that must be torch's default-shaped Adam."""
         return (algo._policy_optimizer, algo._vf_optimizer)
 
-    def _check_joint_diagnostics(self, error):
+    def _check_joint_diagnostics(self, error, what='joint_diagnostics'):
         """The joint diagnostics run the per-layer forward kernels' twins: a
         developer switch that sends the members' networks to another kernel
         (``ga_set_fused_forward(1)``) is refused here -- at construction, and
@@ -1738,9 +1760,10 @@ class PopulationPPO:
         for name, mod in mods:
             if not lib.ga_mlp_forward_members_supported(C.byref(mod.net._desc)):
                 raise error(
-                    'joint_diagnostics: the {} network cannot take the joint '
+                    '{}: the {} network cannot take the joint '
                     'forward as the library is set now: {}'.format(
-                        name, lib.ga_last_error().decode('utf-8', 'replace')))
+                        what, name,
+                        lib.ga_last_error().decode('utf-8', 'replace')))
 
     def _networks(self):
         """Which of the members' networks train in the joint passes."""
@@ -1767,8 +1790,9 @@ class PopulationPPO:
                     setattr(mod.net, name, t[m])
                 rows[name] = t
             self._rows[which] = rows
-        if self._joint_diagnostics:
+        if self._joint_diagnostics or self._joint_before:
             # the old policies' snapshots as rows too: one copy syncs them all
+            # (and one comparison tells which members' still equal their policy)
             t = torch.empty_like(self._rows['policy']['params'])
             for m, algo in enumerate(self.members):
                 t[m].copy_(algo._old_policy.params)
@@ -1911,6 +1935,8 @@ class PopulationPPO:
                              '{}'.format(len(self.members), len(batches)))
         if self._joint_diagnostics:
             self._check_joint_diagnostics(RuntimeError)
+        if self._joint_before:
+            self._check_joint_diagnostics(RuntimeError, 'joint_before')
         ctxs = self._before_trains(batches)
         self._train(ctxs)
         return self._after_trains(itr, ctxs)
@@ -1919,12 +1945,268 @@ class PopulationPPO:
         """Every member's ``_before_train``; linear baselines are predicted for
         all members in one launch first (the previous iteration's fit)."""
         before = [None] * len(self.members)
-        if self._baselines is not None:
+        if self._baselines is not None or self._joint_before:
             batches = [algo._to_device_batch(b)
                        for algo, b in zip(self.members, batches)]
+        if self._joint_before:
+            for m, b in enumerate(batches):
+                if b.n_samples > self.MAX_JOINT_STEPS:
+                    raise ValueError(
+                        'joint_before: member {} has a batch of {} steps; the '
+                        'joint advantage launch takes at most {}'.format(
+                            m, b.n_samples, self.MAX_JOINT_STEPS))
+        if self._baselines is not None:
             before = self._baselines.predict_batches(batches)
+        if self._joint_before:
+            return self._before_trains_joint(batches, before)
         return [algo._before_train(b, v)
                 for algo, b, v in zip(self.members, batches, before)]
+
+    def _forward_members(self, nets, params_of, ctxs, row_at, n_rows):
+        """``ga_mlp_forward_members_f32``: every member's network (parameters
+        ``params_of(m)``) on its batch, into rows ``row_at[m] ..`` of the
+        ``[n_rows + M, ld]`` result, and on the all-zero observation, into row
+        ``n_rows + m``.  Returns the result and what keeps the launch's
+        activations alive."""
+        from garage_amd import _lib
+        import ctypes as C
+        net, M = nets[0], len(nets)
+        dev = net.device
+        ld, aw = net.ld_out, net.act_width
+        out = torch.empty(n_rows + M, ld, dtype=torch.float32, device=dev)
+        acts = torch.empty(max(1, (n_rows + M) * aw), dtype=torch.float32,
+                           device=dev)
+        arr = (_lib.MemberForward * (2 * M))()
+        for e in range(2 * M):
+            m, pad = e % M, e >= M
+            c = ctxs[m]
+            X = c.zero_obs if pad else c.batch.obs_dev
+            at = (n_rows + m) if pad else int(row_at[m])
+            u = arr[e]
+            u.params = params_of(m).data_ptr()
+            u.X, u.ldx = X.data_ptr(), X.stride(0)
+            u.rows = 1 if pad else c.S
+            u.acts = acts.data_ptr() + 4 * at * aw
+            u.out, u.ldo = out.data_ptr() + 4 * at * ld, ld
+        call('ga_mlp_forward_members_f32', C.byref(net._desc), arr, 2 * M,
+             stream_ptr())
+        return out, acts
+
+    def _before_trains_joint(self, batches, baselines):
+        """``_before_trains`` in joint launches: the device part of every
+        member's ``VPG._before_train`` through the ``ga_*_members_f32`` entry
+        points -- each member gets the bits of its lone launches -- and the
+        contexts the default path builds.
+
+        Two host copies for the population.  An early one, while the value
+        forward, the advantage launch and the old policies' forward execute:
+        which members' old policy still equals the current one (one row-wise
+        comparison of the stacked rows; where all do, the old heads ARE the
+        current ones, as in ``VPG._before_train``) and, for Gaussian heads, the
+        log-std parameters, which the KL launch takes as host values.  A last
+        one for the values of the all-zero observation (MLP value functions),
+        which the contexts hold as Python floats."""
+        from garage_amd import _lib
+        import ctypes as C
+        algos, M = self.members, len(self.members)
+        first = algos[0]
+        pol0 = first.policy
+        net0 = pol0.net
+        dev = pol0.device
+        gaussian = pol0.kind == 'gaussian'
+        linear = self._baselines is not None
+        A, ld_out = net0.out_dim, net0.ld_out
+        stream = stream_ptr()
+        f32, f64 = torch.float32, torch.float64
+        zero_obs = torch.zeros(1, batches[0].obs_dev.shape[1], device=dev)
+
+        ctxs = []
+        for a, batch in zip(algos, batches):
+            S = batch.n_samples
+            n_cells, P = a._padded_cells(batch.lengths)
+            a.policy.net._workspace(S)
+            if not linear:
+                a._value_function.net._workspace(S)
+            ctxs.append(types.SimpleNamespace(
+                batch=batch, S=S, zero_obs=zero_obs, n_pad=n_cells - S,
+                n_cells=n_cells, P=P, share=a._dp_setup(S), gaussian=gaussian,
+                steps_before=(a.policy.net.adam_steps, None if linear
+                              else a._value_function.net.adam_steps)))
+        if len({c.P for c in ctxs}) != 1:  # (one padding length a launch)
+            raise ValueError('joint_before: the members\' batches pad to '
+                             'different episode lengths')
+        S = [c.S for c in ctxs]
+        # every member's stretch of a joint vector begins on a 16-byte boundary,
+        # as its own allocation on the default path does
+        at = np.concatenate([[0], np.cumsum([round4(s) for s in S])])
+        total = int(at[-1])
+
+        # ---- the value functions on the batches and on the all-zero observation
+        if linear:
+            v0_ptr = [None] * M
+            for c, v in zip(ctxs, baselines):
+                c.values, c.v0 = v, 0.0
+        else:
+            vnets = [a._value_function.net for a in algos]
+            vout, keep_v = self._forward_members(
+                vnets, lambda m: vnets[m].params, ctxs, at, total)
+            vals = vout[:, 0].contiguous()
+            v0_ptr = [vals.data_ptr() + 4 * (total + m) for m in range(M)]
+            for m, c in enumerate(ctxs):
+                c.values = vals[int(at[m]):int(at[m]) + S[m]].view(-1, 1)
+
+        # ---- returns, advantages and their normalisation: one launch
+        adv = torch.empty(total, dtype=f32, device=dev)
+        ret = torch.empty(total, dtype=f32, device=dev)
+        stats = torch.zeros(M, 4, dtype=f64, device=dev)
+        arr = (_lib.MemberAdvantage * M)()
+        for m, (a, c) in enumerate(zip(algos, ctxs)):
+            u, b = arr[m], c.batch
+            lo = int(at[m])
+            c.adv, c.returns = adv[lo:lo + S[m]], ret[lo:lo + S[m]]
+            longest = int(b.lengths.max())
+            u.rewards = b.rewards_dev.data_ptr()
+            u.values = c.values.data_ptr()
+            if int(b.lengths.min()) == longest:  # an (N, L) matrix
+                u.n_rows, u.T, u.ld = len(b.lengths), longest, longest
+            else:
+                u.offsets = b.ep_off_dev.data_ptr()
+                u.n_rows, u.T, u.ld = len(b.lengths), S[m], 0
+            u.max_len = longest
+            u.v0 = v0_ptr[m]
+            u.adv, u.ret = c.adv.data_ptr(), c.returns.data_ptr()
+            u.stats = stats[m].data_ptr()
+        call('ga_advantages_members_f32', arr, M, int(ctxs[0].P),
+             float(first._discount), float(first._gae_lambda),
+             int(first._center_adv), int(first._positive_adv), stream)
+
+        # ---- the old policies on the batches and on the all-zero observation
+        cur, old = self._rows['policy']['params'], self._old_rows
+        pnets = [a.policy.net for a in algos]
+        head_old, keep_old = self._forward_members(
+            pnets, lambda m: old[m], ctxs, at, total)
+        early = [(old == cur).all(dim=1).to(f64)]
+        if gaussian:
+            early += [old[:, 0].to(f64), cur[:, 0].to(f64)]
+        early = torch.cat(early).cpu().numpy()
+        same = bool(early[:M].all())
+        s_old, s_new = [0.0] * M, [0.0] * M
+        if gaussian:
+            s_old = [a.policy.log_std_of(float(early[M + m]))[0]
+                     for m, a in enumerate(algos)]
+            s_new = [a.policy.log_std_of(float(early[2 * M + m]))[0]
+                     for m, a in enumerate(algos)]
+        # (a member whose old policy equals its policy would get the old heads'
+        # bits again: the forward under the current parameters runs only where
+        # somebody changed a member's parameters between two iterations)
+        head_new, keep_new = (head_old, None) if same else \
+            self._forward_members(pnets, lambda m: cur[m], ctxs, at, total)
+        for m, c in enumerate(ctxs):
+            lo = int(at[m])
+            c.mean_old = head_old[lo:lo + S[m]]
+            c.mean_old_pad = head_old[total + m:total + m + 1]
+            c.s_old = s_old[m]
+
+        # ---- every member's scalars: SLOTS doubles each (fp32 results in the low
+        # half of their slot)
+        SLOTS = 4  # loss, kl sum, kl sum of the padded cell, vf loss
+        scal = torch.zeros(SLOTS * M, dtype=f64, device=dev)
+        scal32 = scal.view(f32)
+        base = scal.data_ptr()
+
+        def slot(m, k):
+            return base + 8 * (SLOTS * m + k)
+        rows = (C.c_int64 * (2 * M))(*(S + [1] * M))
+        need = int(_lib.load().ga_members_diag_partials_doubles(rows, 2 * M))
+        partials = torch.empty(max(1, need), dtype=f64, device=dev)
+        old_ll = torch.empty(total, dtype=f32, device=dev)
+        unused = torch.empty(M, dtype=f32, device=dev)
+
+        la = _lib.MembersLossArgs()
+        la.kind = 0 if gaussian else 2
+        la.A, la.ent_flags = A, first._ent_flags()
+        if gaussian:
+            la.has_min, la.min_log_std, la.has_max, la.max_log_std = \
+                pol0._std_args()
+        else:
+            la.double_softmax = int(pol0.double_softmax)
+
+        def loss(head, params, algo, with_ll):
+            la.algo = algo
+            arr = (_lib.MemberLoss * M)()
+            ll = (C.c_void_p * M)()
+            for m, (a, c) in enumerate(zip(algos, ctxs)):
+                u, lo = arr[m], int(at[m])
+                u.head, u.ld = head.data_ptr() + 4 * lo * ld_out, ld_out
+                u.actions = c.batch.actions_dev.data_ptr()
+                u.lda = c.batch.actions_dev.stride(0)
+                u.adv = c.adv.data_ptr()
+                u.log_std = params[m].data_ptr()
+                u.rows = S[m]
+                u.clip = float(a._lr_clip_range)
+                u.ent_coeff = float(a._policy_ent_coeff)
+                if with_ll:
+                    c.old_ll = old_ll[lo:lo + S[m]]
+                    ll[m] = c.old_ll.data_ptr()
+                    u.loss_out = unused[m].data_ptr()
+                else:
+                    u.old_ll = c.old_ll.data_ptr()
+                    u.loss_out = slot(m, 0)
+            call('ga_ppo_loss_ll_members_f32', C.byref(la), arr,
+                 ll if with_ll else None, M, dptr(partials), partials.numel(),
+                 stream)
+        # the log-likelihoods under the old policies (the VPG objective: no
+        # ratio), then LossBefore with them
+        loss(head_old, old, 1, True)
+        loss(head_new, cur, first._algo_id, False)
+
+        # ---- KLBefore: the batch's rows and the padded cell
+        arr = (_lib.MemberKl * (2 * M))()
+        for e in range(2 * M):
+            m, pad = e % M, e >= M
+            u = arr[e]
+            row = (total + m) if pad else int(at[m])
+            u.head_old = head_old.data_ptr() + 4 * row * ld_out
+            u.head_new = head_new.data_ptr() + 4 * row * ld_out
+            u.ld = ld_out
+            u.rows = 1 if pad else S[m]
+            u.log_std_old, u.log_std_new = float(s_old[m]), float(s_new[m])
+            u.kl_sum_out = slot(m, 2 if pad else 1)
+        call('ga_kl_members_f32', int(not gaussian), A,
+             0 if gaussian else int(pol0.double_softmax), arr, 2 * M,
+             dptr(partials), partials.numel(), stream)
+        # VPG._mean_kl's device arithmetic for all members at once: fp64, the
+        # padded cells where a member has any, torch's division of a tensor by a
+        # Python number as a product with its reciprocal
+        sc = scal.view(M, SLOTS)
+        n_pad = torch.tensor([float(c.n_pad) for c in ctxs], dtype=f64, device=dev)
+        recip = torch.tensor([1.0 / float(c.n_cells) for c in ctxs], dtype=f64,
+                             device=dev)
+        kl = torch.where(n_pad > 0, sc[:, 1] + n_pad * sc[:, 2], sc[:, 1]) * recip
+
+        # ---- the value LossBefore
+        if not linear:
+            arr = (_lib.MemberNll * M)()
+            for m, (a, c) in enumerate(zip(algos, ctxs)):
+                u = arr[m]
+                u.v, u.ldv = c.values.data_ptr(), c.values.stride(0)
+                u.returns = c.returns.data_ptr()
+                u.log_std = a._value_function.net.params.data_ptr()
+                u.rows = S[m]
+                u.loss_out = slot(m, 3)
+            call('ga_gaussian_nll_members_f32', arr, M, dptr(partials),
+                 partials.numel(), stream)
+            v0 = vals[total:total + M].cpu().tolist()  # the last copy
+        for m, (a, c) in enumerate(zip(algos, ctxs)):
+            c.loss_before = scal32[2 * SLOTS * m:2 * SLOTS * m + 1]
+            c.kl_before = kl[m:m + 1]
+            if linear:
+                c.vf_before = a._linear_vf_loss(c.values, c.returns)
+            else:
+                c.vf_before = scal32[2 * (SLOTS * m + 3):2 * (SLOTS * m + 3) + 1]
+                c.v0 = float(v0[m])
+        del keep_old, keep_new
+        return ctxs
 
     def _after_trains(self, itr, ctxs):
         """Every member's ``_after_train``, logged under ``member<m>/``; the just
@@ -2179,6 +2461,8 @@ class PopulationPPO:
         self.__dict__.setdefault('_baselines', None)
         # (snapshots written before the joint diagnostics existed)
         self.__dict__.setdefault('_joint_diagnostics', False)
+        # (... and before the joint work before the update did)
+        self.__dict__.setdefault('_joint_before', False)
         self._adopt()
 
 

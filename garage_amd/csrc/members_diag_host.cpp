@@ -40,30 +40,11 @@ struct TableLayout {
   }
 };
 
-// Takes a slot of `bytes`, lets `fill(host base)` write the tables, uploads them and runs
-// `launch(device base)`; the slot is marked done behind whatever was enqueued.
+// (a whole call through the ring: table_slots.h)
 template <class Fill, class Launch>
 int with_tables(const char* who, size_t bytes, hipStream_t stream, Fill&& fill,
                 Launch&& launch) {
-  std::lock_guard<std::mutex> lock(g_ring.mu);
-  GaTableSlot* slot = g_ring.take(bytes);
-  if (!slot) {
-    ga_set_error("%s: cannot allocate the member tables", who);
-    return GA_ERR_HIP;
-  }
-  memset(slot->host, 0, bytes);
-  fill(static_cast<char*>(slot->host));
-  int rc = GA_OK;
-  if (!GaTableRing::upload(slot, bytes, stream)) {
-    ga_set_error("%s: table upload failed", who);
-    rc = GA_ERR_HIP;
-  }
-  if (!rc) rc = launch(static_cast<char*>(slot->dev));
-  if (!GaTableRing::mark_done(slot, stream) && !rc) {
-    ga_set_error("%s: hipEventRecord failed", who);
-    rc = GA_ERR_HIP;
-  }
-  return rc;
+  return ga_with_tables(g_ring, who, bytes, stream, fill, launch);
 }
 
 int check_count(const char* who, const void* members, int64_t n, int64_t most) {
@@ -265,15 +246,29 @@ extern "C" int ga_mlp_forward_members_f32(const ga_mlp_desc* d, const ga_member_
 extern "C" int ga_ppo_loss_members_f32(const ga_members_loss_args* a,
                                        const ga_member_loss* members, int64_t n,
                                        double* partials, int64_t partials_doubles,
-                                       ga_stream_t stream_) {
-  const char* who = "ga_ppo_loss_members_f32";
+                                       ga_stream_t stream) {
+  GA_REQUIRE(a, "ga_ppo_loss_members_f32: null pointer");
+  GA_REQUIRE(a->algo == 0 || a->algo == 1, "ga_ppo_loss_members_f32: algo must be 0 or 1");
+  return ga_ppo_loss_ll_members_f32(a, members, nullptr, n, partials, partials_doubles,
+                                    stream);
+}
+
+// ll_out (optional): one pointer per entry, null: none -- the rows' new log-likelihoods,
+// which the row bodies write where the table entry names a place (loss_row_bodies.inc).
+// Takes algo 2 as well (TRPO's unclipped surrogate, as the lone entry points do: the rows'
+// objective is lr_objective's, loss_rows.h).
+extern "C" int ga_ppo_loss_ll_members_f32(const ga_members_loss_args* a,
+                                          const ga_member_loss* members,
+                                          float* const* ll_out, int64_t n, double* partials,
+                                          int64_t partials_doubles, ga_stream_t stream_) {
+  const char* who = ll_out ? "ga_ppo_loss_ll_members_f32" : "ga_ppo_loss_members_f32";
   hipStream_t stream = (hipStream_t)stream_;
   GA_REQUIRE(a, "%s: null pointer", who);
   int rc = check_count(who, members, n, 2 * MAX_MEMBERS);
   if (rc) return rc;
   GA_REQUIRE(a->kind == 0 || a->kind == 2, "%s: kind must be 0 (Gaussian) or 2 (categorical)",
              who);
-  GA_REQUIRE(a->algo == 0 || a->algo == 1, "%s: algo must be 0 or 1", who);
+  GA_REQUIRE(a->algo >= 0 && a->algo <= 2, "%s: algo must be 0, 1 or 2", who);
   GA_REQUIRE(a->A >= 1 && a->A <= 8, "%s: A must be 1 .. 8", who);
   const bool cat = a->kind == 2;
   std::vector<int64_t> rows;
@@ -319,6 +314,7 @@ extern "C" int ga_ppo_loss_members_f32(const ga_members_loss_args* a,
             p.double_softmax = a->double_softmax; p.algo = a->algo; p.clip = u.clip;
             p.ent = lr_ent(u.ent_coeff, a->ent_flags);
             p.partials = part; p.ent_sum_out = u.ent_sum_out;
+            p.ll_out = ll_out ? ll_out[m] : nullptr;
             p.loss_out = nb == 1 ? u.loss_out : nullptr;
             e.nb = nb;
             if (nb > 1) {
@@ -335,6 +331,7 @@ extern "C" int ga_ppo_loss_members_f32(const ga_members_loss_args* a,
             p.max_log_std = a->max_log_std; p.has_max = a->has_max; p.M = u.rows; p.A = a->A;
             p.algo = a->algo; p.clip = u.clip; p.ent = lr_ent(u.ent_coeff, a->ent_flags);
             p.partials = part;
+            p.ll_out = ll_out ? ll_out[m] : nullptr;
             p.loss_out = nb == 1 ? u.loss_out : nullptr;
             e.nb = nb;
             if (nb > 1) {

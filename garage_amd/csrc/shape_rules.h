@@ -38,6 +38,9 @@ constexpr int ga_red_blocks(int64_t n) {
   return n <= 256 ? 1 : ((n + 255) / 256 > RED_BLOCKS ? RED_BLOCKS : (int)((n + 255) / 256));
 }
 constexpr int LS_DOT_THREADS = 1024; // the one workgroup of the dot product
+// ---- members_advantage.hip: a member's advantages stay in LDS (4 bytes a step) between
+// the scan and the store; ga_red_blocks(MA_MAX_STEPS) = 128 partials at most
+constexpr int MA_MAX_STEPS = 32768;
 constexpr int FS_MAX_A = 32;         // classes of the categorical Fisher seed (in registers)
 // the head layer inside the loss kernel: 16 lanes own one row of the hidden activations
 constexpr int HL_THREADS = 256;

@@ -5,13 +5,16 @@
 // before the slot is rewritten -- RING calls later: the one place where such an entry point
 // may block its caller.  Written once for ga_update_epoch_members (update_members.cpp) and
 // the population entries of the linear feature baseline (linear_baseline_members_host.cpp);
-// each of them owns one ring and its mutex.  Host C++ only: the HIP runtime calls are the
+// each of them owns one ring and its mutex.  ga_with_tables is a whole call through a ring
+// (members_diag_host.cpp, members_advantage_host.cpp).  Host C++ only: the HIP runtime calls are the
 // ones tests/host/harness.h fakes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include <mutex>
+
+#include "common.h"
 
 struct GaTableSlot {
   void* host = nullptr;
@@ -101,3 +104,30 @@ struct GaTableRing {
     }
   }
 };
+
+// One call's tables through `ring`: takes a slot of `bytes`, lets `fill(host base)` write
+// the tables (into zeroed memory), uploads them and runs `launch(device base)`; the slot
+// is marked done behind whatever was enqueued.  `who` names the entry point in the errors.
+template <class Fill, class Launch>
+int ga_with_tables(GaTableRing& ring, const char* who, size_t bytes, hipStream_t stream,
+                   Fill&& fill, Launch&& launch) {
+  std::lock_guard<std::mutex> lock(ring.mu);
+  GaTableSlot* slot = ring.take(bytes);
+  if (!slot) {
+    ga_set_error("%s: cannot allocate the member tables", who);
+    return GA_ERR_HIP;
+  }
+  memset(slot->host, 0, bytes);
+  fill(static_cast<char*>(slot->host));
+  int rc = GA_OK;
+  if (!GaTableRing::upload(slot, bytes, stream)) {
+    ga_set_error("%s: table upload failed", who);
+    rc = GA_ERR_HIP;
+  }
+  if (!rc) rc = launch(static_cast<char*>(slot->dev));
+  if (!GaTableRing::mark_done(slot, stream) && !rc) {
+    ga_set_error("%s: hipEventRecord failed", who);
+    rc = GA_ERR_HIP;
+  }
+  return rc;
+}

@@ -1488,6 +1488,14 @@ GA_API int ga_ppo_loss_members_f32(const ga_members_loss_args* args,
                                    const ga_member_loss* members, int64_t n_members,
                                    double* partials, int64_t partials_doubles,
                                    ga_stream_t stream);
+/* ... and the rows' new log-likelihoods: ll_out, a HOST array of one device pointer per
+ * entry ([rows] floats; NULL: none for that entry, a NULL array: none at all), as the lone
+ * entry points' ll_out; algo may also be 2 (the unclipped surrogate of TRPO, as the lone
+ * entry points take it).  ga_ppo_loss_members_f32 is this call with a NULL array. */
+GA_API int ga_ppo_loss_ll_members_f32(const ga_members_loss_args* args,
+                                      const ga_member_loss* members, float* const* ll_out,
+                                      int64_t n_members, double* partials,
+                                      int64_t partials_doubles, ga_stream_t stream);
 /* ga_gaussian_nll_loss_f32 of every member, forward only.  1 .. 1024 members. */
 typedef struct ga_member_nll {
   const float* v; int64_t ldv; const float* returns; const float* log_std;
@@ -1518,6 +1526,39 @@ GA_API int ga_episode_stats_members_f32(const ga_member_episodes* members, int64
                                         int terminal, ga_stream_t stream);
 /* frees the pinned / device table slots of the entries above (tests) */
 GA_API void ga_members_diag_release(void);
+
+/* ---- the advantages of a POPULATION in one launch ------------------------------------
+ * What VPG._before_train runs per member between the value function and the old policy
+ * (vpg.py:147-166, 349-379): ga_gae_scan_f32 (mode 1: a row is one episode, no per-step
+ * bonus, no tail flags), then with center ga_stats_f32(0), ga_stats_f32(1) and
+ * ga_adv_center_f32(eps 1e-8), then with positive ga_stats_f32(2) and ga_sub_scalar_f32 --
+ * eight launches a member -- as ONE launch of one workgroup per member, which keeps the
+ * member's advantages in LDS between the scan and their one store: 16 bytes of HBM
+ * traffic per step.  adv, ret and stats of every member are, bit for bit, what those lone
+ * calls give on the member's arguments (the NaN of a one-sample batch included); stats
+ * gets [0] sum, [1] count, [2] squared deviations with center and [3] the minimum with
+ * positive, the other slots are left alone.  rewards, values, offsets, n_rows, T, ld and
+ * max_len are ga_gae_scan_f32's (with offsets T is the total step count S, without S =
+ * n_rows * T and adv / ret have the rows' layout); v0, the value beyond an episode's end,
+ * is read from DEVICE memory when the kernel runs (NULL: 0.0), so no host wait precedes
+ * the call.  The members array is a HOST array; the table goes through pinned memory as
+ * the diagnostics' tables do (a call may block on the call eight earlier; not graph-
+ * capture safe).  Refuses before any copy or launch (negative return, ga_last_error):
+ * null pointers, n_members outside 1 .. 1024, a member with S < 1 or S > 32768
+ * (MA_MAX_STEPS: the LDS of one workgroup), ld < T, max_len outside 1 .. T with offsets,
+ * stats that is not 8-byte aligned. */
+typedef struct ga_member_advantage {
+  const float* rewards; const float* values;  /* packed [S] or [n_rows, ld] */
+  const int64_t* offsets;                     /* n_rows + 1, or NULL */
+  int64_t n_rows, T, ld, max_len;             /* as ga_gae_scan_f32, mode 1 */
+  const float* v0;                            /* device scalar or NULL (0.0) */
+  float bonus_const;
+  float* adv; float* ret; double* stats;      /* stats: 4 doubles */
+} ga_member_advantage;
+GA_API int ga_advantages_members_f32(const ga_member_advantage* members,
+                                     int64_t n_members, int max_episode_length,
+                                     double discount, double gae_lambda, int center,
+                                     int positive, ga_stream_t stream);
 
 /* RCCL communicator for the data-parallel gradient all-reduce (new: the
  * reference has no collective on this path).

@@ -8,6 +8,8 @@ it, with a device synchronise before and after each of the five phases:
   rollout        the launches and progress checks of ``obtain_samples``
   packing        the joint pack (``--per-member-pack``: one ``_pack`` per member)
   before_train   every member's ``_before_train``, one after another
+                 (``--joint-before``: the joint launches and two host copies of
+                 ``PopulationPPO(joint_before=True)``)
   update         ``PopulationPPO._train``: the joint passes of both networks
   after_train    every member's ``_after_train``, one after another
                  (``--joint-diagnostics``: the joint launches and one host copy
@@ -57,6 +59,9 @@ def main():
     ap.add_argument('--joint-diagnostics', action='store_true',
                     help='PopulationPPO(joint_diagnostics=True): the members\' '
                          'diagnostics after the update in joint launches')
+    ap.add_argument('--joint-before', action='store_true',
+                    help='PopulationPPO(joint_before=True): the members\' work '
+                         'before the update in joint launches')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_iteration_phases needs an MI355X: there is '
@@ -66,7 +71,13 @@ def main():
     M = args.members
     env, members = make_members(M, args.minibatch,
                                 'joint' if args.linear_baseline else None)
-    pop = PopulationPPO(members, joint_diagnostics=args.joint_diagnostics)
+    from garage_amd import _lib
+    lib = _lib.load()
+
+    def counted():  # launches the library counts (prof.h: layer products, scans)
+        return sum(int(lib.ga_launch_count(k)) for k in range(16))
+    pop = PopulationPPO(members, joint_diagnostics=args.joint_diagnostics,
+                        joint_before=args.joint_before)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5,
                                    joint_pack=not args.per_member_pack)
@@ -102,7 +113,9 @@ def main():
         tick()
         batches = sampler.obtain_samples(itr, ENVS * STEPS, pop.member_params)
         sampled = tick()
+        n0 = counted()
         ctxs = pop._before_trains(batches)
+        before_launches = counted() - n0
         before = tick()
         pop._train(ctxs)
         update = tick()
@@ -119,7 +132,10 @@ def main():
             phase=k, members=M, minibatch=args.minibatch,
             joint_pack=not args.per_member_pack,
             linear_baseline=args.linear_baseline,
-            joint_diagnostics=args.joint_diagnostics, median_ms=float(np.median(v)),
+            joint_diagnostics=args.joint_diagnostics,
+            joint_before=args.joint_before,
+            counted_launches=before_launches if k == 'before_train' else None,
+            median_ms=float(np.median(v)),
             min_ms=float(v.min()), max_ms=float(v.max()),
             spread=float((v.max() - v.min()) / np.median(v)),
             share=float(np.median(v) / np.median(total)),
