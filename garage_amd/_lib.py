@@ -101,6 +101,28 @@ ENV_ACROBOT = 8
 ENV_MOUNTAIN_CAR = 10
 
 
+# The narrow step at 33 .. 128 inputs is opt-in at the C ABI (ga_set_narrow_wide);
+# the algorithms switch it on around their update calls.  False: they leave it off
+# (A/B runs of one process; GARAGE_AMD_NARROW_WIDE=0 does the same for a whole one).
+NARROW_WIDE = True
+
+
+def narrow_wide_scope(fn):
+    """Runs ``fn`` with ``ga_set_narrow_wide(NARROW_WIDE)`` and puts the library's
+    setting back afterwards."""
+    import functools
+
+    @functools.wraps(fn)
+    def scoped(*args, **kwargs):
+        lib = load()
+        was = lib.ga_set_narrow_wide(int(NARROW_WIDE))
+        try:
+            return fn(*args, **kwargs)
+        finally:
+            lib.ga_set_narrow_wide(was)
+    return scoped
+
+
 def env_ref(kind, env):
     """``ga_env_ref`` of kind ``kind`` to the ctypes env struct ``env`` (kept
     alive by the reference)."""
@@ -449,6 +471,8 @@ SIGNATURES = {
     'ga_update_partials_floats': (c_i64, [C.POINTER(MlpDesc), c_i64]),
     'ga_set_fused_train': (c_int, [c_int]),
     'ga_set_narrow_step': (c_int, [c_int]),
+    'ga_set_narrow_wide': (c_int, [c_int]),
+    'ga_narrow_wide_launches': (c_i64, []),
     'ga_set_fused_first_layer': (c_int, [c_int]),
     'ga_set_pipelined_kloop': (c_int, [c_int]),
     'ga_set_wgrad_paired_columns': (c_int, [c_int]),

@@ -18,6 +18,7 @@ from garage_amd import logger
 from garage_amd._dtypes import (DeviceEpisodeBatch, EpisodeStatistics,
                                 StepType, is_discrete, step_types_as_uint8)
 from garage_amd._lib import call, dptr, stream_ptr
+from garage_amd._lib import narrow_wide_scope as _narrow_wide_scope
 from garage_amd.engine import (HALF_LOG_2PI, center_advantages, gae_scan,
                                pad_rows, reduction_workspace, round4)
 from garage_amd.functions import (log_performance, log_performance_host,
@@ -702,6 +703,7 @@ class VPG:
         return (diff * diff).mean().reshape(1)
 
     # -- the update (vpg.py:230-293) -------------------------------------------
+    @_narrow_wide_scope
     def _train(self, batch, adv, returns, old_ll):
         S = batch.n_samples
         if self._linear_vf:
@@ -913,6 +915,7 @@ class VPG:
         return self._minibatch_step(self._vf_optimizer, self._value_function,
                                     1, batch, None, returns, None, idx)
 
+    @_narrow_wide_scope
     def _minibatch_step(self, opt, module, kind, batch, adv, returns, old_ll,
                         idx):
         """One step through the same entry point as the native epoch loop
@@ -1150,6 +1153,7 @@ class TRPO(VPG):
         self._trpo_share = 1.0  # this rank's share of the global batch
 
     # -- update (vpg.py:230-248 with the constrained policy step) ---------------
+    @_narrow_wide_scope
     def _train(self, batch, adv, returns, old_ll):
         import ctypes as C
         S = batch.n_samples
@@ -1549,7 +1553,7 @@ class PopulationPPO:
     reference counterpart: garage trains one learner per process.
 
     The members must share the algorithm, the networks' shapes (two equal tanh
-    hidden layers of 32 or 64 units, at most 32 inputs and 8 outputs), the head
+    hidden layers of 32 or 64 units, at most 128 inputs and 8 outputs), the head
     kind and its options, ``minibatch_size``, ``max_optimization_epochs``, the
     permutation mode, the entropy configuration and torch's default-shaped Adam
     with the same ``betas`` and ``eps``.  They may differ in ``lr``,
@@ -1588,6 +1592,10 @@ class PopulationPPO:
     ``entropy_method='max'`` is refused (its reward bonus is a host value per
     member, or per-step entropies), as is a member whose batch exceeds 32768
     steps.  Again every member is bit for bit the default path's.
+
+    Both switches take networks of at most 32 inputs (their joint forwards are
+    the per-layer kernels' twins); with wider observations, up to the 128 of the
+    default path, they raise a ``ValueError`` that names the switch.
     """
 
     MAX_JOINT_STEPS = 32768  # MA_MAX_STEPS: a member's advantages live in LDS
@@ -1648,6 +1656,7 @@ class PopulationPPO:
                   ('stop_entropy_gradient', bool(algo._stop_entropy_gradient))]
         return facts
 
+    @_narrow_wide_scope
     def _check_members(self):
         from garage_amd import _lib
         import ctypes as C
@@ -1693,7 +1702,7 @@ class PopulationPPO:
                         C.byref(mod.net._desc)):
                     raise ValueError(
                         '{}: the {} network {} is unsupported (two equal tanh '
-                        'hidden layers of 32 or 64 units, <= 32 inputs, <= 8 '
+                        'hidden layers of 32 or 64 units, <= 128 inputs, <= 8 '
                         'linear outputs, no layer normalization)'.format(
                             who, name, tuple(mod.net.dims)))
         if self._joint_diagnostics:
@@ -1868,6 +1877,7 @@ class PopulationPPO:
         a.partials, a.partials_floats = part.data_ptr(), part.numel()
         return a, arr, mods, opts
 
+    @_narrow_wide_scope
     def _train(self, ctxs):
         """The joint passes: per epoch one ``ga_update_epoch_members`` call for
         the policies, then one for the value functions (on two streams).  The
@@ -2510,7 +2520,9 @@ class PopulationTRPO(PopulationPPO):
             if not _lib.load().ga_members_natural_supported(
                     C.byref(algo.policy.net._desc)):
                 raise ValueError('member {}: the policy network {} is unsupported '
-                                 'by the joint natural-gradient step'.format(
+                                 'by the joint natural-gradient step of '
+                                 'PopulationTRPO (<= 32 inputs; PopulationPPO '
+                                 'takes up to 128)'.format(
                                      m, tuple(algo.policy.net.dims)))
         self._natural_ws = None
 

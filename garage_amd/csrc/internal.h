@@ -13,6 +13,24 @@
 // errors.cpp: sets the thread-local message ga_last_error() returns
 void ga_set_error(const char* fmt, ...);
 
+// The narrow step at 33 .. 128 inputs (shape_rules.h: ga_narrow_wide_supported) is opt-in
+// at the C ABI -- ga_set_narrow_wide(1), update.cpp -- so that ga_update_epoch*,
+// ga_update_partials_floats, ga_update_members_supported and
+// ga_update_members_partials_floats answer callers written against 32 inputs as they
+// always did; the Python algorithms switch it on around their calls.
+// GARAGE_AMD_NARROW_WIDE=0 in the environment (read once) keeps it off whatever is set.
+// One state for update.cpp and update_members.cpp, which are linked into different CPU
+// harnesses.
+#include <stdlib.h>
+inline int g_ga_narrow_wide = 0;
+inline int ga_narrow_wide_on() {
+  static const int vetoed = [] {
+    const char* e = getenv("GARAGE_AMD_NARROW_WIDE");
+    return (e && e[0] == '0') ? 1 : 0;
+  }();
+  return g_ga_narrow_wide && !vetoed;
+}
+
 // lnorm.hip: LayerNorm of the hidden-layer inputs (forward, backward, tangent)
 int ga_ln_forward(const float* X, int64_t ldx, const int32_t* idx, int64_t M, int D,
                   const float* gamma, const float* beta, float* Y, int64_t ldy,

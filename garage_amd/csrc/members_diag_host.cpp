@@ -18,6 +18,7 @@
 
 #include "internal.h"
 #include "members_diag.h"
+#include "shape_rules.h"
 #include "table_slots.h"
 
 namespace {
@@ -97,6 +98,13 @@ extern "C" int ga_mlp_forward_members_supported(const ga_mlp_desc* d) {
     ga_set_error("ga_mlp_forward_members_supported: unsupported network");
     return 0;
   }
+  if (d->dims[0] > NS_IN_OVERLAY) {
+    ga_set_error("ga_mlp_forward_members_supported: %d inputs: the joint launches of "
+                 "joint_diagnostics / joint_before take <= %d (the default PopulationPPO "
+                 "passes, ga_update_epoch_members, take up to %d)", d->dims[0], NS_IN_OVERLAY,
+                 NS_IN_MAX);
+    return 0;
+  }
   for (int64_t rows : {(int64_t)64, (int64_t)1}) {
     ga_mlp_desc dd = *d;
     dd.act_off[0] = 0;
@@ -131,7 +139,7 @@ extern "C" int ga_mlp_forward_members_f32(const ga_mlp_desc* d, const ga_member_
   GA_REQUIRE(d, "%s: null pointer", who);
   int rc = check_count(who, members, n, 2 * MAX_MEMBERS);
   if (rc) return rc;
-  GA_REQUIRE(ga_update_members_supported(d),
+  GA_REQUIRE(ga_update_members_supported(d) && d->dims[0] <= NS_IN_OVERLAY,
              "%s: unsupported network (two equal tanh hidden layers of 32 or 64 units, <= 32 "
              "inputs, <= 8 linear outputs, no layer norm)", who);
   const int L = d->n_layers;  // 3

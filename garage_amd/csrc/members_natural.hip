@@ -757,7 +757,7 @@ __global__ __launch_bounds__(CG_THREADS) void members_candidate_kernel(NaturalPa
 int ng_check(const GaNaturalShared* sh, const GaNaturalDev* table_dev, const char* who) {
   GA_REQUIRE(sh && table_dev, "%s: null pointer", who);
   const int dims[4] = {sh->in_w, sh->H, sh->H, sh->out_w};
-  GA_REQUIRE(ga_narrow_step_supported(3, dims) && sh->n_members >= 1 &&
+  GA_REQUIRE(ga_narrow_overlay_supported(3, dims) && sh->n_members >= 1 &&
                  sh->n_members <= 65535 && sh->n_flat >= 4 &&
                  sh->stride == ga_narrow_step_stride(sh->in_w, sh->H),
              "%s: unsupported shape", who);

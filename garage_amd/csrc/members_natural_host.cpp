@@ -32,7 +32,9 @@ GaTableRing g_ring;
 bool shape_ok(const ga_mlp_desc* d) {
   if (!d || d->n_layers != 3) return false;
   if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return false;
-  return ga_narrow_step_supported(3, d->dims) != 0;
+  // (the persistent kernels keep the first-layer weights where the overlay instantiations
+  // of the narrow step do: <= NS_IN_OVERLAY inputs)
+  return ga_narrow_overlay_supported(3, d->dims) != 0;
 }
 
 // The workspace, in floats from its start: the members' vectors [NG_VECS][n][round4(n_flat)],
@@ -72,7 +74,8 @@ int check_args(const ga_members_natural_args* a, Entry entry, const char* who) {
   const ga_mlp_desc* d = a->desc;
   GA_REQUIRE(shape_ok(d),
              "%s: unsupported network (two equal tanh hidden layers of 32 or 64 units, <= 32 "
-             "inputs, <= 8 linear outputs, no layer norm)", who);
+             "inputs, <= 8 linear outputs, no layer norm; PopulationPPO's passes, "
+             "ga_update_epoch_members, take up to 128 inputs)", who);
   GA_REQUIRE(a->kind == 0 || a->kind == 2,
              "%s: kind must be 0 (Gaussian) or 2 (categorical)", who);
   GA_REQUIRE(flat_ok(d, a->n_flat),

@@ -189,20 +189,21 @@ extern "C" int ga_members_train_step(const GaMembersShared* sh,
   q.sh = *sh; q.table = table_dev; q.k = (int)k;
   const dim3 grid((unsigned)max_tiles, (unsigned)sh->n_members);
   ga_prof_count(GA_PROF_MEMBERS_STEP);
+  const int ldx_s = ga_narrow_ldx(sh->in_w);
+  if (ldx_s > 36) ga_prof_count_narrow_wide();
 #define GA_MEMBERS_LAUNCH(HH, LL)                                                       \
   hipLaunchKernelGGL((narrow_train_members_kernel<HH, LL>), grid, dim3(NS_THREADS), 0, \
                      stream, q)
-  const int in_w = sh->in_w;
-  const int ldx_s = in_w <= 8 ? 12 : (in_w <= 16 ? 20 : 36);
-  if (sh->H == 64) {
-    if (ldx_s == 12) GA_MEMBERS_LAUNCH(64, 12);
-    else if (ldx_s == 20) GA_MEMBERS_LAUNCH(64, 20);
-    else GA_MEMBERS_LAUNCH(64, 36);
-  } else {
-    if (ldx_s == 12) GA_MEMBERS_LAUNCH(32, 12);
-    else if (ldx_s == 20) GA_MEMBERS_LAUNCH(32, 20);
-    else GA_MEMBERS_LAUNCH(32, 36);
+#define GA_MEMBERS_LAUNCH_H(HH)                    \
+  switch (ldx_s) {                                 \
+    case 12: GA_MEMBERS_LAUNCH(HH, 12); break;     \
+    case 20: GA_MEMBERS_LAUNCH(HH, 20); break;     \
+    case 36: GA_MEMBERS_LAUNCH(HH, 36); break;     \
+    case 68: GA_MEMBERS_LAUNCH(HH, 68); break;     \
+    default: GA_MEMBERS_LAUNCH(HH, 132); break;    \
   }
+  if (sh->H == 64) GA_MEMBERS_LAUNCH_H(64) else GA_MEMBERS_LAUNCH_H(32)
+#undef GA_MEMBERS_LAUNCH_H
 #undef GA_MEMBERS_LAUNCH
   GA_CHECK_LAUNCH("narrow_train_members");
   return GA_OK;

@@ -83,10 +83,40 @@ __device__ __forceinline__ ns_f32x16 ns_tile(const float* A, int lda, const floa
   return acc0;
 }
 
-// NS_LDX = floats per staged observation / first-layer weight row: round8(in_w) + 4
-// (12, 20 or 36).  At 12 and 20 the workgroup stays under 80 KB of LDS, so a
-// workgroup of the policy pass and one of the value-function pass (two streams)
-// share a CU.
+// NS_LDX = floats per staged observation / first-layer weight row (ga_narrow_ldx,
+// shape_rules.h): round8(in_w) + 4 up to 32 inputs (12, 20 or 36).  At 12 and 20 the
+// workgroup stays under 80 KB of LDS, so a workgroup of the policy pass and one of the
+// value-function pass (two streams) share a CU.
+//
+// The WIDE instantiations, NS_LDX = 68 and 132 (33 .. 64 and 65 .. 128 inputs).  What
+// was decided, and why:
+//  * X and W1 both stay RESIDENT in LDS, whole, for the whole step; nothing streams in
+//    k-chunks.  The observation tile is read twice (P1, P9) and is the expensive operand
+//    to fetch (64 gathered rows through the minibatch's index), so it has to stay in any
+//    case; W1 beside it brings the workgroup to 143904 B at H = 64, in_w > 64 (111136 B
+//    at NS_LDX = 68; H = 32: 88352 and 63776 B), inside the CU's 160 KB.  A 32-column
+//    k-chunk is 16 MFMAs a wave, a fraction of one global load's latency: a
+//    double-buffered chunk loop would expose that latency once per chunk, while P0 as
+//    it stands has every 16-byte load of X, W1, W2 and the head in flight at once and
+//    waits once.  So the first-layer product is ns_tile over the whole zero-padded
+//    K1 = round8(in_w), as below 33.  (Reasoned from the instruction counts; no
+//    streaming variant was built to measure against.)
+//  * W1 no longer fits over dZ2 (it is up to 2 x dZ2), so it gets LDS of its own BEHIND
+//    the dZ2 / head-plane scratch; the planes then share dZ2's floats alone.  Rows are
+//    padded to every column of the 32-column tiles P9 reads (64 or 128, + 4 floats:
+//    the row stride stays 4 banks off a multiple of 32, as at 36).
+//  * dW1 = dZ1^T X, now the largest gradient region ([H][round4(in_w)], 32 KB), is
+//    produced on the matrix cores in P9: one 32 x 32 tile per wave and turn
+//    (H / 32 x ceil(ld0 / 32) tiles, at most two turns), K = the 64 rows, and each
+//    [32][32] block goes from the accumulators straight to the tile's share -- no sum
+//    is carried from one block to the next and no LDS is written.  (The VALU loop of the
+//    overlay instantiations would take 2048 FMAs and as many LDS quads per thread here.)
+//  * Occupancy: one workgroup per CU (two at H = 32, NS_LDX = 68), which NS_LDX = 36
+//    already is at H = 64 (85536 B).  What the <= 20-float instantiations keep and
+//    these give up is a policy workgroup and a value-function workgroup on ONE CU; a
+//    minibatch is one to four tiles on 256 CUs, so the two chains' workgroups still
+//    run side by side, on different CUs.
+// P2 .. P8 are the same code at every NS_LDX.
 // Both kernels launch it under __launch_bounds__(NS_THREADS, NS_LDX <= 20 ? 2 : 1)
 // (2 waves per SIMD where the LDS tiles allow two workgroups per CU: one of each
 // network's chain -- without the bound the compiler takes 254 + 64 registers and
@@ -100,10 +130,15 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
   constexpr int QW = H / 4;         // hidden columns per wave in the VALU phases
   // dz2 is written in P5; until then its memory holds the first-layer weights (read
   // in P1 only) and the four planes of the head's partial sums (P3)
+  // (WIDE: the first-layer weights lie behind dz2 and the planes, which share floats)
+  constexpr bool WIDE = NS_LDX > NS_IN_OVERLAY + 4;
   constexpr int DZ2_FLOATS = NS_ROWS * LDH;
   constexpr int W1_FLOATS = H * NS_LDX, PLANES_FLOATS = 4 * NS_ROWS * NS_HN;
-  constexpr int SCRATCH = DZ2_FLOATS > W1_FLOATS + PLANES_FLOATS
-                              ? DZ2_FLOATS : W1_FLOATS + PLANES_FLOATS;
+  constexpr int W1_AT = !WIDE ? 0 : (DZ2_FLOATS > PLANES_FLOATS ? DZ2_FLOATS : PLANES_FLOATS);
+  constexpr int PLANES_AT = WIDE ? 0 : W1_FLOATS;
+  constexpr int SCRATCH = WIDE ? W1_AT + W1_FLOATS
+                               : (DZ2_FLOATS > W1_FLOATS + PLANES_FLOATS
+                                      ? DZ2_FLOATS : W1_FLOATS + PLANES_FLOATS);
   __shared__ __attribute__((aligned(16))) float xs[NS_ROWS * NS_LDX];
   __shared__ __attribute__((aligned(16))) float w2s[H * LDH];
   __shared__ __attribute__((aligned(16))) float whs[NS_HN * H];
@@ -114,8 +149,8 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
   __shared__ __attribute__((aligned(16))) float doutl[NS_ROWS * NS_HN];
   __shared__ float b1s[H], b2s[H], bhs[NS_HN];
   float* dz2 = scratch;
-  float* w1s = scratch;
-  float* planes = scratch + W1_FLOATS;
+  float* w1s = scratch + W1_AT;
+  float* planes = scratch + PLANES_AT;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, l31 = lane & 31, half = lane >> 5;
@@ -375,7 +410,24 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
   __syncthreads();
   NS_STAMP(7);
   // ---- P9: dW1[n][k] = sum_r dZ1[r][n] X[r][k], db1
-  {
+  if constexpr (WIDE) {
+    // (CT x ceil(ld0 / 32) tiles on the matrix cores, each stored from its accumulators;
+    // xs is staged, zero padded, up to column NS_LDX - 4 >= 32 ceil(ld0 / 32))
+    const int KT = (ld0 + 31) >> 5;
+    for (int t = wave; t < CT * KT; t += 4) {
+      const int tn = t / KT, tk = t % KT;
+      const ns_f32x16 acc = ns_tile<false, false>(h2 + 32 * tn, LDH, xs + 32 * tk, NS_LDX,
+                                                  NS_ROWS, lane);
+      const int k = 32 * tk + l31;
+      if (k < ld0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int n = 32 * tn + (r & 3) + 8 * (r >> 2) + 4 * half;
+          pW1[(int64_t)n * ld0 + k] = acc[r];
+        }
+      }
+    }
+  } else {
     constexpr int GROUPS = NS_THREADS / H;
     const int n = tid % H, g0 = tid / H;
     for (int q = g0; 4 * q < ld0; q += GROUPS) {
@@ -388,12 +440,12 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
       }
       *reinterpret_cast<float4*>(pW1 + (int64_t)n * ld0 + 4 * q) = g;
     }
-    if (tid >= NS_THREADS - H) {
-      const int nn = tid - (NS_THREADS - H);
-      float b = 0.f;
-      for (int r = 0; r < NS_ROWS; ++r) b += h2[r * LDH + nn];
-      pb1[nn] = b;
-    }
+  }
+  if (tid >= NS_THREADS - H) {
+    const int nn = tid - (NS_THREADS - H);
+    float b = 0.f;
+    for (int r = 0; r < NS_ROWS; ++r) b += h2[r * LDH + nn];
+    pb1[nn] = b;
   }
   __syncthreads();
   NS_STAMP(8);

@@ -1,7 +1,9 @@
 // One optimizer step's forward + loss + backward of a NARROW network in one launch
-// (gfx950): two tanh hidden layers of equal width H = 32 or 64, <= 32 inputs,
+// (gfx950): two tanh hidden layers of equal width H = 32 or 64, <= 128 inputs,
 // <= 8 outputs -- the CartPole-class networks of BASELINE.json configs[0-1]
-// (MLP(32,32), MLP(64,64)) at minibatches of any size.
+// (MLP(32,32), MLP(64,64)) at minibatches of any size, and the same networks on
+// observations up to 128 wide (one-hot grids, multi-task points: the wide
+// instantiations of narrow_body.h).
 //
 // At these widths every weight of the network fits in LDS many times over (18 KB at
 // H = 64), so a workgroup takes 64 rows of the minibatch through the WHOLE step --
@@ -90,20 +92,22 @@ extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
   const double flops =
       6.0 * (double)M * ((double)in_w * H + (double)H * H + (double)H * out_w);
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  const int ldx_s = ga_narrow_ldx(in_w);
   ga_prof_events(GA_PROF_NARROW_STEP, flops, &e0, &e1);
+  if (ldx_s > 36) ga_prof_count_narrow_wide();
 #define GA_NARROW_LAUNCH(HH, LL)                                                      \
   hipExtLaunchKernelGGL((narrow_train_kernel<HH, LL>), grid, dim3(NS_THREADS), 0, stream, \
                         e0, e1, 0, p)
-  const int ldx_s = in_w <= 8 ? 12 : (in_w <= 16 ? 20 : 36);
-  if (H == 64) {
-    if (ldx_s == 12) GA_NARROW_LAUNCH(64, 12);
-    else if (ldx_s == 20) GA_NARROW_LAUNCH(64, 20);
-    else GA_NARROW_LAUNCH(64, 36);
-  } else {
-    if (ldx_s == 12) GA_NARROW_LAUNCH(32, 12);
-    else if (ldx_s == 20) GA_NARROW_LAUNCH(32, 20);
-    else GA_NARROW_LAUNCH(32, 36);
+#define GA_NARROW_LAUNCH_H(HH)                    \
+  switch (ldx_s) {                                \
+    case 12: GA_NARROW_LAUNCH(HH, 12); break;     \
+    case 20: GA_NARROW_LAUNCH(HH, 20); break;     \
+    case 36: GA_NARROW_LAUNCH(HH, 36); break;     \
+    case 68: GA_NARROW_LAUNCH(HH, 68); break;     \
+    default: GA_NARROW_LAUNCH(HH, 132); break;    \
   }
+  if (H == 64) GA_NARROW_LAUNCH_H(64) else GA_NARROW_LAUNCH_H(32)
+#undef GA_NARROW_LAUNCH_H
 #undef GA_NARROW_LAUNCH
   GA_CHECK_LAUNCH("narrow_train");
   return GA_OK;

@@ -54,6 +54,10 @@ void ga_prof_count(int kind) {
   if (kind >= 0 && kind < GA_PROF_KINDS) ++g_launches[kind];
 }
 
+static int64_t g_narrow_wide = 0;
+void ga_prof_count_narrow_wide() { ++g_narrow_wide; }
+extern "C" int64_t ga_narrow_wide_launches(void) { return g_narrow_wide; }
+
 extern "C" int64_t ga_launch_count(int kind) {
   return (kind >= 0 && kind < GA_PROF_KINDS) ? g_launches[kind] : -1;
 }

@@ -36,3 +36,7 @@ enum GaProfKind {
 void ga_prof_events(int kind, double work, hipEvent_t* start, hipEvent_t* stop);
 // Counts a launch of `kind` without timing it (ga_launch_count).
 void ga_prof_count(int kind);
+// Counts a launch of a wide instantiation of the narrow step (33 .. 128 inputs:
+// narrow_train_kernel / narrow_train_members_kernel<H, 68 | 132>), beside the launch's
+// own kind (ga_narrow_wide_launches).
+void ga_prof_count_narrow_wide();

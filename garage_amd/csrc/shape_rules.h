@@ -16,6 +16,8 @@ constexpr int FT_W1_FLOATS = 5120;   // LDS floats for the first layer's weights
 // ---- narrow_body.h: two hidden layers of equal width 32 or 64
 constexpr int NS_ROWS = FT_ROWS;     // (its launches size their grids by ga_fused_tiles)
 constexpr int NS_HN = 8;             // head outputs, at most
+constexpr int NS_IN_OVERLAY = 32;    // inputs, at most, of the overlay instantiations
+constexpr int NS_IN_MAX = 128;       // inputs, at most (the wide instantiations)
 // ---- members_natural.hip: a member's rows are split among at most NG_SHARES persistent
 // workgroups (one gradient share each), a function of the member's row count alone
 constexpr int NG_SHARES = 16;
@@ -115,9 +117,33 @@ inline int ga_fused_first_layer_ok(int in_w, int K) {
 inline int ga_fused_pair_supported(int width, int K, int in_w) {
   return width == 256 && K <= 256 && ga_fused_first_layer_ok(in_w, K);
 }
-inline int ga_narrow_step_supported(int n_layers, const int* dims) {
+// the narrow step's envelope but for the input width: two equal hidden layers of 32 or
+// 64 units, a head of at most NS_HN outputs
+inline int ga_narrow_envelope(int n_layers, const int* dims) {
   return n_layers == 3 && dims[1] == dims[2] && (dims[1] == 32 || dims[1] == 64) &&
-         dims[0] >= 1 && dims[0] <= 32 && dims[3] >= 1 && dims[3] <= NS_HN;
+         dims[3] >= 1 && dims[3] <= NS_HN;
+}
+// up to NS_IN_OVERLAY inputs: the first-layer weights overlay the dZ2 scratch in LDS
+// (narrow_body.h) -- also all that the population's natural-gradient step, joint
+// diagnostics and joint work before the update take
+inline int ga_narrow_overlay_supported(int n_layers, const int* dims) {
+  return ga_narrow_envelope(n_layers, dims) && dims[0] >= 1 && dims[0] <= NS_IN_OVERLAY;
+}
+// NS_IN_OVERLAY + 1 .. NS_IN_MAX inputs: the wide instantiations of the narrow step
+// (first-layer weights in LDS of their own, dW1 on the matrix cores: narrow_body.h)
+inline int ga_narrow_wide_supported(int n_layers, const int* dims) {
+  return ga_narrow_envelope(n_layers, dims) && dims[0] > NS_IN_OVERLAY &&
+         dims[0] <= NS_IN_MAX;
+}
+inline int ga_narrow_step_supported(int n_layers, const int* dims) {
+  return ga_narrow_overlay_supported(n_layers, dims) ||
+         ga_narrow_wide_supported(n_layers, dims);
+}
+// floats per staged observation / first-layer weight row of the instantiation that
+// takes in_w inputs: round8(in_w) + 4 up to 32 inputs (8, 16, 32), then every column
+// of the 32-column tiles the wide backward reads (64, 128) + 4
+inline int ga_narrow_ldx(int in_w) {
+  return in_w <= 8 ? 12 : in_w <= 16 ? 20 : in_w <= 32 ? 36 : in_w <= 64 ? 68 : 132;
 }
 // floats of one tile's gradient shares: dW1 [H][round4(in_w)], db1, dW2 [H][H], db2,
 // dW_head [8][H], db_head [8]

@@ -72,6 +72,15 @@ extern "C" int ga_set_narrow_step(int on) {
   return 0;
 }
 
+// The narrow step at 33 .. 128 inputs (ga_narrow_wide_supported: the wide instantiations
+// of narrow_body.h): off until asked for (internal.h: ga_narrow_wide_on); returns the
+// previous setting, so that a caller can put it back.
+extern "C" int ga_set_narrow_wide(int on) {
+  const int was = g_ga_narrow_wide;
+  g_ga_narrow_wide = on != 0;
+  return was;
+}
+
 // The first layer's forward inside the fused last-hidden-layer kernel (3-layer
 // networks with <= 32 inputs); 0 = its own streaming launch (A/B runs, tests)
 // (GARAGE_AMD_FUSED_FIRST_LAYER=0 in the environment: the same, for A/B runs of
@@ -143,7 +152,8 @@ FusedPlan fused_plan(const ga_mlp_desc* d, int64_t M) {
   if (L < 2 || L > 8 || M < 1) return f;
   // the fused kernels implement tanh hidden layers and a linear output layer
   if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return f;
-  if (g_narrow_step && ga_narrow_step_supported(L, d->dims)) {
+  if (g_narrow_step && ga_narrow_step_supported(L, d->dims) &&
+      (ga_narrow_wide_on() || !ga_narrow_wide_supported(L, d->dims))) {
     f.ok = f.narrow = true;
     f.tiles = ga_fused_tiles(M);
     f.hstride = ga_narrow_step_stride(d->dims[0], d->dims[1]);

@@ -26,7 +26,8 @@ constexpr int64_t ROWS_LIMIT = 1ll << 31;
 int64_t r4(int64_t v) { return (v + 3) & ~(int64_t)3; }
 
 // floats of one member's share of `partials`: [tiles][2] doubles of loss sums, then
-// [tiles][ga_narrow_step_stride] gradient shares (update.cpp's narrow layout)
+// [tiles][ga_narrow_step_stride] gradient shares (update.cpp's narrow layout; the
+// stride grows with round4(in_w), up to NS_IN_MAX inputs: shape_rules.h)
 int64_t member_floats(const ga_mlp_desc* d, int64_t max_rows) {
   const int64_t tiles = ga_fused_tiles(max_rows);
   return 4 * tiles + tiles * ga_narrow_step_stride(d->dims[0], d->dims[1]);
@@ -46,7 +47,8 @@ int check_args(const ga_update_members_args* a) {
   const ga_mlp_desc* d = a->desc;
   GA_REQUIRE(ga_update_members_supported(d),
              "ga_update_epoch_members: unsupported network (two equal tanh hidden layers "
-             "of 32 or 64 units, <= 32 inputs, <= 8 linear outputs, no layer norm)");
+             "of 32 or 64 units, <= %d inputs, <= 8 linear outputs, no layer norm)",
+             ga_narrow_wide_on() ? NS_IN_MAX : NS_IN_OVERLAY);
   GA_REQUIRE(a->kind >= 0 && a->kind <= 2, "ga_update_epoch_members: kind must be 0 .. 2");
   GA_REQUIRE(a->algo == 0 || a->algo == 1, "ga_update_epoch_members: algo must be 0 or 1");
   GA_REQUIRE(a->mb >= 0 && a->mb < ROWS_LIMIT, "ga_update_epoch_members: bad mb");
@@ -100,7 +102,9 @@ int check_args(const ga_update_members_args* a) {
 extern "C" int ga_update_members_supported(const ga_mlp_desc* d) {
   if (!d || d->n_layers != 3) return 0;
   if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return 0;
-  return ga_narrow_step_supported(3, d->dims) ? 1 : 0;
+  // (33 .. 128 inputs: where the caller has asked for them, ga_set_narrow_wide)
+  if (ga_narrow_wide_supported(3, d->dims)) return ga_narrow_wide_on();
+  return ga_narrow_overlay_supported(3, d->dims) ? 1 : 0;
 }
 
 extern "C" int64_t ga_update_members_partials_floats(const ga_mlp_desc* d, int64_t n_members,

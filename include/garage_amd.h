@@ -1235,10 +1235,22 @@ GA_API int64_t ga_update_partials_floats(const ga_mlp_desc* desc, int64_t M);
  * per-layer kernels (0 selects those): results agree to rounding. */
 GA_API int ga_set_fused_train(int on);
 /* 1 (default): networks of two equal tanh hidden layers of 32 or 64 units (<= 32
- * inputs, <= 8 outputs) take forward + loss + backward of a minibatch in ONE launch
+ * inputs, <= 8 outputs; <= 128 inputs under ga_set_narrow_wide(1)) take forward + loss + backward of a minibatch in ONE launch
  * (every weight in LDS, 64 rows per workgroup) followed by the same reduction +
  * Adam launch; 0: the kernels above.  Needs `partials` like them. */
 GA_API int ga_set_narrow_step(int on);
+/* Such networks with 33 .. 128 inputs: 0 (default at this ABI) they take the kernels
+ * above, as every caller written against the 32-input limit expects, and
+ * ga_update_members_supported refuses them; 1: the narrow step's wide instantiations take
+ * them in ga_update_epoch* and ga_update_epoch_members, and ga_update_partials_floats /
+ * ga_update_members_* answer accordingly.  The Python algorithms set 1 around their calls.
+ * GARAGE_AMD_NARROW_WIDE=0 in the environment (read once) keeps it 0 whatever is set.
+ * Returns the previous setting. */
+GA_API int ga_set_narrow_wide(int on);
+/* Launches of the narrow step's instantiations for 33 .. 128 inputs since the library was
+ * loaded, lone (ga_launch_count(11) counts the narrow step whichever instantiation takes
+ * it) and of a population (ga_launch_count(15)). */
+GA_API int64_t ga_narrow_wide_launches(void);
 /* 1 (default): with two hidden layers and <= 32 inputs (first-layer weights of at
  * most 5120 padded floats) the fused last-hidden-layer kernel computes the first
  * layer's outputs itself, k-chunk by k-chunk, instead of reading them back from a
@@ -1333,8 +1345,10 @@ typedef struct ga_update_members_args {
   double* workspace;
 } ga_update_members_args;
 /* 1: networks ga_update_epoch_members takes -- two equal tanh hidden layers of 32 or 64
- * units, <= 32 inputs, <= 8 linear outputs, no layer normalisation (the narrow step's
- * shapes); 0 otherwise, NULL included. */
+ * units, <= 32 inputs (<= 128 under ga_set_narrow_wide(1)), <= 8 linear outputs, no layer
+ * normalisation (the narrow step's shapes); 0 otherwise, NULL included.  The joint diagnostics, the joint work before the
+ * update and the natural-gradient step (ga_mlp_forward_members_supported,
+ * ga_members_natural_supported) stop at 32 inputs. */
 GA_API int ga_update_members_supported(const ga_mlp_desc* desc);
 /* Floats of `partials` for n_members members with minibatches of up to max_rows rows;
  * 0: unsupported network or sizes out of range. */

@@ -18,12 +18,20 @@ batches and from the same initial state, for
 and (c)): the update is then the policies' passes around the closed-form fit, and
 no value-function pass at all.
 
+``--obs-dim D``: the members act in a ``SyntheticVecEnv`` of ``D``-wide observations
+(two discrete actions, episodes of 128 steps) instead of CartPole.  Above 32 inputs the
+small step does not apply and (c) becomes the path such a learner took before the
+narrow step's wide instantiations existed: ``_lib.NARROW_WIDE = False``, the per-layer
+launches (reported as ``lone_per_layer_ms``), so that (b) against (c) is the lone
+default against its predecessor and (a) against (c) the population against lone updates
+without the wide step.
+
 A, B and C take turns inside one process; after warm-up every repeat is timed with HIP
 events around the update and the medians, their ratio and the run-to-run spread
 ((max - min) / median over the repeats) are printed, one JSON line per row.
 
     python tools/population_update_rate.py [--members 1 8 64] [--repeats 10]
-                                           [--linear-baseline]
+                                           [--linear-baseline] [--obs-dim D]
 """
 import argparse
 import json
@@ -40,17 +48,21 @@ if ROOT not in sys.path:
 ENVS, STEPS, EPOCHS = 64, 128, 10
 
 
-def make_members(M, minibatch, linear=None):
-    """``linear``: None -- MLP(64, 64) value functions; 'joint' -- the members of
+def make_members(M, minibatch, linear=None, obs_dim=None):
+    """``obs_dim``: None -- CartPole; D -- synthetic D-wide observations.
+    ``linear``: None -- MLP(64, 64) value functions; 'joint' -- the members of
     one LinearFeatureBaselinePopulation; 'lone' -- lone LinearFeatureBaselines."""
     from garage_amd.algos import PPO
     from garage_amd.baselines import (LinearFeatureBaseline,
                                       LinearFeatureBaselinePopulation)
-    from garage_amd.envs import CartPoleVecEnv
+    from garage_amd.envs import CartPoleVecEnv, SyntheticVecEnv
     from garage_amd.optimizers import OptimizerWrapper
     from garage_amd.policies import (CategoricalMLPPolicy,
                                      GaussianMLPValueFunction)
-    env = CartPoleVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
+    if obs_dim is None:
+        env = CartPoleVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
+    else:
+        env = SyntheticVecEnv(M * ENVS, obs_dim, 2, STEPS, discrete=True, seed=3)
     joint = LinearFeatureBaselinePopulation(env.spec, M) if linear == 'joint' \
         else None
     members = []
@@ -85,14 +97,21 @@ def timed(fn):
     return start.elapsed_time(stop)
 
 
-def measure(M, minibatch, repeats, warmup, linear=False):
+def measure(M, minibatch, repeats, warmup, linear=False, obs_dim=None):
     from garage_amd import _lib
     from garage_amd.algos import PopulationPPO
     from garage_amd.sampler import GpuPopulationSampler
     lib = _lib.load()
-    env, members = make_members(M, minibatch, 'joint' if linear else None)
-    _, lones = make_members(M, minibatch, 'lone' if linear else None)
-    _, narrows = make_members(M, minibatch, 'lone' if linear else None)
+    env, members = make_members(M, minibatch, 'joint' if linear else None, obs_dim)
+    _, lones = make_members(M, minibatch, 'lone' if linear else None, obs_dim)
+    _, narrows = make_members(M, minibatch, 'lone' if linear else None, obs_dim)
+    # (c): the lone narrow path up to 32 inputs, the per-layer path above
+    wide = obs_dim is not None and obs_dim > 32
+    def switch_c(on):
+        if wide:
+            _lib.NARROW_WIDE = bool(on)
+        else:
+            lib.ga_set_small_step(on)
     pop = PopulationPPO(members)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5)
@@ -109,12 +128,12 @@ def measure(M, minibatch, repeats, warmup, linear=False):
             a._train(c.batch, c.adv, c.returns, c.old_ll)
 
     def run_c():
-        lib.ga_set_small_step(0)
+        switch_c(0)
         try:
             for a, c in zip(narrows, narrow):
                 a._train(c.batch, c.adv, c.returns, c.old_ll)
         finally:
-            lib.ga_set_small_step(1)
+            switch_c(1)
 
     for _ in range(warmup):
         run_a()
@@ -130,16 +149,21 @@ def measure(M, minibatch, repeats, warmup, linear=False):
     def spread(t):
         return float((t.max() - t.min()) / np.median(t))
 
-    return dict(
+    c_name = 'lone_per_layer' if wide else 'lone_narrow'
+    row = dict(
         members=M, minibatch=minibatch, linear_baseline=bool(linear),
         samples_per_member=[int(c.S) for c in joint][:4],
         population_ms=float(np.median(ta)), lone_ms=float(np.median(tb)),
-        lone_narrow_ms=float(np.median(tc)),
         lone_over_population=float(np.median(tb) / np.median(ta)),
-        lone_narrow_over_population=float(np.median(tc) / np.median(ta)),
         population_spread=spread(ta), lone_spread=spread(tb),
-        lone_narrow_spread=spread(tc),
         repeats=repeats)
+    row[c_name + '_ms'] = float(np.median(tc))
+    row[c_name + '_over_population'] = float(np.median(tc) / np.median(ta))
+    row[c_name + '_spread'] = spread(tc)
+    if obs_dim is not None:
+        row['obs_dim'] = obs_dim
+        row[c_name + '_over_lone'] = float(np.median(tc) / np.median(tb))
+    return row
 
 
 def main():
@@ -154,6 +178,9 @@ def main():
                     help='LinearFeatureBaseline value functions: one '
                          'LinearFeatureBaselinePopulation in (a), lone ones in '
                          '(b) and (c)')
+    ap.add_argument('--obs-dim', type=int, default=None,
+                    help='synthetic observations of this width instead of CartPole; '
+                         'above 32, (c) is the per-layer path (_lib.NARROW_WIDE off)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_update_rate needs an MI355X: there is nothing '
@@ -163,7 +190,7 @@ def main():
     for minibatch in args.minibatches:
         for M in args.members:
             print(json.dumps(measure(M, minibatch, args.repeats, args.warmup,
-                                     args.linear_baseline)),
+                                     args.linear_baseline, args.obs_dim)),
                   flush=True)
 
 
