@@ -2512,6 +2512,7 @@ class PopulationTRPO(PopulationPPO):
             ('max_backtracks', int(h['max_backtracks'])),
             ('accept_violation', bool(h['accept_violation']))]
 
+    @_narrow_wide_scope
     def _check_members(self):
         from garage_amd import _lib
         import ctypes as C
@@ -2521,8 +2522,9 @@ class PopulationTRPO(PopulationPPO):
                     C.byref(algo.policy.net._desc)):
                 raise ValueError('member {}: the policy network {} is unsupported '
                                  'by the joint natural-gradient step of '
-                                 'PopulationTRPO (<= 32 inputs; PopulationPPO '
-                                 'takes up to 128)'.format(
+                                 'PopulationTRPO (two equal tanh hidden layers of '
+                                 '32 or 64 units, <= 128 inputs, <= 8 linear '
+                                 'outputs)'.format(
                                      m, tuple(algo.policy.net.dims)))
         self._natural_ws = None
 

@@ -12,6 +12,10 @@
 //       written once, when the run is finished: at most NG_SHARES shares per member
 //       whatever its row count.  The run of a workgroup is a function of the member's row
 //       count alone, so a member gets the same bits whatever the population around it.
+//   narrow_natural_wide_kernel<H, NS_LDX, MODE>   the same pass at 33 .. 128 inputs
+//       (NS_LDX = 68, 132): the same grid, run and shares on 32-row tiles, with the
+//       tangent's accumulations on waves of their own and dW1 in MFMA accumulators (its
+//       layout is stated above it).
 //   members_cg_kernel   one workgroup per member: sums the member's shares in share order
 //       and advances its conjugate-gradient recurrence (dots in fp64, fixed order; the
 //       scalars stay on the device), or finishes the step direction and its length.
@@ -569,6 +573,487 @@ __global__ __launch_bounds__(NS_THREADS, 1) void narrow_natural_members_kernel(
   }
 }
 
+// ---- the WIDE instantiations: NS_LDX = 68 and 132 (33 .. 64 and 65 .. 128 inputs) ----
+// The kernel above does not stretch: a product at H = 64 would need 168 000 B of LDS at
+// NS_LDX = 68 and 217 152 B at 132, and its per-thread dW1 shares 32 registers and 64 x 8
+// LDS quads per tile and thread.  narrow_natural_wide_kernel keeps the contract (grid,
+// staging once, one share per workgroup, a run that is a function of S alone: the same
+// 64-row tiles, walked as two halves) with a layout of its own:
+//  * 32-ROW tiles in every mode.  Resident: W1, W2, the head and the biases, and for a
+//    product V1, V2, the tangent's head and biases.  Per tile: X [32][NS_LDX], H1, H2
+//    (later dZ1), dZ2 (T1 until P2 is done) and for a product T2, each [32][H + 4], and
+//    the head buffers [32][8].  NaturalWideLds states the sum: 162 368 B at most.
+//  * 32 rows are ONE row block of the 32 x 32 MFMA tiles, so a hidden layer has H / 32
+//    output tiles for four waves.  In P1 and P2 of a product waves 0, 1 take the primal
+//    accumulations and waves 2, 3 the tangent's.  The tangent waves store the
+//    pre-activation's tangent U (without the (1 - h^2) factor, whose h the other waves
+//    are still computing); the factor is applied where U is read next, after the barrier:
+//    in P2's A operand (ng_tile_tangent) for T1, in P3 for T2.
+//  * dW1 [H][<= 128] is H / 32 x NS_LDX / 32 tiles of dZ1^T X on the matrix cores, kept
+//    in MFMA accumulators across the run (at most two a wave) like dW2, and scattered
+//    into the share's [H][round4(in_w)] once.  X is staged zero padded up to column
+//    NS_LDX - 4, so the columns in_w .. round4(in_w) are exact zeros and no column past
+//    them is stored.
+constexpr int NW_ROWS = 32;
+
+template <int H, int NS_LDX, int MODE>
+struct NaturalWideLds {
+  static constexpr int LDH = H + 4;
+  static constexpr int TILE = NW_ROWS * LDH;
+  static constexpr int HEAD = NW_ROWS * NS_HN;
+  static constexpr int WEIGHTS = H * NS_LDX + H * LDH + NS_HN * H + 2 * H + NS_HN;
+  static constexpr int W1 = 0;
+  static constexpr int W2 = W1 + H * NS_LDX;
+  static constexpr int WH = W2 + H * LDH;
+  static constexpr int BIAS = WH + NS_HN * H;  // b1 [H], b2 [H], b_head [8]
+  static constexpr int XS = W1 + WEIGHTS;
+  static constexpr int H1 = XS + NW_ROWS * NS_LDX;
+  static constexpr int H2 = H1 + TILE;    // later dZ1
+  static constexpr int DZ2 = H2 + TILE;   // MODE_FVP: U1 until P2 is done
+  static constexpr int OUT = DZ2 + TILE;
+  static constexpr int DOUT = OUT + HEAD;
+  static constexpr int BASE_END = DOUT + HEAD;
+  static constexpr int V1 = BASE_END;     // the tangent in the weights' layout
+  static constexpr int V2 = V1 + H * NS_LDX;
+  static constexpr int VH = V2 + H * LDH;
+  static constexpr int VBIAS = VH + NS_HN * H;
+  static constexpr int T2 = V1 + WEIGHTS;
+  static constexpr int TOUT = T2 + TILE;
+  static constexpr int FVP_END = TOUT + HEAD;
+  static constexpr int TOTAL = MODE == NG_MODE_FVP ? FVP_END : BASE_END;
+  static_assert(NS_LDX % 32 == 4 && NS_LDX > NS_IN_OVERLAY + 4, "whole 32-column tiles + 4");
+  static_assert(TOTAL * 4 <= 160 * 1024, "a workgroup's tiles must fit the CU's 160 KB of LDS");
+  static_assert(WEIGHTS % 4 == 0 && TILE % 4 == 0 && (NW_ROWS * NS_LDX) % 4 == 0,
+                "16-B LDS accesses");
+};
+
+// ns_tile<true, true> whose A operand is a tangent still without its tanh factor:
+// A(i, k) = U[i * lda + k] (1 - Hh[i * lda + k]^2)
+__device__ __forceinline__ ns_f32x16 ng_tile_tangent(const float* U, const float* Hh, int lda,
+                                                     const float* B, int ldb, int K, int lane) {
+  const int l31 = lane & 31, half = lane >> 5;
+  ns_f32x16 acc0, acc1;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
+  for (int g = 0; g < K / 8; ++g) {
+    const int k0 = 8 * g + 4 * half;
+    const float4 u = *reinterpret_cast<const float4*>(U + l31 * lda + k0);
+    const float4 h = *reinterpret_cast<const float4*>(Hh + l31 * lda + k0);
+    const float4 b = *reinterpret_cast<const float4*>(B + l31 * ldb + k0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(u.x * (1.f - h.x * h.x), b.x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(u.y * (1.f - h.y * h.y), b.y, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(u.z * (1.f - h.z * h.z), b.z, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(u.w * (1.f - h.w * h.w), b.w, acc1, 0, 0, 0);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc0[i] += acc1[i];
+  return acc0;
+}
+
+template <int H, int NS_LDX, int MODE>
+__global__ __launch_bounds__(NS_THREADS, 1) void narrow_natural_wide_kernel(NaturalParams q) {
+  typedef NaturalWideLds<H, NS_LDX, MODE> Lds;
+  constexpr int LDH = Lds::LDH, ROWS = NW_ROWS;
+  constexpr int CT = H / 32;                  // column tiles of a hidden layer
+  constexpr int KTMAX = (NS_LDX - 4) / 32;    // 32-column tiles of the staged observations
+  constexpr int NACC = (CT * KTMAX + 3) / 4;  // dW1 tiles a wave carries
+  constexpr int QW = H / 8;                   // hidden columns per thread in P5
+  constexpr bool FVP = MODE == NG_MODE_FVP, EVAL = MODE == NG_MODE_EVAL,
+                 GRAD = MODE == NG_MODE_GRAD;
+  __shared__ __attribute__((aligned(16))) float lds[Lds::TOTAL];
+
+  const GaNaturalShared& sh = q.sh;
+  const GaNaturalDev& m = q.table[blockIdx.y];
+  const int S = m.S;
+  const int tiles = (S + NS_ROWS - 1) / NS_ROWS;  // (the 64-row tiles of ga_natural_tiles)
+  const int shares = tiles < NG_SHARES ? tiles : NG_SHARES;
+  const int g = blockIdx.x;
+  if (g >= shares) return;
+  if (EVAL && m.state != NG_SEARCHING) return;
+  if (FVP && sh.respect_done && m.scalars[NG_DONE] != 0.0) return;
+
+  float* xs = lds + Lds::XS;
+  float* w1s = lds + Lds::W1;
+  float* w2s = lds + Lds::W2;
+  float* whs = lds + Lds::WH;
+  float* h1 = lds + Lds::H1;
+  float* h2 = lds + Lds::H2;
+  float* dz2 = lds + Lds::DZ2;
+  float* outl = lds + Lds::OUT;
+  float* doutl = lds + Lds::DOUT;
+  float* b1s = lds + Lds::BIAS;
+  float* b2s = b1s + H;
+  float* bhs = b2s + H;
+  // (only a product's instantiation has these)
+  float* v1s = lds + (FVP ? Lds::V1 : 0);
+  float* v2s = lds + (FVP ? Lds::V2 : 0);
+  float* vhs = lds + (FVP ? Lds::VH : 0);
+  float* u1 = dz2;
+  float* u2 = lds + (FVP ? Lds::T2 : 0);
+  float* toutl = lds + (FVP ? Lds::TOUT : 0);
+  float* vb1s = lds + (FVP ? Lds::VBIAS : 0);
+  float* vb2s = vb1s + H;
+  float* vbhs = vb2s + H;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, l31 = lane & 31, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int in_w = sh.in_w, A = sh.out_w;
+  const int ld0 = (in_w + 3) & ~3;
+  const int K1 = (in_w + 7) & ~7;   // first-layer reduction length, zero padded
+  const int KT = (ld0 + 31) >> 5;   // 32-column tiles of dW1 that hold a column < ld0
+
+  // ---- once: the member's weights (and the tangent) -> LDS
+  NgSource<MODE> src;
+  src.a = EVAL ? m.vectors + NG_PREV * sh.vec_stride : m.params;
+  src.d = m.vectors + NG_DESCENT * sh.vec_stride;
+  src.neg_ratio = m.neg_ratio;
+  ng_stage<H, NS_LDX>(src, sh, w1s, w2s, whs, b1s);
+  if (FVP) {
+    NgTangent tv;
+    tv.v = sh.vec_sel >= 0 ? m.vectors + sh.vec_sel * sh.vec_stride : m.vec;
+    tv.scrub = sh.vec_sel == NG_X;
+    ng_stage<H, NS_LDX>(tv, sh, v1s, v2s, vhs, vb1s);
+  }
+  if (EVAL && g == 0)
+    for (int64_t i = tid; i < sh.n_flat; i += NS_THREADS) m.params[i] = src.at(i);
+
+  // the log-std and what the rows' arithmetic derives from it
+  float s = 0.f, inv_var = 1.f, seed_scale = 0.f, var_ratio = 1.f, inv_std_new = 1.f;
+  if (sh.kind == 0) {
+    s = ga_log_std(src.at(0), sh.has_min, sh.min_log_std, sh.has_max, sh.max_log_std,
+                   nullptr);
+    inv_var = expf(-2.f * s);
+    seed_scale = expf(-2.f * s) / (float)S;
+    if (EVAL) {
+      const float s_old = ga_log_std(src.a[0], sh.has_min, sh.min_log_std, sh.has_max,
+                                     sh.max_log_std, nullptr);
+      const float ratio = expf(s_old - s);
+      var_ratio = ratio * ratio;
+      inv_std_new = expf(-s);
+    }
+  }
+  LossRowArgs L;
+  L.kind = sh.kind; L.actions = m.actions; L.lda = m.lda; L.old_ll = m.old_ll;
+  L.adv = m.adv; L.returns = nullptr; L.idx = nullptr; L.log_std = nullptr;
+  L.has_min = sh.has_min; L.has_max = sh.has_max; L.min_log_std = sh.min_log_std;
+  L.max_log_std = sh.max_log_std; L.A = A; L.algo = 2; L.clip = 0.f;
+  L.ent = lr_ent(m.ent_coeff, sh.ent_flags);
+  L.double_softmax = sh.double_softmax;
+  L.invM = m.inv_S;
+
+  // P1, P2: waves 0, 1 the primal column tiles, waves 2, 3 the tangent's
+  const int tcj = wave & 1;
+  const bool primal_on = wave < 2 && tcj < CT, tangent_on = FVP && wave >= 2 && tcj < CT;
+  // the rows' arithmetic: the first 32 lanes of wave 0
+  const bool rows_on = wave == 0 && lane < ROWS;
+
+  // ---- the shares this workgroup carries across its tiles
+  constexpr int GROUPS = NS_THREADS / H, JPG = NS_HN / GROUPS;
+  ns_f32x16 gW2, gW1[NACC];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gW2[i] = 0.f;
+#pragma unroll
+  for (int a = 0; a < NACC; ++a)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gW1[a][i] = 0.f;
+  float gWh[JPG];
+#pragma unroll
+  for (int i = 0; i < JPG; ++i) gWh[i] = 0.f;
+  float gb1 = 0.f, gb2 = 0.f, gbh = 0.f;
+  double sum0 = 0.0, sum1 = 0.0;  // wave 0: the rows' two batch sums
+
+  // the rows of this workgroup's 64-row tiles, 32 at a time
+  const int64_t t_begin = ((int64_t)g * tiles) / shares;
+  const int64_t t_end = ((int64_t)(g + 1) * tiles) / shares;
+  const int r_end = (int)(t_end * NS_ROWS < (int64_t)S ? t_end * NS_ROWS : (int64_t)S);
+  for (int m0 = (int)(t_begin * NS_ROWS); m0 < r_end; m0 += ROWS) {
+    const bool live = rows_on && m0 + lane < S;
+    // ---- the sample of this lane's row
+    float act[8];
+    float adv = 0.f, old_ll = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) act[j] = 0.f;
+    if (!FVP && live) {
+      const int64_t row = m0 + lane;
+      adv = m.adv[row];
+      old_ll = m.old_ll[row];
+      const float* arow = m.actions + row * m.lda;
+      if (sh.kind == 2) {
+        act[0] = arow[0];
+      } else {
+        const float4 a0 = *reinterpret_cast<const float4*>(arow);
+        act[0] = a0.x; act[1] = a0.y; act[2] = a0.z; act[3] = a0.w;
+        if (A > 4) {
+          const float4 a1 = *reinterpret_cast<const float4*>(arow + 4);
+          act[4] = a1.x; act[5] = a1.y; act[6] = a1.z; act[7] = a1.w;
+        }
+      }
+    }
+    // ---- P0: the tile's observations (zero padded)
+    for (int e = tid; e < ROWS * (NS_LDX / 4); e += NS_THREADS) {
+      const int rr = e / (NS_LDX / 4), qq = e % (NS_LDX / 4);
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m0 + rr < S && 4 * qq < ld0) {
+        x = *reinterpret_cast<const float4*>(m.X + (int64_t)(m0 + rr) * m.ldx + 4 * qq);
+        x.x = (4 * qq + 0 < in_w) ? x.x : 0.f;
+        x.y = (4 * qq + 1 < in_w) ? x.y : 0.f;
+        x.z = (4 * qq + 2 < in_w) ? x.z : 0.f;
+        x.w = (4 * qq + 3 < in_w) ? x.w : 0.f;
+      }
+      *reinterpret_cast<float4*>(xs + rr * NS_LDX + 4 * qq) = x;
+    }
+    __syncthreads();
+    // ---- P1: H1 = tanh(X W1^T + b1) | U1 = X V1^T + vb1
+    if (primal_on || tangent_on) {
+      const ns_f32x16 acc = ns_tile<true, true>(
+          xs, NS_LDX, (tangent_on ? v1s : w1s) + 32 * tcj * NS_LDX, NS_LDX, K1, lane);
+      const int col = 32 * tcj + l31;
+      const float b = tangent_on ? vb1s[col] : b1s[col];
+      float* dst = tangent_on ? u1 : h1;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        dst[row * LDH + col] = tangent_on ? acc[r] + b : ns_tanh(acc[r] + b);
+      }
+    }
+    __syncthreads();
+    // ---- P2: H2 = tanh(H1 W2^T + b2) | U2 = T1 W2^T + H1 V2^T + vb2, T1 = U1 (1 - H1^2)
+    if (primal_on) {
+      const ns_f32x16 acc = ns_tile<true, true>(h1, LDH, w2s + 32 * tcj * LDH, LDH, H, lane);
+      const int col = 32 * tcj + l31;
+      const float b = b2s[col];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        h2[row * LDH + col] = ns_tanh(acc[r] + b);
+      }
+    } else if (tangent_on) {
+      // two accumulations, summed in this order
+      const ns_f32x16 ta = ng_tile_tangent(u1, h1, LDH, w2s + 32 * tcj * LDH, LDH, H, lane);
+      const ns_f32x16 tb = ns_tile<true, true>(h1, LDH, v2s + 32 * tcj * LDH, LDH, H, lane);
+      const int col = 32 * tcj + l31;
+      const float vb = vb2s[col];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        u2[row * LDH + col] = (ta[r] + tb[r]) + vb;
+      }
+    }
+    __syncthreads();  // (every read of U1 is done: its buffer is dZ2 from P5 on)
+    // ---- P3: head outputs and their tangent on the vector lanes (thread = row x output):
+    // out = H2 Wh^T + bh, tout = T2 Wh^T + H2 Vh^T + vbh, T2 = U2 (1 - H2^2)
+    {
+      const int row = tid & 31, j = tid >> 5;
+      float o = bhs[j];
+      float u = FVP ? vbhs[j] : 0.f;
+#pragma unroll 4
+      for (int k = 0; k < H; k += 4) {
+        const float4 h = *reinterpret_cast<const float4*>(h2 + row * LDH + k);
+        const float4 w = *reinterpret_cast<const float4*>(whs + j * H + k);
+        o = fmaf(h.x, w.x, o); o = fmaf(h.y, w.y, o);
+        o = fmaf(h.z, w.z, o); o = fmaf(h.w, w.w, o);
+        if (FVP) {
+          float4 t = *reinterpret_cast<const float4*>(u2 + row * LDH + k);
+          const float4 v = *reinterpret_cast<const float4*>(vhs + j * H + k);
+          t.x *= (1.f - h.x * h.x); t.y *= (1.f - h.y * h.y);
+          t.z *= (1.f - h.z * h.z); t.w *= (1.f - h.w * h.w);
+          u = fmaf(t.x, w.x, u); u = fmaf(t.y, w.y, u);
+          u = fmaf(t.z, w.z, u); u = fmaf(t.w, w.w, u);
+          u = fmaf(h.x, v.x, u); u = fmaf(h.y, v.y, u);
+          u = fmaf(h.z, v.z, u); u = fmaf(h.w, v.w, u);
+        }
+      }
+      outl[row * NS_HN + j] = o;
+      if (FVP) toutl[row * NS_HN + j] = u;
+    }
+    __syncthreads();
+    // ---- P4: the rows' loss arithmetic (wave 0, lane = row)
+    if (rows_on) {
+      float out[8], dout[8];
+      const float4 o0 = *reinterpret_cast<const float4*>(outl + lane * NS_HN);
+      const float4 o1 = *reinterpret_cast<const float4*>(outl + lane * NS_HN + 4);
+      out[0] = o0.x; out[1] = o0.y; out[2] = o0.z; out[3] = o0.w;
+      out[4] = o1.x; out[5] = o1.y; out[6] = o1.z; out[7] = o1.w;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dout[j] = 0.f;
+      if (FVP) {
+        float tout[8];
+        const float4 u0 = *reinterpret_cast<const float4*>(toutl + lane * NS_HN);
+        const float4 u1q = *reinterpret_cast<const float4*>(toutl + lane * NS_HN + 4);
+        tout[0] = u0.x; tout[1] = u0.y; tout[2] = u0.z; tout[3] = u0.w;
+        tout[4] = u1q.x; tout[5] = u1q.y; tout[6] = u1q.z; tout[7] = u1q.w;
+        if (sh.kind == 0)
+          lr_fisher_seed_gauss_row(A, seed_scale, tout, dout);
+        else
+          lr_fisher_seed_cat_row(A, sh.double_softmax, m.inv_S, out, tout, dout);
+      } else {
+        double second = 0.0;
+        double first = lr_row(L, s, inv_var, out, act, adv, old_ll, 0.f, dout, &second);
+        if (GRAD && live) {
+          // the head outputs of the step's starting point (the KL's "old" side)
+          float* hrow = m.heads + (int64_t)(m0 + lane) * NS_HN;
+          *reinterpret_cast<float4*>(hrow) = o0;
+          *reinterpret_cast<float4*>(hrow + 4) = o1;
+        }
+        if (EVAL) {
+          float kl = 0.f;
+          if (live) {
+            const float* hrow = m.heads + (int64_t)(m0 + lane) * NS_HN;
+            const float4 p0 = *reinterpret_cast<const float4*>(hrow);
+            const float4 p1 = *reinterpret_cast<const float4*>(hrow + 4);
+            const float old[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+            kl = sh.kind == 0 ? lr_kl_gauss_row(A, var_ratio, inv_std_new, old, out)
+                              : lr_kl_cat_row(A, sh.double_softmax, old, out);
+          }
+          second = (double)kl;
+        }
+        if (live) {
+          sum0 += first;
+          sum1 += second;
+        }
+      }
+      if (!live) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dout[j] = 0.f;
+      }
+      if (!EVAL) {
+        *reinterpret_cast<float4*>(doutl + lane * NS_HN) =
+            make_float4(dout[0], dout[1], dout[2], dout[3]);
+        *reinterpret_cast<float4*>(doutl + lane * NS_HN + 4) =
+            make_float4(dout[4], dout[5], dout[6], dout[7]);
+      }
+    }
+    if (EVAL) continue;  // (two barriers lie between this P4 and the next tile's P3)
+    __syncthreads();
+    // ---- P5: dZ2 = (dout W_head) (1 - H2^2)   (thread = row x an eighth of the columns)
+    {
+      const int row = tid & 31, c0 = (tid >> 5) * QW;
+      const float4 d0 = *reinterpret_cast<const float4*>(doutl + row * NS_HN);
+      const float4 d1 = *reinterpret_cast<const float4*>(doutl + row * NS_HN + 4);
+      const float dd[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+      for (int i = 0; i < QW / 4; ++i) {
+        const int c = c0 + 4 * i;
+        const float4 h = *reinterpret_cast<const float4*>(h2 + row * LDH + c);
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < NS_HN; ++j) {
+          const float4 w = *reinterpret_cast<const float4*>(whs + j * H + c);
+          z.x = fmaf(dd[j], w.x, z.x); z.y = fmaf(dd[j], w.y, z.y);
+          z.z = fmaf(dd[j], w.z, z.z); z.w = fmaf(dd[j], w.w, z.w);
+        }
+        z.x *= (1.f - h.x * h.x); z.y *= (1.f - h.y * h.y);
+        z.z *= (1.f - h.z * h.z); z.w *= (1.f - h.w * h.w);
+        *reinterpret_cast<float4*>(dz2 + row * LDH + c) = z;
+      }
+    }
+    // ---- P6: head weight / bias gradient, into this thread's registers
+    {
+      const int c = tid % H, j0 = (tid / H) * JPG;
+      for (int r = 0; r < ROWS; ++r) {
+        const float h = h2[r * LDH + c];
+#pragma unroll
+        for (int jj = 0; jj < JPG; ++jj)
+          gWh[jj] = fmaf(doutl[r * NS_HN + j0 + jj], h, gWh[jj]);
+      }
+      if (tid < NS_HN)
+        for (int r = 0; r < ROWS; ++r) gbh += doutl[r * NS_HN + tid];
+    }
+    __syncthreads();  // dz2 complete; every read of h2 done
+    // ---- P7: dW2[n][k] += sum_r dZ2[r][n] H1[r][k]   (CT x CT tiles, one a wave at most)
+    if (wave < CT * CT) {
+      const int tn = wave / CT, tk = wave % CT;
+      const ns_f32x16 acc =
+          ns_tile<false, false>(dz2 + 32 * tn, LDH, h1 + 32 * tk, LDH, ROWS, lane);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) gW2[i] += acc[i];
+    }
+    // ---- P8: dZ1 = (dZ2 W2) (1 - H1^2) -> the h2 buffer   (wave = column tile)
+    if (wave < CT) {
+      const ns_f32x16 acc = ns_tile<true, false>(dz2, LDH, w2s + 32 * wave, LDH, H, lane);
+      const int col = 32 * wave + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const float h = h1[row * LDH + col];
+        h2[row * LDH + col] = acc[r] * (1.f - h * h);
+      }
+    }
+    // bias gradient of layer 2 (column sums of dZ2)
+    if (tid >= NS_THREADS - H) {
+      const int n = tid - (NS_THREADS - H);
+      for (int r = 0; r < ROWS; ++r) gb2 += dz2[r * LDH + n];
+    }
+    __syncthreads();
+    // ---- P9: dW1[n][k] += sum_r dZ1[r][n] X[r][k] (CT x KTMAX tiles, NACC a wave), db1
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      const int t = wave + 4 * a, tn = t / KTMAX, tk = t % KTMAX;
+      if (t < CT * KTMAX && tk < KT) {
+        const ns_f32x16 acc =
+            ns_tile<false, false>(h2 + 32 * tn, LDH, xs + 32 * tk, NS_LDX, ROWS, lane);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) gW1[a][i] += acc[i];
+      }
+    }
+    if (tid >= NS_THREADS - H) {
+      const int nn = tid - (NS_THREADS - H);
+      for (int r = 0; r < ROWS; ++r) gb1 += h2[r * LDH + nn];
+    }
+    __syncthreads();  // xs, h1, h2 are free for the next tile
+  }
+
+  // ---- once: this workgroup's sums and its share
+  if (!FVP && wave == 0) {
+    sum0 = ga_wave_sum(sum0);
+    sum1 = ga_wave_sum(sum1);
+    if (lane == 0) {
+      m.lpart[2 * g + 0] = sum0;
+      m.lpart[2 * g + 1] = sum1;
+    }
+  }
+  if (EVAL) return;
+  float* part = m.part + (int64_t)g * sh.stride;
+  float* pW1 = part;
+  float* pb1 = pW1 + (int64_t)H * ld0;
+  float* pW2 = pb1 + H;
+  float* pb2 = pW2 + (int64_t)H * H;
+  float* pWh = pb2 + H;
+  float* pbh = pWh + NS_HN * H;
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) {
+    const int t = wave + 4 * a, tn = t / KTMAX, tk = t % KTMAX;
+    const int k = 32 * tk + l31;
+    if (t < CT * KTMAX && k < ld0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = 32 * tn + (r & 3) + 8 * (r >> 2) + 4 * half;
+        pW1[(int64_t)n * ld0 + k] = gW1[a][r];
+      }
+    }
+  }
+  {
+    const int c = tid % H, j0 = (tid / H) * JPG;
+#pragma unroll
+    for (int jj = 0; jj < JPG; ++jj) pWh[(j0 + jj) * H + c] = gWh[jj];
+    if (tid < NS_HN) pbh[tid] = gbh;
+    if (tid >= NS_THREADS - H) {
+      pb1[tid - (NS_THREADS - H)] = gb1;
+      pb2[tid - (NS_THREADS - H)] = gb2;
+    }
+  }
+  if (wave < CT * CT) {
+    const int tn = wave / CT, tk = wave % CT;
+    const int k = 32 * tk + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = 32 * tn + (r & 3) + 8 * (r >> 2) + 4 * half;
+      pW2[n * H + k] = gW2[r];
+    }
+  }
+}
+
 // ---- the conjugate-gradient state of a member, one workgroup ------------------------
 constexpr int CG_THREADS = 256;
 constexpr int CG_REGIONS = 6;
@@ -757,7 +1242,7 @@ __global__ __launch_bounds__(CG_THREADS) void members_candidate_kernel(NaturalPa
 int ng_check(const GaNaturalShared* sh, const GaNaturalDev* table_dev, const char* who) {
   GA_REQUIRE(sh && table_dev, "%s: null pointer", who);
   const int dims[4] = {sh->in_w, sh->H, sh->H, sh->out_w};
-  GA_REQUIRE(ga_narrow_overlay_supported(3, dims) && sh->n_members >= 1 &&
+  GA_REQUIRE(ga_narrow_step_supported(3, dims) && sh->n_members >= 1 &&
                  sh->n_members <= 65535 && sh->n_flat >= 4 &&
                  sh->stride == ga_narrow_step_stride(sh->in_w, sh->H),
              "%s: unsupported shape", who);
@@ -778,25 +1263,33 @@ extern "C" int ga_members_natural_launch(const GaNaturalShared* sh,
   q.sh = *sh; q.table = table_dev;
   const dim3 grid((unsigned)NG_SHARES, (unsigned)sh->n_members);
   ga_prof_count(GA_PROF_MEMBERS_STEP);
-#define GA_NATURAL_LAUNCH(HH, LL, MM)                                                       \
-  hipLaunchKernelGGL((narrow_natural_members_kernel<HH, LL, MM>), grid, dim3(NS_THREADS), 0, \
-                     stream, q)
-#define GA_NATURAL_MODES(HH, LL)                                          \
-  do {                                                                    \
-    if (mode == NG_MODE_GRAD) GA_NATURAL_LAUNCH(HH, LL, NG_MODE_GRAD);    \
-    else if (mode == NG_MODE_FVP) GA_NATURAL_LAUNCH(HH, LL, NG_MODE_FVP); \
-    else GA_NATURAL_LAUNCH(HH, LL, NG_MODE_EVAL);                         \
+#define GA_NATURAL_LAUNCH(KERNEL, HH, LL, MM) \
+  hipLaunchKernelGGL((KERNEL<HH, LL, MM>), grid, dim3(NS_THREADS), 0, stream, q)
+#define GA_NATURAL_MODES(KERNEL, HH, LL)                                          \
+  do {                                                                            \
+    if (mode == NG_MODE_GRAD) GA_NATURAL_LAUNCH(KERNEL, HH, LL, NG_MODE_GRAD);    \
+    else if (mode == NG_MODE_FVP) GA_NATURAL_LAUNCH(KERNEL, HH, LL, NG_MODE_FVP); \
+    else GA_NATURAL_LAUNCH(KERNEL, HH, LL, NG_MODE_EVAL);                         \
   } while (0)
-  const int in_w = sh->in_w;
-  const int ldx_s = in_w <= 8 ? 12 : (in_w <= 16 ? 20 : 36);
-  if (sh->H == 64) {
-    if (ldx_s == 12) GA_NATURAL_MODES(64, 12);
-    else if (ldx_s == 20) GA_NATURAL_MODES(64, 20);
-    else GA_NATURAL_MODES(64, 36);
+  const int ldx_s = ga_narrow_ldx(sh->in_w);
+  if (ldx_s > NS_IN_OVERLAY + 4) {
+    // 33 .. 128 inputs: the wide kernel (32-row tiles, dW1 on the matrix cores)
+    ga_prof_count_narrow_wide();
+    if (sh->H == 64) {
+      if (ldx_s == 68) GA_NATURAL_MODES(narrow_natural_wide_kernel, 64, 68);
+      else GA_NATURAL_MODES(narrow_natural_wide_kernel, 64, 132);
+    } else {
+      if (ldx_s == 68) GA_NATURAL_MODES(narrow_natural_wide_kernel, 32, 68);
+      else GA_NATURAL_MODES(narrow_natural_wide_kernel, 32, 132);
+    }
+  } else if (sh->H == 64) {
+    if (ldx_s == 12) GA_NATURAL_MODES(narrow_natural_members_kernel, 64, 12);
+    else if (ldx_s == 20) GA_NATURAL_MODES(narrow_natural_members_kernel, 64, 20);
+    else GA_NATURAL_MODES(narrow_natural_members_kernel, 64, 36);
   } else {
-    if (ldx_s == 12) GA_NATURAL_MODES(32, 12);
-    else if (ldx_s == 20) GA_NATURAL_MODES(32, 20);
-    else GA_NATURAL_MODES(32, 36);
+    if (ldx_s == 12) GA_NATURAL_MODES(narrow_natural_members_kernel, 32, 12);
+    else if (ldx_s == 20) GA_NATURAL_MODES(narrow_natural_members_kernel, 32, 20);
+    else GA_NATURAL_MODES(narrow_natural_members_kernel, 32, 36);
   }
 #undef GA_NATURAL_MODES
 #undef GA_NATURAL_LAUNCH

@@ -32,9 +32,10 @@ GaTableRing g_ring;
 bool shape_ok(const ga_mlp_desc* d) {
   if (!d || d->n_layers != 3) return false;
   if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return false;
-  // (the persistent kernels keep the first-layer weights where the overlay instantiations
-  // of the narrow step do: <= NS_IN_OVERLAY inputs)
-  return ga_narrow_overlay_supported(3, d->dims) != 0;
+  // (<= NS_IN_OVERLAY inputs always; up to NS_IN_MAX, the wide kernel of
+  // members_natural.hip, where the caller has asked for the range: ga_set_narrow_wide)
+  return ga_narrow_overlay_supported(3, d->dims) != 0 ||
+         (ga_narrow_wide_on() && ga_narrow_wide_supported(3, d->dims) != 0);
 }
 
 // The workspace, in floats from its start: the members' vectors [NG_VECS][n][round4(n_flat)],
@@ -74,8 +75,8 @@ int check_args(const ga_members_natural_args* a, Entry entry, const char* who) {
   const ga_mlp_desc* d = a->desc;
   GA_REQUIRE(shape_ok(d),
              "%s: unsupported network (two equal tanh hidden layers of 32 or 64 units, <= 32 "
-             "inputs, <= 8 linear outputs, no layer norm; PopulationPPO's passes, "
-             "ga_update_epoch_members, take up to 128 inputs)", who);
+             "inputs, <= 128 inputs under ga_set_narrow_wide(1), <= 8 linear outputs, no "
+             "layer norm)", who);
   GA_REQUIRE(a->kind == 0 || a->kind == 2,
              "%s: kind must be 0 (Gaussian) or 2 (categorical)", who);
   GA_REQUIRE(flat_ok(d, a->n_flat),

@@ -124,8 +124,8 @@ inline int ga_narrow_envelope(int n_layers, const int* dims) {
          dims[3] >= 1 && dims[3] <= NS_HN;
 }
 // up to NS_IN_OVERLAY inputs: the first-layer weights overlay the dZ2 scratch in LDS
-// (narrow_body.h) -- also all that the population's natural-gradient step, joint
-// diagnostics and joint work before the update take
+// (narrow_body.h) -- also all that the population's joint diagnostics and joint work
+// before the update take
 inline int ga_narrow_overlay_supported(int n_layers, const int* dims) {
   return ga_narrow_envelope(n_layers, dims) && dims[0] >= 1 && dims[0] <= NS_IN_OVERLAY;
 }

@@ -1346,9 +1346,8 @@ typedef struct ga_update_members_args {
 } ga_update_members_args;
 /* 1: networks ga_update_epoch_members takes -- two equal tanh hidden layers of 32 or 64
  * units, <= 32 inputs (<= 128 under ga_set_narrow_wide(1)), <= 8 linear outputs, no layer
- * normalisation (the narrow step's shapes); 0 otherwise, NULL included.  The joint diagnostics, the joint work before the
- * update and the natural-gradient step (ga_mlp_forward_members_supported,
- * ga_members_natural_supported) stop at 32 inputs. */
+ * normalisation (the narrow step's shapes); 0 otherwise, NULL included.  The joint diagnostics and the joint work before the
+ * update (ga_mlp_forward_members_supported) stop at 32 inputs. */
 GA_API int ga_update_members_supported(const ga_mlp_desc* desc);
 /* Floats of `partials` for n_members members with minibatches of up to max_rows rows;
  * 0: unsupported network or sizes out of range. */
@@ -1408,7 +1407,11 @@ typedef struct ga_members_natural_args {
   float* workspace; int64_t workspace_floats;
   double* result;
 } ga_members_natural_args;
-/* 1: the networks these entries take -- those of ga_update_members_supported. */
+/* 1: the networks these entries take -- those of ga_update_members_supported: two equal
+ * tanh hidden layers of 32 or 64 units, <= 8 linear outputs, <= 32 inputs and, under
+ * ga_set_narrow_wide(1), <= 128 (a kernel of their own: 32-row tiles, the first layer's
+ * weight gradient on the matrix cores; counted by ga_narrow_wide_launches).  Members
+ * with <= 32 inputs get the same bits with the switch on or off. */
 GA_API int ga_members_natural_supported(const ga_mlp_desc* desc);
 /* Floats of `workspace` for members of rows[m] samples (HOST array); 0: unsupported
  * network or sizes out of range.  layout (optional, 5 entries), in floats from the start

@@ -18,7 +18,10 @@ inside), and the medians, their ratio and the run-to-run spread ((max - min) / m
 are printed, one JSON line per row, with the launches of one joint step as the
 library's counter gives them.
 
-    python tools/population_trpo_rate.py [--members 1 64] [--repeats 10]
+``--obs-dim N`` puts both heads on a ``SyntheticVecEnv`` of N-wide observations (4
+actions) instead: the wide kernel of the joint step above 32 inputs.
+
+    python tools/population_trpo_rate.py [--members 1 64] [--repeats 10] [--obs-dim 39]
 """
 import argparse
 import json
@@ -37,14 +40,17 @@ ENVS, STEPS = 64, 128
 GA_PROF_MEMBERS_STEP = 15
 
 
-def make_members(M, head):
+def make_members(M, head, obs_dim=None):
     from garage_amd.algos import TRPO
     from garage_amd.baselines import LinearFeatureBaselinePopulation
-    from garage_amd.envs import CartPoleVecEnv, PendulumVecEnv
+    from garage_amd.envs import CartPoleVecEnv, PendulumVecEnv, SyntheticVecEnv
     from garage_amd.optimizers import (ConjugateGradientOptimizer,
                                        OptimizerWrapper)
     from garage_amd.policies import CategoricalMLPPolicy, GaussianMLPPolicy
-    if head == 'categorical':
+    if obs_dim:
+        env = SyntheticVecEnv(M * ENVS, obs_dim, 4, STEPS, seed=3,
+                              discrete=head == 'categorical')
+    elif head == 'categorical':
         env = CartPoleVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
     else:
         env = PendulumVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
@@ -70,13 +76,13 @@ def timed(fn):
     return 1e3 * (time.perf_counter() - t0)
 
 
-def measure(M, head, repeats, warmup):
+def measure(M, head, repeats, warmup, obs_dim=None):
     from garage_amd import _lib
     from garage_amd.algos import PopulationTRPO
     from garage_amd.sampler import GpuPopulationSampler
     lib = _lib.load()
-    env, members = make_members(M, head)
-    _, lones = make_members(M, head)
+    env, members = make_members(M, head, obs_dim)
+    _, lones = make_members(M, head, obs_dim)
     pop = PopulationTRPO(members)
     sampler = GpuPopulationSampler(members[0].policy, env, n_members=M,
                                    max_episode_length=STEPS, seed=5)
@@ -87,6 +93,7 @@ def measure(M, head, repeats, warmup):
         a.policy.net.params.copy_(start[m])
     lone = [a._before_train(b, c.values) for a, b, c in zip(lones, batches, joint)]
 
+    @_lib.narrow_wide_scope  # (as PopulationTRPO._train runs it)
     def run_a():
         pop.member_params.copy_(start)
         pop._natural_step(joint)
@@ -111,7 +118,8 @@ def measure(M, head, repeats, warmup):
     def spread(t):
         return float((t.max() - t.min()) / np.median(t))
 
-    return dict(members=M, head=head, samples_per_member=[int(c.S) for c in joint][:4],
+    return dict(members=M, head=head, obs_dim=int(env.spec.observation_space.flat_dim),
+                samples_per_member=[int(c.S) for c in joint][:4],
                 population_ms=float(np.median(ta)), lone_ms=float(np.median(tb)),
                 lone_over_population=float(np.median(tb) / np.median(ta)),
                 population_spread=spread(ta), lone_spread=spread(tb),
@@ -127,6 +135,9 @@ def main():
     ap.add_argument('--heads', nargs='+', default=['categorical', 'gaussian'])
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--obs-dim', type=int, default=None,
+                    help='observation width of a SyntheticVecEnv in the place of '
+                         'CartPole / Pendulum')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_trpo_rate needs an MI355X: there is nothing to '
@@ -135,7 +146,7 @@ def main():
         raise SystemExit('medians of at least 10 repeats')
     for head in args.heads:
         for M in args.members:
-            print(json.dumps(measure(M, head, args.repeats, args.warmup)), flush=True)
+            print(json.dumps(measure(M, head, args.repeats, args.warmup, args.obs_dim)), flush=True)
 
 
 if __name__ == '__main__':
