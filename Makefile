@@ -6,8 +6,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := garage_amd/csrc
 OUT   := garage_amd/_C
-HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step members_natural lnorm member_pack linear_baseline members_diag members_advantage
-CPPS  := errors prof update update_members members_natural_host comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host members_diag_host members_advantage_host
+HIPS  := gae_scan gemm skinny losses rollout policy_fused small_step fused_train narrow_step members_step members_natural lnorm member_pack linear_baseline members_diag members_advantage linear_solve
+CPPS  := errors prof update update_members members_natural_host comm rollout_loop mlp_layers member_pack_host fused_train_host rollout_host losses_host linear_baseline_host linear_baseline_members_host members_diag_host members_advantage_host linear_solve_host
 OBJS  := $(patsubst %,$(OUT)/%.o,$(HIPS) $(CPPS))
 # -fno-slp-vectorize: hipcc's SLP vectorizer turns pairs of fp32 operations into packed
 # VOP3P instructions and, where one operand is the high half of a register pair, sets

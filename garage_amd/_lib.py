@@ -308,6 +308,12 @@ class LinearPredictMember(C.Structure):
                 ('values', ptr), ('ldv', c_i64)]
 
 
+class LinearSolveMember(C.Structure):
+    """``ga_linear_solve_member``."""
+    _fields_ = [('gram', ptr), ('rhs', ptr), ('reg_coeff', c_f64),
+                ('coeffs', ptr), ('status', ptr)]
+
+
 ABI_VERSION = 5  # ga_abi_version() of the library these structs mirror
 
 # name -> (restype, argtypes); mirrors include/garage_amd.h one to one.
@@ -533,6 +539,10 @@ SIGNATURES = {
     'ga_linear_features_predict_members_f32': (c_int, [
         C.POINTER(LinearPredictMember), c_i64, c_int, ptr]),
     'ga_linear_members_release': (None, []),
+    # the fit's solve and retries (linear_feature_baseline.py:70-79) on the device
+    'ga_linear_solve_workspace_doubles': (c_i64, [c_int, c_i64]),
+    'ga_linear_solve_members_f64': (c_int, [
+        C.POINTER(LinearSolveMember), c_i64, c_int, ptr, c_i64, ptr]),
     'ga_set_allreduce_hook': (None, [ptr]),
     'ga_comm_available': (c_int, []),
     'ga_comm_unique_id': (c_int, [ptr]),

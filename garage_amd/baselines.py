@@ -5,7 +5,9 @@ Mirrors ``garage.np.baselines.LinearFeatureBaseline``
 on ``[clip(obs), clip(obs)**2, al, al**2, al**3, 1]`` with ``al = t / 100``.  The
 one pass over the batch -- the feature rows, their Gram matrix and right-hand side
 in fp64 -- is a HIP kernel (``ga_linear_features_gram_f64``); the ``F x F`` solve
-is the reference's own ``np.linalg.lstsq`` on the host, unchanged; the
+is the reference's own ``np.linalg.lstsq`` on the host, unchanged, or with
+``solver='device'`` a blocked fp64 Cholesky kernel
+(``ga_linear_solve_members_f64``) after which a fit waits for nothing; the
 predictions are a second kernel (``ga_linear_features_predict_f32``).
 
 Two surfaces: the reference's (``fit(paths)`` / ``predict(path)`` on dicts of
@@ -34,11 +36,31 @@ class LinearFeatureBaseline:
         env_spec: Environment specification (its flat observation width).
         reg_coeff (float): Regularization coefficient.
         name (str): Name of baseline.
+        solver (str): ``'host'`` (default): the Gram matrix is copied to the
+            host and solved there by ``np.linalg.lstsq``, as the reference
+            does.  ``'device'``: one more launch solves it on the device
+            (Cholesky in fp64, the reference's five attempts with ``reg_coeff
+            *= 10`` inside the kernel); ``finish_fit`` and the predictions
+            after it wait for nothing, and the host copy of the coefficients is
+            fetched on first need (``get_param_values``, pickling,
+            ``predict``).  After five broken attempts the coefficients are NaN,
+            as the reference's would be; ``solve_status`` is then -1,
+            otherwise the retries used.  The two differ where the regularised
+            matrix is NOT positive definite: ``lstsq`` returns a finite
+            minimum-norm answer, Cholesky breaks down and retries with ten
+            times the regulariser.  A Gram matrix plus ``reg_coeff > 0`` is
+            positive definite.
     """
 
     kind = 'linear'  # what VPG / PPO / TRPO ask a value function
 
-    def __init__(self, env_spec, reg_coeff=1e-5, name='LinearFeatureBaseline'):
+    def __init__(self, env_spec, reg_coeff=1e-5, name='LinearFeatureBaseline',
+                 solver='host'):
+        if solver not in ('host', 'device'):
+            raise ValueError("LinearFeatureBaseline: solver must be 'host' or "
+                             "'device', not {!r}".format(solver))
+        self._solver = solver
+        self._status = None  # of the last device solve, once fetched
         self._obs_dim = int(env_spec.observation_space.flat_dim)
         if not 1 <= self._obs_dim <= MAX_OBS_DIM:
             raise ValueError(
@@ -56,6 +78,8 @@ class LinearFeatureBaseline:
         self._coeffs_dev = None  # fp64 device copy of _coeffs, made on demand
         self._pending = None     # (pinned host buffer, event) of a begun fit
         self._scratch = {}       # device: (gram + rhs, workspace, pinned)
+        self._lazy = None        # device (coefficients + status) not yet in _coeffs
+        self._solve_scratch = {}  # device: (coefficients + status, workspace)
 
     @property
     def n_features(self):
@@ -64,9 +88,32 @@ class LinearFeatureBaseline:
     # -- the reference's surface ---------------------------------------------
     def get_param_values(self):
         """float64 coefficients ``[2 * obs_dim + 4]``, or ``None`` before a fit."""
+        self._sync_host()
         return self._coeffs
 
+    @property
+    def solve_status(self):
+        """Of the last ``solver='device'`` fit: the retries its solve used,
+        0 .. 4, or -1 (five broken attempts, NaN coefficients); else ``None``."""
+        self._sync_host()
+        return self._status
+
+    def _has_coeffs(self):
+        """Whether a fit or ``set_param_values`` gave coefficients -- without
+        waiting for a device solve."""
+        return self._coeffs is not None or self._lazy is not None
+
+    def _sync_host(self):
+        """Fetch what a device solve left (ONE copy of the coefficients and
+        the status word, one wait) into ``_coeffs``, if it is still due."""
+        if self._lazy is not None:
+            store, self._lazy = self._lazy, None
+            self._coeffs, status = _split_store(store.cpu(), 1,
+                                                self.n_features)
+            self._coeffs, self._status = self._coeffs[0], int(status[0])
+
     def set_param_values(self, flattened_params):
+        self._lazy = self._status = None
         if flattened_params is None:
             self._coeffs = None
         else:
@@ -92,7 +139,7 @@ class LinearFeatureBaseline:
         """Values of ONE path (the reference's argument name), float64 ``[T]``;
         zeros before the first fit (``linear_feature_baseline.py:81-93``)."""
         n = len(paths['observations'])
-        if self._coeffs is None:
+        if not self._has_coeffs():
             return np.zeros(n)
         obs, ep_off = self._upload_paths([paths])
         return self._predict(obs, ep_off, 1).view(-1).cpu().numpy().astype(
@@ -121,8 +168,9 @@ class LinearFeatureBaseline:
         self.finish_fit()
 
     def begin_fit(self, batch, returns):
-        """Enqueue the Gram pass and the copy of its result to pinned host
-        memory on the current stream; :meth:`finish_fit` does the rest."""
+        """Enqueue the Gram pass and (``solver='host'``) the copy of its result
+        to pinned host memory on the current stream; :meth:`finish_fit` does
+        the rest."""
         self._begin(batch.obs_dev, batch.ep_off_dev, len(batch.lengths),
                     returns)
 
@@ -142,6 +190,9 @@ class LinearFeatureBaseline:
              self._obs_dim, dptr(ep_off), n_eps, S, dptr(returns),
              dptr(out), out[F * F:].data_ptr(), dptr(self._workspace),
              stream_ptr())
+        if self._solver == 'device':
+            self._pending = (None, None, obs.device)
+            return
         # ONE asynchronous copy (G and b are neighbours), then the event the
         # host waits for
         pinned.copy_(out, non_blocking=True)
@@ -151,12 +202,25 @@ class LinearFeatureBaseline:
 
     def finish_fit(self):
         """Wait for the Gram pass, solve on the host as the reference does
-        (``linear_feature_baseline.py:70-79``) and upload the coefficients."""
+        (``linear_feature_baseline.py:70-79``) and upload the coefficients;
+        with ``solver='device'`` enqueue the solve launch and return."""
         if self._pending is None:
             raise RuntimeError('LinearFeatureBaseline: finish_fit without '
                                'begin_fit')
         pinned, event, dev = self._pending
         self._pending = None
+        if self._solver == 'device':
+            F = self.n_features
+            out = self._scratch[(dev.type, dev.index)][0]
+            store, row, status, workspace = self._solve_target(dev)
+            u = _lib.LinearSolveMember()
+            u.gram, u.rhs = out.data_ptr(), out[F * F:].data_ptr()
+            u.reg_coeff = float(self._reg_coeff)
+            u.coeffs, u.status = row.data_ptr(), status.data_ptr()
+            call('ga_linear_solve_members_f64', u, 1, self._obs_dim,
+                 dptr(workspace), workspace.numel(), stream_ptr())
+            self._solved_on_device(store, row)
+            return
         event.synchronize()
         F = self.n_features
         host = pinned.numpy()
@@ -176,8 +240,28 @@ class LinearFeatureBaseline:
                 break
             reg_coeff *= 10
 
+    def _solve_target(self, device):
+        """Where a device solve of this baseline writes: (the tensor that holds
+        coefficients and status, its ``[F]`` coefficients, its status word,
+        the solve's workspace)."""
+        key = (device.type, device.index)
+        if key not in self._solve_scratch:
+            self._solve_scratch[key] = (
+                _new_store(1, self.n_features, device),
+                _solve_workspace(self._obs_dim, 1, device))
+        store, workspace = self._solve_scratch[key]
+        rows, status = _split_store(store, 1, self.n_features)
+        return store, rows[0], status, workspace
+
+    def _solved_on_device(self, store, row):
+        """A solve into ``row`` of ``store`` is enqueued: the device holds the
+        coefficients, the host copy is due."""
+        self._coeffs, self._status = None, None
+        self._coeffs_dev, self._lazy = row, store
+
     def _upload_coeffs(self, device):
         """``_coeffs`` to ``device`` as ``_coeffs_dev``."""
+        self._sync_host()
         self._coeffs_dev = torch.from_numpy(
             np.ascontiguousarray(self._coeffs, np.float64)).to(device)
 
@@ -194,7 +278,7 @@ class LinearFeatureBaseline:
 
     def _predict(self, obs, ep_off, n_eps):
         S = int(obs.shape[0])
-        if self._coeffs is None:
+        if not self._has_coeffs():
             return torch.zeros(S, 1, dtype=torch.float32, device=obs.device)
         self._check_batch(obs, ep_off, n_eps)
         if self._coeffs_dev is None or self._coeffs_dev.device != obs.device:
@@ -222,7 +306,10 @@ class LinearFeatureBaseline:
         key = (device.type, device.index)
         if key not in self._scratch:
             out = torch.empty(F * F + F, dtype=torch.float64, device=device)
-            pinned = torch.empty(F * F + F, dtype=torch.float64).pin_memory()
+            pinned = None
+            if self._solver == 'host':
+                pinned = torch.empty(F * F + F,
+                                     dtype=torch.float64).pin_memory()
             self._scratch[key] = [out, pinned, None]
         entry = self._scratch[key]
         need = int(_lib.load().ga_linear_gram_workspace_doubles(
@@ -236,14 +323,40 @@ class LinearFeatureBaseline:
 
     # -- pickling: the coefficients travel, device scratch is rebuilt -----------
     def __getstate__(self):
+        self._sync_host()
         state = self.__dict__.copy()
-        for k in ('_coeffs_dev', '_pending', '_scratch', '_workspace'):
+        for k in ('_coeffs_dev', '_pending', '_scratch', '_workspace', '_lazy',
+                  '_solve_scratch'):
             state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('_solver', 'host')
+        self.__dict__.setdefault('_status', None)
         self._reset_device_state()
+
+
+def _new_store(M, F, device):
+    """``M`` rows of ``F`` fp64 coefficients and, behind them, ``M`` int32
+    status words in ONE tensor, so that one copy brings both to the host."""
+    return torch.zeros(M * F + (M + 1) // 2, dtype=torch.float64,
+                       device=device)
+
+
+def _split_store(store, M, F):
+    """``(rows [M, F], status [M])`` of a :func:`_new_store` tensor (views) or
+    of its host copy (numpy arrays)."""
+    if store.device.type == 'cpu':
+        store = store.numpy()
+        return store[:M * F].reshape(M, F).copy(), store[M * F:].view(
+            np.int32)[:M].copy()
+    return store[:M * F].view(M, F), store[M * F:].view(torch.int32)[:M]
+
+
+def _solve_workspace(obs_dim, M, device):
+    need = int(_lib.load().ga_linear_solve_workspace_doubles(obs_dim, M))
+    return torch.empty(need, dtype=torch.float64, device=device)
 
 
 class _PopulationMember(LinearFeatureBaseline):
@@ -251,13 +364,25 @@ class _PopulationMember(LinearFeatureBaseline):
     ``LinearFeatureBaseline`` whose device coefficients are row ``index`` of the
     population's ``(M, F)`` tensor."""
 
-    def __init__(self, population, index, env_spec, reg_coeff, name):
+    def __init__(self, population, index, env_spec, reg_coeff, name, solver):
         self._population, self._index = population, index
-        super().__init__(env_spec, reg_coeff=reg_coeff, name=name)
+        super().__init__(env_spec, reg_coeff=reg_coeff, name=name,
+                         solver=solver)
 
     def set_param_values(self, flattened_params):
         super().set_param_values(flattened_params)
         self._population._row_stale(self._index)
+
+    def _sync_host(self):
+        if self._lazy is not None:
+            self._population._sync_host()
+
+    def _solve_target(self, device):
+        pop, m = self._population, self._index
+        rows, status = pop._row_tensor(device), pop._status_dev
+        pop._fresh[m] = True
+        return pop._store, rows[m], status[m:m + 1], pop._solve_workspace(
+            device)
 
     def _upload_coeffs(self, device):
         self._coeffs_dev = self._population._upload_row(self._index, device)
@@ -268,6 +393,9 @@ class LinearFeatureBaselinePopulation:
     in shared launches (``ga_linear_features_gram_members_f64``,
     ``ga_linear_features_predict_members_f32``): one Gram launch, one reduce
     launch, one copy and one wait for all of them, and one predict launch.
+    With ``solver='device'`` (see :class:`LinearFeatureBaseline`) one launch
+    solves every member's system on the device instead, straight into the
+    rows: no copy, no wait, no host solves.
     Every member gets, bit for bit, what it gets fitted alone on its batch.
     There is no reference counterpart: garage fits one baseline per process.
 
@@ -284,12 +412,17 @@ class LinearFeatureBaselinePopulation:
             members or one per member.
         name (str): Name of the population; member ``m`` is ``name`` +
             ``'/member<m>'``.
+        solver (str): ``'host'`` (default) or ``'device'``, of every member.
     """
 
     MAX_MEMBERS = 1024  # ga_linear_features_*_members_*
 
     def __init__(self, env_spec, n_members, reg_coeff=1e-5,
-                 name='LinearFeatureBaselinePopulation'):
+                 name='LinearFeatureBaselinePopulation', solver='host'):
+        if solver not in ('host', 'device'):
+            raise ValueError("LinearFeatureBaselinePopulation: solver must be "
+                             "'host' or 'device', not {!r}".format(solver))
+        self._solver = solver
         n_members = int(n_members)
         if not 1 <= n_members <= self.MAX_MEMBERS:
             raise ValueError(
@@ -306,13 +439,16 @@ class LinearFeatureBaselinePopulation:
         self.name = name
         self.members = [
             _PopulationMember(self, m, env_spec, reg_coeffs[m],
-                              '{}/member{}'.format(name, m))
+                              '{}/member{}'.format(name, m), solver)
             for m in range(n_members)]
         self._obs_dim = self.members[0]._obs_dim
         self._reset_device_state()
 
     def _reset_device_state(self):
         self._rows = None     # (M, F) fp64 device tensor of the coefficients
+        self._store = None    # solver='device': the tensor _rows is a view of,
+        self._status_dev = None  # and its (M, ) int32 status words
+        self._solve_ws = {}   # device: the solve launch's workspace
         self._fresh = [False] * len(self.members)  # row m holds member m's
         self._pending = None  # (pinned, event, device) of a begun fit
         self._scratch = {}    # device: [out, pinned out, workspace, pinned rows]
@@ -333,8 +469,14 @@ class LinearFeatureBaselinePopulation:
     # -- the rows ---------------------------------------------------------------
     def _row_tensor(self, device):
         if self._rows is None or self._rows.device != device:
-            self._rows = torch.zeros(len(self.members), self.n_features,
-                                     dtype=torch.float64, device=device)
+            M, F = len(self.members), self.n_features
+            if self._solver == 'device':
+                self._sync_host()  # (what the rows of the other device hold)
+                self._store = _new_store(M, F, device)
+                self._rows, self._status_dev = _split_store(self._store, M, F)
+            else:
+                self._rows = torch.zeros(M, F, dtype=torch.float64,
+                                         device=device)
             self._fresh = [False] * len(self.members)
             for member in self.members:
                 member._coeffs_dev = None
@@ -343,8 +485,27 @@ class LinearFeatureBaselinePopulation:
     def _row_stale(self, m):
         self._fresh[m] = False
 
+    def _sync_host(self):
+        """Every member's due host copy: ONE copy of the rows and the status
+        words, one wait."""
+        due = [b for b in self.members if b._lazy is not None]
+        if due:
+            rows, status = _split_store(self._store.cpu(), len(self.members),
+                                        self.n_features)
+            for b in due:
+                b._coeffs, b._status = rows[b._index], int(status[b._index])
+                b._lazy = None
+
+    def _solve_workspace(self, device):
+        key = (device.type, device.index)
+        if key not in self._solve_ws:
+            self._solve_ws[key] = _solve_workspace(
+                self._obs_dim, len(self.members), device)
+        return self._solve_ws[key]
+
     def _upload_row(self, m, device):
         """Member ``m``'s coefficients into its row; returns the row."""
+        self.members[m]._sync_host()
         row = self._row_tensor(device)[m]
         row.copy_(torch.from_numpy(
             np.ascontiguousarray(self.members[m]._coeffs, np.float64)))
@@ -386,8 +547,9 @@ class LinearFeatureBaselinePopulation:
 
     def begin_fit(self, batches, returns):
         """Enqueue every member's Gram pass (one Gram launch, one reduce
-        launch) and ONE copy of all ``M * (F * F + F)`` doubles to pinned host
-        memory on the current stream, then record one event."""
+        launch) and, with ``solver='host'``, ONE copy of all ``M * (F * F +
+        F)`` doubles to pinned host memory on the current stream and one
+        event."""
         import ctypes as C
         if self._pending is not None:
             raise RuntimeError('LinearFeatureBaselinePopulation: begin_fit '
@@ -427,6 +589,9 @@ class LinearFeatureBaselinePopulation:
             u.gram, u.rhs = base.data_ptr(), base[F * F:].data_ptr()
         call('ga_linear_features_gram_members_f64', arr, M, self._obs_dim,
              dptr(workspace), workspace.numel(), stream_ptr())
+        if self._solver == 'device':
+            self._pending = (None, None, device)
+            return
         pinned.copy_(out, non_blocking=True)
         event = torch.cuda.Event()
         event.record()
@@ -436,14 +601,32 @@ class LinearFeatureBaselinePopulation:
         """Wait once, solve every member's system on the host exactly as
         :meth:`LinearFeatureBaseline.finish_fit` does (the member's own
         ``reg_coeff``, the reference's retries) and upload all coefficients in
-        one copy."""
+        one copy.  With ``solver='device'``: enqueue ONE launch that solves
+        every member's system into its row, and return."""
         if self._pending is None:
             raise RuntimeError('LinearFeatureBaselinePopulation: finish_fit '
                                'without begin_fit')
         pinned, event, device = self._pending
         self._pending = None
-        event.synchronize()
         M, F = len(self.members), self.n_features
+        if self._solver == 'device':
+            out = self._scratch[(device.type, device.index)][0]
+            rows, workspace = (self._row_tensor(device),
+                               self._solve_workspace(device))
+            arr = (_lib.LinearSolveMember * M)()
+            for m, member in enumerate(self.members):
+                u, base = arr[m], out[m * (F * F + F):]
+                u.gram, u.rhs = base.data_ptr(), base[F * F:].data_ptr()
+                u.reg_coeff = float(member._reg_coeff)
+                u.coeffs = rows[m].data_ptr()
+                u.status = self._status_dev[m:m + 1].data_ptr()
+            call('ga_linear_solve_members_f64', arr, M, self._obs_dim,
+                 dptr(workspace), workspace.numel(), stream_ptr())
+            for m, member in enumerate(self.members):
+                member._solved_on_device(self._store, rows[m])
+                self._fresh[m] = True
+            return
+        event.synchronize()
         host = pinned.numpy().reshape(M, F * F + F)
         rows_host = self._scratch[(device.type, device.index)][3]
         stage = rows_host.numpy()
@@ -484,14 +667,14 @@ class LinearFeatureBaselinePopulation:
             if batch.obs_dev.device != device:
                 raise ValueError('LinearFeatureBaselinePopulation: member {}: '
                                  'a batch on another device'.format(m))
-            if member._coeffs is not None and not self._fresh[m]:
+            if member._has_coeffs() and not self._fresh[m]:
                 member._upload_coeffs(device)
             v = store[int(starts[m]):int(starts[m]) + sizes[m]]
             u = arr[m]
             u.obs, u.ldo = batch.obs_dev.data_ptr(), batch.obs_dev.stride(0)
             u.ep_off, u.n_eps = batch.ep_off_dev.data_ptr(), len(batch.lengths)
             u.S = sizes[m]
-            u.coeffs = None if member._coeffs is None else rows[m].data_ptr()
+            u.coeffs = rows[m].data_ptr() if member._has_coeffs() else None
             u.values, u.ldv = v.data_ptr(), 1
             values.append(v)
         call('ga_linear_features_predict_members_f32', arr, M, self._obs_dim,
@@ -507,10 +690,13 @@ class LinearFeatureBaselinePopulation:
         key = (device.type, device.index)
         if key not in self._scratch:
             n = M * (F * F + F)
+            host = self._solver == 'host'  # (the device solver copies nothing)
             self._scratch[key] = [
                 torch.empty(n, dtype=torch.float64, device=device),
-                torch.empty(n, dtype=torch.float64).pin_memory(), None,
-                torch.empty(M, F, dtype=torch.float64).pin_memory()]
+                torch.empty(n, dtype=torch.float64).pin_memory() if host
+                else None, None,
+                torch.empty(M, F, dtype=torch.float64).pin_memory() if host
+                else None]
         entry = self._scratch[key]
         need = int(_lib.load().ga_linear_gram_members_workspace_doubles(
             self._obs_dim, M, (C.c_int64 * M)(*sizes)))
@@ -524,13 +710,16 @@ class LinearFeatureBaselinePopulation:
     # -- pickling: the members (coefficients, reg_coeff) travel, device state is
     # rebuilt
     def __getstate__(self):
+        self._sync_host()
         state = self.__dict__.copy()
-        for k in ('_rows', '_fresh', '_pending', '_scratch'):
+        for k in ('_rows', '_store', '_status_dev', '_solve_ws', '_fresh',
+                  '_pending', '_scratch'):
             state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('_solver', 'host')
         self._reset_device_state()
 
 

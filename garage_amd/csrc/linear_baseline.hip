@@ -1,7 +1,8 @@
 // The device side of garage's LinearFeatureBaseline (np/baselines/linear_feature_baseline.py):
 // the normal equations of its ridge regression, G = Phi^T Phi and b = Phi^T r in fp64, and
 // its predictions Phi c, with the feature rows (linear_features.h) formed on the fly and
-// never written to HBM.  The F x F solve stays on the host (garage_amd/baselines.py).
+// never written to HBM.  The F x F solve is the host's (garage_amd/baselines.py) or, opt-in,
+// linear_solve.hip's.
 //
 // Gram pass.  A workgroup of 8 waves takes contiguous slabs of LB_SLAB_ROWS rows.  It
 // first finds every row's step index t inside its episode (one binary search over ep_off

@@ -1694,6 +1694,42 @@ GA_API int ga_linear_features_predict_members_f32(const ga_linear_predict_member
 /* frees the member tables' slots (tests; the library otherwise keeps them) */
 GA_API void ga_linear_members_release(void);
 
+/* The F x F solve of the fit on the device, for a population of baselines of one obs_dim in
+ * ONE launch (one member is a population of one): for every member
+ *   (gram + reg_coeff * I) coeffs = rhs
+ * in fp64 by a blocked Cholesky factorisation, one workgroup a member, the rank-16 updates
+ * on the fp64 matrix instruction -- in place of np.linalg.lstsq(featmat.T.dot(featmat) +
+ * reg_coeff * identity, featmat.T.dot(returns)) and the retry loop around it
+ * (linear_feature_baseline.py:70-79): an attempt breaks down on a pivot that is not finite
+ * or not > 0 or on a coefficient that is not finite, and the next one starts from gram
+ * again with reg_coeff * 10 (the plain fp64 product, repeatedly), five attempts in all.
+ * gram is only read.  No atomics: the same inputs give the same bits, and a member gets the
+ * same bits alone or among others.  For a matrix that is not positive definite lstsq gives
+ * a finite minimum-norm answer where this retries: the two can differ there. */
+typedef struct ga_linear_solve_member {
+  const double* gram;                        /* [F, F] row-major, symmetric (what
+                                                ga_linear_features_gram*_f64 writes) */
+  const double* rhs;                         /* [F] */
+  double reg_coeff;                          /* self._reg_coeff (line 69) */
+  double* coeffs;                            /* [F]: self._coeffs (lines 72-76); all NaN
+                                                after five broken attempts */
+  int32_t* status;                           /* one word: retries used, 0 .. 4 (the
+                                                reg_coeff *= 10 of line 79), or -1 */
+} ga_linear_solve_member;
+/* doubles of `workspace` (the members' factors) for n_members members; -1 for an obs_dim
+ * or n_members the solve refuses */
+GA_API int64_t ga_linear_solve_workspace_doubles(int obs_dim, int64_t n_members);
+/* linear_feature_baseline.py:70-79 for every member, one launch of n_members workgroups.
+ * members_host is a HOST array; its table travels as the Gram entry's does (a call MAY
+ * BLOCK its caller on the call that used its slot eight calls earlier, and is not
+ * graph-capture safe).  Refused before any launch or copy: null pointers, n_members
+ * outside 1 .. 1024, an obs_dim ga_linear_features_supported refuses, gram / rhs / coeffs /
+ * workspace not 8-byte aligned (status: 4-byte), a reg_coeff that is not finite or < 0,
+ * workspace_doubles below ga_linear_solve_workspace_doubles. */
+GA_API int ga_linear_solve_members_f64(const ga_linear_solve_member* members_host,
+                                       int64_t n_members, int obs_dim, double* workspace,
+                                       int64_t workspace_doubles, ga_stream_t stream);
+
 /* ---- measurement ----------------------------------------------------------
  * Optional HIP-event timing of every GEMM / scan launch on its own stream
  * (bench.py's roofline leg; no reference counterpart).  kinds: 0..2 =

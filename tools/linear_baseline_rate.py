@@ -168,16 +168,57 @@ def members_rows(M, repeats, warmup):
             repeats=len(t))), flush=True)
 
 
+def solver_rows(M, repeats, warmup, obs_dim):
+    """The joint fit + predict of M members with ``solver='host'`` against
+    ``solver='device'``, the rows taking turns."""
+    from garage_amd.baselines import LinearFeatureBaselinePopulation
+    n_eps, T = 64, 128
+    made = [make_batch(n_eps, T, obs_dim, seed=m) for m in range(M)]
+    batches, returns = [b for _, b, _ in made], [r for _, _, r in made]
+    pops = {s: LinearFeatureBaselinePopulation(made[0][0], M, solver=s)
+            for s in ('host', 'device')}
+    rows = []
+    for s, pop in pops.items():
+        rows.append((s + ' fit', lambda pop=pop: pop.fit_batches(batches,
+                                                                 returns)))
+        rows.append((s + ' fit+predict', lambda pop=pop: (
+            pop.fit_batches(batches, returns), pop.predict_batches(batches))))
+    times = {name: [] for name, _ in rows}
+    for rep in range(warmup + repeats):
+        for name, fn in rows:
+            ms = host_ms(fn)
+            if rep >= warmup:
+                times[name].append(ms)
+    assert all(b.solve_status == 0 for b in pops['device'])
+    for name, _ in rows:
+        t = np.asarray(times[name])
+        med = float(np.median(t))
+        print(json.dumps(dict(
+            members=M, S=n_eps * T, obs_dim=obs_dim, F=2 * obs_dim + 4,
+            what=name, median_ms=round(med, 4), min_ms=round(float(t.min()), 4),
+            max_ms=round(float(t.max()), 4),
+            spread=round(float((t.max() - t.min()) / med), 3),
+            repeats=len(t))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--repeats', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--solvers', action='store_true',
+                    help="with --members: one population with solver='host' "
+                         "against one with solver='device'")
+    ap.add_argument('--obs-dim', type=int, default=4,
+                    help='observation width of the --solvers rows')
     ap.add_argument('--members', type=int, default=0,
                     help='a population of this many baselines against as many '
                          'lone ones, instead of the kernels\' rates')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('linear_baseline_rate: needs an MI355X')
+    if args.members and args.solvers:
+        solver_rows(args.members, args.repeats, args.warmup, args.obs_dim)
+        return
     if args.members:
         members_rows(args.members, args.repeats, args.warmup)
         return

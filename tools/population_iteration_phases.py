@@ -56,6 +56,8 @@ def main():
     ap.add_argument('--linear-baseline', action='store_true',
                     help='one LinearFeatureBaselinePopulation as the value '
                          'functions')
+    ap.add_argument('--solver', choices=['host', 'device'], default='host',
+                    help='of the --linear-baseline population')
     ap.add_argument('--joint-diagnostics', action='store_true',
                     help='PopulationPPO(joint_diagnostics=True): the members\' '
                          'diagnostics after the update in joint launches')
@@ -70,7 +72,8 @@ def main():
     from garage_amd.sampler import GpuPopulationSampler
     M = args.members
     env, members = make_members(M, args.minibatch,
-                                'joint' if args.linear_baseline else None)
+                                'joint' if args.linear_baseline else None,
+                                solver=args.solver)
     from garage_amd import _lib
     lib = _lib.load()
 
@@ -132,6 +135,7 @@ def main():
             phase=k, members=M, minibatch=args.minibatch,
             joint_pack=not args.per_member_pack,
             linear_baseline=args.linear_baseline,
+            solver=args.solver if args.linear_baseline else None,
             joint_diagnostics=args.joint_diagnostics,
             joint_before=args.joint_before,
             counted_launches=before_launches if k == 'before_train' else None,

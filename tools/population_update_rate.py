@@ -48,7 +48,7 @@ if ROOT not in sys.path:
 ENVS, STEPS, EPOCHS = 64, 128, 10
 
 
-def make_members(M, minibatch, linear=None, obs_dim=None):
+def make_members(M, minibatch, linear=None, obs_dim=None, solver='host'):
     """``obs_dim``: None -- CartPole; D -- synthetic D-wide observations.
     ``linear``: None -- MLP(64, 64) value functions; 'joint' -- the members of
     one LinearFeatureBaselinePopulation; 'lone' -- lone LinearFeatureBaselines."""
@@ -63,8 +63,8 @@ def make_members(M, minibatch, linear=None, obs_dim=None):
         env = CartPoleVecEnv(M * ENVS, max_episode_length=STEPS, seed=3)
     else:
         env = SyntheticVecEnv(M * ENVS, obs_dim, 2, STEPS, discrete=True, seed=3)
-    joint = LinearFeatureBaselinePopulation(env.spec, M) if linear == 'joint' \
-        else None
+    joint = LinearFeatureBaselinePopulation(env.spec, M, solver=solver) \
+        if linear == 'joint' else None
     members = []
     for m in range(M):
         torch.manual_seed(100 + m)
