@@ -105,21 +105,30 @@ ENV_MOUNTAIN_CAR = 10
 # the algorithms switch it on around their update calls.  False: they leave it off
 # (A/B runs of one process; GARAGE_AMD_NARROW_WIDE=0 does the same for a whole one).
 NARROW_WIDE = True
+# The narrow step for hidden nonlinearities other than tanh is opt-in at the C ABI too
+# (ga_set_narrow_acts) and, unlike the range above, opt-in here as well: the process-wide
+# flag of garage_amd.engine.set_narrow_activations, read once from
+# GARAGE_AMD_NARROW_ACTS=1.  While it is set the algorithms switch the library on
+# around the same calls.
+NARROW_ACTS = os.environ.get('GARAGE_AMD_NARROW_ACTS', '') == '1'
 
 
 def narrow_wide_scope(fn):
-    """Runs ``fn`` with ``ga_set_narrow_wide(NARROW_WIDE)`` and puts the library's
-    setting back afterwards."""
+    """Runs ``fn`` with ``ga_set_narrow_wide(NARROW_WIDE)`` and
+    ``ga_set_narrow_acts(NARROW_ACTS)`` and puts the library's settings back
+    afterwards."""
     import functools
 
     @functools.wraps(fn)
     def scoped(*args, **kwargs):
         lib = load()
         was = lib.ga_set_narrow_wide(int(NARROW_WIDE))
+        was_acts = lib.ga_set_narrow_acts(int(NARROW_ACTS))
         try:
             return fn(*args, **kwargs)
         finally:
             lib.ga_set_narrow_wide(was)
+            lib.ga_set_narrow_acts(was_acts)
     return scoped
 
 
@@ -479,6 +488,8 @@ SIGNATURES = {
     'ga_set_narrow_step': (c_int, [c_int]),
     'ga_set_narrow_wide': (c_int, [c_int]),
     'ga_narrow_wide_launches': (c_i64, []),
+    'ga_set_narrow_acts': (c_int, [c_int]),
+    'ga_narrow_acts_on': (c_int, []),
     'ga_set_fused_first_layer': (c_int, [c_int]),
     'ga_set_pipelined_kloop': (c_int, [c_int]),
     'ga_set_wgrad_paired_columns': (c_int, [c_int]),

@@ -1553,8 +1553,9 @@ class PopulationPPO:
     reference counterpart: garage trains one learner per process.
 
     The members must share the algorithm, the networks' shapes (two equal tanh
-    hidden layers of 32 or 64 units, at most 128 inputs and 8 outputs), the head
-    kind and its options, ``minibatch_size``, ``max_optimization_epochs``, the
+    hidden layers of 32 or 64 units, at most 128 inputs and 8 outputs; under
+    ``garage_amd.engine.set_narrow_activations(True)`` any one hidden
+    nonlinearity, the same for all members), the head kind and its options, ``minibatch_size``, ``max_optimization_epochs``, the
     permutation mode, the entropy configuration and torch's default-shaped Adam
     with the same ``betas`` and ``eps``.  They may differ in ``lr``,
     ``lr_clip_range``, ``policy_ent_coeff`` and their optimizers' ``seed``.
@@ -1703,7 +1704,9 @@ class PopulationPPO:
                     raise ValueError(
                         '{}: the {} network {} is unsupported (two equal tanh '
                         'hidden layers of 32 or 64 units, <= 128 inputs, <= 8 '
-                        'linear outputs, no layer normalization)'.format(
+                        'linear outputs, no layer normalization; another hidden '
+                        'nonlinearity only under garage_amd.engine.'
+                        'set_narrow_activations(True))'.format(
                             who, name, tuple(mod.net.dims)))
         if self._joint_diagnostics:
             self._check_joint_diagnostics(ValueError)
@@ -2518,6 +2521,14 @@ class PopulationTRPO(PopulationPPO):
         import ctypes as C
         super()._check_members()
         for m, algo in enumerate(self.members):
+            for name, mod in (('policy', algo.policy),
+                              ('value function', algo._value_function)):
+                if not _is_linear(mod) and mod.net.hidden_act != 'tanh':
+                    raise ValueError(
+                        'member {}: the {} network\'s hidden nonlinearity {!r} is '
+                        'unsupported: PopulationTRPO trains tanh networks only, '
+                        'whatever set_narrow_activations says'.format(
+                            m, name, mod.net.hidden_act))
             if not _lib.load().ga_members_natural_supported(
                     C.byref(algo.policy.net._desc)):
                 raise ValueError('member {}: the policy network {} is unsupported '

@@ -21,6 +21,7 @@ struct ga_fused_loss_args {
   int A;                     // head width
   int algo; float clip; float ent_coeff; int ent_flags;
   int double_softmax;
+  int hidden_act;            // narrow step only: the network's hidden_act code (0 tanh)
 };
 
 struct ga_fused_region {
@@ -52,7 +53,8 @@ int ga_fused_eval_forward(const float* X, int64_t ldx, const int32_t* idx, int64
                           const float* W2, const float* b2, const float* Wh,
                           const float* bh, float* out, int64_t ldo, hipStream_t stream);
 // narrow_step.hip: forward + loss + backward of a 2 x H network (H = 32 or 64) in one
-// launch; part: [tiles][ga_narrow_step_stride] floats, lpart: [tiles][2] doubles
+// launch; part: [tiles][ga_narrow_step_stride] floats, lpart: [tiles][2] doubles.  The
+// hidden layers' activation travels in loss->hidden_act (network code 0 .. 6)
 int ga_narrow_train_step(const float* params, const int64_t* w_off, const int64_t* b_off,
                          int in_w, int H, int out_w, const float* X, int64_t ldx,
                          int64_t M, const ga_fused_loss_args* loss, float* part,

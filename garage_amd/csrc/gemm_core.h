@@ -4,6 +4,7 @@
 // layout notes.
 #pragma once
 #include "common.h"
+#include "act_codes.h"
 #include "gemm_params.h"  // GemmParams, BK, the EPI_* codes, act_forward_code
 
 namespace {
@@ -34,12 +35,13 @@ __device__ __forceinline__ float tanh_fast(float x) {
 // (the codes beyond tanh / relu / none sit behind a wave-uniform branch and a call:
 // inlined into a select chain their exp / log expansions ran for EVERY element of
 // every epilogue -- C5's forward GEMM 230 -> 235 us)
+// (the expressions of codes 3 .. 6, the same in both codings: act_codes.h)
 __device__ __attribute__((noinline)) float act_apply_more(float v, int act) {
   switch (act) {
-    case 3: return 1.f / (1.f + expf(-v));
-    case 4: return v > 0.f ? v : expm1f(v);
-    case 5: return v > 0.f ? v : 0.01f * v;
-    default: return v > 20.f ? v : log1pf(expf(v));  // 6 softplus
+    case 3: return ga_hact_apply<3>(v);
+    case 4: return ga_hact_apply<4>(v);
+    case 5: return ga_hact_apply<5>(v);
+    default: return ga_hact_apply<6>(v);  // 6 softplus
   }
 }
 __device__ __forceinline__ float act_apply(float v, int act) {
@@ -49,10 +51,10 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 }
 __device__ __attribute__((noinline)) float act_slope_more(float h, int hact) {
   switch (hact) {
-    case 3: return h * (1.f - h);
-    case 4: return h > 0.f ? 1.f : h + 1.f;       // exp(x) = h + 1 for x <= 0
-    case 5: return h > 0.f ? 1.f : 0.01f;
-    default: return 1.f - expf(-h);                // 6: sigmoid(x), h = log(1 + e^x)
+    case 3: return ga_hact_slope<3>(h);
+    case 4: return ga_hact_slope<4>(h);
+    case 5: return ga_hact_slope<5>(h);
+    default: return ga_hact_slope<6>(h);  // 6 softplus
   }
 }
 __device__ __forceinline__ float act_slope(float h, int hact) {

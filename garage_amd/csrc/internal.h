@@ -30,6 +30,20 @@ inline int ga_narrow_wide_on() {
   }();
   return g_ga_narrow_wide && !vetoed;
 }
+// The narrow step for networks whose hidden layers are not tanh (hidden_act 1 .. 6: the
+// NS_ACT_ANY instantiations of narrow_body.h) is opt-in the same way --
+// ga_set_narrow_acts(1), update.cpp -- so that the same entry points keep sending such a
+// network to the per-layer kernels, and keep refusing it for a population, until asked.
+// (ga_narrow_acts_on(), update.cpp, reads it back for callers)
+inline int g_ga_narrow_acts = 0;
+// What the narrow step asks of a network beyond its shape (shape_rules.h): tanh hidden
+// layers -- or, under the switch, any hidden_act the descriptor can name --, a linear
+// output layer, no layer normalisation.
+inline int ga_narrow_options_ok(const ga_mlp_desc* d) {
+  if (d->output_act != 0 || d->layer_norm) return 0;
+  return d->hidden_act == 0 ||
+         (g_ga_narrow_acts && d->hidden_act >= 1 && d->hidden_act <= 6);
+}
 
 // lnorm.hip: LayerNorm of the hidden-layer inputs (forward, backward, tangent)
 int ga_ln_forward(const float* X, int64_t ldx, const int32_t* idx, int64_t M, int D,

@@ -98,6 +98,13 @@ extern "C" int ga_mlp_forward_members_supported(const ga_mlp_desc* d) {
     ga_set_error("ga_mlp_forward_members_supported: unsupported network");
     return 0;
   }
+  if (d->hidden_act != 0) {
+    ga_set_error("ga_mlp_forward_members_supported: hidden_act %d: the joint launches of "
+                 "joint_diagnostics / joint_before take tanh hidden layers only, whatever "
+                 "ga_set_narrow_acts says (the default PopulationPPO passes, "
+                 "ga_update_epoch_members, take the others under it)", d->hidden_act);
+    return 0;
+  }
   if (d->dims[0] > NS_IN_OVERLAY) {
     ga_set_error("ga_mlp_forward_members_supported: %d inputs: the joint launches of "
                  "joint_diagnostics / joint_before take <= %d (the default PopulationPPO "

@@ -76,7 +76,7 @@ int check_args(const ga_members_natural_args* a, Entry entry, const char* who) {
   GA_REQUIRE(shape_ok(d),
              "%s: unsupported network (two equal tanh hidden layers of 32 or 64 units, <= 32 "
              "inputs, <= 128 inputs under ga_set_narrow_wide(1), <= 8 linear outputs, no "
-             "layer norm)", who);
+             "layer norm; tanh whatever ga_set_narrow_acts says)", who);
   GA_REQUIRE(a->kind == 0 || a->kind == 2,
              "%s: kind must be 0 (Gaussian) or 2 (categorical)", who);
   GA_REQUIRE(flat_ok(d, a->n_flat),

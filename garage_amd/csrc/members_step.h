@@ -37,6 +37,7 @@ struct GaMembersShared {
   int64_t stride;       // ga_narrow_step_stride(in_w, H)
   int64_t mb;           // rows of a full step (0: the whole batch in step 0)
   int32_t n_members;
+  int32_t hact;         // the members' hidden_act (network code): one for the call
 };
 
 extern "C" {

@@ -60,7 +60,7 @@ __device__ __forceinline__ LossRowArgs members_loss(const GaMemberDev& m,
 // Grid (max tiles of a member in this step, n_members); a workgroup beyond its
 // member's tiles returns.  Every global access is the body's own, behind the body's
 // bounds tests on the member's M (narrow_body.h).
-template <int H, int NS_LDX>
+template <int H, int NS_LDX, int ACT>
 __global__ __launch_bounds__(NS_THREADS, NS_LDX <= 20 ? 2 : 1) void
 narrow_train_members_kernel(MembersTrainParams q) {
   const GaMemberDev& m = q.table[blockIdx.y];
@@ -76,7 +76,8 @@ narrow_train_members_kernel(MembersTrainParams q) {
   p.loss = members_loss(m, q.sh, q.k, M);
   p.part = m.part; p.stride = q.sh.stride; p.lpart = m.lpart;
   p.dbg = nullptr;
-  narrow_train_body<H, NS_LDX>(p, tile);
+  p.hact = q.sh.hact;  // (a kernel argument: wave-uniform, read by NS_ACT_ANY alone)
+  narrow_train_body<H, NS_LDX, ACT>(p, tile);
 }
 
 // The six regions of a narrow network (W0 | b0 | W1 | b1 | 8 head rows | 8), the same
@@ -182,7 +183,7 @@ extern "C" int ga_members_train_step(const GaMembersShared* sh,
   const int dims[4] = {sh->in_w, sh->H, sh->H, sh->out_w};
   GA_REQUIRE(ga_narrow_step_supported(3, dims) && sh->n_members >= 1 &&
                  sh->n_members <= 65535 && max_tiles >= 1 && max_tiles < (1ll << 25) &&
-                 k >= 0 && k < (1ll << 31),
+                 k >= 0 && k < (1ll << 31) && sh->hact >= 0 && sh->hact <= 6,
              "ga_members_train_step: unsupported shape");
   MembersTrainParams q;
   memset(&q, 0, sizeof(q));
@@ -191,18 +192,24 @@ extern "C" int ga_members_train_step(const GaMembersShared* sh,
   ga_prof_count(GA_PROF_MEMBERS_STEP);
   const int ldx_s = ga_narrow_ldx(sh->in_w);
   if (ldx_s > 36) ga_prof_count_narrow_wide();
-#define GA_MEMBERS_LAUNCH(HH, LL)                                                       \
-  hipLaunchKernelGGL((narrow_train_members_kernel<HH, LL>), grid, dim3(NS_THREADS), 0, \
-                     stream, q)
-#define GA_MEMBERS_LAUNCH_H(HH)                    \
-  switch (ldx_s) {                                 \
-    case 12: GA_MEMBERS_LAUNCH(HH, 12); break;     \
-    case 20: GA_MEMBERS_LAUNCH(HH, 20); break;     \
-    case 36: GA_MEMBERS_LAUNCH(HH, 36); break;     \
-    case 68: GA_MEMBERS_LAUNCH(HH, 68); break;     \
-    default: GA_MEMBERS_LAUNCH(HH, 132); break;    \
+#define GA_MEMBERS_LAUNCH(HH, LL, ACT)                                                    \
+  hipLaunchKernelGGL((narrow_train_members_kernel<HH, LL, ACT>), grid, dim3(NS_THREADS), \
+                     0, stream, q)
+#define GA_MEMBERS_LAUNCH_H(HH, ACT)                    \
+  switch (ldx_s) {                                      \
+    case 12: GA_MEMBERS_LAUNCH(HH, 12, ACT); break;     \
+    case 20: GA_MEMBERS_LAUNCH(HH, 20, ACT); break;     \
+    case 36: GA_MEMBERS_LAUNCH(HH, 36, ACT); break;     \
+    case 68: GA_MEMBERS_LAUNCH(HH, 68, ACT); break;     \
+    default: GA_MEMBERS_LAUNCH(HH, 132, ACT); break;    \
   }
-  if (sh->H == 64) GA_MEMBERS_LAUNCH_H(64) else GA_MEMBERS_LAUNCH_H(32)
+  if (sh->hact == 0) {
+    if (sh->H == 64) GA_MEMBERS_LAUNCH_H(64, NS_ACT_TANH)
+    else GA_MEMBERS_LAUNCH_H(32, NS_ACT_TANH)
+  } else {
+    if (sh->H == 64) GA_MEMBERS_LAUNCH_H(64, NS_ACT_ANY)
+    else GA_MEMBERS_LAUNCH_H(32, NS_ACT_ANY)
+  }
 #undef GA_MEMBERS_LAUNCH_H
 #undef GA_MEMBERS_LAUNCH
   GA_CHECK_LAUNCH("narrow_train_members");

@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 
+#include "act_codes.h"
 #include "fused_train.h"
 #include "loss_rows.h"
 
@@ -28,6 +29,21 @@ __device__ __forceinline__ float ns_tanh(float x) {
   return ga_tanh(x);  // common.h
 }
 
+// The body's activation parameter.  NS_ACT_TANH: tanh and 1 - h^2 written into the
+// phases, the code of before.  NS_ACT_ANY: the network's hidden_act code 1 .. 6 arrives
+// in NarrowParams::hact, uniform over the launch; ONE instantiation per shape serves all
+// six (not one per code: six more times the H x NS_LDX x kernel instantiations would
+// take the build with them).  Each of the four phases the activation touches (P1, P2:
+// f(z); P5, P8: dZ times the slope as a function of the stored output, act_codes.h)
+// branches on the code ONCE, in front of its per-element loop, and holds one copy of
+// that loop per code: hact is a kernel argument, so the branch is s_cmp / s_cbranch on
+// an SGPR and the loop behind it is straight-line code for one activation -- no per-lane
+// select chain and no call among the accumulator registers.
+// (The tanh loops stand beside the dispatched ones, not inside the same lambda: taken
+// through it the tanh instantiations computed the same values with another register
+// allocation and schedule, and they are to stay the parent's instruction streams.)
+constexpr int NS_ACT_TANH = 0, NS_ACT_ANY = 1;
+
 struct NarrowParams {
   const float* params;
   int64_t w_off[3], b_off[3];
@@ -38,6 +54,7 @@ struct NarrowParams {
   int64_t stride;   //                  dW_head [8][H], db_head [8]
   double* lpart;    // [tiles][2]
   long long* dbg;   // developer hook: phase timestamps of workgroup 0
+  int hact;         // NS_ACT_ANY: the hidden layers' network code, 1 .. 6
 };
 
 #define NS_STAMP(i) \
@@ -117,13 +134,15 @@ __device__ __forceinline__ ns_f32x16 ns_tile(const float* A, int lda, const floa
 //    minibatch is one to four tiles on 256 CUs, so the two chains' workgroups still
 //    run side by side, on different CUs.
 // P2 .. P8 are the same code at every NS_LDX.
+// (ACT: NS_ACT_TANH or NS_ACT_ANY, above; LDS, tile walk, shares and grid do not depend
+// on it.)
 // Both kernels launch it under __launch_bounds__(NS_THREADS, NS_LDX <= 20 ? 2 : 1)
 // (2 waves per SIMD where the LDS tiles allow two workgroups per CU: one of each
 // network's chain -- without the bound the compiler takes 254 + 64 registers and
 // the two chains' launches can only take turns).
 // tile: which 64 rows of the minibatch (rows [64 tile, 64 tile + 64) of p.M) this
 // workgroup takes; its shares go to p.part + tile * p.stride, p.lpart + 2 * tile.
-template <int H, int NS_LDX>
+template <int H, int NS_LDX, int ACT>
 __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const int tile) {
   constexpr int LDH = H + 4;
   constexpr int CT = H / 32;        // column tiles of a hidden layer
@@ -236,30 +255,50 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
   const int tri = wave & 1, tcj = wave >> 1;
   const bool tile_on = tcj < CT;
 
-  // ---- P1: H1 = tanh(X W1^T + b1)
+  // ---- P1: H1 = f(X W1^T + b1)   (f = tanh at NS_ACT_TANH)
   if (tile_on) {
     const ns_f32x16 acc = ns_tile<true, true>(xs + 32 * tri * NS_LDX, NS_LDX,
                                               w1s + 32 * tcj * NS_LDX, NS_LDX, K1, lane);
     const int col = 32 * tcj + l31;
     const float b = b1s[col];
+    if constexpr (ACT == NS_ACT_TANH) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
-      h1[row * LDH + col] = ns_tanh(acc[r] + b);
+      for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+        h1[row * LDH + col] = ns_tanh(acc[r] + b);
+      }
+    } else {
+      ga_hact_dispatch(p.hact, [&](auto code) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+          h1[row * LDH + col] = ga_hact_apply<decltype(code)::value>(acc[r] + b);
+        }
+      });
     }
   }
   __syncthreads();
   NS_STAMP(2);
-  // ---- P2: H2 = tanh(H1 W2^T + b2)
+  // ---- P2: H2 = f(H1 W2^T + b2)
   if (tile_on) {
     const ns_f32x16 acc = ns_tile<true, true>(h1 + 32 * tri * LDH, LDH,
                                               w2s + 32 * tcj * LDH, LDH, H, lane);
     const int col = 32 * tcj + l31;
     const float b = b2s[col];
+    if constexpr (ACT == NS_ACT_TANH) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
-      h2[row * LDH + col] = ns_tanh(acc[r] + b);
+      for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+        h2[row * LDH + col] = ns_tanh(acc[r] + b);
+      }
+    } else {
+      ga_hact_dispatch(p.hact, [&](auto code) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+          h2[row * LDH + col] = ga_hact_apply<decltype(code)::value>(acc[r] + b);
+        }
+      });
     }
   }
   __syncthreads();
@@ -333,25 +372,47 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
   float* pb2 = pW2 + (int64_t)H * H;
   float* pWh = pb2 + H;
   float* pbh = pWh + NS_HN * H;
-  // ---- P5: dZ2 = (dout W_head) (1 - H2^2)   (lane = row, wave = column quarter)
+  // ---- P5: dZ2 = (dout W_head) f'(H2)   (lane = row, wave = column quarter;
+  // f' = 1 - H2^2 at NS_ACT_TANH)
   {
     const float4 d0 = *reinterpret_cast<const float4*>(doutl + lane * NS_HN);
     const float4 d1 = *reinterpret_cast<const float4*>(doutl + lane * NS_HN + 4);
     const float dd[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+    if constexpr (ACT == NS_ACT_TANH) {
 #pragma unroll
-    for (int i = 0; i < QW / 4; ++i) {
-      const int c = wave * QW + 4 * i;
-      const float4 h = *reinterpret_cast<const float4*>(h2 + lane * LDH + c);
-      float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int i = 0; i < QW / 4; ++i) {
+        const int c = wave * QW + 4 * i;
+        const float4 h = *reinterpret_cast<const float4*>(h2 + lane * LDH + c);
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-      for (int j = 0; j < NS_HN; ++j) {
-        const float4 w = *reinterpret_cast<const float4*>(whs + j * H + c);
-        z.x = fmaf(dd[j], w.x, z.x); z.y = fmaf(dd[j], w.y, z.y);
-        z.z = fmaf(dd[j], w.z, z.z); z.w = fmaf(dd[j], w.w, z.w);
+        for (int j = 0; j < NS_HN; ++j) {
+          const float4 w = *reinterpret_cast<const float4*>(whs + j * H + c);
+          z.x = fmaf(dd[j], w.x, z.x); z.y = fmaf(dd[j], w.y, z.y);
+          z.z = fmaf(dd[j], w.z, z.z); z.w = fmaf(dd[j], w.w, z.w);
+        }
+        z.x *= (1.f - h.x * h.x); z.y *= (1.f - h.y * h.y);
+        z.z *= (1.f - h.z * h.z); z.w *= (1.f - h.w * h.w);
+        *reinterpret_cast<float4*>(dz2 + lane * LDH + c) = z;
       }
-      z.x *= (1.f - h.x * h.x); z.y *= (1.f - h.y * h.y);
-      z.z *= (1.f - h.z * h.z); z.w *= (1.f - h.w * h.w);
-      *reinterpret_cast<float4*>(dz2 + lane * LDH + c) = z;
+    } else {
+      ga_hact_dispatch(p.hact, [&](auto code) {
+        constexpr int HA = decltype(code)::value;
+#pragma unroll
+        for (int i = 0; i < QW / 4; ++i) {
+          const int c = wave * QW + 4 * i;
+          const float4 h = *reinterpret_cast<const float4*>(h2 + lane * LDH + c);
+          float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+          for (int j = 0; j < NS_HN; ++j) {
+            const float4 w = *reinterpret_cast<const float4*>(whs + j * H + c);
+            z.x = fmaf(dd[j], w.x, z.x); z.y = fmaf(dd[j], w.y, z.y);
+            z.z = fmaf(dd[j], w.z, z.z); z.w = fmaf(dd[j], w.w, z.w);
+          }
+          z.x *= ga_hact_slope<HA>(h.x); z.y *= ga_hact_slope<HA>(h.y);
+          z.z *= ga_hact_slope<HA>(h.z); z.w *= ga_hact_slope<HA>(h.w);
+          *reinterpret_cast<float4*>(dz2 + lane * LDH + c) = z;
+        }
+      });
     }
   }
   // ---- P6: head weight / bias gradient shares
@@ -388,16 +449,27 @@ __device__ __forceinline__ void narrow_train_body(const NarrowParams& p, const i
       pW2[n * H + k] = acc[r];
     }
   }
-  // ---- P8: dZ1 = (dZ2 W2) (1 - H1^2) -> the h2 buffer
+  // ---- P8: dZ1 = (dZ2 W2) f'(H1) -> the h2 buffer
   if (tile_on) {
     const ns_f32x16 acc = ns_tile<true, false>(dz2 + 32 * tri * LDH, LDH, w2s + 32 * tcj,
                                                LDH, H, lane);
     const int col = 32 * tcj + l31;
+    if constexpr (ACT == NS_ACT_TANH) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float h = h1[row * LDH + col];
-      h2[row * LDH + col] = acc[r] * (1.f - h * h);
+      for (int r = 0; r < 16; ++r) {
+        const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const float h = h1[row * LDH + col];
+        h2[row * LDH + col] = acc[r] * (1.f - h * h);
+      }
+    } else {
+      ga_hact_dispatch(p.hact, [&](auto code) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = 32 * tri + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const float h = h1[row * LDH + col];
+          h2[row * LDH + col] = acc[r] * ga_hact_slope<decltype(code)::value>(h);
+        }
+      });
     }
   }
   // bias gradient of layer 2 (column sums of dZ2)

@@ -1,5 +1,6 @@
 // One optimizer step's forward + loss + backward of a NARROW network in one launch
-// (gfx950): two tanh hidden layers of equal width H = 32 or 64, <= 128 inputs,
+// (gfx950): two hidden layers of equal width H = 32 or 64 (tanh; any other hidden
+// activation of ga_mlp_desc through the NS_ACT_ANY instantiations), <= 128 inputs,
 // <= 8 outputs -- the CartPole-class networks of BASELINE.json configs[0-1]
 // (MLP(32,32), MLP(64,64)) at minibatches of any size, and the same networks on
 // observations up to 128 wide (one-hot grids, multi-task points: the wide
@@ -32,10 +33,10 @@
 
 namespace {
 
-template <int H, int NS_LDX>
+template <int H, int NS_LDX, int ACT>
 __global__ __launch_bounds__(NS_THREADS, NS_LDX <= 20 ? 2 : 1) void narrow_train_kernel(
     NarrowParams p) {
-  narrow_train_body<H, NS_LDX>(p, blockIdx.x);
+  narrow_train_body<H, NS_LDX, ACT>(p, blockIdx.x);
 }
 
 }  // namespace
@@ -79,6 +80,8 @@ extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
              "ga_narrow_train_step: missing / misaligned minibatch arrays");
   GA_REQUIRE(loss->kind == 2 || loss->log_std, "ga_narrow_train_step: log_std");
   GA_REQUIRE(loss->algo == 0 || loss->algo == 1, "ga_narrow_train_step: algo");
+  GA_REQUIRE(loss->hidden_act >= 0 && loss->hidden_act <= 6,
+             "ga_narrow_train_step: hidden_act %d not in 0..6", loss->hidden_act);
   NarrowParams p;
   memset(&p, 0, sizeof(p));
   p.params = params;
@@ -87,6 +90,7 @@ extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
   p.loss = loss_args(loss, M);
   p.part = part; p.stride = ga_narrow_step_stride(in_w, H); p.lpart = lpart;
   p.dbg = g_ns_dbg;
+  p.hact = loss->hidden_act;
   const dim3 grid((unsigned)ga_fused_tiles(M));
   // algorithmic flops: forward + both backward products of every layer
   const double flops =
@@ -95,18 +99,22 @@ extern "C" int ga_narrow_train_step(const float* params, const int64_t* w_off,
   const int ldx_s = ga_narrow_ldx(in_w);
   ga_prof_events(GA_PROF_NARROW_STEP, flops, &e0, &e1);
   if (ldx_s > 36) ga_prof_count_narrow_wide();
-#define GA_NARROW_LAUNCH(HH, LL)                                                      \
-  hipExtLaunchKernelGGL((narrow_train_kernel<HH, LL>), grid, dim3(NS_THREADS), 0, stream, \
-                        e0, e1, 0, p)
-#define GA_NARROW_LAUNCH_H(HH)                    \
-  switch (ldx_s) {                                \
-    case 12: GA_NARROW_LAUNCH(HH, 12); break;     \
-    case 20: GA_NARROW_LAUNCH(HH, 20); break;     \
-    case 36: GA_NARROW_LAUNCH(HH, 36); break;     \
-    case 68: GA_NARROW_LAUNCH(HH, 68); break;     \
-    default: GA_NARROW_LAUNCH(HH, 132); break;    \
+#define GA_NARROW_LAUNCH(HH, LL, ACT)                                                     \
+  hipExtLaunchKernelGGL((narrow_train_kernel<HH, LL, ACT>), grid, dim3(NS_THREADS), 0,    \
+                        stream, e0, e1, 0, p)
+#define GA_NARROW_LAUNCH_H(HH, ACT)                    \
+  switch (ldx_s) {                                     \
+    case 12: GA_NARROW_LAUNCH(HH, 12, ACT); break;     \
+    case 20: GA_NARROW_LAUNCH(HH, 20, ACT); break;     \
+    case 36: GA_NARROW_LAUNCH(HH, 36, ACT); break;     \
+    case 68: GA_NARROW_LAUNCH(HH, 68, ACT); break;     \
+    default: GA_NARROW_LAUNCH(HH, 132, ACT); break;    \
   }
-  if (H == 64) GA_NARROW_LAUNCH_H(64) else GA_NARROW_LAUNCH_H(32)
+  if (p.hact == 0) {
+    if (H == 64) GA_NARROW_LAUNCH_H(64, NS_ACT_TANH) else GA_NARROW_LAUNCH_H(32, NS_ACT_TANH)
+  } else {
+    if (H == 64) GA_NARROW_LAUNCH_H(64, NS_ACT_ANY) else GA_NARROW_LAUNCH_H(32, NS_ACT_ANY)
+  }
 #undef GA_NARROW_LAUNCH_H
 #undef GA_NARROW_LAUNCH
   GA_CHECK_LAUNCH("narrow_train");

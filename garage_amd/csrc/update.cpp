@@ -81,6 +81,15 @@ extern "C" int ga_set_narrow_wide(int on) {
   return was;
 }
 
+// The narrow step for hidden_act 1 .. 6 (the NS_ACT_ANY instantiations of narrow_body.h;
+// internal.h: ga_narrow_options_ok): off until asked for; returns the previous setting.
+extern "C" int ga_set_narrow_acts(int on) {
+  const int was = g_ga_narrow_acts;
+  g_ga_narrow_acts = on != 0;
+  return was;
+}
+extern "C" int ga_narrow_acts_on(void) { return g_ga_narrow_acts; }
+
 // The first layer's forward inside the fused last-hidden-layer kernel (3-layer
 // networks with <= 32 inputs); 0 = its own streaming launch (A/B runs, tests)
 // (GARAGE_AMD_FUSED_FIRST_LAYER=0 in the environment: the same, for A/B runs of
@@ -150,8 +159,9 @@ FusedPlan fused_plan(const ga_mlp_desc* d, int64_t M) {
   FusedPlan f;
   const int L = d->n_layers;
   if (L < 2 || L > 8 || M < 1) return f;
-  // the fused kernels implement tanh hidden layers and a linear output layer
-  if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return f;
+  // the fused kernels implement tanh hidden layers and a linear output layer (the narrow
+  // step any hidden activation, where asked for: ga_set_narrow_acts)
+  if (!ga_narrow_options_ok(d)) return f;
   if (g_narrow_step && ga_narrow_step_supported(L, d->dims) &&
       (ga_narrow_wide_on() || !ga_narrow_wide_supported(L, d->dims))) {
     f.ok = f.narrow = true;
@@ -163,6 +173,7 @@ FusedPlan fused_plan(const ga_mlp_desc* d, int64_t M) {
     f.floats = f.wpart_off;
     return f;
   }
+  if (d->hidden_act != 0) return f;
   if (!ga_fused_width_ok(d->dims[L - 1]) || d->dims[L] > 8) return f;
   f.ok = true;
   f.tiles = ga_fused_tiles(M);
@@ -325,6 +336,7 @@ void fused_step(const ga_update_args* a, const FusedPlan& f, int64_t k, int64_t 
   la.max_log_std = a->max_log_std; la.A = d->dims[L]; la.algo = a->algo; la.clip = a->clip;
   la.ent_coeff = a->ent_coeff; la.ent_flags = a->ent_flags;
   la.double_softmax = a->double_softmax;
+  la.hidden_act = d->hidden_act;
   s->lpart = reinterpret_cast<double*>(a->partials + f.lpart_off);
   s->hpart = a->partials + f.hpart_off;
   s->wpart = a->partials + f.wpart_off;

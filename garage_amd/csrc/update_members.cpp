@@ -46,8 +46,9 @@ int check_args(const ga_update_members_args* a) {
              "ga_update_epoch_members: n_members must be 1 .. %lld", (long long)MAX_MEMBERS);
   const ga_mlp_desc* d = a->desc;
   GA_REQUIRE(ga_update_members_supported(d),
-             "ga_update_epoch_members: unsupported network (two equal tanh hidden layers "
+             "ga_update_epoch_members: unsupported network (two equal %s hidden layers "
              "of 32 or 64 units, <= %d inputs, <= 8 linear outputs, no layer norm)",
+             g_ga_narrow_acts ? "tanh (or hidden_act 1 .. 6)" : "tanh",
              ga_narrow_wide_on() ? NS_IN_MAX : NS_IN_OVERLAY);
   GA_REQUIRE(a->kind >= 0 && a->kind <= 2, "ga_update_epoch_members: kind must be 0 .. 2");
   GA_REQUIRE(a->algo == 0 || a->algo == 1, "ga_update_epoch_members: algo must be 0 or 1");
@@ -101,7 +102,8 @@ int check_args(const ga_update_members_args* a) {
 
 extern "C" int ga_update_members_supported(const ga_mlp_desc* d) {
   if (!d || d->n_layers != 3) return 0;
-  if (d->hidden_act != 0 || d->output_act != 0 || d->layer_norm) return 0;
+  // (hidden_act 1 .. 6: where the caller has asked for them, ga_set_narrow_acts)
+  if (!ga_narrow_options_ok(d)) return 0;
   // (33 .. 128 inputs: where the caller has asked for them, ga_set_narrow_wide)
   if (ga_narrow_wide_supported(3, d->dims)) return ga_narrow_wide_on();
   return ga_narrow_overlay_supported(3, d->dims) ? 1 : 0;
@@ -147,6 +149,7 @@ extern "C" int ga_update_epoch_members(const ga_update_members_args* a,
   sh.double_softmax = a->double_softmax; sh.zero_slot0 = !a->learn_std;
   sh.stride = ga_narrow_step_stride(sh.in_w, sh.H);
   sh.mb = mb; sh.n_members = (int32_t)n;
+  sh.hact = d->hidden_act;
 
   // [n] members, then [n_steps][n] Adam constants
   const size_t table_bytes = (size_t)n * sizeof(GaMemberDev);

@@ -24,6 +24,19 @@ def require_gpu():
     return torch.device('cuda', torch.cuda.current_device())
 
 
+def set_narrow_activations(on):
+    """Process-wide flag (also ``GARAGE_AMD_NARROW_ACTS=1`` at import; off by
+    default): while set, ``VPG`` / ``PPO`` train narrow networks (two equal hidden
+    layers of 32 or 64 units, <= 128 inputs, <= 8 linear outputs) whose
+    ``hidden_nonlinearity`` is not tanh through the one-launch narrow step instead
+    of the per-layer kernels, and ``PopulationPPO`` takes members that share one
+    such nonlinearity.  ``PopulationTRPO``, ``joint_diagnostics`` and
+    ``joint_before`` stay tanh-only.  Returns the previous setting."""
+    was = _lib.NARROW_ACTS
+    _lib.NARROW_ACTS = bool(on)
+    return was
+
+
 _WS = {}
 
 

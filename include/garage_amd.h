@@ -1247,6 +1247,17 @@ GA_API int ga_set_narrow_step(int on);
  * GARAGE_AMD_NARROW_WIDE=0 in the environment (read once) keeps it 0 whatever is set.
  * Returns the previous setting. */
 GA_API int ga_set_narrow_wide(int on);
+/* Such networks with hidden layers that are not tanh (hidden_act 1 .. 6; output_act 0 and
+ * no layer normalisation as before): 0 (default) they take the per-layer kernels in
+ * ga_update_epoch* and ga_update_members_supported / ga_update_epoch_members refuse them,
+ * as ever; 1: the narrow step's generic-activation instantiations take them (also a
+ * minibatch of <= 64 rows, which for tanh is the small step's), and
+ * ga_update_epoch_members takes members that share one hidden_act.  The small step, the
+ * 64 / 128 / 256-wide fused kernels, ga_*_members_natural and the joint diagnostics stay
+ * tanh-only whatever is set.  ga_set_narrow_acts returns the previous setting,
+ * ga_narrow_acts_on the current one. */
+GA_API int ga_set_narrow_acts(int on);
+GA_API int ga_narrow_acts_on(void);
 /* Launches of the narrow step's instantiations for 33 .. 128 inputs since the library was
  * loaded, lone (ga_launch_count(11) counts the narrow step whichever instantiation takes
  * it) and of a population (ga_launch_count(15)). */

@@ -26,6 +26,12 @@ launches (reported as ``lone_per_layer_ms``), so that (b) against (c) is the lon
 default against its predecessor and (a) against (c) the population against lone updates
 without the wide step.
 
+``--hidden-nonlinearity NAME`` (relu, elu, leaky_relu, sigmoid, softplus, none): the
+members' networks use it instead of tanh.  (a) and (b) then run under
+``garage_amd.engine.set_narrow_activations(True)`` -- the narrow step's generic-activation
+instantiations -- and (c) is the lone update with the flag off: the per-layer launches,
+what such a learner takes by default (reported as ``lone_per_layer_ms``).
+
 A, B and C take turns inside one process; after warm-up every repeat is timed with HIP
 events around the update and the medians, their ratio and the run-to-run spread
 ((max - min) / median over the repeats) are printed, one JSON line per row.
@@ -48,7 +54,8 @@ if ROOT not in sys.path:
 ENVS, STEPS, EPOCHS = 64, 128, 10
 
 
-def make_members(M, minibatch, linear=None, obs_dim=None, solver='host'):
+def make_members(M, minibatch, linear=None, obs_dim=None, solver='host',
+                 hidden='tanh'):
     """``obs_dim``: None -- CartPole; D -- synthetic D-wide observations.
     ``linear``: None -- MLP(64, 64) value functions; 'joint' -- the members of
     one LinearFeatureBaselinePopulation; 'lone' -- lone LinearFeatureBaselines."""
@@ -66,12 +73,14 @@ def make_members(M, minibatch, linear=None, obs_dim=None, solver='host'):
     joint = LinearFeatureBaselinePopulation(env.spec, M, solver=solver) \
         if linear == 'joint' else None
     members = []
+    net_kw = dict(hidden_sizes=(64, 64),
+                  hidden_nonlinearity=None if hidden == 'none' else hidden)
     for m in range(M):
         torch.manual_seed(100 + m)
-        pol = CategoricalMLPPolicy(env.spec, hidden_sizes=(64, 64))
+        pol = CategoricalMLPPolicy(env.spec, **net_kw)
         opt = (torch.optim.Adam, dict(lr=2.5e-4 * (1 + m % 4)))
         if linear is None:
-            vf = GaussianMLPValueFunction(env.spec, hidden_sizes=(64, 64))
+            vf = GaussianMLPValueFunction(env.spec, **net_kw)
             vf_opt = OptimizerWrapper(opt, vf, EPOCHS, minibatch,
                                       permutation='device', seed=1000 + m)
         else:
@@ -97,18 +106,26 @@ def timed(fn):
     return start.elapsed_time(stop)
 
 
-def measure(M, minibatch, repeats, warmup, linear=False, obs_dim=None):
-    from garage_amd import _lib
+def measure(M, minibatch, repeats, warmup, linear=False, obs_dim=None, hidden=None):
+    from garage_amd import _lib, engine
     from garage_amd.algos import PopulationPPO
     from garage_amd.sampler import GpuPopulationSampler
     lib = _lib.load()
-    env, members = make_members(M, minibatch, 'joint' if linear else None, obs_dim)
-    _, lones = make_members(M, minibatch, 'lone' if linear else None, obs_dim)
-    _, narrows = make_members(M, minibatch, 'lone' if linear else None, obs_dim)
-    # (c): the lone narrow path up to 32 inputs, the per-layer path above
+    fn = hidden or 'tanh'
+    env, members = make_members(M, minibatch, 'joint' if linear else None, obs_dim,
+                                hidden=fn)
+    _, lones = make_members(M, minibatch, 'lone' if linear else None, obs_dim, hidden=fn)
+    _, narrows = make_members(M, minibatch, 'lone' if linear else None, obs_dim,
+                              hidden=fn)
+    if hidden is not None:
+        engine.set_narrow_activations(True)
+    # (c): the lone narrow path up to 32 inputs, the per-layer path above (and for
+    # another nonlinearity than tanh)
     wide = obs_dim is not None and obs_dim > 32
     def switch_c(on):
-        if wide:
+        if hidden is not None:
+            engine.set_narrow_activations(bool(on))
+        elif wide:
             _lib.NARROW_WIDE = bool(on)
         else:
             lib.ga_set_small_step(on)
@@ -149,7 +166,7 @@ def measure(M, minibatch, repeats, warmup, linear=False, obs_dim=None):
     def spread(t):
         return float((t.max() - t.min()) / np.median(t))
 
-    c_name = 'lone_per_layer' if wide else 'lone_narrow'
+    c_name = 'lone_per_layer' if wide or hidden is not None else 'lone_narrow'
     row = dict(
         members=M, minibatch=minibatch, linear_baseline=bool(linear),
         samples_per_member=[int(c.S) for c in joint][:4],
@@ -160,6 +177,11 @@ def measure(M, minibatch, repeats, warmup, linear=False, obs_dim=None):
     row[c_name + '_ms'] = float(np.median(tc))
     row[c_name + '_over_population'] = float(np.median(tc) / np.median(ta))
     row[c_name + '_spread'] = spread(tc)
+    for name, t in (('population', ta), ('lone', tb), (c_name, tc)):
+        row[name + '_min_max_ms'] = [float(t.min()), float(t.max())]
+    if hidden is not None:
+        row['hidden_nonlinearity'] = hidden
+        engine.set_narrow_activations(False)
     if obs_dim is not None:
         row['obs_dim'] = obs_dim
         row[c_name + '_over_lone'] = float(np.median(tc) / np.median(tb))
@@ -181,6 +203,11 @@ def main():
     ap.add_argument('--obs-dim', type=int, default=None,
                     help='synthetic observations of this width instead of CartPole; '
                          'above 32, (c) is the per-layer path (_lib.NARROW_WIDE off)')
+    ap.add_argument('--hidden-nonlinearity', default=None,
+                    choices=['relu', 'elu', 'leaky_relu', 'sigmoid', 'softplus', 'none'],
+                    help='the networks\' hidden nonlinearity instead of tanh: (a) and '
+                         '(b) under set_narrow_activations(True), (c) the per-layer '
+                         'path with the flag off')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('population_update_rate needs an MI355X: there is nothing '
@@ -190,7 +217,8 @@ def main():
     for minibatch in args.minibatches:
         for M in args.members:
             print(json.dumps(measure(M, minibatch, args.repeats, args.warmup,
-                                     args.linear_baseline, args.obs_dim)),
+                                     args.linear_baseline, args.obs_dim,
+                                     args.hidden_nonlinearity)),
                   flush=True)
 
 
